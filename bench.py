@@ -13,6 +13,7 @@ Inputs are resident in HBM before the timed region.
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          # no launcher around it: starts the line above as a CHILD process (before this process has
                                           # touched HIP), relays rank 0's JSON line, exits non-zero with the child's stderr tail on failure
+    python bench.py --dump-outputs DIR    # also write rank 0's graph outputs of the last timed step to DIR/<name>.npy (float32)
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md §4 for the fields).
 """
@@ -29,6 +30,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s measured copy)
 SEMITONES = 3.0
 BINS = 513
+DUMP_BYTES = 60 << 20          # --dump-outputs: all arrays together (under 64 MB, decimal, with the .npy headers)
+DUMP_WINDOW = 1 << 14          # elements per sampled window of an output larger than its share
 # vector issue: cycles per wave64 f32 instruction per SIMD (add/sub/mul/fma mix), measured by WALL CLOCK and by SQ counters
 # (tools/ubench/valu_wallclock.hip -> profiles/r05_valu_wallclock.md): 4.6 for a lone wave, 2.15-2.2 for two or more waves per SIMD
 # (= the chip guide's 2 cycles per wave64 instruction on a SIMD-32; v_fma_f32 130 TFLOP/s at the 2.13 GHz held under that load).
@@ -57,7 +60,36 @@ def parse(argv=None):
     ap.add_argument("--no-host-path", action="store_true", help="skip the plugin-boundary measurement (host_path)")
     ap.add_argument("--dry-run", action="store_true", help="rehearsal of the N > 1 plumbing on CPU (gloo): launcher, rendezvous, sharding, the broadcast, "
                                                            "the rank reports and the one JSON line — no GPU work, `value` null (tests/test_shard_gloo.py)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed on rank 0 (mix, pitch and spectrum outputs) as DIR/<name>.npy, "
+                         f"float32, at most {DUMP_BYTES >> 20} MiB in all: an output too large for its share is a fixed, seeded sample of windows")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.dry_run:
+        ap.error("--dump-outputs needs the GPU run (no --dry-run)")
+    return a
+
+
+def dump_sample(ctx, outputs, budget=DUMP_BYTES, window=DUMP_WINDOW, seed=0):
+    """Host copies of device float32 outputs {name: (ptr, shape)} within `budget` bytes, an equal share each.  An output that fits its
+    share comes whole, in its own shape; a larger one as (n, window): the windows at a sorted, seeded choice of window-aligned offsets,
+    the same choice for the same shape on every run."""
+    import numpy as np
+    share = budget // len(outputs) // 4
+    host = {}
+    for name, (ptr, shape) in outputs.items():
+        n = int(np.prod(shape))
+        if n <= share:
+            host[name] = np.empty(shape, np.float32)
+            ctx._ck(ctx.lib.nae_memcpy_d2h(ctx.h, host[name].ctypes.data, ptr, n * 4))
+            continue
+        picks = np.sort(np.random.default_rng(seed).choice(n // window, share // window, replace=False))
+        host[name] = np.empty((picks.size, window), np.float32)
+        for row, w in zip(host[name], picks):
+            ctx._ck(ctx.lib.nae_memcpy_d2h(ctx.h, row.ctypes.data, ptr + int(w) * window * 4, window * 4))
+    ctx.sync()                                           # the copies are queued on the context's stream
+    return host
 
 
 def usable_cores():
@@ -273,6 +305,11 @@ def main():
     if not a.no_kernel_timing:
         ctx.prof_enable(False)
         kernels = ctx.prof_report()
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # before anything below runs the graph (or the WSOLA pitch node into d_pitch) again
+        dumped = dump_sample(ctx, {"mix_out": (d_mix.ptr, (n_streams, 2, S)), "pitch_out": (d_pitch.ptr, (n_streams, pl.out_len, 2)),
+                                   "spectrum_out": (d_spec.ptr, (n_streams, F, 2, BINS))})
     sustained = None
     if a.sustain_seconds > 0:
         # the same step back to back for at least --sustain-seconds (clock and power settled), no per-kernel events
@@ -515,6 +552,11 @@ def main():
         ctx.sync()
         rr = lambda x, y: float(np.sqrt(np.mean((x.astype(np.float64) - y) ** 2)) / np.sqrt(np.mean(y.astype(np.float64) ** 2)))
         out["rms_err_vs_oracle"] = {"pitch_out": rr(gp, refs[0]), "spectrum_out": rr(gs, refs[1].reshape(-1)), "tolerance": 1e-4}
+    if dumped is not None:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
+        out["dumped_outputs"] = {name: list(arr.shape) for name, arr in dumped.items()}
     sys.stdout.flush()
     os.dup2(real_stdout, 1)
     print(json.dumps(out))

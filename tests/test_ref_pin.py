@@ -14,8 +14,15 @@ test pins both facts, so "bit-exact int-PCM gain" is a statement about in-range 
 Every other loop of the path sits inside a process_payload body between FFmpeg / Boost calls: as FUNCTIONS they cannot be compiled
 without stand-ins for headers this image lacks (DESIGN.md §5).  For K3 / K4 / K5 the arithmetic statements alone are compiled (below);
 K6's two packed-integer conversions are one-line lambdas and are compiled as they stand (last test); K2 (pure data movement) and K6's
-planar branches (their statements read AVFrame fields) stay pinned by the numpy restatement only."""
+planar branches (their statements read AVFrame fields) stay pinned by the numpy restatement only.
+
+The reference is not part of this repository, so every test also stands without it: tests/golden/ref_pin.json records, per build and
+per input, a digest of what the reference's code returned (the outputs themselves are several MB) and the boundary text read from its
+sources.  Where oracle/_ref or the reference is present the code runs live and must still match the record; elsewhere the record stands
+in for it, and the oracle and the mirror are held to it bit for bit either way.  NAE_REF_PIN_RECORD=1 (reference present) rewrites it."""
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
@@ -28,27 +35,79 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
 REF_SRC = "/root/reference/src/processor/audio-vol.cpp"
 BUILDS = {"g++": "libref_vol.so", "clang": "libref_vol_clang.so"}
+PIN_FILE = os.path.join(ROOT, "tests", "golden", "ref_pin.json")
+RECORD = os.environ.get("NAE_REF_PIN_RECORD") == "1"
+with open(PIN_FILE, encoding="utf-8") as _f:
+    _PINS = json.load(_f)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _write_record():
+    yield
+    if RECORD:
+        with open(PIN_FILE, "w", encoding="utf-8") as f:
+            json.dump(_PINS, f, indent=1, sort_keys=True)
+            f.write("\n")
+
+
+def pinned(section, name, live=None):
+    """what the reference gives for `name`: live() where the reference is present (checked against the record, or recorded), else
+    the record"""
+    if live is None:
+        assert not RECORD, "NAE_REF_PIN_RECORD=1 needs the reference (or oracle/_ref built from it)"
+        assert name in _PINS[section], f"{section} / {name} is not in tests/golden/ref_pin.json"
+        return _PINS[section][name]
+    got = json.loads(json.dumps(live()))
+    if RECORD:
+        _PINS.setdefault(section, {})[name] = got
+    else:
+        assert got == _PINS[section][name], (section, name, "the reference differs from its record in tests/golden/ref_pin.json")
+    return got
+
+
+def digest(*arrays):
+    """dtype and bytes of the arrays, in order"""
+    h = hashlib.blake2b(digest_size=16)
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(a.dtype.str.encode())
+        h.update(a.view(np.uint8).tobytes())
+    return h.hexdigest()
+
+
+class Ref:
+    """one build of the reference's code: the library under oracle/_ref, or None where it cannot be built (then its record answers)"""
+
+    def __init__(self, which, lib):
+        self.which, self.lib = which, lib
+
+    def out(self, name, run):
+        """digest of the arrays run(lib) returns"""
+        return pinned(self.which, name, (lambda: digest(*run(self.lib))) if self.lib is not None else None)
+
+
+def load_lib(which, builds):
+    so = os.path.join(REF_DIR, builds[which])
+    if not os.path.exists(so):
+        if not os.path.exists(REF_SRC):
+            return None
+        r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout + r.stderr
+    return C.CDLL(so)
 
 
 def load_ref(which):
-    so = os.path.join(REF_DIR, BUILDS[which])
-    if not os.path.exists(so):
-        if not os.path.exists(REF_SRC):
-            pytest.skip("oracle/_ref was not built and /root/reference is not on this box")
-        r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
-    L = C.CDLL(so)
-    for n in ("ref_change_volume_f32", "ref_change_volume_s16", "ref_change_volume_s32"):
-        getattr(L, n).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
-        getattr(L, n).restype = None
-    return L
+    L = load_lib(which, BUILDS)
+    if L is not None:
+        for n in ("ref_change_volume_f32", "ref_change_volume_s16", "ref_change_volume_s32"):
+            getattr(L, n).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
+            getattr(L, n).restype = None
+    return Ref(which, L)
 
 
 @pytest.fixture(scope="module", params=["g++", "clang"])
 def ref(request):
-    L = load_ref(request.param)
-    L.which = request.param
-    return L
+    return load_ref(request.param)
 
 
 def in_range(x, v):
@@ -78,10 +137,6 @@ def ref_change_volume(L, planes, volume):
     return dst
 
 
-def same_bits(a, b):
-    return a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
 @pytest.mark.parametrize("key,vols", [("k1_f32", (0.0, 0.70710678, 1.0, 10.0)), ("k1_s16", (0.5, 0.70710678, 1.0, 3.0, 10.0)),
                                       ("k1_s32", (0.5, 0.70710678, 1.0, 3.0))])
 def test_reference_code_reproduces_the_committed_golden(ref, golden, key, vols):
@@ -90,12 +145,13 @@ def test_reference_code_reproduces_the_committed_golden(ref, golden, key, vols):
     g = golden["nodes"]
     x = g[key + "_in"]
     for v in vols:
-        r = ref_change_volume(ref, [x], v)[0]
         o = orc.change_volume([x], v)[0]
         m = in_range(x, v) if ref.which == "clang" else np.ones(x.shape, bool)
         assert m.sum() > 500
-        assert np.array_equal(r[m].view(np.uint8), o[m].view(np.uint8)), (key, v, "oracle differs from the reference's code")
-        assert np.array_equal(r[m].view(np.uint8), g[f"{key}_v{v}"][m].view(np.uint8)), (key, v, "golden differs from the reference's code")
+        r = ref.out(f"k1_golden/{key}/v{v}", lambda L: [ref_change_volume(L, [x], v)[0][m]])
+        assert r == digest(o[m]), (key, v, "oracle differs from the reference's code")
+        # (r == o[m] above, so this is the reference's code against the golden)
+        assert np.array_equal(o[m].view(np.uint8), g[f"{key}_v{v}"][m].view(np.uint8)), (key, v, "golden differs from the reference's code")
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.int16, np.int32])
@@ -110,10 +166,9 @@ def test_oracle_equals_reference_code_on_random_frames(ref, dtype, planes, elems
             # in range for every volume used here: the reference's float -> int conversion is only defined there
             lim = int(np.iinfo(dtype).max / 10.5)
             src = [rng.integers(-lim, lim, elems, dtype=np.int64).astype(dtype) for _ in range(planes)]
-        r = ref_change_volume(ref, src, v)
+        r = ref.out(f"k1_frames/{np.dtype(dtype).name}/{planes}x{elems}/v{v}", lambda L: ref_change_volume(L, src, v))
         o = orc.change_volume(src, v)
-        for a, b in zip(r, o):
-            assert same_bits(a, b), (dtype, planes, elems, v)
+        assert r == digest(*o), (dtype, planes, elems, v)
 
 
 @pytest.mark.parametrize("dtype", [np.int16, np.int32])
@@ -127,16 +182,18 @@ def test_out_of_range_integer_products(dtype):
     rng = np.random.default_rng(7)
     x = rng.integers(info.min, info.max, 4099, dtype=np.int64, endpoint=True).astype(dtype)
     x[:4] = [info.min, info.max, info.min + 1, info.max - 1]
+    name = np.dtype(dtype).name
     for v in (1.0000001, 2.0, 3.0, 10.0):
         o = orc.change_volume([x], v)[0]
-        r = ref_change_volume(gxx, [x], v)[0]
-        assert same_bits(r, o), (dtype, v, int(np.count_nonzero(r != o)))
-        c = ref_change_volume(clang, [x], v)[0]
+        r = gxx.out(f"k1_out_of_range/{name}/v{v}", lambda L: [ref_change_volume(L, [x], v)[0]])
+        assert r == digest(o), (dtype, v)
         m = in_range(x, v)
         assert 0 < m.sum() and (v < 2.0 or m.sum() < x.size)
-        assert np.array_equal(c[m], o[m]), (dtype, v)
+        c = clang.out(f"k1_out_of_range/{name}/v{v}/in_range", lambda L: [ref_change_volume(L, [x], v)[0][m]])
+        assert c == digest(o[m]), (dtype, v)
         if dtype == np.int16 and v >= 2.0:
-            assert not np.array_equal(c, o)                      # compilers disagree where the reference leaves the result undefined
+            # compilers disagree where the reference leaves the result undefined
+            assert clang.out(f"k1_out_of_range/{name}/v{v}", lambda L: [ref_change_volume(L, [x], v)[0]]) != digest(o)
 
 
 # ---------------------------------------------------------------------------------------------- K3 / K4 / K5: arithmetic statements
@@ -149,19 +206,14 @@ MIX_BUILDS = {"g++": "libref_mix.so", "clang": "libref_mix_clang.so"}
 
 @pytest.fixture(scope="module", params=["g++", "clang"])
 def refmix(request):
-    so = os.path.join(REF_DIR, MIX_BUILDS[request.param])
-    if not os.path.exists(so):
-        if not os.path.exists(REF_SRC):
-            pytest.skip("oracle/_ref was not built and /root/reference is not on this box")
-        r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
-    L = C.CDLL(so)
-    L.ref_amix_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    L.ref_bimix_f32.argtypes = [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.ref_bimix2_downmix_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    for f in (L.ref_amix_f32, L.ref_bimix_f32, L.ref_bimix2_downmix_f32):
-        f.restype = None
-    return L
+    L = load_lib(request.param, MIX_BUILDS)
+    if L is not None:
+        L.ref_amix_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.ref_bimix_f32.argtypes = [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.ref_bimix2_downmix_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        for f in (L.ref_amix_f32, L.ref_bimix_f32, L.ref_bimix2_downmix_f32):
+            f.restype = None
+    return Ref(request.param, L)
 
 
 def special(n, seed):
@@ -180,12 +232,15 @@ def test_k3_mix_statements_of_the_reference(refmix, n_in):
     inR = [orc.fill_uniform(S, 100 + 10 * n_in + i) for i in range(n_in)]
     vol = rng.uniform(0, 1, n_in).astype(np.float32)
     oL, oR = orc.amix(inL, inR, vol)
-    # datas[i] = {left plane, right plane} as uint8_t** (what swr_convert fills, audio-amix.cpp:251-269)
-    pairs = [(C.c_void_p * 2)(inL[i].ctypes.data, inR[i].ctypes.data) for i in range(n_in)]
-    datas = (C.c_void_p * n_in)(*[C.addressof(p) for p in pairs])
-    rL, rR = np.empty(S, np.float32), np.empty(S, np.float32)
-    refmix.ref_amix_f32(datas, vol.ctypes.data, n_in, rL.ctypes.data, rR.ctypes.data, S)
-    assert same_bits(rL, oL) and same_bits(rR, oR)
+
+    def run(L):
+        # datas[i] = {left plane, right plane} as uint8_t** (what swr_convert fills, audio-amix.cpp:251-269)
+        pairs = [(C.c_void_p * 2)(inL[i].ctypes.data, inR[i].ctypes.data) for i in range(n_in)]
+        datas = (C.c_void_p * n_in)(*[C.addressof(p) for p in pairs])
+        rL, rR = np.empty(S, np.float32), np.empty(S, np.float32)
+        L.ref_amix_f32(datas, vol.ctypes.data, n_in, rL.ctypes.data, rR.ctypes.data, S)
+        return [rL, rR]
+    assert refmix.out(f"k3_amix/{n_in}", run) == digest(oL, oR)
 
 
 @pytest.mark.parametrize("bias", [-1.0, -0.3, 0.0, 0.25, 1.0])
@@ -193,44 +248,54 @@ def test_k4_bimix_statements_of_the_reference(refmix, bias):
     S = 4099
     a = [special(S, 21), orc.fill_uniform(S, 22), orc.fill_uniform(S, 23), special(S, 24)]
     oL, oR = orc.bimix(*a, bias)
-    rL, rR = np.empty(S, np.float32), np.empty(S, np.float32)
-    refmix.ref_bimix_f32(*[x.ctypes.data for x in a], C.c_float(bias), rL.ctypes.data, rR.ctypes.data, S)
-    assert same_bits(rL, oL) and same_bits(rR, oR)
+
+    def run(L):
+        rL, rR = np.empty(S, np.float32), np.empty(S, np.float32)
+        L.ref_bimix_f32(*[x.ctypes.data for x in a], C.c_float(bias), rL.ctypes.data, rR.ctypes.data, S)
+        return [rL, rR]
+    assert refmix.out(f"k4_bimix/{bias}", run) == digest(oL, oR)
 
 
 def test_k5_downmix_statement_of_the_reference(refmix):
     S = 4099
     l, r = special(S, 31), special(S, 32)[::-1].copy()
     m = orc.bimix2_downmix(l, r)
-    ref = np.empty(S, np.float32)
-    refmix.ref_bimix2_downmix_f32(l.ctypes.data, r.ctypes.data, ref.ctypes.data, S)
-    assert same_bits(ref, m)          # incl. the subnormal halving: (l + r) * 0.5 is a DOUBLE product rounded once
+
+    def run(L):
+        ref = np.empty(S, np.float32)
+        L.ref_bimix2_downmix_f32(l.ctypes.data, r.ctypes.data, ref.ctypes.data, S)
+        return [ref]
+    assert refmix.out("k5_downmix", run) == digest(m)          # incl. the subnormal halving: (l + r) * 0.5 is a DOUBLE product rounded once
 
 
 @pytest.mark.parametrize("earlier_channel", [0, 1])
 def test_k5_interleave_loops_of_the_reference(refmix, earlier_channel):
     """audio-bimix.cpp:799-803 (single-sided frame) and :836-850 (unaligned + aligned frame), loops and headers as they stand"""
-    refmix.ref_bimix2_interleave_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
-    refmix.ref_bimix2_interleave_f32.restype = None
+    if refmix.lib is not None:
+        refmix.lib.ref_bimix2_interleave_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+        refmix.lib.ref_bimix2_interleave_f32.restype = None
     e, l = special(3000, 41), special(2500, 42)
     for unaligned, aligned in ((0, 2500), (123, 2500), (500, 2000), (2999, 1), (3000, 0), (0, 0)):
         want = orc.bimix2_interleave(e, l, unaligned, aligned, earlier_channel)
-        got = np.empty(2 * (unaligned + aligned), np.float32)
-        refmix.ref_bimix2_interleave_f32(got.ctypes.data, e.ctypes.data, e.size, l.ctypes.data, l.size, unaligned, aligned, earlier_channel)
-        assert same_bits(got, want), (unaligned, aligned)
+
+        def run(L):
+            got = np.empty(2 * (unaligned + aligned), np.float32)
+            L.ref_bimix2_interleave_f32(got.ctypes.data, e.ctypes.data, e.size, l.ctypes.data, l.size, unaligned, aligned, earlier_channel)
+            return [got]
+        assert refmix.out(f"k5_interleave/{earlier_channel}/{unaligned}+{aligned}", run) == digest(want), (unaligned, aligned)
     want = orc.bimix2_interleave(e, None, e.size, 0, earlier_channel)
-    got = np.empty(2 * e.size, np.float32)
-    refmix.ref_bimix2_interleave_f32(got.ctypes.data, e.ctypes.data, e.size, None, 0, 0, 0, earlier_channel)
-    assert same_bits(got, want)
+
+    def run_single(L):
+        got = np.empty(2 * e.size, np.float32)
+        L.ref_bimix2_interleave_f32(got.ctypes.data, e.ctypes.data, e.size, None, 0, 0, 0, earlier_channel)
+        return [got]
+    assert refmix.out(f"k5_interleave/{earlier_channel}/single_sided", run_single) == digest(want)
 
 
 @pytest.mark.parametrize("dtype,fn,fmt", [(np.int16, "ref_k6_s16_packed", orc.FMT_S16), (np.int32, "ref_k6_s32_packed", orc.FMT_S32)])
 def test_k6_packed_integer_lambdas_of_the_reference(refmix, dtype, fn, fmt):
     """audio-velocity.cpp:186 (S16 / 32768.0f) and :207 (S32 / 2147483648.0f): the lambdas as they stand, over every int16 value and
     over random + extreme int32 values"""
-    f = getattr(refmix, fn)
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    f.restype = None
     info = np.iinfo(dtype)
     if dtype == np.int16:
         x = np.arange(info.min, info.max + 1, dtype=np.int64).astype(dtype)
@@ -240,16 +305,23 @@ def test_k6_packed_integer_lambdas_of_the_reference(refmix, dtype, fn, fmt):
         x[:6] = [info.min, info.max, 0, -1, 1, info.min + 1]
     if x.size % 2:
         x = x[:-1]
-    got = np.empty(x.size, np.float32)
-    f(x.ctypes.data, got.ctypes.data, x.size)
+
+    def run(L):
+        f = getattr(L, fn)
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        f.restype = None
+        got = np.empty(x.size, np.float32)
+        f(x.ctypes.data, got.ctypes.data, x.size)
+        return [got]
     rc, want = orc.to_f32_interleaved(fmt, [x], x.size // 2, 2)      # packed stereo: one plane of S * 2 samples
-    assert rc == 0 and same_bits(got, want)
+    assert rc == 0 and refmix.out(f"k6/{fn}", run) == digest(want)
 
 
 def test_k3_weight_renormalisation_of_the_reference(refmix):
     """audio-amix.cpp:379-387: the unlocked weights are scaled to sum 1 (floor 0.001); loops with their headers"""
-    refmix.ref_amix_normalise.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    refmix.ref_amix_normalise.restype = None
+    if refmix.lib is not None:
+        refmix.lib.ref_amix_normalise.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        refmix.lib.ref_amix_normalise.restype = None
     rng = np.random.default_rng(9)
     for n in (1, 2, 5, 16):
         for trial in range(20):
@@ -260,15 +332,18 @@ def test_k3_weight_renormalisation_of_the_reference(refmix):
             if trial == 1:
                 locks[:] = 1                              # nothing unlocked
             want = orc.amix_normalise(v, locks)
-            got = v.copy()
-            refmix.ref_amix_normalise(got.ctypes.data, locks.ctypes.data, n)
-            assert same_bits(got, want), (n, trial)
+
+            def run(L):
+                got = v.copy()
+                L.ref_amix_normalise(got.ctypes.data, locks.ctypes.data, n)
+                return [got]
+            assert refmix.out(f"k3_normalise/{n}/{trial}", run) == digest(want), (n, trial)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
 # The boundary's TEXT: the plugin ABC's pure-virtual list and every processor's identifier, display name, singleton flag,
-# pins and JSON keys, read out of the reference's sources as text (build container only) and compared with what the C++ host mirror's
-# registry holds (`tests/host/selftest registry` prints it from default-constructed nodes).  A renamed pin, a missing override, a dropped
+# pins and JSON keys, read out of the reference's sources as text (or their record where the sources are absent) and compared with what
+# the C++ host mirror's registry holds (`tests/host/selftest registry` prints it from default-constructed nodes).  A renamed pin, a missing override, a dropped
 # JSON key or another identifier fails here.
 REF_ROOT = "/root/reference"
 HOST_DIR = os.path.join(ROOT, "nodey-audio-editor_amd", "host")
@@ -282,9 +357,10 @@ REF_CLASSES = {      # class -> (source file, header) of the reference
 }
 
 
-def _need_reference():
-    if not os.path.exists(os.path.join(REF_ROOT, "include", "infra", "processor.hpp")):
-        pytest.skip("/root/reference is not on this box (the boundary text is pinned in the build container)")
+def _from_reference(name, read):
+    """boundary fact `name`: read() from the reference's sources where they are present, else its record"""
+    present = os.path.exists(os.path.join(REF_ROOT, "include", "infra", "processor.hpp"))
+    return pinned("boundary", name, read if present else None)
 
 
 def _strip_comments(text):
@@ -334,6 +410,10 @@ def _dedupe(seq):
 
 
 def _reference_boundary(cls):
+    return _from_reference(cls, lambda: _read_reference_boundary(cls))
+
+
+def _read_reference_boundary(cls):
     import re
     src_path, hdr_path = REF_CLASSES[cls]
     src = _strip_comments(open(os.path.join(REF_ROOT, src_path), encoding="utf-8").read())
@@ -375,8 +455,8 @@ def test_boundary_pure_virtuals_equal_the_reference_abc():
     """infra::Processor of the mirror declares exactly the reference's pure virtuals (include/infra/processor.hpp:86-113) — draw_title and
     draw_content among them — and `selftest registry` instantiates every registered class through Info::generate, which compiles only if
     the class overrides all of them: the adapters are concrete against the real ABC."""
-    _need_reference()
-    ref = _pure_virtuals(open(os.path.join(REF_ROOT, "include", "infra", "processor.hpp"), encoding="utf-8").read())
+    ref = _from_reference("processor.hpp pure virtuals",
+                          lambda: _pure_virtuals(open(os.path.join(REF_ROOT, "include", "infra", "processor.hpp"), encoding="utf-8").read()))
     mine = _pure_virtuals(open(os.path.join(HOST_DIR, "infra", "processor.hpp"), encoding="utf-8").read())
     assert ref == ["deserialize", "draw_content", "draw_title", "get_pin_attributes", "get_processor_info_non_static", "process_payload", "serialize"], ref
     assert mine == ref
@@ -399,7 +479,6 @@ def test_boundary_pure_virtuals_equal_the_reference_abc():
 def test_boundary_text_of_every_processor_equals_the_reference(cls):
     """identifier, display name, singleton flag, pin identifiers / directions / product type and serialize() keys of one processor class:
     the reference's source text against the mirror's registry (SURVEY.md §8b "Identifiers / pins / JSON keys")."""
-    _need_reference()
     ref = _reference_boundary(cls)
     reg = _mirror_registry()
     assert ref["identifier"] in reg, f"{cls}: identifier {ref['identifier']} is not registered by the mirror"
@@ -415,10 +494,12 @@ def test_boundary_text_of_every_processor_equals_the_reference(cls):
 def test_boundary_register_list_covers_the_reference_hot_path_nodes():
     """src/register.cpp:16-23 registers eight classes; the six on the hot path are replaced under their identifiers, audio_input / audio_output
     (codecs, device I/O: out of scope) stay the reference's, audio_spectrum is new"""
-    _need_reference()
     import re
-    text = _strip_comments(open(os.path.join(REF_ROOT, "src", "register.cpp"), encoding="utf-8").read())
-    registered = re.findall(r"register_processor<\s*(?:processor::)?(\w+)\s*>", text)
+
+    def read():
+        text = _strip_comments(open(os.path.join(REF_ROOT, "src", "register.cpp"), encoding="utf-8").read())
+        return re.findall(r"register_processor<\s*(?:processor::)?(\w+)\s*>", text)
+    registered = _from_reference("register.cpp classes", read)
     assert sorted(registered) == sorted(list(REF_CLASSES) + ["Audio_input", "Audio_output"]), registered
     reg = _mirror_registry()
     assert sorted(reg) == sorted([_reference_boundary(c)["identifier"] for c in REF_CLASSES] + ["audio_spectrum"])
