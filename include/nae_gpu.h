@@ -31,7 +31,9 @@ extern "C" {
  * process-wide latch; now a context may sit on any device, and an index outside [0, nae_device_count()) is NAE_ERR_INVALID.
  * A caller built against 1 keeps working (nothing was removed or re-typed); a caller that needs the additions checks
  * nae_abi_version() >= 2.
- * 3 (round 6): addition — nae_debug_set (the tuning / A-B switches, formerly 14 environment variables read at context creation). */
+ * 3 (round 6): addition — nae_debug_set (the tuning / A-B switches, formerly 14 environment variables read at context creation).
+ *   Later additions within 3 (the version number did not move; a caller probes for them by symbol, e.g. dlsym): nae_spectrum_frames_ex
+ *   and nae_spectrum_block_ex_f32 (spectrum sizes 256 ... 4096, any hop); nae_spectrum_create accepts those sizes and hops. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -125,6 +127,8 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *   rs_single, rs_direct, no_mix_fuse      1: transposer with one stream per workgroup / the direct (unstaged) kernel / mix and transposer as two launches
  *   spec_generic, spec_narrow              1: skip the interleaved-stereo spectrum kernel / its dword stores instead of 16-byte ones
  *   spec_chunk, spec_fine, spec_fine_rounds   frames per chunk of the stereo spectrum kernel / of the short chunks at a launch's end / how many of those per wave
+ *   spec_any        1: 1024-point spectrum launches (nae_spectrum_block_f32, _ex at 1024 / 256, the graph's spectrum node) run the size-generic
+ *                   kernel instead of the 1024-point ones (same results, bit for bit)
  *   td_nc           1 | 2 | 4: candidates per thread of the WSOLA search;  st_unfused  1: filter and cubic stage of the WSOLA chain as two launches
  * The same assignments, comma separated, in the environment variable NAE_DEBUG ("pv_flow=2,pv_fps=4") are applied when a context is created
  * (for measuring a program that creates its contexts itself, e.g. bench.py); an unknown key there fails nae_ctx_create with NAE_ERR_INVALID. */
@@ -314,7 +318,15 @@ int nae_mono_to_stereo_f32(nae_ctx* ctx, const float* mono, float* dst_interleav
 size_t nae_spectrum_frames(size_t T);
 int nae_spectrum_block_f32(nae_ctx* ctx, const nae_sig* src, size_t T, int ch, size_t n_streams, float* dst,
                            size_t dst_stream_stride);
-/* streaming handle: put interleaved samples, receive whole frames [ch][513] */
+/* Any size: n_fft a power of two in [256, 4096] (else NAE_ERR_UNSUPPORTED), 1 <= hop <= n_fft (else NAE_ERR_INVALID).  Frame f starts at
+ * f*hop; frames = T < n_fft ? 0 : (T-n_fft)/hop + 1; per channel periodic Hann_N, un-normalised r2c DFT, |X[k]| for k = 0..n_fft/2
+ * (canonical FFT of DESIGN.md §3: bit-exact against its CPU restatement, and at 1024 the bits of nae_spectrum_block_f32).
+ * dst element (s, frame f, channel c, bin k) at dst_base[s*dst_stream_stride + (f*ch + c)*(n_fft/2 + 1) + k].
+ * nae_spectrum_frames_ex returns 0 for parameters that are not supported.  1024 / 256 runs nae_spectrum_block_f32. */
+size_t nae_spectrum_frames_ex(size_t T, int n_fft, int hop);
+int nae_spectrum_block_ex_f32(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, size_t T, int ch, size_t n_streams, float* dst,
+                              size_t dst_stream_stride);
+/* streaming handle: put interleaved samples, receive whole frames [ch][n_fft/2 + 1]; the sizes and hops of _ex */
 int nae_spectrum_create(nae_ctx* ctx, int n_fft, int hop, int channels, nae_spectrum** h);
 int nae_spectrum_put(nae_spectrum* h, const float* interleaved, size_t S);
 size_t nae_spectrum_available(nae_spectrum* h);                         /* whole frames ready */

@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = [
     "nae_debug_pv_tile_phase", "nae_stretch_create", "nae_stretch_put", "nae_stretch_put_host", "nae_stretch_flush",
     "nae_stretch_available", "nae_stretch_receive", "nae_stretch_receive_host", "nae_stretch_destroy",
     "nae_swr_create", "nae_swr_convert_host", "nae_swr_convert", "nae_swr_buffered", "nae_swr_destroy", "nae_mono_to_stereo_f32",
-    "nae_spectrum_frames", "nae_spectrum_block_f32", "nae_spectrum_create", "nae_spectrum_put",
+    "nae_spectrum_frames", "nae_spectrum_block_f32", "nae_spectrum_frames_ex", "nae_spectrum_block_ex_f32", "nae_spectrum_create", "nae_spectrum_put",
     "nae_spectrum_available", "nae_spectrum_receive", "nae_spectrum_destroy", "nae_graph4_run",
     "nae_wsola_plan_make", "nae_wsola_block_f32", "nae_wsola_create", "nae_wsola_put", "nae_wsola_put_host",
     "nae_wsola_flush", "nae_wsola_available", "nae_wsola_receive", "nae_wsola_receive_host", "nae_wsola_destroy",
@@ -146,6 +146,7 @@ def load_library() -> C.CDLL:
         "nae_swr_buffered": (sz, [vp]),
         "nae_swr_destroy": (i, [vp]), "nae_mono_to_stereo_f32": (i, [vp, vp, vp, sz, f]),
         "nae_spectrum_frames": (sz, [sz]), "nae_spectrum_block_f32": (i, [vp, P(Sig), sz, i, sz, vp, sz]),
+        "nae_spectrum_frames_ex": (sz, [sz, i, i]), "nae_spectrum_block_ex_f32": (i, [vp, i, i, P(Sig), sz, i, sz, vp, sz]),
         "nae_spectrum_create": (i, [vp, i, i, i, P(vp)]), "nae_spectrum_put": (i, [vp, vp, sz]),
         "nae_spectrum_available": (sz, [vp]), "nae_spectrum_receive": (i, [vp, vp, sz, P(sz)]),
         "nae_spectrum_destroy": (i, [vp]), "nae_graph4_run": (i, [vp, P(Graph4)]),
@@ -445,6 +446,14 @@ class Context:
 
     def spectrum_block(self, src: Sig, T: int, ch: int, n_streams: int, dst: int, dst_stream_stride: int):
         self._ck(self.lib.nae_spectrum_block_f32(self.h, C.byref(src), T, ch, n_streams, dst, dst_stream_stride))
+
+    def spectrum_frames_ex(self, T: int, n_fft: int, hop: int) -> int:
+        """frames of T samples at (n_fft, hop); 0 for parameters the library does not support"""
+        return int(self.lib.nae_spectrum_frames_ex(T, n_fft, hop))
+
+    def spectrum_block_ex(self, n_fft: int, hop: int, src: Sig, T: int, ch: int, n_streams: int, dst: int, dst_stream_stride: int):
+        """any size 256..4096 and hop 1..n_fft; records of n_fft/2 + 1 floats"""
+        self._ck(self.lib.nae_spectrum_block_ex_f32(self.h, n_fft, hop, C.byref(src), T, ch, n_streams, dst, dst_stream_stride))
 
     # -- graph
     def graph4(self, g: Graph4):

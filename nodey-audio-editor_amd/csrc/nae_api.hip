@@ -243,6 +243,7 @@ int nae_debug_set(nae_ctx* ctx, const char* key, long long value)
     else if (k == "spec_generic" && flag) ctx->dbg_spec_generic = value != 0;
     else if (k == "spec_narrow" && flag) ctx->dbg_spec_narrow = value != 0;
     else if (k == "spec_chunk" && count) ctx->dbg_spec_chunk = (int)value;
+    else if (k == "spec_any" && flag) ctx->dbg_spec_any = value != 0;
     else if (k == "spec_fine" && count) ctx->dbg_spec_fine = (int)value;
     else if (k == "spec_fine_rounds" && count) ctx->dbg_spec_fine_rounds = (int)value;
     else if (k == "td_nc" && one_of({0, 1, 2, 4})) ctx->dbg_td_nc = (int)value;
@@ -312,6 +313,7 @@ int nae_ctx_destroy(nae_ctx* ctx)
     if (ctx->d_t1024) (void)hipFree(ctx->d_t1024);
     if (ctx->d_hann) (void)hipFree(ctx->d_hann);
     if (ctx->d_spec_ctr) (void)hipFree(ctx->d_spec_ctr);
+    nae_spec_any_free(ctx);
     if (ctx->d_rs_tab) (void)hipFree(ctx->d_rs_tab);
     if (ctx->ws_phase) (void)hipFree(ctx->ws_phase);
     if (ctx->ws_mid) (void)hipFree(ctx->ws_mid);
@@ -691,7 +693,28 @@ int nae_spectrum_block_f32(nae_ctx* ctx, const nae_sig* src, size_t T, int ch, s
     int rc = check_sig(ctx, src, "null source view");
     if (rc) return rc;
     if (ch < 1 || ch > 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
+    if (ctx->dbg_spec_any) return nae_launch_spectrum_any(ctx, NAE_FFT_N, NAE_HOP, src, T, ch, n_streams, dst, dst_stream_stride);
     return nae_launch_spectrum(ctx, src, T, ch, n_streams, dst, dst_stream_stride);
+}
+
+size_t nae_spectrum_frames_ex(size_t T, int n_fft, int hop)
+{
+    if (nae_spectrum_check(n_fft, hop) != NAE_OK) return 0;
+    return T < (size_t)n_fft ? 0 : (T - (size_t)n_fft) / (size_t)hop + 1;
+}
+
+int nae_spectrum_block_ex_f32(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, size_t T, int ch, size_t n_streams, float* dst,
+                              size_t dst_stream_stride)
+{
+    if (!ctx || !dst) return NAE_ERR_INVALID;
+    const int chk = nae_spectrum_check(n_fft, hop);
+    if (chk != NAE_OK)
+        return nae_fail(ctx, chk, chk == NAE_ERR_UNSUPPORTED ? "spectrum: n_fft must be a power of two in [256, 4096]" : "spectrum: hop must be in [1, n_fft]");
+    if (n_fft == NAE_FFT_N && hop == NAE_HOP) return nae_spectrum_block_f32(ctx, src, T, ch, n_streams, dst, dst_stream_stride);
+    int rc = check_sig(ctx, src, "null source view");
+    if (rc) return rc;
+    if (ch < 1 || ch > 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
+    return nae_launch_spectrum_any(ctx, n_fft, hop, src, T, ch, n_streams, dst, dst_stream_stride);
 }
 
 // ------------------------------------------------------------------------------------------------ graph

@@ -33,10 +33,11 @@ struct nae_stretch {
 struct nae_spectrum {
     nae_ctx* ctx;
     int ch;
+    int n_fft = NAE_FFT_N, hop = NAE_HOP;
     // ping-pong pairs: the live data always moves into the OTHER buffer of its pair (an in-place forward move would
     // overlap), and nothing is allocated, freed or waited for once the buffers have grown to their working size
     DevBuf pending, pending_alt;   // interleaved samples not yet covered by a complete hop
-    DevBuf out, out_alt;           // [frames][ch][513]
+    DevBuf out, out_alt;           // [frames][ch][n_fft/2 + 1]
     size_t out_read = 0;           // frames handed out
     size_t out_frames = 0;
 };
@@ -382,12 +383,16 @@ int nae_spectrum_create(nae_ctx* ctx, int n_fft, int hop, int channels, nae_spec
     if (!ctx || !h) return NAE_ERR_INVALID;
     (void)nae_use_device(ctx);
     *h = nullptr;
-    if (n_fft != NAE_FFT_N || hop != NAE_HOP) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "only N = 1024, hop = 256 is implemented");
+    const int chk = nae_spectrum_check(n_fft, hop);
+    if (chk != NAE_OK)
+        return nae_fail(ctx, chk, chk == NAE_ERR_UNSUPPORTED ? "spectrum: n_fft must be a power of two in [256, 4096]" : "spectrum: hop must be in [1, n_fft]");
     if (channels != 1 && channels != 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
     nae_spectrum* s = new (std::nothrow) nae_spectrum();
     if (!s) return NAE_ERR_NOMEM;
     s->ctx = ctx;
     s->ch = channels;
+    s->n_fft = n_fft;
+    s->hop = hop;
     *h = s;
     return NAE_OK;
 }
@@ -405,9 +410,9 @@ int nae_spectrum_put(nae_spectrum* h, const float* interleaved, size_t S)
     if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(put)");
     h->pending.len += n;
     const size_t T = h->pending.len / h->ch;
-    const size_t F = nae_spectrum_frames(T);
+    const size_t F = nae_spectrum_frames_ex(T, h->n_fft, h->hop);
     if (F == 0) return NAE_OK;
-    const size_t rec = (size_t)h->ch * NAE_FFT_BINS;
+    const size_t rec = (size_t)h->ch * (size_t)(h->n_fft / 2 + 1);
     // compact what has been read (into the other buffer of the pair), then append the new frames
     if (h->out_read) {
         const size_t keep = (h->out_frames - h->out_read) * rec;
@@ -426,12 +431,12 @@ int nae_spectrum_put(nae_spectrum* h, const float* interleaved, size_t S)
     rc = devbuf_reserve(ctx, h->out, h->out.len + F * rec);
     if (rc) return rc;
     nae_sig src{h->pending.p, 0, 1, (size_t)h->ch};
-    rc = nae_spectrum_block_f32(ctx, &src, T, h->ch, 1, h->out.p + h->out.len, 0);
+    rc = nae_spectrum_block_ex_f32(ctx, h->n_fft, h->hop, &src, T, h->ch, 1, h->out.p + h->out.len, 0);
     if (rc) return rc;
     h->out.len += F * rec;
     h->out_frames += F;
     // keep the samples the next frame still needs: everything from F*hop on
-    const size_t drop = F * NAE_HOP * h->ch;
+    const size_t drop = F * (size_t)h->hop * h->ch;
     const size_t tail = h->pending.len - drop;
     h->pending_alt.len = 0;
     rc = devbuf_reserve(ctx, h->pending_alt, tail ? tail : 1);
@@ -455,7 +460,7 @@ int nae_spectrum_receive(nae_spectrum* h, float* dst, size_t max_frames, size_t*
     if (n > max_frames) n = max_frames;
     *got = n;
     if (n == 0) return NAE_OK;
-    const size_t rec = (size_t)h->ch * NAE_FFT_BINS;
+    const size_t rec = (size_t)h->ch * (size_t)(h->n_fft / 2 + 1);
     hipError_t e = hipMemcpyAsync(dst, h->out.p + h->out_read * rec, n * rec * sizeof(float), hipMemcpyDeviceToDevice, h->ctx->stream);
     if (e != hipSuccess) return nae_check(h->ctx, e, "hipMemcpyAsync(receive)");
     h->out_read += n;

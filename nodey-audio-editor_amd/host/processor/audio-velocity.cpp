@@ -404,9 +404,39 @@ namespace processor
 	infra::Processor::Info Audio_spectrum::get_processor_info()
 	{
 		return {"audio_spectrum", "FFT Spectrum", false, [] { return std::unique_ptr<infra::Processor>(new Audio_spectrum); },
-				"Hann-windowed 1024-point magnitude spectrum every 256 samples (MI355X)"};
+				"Hann-windowed magnitude spectrum, 256 to 4096 points, any hop (MI355X)"};
 	}
 	std::vector<infra::Processor::Pin_attribute> Audio_spectrum::get_pin_attributes() const { return io_pins(); }
+
+	Json::Value Audio_spectrum::serialize() const
+	{
+		Json::Value value;
+		if (fft_size != default_fft_size) value["fft_size"] = fft_size;
+		if (hop != default_hop) value["hop"] = hop;
+		return value;
+	}
+
+	void Audio_spectrum::deserialize(const Json::Value& value)
+	{
+		const auto wrong = [](const char* field) {
+			return Runtime_error(
+				"Failed to deserialize JSON file",
+				"Audio_spectrum failed to serialize the JSON input because of missing or invalid fields.",
+				std::string("Wrong field: ") + field
+			);
+		};
+		const auto integer = [&](const char* key, int fallback) {
+			if (!value.isMember(key)) return fallback;  // no key: the default (a project saved before the key existed)
+			const Json::Value& v = value[key];
+			if (!v.isDouble() || v.asDouble() != (double)v.asInt()) throw wrong(key);
+			return v.asInt();
+		};
+		const int n = integer("fft_size", default_fft_size), h = integer("hop", default_hop);
+		if (nae_spectrum_frames_ex((size_t)n, n, 1) == 0) throw wrong("fft_size");
+		if (nae_spectrum_frames_ex((size_t)n, n, h) == 0) throw wrong("hop");
+		fft_size = n;
+		hop = h;
+	}
 
 	void Audio_spectrum::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
@@ -467,14 +497,15 @@ namespace processor
 				if (ch != 1 && ch != 2) throw Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
 				sample_rate = frame->sample_rate;
 				time_seconds = frame->pts * av_q2d(frame->time_base);
-				gpu::check(nae_spectrum_create(ctx, 1024, 256, ch, &spectrum), "nae_spectrum_create");
+				gpu::check(nae_spectrum_create(ctx, fft_size, hop, ch, &spectrum), "nae_spectrum_create");
 			}
 			size_t total = 0;
 			float* samples = upload_as_f32(batch, h_raw, d_raw, d_f32, &total);
 			gpu::check(nae_spectrum_put(spectrum, samples, total), "nae_spectrum_put");
 			const size_t ready = nae_spectrum_available(spectrum);
 			if (ready == 0) { gpu::wait(stop_token); continue; }
-			const size_t rec = (size_t)ch * 513;
+			const int bins = fft_size / 2 + 1;
+			const size_t rec = (size_t)ch * bins;
 			float* dout = static_cast<float*>(d_out.reserve(ready * rec * sizeof(float)));
 			float* host = static_cast<float*>(h_out.reserve(ready * rec * sizeof(float)));
 			size_t got = 0;
@@ -487,13 +518,13 @@ namespace processor
 				Frame_data* o = out->data();
 				o->format = AV_SAMPLE_FMT_FLTP;
 				o->sample_rate = sample_rate;
-				o->nb_samples = 513;
+				o->nb_samples = bins;
 				o->ch_layout.nb_channels = ch;
 				o->time_base = {1, 1000000};
 				o->pts = (int64_t)(time_seconds * 1000000);
 				frame_get_buffer(o, 32);
-				for (int c = 0; c < ch; c++) std::memcpy(o->data[c], host + (f * ch + c) * 513, 513 * sizeof(float));
-				time_seconds += 256.0 / sample_rate;
+				for (int c = 0; c < ch; c++) std::memcpy(o->data[c], host + (f * ch + c) * bins, bins * sizeof(float));
+				time_seconds += (double)hop / sample_rate;
 				for (auto& stream : output_stream)
 					while (!stop_token && stream->try_push(out) != channel_op_status::success) nae_fiber::this_fiber::yield();
 			}

@@ -67,12 +67,17 @@ namespace processor
 		void deserialize(const Json::Value& value) override;  // :502-505
 	};
 
-	// New node (registered as "audio_spectrum"): per channel, Hann-windowed 1024-point r2c magnitude every 256
-	// sample-frames.  Output stays an Audio_stream so the editor's pin type check passes: one FLTP frame per hop with
-	// nb_samples = 513 (bins), plane c = |X_c[k]|, pts = start time of the analysed window.
+	// New node (registered as "audio_spectrum"): per channel, Hann-windowed fft_size-point r2c magnitude every hop
+	// sample-frames (JSON keys "fft_size" = 256 ... 4096, a power of two, and "hop" = 1 ... fft_size; defaults 1024 / 256, which
+	// are not written back).  Output stays an Audio_stream so the editor's pin type check passes: one FLTP frame per hop with
+	// nb_samples = fft_size/2 + 1 (bins), plane c = |X_c[k]|, pts = start time of the analysed window.
 	class Audio_spectrum : public infra::Processor
 	{
 	  public:
+
+		static constexpr int default_fft_size = 1024, default_hop = 256;
+		int fft_size = default_fft_size;
+		int hop = default_hop;
 
 		const void* last_context = nullptr;  // the nae_ctx its last process_payload ran on (every running node owns one: gpu-context.hpp); tests only
 
@@ -87,7 +92,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override { return {}; }
-		void deserialize(const Json::Value&) override {}
+		Json::Value serialize() const override;
+		void deserialize(const Json::Value& value) override;
 	};
 }
