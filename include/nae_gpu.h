@@ -128,7 +128,7 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *   spec_generic, spec_narrow              1: skip the interleaved-stereo spectrum kernel / its dword stores instead of 16-byte ones
  *   spec_chunk, spec_fine, spec_fine_rounds   frames per chunk of the stereo spectrum kernel / of the short chunks at a launch's end / how many of those per wave
  *   spec_any        1: 1024-point spectrum launches (nae_spectrum_block_f32, _ex at 1024 / 256, the graph's spectrum node) run the size-generic
- *                   kernel instead of the 1024-point ones (same results, bit for bit)
+ *                   kernel of the other sizes instead of the 1024-point ones, whatever spec_generic says (same results, bit for bit)
  *   td_nc           1 | 2 | 4: candidates per thread of the WSOLA search;  st_unfused  1: filter and cubic stage of the WSOLA chain as two launches
  * The same assignments, comma separated, in the environment variable NAE_DEBUG ("pv_flow=2,pv_fps=4") are applied when a context is created
  * (for measuring a program that creates its contexts itself, e.g. bench.py); an unknown key there fails nae_ctx_create with NAE_ERR_INVALID. */
@@ -322,7 +322,8 @@ int nae_spectrum_block_f32(nae_ctx* ctx, const nae_sig* src, size_t T, int ch, s
  * f*hop; frames = T < n_fft ? 0 : (T-n_fft)/hop + 1; per channel periodic Hann_N, un-normalised r2c DFT, |X[k]| for k = 0..n_fft/2
  * (canonical FFT of DESIGN.md §3: bit-exact against its CPU restatement, and at 1024 the bits of nae_spectrum_block_f32).
  * dst element (s, frame f, channel c, bin k) at dst_base[s*dst_stream_stride + (f*ch + c)*(n_fft/2 + 1) + k].
- * nae_spectrum_frames_ex returns 0 for parameters that are not supported.  1024 / 256 runs nae_spectrum_block_f32. */
+ * nae_spectrum_frames_ex returns 0 for parameters that are not supported.  nae_spectrum_block_f32 and nae_spectrum_frames are
+ * these calls at 1024 / 256. */
 size_t nae_spectrum_frames_ex(size_t T, int n_fft, int hop);
 int nae_spectrum_block_ex_f32(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, size_t T, int ch, size_t n_streams, float* dst,
                               size_t dst_stream_stride);

@@ -684,17 +684,12 @@ int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_s
 }
 
 // ------------------------------------------------------------------------------------------------ K8
-size_t nae_spectrum_frames(size_t T) { return T < NAE_FFT_N ? 0 : (T - NAE_FFT_N) / NAE_HOP + 1; }
+size_t nae_spectrum_frames(size_t T) { return nae_spectrum_frames_ex(T, NAE_FFT_N, NAE_HOP); }
 
 int nae_spectrum_block_f32(nae_ctx* ctx, const nae_sig* src, size_t T, int ch, size_t n_streams, float* dst,
                            size_t dst_stream_stride)
 {
-    if (!ctx || !dst) return NAE_ERR_INVALID;
-    int rc = check_sig(ctx, src, "null source view");
-    if (rc) return rc;
-    if (ch < 1 || ch > 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
-    if (ctx->dbg_spec_any) return nae_launch_spectrum_any(ctx, NAE_FFT_N, NAE_HOP, src, T, ch, n_streams, dst, dst_stream_stride);
-    return nae_launch_spectrum(ctx, src, T, ch, n_streams, dst, dst_stream_stride);
+    return nae_spectrum_block_ex_f32(ctx, NAE_FFT_N, NAE_HOP, src, T, ch, n_streams, dst, dst_stream_stride);
 }
 
 size_t nae_spectrum_frames_ex(size_t T, int n_fft, int hop)
@@ -710,11 +705,10 @@ int nae_spectrum_block_ex_f32(nae_ctx* ctx, int n_fft, int hop, const nae_sig* s
     const int chk = nae_spectrum_check(n_fft, hop);
     if (chk != NAE_OK)
         return nae_fail(ctx, chk, chk == NAE_ERR_UNSUPPORTED ? "spectrum: n_fft must be a power of two in [256, 4096]" : "spectrum: hop must be in [1, n_fft]");
-    if (n_fft == NAE_FFT_N && hop == NAE_HOP) return nae_spectrum_block_f32(ctx, src, T, ch, n_streams, dst, dst_stream_stride);
     int rc = check_sig(ctx, src, "null source view");
     if (rc) return rc;
     if (ch < 1 || ch > 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
-    return nae_launch_spectrum_any(ctx, n_fft, hop, src, T, ch, n_streams, dst, dst_stream_stride);
+    return nae_launch_spectrum(ctx, n_fft, hop, src, T, ch, n_streams, dst, dst_stream_stride);
 }
 
 // ------------------------------------------------------------------------------------------------ graph

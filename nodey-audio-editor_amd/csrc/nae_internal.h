@@ -20,8 +20,8 @@ struct nae_ctx {
     nae::cf* d_w512 = nullptr;   // exp(-2 pi i k/512),  k = 0..511
     nae::cf* d_t1024 = nullptr;  // exp(-2 pi i k/1024), k = 0..512
     float* d_hann = nullptr;     // periodic Hann, 1024
-    unsigned* d_spec_ctr = nullptr;  // work counter of the persistent stereo spectrum kernel (zeroed on the stream in front of every drawing launch; kernels_stft.hip)
-    // tables of the spectrum sizes other than 1024 (n_fft = 256, 512, -, 2048, 4096), built on first use (kernels_spec_any.hip)
+    unsigned* d_spec_ctr = nullptr;  // work counter of the persistent stereo spectrum kernel (zeroed on the stream in front of every drawing launch; kernels_spectrum.hip)
+    // tables of the spectrum sizes other than 1024 (n_fft = 256, 512, -, 2048, 4096), built on first use (kernels_spectrum.hip)
     struct SpecAnyTab { float* hann = nullptr; nae::cf* tn = nullptr; nae::cf* wm = nullptr; };
     SpecAnyTab spec_any_tab[5];
     // grow-only workspaces
@@ -42,7 +42,7 @@ struct nae_ctx {
     bool dbg_spec_narrow = false;    // spec_narrow: the stereo spectrum kernel stores dword pieces (round 1-4 form) instead of 16-byte ones
     int dbg_spec_fine = 0, dbg_spec_fine_rounds = 0;   // spec_fine / spec_fine_rounds: frames of the short chunks at the end of a large launch's list / how many of them per resident wave
     int dbg_spec_chunk = 0;          // spec_chunk: frames one wave of the stereo spectrum kernel walks (0: spec_pick_chunk)
-    bool dbg_spec_any = false;       // spec_any: 1024-point spectrum launches run the size-generic kernel (kernels_spec_any.hip)
+    bool dbg_spec_any = false;       // spec_any: 1024-point spectrum launches run the size-generic kernel (kernels_spectrum.hip)
     int dbg_pv_min_ptile = 0;        // pv_min_ptile: shortest pass-1 tile in frames (0: 16)
     int pv_flow = 1;                 // pv_flow = 0|1|2: launches of at most one workgroup per CU run the one-barrier schedule (pv_flow_kernel) never / with one
                                      // frame per step (default: where it is faster, profiles/r05_flow.md) / in every shape
@@ -88,12 +88,9 @@ int nae_check(nae_ctx* ctx, hipError_t e, const char* what);
 int nae_fail(nae_ctx* ctx, int code, const char* what);
 int nae_ws_reserve(nae_ctx* ctx, void** p, size_t* have, size_t want);
 
-// kernels_stft.hip
-int nae_launch_spectrum(nae_ctx* ctx, const nae_sig* src, size_t T, int ch, size_t n_streams, float* dst,
+// kernels_spectrum.hip: every supported size and hop (arguments checked by the caller); picks the kernel
+int nae_launch_spectrum(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, size_t T, int ch, size_t n_streams, float* dst,
                         size_t dst_stream_stride);
-// kernels_spec_any.hip: every supported size and hop (checked by the caller)
-int nae_launch_spectrum_any(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, size_t T, int ch, size_t n_streams, float* dst,
-                            size_t dst_stream_stride);
 void nae_spec_any_free(nae_ctx* ctx);
 // the one statement of the spectrum's parameter rules (nae_spectrum_frames_ex, nae_spectrum_block_ex_f32, nae_spectrum_create):
 // n_fft a power of two in [256, 4096], else NAE_ERR_UNSUPPORTED; 1 <= hop <= n_fft, else NAE_ERR_INVALID

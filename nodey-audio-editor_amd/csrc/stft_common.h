@@ -1,4 +1,5 @@
-// stft_common.h — kernel-side types shared by the STFT translation units (kernels_stft.hip, kernels_pvpipe.hip).
+// stft_common.h — kernel-side types shared by the STFT translation units (kernels_stft.hip, kernels_pvpipe.hip,
+// kernels_spectrum.hip).
 #pragma once
 #include "nae_internal.h"
 #include "stft_device.h"
@@ -10,6 +11,18 @@ constexpr int kT1024Pad = kPhasePad;             // 513 split twiddles / phases,
 struct Tables { const cf* w512; const cf* t1024; const float* hann; };
 struct SigViewD { const float* base; long long ss, cs, fs; };
 struct OutViewD { float* base; long long ss, cs, fs; };
+
+inline SigViewD to_view(const nae_sig* s)
+{
+    return SigViewD{static_cast<const float*>(s->base), (long long)s->stream_stride, (long long)s->chan_stride,
+                    (long long)s->frame_stride};
+}
+
+// the 1024-point kernels on the padded FFT (spectrum, vocoder pass 1): 8-wave workgroups that stage Hann, the split twiddles,
+// W64 and the pass-A twiddles in LDS, followed by one padded FFT scratch per wave
+constexpr int kWaves = 8;                        // waves per workgroup
+constexpr int kThreads = kWaves * 64;
+constexpr size_t kLdsTablesPad = NAE_FFT_N * sizeof(float) + (kT1024Pad + 64 + kTwaCf) * sizeof(cf);
 
 // wave index as a SCALAR: hipcc cannot prove threadIdx.x >> 6 wave-uniform, and everything derived from it
 // (stream / tile / frame addresses) would otherwise be carried in VGPRs with 64-bit vector address math

@@ -17,8 +17,6 @@ namespace nae {
 struct cf { float x, y; };
 struct __attribute__((packed, aligned(4))) f2u { float x, y; }; // 8-byte access at 4-byte alignment
 
-constexpr int kScratchCf = 520;                 // per-wave LDS scratch, complex elements (512 for the transposes, 513 natural)
-
 __device__ __forceinline__ void wave_lds_sync()
 {
     // order this wave's LDS writes before its following LDS reads (other lanes' data); no instruction
@@ -125,79 +123,14 @@ __device__ __forceinline__ void dft8_fwd(cf (&a)[8])
 }
 #endif
 
-// per-lane twiddles of the two twiddled passes, loop-invariant across frames
-struct FftTw {
-    cf a[7];        // W512^(lane*q), q = 1..7: 14 VGPRs, loop-invariant
-    const cf* b;    // LDS table [m][p] = W512^(8 m p), 64 entries shared by the workgroup; this lane reads row lane&7
-};
-
-__device__ __forceinline__ void load_fft_tw(FftTw& tw, const cf* __restrict__ w512, const cf* w64_lds, int lane)
-{
-#pragma unroll
-    for (int q = 1; q < 8; q++) tw.a[q - 1] = w512[lane * q];
-    tw.b = w64_lds + 8 * (lane & 7);
-}
-
 // bin / packed-sample index held by (lane, register r) after the forward FFT:  k = lane + 64 r  (natural order)
 __device__ __forceinline__ int kl_of_lane(int lane) { return lane; }
 
-// canonical forward 512-point FFT.  in: v[j] = z[lane + 64 j];  out: v[r] = Z[lane + 64 r].
-//
-// The two transposes go through the wave's 512-entry LDS scratch with XOR-swizzled addresses chosen so that every
-// ds_write_b64 (16-lane groups, 32 banks) and ds_read_b64 (32-lane groups, 64 banks) is conflict-free WITHOUT
-// padding, and so that pass C leaves the result in natural order (lane = k mod 64):
-//   T1  element u1[q][l]     at  (l ^ (q << 3)) + 64 q
-//   T2  element u2[q][p][m]  at  (q ^ ((m & 3) << 1)) | ((p ^ (m >> 2)) << 3) | (m << 6)
-// (address bits are an invertible GF(2) map of the index bits whose low 4 / 5 bits are a bijection of the
-//  lane bits that vary inside one write / read group).
-// kLaunder: the 32 swizzled LDS addresses below are loop-invariant, and hoisting them out of the frame loop pins 32
-// VGPRs.  2 = recompute all of them per call (~75 instructions; the 128-VGPR vocoder builds), 1 = recompute only the 14
-// that are one XOR each and keep the 16 two-to-three-instruction ones hoisted (the spectrum kernel: +16 VGPRs, -36
-// instructions per FFT), 0 = keep everything hoisted (the 256-VGPR build).
-template <int kLaunder = 2>
-__device__ __forceinline__ void fft512_fwd(cf (&v)[8], cf* __restrict__ scratch, const FftTw& tw, int lane)
-{
-    int lane_x = lane;                                   // feeds the XOR-with-constant addresses
-    if (kLaunder >= 1) asm volatile("" : "+v"(lane_x));
-    if (kLaunder >= 2) asm volatile("" : "+v"(lane));
-    const int m = lane & 7, qq = lane >> 3;
-    // pass A
-    dft8_fwd(v);
-#pragma unroll
-    for (int q = 1; q < 8; q++) v[q] = cmul_tw(v[q], tw.a[q - 1]);
-    // transpose 1: u1[q][l] -> lane (m, qq) register j = u1[qq][m + 8 j]
-#pragma unroll
-    for (int q = 0; q < 8; q++) scratch[(lane_x ^ (q << 3)) + 64 * q] = v[q];
-    wave_lds_sync();
-    {
-        const int base = m + 64 * qq;
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = scratch[base + ((j ^ qq) << 3)];
-    }
-    wave_lds_sync();
-    // pass B
-    dft8_fwd(v);
-#pragma unroll
-    for (int p = 1; p < 8; p++) v[p] = cmul_tw(v[p], tw.b[p]);
-    // transpose 2: u2[qq][p][m] -> lane (q'' = lane & 7, p'' = lane >> 3) register j = u2[q''][p''][j]
-    {
-        const int base = (qq ^ ((m & 3) << 1)) | (m << 6);
-        const int ph = m >> 2;
-#pragma unroll
-        for (int p = 0; p < 8; p++) scratch[base | ((p ^ ph) << 3)] = v[p];
-    }
-    wave_lds_sync();
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = scratch[(lane_x ^ (((j & 3) << 1) | ((j >> 2) << 3))) + 64 * j];
-    wave_lds_sync();
-    // pass C
-    dft8_fwd(v);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// Low-register form of the same FFT (identical arithmetic, so identical bits): every LDS access is a per-lane base
-// register plus an IMMEDIATE offset — no swizzle arithmetic, no hoisted address registers — and the pass-A twiddles
-// come from an LDS table instead of 14 VGPRs.  Conflict-freedom comes from padding instead of XOR swizzles:
+// Canonical forward 512-point FFT, low-register form.  in: v[j] = z[lane + 64 j];  out: v[r] = Z[lane + 64 r] (natural order).
+// Pass A, transpose 1, pass B (twiddles W512^(8 m p)), transpose 2, pass C.  Every LDS access is a per-lane base register plus
+// an IMMEDIATE offset — no swizzle arithmetic, no hoisted address registers — and the pass-A twiddles come from an LDS table
+// instead of 14 VGPRs.  Conflict-freedom comes from padding:
 //   T1  element u1[q][l]     at  72 q + l          (write: lane l, imm 72 q;  read: lane (m, qq) at 72 qq + m, imm 8 j)
 //   T2  element u2[q][p][m]  at  q + 8 p + 66 m    (write: lane (m, qq) at qq + 66 m, imm 8 p;  read: lane, imm 66 j)
 // ds_write_b64 is serviced in 16-lane groups over 32 banks, ds_read_b64 in 32-lane groups over 64 banks
