@@ -33,7 +33,9 @@ extern "C" {
  * nae_abi_version() >= 2.
  * 3 (round 6): addition — nae_debug_set (the tuning / A-B switches, formerly 14 environment variables read at context creation).
  *   Later additions within 3 (the version number did not move; a caller probes for them by symbol, e.g. dlsym): nae_spectrum_frames_ex
- *   and nae_spectrum_block_ex_f32 (spectrum sizes 256 ... 4096, any hop); nae_spectrum_create accepts those sizes and hops. */
+ *   and nae_spectrum_block_ex_f32 (spectrum sizes 256 ... 4096, any hop); nae_spectrum_create accepts those sizes and hops;
+ *   NAE_STRETCH_PHASE_LOCK with nae_stretch_block_ex_f32, nae_stretch_create_ex and nae_debug_pv_tile_phase_ex (identity phase locking of the
+ *   vocoder). */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -239,8 +241,23 @@ int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_s
                             size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles,
                             size_t* tile_frames);
 
+/* Options of the _ex entries (flags; an unknown bit returns NAE_ERR_INVALID, flags == 0 is exactly the call without _ex).
+ * NAE_STRETCH_PHASE_LOCK: identity phase locking (Laroche & Dolson 1999; DESIGN.md §3, "Phase locking").  Frame f >= 1 advances only the
+ * phase of each spectral peak of the power spectrum and keeps every other bin at its analysis phase offset from its nearest peak:
+ * Qs_f[k] = Qs_{f-1}[p] + inc_f[p] + (Qa_f[k] - Qa_f[p]), p = the peak of bin k (a frame without a peak runs unlocked).  A steady tone keeps its
+ * amplitude (the unlocked vocoder loses 2-16 % on an off-centre tone).  Everything else — analysis, transposer, stage order, lengths — is the
+ * unlocked node's.  Integer phases are bit-exact against the CPU restatement (tests/pv_lock/ref_pv_lock.c) and independent of the tiling. */
+#define NAE_STRETCH_PHASE_LOCK 1u
+int nae_stretch_block_ex_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, const nae_sig* src, size_t in_len, int ch,
+                             size_t n_streams, const nae_sig* dst);
+/* the phase tap of the vocoder selected by `flags` (locked: Qs in front of every tile of the locked recurrence) */
+int nae_debug_pv_tile_phase_ex(nae_ctx* ctx, double rate, double pitch, unsigned flags, const nae_sig* src, size_t in_len, int ch,
+                               size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles, size_t* tile_frames);
+
 /* SoundTouch-shaped streaming handle (interleaved f32, device pointers) */
 int nae_stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, nae_stretch** h);
+/* the same with the flags of nae_stretch_block_ex_f32; the handle's output equals the block call's with those flags */
+int nae_stretch_create_ex(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, nae_stretch** h);
 int nae_stretch_put(nae_stretch* h, const float* interleaved, size_t S);
 int nae_stretch_put_host(nae_stretch* h, const float* interleaved_host, size_t S);
 int nae_stretch_flush(nae_stretch* h);

@@ -24,7 +24,7 @@ EXPORTED_SYMBOLS = [
     "nae_deinterleave_f32", "nae_interleave_f32", "nae_copy_sig_f32", "nae_gain_sig_f32", "nae_amix_f32",
     "nae_amix_sig_f32", "nae_bimix_f32", "nae_bimix2_downmix_f32", "nae_bimix2_interleave_f32",
     "nae_to_f32_interleaved", "nae_clamp_f32", "nae_stretch_plan_make", "nae_stretch_block_f32",
-    "nae_debug_pv_tile_phase", "nae_stretch_create", "nae_stretch_put", "nae_stretch_put_host", "nae_stretch_flush",
+    "nae_debug_pv_tile_phase", "nae_stretch_block_ex_f32", "nae_debug_pv_tile_phase_ex", "nae_stretch_create_ex", "nae_stretch_create", "nae_stretch_put", "nae_stretch_put_host", "nae_stretch_flush",
     "nae_stretch_available", "nae_stretch_receive", "nae_stretch_receive_host", "nae_stretch_destroy",
     "nae_swr_create", "nae_swr_convert_host", "nae_swr_convert", "nae_swr_buffered", "nae_swr_destroy", "nae_mono_to_stereo_f32",
     "nae_spectrum_frames", "nae_spectrum_block_f32", "nae_spectrum_frames_ex", "nae_spectrum_block_ex_f32", "nae_spectrum_create", "nae_spectrum_put",
@@ -32,6 +32,9 @@ EXPORTED_SYMBOLS = [
     "nae_wsola_plan_make", "nae_wsola_block_f32", "nae_wsola_create", "nae_wsola_put", "nae_wsola_put_host",
     "nae_wsola_flush", "nae_wsola_available", "nae_wsola_receive", "nae_wsola_receive_host", "nae_wsola_destroy",
 ]
+
+
+STRETCH_PHASE_LOCK = 1       # NAE_STRETCH_PHASE_LOCK (include/nae_gpu.h)
 
 
 class NaeError(RuntimeError):
@@ -103,7 +106,7 @@ def load_library() -> C.CDLL:
     if not os.path.exists(p):
         raise NaeError(f"{p} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950)")
     lib = C.CDLL(p)
-    vp, sz, i, f, d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
+    vp, sz, i, u, f, d = C.c_void_p, C.c_size_t, C.c_int, C.c_uint, C.c_float, C.c_double
     P = C.POINTER
     sigs = {
         "nae_abi_version": (i, []), "nae_device_count": (i, []),
@@ -137,6 +140,9 @@ def load_library() -> C.CDLL:
         "nae_stretch_plan_make": (i, [d, d, sz, P(StretchPlan)]),
         "nae_stretch_block_f32": (i, [vp, d, d, P(Sig), sz, i, sz, P(Sig)]),
         "nae_debug_pv_tile_phase": (i, [vp, d, d, P(Sig), sz, i, sz, vp, sz, P(sz), P(sz)]),
+        "nae_stretch_block_ex_f32": (i, [vp, d, d, u, P(Sig), sz, i, sz, P(Sig)]),
+        "nae_debug_pv_tile_phase_ex": (i, [vp, d, d, u, P(Sig), sz, i, sz, vp, sz, P(sz), P(sz)]),
+        "nae_stretch_create_ex": (i, [vp, i, i, f, f, u, P(vp)]),
         "nae_stretch_create": (i, [vp, i, i, f, f, P(vp)]), "nae_stretch_put": (i, [vp, vp, sz]),
         "nae_stretch_put_host": (i, [vp, vp, sz]), "nae_stretch_flush": (i, [vp]),
         "nae_stretch_available": (sz, [vp]), "nae_stretch_receive": (i, [vp, vp, sz, P(sz)]),
@@ -414,16 +420,26 @@ class Context:
             raise NaeError(f"nae_stretch_plan_make({rate}, {pitch}) failed: {rc}")
         return pl
 
-    def stretch_block(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
-        self._ck(self.lib.nae_stretch_block_f32(self.h, rate, pitch, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+    def stretch_block(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig,
+                      phase_lock: bool = False):
+        if phase_lock:
+            self._ck(self.lib.nae_stretch_block_ex_f32(self.h, rate, pitch, STRETCH_PHASE_LOCK, C.byref(src), in_len, ch, n_streams,
+                                                       C.byref(dst)))
+        else:
+            self._ck(self.lib.nae_stretch_block_f32(self.h, rate, pitch, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
-    def debug_pv_tile_phase(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int):
+    def debug_pv_tile_phase(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int,
+                            phase_lock: bool = False):
         pl = self.stretch_plan(rate, pitch, in_len)
         cap = n_streams * ch * (pl.frames + 1) * BINS
         out = np.zeros(cap, np.int32)
         nt, tf = C.c_size_t(), C.c_size_t()
-        self._ck(self.lib.nae_debug_pv_tile_phase(self.h, rate, pitch, C.byref(src), in_len, ch, n_streams,
-                                                  out.ctypes.data, cap, C.byref(nt), C.byref(tf)))
+        if phase_lock:
+            self._ck(self.lib.nae_debug_pv_tile_phase_ex(self.h, rate, pitch, STRETCH_PHASE_LOCK, C.byref(src), in_len, ch, n_streams,
+                                                         out.ctypes.data, cap, C.byref(nt), C.byref(tf)))
+        else:
+            self._ck(self.lib.nae_debug_pv_tile_phase(self.h, rate, pitch, C.byref(src), in_len, ch, n_streams,
+                                                      out.ctypes.data, cap, C.byref(nt), C.byref(tf)))
         return out[: n_streams * ch * nt.value * BINS].reshape(n_streams, ch, nt.value, BINS), tf.value
 
     # -- K7 option A: SoundTouch-shaped WSOLA chain
@@ -462,3 +478,37 @@ class Context:
     def graph4_stages(self, g: Graph4, mask: int):
         """stages of the graph: 1 = mix (+ transposer when first), 2 = rest of the pitch node, 4 = spectrum"""
         self._ck(self.lib.nae_debug_graph4_stages(self.h, C.byref(g), mask))
+
+
+class Stretcher:
+    """The SoundTouch-shaped streaming handle (nae_stretch_create_ex): put interleaved f32, flush, receive."""
+
+    def __init__(self, ctx: Context, sample_rate: int, channels: int, rate: float, pitch: float, phase_lock: bool = False):
+        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+        flags = STRETCH_PHASE_LOCK if phase_lock else 0
+        ctx._ck(ctx.lib.nae_stretch_create_ex(ctx.h, sample_rate, channels, rate, pitch, flags, C.byref(self.h)))
+
+    def put(self, dev_ptr: int, frames: int) -> None:
+        self.ctx._ck(self.ctx.lib.nae_stretch_put(self.h, dev_ptr, frames))
+
+    def put_host(self, x: np.ndarray) -> None:
+        x = np.ascontiguousarray(x, np.float32)
+        self.ctx._ck(self.ctx.lib.nae_stretch_put_host(self.h, x.ctypes.data, x.size // self.ch))
+
+    def flush(self) -> None:
+        self.ctx._ck(self.ctx.lib.nae_stretch_flush(self.h))
+
+    def available(self) -> int:
+        return self.ctx.lib.nae_stretch_available(self.h)
+
+    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
+        n = self.available() if max_frames is None else max_frames
+        out = np.empty(max(n, 1) * self.ch, np.float32)
+        got = C.c_size_t()
+        self.ctx._ck(self.ctx.lib.nae_stretch_receive_host(self.h, out.ctypes.data, n, C.byref(got)))
+        return out[: got.value * self.ch]
+
+    def close(self) -> None:
+        if self.h:
+            self.ctx.lib.nae_stretch_destroy(self.h)
+            self.h = C.c_void_p()

@@ -1,0 +1,597 @@
+// kernels_pvlock.hip — K7 phase vocoder with identity phase locking (NAE_STRETCH_PHASE_LOCK; DESIGN.md §3, "Phase locking") for gfx950.
+//
+// The locked Qs recurrence of frame f is a map M_f = (sigma_f, c_f): Qs_f[k] = Qs_{f-1}[sigma_f[k]] + c_f[k] (uint32, wrapping).  Maps compose
+// exactly — (sigma_b, c_b) o (sigma_a, c_a) = (sigma_a[sigma_b], c_a[sigma_b] + c_b), a first — so the three passes of the unlocked vocoder
+// (kernels_stft.hip) keep their shape, with a map where they had a sum:
+//   pass L1 (pvlock_map_kernel)   one wave per (stream-channel, pass-1 tile): analysis, power, peaks, regions and M_f of each frame, composed into
+//                                 the tile's map (sigma uint16, c uint32);
+//   pass L2 (pvlock_scan_kernel)  per stream-channel, the tile maps applied in order: Qs in front of every tile (the record format of the
+//                                 unlocked scan), carry_in / carry_out as there.  Many tiles: 16 chunks composed side by side, then prefixed;
+//   pass L3 (pvlock_synth_kernel) one wave per synthesis tile: from the recorded Qs it walks its frames forward — re-analysis, M_f applied to the
+//                                 Qs vector in LDS, rotation, inverse FFT, window, overlap-add in increasing frame order — and stores its blocks.
+// Every integer is exact, so any tiling gives the same bits; the samples follow the oracle's tolerance path (|X| e^{i Qs}, inverse FFT, overlap-add).
+// The default (unlocked) path does not run any of this: its kernels, launchers and results are untouched.
+#include "pv_roles.h"
+
+namespace nae {
+
+// ------------------------------------------------------------------------------------------------ per-frame lock step
+// Per-wave LDS of the lock step: the FFT scratch (576 complex = 1152 words) doubles, once the spectrum is in registers, as
+//   words [0, 520):    P[k] (float bits), then sigma_f[k]
+//   words [520, 1040): B[k] = inc[k] - Qa[k]   (c_f[k] = B[sigma_f[k]] + Qa[k]: the same integer as inc[p] + (Qa[k] - Qa[p]))
+constexpr int kLockB = kT1024Pad;
+constexpr int kNoPeakHi = 4096;                   // "no peak to the right" (any index above 512)
+static_assert(2 * kT1024Pad <= 2 * kPadScratchCf, "P / sigma and B fit the FFT scratch");
+
+// one frame's analysis: canonical X (v[r] = X[lane + 64 r], nyq = X[512] in every lane) and its phases
+template <bool kUnit>
+__device__ __forceinline__ void lock_analyse(cf (&v)[8], cf& nyq, uint32_t (&qa)[9], const ChanView& in, long long s, const float* hann, cf* scratch,
+                                             const cf* twa, const cf* w64, const cf* t1024, int lane)
+{
+    load_frame_windowed<kUnit>(v, in, s, hann, lane);
+    fft512_pad(v, make_fft_lds(scratch, twa, w64, lane));
+    nyq = rfft_split<false>(v, scratch, t1024, lane);
+    phases_of(v, nyq, qa);
+}
+
+// M_f of frame f >= 1 for this lane's bins k = lane + 64 r (r = 8: k = 512, meaningful in lane 0).  qp: Qa_{f-1}.
+// Power (two products, one add, never fused), peaks, nearest-peak regions: DESIGN.md §3, rules 1-3.
+__device__ __forceinline__ void lock_map_of_frame(const cf (&v)[8], cf nyq, const uint32_t (&qa)[9], const uint32_t (&qp)[9], unsigned d, unsigned R,
+                                                  cf* scratch, int lane, uint32_t (&sig)[9], uint32_t (&c)[9])
+{
+    uint32_t* w = reinterpret_cast<uint32_t*>(scratch);
+    float* P = reinterpret_cast<float*>(scratch);
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const unsigned k = r < 8 ? (unsigned)(lane + 64 * r) : 512u;
+        const cf x = r < 8 ? v[r] : nyq;
+        const uint32_t inc = pipe_inc(qa[r], qp[r], k, d, R);
+        if (r < 8 || lane == 0) {
+            P[k] = x.x * x.x + x.y * x.y;
+            w[kLockB + k] = inc - qa[r];
+        }
+    }
+    wave_lds_sync();
+    // contiguous bins: lane l owns k0 .. k0 + 7 (lane 63 also 512); it reads P[k0 - 2 .. k0 + 10]
+    const int k0 = 8 * lane;
+    const int nb = lane == 63 ? 9 : 8;
+    float pw[13];
+#pragma unroll
+    for (int j = 0; j < 13; j++) {
+        const int i = k0 - 2 + j;
+        pw[j] = (i >= 0 && i < NAE_FFT_BINS) ? P[i] : 0.0f;
+    }
+    unsigned pk = 0;
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+        const int k = k0 + j;
+        bool ok = pw[j + 2] > 0.0f;
+        ok = ok && (k < 1 || pw[j + 2] > pw[j + 1]);
+        ok = ok && (k < 2 || pw[j + 2] > pw[j]);
+        ok = ok && (k + 1 >= NAE_FFT_BINS || pw[j + 2] >= pw[j + 3]);
+        ok = ok && (k + 2 >= NAE_FFT_BINS || pw[j + 2] >= pw[j + 4]);
+        if (ok && j < nb) pk |= 1u << j;
+    }
+    // nearest peak to the left (prefix max of peak indices) and to the right (suffix min), across the wave
+    const int last = pk ? k0 + 31 - __builtin_clz(pk) : -1;
+    const int first = pk ? k0 + __builtin_ctz(pk) : kNoPeakHi;
+    int lmax = last, rmin = first;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int a = __shfl_up(lmax, o, 64), b = __shfl_down(rmin, o, 64);
+        if (lane >= o) lmax = a > lmax ? a : lmax;
+        if (lane + o < 64) rmin = b < rmin ? b : rmin;
+    }
+    int left = __shfl_up(lmax, 1, 64), right = __shfl_down(rmin, 1, 64);
+    if (lane == 0) left = -1;
+    if (lane == 63) right = kNoPeakHi;
+    int lft[9], rgt[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+        if (pk & (1u << j)) left = k0 + j;
+        lft[j] = left;
+    }
+#pragma unroll
+    for (int j = 8; j >= 0; j--) {
+        if (pk & (1u << j)) right = k0 + j;
+        rgt[j] = right;
+    }
+    wave_lds_sync();                              // every lane's P reads are done: sigma_f replaces P
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+        const int k = k0 + j;
+        int s;
+        if (lft[j] < 0 && rgt[j] >= kNoPeakHi) s = k;                 // no peak in the frame: unlocked
+        else if (lft[j] < 0) s = rgt[j];
+        else if (rgt[j] >= kNoPeakHi) s = lft[j];
+        else s = (k - lft[j] <= rgt[j] - k) ? lft[j] : rgt[j];        // a tie goes to the lower peak
+        if (j < nb) w[k] = (uint32_t)s;
+    }
+    wave_lds_sync();
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const int k = r < 8 ? lane + 64 * r : 512;
+        sig[r] = w[k];
+        c[r] = w[kLockB + sig[r]] + qa[r];
+    }
+    wave_lds_sync();                              // the scratch is free again
+}
+
+// ------------------------------------------------------------------------------------------------ pass L1
+// tile maps: c at maps[rec * 520 + k] (uint32), sigma at sig16[rec * 520 + k] (uint16), rec = sc * n_tiles + tile
+constexpr size_t kLockMapWave = kPadScratchCf * sizeof(cf) + kT1024Pad * (sizeof(uint16_t) + sizeof(uint32_t));
+constexpr size_t kLdsLockMap = kLdsTablesPad + kWaves * kLockMapWave;
+static_assert(2 * kLdsLockMap <= 160 * 1024, "two workgroups per CU");
+
+__device__ __forceinline__ void lock_tables(unsigned char* smem, const Tables& tb, float*& hann, cf*& t1024, cf*& w64, cf*& twa)
+{
+    hann = reinterpret_cast<float*>(smem);
+    t1024 = reinterpret_cast<cf*>(smem + NAE_FFT_N * sizeof(float));
+    w64 = t1024 + kT1024Pad;
+    twa = w64 + 64;
+    for (int i = threadIdx.x; i < NAE_FFT_N; i += blockDim.x) hann[i] = tb.hann[i];
+    for (int i = threadIdx.x; i < NAE_FFT_BINS; i += blockDim.x) t1024[i] = tb.t1024[i];
+    if (threadIdx.x < 64) w64[threadIdx.x] = tb.w512[8 * (threadIdx.x >> 3) * (threadIdx.x & 7)];
+    fill_twa(twa, tb.w512, threadIdx.x, blockDim.x);
+    __syncthreads();
+}
+
+template <bool kUnit>
+__global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, PvParams p, long long n_items, uint32_t* __restrict__ maps,
+                                                                 uint16_t* __restrict__ sig16, Tables tb)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* hann; cf *t1024, *w64, *twa;
+    lock_tables(smem, tb, hann, t1024, w64, twa);
+    const int lane = threadIdx.x & 63;
+    unsigned char* mine = smem + kLdsTablesPad + (size_t)wave_id() * kLockMapWave;
+    cf* scratch = reinterpret_cast<cf*>(mine);
+    uint32_t* mc = reinterpret_cast<uint32_t*>(mine + kPadScratchCf * sizeof(cf));
+    uint16_t* ms = reinterpret_cast<uint16_t*>(mc + kT1024Pad);
+    const long long item = (long long)blockIdx.x * kWaves + wave_id();
+    if (item >= n_items) return;
+    const long long sc = item / p.n_tiles;
+    const int tile = (int)(item % p.n_tiles);
+    if (tile >= p.skip_from) return;                    // wave-uniform
+    const long long s_idx = sc / p.ch;
+    const int c = (int)(sc % p.ch);
+    ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
+
+    const long long f0 = p.f_origin + (long long)tile * p.tile;
+    long long f1 = f0 + p.tile;
+    if (f1 > p.f_stop) f1 = p.f_stop;
+    // the running map starts as the identity
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const int k = lane + 64 * r;
+        if (k < NAE_FFT_BINS) { mc[k] = 0u; ms[k] = (uint16_t)k; }
+    }
+    uint32_t qp[9], qa[9];
+#pragma unroll
+    for (int r = 0; r < 9; r++) qp[r] = 0;
+    cf v[8], nyq;
+    long long s_prev = 0;
+#pragma unroll 1
+    for (long long f = (f0 > 0 ? f0 - 1 : 0); f < f1; f++) {
+        const long long s = frame_start(p, f);
+        lock_analyse<kUnit>(v, nyq, qa, in, s, hann, scratch, twa, w64, t1024, lane);
+        if (f >= f0) {
+            uint32_t sg[9], cc[9];
+            if (f == 0) {
+                // Qs_0 = Qa_0: the map (identity, Qa_0) applied to the zero phase in front of the stream
+#pragma unroll
+                for (int r = 0; r < 9; r++) { sg[r] = r < 8 ? (uint32_t)(lane + 64 * r) : 512u; cc[r] = qa[r]; }
+            } else {
+                const unsigned d = (unsigned)(s - s_prev);
+                const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
+                lock_map_of_frame(v, nyq, qa, qp, d, R, scratch, lane, sg, cc);
+            }
+            // running map, then this frame: (ms[sg], mc[sg] + cc); all gathers land before the first write
+            uint32_t ns[9], nc[9];
+#pragma unroll
+            for (int r = 0; r < 9; r++) { ns[r] = ms[sg[r]]; nc[r] = mc[sg[r]] + cc[r]; }
+            wave_lds_sync();
+#pragma unroll
+            for (int r = 0; r < 9; r++) {
+                const int k = lane + 64 * r;
+                if (k < NAE_FFT_BINS) { ms[k] = (uint16_t)ns[r]; mc[k] = nc[r]; }
+            }
+            wave_lds_sync();
+        }
+#pragma unroll
+        for (int r = 0; r < 9; r++) qp[r] = qa[r];
+        s_prev = s;
+    }
+    uint32_t* oc = maps + item * kT1024Pad;
+    uint16_t* os = sig16 + item * kT1024Pad;
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const int k = lane + 64 * r;
+        if (k < NAE_FFT_BINS) { oc[k] = mc[k]; os[k] = ms[k]; }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pass L2
+// One workgroup per stream-channel, one wave per chunk of tiles (1 chunk, or kLockChunks from 256 tiles on).  Tiles >= n_read are the identity
+// (their maps were not computed); record t = Qs in front of tile t, carry_out = Qs behind the last tile.
+constexpr int kLockChunks = 16;
+constexpr size_t kLockScanWave = 3 * kT1024Pad * sizeof(uint32_t);      // chunk map (sigma, c) and the wave's running Qs
+
+__global__ __launch_bounds__(64 * kLockChunks) void pvlock_scan_kernel(uint32_t* __restrict__ rec, const uint32_t* __restrict__ maps,
+                                                                      const uint16_t* __restrict__ sig16, int n_tiles, const uint32_t* __restrict__ carry_in,
+                                                                      uint32_t* __restrict__ carry_out, int n_read)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63, ck = wave_id(), nch = (int)(blockDim.x >> 6);
+    const long long sc = blockIdx.x;
+    uint32_t* base = reinterpret_cast<uint32_t*>(smem);
+    auto chunk_s = [&](int w) { return base + (size_t)w * 3 * kT1024Pad; };
+    auto chunk_c = [&](int w) { return base + (size_t)w * 3 * kT1024Pad + kT1024Pad; };
+    uint32_t* qs = base + (size_t)ck * 3 * kT1024Pad + 2 * kT1024Pad;
+    const int per = (n_tiles + nch - 1) / nch;
+    const int j0 = ck * per < n_tiles ? ck * per : n_tiles;
+    const int j1 = j0 + per < n_tiles ? j0 + per : n_tiles;
+    const int r1 = j1 < n_read ? j1 : n_read;
+    const long long rec0 = sc * (long long)n_tiles;
+    uint32_t* ms = chunk_s(ck);
+    uint32_t* mc = chunk_c(ck);
+    if (nch > 1) {
+        // the chunk's map: its tiles composed in order
+#pragma unroll
+        for (int r = 0; r < 9; r++) {
+            const int k = lane + 64 * r;
+            if (k < NAE_FFT_BINS) { ms[k] = (uint32_t)k; mc[k] = 0u; }
+        }
+        wave_lds_sync();
+        for (int j = j0; j < r1; j++) {
+            const uint32_t* tc = maps + (rec0 + j) * kT1024Pad;
+            const uint16_t* ts = sig16 + (rec0 + j) * kT1024Pad;
+            uint32_t ns[9], nc[9];
+#pragma unroll
+            for (int r = 0; r < 9; r++) {
+                const int k = lane + 64 * r;
+                if (k < NAE_FFT_BINS) { const uint32_t sb = ts[k]; ns[r] = ms[sb]; nc[r] = mc[sb] + tc[k]; }
+            }
+            wave_lds_sync();
+#pragma unroll
+            for (int r = 0; r < 9; r++) {
+                const int k = lane + 64 * r;
+                if (k < NAE_FFT_BINS) { ms[k] = ns[r]; mc[k] = nc[r]; }
+            }
+            wave_lds_sync();
+        }
+    }
+    // Qs in front of the chunk: the carried phase (or zero), then the maps of the chunks before this one
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const int k = lane + 64 * r;
+        if (k < NAE_FFT_BINS) qs[k] = carry_in ? carry_in[sc * kT1024Pad + k] : 0u;
+    }
+    __syncthreads();
+    for (int w = 0; w < ck; w++) {
+        const uint32_t* ws = chunk_s(w);
+        const uint32_t* wc = chunk_c(w);
+        uint32_t nq[9];
+#pragma unroll
+        for (int r = 0; r < 9; r++) {
+            const int k = lane + 64 * r;
+            if (k < NAE_FFT_BINS) nq[r] = qs[ws[k]] + wc[k];
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int r = 0; r < 9; r++) {
+            const int k = lane + 64 * r;
+            if (k < NAE_FFT_BINS) qs[k] = nq[r];
+        }
+        wave_lds_sync();
+    }
+    // the chunk's own tiles: record, then apply
+    for (int j = j0; j < j1; j++) {
+        uint32_t* o = rec + (rec0 + j) * kT1024Pad;
+        const uint32_t* tc = maps + (rec0 + j) * kT1024Pad;
+        const uint16_t* ts = sig16 + (rec0 + j) * kT1024Pad;
+        uint32_t nq[9];
+#pragma unroll
+        for (int r = 0; r < 9; r++) {
+            const int k = lane + 64 * r;
+            if (k < NAE_FFT_BINS) {
+                o[k] = qs[k];
+                nq[r] = j < n_read ? qs[ts[k]] + tc[k] : qs[k];
+            }
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int r = 0; r < 9; r++) {
+            const int k = lane + 64 * r;
+            if (k < NAE_FFT_BINS) qs[k] = nq[r];
+        }
+        wave_lds_sync();
+    }
+    if (carry_out && ck == nch - 1) {
+#pragma unroll
+        for (int r = 0; r < 9; r++) {
+            const int k = lane + 64 * r;
+            if (k < NAE_FFT_BINS) carry_out[sc * kT1024Pad + k] = qs[k];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pass L3
+constexpr size_t kLockSynthWave = kPadScratchCf * sizeof(cf) + kT1024Pad * sizeof(uint32_t);
+constexpr size_t kLdsLockSynth = kLdsTablesPad + kWaves * kLockSynthWave;
+static_assert(2 * kLdsLockSynth <= 160 * 1024, "two workgroups per CU");
+
+template <bool kUnit>
+__global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src, PvParams p, long long n_items, const uint32_t* __restrict__ phase_ws,
+                                                                   OutViewD out, Tables tb)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* hann; cf *t1024, *w64, *twa;
+    lock_tables(smem, tb, hann, t1024, w64, twa);
+    const int lane = threadIdx.x & 63;
+    unsigned char* mine = smem + kLdsTablesPad + (size_t)wave_id() * kLockSynthWave;
+    cf* scratch = reinterpret_cast<cf*>(mine);
+    uint32_t* qs = reinterpret_cast<uint32_t*>(mine + kPadScratchCf * sizeof(cf));
+    const long long item = (long long)blockIdx.x * kWaves + wave_id();
+    if (item >= n_items) return;
+    const long long sc = item / p.n_tiles;
+    const int tile = (int)(item % p.n_tiles);
+    const long long s_idx = sc / p.ch;
+    const int c = (int)(sc % p.ch);
+    ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
+    PipeItem it;
+    it.sc = sc; it.s_idx = s_idx; it.c = c; it.tile = tile;
+    it.b0 = p.f_origin + (long long)tile * p.tile;
+    it.b_end = it.b0 + p.tile < p.f_stop ? it.b0 + p.tile : p.f_stop;
+    long long f_end = it.b_end + 3;                              // frames b0 .. b_end+2 feed blocks b0 .. b_end-1
+    if (f_end > p.frames) f_end = p.frames;
+    const long long f_first = it.b0 > 0 ? it.b0 - 1 : 0;        // b0 - 1 only primes Qa_{f-1}
+    float* optr = out.base + s_idx * out.ss + c * out.cs;
+    const BlockOut bo{optr, out.fs, (out.fs == 1) && ((reinterpret_cast<uintptr_t>(optr) & 15) == 0)};
+
+    // Qs in front of the tile: pass L2's record (or zero)
+    const uint32_t* b = phase_ws + (sc * p.phase_tiles + (long long)tile * p.phase_step) * kT1024Pad;
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const int k = lane + 64 * r;
+        if (k < NAE_FFT_BINS) qs[k] = p.base_zero ? 0u : b[k];
+    }
+    uint32_t qp[9], qa[9];
+#pragma unroll
+    for (int r = 0; r < 9; r++) qp[r] = 0;
+    float r0[4] = {0.0f, 0.0f, 0.0f, 0.0f}, r1[4] = {0.0f, 0.0f, 0.0f, 0.0f}, r2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    cf v[8], nyq;
+    long long s_prev = 0;
+#pragma unroll 1
+    for (long long f = f_first; f < f_end; f++) {
+        const long long s = frame_start(p, f);
+        lock_analyse<kUnit>(v, nyq, qa, in, s, hann, scratch, twa, w64, t1024, lane);
+        if (f >= it.b0) {
+            uint32_t sg[9], cc[9];
+            if (f == 0) {
+#pragma unroll
+                for (int r = 0; r < 9; r++) { sg[r] = r < 8 ? (uint32_t)(lane + 64 * r) : 512u; cc[r] = qa[r]; }
+            } else {
+                const unsigned d = (unsigned)(s - s_prev);
+                const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
+                lock_map_of_frame(v, nyq, qa, qp, d, R, scratch, lane, sg, cc);
+            }
+            uint32_t nq[9];
+#pragma unroll
+            for (int r = 0; r < 9; r++) nq[r] = qs[sg[r]] + cc[r];
+            wave_lds_sync();
+#pragma unroll
+            for (int r = 0; r < 9; r++) {
+                const int k = lane + 64 * r;
+                if (k < NAE_FFT_BINS) qs[k] = nq[r];
+            }
+            if (f == p.carry_frame) {
+#pragma unroll
+                for (int r = 0; r < 9; r++) {
+                    const int k = lane + 64 * r;
+                    if (k < NAE_FFT_BINS) p.carry_out[sc * kT1024Pad + k] = nq[r];
+                }
+            }
+            // synthesis spectrum Y = X e^{i (Qs - Qa)} in natural order, then the c2r pre-twiddle of the oracle's irfft (conjugated: inverse =
+            // conj(FFT(conj Z)) / 512)
+#pragma unroll
+            for (int r = 0; r < 8; r++) scratch[lane + 64 * r] = pipe_rotate(v[r], nq[r], qa[r]);
+            if (lane == 0) scratch[512] = pipe_rotate(nyq, nq[8], qa[8]);
+            wave_lds_sync();
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                const int k = lane + 64 * r;
+                cf Xk = scratch[k], Xm = scratch[512 - k];
+                if (k == 0) { Xk.y = 0.0f; Xm.y = 0.0f; }
+                const cf E = {0.5f * (Xk.x + Xm.x), 0.5f * (Xk.y - Xm.y)};
+                const cf D = {0.5f * (Xk.x - Xm.x), 0.5f * (Xk.y + Xm.y)};
+                const cf T = t1024[k];
+                const cf Q = {T.x * D.x + T.y * D.y, T.x * D.y - T.y * D.x};
+                v[r] = cf{E.x - Q.y, -(E.y + Q.x)};
+            }
+            wave_lds_sync();
+            fft512_pad(v, make_fft_lds(scratch, twa, w64, lane));
+            // time samples 2n, 2n+1 (n = lane + 64 r), windowed: quarter r >> 1 of the frame, offsets 2 lane + 128 (r & 1) + {0, 1}
+            float y[4][4];
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                const float2 w = *reinterpret_cast<const float2*>(hann + 2 * (lane + 64 * r));
+                y[r >> 1][2 * (r & 1)] = w.x * (v[r].x * (1.0f / 512.0f));
+                y[r >> 1][2 * (r & 1) + 1] = w.y * (-v[r].y * (1.0f / 512.0f));
+            }
+            // block f - 3 is complete: its four contributions in increasing frame order, then the gain
+            float o[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                o[i] = (r0[i] + y[0][i]) * NAE_OLA_GAIN;
+                r0[i] = r1[i] + y[1][i];
+                r1[i] = r2[i] + y[2][i];
+                r2[i] = y[3][i];
+            }
+            r3_store_block(p, it, bo, f - 3, o, lane);
+        }
+#pragma unroll
+        for (int r = 0; r < 9; r++) qp[r] = qa[r];
+        s_prev = s;
+    }
+    // frames past the last one do not exist: the blocks they would have completed get nothing more
+#pragma unroll 1
+    for (long long f = f_end > it.b0 ? f_end : it.b0; f < it.b_end + 3; f++) {
+        float o[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            o[i] = r0[i] * NAE_OLA_GAIN;
+            r0[i] = r1[i];
+            r1[i] = r2[i];
+            r2[i] = 0.0f;
+        }
+        r3_store_block(p, it, bo, f - 3, o, lane);
+    }
+}
+
+} // namespace nae
+
+// ================================================================================================ host side
+using namespace nae;
+
+static PvParams lock_params(const nae_stretch_plan& pl, size_t in_len, int ch, int tile, const nae_pv_segment* seg)
+{
+    PvParams p;
+    p.ha_q24 = pl.ha_q24;
+    p.in_len = (long long)in_len;
+    p.frames = seg ? seg->f_limit : (long long)pl.frames;
+    p.mid_len = seg ? seg->mid_limit : (long long)pl.mid_len;
+    p.d0 = pl.d0;
+    p.r_q24_0 = pl.r_q24[0];
+    p.r_q24_1 = pl.r_q24[1];
+    p.ch = ch;
+    p.tile = tile;
+    p.f_origin = seg ? seg->f_origin : 0;
+    const long long cnt = seg ? seg->f_count : (long long)pl.frames;
+    p.f_stop = p.f_origin + cnt;
+    p.n_tiles = (int)((cnt + tile - 1) / tile);
+    p.skip_from = p.n_tiles;
+    p.phase_step = 1;
+    p.phase_tiles = p.n_tiles;
+    p.carry_out = nullptr;
+    p.carry_frame = -1;
+    p.base_zero = 0;
+    return p;
+}
+
+// Shape of a locked block call (synthesis tile = pass-1 tile): one wave walks a tile, so the tiles are cut for four waves per SIMD (16 n_cu
+// stream-channel tiles) where the stream-channels alone do not give them, never shorter than 64 frames (a tile pays one priming and three tail
+// frames).  A single tile per stream-channel needs no pass L1.  pv_tile forces the tile, as for the unlocked vocoder.
+int nae_pick_pvlock_tile(nae_ctx* ctx, size_t frames, size_t n_sc)
+{
+    if (ctx->pv_tile > 0) return ctx->pv_tile;
+    const size_t n_cu = (size_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
+    if (frames == 0 || n_sc == 0) return 64;
+    size_t n_tiles = (16 * n_cu + n_sc - 1) / n_sc;
+    const size_t max_tiles = (frames + 63) / 64;
+    if (n_tiles > max_tiles) n_tiles = max_tiles;
+    if (n_tiles < 1) n_tiles = 1;
+    const size_t tile = (frames + n_tiles - 1) / n_tiles;
+    return (int)(tile < 0x40000000 ? tile : 0x40000000);
+}
+
+// the kernels here take more than 64 KiB of dynamic LDS: the limit is raised for the calling thread's device on every launch (a host call,
+// no device work; the library keeps no process-global state that could remember it)
+static int lock_lds_attr(nae_ctx* ctx, const void* kernel, size_t lds)
+{
+    (void)nae_use_device(ctx);
+    return nae_check(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(pvlock)");
+}
+
+// records [n_sc][n_tiles][520] uint32 (the unlocked layout), then the tile maps: c [n_sc][n_tiles][520] uint32, sigma [n_sc][n_tiles][520] uint16
+size_t nae_pvlock_workspace_bytes(size_t n_frames, int ch, size_t n_streams, int tile)
+{
+    const size_t recs = n_streams * ch * ((n_frames + tile - 1) / tile);
+    return recs * kT1024Pad * (2 * sizeof(uint32_t) + sizeof(uint16_t));
+}
+
+int nae_launch_pvlock_phase(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams, int tile,
+                            int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg)
+{
+    if (tile <= 0 || synth_tile < tile || synth_tile % tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
+    PvParams p = lock_params(*pl, in_len, ch, tile, seg);
+    const long long n_sc = (long long)n_streams * ch;
+    if (n_sc * p.n_tiles == 0) return NAE_OK;
+    const bool need_last = seg && seg->carry_out && !seg->carry_by_synth;
+    const int step = synth_tile / tile;
+    const int n_synth = (p.n_tiles + step - 1) / step;
+    const int n_needed = need_last ? p.n_tiles : (n_synth - 1) * step;      // maps of tiles [0, n_needed) are used
+    if (n_needed == 0) {
+        // the same base records as the unlocked pass 2 leaves: the carried phase, or zero (a lone tile reads none: base_zero)
+        hipError_t e = hipSuccess;
+        if (!(seg && seg->carry_in)) {
+            if (p.n_tiles != 1) e = hipMemsetAsync(phase_ws, 0, (size_t)n_sc * p.n_tiles * kT1024Pad * sizeof(uint32_t), ctx->stream);
+        } else if (p.n_tiles == 1)
+            e = hipMemcpyAsync(phase_ws, seg->carry_in, (size_t)n_sc * kT1024Pad * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream);
+        else
+            e = hipMemcpy2DAsync(phase_ws, (size_t)p.n_tiles * kT1024Pad * sizeof(uint32_t), seg->carry_in, kT1024Pad * sizeof(uint32_t),
+                                 kT1024Pad * sizeof(uint32_t), (size_t)n_sc, hipMemcpyDeviceToDevice, ctx->stream);
+        return nae_check(ctx, e, "phase base init");
+    }
+    const size_t n_rec = (size_t)n_sc * p.n_tiles;
+    uint32_t* maps = phase_ws + n_rec * kT1024Pad;
+    uint16_t* sig16 = reinterpret_cast<uint16_t*>(maps + n_rec * kT1024Pad);
+    Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+    {
+        PvParams pp = p;
+        pp.skip_from = n_needed;
+        const long long items = n_sc * p.n_tiles;
+        const long long grid = (items + kWaves - 1) / kWaves;
+        if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_map_kernel: grid too large");
+        const void* k = src->frame_stride == 1 ? reinterpret_cast<const void*>(pvlock_map_kernel<true>) : reinterpret_cast<const void*>(pvlock_map_kernel<false>);
+        int rc = lock_lds_attr(ctx, k, kLdsLockMap);
+        if (rc) return rc;
+        if (src->frame_stride == 1)
+            NAE_KLAUNCH(ctx, "pvlock_map_kernel", (pvlock_map_kernel<true>), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream,
+                        to_view(src), pp, items, maps, sig16, tb);
+        else
+            NAE_KLAUNCH(ctx, "pvlock_map_kernel", (pvlock_map_kernel<false>), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream,
+                        to_view(src), pp, items, maps, sig16, tb);
+        rc = nae_check(ctx, hipGetLastError(), "pvlock_map_kernel");
+        if (rc) return rc;
+    }
+    if (n_sc > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_scan_kernel: grid too large");
+    const int nch = p.n_tiles >= 256 ? kLockChunks : 1;
+    int rc = lock_lds_attr(ctx, reinterpret_cast<const void*>(pvlock_scan_kernel), nch * kLockScanWave);
+    if (rc) return rc;
+    NAE_KLAUNCH(ctx, "pvlock_scan_kernel", pvlock_scan_kernel, dim3((unsigned)n_sc), dim3(64 * nch), nch * kLockScanWave, ctx->stream, phase_ws, maps,
+                sig16, p.n_tiles, seg ? seg->carry_in : nullptr, seg ? seg->carry_out : nullptr, n_needed);
+    return nae_check(ctx, hipGetLastError(), "pvlock_scan_kernel");
+}
+
+int nae_launch_pvlock_synth(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams, int tile,
+                            int phase_tile, const uint32_t* phase_ws, const nae_sig* out, const nae_pv_segment* seg)
+{
+    if (phase_tile <= 0 || tile < phase_tile || tile % phase_tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
+    PvParams p = lock_params(*pl, in_len, ch, tile, seg);
+    const long long cnt = p.f_stop - p.f_origin;
+    p.phase_step = tile / phase_tile;
+    p.phase_tiles = (int)((cnt + phase_tile - 1) / phase_tile);
+    p.base_zero = (p.n_tiles == 1 && p.phase_tiles == 1 && !(seg && seg->carry_in)) ? 1 : 0;
+    if (seg && seg->carry_by_synth && seg->carry_out) {
+        if (p.n_tiles != 1) return nae_fail(ctx, NAE_ERR_INVALID, "carry_by_synth needs a single synthesis tile");
+        p.carry_out = seg->carry_out;
+        p.carry_frame = p.f_stop - 1;
+    }
+    const long long items = (long long)n_streams * ch * p.n_tiles;
+    if (items == 0) return NAE_OK;
+    const long long grid = (items + kWaves - 1) / kWaves;
+    if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_synth_kernel: grid too large");
+    Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+    int rc = lock_lds_attr(ctx, src->frame_stride == 1 ? reinterpret_cast<const void*>(pvlock_synth_kernel<true>)
+                                                       : reinterpret_cast<const void*>(pvlock_synth_kernel<false>), kLdsLockSynth);
+    if (rc) return rc;
+    const OutViewD ov{static_cast<float*>(out->base), (long long)out->stream_stride, (long long)out->chan_stride, (long long)out->frame_stride};
+    if (src->frame_stride == 1)
+        NAE_KLAUNCH(ctx, "pvlock_synth_kernel", (pvlock_synth_kernel<true>), dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream,
+                    to_view(src), p, items, phase_ws, ov, tb);
+    else
+        NAE_KLAUNCH(ctx, "pvlock_synth_kernel", (pvlock_synth_kernel<false>), dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream,
+                    to_view(src), p, items, phase_ws, ov, tb);
+    return nae_check(ctx, hipGetLastError(), "pvlock_synth_kernel");
+}

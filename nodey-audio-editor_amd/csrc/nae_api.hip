@@ -545,7 +545,7 @@ struct nae_mix_front {
 // (nae_debug_graph4_stages: scheduling experiments run the two from separate calls; the intermediate signal stays in the
 // context's workspace between them).
 static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
-                              const nae_sig* dst, const nae_mix_front* front, int stages = 3)
+                              const nae_sig* dst, const nae_mix_front* front, int stages = 3, bool lock = false)
 {
     if (!ctx) return NAE_ERR_INVALID;
     int rc;
@@ -610,13 +610,16 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
     if (!(stages & 2)) return NAE_OK;
     if (pl.pv_on) {
         int phase_tile = 0, fps = 1;
-        const int tile = nae_pick_pv_shape(ctx, pl.frames, n_streams * ch, &phase_tile, &fps);
-        rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_phase_workspace_bytes(pl.frames, ch, n_streams, phase_tile));
+        int tile;
+        if (lock) tile = phase_tile = nae_pick_pvlock_tile(ctx, pl.frames, n_streams * ch);
+        else tile = nae_pick_pv_shape(ctx, pl.frames, n_streams * ch, &phase_tile, &fps);
+        rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, pl.frames, ch, n_streams, phase_tile));
         if (rc) return rc;
         nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, pv_out_len, nullptr, nullptr};
-        rc = nae_launch_pv_phase(ctx, &pl, pv_src, pv_in_len, ch, n_streams, phase_tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+        rc = nae_launch_pv_phase_any(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, phase_tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
         if (rc) return rc;
-        rc = nae_launch_pv_synth(ctx, &pl, pv_src, pv_in_len, ch, n_streams, tile, phase_tile, static_cast<const uint32_t*>(ctx->ws_phase), pv_dst, &seg, fps);
+        rc = nae_launch_pv_synth_any(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, tile, phase_tile, static_cast<const uint32_t*>(ctx->ws_phase), pv_dst,
+                                     &seg, fps);
         if (rc) return rc;
     }
     if (pl.rs_on && !pl.rs_first) {
@@ -636,11 +639,28 @@ int nae_stretch_block_f32(nae_ctx* ctx, double rate, double pitch, const nae_sig
     return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr);
 }
 
+int nae_stretch_block_ex_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, const nae_sig* src, size_t in_len, int ch,
+                             size_t n_streams, const nae_sig* dst)
+{
+    if (!ctx) return NAE_ERR_INVALID;
+    if (flags & ~NAE_STRETCH_PHASE_LOCK) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
+    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0);
+}
+
 int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch,
                             size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out,
                             size_t* tile_frames)
 {
+    return nae_debug_pv_tile_phase_ex(ctx, rate, pitch, 0u, src, in_len, ch, n_streams, dst_host, dst_capacity, n_tiles_out, tile_frames);
+}
+
+int nae_debug_pv_tile_phase_ex(nae_ctx* ctx, double rate, double pitch, unsigned flags, const nae_sig* src, size_t in_len, int ch,
+                               size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out,
+                               size_t* tile_frames)
+{
     if (!ctx || !dst_host || !n_tiles_out || !tile_frames) return NAE_ERR_INVALID;
+    if (flags & ~NAE_STRETCH_PHASE_LOCK) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
+    const bool lock = (flags & NAE_STRETCH_PHASE_LOCK) != 0;
     int rc = check_sig(ctx, src, "null source view");
     if (rc) return rc;
     nae_stretch_plan pl;
@@ -653,8 +673,8 @@ int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_s
     *tile_frames = (size_t)tile;
     const size_t need = n_streams * ch * n_tiles * NAE_FFT_BINS;
     if (dst_capacity < need) return nae_fail(ctx, NAE_ERR_INVALID, "destination too small");
-    const size_t ws_bytes = nae_pv_phase_workspace_bytes(pl.frames, ch, n_streams, tile);
-    rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, ws_bytes);
+    const size_t ws_bytes = nae_pv_phase_workspace_bytes(pl.frames, ch, n_streams, tile);   // the records (the locked workspace begins with them)
+    rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, pl.frames, ch, n_streams, tile));
     if (rc) return rc;
     const nae_sig* pv_src = src;
     size_t pv_in_len = in_len;
@@ -672,7 +692,7 @@ int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_s
         pv_in_len = pl.mid_len;
     }
     nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, 0, nullptr, nullptr};
-    rc = nae_launch_pv_phase(ctx, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+    rc = nae_launch_pv_phase_any(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
     if (rc) return rc;
     std::vector<int32_t> tmp(ws_bytes / sizeof(int32_t));
     hipError_t e = hipMemcpyAsync(tmp.data(), ctx->ws_phase, ws_bytes, hipMemcpyDeviceToHost, ctx->stream);

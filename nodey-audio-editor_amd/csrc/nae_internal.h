@@ -115,6 +115,30 @@ int nae_launch_pv_phase(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig*
 int nae_launch_pv_synth(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
                         const nae_pv_segment* seg, int frames_per_step);
+// kernels_pvlock.hip: the same passes with identity phase locking (NAE_STRETCH_PHASE_LOCK); same arguments, a larger workspace
+size_t nae_pvlock_workspace_bytes(size_t n_frames, int ch, size_t n_streams, int tile);
+int nae_pick_pvlock_tile(nae_ctx* ctx, size_t frames, size_t n_sc);
+int nae_launch_pvlock_phase(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams, int tile,
+                            int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg);
+int nae_launch_pvlock_synth(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams, int tile,
+                            int phase_tile, const uint32_t* phase_ws, const nae_sig* out, const nae_pv_segment* seg);
+// the vocoder's three passes, unlocked or locked (nae_api.hip, nae_stream.hip)
+inline size_t nae_pv_workspace_bytes(bool lock, size_t n_frames, int ch, size_t n_streams, int tile)
+{
+    return lock ? nae_pvlock_workspace_bytes(n_frames, ch, n_streams, tile) : nae_pv_phase_workspace_bytes(n_frames, ch, n_streams, tile);
+}
+inline int nae_launch_pv_phase_any(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                                   int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg)
+{
+    return lock ? nae_launch_pvlock_phase(ctx, pl, src, in_len, ch, n_streams, tile, synth_tile, phase_ws, seg)
+                : nae_launch_pv_phase(ctx, pl, src, in_len, ch, n_streams, tile, synth_tile, phase_ws, seg);
+}
+inline int nae_launch_pv_synth_any(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                                   int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out, const nae_pv_segment* seg, int frames_per_step)
+{
+    return lock ? nae_launch_pvlock_synth(ctx, pl, src, in_len, ch, n_streams, tile, phase_tile, phase_ws, out, seg)
+                : nae_launch_pv_synth(ctx, pl, src, in_len, ch, n_streams, tile, phase_tile, phase_ws, out, seg, frames_per_step);
+}
 int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t src_len, int ch,
                         size_t n_streams, const float* d_tab, const nae_sig* out, size_t j_begin, size_t j_end);
 int nae_launch_mix_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* a, const nae_sig* b, float va, float vb,

@@ -15,6 +15,7 @@ struct nae_stretch {
     nae_ctx* ctx;
     int sample_rate, ch;
     double rate, pitch;
+    bool lock = false;            // NAE_STRETCH_PHASE_LOCK (nae_stretch_create_ex)
     nae_stretch_plan pl{};        // parameters (in_len = 0)
     DevFifo in;                   // interleaved input, sample-frames [in.base, in_total)
     size_t in_total = 0;
@@ -129,7 +130,7 @@ int stretch_process(nae_stretch* h)
             const bool one_tile = ctx->pv_tile <= 0 && count <= 256;
             const int tile = one_tile ? (int)count : (ctx->pv_tile > 0 ? ctx->pv_tile : 64);
             const int fps = one_tile ? 4 : 1;
-            int rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_phase_workspace_bytes(count, ch, 1, tile));
+            int rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(h->lock, count, ch, 1, tile));
             if (rc) return rc;
             for (int i = 0; i < 2; i++)
                 if (!h->carry[i] && hipMalloc((void**)&h->carry[i], (size_t)ch * kPhasePad * sizeof(uint32_t)) != hipSuccess)
@@ -141,9 +142,9 @@ int stretch_process(nae_stretch* h)
             if (rc) return rc;
             nae_sig src{h->mid.cur.p - (ptrdiff_t)h->mid.base * ch, 0, 1, (size_t)ch};
             nae_sig dst{h->out.cur.p - (ptrdiff_t)h->out.base * ch, 0, 1, (size_t)ch};
-            rc = nae_launch_pv_phase(ctx, &pl, &src, h->mid_total, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+            rc = nae_launch_pv_phase_any(ctx, h->lock, &pl, &src, h->mid_total, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
             if (rc) return rc;
-            rc = nae_launch_pv_synth(ctx, &pl, &src, h->mid_total, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
+            rc = nae_launch_pv_synth_any(ctx, h->lock, &pl, &src, h->mid_total, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
             if (rc) return rc;
             h->carry_cur ^= 1;
             h->blocks_done = B_r;
@@ -176,7 +177,7 @@ int stretch_process(nae_stretch* h)
             const bool one_tile = ctx->pv_tile <= 0 && count <= 256;
             const int tile = one_tile ? (int)count : (ctx->pv_tile > 0 ? ctx->pv_tile : 64);
             const int fps = one_tile ? 4 : 1;
-            int rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_phase_workspace_bytes(count, ch, 1, tile));
+            int rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(h->lock, count, ch, 1, tile));
             if (rc) return rc;
             for (int i = 0; i < 2; i++)
                 if (!h->carry[i] && hipMalloc((void**)&h->carry[i], (size_t)ch * kPhasePad * sizeof(uint32_t)) != hipSuccess)
@@ -212,9 +213,9 @@ int stretch_process(nae_stretch* h)
                 dst = nae_sig{h->out.cur.p - (ptrdiff_t)h->out.base * ch, 0, 1, (size_t)ch};
                 if (h->flushed) seg.mid_limit = (long long)fin.out_len;
             }
-            rc = nae_launch_pv_phase(ctx, &pl, &src, h->in_total, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+            rc = nae_launch_pv_phase_any(ctx, h->lock, &pl, &src, h->in_total, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
             if (rc) return rc;
-            rc = nae_launch_pv_synth(ctx, &pl, &src, h->in_total, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
+            rc = nae_launch_pv_synth_any(ctx, h->lock, &pl, &src, h->in_total, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
             if (rc) return rc;
             h->carry_cur ^= 1;
             h->blocks_done = B_r;
@@ -283,7 +284,13 @@ extern "C" {
 
 int nae_stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, nae_stretch** h)
 {
+    return nae_stretch_create_ex(ctx, sample_rate, channels, rate, pitch, 0u, h);
+}
+
+int nae_stretch_create_ex(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, nae_stretch** h)
+{
     if (!ctx || !h) return NAE_ERR_INVALID;
+    if (flags & ~NAE_STRETCH_PHASE_LOCK) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
     (void)nae_use_device(ctx);
     *h = nullptr;
     // audio-velocity.cpp:371-379 rejects rates outside 8..48 kHz for SoundTouch; the vocoder has no such
@@ -300,6 +307,7 @@ int nae_stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rate, 
     s->ch = channels;
     s->rate = rate;
     s->pitch = pitch;
+    s->lock = (flags & NAE_STRETCH_PHASE_LOCK) != 0;
     s->pl = pl;
     *h = s;
     return NAE_OK;

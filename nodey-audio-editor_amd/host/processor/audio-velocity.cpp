@@ -27,6 +27,18 @@ namespace processor
 		return default_stretch_algorithm();   // no key: a project saved by the reference
 	}
 
+	bool phase_lock_from_json(const Json::Value& value, const char* node_name)
+	{
+		if (!value.isMember("phase_lock")) return false;
+		if (!value["phase_lock"].isBool())
+			throw infra::Processor::Runtime_error(
+				"Failed to deserialize JSON file",
+				std::string(node_name) + " failed to serialize the JSON input because of missing or invalid fields.",
+				"Wrong field: phase_lock"
+			);
+		return value["phase_lock"].asBool();
+	}
+
 	namespace
 	{
 		std::vector<infra::Processor::Pin_attribute> io_pins()
@@ -158,12 +170,13 @@ namespace processor
 				if (st) nae_wsola_destroy(st);
 			}
 			bool open() const { return pv != nullptr || st != nullptr; }
-			void create(Stretch_algorithm algo, int sample_rate, int channels, float velocity, float pitch)
+			void create(Stretch_algorithm algo, bool phase_lock, int sample_rate, int channels, float velocity, float pitch)
 			{
-				if (algo == Stretch_algorithm::Soundtouch)
+				if (algo == Stretch_algorithm::Soundtouch)   // (phase_lock is a vocoder option: the WSOLA chain has no phases to lock)
 					gpu::check(nae_wsola_create(gpu::context(), sample_rate, channels, velocity, pitch, &st), "nae_wsola_create");
 				else
-					gpu::check(nae_stretch_create(gpu::context(), sample_rate, channels, velocity, pitch, &pv), "nae_stretch_create");
+					gpu::check(nae_stretch_create_ex(gpu::context(), sample_rate, channels, velocity, pitch, phase_lock ? NAE_STRETCH_PHASE_LOCK : 0u, &pv),
+							   "nae_stretch_create_ex");
 			}
 			size_t available() const { return pv ? nae_stretch_available(pv) : nae_wsola_available(st); }
 			void put(const float* samples, size_t n)
@@ -182,7 +195,7 @@ namespace processor
 			const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
 			const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
 			const std::atomic<bool>& stop_token, float velocity, float pitch, const std::string& processor_name,
-			Stretch_algorithm algorithm, Batch_stats& batch_stats
+			Stretch_algorithm algorithm, bool phase_lock, Batch_stats& batch_stats
 		)
 		{
 			gpu::Node node;  // this node's context (own stream; device: gpu::pick_device): first local, destroyed last
@@ -281,7 +294,7 @@ namespace processor
 									infra::fmt("%d requires a sample rate between 8000 and 48000 Hz.", frame->sample_rate),
 									infra::fmt("Sample rate: %d", frame->sample_rate)
 								);
-							soundtouch.create(algorithm, frame->sample_rate, frame->ch_layout.nb_channels, velocity, pitch);
+							soundtouch.create(algorithm, phase_lock, frame->sample_rate, frame->ch_layout.nb_channels, velocity, pitch);
 							channel_count = frame->ch_layout.nb_channels;
 							time_seconds = frame->pts * av_q2d(frame->time_base);
 							sample_rate = frame->sample_rate;
@@ -350,7 +363,7 @@ namespace processor
 	)
 	{
 		stretch_process_payload(input, output, stop_token, velocity, keep_pitch ? 1 / velocity : 1, get_processor_info().display_name,
-								algorithm, batch_stats);  // :452-459
+								algorithm, phase_lock, batch_stats);  // :452-459
 	}
 
 	Json::Value Velocity_modifier::serialize() const
@@ -359,6 +372,7 @@ namespace processor
 		value["velocity"] = velocity;
 		value["keep_pitch"] = keep_pitch;
 		if (algorithm != default_stretch_algorithm()) value["algorithm"] = algorithm_name(algorithm);
+		if (phase_lock) value["phase_lock"] = true;
 		return value;
 	}
 
@@ -367,6 +381,7 @@ namespace processor
 		if (value.isMember("velocity") && value["velocity"].isDouble()) velocity = value["velocity"].asFloat();
 		if (value.isMember("keep_pitch") && value["keep_pitch"].isBool()) keep_pitch = value["keep_pitch"].asBool();
 		algorithm = algorithm_from_json(value);
+		phase_lock = phase_lock_from_json(value, "Velocity_modifier");
 	}
 
 	// ------------------------------------------------------------------------------------------ Pitch_modifier
@@ -384,7 +399,7 @@ namespace processor
 	)
 	{
 		stretch_process_payload(input, output, stop_token, 1, std::pow(2.0f, pitch / 12.0f), get_processor_info().display_name,
-								algorithm, batch_stats);  // :469-476
+								algorithm, phase_lock, batch_stats);  // :469-476
 	}
 
 	Json::Value Pitch_modifier::serialize() const
@@ -392,12 +407,14 @@ namespace processor
 		Json::Value value;
 		value["pitch"] = pitch;
 		if (algorithm != default_stretch_algorithm()) value["algorithm"] = algorithm_name(algorithm);
+		if (phase_lock) value["phase_lock"] = true;
 		return value;
 	}
 	void Pitch_modifier::deserialize(const Json::Value& value)
 	{
 		if (value.isMember("pitch") && value["pitch"].isDouble()) pitch = value["pitch"].asFloat();
 		algorithm = algorithm_from_json(value);
+		phase_lock = phase_lock_from_json(value, "Pitch_modifier");
 	}
 
 	// ------------------------------------------------------------------------------------------ Audio_spectrum

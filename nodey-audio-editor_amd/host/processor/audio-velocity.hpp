@@ -17,12 +17,16 @@ namespace processor
 	Stretch_algorithm default_stretch_algorithm();
 	void set_default_stretch_algorithm(Stretch_algorithm a);
 	Stretch_algorithm algorithm_from_json(const Json::Value& value);
+	// "phase_lock" (bool, optional): identity phase locking of the vocoder (NAE_STRETCH_PHASE_LOCK).  No key: false; a value that is not a bool:
+	// Runtime_error "Wrong field: phase_lock"; written back only when true.  With "algorithm": "soundtouch" the key is kept and has no effect.
+	bool phase_lock_from_json(const Json::Value& value, const char* node_name);
 
 	class Velocity_modifier : public infra::Processor
 	{
 		float velocity = 1;
 		bool keep_pitch = false;
 		Stretch_algorithm algorithm = default_stretch_algorithm();
+		bool phase_lock = false;
 
 	  public:
 
@@ -39,7 +43,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override;            // velocity, keep_pitch (audio-velocity.cpp:479-485)
+		Json::Value serialize() const override;            // velocity, keep_pitch (audio-velocity.cpp:479-485); algorithm, phase_lock when not the default
 		void deserialize(const Json::Value& value) override;  // :487-493
 	};
 
@@ -47,6 +51,7 @@ namespace processor
 	{
 		float pitch = 0;  // semitones
 		Stretch_algorithm algorithm = default_stretch_algorithm();
+		bool phase_lock = false;
 
 	  public:
 
@@ -63,7 +68,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override;            // pitch (:495-500)
+		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock when not the default
 		void deserialize(const Json::Value& value) override;  // :502-505
 	};
 
