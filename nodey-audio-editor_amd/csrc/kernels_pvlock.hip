@@ -10,7 +10,8 @@
 //   pass L3 (pvlock_synth_kernel) one wave per synthesis tile: from the recorded Qs it walks its frames forward — re-analysis, M_f applied to the
 //                                 Qs vector in LDS, rotation, inverse FFT, window, overlap-add in increasing frame order — and stores its blocks.
 // Every integer is exact, so any tiling gives the same bits; the samples follow the oracle's tolerance path (|X| e^{i Qs}, inverse FFT, overlap-add).
-// The default (unlocked) path does not run any of this: its kernels, launchers and results are untouched.
+// The default (unlocked) path runs none of these kernels.  The host decisions of both modes (parameters, records needed, base records, synthesis
+// fields, workspace layout) are kernels_stft.hip's nae_launch_pv_phase / nae_launch_pv_synth; the launchers here only launch.
 #include "pv_roles.h"
 
 namespace nae {
@@ -123,26 +124,14 @@ constexpr size_t kLockMapWave = kPadScratchCf * sizeof(cf) + kT1024Pad * (sizeof
 constexpr size_t kLdsLockMap = kLdsTablesPad + kWaves * kLockMapWave;
 static_assert(2 * kLdsLockMap <= 160 * 1024, "two workgroups per CU");
 
-__device__ __forceinline__ void lock_tables(unsigned char* smem, const Tables& tb, float*& hann, cf*& t1024, cf*& w64, cf*& twa)
-{
-    hann = reinterpret_cast<float*>(smem);
-    t1024 = reinterpret_cast<cf*>(smem + NAE_FFT_N * sizeof(float));
-    w64 = t1024 + kT1024Pad;
-    twa = w64 + 64;
-    for (int i = threadIdx.x; i < NAE_FFT_N; i += blockDim.x) hann[i] = tb.hann[i];
-    for (int i = threadIdx.x; i < NAE_FFT_BINS; i += blockDim.x) t1024[i] = tb.t1024[i];
-    if (threadIdx.x < 64) w64[threadIdx.x] = tb.w512[8 * (threadIdx.x >> 3) * (threadIdx.x & 7)];
-    fill_twa(twa, tb.w512, threadIdx.x, blockDim.x);
-    __syncthreads();
-}
-
 template <bool kUnit>
 __global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, PvParams p, long long n_items, uint32_t* __restrict__ maps,
                                                                  uint16_t* __restrict__ sig16, Tables tb)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* hann; cf *t1024, *w64, *twa;
-    lock_tables(smem, tb, hann, t1024, w64, twa);
+    stage_tables(smem, tb, blockDim.x, hann, t1024, w64, twa);
+    __syncthreads();
     const int lane = threadIdx.x & 63;
     unsigned char* mine = smem + kLdsTablesPad + (size_t)wave_id() * kLockMapWave;
     cf* scratch = reinterpret_cast<cf*>(mine);
@@ -327,7 +316,8 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* hann; cf *t1024, *w64, *twa;
-    lock_tables(smem, tb, hann, t1024, w64, twa);
+    stage_tables(smem, tb, blockDim.x, hann, t1024, w64, twa);
+    __syncthreads();
     const int lane = threadIdx.x & 63;
     unsigned char* mine = smem + kLdsTablesPad + (size_t)wave_id() * kLockSynthWave;
     cf* scratch = reinterpret_cast<cf*>(mine);
@@ -454,31 +444,6 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
 // ================================================================================================ host side
 using namespace nae;
 
-static PvParams lock_params(const nae_stretch_plan& pl, size_t in_len, int ch, int tile, const nae_pv_segment* seg)
-{
-    PvParams p;
-    p.ha_q24 = pl.ha_q24;
-    p.in_len = (long long)in_len;
-    p.frames = seg ? seg->f_limit : (long long)pl.frames;
-    p.mid_len = seg ? seg->mid_limit : (long long)pl.mid_len;
-    p.d0 = pl.d0;
-    p.r_q24_0 = pl.r_q24[0];
-    p.r_q24_1 = pl.r_q24[1];
-    p.ch = ch;
-    p.tile = tile;
-    p.f_origin = seg ? seg->f_origin : 0;
-    const long long cnt = seg ? seg->f_count : (long long)pl.frames;
-    p.f_stop = p.f_origin + cnt;
-    p.n_tiles = (int)((cnt + tile - 1) / tile);
-    p.skip_from = p.n_tiles;
-    p.phase_step = 1;
-    p.phase_tiles = p.n_tiles;
-    p.carry_out = nullptr;
-    p.carry_frame = -1;
-    p.base_zero = 0;
-    return p;
-}
-
 // Shape of a locked block call (synthesis tile = pass-1 tile): one wave walks a tile, so the tiles are cut for four waves per SIMD (16 n_cu
 // stream-channel tiles) where the stream-channels alone do not give them, never shorter than 64 frames (a tile pays one priming and three tail
 // frames).  A single tile per stream-channel needs no pass L1.  pv_tile forces the tile, as for the unlocked vocoder.
@@ -495,103 +460,55 @@ int nae_pick_pvlock_tile(nae_ctx* ctx, size_t frames, size_t n_sc)
     return (int)(tile < 0x40000000 ? tile : 0x40000000);
 }
 
-// the kernels here take more than 64 KiB of dynamic LDS: the limit is raised for the calling thread's device on every launch (a host call,
-// no device work; the library keeps no process-global state that could remember it)
-static int lock_lds_attr(nae_ctx* ctx, const void* kernel, size_t lds)
-{
-    (void)nae_use_device(ctx);
-    return nae_check(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(pvlock)");
-}
+// the kernels here take more than 64 KiB of dynamic LDS: the attribute is set as for the vocoder pipeline (nae_pv_lds_attr), once per context
+// and kernel, the scan kernel at its largest size
+constexpr unsigned kAttrLockMap = 1u << 12, kAttrLockScan = 1u << 13, kAttrLockSynth = 1u << 14;   // nae_ctx::pv_attr_done (pipeline: bits 0-10)
 
-// records [n_sc][n_tiles][520] uint32 (the unlocked layout), then the tile maps: c [n_sc][n_tiles][520] uint32, sigma [n_sc][n_tiles][520] uint16
-size_t nae_pvlock_workspace_bytes(size_t n_frames, int ch, size_t n_streams, int tile)
+int nae_launch_pvlock_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
+                            uint32_t* phase_ws, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out)
 {
-    const size_t recs = n_streams * ch * ((n_frames + tile - 1) / tile);
-    return recs * kT1024Pad * (2 * sizeof(uint32_t) + sizeof(uint16_t));
-}
-
-int nae_launch_pvlock_phase(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams, int tile,
-                            int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg)
-{
-    if (tile <= 0 || synth_tile < tile || synth_tile % tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
-    PvParams p = lock_params(*pl, in_len, ch, tile, seg);
-    const long long n_sc = (long long)n_streams * ch;
-    if (n_sc * p.n_tiles == 0) return NAE_OK;
-    const bool need_last = seg && seg->carry_out && !seg->carry_by_synth;
-    const int step = synth_tile / tile;
-    const int n_synth = (p.n_tiles + step - 1) / step;
-    const int n_needed = need_last ? p.n_tiles : (n_synth - 1) * step;      // maps of tiles [0, n_needed) are used
-    if (n_needed == 0) {
-        // the same base records as the unlocked pass 2 leaves: the carried phase, or zero (a lone tile reads none: base_zero)
-        hipError_t e = hipSuccess;
-        if (!(seg && seg->carry_in)) {
-            if (p.n_tiles != 1) e = hipMemsetAsync(phase_ws, 0, (size_t)n_sc * p.n_tiles * kT1024Pad * sizeof(uint32_t), ctx->stream);
-        } else if (p.n_tiles == 1)
-            e = hipMemcpyAsync(phase_ws, seg->carry_in, (size_t)n_sc * kT1024Pad * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream);
-        else
-            e = hipMemcpy2DAsync(phase_ws, (size_t)p.n_tiles * kT1024Pad * sizeof(uint32_t), seg->carry_in, kT1024Pad * sizeof(uint32_t),
-                                 kT1024Pad * sizeof(uint32_t), (size_t)n_sc, hipMemcpyDeviceToDevice, ctx->stream);
-        return nae_check(ctx, e, "phase base init");
-    }
-    const size_t n_rec = (size_t)n_sc * p.n_tiles;
-    uint32_t* maps = phase_ws + n_rec * kT1024Pad;
-    uint16_t* sig16 = reinterpret_cast<uint16_t*>(maps + n_rec * kT1024Pad);
-    Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+    const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
     {
-        PvParams pp = p;
-        pp.skip_from = n_needed;
         const long long items = n_sc * p.n_tiles;
         const long long grid = (items + kWaves - 1) / kWaves;
         if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_map_kernel: grid too large");
-        const void* k = src->frame_stride == 1 ? reinterpret_cast<const void*>(pvlock_map_kernel<true>) : reinterpret_cast<const void*>(pvlock_map_kernel<false>);
-        int rc = lock_lds_attr(ctx, k, kLdsLockMap);
+        int rc = nae_pv_lds_attr(ctx, kAttrLockMap, kLdsLockMap, reinterpret_cast<const void*>(pvlock_map_kernel<true>),
+                                 reinterpret_cast<const void*>(pvlock_map_kernel<false>));
         if (rc) return rc;
-        if (src->frame_stride == 1)
+        if (unit_stride)
             NAE_KLAUNCH(ctx, "pvlock_map_kernel", (pvlock_map_kernel<true>), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream,
-                        to_view(src), pp, items, maps, sig16, tb);
+                        src, p, items, maps, sig16, tb);
         else
             NAE_KLAUNCH(ctx, "pvlock_map_kernel", (pvlock_map_kernel<false>), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream,
-                        to_view(src), pp, items, maps, sig16, tb);
+                        src, p, items, maps, sig16, tb);
         rc = nae_check(ctx, hipGetLastError(), "pvlock_map_kernel");
         if (rc) return rc;
     }
     if (n_sc > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_scan_kernel: grid too large");
-    const int nch = p.n_tiles >= 256 ? kLockChunks : 1;
-    int rc = lock_lds_attr(ctx, reinterpret_cast<const void*>(pvlock_scan_kernel), nch * kLockScanWave);
+    int rc = nae_pv_lds_attr(ctx, kAttrLockScan, kLockChunks * kLockScanWave, reinterpret_cast<const void*>(pvlock_scan_kernel));
     if (rc) return rc;
+    const int nch = p.n_tiles >= 256 ? kLockChunks : 1;
     NAE_KLAUNCH(ctx, "pvlock_scan_kernel", pvlock_scan_kernel, dim3((unsigned)n_sc), dim3(64 * nch), nch * kLockScanWave, ctx->stream, phase_ws, maps,
-                sig16, p.n_tiles, seg ? seg->carry_in : nullptr, seg ? seg->carry_out : nullptr, n_needed);
+                sig16, p.n_tiles, carry_in, carry_out, n_needed);
     return nae_check(ctx, hipGetLastError(), "pvlock_scan_kernel");
 }
 
-int nae_launch_pvlock_synth(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams, int tile,
-                            int phase_tile, const uint32_t* phase_ws, const nae_sig* out, const nae_pv_segment* seg)
+int nae_launch_pvlock_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
+                            const OutViewD& out)
 {
-    if (phase_tile <= 0 || tile < phase_tile || tile % phase_tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
-    PvParams p = lock_params(*pl, in_len, ch, tile, seg);
-    const long long cnt = p.f_stop - p.f_origin;
-    p.phase_step = tile / phase_tile;
-    p.phase_tiles = (int)((cnt + phase_tile - 1) / phase_tile);
-    p.base_zero = (p.n_tiles == 1 && p.phase_tiles == 1 && !(seg && seg->carry_in)) ? 1 : 0;
-    if (seg && seg->carry_by_synth && seg->carry_out) {
-        if (p.n_tiles != 1) return nae_fail(ctx, NAE_ERR_INVALID, "carry_by_synth needs a single synthesis tile");
-        p.carry_out = seg->carry_out;
-        p.carry_frame = p.f_stop - 1;
-    }
-    const long long items = (long long)n_streams * ch * p.n_tiles;
+    const long long items = n_sc * p.n_tiles;
     if (items == 0) return NAE_OK;
     const long long grid = (items + kWaves - 1) / kWaves;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_synth_kernel: grid too large");
-    Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
-    int rc = lock_lds_attr(ctx, src->frame_stride == 1 ? reinterpret_cast<const void*>(pvlock_synth_kernel<true>)
-                                                       : reinterpret_cast<const void*>(pvlock_synth_kernel<false>), kLdsLockSynth);
+    const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+    int rc = nae_pv_lds_attr(ctx, kAttrLockSynth, kLdsLockSynth, reinterpret_cast<const void*>(pvlock_synth_kernel<true>),
+                             reinterpret_cast<const void*>(pvlock_synth_kernel<false>));
     if (rc) return rc;
-    const OutViewD ov{static_cast<float*>(out->base), (long long)out->stream_stride, (long long)out->chan_stride, (long long)out->frame_stride};
-    if (src->frame_stride == 1)
+    if (unit_stride)
         NAE_KLAUNCH(ctx, "pvlock_synth_kernel", (pvlock_synth_kernel<true>), dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream,
-                    to_view(src), p, items, phase_ws, ov, tb);
+                    src, p, items, phase_ws, out, tb);
     else
         NAE_KLAUNCH(ctx, "pvlock_synth_kernel", (pvlock_synth_kernel<false>), dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream,
-                    to_view(src), p, items, phase_ws, ov, tb);
+                    src, p, items, phase_ws, out, tb);
     return nae_check(ctx, hipGetLastError(), "pvlock_synth_kernel");
 }

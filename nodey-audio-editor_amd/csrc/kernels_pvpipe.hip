@@ -96,14 +96,8 @@ __global__ __launch_bounds__(kPipeThreads, kRich ? 4 : 8) void pv_pipe_kernel(Si
     constexpr int kDepth = kG == 1 ? 2 : 4;                  // steps a frame needs beyond its R1 step
     constexpr int kGens = pipe_ola_gens(kG);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* hann = reinterpret_cast<float*>(smem);
-    cf* t1024 = reinterpret_cast<cf*>(smem + NAE_FFT_N * sizeof(float));
-    cf* w64 = t1024 + kT1024Pad;
-    cf* twa = w64 + 64;
-    for (int i = threadIdx.x; i < NAE_FFT_N; i += kPipeThreads) hann[i] = tb.hann[i];
-    for (int i = threadIdx.x; i < NAE_FFT_BINS; i += kPipeThreads) t1024[i] = tb.t1024[i];
-    if (threadIdx.x < 64) w64[threadIdx.x] = tb.w512[8 * (threadIdx.x >> 3) * (threadIdx.x & 7)];
-    fill_twa(twa, tb.w512, threadIdx.x, kPipeThreads);
+    float* hann; cf *t1024, *w64, *twa;
+    stage_tables(smem, tb, kPipeThreads, hann, t1024, w64, twa);
     __shared__ int s_slot;
     if (kG == 1 && threadIdx.x == 0) s_slot = pipe_cu_arrival(g_cu_arrivals);
     __syncthreads();
@@ -601,19 +595,13 @@ __global__ __launch_bounds__(kPipeThreads, 4) void pv_flow_kernel(SigViewD src, 
 
 using namespace nae;
 
-// one launch of one instantiation.  More than 64 KiB of dynamic LDS needs the attribute: once per instantiation and DEVICE, so the flag lives in the
-// context (no process-global launch state: contexts of different devices, or driven by different threads, do not share it)
+// one launch of one instantiation (attr_bit: its bit of nae_ctx::pv_attr_done, bits 0-10)
 template <typename K>
 static int pv_launch(nae_ctx* ctx, const char* name, K kernel_unit, K kernel_strided, unsigned attr_bit, size_t lds, unsigned groups, const SigViewD& src,
                      const PvParams& p, long long n_sc, const uint32_t* phase_ws, const OutViewD& out, bool unit_stride)
 {
-    if (!(ctx->pv_attr_done & attr_bit)) {
-        (void)nae_use_device(ctx);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_unit), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_strided), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return nae_check(ctx, e, "hipFuncSetAttribute(vocoder pipeline)");
-        ctx->pv_attr_done |= attr_bit;
-    }
+    const int rc = nae_pv_lds_attr(ctx, attr_bit, lds, reinterpret_cast<const void*>(kernel_unit), reinterpret_cast<const void*>(kernel_strided));
+    if (rc) return rc;
     const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
     NAE_KLAUNCH(ctx, name, unit_stride ? kernel_unit : kernel_strided, dim3(groups), dim3(kPipeThreads), lds, ctx->stream, src, p, n_sc, phase_ws, out, tb);
     return nae_check(ctx, hipGetLastError(), name);

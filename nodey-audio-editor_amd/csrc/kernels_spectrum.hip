@@ -23,14 +23,8 @@ __global__ __launch_bounds__(kThreads, 4) void spectrum_kernel(SigViewD src, lon
                                                            long long dst_ss, Tables tb)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* hann = reinterpret_cast<float*>(smem);
-    cf* t1024 = reinterpret_cast<cf*>(smem + NAE_FFT_N * sizeof(float));
-    cf* w64 = t1024 + kT1024Pad;
-    cf* twa = w64 + 64;
-    for (int i = threadIdx.x; i < NAE_FFT_N; i += kThreads) hann[i] = tb.hann[i];
-    for (int i = threadIdx.x; i < NAE_FFT_BINS; i += kThreads) t1024[i] = tb.t1024[i];
-    if (threadIdx.x < 64) w64[threadIdx.x] = tb.w512[8 * (threadIdx.x >> 3) * (threadIdx.x & 7)];
-    fill_twa(twa, tb.w512, threadIdx.x, kThreads);
+    float* hann; cf *t1024, *w64, *twa;
+    stage_tables(smem, tb, kThreads, hann, t1024, w64, twa);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     cf* scratch = reinterpret_cast<cf*>(smem + kLdsTablesPad) + wave_id() * kPadScratchCf;
@@ -98,14 +92,8 @@ __global__ __launch_bounds__(kThreads, 4) void spectrum_stereo_kernel(const floa
                                                                      float* __restrict__ dst, long long dst_ss, Tables tb)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* hann = reinterpret_cast<float*>(smem);
-    cf* t1024 = reinterpret_cast<cf*>(smem + NAE_FFT_N * sizeof(float));
-    cf* w64 = t1024 + kT1024Pad;
-    cf* twa = w64 + 64;
-    for (int i = threadIdx.x; i < NAE_FFT_N; i += kThreads) hann[i] = tb.hann[i];
-    for (int i = threadIdx.x; i < NAE_FFT_BINS; i += kThreads) t1024[i] = tb.t1024[i];
-    if (threadIdx.x < 64) w64[threadIdx.x] = tb.w512[8 * (threadIdx.x >> 3) * (threadIdx.x & 7)];
-    fill_twa(twa, tb.w512, threadIdx.x, kThreads);
+    float* hann; cf *t1024, *w64, *twa;
+    stage_tables(smem, tb, kThreads, hann, t1024, w64, twa);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     cf* scratch = reinterpret_cast<cf*>(smem + kLdsTablesPad) + wave_id() * kPadScratchCf;

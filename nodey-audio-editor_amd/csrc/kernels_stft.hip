@@ -27,14 +27,8 @@ __global__ __launch_bounds__(kThreads, 6) void pv_phase_kernel(SigViewD src, PvP
                                                               uint32_t* __restrict__ sums, Tables tb)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* hann = reinterpret_cast<float*>(smem);
-    cf* t1024 = reinterpret_cast<cf*>(smem + NAE_FFT_N * sizeof(float));
-    cf* w64 = t1024 + kT1024Pad;
-    cf* twa = w64 + 64;
-    for (int i = threadIdx.x; i < NAE_FFT_N; i += kThreads) hann[i] = tb.hann[i];
-    for (int i = threadIdx.x; i < NAE_FFT_BINS; i += kThreads) t1024[i] = tb.t1024[i];
-    if (threadIdx.x < 64) w64[threadIdx.x] = tb.w512[8 * (threadIdx.x >> 3) * (threadIdx.x & 7)];
-    fill_twa(twa, tb.w512, threadIdx.x, kThreads);
+    float* hann; cf *t1024, *w64, *twa;
+    stage_tables(smem, tb, kThreads, hann, t1024, w64, twa);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     cf* scratch = reinterpret_cast<cf*>(smem + kLdsTablesPad) + wave_id() * kPadScratchCf;
@@ -615,43 +609,20 @@ static inline OutViewD to_out(const nae_sig* s)
                     (long long)s->frame_stride};
 }
 
-static PvParams make_pv_params(const nae_stretch_plan& pl, size_t in_len, int ch, int tile, const nae_pv_segment* seg)
+// records [n_sc][n_tiles][520] uint32 (the exclusive tile-prefix phases); locked, then the tile maps: c [n_sc][n_tiles][520] uint32,
+// sigma [n_sc][n_tiles][520] uint16
+size_t nae_pv_workspace_bytes(bool lock, size_t n_frames, int ch, size_t n_streams, int tile)
 {
-    PvParams p;
-    p.ha_q24 = pl.ha_q24;
-    p.in_len = (long long)in_len;
-    p.frames = seg ? seg->f_limit : (long long)pl.frames;
-    p.mid_len = seg ? seg->mid_limit : (long long)pl.mid_len;
-    p.d0 = pl.d0;
-    p.r_q24_0 = pl.r_q24[0];
-    p.r_q24_1 = pl.r_q24[1];
-    p.ch = ch;
-    p.tile = tile;
-    p.f_origin = seg ? seg->f_origin : 0;
-    const long long cnt = seg ? seg->f_count : (long long)pl.frames;
-    p.f_stop = p.f_origin + cnt;
-    p.n_tiles = (int)((cnt + tile - 1) / tile);
-    p.skip_from = p.n_tiles;
-    p.phase_step = 1;
-    p.phase_tiles = p.n_tiles;
-    p.carry_out = nullptr;
-    p.carry_frame = -1;
-    p.base_zero = 0;
-    return p;
-}
-
-size_t nae_pv_phase_workspace_bytes(size_t n_frames, int ch, size_t n_streams, int tile)
-{
-    const size_t n_tiles = (n_frames + tile - 1) / tile;
-    return n_streams * ch * n_tiles * kT1024Pad * sizeof(uint32_t);
+    const size_t recs = n_streams * ch * ((n_frames + tile - 1) / tile);
+    return recs * kT1024Pad * (lock ? 2 * sizeof(uint32_t) + sizeof(uint16_t) : sizeof(uint32_t));
 }
 
 // pass 1 + 2: leaves the exclusive tile-prefix phases in `phase_ws` (one record per pass-1 tile).
 // Pass 1 may use shorter tiles than pass 3 (`synth_tile` = a multiple of `tile`): its waves are independent, so short
 // tiles keep the chip full on small batches, while pass 3 wants few long tiles (each re-analyses its frames).
-// Only the sums in front of the last synthesis tile are needed, unless the phase behind the segment is carried on (a
+// Only the sums (locked: maps) in front of the last synthesis tile are needed, unless the phase behind the segment is carried on (a
 // continued stream): nothing at all when the stream-channel is a single synthesis tile.
-int nae_launch_pv_phase(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
+int nae_launch_pv_phase(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg)
 {
     if (tile <= 0 || synth_tile < tile || synth_tile % tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
@@ -661,53 +632,59 @@ int nae_launch_pv_phase(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig*
     const bool need_last = seg && seg->carry_out && !seg->carry_by_synth;
     const int step = synth_tile / tile;
     const int n_synth = (p.n_tiles + step - 1) / step;
-    const int n_needed = need_last ? p.n_tiles : (n_synth - 1) * step;      // sums of tiles [0, n_needed) are used
-    Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+    const int n_needed = need_last ? p.n_tiles : (n_synth - 1) * step;      // sums (maps) of tiles [0, n_needed) are used
+    const uint32_t* carry_in = seg ? seg->carry_in : nullptr;
+    uint32_t* carry_out = seg ? seg->carry_out : nullptr;
     if (n_needed == 0) {
         // base phase of the only synthesis tile (record 0 of each stream-channel): the carried phase, or zero
         hipError_t e = hipSuccess;
-        if (!(seg && seg->carry_in)) {
+        if (!carry_in) {
             // nothing carried in and a single synthesis tile: pass 3 starts from zero by itself (PvParams::base_zero) — no memset launch
             if (p.n_tiles != 1) e = hipMemsetAsync(phase_ws, 0, (size_t)n_sc * p.n_tiles * kT1024Pad * sizeof(uint32_t), ctx->stream);
         }
         else if (p.n_tiles == 1)
-            e = hipMemcpyAsync(phase_ws, seg->carry_in, (size_t)n_sc * kT1024Pad * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream);
+            e = hipMemcpyAsync(phase_ws, carry_in, (size_t)n_sc * kT1024Pad * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream);
         else
-            e = hipMemcpy2DAsync(phase_ws, (size_t)p.n_tiles * kT1024Pad * sizeof(uint32_t), seg->carry_in, kT1024Pad * sizeof(uint32_t),
+            e = hipMemcpy2DAsync(phase_ws, (size_t)p.n_tiles * kT1024Pad * sizeof(uint32_t), carry_in, kT1024Pad * sizeof(uint32_t),
                                  kT1024Pad * sizeof(uint32_t), (size_t)n_sc, hipMemcpyDeviceToDevice, ctx->stream);
         return nae_check(ctx, e, "phase base init");
     }
+    p.skip_from = n_needed;                   // pass 1 skips the tiles whose sums are not needed
+    if (lock) {
+        const size_t n_rec = (size_t)n_sc * p.n_tiles;
+        uint32_t* maps = phase_ws + n_rec * kT1024Pad;
+        uint16_t* sig16 = reinterpret_cast<uint16_t*>(maps + n_rec * kT1024Pad);
+        return nae_launch_pvlock_phase(ctx, p, to_view(src), n_sc, src->frame_stride == 1, n_needed, phase_ws, maps, sig16, carry_in, carry_out);
+    }
+    Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
     {
-        // items are (stream-channel, tile) with tile fastest; the kernel skips the tiles whose sums are not needed
-        PvParams pp = p;
-        pp.skip_from = n_needed;
+        // items are (stream-channel, tile) with tile fastest
         const long long items = n_sc * p.n_tiles;
         const unsigned grid = (unsigned)((items + kWaves - 1) / kWaves);
         const size_t lds = kLdsPhase;
         if (src->frame_stride == 1)
             NAE_KLAUNCH(ctx, "pv_phase_kernel", (pv_phase_kernel<true>), dim3(grid), dim3(kThreads), lds, ctx->stream,
-                        to_view(src), pp, items, phase_ws, tb);
+                        to_view(src), p, items, phase_ws, tb);
         else
             NAE_KLAUNCH(ctx, "pv_phase_kernel", (pv_phase_kernel<false>), dim3(grid), dim3(kThreads), lds, ctx->stream,
-                        to_view(src), pp, items, phase_ws, tb);
+                        to_view(src), p, items, phase_ws, tb);
         int rc = nae_check(ctx, hipGetLastError(), "pv_phase_kernel");
         if (rc) return rc;
     }
-    {
-        if (p.n_tiles >= 256 && n_sc * 9 <= 0x7fffffffll) {
-            NAE_KLAUNCH(ctx, "pv_scan_kernel", pv_scan_chunked_kernel, dim3((unsigned)(n_sc * 9)), dim3(64 * kScanChunks), 0, ctx->stream, phase_ws, n_sc, p.n_tiles,
-                        seg ? seg->carry_in : nullptr, seg ? seg->carry_out : nullptr, n_needed);
-            return nae_check(ctx, hipGetLastError(), "pv_scan_kernel");
-        }
-        const long long threads = n_sc * kT1024Pad;
-        const unsigned grid = (unsigned)((threads + 255) / 256);
-        NAE_KLAUNCH(ctx, "pv_scan_kernel", pv_scan_kernel, dim3(grid), dim3(256), 0, ctx->stream, phase_ws, n_sc, p.n_tiles,
-                    seg ? seg->carry_in : nullptr, seg ? seg->carry_out : nullptr, n_needed);
+    if (p.n_tiles >= 256 && n_sc * 9 <= 0x7fffffffll) {
+        NAE_KLAUNCH(ctx, "pv_scan_kernel", pv_scan_chunked_kernel, dim3((unsigned)(n_sc * 9)), dim3(64 * kScanChunks), 0, ctx->stream, phase_ws, n_sc, p.n_tiles,
+                    carry_in, carry_out, n_needed);
         return nae_check(ctx, hipGetLastError(), "pv_scan_kernel");
     }
+    const long long threads = n_sc * kT1024Pad;
+    const unsigned grid = (unsigned)((threads + 255) / 256);
+    NAE_KLAUNCH(ctx, "pv_scan_kernel", pv_scan_kernel, dim3(grid), dim3(256), 0, ctx->stream, phase_ws, n_sc, p.n_tiles,
+                carry_in, carry_out, n_needed);
+    return nae_check(ctx, hipGetLastError(), "pv_scan_kernel");
 }
 
-int nae_launch_pv_synth(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
+// pass 3 (locked: L3) from the records of pass 2 (or, one tile and nothing carried in, from zero)
+int nae_launch_pv_synth(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
                         const nae_pv_segment* seg, int frames_per_step)
 {
@@ -722,7 +699,9 @@ int nae_launch_pv_synth(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig*
         p.carry_out = seg->carry_out;
         p.carry_frame = p.f_stop - 1;
     }
-    return nae_launch_pv_pipe(ctx, p, to_view(src), (long long)n_streams * ch, phase_ws, to_out(out), src->frame_stride == 1, frames_per_step);
+    const long long n_sc = (long long)n_streams * ch;
+    if (lock) return nae_launch_pvlock_synth(ctx, p, to_view(src), n_sc, src->frame_stride == 1, phase_ws, to_out(out));
+    return nae_launch_pv_pipe(ctx, p, to_view(src), n_sc, phase_ws, to_out(out), src->frame_stride == 1, frames_per_step);
 }
 
 // outputs [j_begin, j_end)

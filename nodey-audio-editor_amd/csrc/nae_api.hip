@@ -616,10 +616,10 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
         rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, pl.frames, ch, n_streams, phase_tile));
         if (rc) return rc;
         nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, pv_out_len, nullptr, nullptr};
-        rc = nae_launch_pv_phase_any(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, phase_tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+        rc = nae_launch_pv_phase(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, phase_tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
         if (rc) return rc;
-        rc = nae_launch_pv_synth_any(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, tile, phase_tile, static_cast<const uint32_t*>(ctx->ws_phase), pv_dst,
-                                     &seg, fps);
+        rc = nae_launch_pv_synth(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, tile, phase_tile, static_cast<const uint32_t*>(ctx->ws_phase), pv_dst,
+                                 &seg, fps);
         if (rc) return rc;
     }
     if (pl.rs_on && !pl.rs_first) {
@@ -673,7 +673,7 @@ int nae_debug_pv_tile_phase_ex(nae_ctx* ctx, double rate, double pitch, unsigned
     *tile_frames = (size_t)tile;
     const size_t need = n_streams * ch * n_tiles * NAE_FFT_BINS;
     if (dst_capacity < need) return nae_fail(ctx, NAE_ERR_INVALID, "destination too small");
-    const size_t ws_bytes = nae_pv_phase_workspace_bytes(pl.frames, ch, n_streams, tile);   // the records (the locked workspace begins with them)
+    const size_t ws_bytes = nae_pv_workspace_bytes(false, pl.frames, ch, n_streams, tile);   // the records (the locked workspace begins with them)
     rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, pl.frames, ch, n_streams, tile));
     if (rc) return rc;
     const nae_sig* pv_src = src;
@@ -692,7 +692,7 @@ int nae_debug_pv_tile_phase_ex(nae_ctx* ctx, double rate, double pitch, unsigned
         pv_in_len = pl.mid_len;
     }
     nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, 0, nullptr, nullptr};
-    rc = nae_launch_pv_phase_any(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+    rc = nae_launch_pv_phase(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
     if (rc) return rc;
     std::vector<int32_t> tmp(ws_bytes / sizeof(int32_t));
     hipError_t e = hipMemcpyAsync(tmp.data(), ctx->ws_phase, ws_bytes, hipMemcpyDeviceToHost, ctx->stream);

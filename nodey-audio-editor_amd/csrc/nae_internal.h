@@ -49,7 +49,8 @@ struct nae_ctx {
     bool pv_lean = false;            // pv_lean: the vocoder pipeline keeps its 64-VGPR shape even when one workgroup per CU would allow
                                      // 128 (leaves half of the register file and 94 KB of LDS to a co-resident kernel: tools/coresidency.py)
     // per-context, per-device launch state (a kernel attribute is set once per device: the flag lives with the context's device)
-    unsigned pv_attr_done = 0;       // bit per pv_pipe_kernel instantiation whose dynamic-LDS attribute has been set through this context
+    unsigned pv_attr_done = 0;       // bit per vocoder kernel (pv_pipe_kernel / pv_flow_kernel instantiation, pvlock_* kernel) whose dynamic-LDS
+                                     // attribute has been set through this context (nae_pv_lds_attr)
     // optional per-kernel timing (hipEvent pairs on the ctx stream), used by bench.py for the roofline line
     bool prof_on = false;
     struct ProfSlot { const char* name; double total_ms; uint64_t launches; };
@@ -109,36 +110,14 @@ struct nae_pv_segment {
     uint32_t* carry_out;          // receives the phase behind frame f_origin+f_count-1 (null: not wanted)
     bool carry_by_synth = false;  // the segment is synthesised as ONE tile and pass 3 itself writes carry_out (no pass 1)
 };
-size_t nae_pv_phase_workspace_bytes(size_t n_frames, int ch, size_t n_streams, int tile);
-int nae_launch_pv_phase(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
+// kernels_stft.hip: the vocoder's passes, unlocked or (lock, NAE_STRETCH_PHASE_LOCK) with identity phase locking on the kernels of kernels_pvlock.hip
+size_t nae_pv_workspace_bytes(bool lock, size_t n_frames, int ch, size_t n_streams, int tile);
+int nae_launch_pv_phase(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg);
-int nae_launch_pv_synth(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
+int nae_launch_pv_synth(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
                         const nae_pv_segment* seg, int frames_per_step);
-// kernels_pvlock.hip: the same passes with identity phase locking (NAE_STRETCH_PHASE_LOCK); same arguments, a larger workspace
-size_t nae_pvlock_workspace_bytes(size_t n_frames, int ch, size_t n_streams, int tile);
-int nae_pick_pvlock_tile(nae_ctx* ctx, size_t frames, size_t n_sc);
-int nae_launch_pvlock_phase(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams, int tile,
-                            int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg);
-int nae_launch_pvlock_synth(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams, int tile,
-                            int phase_tile, const uint32_t* phase_ws, const nae_sig* out, const nae_pv_segment* seg);
-// the vocoder's three passes, unlocked or locked (nae_api.hip, nae_stream.hip)
-inline size_t nae_pv_workspace_bytes(bool lock, size_t n_frames, int ch, size_t n_streams, int tile)
-{
-    return lock ? nae_pvlock_workspace_bytes(n_frames, ch, n_streams, tile) : nae_pv_phase_workspace_bytes(n_frames, ch, n_streams, tile);
-}
-inline int nae_launch_pv_phase_any(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
-                                   int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg)
-{
-    return lock ? nae_launch_pvlock_phase(ctx, pl, src, in_len, ch, n_streams, tile, synth_tile, phase_ws, seg)
-                : nae_launch_pv_phase(ctx, pl, src, in_len, ch, n_streams, tile, synth_tile, phase_ws, seg);
-}
-inline int nae_launch_pv_synth_any(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
-                                   int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out, const nae_pv_segment* seg, int frames_per_step)
-{
-    return lock ? nae_launch_pvlock_synth(ctx, pl, src, in_len, ch, n_streams, tile, phase_tile, phase_ws, out, seg)
-                : nae_launch_pv_synth(ctx, pl, src, in_len, ch, n_streams, tile, phase_tile, phase_ws, out, seg, frames_per_step);
-}
+int nae_pick_pvlock_tile(nae_ctx* ctx, size_t frames, size_t n_sc);   // kernels_pvlock.hip
 int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t src_len, int ch,
                         size_t n_streams, const float* d_tab, const nae_sig* out, size_t j_begin, size_t j_end);
 int nae_launch_mix_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* a, const nae_sig* b, float va, float vb,

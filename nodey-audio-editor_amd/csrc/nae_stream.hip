@@ -62,6 +62,36 @@ size_t frames_available(const nae_stretch_plan& pl, size_t in_total)
     return (size_t)f;
 }
 
+// the vocoder stage over the hop blocks [blocks_done, B_r) of `src` (absolute indexing, src_len samples-frames stored) into `dst`: frames >= F_r
+// are not available, samples >= limit are not stored.  Carries the phase on and advances blocks_done.
+int stretch_pv_stage(nae_stretch* h, const nae_stretch_plan& pl, const nae_sig& src, size_t src_len, size_t F_r, size_t B_r, long long limit,
+                     const nae_sig& dst)
+{
+    nae_ctx* ctx = h->ctx;
+    const int ch = h->ch;
+    const size_t count = B_r - h->blocks_done;
+    // a short segment (what a node's batch of waiting frames gives) is ONE tile run frame-interleaved — four consecutive
+    // frames per step — and the pipeline itself hands the phase on: one launch instead of pass 1 + scan + pass 3.
+    // Long segments (a whole file in one put) are cut into 64-frame tiles that run side by side.
+    const bool one_tile = ctx->pv_tile <= 0 && count <= 256;
+    const int tile = one_tile ? (int)count : (ctx->pv_tile > 0 ? ctx->pv_tile : 64);
+    const int fps = one_tile ? 4 : 1;
+    int rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(h->lock, count, ch, 1, tile));
+    if (rc) return rc;
+    for (int i = 0; i < 2; i++)
+        if (!h->carry[i] && hipMalloc((void**)&h->carry[i], (size_t)ch * kPhasePad * sizeof(uint32_t)) != hipSuccess)
+            return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(carry)");
+    nae_pv_segment seg{(long long)h->blocks_done, (long long)count, (long long)F_r, limit,
+                       h->blocks_done ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
+    rc = nae_launch_pv_phase(ctx, h->lock, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+    if (rc) return rc;
+    rc = nae_launch_pv_synth(ctx, h->lock, &pl, &src, src_len, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
+    if (rc) return rc;
+    h->carry_cur ^= 1;
+    h->blocks_done = B_r;
+    return NAE_OK;
+}
+
 int stretch_process(nae_stretch* h)
 {
     nae_ctx* ctx = h->ctx;
@@ -123,31 +153,13 @@ int stretch_process(nae_stretch* h)
             out_limit = (long long)1 << 60;
         }
         if (B_r > h->blocks_done) {
-            const size_t count = B_r - h->blocks_done;
-            // a short segment (what a node's batch of waiting frames gives) is ONE tile run frame-interleaved — four consecutive
-            // frames per step — and the pipeline itself hands the phase on: one launch instead of pass 1 + scan + pass 3.
-            // Long segments (a whole file in one put) are cut into 64-frame tiles that run side by side.
-            const bool one_tile = ctx->pv_tile <= 0 && count <= 256;
-            const int tile = one_tile ? (int)count : (ctx->pv_tile > 0 ? ctx->pv_tile : 64);
-            const int fps = one_tile ? 4 : 1;
-            int rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(h->lock, count, ch, 1, tile));
-            if (rc) return rc;
-            for (int i = 0; i < 2; i++)
-                if (!h->carry[i] && hipMalloc((void**)&h->carry[i], (size_t)ch * kPhasePad * sizeof(uint32_t)) != hipSuccess)
-                    return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(carry)");
-            nae_pv_segment seg{(long long)h->blocks_done, (long long)count, (long long)F_r, out_limit,
-                               h->blocks_done ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
             const size_t produced_total = h->flushed ? fin.out_len : B_r * NAE_HOP;
-            rc = fifo_reserve_interleaved(ctx, h->out, h->out_total, produced_total, ch);
+            int rc = fifo_reserve_interleaved(ctx, h->out, h->out_total, produced_total, ch);
             if (rc) return rc;
-            nae_sig src{h->mid.cur.p - (ptrdiff_t)h->mid.base * ch, 0, 1, (size_t)ch};
+            const nae_sig src{h->mid.cur.p - (ptrdiff_t)h->mid.base * ch, 0, 1, (size_t)ch};
             nae_sig dst{h->out.cur.p - (ptrdiff_t)h->out.base * ch, 0, 1, (size_t)ch};
-            rc = nae_launch_pv_phase_any(ctx, h->lock, &pl, &src, h->mid_total, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+            rc = stretch_pv_stage(h, pl, src, h->mid_total, F_r, B_r, out_limit, dst);
             if (rc) return rc;
-            rc = nae_launch_pv_synth_any(ctx, h->lock, &pl, &src, h->mid_total, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
-            if (rc) return rc;
-            h->carry_cur ^= 1;
-            h->blocks_done = B_r;
             h->out_total = produced_total;
             const long long s_keep = frame_start_host(pl, (long long)B_r - 1);
             rc = fifo_drop_interleaved(ctx, h->mid, s_keep > 0 ? (size_t)s_keep : 0, h->mid_total, ch);
@@ -170,21 +182,7 @@ int stretch_process(nae_stretch* h)
             mid_limit = (long long)1 << 60;
         }
         if (B_r > h->blocks_done) {
-            const size_t count = B_r - h->blocks_done;
-            // a short segment (what a node's batch of waiting frames gives) is ONE tile run frame-interleaved — four consecutive
-            // frames per step — and the pipeline itself hands the phase on: one launch instead of pass 1 + scan + pass 3.
-            // Long segments (a whole file in one put) are cut into 64-frame tiles that run side by side.
-            const bool one_tile = ctx->pv_tile <= 0 && count <= 256;
-            const int tile = one_tile ? (int)count : (ctx->pv_tile > 0 ? ctx->pv_tile : 64);
-            const int fps = one_tile ? 4 : 1;
-            int rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(h->lock, count, ch, 1, tile));
-            if (rc) return rc;
-            for (int i = 0; i < 2; i++)
-                if (!h->carry[i] && hipMalloc((void**)&h->carry[i], (size_t)ch * kPhasePad * sizeof(uint32_t)) != hipSuccess)
-                    return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(carry)");
-            nae_pv_segment seg{(long long)h->blocks_done, (long long)count, (long long)F_r, mid_limit,
-                               h->blocks_done ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
-            nae_sig src{h->in.cur.p - (ptrdiff_t)h->in.base * ch, 0, 1, (size_t)ch};   // absolute indexing
+            int rc;
             nae_sig dst;
             size_t produced_total = h->flushed ? fin.mid_len : B_r * NAE_HOP;
             if (pl.rs_on) {
@@ -211,14 +209,11 @@ int stretch_process(nae_stretch* h)
                 rc = fifo_reserve_interleaved(ctx, h->out, h->out_total, produced_total, ch);
                 if (rc) return rc;
                 dst = nae_sig{h->out.cur.p - (ptrdiff_t)h->out.base * ch, 0, 1, (size_t)ch};
-                if (h->flushed) seg.mid_limit = (long long)fin.out_len;
+                if (h->flushed) mid_limit = (long long)fin.out_len;
             }
-            rc = nae_launch_pv_phase_any(ctx, h->lock, &pl, &src, h->in_total, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+            const nae_sig src{h->in.cur.p - (ptrdiff_t)h->in.base * ch, 0, 1, (size_t)ch};   // absolute indexing
+            rc = stretch_pv_stage(h, pl, src, h->in_total, F_r, B_r, mid_limit, dst);
             if (rc) return rc;
-            rc = nae_launch_pv_synth_any(ctx, h->lock, &pl, &src, h->in_total, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
-            if (rc) return rc;
-            h->carry_cur ^= 1;
-            h->blocks_done = B_r;
             if (pl.rs_on) h->mid_total = produced_total;
             else h->out_total = produced_total;
             // input still needed: from the start of frame B_r - 1 (it primes the next call's phase difference)

@@ -1,5 +1,5 @@
-// stft_common.h — kernel-side types shared by the STFT translation units (kernels_stft.hip, kernels_pvpipe.hip,
-// kernels_spectrum.hip).
+// stft_common.h — kernel-side types and vocoder launch helpers shared by the STFT translation units (kernels_stft.hip, kernels_pvpipe.hip,
+// kernels_spectrum.hip, kernels_pvlock.hip).
 #pragma once
 #include "nae_internal.h"
 #include "stft_device.h"
@@ -24,6 +24,19 @@ constexpr int kWaves = 8;                        // waves per workgroup
 constexpr int kThreads = kWaves * 64;
 constexpr size_t kLdsTablesPad = NAE_FFT_N * sizeof(float) + (kT1024Pad + 64 + kTwaCf) * sizeof(cf);
 
+// stages the four tables at the front of the LDS (kLdsTablesPad bytes) with n_threads threads; the caller issues the barrier
+__device__ __forceinline__ void stage_tables(unsigned char* smem, const Tables& tb, int n_threads, float*& hann, cf*& t1024, cf*& w64, cf*& twa)
+{
+    hann = reinterpret_cast<float*>(smem);
+    t1024 = reinterpret_cast<cf*>(smem + NAE_FFT_N * sizeof(float));
+    w64 = t1024 + kT1024Pad;
+    twa = w64 + 64;
+    for (int i = threadIdx.x; i < NAE_FFT_N; i += n_threads) hann[i] = tb.hann[i];
+    for (int i = threadIdx.x; i < NAE_FFT_BINS; i += n_threads) t1024[i] = tb.t1024[i];
+    if (threadIdx.x < 64) w64[threadIdx.x] = tb.w512[8 * (threadIdx.x >> 3) * (threadIdx.x & 7)];
+    fill_twa(twa, tb.w512, threadIdx.x, n_threads);
+}
+
 // wave index as a SCALAR: hipcc cannot prove threadIdx.x >> 6 wave-uniform, and everything derived from it
 // (stream / tile / frame addresses) would otherwise be carried in VGPRs with 64-bit vector address math
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
@@ -47,6 +60,45 @@ struct PvParams {
     uint32_t* carry_out;  // pass 3, optional: receives the synthesis phase behind frame `carry_frame`, [stream-channel][520] (a continued
     long long carry_frame; //             stream whose segment is ONE tile: no pass 1 is needed just to carry the phase on)
 };
+
+inline PvParams make_pv_params(const nae_stretch_plan& pl, size_t in_len, int ch, int tile, const nae_pv_segment* seg)
+{
+    PvParams p;
+    p.ha_q24 = pl.ha_q24;
+    p.in_len = (long long)in_len;
+    p.frames = seg ? seg->f_limit : (long long)pl.frames;
+    p.mid_len = seg ? seg->mid_limit : (long long)pl.mid_len;
+    p.d0 = pl.d0;
+    p.r_q24_0 = pl.r_q24[0];
+    p.r_q24_1 = pl.r_q24[1];
+    p.ch = ch;
+    p.tile = tile;
+    p.f_origin = seg ? seg->f_origin : 0;
+    const long long cnt = seg ? seg->f_count : (long long)pl.frames;
+    p.f_stop = p.f_origin + cnt;
+    p.n_tiles = (int)((cnt + tile - 1) / tile);
+    p.skip_from = p.n_tiles;
+    p.phase_step = 1;
+    p.phase_tiles = p.n_tiles;
+    p.carry_out = nullptr;
+    p.carry_frame = -1;
+    p.base_zero = 0;
+    return p;
+}
+
+// More than 64 KiB of dynamic LDS needs the attribute: once per kernel and DEVICE, so the flag (attr_bit of nae_ctx::pv_attr_done) lives in the
+// context (no process-global launch state: contexts of different devices, or driven by different threads, do not share it).  lds: the largest
+// launch of the kernel(s); k1 (optional): a second kernel under the same bit (the strided form of a unit-stride kernel).
+inline int nae_pv_lds_attr(nae_ctx* ctx, unsigned attr_bit, size_t lds, const void* k0, const void* k1 = nullptr)
+{
+    if (ctx->pv_attr_done & attr_bit) return NAE_OK;
+    (void)nae_use_device(ctx);
+    hipError_t e = hipFuncSetAttribute(k0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess && k1) e = hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return nae_check(ctx, e, "hipFuncSetAttribute(vocoder)");
+    ctx->pv_attr_done |= attr_bit;
+    return NAE_OK;
+}
 
 __device__ __forceinline__ long long frame_start(const PvParams& p, long long f)
 {
@@ -79,6 +131,12 @@ __device__ __forceinline__ void phase_inc(const uint32_t (&qa)[9], const uint32_
 
 } // namespace nae
 
-// kernels_pvpipe.hip
+// kernels_pvpipe.hip: pass 3 (PvParams as nae_launch_pv_synth built it)
 int nae_launch_pv_pipe(nae_ctx* ctx, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, const uint32_t* phase_ws,
                        const nae::OutViewD& out, bool unit_stride, int frames_per_step);
+// kernels_pvlock.hip: the locked passes L1 + L2 (the maps of tiles [0, n_needed), then the records in phase_ws; maps / sig16: the tile maps'
+// c and sigma, nae_pv_workspace_bytes) and pass L3
+int nae_launch_pvlock_phase(nae_ctx* ctx, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
+                            uint32_t* phase_ws, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out);
+int nae_launch_pvlock_synth(nae_ctx* ctx, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride,
+                            const uint32_t* phase_ws, const nae::OutViewD& out);
