@@ -35,7 +35,8 @@ extern "C" {
  *   Later additions within 3 (the version number did not move; a caller probes for them by symbol, e.g. dlsym): nae_spectrum_frames_ex
  *   and nae_spectrum_block_ex_f32 (spectrum sizes 256 ... 4096, any hop); nae_spectrum_create accepts those sizes and hops;
  *   NAE_STRETCH_PHASE_LOCK with nae_stretch_block_ex_f32, nae_stretch_create_ex and nae_debug_pv_tile_phase_ex (identity phase locking of the
- *   vocoder). */
+ *   vocoder); nae_stretch_plan_make_n, nae_stretch_block_n_f32, nae_debug_pv_tile_phase_n and nae_stretch_create_n (vocoder frame sizes
+ *   512 ... 4096). */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -131,6 +132,8 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *   spec_chunk, spec_fine, spec_fine_rounds   frames per chunk of the stereo spectrum kernel / of the short chunks at a launch's end / how many of those per wave
  *   spec_any        1: 1024-point spectrum launches (nae_spectrum_block_f32, _ex at 1024 / 256, the graph's spectrum node) run the size-generic
  *                   kernel of the other sizes instead of the 1024-point ones, whatever spec_generic says (same results, bit for bit)
+ *   pv_any          1: unlocked 1024-point vocoder launches run the size-generic kernels of the other frame sizes (the same integer phases, bit
+ *                   for bit; samples within the tolerance); the tile is pv_tile, else one of at least pv_min_ptile frames (default 64)
  *   td_nc           1 | 2 | 4: candidates per thread of the WSOLA search;  st_unfused  1: filter and cubic stage of the WSOLA chain as two launches
  * The same assignments, comma separated, in the environment variable NAE_DEBUG ("pv_flow=2,pv_fps=4") are applied when a context is created
  * (for measuring a program that creates its contexts itself, e.g. bench.py); an unknown key there fails nae_ctx_create with NAE_ERR_INVALID. */
@@ -258,6 +261,20 @@ int nae_debug_pv_tile_phase_ex(nae_ctx* ctx, double rate, double pitch, unsigned
 int nae_stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, nae_stretch** h);
 /* the same with the flags of nae_stretch_block_ex_f32; the handle's output equals the block call's with those flags */
 int nae_stretch_create_ex(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, nae_stretch** h);
+
+/* Vocoder frame size n_fft = 512, 1024, 2048 or 4096: analysis and synthesis frames of n_fft samples, synthesis hop n_fft / 4,
+ * Hann / Hann, gain 2/3.  A longer frame resolves low partials (bins of 48000 / n_fft Hz), a shorter one smears transients less.  The plan's hop,
+ * phase-advance ratios and frame count follow the size; out_len, mid_len, the stage order, the transposer and the rate / tempo limits do not.
+ * n_fft = 1024 is exactly the call without _n (nae_stretch_plan_make, the _ex entries).  Another size: NAE_ERR_UNSUPPORTED, and so is
+ * NAE_STRETCH_PHASE_LOCK at a size other than 1024; an unknown flag bit: NAE_ERR_INVALID.  Integer phases are bit-exact against the CPU
+ * restatement (tests/pv_sizes/ref_pv_sizes.c) and independent of the tiling; a handle's output equals the block call's. */
+int nae_stretch_plan_make_n(double rate, double pitch, int n_fft, size_t in_len, nae_stretch_plan* plan);
+int nae_stretch_block_n_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, const nae_sig* src, size_t in_len, int ch,
+                            size_t n_streams, const nae_sig* dst);
+/* dst_host[n_streams][ch][n_tiles][n_fft/2 + 1] */
+int nae_debug_pv_tile_phase_n(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, const nae_sig* src, size_t in_len, int ch,
+                              size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles, size_t* tile_frames);
+int nae_stretch_create_n(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, nae_stretch** h);
 int nae_stretch_put(nae_stretch* h, const float* interleaved, size_t S);
 int nae_stretch_put_host(nae_stretch* h, const float* interleaved_host, size_t S);
 int nae_stretch_flush(nae_stretch* h);

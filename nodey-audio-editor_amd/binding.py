@@ -24,7 +24,8 @@ EXPORTED_SYMBOLS = [
     "nae_deinterleave_f32", "nae_interleave_f32", "nae_copy_sig_f32", "nae_gain_sig_f32", "nae_amix_f32",
     "nae_amix_sig_f32", "nae_bimix_f32", "nae_bimix2_downmix_f32", "nae_bimix2_interleave_f32",
     "nae_to_f32_interleaved", "nae_clamp_f32", "nae_stretch_plan_make", "nae_stretch_block_f32",
-    "nae_debug_pv_tile_phase", "nae_stretch_block_ex_f32", "nae_debug_pv_tile_phase_ex", "nae_stretch_create_ex", "nae_stretch_create", "nae_stretch_put", "nae_stretch_put_host", "nae_stretch_flush",
+    "nae_debug_pv_tile_phase", "nae_stretch_block_ex_f32", "nae_debug_pv_tile_phase_ex", "nae_stretch_create_ex",
+    "nae_stretch_plan_make_n", "nae_stretch_block_n_f32", "nae_debug_pv_tile_phase_n", "nae_stretch_create_n", "nae_stretch_create", "nae_stretch_put", "nae_stretch_put_host", "nae_stretch_flush",
     "nae_stretch_available", "nae_stretch_receive", "nae_stretch_receive_host", "nae_stretch_destroy",
     "nae_swr_create", "nae_swr_convert_host", "nae_swr_convert", "nae_swr_buffered", "nae_swr_destroy", "nae_mono_to_stereo_f32",
     "nae_spectrum_frames", "nae_spectrum_block_f32", "nae_spectrum_frames_ex", "nae_spectrum_block_ex_f32", "nae_spectrum_create", "nae_spectrum_put",
@@ -143,6 +144,10 @@ def load_library() -> C.CDLL:
         "nae_stretch_block_ex_f32": (i, [vp, d, d, u, P(Sig), sz, i, sz, P(Sig)]),
         "nae_debug_pv_tile_phase_ex": (i, [vp, d, d, u, P(Sig), sz, i, sz, vp, sz, P(sz), P(sz)]),
         "nae_stretch_create_ex": (i, [vp, i, i, f, f, u, P(vp)]),
+        "nae_stretch_plan_make_n": (i, [d, d, i, sz, P(StretchPlan)]),
+        "nae_stretch_block_n_f32": (i, [vp, d, d, u, i, P(Sig), sz, i, sz, P(Sig)]),
+        "nae_debug_pv_tile_phase_n": (i, [vp, d, d, u, i, P(Sig), sz, i, sz, vp, sz, P(sz), P(sz)]),
+        "nae_stretch_create_n": (i, [vp, i, i, f, f, u, i, P(vp)]),
         "nae_stretch_create": (i, [vp, i, i, f, f, P(vp)]), "nae_stretch_put": (i, [vp, vp, sz]),
         "nae_stretch_put_host": (i, [vp, vp, sz]), "nae_stretch_flush": (i, [vp]),
         "nae_stretch_available": (sz, [vp]), "nae_stretch_receive": (i, [vp, vp, sz, P(sz)]),
@@ -413,27 +418,39 @@ class Context:
 
     # -- K7
     @staticmethod
-    def stretch_plan(rate: float, pitch: float, in_len: int) -> StretchPlan:
+    def stretch_plan(rate: float, pitch: float, in_len: int, n_fft: int = 1024) -> StretchPlan:
+        """n_fft: vocoder frame size 512 / 1024 / 2048 / 4096 (1024 calls nae_stretch_plan_make)"""
         pl = StretchPlan()
-        rc = load_library().nae_stretch_plan_make(rate, pitch, in_len, C.byref(pl))
+        if n_fft == 1024:
+            rc = load_library().nae_stretch_plan_make(rate, pitch, in_len, C.byref(pl))
+        else:
+            rc = load_library().nae_stretch_plan_make_n(rate, pitch, n_fft, in_len, C.byref(pl))
         if rc:
-            raise NaeError(f"nae_stretch_plan_make({rate}, {pitch}) failed: {rc}")
+            raise NaeError(f"nae_stretch_plan_make({rate}, {pitch}, n_fft={n_fft}) failed: {rc}")
         return pl
 
     def stretch_block(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig,
-                      phase_lock: bool = False):
-        if phase_lock:
+                      phase_lock: bool = False, n_fft: int = 1024):
+        if n_fft != 1024:
+            self._ck(self.lib.nae_stretch_block_n_f32(self.h, rate, pitch, STRETCH_PHASE_LOCK if phase_lock else 0, n_fft, C.byref(src), in_len,
+                                                      ch, n_streams, C.byref(dst)))
+        elif phase_lock:
             self._ck(self.lib.nae_stretch_block_ex_f32(self.h, rate, pitch, STRETCH_PHASE_LOCK, C.byref(src), in_len, ch, n_streams,
                                                        C.byref(dst)))
         else:
             self._ck(self.lib.nae_stretch_block_f32(self.h, rate, pitch, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
     def debug_pv_tile_phase(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int,
-                            phase_lock: bool = False):
-        pl = self.stretch_plan(rate, pitch, in_len)
-        cap = n_streams * ch * (pl.frames + 1) * BINS
+                            phase_lock: bool = False, n_fft: int = 1024):
+        pl = self.stretch_plan(rate, pitch, in_len, n_fft)
+        bins = n_fft // 2 + 1
+        cap = n_streams * ch * (pl.frames + 1) * bins
         out = np.zeros(cap, np.int32)
         nt, tf = C.c_size_t(), C.c_size_t()
+        if n_fft != 1024:
+            self._ck(self.lib.nae_debug_pv_tile_phase_n(self.h, rate, pitch, STRETCH_PHASE_LOCK if phase_lock else 0, n_fft, C.byref(src), in_len,
+                                                        ch, n_streams, out.ctypes.data, cap, C.byref(nt), C.byref(tf)))
+            return out[: n_streams * ch * nt.value * bins].reshape(n_streams, ch, nt.value, bins), tf.value
         if phase_lock:
             self._ck(self.lib.nae_debug_pv_tile_phase_ex(self.h, rate, pitch, STRETCH_PHASE_LOCK, C.byref(src), in_len, ch, n_streams,
                                                          out.ctypes.data, cap, C.byref(nt), C.byref(tf)))
@@ -481,12 +498,17 @@ class Context:
 
 
 class Stretcher:
-    """The SoundTouch-shaped streaming handle (nae_stretch_create_ex): put interleaved f32, flush, receive."""
+    """The SoundTouch-shaped streaming handle (nae_stretch_create_ex; nae_stretch_create_n for an n_fft other than 1024): put interleaved
+    f32, flush, receive."""
 
-    def __init__(self, ctx: Context, sample_rate: int, channels: int, rate: float, pitch: float, phase_lock: bool = False):
+    def __init__(self, ctx: Context, sample_rate: int, channels: int, rate: float, pitch: float, phase_lock: bool = False,
+                 n_fft: int = 1024):
         self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
         flags = STRETCH_PHASE_LOCK if phase_lock else 0
-        ctx._ck(ctx.lib.nae_stretch_create_ex(ctx.h, sample_rate, channels, rate, pitch, flags, C.byref(self.h)))
+        if n_fft != 1024:
+            ctx._ck(ctx.lib.nae_stretch_create_n(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, C.byref(self.h)))
+        else:
+            ctx._ck(ctx.lib.nae_stretch_create_ex(ctx.h, sample_rate, channels, rate, pitch, flags, C.byref(self.h)))
 
     def put(self, dev_ptr: int, frames: int) -> None:
         self.ctx._ck(self.ctx.lib.nae_stretch_put(self.h, dev_ptr, frames))

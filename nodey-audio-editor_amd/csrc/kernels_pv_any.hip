@@ -1,0 +1,470 @@
+// kernels_pv_any.hip — the K7 phase vocoder at frame sizes N = 512, 1024, 2048, 4096 (hop N/4) for gfx950.
+//
+// The three passes of the 1024-point vocoder (kernels_stft.hip, kernels_pvpipe.hip) restated with N as a template parameter, on the
+// size-generic canonical FFT of fft_any.h:
+//   pass 1 (pv_any_phase_kernel)  one wave per (stream-channel, tile): analysis of each frame, sum of its integer phase increments;
+//   pass 2 (pv_any_scan_kernel, pv_any_scan_chunked_kernel)  per (stream-channel, bin) the exclusive prefix over the tiles, in 16 chunks side
+//                                 by side from 256 tiles on, with carry-in and carry-out;
+//   pass 3 (pv_any_synth_kernel)  one wave per synthesis tile: from its record it walks its frames forward — re-analysis, Qs update, rotation,
+//                                 c2r transform, window, overlap-add in increasing frame order, gain — and stores its hop blocks.
+// Every integer is exact, so every tiling gives the same bits, and the integer phases are the CPU restatement's (tests/pv_sizes/ref_pv_sizes.c);
+// the samples follow the tolerance path.  A wave owns one frame at a time: its FFT scratch (9/8 M complex), the phases Qa_{f-1} and (pass 1) the
+// tile's sum or (pass 3) Qs, [r][lane] for bin lane + 64 r, and in pass 3 the synthesis spectrum (B = N/2 + 1 complex, padded) live in LDS; the
+// three open overlap-add blocks of pass 3 in registers.  (Phases in registers, 2 x (M/64 + 1) per lane, with the bin loop unrolled, spill from
+// N = 2048 on.)
+// N = 1024 runs the shipped kernels unless the debug key pv_any asks for these.  The host decisions (records needed, base records, synthesis
+// fields, workspace) are kernels_stft.hip's nae_launch_pv_phase / nae_launch_pv_synth; the launchers here only launch.
+#include "pv_roles.h"
+#include "fft_any.h"
+
+namespace nae {
+
+template <int N>
+struct PvAny {
+    static constexpr int M = N / 2, H = N / 4, B = M + 1;
+    static constexpr int PAD = (B + 7) & ~7;              // int32 per record: 520 at N = 1024, as the shipped kernels
+    static constexpr int SH = 32 - ilog2c(N);             // a bin's phase advance per sample, in Q0.32: 2^SH
+    static constexpr int NB = M / 64 + 1;                 // bins per lane: k = lane + 64 r; r = NB - 1 is bin M (lane 0)
+    static constexpr int JQ = N / 512;                    // sample pairs per lane in each quarter (hop block) of a frame
+    static constexpr int K = 2 * JQ;                      // samples per lane in each hop block
+    using Gm = FftGeom<M, 1>;
+    static constexpr int ST = NB * 64;                    // uint32 per per-bin state array of a wave
+    static constexpr size_t kWave1 = Gm::SCR * sizeof(cf) + 2 * ST * sizeof(uint32_t);                    // scratch, Qa_{f-1}, sum
+    static constexpr size_t kWave3 = Gm::SCR * sizeof(cf) + PAD * sizeof(cf) + 2 * ST * sizeof(uint32_t); // scratch, Y, Qa_{f-1}, Qs
+    static constexpr int kMaxWaves1 = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave1);
+    static constexpr int kMaxWaves3 = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave3);
+    static constexpr int kWaves1 = kMaxWaves1 < 8 ? kMaxWaves1 : 8;   // 8, 8, 8, 4 waves per workgroup at N = 512 ... 4096
+    static constexpr int kWaves3 = kMaxWaves3 < 8 ? kMaxWaves3 : 8;   // 8, 8, 6, 3
+    // pass-3 waves a CU holds: whole workgroups by LDS (16, 8, 6, 3 at N = 512 ... 4096; registers allow as many)
+    static constexpr int kResident3 = (int)((160 * 1024) / (512 * sizeof(cf) + kWaves3 * kWave3)) * kWaves3;
+    static_assert(N >= 512 && N <= 4096 && (N & (N - 1)) == 0, "vocoder sizes 512 ... 4096");
+    static_assert(kWaves1 >= 1 && kWaves3 >= 1, "a wave's state fits a CU's LDS");
+};
+
+template <int N>
+__device__ __forceinline__ long long pva_frame_start(const PvParams& p, long long f)
+{
+    return (((f - 1) * p.ha_q24 + (1ll << (NAE_HA_FRAC_BITS - 1))) >> NAE_HA_FRAC_BITS) - N / 2;
+}
+
+// one frame: window, canonical FFT of M packed points into the wave's scratch (zero outside [0, in.len))
+template <int N, bool kUnit>
+__device__ __forceinline__ void pva_analyse(cf* scr, const cf* w512l, const SpecAnyTables& tb, const ChanView& in, long long s, int lane)
+{
+    using Gm = typename PvAny<N>::Gm;
+    const bool interior = s >= 0 && s + N <= in.len;       // wave-uniform
+    auto get = [&](int m) -> cf {
+        const float2 h = *reinterpret_cast<const float2*>(tb.hann + 2 * m);
+        const long long i0 = s + 2 * m;
+        float x0, x1;
+        if (interior) {
+            if (kUnit) {
+                const f2u x = *reinterpret_cast<const f2u*>(in.p + i0);
+                x0 = x.x;
+                x1 = x.y;
+            } else {
+                x0 = in.p[i0 * in.fs];
+                x1 = in.p[(i0 + 1) * in.fs];
+            }
+        } else {
+            x0 = (i0 >= 0 && i0 < in.len) ? in.p[i0 * in.fs] : 0.0f;
+            x1 = (i0 + 1 >= 0 && i0 + 1 < in.len) ? in.p[(i0 + 1) * in.fs] : 0.0f;
+        }
+        return cf{x0 * h.x, x1 * h.y};
+    };
+    any_first_pass_from<Gm>(scr, w512l, tb.wm, lane, get);
+    any_passes8<Gm, (Gm::M / Gm::R1)>(scr, w512l, lane);
+    wave_lds_sync();
+}
+
+// canonical phase of bin k: atan2_q32 below N/2, the sign of the real part at N/2
+template <int N>
+__device__ __forceinline__ uint32_t pva_phase(cf x, int k)
+{
+    return k < N / 2 ? atan2_q32(x.y, x.x) : ((x.x < 0.0f) ? 0x80000000u : 0u);
+}
+
+// exact phase increment of one hop for bin k: ((k H) mod N) 2^SH + round(int32(Qa - Qp - ((k d) mod N) 2^SH) R / 2^24)
+template <int N>
+__device__ __forceinline__ uint32_t pva_inc(uint32_t qa, uint32_t qp, unsigned k, unsigned d, unsigned R)
+{
+    using P = PvAny<N>;
+    const uint32_t e = ((k * d) & (N - 1)) << P::SH;
+    const int32_t dw = (int32_t)(qa - qp - e);
+    const uint32_t adv = ((k * (unsigned)P::H) & (N - 1)) << P::SH;
+    // R <= 2^30 at every N (it depends on the tempo only): a positive int32
+    const long long scaled = ((long long)dw * (long long)(int32_t)R + (1ll << (NAE_R_FRAC_BITS - 1))) >> NAE_R_FRAC_BITS;
+    return adv + (uint32_t)scaled;
+}
+
+// ------------------------------------------------------------------------------------------------ pass 1
+// sums[(sc * n_tiles + tile) * PAD + k]
+template <int N, bool kUnit>
+__global__ __launch_bounds__(64 * PvAny<N>::kWaves1) void pv_any_phase_kernel(SigViewD src, PvParams p, long long n_items,
+                                                                             uint32_t* __restrict__ sums, SpecAnyTables tb)
+{
+    using P = PvAny<N>;
+    using Gm = typename P::Gm;
+    __shared__ __attribute__((aligned(16))) cf w512l[512];
+    __shared__ __attribute__((aligned(16))) cf scratch[P::kWaves1 * Gm::SCR];
+    __shared__ uint32_t state[P::kWaves1 * 2 * P::ST];
+    for (int i = threadIdx.x; i < 512; i += 64 * P::kWaves1) w512l[i] = tb.w512[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const long long item = (long long)blockIdx.x * P::kWaves1 + wave_id();
+    if (item >= n_items) return;
+    const long long sc = item / p.n_tiles;
+    const int tile = (int)(item % p.n_tiles);
+    if (tile >= p.skip_from) return;                    // wave-uniform
+    cf* scr = scratch + wave_id() * Gm::SCR;
+    uint32_t* qp = state + wave_id() * 2 * P::ST + lane;  // [r * 64]: Qa_{f-1} of bin lane + 64 r
+    uint32_t* acc = qp + P::ST;                          //           the tile's sum of increments
+    const long long s_idx = sc / p.ch;
+    const int c = (int)(sc % p.ch);
+    const ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
+    const long long f0 = p.f_origin + (long long)tile * p.tile;
+    long long f1 = f0 + p.tile;
+    if (f1 > p.f_stop) f1 = p.f_stop;
+
+    for (int r = 0; r < P::NB; r++) { acc[64 * r] = 0; qp[64 * r] = 0; }
+    long long s_prev = 0;
+    // frame f0 - 1 only primes qp (its increment belongs to the previous tile)
+#pragma unroll 1
+    for (long long f = (f0 > 0 ? f0 - 1 : 0); f < f1; f++) {
+        const long long s = pva_frame_start<N>(p, f);
+        pva_analyse<N, kUnit>(scr, w512l, tb, in, s, lane);
+        const unsigned d = (unsigned)(s - s_prev);
+        const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
+#pragma unroll 2
+        for (int r = 0; r < P::NB; r++) {
+            const int k = lane + 64 * r;
+            const int kc = k < P::B ? k : P::M;            // lanes past bin M (last row) compute bin M and store nothing
+            const uint32_t qa = pva_phase<N>(any_rfft_bin<Gm>(scr, tb.tn, kc), kc);
+            // frame f0 - 1 only primes; the "increment" of frame 0 is its analysis phase
+            if (f >= f0) acc[64 * r] = (f == 0) ? qa : acc[64 * r] + pva_inc<N>(qa, qp[64 * r], (unsigned)kc, d, R);
+            qp[64 * r] = qa;
+        }
+        wave_lds_sync();                                   // the next frame rewrites the scratch
+        s_prev = s;
+    }
+    uint32_t* o = sums + item * P::PAD;
+    for (int r = 0; r < P::NB; r++) {
+        const int k = lane + 64 * r;
+        if (k < P::B) o[k] = acc[64 * r];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pass 2
+// exclusive prefix over tiles, in place; one thread per (stream-channel, bin).  carry_in (optional): the phase in front of tile 0, [n_sc][PAD];
+// carry_out (optional): the phase behind the last tile.  Records at or beyond n_read count as zero.
+template <int N>
+__global__ void pv_any_scan_kernel(uint32_t* __restrict__ sums, long long n_sc, int n_tiles, const uint32_t* __restrict__ carry_in,
+                                   uint32_t* __restrict__ carry_out, int n_read)
+{
+    using P = PvAny<N>;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long sc = t / P::PAD;
+    const int k = (int)(t % P::PAD);
+    if (sc >= n_sc || k >= P::B) return;
+    uint32_t* q = sums + sc * n_tiles * (long long)P::PAD + k;
+    uint32_t run = carry_in ? carry_in[sc * P::PAD + k] : 0u;
+    int j = 0;
+    for (; j + 8 <= n_read; j += 8) {
+        uint32_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = q[(long long)(j + u) * P::PAD];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            q[(long long)(j + u) * P::PAD] = run;
+            run += v[u];
+        }
+    }
+    for (; j < n_tiles; j++) {
+        const uint32_t v = (j < n_read) ? q[(long long)j * P::PAD] : 0u;
+        q[(long long)j * P::PAD] = run;
+        run += v;
+    }
+    if (carry_out) carry_out[sc * P::PAD + k] = run;
+}
+
+// many tiles per stream-channel: 16 threads per bin take a sixteenth of the tiles each, exchange their sums through LDS and prefix their own
+// part (modular sums: the split changes no bit).  One workgroup per (stream-channel, 64 bins).
+constexpr int kAnyScanChunks = 16;
+template <int N>
+__global__ __launch_bounds__(64 * kAnyScanChunks) void pv_any_scan_chunked_kernel(uint32_t* __restrict__ sums, long long n_sc, int n_tiles,
+                                                                                 const uint32_t* __restrict__ carry_in,
+                                                                                 uint32_t* __restrict__ carry_out, int n_read)
+{
+    using P = PvAny<N>;
+    __shared__ uint32_t part[kAnyScanChunks][64];
+    const int kb = threadIdx.x & 63, ck = threadIdx.x >> 6;
+    const long long sc = blockIdx.x / P::NB;
+    const int k = (int)(blockIdx.x % P::NB) * 64 + kb;
+    const bool valid = k < P::B;
+    const int per = (n_tiles + kAnyScanChunks - 1) / kAnyScanChunks;
+    const int j0 = ck * per < n_tiles ? ck * per : n_tiles, j1 = (j0 + per < n_tiles) ? j0 + per : n_tiles;
+    const int r1 = j1 < n_read ? j1 : n_read;
+    uint32_t* q = sums + sc * n_tiles * (long long)P::PAD + (valid ? k : 0);
+    uint32_t sum = 0;
+    if (valid)
+        for (int j = j0; j < r1; j++) sum += q[(long long)j * P::PAD];
+    part[ck][kb] = sum;
+    __syncthreads();
+    uint32_t run = (valid && carry_in) ? carry_in[sc * P::PAD + k] : 0u;
+    for (int c2 = 0; c2 < ck; c2++) run += part[c2][kb];
+    if (!valid) return;
+    for (int j = j0; j < j1; j++) {
+        const uint32_t v = (j < n_read) ? q[(long long)j * P::PAD] : 0u;
+        q[(long long)j * P::PAD] = run;
+        run += v;
+    }
+    if (carry_out && ck == kAnyScanChunks - 1) carry_out[sc * P::PAD + k] = run;
+}
+
+// ------------------------------------------------------------------------------------------------ pass 3
+// hop block `be` of the tile: this lane's samples 2 (lane + 64 jj) + {0, 1} of the block, stored below mid_len
+template <int N>
+__device__ __forceinline__ void pva_store_block(const PvParams& p, long long b0, long long b_end, float* optr, long long fs, long long be,
+                                                const float (&o)[PvAny<N>::K], int lane)
+{
+    using P = PvAny<N>;
+    if (be < b0 || be >= b_end) return;                    // wave-uniform
+    const long long n0 = be * P::H;
+#pragma unroll
+    for (int i = 0; i < P::K; i++) {
+        const long long n = n0 + 2 * (lane + 64 * (i >> 1)) + (i & 1);
+        if (n < p.mid_len) optr[n * fs] = o[i];
+    }
+}
+
+template <int N, bool kUnit>
+__global__ __launch_bounds__(64 * PvAny<N>::kWaves3) void pv_any_synth_kernel(SigViewD src, PvParams p, long long n_items,
+                                                                             const uint32_t* __restrict__ phase_ws, OutViewD out, SpecAnyTables tb)
+{
+    using P = PvAny<N>;
+    using Gm = typename P::Gm;
+    __shared__ __attribute__((aligned(16))) cf w512l[512];
+    __shared__ __attribute__((aligned(16))) cf scratch[P::kWaves3 * Gm::SCR];
+    __shared__ __attribute__((aligned(16))) cf yspec[P::kWaves3 * P::PAD];
+    __shared__ uint32_t state[P::kWaves3 * 2 * P::ST];
+    for (int i = threadIdx.x; i < 512; i += 64 * P::kWaves3) w512l[i] = tb.w512[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const long long item = (long long)blockIdx.x * P::kWaves3 + wave_id();
+    if (item >= n_items) return;
+    cf* scr = scratch + wave_id() * Gm::SCR;
+    cf* ys = yspec + wave_id() * P::PAD;
+    uint32_t* qp = state + wave_id() * 2 * P::ST + lane;  // [r * 64]: Qa_{f-1} of bin lane + 64 r
+    uint32_t* qs = qp + P::ST;                           //           Qs
+    const long long sc = item / p.n_tiles;
+    const int tile = (int)(item % p.n_tiles);
+    const long long s_idx = sc / p.ch;
+    const int c = (int)(sc % p.ch);
+    const ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
+    const long long b0 = p.f_origin + (long long)tile * p.tile;
+    const long long b_end = b0 + p.tile < p.f_stop ? b0 + p.tile : p.f_stop;
+    long long f_end = b_end + 3;                           // frames b0 .. b_end+2 feed blocks b0 .. b_end-1
+    if (f_end > p.frames) f_end = p.frames;
+    const long long f_first = b0 > 0 ? b0 - 1 : 0;        // b0 - 1 only primes Qa_{f-1}
+    float* optr = out.base + s_idx * out.ss + c * out.cs;
+
+    // Qs in front of the tile: pass 2's record (or zero)
+    const uint32_t* rec = phase_ws + (sc * p.phase_tiles + (long long)tile * p.phase_step) * P::PAD;
+    for (int r = 0; r < P::NB; r++) {
+        const int k = lane + 64 * r;
+        qs[64 * r] = (p.base_zero || k >= P::B) ? 0u : rec[k];
+        qp[64 * r] = 0;
+    }
+    float r0[P::K], r1[P::K], r2[P::K];
+#pragma unroll
+    for (int i = 0; i < P::K; i++) r0[i] = r1[i] = r2[i] = 0.0f;
+    long long s_prev = 0;
+#pragma unroll 1
+    for (long long f = f_first; f < f_end; f++) {
+        const long long s = pva_frame_start<N>(p, f);
+        pva_analyse<N, kUnit>(scr, w512l, tb, in, s, lane);
+        const unsigned d = (unsigned)(s - s_prev);
+        const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
+        const bool live = f >= b0;                         // wave-uniform
+#pragma unroll 2
+        for (int r = 0; r < P::NB; r++) {
+            const int k = lane + 64 * r;
+            const int kc = k < P::B ? k : P::M;
+            const cf x = any_rfft_bin<Gm>(scr, tb.tn, kc);
+            const uint32_t qa = pva_phase<N>(x, kc);
+            if (live) {
+                const uint32_t q = qs[64 * r] + ((f == 0) ? qa : pva_inc<N>(qa, qp[64 * r], (unsigned)kc, d, R));
+                qs[64 * r] = q;
+                if (k < P::B) ys[k] = pipe_rotate(x, q, qa);         // Y = X e^{i (Qs - Qa)}
+            }
+            qp[64 * r] = qa;
+        }
+        s_prev = s;
+        if (!live) {
+            wave_lds_sync();
+            continue;
+        }
+        if (f == p.carry_frame) {
+            for (int r = 0; r < P::NB; r++) {
+                const int k = lane + 64 * r;
+                if (k < P::B) p.carry_out[sc * P::PAD + k] = qs[64 * r];
+            }
+        }
+        wave_lds_sync();
+        // c2r: split with T_N, conjugate, forward FFT_M (the first pass builds its inputs from Y), scale by 1/M and conjugate back
+        auto zc = [&](int m) -> cf {
+            cf xk = ys[m], xm = ys[P::M - m];
+            if (m == 0) { xk.y = 0.0f; xm.y = 0.0f; }
+            const cf E = {0.5f * (xk.x + xm.x), 0.5f * (xk.y - xm.y)};
+            const cf D = {0.5f * (xk.x - xm.x), 0.5f * (xk.y + xm.y)};
+            const cf T = tb.tn[m];
+            const cf Q = {T.x * D.x + T.y * D.y, T.x * D.y - T.y * D.x};   // conj(T) D
+            return cf{E.x - Q.y, -(E.y + Q.x)};
+        };
+        any_first_pass_from<Gm>(scr, w512l, tb.wm, lane, zc);
+        any_passes8<Gm, (Gm::M / Gm::R1)>(scr, w512l, lane);
+        wave_lds_sync();
+        // windowed samples 2m, 2m + 1 (m = lane + 64 j) of quarter q = j / JQ, overlap-added in increasing frame order: block f - 3 is complete
+        float o[P::K];
+#pragma unroll 1
+        for (int q = 0; q < 4; q++) {
+            float y[P::K];
+#pragma unroll
+            for (int jj = 0; jj < P::JQ; jj++) {
+                const int m = lane + 64 * (q * P::JQ + jj);
+                const cf z = lds_ld(scr + padx(zpos<Gm>(m)));
+                const float2 w = *reinterpret_cast<const float2*>(tb.hann + 2 * m);
+                y[2 * jj] = w.x * (z.x * (1.0f / P::M));
+                y[2 * jj + 1] = w.y * (-z.y * (1.0f / P::M));
+            }
+#pragma unroll
+            for (int i = 0; i < P::K; i++) {
+                if (q == 0) o[i] = (r0[i] + y[i]) * NAE_OLA_GAIN;
+                else if (q == 1) r0[i] = r1[i] + y[i];
+                else if (q == 2) r1[i] = r2[i] + y[i];
+                else r2[i] = y[i];
+            }
+        }
+        wave_lds_sync();                                   // the next frame rewrites the scratch and Y
+        pva_store_block<N>(p, b0, b_end, optr, out.fs, f - 3, o, lane);
+    }
+    // frames past the last one do not exist: the blocks they would have completed get nothing more
+#pragma unroll 1
+    for (long long f = f_end > b0 ? f_end : b0; f < b_end + 3; f++) {
+        float o[P::K];
+#pragma unroll
+        for (int i = 0; i < P::K; i++) {
+            o[i] = r0[i] * NAE_OLA_GAIN;
+            r0[i] = r1[i];
+            r1[i] = r2[i];
+            r2[i] = 0.0f;
+        }
+        pva_store_block<N>(p, b0, b_end, optr, out.fs, f - 3, o, lane);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ launchers
+template <int N>
+static int launch_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
+                        uint32_t* phase_ws, const uint32_t* carry_in, uint32_t* carry_out, const SpecAnyTables& tb)
+{
+    using P = PvAny<N>;
+    const long long items = n_sc * p.n_tiles;
+    const long long grid = (items + P::kWaves1 - 1) / P::kWaves1;
+    if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_phase_kernel: grid too large");
+    if (unit_stride)
+        NAE_KLAUNCH(ctx, "pv_any_phase_kernel", (pv_any_phase_kernel<N, true>), dim3((unsigned)grid), dim3(64 * P::kWaves1), 0, ctx->stream,
+                    src, p, items, phase_ws, tb);
+    else
+        NAE_KLAUNCH(ctx, "pv_any_phase_kernel", (pv_any_phase_kernel<N, false>), dim3((unsigned)grid), dim3(64 * P::kWaves1), 0, ctx->stream,
+                    src, p, items, phase_ws, tb);
+    int rc = nae_check(ctx, hipGetLastError(), "pv_any_phase_kernel");
+    if (rc) return rc;
+    if (p.n_tiles >= 256 && n_sc * P::NB <= 0x7fffffffll) {
+        NAE_KLAUNCH(ctx, "pv_any_scan_kernel", (pv_any_scan_chunked_kernel<N>), dim3((unsigned)(n_sc * P::NB)), dim3(64 * kAnyScanChunks), 0,
+                    ctx->stream, phase_ws, n_sc, p.n_tiles, carry_in, carry_out, n_needed);
+        return nae_check(ctx, hipGetLastError(), "pv_any_scan_kernel");
+    }
+    const long long threads = n_sc * P::PAD;
+    if ((threads + 255) / 256 > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_scan_kernel: grid too large");
+    NAE_KLAUNCH(ctx, "pv_any_scan_kernel", (pv_any_scan_kernel<N>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
+                phase_ws, n_sc, p.n_tiles, carry_in, carry_out, n_needed);
+    return nae_check(ctx, hipGetLastError(), "pv_any_scan_kernel");
+}
+
+template <int N>
+static int launch_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
+                        const OutViewD& out, const SpecAnyTables& tb)
+{
+    using P = PvAny<N>;
+    const long long items = n_sc * p.n_tiles;
+    if (items == 0) return NAE_OK;
+    const long long grid = (items + P::kWaves3 - 1) / P::kWaves3;
+    if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_synth_kernel: grid too large");
+    if (unit_stride)
+        NAE_KLAUNCH(ctx, "pv_any_synth_kernel", (pv_any_synth_kernel<N, true>), dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream,
+                    src, p, items, phase_ws, out, tb);
+    else
+        NAE_KLAUNCH(ctx, "pv_any_synth_kernel", (pv_any_synth_kernel<N, false>), dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream,
+                    src, p, items, phase_ws, out, tb);
+    return nae_check(ctx, hipGetLastError(), "pv_any_synth_kernel");
+}
+
+} // namespace nae
+
+// ================================================================================================ host side
+using namespace nae;
+
+size_t nae_pv_record_pad(int n_fft) { return (size_t)((n_fft / 2 + 1 + 7) & ~7); }
+
+bool nae_pv_size_ok(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096; }
+
+// Tile of a block call (synthesis tile = pass-1 tile): one wave walks a tile, so the tiles are cut for one round of the pass-3 waves the CUs hold
+// (kResident3 per CU: 16 at 512 down to 3 at 4096) where the stream-channels alone do not give them — more tiles would not add occupancy, only
+// re-analysis (a tile pays one priming and three tail frames) — and never shorter than 64 frames (pv_min_ptile: that many).  A single tile per
+// stream-channel needs no pass 1.  pv_tile forces the tile.
+int nae_pick_pvany_tile(nae_ctx* ctx, int n_fft, size_t frames, size_t n_sc)
+{
+    if (ctx->pv_tile > 0) return ctx->pv_tile;
+    const size_t min_tile = ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64;
+    const size_t n_cu = (size_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
+    if (frames == 0 || n_sc == 0) return (int)min_tile;
+    const size_t resident = n_fft == 512 ? PvAny<512>::kResident3 : n_fft == 2048 ? PvAny<2048>::kResident3
+                          : n_fft == 4096 ? PvAny<4096>::kResident3 : PvAny<1024>::kResident3;
+    size_t n_tiles = (resident * n_cu + n_sc - 1) / n_sc;
+    const size_t max_tiles = (frames + min_tile - 1) / min_tile;
+    if (n_tiles > max_tiles) n_tiles = max_tiles;
+    if (n_tiles < 1) n_tiles = 1;
+    const size_t tile = (frames + n_tiles - 1) / n_tiles;
+    return (int)(tile < 0x40000000 ? tile : 0x40000000);
+}
+
+int nae_launch_pvany_phase(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
+                           uint32_t* phase_ws, const uint32_t* carry_in, uint32_t* carry_out)
+{
+    SpecAnyTables tb;
+    int rc = nae_spec_any_tables(ctx, n_fft, &tb);
+    if (rc) return rc;
+    switch (n_fft) {
+    case 512: return launch_phase<512>(ctx, p, src, n_sc, unit_stride, n_needed, phase_ws, carry_in, carry_out, tb);
+    case 1024: return launch_phase<1024>(ctx, p, src, n_sc, unit_stride, n_needed, phase_ws, carry_in, carry_out, tb);
+    case 2048: return launch_phase<2048>(ctx, p, src, n_sc, unit_stride, n_needed, phase_ws, carry_in, carry_out, tb);
+    case 4096: return launch_phase<4096>(ctx, p, src, n_sc, unit_stride, n_needed, phase_ws, carry_in, carry_out, tb);
+    default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
+    }
+}
+
+int nae_launch_pvany_synth(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride,
+                           const uint32_t* phase_ws, const OutViewD& out)
+{
+    SpecAnyTables tb;
+    int rc = nae_spec_any_tables(ctx, n_fft, &tb);
+    if (rc) return rc;
+    switch (n_fft) {
+    case 512: return launch_synth<512>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb);
+    case 1024: return launch_synth<1024>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb);
+    case 2048: return launch_synth<2048>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb);
+    case 4096: return launch_synth<4096>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb);
+    default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
+    }
+}

@@ -7,6 +7,7 @@
 // The two 1024-point kernels run the padded FFT512 of stft_device.h; all three give the canonical spectrum of DESIGN.md §3.
 // Replaces the FFTW-based spectrum the reference declares but never implements.
 #include "stft_common.h"
+#include "fft_any.h"
 #include <math.h>
 
 namespace nae {
@@ -290,17 +291,10 @@ __global__ __launch_bounds__(kThreads, 4) void spectrum_stereo_kernel(const floa
 }
 
 // ------------------------------------------------------------------------------------------------ every size
-// The canonical FFT of DESIGN.md §3 ("K8 spectrum, every size") on M = n_fft/2 packed complex points, as an in-place
-// decimation-in-frequency sequence of radix passes through a wave-private LDS scratch:
-//   first pass radix R1 = 2, 4 or 8 (M = R1 * 8^s), twiddle W_M^(l q) on its outputs q >= 1;
-//   then s radix-8 passes on blocks of MT = M / (R1 8^(t-1)) points, twiddle W_MT^(l q) = W512[(512/MT) l q] (none when MT = 8).
-// At M = 512 this is the FFT512 of the 1024-point kernels pass for pass, so n_fft = 1024 gives their bits.
+// The canonical FFT of DESIGN.md §3 ("K8 spectrum, every size"): fft_any.h.
 //
 // Mapping: one wave = G = max(1, 512/M) consecutive frames of one (stream, channel); a 512-thread workgroup is 8 such waves that
-// share only the W512 table in LDS.  A pass gives each lane G*M/(64 R) butterflies; its R inputs are read from the scratch (the first
-// pass reads the windowed samples from memory instead) and its R outputs go back to the same positions, so a pass needs no buffer
-// of its own and only a wave-level LDS ordering between passes.  Scratch position p lives at p + p/8: 8-byte accesses of the
-// stride-64, stride-8 and stride-1 passes hit distinct banks.  LDS: 4 KiB + 8 x 9/8 x 512 x 8 B (n_fft <= 1024) ... 8 x 18 KiB
+// share only the W512 table in LDS; the first pass reads the windowed samples from memory.  LDS: 4 KiB + 8 x 9/8 x 512 x 8 B (n_fft <= 1024) ... 8 x 18 KiB
 // (4096): 151 552 B (148 KiB) at 4096 = one workgroup, 2 waves per SIMD.  Hann_N and the split twiddles T_N are read through the caches
 // (each element once per frame, coalesced); the first pass of M = 1024 / 2048 reads W_M likewise.
 // Input reuse: a wave reads each of its frames' samples once; consecutive frames of a stream sit in neighbouring waves of one
@@ -308,156 +302,6 @@ __global__ __launch_bounds__(kThreads, 4) void spectrum_stereo_kernel(const floa
 
 constexpr int kAnyWaves = 8;
 constexpr int kAnyThreads = 64 * kAnyWaves;
-
-struct SpecAnyTables {
-    const float* hann;   // Hann_N[n], n < N
-    const cf* tn;        // T_N[k] = exp(-2 pi i k / N), k = 0..M
-    const cf* wm;        // W_M[k], k < M (only read by the first pass when M > 512)
-    const cf* w512;      // W512[k]
-};
-
-constexpr int ilog2c(int x) { return x <= 1 ? 0 : 1 + ilog2c(x / 2); }
-
-template <int N>
-struct SpecGeom {
-    static constexpr int M = N / 2;
-    static constexpr int kLog = ilog2c(M);
-    static constexpr int R1 = kLog % 3 == 0 ? 8 : (1 << (kLog % 3));
-    static constexpr int S8 = (kLog - ilog2c(R1)) / 3;      // radix-8 passes behind the first
-    static constexpr int G = M >= 512 ? 1 : 512 / M;         // frames per wave
-    static constexpr int BINS = M + 1;
-    static constexpr int SCR = (G * M) + (G * M) / 8;        // padded scratch of one wave, complex
-};
-
-__device__ __forceinline__ int padx(int p) { return p + (p >> 3); }
-
-__device__ __forceinline__ cf mul_mi_any(cf a) { return cf{a.y, -a.x}; }
-
-template <int R>
-__device__ __forceinline__ void dft_r(cf (&a)[R])
-{
-    if constexpr (R == 2) {
-        const cf s = cf{a[0].x + a[1].x, a[0].y + a[1].y}, d = cf{a[0].x - a[1].x, a[0].y - a[1].y};
-        a[0] = s;
-        a[1] = d;
-    } else if constexpr (R == 4) {
-        // the inner layers of DFT8: two radix-2 DIF layers, natural-order output
-        const cf s0 = cf{a[0].x + a[2].x, a[0].y + a[2].y}, d0 = cf{a[0].x - a[2].x, a[0].y - a[2].y};
-        const cf s1 = cf{a[1].x + a[3].x, a[1].y + a[3].y};
-        const cf d1 = mul_mi_any(cf{a[1].x - a[3].x, a[1].y - a[3].y});
-        a[0] = cf{s0.x + s1.x, s0.y + s1.y};
-        a[2] = cf{s0.x - s1.x, s0.y - s1.y};
-        a[1] = cf{d0.x + d1.x, d0.y + d1.y};
-        a[3] = cf{d0.x - d1.x, d0.y - d1.y};
-    } else {
-        dft8_fwd(a);
-    }
-}
-
-// position of Z[k] after the passes: k = q1 + R1 k', k' with s octal digits -> q1 (M/R1) + (k' digit-reversed)
-template <int N>
-__device__ __forceinline__ int zpos(int k)
-{
-    using Gm = SpecGeom<N>;
-    const int q1 = k & (Gm::R1 - 1);
-    int kp = k >> ilog2c(Gm::R1), rev = 0;
-#pragma unroll
-    for (int t = 0; t < Gm::S8; t++) {
-        rev = (rev << 3) | (kp & 7);
-        kp >>= 3;
-    }
-    return q1 * (Gm::M / Gm::R1) + rev;
-}
-
-// how a frame's samples are addressed: frame stride 1 (8-byte pair loads), a stride whose offsets inside one frame fit 32 bits
-// (a wave-uniform base plus an unsigned 32-bit lane offset: no 64-bit vector address arithmetic), or any stride
-enum { kLoadUnit = 0, kLoadStride32 = 1, kLoadStride64 = 2 };
-
-// first pass: windowed samples from memory -> radix R1 -> twiddle -> scratch
-template <int N, int kLoad>
-__device__ __forceinline__ void any_first_pass(cf* scr, const cf* w512l, const SpecAnyTables& tb, const ChanView& in,
-                                               long long s0, long long hop, int nvalid, int lane)
-{
-    using Gm = SpecGeom<N>;
-    constexpr int R = Gm::R1, S = Gm::M / R, BPL = Gm::G * Gm::M / (R * 64);
-    static_assert(S % 64 == 0, "a first-pass butterfly row is whole waves: its frame is wave-uniform");
-#pragma unroll
-    for (int i = 0; i < BPL; i++) {
-        const int t = lane + 64 * i;
-        const int g = (64 * i) / S;                          // wave-uniform
-        const int l = t & (S - 1);
-        cf v[R];
-        if (g < nvalid) {
-            const float* p = in.p + (s0 + g * hop) * in.fs;
-#pragma unroll
-            for (int j = 0; j < R; j++) {
-                const int m = l + S * j;
-                const float2 h = *reinterpret_cast<const float2*>(tb.hann + 2 * m);
-                if (kLoad == kLoadUnit) {
-                    const f2u x = *reinterpret_cast<const f2u*>(p + 2 * m);
-                    v[j] = cf{x.x * h.x, x.y * h.y};
-                } else if (kLoad == kLoadStride32) {
-                    const unsigned fs = (unsigned)in.fs, o0 = (unsigned)(2 * m) * fs;
-                    v[j] = cf{p[o0] * h.x, p[o0 + fs] * h.y};
-                } else {
-                    const long long fs = in.fs;
-                    v[j] = cf{p[(2 * m) * fs] * h.x, p[(2 * m + 1) * fs] * h.y};
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < R; j++) v[j] = cf{0.0f, 0.0f};
-        }
-        dft_r<R>(v);
-#pragma unroll
-        for (int q = 1; q < R; q++) {
-            const cf w = Gm::M > 512 ? tb.wm[l * q] : lds_ld(w512l + (512 / Gm::M) * l * q);
-            v[q] = cmul_tw(v[q], w);
-        }
-        const int base = g * Gm::M + l;
-#pragma unroll
-        for (int j = 0; j < R; j++) lds_st(scr + padx(base + S * j), v[j]);
-    }
-}
-
-// one radix-8 pass on blocks of MT points
-template <int N, int MT>
-__device__ __forceinline__ void any_pass8(cf* scr, const cf* w512l, int lane)
-{
-    using Gm = SpecGeom<N>;
-    constexpr int S = MT / 8, BPL = Gm::G * Gm::M / 512;
-    cf v[BPL][8];
-#pragma unroll
-    for (int i = 0; i < BPL; i++) {
-        const int t = lane + 64 * i;
-        const int base = (t / S) * MT + (t & (S - 1));
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[i][j] = lds_ld(scr + padx(base + S * j));
-    }
-#pragma unroll
-    for (int i = 0; i < BPL; i++) {
-        const int t = lane + 64 * i;
-        const int l = t & (S - 1);
-        const int base = (t / S) * MT + l;
-        dft8_fwd(v[i]);
-        if (MT > 8) {
-#pragma unroll
-            for (int q = 1; q < 8; q++) v[i][q] = cmul_tw(v[i][q], lds_ld(w512l + (512 / MT) * l * q));
-        }
-#pragma unroll
-        for (int j = 0; j < 8; j++) lds_st(scr + padx(base + S * j), v[i][j]);
-    }
-}
-
-template <int N, int MT>
-__device__ __forceinline__ void any_passes8(cf* scr, const cf* w512l, int lane)
-{
-    if constexpr (MT >= 8) {
-        wave_lds_sync();
-        any_pass8<N, MT>(scr, w512l, lane);
-        any_passes8<N, MT / 8>(scr, w512l, lane);
-    }
-}
 
 // item = (stream, channel, group of G consecutive frames), one per wave; consecutive items = consecutive frame groups of one stream-channel
 template <int N, int kLoad>
@@ -481,8 +325,8 @@ __global__ __launch_bounds__(kAnyThreads) void spectrum_any_kernel(SigViewD src,
     const int nvalid = (int)((n_frames - f0) < Gm::G ? (n_frames - f0) : Gm::G);
     const ChanView in{src.base + s * src.ss + c * src.cs, src.fs, 0};
 
-    any_first_pass<N, kLoad>(scr, w512l, tb, in, f0 * hop, hop, nvalid, lane);
-    any_passes8<N, (Gm::M / Gm::R1)>(scr, w512l, lane);
+    any_first_pass<Gm, kLoad>(scr, w512l, tb, in, f0 * hop, hop, nvalid, lane);
+    any_passes8<Gm, (Gm::M / Gm::R1)>(scr, w512l, lane);
     wave_lds_sync();
 
     // r2c split and magnitudes: output element o = g (M+1) + k, consecutive lanes -> consecutive addresses of one record
@@ -493,12 +337,7 @@ __global__ __launch_bounds__(kAnyThreads) void spectrum_any_kernel(SigViewD src,
         const int g = o / Gm::BINS, k = o - g * Gm::BINS;
         if (g >= nvalid) break;
         const cf* zf = scr + g * Gm::M + ((g * Gm::M) >> 3);       // padx(g M + p) = padx(g M) + padx(p): M is a multiple of 8
-        const cf A = lds_ld(zf + padx(zpos<N>(k & (Gm::M - 1))));
-        const cf B = lds_ld(zf + padx(zpos<N>((Gm::M - k) & (Gm::M - 1))));
-        const cf E = cf{0.5f * (A.x + B.x), 0.5f * (A.y - B.y)};
-        const cf O = cf{0.5f * (A.x - B.x), 0.5f * (A.y + B.y)};
-        const cf P = cmul_tw(O, tb.tn[k]);
-        const cf X = cf{E.x + P.y, E.y - P.x};
+        const cf X = any_rfft_bin<Gm>(zf, tb.tn, k);
         out[(unsigned)(g * ch * Gm::BINS + k)] = __builtin_sqrtf(X.x * X.x + X.y * X.y);
     }
 }
@@ -530,8 +369,8 @@ static int spec_pick_chunk(long long frames, long long n_streams, int n_cu)
 static int spec_any_slot(int n_fft) { return ilog2c(n_fft) - 8; }
 
 // Hann_N, T_N and W_M of one size: double, one rounding to f32; built on first use, freed with the context.
-// n_fft = 1024 uses the context's own tables (the same formulas, built at creation).
-static int spec_any_tables(nae_ctx* ctx, int n_fft, SpecAnyTables* tb)
+// n_fft = 1024 uses the context's own tables (the same formulas, built at creation).  The size-generic vocoder (kernels_pv_any.hip) reads them too.
+int nae_spec_any_tables(nae_ctx* ctx, int n_fft, SpecAnyTables* tb)
 {
     tb->w512 = ctx->d_w512;
     if (n_fft == NAE_FFT_N) {
@@ -629,7 +468,7 @@ int nae_launch_spectrum(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, si
     if (F == 0 || n_streams == 0) return NAE_OK;
     if (n_fft != NAE_FFT_N || hop != NAE_HOP || ctx->dbg_spec_any) {
         SpecAnyTables tb;
-        const int rc = spec_any_tables(ctx, n_fft, &tb);
+        const int rc = nae_spec_any_tables(ctx, n_fft, &tb);
         if (rc) return rc;
         switch (n_fft) {
         case 256: launch_any<256>(ctx, src, ch, hop, (long long)F, n_streams, dst, dst_stream_stride, tb); break;

@@ -609,12 +609,12 @@ static inline OutViewD to_out(const nae_sig* s)
                     (long long)s->frame_stride};
 }
 
-// records [n_sc][n_tiles][520] uint32 (the exclusive tile-prefix phases); locked, then the tile maps: c [n_sc][n_tiles][520] uint32,
-// sigma [n_sc][n_tiles][520] uint16
-size_t nae_pv_workspace_bytes(bool lock, size_t n_frames, int ch, size_t n_streams, int tile)
+// records [n_sc][n_tiles][nae_pv_record_pad(n_fft)] uint32 (the exclusive tile-prefix phases; 520 per record at 1024); locked (1024 only), then
+// the tile maps: c [n_sc][n_tiles][520] uint32, sigma [n_sc][n_tiles][520] uint16
+size_t nae_pv_workspace_bytes(bool lock, int n_fft, size_t n_frames, int ch, size_t n_streams, int tile)
 {
     const size_t recs = n_streams * ch * ((n_frames + tile - 1) / tile);
-    return recs * kT1024Pad * (lock ? 2 * sizeof(uint32_t) + sizeof(uint16_t) : sizeof(uint32_t));
+    return recs * nae_pv_record_pad(n_fft) * (lock ? 2 * sizeof(uint32_t) + sizeof(uint16_t) : sizeof(uint32_t));
 }
 
 // pass 1 + 2: leaves the exclusive tile-prefix phases in `phase_ws` (one record per pass-1 tile).
@@ -622,7 +622,8 @@ size_t nae_pv_workspace_bytes(bool lock, size_t n_frames, int ch, size_t n_strea
 // tiles keep the chip full on small batches, while pass 3 wants few long tiles (each re-analyses its frames).
 // Only the sums (locked: maps) in front of the last synthesis tile are needed, unless the phase behind the segment is carried on (a
 // continued stream): nothing at all when the stream-channel is a single synthesis tile.
-int nae_launch_pv_phase(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
+// n_fft other than 1024 (or the debug key pv_any) runs the size-generic kernels of kernels_pv_any.hip; lock is 1024 only (the callers check).
+int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg)
 {
     if (tile <= 0 || synth_tile < tile || synth_tile % tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
@@ -635,21 +636,24 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, con
     const int n_needed = need_last ? p.n_tiles : (n_synth - 1) * step;      // sums (maps) of tiles [0, n_needed) are used
     const uint32_t* carry_in = seg ? seg->carry_in : nullptr;
     uint32_t* carry_out = seg ? seg->carry_out : nullptr;
+    const size_t pad = nae_pv_record_pad(n_fft);
     if (n_needed == 0) {
         // base phase of the only synthesis tile (record 0 of each stream-channel): the carried phase, or zero
         hipError_t e = hipSuccess;
         if (!carry_in) {
             // nothing carried in and a single synthesis tile: pass 3 starts from zero by itself (PvParams::base_zero) — no memset launch
-            if (p.n_tiles != 1) e = hipMemsetAsync(phase_ws, 0, (size_t)n_sc * p.n_tiles * kT1024Pad * sizeof(uint32_t), ctx->stream);
+            if (p.n_tiles != 1) e = hipMemsetAsync(phase_ws, 0, (size_t)n_sc * p.n_tiles * pad * sizeof(uint32_t), ctx->stream);
         }
         else if (p.n_tiles == 1)
-            e = hipMemcpyAsync(phase_ws, carry_in, (size_t)n_sc * kT1024Pad * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream);
+            e = hipMemcpyAsync(phase_ws, carry_in, (size_t)n_sc * pad * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream);
         else
-            e = hipMemcpy2DAsync(phase_ws, (size_t)p.n_tiles * kT1024Pad * sizeof(uint32_t), carry_in, kT1024Pad * sizeof(uint32_t),
-                                 kT1024Pad * sizeof(uint32_t), (size_t)n_sc, hipMemcpyDeviceToDevice, ctx->stream);
+            e = hipMemcpy2DAsync(phase_ws, (size_t)p.n_tiles * pad * sizeof(uint32_t), carry_in, pad * sizeof(uint32_t),
+                                 pad * sizeof(uint32_t), (size_t)n_sc, hipMemcpyDeviceToDevice, ctx->stream);
         return nae_check(ctx, e, "phase base init");
     }
     p.skip_from = n_needed;                   // pass 1 skips the tiles whose sums are not needed
+    if (!lock && (n_fft != NAE_FFT_N || ctx->dbg_pv_any))
+        return nae_launch_pvany_phase(ctx, n_fft, p, to_view(src), n_sc, src->frame_stride == 1, n_needed, phase_ws, carry_in, carry_out);
     if (lock) {
         const size_t n_rec = (size_t)n_sc * p.n_tiles;
         uint32_t* maps = phase_ws + n_rec * kT1024Pad;
@@ -684,7 +688,7 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, con
 }
 
 // pass 3 (locked: L3) from the records of pass 2 (or, one tile and nothing carried in, from zero)
-int nae_launch_pv_synth(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
+int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
                         const nae_pv_segment* seg, int frames_per_step)
 {
@@ -701,6 +705,7 @@ int nae_launch_pv_synth(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, con
     }
     const long long n_sc = (long long)n_streams * ch;
     if (lock) return nae_launch_pvlock_synth(ctx, p, to_view(src), n_sc, src->frame_stride == 1, phase_ws, to_out(out));
+    if (n_fft != NAE_FFT_N || ctx->dbg_pv_any) return nae_launch_pvany_synth(ctx, n_fft, p, to_view(src), n_sc, src->frame_stride == 1, phase_ws, to_out(out));
     return nae_launch_pv_pipe(ctx, p, to_view(src), n_sc, phase_ws, to_out(out), src->frame_stride == 1, frames_per_step);
 }
 

@@ -244,6 +244,7 @@ int nae_debug_set(nae_ctx* ctx, const char* key, long long value)
     else if (k == "spec_narrow" && flag) ctx->dbg_spec_narrow = value != 0;
     else if (k == "spec_chunk" && count) ctx->dbg_spec_chunk = (int)value;
     else if (k == "spec_any" && flag) ctx->dbg_spec_any = value != 0;
+    else if (k == "pv_any" && flag) ctx->dbg_pv_any = value != 0;
     else if (k == "spec_fine" && count) ctx->dbg_spec_fine = (int)value;
     else if (k == "spec_fine_rounds" && count) ctx->dbg_spec_fine_rounds = (int)value;
     else if (k == "td_nc" && one_of({0, 1, 2, 4})) ctx->dbg_td_nc = (int)value;
@@ -486,8 +487,17 @@ int nae_prof_get(nae_ctx* ctx, int index, char* name, size_t name_cap, double* t
 // setPitch(pitch) give a time-stretch of 1/pitch followed by a resampling of rate*pitch.
 int nae_stretch_plan_make(double rate, double pitch, size_t in_len, nae_stretch_plan* pl)
 {
+    return nae_stretch_plan_make_n(rate, pitch, NAE_FFT_N, in_len, pl);
+}
+
+// frame size n_fft, synthesis hop H = n_fft / 4: the hop, the phase-advance ratios and the frame count follow the size,
+// everything else does not
+int nae_stretch_plan_make_n(double rate, double pitch, int n_fft, size_t in_len, nae_stretch_plan* pl)
+{
     if (!pl) return NAE_ERR_INVALID;
     memset(pl, 0, sizeof *pl);
+    if (!nae_pv_size_ok(n_fft)) return NAE_ERR_UNSUPPORTED;
+    const int hop = n_fft / 4;
     if (!(rate > 0.0) || !(pitch > 0.0)) return NAE_ERR_INVALID;
     double tempo = 1.0 / pitch, rho = rate * pitch;
     if (fabs(tempo - 1.0) < 1e-6) tempo = 1.0;
@@ -498,11 +508,11 @@ int nae_stretch_plan_make(double rate, double pitch, size_t in_len, nae_stretch_
     if (pl->rs_on && (rho < NAE_RATE_MIN || rho > NAE_RATE_MAX)) return NAE_ERR_UNSUPPORTED;
     pl->tempo_eff = tempo;
     pl->rate_eff = rho;
-    pl->ha_q24 = (int64_t)llround((double)NAE_HOP * tempo * (double)(1 << NAE_HA_FRAC_BITS));
+    pl->ha_q24 = (int64_t)llround((double)hop * tempo * (double)(1 << NAE_HA_FRAC_BITS));
     pl->d0 = (int32_t)(pl->ha_q24 >> NAE_HA_FRAC_BITS);
     for (int i = 0; i < 2; i++) {
         const uint64_t d = (uint64_t)(pl->d0 + i);
-        pl->r_q24[i] = (uint32_t)((((uint64_t)NAE_HOP << NAE_R_FRAC_BITS) + d / 2) / d);
+        pl->r_q24[i] = (uint32_t)((((uint64_t)hop << NAE_R_FRAC_BITS) + d / 2) / d);
     }
     pl->step_q32 = (uint64_t)llround(rho * 4294967296.0);
     pl->out_len = (size_t)floor((double)in_len / (tempo * rho) + 0.5);
@@ -522,7 +532,7 @@ int nae_stretch_plan_make(double rate, double pitch, size_t in_len, nae_stretch_
         pl->mid_len = pl->out_len;
         pv_out = pl->out_len;
     }
-    pl->frames = pl->pv_on ? (pv_out + NAE_FFT_N / 2 + NAE_HOP - 1) / NAE_HOP + 1 : 0;
+    pl->frames = pl->pv_on ? (pv_out + n_fft / 2 + hop - 1) / hop + 1 : 0;
     return NAE_OK;
 }
 
@@ -533,6 +543,16 @@ static int check_sig(nae_ctx* ctx, const nae_sig* s, const char* what)
 }
 
 } // extern "C"
+
+// the one statement of the _n entries' rules: an unknown flag NAE_ERR_INVALID; a size outside 512 / 1024 / 2048 / 4096, or the phase lock at a
+// size other than 1024, NAE_ERR_UNSUPPORTED
+int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft)
+{
+    if (flags & ~NAE_STRETCH_PHASE_LOCK) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
+    if (!nae_pv_size_ok(n_fft)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
+    if ((flags & NAE_STRETCH_PHASE_LOCK) && n_fft != NAE_FFT_N) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "phase locking runs at n_fft = 1024 only");
+    return NAE_OK;
+}
 
 // a 2-input mix node in front of the stretch node (graph4): when the transposer runs first it can mix while staging
 struct nae_mix_front {
@@ -545,14 +565,14 @@ struct nae_mix_front {
 // (nae_debug_graph4_stages: scheduling experiments run the two from separate calls; the intermediate signal stays in the
 // context's workspace between them).
 static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
-                              const nae_sig* dst, const nae_mix_front* front, int stages = 3, bool lock = false)
+                              const nae_sig* dst, const nae_mix_front* front, int stages = 3, bool lock = false, int n_fft = NAE_FFT_N)
 {
     if (!ctx) return NAE_ERR_INVALID;
     int rc;
     if ((rc = check_sig(ctx, src, "null source view")) || (rc = check_sig(ctx, dst, "null destination view"))) return rc;
     if (ch < 1 || ch > 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
     nae_stretch_plan pl;
-    rc = nae_stretch_plan_make(rate, pitch, in_len, &pl);
+    rc = nae_stretch_plan_make_n(rate, pitch, n_fft, in_len, &pl);
     if (rc) return nae_fail(ctx, rc, "rate/pitch outside the supported range");
     // the mix node in front: fused into the transposer when that runs first, else its own launch (src = its output)
     bool mix_pending = front != nullptr && (stages & 1);
@@ -580,7 +600,7 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
         rc = nae_ensure_rs_table(ctx, pl.rate_eff);
         if (rc) return rc;
     }
-    // stage order (DESIGN.md §3.3): transposer first when it shrinks the signal (rate_eff > 1), else vocoder first
+    // stage order (DESIGN.md §3, K7): transposer first when it shrinks the signal (rate_eff > 1), else vocoder first
     const nae_sig* pv_src = src;
     size_t pv_in_len = in_len;
     const nae_sig* pv_dst = dst;
@@ -612,13 +632,14 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
         int phase_tile = 0, fps = 1;
         int tile;
         if (lock) tile = phase_tile = nae_pick_pvlock_tile(ctx, pl.frames, n_streams * ch);
+        else if (n_fft != NAE_FFT_N || ctx->dbg_pv_any) tile = phase_tile = nae_pick_pvany_tile(ctx, n_fft, pl.frames, n_streams * ch);
         else tile = nae_pick_pv_shape(ctx, pl.frames, n_streams * ch, &phase_tile, &fps);
-        rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, pl.frames, ch, n_streams, phase_tile));
+        rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, n_fft, pl.frames, ch, n_streams, phase_tile));
         if (rc) return rc;
         nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, pv_out_len, nullptr, nullptr};
-        rc = nae_launch_pv_phase(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, phase_tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+        rc = nae_launch_pv_phase(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, phase_tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
         if (rc) return rc;
-        rc = nae_launch_pv_synth(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, tile, phase_tile, static_cast<const uint32_t*>(ctx->ws_phase), pv_dst,
+        rc = nae_launch_pv_synth(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, tile, phase_tile, static_cast<const uint32_t*>(ctx->ws_phase), pv_dst,
                                  &seg, fps);
         if (rc) return rc;
     }
@@ -647,6 +668,15 @@ int nae_stretch_block_ex_f32(nae_ctx* ctx, double rate, double pitch, unsigned f
     return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0);
 }
 
+int nae_stretch_block_n_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, const nae_sig* src, size_t in_len, int ch,
+                            size_t n_streams, const nae_sig* dst)
+{
+    if (!ctx) return NAE_ERR_INVALID;
+    const int rc = nae_stretch_n_check(ctx, flags, n_fft);
+    if (rc) return rc;
+    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft);
+}
+
 int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch,
                             size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out,
                             size_t* tile_frames)
@@ -658,23 +688,34 @@ int nae_debug_pv_tile_phase_ex(nae_ctx* ctx, double rate, double pitch, unsigned
                                size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out,
                                size_t* tile_frames)
 {
-    if (!ctx || !dst_host || !n_tiles_out || !tile_frames) return NAE_ERR_INVALID;
+    if (!ctx) return NAE_ERR_INVALID;
     if (flags & ~NAE_STRETCH_PHASE_LOCK) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
+    return nae_debug_pv_tile_phase_n(ctx, rate, pitch, flags, NAE_FFT_N, src, in_len, ch, n_streams, dst_host, dst_capacity, n_tiles_out, tile_frames);
+}
+
+int nae_debug_pv_tile_phase_n(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, const nae_sig* src, size_t in_len, int ch,
+                              size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out, size_t* tile_frames)
+{
+    if (!ctx) return NAE_ERR_INVALID;
+    int rc = nae_stretch_n_check(ctx, flags, n_fft);
+    if (rc) return rc;
+    if (!dst_host || !n_tiles_out || !tile_frames) return NAE_ERR_INVALID;
     const bool lock = (flags & NAE_STRETCH_PHASE_LOCK) != 0;
-    int rc = check_sig(ctx, src, "null source view");
+    rc = check_sig(ctx, src, "null source view");
     if (rc) return rc;
     nae_stretch_plan pl;
-    rc = nae_stretch_plan_make(rate, pitch, in_len, &pl);
+    rc = nae_stretch_plan_make_n(rate, pitch, n_fft, in_len, &pl);
     if (rc) return nae_fail(ctx, rc, "rate/pitch outside the supported range");
     if (!pl.pv_on) return nae_fail(ctx, NAE_ERR_STATE, "phase vocoder stage is bypassed for these parameters");
     const int tile = ctx->pv_tile > 0 ? ctx->pv_tile : 64;
     const size_t n_tiles = (pl.frames + tile - 1) / tile;
     *n_tiles_out = n_tiles;
     *tile_frames = (size_t)tile;
-    const size_t need = n_streams * ch * n_tiles * NAE_FFT_BINS;
+    const size_t bins = (size_t)n_fft / 2 + 1, pad = nae_pv_record_pad(n_fft);
+    const size_t need = n_streams * ch * n_tiles * bins;
     if (dst_capacity < need) return nae_fail(ctx, NAE_ERR_INVALID, "destination too small");
-    const size_t ws_bytes = nae_pv_workspace_bytes(false, pl.frames, ch, n_streams, tile);   // the records (the locked workspace begins with them)
-    rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, pl.frames, ch, n_streams, tile));
+    const size_t ws_bytes = nae_pv_workspace_bytes(false, n_fft, pl.frames, ch, n_streams, tile);   // the records (the locked workspace begins with them)
+    rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, n_fft, pl.frames, ch, n_streams, tile));
     if (rc) return rc;
     const nae_sig* pv_src = src;
     size_t pv_in_len = in_len;
@@ -692,14 +733,14 @@ int nae_debug_pv_tile_phase_ex(nae_ctx* ctx, double rate, double pitch, unsigned
         pv_in_len = pl.mid_len;
     }
     nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, 0, nullptr, nullptr};
-    rc = nae_launch_pv_phase(ctx, lock, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+    rc = nae_launch_pv_phase(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
     if (rc) return rc;
     std::vector<int32_t> tmp(ws_bytes / sizeof(int32_t));
     hipError_t e = hipMemcpyAsync(tmp.data(), ctx->ws_phase, ws_bytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return nae_check(ctx, e, "copy phase workspace");
     for (size_t rec = 0; rec < n_streams * ch * n_tiles; rec++)
-        memcpy(dst_host + rec * NAE_FFT_BINS, tmp.data() + rec * kPhasePad, NAE_FFT_BINS * sizeof(int32_t));
+        memcpy(dst_host + rec * bins, tmp.data() + rec * pad, bins * sizeof(int32_t));
     return NAE_OK;
 }
 

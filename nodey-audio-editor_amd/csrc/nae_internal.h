@@ -43,6 +43,7 @@ struct nae_ctx {
     int dbg_spec_fine = 0, dbg_spec_fine_rounds = 0;   // spec_fine / spec_fine_rounds: frames of the short chunks at the end of a large launch's list / how many of them per resident wave
     int dbg_spec_chunk = 0;          // spec_chunk: frames one wave of the stereo spectrum kernel walks (0: spec_pick_chunk)
     bool dbg_spec_any = false;       // spec_any: 1024-point spectrum launches run the size-generic kernel (kernels_spectrum.hip)
+    bool dbg_pv_any = false;         // pv_any: unlocked 1024-point vocoder launches run the size-generic kernels (kernels_pv_any.hip)
     int dbg_pv_min_ptile = 0;        // pv_min_ptile: shortest pass-1 tile in frames (0: 16)
     int pv_flow = 1;                 // pv_flow = 0|1|2: launches of at most one workgroup per CU run the one-barrier schedule (pv_flow_kernel) never / with one
                                      // frame per step (default: where it is faster, profiles/r05_flow.md) / in every shape
@@ -110,14 +111,21 @@ struct nae_pv_segment {
     uint32_t* carry_out;          // receives the phase behind frame f_origin+f_count-1 (null: not wanted)
     bool carry_by_synth = false;  // the segment is synthesised as ONE tile and pass 3 itself writes carry_out (no pass 1)
 };
-// kernels_stft.hip: the vocoder's passes, unlocked or (lock, NAE_STRETCH_PHASE_LOCK) with identity phase locking on the kernels of kernels_pvlock.hip
-size_t nae_pv_workspace_bytes(bool lock, size_t n_frames, int ch, size_t n_streams, int tile);
-int nae_launch_pv_phase(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
+// kernels_stft.hip: the vocoder's passes, unlocked or (lock, NAE_STRETCH_PHASE_LOCK) with identity phase locking on the kernels of kernels_pvlock.hip;
+// frame size n_fft (512 ... 4096; not 1024, or the debug key pv_any: the size-generic kernels of kernels_pv_any.hip)
+size_t nae_pv_workspace_bytes(bool lock, int n_fft, size_t n_frames, int ch, size_t n_streams, int tile);
+int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg);
-int nae_launch_pv_synth(nae_ctx* ctx, bool lock, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
+int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
                         const nae_pv_segment* seg, int frames_per_step);
 int nae_pick_pvlock_tile(nae_ctx* ctx, size_t frames, size_t n_sc);   // kernels_pvlock.hip
+// kernels_pv_any.hip: the vocoder sizes (512, 1024, 2048, 4096), the record length of a size (int32: N/2 + 1 padded to a multiple of 8), the
+// tile of a size-generic block call
+bool nae_pv_size_ok(int n_fft);
+size_t nae_pv_record_pad(int n_fft);
+int nae_pick_pvany_tile(nae_ctx* ctx, int n_fft, size_t frames, size_t n_sc);
+int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft);   // nae_api.hip: flags and size of the _n entries
 int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t src_len, int ch,
                         size_t n_streams, const float* d_tab, const nae_sig* out, size_t j_begin, size_t j_end);
 int nae_launch_mix_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* a, const nae_sig* b, float va, float vb,

@@ -16,6 +16,7 @@ struct nae_stretch {
     int sample_rate, ch;
     double rate, pitch;
     bool lock = false;            // NAE_STRETCH_PHASE_LOCK (nae_stretch_create_ex)
+    int n_fft = NAE_FFT_N;        // vocoder frame size, hop n_fft / 4 (nae_stretch_create_n)
     nae_stretch_plan pl{};        // parameters (in_len = 0)
     DevFifo in;                   // interleaved input, sample-frames [in.base, in_total)
     size_t in_total = 0;
@@ -45,20 +46,20 @@ struct nae_spectrum {
 
 namespace {
 
-inline long long frame_start_host(const nae_stretch_plan& pl, long long f)
+inline long long frame_start_host(const nae_stretch_plan& pl, int n_fft, long long f)
 {
-    return (((f - 1) * pl.ha_q24 + (1ll << (NAE_HA_FRAC_BITS - 1))) >> NAE_HA_FRAC_BITS) - NAE_FFT_N / 2;
+    return (((f - 1) * pl.ha_q24 + (1ll << (NAE_HA_FRAC_BITS - 1))) >> NAE_HA_FRAC_BITS) - n_fft / 2;
 }
 
-// number of leading frames whose 1024-sample window lies inside [.., in_total)
-size_t frames_available(const nae_stretch_plan& pl, size_t in_total)
+// number of leading frames whose n_fft-sample window lies inside [.., in_total)
+size_t frames_available(const nae_stretch_plan& pl, int n_fft, size_t in_total)
 {
-    if (in_total < NAE_FFT_N / 2) return 0;
+    if (in_total < (size_t)n_fft / 2) return 0;
     // estimate, then correct with the exact start formula
-    long long f = (long long)(((double)in_total - 512.0) / ((double)pl.ha_q24 / (double)(1 << NAE_HA_FRAC_BITS))) + 2;
+    long long f = (long long)(((double)in_total - 0.5 * n_fft) / ((double)pl.ha_q24 / (double)(1 << NAE_HA_FRAC_BITS))) + 2;
     if (f < 0) f = 0;
-    while (f > 0 && frame_start_host(pl, f - 1) + NAE_FFT_N > (long long)in_total) f--;
-    while (frame_start_host(pl, f) + NAE_FFT_N <= (long long)in_total) f++;
+    while (f > 0 && frame_start_host(pl, n_fft, f - 1) + n_fft > (long long)in_total) f--;
+    while (frame_start_host(pl, n_fft, f) + n_fft <= (long long)in_total) f++;
     return (size_t)f;
 }
 
@@ -76,16 +77,16 @@ int stretch_pv_stage(nae_stretch* h, const nae_stretch_plan& pl, const nae_sig& 
     const bool one_tile = ctx->pv_tile <= 0 && count <= 256;
     const int tile = one_tile ? (int)count : (ctx->pv_tile > 0 ? ctx->pv_tile : 64);
     const int fps = one_tile ? 4 : 1;
-    int rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(h->lock, count, ch, 1, tile));
+    int rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(h->lock, h->n_fft, count, ch, 1, tile));
     if (rc) return rc;
     for (int i = 0; i < 2; i++)
-        if (!h->carry[i] && hipMalloc((void**)&h->carry[i], (size_t)ch * kPhasePad * sizeof(uint32_t)) != hipSuccess)
+        if (!h->carry[i] && hipMalloc((void**)&h->carry[i], (size_t)ch * nae_pv_record_pad(h->n_fft) * sizeof(uint32_t)) != hipSuccess)
             return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(carry)");
     nae_pv_segment seg{(long long)h->blocks_done, (long long)count, (long long)F_r, limit,
                        h->blocks_done ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
-    rc = nae_launch_pv_phase(ctx, h->lock, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+    rc = nae_launch_pv_phase(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
     if (rc) return rc;
-    rc = nae_launch_pv_synth(ctx, h->lock, &pl, &src, src_len, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
+    rc = nae_launch_pv_synth(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
     if (rc) return rc;
     h->carry_cur ^= 1;
     h->blocks_done = B_r;
@@ -97,9 +98,10 @@ int stretch_process(nae_stretch* h)
     nae_ctx* ctx = h->ctx;
     const int ch = h->ch;
     const nae_stretch_plan& pl = h->pl;
+    const size_t hop = (size_t)h->n_fft / 4;     // hop blocks of the vocoder stage
     nae_stretch_plan fin{};
     if (h->flushed) {
-        int rc = nae_stretch_plan_make(h->rate, h->pitch, h->in_total, &fin);
+        int rc = nae_stretch_plan_make_n(h->rate, h->pitch, h->n_fft, h->in_total, &fin);
         if (rc) return rc;
     }
     // ---- neither stage: the node is a wire
@@ -145,15 +147,15 @@ int stretch_process(nae_stretch* h)
         long long out_limit;
         if (h->flushed) {
             F_r = fin.frames;
-            B_r = (fin.out_len + NAE_HOP - 1) / NAE_HOP;
+            B_r = (fin.out_len + hop - 1) / hop;
             out_limit = (long long)fin.out_len;
         } else {
-            F_r = frames_available(pl, h->mid_total);
+            F_r = frames_available(pl, h->n_fft, h->mid_total);
             B_r = F_r >= 3 ? F_r - 3 : 0;
             out_limit = (long long)1 << 60;
         }
         if (B_r > h->blocks_done) {
-            const size_t produced_total = h->flushed ? fin.out_len : B_r * NAE_HOP;
+            const size_t produced_total = h->flushed ? fin.out_len : B_r * hop;
             int rc = fifo_reserve_interleaved(ctx, h->out, h->out_total, produced_total, ch);
             if (rc) return rc;
             const nae_sig src{h->mid.cur.p - (ptrdiff_t)h->mid.base * ch, 0, 1, (size_t)ch};
@@ -161,7 +163,7 @@ int stretch_process(nae_stretch* h)
             rc = stretch_pv_stage(h, pl, src, h->mid_total, F_r, B_r, out_limit, dst);
             if (rc) return rc;
             h->out_total = produced_total;
-            const long long s_keep = frame_start_host(pl, (long long)B_r - 1);
+            const long long s_keep = frame_start_host(pl, h->n_fft, (long long)B_r - 1);
             rc = fifo_drop_interleaved(ctx, h->mid, s_keep > 0 ? (size_t)s_keep : 0, h->mid_total, ch);
             if (rc) return rc;
         }
@@ -174,17 +176,17 @@ int stretch_process(nae_stretch* h)
         long long mid_limit;
         if (h->flushed) {
             F_r = fin.frames;
-            B_r = (fin.mid_len + NAE_HOP - 1) / NAE_HOP;
+            B_r = (fin.mid_len + hop - 1) / hop;
             mid_limit = (long long)fin.mid_len;
         } else {
-            F_r = frames_available(pl, h->in_total);
+            F_r = frames_available(pl, h->n_fft, h->in_total);
             B_r = F_r >= 3 ? F_r - 3 : 0;
             mid_limit = (long long)1 << 60;
         }
         if (B_r > h->blocks_done) {
             int rc;
             nae_sig dst;
-            size_t produced_total = h->flushed ? fin.mid_len : B_r * NAE_HOP;
+            size_t produced_total = h->flushed ? fin.mid_len : B_r * hop;
             if (pl.rs_on) {
                 // planar mid FIFO: grow (re-pack planes) when the per-channel capacity is too small
                 const size_t need = produced_total - h->mid.base;
@@ -217,7 +219,7 @@ int stretch_process(nae_stretch* h)
             if (pl.rs_on) h->mid_total = produced_total;
             else h->out_total = produced_total;
             // input still needed: from the start of frame B_r - 1 (it primes the next call's phase difference)
-            const long long s_keep = frame_start_host(pl, (long long)B_r - 1);
+            const long long s_keep = frame_start_host(pl, h->n_fft, (long long)B_r - 1);
             rc = fifo_drop_interleaved(ctx, h->in, s_keep > 0 ? (size_t)s_keep : 0, h->in_total, ch);
             if (rc) return rc;
         }
@@ -286,6 +288,14 @@ int nae_stretch_create_ex(nae_ctx* ctx, int sample_rate, int channels, float rat
 {
     if (!ctx || !h) return NAE_ERR_INVALID;
     if (flags & ~NAE_STRETCH_PHASE_LOCK) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
+    return nae_stretch_create_n(ctx, sample_rate, channels, rate, pitch, flags, NAE_FFT_N, h);
+}
+
+int nae_stretch_create_n(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, nae_stretch** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    const int chk = nae_stretch_n_check(ctx, flags, n_fft);
+    if (chk) return chk;
     (void)nae_use_device(ctx);
     *h = nullptr;
     // audio-velocity.cpp:371-379 rejects rates outside 8..48 kHz for SoundTouch; the vocoder has no such
@@ -293,7 +303,7 @@ int nae_stretch_create_ex(nae_ctx* ctx, int sample_rate, int channels, float rat
     if (sample_rate != 0 && (sample_rate < 8000 || sample_rate > 48000)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "Unsupported sample rate: requires 8000..48000 Hz");
     if (channels != 1 && channels != 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
     nae_stretch_plan pl;
-    int rc = nae_stretch_plan_make(rate, pitch, 0, &pl);
+    int rc = nae_stretch_plan_make_n(rate, pitch, n_fft, 0, &pl);
     if (rc) return nae_fail(ctx, rc, "rate/pitch outside the supported range");
     nae_stretch* s = new (std::nothrow) nae_stretch();
     if (!s) return NAE_ERR_NOMEM;
@@ -303,6 +313,7 @@ int nae_stretch_create_ex(nae_ctx* ctx, int sample_rate, int channels, float rat
     s->rate = rate;
     s->pitch = pitch;
     s->lock = (flags & NAE_STRETCH_PHASE_LOCK) != 0;
+    s->n_fft = n_fft;
     s->pl = pl;
     *h = s;
     return NAE_OK;

@@ -26,7 +26,7 @@ __device__ __forceinline__ int pipe_lane(int lane)
     return lane;
 }
 
-// exact phase increment of one hop for bin k (DESIGN.md §3.3): adv + round(dw * R / 2^24)
+// exact phase increment of one hop for bin k (DESIGN.md §3, K7): adv + round(dw * R / 2^24)
 __device__ __forceinline__ uint32_t pipe_inc(uint32_t qa, uint32_t qp, unsigned k, unsigned d, unsigned R)
 {
     const uint32_t e = ((k * d) & (NAE_FFT_N - 1)) << 22;
@@ -232,7 +232,7 @@ struct PhaseLane {
     {
 #pragma unroll
         for (int q = 0; q < 4; q++) qa[q] = atan2_q32(va[q].y, va[q].x);
-        // bin N/2 of a real signal is real: its phase is 0 or 1/2 turn by the sign of the real part (DESIGN.md §3.3)
+        // bin N/2 of a real signal is real: its phase is 0 or 1/2 turn by the sign of the real part (DESIGN.md §3, K7)
         if (h == 0) qa[4] = (va[4].x < 0.0f) ? 0x80000000u : 0u;
     }
     // phase increment of all items of this lane (exact integers)

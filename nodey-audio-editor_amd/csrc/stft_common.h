@@ -110,7 +110,7 @@ __device__ __forceinline__ void phases_of(const cf (&v)[8], cf nyq, uint32_t (&q
 {
 #pragma unroll
     for (int r = 0; r < 8; r++) qa[r] = atan2_q32(v[r].y, v[r].x);
-    qa[8] = (nyq.x < 0.0f) ? 0x80000000u : 0u;     // bin N/2 of a real signal is real (DESIGN.md §3.3)
+    qa[8] = (nyq.x < 0.0f) ? 0x80000000u : 0u;     // bin N/2 of a real signal is real (DESIGN.md §3, K7)
 }
 
 // phase increment of one hop for this lane's 9 bins (integer, exact)
@@ -140,3 +140,9 @@ int nae_launch_pvlock_phase(nae_ctx* ctx, const nae::PvParams& p, const nae::Sig
                             uint32_t* phase_ws, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out);
 int nae_launch_pvlock_synth(nae_ctx* ctx, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride,
                             const uint32_t* phase_ws, const nae::OutViewD& out);
+// kernels_pv_any.hip: passes 1 + 2 and pass 3 of the vocoder at n_fft = 512 ... 4096 (records of nae_pv_record_pad(n_fft) int32)
+int nae_launch_pvany_phase(nae_ctx* ctx, int n_fft, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
+                           uint32_t* phase_ws, const uint32_t* carry_in, uint32_t* carry_out);
+int nae_launch_pvany_synth(nae_ctx* ctx, int n_fft, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride,
+                           const uint32_t* phase_ws, const nae::OutViewD& out);
+

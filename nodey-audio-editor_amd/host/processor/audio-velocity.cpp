@@ -39,6 +39,24 @@ namespace processor
 		return value["phase_lock"].asBool();
 	}
 
+	int fft_size_from_json(const Json::Value& value, const char* node_name, bool phase_lock)
+	{
+		if (!value.isMember("fft_size")) return 1024;
+		const Json::Value& v = value["fft_size"];
+		// compared as a double with the sizes first: a number outside int's range is never converted
+		int n = 0;
+		if (v.isDouble())
+			for (int size : {512, 1024, 2048, 4096})
+				if (v.asDouble() == (double)size) n = size;
+		if (n == 0 || (phase_lock && n != 1024))
+			throw infra::Processor::Runtime_error(
+				"Failed to deserialize JSON file",
+				std::string(node_name) + " failed to serialize the JSON input because of missing or invalid fields.",
+				"Wrong field: fft_size"
+			);
+		return n;
+	}
+
 	namespace
 	{
 		std::vector<infra::Processor::Pin_attribute> io_pins()
@@ -170,13 +188,14 @@ namespace processor
 				if (st) nae_wsola_destroy(st);
 			}
 			bool open() const { return pv != nullptr || st != nullptr; }
-			void create(Stretch_algorithm algo, bool phase_lock, int sample_rate, int channels, float velocity, float pitch)
+			void create(Stretch_algorithm algo, bool phase_lock, int fft_size, int sample_rate, int channels, float velocity, float pitch)
 			{
-				if (algo == Stretch_algorithm::Soundtouch)   // (phase_lock is a vocoder option: the WSOLA chain has no phases to lock)
+				if (algo == Stretch_algorithm::Soundtouch)   // (phase_lock and fft_size are vocoder options: the WSOLA chain has neither)
 					gpu::check(nae_wsola_create(gpu::context(), sample_rate, channels, velocity, pitch, &st), "nae_wsola_create");
 				else
-					gpu::check(nae_stretch_create_ex(gpu::context(), sample_rate, channels, velocity, pitch, phase_lock ? NAE_STRETCH_PHASE_LOCK : 0u, &pv),
-							   "nae_stretch_create_ex");
+					gpu::check(nae_stretch_create_n(gpu::context(), sample_rate, channels, velocity, pitch, phase_lock ? NAE_STRETCH_PHASE_LOCK : 0u,
+												   fft_size, &pv),
+							   "nae_stretch_create_n");
 			}
 			size_t available() const { return pv ? nae_stretch_available(pv) : nae_wsola_available(st); }
 			void put(const float* samples, size_t n)
@@ -195,7 +214,7 @@ namespace processor
 			const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
 			const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
 			const std::atomic<bool>& stop_token, float velocity, float pitch, const std::string& processor_name,
-			Stretch_algorithm algorithm, bool phase_lock, Batch_stats& batch_stats
+			Stretch_algorithm algorithm, bool phase_lock, int fft_size, Batch_stats& batch_stats
 		)
 		{
 			gpu::Node node;  // this node's context (own stream; device: gpu::pick_device): first local, destroyed last
@@ -294,7 +313,7 @@ namespace processor
 									infra::fmt("%d requires a sample rate between 8000 and 48000 Hz.", frame->sample_rate),
 									infra::fmt("Sample rate: %d", frame->sample_rate)
 								);
-							soundtouch.create(algorithm, phase_lock, frame->sample_rate, frame->ch_layout.nb_channels, velocity, pitch);
+							soundtouch.create(algorithm, phase_lock, fft_size, frame->sample_rate, frame->ch_layout.nb_channels, velocity, pitch);
 							channel_count = frame->ch_layout.nb_channels;
 							time_seconds = frame->pts * av_q2d(frame->time_base);
 							sample_rate = frame->sample_rate;
@@ -363,7 +382,7 @@ namespace processor
 	)
 	{
 		stretch_process_payload(input, output, stop_token, velocity, keep_pitch ? 1 / velocity : 1, get_processor_info().display_name,
-								algorithm, phase_lock, batch_stats);  // :452-459
+								algorithm, phase_lock, fft_size, batch_stats);  // :452-459
 	}
 
 	Json::Value Velocity_modifier::serialize() const
@@ -373,6 +392,7 @@ namespace processor
 		value["keep_pitch"] = keep_pitch;
 		if (algorithm != default_stretch_algorithm()) value["algorithm"] = algorithm_name(algorithm);
 		if (phase_lock) value["phase_lock"] = true;
+		if (fft_size != 1024) value["fft_size"] = fft_size;
 		return value;
 	}
 
@@ -382,6 +402,7 @@ namespace processor
 		if (value.isMember("keep_pitch") && value["keep_pitch"].isBool()) keep_pitch = value["keep_pitch"].asBool();
 		algorithm = algorithm_from_json(value);
 		phase_lock = phase_lock_from_json(value, "Velocity_modifier");
+		fft_size = fft_size_from_json(value, "Velocity_modifier", phase_lock);
 	}
 
 	// ------------------------------------------------------------------------------------------ Pitch_modifier
@@ -399,7 +420,7 @@ namespace processor
 	)
 	{
 		stretch_process_payload(input, output, stop_token, 1, std::pow(2.0f, pitch / 12.0f), get_processor_info().display_name,
-								algorithm, phase_lock, batch_stats);  // :469-476
+								algorithm, phase_lock, fft_size, batch_stats);  // :469-476
 	}
 
 	Json::Value Pitch_modifier::serialize() const
@@ -408,6 +429,7 @@ namespace processor
 		value["pitch"] = pitch;
 		if (algorithm != default_stretch_algorithm()) value["algorithm"] = algorithm_name(algorithm);
 		if (phase_lock) value["phase_lock"] = true;
+		if (fft_size != 1024) value["fft_size"] = fft_size;
 		return value;
 	}
 	void Pitch_modifier::deserialize(const Json::Value& value)
@@ -415,6 +437,7 @@ namespace processor
 		if (value.isMember("pitch") && value["pitch"].isDouble()) pitch = value["pitch"].asFloat();
 		algorithm = algorithm_from_json(value);
 		phase_lock = phase_lock_from_json(value, "Pitch_modifier");
+		fft_size = fft_size_from_json(value, "Pitch_modifier", phase_lock);
 	}
 
 	// ------------------------------------------------------------------------------------------ Audio_spectrum

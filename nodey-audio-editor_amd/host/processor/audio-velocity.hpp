@@ -20,6 +20,10 @@ namespace processor
 	// "phase_lock" (bool, optional): identity phase locking of the vocoder (NAE_STRETCH_PHASE_LOCK).  No key: false; a value that is not a bool:
 	// Runtime_error "Wrong field: phase_lock"; written back only when true.  With "algorithm": "soundtouch" the key is kept and has no effect.
 	bool phase_lock_from_json(const Json::Value& value, const char* node_name);
+	// "fft_size" (integer, optional): the vocoder's frame size, 512 / 1024 / 2048 / 4096 (nae_stretch_create_n).  No key: 1024; a value that is not
+	// one of those, or a size other than 1024 with "phase_lock": true: Runtime_error "Wrong field: fft_size"; written back only when not 1024.
+	// With "algorithm": "soundtouch" the key is kept and has no effect.
+	int fft_size_from_json(const Json::Value& value, const char* node_name, bool phase_lock);
 
 	class Velocity_modifier : public infra::Processor
 	{
@@ -27,6 +31,7 @@ namespace processor
 		bool keep_pitch = false;
 		Stretch_algorithm algorithm = default_stretch_algorithm();
 		bool phase_lock = false;
+		int fft_size = 1024;
 
 	  public:
 
@@ -43,7 +48,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override;            // velocity, keep_pitch (audio-velocity.cpp:479-485); algorithm, phase_lock when not the default
+		Json::Value serialize() const override;            // velocity, keep_pitch (audio-velocity.cpp:479-485); algorithm, phase_lock, fft_size when not the default
 		void deserialize(const Json::Value& value) override;  // :487-493
 	};
 
@@ -52,6 +57,7 @@ namespace processor
 		float pitch = 0;  // semitones
 		Stretch_algorithm algorithm = default_stretch_algorithm();
 		bool phase_lock = false;
+		int fft_size = 1024;
 
 	  public:
 
@@ -68,7 +74,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock when not the default
+		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock, fft_size when not the default
 		void deserialize(const Json::Value& value) override;  // :502-505
 	};
 
