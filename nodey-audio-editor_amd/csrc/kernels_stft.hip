@@ -219,7 +219,8 @@ constexpr int kRsOutWide = 768;                  // round 4 (16-byte tap reads):
                                                  // 1536-frame staging rows (rho <= 1.96), see rs_pick_tile
 constexpr int kRsRow = 20;                       // LDS row stride of the coefficient table (16 taps + 4 pad): a 64-B
                                                  // stride maps every row to one of 4 bank slots (4-way conflicts on b128)
-constexpr int kRsMaxSpan = 4096 + 32;            // staged source samples per channel (rho <= 4)
+constexpr int kRsMaxSpan = 4096 + 32;            // staged source samples per channel: 512-frame tiles up to floor(512 rho) + 28 <= 4128,
+                                                 // i.e. rho < 4101/512 ~ 8.01 (tests/test_gpu_stretch_range.py pins the switch)
 
 // coefficient table -> LDS (rows rotated by rs_slot): 16-byte loads, ALL of a thread's loads requested before the first LDS write.
 // (The table is 8 KB per workgroup out of L2; one dword per thread and trip with a wait in every trip — what the first version
@@ -715,7 +716,7 @@ int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig*
 {
     if (j_end <= j_begin || n_streams == 0) return NAE_OK;
     const size_t count = j_end - j_begin;
-    // tiled kernel while one tile's source span fits the staging buffer (rho <= 4), else the direct kernel
+    // tiled kernel while one tile's source span fits the staging buffer (rho < 4101/512 ~ 8.01), else the direct kernel
     const double rho = (double)pl->step_q32 / 4294967296.0;
     long long span_need = 0;
     const int tile_out = rs_pick_tile(rho, &span_need);

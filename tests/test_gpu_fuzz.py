@@ -26,6 +26,12 @@ def test_fuzz_stretch_one_barrier_pipeline_in_every_shape(nae):
         assert fuzz_stretch.main(cases=10, seed=5, ctx=c, nae=nae) <= 1e-4
 
 
+def test_fuzz_stretch_any_size_and_range_seeded(nae, ctx):
+    """every frame size, the lock, tempo 1/64 ... 16 and rho 1/16 ... 16, edge lengths, batches around the tile-policy switch"""
+    import fuzz_stretch_any
+    assert fuzz_stretch_any.main(cases=16, seed=3, ctx=ctx, nae=nae) <= 1e-4
+
+
 def test_fuzz_wsola_seeded(nae, ctx):
     import fuzz_wsola
     assert fuzz_wsola.main(cases=8, seed=3, ctx=ctx, nae=nae) >= 4     # samples and overlap offsets bit-exact

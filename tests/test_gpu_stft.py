@@ -360,6 +360,22 @@ def test_graph4_matches_node_by_node_oracle(ctx, nae, n_streams, S, semis, rate,
         d.free()
 
 
+@pytest.mark.parametrize("semis,fused", [(12, True), (19, False), (24, False)])
+def test_graph4_past_the_fused_mix(ctx, nae, semis, fused):
+    """test_graph4_matches_node_by_node_oracle at +12 semitones (rho = 2: the mix is staged inside the transposer, mix_resample_tile_kernel)
+    and at +19 / +24 (rho ~ 3.0 / 4: the staging row floor(512 rho) + 28 passes 1536 frames, so the mix and the transposer run as separate
+    launches); the node-by-node oracle holds on both sides"""
+    ctx.prof_reset(); ctx.prof_enable(True)
+    try:
+        test_graph4_matches_node_by_node_oracle(ctx, nae, 5, 9000, semis, 1.0, True, True, (0.5, 0.5))
+        ctx.sync()
+    finally:
+        ctx.prof_enable(False)
+    launched = set(ctx.prof_report())
+    assert ("mix_resample_tile_kernel" in launched) == fused, launched
+    assert fused or "resample_tile_kernel" in launched, launched
+
+
 def stream_stretch(ctx, x, ch, rate, pitch, put_sizes, recv_chunk=3456, device_put=False):
     """drive the SoundTouch-shaped handle the way audio-velocity.cpp:344-440 does: put a frame, drain what is ready"""
     import ctypes as C

@@ -92,13 +92,13 @@ def test_plan_of_every_size(nae, ref, rate, pitch):
 
 
 def test_plan_ratio_at_the_tempo_limits(nae):
-    """R = round(2^24 H / d) ~ 2^24 / tempo depends on the tempo only: a positive int32 at every size and at both tempo limits"""
+    """R = round(2^24 H / d) ~ 2^24 / tempo depends on the tempo only: a positive int32 at every size and at both tempo limits (1/64 and 16,
+    NAE_TEMPO_MIN / NAE_TEMPO_MAX; tests/test_stretch_range_cpu.py checks one step outside them)"""
     import struct
-    for tempo in (0.25, 0.2500001, 3.999, 4.0):
+    for tempo, rate in [(t, 1.0 / t) for t in (0.25, 0.2500001, 3.999, 4.0)] + [(1 / 64, 1 / 64), (16.0, 16.0)]:
         for n_fft in (512, 1024, 2048, 4096):
-            rc, pl = lib_plan(nae, 1.0 / tempo, 1.0 / tempo, n_fft, 10000)
-            if rc:
-                continue           # outside the supported tempo range (the limits are N-independent)
+            rc, pl = lib_plan(nae, rate, 1.0 / tempo, n_fft, 10000)
+            assert rc == 0, (tempo, n_fft, rc)
             assert pl.pv_on
             for r in pl.r_q24:
                 assert 0 < r <= 2 ** 30 and struct.unpack("i", struct.pack("I", r))[0] > 0
