@@ -18,6 +18,7 @@
 #define NAE_FFT_BINS 513        /* r2c bins k = 0..N/2                     */
 #define NAE_HOP 256             /* synthesis hop / spectrum hop (N/4)      */
 #define NAE_OLA_GAIN (2.0f / 3.0f) /* 1 / sum_t hann^2 at hop N/4 = 1/1.5  */
+#define NAE_FORMANT_MAX_GAIN 16.0f /* formant preservation: largest envelope gain of a bin ("Formant preservation") */
 
 /* atan2 -> Q0.32 turns (revision 2 of the K7 / phase specification).  Every step is an IEEE f32 add / mul /
  * fma or a two's-complement integer operation, so C and the GPU give the same 32 bits — and none of them is a division:

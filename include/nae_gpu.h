@@ -36,7 +36,8 @@ extern "C" {
  *   and nae_spectrum_block_ex_f32 (spectrum sizes 256 ... 4096, any hop); nae_spectrum_create accepts those sizes and hops;
  *   NAE_STRETCH_PHASE_LOCK with nae_stretch_block_ex_f32, nae_stretch_create_ex and nae_debug_pv_tile_phase_ex (identity phase locking of the
  *   vocoder); nae_stretch_plan_make_n, nae_stretch_block_n_f32, nae_debug_pv_tile_phase_n and nae_stretch_create_n (vocoder frame sizes
- *   512 ... 4096). */
+ *   512 ... 4096); nae_stretch_formant_lifter, nae_stretch_block_formant_f32 and nae_stretch_create_formant (formant-preserving pitch
+ *   shift). */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -275,6 +276,21 @@ int nae_stretch_block_n_f32(nae_ctx* ctx, double rate, double pitch, unsigned fl
 int nae_debug_pv_tile_phase_n(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, const nae_sig* src, size_t in_len, int ch,
                               size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles, size_t* tile_frames);
 int nae_stretch_create_n(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, nae_stretch** h);
+
+/* Formant preservation ("Formant preservation"): when the node runs both the vocoder and the transposer (a pitch change), each
+ * synthesis frame's magnitudes are multiplied by G[k] = min(E(k rho) / E(k), NAE_FORMANT_MAX_GAIN), where E is the frame's cepstral envelope
+ * (the log2 spectrum liftered to quefrencies below `lifter` samples) and rho = plan.rate_eff, so the output keeps the input's spectral
+ * envelope while its harmonics move.  Phases, lengths, stage order and the transposer are the _n call's; so are flags and n_fft
+ * (NAE_STRETCH_PHASE_LOCK at 1024).  lifter == 0 is exactly the _n call; lifter < 0 or > n_fft / 4: NAE_ERR_INVALID.  Without a pitch change
+ * (no transposer, or no vocoder) a lifter changes nothing.  Samples follow the tolerance path against tests/pv_formant/ref_pv_formant.c;
+ * the result is independent of the tiling, and a handle's output equals the block call's.
+ * nae_stretch_formant_lifter: the default lifter, min(max(sample_rate / 700, 1), n_fft / 4) (68 at 48 kHz, 63 at 44.1 kHz, n_fft 1024); 0 for
+ * an unsupported n_fft or a sample_rate <= 0. */
+int nae_stretch_formant_lifter(int sample_rate, int n_fft);
+int nae_stretch_block_formant_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, int lifter,
+                                  const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst);
+int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags,
+                               int n_fft, int lifter, nae_stretch** h);
 int nae_stretch_put(nae_stretch* h, const float* interleaved, size_t S);
 int nae_stretch_put_host(nae_stretch* h, const float* interleaved_host, size_t S);
 int nae_stretch_flush(nae_stretch* h);

@@ -25,7 +25,8 @@ EXPORTED_SYMBOLS = [
     "nae_amix_sig_f32", "nae_bimix_f32", "nae_bimix2_downmix_f32", "nae_bimix2_interleave_f32",
     "nae_to_f32_interleaved", "nae_clamp_f32", "nae_stretch_plan_make", "nae_stretch_block_f32",
     "nae_debug_pv_tile_phase", "nae_stretch_block_ex_f32", "nae_debug_pv_tile_phase_ex", "nae_stretch_create_ex",
-    "nae_stretch_plan_make_n", "nae_stretch_block_n_f32", "nae_debug_pv_tile_phase_n", "nae_stretch_create_n", "nae_stretch_create", "nae_stretch_put", "nae_stretch_put_host", "nae_stretch_flush",
+    "nae_stretch_plan_make_n", "nae_stretch_block_n_f32", "nae_debug_pv_tile_phase_n", "nae_stretch_create_n",
+    "nae_stretch_formant_lifter", "nae_stretch_block_formant_f32", "nae_stretch_create_formant", "nae_stretch_create", "nae_stretch_put", "nae_stretch_put_host", "nae_stretch_flush",
     "nae_stretch_available", "nae_stretch_receive", "nae_stretch_receive_host", "nae_stretch_destroy",
     "nae_swr_create", "nae_swr_convert_host", "nae_swr_convert", "nae_swr_buffered", "nae_swr_destroy", "nae_mono_to_stereo_f32",
     "nae_spectrum_frames", "nae_spectrum_block_f32", "nae_spectrum_frames_ex", "nae_spectrum_block_ex_f32", "nae_spectrum_create", "nae_spectrum_put",
@@ -148,6 +149,9 @@ def load_library() -> C.CDLL:
         "nae_stretch_block_n_f32": (i, [vp, d, d, u, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_debug_pv_tile_phase_n": (i, [vp, d, d, u, i, P(Sig), sz, i, sz, vp, sz, P(sz), P(sz)]),
         "nae_stretch_create_n": (i, [vp, i, i, f, f, u, i, P(vp)]),
+        "nae_stretch_formant_lifter": (i, [i, i]),
+        "nae_stretch_block_formant_f32": (i, [vp, d, d, u, i, i, P(Sig), sz, i, sz, P(Sig)]),
+        "nae_stretch_create_formant": (i, [vp, i, i, f, f, u, i, i, P(vp)]),
         "nae_stretch_create": (i, [vp, i, i, f, f, P(vp)]), "nae_stretch_put": (i, [vp, vp, sz]),
         "nae_stretch_put_host": (i, [vp, vp, sz]), "nae_stretch_flush": (i, [vp]),
         "nae_stretch_available": (sz, [vp]), "nae_stretch_receive": (i, [vp, vp, sz, P(sz)]),
@@ -430,8 +434,12 @@ class Context:
         return pl
 
     def stretch_block(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig,
-                      phase_lock: bool = False, n_fft: int = 1024):
-        if n_fft != 1024:
+                      phase_lock: bool = False, n_fft: int = 1024, formant: int = 0):
+        """formant: the lifter of formant preservation (formant_lifter() gives the default), 0 = off"""
+        if formant:
+            self._ck(self.lib.nae_stretch_block_formant_f32(self.h, rate, pitch, STRETCH_PHASE_LOCK if phase_lock else 0, n_fft, formant,
+                                                            C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+        elif n_fft != 1024:
             self._ck(self.lib.nae_stretch_block_n_f32(self.h, rate, pitch, STRETCH_PHASE_LOCK if phase_lock else 0, n_fft, C.byref(src), in_len,
                                                       ch, n_streams, C.byref(dst)))
         elif phase_lock:
@@ -497,15 +505,22 @@ class Context:
         self._ck(self.lib.nae_debug_graph4_stages(self.h, C.byref(g), mask))
 
 
+def formant_lifter(sample_rate: int, n_fft: int = 1024) -> int:
+    """the default lifter of formant preservation (nae_stretch_formant_lifter); 0 for an unsupported size"""
+    return int(load_library().nae_stretch_formant_lifter(sample_rate, n_fft))
+
+
 class Stretcher:
-    """The SoundTouch-shaped streaming handle (nae_stretch_create_ex; nae_stretch_create_n for an n_fft other than 1024): put interleaved
-    f32, flush, receive."""
+    """The SoundTouch-shaped streaming handle (nae_stretch_create_ex; nae_stretch_create_n for an n_fft other than 1024;
+    nae_stretch_create_formant with a formant lifter): put interleaved f32, flush, receive."""
 
     def __init__(self, ctx: Context, sample_rate: int, channels: int, rate: float, pitch: float, phase_lock: bool = False,
-                 n_fft: int = 1024):
+                 n_fft: int = 1024, formant: int = 0):
         self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
         flags = STRETCH_PHASE_LOCK if phase_lock else 0
-        if n_fft != 1024:
+        if formant:
+            ctx._ck(ctx.lib.nae_stretch_create_formant(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, formant, C.byref(self.h)))
+        elif n_fft != 1024:
             ctx._ck(ctx.lib.nae_stretch_create_n(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, C.byref(self.h)))
         else:
             ctx._ck(ctx.lib.nae_stretch_create_ex(ctx.h, sample_rate, channels, rate, pitch, flags, C.byref(self.h)))

@@ -19,7 +19,7 @@
 
 namespace nae {
 
-template <int N>
+template <int N, bool kFormant = false>
 struct PvAny {
     static constexpr int M = N / 2, H = N / 4, B = M + 1;
     static constexpr int PAD = (B + 7) & ~7;              // int32 per record: 520 at N = 1024, as the shipped kernels
@@ -30,12 +30,13 @@ struct PvAny {
     using Gm = FftGeom<M, 1>;
     static constexpr int ST = NB * 64;                    // uint32 per per-bin state array of a wave
     static constexpr size_t kWave1 = Gm::SCR * sizeof(cf) + 2 * ST * sizeof(uint32_t);                    // scratch, Qa_{f-1}, sum
-    static constexpr size_t kWave3 = Gm::SCR * sizeof(cf) + PAD * sizeof(cf) + 2 * ST * sizeof(uint32_t); // scratch, Y, Qa_{f-1}, Qs
+    static constexpr size_t kWave3 = Gm::SCR * sizeof(cf) + PAD * sizeof(cf) + 2 * ST * sizeof(uint32_t) // scratch, Y, Qa_{f-1}, Qs
+                                   + (kFormant ? PAD * sizeof(float) : 0);                                 // formant: L / c' / Ls
     static constexpr int kMaxWaves1 = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave1);
     static constexpr int kMaxWaves3 = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave3);
     static constexpr int kWaves1 = kMaxWaves1 < 8 ? kMaxWaves1 : 8;   // 8, 8, 8, 4 waves per workgroup at N = 512 ... 4096
-    static constexpr int kWaves3 = kMaxWaves3 < 8 ? kMaxWaves3 : 8;   // 8, 8, 6, 3
-    // pass-3 waves a CU holds: whole workgroups by LDS (16, 8, 6, 3 at N = 512 ... 4096; registers allow as many)
+    static constexpr int kWaves3 = kMaxWaves3 < 8 ? kMaxWaves3 : 8;   // 8, 8, 6, 3 (formant: 8, 8, 5, 2)
+    // pass-3 waves a CU holds: whole workgroups by LDS (16, 8, 6, 3 at N = 512 ... 4096, formant 16, 8, 5, 2; registers allow as many)
     static constexpr int kResident3 = (int)((160 * 1024) / (512 * sizeof(cf) + kWaves3 * kWave3)) * kWaves3;
     static_assert(N >= 512 && N <= 4096 && (N & (N - 1)) == 0, "vocoder sizes 512 ... 4096");
     static_assert(kWaves1 >= 1 && kWaves3 >= 1, "a wave's state fits a CU's LDS");
@@ -237,16 +238,74 @@ __device__ __forceinline__ void pva_store_block(const PvParams& p, long long b0,
     }
 }
 
-template <int N, bool kUnit>
-__global__ __launch_bounds__(64 * PvAny<N>::kWaves3) void pv_any_synth_kernel(SigViewD src, PvParams p, long long n_items,
-                                                                             const uint32_t* __restrict__ phase_ws, OutViewD out, SpecAnyTables tb)
+// c2r input point m of a real half spectrum R[0..M] (the synthesis's split with T_N, conjugated; pass 3's zc with Y = R + 0i)
+template <int M>
+__device__ __forceinline__ cf pva_c2r_real_point(const float* rs, const cf* tn, int m)
 {
-    using P = PvAny<N>;
+    const cf xk = {rs[m], 0.0f}, xm = {rs[M - m], 0.0f};
+    const cf E = {0.5f * (xk.x + xm.x), 0.5f * (xk.y - xm.y)};
+    const cf D = {0.5f * (xk.x - xm.x), 0.5f * (xk.y + xm.y)};
+    const cf T = tn[m];
+    const cf Q = {T.x * D.x + T.y * D.y, T.x * D.y - T.y * D.x};   // conj(T) D
+    return cf{E.x - Q.y, -(E.y + Q.x)};
+}
+
+// formant preservation ("Formant preservation"), steps 2-5 of one frame: lb[k] = L[k] (k <= M) on entry, ys = the synthesis
+// spectrum.  The cepstrum c = c2r_N(L), lifted to n < q and n > N - q, goes back into lb (c[n] at lb[n], c[N - j] at lb[M - j]: q <= N/4, so the
+// two ranges do not meet); the envelope Ls = Re r2c_N(c') replaces it; then Y[k] *= G[k] = min(2^(Ls(k g) - Ls[k]), NAE_FORMANT_MAX_GAIN).
+template <int N>
+__device__ __forceinline__ void pva_formant(cf* scr, const cf* w512l, const SpecAnyTables& tb, cf* ys, float* lb, int q, float g, int lane)
+{
+    using Gm = typename PvAny<N, true>::Gm;
+    constexpr int M = N / 2;
+    any_first_pass_from<Gm>(scr, w512l, tb.wm, lane, [&](int m) { return pva_c2r_real_point<M>(lb, tb.tn, m); });
+    any_passes8<Gm, (Gm::M / Gm::R1)>(scr, w512l, lane);
+    wave_lds_sync();
+#pragma unroll 1
+    for (int t = lane; t < M; t += 64) {
+        const int n = t < q ? t : (t > M - q ? t + M : -1);
+        if (n >= 0) {
+            const cf z = lds_ld(scr + padx(zpos<Gm>(n >> 1)));
+            lb[t] = (n & 1) ? -z.y * (1.0f / M) : z.x * (1.0f / M);
+        }
+    }
+    wave_lds_sync();
+    auto lifted = [&](int n) -> float { return n < q ? lb[n] : (n > N - q ? lb[n - M] : 0.0f); };
+    any_first_pass_from<Gm>(scr, w512l, tb.wm, lane, [&](int m) { return cf{lifted(2 * m), lifted(2 * m + 1)}; });
+    any_passes8<Gm, (Gm::M / Gm::R1)>(scr, w512l, lane);
+    wave_lds_sync();
+#pragma unroll 1
+    for (int k = lane; k <= M; k += 64) lb[k] = any_rfft_bin<Gm>(scr, tb.tn, k).x;
+    wave_lds_sync();
+#pragma unroll 1
+    for (int k = lane; k <= M; k += 64) {
+        const float u = (float)k * g;
+        float G = 0.0f;
+        if (u <= (float)M) {
+            const int i = (int)u;
+            const float t = u - (float)i;
+            const float lu = i == M ? lb[M] : lb[i] + t * (lb[i + 1] - lb[i]);
+            G = fminf(__builtin_amdgcn_exp2f(lu - lb[k]), NAE_FORMANT_MAX_GAIN);
+        }
+        const cf y = ys[k];
+        ys[k] = cf{G * y.x, G * y.y};
+    }
+    wave_lds_sync();
+}
+
+// kFormant: formant preservation with lifter `lifter` and transposer ratio g (nae_stretch_block_formant_f32); off, both are unused
+template <int N, bool kUnit, bool kFormant>
+__global__ __launch_bounds__(64 * (kFormant ? PvAny<N, true>::kWaves3 : PvAny<N>::kWaves3)) void pv_any_synth_kernel(SigViewD src, PvParams p, long long n_items,
+                                                                                       const uint32_t* __restrict__ phase_ws, OutViewD out,
+                                                                                       SpecAnyTables tb, int lifter, float g)
+{
+    using P = PvAny<N, kFormant>;
     using Gm = typename P::Gm;
     __shared__ __attribute__((aligned(16))) cf w512l[512];
     __shared__ __attribute__((aligned(16))) cf scratch[P::kWaves3 * Gm::SCR];
     __shared__ __attribute__((aligned(16))) cf yspec[P::kWaves3 * P::PAD];
     __shared__ uint32_t state[P::kWaves3 * 2 * P::ST];
+    __shared__ float lbuf[kFormant ? P::kWaves3 * P::PAD : 1];   // formant: L, then c', then Ls
     for (int i = threadIdx.x; i < 512; i += 64 * P::kWaves3) w512l[i] = tb.w512[i];
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -254,6 +313,7 @@ __global__ __launch_bounds__(64 * PvAny<N>::kWaves3) void pv_any_synth_kernel(Si
     if (item >= n_items) return;
     cf* scr = scratch + wave_id() * Gm::SCR;
     cf* ys = yspec + wave_id() * P::PAD;
+    float* lb = lbuf + (kFormant ? wave_id() * P::PAD : 0);
     uint32_t* qp = state + wave_id() * 2 * P::ST + lane;  // [r * 64]: Qa_{f-1} of bin lane + 64 r
     uint32_t* qs = qp + P::ST;                           //           Qs
     const long long sc = item / p.n_tiles;
@@ -296,6 +356,8 @@ __global__ __launch_bounds__(64 * PvAny<N>::kWaves3) void pv_any_synth_kernel(Si
                 const uint32_t q = qs[64 * r] + ((f == 0) ? qa : pva_inc<N>(qa, qp[64 * r], (unsigned)kc, d, R));
                 qs[64 * r] = q;
                 if (k < P::B) ys[k] = pipe_rotate(x, q, qa);         // Y = X e^{i (Qs - Qa)}
+                if constexpr (kFormant)
+                    if (k < P::B) lb[k] = __builtin_amdgcn_logf(fmaxf(sqrt_rn(x.x * x.x + x.y * x.y), 0x1p-40f));   // L = log2 max(|X|, 2^-40)
             }
             qp[64 * r] = qa;
         }
@@ -311,6 +373,7 @@ __global__ __launch_bounds__(64 * PvAny<N>::kWaves3) void pv_any_synth_kernel(Si
             }
         }
         wave_lds_sync();
+        if constexpr (kFormant) pva_formant<N>(scr, w512l, tb, ys, lb, lifter, g, lane);
         // c2r: split with T_N, conjugate, forward FFT_M (the first pass builds its inputs from Y), scale by 1/M and conjugate back
         auto zc = [&](int m) -> cf {
             cf xk = ys[m], xm = ys[P::M - m];
@@ -392,22 +455,31 @@ static int launch_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src, lo
     return nae_check(ctx, hipGetLastError(), "pv_any_scan_kernel");
 }
 
-template <int N>
+template <int N, bool kFormant>
 static int launch_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
-                        const OutViewD& out, const SpecAnyTables& tb)
+                        const OutViewD& out, const SpecAnyTables& tb, int lifter, float g)
 {
-    using P = PvAny<N>;
+    using P = PvAny<N, kFormant>;
+    const char* name = kFormant ? "pv_any_synth_formant_kernel" : "pv_any_synth_kernel";
     const long long items = n_sc * p.n_tiles;
     if (items == 0) return NAE_OK;
     const long long grid = (items + P::kWaves3 - 1) / P::kWaves3;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_synth_kernel: grid too large");
     if (unit_stride)
-        NAE_KLAUNCH(ctx, "pv_any_synth_kernel", (pv_any_synth_kernel<N, true>), dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream,
-                    src, p, items, phase_ws, out, tb);
+        NAE_KLAUNCH(ctx, name, (pv_any_synth_kernel<N, true, kFormant>), dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream,
+                    src, p, items, phase_ws, out, tb, lifter, g);
     else
-        NAE_KLAUNCH(ctx, "pv_any_synth_kernel", (pv_any_synth_kernel<N, false>), dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream,
-                    src, p, items, phase_ws, out, tb);
-    return nae_check(ctx, hipGetLastError(), "pv_any_synth_kernel");
+        NAE_KLAUNCH(ctx, name, (pv_any_synth_kernel<N, false, kFormant>), dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream,
+                    src, p, items, phase_ws, out, tb, lifter, g);
+    return nae_check(ctx, hipGetLastError(), name);
+}
+
+template <int N>
+static int launch_synth_n(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
+                          const OutViewD& out, const SpecAnyTables& tb, int lifter, float g)
+{
+    if (lifter > 0) return launch_synth<N, true>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g);
+    return launch_synth<N, false>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, 0, 0.0f);
 }
 
 } // namespace nae
@@ -423,14 +495,16 @@ bool nae_pv_size_ok(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft =
 // (kResident3 per CU: 16 at 512 down to 3 at 4096) where the stream-channels alone do not give them — more tiles would not add occupancy, only
 // re-analysis (a tile pays one priming and three tail frames) — and never shorter than 64 frames (pv_min_ptile: that many).  A single tile per
 // stream-channel needs no pass 1.  pv_tile forces the tile.
-int nae_pick_pvany_tile(nae_ctx* ctx, int n_fft, size_t frames, size_t n_sc)
+int nae_pick_pvany_tile(nae_ctx* ctx, int n_fft, size_t frames, size_t n_sc, bool formant)
 {
     if (ctx->pv_tile > 0) return ctx->pv_tile;
     const size_t min_tile = ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64;
     const size_t n_cu = (size_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
     if (frames == 0 || n_sc == 0) return (int)min_tile;
-    const size_t resident = n_fft == 512 ? PvAny<512>::kResident3 : n_fft == 2048 ? PvAny<2048>::kResident3
-                          : n_fft == 4096 ? PvAny<4096>::kResident3 : PvAny<1024>::kResident3;
+    const size_t resident = formant ? (n_fft == 512 ? PvAny<512, true>::kResident3 : n_fft == 2048 ? PvAny<2048, true>::kResident3
+                                       : n_fft == 4096 ? PvAny<4096, true>::kResident3 : PvAny<1024, true>::kResident3)
+                                    : (n_fft == 512 ? PvAny<512>::kResident3 : n_fft == 2048 ? PvAny<2048>::kResident3
+                                       : n_fft == 4096 ? PvAny<4096>::kResident3 : PvAny<1024>::kResident3);
     size_t n_tiles = (resident * n_cu + n_sc - 1) / n_sc;
     const size_t max_tiles = (frames + min_tile - 1) / min_tile;
     if (n_tiles > max_tiles) n_tiles = max_tiles;
@@ -455,16 +529,16 @@ int nae_launch_pvany_phase(nae_ctx* ctx, int n_fft, const PvParams& p, const Sig
 }
 
 int nae_launch_pvany_synth(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride,
-                           const uint32_t* phase_ws, const OutViewD& out)
+                           const uint32_t* phase_ws, const OutViewD& out, int lifter, float g)
 {
     SpecAnyTables tb;
     int rc = nae_spec_any_tables(ctx, n_fft, &tb);
     if (rc) return rc;
     switch (n_fft) {
-    case 512: return launch_synth<512>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb);
-    case 1024: return launch_synth<1024>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb);
-    case 2048: return launch_synth<2048>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb);
-    case 4096: return launch_synth<4096>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb);
+    case 512: return launch_synth_n<512>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g);
+    case 1024: return launch_synth_n<1024>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g);
+    case 2048: return launch_synth_n<2048>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g);
+    case 4096: return launch_synth_n<4096>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g);
     default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
     }
 }

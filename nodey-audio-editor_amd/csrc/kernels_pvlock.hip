@@ -310,9 +310,72 @@ constexpr size_t kLockSynthWave = kPadScratchCf * sizeof(cf) + kT1024Pad * sizeo
 constexpr size_t kLdsLockSynth = kLdsTablesPad + kWaves * kLockSynthWave;
 static_assert(2 * kLdsLockSynth <= 160 * 1024, "two workgroups per CU");
 
-template <bool kUnit>
+// formant preservation ("Formant preservation") of one frame, in two steps around the rotation.  lock_formant_log: L = log2
+// max(|X|, 2^-40) from this lane's bins k = lane + 64 r (r = 8: k = 512) into the FFT scratch, as floats.  lock_formant_apply: the cepstrum of L
+// (in registers: n = 2 (lane + 64 r) + {0, 1}), lifted, its r2c Ls (into the scratch), and Y[k] *= G[k].
+__device__ __forceinline__ void lock_formant_log(const cf (&v)[8], cf nyq, cf* scratch, int lane)
+{
+    float* lf = reinterpret_cast<float*>(scratch);
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const cf x = r < 8 ? v[r] : nyq;
+        if (r < 8 || lane == 0) lf[r < 8 ? lane + 64 * r : 512] = __builtin_amdgcn_logf(fmaxf(sqrt_rn(x.x * x.x + x.y * x.y), 0x1p-40f));
+    }
+    wave_lds_sync();
+}
+
+__device__ __forceinline__ void lock_formant_apply(cf (&y)[8], cf& ynyq, cf* scratch, const cf* twa, const cf* w64, const cf* t1024, int q, float g,
+                                                   int lane)
+{
+    float* lf = reinterpret_cast<float*>(scratch);
+    // cepstrum c = c2r_N(L + 0i): the synthesis's split, FFT and 1/512
+    cf u[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int k = lane + 64 * r;
+        const cf Xk = {lf[k], 0.0f}, Xm = {lf[512 - k], 0.0f};
+        const cf E = {0.5f * (Xk.x + Xm.x), 0.5f * (Xk.y - Xm.y)};
+        const cf D = {0.5f * (Xk.x - Xm.x), 0.5f * (Xk.y + Xm.y)};
+        const cf T = t1024[k];
+        const cf Q = {T.x * D.x + T.y * D.y, T.x * D.y - T.y * D.x};
+        u[r] = cf{E.x - Q.y, -(E.y + Q.x)};
+    }
+    wave_lds_sync();
+    fft512_pad(u, make_fft_lds(scratch, twa, w64, lane));
+    // lifter, then the envelope Ls = Re r2c_N(c') (packed pairs, no window)
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int n = 2 * (lane + 64 * r);
+        const float c0 = u[r].x * (1.0f / 512.0f), c1 = -u[r].y * (1.0f / 512.0f);
+        u[r] = cf{(n < q || n > NAE_FFT_N - q) ? c0 : 0.0f, (n + 1 < q || n + 1 > NAE_FFT_N - q) ? c1 : 0.0f};
+    }
+    fft512_pad(u, make_fft_lds(scratch, twa, w64, lane));
+    const cf ls512 = rfft_split<false>(u, scratch, t1024, lane);
+#pragma unroll
+    for (int r = 0; r < 8; r++) lf[lane + 64 * r] = u[r].x;
+    if (lane == 0) lf[512] = ls512.x;
+    wave_lds_sync();
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const int k = r < 8 ? lane + 64 * r : 512;
+        const float uk = (float)k * g;
+        float G = 0.0f;
+        if (uk <= 512.0f) {
+            const int i = (int)uk;
+            const float t = uk - (float)i;
+            const float lu = i == 512 ? lf[512] : lf[i] + t * (lf[i + 1] - lf[i]);
+            G = fminf(__builtin_amdgcn_exp2f(lu - lf[k]), NAE_FORMANT_MAX_GAIN);
+        }
+        cf& yk = r < 8 ? y[r] : ynyq;
+        yk = cf{G * yk.x, G * yk.y};
+    }
+    wave_lds_sync();                              // Y replaces Ls in the scratch
+}
+
+// kFormant: formant preservation with lifter `lifter` and transposer ratio g; off, both are unused
+template <bool kUnit, bool kFormant>
 __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src, PvParams p, long long n_items, const uint32_t* __restrict__ phase_ws,
-                                                                   OutViewD out, Tables tb)
+                                                                   OutViewD out, Tables tb, int lifter, float g)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* hann; cf *t1024, *w64, *twa;
@@ -382,11 +445,22 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
                     if (k < NAE_FFT_BINS) p.carry_out[sc * kT1024Pad + k] = nq[r];
                 }
             }
-            // synthesis spectrum Y = X e^{i (Qs - Qa)} in natural order, then the c2r pre-twiddle of the oracle's irfft (conjugated: inverse =
-            // conj(FFT(conj Z)) / 512)
+            // synthesis spectrum Y = X e^{i (Qs - Qa)} (formant: G X e^{i (Qs - Qa)}) in natural order, then the c2r pre-twiddle of the oracle's
+            // irfft (conjugated: inverse = conj(FFT(conj Z)) / 512)
+            if constexpr (kFormant) {
+                lock_formant_log(v, nyq, scratch, lane);
 #pragma unroll
-            for (int r = 0; r < 8; r++) scratch[lane + 64 * r] = pipe_rotate(v[r], nq[r], qa[r]);
-            if (lane == 0) scratch[512] = pipe_rotate(nyq, nq[8], qa[8]);
+                for (int r = 0; r < 8; r++) v[r] = pipe_rotate(v[r], nq[r], qa[r]);
+                nyq = pipe_rotate(nyq, nq[8], qa[8]);
+                lock_formant_apply(v, nyq, scratch, twa, w64, t1024, lifter, g, lane);
+#pragma unroll
+                for (int r = 0; r < 8; r++) scratch[lane + 64 * r] = v[r];
+                if (lane == 0) scratch[512] = nyq;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 8; r++) scratch[lane + 64 * r] = pipe_rotate(v[r], nq[r], qa[r]);
+                if (lane == 0) scratch[512] = pipe_rotate(nyq, nq[8], qa[8]);
+            }
             wave_lds_sync();
 #pragma unroll
             for (int r = 0; r < 8; r++) {
@@ -462,7 +536,8 @@ int nae_pick_pvlock_tile(nae_ctx* ctx, size_t frames, size_t n_sc)
 
 // the kernels here take more than 64 KiB of dynamic LDS: the attribute is set as for the vocoder pipeline (nae_pv_lds_attr), once per context
 // and kernel, the scan kernel at its largest size
-constexpr unsigned kAttrLockMap = 1u << 12, kAttrLockScan = 1u << 13, kAttrLockSynth = 1u << 14;   // nae_ctx::pv_attr_done (pipeline: bits 0-10)
+constexpr unsigned kAttrLockMap = 1u << 12, kAttrLockScan = 1u << 13, kAttrLockSynth = 1u << 14,   // nae_ctx::pv_attr_done (pipeline: bits 0-10)
+                   kAttrLockSynthF = 1u << 15;
 
 int nae_launch_pvlock_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
                             uint32_t* phase_ws, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out)
@@ -493,22 +568,32 @@ int nae_launch_pvlock_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src
     return nae_check(ctx, hipGetLastError(), "pvlock_scan_kernel");
 }
 
-int nae_launch_pvlock_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
-                            const OutViewD& out)
+template <bool kFormant>
+static int launch_lock_synth(nae_ctx* ctx, unsigned attr_bit, const char* name, const PvParams& p, const SigViewD& src, long long items, bool unit_stride,
+                             const uint32_t* phase_ws, const OutViewD& out, int lifter, float g)
 {
-    const long long items = n_sc * p.n_tiles;
-    if (items == 0) return NAE_OK;
     const long long grid = (items + kWaves - 1) / kWaves;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_synth_kernel: grid too large");
     const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
-    int rc = nae_pv_lds_attr(ctx, kAttrLockSynth, kLdsLockSynth, reinterpret_cast<const void*>(pvlock_synth_kernel<true>),
-                             reinterpret_cast<const void*>(pvlock_synth_kernel<false>));
+    int rc = nae_pv_lds_attr(ctx, attr_bit, kLdsLockSynth, reinterpret_cast<const void*>(pvlock_synth_kernel<true, kFormant>),
+                             reinterpret_cast<const void*>(pvlock_synth_kernel<false, kFormant>));
     if (rc) return rc;
     if (unit_stride)
-        NAE_KLAUNCH(ctx, "pvlock_synth_kernel", (pvlock_synth_kernel<true>), dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream,
-                    src, p, items, phase_ws, out, tb);
+        NAE_KLAUNCH(ctx, name, (pvlock_synth_kernel<true, kFormant>), dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream,
+                    src, p, items, phase_ws, out, tb, lifter, g);
     else
-        NAE_KLAUNCH(ctx, "pvlock_synth_kernel", (pvlock_synth_kernel<false>), dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream,
-                    src, p, items, phase_ws, out, tb);
-    return nae_check(ctx, hipGetLastError(), "pvlock_synth_kernel");
+        NAE_KLAUNCH(ctx, name, (pvlock_synth_kernel<false, kFormant>), dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream,
+                    src, p, items, phase_ws, out, tb, lifter, g);
+    return nae_check(ctx, hipGetLastError(), name);
+}
+
+// lifter > 0: formant preservation (pvlock_synth_formant_kernel)
+int nae_launch_pvlock_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
+                            const OutViewD& out, int lifter, float g)
+{
+    const long long items = n_sc * p.n_tiles;
+    if (items == 0) return NAE_OK;
+    if (lifter > 0)
+        return launch_lock_synth<true>(ctx, kAttrLockSynthF, "pvlock_synth_formant_kernel", p, src, items, unit_stride, phase_ws, out, lifter, g);
+    return launch_lock_synth<false>(ctx, kAttrLockSynth, "pvlock_synth_kernel", p, src, items, unit_stride, phase_ws, out, 0, 0.0f);
 }

@@ -688,13 +688,15 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
     return nae_check(ctx, hipGetLastError(), "pv_scan_kernel");
 }
 
-// pass 3 (locked: L3) from the records of pass 2 (or, one tile and nothing carried in, from zero)
+// pass 3 (locked: L3) from the records of pass 2 (or, one tile and nothing carried in, from zero); lifter > 0 with both stages on: formant
+// preservation (unlocked: on the size-generic pass 3 at every size, which reads the same records)
 int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
-                        const nae_pv_segment* seg, int frames_per_step)
+                        const nae_pv_segment* seg, int frames_per_step, int lifter)
 {
     if (phase_tile <= 0 || tile < phase_tile || tile % phase_tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
     PvParams p = make_pv_params(*pl, in_len, ch, tile, seg);
+    lifter = nae_formant_lifter_eff(*pl, lifter);
     const long long cnt = p.f_stop - p.f_origin;
     p.phase_step = tile / phase_tile;
     p.phase_tiles = (int)((cnt + phase_tile - 1) / phase_tile);
@@ -705,8 +707,10 @@ int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
         p.carry_frame = p.f_stop - 1;
     }
     const long long n_sc = (long long)n_streams * ch;
-    if (lock) return nae_launch_pvlock_synth(ctx, p, to_view(src), n_sc, src->frame_stride == 1, phase_ws, to_out(out));
-    if (n_fft != NAE_FFT_N || ctx->dbg_pv_any) return nae_launch_pvany_synth(ctx, n_fft, p, to_view(src), n_sc, src->frame_stride == 1, phase_ws, to_out(out));
+    const float g = (float)pl->rate_eff;                   // formant preservation: the transposer ratio
+    if (lock) return nae_launch_pvlock_synth(ctx, p, to_view(src), n_sc, src->frame_stride == 1, phase_ws, to_out(out), lifter, g);
+    if (n_fft != NAE_FFT_N || ctx->dbg_pv_any || lifter > 0)
+        return nae_launch_pvany_synth(ctx, n_fft, p, to_view(src), n_sc, src->frame_stride == 1, phase_ws, to_out(out), lifter, g);
     return nae_launch_pv_pipe(ctx, p, to_view(src), n_sc, phase_ws, to_out(out), src->frame_stride == 1, frames_per_step);
 }
 

@@ -554,6 +554,13 @@ int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft)
     return NAE_OK;
 }
 
+// the lifter of the _formant entries: 0 (off) ... n_fft / 4, else NAE_ERR_INVALID
+int nae_formant_check(nae_ctx* ctx, int n_fft, int lifter)
+{
+    if (lifter < 0 || lifter > n_fft / 4) return nae_fail(ctx, NAE_ERR_INVALID, "formant lifter must be in [0, n_fft / 4]");
+    return NAE_OK;
+}
+
 // a 2-input mix node in front of the stretch node (graph4): when the transposer runs first it can mix while staging
 struct nae_mix_front {
     const nae_sig* a;
@@ -565,7 +572,8 @@ struct nae_mix_front {
 // (nae_debug_graph4_stages: scheduling experiments run the two from separate calls; the intermediate signal stays in the
 // context's workspace between them).
 static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
-                              const nae_sig* dst, const nae_mix_front* front, int stages = 3, bool lock = false, int n_fft = NAE_FFT_N)
+                              const nae_sig* dst, const nae_mix_front* front, int stages = 3, bool lock = false, int n_fft = NAE_FFT_N,
+                              int lifter = 0)
 {
     if (!ctx) return NAE_ERR_INVALID;
     int rc;
@@ -631,8 +639,9 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
     if (pl.pv_on) {
         int phase_tile = 0, fps = 1;
         int tile;
+        const int q = nae_formant_lifter_eff(pl, lifter);
         if (lock) tile = phase_tile = nae_pick_pvlock_tile(ctx, pl.frames, n_streams * ch);
-        else if (n_fft != NAE_FFT_N || ctx->dbg_pv_any) tile = phase_tile = nae_pick_pvany_tile(ctx, n_fft, pl.frames, n_streams * ch);
+        else if (n_fft != NAE_FFT_N || ctx->dbg_pv_any || q > 0) tile = phase_tile = nae_pick_pvany_tile(ctx, n_fft, pl.frames, n_streams * ch, q > 0);
         else tile = nae_pick_pv_shape(ctx, pl.frames, n_streams * ch, &phase_tile, &fps);
         rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, n_fft, pl.frames, ch, n_streams, phase_tile));
         if (rc) return rc;
@@ -640,7 +649,7 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
         rc = nae_launch_pv_phase(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, phase_tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
         if (rc) return rc;
         rc = nae_launch_pv_synth(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, tile, phase_tile, static_cast<const uint32_t*>(ctx->ws_phase), pv_dst,
-                                 &seg, fps);
+                                 &seg, fps, q);
         if (rc) return rc;
     }
     if (pl.rs_on && !pl.rs_first) {
@@ -675,6 +684,24 @@ int nae_stretch_block_n_f32(nae_ctx* ctx, double rate, double pitch, unsigned fl
     const int rc = nae_stretch_n_check(ctx, flags, n_fft);
     if (rc) return rc;
     return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft);
+}
+
+int nae_stretch_formant_lifter(int sample_rate, int n_fft)
+{
+    if (!nae_pv_size_ok(n_fft) || sample_rate <= 0) return 0;
+    int q = sample_rate / 700;
+    if (q < 1) q = 1;
+    return q < n_fft / 4 ? q : n_fft / 4;
+}
+
+int nae_stretch_block_formant_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, int lifter, const nae_sig* src, size_t in_len,
+                                  int ch, size_t n_streams, const nae_sig* dst)
+{
+    if (!ctx) return NAE_ERR_INVALID;
+    int rc = nae_stretch_n_check(ctx, flags, n_fft);
+    if (rc) return rc;
+    if ((rc = nae_formant_check(ctx, n_fft, lifter))) return rc;
+    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft, lifter);
 }
 
 int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch,

@@ -112,20 +112,24 @@ struct nae_pv_segment {
     bool carry_by_synth = false;  // the segment is synthesised as ONE tile and pass 3 itself writes carry_out (no pass 1)
 };
 // kernels_stft.hip: the vocoder's passes, unlocked or (lock, NAE_STRETCH_PHASE_LOCK) with identity phase locking on the kernels of kernels_pvlock.hip;
-// frame size n_fft (512 ... 4096; not 1024, or the debug key pv_any: the size-generic kernels of kernels_pv_any.hip)
+// frame size n_fft (512 ... 4096; not 1024, or the debug key pv_any: the size-generic kernels of kernels_pv_any.hip).  lifter > 0: pass 3 preserves
+// the formants (nae_formant_lifter_eff; unlocked, at every size on the size-generic pass 3)
 size_t nae_pv_workspace_bytes(bool lock, int n_fft, size_t n_frames, int ch, size_t n_streams, int tile);
 int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg);
 int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
-                        const nae_pv_segment* seg, int frames_per_step);
+                        const nae_pv_segment* seg, int frames_per_step, int lifter = 0);
+// the lifter pass 3 runs with: formant preservation applies only when the plan runs both the vocoder and the transposer
+inline int nae_formant_lifter_eff(const nae_stretch_plan& pl, int lifter) { return pl.pv_on && pl.rs_on ? lifter : 0; }
 int nae_pick_pvlock_tile(nae_ctx* ctx, size_t frames, size_t n_sc);   // kernels_pvlock.hip
 // kernels_pv_any.hip: the vocoder sizes (512, 1024, 2048, 4096), the record length of a size (int32: N/2 + 1 padded to a multiple of 8), the
-// tile of a size-generic block call
+// tile of a size-generic block call (formant: for the formant pass 3)
 bool nae_pv_size_ok(int n_fft);
 size_t nae_pv_record_pad(int n_fft);
-int nae_pick_pvany_tile(nae_ctx* ctx, int n_fft, size_t frames, size_t n_sc);
+int nae_pick_pvany_tile(nae_ctx* ctx, int n_fft, size_t frames, size_t n_sc, bool formant = false);
 int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft);   // nae_api.hip: flags and size of the _n entries
+int nae_formant_check(nae_ctx* ctx, int n_fft, int lifter);         // nae_api.hip: the lifter of the _formant entries
 int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t src_len, int ch,
                         size_t n_streams, const float* d_tab, const nae_sig* out, size_t j_begin, size_t j_end);
 int nae_launch_mix_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* a, const nae_sig* b, float va, float vb,

@@ -17,6 +17,7 @@ struct nae_stretch {
     double rate, pitch;
     bool lock = false;            // NAE_STRETCH_PHASE_LOCK (nae_stretch_create_ex)
     int n_fft = NAE_FFT_N;        // vocoder frame size, hop n_fft / 4 (nae_stretch_create_n)
+    int lifter = 0;               // formant preservation's lifter, 0 = off (nae_stretch_create_formant)
     nae_stretch_plan pl{};        // parameters (in_len = 0)
     DevFifo in;                   // interleaved input, sample-frames [in.base, in_total)
     size_t in_total = 0;
@@ -86,7 +87,8 @@ int stretch_pv_stage(nae_stretch* h, const nae_stretch_plan& pl, const nae_sig& 
                        h->blocks_done ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
     rc = nae_launch_pv_phase(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
     if (rc) return rc;
-    rc = nae_launch_pv_synth(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
+    rc = nae_launch_pv_synth(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps,
+                             h->lifter);
     if (rc) return rc;
     h->carry_cur ^= 1;
     h->blocks_done = B_r;
@@ -293,9 +295,16 @@ int nae_stretch_create_ex(nae_ctx* ctx, int sample_rate, int channels, float rat
 
 int nae_stretch_create_n(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, nae_stretch** h)
 {
+    return nae_stretch_create_formant(ctx, sample_rate, channels, rate, pitch, flags, n_fft, 0, h);
+}
+
+int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
+                               nae_stretch** h)
+{
     if (!ctx || !h) return NAE_ERR_INVALID;
-    const int chk = nae_stretch_n_check(ctx, flags, n_fft);
+    int chk = nae_stretch_n_check(ctx, flags, n_fft);
     if (chk) return chk;
+    if ((chk = nae_formant_check(ctx, n_fft, lifter))) return chk;
     (void)nae_use_device(ctx);
     *h = nullptr;
     // audio-velocity.cpp:371-379 rejects rates outside 8..48 kHz for SoundTouch; the vocoder has no such
@@ -314,6 +323,7 @@ int nae_stretch_create_n(nae_ctx* ctx, int sample_rate, int channels, float rate
     s->pitch = pitch;
     s->lock = (flags & NAE_STRETCH_PHASE_LOCK) != 0;
     s->n_fft = n_fft;
+    s->lifter = lifter;
     s->pl = pl;
     *h = s;
     return NAE_OK;

@@ -24,6 +24,10 @@ namespace processor
 	// one of those, or a size other than 1024 with "phase_lock": true: Runtime_error "Wrong field: fft_size"; written back only when not 1024.
 	// With "algorithm": "soundtouch" the key is kept and has no effect.
 	int fft_size_from_json(const Json::Value& value, const char* node_name, bool phase_lock);
+	// "formant" (bool, optional, Pitch_modifier only): formant-preserving pitch shift (nae_stretch_create_formant, lifter
+	// nae_stretch_formant_lifter(sample rate, fft_size)).  No key: false; a value that is not a bool: Runtime_error "Wrong field: formant";
+	// written back only when true.  It combines with "phase_lock" and "fft_size"; with "algorithm": "soundtouch" it is kept and has no effect.
+	bool formant_from_json(const Json::Value& value, const char* node_name);
 
 	class Velocity_modifier : public infra::Processor
 	{
@@ -58,6 +62,7 @@ namespace processor
 		Stretch_algorithm algorithm = default_stretch_algorithm();
 		bool phase_lock = false;
 		int fft_size = 1024;
+		bool formant = false;
 
 	  public:
 
@@ -74,7 +79,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock, fft_size when not the default
+		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock, fft_size, formant when not the default
 		void deserialize(const Json::Value& value) override;  // :502-505
 	};
 

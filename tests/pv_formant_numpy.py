@@ -1,0 +1,81 @@
+"""Independent float64 statement of formant preservation ("Formant preservation") on the K7 node at frame size N, with numpy's
+own FFT: tests/pv_sizes_numpy.py's vocoder with each synthesis frame's magnitudes multiplied by G[k] of the frame's cepstral envelope.  It pins
+the CPU statement tests/pv_formant/ref_pv_formant.c to the specification."""
+import numpy as np
+
+import pv_sizes_numpy
+from golden import pv_numpy
+
+
+def gain(X, N, q, g):
+    """G[0..N/2] of one analysis spectrum X (steps 1-5)"""
+    M = N // 2
+    L = np.log2(np.maximum(np.abs(X), 2.0 ** -40))
+    c = np.fft.irfft(L, N)
+    n = np.arange(N)
+    c[~((n < q) | (n > N - q))] = 0.0
+    Ls = np.fft.rfft(c).real
+    u = np.float64(np.float32(np.arange(M + 1, dtype=np.float32) * np.float32(g)))
+    G = np.zeros(M + 1)
+    ok = u <= M
+    i = np.minimum(u, M).astype(np.int64)
+    t = u - i
+    lu = np.where(i == M, Ls[M], Ls[np.minimum(i, M - 1)] + t * (Ls[np.minimum(i + 1, M)] - Ls[np.minimum(i, M - 1)]))
+    G[ok] = np.minimum(np.exp2(lu - Ls), 16.0)[ok]
+    return G
+
+
+def vocoder(x, pl, M, q, g):
+    """one channel, float64 in/out"""
+    N = pl["N"]
+    H, bins, sh = N // 4, N // 2 + 1, 32 - int(np.log2(N))
+    w = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(N) / N)
+    k = np.arange(bins)
+    v = np.zeros(M + N + H)
+    qs = qa_prev = None
+    s_prev = 0
+    for f in range(pl["frames"]):
+        s = (((f - 1) * pl["ha"] + (1 << 23)) >> 24) - N // 2
+        idx = s + np.arange(N)
+        ok = (idx >= 0) & (idx < x.size)
+        fr = np.where(ok, x[np.clip(idx, 0, max(x.size - 1, 0))] if x.size else 0.0, 0.0)
+        X = np.fft.rfft(fr * w)
+        qa = np.round(np.angle(X) / (2 * np.pi) * 2 ** 32).astype(np.int64) & 0xFFFFFFFF
+        if f == 0:
+            qs = qa.copy()
+        else:
+            d = s - s_prev
+            R = ((H << 24) + d // 2) // d
+            e = ((k * d) & (N - 1)) << sh
+            dw = (qa - qa_prev - e) & 0xFFFFFFFF
+            dw = np.where(dw >= 2 ** 31, dw - 2 ** 32, dw)
+            adv = ((k * H) & (N - 1)) << sh
+            qs = (qs + adv + ((dw * R + (1 << 23)) >> 24)) & 0xFFFFFFFF
+        qa_prev, s_prev = qa, s
+        ph = np.where(qs >= 2 ** 31, qs - 2 ** 32, qs) / 2.0 ** 32 * 2 * np.pi
+        Y = gain(X, N, q, g) * np.abs(X) * np.exp(1j * ph)
+        Y[0] = Y[0].real
+        Y[-1] = Y[-1].real
+        y = np.fft.irfft(Y, N)
+        o = (f - 1) * H - N // 2
+        lo, hi = max(o, 0), min(o + N, M)
+        if hi > lo:
+            v[lo:hi] += (w * y)[lo - o:hi - o]
+    return v[:M] * (2.0 / 3.0)
+
+
+def stretch(x, ch, rate, pitch, N, q):
+    """interleaved [L*ch] -> interleaved [out_len*ch], float64; both stages on (a pitch change)"""
+    x = np.asarray(x, np.float64).reshape(-1, ch)
+    pl = pv_sizes_numpy.plan(rate, pitch, x.shape[0], N)
+    assert pl["pv_on"] and pl["rs_on"]
+    g = float(np.float32(pl["rho"]))
+    out = np.zeros((pl["out_len"], ch))
+    tr = pv_numpy.transposer
+    for c in range(ch):
+        s = x[:, c]
+        if pl["rs_first"]:
+            out[:, c] = vocoder(tr(s, pl, pl["mid"]), pl, pl["out_len"], q, g)
+        else:
+            out[:, c] = tr(vocoder(s, pl, pl["mid"], q, g), pl, pl["out_len"])
+    return out.reshape(-1)
