@@ -2,7 +2,8 @@
 """Randomised differential run (GPU box) over the whole supported K7 range: frame sizes 512 ... 4096 (the phase lock at 1024), log-uniform
 tempo over [1/64, 16] and transposer ratio over [1/16, 16], edge-heavy input lengths, batches around the size-generic tile policy's switch
 (kResident3 * n_cu stream-channels) and planar / interleaved layouts, against the matching CPU restatement (orc at 1024, ref_pv_sizes.c at the
-other sizes, ref_pv_lock.c locked).  Returns the worst relative RMS error.
+other sizes, ref_pv_lock.c locked).  A formant dimension from its own generator (the draws above stay the seed's): half the cases take a lifter
+in 1 ... N/4 (ref_pv_formant.c is then the restatement), and every case an input level 2^-36 ... 2^20.  Returns the worst relative RMS error.
     python tests/tools/fuzz_stretch_any.py [cases=40] [seed=1]"""
 import ctypes as C
 import os
@@ -15,6 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import naeload
 import orc
+import pv_formant_ref
 import pv_lock_ref
 import pv_sizes_ref
 
@@ -41,7 +43,8 @@ def main(cases=40, seed=1, ctx=None, nae=None, max_samples=4_000_000):
     if ctx is None:
         ctx = nae.Context(0)
     tmp = tempfile.mkdtemp(prefix="fuzz_any_")
-    ref, lref = pv_sizes_ref.build(tmp), pv_lock_ref.build(tmp)
+    ref, lref, fref = pv_sizes_ref.build(tmp), pv_lock_ref.build(tmp), pv_formant_ref.build(tmp)
+    frng = np.random.default_rng([seed, 7])
     n_cu = cu_count()
     worst = 0.0
     for k in range(cases):
@@ -63,11 +66,14 @@ def main(cases=40, seed=1, ctx=None, nae=None, max_samples=4_000_000):
             n_streams = max(1, n_streams // 4)
         planar_in, planar_out = bool(rng.integers(2)), bool(rng.integers(2))
         x = (0.5 * rng.uniform(-1, 1, (n_streams, L, ch))).astype(np.float32)
+        lifter = int(frng.integers(1, N // 4 + 1)) if frng.integers(2) else 0
+        level = 2.0 ** int(frng.integers(-36, 21))
+        x *= np.float32(level)
         flat = np.ascontiguousarray(x.transpose(0, 2, 1)).reshape(-1) if planar_in else x.reshape(-1)
         d_x, d_o = ctx.array(flat), ctx.empty(max(1, n_streams * pl.out_len * ch))
         src = nae.Sig.planar(d_x.ptr, L, ch) if planar_in else nae.Sig.interleaved(d_x.ptr, L, ch)
         dst = nae.Sig.planar(d_o.ptr, pl.out_len, ch) if planar_out else nae.Sig.interleaved(d_o.ptr, pl.out_len, ch)
-        ctx.stretch_block(rate, pitch, src, L, ch, n_streams, dst, phase_lock=lock, n_fft=n_fft)
+        ctx.stretch_block(rate, pitch, src, L, ch, n_streams, dst, phase_lock=lock, n_fft=n_fft, formant=lifter)
         out = d_o.download()[: n_streams * pl.out_len * ch]
         out = out.reshape(n_streams, ch, pl.out_len).transpose(0, 2, 1) if planar_out else out.reshape(n_streams, pl.out_len, ch)
         d_x.free(); d_o.free()
@@ -75,7 +81,9 @@ def main(cases=40, seed=1, ctx=None, nae=None, max_samples=4_000_000):
         errs = []
         for s in sorted({0, n_streams // 2, n_streams - 1}):
             xs = x[s].reshape(-1)
-            if lock:
+            if lifter:
+                want = pv_formant_ref.stretch(fref, xs, ch, rate, pitch, n_fft, lifter, lock=lock)
+            elif lock:
                 want = pv_lock_ref.stretch(lref, xs, ch, rate, pitch, 1)
             elif n_fft == 1024:
                 want = orc.stretch(xs, ch, rate, pitch)
@@ -83,13 +91,13 @@ def main(cases=40, seed=1, ctx=None, nae=None, max_samples=4_000_000):
                 want = pv_sizes_ref.stretch(ref, xs, ch, rate, pitch, n_fft)
             want = want.reshape(-1, ch)
             assert want.shape == out[s].shape, (want.shape, out[s].shape)
-            if want.size and np.sqrt(np.mean(want.astype(np.float64) ** 2)) >= 1e-6:    # near-silent references: the edge-length rule
+            if want.size and np.sqrt(np.mean(want.astype(np.float64) ** 2)) >= 1e-6 * level:    # near-silent references: the edge-length rule
                 errs.append(rel_rms(out[s], want))
         e = max(errs) if errs else 0.0
         worst = max(worst, e)
         flag = "" if e <= 1e-4 else "   <-- ABOVE TOLERANCE"
         print(f"case {k:3d}: N {n_fft:4d}{' lock' if lock else '     '} streams {n_streams:5d} ch {ch} L {L:6d} tempo {tempo:8.5f} rho {rho:8.5f} "
-              f"{'P' if planar_in else 'I'}->{'P' if planar_out else 'I'} out {pl.out_len:7d}  rel-RMS {e:.2e}{flag}", flush=True)
+              f"{'P' if planar_in else 'I'}->{'P' if planar_out else 'I'} q {lifter:4d} level 2^{int(np.log2(level)):+d} out {pl.out_len:7d}  rel-RMS {e:.2e}{flag}", flush=True)
     print(f"worst rel-RMS {worst:.2e} over {cases} cases (tolerance 1e-4)")
     return worst
 
