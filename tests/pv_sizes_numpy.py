@@ -1,7 +1,9 @@
 """Independent float64 restatement of the K7 node at frame size N (analysis and synthesis frames of N samples, hop
 H = N/4, Hann/Hann, gain 2/3, exact Q0.32 phase accumulation; the transposer and the stage order of every size), with numpy's own FFT.
 tests/golden/pv_numpy.py states the same node at N = 1024 and is kept as it is; this one takes N as a parameter and reuses its
-N-independent parts (plan fields, transposer).  It pins the CPU restatement tests/pv_sizes/ref_pv_sizes.c to the specification at every size."""
+N-independent parts (plan fields, transposer).  With a lifter q > 0 it states formant preservation ("Formant preservation"):
+each synthesis frame's magnitudes multiplied by G[k] of the frame's cepstral envelope.  It pins the CPU statement tests/pv_ref/ref_pv.c to the
+specification at every size."""
 import numpy as np
 
 from golden import pv_numpy
@@ -16,8 +18,26 @@ def plan(rate, pitch, L, N):
     return pl
 
 
-def vocoder(x, pl, M):
-    """one channel, float64 in/out"""
+def gain(X, N, q, g):
+    """G[0..N/2] of one analysis spectrum X (steps 1-5)"""
+    M = N // 2
+    L = np.log2(np.maximum(np.abs(X), 2.0 ** -40))
+    c = np.fft.irfft(L, N)
+    n = np.arange(N)
+    c[~((n < q) | (n > N - q))] = 0.0
+    Ls = np.fft.rfft(c).real
+    u = np.float64(np.float32(np.arange(M + 1, dtype=np.float32) * np.float32(g)))
+    G = np.zeros(M + 1)
+    ok = u <= M
+    i = np.minimum(u, M).astype(np.int64)
+    t = u - i
+    lu = np.where(i == M, Ls[M], Ls[np.minimum(i, M - 1)] + t * (Ls[np.minimum(i + 1, M)] - Ls[np.minimum(i, M - 1)]))
+    G[ok] = np.minimum(np.exp2(lu - Ls), 16.0)[ok]
+    return G
+
+
+def vocoder(x, pl, M, q=0, g=1.0):
+    """one channel, float64 in/out; q > 0: formant preservation with transposer ratio g"""
     N = pl["N"]
     H, bins, sh = N // 4, N // 2 + 1, 32 - int(np.log2(N))
     w = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(N) / N)
@@ -46,7 +66,8 @@ def vocoder(x, pl, M):
             assert d in (d0, d0 + 1)
         qa_prev, s_prev = qa, s
         ph = np.where(qs >= 2 ** 31, qs - 2 ** 32, qs) / 2.0 ** 32 * 2 * np.pi
-        Y = np.abs(X) * np.exp(1j * ph)
+        mag = gain(X, N, q, g) * np.abs(X) if q > 0 else np.abs(X)
+        Y = mag * np.exp(1j * ph)
         Y[0] = Y[0].real
         Y[-1] = Y[-1].real
         y = np.fft.irfft(Y, N)
@@ -57,10 +78,12 @@ def vocoder(x, pl, M):
     return v[:M] * (2.0 / 3.0)
 
 
-def stretch(x, ch, rate, pitch, N):
-    """interleaved [L*ch] -> interleaved [out_len*ch], float64"""
+def stretch(x, ch, rate, pitch, N, q=0):
+    """interleaved [L*ch] -> interleaved [out_len*ch], float64; a lifter q > 0 needs both stages on (a pitch change)"""
     x = np.asarray(x, np.float64).reshape(-1, ch)
     pl = plan(rate, pitch, x.shape[0], N)
+    assert q == 0 or (pl["pv_on"] and pl["rs_on"])
+    g = float(np.float32(pl["rho"]))
     out = np.zeros((pl["out_len"], ch))
     tr = pv_numpy.transposer
     for c in range(ch):
@@ -68,9 +91,9 @@ def stretch(x, ch, rate, pitch, N):
         if not pl["pv_on"] and not pl["rs_on"]:
             out[:, c] = s
         elif pl["rs_first"]:
-            out[:, c] = vocoder(tr(s, pl, pl["mid"]), pl, pl["out_len"])
+            out[:, c] = vocoder(tr(s, pl, pl["mid"]), pl, pl["out_len"], q, g)
         elif pl["pv_on"] and pl["rs_on"]:
-            out[:, c] = tr(vocoder(s, pl, pl["mid"]), pl, pl["out_len"])
+            out[:, c] = tr(vocoder(s, pl, pl["mid"], q, g), pl, pl["out_len"])
         elif pl["pv_on"]:
             out[:, c] = vocoder(s, pl, pl["out_len"])
         else:

@@ -1,4 +1,4 @@
-"""Formant preservation on the GPU over its whole range, against the CPU statement tests/pv_formant/ref_pv_formant.c: the lifters where the
+"""Formant preservation on the GPU over its whole range, against the CPU statement tests/pv_ref/ref_pv.c: the lifters where the
 kernels' cepstral indexing changes (1, 2, odd, N/4 - 1 and N/4, where pva_formant's two packed ranges meet; odd lifters on the locked
 kernel's (n, n + 1) pairs), the high-rate default lifters, the tempo and transposer limits, both sides of the snap to rho = 1, signal levels
 where the spectral floor and the gain cap bind, non-finite samples, and envelopes that change every frame.
@@ -11,8 +11,9 @@ import numpy as np
 import pytest
 
 import orc
-import pv_formant_ref
+import pv_ref
 from conftest import rel_rms
+from pv_gpu import block, profiled, same_bits, stream
 from test_pv_formant_range_cpu import RHO_DIRECT, cap_signal, floor_signal
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,7 @@ ORDERS = [(1.0, 2.0), (0.25, 2.0)]          # rho = 2: transposer first; rho = 1
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_formant_ref.build(str(tmp_path_factory.mktemp("ref_pv_formant")))
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 @pytest.fixture(scope="module")
@@ -41,17 +42,7 @@ def tile_ctxs(nae):
 
 def run(c, nae, x, ch, rate, pitch, n_fft, lifter, lock=False, n_streams=1):
     """x: [n_streams][L][ch] flattened -> (interleaved output [n_streams][out_len * ch], kernels launched)"""
-    L = x.size // (ch * n_streams)
-    pl = c.stretch_plan(rate, pitch, L, n_fft)
-    d_x, d_o = c.array(np.ascontiguousarray(x, np.float32)), c.empty(max(1, n_streams * pl.out_len * ch))
-    c.prof_reset(); c.prof_enable(True)
-    c.stretch_block(rate, pitch, nae.Sig.interleaved(d_x.ptr, L, ch), L, ch, n_streams, nae.Sig.interleaved(d_o.ptr, pl.out_len, ch),
-                    phase_lock=lock, n_fft=n_fft, formant=lifter)
-    out = d_o.download()[: n_streams * pl.out_len * ch]
-    c.prof_enable(False)
-    launched = set(c.prof_report())
-    d_x.free(); d_o.free()
-    return out, launched
+    return profiled(c, block, c, nae, x, ch, rate, pitch, n_fft, lock=lock, lifter=lifter, n_streams=n_streams)
 
 
 def formant_kernel(lock):
@@ -63,15 +54,11 @@ def assert_formant_ran(launched, lock):
     assert formant_kernel(lock) in launched and plain not in launched, launched
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def check(c, nae, ref, x, ch, rate, pitch, n_fft, q, lock, label, per_channel=False):
     """the formant kernel ran; finite; within TOL of the statement (each channel on its own if per_channel); returns (output, worst error)"""
     got, launched = run(c, nae, x, ch, rate, pitch, n_fft, q, lock)
     assert_formant_ran(launched, lock)
-    want = pv_formant_ref.stretch(ref, x, ch, rate, pitch, n_fft, q, lock=lock)
+    want = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock=lock, lifter=q)
     assert got.size == want.size > 0 and np.isfinite(got).all(), label
     if per_channel:
         e = max(rel_rms(got[k::ch], want[k::ch]) for k in range(ch))
@@ -105,35 +92,6 @@ def test_lifters_locked(ctx, nae, ref):
                 check(ctx, nae, ref, x, ch, rate, pitch, 1024, q, True, f"locked q={q} {rate}/{pitch} ch{ch}")
 
 
-def stream(ctx, x, ch, rate, pitch, n_fft, lifter, lock, put_sizes, sample_rate=48000):
-    """nae_stretch_create_formant (sample_rate 0: no 8 - 48 kHz check), puts of put_sizes (the last one repeated), flush, receive: the whole output, interleaved"""
-    lib = ctx.lib
-    L = x.size // ch
-    h = C.c_void_p()
-    assert lib.nae_stretch_create_formant(ctx.h, sample_rate, ch, rate, pitch, 1 if lock else 0, n_fft, lifter, C.byref(h)) == 0
-    outs, pos, i = [], 0, 0
-
-    def drain():
-        n = lib.nae_stretch_available(h)
-        if n:
-            buf = np.empty(n * ch, np.float32)
-            got = C.c_size_t()
-            assert lib.nae_stretch_receive_host(h, buf.ctypes.data, n, C.byref(got)) == 0
-            outs.append(buf[: got.value * ch])
-
-    while pos < L:
-        n = min(put_sizes[i] if i < len(put_sizes) else put_sizes[-1], L - pos)
-        i += 1
-        chunk = np.ascontiguousarray(x[pos * ch:(pos + n) * ch])
-        assert lib.nae_stretch_put_host(h, chunk.ctypes.data, n) == 0
-        pos += n
-        drain()
-    assert lib.nae_stretch_flush(h) == 0
-    drain()
-    assert lib.nae_stretch_destroy(h) == 0
-    return np.concatenate(outs) if outs else np.zeros(0, np.float32)
-
-
 @pytest.mark.parametrize("sample_rate", [96000, 192000])
 @pytest.mark.parametrize("n_fft,lock", CONFIGS)
 def test_high_rate_default_lifters(ctx, nae, ref, n_fft, lock, sample_rate):
@@ -148,7 +106,8 @@ def test_high_rate_default_lifters(ctx, nae, ref, n_fft, lock, sample_rate):
     rng = np.random.default_rng(sample_rate + n_fft + lock)
     h = C.c_void_p()
     assert ctx.lib.nae_stretch_create_formant(ctx.h, sample_rate, ch, rate, pitch, 1 if lock else 0, n_fft, q, C.byref(h)) == -2
-    y = stream(ctx, x, ch, rate, pitch, n_fft, q, lock, [int(v) for v in rng.integers(1, 6000, 12)], 0)
+    y = stream(ctx, x, ch, rate, pitch, [int(v) for v in rng.integers(1, 6000, 12)], "formant", n_fft, flags=int(lock), lifter=q,
+               sample_rate=0, repeat_last=True)
     assert same_bits(y, blk)
 
 
@@ -169,7 +128,7 @@ def test_range_limits(ctx, tile_ctxs, nae, ref, n_fft, lock, tempo, rho):
     got, launched = run(ctx, nae, x, ch, rate, pitch, n_fft, q, lock)
     assert_formant_ran(launched, lock)
     assert ("resample_kernel" in launched) == (rate * pitch >= RHO_DIRECT), (rate * pitch, launched)
-    want = pv_formant_ref.stretch(ref, x, ch, rate, pitch, n_fft, q, lock=lock)
+    want = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock=lock, lifter=q)
     assert got.size == want.size > 0 and np.isfinite(got).all()
     e = rel_rms(got, want)
     print(f"N={n_fft} lock={lock} tempo {tempo:.4g} rho {rho:.4g}: {e:.3g}")
@@ -179,7 +138,7 @@ def test_range_limits(ctx, tile_ctxs, nae, ref, n_fft, lock, tempo, rho):
         assert same_bits(t, got), tile
     rng = np.random.default_rng(n_fft + int(lock))
     puts = [1] * min(L // 4, 1500) + [int(v) for v in rng.integers(1, max(2, L // 6), 30)]
-    assert same_bits(stream(ctx, x, ch, rate, pitch, n_fft, q, lock, puts), got)
+    assert same_bits(stream(ctx, x, ch, rate, pitch, puts, "formant", n_fft, flags=int(lock), lifter=q, repeat_last=True), got)
 
 
 # ------------------------------------------------------------------------------------------------ near rho = 1
@@ -193,7 +152,7 @@ NEAR_ONE = {-1: 1e-4, 1: 4e-2}
 def test_near_rho_one(ctx, nae, ref, n_fft, lock):
     """tempo 1/2.  Inside the 1e-6 snap (rho = 1 +- 5e-7) the transposer is off, so formant preservation is: the lifter-0 bits.  Just outside
     (1 +- 2e-6) the formant kernel runs, within the bar of the statement and within NEAR_ONE of the unflagged call, but not equal to it"""
-    L, ch, q = 16000, 2, pv_formant_ref.default_lifter(48000, n_fft)
+    L, ch, q = 16000, 2, pv_ref.default_lifter(48000, n_fft)
     x = (0.5 * orc.fill_uniform(L * ch, 17)).astype(np.float32)
     pitch = 2.0
     for d in (-5e-7, 5e-7):
@@ -221,7 +180,7 @@ def test_levels(ctx, nae, ref, n_fft, lock):
     """silence: exact zeros.  A silent channel beside a loud one: the silent one exactly zero, the loud one within the bar.  Noise at 2^-36,
     per channel.  Noise scaled by 2^20 and 2^-20: within the bar of the statement, and of the unscaled output scaled"""
     L, ch = 12000, 2
-    q = pv_formant_ref.default_lifter(48000, n_fft)
+    q = pv_ref.default_lifter(48000, n_fft)
     noise = (0.5 * orc.fill_uniform(L * ch, 23)).astype(np.float32)
     for rate, pitch in ORDERS:
         tag = f"N={n_fft} lock={lock} {rate}/{pitch}"
@@ -248,7 +207,7 @@ def test_cap_and_floor_signals(ctx, nae, ref, n_fft, lock):
     """the signals of tests/test_pv_formant_range_cpu.py: the cap signal shifted down by rho = 1/4 and 1/2 (G = 16 on 13 % of the energy at
     1/4), the floor signal (2^-36, 60 - 72 % of the bins on the floor) shifted down and up, stereo with the second channel at half level"""
     L, ch = 12000, 2
-    q = pv_formant_ref.default_lifter(48000, n_fft)
+    q = pv_ref.default_lifter(48000, n_fft)
     for kind, rho in (("cap", 0.25), ("cap", 0.5), ("floor", 0.5), ("floor", 2.0)):
         m = (cap_signal if kind == "cap" else floor_signal)(L)
         x = np.stack([m, np.float32(0.5) * m], 1).reshape(-1).astype(np.float32)
@@ -262,14 +221,14 @@ def test_non_finite_sample_is_confined(ctx, nae, ref, n_fft, lock, bad):
     """one NaN or +Inf sample in channel 0 with the lifter on: the non-finite span is the unflagged call's to +-16 samples (the transposer's
     reach), channel 1 stays finite, and the rest of the output is within the bar of the statement"""
     L, ch, rate, pitch = 40000, 2, 1.0, 2 ** (3 / 12)
-    q = pv_formant_ref.default_lifter(48000, n_fft)
+    q = pv_ref.default_lifter(48000, n_fft)
     x = (0.5 * orc.fill_uniform(L * ch, 43)).reshape(L, ch).copy()
     x[20001, 0] = bad
     x = x.reshape(-1)
     got, launched = run(ctx, nae, x, ch, rate, pitch, n_fft, q, lock)
     assert_formant_ran(launched, lock)
     off, _ = run(ctx, nae, x, ch, rate, pitch, n_fft, 0, lock)
-    want = pv_formant_ref.stretch(ref, x, ch, rate, pitch, n_fft, q, lock=lock)
+    want = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock=lock, lifter=q)
     got, off, want = got.reshape(-1, ch), off.reshape(-1, ch), want.reshape(-1, ch)
     assert got.shape == want.shape == off.shape
     bad_got, bad_off = ~np.isfinite(got), ~np.isfinite(off)
@@ -303,7 +262,7 @@ def changing(L, seg, seed):
 def test_changing_envelope(ctx, nae, ref, n_fft, lock):
     """a new level and spectrum every 1.3 analysis hops, both stage orders, stereo (channel 1 offset by half a segment): within the bar"""
     L, ch = 24000, 2
-    q = pv_formant_ref.default_lifter(48000, n_fft)
+    q = pv_ref.default_lifter(48000, n_fft)
     seg = int(1.3 * n_fft / 4)
     for rate, pitch in ORDERS + [(1.0, 2 ** (-5 / 12))]:
         a = changing(L, seg, 5)
@@ -340,7 +299,7 @@ def test_mixed_batch_each_equals_its_lone_run(ctx, nae, n_fft, lock):
     """24 streams of the six kinds of batch_kinds: each equals its own lone run bit for bit (NaN payloads included), so no envelope leaks
     between streams, waves or frames"""
     n, L, ch, rate, pitch = 24, 9000, 2, 1.0, 2 ** (4 / 12)
-    q = pv_formant_ref.default_lifter(48000, n_fft)
+    q = pv_ref.default_lifter(48000, n_fft)
     x = batch_kinds(n, L, ch, 31)
     got, launched = run(ctx, nae, x, ch, rate, pitch, n_fft, q, lock, n_streams=n)
     assert_formant_ran(launched, lock)

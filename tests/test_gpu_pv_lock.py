@@ -1,4 +1,4 @@
-"""K7 with identity phase locking (NAE_STRETCH_PHASE_LOCK) on the GPU, against the CPU restatement tests/pv_lock/ref_pv_lock.c.
+"""K7 with identity phase locking (NAE_STRETCH_PHASE_LOCK) on the GPU, against the CPU statement tests/pv_ref/ref_pv.c.
 
 Bars: the integer synthesis phases are bit-exact; the samples are within 1e-4 relative RMS (the tolerance path of the unlocked node);
 every tiling, the streaming handle and every batch position give the same bits; flags == 0 through the _ex entries is the unlocked call."""
@@ -7,9 +7,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import node_harness
 import orc
-import pv_lock_ref
+import pv_ref
 from conftest import rel_rms
+from pv_gpu import block, signal, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -20,30 +22,7 @@ PAIRS = [(1.0, 2 ** (3 / 12)), (1.0, 2 ** (-5 / 12)), (1.5, 1 / 1.5), (0.5, 2.0)
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_lock_ref.build(str(tmp_path_factory.mktemp("ref_pv_lock")))
-
-
-def tone(L, amp=(0.5, 0.25), f=(1000.0, 3300.0)):
-    n = np.arange(L)
-    return sum(a * np.sin(2 * np.pi * fr * n / 48000) for a, fr in zip(amp, f)).astype(np.float32)
-
-
-def signal(kind, L, ch, seed=41):
-    if kind == "noise":
-        return orc.fill_uniform(L * ch, seed)
-    m = tone(L)
-    return np.stack([m, 0.5 * m], 1).reshape(-1).astype(np.float32) if ch == 2 else m
-
-
-def lock_stretch(ctx, nae, x, ch, rate, pitch, n_streams=1, phase_lock=True):
-    L = x.size // (ch * n_streams)
-    pl = ctx.stretch_plan(rate, pitch, L)
-    d_x, d_o = ctx.array(x), ctx.empty(max(1, n_streams * pl.out_len * ch))
-    ctx.stretch_block(rate, pitch, nae.Sig.interleaved(d_x.ptr, L, ch), L, ch, n_streams, nae.Sig.interleaved(d_o.ptr, pl.out_len, ch),
-                      phase_lock=phase_lock)
-    out = d_o.download()[: n_streams * pl.out_len * ch]
-    d_x.free(); d_o.free()
-    return out
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 @pytest.mark.parametrize("kind", ["noise", "tone"])
@@ -59,8 +38,8 @@ def test_locked_integer_phases_bit_exact(nae, ref, rate, pitch, kind, tile):
         got, t = c.debug_pv_tile_phase(rate, pitch, nae.Sig.interleaved(d_x.ptr, L, ch), L, ch, 1, phase_lock=True)
         d_x.free()
     assert t == tile
-    qs = pv_lock_ref.synth_phase(ref, x, ch, rate, pitch, 1)
-    assert not np.array_equal(qs, pv_lock_ref.synth_phase(ref, x, ch, rate, pitch, 0)), "locking changes the phases"
+    qs = pv_ref.synth_phase(ref, x, ch, rate, pitch, lock=True)
+    assert not np.array_equal(qs, pv_ref.synth_phase(ref, x, ch, rate, pitch, lock=False)), "locking changes the phases"
     n_tiles = got.shape[2]
     assert n_tiles >= 2
     for j in range(n_tiles):
@@ -74,13 +53,13 @@ def test_locked_integer_phases_bit_exact(nae, ref, rate, pitch, kind, tile):
 def test_locked_samples_vs_restatement(ctx, nae, ref, rate, pitch, kind):
     L, ch = 30000, 2
     x = signal(kind, L, ch, 43)
-    got = lock_stretch(ctx, nae, x, ch, rate, pitch)
-    want = pv_lock_ref.stretch(ref, x, ch, rate, pitch, 1)
+    got = block(ctx, nae, x, ch, rate, pitch, lock=True)
+    want = pv_ref.stretch(ref, x, ch, rate, pitch, lock=True)
     assert got.size == want.size and np.isfinite(got).all()
     e = rel_rms(got, want)
     print(f"locked rel RMS {rate:.4f}/{pitch:.4f} {kind}: {e:.3g}")
     assert e <= TOL, e
-    assert rel_rms(got, pv_lock_ref.stretch(ref, x, ch, rate, pitch, 0)) > 10 * TOL, "the locked output is not the unlocked one"
+    assert rel_rms(got, pv_ref.stretch(ref, x, ch, rate, pitch, lock=False)) > 10 * TOL, "the locked output is not the unlocked one"
 
 
 def test_locked_every_tiling_gives_the_same_bits(nae):
@@ -95,7 +74,7 @@ def test_locked_every_tiling_gives_the_same_bits(nae):
             for k, v in knobs.items():
                 c.debug_set(k, v)
             c.prof_reset(); c.prof_enable(True)
-            outs[key] = lock_stretch(c, nae, x, ch, rate, pitch)
+            outs[key] = block(c, nae, x, ch, rate, pitch, lock=True)
             c.prof_enable(False)
             launched[key] = set(c.prof_report())
     pl = nae.Context.stretch_plan(rate, pitch, L)
@@ -106,48 +85,14 @@ def test_locked_every_tiling_gives_the_same_bits(nae):
         assert np.array_equal(outs[key].view(np.uint32), outs["one tile"].view(np.uint32)), key
 
 
-def stream_lock(ctx, x, ch, rate, pitch, put_sizes, device_put=False, flags=LOCK):
-    lib = ctx.lib
-    L = x.size // ch
-    h = C.c_void_p()
-    assert lib.nae_stretch_create_ex(ctx.h, 48000, ch, rate, pitch, flags, C.byref(h)) == 0
-    outs, pos, i = [], 0, 0
-    d_x = ctx.array(x) if device_put else None
-
-    def drain():
-        n = lib.nae_stretch_available(h)
-        if n:
-            buf = np.empty(n * ch, np.float32)
-            got = C.c_size_t()
-            assert lib.nae_stretch_receive_host(h, buf.ctypes.data, n, C.byref(got)) == 0
-            outs.append(buf[: got.value * ch])
-
-    while pos < L:
-        n = min(put_sizes[i % len(put_sizes)], L - pos)
-        i += 1
-        if device_put:
-            assert lib.nae_stretch_put(h, d_x.at(pos * ch), n) == 0
-        else:
-            chunk = np.ascontiguousarray(x[pos * ch:(pos + n) * ch])
-            assert lib.nae_stretch_put_host(h, chunk.ctypes.data, n) == 0
-        pos += n
-        drain()
-    assert lib.nae_stretch_flush(h) == 0
-    drain()
-    assert lib.nae_stretch_destroy(h) == 0
-    if d_x is not None:
-        d_x.free()
-    return np.concatenate(outs) if outs else np.zeros(0, np.float32)
-
-
 @pytest.mark.parametrize("rate,pitch", [(1.0, float(np.float32(2 ** (3 / 12)))), (1.0, float(np.float32(2 ** (-7 / 12)))),
                                         (1.5, float(np.float32(1 / 1.5)))])
 def test_locked_stream_handle_equals_block(ctx, nae, rate, pitch):
     """uneven small pieces (one tile per segment, pass L3 carries the phase) equal the locked block call bit for bit"""
     L, ch = 150000, 2
     x = (0.5 * orc.fill_uniform(L * ch, 7)).astype(np.float32)
-    blk = lock_stretch(ctx, nae, x, ch, rate, pitch)
-    y = stream_lock(ctx, x, ch, rate, pitch, [1152, 4001, 777, 20000])
+    blk = block(ctx, nae, x, ch, rate, pitch, lock=True)
+    y = stream(ctx, x, ch, rate, pitch, [1152, 4001, 777, 20000], "ex", flags=LOCK)
     assert y.size == blk.size
     assert np.array_equal(y.view(np.uint32), blk.view(np.uint32))
 
@@ -157,11 +102,11 @@ def test_locked_stream_pieces_of_256_tiles(nae):
     ch, L, rate, pitch = 2, 2_600_000, 1.0, float(np.float32(2 ** (3 / 12)))
     x = (0.5 * orc.fill_uniform(L * ch, 123)).astype(np.float32)
     with nae.Context(0) as c:
-        blk = lock_stretch(c, nae, x, ch, rate, pitch)
+        blk = block(c, nae, x, ch, rate, pitch, lock=True)
     with nae.Context(0) as c:
         c.debug_set("pv_tile", 16)
         c.prof_reset(); c.prof_enable(True)
-        y = stream_lock(c, x, ch, rate, pitch, [1_100_000, 1_100_000, 400_000], device_put=True)
+        y = stream(c, x, ch, rate, pitch, [1_100_000, 1_100_000, 400_000], "ex", flags=LOCK, device_put=True)
         c.prof_enable(False)
         assert "pvlock_scan_kernel" in set(c.prof_report())
     assert y.size == blk.size
@@ -171,9 +116,9 @@ def test_locked_stream_pieces_of_256_tiles(nae):
 def test_locked_batch_of_1024_equals_lone_runs(ctx, nae):
     n, L, ch, pitch = 1024, 12000, 2, 2 ** (3 / 12)
     x = orc.fill_uniform(n * L * ch, 47)
-    got = lock_stretch(ctx, nae, x, ch, 1.0, pitch, n).reshape(n, -1)
+    got = block(ctx, nae, x, ch, 1.0, pitch, lock=True, n_streams=n).reshape(n, -1)
     for s in (0, 1, 2, 3, 511, 1022, 1023):
-        one = lock_stretch(ctx, nae, x.reshape(n, -1)[s].copy(), ch, 1.0, pitch)
+        one = block(ctx, nae, x.reshape(n, -1)[s].copy(), ch, 1.0, pitch, lock=True)
         assert np.array_equal(one.view(np.uint32), got[s].view(np.uint32)), s
 
 
@@ -182,8 +127,8 @@ def test_locked_non_finite_sample_is_confined(ctx, nae, ref):
     L, ch, pitch = 60000, 2, 2 ** (3 / 12)
     x = (0.5 * orc.fill_uniform(L * ch, 43)).reshape(L, ch).copy()
     x[30001, 0] = np.nan
-    got = lock_stretch(ctx, nae, x.reshape(-1), ch, 1.0, pitch).reshape(-1, ch)
-    want = pv_lock_ref.stretch(ref, x.reshape(-1), ch, 1.0, pitch, 1).reshape(-1, ch)
+    got = block(ctx, nae, x.reshape(-1), ch, 1.0, pitch, lock=True).reshape(-1, ch)
+    want = pv_ref.stretch(ref, x.reshape(-1), ch, 1.0, pitch, lock=True).reshape(-1, ch)
     bad_ref, bad_got = ~np.isfinite(want), ~np.isfinite(got)
     assert not bad_ref[:, 1].any() and not bad_got[:, 1].any()
     assert 1000 < bad_ref[:, 0].sum() < 4000
@@ -230,7 +175,7 @@ def test_flags_zero_is_the_existing_call(ctx, nae):
     assert tf.value == ta and np.array_equal(a.reshape(-1), b[: a.size])
     d_x.free(); d_a.free(); d_b.free()
     p32 = float(np.float32(pitch))
-    y0 = stream_lock(ctx, x, ch, rate, p32, [1152, 3000], flags=0)
+    y0 = stream(ctx, x, ch, rate, p32, [1152, 3000], "ex", flags=0)
     h = C.c_void_p()
     assert lib.nae_stretch_create(ctx.h, 48000, ch, rate, p32, C.byref(h)) == 0
     assert lib.nae_stretch_put_host(h, x.ctypes.data, L) == 0 and lib.nae_stretch_flush(h) == 0
@@ -249,13 +194,12 @@ def test_python_stretcher_phase_lock(ctx, nae):
     s.flush()
     y = s.receive_host()
     s.close()
-    assert np.array_equal(y.view(np.uint32), lock_stretch(ctx, nae, x, ch, 1.0, pitch).view(np.uint32))
+    assert np.array_equal(y.view(np.uint32), block(ctx, nae, x, ch, 1.0, pitch, lock=True).view(np.uint32))
 
 
 def test_host_graph_pitch_node_phase_lock(tmp_path):
     """source -> Pitch_modifier {"pitch": 3, "phase_lock": true} -> sink equals the locked block call bit for bit (host mirror)"""
     import subprocess
-    from test_pv_lock_cpu import build_host_pv_lock
-    exe = build_host_pv_lock(str(tmp_path))
-    r = subprocess.run([exe, "gpu"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "HOST PV LOCK OK gpu" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    exe = node_harness.build("pv_ref/host_pv_node.cpp", str(tmp_path))
+    r = subprocess.run([exe, "gpu", "phase_lock"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "HOST PV NODE OK gpu phase_lock" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

@@ -1,4 +1,4 @@
-"""K7 at vocoder frame sizes 512 ... 4096 on the GPU (kernels_pv_any.hip), against the CPU restatement tests/pv_sizes/ref_pv_sizes.c.
+"""K7 at vocoder frame sizes 512 ... 4096 on the GPU (kernels_pv_any.hip), against the CPU statement tests/pv_ref/ref_pv.c.
 
 Bars: the integer synthesis phases are bit-exact; the samples are within 1e-4 relative RMS; every tiling, batch position, layout and the
 streaming handle give the same bits; at 1024 the size-generic kernels (debug key pv_any) give the shipped kernels' integer phases, and _n at
@@ -8,9 +8,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import node_harness
 import orc
-import pv_sizes_ref
+import pv_ref
 from conftest import rel_rms
+from pv_gpu import block, signal, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -21,30 +23,7 @@ SIZES = [512, 2048, 4096]
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_sizes_ref.build(str(tmp_path_factory.mktemp("ref_pv_sizes")))
-
-
-def tone(L, amp=(0.5, 0.25), f=(1000.0, 3300.0)):
-    n = np.arange(L)
-    return sum(a * np.sin(2 * np.pi * fr * n / 48000) for a, fr in zip(amp, f)).astype(np.float32)
-
-
-def signal(kind, L, ch, seed=41):
-    if kind == "noise":
-        return orc.fill_uniform(L * ch, seed)
-    m = tone(L)
-    return np.stack([m, 0.5 * m], 1).reshape(-1).astype(np.float32) if ch == 2 else m
-
-
-def stretch_n(ctx, nae, x, ch, rate, pitch, n_fft, n_streams=1):
-    L = x.size // (ch * n_streams)
-    pl = ctx.stretch_plan(rate, pitch, L, n_fft)
-    d_x, d_o = ctx.array(x), ctx.empty(max(1, n_streams * pl.out_len * ch))
-    ctx.stretch_block(rate, pitch, nae.Sig.interleaved(d_x.ptr, L, ch), L, ch, n_streams, nae.Sig.interleaved(d_o.ptr, pl.out_len, ch),
-                      n_fft=n_fft)
-    out = d_o.download()[: n_streams * pl.out_len * ch]
-    d_x.free(); d_o.free()
-    return out
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 def tile_phases(c, nae, x, ch, rate, pitch, n_fft):
@@ -68,7 +47,7 @@ def test_integer_phases_bit_exact(nae, ref, n_fft, rate, pitch, kind, ch):
         c.debug_set("pv_tile", tile)
         got, t = tile_phases(c, nae, x, ch, rate, pitch, n_fft)
     assert t == tile
-    qs = pv_sizes_ref.synth_phase(ref, x, ch, rate, pitch, n_fft)
+    qs = pv_ref.synth_phase(ref, x, ch, rate, pitch, n_fft)
     n_tiles = got.shape[2]
     assert n_tiles >= 2 and got.shape[3] == n_fft // 2 + 1
     for j in range(n_tiles):
@@ -85,14 +64,14 @@ def test_samples_vs_restatement(ctx, nae, ref, n_fft, rate, pitch, kind, ch):
     """within 1e-4 relative RMS; (2.0, 1.0) is the transposer alone (the frame size has no effect there: bit-equal to 1024)"""
     L = 30000
     x = signal(kind, L, ch, 43)
-    got = stretch_n(ctx, nae, x, ch, rate, pitch, n_fft)
-    want = pv_sizes_ref.stretch(ref, x, ch, rate, pitch, n_fft)
+    got = block(ctx, nae, x, ch, rate, pitch, n_fft)
+    want = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft)
     assert got.size == want.size and np.isfinite(got).all()
     e = rel_rms(got, want)
     print(f"N={n_fft} rel RMS {rate:.4f}/{pitch:.4f} {kind} ch{ch}: {e:.3g}")
     assert e <= TOL, e
     if rate == 2.0:
-        assert np.array_equal(got.view(np.uint32), stretch_n(ctx, nae, x, ch, rate, pitch, 1024).view(np.uint32))
+        assert np.array_equal(got.view(np.uint32), block(ctx, nae, x, ch, rate, pitch, 1024).view(np.uint32))
 
 
 @pytest.mark.parametrize("n_fft", SIZES)
@@ -110,7 +89,7 @@ def test_every_tiling_gives_the_same_bits(nae, n_fft):
             for k, v in knobs.items():
                 c.debug_set(k, v)
             c.prof_reset(); c.prof_enable(True)
-            outs[key] = stretch_n(c, nae, x, ch, rate, pitch, n_fft)
+            outs[key] = block(c, nae, x, ch, rate, pitch, n_fft)
             c.prof_enable(False)
             launched = set(c.prof_report())
             if key == "16-frame tiles":
@@ -127,9 +106,9 @@ def test_batch_positions_and_layouts(ctx, nae, n_fft):
     """stream s of a batch equals its lone run bit for bit; interleaved, planar and shared-source (stream_stride 0) layouts agree"""
     n, L, ch, rate, pitch = 64, 12000, 2, 1.0, 2 ** (3 / 12)
     x = orc.fill_uniform(n * L * ch, 47)
-    got = stretch_n(ctx, nae, x, ch, rate, pitch, n_fft, n).reshape(n, -1)
+    got = block(ctx, nae, x, ch, rate, pitch, n_fft, n_streams=n).reshape(n, -1)
     for s in (0, 1, 31, 62, 63):
-        one = stretch_n(ctx, nae, x.reshape(n, -1)[s].copy(), ch, rate, pitch, n_fft)
+        one = block(ctx, nae, x.reshape(n, -1)[s].copy(), ch, rate, pitch, n_fft)
         assert np.array_equal(one.view(np.uint32), got[s].view(np.uint32)), s
     pl = ctx.stretch_plan(rate, pitch, L, n_fft)
     one = x.reshape(n, -1)[3].copy()
@@ -147,34 +126,6 @@ def test_batch_positions_and_layouts(ctx, nae, n_fft):
     d_p.free(); d_i.free(); d_o.free()
 
 
-def stream_n(ctx, x, ch, rate, pitch, n_fft, put_sizes):
-    lib = ctx.lib
-    L = x.size // ch
-    h = C.c_void_p()
-    assert lib.nae_stretch_create_n(ctx.h, 48000, ch, rate, pitch, 0, n_fft, C.byref(h)) == 0
-    outs, pos, i = [], 0, 0
-
-    def drain():
-        n = lib.nae_stretch_available(h)
-        if n:
-            buf = np.empty(n * ch, np.float32)
-            got = C.c_size_t()
-            assert lib.nae_stretch_receive_host(h, buf.ctypes.data, n, C.byref(got)) == 0
-            outs.append(buf[: got.value * ch])
-
-    while pos < L:
-        n = min(put_sizes[i % len(put_sizes)], L - pos)
-        i += 1
-        chunk = np.ascontiguousarray(x[pos * ch:(pos + n) * ch])
-        assert lib.nae_stretch_put_host(h, chunk.ctypes.data, n) == 0
-        pos += n
-        drain()
-    assert lib.nae_stretch_flush(h) == 0
-    drain()
-    assert lib.nae_stretch_destroy(h) == 0
-    return np.concatenate(outs) if outs else np.zeros(0, np.float32)
-
-
 @pytest.mark.parametrize("rate,pitch", [(1.0, float(np.float32(2 ** (3 / 12)))), (1.0, float(np.float32(2 ** (-7 / 12)))),
                                         (1.5, float(np.float32(1 / 1.5)))])
 @pytest.mark.parametrize("n_fft", SIZES)
@@ -182,10 +133,10 @@ def test_stream_handle_equals_block(ctx, nae, n_fft, rate, pitch):
     """1152-frame puts and seeded random cuts, flush included, equal the block call bit for bit"""
     L, ch = 150000, 2
     x = (0.5 * orc.fill_uniform(L * ch, 7)).astype(np.float32)
-    blk = stretch_n(ctx, nae, x, ch, rate, pitch, n_fft)
+    blk = block(ctx, nae, x, ch, rate, pitch, n_fft)
     rng = np.random.default_rng(n_fft)
     for puts in ([1152], [int(v) for v in rng.integers(1, 30000, 40)]):
-        y = stream_n(ctx, x, ch, rate, pitch, n_fft, puts)
+        y = stream(ctx, x, ch, rate, pitch, puts, "n", n_fft)
         assert y.size == blk.size
         assert np.array_equal(y.view(np.uint32), blk.view(np.uint32)), puts[:4]
 
@@ -199,8 +150,8 @@ def test_stream_segment_of_many_tiles_after_one_block(ctx, nae, n_fft):
     ha = n_fft // 4 * 1.5
     first = int(2 * ha + n_fft // 2) + n_fft // 16             # frame 3 ends inside it, frame 4 does not
     assert 2 * ha + n_fft // 2 <= first < 3 * ha + n_fft // 2
-    blk = stretch_n(ctx, nae, x, ch, rate, pitch, n_fft)
-    y = stream_n(ctx, x, ch, rate, pitch, n_fft, [first, L])
+    blk = block(ctx, nae, x, ch, rate, pitch, n_fft)
+    y = stream(ctx, x, ch, rate, pitch, [first, L], "n", n_fft)
     assert y.size == blk.size
     assert np.array_equal(y.view(np.uint32), blk.view(np.uint32))
 
@@ -213,7 +164,7 @@ def test_python_stretcher_n_fft(ctx, nae):
     s.flush()
     y = s.receive_host()
     s.close()
-    assert np.array_equal(y.view(np.uint32), stretch_n(ctx, nae, x, ch, 1.0, pitch, 2048).view(np.uint32))
+    assert np.array_equal(y.view(np.uint32), block(ctx, nae, x, ch, 1.0, pitch, 2048).view(np.uint32))
 
 
 @pytest.mark.parametrize("n_fft", SIZES)
@@ -223,8 +174,8 @@ def test_non_finite_sample_is_confined(ctx, nae, ref, n_fft):
     L, ch, pitch = 60000, 2, 2 ** (3 / 12)
     x = (0.5 * orc.fill_uniform(L * ch, 43)).reshape(L, ch).copy()
     x[30001, 0] = np.nan
-    got = stretch_n(ctx, nae, x.reshape(-1), ch, 1.0, pitch, n_fft).reshape(-1, ch)
-    want = pv_sizes_ref.stretch(ref, x.reshape(-1), ch, 1.0, pitch, n_fft).reshape(-1, ch)
+    got = block(ctx, nae, x.reshape(-1), ch, 1.0, pitch, n_fft).reshape(-1, ch)
+    want = pv_ref.stretch(ref, x.reshape(-1), ch, 1.0, pitch, n_fft).reshape(-1, ch)
     bad_ref, bad_got = ~np.isfinite(want), ~np.isfinite(got)
     assert not bad_ref[:, 1].any() and not bad_got[:, 1].any()
     assert 0 < bad_ref[:, 0].sum() < 4 * n_fft
@@ -248,7 +199,7 @@ def test_generic_kernels_at_1024_match_the_shipped_ones(nae, rate, pitch, kind):
             c.debug_set("pv_tile", 16)
             c.debug_set("pv_any", key)
             c.prof_reset(); c.prof_enable(True)
-            res[key] = tile_phases(c, nae, x, ch, rate, pitch, 1024)[0], stretch_n(c, nae, x, ch, rate, pitch, 1024)
+            res[key] = tile_phases(c, nae, x, ch, rate, pitch, 1024)[0], block(c, nae, x, ch, rate, pitch, 1024)
             c.prof_enable(False)
             launched = set(c.prof_report())
             assert ("pv_any_synth_kernel" in launched) == (key == 1), launched
@@ -311,14 +262,13 @@ def test_host_graph_pitch_node_fft_size(tmp_path, ref):
     """source -> Pitch_modifier {"pitch": 3, "fft_size": 4096} -> sink through the fiber runner equals the 4096-point block call bit for bit
     (host mirror) and the CPU restatement within 1e-4"""
     import subprocess
-    from test_pv_sizes_cpu import build_host_pv_sizes
-    exe = build_host_pv_sizes(str(tmp_path))
+    exe = node_harness.build("pv_ref/host_pv_node.cpp", str(tmp_path))
     out = str(tmp_path / "graph.f32")
-    r = subprocess.run([exe, "gpu", out], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "HOST PV SIZES OK gpu" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    r = subprocess.run([exe, "gpu", "fft_size", out], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "HOST PV NODE OK gpu fft_size" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
     data = np.fromfile(out, np.float32)
     x, got = data[: 60000 * 2], data[60000 * 2:]
     pitch = float(np.float32(2 ** (3 / 12)))
-    want = pv_sizes_ref.stretch(ref, x, 2, 1.0, pitch, 4096)
+    want = pv_ref.stretch(ref, x, 2, 1.0, pitch, 4096)
     assert got.size == want.size
     assert rel_rms(got, want) <= TOL, rel_rms(got, want)

@@ -5,8 +5,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import node_harness
 import orc
-from test_spectrum_sizes_cpu import SIZES, _build_ref, build_host_spectrum, ref_spectrum
+from test_spectrum_sizes_cpu import SIZES, _build_ref, ref_spectrum
 
 pytestmark = pytest.mark.gpu
 
@@ -200,12 +201,7 @@ def test_handle_and_block_reject_bad_parameters(ctx, nae):
 
 def test_host_node_at_4096_hop_512(tmp_path):
     """source -> spectrum {"fft_size": 4096, "hop": 512} -> sink equals the block call, pts advance by hop / sample_rate"""
-    import os
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for d in (os.path.join(root, "nodey-audio-editor_amd"), os.path.join(root, "nodey-audio-editor_amd", "host")):
-        r = subprocess.run(["make", "-C", d, "-j4"], capture_output=True, text=True)   # a current library and host archive
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    exe = build_host_spectrum(str(tmp_path))
+    exe = node_harness.build("spec_sizes/host_spectrum.cpp", str(tmp_path))
     r = subprocess.run([exe, "gpu"], capture_output=True, text=True, timeout=240)
     assert r.returncode == 0 and "HOST SPECTRUM OK gpu" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

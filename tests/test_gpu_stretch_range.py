@@ -2,7 +2,7 @@
 its 4-stream groups, the direct kernel past the staging limit), the vocoder at tempos 1/64 ... 16 at every frame size (locked at 1024),
 inputs around one frame long, the size-generic tile policy on both sides of its switch, and the streaming handle at the extremes.
 
-References: orc.stretch / orc.pv_synth_phase at 1024, tests/pv_sizes/ref_pv_sizes.c at the other sizes, tests/pv_lock/ref_pv_lock.c locked.
+References: orc.stretch / orc.pv_synth_phase at 1024, tests/pv_ref/ref_pv.c at the other sizes and locked.
 Bars: integer phases bit-exact, samples within 1e-4 relative RMS; prof_report names the kernel that ran, so no case is vacuous."""
 import ctypes as C
 
@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 
 import orc
-import pv_lock_ref
-import pv_sizes_ref
+import pv_ref
 from conftest import rel_rms
+from pv_gpu import block, profiled, same_bits, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -23,12 +23,7 @@ RESIDENT3 = {512: 16, 1024: 8, 2048: 6, 4096: 3}     # PvAny<N>::kResident3 (ker
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_sizes_ref.build(str(tmp_path_factory.mktemp("ref_pv_sizes")))
-
-
-@pytest.fixture(scope="module")
-def lref(tmp_path_factory):
-    return pv_lock_ref.build(str(tmp_path_factory.mktemp("ref_pv_lock")))
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 @pytest.fixture(scope="module")
@@ -45,36 +40,17 @@ def ctxs(nae):
         c.close()
 
 
-def want_ref(ref, lref, x, ch, rate, pitch, n_fft, lock=False):
-    if lock:
-        return pv_lock_ref.stretch(lref, x, ch, rate, pitch, 1)
-    if n_fft == 1024:
+def want_ref(ref, x, ch, rate, pitch, n_fft, lock=False):
+    if n_fft == 1024 and not lock:
         return orc.stretch(x, ch, rate, pitch)
-    return pv_sizes_ref.stretch(ref, x, ch, rate, pitch, n_fft)
+    return pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock)
 
 
 def run(c, nae, x, ch, rate, pitch, n_fft=1024, n_streams=1, lock=False, planar_in=False, planar_out=False):
-    """x: [n_streams][L][ch] flattened; returns [n_streams][out_len * ch] interleaved, and the kernels launched"""
-    L = x.size // (ch * n_streams)
-    pl = c.stretch_plan(rate, pitch, L, n_fft)
-    xs = x.reshape(n_streams, L, ch)
-    flat = np.ascontiguousarray(xs.transpose(0, 2, 1)).reshape(-1) if planar_in else x
-    d_x, d_o = c.array(np.ascontiguousarray(flat, np.float32)), c.empty(max(1, n_streams * pl.out_len * ch))
-    src = nae.Sig.planar(d_x.ptr, L, ch) if planar_in else nae.Sig.interleaved(d_x.ptr, L, ch)
-    dst = nae.Sig.planar(d_o.ptr, pl.out_len, ch) if planar_out else nae.Sig.interleaved(d_o.ptr, pl.out_len, ch)
-    c.prof_reset(); c.prof_enable(True)
-    c.stretch_block(rate, pitch, src, L, ch, n_streams, dst, phase_lock=lock, n_fft=n_fft)
-    out = d_o.download()[: n_streams * pl.out_len * ch].reshape(n_streams, -1)
-    c.prof_enable(False)
-    launched = set(c.prof_report())
-    d_x.free(); d_o.free()
-    if planar_out:
-        out = np.ascontiguousarray(out.reshape(n_streams, ch, pl.out_len).transpose(0, 2, 1)).reshape(n_streams, -1)
-    return out, launched, pl
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    """x: [n_streams][L][ch] flattened; returns [n_streams][out_len * ch] interleaved, the kernels launched and the plan"""
+    out, launched = profiled(c, block, c, nae, x, ch, rate, pitch, n_fft, lock=lock, n_streams=n_streams, planar_in=planar_in,
+                             planar_out=planar_out)
+    return out.reshape(n_streams, -1), launched, c.stretch_plan(rate, pitch, x.size // (ch * n_streams), n_fft)
 
 
 # ------------------------------------------------------------------------------------------------ B.1 transposer regimes
@@ -157,11 +133,11 @@ def test_vocoder_at_the_tempo_limits(ctx, tile_ctxs, nae, ref, n_fft, tempo, rho
     x, ch = case_signal(tempo, rho, n_fft, 71)
     pl = ctx.stretch_plan(rate, pitch, x.size // ch, n_fft)
     assert pl.pv_on and bool(pl.rs_on) == (rho != 1.0)
-    qs = orc.pv_synth_phase(x, ch, rate, pitch) if n_fft == 1024 else pv_sizes_ref.synth_phase(ref, x, ch, rate, pitch, n_fft)
+    qs = orc.pv_synth_phase(x, ch, rate, pitch) if n_fft == 1024 else pv_ref.synth_phase(ref, x, ch, rate, pitch, n_fft)
     for tile in (16, 1):
         check_tile_phases(tile_ctxs[tile], nae, x, ch, rate, pitch, n_fft, qs, tile)
     got, launched, _ = run(ctx, nae, x, ch, rate, pitch, n_fft)
-    want = want_ref(ref, None, x, ch, rate, pitch, n_fft)
+    want = want_ref(ref, x, ch, rate, pitch, n_fft)
     assert got[0].size == want.size and np.isfinite(got).all()
     e = rel_rms(got[0], want)
     print(f"N={n_fft} tempo {tempo:.4f} rho {rho:.4f} ch{ch}: {e:.3g}")
@@ -173,15 +149,15 @@ def test_vocoder_at_the_tempo_limits(ctx, tile_ctxs, nae, ref, n_fft, tempo, rho
 
 @pytest.mark.parametrize("rho", RHOS)
 @pytest.mark.parametrize("tempo", TEMPOS)
-def test_locked_vocoder_at_the_tempo_limits(ctx, tile_ctxs, nae, lref, tempo, rho):
+def test_locked_vocoder_at_the_tempo_limits(ctx, tile_ctxs, nae, ref, tempo, rho):
     pitch = 1 / tempo
     rate = rho / pitch
     x, ch = case_signal(tempo, rho, 1024, 73)
-    qs = pv_lock_ref.synth_phase(lref, x, ch, rate, pitch, 1)
+    qs = pv_ref.synth_phase(ref, x, ch, rate, pitch, lock=True)
     for tile in (16, 1):
         check_tile_phases(tile_ctxs[tile], nae, x, ch, rate, pitch, 1024, qs, tile, lock=True)
     got, launched, _ = run(ctx, nae, x, ch, rate, pitch, 1024, lock=True)
-    want = pv_lock_ref.stretch(lref, x, ch, rate, pitch, 1)
+    want = pv_ref.stretch(ref, x, ch, rate, pitch, lock=True)
     assert got[0].size == want.size and np.isfinite(got).all()
     e = rel_rms(got[0], want)
     print(f"locked tempo {tempo:.4f} rho {rho:.4f} ch{ch}: {e:.3g}")
@@ -192,7 +168,7 @@ def test_locked_vocoder_at_the_tempo_limits(ctx, tile_ctxs, nae, lref, tempo, rh
 # ------------------------------------------------------------------------------------------------ B.3 edge lengths
 @pytest.mark.parametrize("rate,pitch", [(0.7, 1 / 0.7), (1.6, 1 / 1.6), (1.0, 2 ** (3 / 12)), (1.0, 2 ** (-5 / 12))])
 @pytest.mark.parametrize("n_fft,lock", [(512, False), (2048, False), (4096, False), (1024, True)])
-def test_edge_lengths(ctx, nae, ref, lref, n_fft, lock, rate, pitch):
+def test_edge_lengths(ctx, nae, ref, n_fft, lock, rate, pitch):
     """inputs of 0, 1, H - 1, H, N/2 - 1, N/2, N - 1, N, N + 1, N + H + 1 frames, tempo below and above 1 (and both stage orders): the plan's
     length, finite, within 1e-4 of the restatement (or a near-silent reference, the rule of test_k7_edge_lengths)"""
     N, H, ch = n_fft, n_fft // 4, 2
@@ -207,7 +183,7 @@ def test_edge_lengths(ctx, nae, ref, lref, n_fft, lock, rate, pitch):
             d.free()
             continue
         got, _, _ = run(ctx, nae, x, ch, rate, pitch, n_fft, lock=lock)
-        want = want_ref(ref, lref, x, ch, rate, pitch, n_fft, lock)
+        want = want_ref(ref, x, ch, rate, pitch, n_fft, lock)
         assert got[0].size == pl.out_len * ch == want.size, L
         assert np.isfinite(got).all(), L
         assert rel_rms(got[0], want) <= TOL or np.sqrt(np.mean(want.astype(np.float64) ** 2)) < 1e-6, (L, rel_rms(got[0], want))
@@ -263,43 +239,11 @@ def test_tile_policy_threshold(nae, ref, n_fft):
                 lone, _, _ = run(c, nae, xs, 1, tempo, 1 / tempo, n_fft)
                 assert same_bits(rows[s], lone[0]), (n_sc, s)
                 if s != n_sc // 2:
-                    assert rel_rms(rows[s], want_ref(ref, None, xs, 1, tempo, 1 / tempo, n_fft)) <= TOL, (n_sc, s)
+                    assert rel_rms(rows[s], want_ref(ref, xs, 1, tempo, 1 / tempo, n_fft)) <= TOL, (n_sc, s)
     assert seen == {thr - 1: True, thr: False, thr + 1: False}, seen
 
 
 # ------------------------------------------------------------------------------------------------ B.5 streaming handle at the extremes
-def stream_n(ctx, x, ch, rate, pitch, n_fft, lock, put_sizes):
-    lib = ctx.lib
-    L = x.size // ch
-    h = C.c_void_p()
-    flags = 1 if lock else 0
-    if n_fft == 1024:
-        assert lib.nae_stretch_create_ex(ctx.h, 48000, ch, C.c_float(rate), C.c_float(pitch), flags, C.byref(h)) == 0
-    else:
-        assert lib.nae_stretch_create_n(ctx.h, 48000, ch, C.c_float(rate), C.c_float(pitch), flags, n_fft, C.byref(h)) == 0
-    outs, pos, i = [], 0, 0
-
-    def drain():
-        n = lib.nae_stretch_available(h)
-        if n:
-            buf = np.empty(n * ch, np.float32)
-            got = C.c_size_t()
-            assert lib.nae_stretch_receive_host(h, buf.ctypes.data, n, C.byref(got)) == 0
-            outs.append(buf[: got.value * ch])
-
-    while pos < L:
-        n = min(put_sizes[i] if i < len(put_sizes) else put_sizes[-1], L - pos)
-        i += 1
-        chunk = np.ascontiguousarray(x[pos * ch:(pos + n) * ch])
-        assert lib.nae_stretch_put_host(h, chunk.ctypes.data, n) == 0
-        pos += n
-        drain()
-    assert lib.nae_stretch_flush(h) == 0
-    drain()
-    assert lib.nae_stretch_destroy(h) == 0
-    return np.concatenate(outs) if outs else np.zeros(0, np.float32)
-
-
 EXTREMES = [(1 / 64, 1.0), (16.0, 1.0), (1.0, 16.0)]     # (tempo, rho)
 
 
@@ -317,6 +261,6 @@ def test_stream_handle_at_the_extremes(ctx, nae, n_fft, lock, tempo, rho):
     rng = np.random.default_rng(n_fft + int(lock))
     ones = min(L // 4, 1500)
     puts = [1] * ones + [int(v) for v in rng.integers(1, max(2, L // 6), 30)]
-    y = stream_n(ctx, x, ch, rate, pitch, n_fft, lock, puts)
+    y = stream(ctx, x, ch, rate, pitch, puts, "ex" if n_fft == 1024 else "n", n_fft, flags=int(lock), repeat_last=True)
     assert y.size == blk[0].size
     assert same_bits(y, blk[0])

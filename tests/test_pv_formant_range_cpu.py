@@ -1,18 +1,17 @@
-"""Formant preservation over its whole range, no GPU: the CPU statement tests/pv_formant/ref_pv_formant.c pinned to the float64 numpy
-statement (tests/pv_formant_numpy.py) at every frame size, at the lifters where the kernels change behaviour (1, 2, odd, N/4 - 1, N/4) and
+"""Formant preservation over its whole range, no GPU: the CPU statement tests/pv_ref/ref_pv.c pinned to the float64 numpy
+statement (tests/pv_sizes_numpy.py) at every frame size, at the lifters where the kernels change behaviour (1, 2, odd, N/4 - 1, N/4) and
 at the tempo and transposer limits; the default lifter at every sample rate up to 192 kHz; and the two signals that make the gain cap and the
 spectral floor bind, shown to do so, which tests/test_gpu_pv_formant_range.py runs on the GPU."""
 import numpy as np
 import pytest
 
 import orc
-import pv_formant_numpy
-import pv_formant_ref
+import pv_ref
 import pv_sizes_numpy
 from conftest import rel_rms
 from golden import pv_numpy
 
-SIZES = pv_formant_ref.SIZES
+SIZES = pv_ref.SIZES
 FLOOR, CAP = 2.0 ** -40, 16.0          # the spectral floor of step 1 and NAE_FORMANT_MAX_GAIN
 RHO_DIRECT = 4101 / 512                # from here on the transposer runs resample_kernel (tests/test_gpu_stretch_range.py)
 
@@ -43,20 +42,20 @@ def pin_length(tempo, rho, n_fft):
 
 
 def numpy_statement_all_lifters(x, tempo, rho, n_fft, qs):
-    """pv_formant_numpy.stretch for mono x at every lifter in qs, sharing the transposer when it runs first"""
+    """pv_sizes_numpy.stretch for mono x at every lifter in qs, sharing the transposer when it runs first"""
     pl = pv_sizes_numpy.plan(rho * tempo, 1 / tempo, x.size, n_fft)
     assert pl["pv_on"] and pl["rs_on"]
     g = float(np.float32(pl["rho"]))
     x = x.astype(np.float64)
     if pl["rs_first"]:
         v = pv_numpy.transposer(x, pl, pl["mid"])
-        return {q: pv_formant_numpy.vocoder(v, pl, pl["out_len"], q, g) for q in qs}
-    return {q: pv_numpy.transposer(pv_formant_numpy.vocoder(x, pl, pl["mid"], q, g), pl, pl["out_len"]) for q in qs}
+        return {q: pv_sizes_numpy.vocoder(v, pl, pl["out_len"], q, g) for q in qs}
+    return {q: pv_numpy.transposer(pv_sizes_numpy.vocoder(x, pl, pl["mid"], q, g), pl, pl["out_len"]) for q in qs}
 
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_formant_ref.build(str(tmp_path_factory.mktemp("ref_pv_formant")))
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 @pytest.mark.parametrize("tempo,rho", PIN_CASES)
@@ -69,7 +68,7 @@ def test_statement_pinned_over_the_range(ref, n_fft, tempo, rho):
     want = numpy_statement_all_lifters(x, tempo, rho, n_fft, lifters(n_fft))
     bar = pin_bar(tempo, rho)
     for q in lifters(n_fft):
-        got = pv_formant_ref.stretch(ref, x, 1, rho * tempo, 1 / tempo, n_fft, q)
+        got = pv_ref.stretch(ref, x, 1, rho * tempo, 1 / tempo, n_fft, lifter=q)
         assert got.size == want[q].size > 0, q
         e = rel_rms(got, want[q])
         print(f"N={n_fft} tempo {tempo:.4g} rho {rho:.4g} q={q}: {e:.3g}")
@@ -82,19 +81,19 @@ RATES = {1000: 1, 8000: 11, 11025: 15, 22050: 31, 44100: 63, 48000: 68, 88200: 1
 
 @pytest.mark.parametrize("n_fft", SIZES)
 def test_default_lifter_at_every_rate(nae, n_fft):
-    """nae_stretch_formant_lifter, nae.formant_lifter and pv_formant_ref.default_lifter agree, and the clamp to N/4 applies exactly where
+    """nae_stretch_formant_lifter, nae.formant_lifter and pv_ref.default_lifter agree, and the clamp to N/4 applies exactly where
     sample_rate // 700 exceeds it: 96000, 176400 and 192000 Hz at N = 512 (128), 192000 Hz at N = 1024 (256); q = 1 at 1000 Hz and below"""
     lib = nae.load_library()
     for sr, raw in RATES.items():
         want = min(raw, n_fft // 4)
-        got = (lib.nae_stretch_formant_lifter(sr, n_fft), nae.formant_lifter(sr, n_fft), pv_formant_ref.default_lifter(sr, n_fft))
+        got = (lib.nae_stretch_formant_lifter(sr, n_fft), nae.formant_lifter(sr, n_fft), pv_ref.default_lifter(sr, n_fft))
         assert got == (want,) * 3, (sr, got, want)
     clamped = {sr for sr, raw in RATES.items() if raw > n_fft // 4}
     assert clamped == {512: {96000, 176400, 192000}, 1024: {192000}, 2048: set(), 4096: set()}[n_fft]
     for sr in clamped:
         assert nae.formant_lifter(sr, n_fft) == n_fft // 4
     for sr in (1, 300, 699, 1000, 1399):
-        assert nae.formant_lifter(sr, n_fft) == 1 == pv_formant_ref.default_lifter(sr, n_fft), sr
+        assert nae.formant_lifter(sr, n_fft) == 1 == pv_ref.default_lifter(sr, n_fft), sr
     assert nae.formant_lifter(1400, n_fft) == 2
 
 
@@ -126,7 +125,7 @@ def analysis_gains(x, n_fft, q, rho):
     Gs, As = [], []
     for s in range(0, x.size - n_fft + 1, n_fft // 2):
         X = np.fft.rfft(x[s:s + n_fft] * w)
-        Gs.append(pv_formant_numpy.gain(X, n_fft, q, g))
+        Gs.append(pv_sizes_numpy.gain(X, n_fft, q, g))
         As.append(np.abs(X))
     return np.array(Gs), np.array(As)
 
@@ -167,9 +166,9 @@ def test_statement_pinned_where_the_clamps_bind(ref, n_fft, kind, rho):
     the log spectrum) measured 3.8e-6 - 6.1e-4 for the same reason white noise is the range pin's signal"""
     L = 12000
     x = (cap_signal if kind == "cap" else floor_signal)(L)
-    q = pv_formant_ref.default_lifter(48000, n_fft)
-    got = pv_formant_ref.stretch(ref, x, 1, 1.0, rho, n_fft, q)
-    want = pv_formant_numpy.stretch(x, 1, 1.0, rho, n_fft, q)
+    q = pv_ref.default_lifter(48000, n_fft)
+    got = pv_ref.stretch(ref, x, 1, 1.0, rho, n_fft, lifter=q)
+    want = pv_sizes_numpy.stretch(x, 1, 1.0, rho, n_fft, q)
     assert got.size == want.size
     e = rel_rms(got, want)
     print(f"N={n_fft} {kind} rho {rho}: {e:.3g}")

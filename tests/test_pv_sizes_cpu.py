@@ -1,4 +1,4 @@
-"""K7 at vocoder frame sizes 512 ... 4096, no GPU: the CPU restatement (tests/pv_sizes/ref_pv_sizes.c) pinned to the oracle at N = 1024 and to
+"""K7 at vocoder frame sizes 512 ... 4096, no GPU: the CPU statement (tests/pv_ref/ref_pv.c) pinned to the oracle at N = 1024 and to
 the float64 numpy restatement (tests/pv_sizes_numpy.py) at the other sizes, the plan of every size through the library, what a size changes
 on clicks and on close low partials, and the C ABI's declarations."""
 import ctypes as C
@@ -9,10 +9,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import node_harness
 import orc
+import pv_ref
 import pv_sizes_numpy
-import pv_sizes_ref
 from conftest import rel_rms
+from pv_gpu import tone
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAIRS = [(1.0, 2 ** (3 / 12)), (1.0, 2 ** (-5 / 12)), (1.5, 1 / 1.5), (0.5, 2.0)]   # those of tests/test_gpu_pv_lock.py
@@ -22,12 +24,7 @@ UNSUPPORTED = -2   # NAE_ERR_UNSUPPORTED
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_sizes_ref.build(str(tmp_path_factory.mktemp("ref_pv_sizes")))
-
-
-def tone(L, f=(1000.0, 3300.0), amp=(0.5, 0.25)):
-    n = np.arange(L)
-    return sum(a * np.sin(2 * np.pi * fr * n / 48000) for a, fr in zip(amp, f)).astype(np.float32)
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 @pytest.mark.parametrize("ch", [1, 2])
@@ -37,9 +34,9 @@ def test_restatement_at_1024_is_the_oracle(ref, rate, pitch, ch):
     L = 20000
     m = tone(L)
     for x in (orc.fill_uniform(L * ch, 3), np.stack([m, 0.5 * m], 1).reshape(-1) if ch == 2 else m):
-        a, b = pv_sizes_ref.stretch(ref, x, ch, rate, pitch, 1024), orc.stretch(x, ch, rate, pitch)
+        a, b = pv_ref.stretch(ref, x, ch, rate, pitch, 1024), orc.stretch(x, ch, rate, pitch)
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
-        assert np.array_equal(pv_sizes_ref.synth_phase(ref, x, ch, rate, pitch, 1024), orc.pv_synth_phase(x, ch, rate, pitch))
+        assert np.array_equal(pv_ref.synth_phase(ref, x, ch, rate, pitch, 1024), orc.pv_synth_phase(x, ch, rate, pitch))
 
 
 @pytest.mark.parametrize("n_fft", [512, 2048, 4096])
@@ -50,7 +47,7 @@ def test_restatement_matches_the_numpy_specification(ref, n_fft, rate, pitch):
     Hann main-lobe bin 1-2 bins away from a partial advances by about half a turn or more per analysis hop, so float32 against float64
     rounding decides its phase wrap, and the two restatements differ by 1e-3 at every size, 1024 included."""
     x = tone(24000)
-    got = pv_sizes_ref.stretch(ref, x, 1, rate, pitch, n_fft)
+    got = pv_ref.stretch(ref, x, 1, rate, pitch, n_fft)
     want = pv_sizes_numpy.stretch(x, 1, rate, pitch, n_fft)
     assert got.size == want.size
     assert rel_rms(got, want) <= 1e-5, rel_rms(got, want)
@@ -75,7 +72,7 @@ def test_plan_of_every_size(nae, ref, rate, pitch):
     for n_fft in (512, 1024, 2048, 4096):
         rc, pl = lib_plan(nae, rate, pitch, n_fft, L)
         assert rc == 0
-        rc2, want = pv_sizes_ref.plan(ref, rate, pitch, n_fft, L)
+        rc2, want = pv_ref.plan(ref, rate, pitch, n_fft, L)
         assert rc2 == 0
         for f in FIELDS:
             assert getattr(pl, f) == getattr(want, f), (n_fft, f)
@@ -117,7 +114,7 @@ def click_width(ref, n_fft):
     x = np.zeros(L, np.float32)
     pos = np.arange(4800, L - 4800, 9600)
     x[pos] = 1.0
-    y = pv_sizes_ref.stretch(ref, x, 1, 1.5, 1 / 1.5, n_fft).astype(np.float64)
+    y = pv_ref.stretch(ref, x, 1, 1.5, 1 / 1.5, n_fft).astype(np.float64)
     widths = []
     for p in pos:
         c = int(round(p / 1.5))
@@ -140,7 +137,7 @@ def two_tone_gains(ref, n_fft):
     L, f1, f2, p = 96000, 110.0, 140.0, 2 ** (3 / 12)
     n = np.arange(L)
     x = (0.3 * np.sin(2 * np.pi * f1 * n / 48000) + 0.3 * np.sin(2 * np.pi * f2 * n / 48000)).astype(np.float32)
-    y = pv_sizes_ref.stretch(ref, x, 1, 1.0, p, n_fft).astype(np.float64)
+    y = pv_ref.stretch(ref, x, 1, 1.0, p, n_fft).astype(np.float64)
     seg = y[y.size // 4: 3 * y.size // 4]
     t = np.arange(seg.size)
     g = []
@@ -167,24 +164,9 @@ def test_abi_declares_the_sizes(nae):
     assert re.search(r"#define\s+NAE_ABI_VERSION\s+3\b", h)
 
 
-def build_host_pv_sizes(out_dir):
-    """tests/pv_sizes/host_pv_sizes.cpp with the flags of tests/host/Makefile"""
-    pkg = os.path.join(ROOT, "nodey-audio-editor_amd")
-    for d in (pkg, os.path.join(pkg, "host")):
-        r = subprocess.run(["make", "-C", d, "-j4"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    exe = os.path.join(out_dir, "host_pv_sizes")
-    cmd = ["g++", "-O1", "-g", "-std=c++20", "-pthread", "-Wall", "-Wno-unused-parameter", "-I" + os.path.join(pkg, "host"),
-           "-I" + os.path.join(ROOT, "include"), "-ffp-contract=off", os.path.join(ROOT, "tests", "pv_sizes", "host_pv_sizes.cpp"), "-o", exe,
-           os.path.join(pkg, "host", "libnae_host.a"), "-L" + pkg, "-lnae_gpu", "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 def test_host_node_fft_size_key(tmp_path):
     """Velocity_modifier / Pitch_modifier: "fft_size" round-trips, is absent by default and at 1024; a value outside 512 / 1024 / 2048 / 4096
     and a size other than 1024 with "phase_lock": true are "Wrong field: fft_size" """
-    exe = build_host_pv_sizes(str(tmp_path))
-    r = subprocess.run([exe, "json"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "HOST PV SIZES OK json" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    exe = node_harness.build("pv_ref/host_pv_node.cpp", str(tmp_path))
+    r = subprocess.run([exe, "json", "fft_size"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "HOST PV NODE OK json fft_size" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import node_harness
 import orc
 from conftest import rel_rms
 
@@ -121,22 +122,6 @@ def test_ref_frames_match_the_library(ref, nae):
 
 def test_host_node_json_keys(tmp_path):
     """the host node's JSON: round trip, nothing written at the defaults, bad size / hop rejected with "Wrong field: ..." """
-    host = os.path.join(ROOT, "nodey-audio-editor_amd", "host")
-    for d in (os.path.join(ROOT, "nodey-audio-editor_amd"), host):
-        r = subprocess.run(["make", "-C", d, "-j4"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    exe = build_host_spectrum(str(tmp_path))
+    exe = node_harness.build("spec_sizes/host_spectrum.cpp", str(tmp_path))
     r = subprocess.run([exe, "json"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "HOST SPECTRUM OK json" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-
-
-def build_host_spectrum(out_dir):
-    """tests/spec_sizes/host_spectrum.cpp with the flags of tests/host/Makefile"""
-    pkg = os.path.join(ROOT, "nodey-audio-editor_amd")
-    exe = os.path.join(out_dir, "host_spectrum")
-    cmd = ["g++", "-O1", "-g", "-std=c++20", "-pthread", "-Wall", "-Wno-unused-parameter", "-I" + os.path.join(pkg, "host"),
-           "-I" + os.path.join(ROOT, "include"), "-ffp-contract=off", os.path.join(HERE, "host_spectrum.cpp"), "-o", exe,
-           os.path.join(pkg, "host", "libnae_host.a"), "-L" + pkg, "-lnae_gpu", "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe

@@ -1,5 +1,5 @@
 """K7 over the whole supported parameter range, no GPU: the plan of every frame size at the tempo limits (1/64, 16), the transposer limits
-(rho = 1/16, 16), one step outside each and on both sides of the 1e-6 snap to 1; and the CPU restatement tests/pv_sizes/ref_pv_sizes.c
+(rho = 1/16, 16), one step outside each and on both sides of the 1e-6 snap to 1; and the CPU statement tests/pv_ref/ref_pv.c
 against the float64 specification tests/pv_sizes_numpy.py at every size, at extreme tempos and at the transposer ratios where the GPU
 changes kernels (tests/test_gpu_stretch_range.py)."""
 import math
@@ -8,19 +8,20 @@ import numpy as np
 import pytest
 
 import orc
+import pv_ref
 import pv_sizes_numpy
-import pv_sizes_ref
 from conftest import rel_rms
+from pv_gpu import tone
+from pv_ref import SIZES
 from test_pv_sizes_cpu import FIELDS, lib_plan
 
-SIZES = (512, 1024, 2048, 4096)
 UNSUPPORTED = -2   # NAE_ERR_UNSUPPORTED
 TEMPO_MIN, TEMPO_MAX, RHO_MIN, RHO_MAX = 1 / 64, 16.0, 1 / 16, 16.0
 
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_sizes_ref.build(str(tmp_path_factory.mktemp("ref_pv_sizes")))
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 def below(v):
@@ -65,7 +66,7 @@ def test_plan_at_the_limits(nae, ref, n_fft):
     for rate, pitch in inside_cases():
         rc, pl = lib_plan(nae, rate, pitch, n_fft, L)
         assert rc == 0, (rate, pitch)
-        rc2, want = pv_sizes_ref.plan(ref, rate, pitch, n_fft, L)
+        rc2, want = pv_ref.plan(ref, rate, pitch, n_fft, L)
         assert rc2 == 0
         for f in FIELDS:
             assert getattr(pl, f) == getattr(want, f), (rate, pitch, f)
@@ -82,7 +83,7 @@ def test_plan_at_the_limits(nae, ref, n_fft):
     for rate, pitch in outside_cases():
         rc, _ = lib_plan(nae, rate, pitch, n_fft, L)
         assert rc == UNSUPPORTED, (rate, pitch, rc)
-        assert pv_sizes_ref.plan(ref, rate, pitch, n_fft, L)[0] == UNSUPPORTED
+        assert pv_ref.plan(ref, rate, pitch, n_fft, L)[0] == UNSUPPORTED
         if n_fft == 1024:
             assert orc.plan(rate, pitch, L)[0] == UNSUPPORTED
 
@@ -97,13 +98,8 @@ def test_plan_snaps_to_one_within_1e6(nae, ref, n_fft):
         rc, pl = lib_plan(nae, 1 + eps, 1.0, n_fft, 10000)                     # rho 1 + eps, tempo 1
         assert rc == 0 and bool(pl.rs_on) == on and not pl.pv_on, eps
         assert (pl.rate_eff == 1.0) == (not on)
-        rc2, want = pv_sizes_ref.plan(ref, 1 + eps, 1.0, n_fft, 10000)
+        rc2, want = pv_ref.plan(ref, 1 + eps, 1.0, n_fft, 10000)
         assert rc2 == 0 and want.rs_on == pl.rs_on and want.out_len == pl.out_len
-
-
-def tone(L):
-    n = np.arange(L)
-    return (0.5 * np.sin(2 * np.pi * 1000.0 * n / 48000) + 0.25 * np.sin(2 * np.pi * 3300.0 * n / 48000)).astype(np.float32)
 
 
 # (tempo, rho): the vocoder alone, the transposer alone (rho past the GPU's tile switches and the direct kernel), and both on both stage
@@ -116,7 +112,7 @@ BOTH = [(1 / 64, 16.0), (0.3, 3.9), (0.1, 8.01), (0.75, 1 / 16), (0.9, 0.26), (1
 @pytest.mark.parametrize("tempo,rho", VOCODER + TRANSPOSER + BOTH)
 @pytest.mark.parametrize("n_fft", SIZES)
 def test_restatement_matches_the_specification_over_the_range(ref, n_fft, tempo, rho):
-    """ref_pv_sizes.c against pv_sizes_numpy.py, ~12000 output frames, noise mono and stereo, and the two-tone signal where the vocoder is off
+    """ref_pv.c against pv_sizes_numpy.py, ~12000 output frames, noise mono and stereo, and the two-tone signal where the vocoder is off
     or the tempo is 1/64.  Within 1e-5 relative RMS (measured at most 2.7e-6 for tempos 0.1 - 0.9 and 8.8e-8 for the transposer alone), except
     at tempo 1/64: there R = H / d = 64, and every analysis phase's float32 rounding reaches the synthesis phase 64 times larger (the increments
     telescope to R times the last frame's error), measured 1.3e-5 - 4.0e-5 at every size, so the bar there is 1e-4.
@@ -133,7 +129,7 @@ def test_restatement_matches_the_specification_over_the_range(ref, n_fft, tempo,
         m = tone(n)
         signals += [("tone", 1, m), ("tone", 2, np.stack([m, 0.5 * m], 1).reshape(-1))]
     for kind, ch, x in signals:
-        got = pv_sizes_ref.stretch(ref, x, ch, rate, pitch, n_fft)
+        got = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft)
         want = pv_sizes_numpy.stretch(x, ch, rate, pitch, n_fft)
         assert got.size == want.size and got.size > 0
         e = rel_rms(got, want)

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Randomised differential run (GPU box) over the whole supported K7 range: frame sizes 512 ... 4096 (the phase lock at 1024), log-uniform
 tempo over [1/64, 16] and transposer ratio over [1/16, 16], edge-heavy input lengths, batches around the size-generic tile policy's switch
-(kResident3 * n_cu stream-channels) and planar / interleaved layouts, against the matching CPU restatement (orc at 1024, ref_pv_sizes.c at the
-other sizes, ref_pv_lock.c locked).  A formant dimension from its own generator (the draws above stay the seed's): half the cases take a lifter
-in 1 ... N/4 (ref_pv_formant.c is then the restatement), and every case an input level 2^-36 ... 2^20.  Returns the worst relative RMS error.
+(kResident3 * n_cu stream-channels) and planar / interleaved layouts, against the CPU statement (orc at 1024 unlocked without a lifter,
+tests/pv_ref/ref_pv.c otherwise).  A formant dimension from its own generator (the draws above stay the seed's): half the cases take a lifter
+in 1 ... N/4, and every case an input level 2^-36 ... 2^20.  Returns the worst relative RMS error.
     python tests/tools/fuzz_stretch_any.py [cases=40] [seed=1]"""
 import ctypes as C
 import os
@@ -16,9 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import naeload
 import orc
-import pv_formant_ref
-import pv_lock_ref
-import pv_sizes_ref
+import pv_ref
 
 RESIDENT3 = {512: 16, 1024: 8, 2048: 6, 4096: 3}     # PvAny<N>::kResident3 (kernels_pv_any.hip)
 
@@ -43,7 +41,7 @@ def main(cases=40, seed=1, ctx=None, nae=None, max_samples=4_000_000):
     if ctx is None:
         ctx = nae.Context(0)
     tmp = tempfile.mkdtemp(prefix="fuzz_any_")
-    ref, lref, fref = pv_sizes_ref.build(tmp), pv_lock_ref.build(tmp), pv_formant_ref.build(tmp)
+    ref = pv_ref.build(tmp)
     frng = np.random.default_rng([seed, 7])
     n_cu = cu_count()
     worst = 0.0
@@ -81,14 +79,10 @@ def main(cases=40, seed=1, ctx=None, nae=None, max_samples=4_000_000):
         errs = []
         for s in sorted({0, n_streams // 2, n_streams - 1}):
             xs = x[s].reshape(-1)
-            if lifter:
-                want = pv_formant_ref.stretch(fref, xs, ch, rate, pitch, n_fft, lifter, lock=lock)
-            elif lock:
-                want = pv_lock_ref.stretch(lref, xs, ch, rate, pitch, 1)
-            elif n_fft == 1024:
+            if n_fft == 1024 and not lock and not lifter:
                 want = orc.stretch(xs, ch, rate, pitch)
             else:
-                want = pv_sizes_ref.stretch(ref, xs, ch, rate, pitch, n_fft)
+                want = pv_ref.stretch(ref, xs, ch, rate, pitch, n_fft, lock, lifter)
             want = want.reshape(-1, ch)
             assert want.shape == out[s].shape, (want.shape, out[s].shape)
             if want.size and np.sqrt(np.mean(want.astype(np.float64) ** 2)) >= 1e-6 * level:    # near-silent references: the edge-length rule
