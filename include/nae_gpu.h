@@ -250,7 +250,7 @@ int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_s
  * phase of each spectral peak of the power spectrum and keeps every other bin at its analysis phase offset from its nearest peak:
  * Qs_f[k] = Qs_{f-1}[p] + inc_f[p] + (Qa_f[k] - Qa_f[p]), p = the peak of bin k (a frame without a peak runs unlocked).  A steady tone keeps its
  * amplitude (the unlocked vocoder loses 2-16 % on an off-centre tone).  Everything else — analysis, transposer, stage order, lengths — is the
- * unlocked node's.  Integer phases are bit-exact against the CPU restatement (tests/pv_lock/ref_pv_lock.c) and independent of the tiling. */
+ * unlocked node's.  Integer phases are bit-exact against the CPU statement (tests/pv_ref/ref_pv.c) and independent of the tiling. */
 #define NAE_STRETCH_PHASE_LOCK 1u
 int nae_stretch_block_ex_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, const nae_sig* src, size_t in_len, int ch,
                              size_t n_streams, const nae_sig* dst);
@@ -268,7 +268,7 @@ int nae_stretch_create_ex(nae_ctx* ctx, int sample_rate, int channels, float rat
  * phase-advance ratios and frame count follow the size; out_len, mid_len, the stage order, the transposer and the rate / tempo limits do not.
  * n_fft = 1024 is exactly the call without _n (nae_stretch_plan_make, the _ex entries).  Another size: NAE_ERR_UNSUPPORTED, and so is
  * NAE_STRETCH_PHASE_LOCK at a size other than 1024; an unknown flag bit: NAE_ERR_INVALID.  Integer phases are bit-exact against the CPU
- * restatement (tests/pv_sizes/ref_pv_sizes.c) and independent of the tiling; a handle's output equals the block call's. */
+ * statement (tests/pv_ref/ref_pv.c) and independent of the tiling; a handle's output equals the block call's. */
 int nae_stretch_plan_make_n(double rate, double pitch, int n_fft, size_t in_len, nae_stretch_plan* plan);
 int nae_stretch_block_n_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, const nae_sig* src, size_t in_len, int ch,
                             size_t n_streams, const nae_sig* dst);
@@ -282,7 +282,7 @@ int nae_stretch_create_n(nae_ctx* ctx, int sample_rate, int channels, float rate
  * (the log2 spectrum liftered to quefrencies below `lifter` samples) and rho = plan.rate_eff, so the output keeps the input's spectral
  * envelope while its harmonics move.  Phases, lengths, stage order and the transposer are the _n call's; so are flags and n_fft
  * (NAE_STRETCH_PHASE_LOCK at 1024).  lifter == 0 is exactly the _n call; lifter < 0 or > n_fft / 4: NAE_ERR_INVALID.  Without a pitch change
- * (no transposer, or no vocoder) a lifter changes nothing.  Samples follow the tolerance path against tests/pv_formant/ref_pv_formant.c;
+ * (no transposer, or no vocoder) a lifter changes nothing.  Samples follow the tolerance path against tests/pv_ref/ref_pv.c;
  * the result is independent of the tiling, and a handle's output equals the block call's.
  * nae_stretch_formant_lifter: the default lifter, min(max(sample_rate / 700, 1), n_fft / 4) (68 at 48 kHz, 63 at 44.1 kHz, n_fft 1024); 0 for
  * an unsupported n_fft or a sample_rate <= 0. */

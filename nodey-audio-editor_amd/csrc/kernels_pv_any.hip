@@ -3,19 +3,21 @@
 // The three passes of the 1024-point vocoder (kernels_stft.hip, kernels_pvpipe.hip) restated with N as a template parameter, on the
 // size-generic canonical FFT of fft_any.h:
 //   pass 1 (pv_any_phase_kernel)  one wave per (stream-channel, tile): analysis of each frame, sum of its integer phase increments;
-//   pass 2 (pv_any_scan_kernel, pv_any_scan_chunked_kernel)  per (stream-channel, bin) the exclusive prefix over the tiles, in 16 chunks side
-//                                 by side from 256 tiles on, with carry-in and carry-out;
+//   pass 2 (pv_scan_kernel, pv_scan_chunked_kernel)  per (stream-channel, bin) the exclusive prefix over the tiles, in 16 chunks side by side
+//                                 from 256 tiles on, with carry-in and carry-out — the one scan of the unlocked vocoder, at 1024 after the
+//                                 shipped pass 1 too;
 //   pass 3 (pv_any_synth_kernel)  one wave per synthesis tile: from its record it walks its frames forward — re-analysis, Qs update, rotation,
 //                                 c2r transform, window, overlap-add in increasing frame order, gain — and stores its hop blocks.
-// Every integer is exact, so every tiling gives the same bits, and the integer phases are the CPU restatement's (tests/pv_sizes/ref_pv_sizes.c);
+// Every integer is exact, so every tiling gives the same bits, and the integer phases are the CPU statement's (tests/pv_ref/ref_pv.c);
 // the samples follow the tolerance path.  A wave owns one frame at a time: its FFT scratch (9/8 M complex), the phases Qa_{f-1} and (pass 1) the
 // tile's sum or (pass 3) Qs, [r][lane] for bin lane + 64 r, and in pass 3 the synthesis spectrum (B = N/2 + 1 complex, padded) live in LDS; the
 // three open overlap-add blocks of pass 3 in registers.  (Phases in registers, 2 x (M/64 + 1) per lane, with the bin loop unrolled, spill from
 // N = 2048 on.)
-// N = 1024 runs the shipped kernels unless the debug key pv_any asks for these.  The host decisions (records needed, base records, synthesis
-// fields, workspace) are kernels_stft.hip's nae_launch_pv_phase / nae_launch_pv_synth; the launchers here only launch.
+// N = 1024 runs the shipped passes 1 and 3 unless the debug key pv_any (or, pass 3, a lifter) asks for these: nae_pv_route_of.  The host
+// decisions (records needed, base records, synthesis fields, workspace) are kernels_stft.hip's nae_launch_pv_phase / nae_launch_pv_synth.
 #include "pv_roles.h"
 #include "fft_any.h"
+#include <type_traits>
 
 namespace nae {
 
@@ -156,70 +158,92 @@ __global__ __launch_bounds__(64 * PvAny<N>::kWaves1) void pv_any_phase_kernel(Si
 }
 
 // ------------------------------------------------------------------------------------------------ pass 2
-// exclusive prefix over tiles, in place; one thread per (stream-channel, bin).  carry_in (optional): the phase in front of tile 0, [n_sc][PAD];
-// carry_out (optional): the phase behind the last tile.  Records at or beyond n_read count as zero.
+// the one scan of the unlocked vocoder (after pv_phase_kernel or pv_any_phase_kernel): exclusive prefix over tiles, in place; one thread per
+// (stream-channel, bin).  carry_in (optional): the phase in front of tile 0, [n_sc][PAD]; carry_out (optional): the phase behind the last tile.
+// Records at or beyond n_read count as zero.
 template <int N>
-__global__ void pv_any_scan_kernel(uint32_t* __restrict__ sums, long long n_sc, int n_tiles, const uint32_t* __restrict__ carry_in,
-                                   uint32_t* __restrict__ carry_out, int n_read)
+__global__ void pv_scan_kernel(uint32_t* __restrict__ sums, long long n_sc, int n_tiles, const uint32_t* __restrict__ carry_in,
+                               uint32_t* __restrict__ carry_out, int n_read)
 {
     using P = PvAny<N>;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long sc = t / P::PAD;
     const int k = (int)(t % P::PAD);
     if (sc >= n_sc || k >= P::B) return;
-    uint32_t* q = sums + sc * n_tiles * (long long)P::PAD + k;
+    uint32_t* p = sums + sc * n_tiles * (long long)P::PAD + k;
     uint32_t run = carry_in ? carry_in[sc * P::PAD + k] : 0u;
     int j = 0;
+    // the loads do not depend on the running sum: fetch 8 tiles ahead, then prefix them
     for (; j + 8 <= n_read; j += 8) {
         uint32_t v[8];
 #pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = q[(long long)(j + u) * P::PAD];
+        for (int u = 0; u < 8; u++) v[u] = p[(long long)(j + u) * P::PAD];
 #pragma unroll
         for (int u = 0; u < 8; u++) {
-            q[(long long)(j + u) * P::PAD] = run;
+            p[(long long)(j + u) * P::PAD] = run;
             run += v[u];
         }
     }
     for (; j < n_tiles; j++) {
-        const uint32_t v = (j < n_read) ? q[(long long)j * P::PAD] : 0u;
-        q[(long long)j * P::PAD] = run;
+        const uint32_t v = (j < n_read) ? p[(long long)j * P::PAD] : 0u;
+        p[(long long)j * P::PAD] = run;
         run += v;
     }
     if (carry_out) carry_out[sc * P::PAD + k] = run;
 }
 
-// many tiles per stream-channel: 16 threads per bin take a sixteenth of the tiles each, exchange their sums through LDS and prefix their own
-// part (modular sums: the split changes no bit).  One workgroup per (stream-channel, 64 bins).
-constexpr int kAnyScanChunks = 16;
+// the same for many tiles per stream-channel (a long lone stream: thousands of tiles on a few stream-channels, where one thread per bin walks them
+// one after the other): 16 threads per bin take a sixteenth of the tiles each — sum it, exchange the 16 sums through LDS, prefix the own part
+// (modular integer sums: the split changes no bit).  One workgroup per (stream-channel, 64 bins).
+constexpr int kScanChunks = 16;
 template <int N>
-__global__ __launch_bounds__(64 * kAnyScanChunks) void pv_any_scan_chunked_kernel(uint32_t* __restrict__ sums, long long n_sc, int n_tiles,
-                                                                                 const uint32_t* __restrict__ carry_in,
-                                                                                 uint32_t* __restrict__ carry_out, int n_read)
+__global__ __launch_bounds__(64 * kScanChunks) void pv_scan_chunked_kernel(uint32_t* __restrict__ sums, long long n_sc, int n_tiles,
+                                                                          const uint32_t* __restrict__ carry_in, uint32_t* __restrict__ carry_out, int n_read)
 {
     using P = PvAny<N>;
-    __shared__ uint32_t part[kAnyScanChunks][64];
+    __shared__ uint32_t part[kScanChunks][64];
     const int kb = threadIdx.x & 63, ck = threadIdx.x >> 6;
     const long long sc = blockIdx.x / P::NB;
     const int k = (int)(blockIdx.x % P::NB) * 64 + kb;
     const bool valid = k < P::B;
-    const int per = (n_tiles + kAnyScanChunks - 1) / kAnyScanChunks;
-    const int j0 = ck * per < n_tiles ? ck * per : n_tiles, j1 = (j0 + per < n_tiles) ? j0 + per : n_tiles;
-    const int r1 = j1 < n_read ? j1 : n_read;
-    uint32_t* q = sums + sc * n_tiles * (long long)P::PAD + (valid ? k : 0);
+    const int per = (n_tiles + kScanChunks - 1) / kScanChunks;
+    const int j0 = ck * per, j1 = (j0 + per < n_tiles) ? j0 + per : n_tiles;
+    const int r1 = j1 < n_read ? j1 : n_read;                       // tiles at or beyond n_read count as zero
+    uint32_t* p = sums + sc * n_tiles * (long long)P::PAD + (valid ? k : 0);
     uint32_t sum = 0;
-    if (valid)
-        for (int j = j0; j < r1; j++) sum += q[(long long)j * P::PAD];
+    if (valid) {
+        int j = j0;
+        for (; j + 8 <= r1; j += 8) {
+            uint32_t v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) v[u] = p[(long long)(j + u) * P::PAD];
+#pragma unroll
+            for (int u = 0; u < 8; u++) sum += v[u];
+        }
+        for (; j < r1; j++) sum += p[(long long)j * P::PAD];
+    }
     part[ck][kb] = sum;
     __syncthreads();
     uint32_t run = (valid && carry_in) ? carry_in[sc * P::PAD + k] : 0u;
     for (int c2 = 0; c2 < ck; c2++) run += part[c2][kb];
     if (!valid) return;
-    for (int j = j0; j < j1; j++) {
-        const uint32_t v = (j < n_read) ? q[(long long)j * P::PAD] : 0u;
-        q[(long long)j * P::PAD] = run;
+    int j = j0;
+    for (; j + 8 <= r1; j += 8) {
+        uint32_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = p[(long long)(j + u) * P::PAD];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            p[(long long)(j + u) * P::PAD] = run;
+            run += v[u];
+        }
+    }
+    for (; j < j1; j++) {
+        const uint32_t v = (j < n_read) ? p[(long long)j * P::PAD] : 0u;
+        p[(long long)j * P::PAD] = run;
         run += v;
     }
-    if (carry_out && ck == kAnyScanChunks - 1) carry_out[sc * P::PAD + k] = run;
+    if (carry_out && ck == kScanChunks - 1) carry_out[sc * P::PAD + k] = run;
 }
 
 // ------------------------------------------------------------------------------------------------ pass 3
@@ -428,31 +452,34 @@ __global__ __launch_bounds__(64 * (kFormant ? PvAny<N, true>::kWaves3 : PvAny<N>
 
 // ------------------------------------------------------------------------------------------------ launchers
 template <int N>
-static int launch_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
-                        uint32_t* phase_ws, const uint32_t* carry_in, uint32_t* carry_out, const SpecAnyTables& tb)
+static int launch_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, uint32_t* phase_ws,
+                        const SpecAnyTables& tb)
 {
     using P = PvAny<N>;
     const long long items = n_sc * p.n_tiles;
     const long long grid = (items + P::kWaves1 - 1) / P::kWaves1;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_phase_kernel: grid too large");
-    if (unit_stride)
-        NAE_KLAUNCH(ctx, "pv_any_phase_kernel", (pv_any_phase_kernel<N, true>), dim3((unsigned)grid), dim3(64 * P::kWaves1), 0, ctx->stream,
-                    src, p, items, phase_ws, tb);
-    else
-        NAE_KLAUNCH(ctx, "pv_any_phase_kernel", (pv_any_phase_kernel<N, false>), dim3((unsigned)grid), dim3(64 * P::kWaves1), 0, ctx->stream,
-                    src, p, items, phase_ws, tb);
-    int rc = nae_check(ctx, hipGetLastError(), "pv_any_phase_kernel");
-    if (rc) return rc;
-    if (p.n_tiles >= 256 && n_sc * P::NB <= 0x7fffffffll) {
-        NAE_KLAUNCH(ctx, "pv_any_scan_kernel", (pv_any_scan_chunked_kernel<N>), dim3((unsigned)(n_sc * P::NB)), dim3(64 * kAnyScanChunks), 0,
-                    ctx->stream, phase_ws, n_sc, p.n_tiles, carry_in, carry_out, n_needed);
-        return nae_check(ctx, hipGetLastError(), "pv_any_scan_kernel");
+    NAE_KLAUNCH(ctx, "pv_any_phase_kernel", (unit_stride ? pv_any_phase_kernel<N, true> : pv_any_phase_kernel<N, false>), dim3((unsigned)grid),
+                dim3(64 * P::kWaves1), 0, ctx->stream, src, p, items, phase_ws, tb);
+    return nae_check(ctx, hipGetLastError(), "pv_any_phase_kernel");
+}
+
+// from 256 tiles per stream-channel on, 16 threads per bin (pv_scan_chunked_kernel); else one (pv_scan_kernel)
+template <int N>
+static int launch_scan(nae_ctx* ctx, const char* name, uint32_t* phase_ws, long long n_sc, int n_tiles, const uint32_t* carry_in,
+                       uint32_t* carry_out, int n_read)
+{
+    using P = PvAny<N>;
+    if (n_tiles >= 256 && n_sc * P::NB <= 0x7fffffffll) {
+        NAE_KLAUNCH(ctx, name, (pv_scan_chunked_kernel<N>), dim3((unsigned)(n_sc * P::NB)), dim3(64 * kScanChunks), 0, ctx->stream,
+                    phase_ws, n_sc, n_tiles, carry_in, carry_out, n_read);
+        return nae_check(ctx, hipGetLastError(), name);
     }
-    const long long threads = n_sc * P::PAD;
-    if ((threads + 255) / 256 > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_scan_kernel: grid too large");
-    NAE_KLAUNCH(ctx, "pv_any_scan_kernel", (pv_any_scan_kernel<N>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
-                phase_ws, n_sc, p.n_tiles, carry_in, carry_out, n_needed);
-    return nae_check(ctx, hipGetLastError(), "pv_any_scan_kernel");
+    const long long grid = (n_sc * P::PAD + 255) / 256;
+    if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_scan_kernel: grid too large");
+    NAE_KLAUNCH(ctx, name, (pv_scan_kernel<N>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, phase_ws, n_sc, n_tiles, carry_in, carry_out,
+                n_read);
+    return nae_check(ctx, hipGetLastError(), name);
 }
 
 template <int N, bool kFormant>
@@ -465,21 +492,22 @@ static int launch_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, lo
     if (items == 0) return NAE_OK;
     const long long grid = (items + P::kWaves3 - 1) / P::kWaves3;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_synth_kernel: grid too large");
-    if (unit_stride)
-        NAE_KLAUNCH(ctx, name, (pv_any_synth_kernel<N, true, kFormant>), dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream,
-                    src, p, items, phase_ws, out, tb, lifter, g);
-    else
-        NAE_KLAUNCH(ctx, name, (pv_any_synth_kernel<N, false, kFormant>), dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream,
-                    src, p, items, phase_ws, out, tb, lifter, g);
+    NAE_KLAUNCH(ctx, name, (unit_stride ? pv_any_synth_kernel<N, true, kFormant> : pv_any_synth_kernel<N, false, kFormant>), dim3((unsigned)grid),
+                dim3(64 * P::kWaves3), 0, ctx->stream, src, p, items, phase_ws, out, tb, lifter, g);
     return nae_check(ctx, hipGetLastError(), name);
 }
 
-template <int N>
-static int launch_synth_n(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
-                          const OutViewD& out, const SpecAnyTables& tb, int lifter, float g)
+// f(std::integral_constant<int, N>()) at the vocoder size N = n_fft
+template <typename F>
+static int at_size(nae_ctx* ctx, int n_fft, F&& f)
 {
-    if (lifter > 0) return launch_synth<N, true>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g);
-    return launch_synth<N, false>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, 0, 0.0f);
+    switch (n_fft) {
+    case 512: return f(std::integral_constant<int, 512>());
+    case 1024: return f(std::integral_constant<int, 1024>());
+    case 2048: return f(std::integral_constant<int, 2048>());
+    case 4096: return f(std::integral_constant<int, 4096>());
+    default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
+    }
 }
 
 } // namespace nae
@@ -491,41 +519,28 @@ size_t nae_pv_record_pad(int n_fft) { return (size_t)((n_fft / 2 + 1 + 7) & ~7);
 
 bool nae_pv_size_ok(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096; }
 
-// Tile of a block call (synthesis tile = pass-1 tile): one wave walks a tile, so the tiles are cut for one round of the pass-3 waves the CUs hold
-// (kResident3 per CU: 16 at 512 down to 3 at 4096) where the stream-channels alone do not give them — more tiles would not add occupancy, only
-// re-analysis (a tile pays one priming and three tail frames) — and never shorter than 64 frames (pv_min_ptile: that many).  A single tile per
-// stream-channel needs no pass 1.  pv_tile forces the tile.
-int nae_pick_pvany_tile(nae_ctx* ctx, int n_fft, size_t frames, size_t n_sc, bool formant)
+int nae_pv_resident3(nae_ctx* ctx, int n_fft, bool formant)
 {
-    if (ctx->pv_tile > 0) return ctx->pv_tile;
-    const size_t min_tile = ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64;
-    const size_t n_cu = (size_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
-    if (frames == 0 || n_sc == 0) return (int)min_tile;
-    const size_t resident = formant ? (n_fft == 512 ? PvAny<512, true>::kResident3 : n_fft == 2048 ? PvAny<2048, true>::kResident3
-                                       : n_fft == 4096 ? PvAny<4096, true>::kResident3 : PvAny<1024, true>::kResident3)
-                                    : (n_fft == 512 ? PvAny<512>::kResident3 : n_fft == 2048 ? PvAny<2048>::kResident3
-                                       : n_fft == 4096 ? PvAny<4096>::kResident3 : PvAny<1024>::kResident3);
-    size_t n_tiles = (resident * n_cu + n_sc - 1) / n_sc;
-    const size_t max_tiles = (frames + min_tile - 1) / min_tile;
-    if (n_tiles > max_tiles) n_tiles = max_tiles;
-    if (n_tiles < 1) n_tiles = 1;
-    const size_t tile = (frames + n_tiles - 1) / n_tiles;
-    return (int)(tile < 0x40000000 ? tile : 0x40000000);
+    return at_size(ctx, n_fft, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        return formant ? PvAny<N, true>::kResident3 : PvAny<N>::kResident3;
+    });
 }
 
-int nae_launch_pvany_phase(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
-                           uint32_t* phase_ws, const uint32_t* carry_in, uint32_t* carry_out)
+int nae_launch_pvany_phase(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, uint32_t* phase_ws)
 {
     SpecAnyTables tb;
     int rc = nae_spec_any_tables(ctx, n_fft, &tb);
     if (rc) return rc;
-    switch (n_fft) {
-    case 512: return launch_phase<512>(ctx, p, src, n_sc, unit_stride, n_needed, phase_ws, carry_in, carry_out, tb);
-    case 1024: return launch_phase<1024>(ctx, p, src, n_sc, unit_stride, n_needed, phase_ws, carry_in, carry_out, tb);
-    case 2048: return launch_phase<2048>(ctx, p, src, n_sc, unit_stride, n_needed, phase_ws, carry_in, carry_out, tb);
-    case 4096: return launch_phase<4096>(ctx, p, src, n_sc, unit_stride, n_needed, phase_ws, carry_in, carry_out, tb);
-    default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
-    }
+    return at_size(ctx, n_fft, [&](auto n) { return launch_phase<decltype(n)::value>(ctx, p, src, n_sc, unit_stride, phase_ws, tb); });
+}
+
+int nae_launch_pv_scan(nae_ctx* ctx, int n_fft, const char* name, uint32_t* phase_ws, long long n_sc, int n_tiles, const uint32_t* carry_in,
+                       uint32_t* carry_out, int n_read)
+{
+    return at_size(ctx, n_fft, [&](auto n) {
+        return launch_scan<decltype(n)::value>(ctx, name, phase_ws, n_sc, n_tiles, carry_in, carry_out, n_read);
+    });
 }
 
 int nae_launch_pvany_synth(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride,
@@ -534,11 +549,9 @@ int nae_launch_pvany_synth(nae_ctx* ctx, int n_fft, const PvParams& p, const Sig
     SpecAnyTables tb;
     int rc = nae_spec_any_tables(ctx, n_fft, &tb);
     if (rc) return rc;
-    switch (n_fft) {
-    case 512: return launch_synth_n<512>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g);
-    case 1024: return launch_synth_n<1024>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g);
-    case 2048: return launch_synth_n<2048>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g);
-    case 4096: return launch_synth_n<4096>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g);
-    default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
-    }
+    return at_size(ctx, n_fft, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        return lifter > 0 ? launch_synth<N, true>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g)
+                          : launch_synth<N, false>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, 0, 0.0f);
+    });
 }

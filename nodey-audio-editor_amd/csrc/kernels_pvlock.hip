@@ -518,22 +518,6 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
 // ================================================================================================ host side
 using namespace nae;
 
-// Shape of a locked block call (synthesis tile = pass-1 tile): one wave walks a tile, so the tiles are cut for four waves per SIMD (16 n_cu
-// stream-channel tiles) where the stream-channels alone do not give them, never shorter than 64 frames (a tile pays one priming and three tail
-// frames).  A single tile per stream-channel needs no pass L1.  pv_tile forces the tile, as for the unlocked vocoder.
-int nae_pick_pvlock_tile(nae_ctx* ctx, size_t frames, size_t n_sc)
-{
-    if (ctx->pv_tile > 0) return ctx->pv_tile;
-    const size_t n_cu = (size_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
-    if (frames == 0 || n_sc == 0) return 64;
-    size_t n_tiles = (16 * n_cu + n_sc - 1) / n_sc;
-    const size_t max_tiles = (frames + 63) / 64;
-    if (n_tiles > max_tiles) n_tiles = max_tiles;
-    if (n_tiles < 1) n_tiles = 1;
-    const size_t tile = (frames + n_tiles - 1) / n_tiles;
-    return (int)(tile < 0x40000000 ? tile : 0x40000000);
-}
-
 // the kernels here take more than 64 KiB of dynamic LDS: the attribute is set as for the vocoder pipeline (nae_pv_lds_attr), once per context
 // and kernel, the scan kernel at its largest size
 constexpr unsigned kAttrLockMap = 1u << 12, kAttrLockScan = 1u << 13, kAttrLockSynth = 1u << 14,   // nae_ctx::pv_attr_done (pipeline: bits 0-10)
@@ -550,12 +534,8 @@ int nae_launch_pvlock_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src
         int rc = nae_pv_lds_attr(ctx, kAttrLockMap, kLdsLockMap, reinterpret_cast<const void*>(pvlock_map_kernel<true>),
                                  reinterpret_cast<const void*>(pvlock_map_kernel<false>));
         if (rc) return rc;
-        if (unit_stride)
-            NAE_KLAUNCH(ctx, "pvlock_map_kernel", (pvlock_map_kernel<true>), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream,
-                        src, p, items, maps, sig16, tb);
-        else
-            NAE_KLAUNCH(ctx, "pvlock_map_kernel", (pvlock_map_kernel<false>), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream,
-                        src, p, items, maps, sig16, tb);
+        NAE_KLAUNCH(ctx, "pvlock_map_kernel", (unit_stride ? pvlock_map_kernel<true> : pvlock_map_kernel<false>), dim3((unsigned)grid), dim3(kThreads),
+                    kLdsLockMap, ctx->stream, src, p, items, maps, sig16, tb);
         rc = nae_check(ctx, hipGetLastError(), "pvlock_map_kernel");
         if (rc) return rc;
     }
@@ -578,12 +558,8 @@ static int launch_lock_synth(nae_ctx* ctx, unsigned attr_bit, const char* name, 
     int rc = nae_pv_lds_attr(ctx, attr_bit, kLdsLockSynth, reinterpret_cast<const void*>(pvlock_synth_kernel<true, kFormant>),
                              reinterpret_cast<const void*>(pvlock_synth_kernel<false, kFormant>));
     if (rc) return rc;
-    if (unit_stride)
-        NAE_KLAUNCH(ctx, name, (pvlock_synth_kernel<true, kFormant>), dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream,
-                    src, p, items, phase_ws, out, tb, lifter, g);
-    else
-        NAE_KLAUNCH(ctx, name, (pvlock_synth_kernel<false, kFormant>), dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream,
-                    src, p, items, phase_ws, out, tb, lifter, g);
+    NAE_KLAUNCH(ctx, name, (unit_stride ? pvlock_synth_kernel<true, kFormant> : pvlock_synth_kernel<false, kFormant>), dim3((unsigned)grid),
+                dim3(kThreads), kLdsLockSynth, ctx->stream, src, p, items, phase_ws, out, tb, lifter, g);
     return nae_check(ctx, hipGetLastError(), name);
 }
 

@@ -5,7 +5,7 @@
 //     that only share the read-only Hann / split-twiddle tables in LDS (one __syncthreads after the table
 //     fill, none afterwards).
 //   * the phase accumulator is Q0.32 integer, so the time recurrence of the vocoder is an exact prefix sum:
-//     pass 1 (pv_phase_kernel) reduces each tile's phase increments, pass 2 (pv_scan_kernel) scans tiles,
+//     pass 1 (pv_phase_kernel) reduces each tile's phase increments, pass 2 (pv_scan_kernel, kernels_pv_any.hip) scans tiles,
 //     pass 3 (kernels_pvpipe.hip) recomputes the tile with the right starting phase and overlap-adds in registers.
 //     HBM traffic stays at the algorithmic 4 B in + 4 B out per sample per channel (+ one re-read in pass 1).
 //
@@ -77,89 +77,6 @@ __global__ __launch_bounds__(kThreads, 6) void pv_phase_kernel(SigViewD src, PvP
 #pragma unroll
     for (int r = 0; r < 8; r++) o[kl + 64 * r] = acc[r];
     if (lane == 0) o[512] = acc[8];
-}
-
-// pass 2: exclusive prefix over tiles, in place.  one thread per (stream-channel, bin).
-// carry_in (optional): phase in front of tile 0, [n_sc][520]; carry_out (optional): phase behind the last tile.
-__global__ void pv_scan_kernel(uint32_t* __restrict__ sums, long long n_sc, int n_tiles,
-                               const uint32_t* __restrict__ carry_in, uint32_t* __restrict__ carry_out, int n_read)
-{
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long sc = t / kT1024Pad;
-    const int k = (int)(t % kT1024Pad);
-    if (sc >= n_sc || k >= NAE_FFT_BINS) return;
-    uint32_t* p = sums + sc * n_tiles * (long long)kT1024Pad + k;
-    uint32_t run = carry_in ? carry_in[sc * kT1024Pad + k] : 0u;
-    int j = 0;
-    // the loads do not depend on the running sum: fetch 8 tiles ahead, then prefix them
-    for (; j + 8 <= n_read; j += 8) {
-        uint32_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = p[(long long)(j + u) * kT1024Pad];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            p[(long long)(j + u) * kT1024Pad] = run;
-            run += v[u];
-        }
-    }
-    for (; j < n_tiles; j++) {
-        const uint32_t v = (j < n_read) ? p[(long long)j * kT1024Pad] : 0u;
-        p[(long long)j * kT1024Pad] = run;
-        run += v;
-    }
-    if (carry_out) carry_out[sc * kT1024Pad + k] = run;
-}
-
-// the same for many tiles per stream-channel (a long lone stream: thousands of tiles on a few stream-channels, where one thread per bin walks them
-// one after the other): 16 threads per bin take a sixteenth of the tiles each — sum it, exchange the 16 sums through LDS, prefix the own part
-// (modular integer sums: the split changes no bit).  One workgroup per (stream-channel, 64 bins).
-constexpr int kScanChunks = 16;
-__global__ __launch_bounds__(64 * kScanChunks) void pv_scan_chunked_kernel(uint32_t* __restrict__ sums, long long n_sc, int n_tiles,
-                                                                          const uint32_t* __restrict__ carry_in, uint32_t* __restrict__ carry_out, int n_read)
-{
-    __shared__ uint32_t part[kScanChunks][64];
-    const int kb = threadIdx.x & 63, ck = threadIdx.x >> 6;
-    const long long sc = blockIdx.x / 9;
-    const int k = (int)(blockIdx.x % 9) * 64 + kb;
-    const bool valid = k < NAE_FFT_BINS;
-    const int per = (n_tiles + kScanChunks - 1) / kScanChunks;
-    const int j0 = ck * per, j1 = (j0 + per < n_tiles) ? j0 + per : n_tiles;
-    const int r1 = j1 < n_read ? j1 : n_read;                       // tiles at or beyond n_read count as zero
-    uint32_t* p = sums + sc * n_tiles * (long long)kT1024Pad + (valid ? k : 0);
-    uint32_t sum = 0;
-    if (valid) {
-        int j = j0;
-        for (; j + 8 <= r1; j += 8) {
-            uint32_t v[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) v[u] = p[(long long)(j + u) * kT1024Pad];
-#pragma unroll
-            for (int u = 0; u < 8; u++) sum += v[u];
-        }
-        for (; j < r1; j++) sum += p[(long long)j * kT1024Pad];
-    }
-    part[ck][kb] = sum;
-    __syncthreads();
-    uint32_t run = (valid && carry_in) ? carry_in[sc * kT1024Pad + k] : 0u;
-    for (int c2 = 0; c2 < ck; c2++) run += part[c2][kb];
-    if (!valid) return;
-    int j = j0;
-    for (; j + 8 <= r1; j += 8) {
-        uint32_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = p[(long long)(j + u) * kT1024Pad];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            p[(long long)(j + u) * kT1024Pad] = run;
-            run += v[u];
-        }
-    }
-    for (; j < j1; j++) {
-        const uint32_t v = (j < n_read) ? p[(long long)j * kT1024Pad] : 0u;
-        p[(long long)j * kT1024Pad] = run;
-        run += v;
-    }
-    if (carry_out && ck == kScanChunks - 1) carry_out[sc * kT1024Pad + k] = run;
 }
 
 // rate transposer: out[j] = sum_i tab(phase)[i] * v[idx - 7 + i],  pos = j * step (Q32.32)
@@ -623,7 +540,7 @@ size_t nae_pv_workspace_bytes(bool lock, int n_fft, size_t n_frames, int ch, siz
 // tiles keep the chip full on small batches, while pass 3 wants few long tiles (each re-analyses its frames).
 // Only the sums (locked: maps) in front of the last synthesis tile are needed, unless the phase behind the segment is carried on (a
 // continued stream): nothing at all when the stream-channel is a single synthesis tile.
-// n_fft other than 1024 (or the debug key pv_any) runs the size-generic kernels of kernels_pv_any.hip; lock is 1024 only (the callers check).
+// Pass 1 as nae_pv_route_of says; unlocked, either pass 1 is followed by the one scan (pv_scan_kernel, kernels_pv_any.hip).
 int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg)
 {
@@ -653,43 +570,34 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
         return nae_check(ctx, e, "phase base init");
     }
     p.skip_from = n_needed;                   // pass 1 skips the tiles whose sums are not needed
-    if (!lock && (n_fft != NAE_FFT_N || ctx->dbg_pv_any))
-        return nae_launch_pvany_phase(ctx, n_fft, p, to_view(src), n_sc, src->frame_stride == 1, n_needed, phase_ws, carry_in, carry_out);
-    if (lock) {
+    const PvKernels pass1 = nae_pv_route_of(ctx, lock, n_fft, 0).pass1;
+    const bool unit_stride = src->frame_stride == 1;
+    if (pass1 == PvKernels::kLock) {
         const size_t n_rec = (size_t)n_sc * p.n_tiles;
         uint32_t* maps = phase_ws + n_rec * kT1024Pad;
         uint16_t* sig16 = reinterpret_cast<uint16_t*>(maps + n_rec * kT1024Pad);
-        return nae_launch_pvlock_phase(ctx, p, to_view(src), n_sc, src->frame_stride == 1, n_needed, phase_ws, maps, sig16, carry_in, carry_out);
+        return nae_launch_pvlock_phase(ctx, p, to_view(src), n_sc, unit_stride, n_needed, phase_ws, maps, sig16, carry_in, carry_out);
     }
-    Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
-    {
+    if (pass1 == PvKernels::kAny) {
+        const int rc = nae_launch_pvany_phase(ctx, n_fft, p, to_view(src), n_sc, unit_stride, phase_ws);
+        if (rc) return rc;
+    } else {
         // items are (stream-channel, tile) with tile fastest
         const long long items = n_sc * p.n_tiles;
-        const unsigned grid = (unsigned)((items + kWaves - 1) / kWaves);
-        const size_t lds = kLdsPhase;
-        if (src->frame_stride == 1)
-            NAE_KLAUNCH(ctx, "pv_phase_kernel", (pv_phase_kernel<true>), dim3(grid), dim3(kThreads), lds, ctx->stream,
-                        to_view(src), p, items, phase_ws, tb);
-        else
-            NAE_KLAUNCH(ctx, "pv_phase_kernel", (pv_phase_kernel<false>), dim3(grid), dim3(kThreads), lds, ctx->stream,
-                        to_view(src), p, items, phase_ws, tb);
-        int rc = nae_check(ctx, hipGetLastError(), "pv_phase_kernel");
+        const long long grid = (items + kWaves - 1) / kWaves;
+        if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_phase_kernel: grid too large");
+        const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+        NAE_KLAUNCH(ctx, "pv_phase_kernel", (unit_stride ? pv_phase_kernel<true> : pv_phase_kernel<false>), dim3((unsigned)grid), dim3(kThreads),
+                    kLdsPhase, ctx->stream, to_view(src), p, items, phase_ws, tb);
+        const int rc = nae_check(ctx, hipGetLastError(), "pv_phase_kernel");
         if (rc) return rc;
     }
-    if (p.n_tiles >= 256 && n_sc * 9 <= 0x7fffffffll) {
-        NAE_KLAUNCH(ctx, "pv_scan_kernel", pv_scan_chunked_kernel, dim3((unsigned)(n_sc * 9)), dim3(64 * kScanChunks), 0, ctx->stream, phase_ws, n_sc, p.n_tiles,
-                    carry_in, carry_out, n_needed);
-        return nae_check(ctx, hipGetLastError(), "pv_scan_kernel");
-    }
-    const long long threads = n_sc * kT1024Pad;
-    const unsigned grid = (unsigned)((threads + 255) / 256);
-    NAE_KLAUNCH(ctx, "pv_scan_kernel", pv_scan_kernel, dim3(grid), dim3(256), 0, ctx->stream, phase_ws, n_sc, p.n_tiles,
-                carry_in, carry_out, n_needed);
-    return nae_check(ctx, hipGetLastError(), "pv_scan_kernel");
+    return nae_launch_pv_scan(ctx, n_fft, pass1 == PvKernels::kAny ? "pv_any_scan_kernel" : "pv_scan_kernel", phase_ws, n_sc, p.n_tiles, carry_in,
+                              carry_out, n_needed);
 }
 
-// pass 3 (locked: L3) from the records of pass 2 (or, one tile and nothing carried in, from zero); lifter > 0 with both stages on: formant
-// preservation (unlocked: on the size-generic pass 3 at every size, which reads the same records)
+// pass 3 (locked: L3) from the records of pass 2 (or, one tile and nothing carried in, from zero), on the kernels nae_pv_route_of says; lifter > 0
+// with both stages on: formant preservation
 int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
                         const nae_pv_segment* seg, int frames_per_step, int lifter)
@@ -708,10 +616,11 @@ int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
     }
     const long long n_sc = (long long)n_streams * ch;
     const float g = (float)pl->rate_eff;                   // formant preservation: the transposer ratio
-    if (lock) return nae_launch_pvlock_synth(ctx, p, to_view(src), n_sc, src->frame_stride == 1, phase_ws, to_out(out), lifter, g);
-    if (n_fft != NAE_FFT_N || ctx->dbg_pv_any || lifter > 0)
-        return nae_launch_pvany_synth(ctx, n_fft, p, to_view(src), n_sc, src->frame_stride == 1, phase_ws, to_out(out), lifter, g);
-    return nae_launch_pv_pipe(ctx, p, to_view(src), n_sc, phase_ws, to_out(out), src->frame_stride == 1, frames_per_step);
+    const bool unit_stride = src->frame_stride == 1;
+    const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, lifter).pass3;
+    if (pass3 == PvKernels::kLock) return nae_launch_pvlock_synth(ctx, p, to_view(src), n_sc, unit_stride, phase_ws, to_out(out), lifter, g);
+    if (pass3 == PvKernels::kAny) return nae_launch_pvany_synth(ctx, n_fft, p, to_view(src), n_sc, unit_stride, phase_ws, to_out(out), lifter, g);
+    return nae_launch_pv_pipe(ctx, p, to_view(src), n_sc, phase_ws, to_out(out), unit_stride, frames_per_step);
 }
 
 // outputs [j_begin, j_end)

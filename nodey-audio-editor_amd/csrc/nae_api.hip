@@ -208,6 +208,23 @@ int nae_pick_pv_shape(nae_ctx* ctx, size_t frames, size_t n_sc, int* phase_tile,
     return (int)(pt * step);
 }
 
+// Tile of a block call whose pass 3 walks one tile per wave (the size-generic and the locked vocoder; synthesis tile = pass-1 tile): the tiles are
+// cut for one round of the `resident` pass-3 waves a CU holds where the stream-channels alone do not give them — more tiles would not add occupancy,
+// only re-analysis (a tile pays one priming and three tail frames) — and never shorter than `min_tile` frames.  A single tile per stream-channel
+// needs no pass 1.  pv_tile forces the tile.
+static int pick_wave_tile(nae_ctx* ctx, size_t frames, size_t n_sc, size_t resident, size_t min_tile)
+{
+    if (ctx->pv_tile > 0) return ctx->pv_tile;
+    const size_t n_cu = (size_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
+    if (frames == 0 || n_sc == 0) return (int)min_tile;
+    size_t n_tiles = (resident * n_cu + n_sc - 1) / n_sc;
+    const size_t max_tiles = (frames + min_tile - 1) / min_tile;
+    if (n_tiles > max_tiles) n_tiles = max_tiles;
+    if (n_tiles < 1) n_tiles = 1;
+    const size_t tile = (frames + n_tiles - 1) / n_tiles;
+    return (int)(tile < 0x40000000 ? tile : 0x40000000);
+}
+
 extern "C" {
 
 int nae_abi_version(void) { return NAE_ABI_VERSION; }
@@ -544,6 +561,16 @@ static int check_sig(nae_ctx* ctx, const nae_sig* s, const char* what)
 
 } // extern "C"
 
+// the signal between the transposer and the vocoder: planar in the context's workspace, rows padded to 4 frames (16-byte accesses on both sides)
+static int reserve_mid(nae_ctx* ctx, const nae_stretch_plan& pl, int ch, size_t n_streams, nae_sig* mid)
+{
+    const size_t mid_stride = (pl.mid_len + 3) & ~(size_t)3;
+    const int rc = nae_ws_reserve(ctx, &ctx->ws_mid, &ctx->ws_mid_bytes, n_streams * ch * mid_stride * sizeof(float));
+    if (rc) return rc;
+    *mid = nae_sig{ctx->ws_mid, (size_t)ch * mid_stride, mid_stride, 1};
+    return NAE_OK;
+}
+
 // the one statement of the _n entries' rules: an unknown flag NAE_ERR_INVALID; a size outside 512 / 1024 / 2048 / 4096, or the phase lock at a
 // size other than 1024, NAE_ERR_UNSUPPORTED
 int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft)
@@ -597,13 +624,8 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
         return (stages & 2) ? nae_launch_copy_sig(ctx, src, dst, in_len, ch, n_streams, false, 1.0f) : NAE_OK;
     }
 
-    const size_t mid_stride = (pl.mid_len + 3) & ~(size_t)3;
     nae_sig mid{};
-    if (pl.pv_on && pl.rs_on) {
-        rc = nae_ws_reserve(ctx, &ctx->ws_mid, &ctx->ws_mid_bytes, n_streams * ch * mid_stride * sizeof(float));
-        if (rc) return rc;
-        mid = nae_sig{ctx->ws_mid, (size_t)ch * mid_stride, mid_stride, 1};   // planar: 16-byte accesses on both sides
-    }
+    if (pl.pv_on && pl.rs_on && (rc = reserve_mid(ctx, pl, ch, n_streams, &mid))) return rc;
     if (pl.rs_on) {
         rc = nae_ensure_rs_table(ctx, pl.rate_eff);
         if (rc) return rc;
@@ -640,8 +662,12 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
         int phase_tile = 0, fps = 1;
         int tile;
         const int q = nae_formant_lifter_eff(pl, lifter);
-        if (lock) tile = phase_tile = nae_pick_pvlock_tile(ctx, pl.frames, n_streams * ch);
-        else if (n_fft != NAE_FFT_N || ctx->dbg_pv_any || q > 0) tile = phase_tile = nae_pick_pvany_tile(ctx, n_fft, pl.frames, n_streams * ch, q > 0);
+        const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, q).pass3;
+        if (pass3 == PvKernels::kLock)   // four waves per SIMD, tiles of at least 64 frames (pv_min_ptile does not apply)
+            tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, 16, 64);
+        else if (pass3 == PvKernels::kAny)
+            tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, (size_t)nae_pv_resident3(ctx, n_fft, q > 0),
+                                               ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64);
         else tile = nae_pick_pv_shape(ctx, pl.frames, n_streams * ch, &phase_tile, &fps);
         rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, n_fft, pl.frames, ch, n_streams, phase_tile));
         if (rc) return rc;
@@ -748,10 +774,8 @@ int nae_debug_pv_tile_phase_n(nae_ctx* ctx, double rate, double pitch, unsigned 
     size_t pv_in_len = in_len;
     nae_sig mid{};
     if (pl.rs_first) {
-        const size_t mid_stride = (pl.mid_len + 3) & ~(size_t)3;
-        rc = nae_ws_reserve(ctx, &ctx->ws_mid, &ctx->ws_mid_bytes, n_streams * ch * mid_stride * sizeof(float));
+        rc = reserve_mid(ctx, pl, ch, n_streams, &mid);
         if (rc) return rc;
-        mid = nae_sig{ctx->ws_mid, (size_t)ch * mid_stride, mid_stride, 1};
         rc = nae_ensure_rs_table(ctx, pl.rate_eff);
         if (rc) return rc;
         rc = nae_launch_resample(ctx, &pl, src, in_len, ch, n_streams, ctx->d_rs_tab, &mid, 0, pl.mid_len);

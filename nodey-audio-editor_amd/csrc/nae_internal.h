@@ -122,12 +122,25 @@ int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
                         const nae_pv_segment* seg, int frames_per_step, int lifter = 0);
 // the lifter pass 3 runs with: formant preservation applies only when the plan runs both the vocoder and the transposer
 inline int nae_formant_lifter_eff(const nae_stretch_plan& pl, int lifter) { return pl.pv_on && pl.rs_on ? lifter : 0; }
-int nae_pick_pvlock_tile(nae_ctx* ctx, size_t frames, size_t n_sc);   // kernels_pvlock.hip
+// The kernels a vocoder call runs, for the tile choice of a block call, nae_launch_pv_phase and nae_launch_pv_synth:
+//   pass 1  kShipped: pv_phase_kernel (1024 points); kAny: pv_any_phase_kernel<N> (kernels_pv_any.hip); kLock: pvlock_map_kernel and its scan;
+//   pass 3  kShipped: the pipeline (kernels_pvpipe.hip);  kAny: pv_any_synth_kernel<N>;                   kLock: pvlock_synth_kernel.
+// Locked calls (1024 only: the callers check) run the locked kernels; unlocked calls at other sizes, or under the debug key pv_any, the size-generic
+// ones.  Pass 1 does not depend on the lifter.  Unlocked 1024-point calls with formant preservation (lifter_eff > 0) run the shipped pass 1 and
+// the size-generic pass 3: the pipeline has no formant stage, and the two passes share the record layout.
+enum class PvKernels { kShipped, kAny, kLock };
+struct nae_pv_route { PvKernels pass1, pass3; };
+inline nae_pv_route nae_pv_route_of(const nae_ctx* ctx, bool lock, int n_fft, int lifter_eff)
+{
+    if (lock) return {PvKernels::kLock, PvKernels::kLock};
+    const PvKernels pass1 = n_fft != NAE_FFT_N || ctx->dbg_pv_any ? PvKernels::kAny : PvKernels::kShipped;
+    return {pass1, lifter_eff > 0 ? PvKernels::kAny : pass1};
+}
 // kernels_pv_any.hip: the vocoder sizes (512, 1024, 2048, 4096), the record length of a size (int32: N/2 + 1 padded to a multiple of 8), the
-// tile of a size-generic block call (formant: for the formant pass 3)
+// pass-3 waves a CU holds on the size-generic kernels (PvAny<N>::kResident3; formant: of the formant pass 3)
 bool nae_pv_size_ok(int n_fft);
 size_t nae_pv_record_pad(int n_fft);
-int nae_pick_pvany_tile(nae_ctx* ctx, int n_fft, size_t frames, size_t n_sc, bool formant = false);
+int nae_pv_resident3(nae_ctx* ctx, int n_fft, bool formant);
 int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft);   // nae_api.hip: flags and size of the _n entries
 int nae_formant_check(nae_ctx* ctx, int n_fft, int lifter);         // nae_api.hip: the lifter of the _formant entries
 int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t src_len, int ch,
