@@ -7,7 +7,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <utility>
 
 #include "stream_util.h"
 
@@ -19,17 +18,15 @@ struct nae_stretch {
     int n_fft = NAE_FFT_N;        // vocoder frame size, hop n_fft / 4 (nae_stretch_create_n)
     int lifter = 0;               // formant preservation's lifter, 0 = off (nae_stretch_create_formant)
     nae_stretch_plan pl{};        // parameters (in_len = 0)
-    DevFifo in;                   // interleaved input, sample-frames [in.base, in_total)
-    size_t in_total = 0;
+    DevFifo in;                   // interleaved input, sample-frames
     // phase vocoder
     size_t blocks_done = 0;       // hop blocks produced == frames folded into the carried phase
     uint32_t* carry[2] = {nullptr, nullptr};
     int carry_cur = 0;
-    DevFifo mid;                  // planar stretched signal, per-channel capacity mid_cap, samples [mid.base, mid_total)
-    size_t mid_cap = 0, mid_total = 0;
+    DevFifo mid;                  // between the stages: planar when the vocoder runs first, else interleaved
     // output
-    DevFifo out;                  // interleaved result, sample-frames [out.base, out_total)
-    size_t out_total = 0, out_read = 0;
+    DevFifo out;                  // interleaved result, sample-frames
+    size_t out_read = 0;
     bool flushed = false;
 };
 
@@ -37,12 +34,9 @@ struct nae_spectrum {
     nae_ctx* ctx;
     int ch;
     int n_fft = NAE_FFT_N, hop = NAE_HOP;
-    // ping-pong pairs: the live data always moves into the OTHER buffer of its pair (an in-place forward move would
-    // overlap), and nothing is allocated, freed or waited for once the buffers have grown to their working size
-    DevBuf pending, pending_alt;   // interleaved samples not yet covered by a complete hop
-    DevBuf out, out_alt;           // [frames][ch][n_fft/2 + 1]
+    DevFifo pending;               // interleaved samples, from the first one the next frame needs
+    DevFifo out;                   // frames of [ch][n_fft/2 + 1]
     size_t out_read = 0;           // frames handed out
-    size_t out_frames = 0;
 };
 
 namespace {
@@ -101,49 +95,38 @@ int stretch_process(nae_stretch* h)
     const int ch = h->ch;
     const nae_stretch_plan& pl = h->pl;
     const size_t hop = (size_t)h->n_fft / 4;     // hop blocks of the vocoder stage
+    DevFifo &in = h->in, &mid = h->mid, &out = h->out;
     nae_stretch_plan fin{};
     if (h->flushed) {
-        int rc = nae_stretch_plan_make_n(h->rate, h->pitch, h->n_fft, h->in_total, &fin);
+        int rc = nae_stretch_plan_make_n(h->rate, h->pitch, h->n_fft, in.total, &fin);
         if (rc) return rc;
     }
     // ---- neither stage: the node is a wire
     if (!pl.pv_on && !pl.rs_on) {
-        const size_t n = h->in_total - h->out_total;
-        if (n) {
-            int rc = fifo_reserve_interleaved(ctx, h->out, h->out_total, h->in_total, ch);
-            if (rc) return rc;
-            hipError_t e = hipMemcpyAsync(h->out.cur.p + (h->out_total - h->out.base) * ch, h->in.cur.p + (h->out_total - h->in.base) * ch,
-                                          n * ch * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
-            if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(wire)");
-            h->out_total = h->in_total;
-            return fifo_drop_interleaved(ctx, h->in, h->in_total, h->in_total, ch);
-        }
-        return NAE_OK;
+        if (in.total == out.total) return NAE_OK;
+        const int rc = out.push(ctx, in.at(out.total), in.total - out.total, false);
+        if (!rc) in.drop((long long)in.total);
+        return rc;
     }
     // ---- transposer first (rate_eff > 1): in -> [RS] -> mid (interleaved FIFO) -> [PV] -> out
     if (pl.rs_first) {
         size_t J_r;
         if (h->flushed) J_r = fin.mid_len;
-        else if (h->in_total <= NAE_RS_TAPS / 2) J_r = 0;
+        else if (in.total <= NAE_RS_TAPS / 2) J_r = 0;
         else {
-            const unsigned __int128 lim = ((unsigned __int128)(h->in_total - NAE_RS_TAPS / 2) << 32) - 1;
+            const unsigned __int128 lim = ((unsigned __int128)(in.total - NAE_RS_TAPS / 2) << 32) - 1;
             J_r = (size_t)(lim / pl.step_q32) + 1;
         }
-        if (J_r > h->mid_total) {
+        if (J_r > mid.total) {
             int rc = nae_ensure_rs_table(ctx, pl.rate_eff);
+            if (!rc) rc = mid.reserve(ctx, J_r);
             if (rc) return rc;
-            rc = fifo_reserve_interleaved(ctx, h->mid, h->mid_total, J_r, ch);
+            const nae_sig src = in.view(), dst = mid.view();
+            rc = nae_launch_resample(ctx, &pl, &src, in.total, ch, 1, ctx->d_rs_tab, &dst, mid.total, J_r);
             if (rc) return rc;
-            nae_sig src{h->in.cur.p - (ptrdiff_t)h->in.base * ch, 0, 1, (size_t)ch};
-            nae_sig dst{h->mid.cur.p - (ptrdiff_t)h->mid.base * ch, 0, 1, (size_t)ch};
-            rc = nae_launch_resample(ctx, &pl, &src, h->in_total, ch, 1, ctx->d_rs_tab, &dst, h->mid_total, J_r);
-            if (rc) return rc;
-            h->mid_total = J_r;
+            mid.total = J_r;
             const unsigned __int128 pos = (unsigned __int128)J_r * pl.step_q32;
-            const long long need_from = ((long long)(pos >> 32) - (NAE_RS_TAPS / 2 - 1)) & ~3ll;
-            const size_t nb = need_from > 0 ? (size_t)need_from : 0;
-            rc = fifo_drop_interleaved(ctx, h->in, nb < h->in_total ? nb : h->in_total, h->in_total, ch);
-            if (rc) return rc;
+            in.drop(((long long)(pos >> 32) - (NAE_RS_TAPS / 2 - 1)) & ~3ll);
         }
         size_t F_r, B_r;
         long long out_limit;
@@ -152,22 +135,18 @@ int stretch_process(nae_stretch* h)
             B_r = (fin.out_len + hop - 1) / hop;
             out_limit = (long long)fin.out_len;
         } else {
-            F_r = frames_available(pl, h->n_fft, h->mid_total);
+            F_r = frames_available(pl, h->n_fft, mid.total);
             B_r = F_r >= 3 ? F_r - 3 : 0;
             out_limit = (long long)1 << 60;
         }
         if (B_r > h->blocks_done) {
             const size_t produced_total = h->flushed ? fin.out_len : B_r * hop;
-            int rc = fifo_reserve_interleaved(ctx, h->out, h->out_total, produced_total, ch);
+            int rc = out.reserve(ctx, produced_total);
             if (rc) return rc;
-            const nae_sig src{h->mid.cur.p - (ptrdiff_t)h->mid.base * ch, 0, 1, (size_t)ch};
-            nae_sig dst{h->out.cur.p - (ptrdiff_t)h->out.base * ch, 0, 1, (size_t)ch};
-            rc = stretch_pv_stage(h, pl, src, h->mid_total, F_r, B_r, out_limit, dst);
+            rc = stretch_pv_stage(h, pl, mid.view(), mid.total, F_r, B_r, out_limit, out.view());
             if (rc) return rc;
-            h->out_total = produced_total;
-            const long long s_keep = frame_start_host(pl, h->n_fft, (long long)B_r - 1);
-            rc = fifo_drop_interleaved(ctx, h->mid, s_keep > 0 ? (size_t)s_keep : 0, h->mid_total, ch);
-            if (rc) return rc;
+            out.total = produced_total;
+            mid.drop(frame_start_host(pl, h->n_fft, (long long)B_r - 1));
         }
         return NAE_OK;
     }
@@ -181,97 +160,48 @@ int stretch_process(nae_stretch* h)
             B_r = (fin.mid_len + hop - 1) / hop;
             mid_limit = (long long)fin.mid_len;
         } else {
-            F_r = frames_available(pl, h->n_fft, h->in_total);
+            F_r = frames_available(pl, h->n_fft, in.total);
             B_r = F_r >= 3 ? F_r - 3 : 0;
             mid_limit = (long long)1 << 60;
         }
         if (B_r > h->blocks_done) {
-            int rc;
-            nae_sig dst;
             size_t produced_total = h->flushed ? fin.mid_len : B_r * hop;
-            if (pl.rs_on) {
-                // planar mid FIFO: grow (re-pack planes) when the per-channel capacity is too small
-                const size_t need = produced_total - h->mid.base;
-                if (need > h->mid_cap) {
-                    size_t cap = h->mid_cap ? h->mid_cap : 1 << 15;
-                    while (cap < need) cap *= 2;
-                    h->mid.alt.len = 0;
-                    rc = devbuf_reserve(ctx, h->mid.alt, cap * ch);
-                    if (rc) return rc;
-                    const size_t keep = h->mid_total - h->mid.base;
-                    for (int c = 0; c < ch && keep; c++) {
-                        hipError_t e = hipMemcpyAsync(h->mid.alt.p + (size_t)c * cap, h->mid.cur.p + (size_t)c * h->mid_cap, keep * sizeof(float),
-                                                      hipMemcpyDeviceToDevice, ctx->stream);
-                        if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(mid grow)");
-                    }
-                    std::swap(h->mid.cur, h->mid.alt);
-                    h->mid_cap = cap;
-                }
-                dst = nae_sig{h->mid.cur.p - (ptrdiff_t)h->mid.base, 0, h->mid_cap, 1};
-            } else {
-                if (h->flushed && produced_total > fin.out_len) produced_total = fin.out_len;
-                rc = fifo_reserve_interleaved(ctx, h->out, h->out_total, produced_total, ch);
-                if (rc) return rc;
-                dst = nae_sig{h->out.cur.p - (ptrdiff_t)h->out.base * ch, 0, 1, (size_t)ch};
-                if (h->flushed) mid_limit = (long long)fin.out_len;
+            DevFifo& dst = pl.rs_on ? mid : out;
+            if (!pl.rs_on && h->flushed) {
+                if (produced_total > fin.out_len) produced_total = fin.out_len;
+                mid_limit = (long long)fin.out_len;
             }
-            const nae_sig src{h->in.cur.p - (ptrdiff_t)h->in.base * ch, 0, 1, (size_t)ch};   // absolute indexing
-            rc = stretch_pv_stage(h, pl, src, h->in_total, F_r, B_r, mid_limit, dst);
+            int rc = dst.reserve(ctx, produced_total);
             if (rc) return rc;
-            if (pl.rs_on) h->mid_total = produced_total;
-            else h->out_total = produced_total;
+            rc = stretch_pv_stage(h, pl, in.view(), in.total, F_r, B_r, mid_limit, dst.view());
+            if (rc) return rc;
+            dst.total = produced_total;
             // input still needed: from the start of frame B_r - 1 (it primes the next call's phase difference)
-            const long long s_keep = frame_start_host(pl, h->n_fft, (long long)B_r - 1);
-            rc = fifo_drop_interleaved(ctx, h->in, s_keep > 0 ? (size_t)s_keep : 0, h->in_total, ch);
-            if (rc) return rc;
+            in.drop(frame_start_host(pl, h->n_fft, (long long)B_r - 1));
         }
     }
     // ---- stage 2: rate transposer over the outputs whose 16 taps are known
     if (pl.rs_on) {
-        const size_t src_avail = pl.pv_on ? h->mid_total : h->in_total;
+        DevFifo& src = pl.pv_on ? mid : in;
         size_t J_r;
         if (h->flushed) J_r = fin.out_len;
-        else if (src_avail <= NAE_RS_TAPS / 2) J_r = 0;
+        else if (src.total <= NAE_RS_TAPS / 2) J_r = 0;
         else {
-            const unsigned __int128 lim = ((unsigned __int128)(src_avail - NAE_RS_TAPS / 2) << 32) - 1;
+            const unsigned __int128 lim = ((unsigned __int128)(src.total - NAE_RS_TAPS / 2) << 32) - 1;
             J_r = (size_t)(lim / pl.step_q32) + 1;
         }
-        if (J_r > h->out_total) {
+        if (J_r > out.total) {
             int rc = nae_ensure_rs_table(ctx, pl.rate_eff);
+            if (!rc) rc = out.reserve(ctx, J_r);
             if (rc) return rc;
-            rc = fifo_reserve_interleaved(ctx, h->out, h->out_total, J_r, ch);
+            const nae_sig sv = src.view(), dv = out.view();
+            const size_t src_len = h->flushed && pl.pv_on ? fin.mid_len : src.total;
+            rc = nae_launch_resample(ctx, &pl, &sv, src_len, ch, 1, ctx->d_rs_tab, &dv, out.total, J_r);
             if (rc) return rc;
-            nae_sig src = pl.pv_on ? nae_sig{h->mid.cur.p - (ptrdiff_t)h->mid.base, 0, h->mid_cap, 1}
-                                   : nae_sig{h->in.cur.p - (ptrdiff_t)h->in.base * ch, 0, 1, (size_t)ch};
-            nae_sig dst{h->out.cur.p - (ptrdiff_t)h->out.base * ch, 0, 1, (size_t)ch};
-            const size_t src_len = h->flushed ? (pl.pv_on ? fin.mid_len : h->in_total) : src_avail;
-            rc = nae_launch_resample(ctx, &pl, &src, src_len, ch, 1, ctx->d_rs_tab, &dst, h->out_total, J_r);
-            if (rc) return rc;
-            h->out_total = J_r;
-            // source still needed: from idx(J_r) - 7
+            out.total = J_r;
+            // source still needed: from idx(J_r) - 7, rounded DOWN to a multiple of 4 samples as the tiled kernel stages it
             const unsigned __int128 pos = (unsigned __int128)J_r * pl.step_q32;
-            // the tiled kernel stages from (idx - 7) rounded DOWN to a multiple of 4 samples: keep that much
-            const long long need_from = ((long long)(pos >> 32) - (NAE_RS_TAPS / 2 - 1)) & ~3ll;
-            const size_t nb = need_from > 0 ? (size_t)need_from : 0;
-            if (pl.pv_on) {
-                if (nb > h->mid.base) {   // planar: shift every plane
-                    const size_t nbase = nb < h->mid_total ? nb : h->mid_total;
-                    const size_t keep = h->mid_total - nbase;
-                    h->mid.alt.len = 0;
-                    rc = devbuf_reserve(ctx, h->mid.alt, h->mid_cap * ch);
-                    if (rc) return rc;
-                    for (int c = 0; c < ch && keep; c++) {
-                        hipError_t e = hipMemcpyAsync(h->mid.alt.p + (size_t)c * h->mid_cap, h->mid.cur.p + (size_t)c * h->mid_cap + (nbase - h->mid.base),
-                                                      keep * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
-                        if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(mid shift)");
-                    }
-                    std::swap(h->mid.cur, h->mid.alt);
-                    h->mid.base = nbase;
-                }
-            } else {
-                rc = fifo_drop_interleaved(ctx, h->in, nb < h->in_total ? nb : h->in_total, h->in_total, ch);
-                if (rc) return rc;
-            }
+            src.drop(((long long)(pos >> 32) - (NAE_RS_TAPS / 2 - 1)) & ~3ll);
         }
     }
     return NAE_OK;
@@ -325,6 +255,8 @@ int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, floa
     s->n_fft = n_fft;
     s->lifter = lifter;
     s->pl = pl;
+    s->in.width = s->mid.width = s->out.width = (size_t)channels;
+    s->mid.planar = !pl.rs_first;
     *h = s;
     return NAE_OK;
 }
@@ -335,16 +267,8 @@ static int stretch_append(nae_stretch* h, const float* p, size_t S, bool host)
     (void)nae_use_device(h->ctx);
     if (h->flushed) return nae_fail(h->ctx, NAE_ERR_STATE, "put after flush");
     if (S == 0) return NAE_OK;
-    const size_t n = S * h->ch;
-    int rc = fifo_reserve_interleaved(h->ctx, h->in, h->in_total, h->in_total + S, h->ch);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(h->in.cur.p + (h->in_total - h->in.base) * h->ch, p, n * sizeof(float),
-                                  host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->ctx->stream);
-    if (e != hipSuccess) return nae_check(h->ctx, e, "hipMemcpyAsync(put)");
-    if (host) (void)hipStreamSynchronize(h->ctx->stream); // the caller may reuse its buffer
-    h->in_total += S;
-    h->in.cur.len = (h->in_total - h->in.base) * h->ch;
-    return stretch_process(h);
+    const int rc = h->in.push(h->ctx, p, S, host);
+    return rc ? rc : stretch_process(h);
 }
 
 int nae_stretch_put(nae_stretch* h, const float* interleaved, size_t S) { return stretch_append(h, interleaved, S, false); }
@@ -361,26 +285,19 @@ int nae_stretch_flush(nae_stretch* h)
     return stretch_process(h);
 }
 
-size_t nae_stretch_available(nae_stretch* h) { return h ? h->out_total - h->out_read : 0; }
+size_t nae_stretch_available(nae_stretch* h) { return h ? h->out.total - h->out_read : 0; }
 
 static int stretch_take(nae_stretch* h, float* dst, size_t max_frames, size_t* got, bool host)
 {
     if (!h || !got || (max_frames && !dst)) return NAE_ERR_INVALID;
     (void)nae_use_device(h->ctx);
-    size_t n = h->out_total - h->out_read;
+    size_t n = h->out.total - h->out_read;
     if (n > max_frames) n = max_frames;
     *got = n;
     if (n == 0) return NAE_OK;
-    hipError_t e = hipMemcpyAsync(dst, h->out.cur.p + (h->out_read - h->out.base) * h->ch, n * h->ch * sizeof(float),
-                                  host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->ctx->stream);
-    if (e != hipSuccess) return nae_check(h->ctx, e, "hipMemcpyAsync(receive)");
-    if (host) {
-        e = hipStreamSynchronize(h->ctx->stream);
-        if (e != hipSuccess) return nae_check(h->ctx, e, "hipStreamSynchronize");
-    }
+    const int rc = h->out.pop(h->ctx, h->out_read, dst, n, host);
+    if (rc) return rc;
     h->out_read += n;
-    // drop what has been handed out once it dominates the buffer
-    if (h->out_read - h->out.base > (1u << 16)) return fifo_drop_interleaved(h->ctx, h->out, h->out_read, h->out_total, h->ch);
     return NAE_OK;
 }
 
@@ -392,9 +309,9 @@ int nae_stretch_destroy(nae_stretch* h)
     if (!h) return NAE_OK;
     (void)nae_use_device(h->ctx);
     (void)hipStreamSynchronize(h->ctx->stream);
-    fifo_free(h->in);
-    fifo_free(h->mid);
-    fifo_free(h->out);
+    h->in.free();
+    h->mid.free();
+    h->out.free();
     for (int i = 0; i < 2; i++)
         if (h->carry[i]) (void)hipFree(h->carry[i]);
     delete h;
@@ -417,6 +334,8 @@ int nae_spectrum_create(nae_ctx* ctx, int n_fft, int hop, int channels, nae_spec
     s->ch = channels;
     s->n_fft = n_fft;
     s->hop = hop;
+    s->pending.width = (size_t)channels;
+    s->out.width = (size_t)channels * (size_t)(n_fft / 2 + 1);
     *h = s;
     return NAE_OK;
 }
@@ -427,66 +346,34 @@ int nae_spectrum_put(nae_spectrum* h, const float* interleaved, size_t S)
     (void)nae_use_device(h->ctx);
     if (S == 0) return NAE_OK;
     nae_ctx* ctx = h->ctx;
-    const size_t n = S * h->ch;
-    int rc = devbuf_reserve(ctx, h->pending, h->pending.len + n);
+    int rc = h->pending.push(ctx, interleaved, S, false);
     if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(h->pending.p + h->pending.len, interleaved, n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(put)");
-    h->pending.len += n;
-    const size_t T = h->pending.len / h->ch;
+    const size_t start = h->out.total * (size_t)h->hop;     // first sample of the next frame
+    const size_t T = h->pending.total - start;
     const size_t F = nae_spectrum_frames_ex(T, h->n_fft, h->hop);
     if (F == 0) return NAE_OK;
-    const size_t rec = (size_t)h->ch * (size_t)(h->n_fft / 2 + 1);
-    // compact what has been read (into the other buffer of the pair), then append the new frames
-    if (h->out_read) {
-        const size_t keep = (h->out_frames - h->out_read) * rec;
-        if (keep) {
-            h->out_alt.len = 0;
-            rc = devbuf_reserve(ctx, h->out_alt, keep + F * rec);
-            if (rc) return rc;
-            e = hipMemcpyAsync(h->out_alt.p, h->out.p + h->out_read * rec, keep * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
-            if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(compact)");
-            std::swap(h->out, h->out_alt);
-        }
-        h->out.len = keep;
-        h->out_frames -= h->out_read;
-        h->out_read = 0;
-    }
-    rc = devbuf_reserve(ctx, h->out, h->out.len + F * rec);
+    if ((rc = h->out.reserve(ctx, h->out.total + F))) return rc;
+    const nae_sig src{h->pending.at(start), 0, 1, (size_t)h->ch};
+    rc = nae_spectrum_block_ex_f32(ctx, h->n_fft, h->hop, &src, T, h->ch, 1, h->out.at(h->out.total), 0);
     if (rc) return rc;
-    nae_sig src{h->pending.p, 0, 1, (size_t)h->ch};
-    rc = nae_spectrum_block_ex_f32(ctx, h->n_fft, h->hop, &src, T, h->ch, 1, h->out.p + h->out.len, 0);
-    if (rc) return rc;
-    h->out.len += F * rec;
-    h->out_frames += F;
-    // keep the samples the next frame still needs: everything from F*hop on
-    const size_t drop = F * (size_t)h->hop * h->ch;
-    const size_t tail = h->pending.len - drop;
-    h->pending_alt.len = 0;
-    rc = devbuf_reserve(ctx, h->pending_alt, tail ? tail : 1);
-    if (rc) return rc;
-    if (tail) {
-        e = hipMemcpyAsync(h->pending_alt.p, h->pending.p + drop, tail * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(tail)");
-    }
-    std::swap(h->pending, h->pending_alt);
-    h->pending.len = tail;
+    h->out.total += F;
+    // keep the samples the next frame still needs: everything from its start on
+    h->pending.drop((long long)(h->out.total * (size_t)h->hop));
     return NAE_OK;
 }
 
-size_t nae_spectrum_available(nae_spectrum* h) { return h ? h->out_frames - h->out_read : 0; }
+size_t nae_spectrum_available(nae_spectrum* h) { return h ? h->out.total - h->out_read : 0; }
 
 int nae_spectrum_receive(nae_spectrum* h, float* dst, size_t max_frames, size_t* got)
 {
     if (!h || !got || (max_frames && !dst)) return NAE_ERR_INVALID;
     (void)nae_use_device(h->ctx);
-    size_t n = h->out_frames - h->out_read;
+    size_t n = h->out.total - h->out_read;
     if (n > max_frames) n = max_frames;
     *got = n;
     if (n == 0) return NAE_OK;
-    const size_t rec = (size_t)h->ch * (size_t)(h->n_fft / 2 + 1);
-    hipError_t e = hipMemcpyAsync(dst, h->out.p + h->out_read * rec, n * rec * sizeof(float), hipMemcpyDeviceToDevice, h->ctx->stream);
-    if (e != hipSuccess) return nae_check(h->ctx, e, "hipMemcpyAsync(receive)");
+    const int rc = h->out.pop(h->ctx, h->out_read, dst, n, false);
+    if (rc) return rc;
     h->out_read += n;
     return NAE_OK;
 }
@@ -496,10 +383,8 @@ int nae_spectrum_destroy(nae_spectrum* h)
     if (!h) return NAE_OK;
     (void)nae_use_device(h->ctx);
     (void)hipStreamSynchronize(h->ctx->stream);
-    devbuf_free(h->pending);
-    devbuf_free(h->pending_alt);
-    devbuf_free(h->out);
-    devbuf_free(h->out_alt);
+    h->pending.free();
+    h->out.free();
     delete h;
     return NAE_OK;
 }

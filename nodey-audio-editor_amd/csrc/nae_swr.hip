@@ -193,10 +193,8 @@ struct nae_swr {
     bool identity;
     SwrPlan pl{};
     float* d_bank = nullptr;
-    DevFifo in;                // interleaved stereo f32 frames [in.base, n_in)
-    size_t n_in = 0;
-    DevFifo out;               // interleaved stereo f32 frames [out.base, n_out)
-    size_t n_out = 0, n_read = 0;
+    DevFifo in, out;           // interleaved stereo f32 frames
+    size_t n_read = 0;
     DevBuf raw, f32, planes;   // staging of one convert call
     bool flushed = false;
 };
@@ -205,34 +203,33 @@ static int swr_run(nae_swr* h)
 {
     nae_ctx* ctx = h->ctx;
     const SwrPlan& p = h->pl;
-    const size_t refl = h->flushed ? swr_reflection(p, h->n_in) : 0;
-    const size_t n_avail = h->n_in ? swr_outputs_upto(p, h->n_in + refl) : 0;
-    if (n_avail <= h->n_out) return NAE_OK;
-    const size_t count = n_avail - h->n_out;
+    DevFifo &in = h->in, &out = h->out;
+    const size_t refl = h->flushed ? swr_reflection(p, in.total) : 0;
+    const size_t n_avail = in.total ? swr_outputs_upto(p, in.total + refl) : 0;
+    if (n_avail <= out.total) return NAE_OK;
+    const size_t count = n_avail - out.total;
     if (count > 0x3fffffff) return nae_fail(ctx, NAE_ERR_INVALID, "too many output frames in one call");
-    int rc = fifo_reserve_interleaved(ctx, h->out, h->n_out, n_avail, 2);
+    int rc = out.reserve(ctx, n_avail);
     if (rc) return rc;
     SwrKernelArgs a;
-    a.in = h->in.cur.p; a.in_base = (long long)h->in.base; a.n_in = (long long)h->n_in; a.refl = (int)refl;
+    a.in = in.p; a.in_base = (long long)in.base; a.n_in = (long long)in.total; a.refl = (int)refl;
     a.L = p.L; a.alloc = p.alloc; a.P = p.P; a.src_incr = p.src_incr; a.div = p.div; a.mod = p.mod;
     long long s; int ph;
-    swr_position(p, h->n_out, &s, &ph, &a.pos0, &a.frac0);
+    swr_position(p, out.total, &s, &ph, &a.pos0, &a.frac0);
     a.bank = h->d_bank;
     a.count = (int)count;
-    a.out = h->out.cur.p + (h->n_out - h->out.base) * 2;
+    a.out = out.at(out.total);
     a.span_cap = (int)((double)kSwrTile * p.in_rate / p.out_rate) + p.L + 4;
     const unsigned grid = (unsigned)((count + kSwrTile - 1) / kSwrTile);
     NAE_KLAUNCH(ctx, "swr_resample_kernel", swr_resample_kernel, dim3(grid), dim3(kSwrTile), (size_t)a.span_cap * sizeof(float2), ctx->stream, a);
     rc = nae_check(ctx, hipGetLastError(), "swr_resample_kernel");
     if (rc) return rc;
-    h->n_out = n_avail;
-    h->out.cur.len = (h->n_out - h->out.base) * 2;
-    // input in front of the next window is no longer needed — except the first L frames while a window can still start
-    // in front of sample 0 (reflection), and never the tail the flush reflects
-    if (!h->flushed) {
-        swr_position(p, h->n_out, &s, &ph);
-        if (s > (long long)h->in.base + (1 << 16)) return fifo_drop_interleaved(ctx, h->in, (size_t)s, h->n_in, 2);
-    }
+    out.total = n_avail;
+    // input in front of the next window is no longer needed (a window that starts in front of sample 0 reflects about
+    // it, and s < 0 then drops nothing) — but never the tail the flush reflects
+    if (h->flushed) return NAE_OK;
+    swr_position(p, out.total, &s, &ph);
+    in.drop(s);
     return NAE_OK;
 }
 
@@ -253,6 +250,7 @@ int nae_swr_create(nae_ctx* ctx, int in_fmt, int in_rate, int in_channels, int o
     if (!s) return NAE_ERR_NOMEM;
     s->ctx = ctx; s->in_fmt = in_fmt; s->in_rate = in_rate; s->in_ch = in_channels; s->out_rate = out_rate;
     s->identity = in_rate == out_rate;
+    s->in.width = s->out.width = 2;
     if (!s->identity) {
         int rc = swr_plan_make(in_rate, out_rate, &s->pl);
         if (rc) { delete s; return nae_fail(ctx, rc, "sample-rate ratio outside the supported range (at most ~15x down, reducible to 30-bit increments)"); }
@@ -266,7 +264,7 @@ int nae_swr_create(nae_ctx* ctx, int in_fmt, int in_rate, int in_channels, int o
     return NAE_OK;
 }
 
-size_t nae_swr_buffered(nae_swr* h) { return h ? h->n_out - h->n_read : 0; }
+size_t nae_swr_buffered(nae_swr* h) { return h ? h->out.total - h->n_read : 0; }
 
 /* upload + format conversion of one call's input, appended to the input FIFO (or, equal rates, straight to the output
  * FIFO: a wire); queued on the stream, nothing waited for */
@@ -289,10 +287,9 @@ static int swr_feed(nae_swr* h, const void* const* planes, size_t n_in)
         if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(swr in)");
     }
     // format -> f32 (K6 scaling), mono -> stereo (L = R = m / sqrt(2), swr's default float rematrix)
-    DevFifo& dstf = h->identity ? h->out : h->in;
-    size_t& total = h->identity ? h->n_out : h->n_in;
-    if ((rc = fifo_reserve_interleaved(ctx, dstf, total, total + n_in, 2))) return rc;
-    float* tail = dstf.cur.p + (total - dstf.base) * 2;
+    DevFifo& dst = h->identity ? h->out : h->in;
+    if ((rc = dst.reserve(ctx, dst.total + n_in))) return rc;
+    float* tail = dst.at(dst.total);
     if (h->in_ch == 2) {
         if ((rc = nae_to_f32_interleaved(ctx, h->in_fmt, dp, n_in, 2, tail))) return rc;
     } else {
@@ -300,8 +297,7 @@ static int swr_feed(nae_swr* h, const void* const* planes, size_t n_in)
         if ((rc = nae_to_f32_interleaved(ctx, h->in_fmt, dp, n_in, 1, h->f32.p))) return rc;
         if ((rc = nae_mono_to_stereo_f32(ctx, h->f32.p, tail, n_in, 0.70710678118654752440f))) return rc;
     }
-    total += n_in;
-    dstf.cur.len = (total - dstf.base) * 2;
+    dst.total += n_in;
     return NAE_OK;
 }
 
@@ -309,15 +305,15 @@ static int swr_feed(nae_swr* h, const void* const* planes, size_t n_in)
 static int swr_emit(nae_swr* h, float* dL, float* dR, size_t max_out, size_t* n_out)
 {
     nae_ctx* ctx = h->ctx;
-    size_t n = h->n_out - h->n_read;
+    size_t n = h->out.total - h->n_read;
     if (n > max_out) n = max_out;
     *n_out = n;
     if (n == 0) return NAE_OK;
     float* planes_out[2] = {dL, dR};
-    int rc = nae_deinterleave_f32(ctx, h->out.cur.p + (h->n_read - h->out.base) * 2, planes_out, n, 2);
+    int rc = nae_deinterleave_f32(ctx, h->out.at(h->n_read), planes_out, n, 2);
     if (rc) return rc;
     h->n_read += n;
-    if (h->n_read - h->out.base > (1u << 16)) return fifo_drop_interleaved(ctx, h->out, h->n_read, h->n_out, 2);
+    h->out.drop((long long)h->n_read);
     return NAE_OK;
 }
 
@@ -342,7 +338,7 @@ int nae_swr_convert_host(nae_swr* h, const void* const* planes, size_t n_in, flo
     *n_out = 0;
     int rc;
     if ((rc = swr_convert_common(h, planes, n_in))) return rc;
-    size_t n = h->n_out - h->n_read;
+    size_t n = h->out.total - h->n_read;
     if (n > max_out) n = max_out;
     if (n == 0) {
         // the caller may reuse its planes
@@ -375,8 +371,8 @@ int nae_swr_destroy(nae_swr* h)
     if (!h) return NAE_OK;
     (void)nae_use_device(h->ctx);
     (void)hipStreamSynchronize(h->ctx->stream);
-    fifo_free(h->in);
-    fifo_free(h->out);
+    h->in.free();
+    h->out.free();
     devbuf_free(h->raw); devbuf_free(h->f32); devbuf_free(h->planes);
     if (h->d_bank) (void)hipFree(h->d_bank);
     delete h;

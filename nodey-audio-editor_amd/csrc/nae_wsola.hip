@@ -3,6 +3,7 @@
 //
 // Replaces soundtouch::SoundTouch as used by /root/reference/src/processor/audio-velocity.cpp:369-428.
 #include "st_chain.h"
+#include "stream_util.h"
 #include <math.h>
 #include <new>
 #include <string.h>
@@ -365,73 +366,12 @@ int nae_wsola_block_f32(nae_ctx* ctx, int sample_rate, double rate, double pitch
     return rc;
 }
 
+} // extern "C"
 
 // ------------------------------------------------------------------ streaming handle
 // SoundTouch-shaped calls (audio-velocity.cpp:403 putSamples, :399 numSamples, :298 receiveSamples, :427 flush) on
 // one stream.  Every put advances the scalar bookkeeping, then each stage is launched once for the index range
 // that became computable; the FIFOs between the stages are addressed by absolute frame index.
-} // extern "C"
-
-namespace {
-
-struct AbsFifo {                 // frames [base, total) live at p[(i - base) * w]
-    float* p = nullptr;
-    size_t cap = 0;              // frames
-    long long base = 0, total = 0;
-    int w = 1;
-};
-
-int absfifo_reserve(nae_ctx* ctx, AbsFifo& f, long long want_total)
-{
-    if (want_total - f.base <= (long long)f.cap) return NAE_OK;
-    size_t cap = f.cap ? f.cap : 8192;
-    while ((long long)cap < want_total - f.base) cap *= 2;
-    float* np = nullptr;
-    if (hipMalloc((void**)&np, cap * (size_t)f.w * sizeof(float)) != hipSuccess) return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(stream FIFO)");
-    const long long live = f.total - f.base;
-    if (live > 0) {
-        hipError_t e = hipMemcpyAsync(np, f.p, (size_t)live * (size_t)f.w * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) { (void)hipFree(np); return nae_check(ctx, e, "hipMemcpyAsync(FIFO grow)"); }
-    }
-    if (f.p) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(f.p);
-    }
-    f.p = np;
-    f.cap = cap;
-    return NAE_OK;
-}
-
-// forget frames below new_base; the live part moves to the front once the dead prefix is at least as long (the two
-// regions of the copy then do not overlap)
-int absfifo_drop(nae_ctx* ctx, AbsFifo& f, long long new_base)
-{
-    if (new_base > f.total) new_base = f.total;
-    if (new_base <= f.base) return NAE_OK;
-    const long long dead = new_base - f.base, live = f.total - new_base;
-    if (live == 0) {
-        f.base = new_base;
-        return NAE_OK;
-    }
-    if (dead < live) return NAE_OK;      // not yet worth it (and not safe in place)
-    hipError_t e = hipMemcpyAsync(f.p, f.p + (size_t)dead * (size_t)f.w, (size_t)live * (size_t)f.w * sizeof(float),
-                                  hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(FIFO compact)");
-    f.base = new_base;
-    return NAE_OK;
-}
-
-void absfifo_free(AbsFifo& f)
-{
-    if (f.p) (void)hipFree(f.p);
-    f = AbsFifo{};
-}
-
-StView view_of(const AbsFifo& f, long long valid_end) { return StView{f.p, 0, 1, (long long)f.w, f.base, valid_end}; }
-StOut out_of(const AbsFifo& f) { return StOut{f.p, 0, 1, (long long)f.w, f.base}; }
-
-} // namespace
-
 struct nae_wsola {
     nae_ctx* ctx = nullptr;
     StCfg cfg;
@@ -439,9 +379,8 @@ struct nae_wsola {
     long long* d_pos = nullptr;
     float* d_fract = nullptr;
     size_t tab_cap = 0;
-    AbsFifo in, a, b, out;       // input, stage 1 -> 2, stage 2 -> 3, result
+    DevFifo in, a, b, out;       // input (frames really put: flush zeros are virtual), stage 1 -> 2, stage 2 -> 3, result
     float* d_mid = nullptr;      // stretcher tail carried between calls
-    long long in_real = 0;       // frames really put (flush zeros are virtual)
     long long received = 0;
     long long out_limit = -1;    // total frames that may ever be handed out once flushed
     bool flushed = false;
@@ -473,21 +412,20 @@ int wsola_run(nae_wsola* h, const StState& before)
         rc = st_launch_cu_table(ctx, before.cu_pos, before.cu_fract, c.rate, cu_new, h->d_pos, h->d_fract);
         if (rc) return rc;
     }
-    AbsFifo* chain[4] = {&h->in, &h->a, &h->b, &h->out};
+    DevFifo* chain[4] = {&h->in, &h->a, &h->b, &h->out};
     const int kinds[3][3] = {{0, 1, 2}, {1, 2, 0}, {2, 1, 0}};   // 0 TD, 1 AA, 2 CU per stage slot
-    long long in_valid[3];
-    in_valid[0] = h->in_real;
     for (int slot = 0; slot < 3; slot++) {
         const int kind = kinds[c.order][slot];
-        AbsFifo& src = *chain[slot];
-        AbsFifo& dst = *chain[slot + 1];
+        DevFifo& src = *chain[slot];
+        DevFifo& dst = *chain[slot + 1];
         const long long out_before = kind == 0 ? before.td_out : (kind == 1 ? before.aa_out : before.cu_out);
         const long long out_now = kind == 0 ? now.td_out : (kind == 1 ? now.aa_out : now.cu_out);
         if (out_now > out_before) {
-            rc = absfifo_reserve(ctx, dst, out_now);
+            rc = dst.reserve(ctx, (size_t)out_now);
             if (rc) return rc;
-            const StView vin = view_of(src, in_valid[slot]);
-            const StOut vout = out_of(dst);
+            const long long w = (long long)src.width;
+            const StView vin{src.p, 0, 1, w, (long long)src.base, (long long)src.total};
+            const StOut vout{dst.p, 0, 1, w, (long long)dst.base};
             if (kind == 0) {
                 const TdRange r{before.td_ip, before.td_out, now.td_nseq - before.td_nseq, before.td_skip, before.td_begin ? 1 : 0,
                                 out_now};
@@ -498,13 +436,11 @@ int wsola_run(nae_wsola* h, const StState& before)
                 rc = st_launch_cu(ctx, c, vin, h->d_pos, h->d_fract, before.cu_out, out_before, out_now, vout, 1);
             }
             if (rc) return rc;
-            dst.total = out_now;
+            dst.total = (size_t)out_now;
         }
-        if (slot < 2) in_valid[slot + 1] = dst.total;
         // what this stage will never read again
         const long long keep_from = kind == 0 ? now.td_ip : (kind == 1 ? now.aa_out : now.cu_pos);
-        rc = absfifo_drop(ctx, src, keep_from);
-        if (rc) return rc;
+        src.drop(keep_from);
     }
     return NAE_OK;
 }
@@ -527,7 +463,7 @@ int nae_wsola_create(nae_ctx* ctx, int sample_rate, int channels, double rate, d
         return nae_fail(ctx, rc, rc == NAE_ERR_UNSUPPORTED ? "nae_wsola_create: sample rate outside 8000..48000 Hz or ratio out of range"
                                                            : "nae_wsola_create: bad parameters");
     }
-    h->in.w = h->a.w = h->b.w = h->out.w = channels;
+    h->in.width = h->a.width = h->b.width = h->out.width = (size_t)channels;
     if (hipMalloc((void**)&h->d_mid, (size_t)h->cfg.ovl * (size_t)channels * sizeof(float)) != hipSuccess) {
         delete h;
         return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(stretcher tail)");
@@ -544,18 +480,8 @@ static int wsola_append(nae_wsola* h, const float* p, size_t S, bool host)
     if (h->flushed) return nae_fail(ctx, NAE_ERR_STATE, "nae_wsola_put after flush");
     if (S == 0) return NAE_OK;
     if (!p) return nae_fail(ctx, NAE_ERR_INVALID, "nae_wsola_put: null samples");
-    int rc = absfifo_reserve(ctx, h->in, h->in.total + (long long)S);
+    const int rc = h->in.push(ctx, p, S, host);
     if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(h->in.p + (size_t)(h->in.total - h->in.base) * (size_t)h->in.w, p, S * (size_t)h->in.w * sizeof(float),
-                                  host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(put)");
-    if (host) {
-        // the caller may reuse its buffer as soon as the call returns (with pinned memory the copy is truly asynchronous)
-        e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return nae_check(ctx, e, "hipStreamSynchronize(put)");
-    }
-    h->in.total += (long long)S;
-    h->in_real = h->in.total;
     const StState before = h->st;
     st_sim_put(h->cfg, h->st, (long long)S, nullptr);
     return wsola_run(h, before);
@@ -581,7 +507,7 @@ int nae_wsola_flush(nae_wsola* h)
 size_t nae_wsola_available(const nae_wsola* h)
 {
     if (!h) return 0;
-    long long total = h->out.total;
+    long long total = (long long)h->out.total;
     if (h->out_limit >= 0 && total > h->out_limit) total = h->out_limit;
     return total > h->received ? (size_t)(total - h->received) : 0;
 }
@@ -596,15 +522,10 @@ static int wsola_take(nae_wsola* h, float* dst, size_t max_frames, size_t* got, 
     if (got) *got = n;
     if (n == 0) return NAE_OK;
     if (!dst) return nae_fail(ctx, NAE_ERR_INVALID, "nae_wsola_receive: null destination");
-    hipError_t e = hipMemcpyAsync(dst, h->out.p + (size_t)(h->received - h->out.base) * (size_t)h->out.w, n * (size_t)h->out.w * sizeof(float),
-                                  host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(receive)");
-    if (host) {
-        e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return nae_check(ctx, e, "hipStreamSynchronize");
-    }
+    const int rc = h->out.pop(ctx, (size_t)h->received, dst, n, host);
+    if (rc) return rc;
     h->received += (long long)n;
-    return absfifo_drop(ctx, h->out, h->received);
+    return NAE_OK;
 }
 
 int nae_wsola_receive(nae_wsola* h, float* dst, size_t max_frames, size_t* got) { return wsola_take(h, dst, max_frames, got, false); }
@@ -615,10 +536,10 @@ int nae_wsola_destroy(nae_wsola* h)
     if (!h) return NAE_OK;
     if (h->ctx) (void)nae_use_device(h->ctx);
     if (h->ctx && h->ctx->stream) (void)hipStreamSynchronize(h->ctx->stream);
-    absfifo_free(h->in);
-    absfifo_free(h->a);
-    absfifo_free(h->b);
-    absfifo_free(h->out);
+    h->in.free();
+    h->a.free();
+    h->b.free();
+    h->out.free();
     if (h->d_mid) (void)hipFree(h->d_mid);
     if (h->d_pos) (void)hipFree(h->d_pos);
     if (h->d_fract) (void)hipFree(h->d_fract);

@@ -1,0 +1,151 @@
+"""Long streams through every streaming handle (nae_stretch, nae_wsola, nae_swr, nae_spectrum): 300 000+ frames in an
+uneven cycle of put sizes, with receives that take everything, part of what is available or nothing.  Every device FIFO
+of the handles grows several times and is compacted many times; the output equals the block call or the oracle bit for
+bit."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import orc
+import pv_ref
+from pv_gpu import block, same_bits
+from test_gpu_spectrum_sizes import bins, gpu_ex
+
+pytestmark = pytest.mark.gpu
+
+L = 400_000
+PUTS = [1, 37, 1152, 4096, 20000, 1, 37, 1152, 4096, 20000, 90001]
+
+
+def f32(v):
+    return float(np.float32(v))
+
+
+def schedule(L, put_sizes=PUTS):
+    """(first frame, frames) of every put, and how much of what is available the receive after it takes"""
+    pos, i = 0, 0
+    while pos < L:
+        n = min(put_sizes[i % len(put_sizes)], L - pos)
+        yield pos, n, (None, 0.5, None, 1.0)[i % 4]       # nothing, about half, nothing, everything
+        pos += n
+        i += 1
+
+
+def part(avail, share):
+    return 0 if share is None else (avail if share == 1.0 else avail // 2 + 1 if avail else 0)
+
+
+def drive(lib, h, prefix, x, ch):
+    """put_host / available / receive_host / flush / receive everything of a nae_stretch or nae_wsola handle"""
+    put, available, receive = (getattr(lib, f"nae_{prefix}_{f}") for f in ("put_host", "available", "receive_host"))
+    outs, got = [], C.c_size_t()
+
+    def take(n):
+        if n:
+            buf = np.empty(n * ch, np.float32)
+            assert receive(h, buf.ctypes.data, n, C.byref(got)) == 0
+            assert got.value == n
+            outs.append(buf)
+
+    for pos, n, share in schedule(x.size // ch):
+        chunk = np.ascontiguousarray(x[pos * ch:(pos + n) * ch])
+        assert put(h, chunk.ctypes.data, n) == 0
+        take(part(available(h), share))
+    assert getattr(lib, f"nae_{prefix}_flush")(h) == 0
+    assert put(h, x.ctypes.data, 1) == -5                              # NAE_ERR_STATE: put after flush
+    take(available(h))
+    assert available(h) == 0
+    assert getattr(lib, f"nae_{prefix}_destroy")(h) == 0
+    return np.concatenate(outs)
+
+
+@pytest.mark.parametrize("rate,pitch,flags,lifter", [
+    (1.0, 1.0, 0, False),                        # wire
+    (1.5, f32(1 / 1.5), 0, False),               # vocoder only
+    (f32(0.8), 1.0, 0, False),                   # transposer only
+    (1.0, f32(2 ** (3 / 12)), 0, False),         # transposer, then vocoder
+    (1.0, f32(2 ** (-4 / 12)), 0, False),        # vocoder, then transposer (planar mid FIFO)
+    (1.0, f32(2 ** (-4 / 12)), 1, False),        # phase-locked
+    (1.0, f32(2 ** (4 / 12)), 0, True),          # formant-preserving
+])
+def test_stretch_long_stream_equals_block(ctx, nae, rate, pitch, flags, lifter):
+    ch, n_fft = 2, 1024
+    x = (0.5 * orc.fill_uniform(L * ch, 23)).astype(np.float32)
+    q = pv_ref.default_lifter(48000, n_fft) if lifter else 0
+    h = C.c_void_p()
+    assert ctx.lib.nae_stretch_create_formant(ctx.h, 48000, ch, rate, pitch, flags, n_fft, q, C.byref(h)) == 0
+    y = drive(ctx.lib, h, "stretch", x, ch)
+    want = block(ctx, nae, x, ch, rate, pitch, n_fft, lock=bool(flags), lifter=q)
+    assert y.size == want.size
+    assert same_bits(y, want)
+
+
+@pytest.mark.parametrize("ch,rate,pitch", [(2, 1.0, 2 ** (3 / 12)), (2, 1.0, 2 ** (-4 / 12)), (1, 1.5, 1 / 1.5)])
+def test_wsola_long_stream_equals_oracle(ctx, nae, ch, rate, pitch):
+    x = orc.fill_uniform(L * ch, 29)
+    h = C.c_void_p()
+    assert ctx.lib.nae_wsola_create(ctx.h, 48000, ch, rate, pitch, C.byref(h)) == 0
+    y = drive(ctx.lib, h, "wsola", x, ch)
+    want = orc.st_process(x, ch, 48000, rate, pitch, chunk=PUTS)
+    assert y.size == want.size
+    assert same_bits(y, want)
+
+
+@pytest.mark.parametrize("fmt_name,ch", [("FLT", 2), ("S16", 1)])
+def test_swr_long_stream_equals_oracle(ctx, nae, fmt_name, ch):
+    """44.1 -> 48 kHz; the references are built as tests/test_gpu_nodes.py builds them"""
+    lib = ctx.lib
+    if fmt_name == "FLT":
+        m = orc.fill_uniform(L, 31)
+        x = np.stack([m, -m], 1).reshape(-1).astype(np.float32)
+        want_L, want_R = orc.swr_resample(m, 44100, 48000), orc.swr_resample(-m, 44100, 48000)
+    else:
+        x = (orc.fill_uniform(L, 31) * 30000).astype(np.int16)
+        rc, f = orc.to_f32_interleaved(orc.FMT_S16, [x], L, 1)
+        want_L = want_R = orc.swr_resample((f * np.float32(0.70710678118654752440)).astype(np.float32), 44100, 48000)
+    h, got = C.c_void_p(), C.c_size_t()
+    assert lib.nae_swr_create(ctx.h, getattr(nae, "FMT_" + fmt_name), 44100, ch, 48000, C.byref(h)) == 0
+    outL, outR = [], []
+
+    def convert(planes, n, max_out):
+        bl, br = np.zeros(max(max_out, 1), np.float32), np.zeros(max(max_out, 1), np.float32)
+        assert lib.nae_swr_convert_host(h, planes, n, bl.ctypes.data, br.ctypes.data, max_out, C.byref(got)) == 0
+        outL.append(bl[: got.value]); outR.append(br[: got.value])
+        return got.value
+
+    for pos, n, share in schedule(L):
+        chunk = np.ascontiguousarray(x[pos * ch:(pos + n) * ch])
+        convert((C.c_void_p * 1)(chunk.ctypes.data), n, part(lib.nae_swr_buffered(h) + n, share))
+    while convert(None, 0, 50000):
+        pass
+    assert lib.nae_swr_buffered(h) == 0
+    assert lib.nae_swr_destroy(h) == 0
+    assert same_bits(np.concatenate(outL), want_L)
+    assert same_bits(np.concatenate(outR), want_R)
+
+
+@pytest.mark.parametrize("n_fft,hop", [(1024, 256), (4096, 1000)])
+def test_spectrum_long_stream_equals_block(ctx, nae, n_fft, hop):
+    lib, ch, B = ctx.lib, 2, bins(n_fft)
+    x = orc.fill_uniform(L * ch, 37)
+    want = gpu_ex(ctx, nae, n_fft, hop, x, ch)[0]
+    h, got = C.c_void_p(), C.c_size_t()
+    assert lib.nae_spectrum_create(ctx.h, n_fft, hop, ch, C.byref(h)) == 0
+    d_x, d_o = ctx.array(x), ctx.empty(want.size + ch * B)
+    frames = 0
+    for pos, n, share in schedule(L):
+        assert lib.nae_spectrum_put(h, C.c_void_p(d_x.at(pos * ch)), n) == 0
+        take = part(lib.nae_spectrum_available(h), share)
+        assert lib.nae_spectrum_receive(h, C.c_void_p(d_o.at(frames * ch * B)), take, C.byref(got)) == 0
+        assert got.value == take
+        frames += take
+    rest = lib.nae_spectrum_available(h)
+    assert lib.nae_spectrum_receive(h, C.c_void_p(d_o.at(frames * ch * B)), rest, C.byref(got)) == 0
+    frames += got.value
+    assert lib.nae_spectrum_available(h) == 0
+    assert lib.nae_spectrum_destroy(h) == 0
+    assert frames == want.shape[0]
+    out = d_o.download()[: want.size].reshape(want.shape)
+    d_x.free(); d_o.free()
+    assert same_bits(out, want)
