@@ -19,6 +19,13 @@
 #define NAE_HOP 256             /* synthesis hop / spectrum hop (N/4)      */
 #define NAE_OLA_GAIN (2.0f / 3.0f) /* 1 / sum_t hann^2 at hop N/4 = 1/1.5  */
 #define NAE_FORMANT_MAX_GAIN 16.0f /* formant preservation: largest envelope gain of a bin ("Formant preservation") */
+/* transient preservation ("Transient preservation"): bin k of frame f rises iff P_f[k] > RISE * P_{f-1}[k] and
+ * P_f[k] > FLOOR * N; frame f is "high" iff DEN * (rising bins) >= NUM * (N/2 + 1); an onset is an upward crossing of "high" at f >= 2.
+ * RISE is +6 dB: at +3 dB steady white noise crosses 3/8 at N = 512 and 1024 (DESIGN.md gives the numbers). */
+#define NAE_TRANSIENT_RISE 4.0f
+#define NAE_TRANSIENT_FLOOR 0x1p-20f
+#define NAE_TRANSIENT_NUM 3
+#define NAE_TRANSIENT_DEN 8
 
 /* atan2 -> Q0.32 turns (revision 2 of the K7 / phase specification).  Every step is an IEEE f32 add / mul /
  * fma or a two's-complement integer operation, so C and the GPU give the same 32 bits — and none of them is a division:

@@ -37,7 +37,8 @@ extern "C" {
  *   NAE_STRETCH_PHASE_LOCK with nae_stretch_block_ex_f32, nae_stretch_create_ex and nae_debug_pv_tile_phase_ex (identity phase locking of the
  *   vocoder); nae_stretch_plan_make_n, nae_stretch_block_n_f32, nae_debug_pv_tile_phase_n and nae_stretch_create_n (vocoder frame sizes
  *   512 ... 4096); nae_stretch_formant_lifter, nae_stretch_block_formant_f32 and nae_stretch_create_formant (formant-preserving pitch
- *   shift). */
+ *   shift); NAE_STRETCH_TRANSIENTS with the _n and _formant entries (transient preservation), which a caller probes for by its return code:
+ *   a library without it answers NAE_ERR_INVALID. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -291,6 +292,17 @@ int nae_stretch_block_formant_f32(nae_ctx* ctx, double rate, double pitch, unsig
                                   const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst);
 int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags,
                                int n_fft, int lifter, nae_stretch** h);
+
+/* NAE_STRETCH_TRANSIENTS: transient preservation ("Transient preservation"), a flag of the _n and _formant entries
+ * (nae_stretch_block_n_f32, nae_stretch_create_n, nae_debug_pv_tile_phase_n, nae_stretch_block_formant_f32, nae_stretch_create_formant) at
+ * every n_fft.  Frame f >= 2 is an onset when the number of bins whose power rises more than NAE_TRANSIENT_RISE times (+6 dB) over frame
+ * f - 1 crosses NAE_TRANSIENT_NUM / NAE_TRANSIENT_DEN of the bins upwards; an onset frame takes its analysis phase as its synthesis phase, so an
+ * attack keeps its shape instead of spreading over the frame.  Other frames, magnitudes, lengths and the transposer are unchanged; a signal
+ * without onsets gives the unflagged call's bits.  It combines with NAE_STRETCH_PHASE_LOCK at 1024 (the locked maps reset too; the lock
+ * at another size stays NAE_ERR_UNSUPPORTED); the _ex entries answer NAE_ERR_INVALID.  Without the vocoder stage (no tempo change) the flag
+ * changes nothing.  Integer phases are bit-exact against the CPU
+ * statement (tests/pv_transient/ref_pv_tr.c) and independent of the tiling; a handle's output equals the block call's. */
+#define NAE_STRETCH_TRANSIENTS 4u
 int nae_stretch_put(nae_stretch* h, const float* interleaved, size_t S);
 int nae_stretch_put_host(nae_stretch* h, const float* interleaved_host, size_t S);
 int nae_stretch_flush(nae_stretch* h);

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
 
 
 STRETCH_PHASE_LOCK = 1       # NAE_STRETCH_PHASE_LOCK (include/nae_gpu.h)
+STRETCH_TRANSIENTS = 4       # NAE_STRETCH_TRANSIENTS (include/nae_gpu.h): the _n and _formant entries only
 
 
 class NaeError(RuntimeError):
@@ -434,13 +435,15 @@ class Context:
         return pl
 
     def stretch_block(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig,
-                      phase_lock: bool = False, n_fft: int = 1024, formant: int = 0):
-        """formant: the lifter of formant preservation (formant_lifter() gives the default), 0 = off"""
+                      phase_lock: bool = False, n_fft: int = 1024, formant: int = 0, transients: bool = False):
+        """formant: the lifter of formant preservation (formant_lifter() gives the default), 0 = off; transients: transient preservation
+        (nae_stretch_block_n_f32 at every size)"""
+        flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0)
         if formant:
-            self._ck(self.lib.nae_stretch_block_formant_f32(self.h, rate, pitch, STRETCH_PHASE_LOCK if phase_lock else 0, n_fft, formant,
+            self._ck(self.lib.nae_stretch_block_formant_f32(self.h, rate, pitch, flags, n_fft, formant,
                                                             C.byref(src), in_len, ch, n_streams, C.byref(dst)))
-        elif n_fft != 1024:
-            self._ck(self.lib.nae_stretch_block_n_f32(self.h, rate, pitch, STRETCH_PHASE_LOCK if phase_lock else 0, n_fft, C.byref(src), in_len,
+        elif n_fft != 1024 or transients:
+            self._ck(self.lib.nae_stretch_block_n_f32(self.h, rate, pitch, flags, n_fft, C.byref(src), in_len,
                                                       ch, n_streams, C.byref(dst)))
         elif phase_lock:
             self._ck(self.lib.nae_stretch_block_ex_f32(self.h, rate, pitch, STRETCH_PHASE_LOCK, C.byref(src), in_len, ch, n_streams,
@@ -449,14 +452,15 @@ class Context:
             self._ck(self.lib.nae_stretch_block_f32(self.h, rate, pitch, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
     def debug_pv_tile_phase(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int,
-                            phase_lock: bool = False, n_fft: int = 1024):
+                            phase_lock: bool = False, n_fft: int = 1024, transients: bool = False):
         pl = self.stretch_plan(rate, pitch, in_len, n_fft)
         bins = n_fft // 2 + 1
         cap = n_streams * ch * (pl.frames + 1) * bins
         out = np.zeros(cap, np.int32)
         nt, tf = C.c_size_t(), C.c_size_t()
-        if n_fft != 1024:
-            self._ck(self.lib.nae_debug_pv_tile_phase_n(self.h, rate, pitch, STRETCH_PHASE_LOCK if phase_lock else 0, n_fft, C.byref(src), in_len,
+        if n_fft != 1024 or transients:
+            flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0)
+            self._ck(self.lib.nae_debug_pv_tile_phase_n(self.h, rate, pitch, flags, n_fft, C.byref(src), in_len,
                                                         ch, n_streams, out.ctypes.data, cap, C.byref(nt), C.byref(tf)))
             return out[: n_streams * ch * nt.value * bins].reshape(n_streams, ch, nt.value, bins), tf.value
         if phase_lock:
@@ -515,12 +519,12 @@ class Stretcher:
     nae_stretch_create_formant with a formant lifter): put interleaved f32, flush, receive."""
 
     def __init__(self, ctx: Context, sample_rate: int, channels: int, rate: float, pitch: float, phase_lock: bool = False,
-                 n_fft: int = 1024, formant: int = 0):
+                 n_fft: int = 1024, formant: int = 0, transients: bool = False):
         self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
-        flags = STRETCH_PHASE_LOCK if phase_lock else 0
+        flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0)
         if formant:
             ctx._ck(ctx.lib.nae_stretch_create_formant(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, formant, C.byref(self.h)))
-        elif n_fft != 1024:
+        elif n_fft != 1024 or transients:
             ctx._ck(ctx.lib.nae_stretch_create_n(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, C.byref(self.h)))
         else:
             ctx._ck(ctx.lib.nae_stretch_create_ex(ctx.h, sample_rate, channels, rate, pitch, flags, C.byref(self.h)))

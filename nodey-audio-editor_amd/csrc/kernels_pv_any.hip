@@ -13,7 +13,10 @@
 // tile's sum or (pass 3) Qs, [r][lane] for bin lane + 64 r, and in pass 3 the synthesis spectrum (B = N/2 + 1 complex, padded) live in LDS; the
 // three open overlap-add blocks of pass 3 in registers.  (Phases in registers, 2 x (M/64 + 1) per lane, with the bin loop unrolled, spill from
 // N = 2048 on.)
-// N = 1024 runs the shipped passes 1 and 3 unless the debug key pv_any (or, pass 3, a lifter) asks for these: nae_pv_route_of.  The host
+// kTransient (NAE_STRETCH_TRANSIENTS; DESIGN.md §3, "Transient preservation"): passes 1 and 3 also keep P_{f-1} (ST floats per wave) in LDS,
+// count the rising bins of each row with a ballot, and at an onset restart the sum / Qs from Qa; pass 1 flags the record in slot B and pass 2 is
+// the segmented scan.  Waves per workgroup: pass 1 8 / 8 / 7 / 3 at N = 512 ... 4096, pass 3 8 / 8 / 5 / 2 (with formants 8 / 8 / 4 / 2).
+// N = 1024 runs the shipped passes 1 and 3 unless the debug key pv_any (or, pass 3, a lifter; or transients) asks for these: nae_pv_route_of.  The host
 // decisions (records needed, base records, synthesis fields, workspace) are kernels_stft.hip's nae_launch_pv_phase / nae_launch_pv_synth.
 #include "pv_roles.h"
 #include "fft_any.h"
@@ -21,7 +24,7 @@
 
 namespace nae {
 
-template <int N, bool kFormant = false>
+template <int N, bool kFormant = false, bool kTransient = false>
 struct PvAny {
     static constexpr int M = N / 2, H = N / 4, B = M + 1;
     static constexpr int PAD = (B + 7) & ~7;              // int32 per record: 520 at N = 1024, as the shipped kernels
@@ -31,14 +34,17 @@ struct PvAny {
     static constexpr int K = 2 * JQ;                      // samples per lane in each hop block
     using Gm = FftGeom<M, 1>;
     static constexpr int ST = NB * 64;                    // uint32 per per-bin state array of a wave
-    static constexpr size_t kWave1 = Gm::SCR * sizeof(cf) + 2 * ST * sizeof(uint32_t);                    // scratch, Qa_{f-1}, sum
+    static constexpr size_t kWave1 = Gm::SCR * sizeof(cf) + 2 * ST * sizeof(uint32_t)                     // scratch, Qa_{f-1}, sum
+                                   + (kTransient ? ST * sizeof(float) : 0);                                // transients: P_{f-1}
     static constexpr size_t kWave3 = Gm::SCR * sizeof(cf) + PAD * sizeof(cf) + 2 * ST * sizeof(uint32_t) // scratch, Y, Qa_{f-1}, Qs
-                                   + (kFormant ? PAD * sizeof(float) : 0);                                 // formant: L / c' / Ls
+                                   + (kFormant ? PAD * sizeof(float) : 0)                                  // formant: L / c' / Ls
+                                   + (kTransient ? ST * sizeof(float) : 0);                                // transients: P_{f-1}
     static constexpr int kMaxWaves1 = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave1);
     static constexpr int kMaxWaves3 = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave3);
-    static constexpr int kWaves1 = kMaxWaves1 < 8 ? kMaxWaves1 : 8;   // 8, 8, 8, 4 waves per workgroup at N = 512 ... 4096
-    static constexpr int kWaves3 = kMaxWaves3 < 8 ? kMaxWaves3 : 8;   // 8, 8, 6, 3 (formant: 8, 8, 5, 2)
-    // pass-3 waves a CU holds: whole workgroups by LDS (16, 8, 6, 3 at N = 512 ... 4096, formant 16, 8, 5, 2; registers allow as many)
+    static constexpr int kWaves1 = kMaxWaves1 < 8 ? kMaxWaves1 : 8;   // 8, 8, 8, 4 waves per workgroup at N = 512 ... 4096 (transients: 8, 8, 7, 3)
+    static constexpr int kWaves3 = kMaxWaves3 < 8 ? kMaxWaves3 : 8;   // 8, 8, 6, 3 (formant: 8, 8, 5, 2; transients: 8, 8, 5, 2; both: 8, 8, 4, 2)
+    // pass-3 waves a CU holds: whole workgroups by LDS (16, 8, 6, 3 at N = 512 ... 4096, formant 16, 8, 5, 2; registers allow as many; transients
+    // 16, 8, 5, 2; formant and transients 16, 8, 4, 2)
     static constexpr int kResident3 = (int)((160 * 1024) / (512 * sizeof(cf) + kWaves3 * kWave3)) * kWaves3;
     static_assert(N >= 512 && N <= 4096 && (N & (N - 1)) == 0, "vocoder sizes 512 ... 4096");
     static_assert(kWaves1 >= 1 && kWaves3 >= 1, "a wave's state fits a CU's LDS");
@@ -100,17 +106,37 @@ __device__ __forceinline__ uint32_t pva_inc(uint32_t qa, uint32_t qp, unsigned k
     return adv + (uint32_t)scaled;
 }
 
+// transient preservation ("Transient preservation"), rules 1-3 for bin k (k < B) of a row: does P = |X|^2 (two products and an
+// add, never fused) rise over the previous frame's P in pp?  pp takes P.  The wave's count of rising bins of the row is the popcount of the ballot.
+template <int N>
+__device__ __forceinline__ int pva_rises(cf x, int k, float* pp, bool counted)
+{
+    const float P = x.x * x.x + x.y * x.y;
+    const bool rise = counted && k < N / 2 + 1 && P > NAE_TRANSIENT_RISE * *pp && P > NAE_TRANSIENT_FLOOR * (float)N;
+    *pp = P;
+    return __popcll(__ballot(rise));
+}
+
+// rule 4: frame f is an onset iff f >= 2, it is high and the frame before is not (high: DEN * count >= NUM * B)
+template <int N>
+__device__ __forceinline__ bool pva_high(int count)
+{
+    return NAE_TRANSIENT_DEN * count >= NAE_TRANSIENT_NUM * (N / 2 + 1);
+}
+
 // ------------------------------------------------------------------------------------------------ pass 1
-// sums[(sc * n_tiles + tile) * PAD + k]
-template <int N, bool kUnit>
-__global__ __launch_bounds__(64 * PvAny<N>::kWaves1) void pv_any_phase_kernel(SigViewD src, PvParams p, long long n_items,
+// sums[(sc * n_tiles + tile) * PAD + k].  kTransient: an onset frame of the tile restarts the sum at its Qa, and the record's slot B is 1 when the
+// tile holds an onset (the summary (r, S) of DESIGN.md §3); frames f0 - 2 and f0 - 1 prime P and "high"
+template <int N, bool kUnit, bool kTransient = false>
+__global__ __launch_bounds__(64 * (PvAny<N, false, kTransient>::kWaves1)) void pv_any_phase_kernel(SigViewD src, PvParams p, long long n_items,
                                                                              uint32_t* __restrict__ sums, SpecAnyTables tb)
 {
-    using P = PvAny<N>;
+    using P = PvAny<N, false, kTransient>;
     using Gm = typename P::Gm;
     __shared__ __attribute__((aligned(16))) cf w512l[512];
     __shared__ __attribute__((aligned(16))) cf scratch[P::kWaves1 * Gm::SCR];
     __shared__ uint32_t state[P::kWaves1 * 2 * P::ST];
+    __shared__ float pprev[kTransient ? P::kWaves1 * P::ST : 1];   // transients: P_{f-1} of bin lane + 64 r
     for (int i = threadIdx.x; i < 512; i += 64 * P::kWaves1) w512l[i] = tb.w512[i];
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -122,6 +148,7 @@ __global__ __launch_bounds__(64 * PvAny<N>::kWaves1) void pv_any_phase_kernel(Si
     cf* scr = scratch + wave_id() * Gm::SCR;
     uint32_t* qp = state + wave_id() * 2 * P::ST + lane;  // [r * 64]: Qa_{f-1} of bin lane + 64 r
     uint32_t* acc = qp + P::ST;                          //           the tile's sum of increments
+    float* pp = pprev + (kTransient ? wave_id() * P::ST + lane : 0);
     const long long s_idx = sc / p.ch;
     const int c = (int)(sc % p.ch);
     const ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
@@ -131,21 +158,36 @@ __global__ __launch_bounds__(64 * PvAny<N>::kWaves1) void pv_any_phase_kernel(Si
 
     for (int r = 0; r < P::NB; r++) { acc[64 * r] = 0; qp[64 * r] = 0; }
     long long s_prev = 0;
-    // frame f0 - 1 only primes qp (its increment belongs to the previous tile)
+    const long long f_first = kTransient ? (f0 > 2 ? f0 - 2 : 0) : (f0 > 0 ? f0 - 1 : 0);
+    bool high_prev = false;                                // transients: high(f - 1), wave-uniform
+    uint32_t reset = 0;                                    //             an onset in [f0, f1)
+    // frames before f0 only prime qp (their increments belong to the previous tile) and, with transients, P and high
 #pragma unroll 1
-    for (long long f = (f0 > 0 ? f0 - 1 : 0); f < f1; f++) {
+    for (long long f = f_first; f < f1; f++) {
         const long long s = pva_frame_start<N>(p, f);
         pva_analyse<N, kUnit>(scr, w512l, tb, in, s, lane);
         const unsigned d = (unsigned)(s - s_prev);
         const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
+        int rising = 0;
 #pragma unroll 2
         for (int r = 0; r < P::NB; r++) {
             const int k = lane + 64 * r;
             const int kc = k < P::B ? k : P::M;            // lanes past bin M (last row) compute bin M and store nothing
-            const uint32_t qa = pva_phase<N>(any_rfft_bin<Gm>(scr, tb.tn, kc), kc);
+            const cf x = any_rfft_bin<Gm>(scr, tb.tn, kc);
+            const uint32_t qa = pva_phase<N>(x, kc);
             // frame f0 - 1 only primes; the "increment" of frame 0 is its analysis phase
             if (f >= f0) acc[64 * r] = (f == 0) ? qa : acc[64 * r] + pva_inc<N>(qa, qp[64 * r], (unsigned)kc, d, R);
             qp[64 * r] = qa;
+            if constexpr (kTransient) rising += pva_rises<N>(x, k, pp + 64 * r, f > f_first);
+        }
+        if constexpr (kTransient) {
+            const bool high = f > f_first && pva_high<N>(rising);
+            if (f >= f0 && f >= 2 && high && !high_prev) {     // an onset: the sum restarts at Qa_f (wave-uniform)
+#pragma unroll 1
+                for (int r = 0; r < P::NB; r++) acc[64 * r] = qp[64 * r];
+                reset = 1;
+            }
+            high_prev = high;
         }
         wave_lds_sync();                                   // the next frame rewrites the scratch
         s_prev = s;
@@ -155,13 +197,15 @@ __global__ __launch_bounds__(64 * PvAny<N>::kWaves1) void pv_any_phase_kernel(Si
         const int k = lane + 64 * r;
         if (k < P::B) o[k] = acc[64 * r];
     }
+    if (kTransient && lane == 0) o[P::B] = reset;          // slot B of the padding (PAD - B = 7 at every N)
 }
 
 // ------------------------------------------------------------------------------------------------ pass 2
 // the one scan of the unlocked vocoder (after pv_phase_kernel or pv_any_phase_kernel): exclusive prefix over tiles, in place; one thread per
 // (stream-channel, bin).  carry_in (optional): the phase in front of tile 0, [n_sc][PAD]; carry_out (optional): the phase behind the last tile.
-// Records at or beyond n_read count as zero.
-template <int N>
+// Records at or beyond n_read count as zero.  kSeg (transients): the segmented scan — a record whose slot B is set restarts the running value at
+// its own sum, (r1, S1) then (r2, S2) = r2 ? (1, S2) : (r1, S1 + S2); the carried phase does not cross a reset.
+template <int N, bool kSeg = false>
 __global__ void pv_scan_kernel(uint32_t* __restrict__ sums, long long n_sc, int n_tiles, const uint32_t* __restrict__ carry_in,
                                uint32_t* __restrict__ carry_out, int n_read)
 {
@@ -171,37 +215,45 @@ __global__ void pv_scan_kernel(uint32_t* __restrict__ sums, long long n_sc, int 
     const int k = (int)(t % P::PAD);
     if (sc >= n_sc || k >= P::B) return;
     uint32_t* p = sums + sc * n_tiles * (long long)P::PAD + k;
+    const uint32_t* fl = sums + sc * n_tiles * (long long)P::PAD + P::B;   // kSeg: the tiles' reset flags (read only)
     uint32_t run = carry_in ? carry_in[sc * P::PAD + k] : 0u;
     int j = 0;
     // the loads do not depend on the running sum: fetch 8 tiles ahead, then prefix them
     for (; j + 8 <= n_read; j += 8) {
-        uint32_t v[8];
+        uint32_t v[8], r[8];
 #pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = p[(long long)(j + u) * P::PAD];
+        for (int u = 0; u < 8; u++) {
+            v[u] = p[(long long)(j + u) * P::PAD];
+            if constexpr (kSeg) r[u] = fl[(long long)(j + u) * P::PAD];
+        }
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             p[(long long)(j + u) * P::PAD] = run;
-            run += v[u];
+            if constexpr (kSeg) run = r[u] ? v[u] : run + v[u];
+            else run += v[u];
         }
     }
     for (; j < n_tiles; j++) {
         const uint32_t v = (j < n_read) ? p[(long long)j * P::PAD] : 0u;
         p[(long long)j * P::PAD] = run;
-        run += v;
+        if constexpr (kSeg) run = (j < n_read && fl[(long long)j * P::PAD]) ? v : run + v;
+        else run += v;
     }
     if (carry_out) carry_out[sc * P::PAD + k] = run;
 }
 
 // the same for many tiles per stream-channel (a long lone stream: thousands of tiles on a few stream-channels, where one thread per bin walks them
 // one after the other): 16 threads per bin take a sixteenth of the tiles each — sum it, exchange the 16 sums through LDS, prefix the own part
-// (modular integer sums: the split changes no bit).  One workgroup per (stream-channel, 64 bins).
+// (modular integer sums: the split changes no bit).  One workgroup per (stream-channel, 64 bins).  kSeg: the segmented scan, each sixteenth's
+// summary a (reset seen, sum since the last reset) pair.
 constexpr int kScanChunks = 16;
-template <int N>
+template <int N, bool kSeg = false>
 __global__ __launch_bounds__(64 * kScanChunks) void pv_scan_chunked_kernel(uint32_t* __restrict__ sums, long long n_sc, int n_tiles,
                                                                           const uint32_t* __restrict__ carry_in, uint32_t* __restrict__ carry_out, int n_read)
 {
     using P = PvAny<N>;
     __shared__ uint32_t part[kScanChunks][64];
+    __shared__ uint32_t pflag[kSeg ? kScanChunks : 1][64];
     const int kb = threadIdx.x & 63, ck = threadIdx.x >> 6;
     const long long sc = blockIdx.x / P::NB;
     const int k = (int)(blockIdx.x % P::NB) * 64 + kb;
@@ -210,38 +262,60 @@ __global__ __launch_bounds__(64 * kScanChunks) void pv_scan_chunked_kernel(uint3
     const int j0 = ck * per, j1 = (j0 + per < n_tiles) ? j0 + per : n_tiles;
     const int r1 = j1 < n_read ? j1 : n_read;                       // tiles at or beyond n_read count as zero
     uint32_t* p = sums + sc * n_tiles * (long long)P::PAD + (valid ? k : 0);
-    uint32_t sum = 0;
+    const uint32_t* fl = sums + sc * n_tiles * (long long)P::PAD + P::B;   // kSeg: the tiles' reset flags (read only)
+    uint32_t sum = 0, seen = 0;
     if (valid) {
         int j = j0;
         for (; j + 8 <= r1; j += 8) {
-            uint32_t v[8];
+            uint32_t v[8], r[8];
 #pragma unroll
-            for (int u = 0; u < 8; u++) v[u] = p[(long long)(j + u) * P::PAD];
+            for (int u = 0; u < 8; u++) {
+                v[u] = p[(long long)(j + u) * P::PAD];
+                if constexpr (kSeg) r[u] = fl[(long long)(j + u) * P::PAD];
+            }
 #pragma unroll
-            for (int u = 0; u < 8; u++) sum += v[u];
+            for (int u = 0; u < 8; u++) {
+                if constexpr (kSeg) { sum = r[u] ? v[u] : sum + v[u]; seen |= r[u]; }
+                else sum += v[u];
+            }
         }
-        for (; j < r1; j++) sum += p[(long long)j * P::PAD];
+        for (; j < r1; j++) {
+            if constexpr (kSeg) {
+                const uint32_t r = fl[(long long)j * P::PAD];
+                sum = r ? p[(long long)j * P::PAD] : sum + p[(long long)j * P::PAD];
+                seen |= r;
+            } else sum += p[(long long)j * P::PAD];
+        }
     }
     part[ck][kb] = sum;
+    if constexpr (kSeg) pflag[ck][kb] = seen;
     __syncthreads();
     uint32_t run = (valid && carry_in) ? carry_in[sc * P::PAD + k] : 0u;
-    for (int c2 = 0; c2 < ck; c2++) run += part[c2][kb];
+    for (int c2 = 0; c2 < ck; c2++) {
+        if constexpr (kSeg) run = pflag[c2][kb] ? part[c2][kb] : run + part[c2][kb];
+        else run += part[c2][kb];
+    }
     if (!valid) return;
     int j = j0;
     for (; j + 8 <= r1; j += 8) {
-        uint32_t v[8];
+        uint32_t v[8], r[8];
 #pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = p[(long long)(j + u) * P::PAD];
+        for (int u = 0; u < 8; u++) {
+            v[u] = p[(long long)(j + u) * P::PAD];
+            if constexpr (kSeg) r[u] = fl[(long long)(j + u) * P::PAD];
+        }
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             p[(long long)(j + u) * P::PAD] = run;
-            run += v[u];
+            if constexpr (kSeg) run = r[u] ? v[u] : run + v[u];
+            else run += v[u];
         }
     }
     for (; j < j1; j++) {
         const uint32_t v = (j < n_read) ? p[(long long)j * P::PAD] : 0u;
         p[(long long)j * P::PAD] = run;
-        run += v;
+        if constexpr (kSeg) run = (j < n_read && fl[(long long)j * P::PAD]) ? v : run + v;
+        else run += v;
     }
     if (carry_out && ck == kScanChunks - 1) carry_out[sc * P::PAD + k] = run;
 }
@@ -317,19 +391,21 @@ __device__ __forceinline__ void pva_formant(cf* scr, const cf* w512l, const Spec
     wave_lds_sync();
 }
 
-// kFormant: formant preservation with lifter `lifter` and transposer ratio g (nae_stretch_block_formant_f32); off, both are unused
-template <int N, bool kUnit, bool kFormant>
-__global__ __launch_bounds__(64 * (kFormant ? PvAny<N, true>::kWaves3 : PvAny<N>::kWaves3)) void pv_any_synth_kernel(SigViewD src, PvParams p, long long n_items,
+// kFormant: formant preservation with lifter `lifter` and transposer ratio g (nae_stretch_block_formant_f32); off, both are unused.
+// kTransient: an onset frame takes Qs = Qa ("Transient preservation"); frames b0 - 2 and b0 - 1 prime P and "high".
+template <int N, bool kUnit, bool kFormant, bool kTransient = false>
+__global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient>::kWaves3)) void pv_any_synth_kernel(SigViewD src, PvParams p, long long n_items,
                                                                                        const uint32_t* __restrict__ phase_ws, OutViewD out,
                                                                                        SpecAnyTables tb, int lifter, float g)
 {
-    using P = PvAny<N, kFormant>;
+    using P = PvAny<N, kFormant, kTransient>;
     using Gm = typename P::Gm;
     __shared__ __attribute__((aligned(16))) cf w512l[512];
     __shared__ __attribute__((aligned(16))) cf scratch[P::kWaves3 * Gm::SCR];
     __shared__ __attribute__((aligned(16))) cf yspec[P::kWaves3 * P::PAD];
     __shared__ uint32_t state[P::kWaves3 * 2 * P::ST];
     __shared__ float lbuf[kFormant ? P::kWaves3 * P::PAD : 1];   // formant: L, then c', then Ls
+    __shared__ float pprev[kTransient ? P::kWaves3 * P::ST : 1];  // transients: P_{f-1} of bin lane + 64 r
     for (int i = threadIdx.x; i < 512; i += 64 * P::kWaves3) w512l[i] = tb.w512[i];
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -340,6 +416,7 @@ __global__ __launch_bounds__(64 * (kFormant ? PvAny<N, true>::kWaves3 : PvAny<N>
     float* lb = lbuf + (kFormant ? wave_id() * P::PAD : 0);
     uint32_t* qp = state + wave_id() * 2 * P::ST + lane;  // [r * 64]: Qa_{f-1} of bin lane + 64 r
     uint32_t* qs = qp + P::ST;                           //           Qs
+    float* pp = pprev + (kTransient ? wave_id() * P::ST + lane : 0);
     const long long sc = item / p.n_tiles;
     const int tile = (int)(item % p.n_tiles);
     const long long s_idx = sc / p.ch;
@@ -349,7 +426,8 @@ __global__ __launch_bounds__(64 * (kFormant ? PvAny<N, true>::kWaves3 : PvAny<N>
     const long long b_end = b0 + p.tile < p.f_stop ? b0 + p.tile : p.f_stop;
     long long f_end = b_end + 3;                           // frames b0 .. b_end+2 feed blocks b0 .. b_end-1
     if (f_end > p.frames) f_end = p.frames;
-    const long long f_first = b0 > 0 ? b0 - 1 : 0;        // b0 - 1 only primes Qa_{f-1}
+    // b0 - 1 only primes Qa_{f-1}; with transients b0 - 2 and b0 - 1 also prime P and "high"
+    const long long f_first = kTransient ? (b0 > 2 ? b0 - 2 : 0) : (b0 > 0 ? b0 - 1 : 0);
     float* optr = out.base + s_idx * out.ss + c * out.cs;
 
     // Qs in front of the tile: pass 2's record (or zero)
@@ -363,6 +441,7 @@ __global__ __launch_bounds__(64 * (kFormant ? PvAny<N, true>::kWaves3 : PvAny<N>
 #pragma unroll
     for (int i = 0; i < P::K; i++) r0[i] = r1[i] = r2[i] = 0.0f;
     long long s_prev = 0;
+    bool high_prev = false;                                // transients: high(f - 1), wave-uniform
 #pragma unroll 1
     for (long long f = f_first; f < f_end; f++) {
         const long long s = pva_frame_start<N>(p, f);
@@ -370,6 +449,7 @@ __global__ __launch_bounds__(64 * (kFormant ? PvAny<N, true>::kWaves3 : PvAny<N>
         const unsigned d = (unsigned)(s - s_prev);
         const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
         const bool live = f >= b0;                         // wave-uniform
+        int rising = 0;
 #pragma unroll 2
         for (int r = 0; r < P::NB; r++) {
             const int k = lane + 64 * r;
@@ -384,6 +464,21 @@ __global__ __launch_bounds__(64 * (kFormant ? PvAny<N, true>::kWaves3 : PvAny<N>
                     if (k < P::B) lb[k] = __builtin_amdgcn_logf(fmaxf(sqrt_rn(x.x * x.x + x.y * x.y), 0x1p-40f));   // L = log2 max(|X|, 2^-40)
             }
             qp[64 * r] = qa;
+            if constexpr (kTransient) rising += pva_rises<N>(x, k, pp + 64 * r, f > f_first);
+        }
+        if constexpr (kTransient) {
+            const bool high = f > f_first && pva_high<N>(rising);
+            if (live && f >= 2 && high && !high_prev) {        // an onset: Qs = Qa_f, Y = X (wave-uniform)
+#pragma unroll 1
+                for (int r = 0; r < P::NB; r++) {
+                    const int k = lane + 64 * r;
+                    const int kc = k < P::B ? k : P::M;
+                    const uint32_t qa = qp[64 * r];
+                    qs[64 * r] = qa;
+                    if (k < P::B) ys[k] = pipe_rotate(any_rfft_bin<Gm>(scr, tb.tn, kc), qa, qa);
+                }
+            }
+            high_prev = high;
         }
         s_prev = s;
         if (!live) {
@@ -451,49 +546,53 @@ __global__ __launch_bounds__(64 * (kFormant ? PvAny<N, true>::kWaves3 : PvAny<N>
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-template <int N>
+template <int N, bool kTransient>
 static int launch_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, uint32_t* phase_ws,
                         const SpecAnyTables& tb)
 {
-    using P = PvAny<N>;
+    using P = PvAny<N, false, kTransient>;
+    const char* name = kTransient ? "pv_any_phase_transient_kernel" : "pv_any_phase_kernel";
     const long long items = n_sc * p.n_tiles;
     const long long grid = (items + P::kWaves1 - 1) / P::kWaves1;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_phase_kernel: grid too large");
-    NAE_KLAUNCH(ctx, "pv_any_phase_kernel", (unit_stride ? pv_any_phase_kernel<N, true> : pv_any_phase_kernel<N, false>), dim3((unsigned)grid),
+    NAE_KLAUNCH(ctx, name, (unit_stride ? pv_any_phase_kernel<N, true, kTransient> : pv_any_phase_kernel<N, false, kTransient>), dim3((unsigned)grid),
                 dim3(64 * P::kWaves1), 0, ctx->stream, src, p, items, phase_ws, tb);
-    return nae_check(ctx, hipGetLastError(), "pv_any_phase_kernel");
+    return nae_check(ctx, hipGetLastError(), name);
 }
 
 // from 256 tiles per stream-channel on, 16 threads per bin (pv_scan_chunked_kernel); else one (pv_scan_kernel)
-template <int N>
+template <int N, bool kSeg>
 static int launch_scan(nae_ctx* ctx, const char* name, uint32_t* phase_ws, long long n_sc, int n_tiles, const uint32_t* carry_in,
                        uint32_t* carry_out, int n_read)
 {
     using P = PvAny<N>;
     if (n_tiles >= 256 && n_sc * P::NB <= 0x7fffffffll) {
-        NAE_KLAUNCH(ctx, name, (pv_scan_chunked_kernel<N>), dim3((unsigned)(n_sc * P::NB)), dim3(64 * kScanChunks), 0, ctx->stream,
+        if (kSeg) name = "pv_any_scan_chunked_transient_kernel";   // the segmented scans have profile names of their own
+        NAE_KLAUNCH(ctx, name, (pv_scan_chunked_kernel<N, kSeg>), dim3((unsigned)(n_sc * P::NB)), dim3(64 * kScanChunks), 0, ctx->stream,
                     phase_ws, n_sc, n_tiles, carry_in, carry_out, n_read);
         return nae_check(ctx, hipGetLastError(), name);
     }
     const long long grid = (n_sc * P::PAD + 255) / 256;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_scan_kernel: grid too large");
-    NAE_KLAUNCH(ctx, name, (pv_scan_kernel<N>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, phase_ws, n_sc, n_tiles, carry_in, carry_out,
+    if (kSeg) name = "pv_any_scan_transient_kernel";
+    NAE_KLAUNCH(ctx, name, (pv_scan_kernel<N, kSeg>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, phase_ws, n_sc, n_tiles, carry_in, carry_out,
                 n_read);
     return nae_check(ctx, hipGetLastError(), name);
 }
 
-template <int N, bool kFormant>
+template <int N, bool kFormant, bool kTransient>
 static int launch_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
                         const OutViewD& out, const SpecAnyTables& tb, int lifter, float g)
 {
-    using P = PvAny<N, kFormant>;
-    const char* name = kFormant ? "pv_any_synth_formant_kernel" : "pv_any_synth_kernel";
+    using P = PvAny<N, kFormant, kTransient>;
+    const char* name = kTransient ? (kFormant ? "pv_any_synth_formant_transient_kernel" : "pv_any_synth_transient_kernel")
+                                  : (kFormant ? "pv_any_synth_formant_kernel" : "pv_any_synth_kernel");
     const long long items = n_sc * p.n_tiles;
     if (items == 0) return NAE_OK;
     const long long grid = (items + P::kWaves3 - 1) / P::kWaves3;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_synth_kernel: grid too large");
-    NAE_KLAUNCH(ctx, name, (unit_stride ? pv_any_synth_kernel<N, true, kFormant> : pv_any_synth_kernel<N, false, kFormant>), dim3((unsigned)grid),
-                dim3(64 * P::kWaves3), 0, ctx->stream, src, p, items, phase_ws, out, tb, lifter, g);
+    NAE_KLAUNCH(ctx, name, (unit_stride ? pv_any_synth_kernel<N, true, kFormant, kTransient> : pv_any_synth_kernel<N, false, kFormant, kTransient>),
+                dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream, src, p, items, phase_ws, out, tb, lifter, g);
     return nae_check(ctx, hipGetLastError(), name);
 }
 
@@ -519,39 +618,50 @@ size_t nae_pv_record_pad(int n_fft) { return (size_t)((n_fft / 2 + 1 + 7) & ~7);
 
 bool nae_pv_size_ok(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096; }
 
-int nae_pv_resident3(nae_ctx* ctx, int n_fft, bool formant)
+int nae_pv_resident3(nae_ctx* ctx, int n_fft, bool formant, bool transients)
 {
     return at_size(ctx, n_fft, [&](auto n) {
         constexpr int N = decltype(n)::value;
+        if (transients) return formant ? PvAny<N, true, true>::kResident3 : PvAny<N, false, true>::kResident3;
         return formant ? PvAny<N, true>::kResident3 : PvAny<N>::kResident3;
     });
 }
 
-int nae_launch_pvany_phase(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, uint32_t* phase_ws)
-{
-    SpecAnyTables tb;
-    int rc = nae_spec_any_tables(ctx, n_fft, &tb);
-    if (rc) return rc;
-    return at_size(ctx, n_fft, [&](auto n) { return launch_phase<decltype(n)::value>(ctx, p, src, n_sc, unit_stride, phase_ws, tb); });
-}
-
-int nae_launch_pv_scan(nae_ctx* ctx, int n_fft, const char* name, uint32_t* phase_ws, long long n_sc, int n_tiles, const uint32_t* carry_in,
-                       uint32_t* carry_out, int n_read)
-{
-    return at_size(ctx, n_fft, [&](auto n) {
-        return launch_scan<decltype(n)::value>(ctx, name, phase_ws, n_sc, n_tiles, carry_in, carry_out, n_read);
-    });
-}
-
-int nae_launch_pvany_synth(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride,
-                           const uint32_t* phase_ws, const OutViewD& out, int lifter, float g)
+int nae_launch_pvany_phase(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, uint32_t* phase_ws,
+                           bool transients)
 {
     SpecAnyTables tb;
     int rc = nae_spec_any_tables(ctx, n_fft, &tb);
     if (rc) return rc;
     return at_size(ctx, n_fft, [&](auto n) {
         constexpr int N = decltype(n)::value;
-        return lifter > 0 ? launch_synth<N, true>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g)
-                          : launch_synth<N, false>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, 0, 0.0f);
+        return transients ? launch_phase<N, true>(ctx, p, src, n_sc, unit_stride, phase_ws, tb)
+                          : launch_phase<N, false>(ctx, p, src, n_sc, unit_stride, phase_ws, tb);
+    });
+}
+
+int nae_launch_pv_scan(nae_ctx* ctx, int n_fft, const char* name, uint32_t* phase_ws, long long n_sc, int n_tiles, const uint32_t* carry_in,
+                       uint32_t* carry_out, int n_read, bool segmented)
+{
+    return at_size(ctx, n_fft, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        return segmented ? launch_scan<N, true>(ctx, name, phase_ws, n_sc, n_tiles, carry_in, carry_out, n_read)
+                         : launch_scan<N, false>(ctx, name, phase_ws, n_sc, n_tiles, carry_in, carry_out, n_read);
+    });
+}
+
+int nae_launch_pvany_synth(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride,
+                           const uint32_t* phase_ws, const OutViewD& out, int lifter, float g, bool transients)
+{
+    SpecAnyTables tb;
+    int rc = nae_spec_any_tables(ctx, n_fft, &tb);
+    if (rc) return rc;
+    return at_size(ctx, n_fft, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        if (transients)
+            return lifter > 0 ? launch_synth<N, true, true>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g)
+                              : launch_synth<N, false, true>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, 0, 0.0f);
+        return lifter > 0 ? launch_synth<N, true, false>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g)
+                          : launch_synth<N, false, false>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, 0, 0.0f);
     });
 }

@@ -118,13 +118,33 @@ __device__ __forceinline__ void lock_map_of_frame(const cf (&v)[8], cf nyq, cons
     wave_lds_sync();                              // the scratch is free again
 }
 
+// transient preservation ("Transient preservation"), rules 1-4 for this lane's bins k = lane + 64 r (r = 8: k = 512, lane 0):
+// P = |X|^2 (two products and an add, never fused) against the previous frame's P in pp (registers), counted across the wave with a ballot; pp
+// takes P.  Returns high(f); counted = false (the first frame of a walk) counts nothing.
+__device__ __forceinline__ bool lock_high(const cf (&v)[8], cf nyq, float (&pp)[9], bool counted, int lane)
+{
+    int rising = 0;
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const cf x = r < 8 ? v[r] : nyq;
+        const float P = x.x * x.x + x.y * x.y;
+        const bool mine = r < 8 || lane == 0;
+        const bool rise = counted && mine && P > NAE_TRANSIENT_RISE * pp[r] && P > NAE_TRANSIENT_FLOOR * (float)NAE_FFT_N;
+        rising += __popcll(__ballot(rise));
+        pp[r] = P;
+    }
+    return counted && NAE_TRANSIENT_DEN * rising >= NAE_TRANSIENT_NUM * NAE_FFT_BINS;
+}
+
 // ------------------------------------------------------------------------------------------------ pass L1
-// tile maps: c at maps[rec * 520 + k] (uint32), sigma at sig16[rec * 520 + k] (uint16), rec = sc * n_tiles + tile
+// tile maps: c at maps[rec * 520 + k] (uint32), sigma at sig16[rec * 520 + k] (uint16), rec = sc * n_tiles + tile.  kTransient: an onset frame's
+// map is the reset map (Qs = Qa: it ignores its input), the running map becomes it, and maps[rec * 520 + 513] (a padding slot) is 1 when the tile
+// holds an onset — the map (sigma, c, r) of DESIGN.md §3; frames f0 - 2 and f0 - 1 prime P and "high" 
 constexpr size_t kLockMapWave = kPadScratchCf * sizeof(cf) + kT1024Pad * (sizeof(uint16_t) + sizeof(uint32_t));
 constexpr size_t kLdsLockMap = kLdsTablesPad + kWaves * kLockMapWave;
 static_assert(2 * kLdsLockMap <= 160 * 1024, "two workgroups per CU");
 
-template <bool kUnit>
+template <bool kUnit, bool kTransient = false>
 __global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, PvParams p, long long n_items, uint32_t* __restrict__ maps,
                                                                  uint16_t* __restrict__ sig16, Tables tb)
 {
@@ -160,14 +180,26 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, P
     for (int r = 0; r < 9; r++) qp[r] = 0;
     cf v[8], nyq;
     long long s_prev = 0;
+    const long long f_first = kTransient ? (f0 > 2 ? f0 - 2 : 0) : (f0 > 0 ? f0 - 1 : 0);
+    float pp[9];                                        // transients: P_{f-1} of this lane's bins
+    bool high_prev = false;                             //             high(f - 1), wave-uniform
+    uint32_t reset = 0;                                 //             an onset in [f0, f1)
 #pragma unroll 1
-    for (long long f = (f0 > 0 ? f0 - 1 : 0); f < f1; f++) {
+    for (long long f = f_first; f < f1; f++) {
         const long long s = frame_start(p, f);
         lock_analyse<kUnit>(v, nyq, qa, in, s, hann, scratch, twa, w64, t1024, lane);
+        bool onset = false;
+        if constexpr (kTransient) {
+            const bool high = lock_high(v, nyq, pp, f > f_first, lane);
+            onset = f >= 2 && high && !high_prev;
+            high_prev = high;
+        }
         if (f >= f0) {
             uint32_t sg[9], cc[9];
-            if (f == 0) {
-                // Qs_0 = Qa_0: the map (identity, Qa_0) applied to the zero phase in front of the stream
+            if (f == 0 || onset) {
+                // Qs_0 = Qa_0: the map (identity, Qa_0) applied to the zero phase in front of the stream; an onset's reset map is the same,
+                // and whatever ran before it no longer matters
+                if (onset) reset = 1;
 #pragma unroll
                 for (int r = 0; r < 9; r++) { sg[r] = r < 8 ? (uint32_t)(lane + 64 * r) : 512u; cc[r] = qa[r]; }
             } else {
@@ -175,10 +207,13 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, P
                 const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
                 lock_map_of_frame(v, nyq, qa, qp, d, R, scratch, lane, sg, cc);
             }
-            // running map, then this frame: (ms[sg], mc[sg] + cc); all gathers land before the first write
+            // running map, then this frame: (ms[sg], mc[sg] + cc), or after a reset map the reset map; all gathers land before the first write
             uint32_t ns[9], nc[9];
 #pragma unroll
-            for (int r = 0; r < 9; r++) { ns[r] = ms[sg[r]]; nc[r] = mc[sg[r]] + cc[r]; }
+            for (int r = 0; r < 9; r++) {
+                if (onset) { ns[r] = sg[r]; nc[r] = cc[r]; }
+                else { ns[r] = ms[sg[r]]; nc[r] = mc[sg[r]] + cc[r]; }
+            }
             wave_lds_sync();
 #pragma unroll
             for (int r = 0; r < 9; r++) {
@@ -198,14 +233,18 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, P
         const int k = lane + 64 * r;
         if (k < NAE_FFT_BINS) { oc[k] = mc[k]; os[k] = ms[k]; }
     }
+    if (kTransient && lane == 0) oc[NAE_FFT_BINS] = reset;   // slot 513 of the c record (padded to 520)
 }
 
 // ------------------------------------------------------------------------------------------------ pass L2
 // One workgroup per stream-channel, one wave per chunk of tiles (1 chunk, or kLockChunks from 256 tiles on).  Tiles >= n_read are the identity
-// (their maps were not computed); record t = Qs in front of tile t, carry_out = Qs behind the last tile.
+// (their maps were not computed); record t = Qs in front of tile t, carry_out = Qs behind the last tile.  kTransient: a tile map with slot 513 set
+// is a reset map — composed after anything it is itself (sigma_b, c_b, 1), applied it gives c_b — and a chunk's map carries the flag in the same
+// slot of its c array; the carried phase does not cross a reset.
 constexpr int kLockChunks = 16;
 constexpr size_t kLockScanWave = 3 * kT1024Pad * sizeof(uint32_t);      // chunk map (sigma, c) and the wave's running Qs
 
+template <bool kTransient = false>
 __global__ __launch_bounds__(64 * kLockChunks) void pvlock_scan_kernel(uint32_t* __restrict__ rec, const uint32_t* __restrict__ maps,
                                                                       const uint16_t* __restrict__ sig16, int n_tiles, const uint32_t* __restrict__ carry_in,
                                                                       uint32_t* __restrict__ carry_out, int n_read)
@@ -224,6 +263,7 @@ __global__ __launch_bounds__(64 * kLockChunks) void pvlock_scan_kernel(uint32_t*
     const long long rec0 = sc * (long long)n_tiles;
     uint32_t* ms = chunk_s(ck);
     uint32_t* mc = chunk_c(ck);
+    uint32_t chunk_reset = 0;                           // kTransient: a reset map among the chunk's tiles
     if (nch > 1) {
         // the chunk's map: its tiles composed in order
 #pragma unroll
@@ -235,11 +275,17 @@ __global__ __launch_bounds__(64 * kLockChunks) void pvlock_scan_kernel(uint32_t*
         for (int j = j0; j < r1; j++) {
             const uint32_t* tc = maps + (rec0 + j) * kT1024Pad;
             const uint16_t* ts = sig16 + (rec0 + j) * kT1024Pad;
+            const bool rb = kTransient && tc[NAE_FFT_BINS] != 0u;   // wave-uniform
+            if (rb) chunk_reset = 1;
             uint32_t ns[9], nc[9];
 #pragma unroll
             for (int r = 0; r < 9; r++) {
                 const int k = lane + 64 * r;
-                if (k < NAE_FFT_BINS) { const uint32_t sb = ts[k]; ns[r] = ms[sb]; nc[r] = mc[sb] + tc[k]; }
+                if (k < NAE_FFT_BINS) {
+                    const uint32_t sb = ts[k];
+                    if (rb) { ns[r] = sb; nc[r] = tc[k]; }
+                    else { ns[r] = ms[sb]; nc[r] = mc[sb] + tc[k]; }
+                }
             }
             wave_lds_sync();
 #pragma unroll
@@ -256,15 +302,17 @@ __global__ __launch_bounds__(64 * kLockChunks) void pvlock_scan_kernel(uint32_t*
         const int k = lane + 64 * r;
         if (k < NAE_FFT_BINS) qs[k] = carry_in ? carry_in[sc * kT1024Pad + k] : 0u;
     }
+    if (kTransient && nch > 1 && lane == 0) mc[NAE_FFT_BINS] = chunk_reset;   // the chunk map's flag, in slot 513 of its c array
     __syncthreads();
     for (int w = 0; w < ck; w++) {
         const uint32_t* ws = chunk_s(w);
         const uint32_t* wc = chunk_c(w);
+        const bool rw = kTransient && wc[NAE_FFT_BINS] != 0u;      // wave-uniform
         uint32_t nq[9];
 #pragma unroll
         for (int r = 0; r < 9; r++) {
             const int k = lane + 64 * r;
-            if (k < NAE_FFT_BINS) nq[r] = qs[ws[k]] + wc[k];
+            if (k < NAE_FFT_BINS) nq[r] = rw ? wc[k] : qs[ws[k]] + wc[k];
         }
         wave_lds_sync();
 #pragma unroll
@@ -279,13 +327,14 @@ __global__ __launch_bounds__(64 * kLockChunks) void pvlock_scan_kernel(uint32_t*
         uint32_t* o = rec + (rec0 + j) * kT1024Pad;
         const uint32_t* tc = maps + (rec0 + j) * kT1024Pad;
         const uint16_t* ts = sig16 + (rec0 + j) * kT1024Pad;
+        const bool rb = kTransient && j < n_read && tc[NAE_FFT_BINS] != 0u;   // wave-uniform
         uint32_t nq[9];
 #pragma unroll
         for (int r = 0; r < 9; r++) {
             const int k = lane + 64 * r;
             if (k < NAE_FFT_BINS) {
                 o[k] = qs[k];
-                nq[r] = j < n_read ? qs[ts[k]] + tc[k] : qs[k];
+                nq[r] = rb ? tc[k] : j < n_read ? qs[ts[k]] + tc[k] : qs[k];
             }
         }
         wave_lds_sync();
@@ -372,8 +421,9 @@ __device__ __forceinline__ void lock_formant_apply(cf (&y)[8], cf& ynyq, cf* scr
     wave_lds_sync();                              // Y replaces Ls in the scratch
 }
 
-// kFormant: formant preservation with lifter `lifter` and transposer ratio g; off, both are unused
-template <bool kUnit, bool kFormant>
+// kFormant: formant preservation with lifter `lifter` and transposer ratio g; off, both are unused.  kTransient: an onset frame takes Qs = Qa
+// ("Transient preservation"); frames b0 - 2 and b0 - 1 prime P and "high".
+template <bool kUnit, bool kFormant, bool kTransient = false>
 __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src, PvParams p, long long n_items, const uint32_t* __restrict__ phase_ws,
                                                                    OutViewD out, Tables tb, int lifter, float g)
 {
@@ -398,7 +448,8 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
     it.b_end = it.b0 + p.tile < p.f_stop ? it.b0 + p.tile : p.f_stop;
     long long f_end = it.b_end + 3;                              // frames b0 .. b_end+2 feed blocks b0 .. b_end-1
     if (f_end > p.frames) f_end = p.frames;
-    const long long f_first = it.b0 > 0 ? it.b0 - 1 : 0;        // b0 - 1 only primes Qa_{f-1}
+    // b0 - 1 only primes Qa_{f-1}; with transients b0 - 2 and b0 - 1 also prime P and "high"
+    const long long f_first = kTransient ? (it.b0 > 2 ? it.b0 - 2 : 0) : (it.b0 > 0 ? it.b0 - 1 : 0);
     float* optr = out.base + s_idx * out.ss + c * out.cs;
     const BlockOut bo{optr, out.fs, (out.fs == 1) && ((reinterpret_cast<uintptr_t>(optr) & 15) == 0)};
 
@@ -415,13 +466,21 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
     float r0[4] = {0.0f, 0.0f, 0.0f, 0.0f}, r1[4] = {0.0f, 0.0f, 0.0f, 0.0f}, r2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     cf v[8], nyq;
     long long s_prev = 0;
+    float pp[9];                                                // transients: P_{f-1} of this lane's bins
+    bool high_prev = false;                                     //             high(f - 1), wave-uniform
 #pragma unroll 1
     for (long long f = f_first; f < f_end; f++) {
         const long long s = frame_start(p, f);
         lock_analyse<kUnit>(v, nyq, qa, in, s, hann, scratch, twa, w64, t1024, lane);
+        bool onset = false;
+        if constexpr (kTransient) {
+            const bool high = lock_high(v, nyq, pp, f > f_first, lane);
+            onset = f >= 2 && high && !high_prev;
+            high_prev = high;
+        }
         if (f >= it.b0) {
             uint32_t sg[9], cc[9];
-            if (f == 0) {
+            if (f == 0 || onset) {                              // Qs_0 = Qa_0; an onset's Qs_f = Qa_f (applied to Qs_{f-1} = 0 below)
 #pragma unroll
                 for (int r = 0; r < 9; r++) { sg[r] = r < 8 ? (uint32_t)(lane + 64 * r) : 512u; cc[r] = qa[r]; }
             } else {
@@ -431,7 +490,7 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
             }
             uint32_t nq[9];
 #pragma unroll
-            for (int r = 0; r < 9; r++) nq[r] = qs[sg[r]] + cc[r];
+            for (int r = 0; r < 9; r++) nq[r] = onset ? cc[r] : qs[sg[r]] + cc[r];
             wave_lds_sync();
 #pragma unroll
             for (int r = 0; r < 9; r++) {
@@ -521,55 +580,69 @@ using namespace nae;
 // the kernels here take more than 64 KiB of dynamic LDS: the attribute is set as for the vocoder pipeline (nae_pv_lds_attr), once per context
 // and kernel, the scan kernel at its largest size
 constexpr unsigned kAttrLockMap = 1u << 12, kAttrLockScan = 1u << 13, kAttrLockSynth = 1u << 14,   // nae_ctx::pv_attr_done (pipeline: bits 0-10)
-                   kAttrLockSynthF = 1u << 15;
+                   kAttrLockSynthF = 1u << 15, kAttrLockMapT = 1u << 16, kAttrLockScanT = 1u << 17, kAttrLockSynthT = 1u << 18,
+                   kAttrLockSynthFT = 1u << 19;
 
+// transients: the kTransient instantiations (reset maps, the segmented scan; profile names pvlock_map_transient_kernel and
+// pvlock_scan_transient_kernel)
 int nae_launch_pvlock_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
-                            uint32_t* phase_ws, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out)
+                            uint32_t* phase_ws, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out, bool transients)
 {
     const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
     {
         const long long items = n_sc * p.n_tiles;
         const long long grid = (items + kWaves - 1) / kWaves;
         if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_map_kernel: grid too large");
-        int rc = nae_pv_lds_attr(ctx, kAttrLockMap, kLdsLockMap, reinterpret_cast<const void*>(pvlock_map_kernel<true>),
-                                 reinterpret_cast<const void*>(pvlock_map_kernel<false>));
+        const char* name = transients ? "pvlock_map_transient_kernel" : "pvlock_map_kernel";
+        auto k_unit = transients ? pvlock_map_kernel<true, true> : pvlock_map_kernel<true, false>;
+        auto k_strided = transients ? pvlock_map_kernel<false, true> : pvlock_map_kernel<false, false>;
+        int rc = nae_pv_lds_attr(ctx, transients ? kAttrLockMapT : kAttrLockMap, kLdsLockMap, reinterpret_cast<const void*>(k_unit),
+                                 reinterpret_cast<const void*>(k_strided));
         if (rc) return rc;
-        NAE_KLAUNCH(ctx, "pvlock_map_kernel", (unit_stride ? pvlock_map_kernel<true> : pvlock_map_kernel<false>), dim3((unsigned)grid), dim3(kThreads),
-                    kLdsLockMap, ctx->stream, src, p, items, maps, sig16, tb);
-        rc = nae_check(ctx, hipGetLastError(), "pvlock_map_kernel");
+        NAE_KLAUNCH(ctx, name, (unit_stride ? k_unit : k_strided), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream, src, p, items, maps,
+                    sig16, tb);
+        rc = nae_check(ctx, hipGetLastError(), name);
         if (rc) return rc;
     }
     if (n_sc > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_scan_kernel: grid too large");
-    int rc = nae_pv_lds_attr(ctx, kAttrLockScan, kLockChunks * kLockScanWave, reinterpret_cast<const void*>(pvlock_scan_kernel));
+    const char* name = transients ? "pvlock_scan_transient_kernel" : "pvlock_scan_kernel";
+    auto k_scan = transients ? pvlock_scan_kernel<true> : pvlock_scan_kernel<false>;
+    int rc = nae_pv_lds_attr(ctx, transients ? kAttrLockScanT : kAttrLockScan, kLockChunks * kLockScanWave, reinterpret_cast<const void*>(k_scan));
     if (rc) return rc;
     const int nch = p.n_tiles >= 256 ? kLockChunks : 1;
-    NAE_KLAUNCH(ctx, "pvlock_scan_kernel", pvlock_scan_kernel, dim3((unsigned)n_sc), dim3(64 * nch), nch * kLockScanWave, ctx->stream, phase_ws, maps,
-                sig16, p.n_tiles, carry_in, carry_out, n_needed);
-    return nae_check(ctx, hipGetLastError(), "pvlock_scan_kernel");
+    NAE_KLAUNCH(ctx, name, k_scan, dim3((unsigned)n_sc), dim3(64 * nch), nch * kLockScanWave, ctx->stream, phase_ws, maps, sig16, p.n_tiles, carry_in,
+                carry_out, n_needed);
+    return nae_check(ctx, hipGetLastError(), name);
 }
 
-template <bool kFormant>
+template <bool kFormant, bool kTransient>
 static int launch_lock_synth(nae_ctx* ctx, unsigned attr_bit, const char* name, const PvParams& p, const SigViewD& src, long long items, bool unit_stride,
                              const uint32_t* phase_ws, const OutViewD& out, int lifter, float g)
 {
     const long long grid = (items + kWaves - 1) / kWaves;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_synth_kernel: grid too large");
     const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
-    int rc = nae_pv_lds_attr(ctx, attr_bit, kLdsLockSynth, reinterpret_cast<const void*>(pvlock_synth_kernel<true, kFormant>),
-                             reinterpret_cast<const void*>(pvlock_synth_kernel<false, kFormant>));
+    int rc = nae_pv_lds_attr(ctx, attr_bit, kLdsLockSynth, reinterpret_cast<const void*>(pvlock_synth_kernel<true, kFormant, kTransient>),
+                             reinterpret_cast<const void*>(pvlock_synth_kernel<false, kFormant, kTransient>));
     if (rc) return rc;
-    NAE_KLAUNCH(ctx, name, (unit_stride ? pvlock_synth_kernel<true, kFormant> : pvlock_synth_kernel<false, kFormant>), dim3((unsigned)grid),
-                dim3(kThreads), kLdsLockSynth, ctx->stream, src, p, items, phase_ws, out, tb, lifter, g);
+    NAE_KLAUNCH(ctx, name, (unit_stride ? pvlock_synth_kernel<true, kFormant, kTransient> : pvlock_synth_kernel<false, kFormant, kTransient>),
+                dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream, src, p, items, phase_ws, out, tb, lifter, g);
     return nae_check(ctx, hipGetLastError(), name);
 }
 
-// lifter > 0: formant preservation (pvlock_synth_formant_kernel)
+// lifter > 0: formant preservation (pvlock_synth_formant_kernel); transients: onsets reset Qs (the *_transient_kernel instantiations)
 int nae_launch_pvlock_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
-                            const OutViewD& out, int lifter, float g)
+                            const OutViewD& out, int lifter, float g, bool transients)
 {
     const long long items = n_sc * p.n_tiles;
     if (items == 0) return NAE_OK;
+    if (transients) {
+        if (lifter > 0)
+            return launch_lock_synth<true, true>(ctx, kAttrLockSynthFT, "pvlock_synth_formant_transient_kernel", p, src, items, unit_stride, phase_ws,
+                                                 out, lifter, g);
+        return launch_lock_synth<false, true>(ctx, kAttrLockSynthT, "pvlock_synth_transient_kernel", p, src, items, unit_stride, phase_ws, out, 0, 0.0f);
+    }
     if (lifter > 0)
-        return launch_lock_synth<true>(ctx, kAttrLockSynthF, "pvlock_synth_formant_kernel", p, src, items, unit_stride, phase_ws, out, lifter, g);
-    return launch_lock_synth<false>(ctx, kAttrLockSynth, "pvlock_synth_kernel", p, src, items, unit_stride, phase_ws, out, 0, 0.0f);
+        return launch_lock_synth<true, false>(ctx, kAttrLockSynthF, "pvlock_synth_formant_kernel", p, src, items, unit_stride, phase_ws, out, lifter, g);
+    return launch_lock_synth<false, false>(ctx, kAttrLockSynth, "pvlock_synth_kernel", p, src, items, unit_stride, phase_ws, out, 0, 0.0f);
 }

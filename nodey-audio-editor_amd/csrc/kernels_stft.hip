@@ -570,16 +570,17 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
         return nae_check(ctx, e, "phase base init");
     }
     p.skip_from = n_needed;                   // pass 1 skips the tiles whose sums are not needed
-    const PvKernels pass1 = nae_pv_route_of(ctx, lock, n_fft, 0).pass1;
+    const bool transients = seg && seg->transients;
+    const PvKernels pass1 = nae_pv_route_of(ctx, lock, n_fft, 0, transients).pass1;
     const bool unit_stride = src->frame_stride == 1;
     if (pass1 == PvKernels::kLock) {
         const size_t n_rec = (size_t)n_sc * p.n_tiles;
         uint32_t* maps = phase_ws + n_rec * kT1024Pad;
         uint16_t* sig16 = reinterpret_cast<uint16_t*>(maps + n_rec * kT1024Pad);
-        return nae_launch_pvlock_phase(ctx, p, to_view(src), n_sc, unit_stride, n_needed, phase_ws, maps, sig16, carry_in, carry_out);
+        return nae_launch_pvlock_phase(ctx, p, to_view(src), n_sc, unit_stride, n_needed, phase_ws, maps, sig16, carry_in, carry_out, transients);
     }
     if (pass1 == PvKernels::kAny) {
-        const int rc = nae_launch_pvany_phase(ctx, n_fft, p, to_view(src), n_sc, unit_stride, phase_ws);
+        const int rc = nae_launch_pvany_phase(ctx, n_fft, p, to_view(src), n_sc, unit_stride, phase_ws, transients);
         if (rc) return rc;
     } else {
         // items are (stream-channel, tile) with tile fastest
@@ -593,7 +594,7 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
         if (rc) return rc;
     }
     return nae_launch_pv_scan(ctx, n_fft, pass1 == PvKernels::kAny ? "pv_any_scan_kernel" : "pv_scan_kernel", phase_ws, n_sc, p.n_tiles, carry_in,
-                              carry_out, n_needed);
+                              carry_out, n_needed, transients);
 }
 
 // pass 3 (locked: L3) from the records of pass 2 (or, one tile and nothing carried in, from zero), on the kernels nae_pv_route_of says; lifter > 0
@@ -617,9 +618,12 @@ int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
     const long long n_sc = (long long)n_streams * ch;
     const float g = (float)pl->rate_eff;                   // formant preservation: the transposer ratio
     const bool unit_stride = src->frame_stride == 1;
-    const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, lifter).pass3;
-    if (pass3 == PvKernels::kLock) return nae_launch_pvlock_synth(ctx, p, to_view(src), n_sc, unit_stride, phase_ws, to_out(out), lifter, g);
-    if (pass3 == PvKernels::kAny) return nae_launch_pvany_synth(ctx, n_fft, p, to_view(src), n_sc, unit_stride, phase_ws, to_out(out), lifter, g);
+    const bool transients = seg && seg->transients;
+    const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, lifter, transients).pass3;
+    if (pass3 == PvKernels::kLock)
+        return nae_launch_pvlock_synth(ctx, p, to_view(src), n_sc, unit_stride, phase_ws, to_out(out), lifter, g, transients);
+    if (pass3 == PvKernels::kAny)
+        return nae_launch_pvany_synth(ctx, n_fft, p, to_view(src), n_sc, unit_stride, phase_ws, to_out(out), lifter, g, transients);
     return nae_launch_pv_pipe(ctx, p, to_view(src), n_sc, phase_ws, to_out(out), unit_stride, frames_per_step);
 }
 

@@ -571,11 +571,11 @@ static int reserve_mid(nae_ctx* ctx, const nae_stretch_plan& pl, int ch, size_t 
     return NAE_OK;
 }
 
-// the one statement of the _n entries' rules: an unknown flag NAE_ERR_INVALID; a size outside 512 / 1024 / 2048 / 4096, or the phase lock at a
-// size other than 1024, NAE_ERR_UNSUPPORTED
+// the one statement of the _n entries' rules: an unknown flag NAE_ERR_INVALID; a size outside 512 / 1024 / 2048 / 4096, the phase lock at a
+// size other than 1024 (with or without NAE_STRETCH_TRANSIENTS), NAE_ERR_UNSUPPORTED
 int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft)
 {
-    if (flags & ~NAE_STRETCH_PHASE_LOCK) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
+    if (flags & ~(NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS)) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
     if (!nae_pv_size_ok(n_fft)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
     if ((flags & NAE_STRETCH_PHASE_LOCK) && n_fft != NAE_FFT_N) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "phase locking runs at n_fft = 1024 only");
     return NAE_OK;
@@ -600,7 +600,7 @@ struct nae_mix_front {
 // context's workspace between them).
 static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
                               const nae_sig* dst, const nae_mix_front* front, int stages = 3, bool lock = false, int n_fft = NAE_FFT_N,
-                              int lifter = 0)
+                              int lifter = 0, bool transients = false)
 {
     if (!ctx) return NAE_ERR_INVALID;
     int rc;
@@ -662,16 +662,17 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
         int phase_tile = 0, fps = 1;
         int tile;
         const int q = nae_formant_lifter_eff(pl, lifter);
-        const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, q).pass3;
+        const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, q, transients).pass3;
         if (pass3 == PvKernels::kLock)   // four waves per SIMD, tiles of at least 64 frames (pv_min_ptile does not apply)
             tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, 16, 64);
         else if (pass3 == PvKernels::kAny)
-            tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, (size_t)nae_pv_resident3(ctx, n_fft, q > 0),
+            tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, (size_t)nae_pv_resident3(ctx, n_fft, q > 0, transients),
                                                ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64);
         else tile = nae_pick_pv_shape(ctx, pl.frames, n_streams * ch, &phase_tile, &fps);
         rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, n_fft, pl.frames, ch, n_streams, phase_tile));
         if (rc) return rc;
         nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, pv_out_len, nullptr, nullptr};
+        seg.transients = transients;
         rc = nae_launch_pv_phase(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, phase_tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
         if (rc) return rc;
         rc = nae_launch_pv_synth(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, tile, phase_tile, static_cast<const uint32_t*>(ctx->ws_phase), pv_dst,
@@ -709,7 +710,8 @@ int nae_stretch_block_n_f32(nae_ctx* ctx, double rate, double pitch, unsigned fl
     if (!ctx) return NAE_ERR_INVALID;
     const int rc = nae_stretch_n_check(ctx, flags, n_fft);
     if (rc) return rc;
-    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft);
+    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft, 0,
+                              (flags & NAE_STRETCH_TRANSIENTS) != 0);
 }
 
 int nae_stretch_formant_lifter(int sample_rate, int n_fft)
@@ -727,7 +729,8 @@ int nae_stretch_block_formant_f32(nae_ctx* ctx, double rate, double pitch, unsig
     int rc = nae_stretch_n_check(ctx, flags, n_fft);
     if (rc) return rc;
     if ((rc = nae_formant_check(ctx, n_fft, lifter))) return rc;
-    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft, lifter);
+    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft, lifter,
+                              (flags & NAE_STRETCH_TRANSIENTS) != 0);
 }
 
 int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch,
@@ -784,6 +787,7 @@ int nae_debug_pv_tile_phase_n(nae_ctx* ctx, double rate, double pitch, unsigned 
         pv_in_len = pl.mid_len;
     }
     nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, 0, nullptr, nullptr};
+    seg.transients = (flags & NAE_STRETCH_TRANSIENTS) != 0;
     rc = nae_launch_pv_phase(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
     if (rc) return rc;
     std::vector<int32_t> tmp(ws_bytes / sizeof(int32_t));

@@ -110,6 +110,7 @@ struct nae_pv_segment {
     const uint32_t* carry_in;     // [n_streams*ch][520] phase behind frame f_origin-1 (null: zero)
     uint32_t* carry_out;          // receives the phase behind frame f_origin+f_count-1 (null: not wanted)
     bool carry_by_synth = false;  // the segment is synthesised as ONE tile and pass 3 itself writes carry_out (no pass 1)
+    bool transients = false;      // NAE_STRETCH_TRANSIENTS: onsets reset the synthesis phase (passes 1 and 3 prime from f_origin - 2)
 };
 // kernels_stft.hip: the vocoder's passes, unlocked or (lock, NAE_STRETCH_PHASE_LOCK) with identity phase locking on the kernels of kernels_pvlock.hip;
 // frame size n_fft (512 ... 4096; not 1024, or the debug key pv_any: the size-generic kernels of kernels_pv_any.hip).  lifter > 0: pass 3 preserves
@@ -127,20 +128,22 @@ inline int nae_formant_lifter_eff(const nae_stretch_plan& pl, int lifter) { retu
 //   pass 3  kShipped: the pipeline (kernels_pvpipe.hip);  kAny: pv_any_synth_kernel<N>;                   kLock: pvlock_synth_kernel.
 // Locked calls (1024 only: the callers check) run the locked kernels; unlocked calls at other sizes, or under the debug key pv_any, the size-generic
 // ones.  Pass 1 does not depend on the lifter.  Unlocked 1024-point calls with formant preservation (lifter_eff > 0) run the shipped pass 1 and
-// the size-generic pass 3: the pipeline has no formant stage, and the two passes share the record layout.
+// the size-generic pass 3: the pipeline has no formant stage, and the two passes share the record layout.  Unlocked calls with transient
+// preservation run the size-generic passes at every size, 1024 included: the shipped pass 1 and the pipeline have no onset detector; locked
+// ones the transient instantiations of the locked kernels.
 enum class PvKernels { kShipped, kAny, kLock };
 struct nae_pv_route { PvKernels pass1, pass3; };
-inline nae_pv_route nae_pv_route_of(const nae_ctx* ctx, bool lock, int n_fft, int lifter_eff)
+inline nae_pv_route nae_pv_route_of(const nae_ctx* ctx, bool lock, int n_fft, int lifter_eff, bool transients = false)
 {
     if (lock) return {PvKernels::kLock, PvKernels::kLock};
-    const PvKernels pass1 = n_fft != NAE_FFT_N || ctx->dbg_pv_any ? PvKernels::kAny : PvKernels::kShipped;
+    const PvKernels pass1 = n_fft != NAE_FFT_N || ctx->dbg_pv_any || transients ? PvKernels::kAny : PvKernels::kShipped;
     return {pass1, lifter_eff > 0 ? PvKernels::kAny : pass1};
 }
 // kernels_pv_any.hip: the vocoder sizes (512, 1024, 2048, 4096), the record length of a size (int32: N/2 + 1 padded to a multiple of 8), the
 // pass-3 waves a CU holds on the size-generic kernels (PvAny<N>::kResident3; formant: of the formant pass 3)
 bool nae_pv_size_ok(int n_fft);
 size_t nae_pv_record_pad(int n_fft);
-int nae_pv_resident3(nae_ctx* ctx, int n_fft, bool formant);
+int nae_pv_resident3(nae_ctx* ctx, int n_fft, bool formant, bool transients = false);
 int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft);   // nae_api.hip: flags and size of the _n entries
 int nae_formant_check(nae_ctx* ctx, int n_fft, int lifter);         // nae_api.hip: the lifter of the _formant entries
 int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t src_len, int ch,

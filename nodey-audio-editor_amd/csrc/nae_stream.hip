@@ -17,6 +17,7 @@ struct nae_stretch {
     bool lock = false;            // NAE_STRETCH_PHASE_LOCK (nae_stretch_create_ex)
     int n_fft = NAE_FFT_N;        // vocoder frame size, hop n_fft / 4 (nae_stretch_create_n)
     int lifter = 0;               // formant preservation's lifter, 0 = off (nae_stretch_create_formant)
+    bool transients = false;      // NAE_STRETCH_TRANSIENTS (nae_stretch_create_n / _formant)
     nae_stretch_plan pl{};        // parameters (in_len = 0)
     DevFifo in;                   // interleaved input, sample-frames
     // phase vocoder
@@ -79,6 +80,7 @@ int stretch_pv_stage(nae_stretch* h, const nae_stretch_plan& pl, const nae_sig& 
             return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(carry)");
     nae_pv_segment seg{(long long)h->blocks_done, (long long)count, (long long)F_r, limit,
                        h->blocks_done ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
+    seg.transients = h->transients;
     rc = nae_launch_pv_phase(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
     if (rc) return rc;
     rc = nae_launch_pv_synth(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps,
@@ -88,6 +90,9 @@ int stretch_pv_stage(nae_stretch* h, const nae_stretch_plan& pl, const nae_sig& 
     h->blocks_done = B_r;
     return NAE_OK;
 }
+
+// frames in front of a segment that its passes re-analyse: 1, or 2 with transient preservation (onset(f) reads frames f - 2 .. f)
+inline long long prime_frames(const nae_stretch* h) { return h->transients ? 2 : 1; }
 
 int stretch_process(nae_stretch* h)
 {
@@ -146,7 +151,7 @@ int stretch_process(nae_stretch* h)
             rc = stretch_pv_stage(h, pl, mid.view(), mid.total, F_r, B_r, out_limit, out.view());
             if (rc) return rc;
             out.total = produced_total;
-            mid.drop(frame_start_host(pl, h->n_fft, (long long)B_r - 1));
+            mid.drop(frame_start_host(pl, h->n_fft, (long long)B_r - prime_frames(h)));
         }
         return NAE_OK;
     }
@@ -176,8 +181,9 @@ int stretch_process(nae_stretch* h)
             rc = stretch_pv_stage(h, pl, in.view(), in.total, F_r, B_r, mid_limit, dst.view());
             if (rc) return rc;
             dst.total = produced_total;
-            // input still needed: from the start of frame B_r - 1 (it primes the next call's phase difference)
-            in.drop(frame_start_host(pl, h->n_fft, (long long)B_r - 1));
+            // input still needed: from the start of frame B_r - 1 (it primes the next call's phase difference; with transients also
+            // frame B_r - 2, which primes its onset rule)
+            in.drop(frame_start_host(pl, h->n_fft, (long long)B_r - prime_frames(h)));
         }
     }
     // ---- stage 2: rate transposer over the outputs whose 16 taps are known
@@ -252,6 +258,7 @@ int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, floa
     s->rate = rate;
     s->pitch = pitch;
     s->lock = (flags & NAE_STRETCH_PHASE_LOCK) != 0;
+    s->transients = pl.pv_on && (flags & NAE_STRETCH_TRANSIENTS) != 0;
     s->n_fft = n_fft;
     s->lifter = lifter;
     s->pl = pl;

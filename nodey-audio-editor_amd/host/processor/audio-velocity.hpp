@@ -28,6 +28,10 @@ namespace processor
 	// nae_stretch_formant_lifter(sample rate, fft_size)).  No key: false; a value that is not a bool: Runtime_error "Wrong field: formant";
 	// written back only when true.  It combines with "phase_lock" and "fft_size"; with "algorithm": "soundtouch" it is kept and has no effect.
 	bool formant_from_json(const Json::Value& value, const char* node_name);
+	// "transients" (bool, optional): transient preservation of the vocoder (NAE_STRETCH_TRANSIENTS: an onset frame resets the synthesis phase).
+	// No key: false; a value that is not a bool: Runtime_error "Wrong field: transients"; written back only when true.  It combines with
+	// "phase_lock", "fft_size" and "formant"; with "algorithm": "soundtouch" it is kept and has no effect.
+	bool transients_from_json(const Json::Value& value, const char* node_name);
 
 	class Velocity_modifier : public infra::Processor
 	{
@@ -36,6 +40,7 @@ namespace processor
 		Stretch_algorithm algorithm = default_stretch_algorithm();
 		bool phase_lock = false;
 		int fft_size = 1024;
+		bool transients = false;
 
 	  public:
 
@@ -52,7 +57,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override;            // velocity, keep_pitch (audio-velocity.cpp:479-485); algorithm, phase_lock, fft_size when not the default
+		Json::Value serialize() const override;            // velocity, keep_pitch (audio-velocity.cpp:479-485); algorithm, phase_lock, fft_size, transients when not the default
 		void deserialize(const Json::Value& value) override;  // :487-493
 	};
 
@@ -63,6 +68,7 @@ namespace processor
 		bool phase_lock = false;
 		int fft_size = 1024;
 		bool formant = false;
+		bool transients = false;
 
 	  public:
 
@@ -79,7 +85,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock, fft_size, formant when not the default
+		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock, fft_size, formant, transients when not the default
 		void deserialize(const Json::Value& value) override;  // :502-505
 	};
 
