@@ -19,6 +19,9 @@
 #define NAE_HOP 256             /* synthesis hop / spectrum hop (N/4)      */
 #define NAE_OLA_GAIN (2.0f / 3.0f) /* 1 / sum_t hann^2 at hop N/4 = 1/1.5  */
 #define NAE_FORMANT_MAX_GAIN 16.0f /* formant preservation: largest envelope gain of a bin ("Formant preservation") */
+/* formant shift ("Formant shift"): the range of formant_ratio, +-24 semitones */
+#define NAE_FORMANT_SHIFT_MIN 0.25
+#define NAE_FORMANT_SHIFT_MAX 4.0
 /* transient preservation ("Transient preservation"): bin k of frame f rises iff P_f[k] > RISE * P_{f-1}[k] and
  * P_f[k] > FLOOR * N; frame f is "high" iff DEN * (rising bins) >= NUM * (N/2 + 1); an onset is an upward crossing of "high" at f >= 2.
  * RISE is +6 dB: at +3 dB steady white noise crosses 3/8 at N = 512 and 1024 (DESIGN.md gives the numbers). */

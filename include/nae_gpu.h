@@ -38,7 +38,8 @@ extern "C" {
  *   vocoder); nae_stretch_plan_make_n, nae_stretch_block_n_f32, nae_debug_pv_tile_phase_n and nae_stretch_create_n (vocoder frame sizes
  *   512 ... 4096); nae_stretch_formant_lifter, nae_stretch_block_formant_f32 and nae_stretch_create_formant (formant-preserving pitch
  *   shift); NAE_STRETCH_TRANSIENTS with the _n and _formant entries (transient preservation), which a caller probes for by its return code:
- *   a library without it answers NAE_ERR_INVALID. */
+ *   a library without it answers NAE_ERR_INVALID; nae_stretch_plan_make_shift, nae_stretch_block_formant_shift_f32 and
+ *   nae_stretch_create_formant_shift (formant shift independent of the pitch). */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -292,6 +293,31 @@ int nae_stretch_block_formant_f32(nae_ctx* ctx, double rate, double pitch, unsig
                                   const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst);
 int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags,
                                int n_fft, int lifter, nae_stretch** h);
+
+/* Formant shift ("Formant shift"): the output's spectral envelope is the input's scaled in frequency by formant_ratio (phi > 0),
+ * E_out(f) = E_in(f / phi), with or without a pitch change; phi = 1 is formant preservation.  The gain rule is the _formant entries' with the
+ * ratio g = (float)(plan.rate_eff / phi).  The envelope stage runs when lifter > 0 and |plan.rate_eff / phi - 1| >= 1e-6; otherwise the call is
+ * the _n call with the same flags, bit for bit (lifter == 0 is exactly the _n call, whatever the valid phi).  Four cases:
+ *   A  a pitch change (vocoder and transposer): the formant pass with the new g, locked or not;
+ *   B  a tempo change only (rate_eff = 1, e.g. rate = 1 / pitch): the same pass with g = 1 / phi;
+ *   C  a rate change only (pitch = 1): the vocoder stage is forced on at tempo 1 and runs with the transposer in the usual order (transposer
+ *      first when rate_eff > 1);
+ *   D  neither (rate pitch = 1, pitch = 1): the forced stage alone, out_len = in_len.
+ * The forced stage is an STFT pass — analysis, Y = G X, c2r, Hann, overlap-add, gain 2/3; the synthesis phase equals the analysis phase in every
+ * frame, so NAE_STRETCH_PHASE_LOCK (1024) and NAE_STRETCH_TRANSIENTS are accepted and change nothing there.  nae_stretch_plan_make_shift is the
+ * plan: nae_stretch_plan_make_n's, and in cases C and D with the stage on pv_on = 1, tempo_eff = 1, ha_q24 = (n_fft / 4) << 24,
+ * d0 = n_fft / 4, r_q24[0] = 2^24 and the frame count of the usual formula; out_len, mid_len, rs_first and the transposer are unchanged.
+ * With phi = 1 cases A, B and D give the _formant call's bits.  Case C differs: the _formant entries do nothing without a pitch change, so
+ * there they are a plain resampling (the formants move with the rate), while this entry with phi = 1 runs the envelope stage and keeps the
+ * formants in place.  Flags, n_fft and lifter follow the _formant entries' rules.  phi not finite or <= 0: NAE_ERR_INVALID; outside
+ * [NAE_FORMANT_SHIFT_MIN, NAE_FORMANT_SHIFT_MAX] = [0.25, 4] (+-24 semitones): NAE_ERR_UNSUPPORTED; phi is checked whatever the lifter.  The
+ * cap NAE_FORMANT_MAX_GAIN stays.  Samples follow the tolerance path against tests/pv_fshift/ref_pv_fs.c; the result is independent of the
+ * tiling, and a handle's output equals the block call's. */
+int nae_stretch_plan_make_shift(double rate, double pitch, double formant_ratio, int lifter, int n_fft, size_t in_len, nae_stretch_plan* plan);
+int nae_stretch_block_formant_shift_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, int lifter, double formant_ratio,
+                                        const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst);
+int nae_stretch_create_formant_shift(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
+                                     double formant_ratio, nae_stretch** h);
 
 /* NAE_STRETCH_TRANSIENTS: transient preservation ("Transient preservation"), a flag of the _n and _formant entries
  * (nae_stretch_block_n_f32, nae_stretch_create_n, nae_debug_pv_tile_phase_n, nae_stretch_block_formant_f32, nae_stretch_create_formant) at

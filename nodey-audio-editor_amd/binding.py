@@ -26,7 +26,8 @@ EXPORTED_SYMBOLS = [
     "nae_to_f32_interleaved", "nae_clamp_f32", "nae_stretch_plan_make", "nae_stretch_block_f32",
     "nae_debug_pv_tile_phase", "nae_stretch_block_ex_f32", "nae_debug_pv_tile_phase_ex", "nae_stretch_create_ex",
     "nae_stretch_plan_make_n", "nae_stretch_block_n_f32", "nae_debug_pv_tile_phase_n", "nae_stretch_create_n",
-    "nae_stretch_formant_lifter", "nae_stretch_block_formant_f32", "nae_stretch_create_formant", "nae_stretch_create", "nae_stretch_put", "nae_stretch_put_host", "nae_stretch_flush",
+    "nae_stretch_formant_lifter", "nae_stretch_block_formant_f32", "nae_stretch_create_formant",
+    "nae_stretch_plan_make_shift", "nae_stretch_block_formant_shift_f32", "nae_stretch_create_formant_shift", "nae_stretch_create", "nae_stretch_put", "nae_stretch_put_host", "nae_stretch_flush",
     "nae_stretch_available", "nae_stretch_receive", "nae_stretch_receive_host", "nae_stretch_destroy",
     "nae_swr_create", "nae_swr_convert_host", "nae_swr_convert", "nae_swr_buffered", "nae_swr_destroy", "nae_mono_to_stereo_f32",
     "nae_spectrum_frames", "nae_spectrum_block_f32", "nae_spectrum_frames_ex", "nae_spectrum_block_ex_f32", "nae_spectrum_create", "nae_spectrum_put",
@@ -38,6 +39,7 @@ EXPORTED_SYMBOLS = [
 
 STRETCH_PHASE_LOCK = 1       # NAE_STRETCH_PHASE_LOCK (include/nae_gpu.h)
 STRETCH_TRANSIENTS = 4       # NAE_STRETCH_TRANSIENTS (include/nae_gpu.h): the _n and _formant entries only
+FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX = 0.25, 4.0   # NAE_FORMANT_SHIFT_MIN / _MAX (include/nae_dsp_spec.h): the range of formant_ratio
 
 
 class NaeError(RuntimeError):
@@ -153,6 +155,9 @@ def load_library() -> C.CDLL:
         "nae_stretch_formant_lifter": (i, [i, i]),
         "nae_stretch_block_formant_f32": (i, [vp, d, d, u, i, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_stretch_create_formant": (i, [vp, i, i, f, f, u, i, i, P(vp)]),
+        "nae_stretch_plan_make_shift": (i, [d, d, d, i, i, sz, P(StretchPlan)]),
+        "nae_stretch_block_formant_shift_f32": (i, [vp, d, d, u, i, i, d, P(Sig), sz, i, sz, P(Sig)]),
+        "nae_stretch_create_formant_shift": (i, [vp, i, i, f, f, u, i, i, d, P(vp)]),
         "nae_stretch_create": (i, [vp, i, i, f, f, P(vp)]), "nae_stretch_put": (i, [vp, vp, sz]),
         "nae_stretch_put_host": (i, [vp, vp, sz]), "nae_stretch_flush": (i, [vp]),
         "nae_stretch_available": (sz, [vp]), "nae_stretch_receive": (i, [vp, vp, sz, P(sz)]),
@@ -423,10 +428,14 @@ class Context:
 
     # -- K7
     @staticmethod
-    def stretch_plan(rate: float, pitch: float, in_len: int, n_fft: int = 1024) -> StretchPlan:
-        """n_fft: vocoder frame size 512 / 1024 / 2048 / 4096 (1024 calls nae_stretch_plan_make)"""
+    def stretch_plan(rate: float, pitch: float, in_len: int, n_fft: int = 1024, formant: int = 0,
+                     formant_ratio: Optional[float] = None) -> StretchPlan:
+        """n_fft: vocoder frame size 512 / 1024 / 2048 / 4096 (1024 calls nae_stretch_plan_make); formant_ratio: the plan of the formant
+        shift with lifter `formant` (nae_stretch_plan_make_shift)"""
         pl = StretchPlan()
-        if n_fft == 1024:
+        if formant_ratio is not None:
+            rc = load_library().nae_stretch_plan_make_shift(rate, pitch, formant_ratio, formant, n_fft, in_len, C.byref(pl))
+        elif n_fft == 1024:
             rc = load_library().nae_stretch_plan_make(rate, pitch, in_len, C.byref(pl))
         else:
             rc = load_library().nae_stretch_plan_make_n(rate, pitch, n_fft, in_len, C.byref(pl))
@@ -435,11 +444,16 @@ class Context:
         return pl
 
     def stretch_block(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig,
-                      phase_lock: bool = False, n_fft: int = 1024, formant: int = 0, transients: bool = False):
+                      phase_lock: bool = False, n_fft: int = 1024, formant: int = 0, transients: bool = False,
+                      formant_ratio: Optional[float] = None):
         """formant: the lifter of formant preservation (formant_lifter() gives the default), 0 = off; transients: transient preservation
-        (nae_stretch_block_n_f32 at every size)"""
+        (nae_stretch_block_n_f32 at every size); formant_ratio: the formant shift with that lifter (nae_stretch_block_formant_shift_f32;
+        dst receives stretch_plan(..., formant=, formant_ratio=).out_len frames)"""
         flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0)
-        if formant:
+        if formant_ratio is not None:
+            self._ck(self.lib.nae_stretch_block_formant_shift_f32(self.h, rate, pitch, flags, n_fft, formant, formant_ratio,
+                                                                  C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+        elif formant:
             self._ck(self.lib.nae_stretch_block_formant_f32(self.h, rate, pitch, flags, n_fft, formant,
                                                             C.byref(src), in_len, ch, n_streams, C.byref(dst)))
         elif n_fft != 1024 or transients:
@@ -516,13 +530,17 @@ def formant_lifter(sample_rate: int, n_fft: int = 1024) -> int:
 
 class Stretcher:
     """The SoundTouch-shaped streaming handle (nae_stretch_create_ex; nae_stretch_create_n for an n_fft other than 1024;
-    nae_stretch_create_formant with a formant lifter): put interleaved f32, flush, receive."""
+    nae_stretch_create_formant with a formant lifter; nae_stretch_create_formant_shift with a formant_ratio): put interleaved f32, flush,
+    receive."""
 
     def __init__(self, ctx: Context, sample_rate: int, channels: int, rate: float, pitch: float, phase_lock: bool = False,
-                 n_fft: int = 1024, formant: int = 0, transients: bool = False):
+                 n_fft: int = 1024, formant: int = 0, transients: bool = False, formant_ratio: Optional[float] = None):
         self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
         flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0)
-        if formant:
+        if formant_ratio is not None:
+            ctx._ck(ctx.lib.nae_stretch_create_formant_shift(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, formant, formant_ratio,
+                                                             C.byref(self.h)))
+        elif formant:
             ctx._ck(ctx.lib.nae_stretch_create_formant(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, formant, C.byref(self.h)))
         elif n_fft != 1024 or transients:
             ctx._ck(ctx.lib.nae_stretch_create_n(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, C.byref(self.h)))

@@ -18,73 +18,9 @@
 // the segmented scan.  Waves per workgroup: pass 1 8 / 8 / 7 / 3 at N = 512 ... 4096, pass 3 8 / 8 / 5 / 2 (with formants 8 / 8 / 4 / 2).
 // N = 1024 runs the shipped passes 1 and 3 unless the debug key pv_any (or, pass 3, a lifter; or transients) asks for these: nae_pv_route_of.  The host
 // decisions (records needed, base records, synthesis fields, workspace) are kernels_stft.hip's nae_launch_pv_phase / nae_launch_pv_synth.
-#include "pv_roles.h"
-#include "fft_any.h"
-#include <type_traits>
+#include "pv_any.h"
 
 namespace nae {
-
-template <int N, bool kFormant = false, bool kTransient = false>
-struct PvAny {
-    static constexpr int M = N / 2, H = N / 4, B = M + 1;
-    static constexpr int PAD = (B + 7) & ~7;              // int32 per record: 520 at N = 1024, as the shipped kernels
-    static constexpr int SH = 32 - ilog2c(N);             // a bin's phase advance per sample, in Q0.32: 2^SH
-    static constexpr int NB = M / 64 + 1;                 // bins per lane: k = lane + 64 r; r = NB - 1 is bin M (lane 0)
-    static constexpr int JQ = N / 512;                    // sample pairs per lane in each quarter (hop block) of a frame
-    static constexpr int K = 2 * JQ;                      // samples per lane in each hop block
-    using Gm = FftGeom<M, 1>;
-    static constexpr int ST = NB * 64;                    // uint32 per per-bin state array of a wave
-    static constexpr size_t kWave1 = Gm::SCR * sizeof(cf) + 2 * ST * sizeof(uint32_t)                     // scratch, Qa_{f-1}, sum
-                                   + (kTransient ? ST * sizeof(float) : 0);                                // transients: P_{f-1}
-    static constexpr size_t kWave3 = Gm::SCR * sizeof(cf) + PAD * sizeof(cf) + 2 * ST * sizeof(uint32_t) // scratch, Y, Qa_{f-1}, Qs
-                                   + (kFormant ? PAD * sizeof(float) : 0)                                  // formant: L / c' / Ls
-                                   + (kTransient ? ST * sizeof(float) : 0);                                // transients: P_{f-1}
-    static constexpr int kMaxWaves1 = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave1);
-    static constexpr int kMaxWaves3 = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave3);
-    static constexpr int kWaves1 = kMaxWaves1 < 8 ? kMaxWaves1 : 8;   // 8, 8, 8, 4 waves per workgroup at N = 512 ... 4096 (transients: 8, 8, 7, 3)
-    static constexpr int kWaves3 = kMaxWaves3 < 8 ? kMaxWaves3 : 8;   // 8, 8, 6, 3 (formant: 8, 8, 5, 2; transients: 8, 8, 5, 2; both: 8, 8, 4, 2)
-    // pass-3 waves a CU holds: whole workgroups by LDS (16, 8, 6, 3 at N = 512 ... 4096, formant 16, 8, 5, 2; registers allow as many; transients
-    // 16, 8, 5, 2; formant and transients 16, 8, 4, 2)
-    static constexpr int kResident3 = (int)((160 * 1024) / (512 * sizeof(cf) + kWaves3 * kWave3)) * kWaves3;
-    static_assert(N >= 512 && N <= 4096 && (N & (N - 1)) == 0, "vocoder sizes 512 ... 4096");
-    static_assert(kWaves1 >= 1 && kWaves3 >= 1, "a wave's state fits a CU's LDS");
-};
-
-template <int N>
-__device__ __forceinline__ long long pva_frame_start(const PvParams& p, long long f)
-{
-    return (((f - 1) * p.ha_q24 + (1ll << (NAE_HA_FRAC_BITS - 1))) >> NAE_HA_FRAC_BITS) - N / 2;
-}
-
-// one frame: window, canonical FFT of M packed points into the wave's scratch (zero outside [0, in.len))
-template <int N, bool kUnit>
-__device__ __forceinline__ void pva_analyse(cf* scr, const cf* w512l, const SpecAnyTables& tb, const ChanView& in, long long s, int lane)
-{
-    using Gm = typename PvAny<N>::Gm;
-    const bool interior = s >= 0 && s + N <= in.len;       // wave-uniform
-    auto get = [&](int m) -> cf {
-        const float2 h = *reinterpret_cast<const float2*>(tb.hann + 2 * m);
-        const long long i0 = s + 2 * m;
-        float x0, x1;
-        if (interior) {
-            if (kUnit) {
-                const f2u x = *reinterpret_cast<const f2u*>(in.p + i0);
-                x0 = x.x;
-                x1 = x.y;
-            } else {
-                x0 = in.p[i0 * in.fs];
-                x1 = in.p[(i0 + 1) * in.fs];
-            }
-        } else {
-            x0 = (i0 >= 0 && i0 < in.len) ? in.p[i0 * in.fs] : 0.0f;
-            x1 = (i0 + 1 >= 0 && i0 + 1 < in.len) ? in.p[(i0 + 1) * in.fs] : 0.0f;
-        }
-        return cf{x0 * h.x, x1 * h.y};
-    };
-    any_first_pass_from<Gm>(scr, w512l, tb.wm, lane, get);
-    any_passes8<Gm, (Gm::M / Gm::R1)>(scr, w512l, lane);
-    wave_lds_sync();
-}
 
 // canonical phase of bin k: atan2_q32 below N/2, the sign of the real part at N/2
 template <int N>
@@ -321,76 +257,6 @@ __global__ __launch_bounds__(64 * kScanChunks) void pv_scan_chunked_kernel(uint3
 }
 
 // ------------------------------------------------------------------------------------------------ pass 3
-// hop block `be` of the tile: this lane's samples 2 (lane + 64 jj) + {0, 1} of the block, stored below mid_len
-template <int N>
-__device__ __forceinline__ void pva_store_block(const PvParams& p, long long b0, long long b_end, float* optr, long long fs, long long be,
-                                                const float (&o)[PvAny<N>::K], int lane)
-{
-    using P = PvAny<N>;
-    if (be < b0 || be >= b_end) return;                    // wave-uniform
-    const long long n0 = be * P::H;
-#pragma unroll
-    for (int i = 0; i < P::K; i++) {
-        const long long n = n0 + 2 * (lane + 64 * (i >> 1)) + (i & 1);
-        if (n < p.mid_len) optr[n * fs] = o[i];
-    }
-}
-
-// c2r input point m of a real half spectrum R[0..M] (the synthesis's split with T_N, conjugated; pass 3's zc with Y = R + 0i)
-template <int M>
-__device__ __forceinline__ cf pva_c2r_real_point(const float* rs, const cf* tn, int m)
-{
-    const cf xk = {rs[m], 0.0f}, xm = {rs[M - m], 0.0f};
-    const cf E = {0.5f * (xk.x + xm.x), 0.5f * (xk.y - xm.y)};
-    const cf D = {0.5f * (xk.x - xm.x), 0.5f * (xk.y + xm.y)};
-    const cf T = tn[m];
-    const cf Q = {T.x * D.x + T.y * D.y, T.x * D.y - T.y * D.x};   // conj(T) D
-    return cf{E.x - Q.y, -(E.y + Q.x)};
-}
-
-// formant preservation ("Formant preservation"), steps 2-5 of one frame: lb[k] = L[k] (k <= M) on entry, ys = the synthesis
-// spectrum.  The cepstrum c = c2r_N(L), lifted to n < q and n > N - q, goes back into lb (c[n] at lb[n], c[N - j] at lb[M - j]: q <= N/4, so the
-// two ranges do not meet); the envelope Ls = Re r2c_N(c') replaces it; then Y[k] *= G[k] = min(2^(Ls(k g) - Ls[k]), NAE_FORMANT_MAX_GAIN).
-template <int N>
-__device__ __forceinline__ void pva_formant(cf* scr, const cf* w512l, const SpecAnyTables& tb, cf* ys, float* lb, int q, float g, int lane)
-{
-    using Gm = typename PvAny<N, true>::Gm;
-    constexpr int M = N / 2;
-    any_first_pass_from<Gm>(scr, w512l, tb.wm, lane, [&](int m) { return pva_c2r_real_point<M>(lb, tb.tn, m); });
-    any_passes8<Gm, (Gm::M / Gm::R1)>(scr, w512l, lane);
-    wave_lds_sync();
-#pragma unroll 1
-    for (int t = lane; t < M; t += 64) {
-        const int n = t < q ? t : (t > M - q ? t + M : -1);
-        if (n >= 0) {
-            const cf z = lds_ld(scr + padx(zpos<Gm>(n >> 1)));
-            lb[t] = (n & 1) ? -z.y * (1.0f / M) : z.x * (1.0f / M);
-        }
-    }
-    wave_lds_sync();
-    auto lifted = [&](int n) -> float { return n < q ? lb[n] : (n > N - q ? lb[n - M] : 0.0f); };
-    any_first_pass_from<Gm>(scr, w512l, tb.wm, lane, [&](int m) { return cf{lifted(2 * m), lifted(2 * m + 1)}; });
-    any_passes8<Gm, (Gm::M / Gm::R1)>(scr, w512l, lane);
-    wave_lds_sync();
-#pragma unroll 1
-    for (int k = lane; k <= M; k += 64) lb[k] = any_rfft_bin<Gm>(scr, tb.tn, k).x;
-    wave_lds_sync();
-#pragma unroll 1
-    for (int k = lane; k <= M; k += 64) {
-        const float u = (float)k * g;
-        float G = 0.0f;
-        if (u <= (float)M) {
-            const int i = (int)u;
-            const float t = u - (float)i;
-            const float lu = i == M ? lb[M] : lb[i] + t * (lb[i + 1] - lb[i]);
-            G = fminf(__builtin_amdgcn_exp2f(lu - lb[k]), NAE_FORMANT_MAX_GAIN);
-        }
-        const cf y = ys[k];
-        ys[k] = cf{G * y.x, G * y.y};
-    }
-    wave_lds_sync();
-}
-
 // kFormant: formant preservation with lifter `lifter` and transposer ratio g (nae_stretch_block_formant_f32); off, both are unused.
 // kTransient: an onset frame takes Qs = Qa ("Transient preservation"); frames b0 - 2 and b0 - 1 prime P and "high".
 template <int N, bool kUnit, bool kFormant, bool kTransient = false>
@@ -594,19 +460,6 @@ static int launch_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, lo
     NAE_KLAUNCH(ctx, name, (unit_stride ? pv_any_synth_kernel<N, true, kFormant, kTransient> : pv_any_synth_kernel<N, false, kFormant, kTransient>),
                 dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream, src, p, items, phase_ws, out, tb, lifter, g);
     return nae_check(ctx, hipGetLastError(), name);
-}
-
-// f(std::integral_constant<int, N>()) at the vocoder size N = n_fft
-template <typename F>
-static int at_size(nae_ctx* ctx, int n_fft, F&& f)
-{
-    switch (n_fft) {
-    case 512: return f(std::integral_constant<int, 512>());
-    case 1024: return f(std::integral_constant<int, 1024>());
-    case 2048: return f(std::integral_constant<int, 2048>());
-    case 4096: return f(std::integral_constant<int, 4096>());
-    default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
-    }
 }
 
 } // namespace nae

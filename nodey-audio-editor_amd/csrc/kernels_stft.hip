@@ -545,6 +545,7 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
                         size_t n_streams, int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg)
 {
     if (tile <= 0 || synth_tile < tile || synth_tile % tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
+    if (nae_plan_forced(*pl)) return NAE_OK;   // the envelope pass carries no phase
     PvParams p = make_pv_params(*pl, in_len, ch, tile, seg);
     const long long n_sc = (long long)n_streams * ch;
     if (n_sc * p.n_tiles == 0) return NAE_OK;
@@ -598,14 +599,15 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
 }
 
 // pass 3 (locked: L3) from the records of pass 2 (or, one tile and nothing carried in, from zero), on the kernels nae_pv_route_of says; lifter > 0
-// with both stages on: formant preservation
+// with the envelope stage on (nae_formant_lifter_eff): formant preservation, or with formant_ratio != 1 the formant shift; a forced plan runs the
+// envelope pass alone
 int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
-                        const nae_pv_segment* seg, int frames_per_step, int lifter)
+                        const nae_pv_segment* seg, int frames_per_step, int lifter, double formant_ratio)
 {
     if (phase_tile <= 0 || tile < phase_tile || tile % phase_tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
     PvParams p = make_pv_params(*pl, in_len, ch, tile, seg);
-    lifter = nae_formant_lifter_eff(*pl, lifter);
+    lifter = nae_formant_lifter_eff(*pl, lifter, formant_ratio);
     const long long cnt = p.f_stop - p.f_origin;
     p.phase_step = tile / phase_tile;
     p.phase_tiles = (int)((cnt + phase_tile - 1) / phase_tile);
@@ -616,10 +618,11 @@ int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
         p.carry_frame = p.f_stop - 1;
     }
     const long long n_sc = (long long)n_streams * ch;
-    const float g = (float)pl->rate_eff;                   // formant preservation: the transposer ratio
+    const float g = nae_formant_g(*pl, formant_ratio);     // formant preservation: the transposer ratio (over the formant shift)
     const bool unit_stride = src->frame_stride == 1;
     const bool transients = seg && seg->transients;
-    const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, lifter, transients).pass3;
+    const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, lifter, transients, nae_plan_forced(*pl)).pass3;
+    if (pass3 == PvKernels::kEnv) return nae_launch_pvenv(ctx, n_fft, p, to_view(src), n_sc, unit_stride, to_out(out), lifter, g);
     if (pass3 == PvKernels::kLock)
         return nae_launch_pvlock_synth(ctx, p, to_view(src), n_sc, unit_stride, phase_ws, to_out(out), lifter, g, transients);
     if (pass3 == PvKernels::kAny)

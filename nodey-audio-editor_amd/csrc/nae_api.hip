@@ -4,6 +4,7 @@
 #include "nae_internal.h"
 #include <string>
 #include <initializer_list>
+#include <cmath>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -511,15 +512,24 @@ int nae_stretch_plan_make(double rate, double pitch, size_t in_len, nae_stretch_
 // everything else does not
 int nae_stretch_plan_make_n(double rate, double pitch, int n_fft, size_t in_len, nae_stretch_plan* pl)
 {
+    return nae_stretch_plan_make_shift(rate, pitch, 1.0, 0, n_fft, in_len, pl);
+}
+
+// the plan of the _formant_shift entries ("Formant shift"): the _n plan, with the vocoder stage forced on (tempo_eff = 1: ha = H,
+// d0 = H, r = 2^24) when the envelope stage runs (nae_formant_stage_on) and the tempo is 1.  lifter = 0 is the _n plan.
+int nae_stretch_plan_make_shift(double rate, double pitch, double formant_ratio, int lifter, int n_fft, size_t in_len, nae_stretch_plan* pl)
+{
     if (!pl) return NAE_ERR_INVALID;
     memset(pl, 0, sizeof *pl);
     if (!nae_pv_size_ok(n_fft)) return NAE_ERR_UNSUPPORTED;
     const int hop = n_fft / 4;
     if (!(rate > 0.0) || !(pitch > 0.0)) return NAE_ERR_INVALID;
+    if (!std::isfinite(formant_ratio) || !(formant_ratio > 0.0) || lifter < 0 || lifter > n_fft / 4) return NAE_ERR_INVALID;
+    if (formant_ratio < NAE_FORMANT_SHIFT_MIN || formant_ratio > NAE_FORMANT_SHIFT_MAX) return NAE_ERR_UNSUPPORTED;
     double tempo = 1.0 / pitch, rho = rate * pitch;
     if (fabs(tempo - 1.0) < 1e-6) tempo = 1.0;
     if (fabs(rho - 1.0) < 1e-6) rho = 1.0;
-    pl->pv_on = tempo != 1.0;
+    pl->pv_on = tempo != 1.0 || nae_formant_stage_on(rho, lifter, formant_ratio);
     pl->rs_on = rho != 1.0;
     if (pl->pv_on && (tempo < NAE_TEMPO_MIN || tempo > NAE_TEMPO_MAX)) return NAE_ERR_UNSUPPORTED;
     if (pl->rs_on && (rho < NAE_RATE_MIN || rho > NAE_RATE_MAX)) return NAE_ERR_UNSUPPORTED;
@@ -600,15 +610,17 @@ struct nae_mix_front {
 // context's workspace between them).
 static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
                               const nae_sig* dst, const nae_mix_front* front, int stages = 3, bool lock = false, int n_fft = NAE_FFT_N,
-                              int lifter = 0, bool transients = false)
+                              int lifter = 0, bool transients = false, const double* formant_ratio = nullptr)
 {
     if (!ctx) return NAE_ERR_INVALID;
     int rc;
     if ((rc = check_sig(ctx, src, "null source view")) || (rc = check_sig(ctx, dst, "null destination view"))) return rc;
     if (ch < 1 || ch > 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
+    // the _formant_shift entry (formant_ratio given): its own plan, with the vocoder stage forced on for a shift at tempo 1
     nae_stretch_plan pl;
-    rc = nae_stretch_plan_make_n(rate, pitch, n_fft, in_len, &pl);
-    if (rc) return nae_fail(ctx, rc, "rate/pitch outside the supported range");
+    const double phi = formant_ratio ? *formant_ratio : 1.0;
+    rc = formant_ratio ? nae_stretch_plan_make_shift(rate, pitch, phi, lifter, n_fft, in_len, &pl) : nae_stretch_plan_make_n(rate, pitch, n_fft, in_len, &pl);
+    if (rc) return nae_fail(ctx, rc, formant_ratio ? "rate/pitch/formant ratio outside the supported range" : "rate/pitch outside the supported range");
     // the mix node in front: fused into the transposer when that runs first, else its own launch (src = its output)
     bool mix_pending = front != nullptr && (stages & 1);
     auto run_mix = [&]() -> int {
@@ -661,22 +673,26 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
     if (pl.pv_on) {
         int phase_tile = 0, fps = 1;
         int tile;
-        const int q = nae_formant_lifter_eff(pl, lifter);
-        const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, q, transients).pass3;
-        if (pass3 == PvKernels::kLock)   // four waves per SIMD, tiles of at least 64 frames (pv_min_ptile does not apply)
+        const int q = nae_formant_lifter_eff(pl, lifter, phi);
+        const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, q, transients, nae_plan_forced(pl)).pass3;
+        if (pass3 == PvKernels::kEnv)    // no pass 1: one tile rule, the kernel's own residency
+            tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, (size_t)nae_pvenv_resident(ctx, n_fft),
+                                               ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64);
+        else if (pass3 == PvKernels::kLock)   // four waves per SIMD, tiles of at least 64 frames (pv_min_ptile does not apply)
             tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, 16, 64);
         else if (pass3 == PvKernels::kAny)
             tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, (size_t)nae_pv_resident3(ctx, n_fft, q > 0, transients),
                                                ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64);
         else tile = nae_pick_pv_shape(ctx, pl.frames, n_streams * ch, &phase_tile, &fps);
-        rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, n_fft, pl.frames, ch, n_streams, phase_tile));
+        if (pass3 != PvKernels::kEnv)    // the envelope pass has no phase workspace
+            rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, n_fft, pl.frames, ch, n_streams, phase_tile));
         if (rc) return rc;
         nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, pv_out_len, nullptr, nullptr};
         seg.transients = transients;
         rc = nae_launch_pv_phase(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, phase_tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
         if (rc) return rc;
         rc = nae_launch_pv_synth(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, tile, phase_tile, static_cast<const uint32_t*>(ctx->ws_phase), pv_dst,
-                                 &seg, fps, q);
+                                 &seg, fps, lifter, phi);
         if (rc) return rc;
     }
     if (pl.rs_on && !pl.rs_first) {
@@ -731,6 +747,17 @@ int nae_stretch_block_formant_f32(nae_ctx* ctx, double rate, double pitch, unsig
     if ((rc = nae_formant_check(ctx, n_fft, lifter))) return rc;
     return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft, lifter,
                               (flags & NAE_STRETCH_TRANSIENTS) != 0);
+}
+
+int nae_stretch_block_formant_shift_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, int lifter, double formant_ratio,
+                                        const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst)
+{
+    if (!ctx) return NAE_ERR_INVALID;
+    int rc = nae_stretch_n_check(ctx, flags, n_fft);
+    if (rc) return rc;
+    if ((rc = nae_formant_check(ctx, n_fft, lifter))) return rc;
+    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft, lifter,
+                              (flags & NAE_STRETCH_TRANSIENTS) != 0, &formant_ratio);
 }
 
 int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch,

@@ -120,9 +120,24 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
                         size_t n_streams, int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg);
 int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
-                        const nae_pv_segment* seg, int frames_per_step, int lifter = 0);
-// the lifter pass 3 runs with: formant preservation applies only when the plan runs both the vocoder and the transposer
-inline int nae_formant_lifter_eff(const nae_stretch_plan& pl, int lifter) { return pl.pv_on && pl.rs_on ? lifter : 0; }
+                        const nae_pv_segment* seg, int frames_per_step, int lifter = 0, double formant_ratio = 1.0);
+// the lifter pass 3 runs with ("Formant shift"): the envelope stage runs on the vocoder's frames when the envelope's ratio
+// rate_eff / formant_ratio is not 1.  With formant_ratio = 1 (the _formant entries) that is a plan with both the vocoder and the transposer
+// (rate_eff is snapped to 1 within 1e-6); the _formant_shift entries' plan (nae_stretch_plan_make_shift) has the vocoder stage forced on where
+// the stage runs at tempo 1.
+inline bool nae_formant_stage_on(double rate_eff, int lifter, double formant_ratio)
+{
+    const double r = rate_eff / formant_ratio - 1.0;
+    return lifter > 0 && (r <= -1e-6 || r >= 1e-6);
+}
+inline int nae_formant_lifter_eff(const nae_stretch_plan& pl, int lifter, double formant_ratio = 1.0)
+{
+    return pl.pv_on && nae_formant_stage_on(pl.rate_eff, lifter, formant_ratio) ? lifter : 0;
+}
+// the transposer ratio g of the gain rule: one rounding of rate_eff / formant_ratio (at formant_ratio = 1, (float)rate_eff)
+inline float nae_formant_g(const nae_stretch_plan& pl, double formant_ratio) { return (float)(pl.rate_eff / formant_ratio); }
+// a plan with the vocoder stage forced on at tempo 1 (nae_stretch_plan_make_shift): Qs = Qa in every frame, the stage is the envelope pass alone
+inline bool nae_plan_forced(const nae_stretch_plan& pl) { return pl.pv_on && pl.tempo_eff == 1.0; }
 // The kernels a vocoder call runs, for the tile choice of a block call, nae_launch_pv_phase and nae_launch_pv_synth:
 //   pass 1  kShipped: pv_phase_kernel (1024 points); kAny: pv_any_phase_kernel<N> (kernels_pv_any.hip); kLock: pvlock_map_kernel and its scan;
 //   pass 3  kShipped: the pipeline (kernels_pvpipe.hip);  kAny: pv_any_synth_kernel<N>;                   kLock: pvlock_synth_kernel.
@@ -131,10 +146,13 @@ inline int nae_formant_lifter_eff(const nae_stretch_plan& pl, int lifter) { retu
 // the size-generic pass 3: the pipeline has no formant stage, and the two passes share the record layout.  Unlocked calls with transient
 // preservation run the size-generic passes at every size, 1024 included: the shipped pass 1 and the pipeline have no onset detector; locked
 // ones the transient instantiations of the locked kernels.
-enum class PvKernels { kShipped, kAny, kLock };
+//   kEnv (pass 3 only; a forced plan, nae_plan_forced): pv_env_kernel<N> (kernels_pvenv.hip) — there is no pass 1 and no scan, and the lock and
+//   transient preservation change nothing (Qs = Qa either way).
+enum class PvKernels { kShipped, kAny, kLock, kEnv };
 struct nae_pv_route { PvKernels pass1, pass3; };
-inline nae_pv_route nae_pv_route_of(const nae_ctx* ctx, bool lock, int n_fft, int lifter_eff, bool transients = false)
+inline nae_pv_route nae_pv_route_of(const nae_ctx* ctx, bool lock, int n_fft, int lifter_eff, bool transients = false, bool forced = false)
 {
+    if (forced) return {PvKernels::kEnv, PvKernels::kEnv};
     if (lock) return {PvKernels::kLock, PvKernels::kLock};
     const PvKernels pass1 = n_fft != NAE_FFT_N || ctx->dbg_pv_any || transients ? PvKernels::kAny : PvKernels::kShipped;
     return {pass1, lifter_eff > 0 ? PvKernels::kAny : pass1};
@@ -144,6 +162,7 @@ inline nae_pv_route nae_pv_route_of(const nae_ctx* ctx, bool lock, int n_fft, in
 bool nae_pv_size_ok(int n_fft);
 size_t nae_pv_record_pad(int n_fft);
 int nae_pv_resident3(nae_ctx* ctx, int n_fft, bool formant, bool transients = false);
+int nae_pvenv_resident(nae_ctx* ctx, int n_fft);                    // kernels_pvenv.hip: the waves of pv_env_kernel<n_fft> a CU holds (PvEnv<N>::kResident)
 int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft);   // nae_api.hip: flags and size of the _n entries
 int nae_formant_check(nae_ctx* ctx, int n_fft, int lifter);         // nae_api.hip: the lifter of the _formant entries
 int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t src_len, int ch,

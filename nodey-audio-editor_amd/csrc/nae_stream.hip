@@ -18,6 +18,8 @@ struct nae_stretch {
     int n_fft = NAE_FFT_N;        // vocoder frame size, hop n_fft / 4 (nae_stretch_create_n)
     int lifter = 0;               // formant preservation's lifter, 0 = off (nae_stretch_create_formant)
     bool transients = false;      // NAE_STRETCH_TRANSIENTS (nae_stretch_create_n / _formant)
+    double formant_ratio = 1.0;   // the formant shift (nae_stretch_create_formant_shift); shift: the plan is nae_stretch_plan_make_shift's
+    bool shift = false;
     nae_stretch_plan pl{};        // parameters (in_len = 0)
     DevFifo in;                   // interleaved input, sample-frames
     // phase vocoder
@@ -73,18 +75,19 @@ int stretch_pv_stage(nae_stretch* h, const nae_stretch_plan& pl, const nae_sig& 
     const bool one_tile = ctx->pv_tile <= 0 && count <= 256;
     const int tile = one_tile ? (int)count : (ctx->pv_tile > 0 ? ctx->pv_tile : 64);
     const int fps = one_tile ? 4 : 1;
-    int rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(h->lock, h->n_fft, count, ch, 1, tile));
+    const bool forced = nae_plan_forced(pl);      // the envelope pass: no phase workspace and nothing carried
+    int rc = forced ? NAE_OK : nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(h->lock, h->n_fft, count, ch, 1, tile));
     if (rc) return rc;
-    for (int i = 0; i < 2; i++)
+    for (int i = 0; i < 2 && !forced; i++)
         if (!h->carry[i] && hipMalloc((void**)&h->carry[i], (size_t)ch * nae_pv_record_pad(h->n_fft) * sizeof(uint32_t)) != hipSuccess)
             return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(carry)");
     nae_pv_segment seg{(long long)h->blocks_done, (long long)count, (long long)F_r, limit,
-                       h->blocks_done ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
+                       h->blocks_done && !forced ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
     seg.transients = h->transients;
     rc = nae_launch_pv_phase(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
     if (rc) return rc;
     rc = nae_launch_pv_synth(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps,
-                             h->lifter);
+                             h->lifter, h->formant_ratio);
     if (rc) return rc;
     h->carry_cur ^= 1;
     h->blocks_done = B_r;
@@ -103,10 +106,11 @@ int stretch_process(nae_stretch* h)
     DevFifo &in = h->in, &mid = h->mid, &out = h->out;
     nae_stretch_plan fin{};
     if (h->flushed) {
-        int rc = nae_stretch_plan_make_n(h->rate, h->pitch, h->n_fft, in.total, &fin);
+        int rc = h->shift ? nae_stretch_plan_make_shift(h->rate, h->pitch, h->formant_ratio, h->lifter, h->n_fft, in.total, &fin)
+                          : nae_stretch_plan_make_n(h->rate, h->pitch, h->n_fft, in.total, &fin);
         if (rc) return rc;
     }
-    // ---- neither stage: the node is a wire
+    // ---- neither stage: the node is a wire (a formant shift at tempo 1 has the vocoder stage forced on and does not come here)
     if (!pl.pv_on && !pl.rs_on) {
         if (in.total == out.total) return NAE_OK;
         const int rc = out.push(ctx, in.at(out.total), in.total - out.total, false);
@@ -234,8 +238,24 @@ int nae_stretch_create_n(nae_ctx* ctx, int sample_rate, int channels, float rate
     return nae_stretch_create_formant(ctx, sample_rate, channels, rate, pitch, flags, n_fft, 0, h);
 }
 
+static int stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
+                          const double* formant_ratio, nae_stretch** h);
+
 int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
                                nae_stretch** h)
+{
+    return stretch_create(ctx, sample_rate, channels, rate, pitch, flags, n_fft, lifter, nullptr, h);
+}
+
+int nae_stretch_create_formant_shift(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
+                                     double formant_ratio, nae_stretch** h)
+{
+    return stretch_create(ctx, sample_rate, channels, rate, pitch, flags, n_fft, lifter, &formant_ratio, h);
+}
+
+// formant_ratio given: the _formant_shift entry, with its own plan
+static int stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
+                          const double* formant_ratio, nae_stretch** h)
 {
     if (!ctx || !h) return NAE_ERR_INVALID;
     int chk = nae_stretch_n_check(ctx, flags, n_fft);
@@ -248,8 +268,8 @@ int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, floa
     if (sample_rate != 0 && (sample_rate < 8000 || sample_rate > 48000)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "Unsupported sample rate: requires 8000..48000 Hz");
     if (channels != 1 && channels != 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
     nae_stretch_plan pl;
-    int rc = nae_stretch_plan_make_n(rate, pitch, n_fft, 0, &pl);
-    if (rc) return nae_fail(ctx, rc, "rate/pitch outside the supported range");
+    int rc = formant_ratio ? nae_stretch_plan_make_shift(rate, pitch, *formant_ratio, lifter, n_fft, 0, &pl) : nae_stretch_plan_make_n(rate, pitch, n_fft, 0, &pl);
+    if (rc) return nae_fail(ctx, rc, formant_ratio ? "rate/pitch/formant ratio outside the supported range" : "rate/pitch outside the supported range");
     nae_stretch* s = new (std::nothrow) nae_stretch();
     if (!s) return NAE_ERR_NOMEM;
     s->ctx = ctx;
@@ -258,7 +278,8 @@ int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, floa
     s->rate = rate;
     s->pitch = pitch;
     s->lock = (flags & NAE_STRETCH_PHASE_LOCK) != 0;
-    s->transients = pl.pv_on && (flags & NAE_STRETCH_TRANSIENTS) != 0;
+    s->transients = pl.pv_on && !nae_plan_forced(pl) && (flags & NAE_STRETCH_TRANSIENTS) != 0;   // a forced stage has Qs = Qa: nothing to reset
+    if (formant_ratio) { s->formant_ratio = *formant_ratio; s->shift = true; }
     s->n_fft = n_fft;
     s->lifter = lifter;
     s->pl = pl;

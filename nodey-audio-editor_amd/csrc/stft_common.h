@@ -150,4 +150,7 @@ int nae_launch_pv_scan(nae_ctx* ctx, int n_fft, const char* name, uint32_t* phas
 // lifter > 0 (pass 3): formant preservation with that lifter and transposer ratio g ("Formant preservation"); 0: off
 int nae_launch_pvany_synth(nae_ctx* ctx, int n_fft, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride,
                            const uint32_t* phase_ws, const nae::OutViewD& out, int lifter, float g, bool transients);
+// kernels_pvenv.hip: the envelope pass of a forced plan (formant shift at tempo 1) — analysis, gain with lifter and ratio g, synthesis; no phases
+int nae_launch_pvenv(nae_ctx* ctx, int n_fft, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride,
+                     const nae::OutViewD& out, int lifter, float g);
 

@@ -63,6 +63,25 @@ namespace processor
 		return value["transients"].asBool();
 	}
 
+	float formant_shift_from_json(const Json::Value& value, const char* node_name)
+	{
+		if (!value.isMember("formant_shift")) return 0;
+		if (!value["formant_shift"].isDouble())
+			throw infra::Processor::Runtime_error(
+				"Failed to deserialize JSON file",
+				std::string(node_name) + " failed to serialize the JSON input because of missing or invalid fields.",
+				"Wrong field: formant_shift"
+			);
+		const float semitones = value["formant_shift"].asFloat();
+		if (!(semitones >= -24.0f && semitones <= 24.0f))
+			throw infra::Processor::Runtime_error(
+				"Failed to deserialize JSON file",
+				std::string(node_name) + " accepts a formant shift between -24 and 24 semitones.",
+				"Out of range: formant_shift"
+			);
+		return semitones;
+	}
+
 	int fft_size_from_json(const Json::Value& value, const char* node_name, bool phase_lock)
 	{
 		if (!value.isMember("fft_size")) return 1024;
@@ -212,13 +231,18 @@ namespace processor
 				if (st) nae_wsola_destroy(st);
 			}
 			bool open() const { return pv != nullptr || st != nullptr; }
-			void create(Stretch_algorithm algo, bool phase_lock, int fft_size, bool formant, bool transients, int sample_rate, int channels,
-						float velocity, float pitch)
+			void create(Stretch_algorithm algo, bool phase_lock, int fft_size, bool formant, bool transients, float formant_shift, int sample_rate,
+						int channels, float velocity, float pitch)
 			{
 				const unsigned flags = (phase_lock ? NAE_STRETCH_PHASE_LOCK : 0u) | (transients ? NAE_STRETCH_TRANSIENTS : 0u);
-				// (phase_lock, fft_size, formant and transients are vocoder options: the WSOLA chain has none)
+				// (phase_lock, fft_size, formant, formant_shift and transients are vocoder options: the WSOLA chain has none)
 				if (algo == Stretch_algorithm::Soundtouch)
 					gpu::check(nae_wsola_create(gpu::context(), sample_rate, channels, velocity, pitch, &st), "nae_wsola_create");
+				else if (formant_shift != 0)   // the envelope stage with the default lifter, whether or not "formant" is set
+					gpu::check(nae_stretch_create_formant_shift(gpu::context(), sample_rate, channels, velocity, pitch, flags, fft_size,
+																nae_stretch_formant_lifter(sample_rate, fft_size),
+																std::pow(2.0, (double)formant_shift / 12.0), &pv),
+							   "nae_stretch_create_formant_shift");
 				else if (formant)
 					gpu::check(nae_stretch_create_formant(gpu::context(), sample_rate, channels, velocity, pitch, flags, fft_size,
 														  nae_stretch_formant_lifter(sample_rate, fft_size), &pv),
@@ -244,7 +268,7 @@ namespace processor
 			const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
 			const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
 			const std::atomic<bool>& stop_token, float velocity, float pitch, const std::string& processor_name,
-			Stretch_algorithm algorithm, bool phase_lock, int fft_size, bool formant, bool transients, Batch_stats& batch_stats
+			Stretch_algorithm algorithm, bool phase_lock, int fft_size, bool formant, bool transients, float formant_shift, Batch_stats& batch_stats
 		)
 		{
 			gpu::Node node;  // this node's context (own stream; device: gpu::pick_device): first local, destroyed last
@@ -343,7 +367,7 @@ namespace processor
 									infra::fmt("%d requires a sample rate between 8000 and 48000 Hz.", frame->sample_rate),
 									infra::fmt("Sample rate: %d", frame->sample_rate)
 								);
-							soundtouch.create(algorithm, phase_lock, fft_size, formant, transients, frame->sample_rate, frame->ch_layout.nb_channels, velocity, pitch);
+							soundtouch.create(algorithm, phase_lock, fft_size, formant, transients, formant_shift, frame->sample_rate, frame->ch_layout.nb_channels, velocity, pitch);
 							channel_count = frame->ch_layout.nb_channels;
 							time_seconds = frame->pts * av_q2d(frame->time_base);
 							sample_rate = frame->sample_rate;
@@ -412,7 +436,7 @@ namespace processor
 	)
 	{
 		stretch_process_payload(input, output, stop_token, velocity, keep_pitch ? 1 / velocity : 1, get_processor_info().display_name,
-								algorithm, phase_lock, fft_size, false, transients, batch_stats);  // :452-459
+								algorithm, phase_lock, fft_size, false, transients, 0, batch_stats);  // :452-459
 	}
 
 	Json::Value Velocity_modifier::serialize() const
@@ -452,7 +476,7 @@ namespace processor
 	)
 	{
 		stretch_process_payload(input, output, stop_token, 1, std::pow(2.0f, pitch / 12.0f), get_processor_info().display_name,
-								algorithm, phase_lock, fft_size, formant, transients, batch_stats);  // :469-476
+								algorithm, phase_lock, fft_size, formant, transients, formant_shift, batch_stats);  // :469-476
 	}
 
 	Json::Value Pitch_modifier::serialize() const
@@ -463,6 +487,7 @@ namespace processor
 		if (phase_lock) value["phase_lock"] = true;
 		if (fft_size != 1024) value["fft_size"] = fft_size;
 		if (formant) value["formant"] = true;
+		if (formant_shift != 0) value["formant_shift"] = formant_shift;
 		if (transients) value["transients"] = true;
 		return value;
 	}
@@ -473,6 +498,7 @@ namespace processor
 		phase_lock = phase_lock_from_json(value, "Pitch_modifier");
 		fft_size = fft_size_from_json(value, "Pitch_modifier", phase_lock);
 		formant = formant_from_json(value, "Pitch_modifier");
+		formant_shift = formant_shift_from_json(value, "Pitch_modifier");
 		transients = transients_from_json(value, "Pitch_modifier");
 	}
 

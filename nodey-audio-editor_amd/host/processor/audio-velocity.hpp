@@ -28,6 +28,12 @@ namespace processor
 	// nae_stretch_formant_lifter(sample rate, fft_size)).  No key: false; a value that is not a bool: Runtime_error "Wrong field: formant";
 	// written back only when true.  It combines with "phase_lock" and "fft_size"; with "algorithm": "soundtouch" it is kept and has no effect.
 	bool formant_from_json(const Json::Value& value, const char* node_name);
+	// "formant_shift" (number of semitones, optional, Pitch_modifier only): moves the formants by that much, with or without a pitch change
+	// (nae_stretch_create_formant_shift with formant_ratio 2^(semitones / 12) and the default lifter, whether or not "formant" is set; with
+	// "pitch": 0 the node then runs the envelope stage instead of being a wire).  No key: 0; a value that is not a number: Runtime_error
+	// "Wrong field: formant_shift"; beyond +-24: Runtime_error "Out of range: formant_shift"; written back only when not 0.  It combines with
+	// "phase_lock", "fft_size" and "transients"; with "algorithm": "soundtouch" it is kept and has no effect.
+	float formant_shift_from_json(const Json::Value& value, const char* node_name);
 	// "transients" (bool, optional): transient preservation of the vocoder (NAE_STRETCH_TRANSIENTS: an onset frame resets the synthesis phase).
 	// No key: false; a value that is not a bool: Runtime_error "Wrong field: transients"; written back only when true.  It combines with
 	// "phase_lock", "fft_size" and "formant"; with "algorithm": "soundtouch" it is kept and has no effect.
@@ -68,6 +74,7 @@ namespace processor
 		bool phase_lock = false;
 		int fft_size = 1024;
 		bool formant = false;
+		float formant_shift = 0;  // semitones
 		bool transients = false;
 
 	  public:
@@ -85,7 +92,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock, fft_size, formant, transients when not the default
+		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock, fft_size, formant, formant_shift, transients when not the default
 		void deserialize(const Json::Value& value) override;  // :502-505
 	};
 

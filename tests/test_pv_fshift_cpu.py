@@ -1,0 +1,263 @@
+"""Formant shift independent of the pitch ("Formant shift"), no GPU: the library's plan against the CPU statement
+tests/pv_fshift/ref_pv_fs.c in the four cases (A a pitch change, B a tempo change only, C a rate change only, D neither), limits and error
+codes; the statement against ref_pv_stretch at formant_ratio 1, its forced stage under the lock and transient preservation, and against the
+float64 numpy statement (tests/pv_fs_ref.py); what the shift does to a vowel; the host node's "formant_shift" key and the C ABI's
+declarations."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import node_harness
+import orc
+import pv_fs_ref
+import pv_ref
+from conftest import rel_rms
+from pv_gpu import tone
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOLS = ("nae_stretch_plan_make_shift", "nae_stretch_block_formant_shift_f32", "nae_stretch_create_formant_shift")
+# (rate, pitch) of the four cases; A and C in both stage orders
+CASES = {"A_up": (1.0, 2 ** (4 / 12)), "A_down": (1.0, 2 ** (-5 / 12)), "B": (1.5, 1 / 1.5), "C_down": (0.8, 1.0), "C_up": (1.25, 1.0),
+         "D": (1.0, 1.0)}
+UP, DOWN = 2 ** (4 / 12), 2 ** (-5 / 12)
+
+
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    return pv_fs_ref.build(str(tmp_path_factory.mktemp("ref_pv_fs")))
+
+
+@pytest.mark.parametrize("n_fft", pv_ref.SIZES)
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_plan_is_the_statements(nae, ref, case, n_fft):
+    """nae_stretch_plan_make_shift equals the CPU statement's plan field for field; cases C and D carry the forced stage (pv_on, tempo 1,
+    ha = H << 24, d0 = H, r = 2^24, the usual frame count) with out_len and the transposer as the _n plan has them and mid_len by the stage order"""
+    rate, pitch = CASES[case]
+    q = pv_ref.default_lifter(48000, n_fft)
+    H = n_fft // 4
+    for L in (0, 1, 777, 20000):
+        for phi in (UP, DOWN, 1.0):
+            got = nae.Context.stretch_plan(rate, pitch, L, n_fft, formant=q, formant_ratio=phi)
+            rc, want = pv_fs_ref.plan(ref, rate, pitch, phi, q, n_fft, L)
+            assert rc == 0 and pv_fs_ref.plan_fields(got) == pv_fs_ref.plan_fields(want), (L, phi)
+            plain = nae.Context.stretch_plan(rate, pitch, L, n_fft)
+            forced = case[0] in "CD" and abs(plain.rate_eff / phi - 1.0) >= 1e-6
+            assert (got.pv_on and got.tempo_eff == 1.0) == forced, (L, phi)
+            if forced:
+                assert (got.ha_q24, got.d0, got.r_q24[0]) == (H << 24, H, 1 << 24)
+                pv_out = got.out_len if got.rs_first else got.mid_len
+                assert got.frames == (pv_out + n_fft // 2 + H - 1) // H + 1
+                assert got.rs_first == (plain.rs_on and plain.rate_eff > 1.0)
+                assert (got.rs_on, got.rate_eff, got.step_q32, got.out_len) == (plain.rs_on, plain.rate_eff, plain.step_q32, plain.out_len)
+                # mid_len by the stage order's usual formula: the transposer's output when it runs first, else what it reads
+                assert got.mid_len == (int(np.floor(L / plain.rate_eff + 0.5)) if got.rs_first else plain.mid_len)
+            else:
+                assert pv_fs_ref.plan_fields(got) == pv_fs_ref.plan_fields(plain), (L, phi)
+
+
+def test_plan_without_the_envelope_stage_is_the_n_plan(nae):
+    """lifter 0 with any ratio, and a ratio that cancels the transposer's (rho / phi = 1), give nae_stretch_plan_make_n's plan"""
+    for n_fft in pv_ref.SIZES:
+        for rate, pitch in CASES.values():
+            plain = pv_fs_ref.plan_fields(nae.Context.stretch_plan(rate, pitch, 5000, n_fft))
+            for phi in (0.25, DOWN, 1.0, UP, 4.0):
+                assert pv_fs_ref.plan_fields(nae.Context.stretch_plan(rate, pitch, 5000, n_fft, formant=0, formant_ratio=phi)) == plain
+            rho = nae.Context.stretch_plan(rate, pitch, 5000, n_fft).rate_eff
+            for phi in (rho, rho * (1 + 5e-7)):
+                assert pv_fs_ref.plan_fields(nae.Context.stretch_plan(rate, pitch, 5000, n_fft, formant=17, formant_ratio=phi)) == plain
+
+
+def test_plan_limits_and_error_codes(nae, ref):
+    import ctypes as C
+    lib = nae.load_library()
+    pl = nae.StretchPlan()
+
+    def rc(rate, pitch, phi, q, n_fft, p=pl):
+        return lib.nae_stretch_plan_make_shift(rate, pitch, phi, q, n_fft, 1000, C.byref(p) if p is not None else None)
+
+    INVALID, UNSUPPORTED = -1, -2
+    for phi in (0.0, -1.0, float("nan"), float("inf"), -float("inf")):
+        assert rc(1.0, 1.0, phi, 68, 1024) == INVALID, phi
+        assert rc(1.0, 1.0, phi, 0, 1024) == INVALID, phi
+        assert pv_fs_ref.plan(ref, 1.0, 1.0, phi, 68, 1024, 1000)[0] == -1
+    for phi in (0.2, 0.2499, 4.001, 5.0):
+        assert rc(1.0, 1.0, phi, 68, 1024) == UNSUPPORTED, phi
+        assert pv_fs_ref.plan(ref, 1.0, 1.0, phi, 68, 1024, 1000)[0] == -2
+    for phi in (0.25, 4.0):
+        assert rc(1.0, 1.0, phi, 68, 1024) == 0, phi
+    assert rc(1.0, 1.0, UP, -1, 1024) == INVALID and rc(1.0, 1.0, UP, 257, 1024) == INVALID and rc(1.0, 1.0, UP, 256, 1024) == 0
+    assert rc(1.0, 1.0, UP, 68, 1000) == UNSUPPORTED and rc(0.0, 1.0, UP, 68, 1024) == INVALID and rc(1.0, -1.0, UP, 68, 1024) == INVALID
+    assert rc(1.0, 1.0, UP, 68, 1024, None) == INVALID
+    assert rc(1.0, 100.0, UP, 68, 1024) == UNSUPPORTED          # the tempo limit still holds
+    spec = open(os.path.join(ROOT, "include", "nae_dsp_spec.h")).read()
+    assert re.search(r"#define NAE_FORMANT_SHIFT_MIN 0\.25\b", spec) and re.search(r"#define NAE_FORMANT_SHIFT_MAX 4\.0\b", spec)
+    assert (nae.FORMANT_SHIFT_MIN, nae.FORMANT_SHIFT_MAX) == (0.25, 4.0) == (pv_fs_ref.SHIFT_MIN, pv_fs_ref.SHIFT_MAX)
+
+
+@pytest.mark.parametrize("n_fft", pv_ref.SIZES)
+@pytest.mark.parametrize("case", ["A_up", "A_down", "B", "D"])
+def test_ratio_one_is_the_formant_statement(ref, case, n_fft):
+    """formant_ratio 1 in cases A, B, D: ref_pv_stretch with the same lifter bit for bit (and the lock at 1024)"""
+    rate, pitch = CASES[case]
+    q = pv_ref.default_lifter(48000, n_fft)
+    for ch, x in ((1, orc.fill_uniform(9000, 5)), (2, np.stack([tone(9000), 0.5 * tone(9000)], 1).reshape(-1))):
+        for lock in ((False, True) if n_fft == 1024 else (False,)):
+            got = pv_fs_ref.stretch(ref, x, ch, rate, pitch, 1.0, n_fft, lock=lock, lifter=q)
+            want = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock=lock, lifter=q)
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (ch, lock)
+
+
+@pytest.mark.parametrize("case", ["C_down", "C_up", "D"])
+def test_forced_stage_ignores_lock_and_transients(ref, case):
+    """the forced stage: the recurrence leaves Qs = Qa in every bin of every frame, unlocked, locked and with onset resets, so the lock (1024)
+    and transient preservation give the unflagged stage's bits"""
+    rate, pitch = CASES[case]
+    x = orc.fill_uniform(2 * 12000, 8) * np.repeat((np.arange(12000) % 4000 < 300).astype(np.float32) * 0.95 + 0.05, 2)   # bursts: onsets
+    for n_fft in pv_ref.SIZES:
+        q = pv_ref.default_lifter(48000, n_fft)
+        base = pv_fs_ref.stretch(ref, x, 2, rate, pitch, UP, n_fft, lifter=q)
+        for lock, tr in ((False, True), (True, False), (True, True)):
+            if lock and n_fft != 1024:
+                continue
+            assert pv_fs_ref.forced_phase_diff(ref, x, 2, rate, pitch, UP, n_fft, lock, q, tr) == 0, (n_fft, lock, tr)
+            got = pv_fs_ref.stretch(ref, x, 2, rate, pitch, UP, n_fft, lock=lock, lifter=q, transients=tr)
+            assert np.array_equal(got.view(np.uint32), base.view(np.uint32)), (n_fft, lock, tr)
+        assert pv_fs_ref.forced_phase_diff(ref, x, 2, rate, pitch, UP, n_fft, False, q, False) == 0
+    # a stage that is not forced does move its phases (the counter counts)
+    assert pv_fs_ref.forced_phase_diff(ref, x, 2, 1.0, 2.0, UP, 1024, False, 68, False) > 0
+
+
+NUMPY_CASES = [("A first", 1.0, 2.0), ("A last", 0.25, 2.0), ("B", 0.5, 2.0), ("C last", 0.8, 1.0), ("C first", 1.25, 1.0), ("D", 1.0, 1.0)]
+
+
+@pytest.mark.parametrize("n_fft", pv_ref.SIZES)
+@pytest.mark.parametrize("name,rate,pitch", NUMPY_CASES)
+def test_statement_matches_the_numpy_specification(ref, n_fft, name, rate, pitch):
+    """white noise, default lifter, formant_ratio on both sides of 1: tempo 1/2 in both stage orders (case A) and alone (case B),
+    tempo 1 (C in both orders, D), every N, within 1e-5 of the float64 statement — the bar tests/test_pv_formant_cpu.py holds the formant
+    statement to.  Measured 1.6e-7 - 5.5e-7."""
+    x = orc.fill_uniform(24000, 3)
+    q = pv_ref.default_lifter(48000, n_fft)
+    for phi in (UP, DOWN):
+        got = pv_fs_ref.stretch(ref, x, 1, rate, pitch, phi, n_fft, lifter=q)
+        want = pv_fs_ref.numpy_stretch(x, 1, rate, pitch, n_fft, q, phi)
+        assert got.size == want.size
+        e = rel_rms(got, want)
+        print(f"{name} N={n_fft} phi={phi:.4f}: {e:.3e}")
+        assert e <= 1e-5, (phi, e)
+
+
+SR, F0 = 48000, 140.0
+
+
+def envelope(f):
+    """the vowel's spectral envelope: resonances at 700, 1200 and 2600 Hz over a floor"""
+    return 0.03 + np.exp(-0.5 * ((f - 700) / 130) ** 2) + 0.6 * np.exp(-0.5 * ((f - 1200) / 150) ** 2) + 0.3 * np.exp(-0.5 * ((f - 2600) / 220) ** 2)
+
+
+def vowel(L):
+    t = np.arange(L) / SR
+    y = np.zeros(L)
+    for h in range(1, int(8000 / F0)):
+        y += envelope(h * F0) * np.sin(2 * np.pi * h * F0 * t + 0.7 * h * h)
+    return (0.1 * y).astype(np.float32)
+
+
+def harmonic_quality(y, f0, phi):
+    """(RMS dB error of the harmonic amplitudes below 5 kHz against the target envelope envelope(f / phi) after removing the mean, F1
+    estimate): amplitudes from a Hann DFT of the steady middle half; F1 = the power centroid of the harmonics in (350 - 1050 Hz) * phi"""
+    mid = y[y.size // 4: 3 * y.size // 4].astype(np.float64)
+    w = np.hanning(mid.size)
+    t = np.arange(mid.size) / SR
+    f = np.arange(1, int(5000 / f0) + 1) * f0
+    a = np.array([abs(np.sum(mid * w * np.exp(-2j * np.pi * fr * t))) for fr in f])
+    err = 20 * np.log10(a) - 20 * np.log10(envelope(f / phi))
+    err -= err.mean()
+    sel = (f >= 350 * phi) & (f <= 1050 * phi)
+    return float(np.sqrt(np.mean(err ** 2))), float(np.sum(f[sel] * a[sel] ** 2) / np.sum(a[sel] ** 2))
+
+
+@pytest.mark.parametrize("n_fft", [1024, 2048])
+@pytest.mark.parametrize("pitch_st,shift_st", [(0, 4), (0, -5), (4, -3)])
+def test_vowel_takes_the_shifted_envelope(ref, n_fft, pitch_st, shift_st):
+    """a 140 Hz vowel at 48 kHz (F1 centroid 717 Hz in): "pitch": 0 with the formants +4 / -5 semitones, and pitch +4 with the formants -3,
+    against the target envelope(f / phi), the F1 window scaled by phi.  Bars: 6 dB RMS in every case, and formant_ratio 1 on the same input
+    misses that bar against the same target.  Measured on the CPU statement, N = 1024 / 2048:
+      pitch 0, +4:  2.38 / 2.84 dB (ratio 1: 10.58 dB), F1 717 -> 885 / 880 Hz (+168 / +163; target 903)
+      pitch 0, -5:  2.35 / 4.15 dB (ratio 1: 10.50 dB), F1 717 -> 612 / 616 Hz (-105 / -101; target 537)
+      pitch +4, -3: 2.76 / 2.29 dB (ratio 1: 8.13 / 7.48 dB), F1 717 -> 720 / 702 Hz (target 603)
+    The F1 centroid.  For the two pure shifts it moves from the input's in the shift's direction by more than 65 Hz.  For pitch +4 with the
+    formants -3 that comparison does not measure the shift, and it is replaced:
+      * the input's 717 Hz is a centroid on the 140-Hz grid in 350 - 1050 Hz; the output's harmonics lie on a 176-Hz grid (353, 529, 706,
+        882 Hz in the scaled window 294 - 883 Hz, the last one 1 Hz inside its edge), where formant preservation alone (ratio 1, pitch +4)
+        reads 773 / 749 Hz in the same window.  Most of "717 -> 720" is that change of grid, not the formant.
+      * per harmonic, against the ratio-1 output at the same pitch (dB below the strongest), the formant does move down: 353 Hz -21.8 ->
+        -15.5 / -12.8, 529 Hz -10.0 / -7.3 -> -5.4 / -0.5, 1235 Hz (the old F2) -10.0 / -6.3 -> -16.5 / -13.9.  No gain comes near
+        NAE_FORMANT_MAX_GAIN (24 dB).  What limits the centroid is the liftered envelope: below 1 / 700 s of quefrency it is wider than the
+        vowel's 130-Hz resonance, so G = E(k g) / E(k) has less contrast than the target and the harmonic at the old peak (706 Hz: +2.8 / +0.1
+        dB over target, 529 Hz: -5.6 / -3.4 dB) stays the strongest.  The float64 statement agrees with this one to 5.5e-7 (the test above): it is the
+        rule's, not the arithmetic's.
+      * measured consistently — the shifted output against the ratio-1 output at the same pitch, both in the scaled window, over what the
+        target envelope itself gives on that grid — the three cases agree: pitch 0 / +4: +45 / +40 Hz of +66 (69 / 61 %); pitch 0 / -5: -50 /
+        -47 Hz of -126 (40 / 37 %); pitch +4 / -3: -53 / -48 Hz of -85 (62 / 56 %).  A 3-semitone shift has an on-grid target of 85 Hz, so a
+        65-Hz bar would ask for 77 % of it, more than either pure shift reaches.
+    So every case asserts the movement in that consistent form: in the shift's direction by more than 65 / 186 = 35 % of the on-grid target
+    movement, the fraction the 65-Hz bar is of the pure shifts' targets (186 / 180 Hz).  An output whose first formant did not move scores 0 %."""
+    x = vowel(48000)
+    p, phi = 2 ** (pitch_st / 12), 2 ** (shift_st / 12)
+    q = pv_ref.default_lifter(SR, n_fft)
+    f1_in = harmonic_quality(x, F0, 1.0)[1]
+    assert abs(f1_in - 717) < 5
+    y_on, y_one = pv_fs_ref.stretch(ref, x, 1, 1.0, p, phi, n_fft, lifter=q), pv_fs_ref.stretch(ref, x, 1, 1.0, p, 1.0, n_fft, lifter=q)
+    e_on, f1_on = harmonic_quality(y_on, F0 * p, phi)
+    e_one, f1_one = harmonic_quality(y_one, F0 * p, phi)
+    # what the envelopes themselves give on the output's harmonic grid in the same window
+    f = np.arange(1, int(5000 / (F0 * p)) + 1) * F0 * p
+    sel = (f >= 350 * phi) & (f <= 1050 * phi)
+    cen = lambda a: float(np.sum(f[sel] * a[sel] ** 2) / np.sum(a[sel] ** 2))
+    ideal = cen(envelope(f / phi)) - cen(envelope(f))
+    print(f"N={n_fft} pitch {pitch_st:+d} shift {shift_st:+d}: {e_on:.2f} dB, ratio 1: {e_one:.2f} dB, F1 {f1_in:.0f} -> {f1_on:.0f} Hz "
+          f"(target {717 * phi:.0f}); against ratio 1 in the same window {f1_one:.0f} -> {f1_on:.0f}: {f1_on - f1_one:+.0f} of {ideal:+.0f} Hz")
+    assert e_on <= 6.0, e_on
+    assert e_one > 6.0, e_one
+    assert np.sign(ideal) == np.sign(shift_st)
+    assert (f1_on - f1_one) / ideal > 65 / 186, (f1_one, f1_on, ideal)
+    if pitch_st == 0:
+        assert (f1_on - f1_in) * np.sign(shift_st) > 65, (f1_in, f1_on)
+
+
+def test_only_a_forced_plan_has_the_vocoder_at_tempo_one(nae):
+    """the kernels recognise a forced plan by pv_on with tempo_eff == 1: no _n plan has both, whatever the rate and pitch (a tempo within 1e-6
+    of 1 is snapped to 1 and switches the vocoder off), nor a shift plan without the envelope stage"""
+    pitches = [1.0, 1 + 5e-7, 1 - 5e-7, 1 + 1e-6, 1 - 1e-6, 1 + 2e-6, 1 - 2e-6, float(np.nextafter(1.0, 2.0)), float(np.nextafter(1.0, 0.0)),
+               2 ** (1 / 12), 0.5, 2.0, 1 / 1.5]
+    for n_fft in pv_ref.SIZES:
+        for pitch in pitches:
+            for rate in (1.0, 0.8, 1.25, 1 / pitch):
+                for pl in (nae.Context.stretch_plan(rate, pitch, 5000, n_fft),
+                           nae.Context.stretch_plan(rate, pitch, 5000, n_fft, formant=0, formant_ratio=UP)):
+                    assert not (pl.pv_on and pl.tempo_eff == 1.0), (n_fft, rate, pitch)
+                    assert bool(pl.pv_on) == (pl.tempo_eff != 1.0), (n_fft, rate, pitch)
+
+
+def test_abi_declares_the_shift_entries(nae):
+    hdr = open(os.path.join(ROOT, "include", "nae_gpu.h")).read()
+    assert re.search(r"#define NAE_ABI_VERSION 3\b", hdr)
+    later = hdr[hdr.index("Later additions within 3"): hdr.index("#define NAE_ABI_VERSION")]
+    for s in SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % s, hdr), s
+        assert s in later, s
+        assert s in nae.EXPORTED_SYMBOLS, s
+        assert hasattr(nae.load_library(), s), s
+
+
+def test_host_node_formant_shift_key(tmp_path):
+    """Pitch_modifier: "formant_shift" round-trips, is absent by default and at 0, a value that is not a number is "Wrong field:
+    formant_shift", beyond +-24 it is a Runtime_error, it combines with phase_lock, fft_size, transients and formant, is kept with the
+    soundtouch algorithm; Velocity_modifier has no such key"""
+    exe = node_harness.build("pv_fshift/host_pv_fshift.cpp", str(tmp_path))
+    r = subprocess.run([exe, "json"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "HOST PV FSHIFT OK json" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
