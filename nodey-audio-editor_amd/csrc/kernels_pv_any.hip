@@ -413,16 +413,15 @@ __global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient>::kWaves3)) voi
 
 // ------------------------------------------------------------------------------------------------ launchers
 template <int N, bool kTransient>
-static int launch_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, uint32_t* phase_ws,
-                        const SpecAnyTables& tb)
+static int launch_phase(nae_ctx* ctx, const PvJob& j, const SpecAnyTables& tb)
 {
     using P = PvAny<N, false, kTransient>;
     const char* name = kTransient ? "pv_any_phase_transient_kernel" : "pv_any_phase_kernel";
-    const long long items = n_sc * p.n_tiles;
+    const long long items = j.n_sc * j.p.n_tiles;
     const long long grid = (items + P::kWaves1 - 1) / P::kWaves1;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_phase_kernel: grid too large");
-    NAE_KLAUNCH(ctx, name, (unit_stride ? pv_any_phase_kernel<N, true, kTransient> : pv_any_phase_kernel<N, false, kTransient>), dim3((unsigned)grid),
-                dim3(64 * P::kWaves1), 0, ctx->stream, src, p, items, phase_ws, tb);
+    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pv_any_phase_kernel<N, true, kTransient> : pv_any_phase_kernel<N, false, kTransient>), dim3((unsigned)grid),
+                dim3(64 * P::kWaves1), 0, ctx->stream, j.src, j.p, items, j.phase_ws, tb);
     return nae_check(ctx, hipGetLastError(), name);
 }
 
@@ -447,18 +446,17 @@ static int launch_scan(nae_ctx* ctx, const char* name, uint32_t* phase_ws, long 
 }
 
 template <int N, bool kFormant, bool kTransient>
-static int launch_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
-                        const OutViewD& out, const SpecAnyTables& tb, int lifter, float g)
+static int launch_synth(nae_ctx* ctx, const PvJob& j, const SpecAnyTables& tb)
 {
     using P = PvAny<N, kFormant, kTransient>;
     const char* name = kTransient ? (kFormant ? "pv_any_synth_formant_transient_kernel" : "pv_any_synth_transient_kernel")
                                   : (kFormant ? "pv_any_synth_formant_kernel" : "pv_any_synth_kernel");
-    const long long items = n_sc * p.n_tiles;
+    const long long items = j.n_sc * j.p.n_tiles;
     if (items == 0) return NAE_OK;
     const long long grid = (items + P::kWaves3 - 1) / P::kWaves3;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_synth_kernel: grid too large");
-    NAE_KLAUNCH(ctx, name, (unit_stride ? pv_any_synth_kernel<N, true, kFormant, kTransient> : pv_any_synth_kernel<N, false, kFormant, kTransient>),
-                dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream, src, p, items, phase_ws, out, tb, lifter, g);
+    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pv_any_synth_kernel<N, true, kFormant, kTransient> : pv_any_synth_kernel<N, false, kFormant, kTransient>),
+                dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream, j.src, j.p, items, j.phase_ws, j.out, tb, j.lifter, j.g);
     return nae_check(ctx, hipGetLastError(), name);
 }
 
@@ -471,25 +469,25 @@ size_t nae_pv_record_pad(int n_fft) { return (size_t)((n_fft / 2 + 1 + 7) & ~7);
 
 bool nae_pv_size_ok(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096; }
 
-int nae_pv_resident3(nae_ctx* ctx, int n_fft, bool formant, bool transients)
+int nae_pv_resident(nae_ctx* ctx, const nae_pv_run& r, PvKernels pass3)
 {
-    return at_size(ctx, n_fft, [&](auto n) {
+    if (pass3 == PvKernels::kLock) return 16;
+    return at_size(ctx, r.n_fft, [&](auto n) {
         constexpr int N = decltype(n)::value;
-        if (transients) return formant ? PvAny<N, true, true>::kResident3 : PvAny<N, false, true>::kResident3;
-        return formant ? PvAny<N, true>::kResident3 : PvAny<N>::kResident3;
+        if (pass3 == PvKernels::kEnv) return PvEnv<N>::kResident;
+        if (r.transients) return r.lifter > 0 ? PvAny<N, true, true>::kResident3 : PvAny<N, false, true>::kResident3;
+        return r.lifter > 0 ? PvAny<N, true>::kResident3 : PvAny<N>::kResident3;
     });
 }
 
-int nae_launch_pvany_phase(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, uint32_t* phase_ws,
-                           bool transients)
+int nae_launch_pvany_phase(nae_ctx* ctx, const PvJob& j)
 {
     SpecAnyTables tb;
-    int rc = nae_spec_any_tables(ctx, n_fft, &tb);
+    int rc = nae_spec_any_tables(ctx, j.n_fft, &tb);
     if (rc) return rc;
-    return at_size(ctx, n_fft, [&](auto n) {
+    return at_size(ctx, j.n_fft, [&](auto n) {
         constexpr int N = decltype(n)::value;
-        return transients ? launch_phase<N, true>(ctx, p, src, n_sc, unit_stride, phase_ws, tb)
-                          : launch_phase<N, false>(ctx, p, src, n_sc, unit_stride, phase_ws, tb);
+        return j.transients ? launch_phase<N, true>(ctx, j, tb) : launch_phase<N, false>(ctx, j, tb);
     });
 }
 
@@ -503,18 +501,14 @@ int nae_launch_pv_scan(nae_ctx* ctx, int n_fft, const char* name, uint32_t* phas
     });
 }
 
-int nae_launch_pvany_synth(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride,
-                           const uint32_t* phase_ws, const OutViewD& out, int lifter, float g, bool transients)
+int nae_launch_pvany_synth(nae_ctx* ctx, const PvJob& j)
 {
     SpecAnyTables tb;
-    int rc = nae_spec_any_tables(ctx, n_fft, &tb);
+    int rc = nae_spec_any_tables(ctx, j.n_fft, &tb);
     if (rc) return rc;
-    return at_size(ctx, n_fft, [&](auto n) {
+    return at_size(ctx, j.n_fft, [&](auto n) {
         constexpr int N = decltype(n)::value;
-        if (transients)
-            return lifter > 0 ? launch_synth<N, true, true>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g)
-                              : launch_synth<N, false, true>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, 0, 0.0f);
-        return lifter > 0 ? launch_synth<N, true, false>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, lifter, g)
-                          : launch_synth<N, false, false>(ctx, p, src, n_sc, unit_stride, phase_ws, out, tb, 0, 0.0f);
+        if (j.transients) return j.lifter > 0 ? launch_synth<N, true, true>(ctx, j, tb) : launch_synth<N, false, true>(ctx, j, tb);
+        return j.lifter > 0 ? launch_synth<N, true, false>(ctx, j, tb) : launch_synth<N, false, false>(ctx, j, tb);
     });
 }

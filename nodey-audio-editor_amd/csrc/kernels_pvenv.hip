@@ -66,16 +66,15 @@ __global__ __launch_bounds__(64 * (PvEnv<N>::kWaves)) void pv_env_kernel(SigView
 }
 
 template <int N>
-static int launch_env(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const OutViewD& out,
-                      const SpecAnyTables& tb, int lifter, float g)
+static int launch_env(nae_ctx* ctx, const PvJob& j, const SpecAnyTables& tb)
 {
     using E = PvEnv<N>;
-    const long long items = n_sc * p.n_tiles;
+    const long long items = j.n_sc * j.p.n_tiles;
     if (items == 0) return NAE_OK;
     const long long grid = (items + E::kWaves - 1) / E::kWaves;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_env_kernel: grid too large");
-    NAE_KLAUNCH(ctx, "pv_env_kernel", (unit_stride ? pv_env_kernel<N, true> : pv_env_kernel<N, false>), dim3((unsigned)grid), dim3(64 * E::kWaves), 0,
-                ctx->stream, src, p, items, out, tb, lifter, g);
+    NAE_KLAUNCH(ctx, "pv_env_kernel", (j.unit_stride ? pv_env_kernel<N, true> : pv_env_kernel<N, false>), dim3((unsigned)grid), dim3(64 * E::kWaves), 0,
+                ctx->stream, j.src, j.p, items, j.out, tb, j.lifter, j.g);
     return nae_check(ctx, hipGetLastError(), "pv_env_kernel");
 }
 
@@ -84,16 +83,10 @@ static int launch_env(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long
 // ================================================================================================ host side
 using namespace nae;
 
-int nae_pvenv_resident(nae_ctx* ctx, int n_fft)
-{
-    return at_size(ctx, n_fft, [&](auto n) { return PvEnv<decltype(n)::value>::kResident; });
-}
-
-int nae_launch_pvenv(nae_ctx* ctx, int n_fft, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const OutViewD& out,
-                     int lifter, float g)
+int nae_launch_pvenv(nae_ctx* ctx, const PvJob& j)
 {
     SpecAnyTables tb;
-    const int rc = nae_spec_any_tables(ctx, n_fft, &tb);
+    const int rc = nae_spec_any_tables(ctx, j.n_fft, &tb);
     if (rc) return rc;
-    return at_size(ctx, n_fft, [&](auto n) { return launch_env<decltype(n)::value>(ctx, p, src, n_sc, unit_stride, out, tb, lifter, g); });
+    return at_size(ctx, j.n_fft, [&](auto n) { return launch_env<decltype(n)::value>(ctx, j, tb); });
 }

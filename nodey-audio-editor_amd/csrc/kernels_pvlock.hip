@@ -585,64 +585,58 @@ constexpr unsigned kAttrLockMap = 1u << 12, kAttrLockScan = 1u << 13, kAttrLockS
 
 // transients: the kTransient instantiations (reset maps, the segmented scan; profile names pvlock_map_transient_kernel and
 // pvlock_scan_transient_kernel)
-int nae_launch_pvlock_phase(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
-                            uint32_t* phase_ws, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out, bool transients)
+int nae_launch_pvlock_phase(nae_ctx* ctx, const PvJob& j, int n_needed, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out)
 {
     const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
     {
-        const long long items = n_sc * p.n_tiles;
+        const long long items = j.n_sc * j.p.n_tiles;
         const long long grid = (items + kWaves - 1) / kWaves;
         if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_map_kernel: grid too large");
-        const char* name = transients ? "pvlock_map_transient_kernel" : "pvlock_map_kernel";
-        auto k_unit = transients ? pvlock_map_kernel<true, true> : pvlock_map_kernel<true, false>;
-        auto k_strided = transients ? pvlock_map_kernel<false, true> : pvlock_map_kernel<false, false>;
-        int rc = nae_pv_lds_attr(ctx, transients ? kAttrLockMapT : kAttrLockMap, kLdsLockMap, reinterpret_cast<const void*>(k_unit),
+        const char* name = j.transients ? "pvlock_map_transient_kernel" : "pvlock_map_kernel";
+        auto k_unit = j.transients ? pvlock_map_kernel<true, true> : pvlock_map_kernel<true, false>;
+        auto k_strided = j.transients ? pvlock_map_kernel<false, true> : pvlock_map_kernel<false, false>;
+        int rc = nae_pv_lds_attr(ctx, j.transients ? kAttrLockMapT : kAttrLockMap, kLdsLockMap, reinterpret_cast<const void*>(k_unit),
                                  reinterpret_cast<const void*>(k_strided));
         if (rc) return rc;
-        NAE_KLAUNCH(ctx, name, (unit_stride ? k_unit : k_strided), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream, src, p, items, maps,
-                    sig16, tb);
+        NAE_KLAUNCH(ctx, name, (j.unit_stride ? k_unit : k_strided), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream, j.src, j.p, items,
+                    maps, sig16, tb);
         rc = nae_check(ctx, hipGetLastError(), name);
         if (rc) return rc;
     }
-    if (n_sc > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_scan_kernel: grid too large");
-    const char* name = transients ? "pvlock_scan_transient_kernel" : "pvlock_scan_kernel";
-    auto k_scan = transients ? pvlock_scan_kernel<true> : pvlock_scan_kernel<false>;
-    int rc = nae_pv_lds_attr(ctx, transients ? kAttrLockScanT : kAttrLockScan, kLockChunks * kLockScanWave, reinterpret_cast<const void*>(k_scan));
+    if (j.n_sc > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_scan_kernel: grid too large");
+    const char* name = j.transients ? "pvlock_scan_transient_kernel" : "pvlock_scan_kernel";
+    auto k_scan = j.transients ? pvlock_scan_kernel<true> : pvlock_scan_kernel<false>;
+    int rc = nae_pv_lds_attr(ctx, j.transients ? kAttrLockScanT : kAttrLockScan, kLockChunks * kLockScanWave, reinterpret_cast<const void*>(k_scan));
     if (rc) return rc;
-    const int nch = p.n_tiles >= 256 ? kLockChunks : 1;
-    NAE_KLAUNCH(ctx, name, k_scan, dim3((unsigned)n_sc), dim3(64 * nch), nch * kLockScanWave, ctx->stream, phase_ws, maps, sig16, p.n_tiles, carry_in,
+    const int nch = j.p.n_tiles >= 256 ? kLockChunks : 1;
+    NAE_KLAUNCH(ctx, name, k_scan, dim3((unsigned)j.n_sc), dim3(64 * nch), nch * kLockScanWave, ctx->stream, j.phase_ws, maps, sig16, j.p.n_tiles, carry_in,
                 carry_out, n_needed);
     return nae_check(ctx, hipGetLastError(), name);
 }
 
 template <bool kFormant, bool kTransient>
-static int launch_lock_synth(nae_ctx* ctx, unsigned attr_bit, const char* name, const PvParams& p, const SigViewD& src, long long items, bool unit_stride,
-                             const uint32_t* phase_ws, const OutViewD& out, int lifter, float g)
+static int launch_lock_synth(nae_ctx* ctx, unsigned attr_bit, const char* name, const PvJob& j)
 {
+    const long long items = j.n_sc * j.p.n_tiles;
     const long long grid = (items + kWaves - 1) / kWaves;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_synth_kernel: grid too large");
     const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
     int rc = nae_pv_lds_attr(ctx, attr_bit, kLdsLockSynth, reinterpret_cast<const void*>(pvlock_synth_kernel<true, kFormant, kTransient>),
                              reinterpret_cast<const void*>(pvlock_synth_kernel<false, kFormant, kTransient>));
     if (rc) return rc;
-    NAE_KLAUNCH(ctx, name, (unit_stride ? pvlock_synth_kernel<true, kFormant, kTransient> : pvlock_synth_kernel<false, kFormant, kTransient>),
-                dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream, src, p, items, phase_ws, out, tb, lifter, g);
+    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pvlock_synth_kernel<true, kFormant, kTransient> : pvlock_synth_kernel<false, kFormant, kTransient>),
+                dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream, j.src, j.p, items, j.phase_ws, j.out, tb, j.lifter, j.g);
     return nae_check(ctx, hipGetLastError(), name);
 }
 
 // lifter > 0: formant preservation (pvlock_synth_formant_kernel); transients: onsets reset Qs (the *_transient_kernel instantiations)
-int nae_launch_pvlock_synth(nae_ctx* ctx, const PvParams& p, const SigViewD& src, long long n_sc, bool unit_stride, const uint32_t* phase_ws,
-                            const OutViewD& out, int lifter, float g, bool transients)
+int nae_launch_pvlock_synth(nae_ctx* ctx, const PvJob& j)
 {
-    const long long items = n_sc * p.n_tiles;
-    if (items == 0) return NAE_OK;
-    if (transients) {
-        if (lifter > 0)
-            return launch_lock_synth<true, true>(ctx, kAttrLockSynthFT, "pvlock_synth_formant_transient_kernel", p, src, items, unit_stride, phase_ws,
-                                                 out, lifter, g);
-        return launch_lock_synth<false, true>(ctx, kAttrLockSynthT, "pvlock_synth_transient_kernel", p, src, items, unit_stride, phase_ws, out, 0, 0.0f);
+    if (j.n_sc * j.p.n_tiles == 0) return NAE_OK;
+    if (j.transients) {
+        if (j.lifter > 0) return launch_lock_synth<true, true>(ctx, kAttrLockSynthFT, "pvlock_synth_formant_transient_kernel", j);
+        return launch_lock_synth<false, true>(ctx, kAttrLockSynthT, "pvlock_synth_transient_kernel", j);
     }
-    if (lifter > 0)
-        return launch_lock_synth<true, false>(ctx, kAttrLockSynthF, "pvlock_synth_formant_kernel", p, src, items, unit_stride, phase_ws, out, lifter, g);
-    return launch_lock_synth<false, false>(ctx, kAttrLockSynth, "pvlock_synth_kernel", p, src, items, unit_stride, phase_ws, out, 0, 0.0f);
+    if (j.lifter > 0) return launch_lock_synth<true, false>(ctx, kAttrLockSynthF, "pvlock_synth_formant_kernel", j);
+    return launch_lock_synth<false, false>(ctx, kAttrLockSynth, "pvlock_synth_kernel", j);
 }

@@ -535,19 +535,35 @@ size_t nae_pv_workspace_bytes(bool lock, int n_fft, size_t n_frames, int ch, siz
     return recs * nae_pv_record_pad(n_fft) * (lock ? 2 * sizeof(uint32_t) + sizeof(uint16_t) : sizeof(uint32_t));
 }
 
+// the context's phase workspace for a call of n_frames frames in pass-1 tiles of `tile`; the envelope pass (a forced plan) has none
+int nae_pv_reserve_ws(nae_ctx* ctx, const nae_pv_run& r, size_t n_frames, int ch, size_t n_streams, int tile)
+{
+    if (r.forced) return NAE_OK;
+    return nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(r.lock, r.n_fft, n_frames, ch, n_streams, tile));
+}
+
+// what both passes hand their leaf launchers (pass 1: no output)
+static PvJob make_pv_job(const nae_pv_run& r, const nae_stretch_plan& pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams, int tile,
+                         const nae_pv_segment* seg, uint32_t* phase_ws, const nae_sig* out)
+{
+    return PvJob{r.n_fft, make_pv_params(pl, in_len, ch, tile, seg), to_view(src), out ? to_out(out) : OutViewD{}, (long long)n_streams * ch,
+                 src->frame_stride == 1, phase_ws, r.lifter, r.g, r.transients};
+}
+
 // pass 1 + 2: leaves the exclusive tile-prefix phases in `phase_ws` (one record per pass-1 tile).
 // Pass 1 may use shorter tiles than pass 3 (`synth_tile` = a multiple of `tile`): its waves are independent, so short
 // tiles keep the chip full on small batches, while pass 3 wants few long tiles (each re-analyses its frames).
 // Only the sums (locked: maps) in front of the last synthesis tile are needed, unless the phase behind the segment is carried on (a
 // continued stream): nothing at all when the stream-channel is a single synthesis tile.
 // Pass 1 as nae_pv_route_of says; unlocked, either pass 1 is followed by the one scan (pv_scan_kernel, kernels_pv_any.hip).
-int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
-                        size_t n_streams, int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg)
+int nae_launch_pv_phase(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                        int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg)
 {
     if (tile <= 0 || synth_tile < tile || synth_tile % tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
-    if (nae_plan_forced(*pl)) return NAE_OK;   // the envelope pass carries no phase
-    PvParams p = make_pv_params(*pl, in_len, ch, tile, seg);
-    const long long n_sc = (long long)n_streams * ch;
+    if (r.forced) return NAE_OK;   // the envelope pass carries no phase
+    PvJob j = make_pv_job(r, *pl, src, in_len, ch, n_streams, tile, seg, phase_ws, nullptr);
+    PvParams& p = j.p;
+    const long long n_sc = j.n_sc;
     if (n_sc * p.n_tiles == 0) return NAE_OK;
     const bool need_last = seg && seg->carry_out && !seg->carry_by_synth;
     const int step = synth_tile / tile;
@@ -555,7 +571,7 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
     const int n_needed = need_last ? p.n_tiles : (n_synth - 1) * step;      // sums (maps) of tiles [0, n_needed) are used
     const uint32_t* carry_in = seg ? seg->carry_in : nullptr;
     uint32_t* carry_out = seg ? seg->carry_out : nullptr;
-    const size_t pad = nae_pv_record_pad(n_fft);
+    const size_t pad = nae_pv_record_pad(r.n_fft);
     if (n_needed == 0) {
         // base phase of the only synthesis tile (record 0 of each stream-channel): the carried phase, or zero
         hipError_t e = hipSuccess;
@@ -571,17 +587,15 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
         return nae_check(ctx, e, "phase base init");
     }
     p.skip_from = n_needed;                   // pass 1 skips the tiles whose sums are not needed
-    const bool transients = seg && seg->transients;
-    const PvKernels pass1 = nae_pv_route_of(ctx, lock, n_fft, 0, transients).pass1;
-    const bool unit_stride = src->frame_stride == 1;
+    const PvKernels pass1 = nae_pv_route_of(ctx, r).pass1;
     if (pass1 == PvKernels::kLock) {
         const size_t n_rec = (size_t)n_sc * p.n_tiles;
         uint32_t* maps = phase_ws + n_rec * kT1024Pad;
         uint16_t* sig16 = reinterpret_cast<uint16_t*>(maps + n_rec * kT1024Pad);
-        return nae_launch_pvlock_phase(ctx, p, to_view(src), n_sc, unit_stride, n_needed, phase_ws, maps, sig16, carry_in, carry_out, transients);
+        return nae_launch_pvlock_phase(ctx, j, n_needed, maps, sig16, carry_in, carry_out);
     }
     if (pass1 == PvKernels::kAny) {
-        const int rc = nae_launch_pvany_phase(ctx, n_fft, p, to_view(src), n_sc, unit_stride, phase_ws, transients);
+        const int rc = nae_launch_pvany_phase(ctx, j);
         if (rc) return rc;
     } else {
         // items are (stream-channel, tile) with tile fastest
@@ -589,25 +603,23 @@ int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
         const long long grid = (items + kWaves - 1) / kWaves;
         if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_phase_kernel: grid too large");
         const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
-        NAE_KLAUNCH(ctx, "pv_phase_kernel", (unit_stride ? pv_phase_kernel<true> : pv_phase_kernel<false>), dim3((unsigned)grid), dim3(kThreads),
-                    kLdsPhase, ctx->stream, to_view(src), p, items, phase_ws, tb);
+        NAE_KLAUNCH(ctx, "pv_phase_kernel", (j.unit_stride ? pv_phase_kernel<true> : pv_phase_kernel<false>), dim3((unsigned)grid), dim3(kThreads),
+                    kLdsPhase, ctx->stream, j.src, p, items, phase_ws, tb);
         const int rc = nae_check(ctx, hipGetLastError(), "pv_phase_kernel");
         if (rc) return rc;
     }
-    return nae_launch_pv_scan(ctx, n_fft, pass1 == PvKernels::kAny ? "pv_any_scan_kernel" : "pv_scan_kernel", phase_ws, n_sc, p.n_tiles, carry_in,
-                              carry_out, n_needed, transients);
+    return nae_launch_pv_scan(ctx, r.n_fft, pass1 == PvKernels::kAny ? "pv_any_scan_kernel" : "pv_scan_kernel", phase_ws, n_sc, p.n_tiles, carry_in,
+                              carry_out, n_needed, r.transients);
 }
 
-// pass 3 (locked: L3) from the records of pass 2 (or, one tile and nothing carried in, from zero), on the kernels nae_pv_route_of says; lifter > 0
-// with the envelope stage on (nae_formant_lifter_eff): formant preservation, or with formant_ratio != 1 the formant shift; a forced plan runs the
-// envelope pass alone
-int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
-                        size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
-                        const nae_pv_segment* seg, int frames_per_step, int lifter, double formant_ratio)
+// pass 3 (locked: L3) from the records of pass 2 (or, one tile and nothing carried in, from zero), on the kernels nae_pv_route_of says; r.lifter > 0:
+// formant preservation, or with a formant ratio other than 1 the formant shift; a forced plan runs the envelope pass alone
+int nae_launch_pv_synth(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                        int tile, int phase_tile, uint32_t* phase_ws, const nae_sig* out, const nae_pv_segment* seg, int frames_per_step)
 {
     if (phase_tile <= 0 || tile < phase_tile || tile % phase_tile) return nae_fail(ctx, NAE_ERR_INVALID, "phase tile must divide the synthesis tile");
-    PvParams p = make_pv_params(*pl, in_len, ch, tile, seg);
-    lifter = nae_formant_lifter_eff(*pl, lifter, formant_ratio);
+    PvJob j = make_pv_job(r, *pl, src, in_len, ch, n_streams, tile, seg, phase_ws, out);
+    PvParams& p = j.p;
     const long long cnt = p.f_stop - p.f_origin;
     p.phase_step = tile / phase_tile;
     p.phase_tiles = (int)((cnt + phase_tile - 1) / phase_tile);
@@ -617,17 +629,11 @@ int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_pl
         p.carry_out = seg->carry_out;
         p.carry_frame = p.f_stop - 1;
     }
-    const long long n_sc = (long long)n_streams * ch;
-    const float g = nae_formant_g(*pl, formant_ratio);     // formant preservation: the transposer ratio (over the formant shift)
-    const bool unit_stride = src->frame_stride == 1;
-    const bool transients = seg && seg->transients;
-    const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, lifter, transients, nae_plan_forced(*pl)).pass3;
-    if (pass3 == PvKernels::kEnv) return nae_launch_pvenv(ctx, n_fft, p, to_view(src), n_sc, unit_stride, to_out(out), lifter, g);
-    if (pass3 == PvKernels::kLock)
-        return nae_launch_pvlock_synth(ctx, p, to_view(src), n_sc, unit_stride, phase_ws, to_out(out), lifter, g, transients);
-    if (pass3 == PvKernels::kAny)
-        return nae_launch_pvany_synth(ctx, n_fft, p, to_view(src), n_sc, unit_stride, phase_ws, to_out(out), lifter, g, transients);
-    return nae_launch_pv_pipe(ctx, p, to_view(src), n_sc, phase_ws, to_out(out), unit_stride, frames_per_step);
+    const PvKernels pass3 = nae_pv_route_of(ctx, r).pass3;
+    if (pass3 == PvKernels::kEnv) return nae_launch_pvenv(ctx, j);
+    if (pass3 == PvKernels::kLock) return nae_launch_pvlock_synth(ctx, j);
+    if (pass3 == PvKernels::kAny) return nae_launch_pvany_synth(ctx, j);
+    return nae_launch_pv_pipe(ctx, j, frames_per_step);
 }
 
 // outputs [j_begin, j_end)

@@ -226,6 +226,22 @@ static int pick_wave_tile(nae_ctx* ctx, size_t frames, size_t n_sc, size_t resid
     return (int)(tile < 0x40000000 ? tile : 0x40000000);
 }
 
+// Tiles of a block call on the kernels it runs, and the phase workspace for them: the pipeline's shape rule, else one tile per pass-3 wave
+struct PvBlockShape { int tile, phase_tile, frames_per_step; };
+static int pv_block_shape(nae_ctx* ctx, const nae_pv_run& r, size_t frames, int ch, size_t n_streams, PvBlockShape* s)
+{
+    const PvKernels pass3 = nae_pv_route_of(ctx, r).pass3;
+    const size_t n_sc = n_streams * ch;
+    s->frames_per_step = 1;
+    if (pass3 == PvKernels::kShipped) s->tile = nae_pick_pv_shape(ctx, frames, n_sc, &s->phase_tile, &s->frames_per_step);
+    else {
+        // the kernel's own residency (locked: four waves per SIMD), tiles of at least 64 frames (pv_min_ptile does not apply to the locked route)
+        const size_t min_tile = pass3 != PvKernels::kLock && ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64;
+        s->tile = s->phase_tile = pick_wave_tile(ctx, frames, n_sc, (size_t)nae_pv_resident(ctx, r, pass3), min_tile);
+    }
+    return nae_pv_reserve_ws(ctx, r, frames, ch, n_streams, s->phase_tile);
+}
+
 extern "C" {
 
 int nae_abi_version(void) { return NAE_ABI_VERSION; }
@@ -581,21 +597,23 @@ static int reserve_mid(nae_ctx* ctx, const nae_stretch_plan& pl, int ch, size_t 
     return NAE_OK;
 }
 
-// the one statement of the _n entries' rules: an unknown flag NAE_ERR_INVALID; a size outside 512 / 1024 / 2048 / 4096, the phase lock at a
-// size other than 1024 (with or without NAE_STRETCH_TRANSIENTS), NAE_ERR_UNSUPPORTED
-int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft)
+int nae_pv_opts_check(nae_ctx* ctx, unsigned flags, unsigned allowed, int n_fft, int lifter, const double* formant_ratio, nae_pv_opts* o)
 {
-    if (flags & ~(NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS)) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
+    if (!ctx) return NAE_ERR_INVALID;
+    if (flags & ~allowed) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
     if (!nae_pv_size_ok(n_fft)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
     if ((flags & NAE_STRETCH_PHASE_LOCK) && n_fft != NAE_FFT_N) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "phase locking runs at n_fft = 1024 only");
+    if (lifter < 0 || lifter > n_fft / 4) return nae_fail(ctx, NAE_ERR_INVALID, "formant lifter must be in [0, n_fft / 4]");
+    *o = nae_pv_opts{n_fft, lifter, (flags & NAE_STRETCH_PHASE_LOCK) != 0, (flags & NAE_STRETCH_TRANSIENTS) != 0, formant_ratio != nullptr,
+                     formant_ratio ? *formant_ratio : 1.0};
     return NAE_OK;
 }
 
-// the lifter of the _formant entries: 0 (off) ... n_fft / 4, else NAE_ERR_INVALID
-int nae_formant_check(nae_ctx* ctx, int n_fft, int lifter)
+int nae_pv_plan_make(nae_ctx* ctx, const nae_pv_opts& o, double rate, double pitch, size_t in_len, nae_stretch_plan* pl)
 {
-    if (lifter < 0 || lifter > n_fft / 4) return nae_fail(ctx, NAE_ERR_INVALID, "formant lifter must be in [0, n_fft / 4]");
-    return NAE_OK;
+    const int rc = o.shift ? nae_stretch_plan_make_shift(rate, pitch, o.formant_ratio, o.lifter, o.n_fft, in_len, pl)
+                           : nae_stretch_plan_make_n(rate, pitch, o.n_fft, in_len, pl);
+    return rc ? nae_fail(ctx, rc, o.shift ? "rate/pitch/formant ratio outside the supported range" : "rate/pitch outside the supported range") : NAE_OK;
 }
 
 // a 2-input mix node in front of the stretch node (graph4): when the transposer runs first it can mix while staging
@@ -608,19 +626,14 @@ struct nae_mix_front {
 // stages: bit 0 = the front stage (the mix node, and the transposer when it runs first), bit 1 = everything behind it
 // (nae_debug_graph4_stages: scheduling experiments run the two from separate calls; the intermediate signal stays in the
 // context's workspace between them).
-static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
-                              const nae_sig* dst, const nae_mix_front* front, int stages = 3, bool lock = false, int n_fft = NAE_FFT_N,
-                              int lifter = 0, bool transients = false, const double* formant_ratio = nullptr)
+static int stretch_block_impl(nae_ctx* ctx, const nae_pv_opts& o, double rate, double pitch, const nae_sig* src, size_t in_len, int ch,
+                              size_t n_streams, const nae_sig* dst, const nae_mix_front* front, int stages)
 {
-    if (!ctx) return NAE_ERR_INVALID;
     int rc;
     if ((rc = check_sig(ctx, src, "null source view")) || (rc = check_sig(ctx, dst, "null destination view"))) return rc;
     if (ch < 1 || ch > 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
-    // the _formant_shift entry (formant_ratio given): its own plan, with the vocoder stage forced on for a shift at tempo 1
     nae_stretch_plan pl;
-    const double phi = formant_ratio ? *formant_ratio : 1.0;
-    rc = formant_ratio ? nae_stretch_plan_make_shift(rate, pitch, phi, lifter, n_fft, in_len, &pl) : nae_stretch_plan_make_n(rate, pitch, n_fft, in_len, &pl);
-    if (rc) return nae_fail(ctx, rc, formant_ratio ? "rate/pitch/formant ratio outside the supported range" : "rate/pitch outside the supported range");
+    if ((rc = nae_pv_plan_make(ctx, o, rate, pitch, in_len, &pl))) return rc;
     // the mix node in front: fused into the transposer when that runs first, else its own launch (src = its output)
     bool mix_pending = front != nullptr && (stages & 1);
     auto run_mix = [&]() -> int {
@@ -671,28 +684,14 @@ static int stretch_block_impl(nae_ctx* ctx, double rate, double pitch, const nae
     if ((rc = run_mix())) return rc;     // vocoder first / transposer only: the mix is a launch of its own
     if (!(stages & 2)) return NAE_OK;
     if (pl.pv_on) {
-        int phase_tile = 0, fps = 1;
-        int tile;
-        const int q = nae_formant_lifter_eff(pl, lifter, phi);
-        const PvKernels pass3 = nae_pv_route_of(ctx, lock, n_fft, q, transients, nae_plan_forced(pl)).pass3;
-        if (pass3 == PvKernels::kEnv)    // no pass 1: one tile rule, the kernel's own residency
-            tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, (size_t)nae_pvenv_resident(ctx, n_fft),
-                                               ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64);
-        else if (pass3 == PvKernels::kLock)   // four waves per SIMD, tiles of at least 64 frames (pv_min_ptile does not apply)
-            tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, 16, 64);
-        else if (pass3 == PvKernels::kAny)
-            tile = phase_tile = pick_wave_tile(ctx, pl.frames, n_streams * ch, (size_t)nae_pv_resident3(ctx, n_fft, q > 0, transients),
-                                               ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64);
-        else tile = nae_pick_pv_shape(ctx, pl.frames, n_streams * ch, &phase_tile, &fps);
-        if (pass3 != PvKernels::kEnv)    // the envelope pass has no phase workspace
-            rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, n_fft, pl.frames, ch, n_streams, phase_tile));
+        const nae_pv_run run = nae_pv_resolve(o, pl);
+        PvBlockShape sh;
+        if ((rc = pv_block_shape(ctx, run, pl.frames, ch, n_streams, &sh))) return rc;
+        const nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, pv_out_len, nullptr, nullptr};
+        rc = nae_launch_pv_phase(ctx, run, &pl, pv_src, pv_in_len, ch, n_streams, sh.phase_tile, sh.tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
         if (rc) return rc;
-        nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, pv_out_len, nullptr, nullptr};
-        seg.transients = transients;
-        rc = nae_launch_pv_phase(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, phase_tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
-        if (rc) return rc;
-        rc = nae_launch_pv_synth(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, tile, phase_tile, static_cast<const uint32_t*>(ctx->ws_phase), pv_dst,
-                                 &seg, fps, lifter, phi);
+        rc = nae_launch_pv_synth(ctx, run, &pl, pv_src, pv_in_len, ch, n_streams, sh.tile, sh.phase_tile, static_cast<uint32_t*>(ctx->ws_phase),
+                                 pv_dst, &seg, sh.frames_per_step);
         if (rc) return rc;
     }
     if (pl.rs_on && !pl.rs_first) {
@@ -709,25 +708,21 @@ extern "C" {
 int nae_stretch_block_f32(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch,
                           size_t n_streams, const nae_sig* dst)
 {
-    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr);
+    return nae_stretch_block_ex_f32(ctx, rate, pitch, 0u, src, in_len, ch, n_streams, dst);
 }
 
 int nae_stretch_block_ex_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, const nae_sig* src, size_t in_len, int ch,
                              size_t n_streams, const nae_sig* dst)
 {
-    if (!ctx) return NAE_ERR_INVALID;
-    if (flags & ~NAE_STRETCH_PHASE_LOCK) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
-    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0);
+    nae_pv_opts o;
+    const int rc = nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK, NAE_FFT_N, 0, nullptr, &o);
+    return rc ? rc : stretch_block_impl(ctx, o, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3);
 }
 
 int nae_stretch_block_n_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, const nae_sig* src, size_t in_len, int ch,
                             size_t n_streams, const nae_sig* dst)
 {
-    if (!ctx) return NAE_ERR_INVALID;
-    const int rc = nae_stretch_n_check(ctx, flags, n_fft);
-    if (rc) return rc;
-    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft, 0,
-                              (flags & NAE_STRETCH_TRANSIENTS) != 0);
+    return nae_stretch_block_formant_f32(ctx, rate, pitch, flags, n_fft, 0, src, in_len, ch, n_streams, dst);
 }
 
 int nae_stretch_formant_lifter(int sample_rate, int n_fft)
@@ -741,65 +736,39 @@ int nae_stretch_formant_lifter(int sample_rate, int n_fft)
 int nae_stretch_block_formant_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, int lifter, const nae_sig* src, size_t in_len,
                                   int ch, size_t n_streams, const nae_sig* dst)
 {
-    if (!ctx) return NAE_ERR_INVALID;
-    int rc = nae_stretch_n_check(ctx, flags, n_fft);
-    if (rc) return rc;
-    if ((rc = nae_formant_check(ctx, n_fft, lifter))) return rc;
-    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft, lifter,
-                              (flags & NAE_STRETCH_TRANSIENTS) != 0);
+    nae_pv_opts o;
+    const int rc = nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, n_fft, lifter, nullptr, &o);
+    return rc ? rc : stretch_block_impl(ctx, o, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3);
 }
 
 int nae_stretch_block_formant_shift_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, int lifter, double formant_ratio,
                                         const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst)
 {
-    if (!ctx) return NAE_ERR_INVALID;
-    int rc = nae_stretch_n_check(ctx, flags, n_fft);
-    if (rc) return rc;
-    if ((rc = nae_formant_check(ctx, n_fft, lifter))) return rc;
-    return stretch_block_impl(ctx, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3, (flags & NAE_STRETCH_PHASE_LOCK) != 0, n_fft, lifter,
-                              (flags & NAE_STRETCH_TRANSIENTS) != 0, &formant_ratio);
+    nae_pv_opts o;
+    const int rc = nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, n_fft, lifter, &formant_ratio, &o);
+    return rc ? rc : stretch_block_impl(ctx, o, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3);
 }
 
-int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch,
-                            size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out,
-                            size_t* tile_frames)
+// pass 1 + 2 of a block call in tiles of 64 frames (pv_tile), the records copied to the host
+static int pv_tile_phase_impl(nae_ctx* ctx, const nae_pv_opts& o, double rate, double pitch, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                              int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out, size_t* tile_frames)
 {
-    return nae_debug_pv_tile_phase_ex(ctx, rate, pitch, 0u, src, in_len, ch, n_streams, dst_host, dst_capacity, n_tiles_out, tile_frames);
-}
-
-int nae_debug_pv_tile_phase_ex(nae_ctx* ctx, double rate, double pitch, unsigned flags, const nae_sig* src, size_t in_len, int ch,
-                               size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out,
-                               size_t* tile_frames)
-{
-    if (!ctx) return NAE_ERR_INVALID;
-    if (flags & ~NAE_STRETCH_PHASE_LOCK) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
-    return nae_debug_pv_tile_phase_n(ctx, rate, pitch, flags, NAE_FFT_N, src, in_len, ch, n_streams, dst_host, dst_capacity, n_tiles_out, tile_frames);
-}
-
-int nae_debug_pv_tile_phase_n(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, const nae_sig* src, size_t in_len, int ch,
-                              size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out, size_t* tile_frames)
-{
-    if (!ctx) return NAE_ERR_INVALID;
-    int rc = nae_stretch_n_check(ctx, flags, n_fft);
-    if (rc) return rc;
     if (!dst_host || !n_tiles_out || !tile_frames) return NAE_ERR_INVALID;
-    const bool lock = (flags & NAE_STRETCH_PHASE_LOCK) != 0;
-    rc = check_sig(ctx, src, "null source view");
+    int rc = check_sig(ctx, src, "null source view");
     if (rc) return rc;
     nae_stretch_plan pl;
-    rc = nae_stretch_plan_make_n(rate, pitch, n_fft, in_len, &pl);
-    if (rc) return nae_fail(ctx, rc, "rate/pitch outside the supported range");
+    if ((rc = nae_pv_plan_make(ctx, o, rate, pitch, in_len, &pl))) return rc;
     if (!pl.pv_on) return nae_fail(ctx, NAE_ERR_STATE, "phase vocoder stage is bypassed for these parameters");
     const int tile = ctx->pv_tile > 0 ? ctx->pv_tile : 64;
     const size_t n_tiles = (pl.frames + tile - 1) / tile;
     *n_tiles_out = n_tiles;
     *tile_frames = (size_t)tile;
-    const size_t bins = (size_t)n_fft / 2 + 1, pad = nae_pv_record_pad(n_fft);
+    const nae_pv_run run = nae_pv_resolve(o, pl);   // an _n plan with the stage on: never forced, the transient flag as given
+    const size_t bins = (size_t)o.n_fft / 2 + 1, pad = nae_pv_record_pad(o.n_fft);
     const size_t need = n_streams * ch * n_tiles * bins;
     if (dst_capacity < need) return nae_fail(ctx, NAE_ERR_INVALID, "destination too small");
-    const size_t ws_bytes = nae_pv_workspace_bytes(false, n_fft, pl.frames, ch, n_streams, tile);   // the records (the locked workspace begins with them)
-    rc = nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(lock, n_fft, pl.frames, ch, n_streams, tile));
-    if (rc) return rc;
+    const size_t ws_bytes = nae_pv_workspace_bytes(false, o.n_fft, pl.frames, ch, n_streams, tile);   // the records (the locked workspace begins with them)
+    if ((rc = nae_pv_reserve_ws(ctx, run, pl.frames, ch, n_streams, tile))) return rc;
     const nae_sig* pv_src = src;
     size_t pv_in_len = in_len;
     nae_sig mid{};
@@ -813,9 +782,8 @@ int nae_debug_pv_tile_phase_n(nae_ctx* ctx, double rate, double pitch, unsigned 
         pv_src = &mid;
         pv_in_len = pl.mid_len;
     }
-    nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, 0, nullptr, nullptr};
-    seg.transients = (flags & NAE_STRETCH_TRANSIENTS) != 0;
-    rc = nae_launch_pv_phase(ctx, lock, n_fft, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+    const nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, 0, nullptr, nullptr};
+    rc = nae_launch_pv_phase(ctx, run, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
     if (rc) return rc;
     std::vector<int32_t> tmp(ws_bytes / sizeof(int32_t));
     hipError_t e = hipMemcpyAsync(tmp.data(), ctx->ws_phase, ws_bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -824,6 +792,30 @@ int nae_debug_pv_tile_phase_n(nae_ctx* ctx, double rate, double pitch, unsigned 
     for (size_t rec = 0; rec < n_streams * ch * n_tiles; rec++)
         memcpy(dst_host + rec * bins, tmp.data() + rec * pad, bins * sizeof(int32_t));
     return NAE_OK;
+}
+
+int nae_debug_pv_tile_phase(nae_ctx* ctx, double rate, double pitch, const nae_sig* src, size_t in_len, int ch,
+                            size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out,
+                            size_t* tile_frames)
+{
+    return nae_debug_pv_tile_phase_ex(ctx, rate, pitch, 0u, src, in_len, ch, n_streams, dst_host, dst_capacity, n_tiles_out, tile_frames);
+}
+
+int nae_debug_pv_tile_phase_ex(nae_ctx* ctx, double rate, double pitch, unsigned flags, const nae_sig* src, size_t in_len, int ch,
+                               size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out,
+                               size_t* tile_frames)
+{
+    nae_pv_opts o;
+    const int rc = nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK, NAE_FFT_N, 0, nullptr, &o);
+    return rc ? rc : pv_tile_phase_impl(ctx, o, rate, pitch, src, in_len, ch, n_streams, dst_host, dst_capacity, n_tiles_out, tile_frames);
+}
+
+int nae_debug_pv_tile_phase_n(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, const nae_sig* src, size_t in_len, int ch,
+                              size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out, size_t* tile_frames)
+{
+    nae_pv_opts o;
+    const int rc = nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, n_fft, 0, nullptr, &o);
+    return rc ? rc : pv_tile_phase_impl(ctx, o, rate, pitch, src, in_len, ch, n_streams, dst_host, dst_capacity, n_tiles_out, tile_frames);
 }
 
 // ------------------------------------------------------------------------------------------------ K8
@@ -864,7 +856,7 @@ static int graph4_stages(nae_ctx* ctx, const nae_graph4* g, int mask)
     if (!g->in_a.base || !g->in_b.base || !g->mix_out.base) return nae_fail(ctx, NAE_ERR_INVALID, "nae_graph4_run: null signal");
     const nae_mix_front front{&g->in_a, &g->in_b, g->vol_a, g->vol_b};
     int rc = NAE_OK;
-    if (mask & 3) rc = stretch_block_impl(ctx, g->rate, g->pitch, &g->mix_out, g->S, 2, g->n_streams, &g->pitch_out, &front, mask & 3);
+    if (mask & 3) rc = stretch_block_impl(ctx, nae_pv_opts{}, g->rate, g->pitch, &g->mix_out, g->S, 2, g->n_streams, &g->pitch_out, &front, mask & 3);
     if (rc || !(mask & 4)) return rc;
     nae_stretch_plan pl;
     rc = nae_stretch_plan_make(g->rate, g->pitch, g->S, &pl);

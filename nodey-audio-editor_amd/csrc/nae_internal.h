@@ -110,27 +110,30 @@ struct nae_pv_segment {
     const uint32_t* carry_in;     // [n_streams*ch][520] phase behind frame f_origin-1 (null: zero)
     uint32_t* carry_out;          // receives the phase behind frame f_origin+f_count-1 (null: not wanted)
     bool carry_by_synth = false;  // the segment is synthesised as ONE tile and pass 3 itself writes carry_out (no pass 1)
-    bool transients = false;      // NAE_STRETCH_TRANSIENTS: onsets reset the synthesis phase (passes 1 and 3 prime from f_origin - 2)
 };
-// kernels_stft.hip: the vocoder's passes, unlocked or (lock, NAE_STRETCH_PHASE_LOCK) with identity phase locking on the kernels of kernels_pvlock.hip;
-// frame size n_fft (512 ... 4096; not 1024, or the debug key pv_any: the size-generic kernels of kernels_pv_any.hip).  lifter > 0: pass 3 preserves
-// the formants (nae_formant_lifter_eff; unlocked, at every size on the size-generic pass 3)
-size_t nae_pv_workspace_bytes(bool lock, int n_fft, size_t n_frames, int ch, size_t n_streams, int tile);
-int nae_launch_pv_phase(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
-                        size_t n_streams, int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg);
-int nae_launch_pv_synth(nae_ctx* ctx, bool lock, int n_fft, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch,
-                        size_t n_streams, int tile, int phase_tile, const uint32_t* phase_ws, const nae_sig* out,
-                        const nae_pv_segment* seg, int frames_per_step, int lifter = 0, double formant_ratio = 1.0);
-// the lifter pass 3 runs with ("Formant shift"): the envelope stage runs on the vocoder's frames when the envelope's ratio
-// rate_eff / formant_ratio is not 1.  With formant_ratio = 1 (the _formant entries) that is a plan with both the vocoder and the transposer
-// (rate_eff is snapped to 1 within 1e-6); the _formant_shift entries' plan (nae_stretch_plan_make_shift) has the vocoder stage forced on where
-// the stage runs at tempo 1.
+// What an entry's caller asked of the vocoder: lock = NAE_STRETCH_PHASE_LOCK, transients = NAE_STRETCH_TRANSIENTS, lifter 0 = no formant stage.
+// shift: a _formant_shift entry, whose plan (nae_stretch_plan_make_shift) may force the vocoder stage on; it says more than formant_ratio != 1 (the
+// _formant entries with a lifter and a rate-only change run the transposer alone, _formant_shift with ratio 1 the forced envelope stage).
+struct nae_pv_opts {
+    int n_fft = NAE_FFT_N, lifter = 0;
+    bool lock = false, transients = false, shift = false;
+    double formant_ratio = 1.0;
+};
+// nae_api.hip: the one statement of the entries' option rules, in this order: a null context NAE_ERR_INVALID (nothing touched); a flag outside
+// `allowed` (the _ex entries NAE_STRETCH_PHASE_LOCK, the others also NAE_STRETCH_TRANSIENTS) NAE_ERR_INVALID; a size outside 512 ... 4096, the lock
+// at a size other than 1024, NAE_ERR_UNSUPPORTED; a lifter outside 0 ... n_fft / 4 NAE_ERR_INVALID.  formant_ratio given: a _formant_shift entry.
+int nae_pv_opts_check(nae_ctx* ctx, unsigned flags, unsigned allowed, int n_fft, int lifter, const double* formant_ratio, nae_pv_opts* o);
+// nae_api.hip: the plan of a call with these options (the _shift plan of the _formant_shift entries, else the _n plan); a failure leaves its text
+int nae_pv_plan_make(nae_ctx* ctx, const nae_pv_opts& o, double rate, double pitch, size_t in_len, nae_stretch_plan* pl);
+// the envelope stage runs on the vocoder's frames ("Formant shift") when the envelope's ratio rate_eff / formant_ratio is not 1.
+// With formant_ratio = 1 (the _formant entries) that is a plan with both the vocoder and the transposer (rate_eff is snapped to 1 within 1e-6);
+// the _formant_shift entries' plan (nae_stretch_plan_make_shift) has the vocoder stage forced on where the stage runs at tempo 1.
 inline bool nae_formant_stage_on(double rate_eff, int lifter, double formant_ratio)
 {
     const double r = rate_eff / formant_ratio - 1.0;
     return lifter > 0 && (r <= -1e-6 || r >= 1e-6);
 }
-inline int nae_formant_lifter_eff(const nae_stretch_plan& pl, int lifter, double formant_ratio = 1.0)
+inline int nae_formant_lifter_eff(const nae_stretch_plan& pl, int lifter, double formant_ratio)
 {
     return pl.pv_on && nae_formant_stage_on(pl.rate_eff, lifter, formant_ratio) ? lifter : 0;
 }
@@ -138,33 +141,52 @@ inline int nae_formant_lifter_eff(const nae_stretch_plan& pl, int lifter, double
 inline float nae_formant_g(const nae_stretch_plan& pl, double formant_ratio) { return (float)(pl.rate_eff / formant_ratio); }
 // a plan with the vocoder stage forced on at tempo 1 (nae_stretch_plan_make_shift): Qs = Qa in every frame, the stage is the envelope pass alone
 inline bool nae_plan_forced(const nae_stretch_plan& pl) { return pl.pv_on && pl.tempo_eff == 1.0; }
+// The options as a plan runs them: what the tile choice, the two pass launchers and a handle's priming read (nothing works them out again)
+struct nae_pv_run {
+    int n_fft; bool lock;
+    int lifter;        // the effective lifter (nae_formant_lifter_eff): > 0 where pass 3 runs the envelope stage
+    float g;           // its transposer ratio (nae_formant_g); 0 with the stage off
+    bool forced;       // nae_plan_forced: the envelope pass alone — no pass 1, no scan, no phase workspace, nothing carried
+    bool transients;   // the flag, with the stage on and not forced (a forced stage has Qs = Qa: nothing to reset)
+};
+inline nae_pv_run nae_pv_resolve(const nae_pv_opts& o, const nae_stretch_plan& pl)
+{
+    const int lifter = nae_formant_lifter_eff(pl, o.lifter, o.formant_ratio);
+    const bool forced = nae_plan_forced(pl);
+    return {o.n_fft, o.lock, lifter, lifter > 0 ? nae_formant_g(pl, o.formant_ratio) : 0.0f, forced, o.transients && pl.pv_on && !forced};
+}
 // The kernels a vocoder call runs, for the tile choice of a block call, nae_launch_pv_phase and nae_launch_pv_synth:
 //   pass 1  kShipped: pv_phase_kernel (1024 points); kAny: pv_any_phase_kernel<N> (kernels_pv_any.hip); kLock: pvlock_map_kernel and its scan;
 //   pass 3  kShipped: the pipeline (kernels_pvpipe.hip);  kAny: pv_any_synth_kernel<N>;                   kLock: pvlock_synth_kernel.
-// Locked calls (1024 only: the callers check) run the locked kernels; unlocked calls at other sizes, or under the debug key pv_any, the size-generic
-// ones.  Pass 1 does not depend on the lifter.  Unlocked 1024-point calls with formant preservation (lifter_eff > 0) run the shipped pass 1 and
-// the size-generic pass 3: the pipeline has no formant stage, and the two passes share the record layout.  Unlocked calls with transient
+// Locked calls (1024 only: nae_pv_opts_check) run the locked kernels; unlocked calls at other sizes, or under the debug key pv_any, the size-generic
+// ones.  Pass 1 does not depend on the lifter.  Unlocked 1024-point calls with formant preservation (nae_pv_run::lifter > 0) run the shipped pass 1
+// and the size-generic pass 3: the pipeline has no formant stage, and the two passes share the record layout.  Unlocked calls with transient
 // preservation run the size-generic passes at every size, 1024 included: the shipped pass 1 and the pipeline have no onset detector; locked
 // ones the transient instantiations of the locked kernels.
-//   kEnv (pass 3 only; a forced plan, nae_plan_forced): pv_env_kernel<N> (kernels_pvenv.hip) — there is no pass 1 and no scan, and the lock and
+//   kEnv (a forced plan, nae_plan_forced): pass 3 is pv_env_kernel<N> (kernels_pvenv.hip) — there is no pass 1 and no scan, and the lock and
 //   transient preservation change nothing (Qs = Qa either way).
+// Asked at each launch, not kept in nae_pv_run: the debug key may change during a handle's life.
 enum class PvKernels { kShipped, kAny, kLock, kEnv };
 struct nae_pv_route { PvKernels pass1, pass3; };
-inline nae_pv_route nae_pv_route_of(const nae_ctx* ctx, bool lock, int n_fft, int lifter_eff, bool transients = false, bool forced = false)
+inline nae_pv_route nae_pv_route_of(const nae_ctx* ctx, const nae_pv_run& r)
 {
-    if (forced) return {PvKernels::kEnv, PvKernels::kEnv};
-    if (lock) return {PvKernels::kLock, PvKernels::kLock};
-    const PvKernels pass1 = n_fft != NAE_FFT_N || ctx->dbg_pv_any || transients ? PvKernels::kAny : PvKernels::kShipped;
-    return {pass1, lifter_eff > 0 ? PvKernels::kAny : pass1};
+    if (r.forced) return {PvKernels::kEnv, PvKernels::kEnv};
+    if (r.lock) return {PvKernels::kLock, PvKernels::kLock};
+    const PvKernels pass1 = r.n_fft != NAE_FFT_N || ctx->dbg_pv_any || r.transients ? PvKernels::kAny : PvKernels::kShipped;
+    return {pass1, r.lifter > 0 ? PvKernels::kAny : pass1};
 }
+// kernels_stft.hip: the vocoder's passes on the kernels nae_pv_route_of says, and their phase workspace (nae_pv_reserve_ws: none for a forced plan)
+size_t nae_pv_workspace_bytes(bool lock, int n_fft, size_t n_frames, int ch, size_t n_streams, int tile);
+int nae_pv_reserve_ws(nae_ctx* ctx, const nae_pv_run& r, size_t n_frames, int ch, size_t n_streams, int tile);
+int nae_launch_pv_phase(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                        int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg);
+int nae_launch_pv_synth(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                        int tile, int phase_tile, uint32_t* phase_ws, const nae_sig* out, const nae_pv_segment* seg, int frames_per_step);
 // kernels_pv_any.hip: the vocoder sizes (512, 1024, 2048, 4096), the record length of a size (int32: N/2 + 1 padded to a multiple of 8), the
-// pass-3 waves a CU holds on the size-generic kernels (PvAny<N>::kResident3; formant: of the formant pass 3)
+// pass-3 waves a CU holds on the kernels `pass3` (kAny: PvAny<N, formant, transients>::kResident3; kEnv: PvEnv<N>::kResident; kLock: 16)
 bool nae_pv_size_ok(int n_fft);
 size_t nae_pv_record_pad(int n_fft);
-int nae_pv_resident3(nae_ctx* ctx, int n_fft, bool formant, bool transients = false);
-int nae_pvenv_resident(nae_ctx* ctx, int n_fft);                    // kernels_pvenv.hip: the waves of pv_env_kernel<n_fft> a CU holds (PvEnv<N>::kResident)
-int nae_stretch_n_check(nae_ctx* ctx, unsigned flags, int n_fft);   // nae_api.hip: flags and size of the _n entries
-int nae_formant_check(nae_ctx* ctx, int n_fft, int lifter);         // nae_api.hip: the lifter of the _formant entries
+int nae_pv_resident(nae_ctx* ctx, const nae_pv_run& r, PvKernels pass3);
 int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t src_len, int ch,
                         size_t n_streams, const float* d_tab, const nae_sig* out, size_t j_begin, size_t j_end);
 int nae_launch_mix_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* a, const nae_sig* b, float va, float vb,

@@ -14,13 +14,9 @@ struct nae_stretch {
     nae_ctx* ctx;
     int sample_rate, ch;
     double rate, pitch;
-    bool lock = false;            // NAE_STRETCH_PHASE_LOCK (nae_stretch_create_ex)
-    int n_fft = NAE_FFT_N;        // vocoder frame size, hop n_fft / 4 (nae_stretch_create_n)
-    int lifter = 0;               // formant preservation's lifter, 0 = off (nae_stretch_create_formant)
-    bool transients = false;      // NAE_STRETCH_TRANSIENTS (nae_stretch_create_n / _formant)
-    double formant_ratio = 1.0;   // the formant shift (nae_stretch_create_formant_shift); shift: the plan is nae_stretch_plan_make_shift's
-    bool shift = false;
+    nae_pv_opts opts;             // what the nae_stretch_create* entry asked for
     nae_stretch_plan pl{};        // parameters (in_len = 0)
+    nae_pv_run run{};             // the options as this plan runs them (none of it depends on in_len)
     DevFifo in;                   // interleaved input, sample-frames
     // phase vocoder
     size_t blocks_done = 0;       // hop blocks produced == frames folded into the carried phase
@@ -75,19 +71,17 @@ int stretch_pv_stage(nae_stretch* h, const nae_stretch_plan& pl, const nae_sig& 
     const bool one_tile = ctx->pv_tile <= 0 && count <= 256;
     const int tile = one_tile ? (int)count : (ctx->pv_tile > 0 ? ctx->pv_tile : 64);
     const int fps = one_tile ? 4 : 1;
-    const bool forced = nae_plan_forced(pl);      // the envelope pass: no phase workspace and nothing carried
-    int rc = forced ? NAE_OK : nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(h->lock, h->n_fft, count, ch, 1, tile));
+    const bool forced = h->run.forced;            // the envelope pass: no phase workspace and nothing carried
+    int rc = nae_pv_reserve_ws(ctx, h->run, count, ch, 1, tile);
     if (rc) return rc;
     for (int i = 0; i < 2 && !forced; i++)
-        if (!h->carry[i] && hipMalloc((void**)&h->carry[i], (size_t)ch * nae_pv_record_pad(h->n_fft) * sizeof(uint32_t)) != hipSuccess)
+        if (!h->carry[i] && hipMalloc((void**)&h->carry[i], (size_t)ch * nae_pv_record_pad(h->opts.n_fft) * sizeof(uint32_t)) != hipSuccess)
             return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(carry)");
-    nae_pv_segment seg{(long long)h->blocks_done, (long long)count, (long long)F_r, limit,
-                       h->blocks_done && !forced ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
-    seg.transients = h->transients;
-    rc = nae_launch_pv_phase(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+    const nae_pv_segment seg{(long long)h->blocks_done, (long long)count, (long long)F_r, limit,
+                             h->blocks_done && !forced ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
+    rc = nae_launch_pv_phase(ctx, h->run, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
     if (rc) return rc;
-    rc = nae_launch_pv_synth(ctx, h->lock, h->n_fft, &pl, &src, src_len, ch, 1, tile, tile, static_cast<const uint32_t*>(ctx->ws_phase), &dst, &seg, fps,
-                             h->lifter, h->formant_ratio);
+    rc = nae_launch_pv_synth(ctx, h->run, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
     if (rc) return rc;
     h->carry_cur ^= 1;
     h->blocks_done = B_r;
@@ -95,21 +89,18 @@ int stretch_pv_stage(nae_stretch* h, const nae_stretch_plan& pl, const nae_sig& 
 }
 
 // frames in front of a segment that its passes re-analyse: 1, or 2 with transient preservation (onset(f) reads frames f - 2 .. f)
-inline long long prime_frames(const nae_stretch* h) { return h->transients ? 2 : 1; }
+inline long long prime_frames(const nae_stretch* h) { return h->run.transients ? 2 : 1; }
 
 int stretch_process(nae_stretch* h)
 {
     nae_ctx* ctx = h->ctx;
     const int ch = h->ch;
     const nae_stretch_plan& pl = h->pl;
-    const size_t hop = (size_t)h->n_fft / 4;     // hop blocks of the vocoder stage
+    const int n_fft = h->opts.n_fft;
+    const size_t hop = (size_t)n_fft / 4;        // hop blocks of the vocoder stage
     DevFifo &in = h->in, &mid = h->mid, &out = h->out;
     nae_stretch_plan fin{};
-    if (h->flushed) {
-        int rc = h->shift ? nae_stretch_plan_make_shift(h->rate, h->pitch, h->formant_ratio, h->lifter, h->n_fft, in.total, &fin)
-                          : nae_stretch_plan_make_n(h->rate, h->pitch, h->n_fft, in.total, &fin);
-        if (rc) return rc;
-    }
+    if (const int rc = h->flushed ? nae_pv_plan_make(ctx, h->opts, h->rate, h->pitch, in.total, &fin) : NAE_OK) return rc;
     // ---- neither stage: the node is a wire (a formant shift at tempo 1 has the vocoder stage forced on and does not come here)
     if (!pl.pv_on && !pl.rs_on) {
         if (in.total == out.total) return NAE_OK;
@@ -144,7 +135,7 @@ int stretch_process(nae_stretch* h)
             B_r = (fin.out_len + hop - 1) / hop;
             out_limit = (long long)fin.out_len;
         } else {
-            F_r = frames_available(pl, h->n_fft, mid.total);
+            F_r = frames_available(pl, n_fft, mid.total);
             B_r = F_r >= 3 ? F_r - 3 : 0;
             out_limit = (long long)1 << 60;
         }
@@ -155,7 +146,7 @@ int stretch_process(nae_stretch* h)
             rc = stretch_pv_stage(h, pl, mid.view(), mid.total, F_r, B_r, out_limit, out.view());
             if (rc) return rc;
             out.total = produced_total;
-            mid.drop(frame_start_host(pl, h->n_fft, (long long)B_r - prime_frames(h)));
+            mid.drop(frame_start_host(pl, n_fft, (long long)B_r - prime_frames(h)));
         }
         return NAE_OK;
     }
@@ -169,7 +160,7 @@ int stretch_process(nae_stretch* h)
             B_r = (fin.mid_len + hop - 1) / hop;
             mid_limit = (long long)fin.mid_len;
         } else {
-            F_r = frames_available(pl, h->n_fft, in.total);
+            F_r = frames_available(pl, n_fft, in.total);
             B_r = F_r >= 3 ? F_r - 3 : 0;
             mid_limit = (long long)1 << 60;
         }
@@ -187,7 +178,7 @@ int stretch_process(nae_stretch* h)
             dst.total = produced_total;
             // input still needed: from the start of frame B_r - 1 (it primes the next call's phase difference; with transients also
             // frame B_r - 2, which primes its onset rule)
-            in.drop(frame_start_host(pl, h->n_fft, (long long)B_r - prime_frames(h)));
+            in.drop(frame_start_host(pl, n_fft, (long long)B_r - prime_frames(h)));
         }
     }
     // ---- stage 2: rate transposer over the outputs whose 16 taps are known
@@ -221,46 +212,8 @@ int stretch_process(nae_stretch* h)
 
 extern "C" {
 
-int nae_stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, nae_stretch** h)
+static int stretch_create(nae_ctx* ctx, const nae_pv_opts& o, int sample_rate, int channels, float rate, float pitch, nae_stretch** h)
 {
-    return nae_stretch_create_ex(ctx, sample_rate, channels, rate, pitch, 0u, h);
-}
-
-int nae_stretch_create_ex(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, nae_stretch** h)
-{
-    if (!ctx || !h) return NAE_ERR_INVALID;
-    if (flags & ~NAE_STRETCH_PHASE_LOCK) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
-    return nae_stretch_create_n(ctx, sample_rate, channels, rate, pitch, flags, NAE_FFT_N, h);
-}
-
-int nae_stretch_create_n(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, nae_stretch** h)
-{
-    return nae_stretch_create_formant(ctx, sample_rate, channels, rate, pitch, flags, n_fft, 0, h);
-}
-
-static int stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
-                          const double* formant_ratio, nae_stretch** h);
-
-int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
-                               nae_stretch** h)
-{
-    return stretch_create(ctx, sample_rate, channels, rate, pitch, flags, n_fft, lifter, nullptr, h);
-}
-
-int nae_stretch_create_formant_shift(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
-                                     double formant_ratio, nae_stretch** h)
-{
-    return stretch_create(ctx, sample_rate, channels, rate, pitch, flags, n_fft, lifter, &formant_ratio, h);
-}
-
-// formant_ratio given: the _formant_shift entry, with its own plan
-static int stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
-                          const double* formant_ratio, nae_stretch** h)
-{
-    if (!ctx || !h) return NAE_ERR_INVALID;
-    int chk = nae_stretch_n_check(ctx, flags, n_fft);
-    if (chk) return chk;
-    if ((chk = nae_formant_check(ctx, n_fft, lifter))) return chk;
     (void)nae_use_device(ctx);
     *h = nullptr;
     // audio-velocity.cpp:371-379 rejects rates outside 8..48 kHz for SoundTouch; the vocoder has no such
@@ -268,8 +221,7 @@ static int stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rat
     if (sample_rate != 0 && (sample_rate < 8000 || sample_rate > 48000)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "Unsupported sample rate: requires 8000..48000 Hz");
     if (channels != 1 && channels != 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
     nae_stretch_plan pl;
-    int rc = formant_ratio ? nae_stretch_plan_make_shift(rate, pitch, *formant_ratio, lifter, n_fft, 0, &pl) : nae_stretch_plan_make_n(rate, pitch, n_fft, 0, &pl);
-    if (rc) return nae_fail(ctx, rc, formant_ratio ? "rate/pitch/formant ratio outside the supported range" : "rate/pitch outside the supported range");
+    if (const int rc = nae_pv_plan_make(ctx, o, rate, pitch, 0, &pl)) return rc;
     nae_stretch* s = new (std::nothrow) nae_stretch();
     if (!s) return NAE_ERR_NOMEM;
     s->ctx = ctx;
@@ -277,16 +229,47 @@ static int stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rat
     s->ch = channels;
     s->rate = rate;
     s->pitch = pitch;
-    s->lock = (flags & NAE_STRETCH_PHASE_LOCK) != 0;
-    s->transients = pl.pv_on && !nae_plan_forced(pl) && (flags & NAE_STRETCH_TRANSIENTS) != 0;   // a forced stage has Qs = Qa: nothing to reset
-    if (formant_ratio) { s->formant_ratio = *formant_ratio; s->shift = true; }
-    s->n_fft = n_fft;
-    s->lifter = lifter;
+    s->opts = o;
     s->pl = pl;
+    s->run = nae_pv_resolve(o, pl);
     s->in.width = s->mid.width = s->out.width = (size_t)channels;
     s->mid.planar = !pl.rs_first;
     *h = s;
     return NAE_OK;
+}
+
+// the create entries: a null handle pointer NAE_ERR_INVALID first, the options checked into a record (nae_pv_opts_check), then the one implementation
+int nae_stretch_create(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, nae_stretch** h)
+{
+    return nae_stretch_create_ex(ctx, sample_rate, channels, rate, pitch, 0u, h);
+}
+
+int nae_stretch_create_ex(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, nae_stretch** h)
+{
+    nae_pv_opts o;
+    const int rc = h ? nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK, NAE_FFT_N, 0, nullptr, &o) : NAE_ERR_INVALID;
+    return rc ? rc : stretch_create(ctx, o, sample_rate, channels, rate, pitch, h);
+}
+
+int nae_stretch_create_n(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, nae_stretch** h)
+{
+    return nae_stretch_create_formant(ctx, sample_rate, channels, rate, pitch, flags, n_fft, 0, h);
+}
+
+int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
+                               nae_stretch** h)
+{
+    nae_pv_opts o;
+    const int rc = h ? nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, n_fft, lifter, nullptr, &o) : NAE_ERR_INVALID;
+    return rc ? rc : stretch_create(ctx, o, sample_rate, channels, rate, pitch, h);
+}
+
+int nae_stretch_create_formant_shift(nae_ctx* ctx, int sample_rate, int channels, float rate, float pitch, unsigned flags, int n_fft, int lifter,
+                                     double formant_ratio, nae_stretch** h)
+{
+    nae_pv_opts o;
+    const int rc = h ? nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, n_fft, lifter, &formant_ratio, &o) : NAE_ERR_INVALID;
+    return rc ? rc : stretch_create(ctx, o, sample_rate, channels, rate, pitch, h);
 }
 
 static int stretch_append(nae_stretch* h, const float* p, size_t S, bool host)

@@ -131,26 +131,32 @@ __device__ __forceinline__ void phase_inc(const uint32_t (&qa)[9], const uint32_
 
 } // namespace nae
 
-// kernels_pvpipe.hip: pass 3 (PvParams as nae_launch_pv_synth built it)
-int nae_launch_pv_pipe(nae_ctx* ctx, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, const uint32_t* phase_ws,
-                       const nae::OutViewD& out, bool unit_stride, int frames_per_step);
+// What the vocoder's leaf launchers share, as nae_launch_pv_phase / nae_launch_pv_synth (kernels_stft.hip) built it from the nae_pv_run.  Pass 1
+// has no `out` and writes `phase_ws`, pass 3 reads it; lifter > 0 (pass 3): formant preservation with that lifter and transposer ratio g ("Formant
+// preservation"); transients: passes 1 and 3 detect onsets and reset Qs there, pass 1 flags its records and the scan is the segmented one
+namespace nae {
+struct PvJob {
+    int n_fft;
+    PvParams p;
+    SigViewD src; OutViewD out;
+    long long n_sc; bool unit_stride;
+    uint32_t* phase_ws;
+    int lifter; float g; bool transients;
+};
+}
+
+// kernels_pvpipe.hip: pass 3 at 1024 points (no lifter, no transients)
+int nae_launch_pv_pipe(nae_ctx* ctx, const nae::PvJob& j, int frames_per_step);
 // kernels_pvlock.hip: the locked passes L1 + L2 (the maps of tiles [0, n_needed), then the records in phase_ws; maps / sig16: the tile maps'
 // c and sigma, nae_pv_workspace_bytes) and pass L3
-int nae_launch_pvlock_phase(nae_ctx* ctx, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride, int n_needed,
-                            uint32_t* phase_ws, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out, bool transients);
-int nae_launch_pvlock_synth(nae_ctx* ctx, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride,
-                            const uint32_t* phase_ws, const nae::OutViewD& out, int lifter, float g, bool transients);
+int nae_launch_pvlock_phase(nae_ctx* ctx, const nae::PvJob& j, int n_needed, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in,
+                            uint32_t* carry_out);
+int nae_launch_pvlock_synth(nae_ctx* ctx, const nae::PvJob& j);
 // kernels_pv_any.hip: pass 1 and pass 3 of the vocoder at n_fft = 512 ... 4096 (records of nae_pv_record_pad(n_fft) int32), and pass 2 of the
-// unlocked vocoder after either pass 1 (the records of tiles [0, n_read) in phase_ws; `name`: the profile name).  transients: pass 1 and pass 3
-// detect onsets and reset Qs there, pass 1 flags its records and the scan is the segmented one ("Transient preservation")
-int nae_launch_pvany_phase(nae_ctx* ctx, int n_fft, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride,
-                           uint32_t* phase_ws, bool transients);
+// unlocked vocoder after either pass 1 (the records of tiles [0, n_read) in phase_ws; `name`: the profile name)
+int nae_launch_pvany_phase(nae_ctx* ctx, const nae::PvJob& j);
 int nae_launch_pv_scan(nae_ctx* ctx, int n_fft, const char* name, uint32_t* phase_ws, long long n_sc, int n_tiles, const uint32_t* carry_in,
                        uint32_t* carry_out, int n_read, bool segmented);
-// lifter > 0 (pass 3): formant preservation with that lifter and transposer ratio g ("Formant preservation"); 0: off
-int nae_launch_pvany_synth(nae_ctx* ctx, int n_fft, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride,
-                           const uint32_t* phase_ws, const nae::OutViewD& out, int lifter, float g, bool transients);
+int nae_launch_pvany_synth(nae_ctx* ctx, const nae::PvJob& j);
 // kernels_pvenv.hip: the envelope pass of a forced plan (formant shift at tempo 1) — analysis, gain with lifter and ratio g, synthesis; no phases
-int nae_launch_pvenv(nae_ctx* ctx, int n_fft, const nae::PvParams& p, const nae::SigViewD& src, long long n_sc, bool unit_stride,
-                     const nae::OutViewD& out, int lifter, float g);
-
+int nae_launch_pvenv(nae_ctx* ctx, const nae::PvJob& j);
