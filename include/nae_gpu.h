@@ -39,7 +39,9 @@ extern "C" {
  *   512 ... 4096); nae_stretch_formant_lifter, nae_stretch_block_formant_f32 and nae_stretch_create_formant (formant-preserving pitch
  *   shift); NAE_STRETCH_TRANSIENTS with the _n and _formant entries (transient preservation), which a caller probes for by its return code:
  *   a library without it answers NAE_ERR_INVALID; nae_stretch_plan_make_shift, nae_stretch_block_formant_shift_f32 and
- *   nae_stretch_create_formant_shift (formant shift independent of the pitch). */
+ *   nae_stretch_create_formant_shift (formant shift independent of the pitch); NAE_STRETCH_LINK_CHANNELS with the _n, _formant and
+ *   _formant_shift entries (one onset decision and one phase-lock region map per stereo stream), probed by return code as
+ *   NAE_STRETCH_TRANSIENTS is. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -329,6 +331,16 @@ int nae_stretch_create_formant_shift(nae_ctx* ctx, int sample_rate, int channels
  * changes nothing.  Integer phases are bit-exact against the CPU
  * statement (tests/pv_transient/ref_pv_tr.c) and independent of the tiling; a handle's output equals the block call's. */
 #define NAE_STRETCH_TRANSIENTS 4u
+/* NAE_STRETCH_LINK_CHANNELS: channel link ("Channel link"), a flag of the _n, _formant and _formant_shift entries (block, create
+ * and nae_debug_pv_tile_phase_n).  On a stereo stream the onset rule of NAE_STRETCH_TRANSIENTS and the peaks and regions of
+ * NAE_STRETCH_PHASE_LOCK read the linked power Pl[k] = 0.5f (P0[k] + P1[k]) of the two channels in place of each channel's own, so both
+ * channels reset at the same frames and lock to the same bins; each channel keeps its own analysis phase, increments, magnitudes and
+ * synthesis phase.  The link is effective with ch == 2, the vocoder stage on and not forced, and the lock or transient preservation
+ * effective; in every other case (mono, neither option, a forced stage, no vocoder stage) the call gives the bits of the call without
+ * the flag.  With the lock at a size other than 1024 the call stays NAE_ERR_UNSUPPORTED; the _ex entries answer NAE_ERR_INVALID; bits 2
+ * and 8 stay unknown flags.  Integer phases are bit-exact against the CPU statement (tests/pv_link/ref_pv_link.c) and independent of the
+ * tiling; a handle's output equals the block call's. */
+#define NAE_STRETCH_LINK_CHANNELS 16u
 int nae_stretch_put(nae_stretch* h, const float* interleaved, size_t S);
 int nae_stretch_put_host(nae_stretch* h, const float* interleaved_host, size_t S);
 int nae_stretch_flush(nae_stretch* h);

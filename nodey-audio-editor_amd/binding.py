@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
 
 STRETCH_PHASE_LOCK = 1       # NAE_STRETCH_PHASE_LOCK (include/nae_gpu.h)
 STRETCH_TRANSIENTS = 4       # NAE_STRETCH_TRANSIENTS (include/nae_gpu.h): the _n and _formant entries only
+STRETCH_LINK_CHANNELS = 16   # NAE_STRETCH_LINK_CHANNELS: one onset decision and one lock map per stereo stream; the same entries
 FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX = 0.25, 4.0   # NAE_FORMANT_SHIFT_MIN / _MAX (include/nae_dsp_spec.h): the range of formant_ratio
 
 
@@ -445,18 +446,19 @@ class Context:
 
     def stretch_block(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig,
                       phase_lock: bool = False, n_fft: int = 1024, formant: int = 0, transients: bool = False,
-                      formant_ratio: Optional[float] = None):
+                      formant_ratio: Optional[float] = None, link_channels: bool = False):
         """formant: the lifter of formant preservation (formant_lifter() gives the default), 0 = off; transients: transient preservation
         (nae_stretch_block_n_f32 at every size); formant_ratio: the formant shift with that lifter (nae_stretch_block_formant_shift_f32;
-        dst receives stretch_plan(..., formant=, formant_ratio=).out_len frames)"""
-        flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0)
+        dst receives stretch_plan(..., formant=, formant_ratio=).out_len frames); link_channels: the channel link (the _n entries, as
+        transients)"""
+        flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0) | (STRETCH_LINK_CHANNELS if link_channels else 0)
         if formant_ratio is not None:
             self._ck(self.lib.nae_stretch_block_formant_shift_f32(self.h, rate, pitch, flags, n_fft, formant, formant_ratio,
                                                                   C.byref(src), in_len, ch, n_streams, C.byref(dst)))
         elif formant:
             self._ck(self.lib.nae_stretch_block_formant_f32(self.h, rate, pitch, flags, n_fft, formant,
                                                             C.byref(src), in_len, ch, n_streams, C.byref(dst)))
-        elif n_fft != 1024 or transients:
+        elif n_fft != 1024 or transients or link_channels:
             self._ck(self.lib.nae_stretch_block_n_f32(self.h, rate, pitch, flags, n_fft, C.byref(src), in_len,
                                                       ch, n_streams, C.byref(dst)))
         elif phase_lock:
@@ -466,14 +468,15 @@ class Context:
             self._ck(self.lib.nae_stretch_block_f32(self.h, rate, pitch, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
     def debug_pv_tile_phase(self, rate: float, pitch: float, src: Sig, in_len: int, ch: int, n_streams: int,
-                            phase_lock: bool = False, n_fft: int = 1024, transients: bool = False):
+                            phase_lock: bool = False, n_fft: int = 1024, transients: bool = False, link_channels: bool = False):
         pl = self.stretch_plan(rate, pitch, in_len, n_fft)
         bins = n_fft // 2 + 1
         cap = n_streams * ch * (pl.frames + 1) * bins
         out = np.zeros(cap, np.int32)
         nt, tf = C.c_size_t(), C.c_size_t()
-        if n_fft != 1024 or transients:
-            flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0)
+        if n_fft != 1024 or transients or link_channels:
+            flags = ((STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0)
+                     | (STRETCH_LINK_CHANNELS if link_channels else 0))
             self._ck(self.lib.nae_debug_pv_tile_phase_n(self.h, rate, pitch, flags, n_fft, C.byref(src), in_len,
                                                         ch, n_streams, out.ctypes.data, cap, C.byref(nt), C.byref(tf)))
             return out[: n_streams * ch * nt.value * bins].reshape(n_streams, ch, nt.value, bins), tf.value
@@ -534,15 +537,16 @@ class Stretcher:
     receive."""
 
     def __init__(self, ctx: Context, sample_rate: int, channels: int, rate: float, pitch: float, phase_lock: bool = False,
-                 n_fft: int = 1024, formant: int = 0, transients: bool = False, formant_ratio: Optional[float] = None):
+                 n_fft: int = 1024, formant: int = 0, transients: bool = False, formant_ratio: Optional[float] = None,
+                 link_channels: bool = False):
         self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
-        flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0)
+        flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0) | (STRETCH_LINK_CHANNELS if link_channels else 0)
         if formant_ratio is not None:
             ctx._ck(ctx.lib.nae_stretch_create_formant_shift(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, formant, formant_ratio,
                                                              C.byref(self.h)))
         elif formant:
             ctx._ck(ctx.lib.nae_stretch_create_formant(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, formant, C.byref(self.h)))
-        elif n_fft != 1024 or transients:
+        elif n_fft != 1024 or transients or link_channels:
             ctx._ck(ctx.lib.nae_stretch_create_n(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, C.byref(self.h)))
         else:
             ctx._ck(ctx.lib.nae_stretch_create_ex(ctx.h, sample_rate, channels, rate, pitch, flags, C.byref(self.h)))

@@ -16,6 +16,10 @@
 // kTransient (NAE_STRETCH_TRANSIENTS; DESIGN.md §3, "Transient preservation"): passes 1 and 3 also keep P_{f-1} (ST floats per wave) in LDS,
 // count the rising bins of each row with a ballot, and at an onset restart the sum / Qs from Qa; pass 1 flags the record in slot B and pass 2 is
 // the segmented scan.  Waves per workgroup: pass 1 8 / 8 / 7 / 3 at N = 512 ... 4096, pass 3 8 / 8 / 5 / 2 (with formants 8 / 8 / 4 / 2).
+// kLink (NAE_STRETCH_LINK_CHANNELS with kTransient; DESIGN.md §3, "Channel link"): the wave of channel c also analyses channel c ^ 1 of its stream in
+// front of each frame — a second pva_analyse into the same scratch, of which it keeps the power row (ST floats per wave in LDS) — and the onset rule
+// reads Pl = 0.5 (P^0 + P^1) in place of P, so both channels' waves take the same decisions; pass 2 is unchanged.  Waves per workgroup: pass 1
+// 8 / 8 / 6 / 3, pass 3 8 / 8 / 4 / 2 (with formants 8 / 7 / 4 / 2).
 // N = 1024 runs the shipped passes 1 and 3 unless the debug key pv_any (or, pass 3, a lifter; or transients) asks for these: nae_pv_route_of.  The host
 // decisions (records needed, base records, synthesis fields, workspace) are kernels_stft.hip's nae_launch_pv_phase / nae_launch_pv_synth.
 #include "pv_any.h"
@@ -53,6 +57,35 @@ __device__ __forceinline__ int pva_rises(cf x, int k, float* pp, bool counted)
     return __popcll(__ballot(rise));
 }
 
+// channel link ("Channel link"): the power row of the stream's other channel for frame start s — its analysis into the wave's scratch,
+// P of bin lane + 64 r into po[64 r] (read back by the same lane only) — after which the scratch is free for the wave's own frame
+template <int N, bool kUnit>
+__device__ __forceinline__ void pva_other_power(cf* scr, const cf* w512l, const SpecAnyTables& tb, const ChanView& in2, long long s, float* po, int lane)
+{
+    using P = PvAny<N>;
+    using Gm = typename P::Gm;
+    pva_analyse<N, kUnit>(scr, w512l, tb, in2, s, lane);
+#pragma unroll 2
+    for (int r = 0; r < P::NB; r++) {
+        const int k = lane + 64 * r;
+        const cf x = any_rfft_bin<Gm>(scr, tb.tn, k < P::B ? k : P::M);
+        po[64 * r] = x.x * x.x + x.y * x.y;
+    }
+    wave_lds_sync();
+}
+
+// pva_rises on the linked power Pl = 0.5 (P^0 + P^1): own is this channel's P, other the other channel's (one IEEE add — it commutes, so either
+// channel's wave gets the bits of P^0 + P^1 — then one product); pp keeps Pl_{f-1}
+template <int N>
+__device__ __forceinline__ int pva_rises_linked(cf x, int k, float* pp, float other, bool counted)
+{
+    const float own = x.x * x.x + x.y * x.y;
+    const float P = 0.5f * (own + other);
+    const bool rise = counted && k < N / 2 + 1 && P > NAE_TRANSIENT_RISE * *pp && P > NAE_TRANSIENT_FLOOR * (float)N;
+    *pp = P;
+    return __popcll(__ballot(rise));
+}
+
 // rule 4: frame f is an onset iff f >= 2, it is high and the frame before is not (high: DEN * count >= NUM * B)
 template <int N>
 __device__ __forceinline__ bool pva_high(int count)
@@ -63,16 +96,18 @@ __device__ __forceinline__ bool pva_high(int count)
 // ------------------------------------------------------------------------------------------------ pass 1
 // sums[(sc * n_tiles + tile) * PAD + k].  kTransient: an onset frame of the tile restarts the sum at its Qa, and the record's slot B is 1 when the
 // tile holds an onset (the summary (r, S) of DESIGN.md §3); frames f0 - 2 and f0 - 1 prime P and "high"
-template <int N, bool kUnit, bool kTransient = false>
-__global__ __launch_bounds__(64 * (PvAny<N, false, kTransient>::kWaves1)) void pv_any_phase_kernel(SigViewD src, PvParams p, long long n_items,
+template <int N, bool kUnit, bool kTransient = false, bool kLink = false>
+__global__ __launch_bounds__(64 * (PvAny<N, false, kTransient, kLink>::kWaves1)) void pv_any_phase_kernel(SigViewD src, PvParams p, long long n_items,
                                                                              uint32_t* __restrict__ sums, SpecAnyTables tb)
 {
-    using P = PvAny<N, false, kTransient>;
+    static_assert(kTransient || !kLink, "unlocked, the link acts on the onset rule only");
+    using P = PvAny<N, false, kTransient, kLink>;
     using Gm = typename P::Gm;
     __shared__ __attribute__((aligned(16))) cf w512l[512];
     __shared__ __attribute__((aligned(16))) cf scratch[P::kWaves1 * Gm::SCR];
     __shared__ uint32_t state[P::kWaves1 * 2 * P::ST];
     __shared__ float pprev[kTransient ? P::kWaves1 * P::ST : 1];   // transients: P_{f-1} of bin lane + 64 r
+    __shared__ float pother[kLink ? P::kWaves1 * P::ST : 1];       // link: the other channel's P_f
     for (int i = threadIdx.x; i < 512; i += 64 * P::kWaves1) w512l[i] = tb.w512[i];
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -85,9 +120,11 @@ __global__ __launch_bounds__(64 * (PvAny<N, false, kTransient>::kWaves1)) void p
     uint32_t* qp = state + wave_id() * 2 * P::ST + lane;  // [r * 64]: Qa_{f-1} of bin lane + 64 r
     uint32_t* acc = qp + P::ST;                          //           the tile's sum of increments
     float* pp = pprev + (kTransient ? wave_id() * P::ST + lane : 0);
+    float* po = pother + (kLink ? wave_id() * P::ST + lane : 0);
     const long long s_idx = sc / p.ch;
     const int c = (int)(sc % p.ch);
     const ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
+    const ChanView in2{src.base + s_idx * src.ss + (c ^ 1) * src.cs, src.fs, p.in_len};   // link (ch == 2): the stream's other channel
     const long long f0 = p.f_origin + (long long)tile * p.tile;
     long long f1 = f0 + p.tile;
     if (f1 > p.f_stop) f1 = p.f_stop;
@@ -101,6 +138,7 @@ __global__ __launch_bounds__(64 * (PvAny<N, false, kTransient>::kWaves1)) void p
 #pragma unroll 1
     for (long long f = f_first; f < f1; f++) {
         const long long s = pva_frame_start<N>(p, f);
+        if constexpr (kLink) pva_other_power<N, kUnit>(scr, w512l, tb, in2, s, po, lane);
         pva_analyse<N, kUnit>(scr, w512l, tb, in, s, lane);
         const unsigned d = (unsigned)(s - s_prev);
         const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
@@ -114,7 +152,8 @@ __global__ __launch_bounds__(64 * (PvAny<N, false, kTransient>::kWaves1)) void p
             // frame f0 - 1 only primes; the "increment" of frame 0 is its analysis phase
             if (f >= f0) acc[64 * r] = (f == 0) ? qa : acc[64 * r] + pva_inc<N>(qa, qp[64 * r], (unsigned)kc, d, R);
             qp[64 * r] = qa;
-            if constexpr (kTransient) rising += pva_rises<N>(x, k, pp + 64 * r, f > f_first);
+            if constexpr (kLink) rising += pva_rises_linked<N>(x, k, pp + 64 * r, po[64 * r], f > f_first);
+            else if constexpr (kTransient) rising += pva_rises<N>(x, k, pp + 64 * r, f > f_first);
         }
         if constexpr (kTransient) {
             const bool high = f > f_first && pva_high<N>(rising);
@@ -259,12 +298,13 @@ __global__ __launch_bounds__(64 * kScanChunks) void pv_scan_chunked_kernel(uint3
 // ------------------------------------------------------------------------------------------------ pass 3
 // kFormant: formant preservation with lifter `lifter` and transposer ratio g (nae_stretch_block_formant_f32); off, both are unused.
 // kTransient: an onset frame takes Qs = Qa ("Transient preservation"); frames b0 - 2 and b0 - 1 prime P and "high".
-template <int N, bool kUnit, bool kFormant, bool kTransient = false>
-__global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient>::kWaves3)) void pv_any_synth_kernel(SigViewD src, PvParams p, long long n_items,
+template <int N, bool kUnit, bool kFormant, bool kTransient = false, bool kLink = false>
+__global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient, kLink>::kWaves3)) void pv_any_synth_kernel(SigViewD src, PvParams p, long long n_items,
                                                                                        const uint32_t* __restrict__ phase_ws, OutViewD out,
                                                                                        SpecAnyTables tb, int lifter, float g)
 {
-    using P = PvAny<N, kFormant, kTransient>;
+    static_assert(kTransient || !kLink, "unlocked, the link acts on the onset rule only");
+    using P = PvAny<N, kFormant, kTransient, kLink>;
     using Gm = typename P::Gm;
     __shared__ __attribute__((aligned(16))) cf w512l[512];
     __shared__ __attribute__((aligned(16))) cf scratch[P::kWaves3 * Gm::SCR];
@@ -272,6 +312,7 @@ __global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient>::kWaves3)) voi
     __shared__ uint32_t state[P::kWaves3 * 2 * P::ST];
     __shared__ float lbuf[kFormant ? P::kWaves3 * P::PAD : 1];   // formant: L, then c', then Ls
     __shared__ float pprev[kTransient ? P::kWaves3 * P::ST : 1];  // transients: P_{f-1} of bin lane + 64 r
+    __shared__ float pother[kLink ? P::kWaves3 * P::ST : 1];      // link: the other channel's P_f
     for (int i = threadIdx.x; i < 512; i += 64 * P::kWaves3) w512l[i] = tb.w512[i];
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -283,11 +324,13 @@ __global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient>::kWaves3)) voi
     uint32_t* qp = state + wave_id() * 2 * P::ST + lane;  // [r * 64]: Qa_{f-1} of bin lane + 64 r
     uint32_t* qs = qp + P::ST;                           //           Qs
     float* pp = pprev + (kTransient ? wave_id() * P::ST + lane : 0);
+    float* po = pother + (kLink ? wave_id() * P::ST + lane : 0);
     const long long sc = item / p.n_tiles;
     const int tile = (int)(item % p.n_tiles);
     const long long s_idx = sc / p.ch;
     const int c = (int)(sc % p.ch);
     const ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
+    const ChanView in2{src.base + s_idx * src.ss + (c ^ 1) * src.cs, src.fs, p.in_len};   // link (ch == 2): the stream's other channel
     const long long b0 = p.f_origin + (long long)tile * p.tile;
     const long long b_end = b0 + p.tile < p.f_stop ? b0 + p.tile : p.f_stop;
     long long f_end = b_end + 3;                           // frames b0 .. b_end+2 feed blocks b0 .. b_end-1
@@ -311,6 +354,7 @@ __global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient>::kWaves3)) voi
 #pragma unroll 1
     for (long long f = f_first; f < f_end; f++) {
         const long long s = pva_frame_start<N>(p, f);
+        if constexpr (kLink) pva_other_power<N, kUnit>(scr, w512l, tb, in2, s, po, lane);
         pva_analyse<N, kUnit>(scr, w512l, tb, in, s, lane);
         const unsigned d = (unsigned)(s - s_prev);
         const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
@@ -330,7 +374,8 @@ __global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient>::kWaves3)) voi
                     if (k < P::B) lb[k] = __builtin_amdgcn_logf(fmaxf(sqrt_rn(x.x * x.x + x.y * x.y), 0x1p-40f));   // L = log2 max(|X|, 2^-40)
             }
             qp[64 * r] = qa;
-            if constexpr (kTransient) rising += pva_rises<N>(x, k, pp + 64 * r, f > f_first);
+            if constexpr (kLink) rising += pva_rises_linked<N>(x, k, pp + 64 * r, po[64 * r], f > f_first);
+            else if constexpr (kTransient) rising += pva_rises<N>(x, k, pp + 64 * r, f > f_first);
         }
         if constexpr (kTransient) {
             const bool high = f > f_first && pva_high<N>(rising);
@@ -412,15 +457,15 @@ __global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient>::kWaves3)) voi
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-template <int N, bool kTransient>
+template <int N, bool kTransient, bool kLink = false>
 static int launch_phase(nae_ctx* ctx, const PvJob& j, const SpecAnyTables& tb)
 {
-    using P = PvAny<N, false, kTransient>;
-    const char* name = kTransient ? "pv_any_phase_transient_kernel" : "pv_any_phase_kernel";
+    using P = PvAny<N, false, kTransient, kLink>;
+    const char* name = kLink ? "pv_any_phase_link_kernel" : kTransient ? "pv_any_phase_transient_kernel" : "pv_any_phase_kernel";
     const long long items = j.n_sc * j.p.n_tiles;
     const long long grid = (items + P::kWaves1 - 1) / P::kWaves1;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_phase_kernel: grid too large");
-    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pv_any_phase_kernel<N, true, kTransient> : pv_any_phase_kernel<N, false, kTransient>), dim3((unsigned)grid),
+    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pv_any_phase_kernel<N, true, kTransient, kLink> : pv_any_phase_kernel<N, false, kTransient, kLink>), dim3((unsigned)grid),
                 dim3(64 * P::kWaves1), 0, ctx->stream, j.src, j.p, items, j.phase_ws, tb);
     return nae_check(ctx, hipGetLastError(), name);
 }
@@ -445,17 +490,18 @@ static int launch_scan(nae_ctx* ctx, const char* name, uint32_t* phase_ws, long 
     return nae_check(ctx, hipGetLastError(), name);
 }
 
-template <int N, bool kFormant, bool kTransient>
+template <int N, bool kFormant, bool kTransient, bool kLink = false>
 static int launch_synth(nae_ctx* ctx, const PvJob& j, const SpecAnyTables& tb)
 {
-    using P = PvAny<N, kFormant, kTransient>;
-    const char* name = kTransient ? (kFormant ? "pv_any_synth_formant_transient_kernel" : "pv_any_synth_transient_kernel")
+    using P = PvAny<N, kFormant, kTransient, kLink>;
+    const char* name = kLink      ? (kFormant ? "pv_any_synth_formant_link_kernel" : "pv_any_synth_link_kernel")
+                     : kTransient ? (kFormant ? "pv_any_synth_formant_transient_kernel" : "pv_any_synth_transient_kernel")
                                   : (kFormant ? "pv_any_synth_formant_kernel" : "pv_any_synth_kernel");
     const long long items = j.n_sc * j.p.n_tiles;
     if (items == 0) return NAE_OK;
     const long long grid = (items + P::kWaves3 - 1) / P::kWaves3;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_synth_kernel: grid too large");
-    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pv_any_synth_kernel<N, true, kFormant, kTransient> : pv_any_synth_kernel<N, false, kFormant, kTransient>),
+    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pv_any_synth_kernel<N, true, kFormant, kTransient, kLink> : pv_any_synth_kernel<N, false, kFormant, kTransient, kLink>),
                 dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream, j.src, j.p, items, j.phase_ws, j.out, tb, j.lifter, j.g);
     return nae_check(ctx, hipGetLastError(), name);
 }
@@ -475,6 +521,7 @@ int nae_pv_resident(nae_ctx* ctx, const nae_pv_run& r, PvKernels pass3)
     return at_size(ctx, r.n_fft, [&](auto n) {
         constexpr int N = decltype(n)::value;
         if (pass3 == PvKernels::kEnv) return PvEnv<N>::kResident;
+        if (r.link && r.transients) return r.lifter > 0 ? PvAny<N, true, true, true>::kResident3 : PvAny<N, false, true, true>::kResident3;
         if (r.transients) return r.lifter > 0 ? PvAny<N, true, true>::kResident3 : PvAny<N, false, true>::kResident3;
         return r.lifter > 0 ? PvAny<N, true>::kResident3 : PvAny<N>::kResident3;
     });
@@ -487,6 +534,7 @@ int nae_launch_pvany_phase(nae_ctx* ctx, const PvJob& j)
     if (rc) return rc;
     return at_size(ctx, j.n_fft, [&](auto n) {
         constexpr int N = decltype(n)::value;
+        if (j.link && j.transients) return launch_phase<N, true, true>(ctx, j, tb);
         return j.transients ? launch_phase<N, true>(ctx, j, tb) : launch_phase<N, false>(ctx, j, tb);
     });
 }
@@ -508,6 +556,7 @@ int nae_launch_pvany_synth(nae_ctx* ctx, const PvJob& j)
     if (rc) return rc;
     return at_size(ctx, j.n_fft, [&](auto n) {
         constexpr int N = decltype(n)::value;
+        if (j.link && j.transients) return j.lifter > 0 ? launch_synth<N, true, true, true>(ctx, j, tb) : launch_synth<N, false, true, true>(ctx, j, tb);
         if (j.transients) return j.lifter > 0 ? launch_synth<N, true, true>(ctx, j, tb) : launch_synth<N, false, true>(ctx, j, tb);
         return j.lifter > 0 ? launch_synth<N, true, false>(ctx, j, tb) : launch_synth<N, false, false>(ctx, j, tb);
     });

@@ -10,6 +10,9 @@
 //   pass L3 (pvlock_synth_kernel) one wave per synthesis tile: from the recorded Qs it walks its frames forward — re-analysis, M_f applied to the
 //                                 Qs vector in LDS, rotation, inverse FFT, window, overlap-add in increasing frame order — and stores its blocks.
 // Every integer is exact, so any tiling gives the same bits; the samples follow the oracle's tolerance path (|X| e^{i Qs}, inverse FFT, overlap-add).
+// kLink (NAE_STRETCH_LINK_CHANNELS; DESIGN.md §3, "Channel link"): the wave of channel c also analyses channel c ^ 1 of its stream in front of each
+// frame and keeps its power (9 registers); peaks, regions and the onset rule read Pl = 0.5 (P^0 + P^1), so sigma_f and the resets are the same in
+// both channels' waves.  B, Qa, inc and Qs stay the channel's own; pass L2 is unchanged.
 // The default (unlocked) path runs none of these kernels.  The host decisions of both modes (parameters, records needed, base records, synthesis
 // fields, workspace layout) are kernels_stft.hip's nae_launch_pv_phase / nae_launch_pv_synth; the launchers here only launch.
 #include "pv_roles.h"
@@ -35,10 +38,38 @@ __device__ __forceinline__ void lock_analyse(cf (&v)[8], cf& nyq, uint32_t (&qa)
     phases_of(v, nyq, qa);
 }
 
+// channel link: P of the stream's other channel for frame start s, for this lane's bins (the analysis of lock_analyse without the phases)
+template <bool kUnit>
+__device__ __forceinline__ void lock_other_power(float (&po)[9], const ChanView& in2, long long s, const float* hann, cf* scratch, const cf* twa,
+                                                 const cf* w64, const cf* t1024, int lane)
+{
+    cf v[8];
+    load_frame_windowed<kUnit>(v, in2, s, hann, lane);
+    fft512_pad(v, make_fft_lds(scratch, twa, w64, lane));
+    const cf nyq = rfft_split<false>(v, scratch, t1024, lane);
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const cf x = r < 8 ? v[r] : nyq;
+        po[r] = x.x * x.x + x.y * x.y;
+    }
+}
+
+// the linked power Pl = 0.5 (P^0 + P^1) of this lane's bins, in place over the other channel's P: one IEEE add (it commutes, so either channel's
+// wave gets the bits of P^0 + P^1), one product
+__device__ __forceinline__ void lock_linked_power(const cf (&v)[8], cf nyq, float (&pl)[9])
+{
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const cf x = r < 8 ? v[r] : nyq;
+        pl[r] = 0.5f * ((x.x * x.x + x.y * x.y) + pl[r]);
+    }
+}
+
 // M_f of frame f >= 1 for this lane's bins k = lane + 64 r (r = 8: k = 512, meaningful in lane 0).  qp: Qa_{f-1}.
-// Power (two products, one add, never fused), peaks, nearest-peak regions: DESIGN.md §3, rules 1-3.
+// Power (two products, one add, never fused), peaks, nearest-peak regions: DESIGN.md §3, rules 1-3.  kLink: peaks and regions on the linked power pl.
+template <bool kLink = false>
 __device__ __forceinline__ void lock_map_of_frame(const cf (&v)[8], cf nyq, const uint32_t (&qa)[9], const uint32_t (&qp)[9], unsigned d, unsigned R,
-                                                  cf* scratch, int lane, uint32_t (&sig)[9], uint32_t (&c)[9])
+                                                  cf* scratch, int lane, uint32_t (&sig)[9], uint32_t (&c)[9], const float* pl = nullptr)
 {
     uint32_t* w = reinterpret_cast<uint32_t*>(scratch);
     float* P = reinterpret_cast<float*>(scratch);
@@ -48,7 +79,8 @@ __device__ __forceinline__ void lock_map_of_frame(const cf (&v)[8], cf nyq, cons
         const cf x = r < 8 ? v[r] : nyq;
         const uint32_t inc = pipe_inc(qa[r], qp[r], k, d, R);
         if (r < 8 || lane == 0) {
-            P[k] = x.x * x.x + x.y * x.y;
+            if constexpr (kLink) P[k] = pl[r];
+            else P[k] = x.x * x.x + x.y * x.y;
             w[kLockB + k] = inc - qa[r];
         }
     }
@@ -136,6 +168,21 @@ __device__ __forceinline__ bool lock_high(const cf (&v)[8], cf nyq, float (&pp)[
     return counted && NAE_TRANSIENT_DEN * rising >= NAE_TRANSIENT_NUM * NAE_FFT_BINS;
 }
 
+// lock_high on the linked power pl ("Channel link"); pp keeps Pl_{f-1}
+__device__ __forceinline__ bool lock_high_linked(const float (&pl)[9], float (&pp)[9], bool counted, int lane)
+{
+    int rising = 0;
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+        const float P = pl[r];
+        const bool mine = r < 8 || lane == 0;
+        const bool rise = counted && mine && P > NAE_TRANSIENT_RISE * pp[r] && P > NAE_TRANSIENT_FLOOR * (float)NAE_FFT_N;
+        rising += __popcll(__ballot(rise));
+        pp[r] = P;
+    }
+    return counted && NAE_TRANSIENT_DEN * rising >= NAE_TRANSIENT_NUM * NAE_FFT_BINS;
+}
+
 // ------------------------------------------------------------------------------------------------ pass L1
 // tile maps: c at maps[rec * 520 + k] (uint32), sigma at sig16[rec * 520 + k] (uint16), rec = sc * n_tiles + tile.  kTransient: an onset frame's
 // map is the reset map (Qs = Qa: it ignores its input), the running map becomes it, and maps[rec * 520 + 513] (a padding slot) is 1 when the tile
@@ -144,7 +191,7 @@ constexpr size_t kLockMapWave = kPadScratchCf * sizeof(cf) + kT1024Pad * (sizeof
 constexpr size_t kLdsLockMap = kLdsTablesPad + kWaves * kLockMapWave;
 static_assert(2 * kLdsLockMap <= 160 * 1024, "two workgroups per CU");
 
-template <bool kUnit, bool kTransient = false>
+template <bool kUnit, bool kTransient = false, bool kLink = false>
 __global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, PvParams p, long long n_items, uint32_t* __restrict__ maps,
                                                                  uint16_t* __restrict__ sig16, Tables tb)
 {
@@ -165,6 +212,7 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, P
     const long long s_idx = sc / p.ch;
     const int c = (int)(sc % p.ch);
     ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
+    const ChanView in2{src.base + s_idx * src.ss + (c ^ 1) * src.cs, src.fs, p.in_len};   // link (ch == 2): the stream's other channel
 
     const long long f0 = p.f_origin + (long long)tile * p.tile;
     long long f1 = f0 + p.tile;
@@ -184,13 +232,16 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, P
     float pp[9];                                        // transients: P_{f-1} of this lane's bins
     bool high_prev = false;                             //             high(f - 1), wave-uniform
     uint32_t reset = 0;                                 //             an onset in [f0, f1)
+    float pl[9];                                        // link: Pl_f of this lane's bins
 #pragma unroll 1
     for (long long f = f_first; f < f1; f++) {
         const long long s = frame_start(p, f);
+        if constexpr (kLink) lock_other_power<kUnit>(pl, in2, s, hann, scratch, twa, w64, t1024, lane);
         lock_analyse<kUnit>(v, nyq, qa, in, s, hann, scratch, twa, w64, t1024, lane);
+        if constexpr (kLink) lock_linked_power(v, nyq, pl);
         bool onset = false;
         if constexpr (kTransient) {
-            const bool high = lock_high(v, nyq, pp, f > f_first, lane);
+            const bool high = kLink ? lock_high_linked(pl, pp, f > f_first, lane) : lock_high(v, nyq, pp, f > f_first, lane);
             onset = f >= 2 && high && !high_prev;
             high_prev = high;
         }
@@ -205,7 +256,7 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, P
             } else {
                 const unsigned d = (unsigned)(s - s_prev);
                 const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
-                lock_map_of_frame(v, nyq, qa, qp, d, R, scratch, lane, sg, cc);
+                lock_map_of_frame<kLink>(v, nyq, qa, qp, d, R, scratch, lane, sg, cc, pl);
             }
             // running map, then this frame: (ms[sg], mc[sg] + cc), or after a reset map the reset map; all gathers land before the first write
             uint32_t ns[9], nc[9];
@@ -423,7 +474,7 @@ __device__ __forceinline__ void lock_formant_apply(cf (&y)[8], cf& ynyq, cf* scr
 
 // kFormant: formant preservation with lifter `lifter` and transposer ratio g; off, both are unused.  kTransient: an onset frame takes Qs = Qa
 // ("Transient preservation"); frames b0 - 2 and b0 - 1 prime P and "high".
-template <bool kUnit, bool kFormant, bool kTransient = false>
+template <bool kUnit, bool kFormant, bool kTransient = false, bool kLink = false>
 __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src, PvParams p, long long n_items, const uint32_t* __restrict__ phase_ws,
                                                                    OutViewD out, Tables tb, int lifter, float g)
 {
@@ -442,6 +493,7 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
     const long long s_idx = sc / p.ch;
     const int c = (int)(sc % p.ch);
     ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
+    const ChanView in2{src.base + s_idx * src.ss + (c ^ 1) * src.cs, src.fs, p.in_len};   // link (ch == 2): the stream's other channel
     PipeItem it;
     it.sc = sc; it.s_idx = s_idx; it.c = c; it.tile = tile;
     it.b0 = p.f_origin + (long long)tile * p.tile;
@@ -468,13 +520,16 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
     long long s_prev = 0;
     float pp[9];                                                // transients: P_{f-1} of this lane's bins
     bool high_prev = false;                                     //             high(f - 1), wave-uniform
+    float pl[9];                                                // link: Pl_f of this lane's bins
 #pragma unroll 1
     for (long long f = f_first; f < f_end; f++) {
         const long long s = frame_start(p, f);
+        if constexpr (kLink) lock_other_power<kUnit>(pl, in2, s, hann, scratch, twa, w64, t1024, lane);
         lock_analyse<kUnit>(v, nyq, qa, in, s, hann, scratch, twa, w64, t1024, lane);
+        if constexpr (kLink) lock_linked_power(v, nyq, pl);
         bool onset = false;
         if constexpr (kTransient) {
-            const bool high = lock_high(v, nyq, pp, f > f_first, lane);
+            const bool high = kLink ? lock_high_linked(pl, pp, f > f_first, lane) : lock_high(v, nyq, pp, f > f_first, lane);
             onset = f >= 2 && high && !high_prev;
             high_prev = high;
         }
@@ -486,7 +541,7 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
             } else {
                 const unsigned d = (unsigned)(s - s_prev);
                 const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
-                lock_map_of_frame(v, nyq, qa, qp, d, R, scratch, lane, sg, cc);
+                lock_map_of_frame<kLink>(v, nyq, qa, qp, d, R, scratch, lane, sg, cc, pl);
             }
             uint32_t nq[9];
 #pragma unroll
@@ -581,10 +636,11 @@ using namespace nae;
 // and kernel, the scan kernel at its largest size
 constexpr unsigned kAttrLockMap = 1u << 12, kAttrLockScan = 1u << 13, kAttrLockSynth = 1u << 14,   // nae_ctx::pv_attr_done (pipeline: bits 0-10)
                    kAttrLockSynthF = 1u << 15, kAttrLockMapT = 1u << 16, kAttrLockScanT = 1u << 17, kAttrLockSynthT = 1u << 18,
-                   kAttrLockSynthFT = 1u << 19;
+                   kAttrLockSynthFT = 1u << 19;   // a kLink instantiation: its unlinked kernel's bit << 8 (bits 20-27)
 
 // transients: the kTransient instantiations (reset maps, the segmented scan; profile names pvlock_map_transient_kernel and
 // pvlock_scan_transient_kernel)
+// link: the kLink instantiations of the map kernel (pvlock_map_link_kernel, pvlock_map_transient_link_kernel); the scan does not change
 int nae_launch_pvlock_phase(nae_ctx* ctx, const PvJob& j, int n_needed, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out)
 {
     const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
@@ -592,10 +648,13 @@ int nae_launch_pvlock_phase(nae_ctx* ctx, const PvJob& j, int n_needed, uint32_t
         const long long items = j.n_sc * j.p.n_tiles;
         const long long grid = (items + kWaves - 1) / kWaves;
         if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_map_kernel: grid too large");
-        const char* name = j.transients ? "pvlock_map_transient_kernel" : "pvlock_map_kernel";
-        auto k_unit = j.transients ? pvlock_map_kernel<true, true> : pvlock_map_kernel<true, false>;
-        auto k_strided = j.transients ? pvlock_map_kernel<false, true> : pvlock_map_kernel<false, false>;
-        int rc = nae_pv_lds_attr(ctx, j.transients ? kAttrLockMapT : kAttrLockMap, kLdsLockMap, reinterpret_cast<const void*>(k_unit),
+        const char* name = j.link ? (j.transients ? "pvlock_map_transient_link_kernel" : "pvlock_map_link_kernel")
+                                  : (j.transients ? "pvlock_map_transient_kernel" : "pvlock_map_kernel");
+        auto k_unit = j.link ? (j.transients ? pvlock_map_kernel<true, true, true> : pvlock_map_kernel<true, false, true>)
+                             : (j.transients ? pvlock_map_kernel<true, true> : pvlock_map_kernel<true, false>);
+        auto k_strided = j.link ? (j.transients ? pvlock_map_kernel<false, true, true> : pvlock_map_kernel<false, false, true>)
+                                : (j.transients ? pvlock_map_kernel<false, true> : pvlock_map_kernel<false, false>);
+        int rc = nae_pv_lds_attr(ctx, (j.transients ? kAttrLockMapT : kAttrLockMap) << (j.link ? 8 : 0), kLdsLockMap, reinterpret_cast<const void*>(k_unit),
                                  reinterpret_cast<const void*>(k_strided));
         if (rc) return rc;
         NAE_KLAUNCH(ctx, name, (j.unit_stride ? k_unit : k_strided), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream, j.src, j.p, items,
@@ -614,17 +673,17 @@ int nae_launch_pvlock_phase(nae_ctx* ctx, const PvJob& j, int n_needed, uint32_t
     return nae_check(ctx, hipGetLastError(), name);
 }
 
-template <bool kFormant, bool kTransient>
+template <bool kFormant, bool kTransient, bool kLink = false>
 static int launch_lock_synth(nae_ctx* ctx, unsigned attr_bit, const char* name, const PvJob& j)
 {
     const long long items = j.n_sc * j.p.n_tiles;
     const long long grid = (items + kWaves - 1) / kWaves;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_synth_kernel: grid too large");
     const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
-    int rc = nae_pv_lds_attr(ctx, attr_bit, kLdsLockSynth, reinterpret_cast<const void*>(pvlock_synth_kernel<true, kFormant, kTransient>),
-                             reinterpret_cast<const void*>(pvlock_synth_kernel<false, kFormant, kTransient>));
+    int rc = nae_pv_lds_attr(ctx, attr_bit, kLdsLockSynth, reinterpret_cast<const void*>(pvlock_synth_kernel<true, kFormant, kTransient, kLink>),
+                             reinterpret_cast<const void*>(pvlock_synth_kernel<false, kFormant, kTransient, kLink>));
     if (rc) return rc;
-    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pvlock_synth_kernel<true, kFormant, kTransient> : pvlock_synth_kernel<false, kFormant, kTransient>),
+    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pvlock_synth_kernel<true, kFormant, kTransient, kLink> : pvlock_synth_kernel<false, kFormant, kTransient, kLink>),
                 dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream, j.src, j.p, items, j.phase_ws, j.out, tb, j.lifter, j.g);
     return nae_check(ctx, hipGetLastError(), name);
 }
@@ -633,6 +692,14 @@ static int launch_lock_synth(nae_ctx* ctx, unsigned attr_bit, const char* name, 
 int nae_launch_pvlock_synth(nae_ctx* ctx, const PvJob& j)
 {
     if (j.n_sc * j.p.n_tiles == 0) return NAE_OK;
+    if (j.link) {   // the kLink instantiations (*_link_kernel)
+        if (j.transients) {
+            if (j.lifter > 0) return launch_lock_synth<true, true, true>(ctx, kAttrLockSynthFT << 8, "pvlock_synth_formant_transient_link_kernel", j);
+            return launch_lock_synth<false, true, true>(ctx, kAttrLockSynthT << 8, "pvlock_synth_transient_link_kernel", j);
+        }
+        if (j.lifter > 0) return launch_lock_synth<true, false, true>(ctx, kAttrLockSynthF << 8, "pvlock_synth_formant_link_kernel", j);
+        return launch_lock_synth<false, false, true>(ctx, kAttrLockSynth << 8, "pvlock_synth_link_kernel", j);
+    }
     if (j.transients) {
         if (j.lifter > 0) return launch_lock_synth<true, true>(ctx, kAttrLockSynthFT, "pvlock_synth_formant_transient_kernel", j);
         return launch_lock_synth<false, true>(ctx, kAttrLockSynthT, "pvlock_synth_transient_kernel", j);

@@ -547,7 +547,7 @@ static PvJob make_pv_job(const nae_pv_run& r, const nae_stretch_plan& pl, const 
                          const nae_pv_segment* seg, uint32_t* phase_ws, const nae_sig* out)
 {
     return PvJob{r.n_fft, make_pv_params(pl, in_len, ch, tile, seg), to_view(src), out ? to_out(out) : OutViewD{}, (long long)n_streams * ch,
-                 src->frame_stride == 1, phase_ws, r.lifter, r.g, r.transients};
+                 src->frame_stride == 1, phase_ws, r.lifter, r.g, r.transients, r.link};
 }
 
 // pass 1 + 2: leaves the exclusive tile-prefix phases in `phase_ws` (one record per pass-1 tile).

@@ -605,7 +605,7 @@ int nae_pv_opts_check(nae_ctx* ctx, unsigned flags, unsigned allowed, int n_fft,
     if ((flags & NAE_STRETCH_PHASE_LOCK) && n_fft != NAE_FFT_N) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "phase locking runs at n_fft = 1024 only");
     if (lifter < 0 || lifter > n_fft / 4) return nae_fail(ctx, NAE_ERR_INVALID, "formant lifter must be in [0, n_fft / 4]");
     *o = nae_pv_opts{n_fft, lifter, (flags & NAE_STRETCH_PHASE_LOCK) != 0, (flags & NAE_STRETCH_TRANSIENTS) != 0, formant_ratio != nullptr,
-                     formant_ratio ? *formant_ratio : 1.0};
+                     formant_ratio ? *formant_ratio : 1.0, (flags & NAE_STRETCH_LINK_CHANNELS) != 0};
     return NAE_OK;
 }
 
@@ -684,7 +684,7 @@ static int stretch_block_impl(nae_ctx* ctx, const nae_pv_opts& o, double rate, d
     if ((rc = run_mix())) return rc;     // vocoder first / transposer only: the mix is a launch of its own
     if (!(stages & 2)) return NAE_OK;
     if (pl.pv_on) {
-        const nae_pv_run run = nae_pv_resolve(o, pl);
+        const nae_pv_run run = nae_pv_resolve(o, pl, ch);
         PvBlockShape sh;
         if ((rc = pv_block_shape(ctx, run, pl.frames, ch, n_streams, &sh))) return rc;
         const nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, pv_out_len, nullptr, nullptr};
@@ -737,7 +737,7 @@ int nae_stretch_block_formant_f32(nae_ctx* ctx, double rate, double pitch, unsig
                                   int ch, size_t n_streams, const nae_sig* dst)
 {
     nae_pv_opts o;
-    const int rc = nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, n_fft, lifter, nullptr, &o);
+    const int rc = nae_pv_opts_check(ctx, flags, kPvFlagsN, n_fft, lifter, nullptr, &o);
     return rc ? rc : stretch_block_impl(ctx, o, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3);
 }
 
@@ -745,7 +745,7 @@ int nae_stretch_block_formant_shift_f32(nae_ctx* ctx, double rate, double pitch,
                                         const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst)
 {
     nae_pv_opts o;
-    const int rc = nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, n_fft, lifter, &formant_ratio, &o);
+    const int rc = nae_pv_opts_check(ctx, flags, kPvFlagsN, n_fft, lifter, &formant_ratio, &o);
     return rc ? rc : stretch_block_impl(ctx, o, rate, pitch, src, in_len, ch, n_streams, dst, nullptr, 3);
 }
 
@@ -763,7 +763,7 @@ static int pv_tile_phase_impl(nae_ctx* ctx, const nae_pv_opts& o, double rate, d
     const size_t n_tiles = (pl.frames + tile - 1) / tile;
     *n_tiles_out = n_tiles;
     *tile_frames = (size_t)tile;
-    const nae_pv_run run = nae_pv_resolve(o, pl);   // an _n plan with the stage on: never forced, the transient flag as given
+    const nae_pv_run run = nae_pv_resolve(o, pl, ch);   // an _n plan with the stage on: never forced, the transient flag as given
     const size_t bins = (size_t)o.n_fft / 2 + 1, pad = nae_pv_record_pad(o.n_fft);
     const size_t need = n_streams * ch * n_tiles * bins;
     if (dst_capacity < need) return nae_fail(ctx, NAE_ERR_INVALID, "destination too small");
@@ -814,7 +814,7 @@ int nae_debug_pv_tile_phase_n(nae_ctx* ctx, double rate, double pitch, unsigned 
                               size_t n_streams, int32_t* dst_host, size_t dst_capacity, size_t* n_tiles_out, size_t* tile_frames)
 {
     nae_pv_opts o;
-    const int rc = nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, n_fft, 0, nullptr, &o);
+    const int rc = nae_pv_opts_check(ctx, flags, kPvFlagsN, n_fft, 0, nullptr, &o);
     return rc ? rc : pv_tile_phase_impl(ctx, o, rate, pitch, src, in_len, ch, n_streams, dst_host, dst_capacity, n_tiles_out, tile_frames);
 }
 

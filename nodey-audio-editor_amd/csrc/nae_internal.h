@@ -111,17 +111,20 @@ struct nae_pv_segment {
     uint32_t* carry_out;          // receives the phase behind frame f_origin+f_count-1 (null: not wanted)
     bool carry_by_synth = false;  // the segment is synthesised as ONE tile and pass 3 itself writes carry_out (no pass 1)
 };
-// What an entry's caller asked of the vocoder: lock = NAE_STRETCH_PHASE_LOCK, transients = NAE_STRETCH_TRANSIENTS, lifter 0 = no formant stage.
+// What an entry's caller asked of the vocoder: lock = NAE_STRETCH_PHASE_LOCK, transients = NAE_STRETCH_TRANSIENTS, link =
+// NAE_STRETCH_LINK_CHANNELS, lifter 0 = no formant stage.
 // shift: a _formant_shift entry, whose plan (nae_stretch_plan_make_shift) may force the vocoder stage on; it says more than formant_ratio != 1 (the
 // _formant entries with a lifter and a rate-only change run the transposer alone, _formant_shift with ratio 1 the forced envelope stage).
 struct nae_pv_opts {
     int n_fft = NAE_FFT_N, lifter = 0;
     bool lock = false, transients = false, shift = false;
     double formant_ratio = 1.0;
+    bool link = false;
 };
 // nae_api.hip: the one statement of the entries' option rules, in this order: a null context NAE_ERR_INVALID (nothing touched); a flag outside
-// `allowed` (the _ex entries NAE_STRETCH_PHASE_LOCK, the others also NAE_STRETCH_TRANSIENTS) NAE_ERR_INVALID; a size outside 512 ... 4096, the lock
+// `allowed` (the _ex entries NAE_STRETCH_PHASE_LOCK, the others kPvFlagsN) NAE_ERR_INVALID; a size outside 512 ... 4096, the lock
 // at a size other than 1024, NAE_ERR_UNSUPPORTED; a lifter outside 0 ... n_fft / 4 NAE_ERR_INVALID.  formant_ratio given: a _formant_shift entry.
+constexpr unsigned kPvFlagsN = NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS | NAE_STRETCH_LINK_CHANNELS;   // the _n, _formant and _formant_shift entries
 int nae_pv_opts_check(nae_ctx* ctx, unsigned flags, unsigned allowed, int n_fft, int lifter, const double* formant_ratio, nae_pv_opts* o);
 // nae_api.hip: the plan of a call with these options (the _shift plan of the _formant_shift entries, else the _n plan); a failure leaves its text
 int nae_pv_plan_make(nae_ctx* ctx, const nae_pv_opts& o, double rate, double pitch, size_t in_len, nae_stretch_plan* pl);
@@ -148,12 +151,17 @@ struct nae_pv_run {
     float g;           // its transposer ratio (nae_formant_g); 0 with the stage off
     bool forced;       // nae_plan_forced: the envelope pass alone — no pass 1, no scan, no phase workspace, nothing carried
     bool transients;   // the flag, with the stage on and not forced (a forced stage has Qs = Qa: nothing to reset)
+    bool link;         // the channel link as it is effective ("Channel link", rule 4): the flag, two channels, the stage on and not
+                       // forced, and the lock or transient preservation effective — else the call is the unflagged one
 };
-inline nae_pv_run nae_pv_resolve(const nae_pv_opts& o, const nae_stretch_plan& pl)
+inline nae_pv_run nae_pv_resolve(const nae_pv_opts& o, const nae_stretch_plan& pl, int ch)
 {
     const int lifter = nae_formant_lifter_eff(pl, o.lifter, o.formant_ratio);
     const bool forced = nae_plan_forced(pl);
-    return {o.n_fft, o.lock, lifter, lifter > 0 ? nae_formant_g(pl, o.formant_ratio) : 0.0f, forced, o.transients && pl.pv_on && !forced};
+    const bool stage = pl.pv_on && !forced;
+    const bool transients = o.transients && stage;
+    return {o.n_fft, o.lock, lifter, lifter > 0 ? nae_formant_g(pl, o.formant_ratio) : 0.0f, forced, transients,
+            o.link && ch == 2 && stage && (o.lock || transients)};
 }
 // The kernels a vocoder call runs, for the tile choice of a block call, nae_launch_pv_phase and nae_launch_pv_synth:
 //   pass 1  kShipped: pv_phase_kernel (1024 points); kAny: pv_any_phase_kernel<N> (kernels_pv_any.hip); kLock: pvlock_map_kernel and its scan;
@@ -162,7 +170,8 @@ inline nae_pv_run nae_pv_resolve(const nae_pv_opts& o, const nae_stretch_plan& p
 // ones.  Pass 1 does not depend on the lifter.  Unlocked 1024-point calls with formant preservation (nae_pv_run::lifter > 0) run the shipped pass 1
 // and the size-generic pass 3: the pipeline has no formant stage, and the two passes share the record layout.  Unlocked calls with transient
 // preservation run the size-generic passes at every size, 1024 included: the shipped pass 1 and the pipeline have no onset detector; locked
-// ones the transient instantiations of the locked kernels.
+// ones the transient instantiations of the locked kernels.  A linked call (nae_pv_run::link) runs the kLink instantiations of the same kernels: unlocked
+// it routes to the size-generic passes at every size, as a transient call does.
 //   kEnv (a forced plan, nae_plan_forced): pass 3 is pv_env_kernel<N> (kernels_pvenv.hip) — there is no pass 1 and no scan, and the lock and
 //   transient preservation change nothing (Qs = Qa either way).
 // Asked at each launch, not kept in nae_pv_run: the debug key may change during a handle's life.
@@ -172,7 +181,7 @@ inline nae_pv_route nae_pv_route_of(const nae_ctx* ctx, const nae_pv_run& r)
 {
     if (r.forced) return {PvKernels::kEnv, PvKernels::kEnv};
     if (r.lock) return {PvKernels::kLock, PvKernels::kLock};
-    const PvKernels pass1 = r.n_fft != NAE_FFT_N || ctx->dbg_pv_any || r.transients ? PvKernels::kAny : PvKernels::kShipped;
+    const PvKernels pass1 = r.n_fft != NAE_FFT_N || ctx->dbg_pv_any || r.transients || r.link ? PvKernels::kAny : PvKernels::kShipped;
     return {pass1, r.lifter > 0 ? PvKernels::kAny : pass1};
 }
 // kernels_stft.hip: the vocoder's passes on the kernels nae_pv_route_of says, and their phase workspace (nae_pv_reserve_ws: none for a forced plan)
@@ -183,7 +192,7 @@ int nae_launch_pv_phase(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_pla
 int nae_launch_pv_synth(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
                         int tile, int phase_tile, uint32_t* phase_ws, const nae_sig* out, const nae_pv_segment* seg, int frames_per_step);
 // kernels_pv_any.hip: the vocoder sizes (512, 1024, 2048, 4096), the record length of a size (int32: N/2 + 1 padded to a multiple of 8), the
-// pass-3 waves a CU holds on the kernels `pass3` (kAny: PvAny<N, formant, transients>::kResident3; kEnv: PvEnv<N>::kResident; kLock: 16)
+// pass-3 waves a CU holds on the kernels `pass3` (kAny: PvAny<N, formant, transients, link>::kResident3; kEnv: PvEnv<N>::kResident; kLock: 16)
 bool nae_pv_size_ok(int n_fft);
 size_t nae_pv_record_pad(int n_fft);
 int nae_pv_resident(nae_ctx* ctx, const nae_pv_run& r, PvKernels pass3);

@@ -231,7 +231,7 @@ static int stretch_create(nae_ctx* ctx, const nae_pv_opts& o, int sample_rate, i
     s->pitch = pitch;
     s->opts = o;
     s->pl = pl;
-    s->run = nae_pv_resolve(o, pl);
+    s->run = nae_pv_resolve(o, pl, channels);
     s->in.width = s->mid.width = s->out.width = (size_t)channels;
     s->mid.planar = !pl.rs_first;
     *h = s;
@@ -260,7 +260,7 @@ int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, floa
                                nae_stretch** h)
 {
     nae_pv_opts o;
-    const int rc = h ? nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, n_fft, lifter, nullptr, &o) : NAE_ERR_INVALID;
+    const int rc = h ? nae_pv_opts_check(ctx, flags, kPvFlagsN, n_fft, lifter, nullptr, &o) : NAE_ERR_INVALID;
     return rc ? rc : stretch_create(ctx, o, sample_rate, channels, rate, pitch, h);
 }
 
@@ -268,7 +268,7 @@ int nae_stretch_create_formant_shift(nae_ctx* ctx, int sample_rate, int channels
                                      double formant_ratio, nae_stretch** h)
 {
     nae_pv_opts o;
-    const int rc = h ? nae_pv_opts_check(ctx, flags, NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, n_fft, lifter, &formant_ratio, &o) : NAE_ERR_INVALID;
+    const int rc = h ? nae_pv_opts_check(ctx, flags, kPvFlagsN, n_fft, lifter, &formant_ratio, &o) : NAE_ERR_INVALID;
     return rc ? rc : stretch_create(ctx, o, sample_rate, channels, rate, pitch, h);
 }
 

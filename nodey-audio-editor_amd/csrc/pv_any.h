@@ -7,7 +7,7 @@
 
 namespace nae {
 
-template <int N, bool kFormant = false, bool kTransient = false>
+template <int N, bool kFormant = false, bool kTransient = false, bool kLink = false>
 struct PvAny {
     static constexpr int M = N / 2, H = N / 4, B = M + 1;
     static constexpr int PAD = (B + 7) & ~7;              // int32 per record: 520 at N = 1024, as the shipped kernels
@@ -18,17 +18,22 @@ struct PvAny {
     using Gm = FftGeom<M, 1>;
     static constexpr int ST = NB * 64;                    // uint32 per per-bin state array of a wave
     static constexpr size_t kWave1 = Gm::SCR * sizeof(cf) + 2 * ST * sizeof(uint32_t)                     // scratch, Qa_{f-1}, sum
-                                   + (kTransient ? ST * sizeof(float) : 0);                                // transients: P_{f-1}
+                                   + (kTransient ? ST * sizeof(float) : 0)                                 // transients: P_{f-1}
+                                   + (kLink ? ST * sizeof(float) : 0);                                     // link: the other channel's P_f
     static constexpr size_t kWave3 = Gm::SCR * sizeof(cf) + PAD * sizeof(cf) + 2 * ST * sizeof(uint32_t) // scratch, Y, Qa_{f-1}, Qs
                                    + (kFormant ? PAD * sizeof(float) : 0)                                  // formant: L / c' / Ls
-                                   + (kTransient ? ST * sizeof(float) : 0);                                // transients: P_{f-1}
+                                   + (kTransient ? ST * sizeof(float) : 0)                                 // transients: P_{f-1}
+                                   + (kLink ? ST * sizeof(float) : 0);                                     // link: the other channel's P_f
     static constexpr int kMaxWaves1 = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave1);
     static constexpr int kMaxWaves3 = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave3);
-    static constexpr int kWaves1 = kMaxWaves1 < 8 ? kMaxWaves1 : 8;   // 8, 8, 8, 4 waves per workgroup at N = 512 ... 4096 (transients: 8, 8, 7, 3)
-    static constexpr int kWaves3 = kMaxWaves3 < 8 ? kMaxWaves3 : 8;   // 8, 8, 6, 3 (formant: 8, 8, 5, 2; transients: 8, 8, 5, 2; both: 8, 8, 4, 2)
+    static constexpr int kWaves1 = kMaxWaves1 < 8 ? kMaxWaves1 : 8;   // 8, 8, 8, 4 waves per workgroup at N = 512 ... 4096 (transients: 8, 8, 7, 3; linked: 8, 8, 6, 3)
+    static constexpr int kWaves3 = kMaxWaves3 < 8 ? kMaxWaves3 : 8;   // 8, 8, 6, 3 (formant: 8, 8, 5, 2; transients: 8, 8, 5, 2; both: 8, 8, 4, 2; linked: 8, 8, 4, 2, with formant 8, 7, 4, 2)
     // pass-3 waves a CU holds: whole workgroups by LDS (16, 8, 6, 3 at N = 512 ... 4096, formant 16, 8, 5, 2; registers allow as many; transients
-    // 16, 8, 5, 2; formant and transients 16, 8, 4, 2)
-    static constexpr int kResident3 = (int)((160 * 1024) / (512 * sizeof(cf) + kWaves3 * kWave3)) * kWaves3;
+    // 16, 8, 5, 2; formant and transients 16, 8, 4, 2).  Linked (with transients): by LDS 16, 8, 4, 2 and with formants 8, 7, 4, 2; the linked
+    // kernels at 512 take 132 ... 157 VGPRs, three waves per SIMD and so one workgroup of 8 waves: 8, 8, 4, 2 and 8, 7, 4, 2
+    // (profiles/r14_pv_link.md)
+    static constexpr int kLdsResident3 = (int)((160 * 1024) / (512 * sizeof(cf) + kWaves3 * kWave3)) * kWaves3;
+    static constexpr int kResident3 = kLink && N == 512 && kLdsResident3 > 8 ? 8 : kLdsResident3;
     static_assert(N >= 512 && N <= 4096 && (N & (N - 1)) == 0, "vocoder sizes 512 ... 4096");
     static_assert(kWaves1 >= 1 && kWaves3 >= 1, "a wave's state fits a CU's LDS");
 };

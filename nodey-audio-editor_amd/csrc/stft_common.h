@@ -133,7 +133,8 @@ __device__ __forceinline__ void phase_inc(const uint32_t (&qa)[9], const uint32_
 
 // What the vocoder's leaf launchers share, as nae_launch_pv_phase / nae_launch_pv_synth (kernels_stft.hip) built it from the nae_pv_run.  Pass 1
 // has no `out` and writes `phase_ws`, pass 3 reads it; lifter > 0 (pass 3): formant preservation with that lifter and transposer ratio g ("Formant
-// preservation"); transients: passes 1 and 3 detect onsets and reset Qs there, pass 1 flags its records and the scan is the segmented one
+// preservation"); transients: passes 1 and 3 detect onsets and reset Qs there, pass 1 flags its records and the scan is the segmented one;
+// link: the kLink instantiations — the onset rule and the lock's peaks and regions read the linked power of the stream's two channels
 namespace nae {
 struct PvJob {
     int n_fft;
@@ -141,7 +142,7 @@ struct PvJob {
     SigViewD src; OutViewD out;
     long long n_sc; bool unit_stride;
     uint32_t* phase_ws;
-    int lifter; float g; bool transients;
+    int lifter; float g; bool transients, link;
 };
 }
 

@@ -63,6 +63,18 @@ namespace processor
 		return value["transients"].asBool();
 	}
 
+	bool link_channels_from_json(const Json::Value& value, const char* node_name)
+	{
+		if (!value.isMember("link_channels")) return false;
+		if (!value["link_channels"].isBool())
+			throw infra::Processor::Runtime_error(
+				"Failed to deserialize JSON file",
+				std::string(node_name) + " failed to serialize the JSON input because of missing or invalid fields.",
+				"Wrong field: link_channels"
+			);
+		return value["link_channels"].asBool();
+	}
+
 	float formant_shift_from_json(const Json::Value& value, const char* node_name)
 	{
 		if (!value.isMember("formant_shift")) return 0;
@@ -231,11 +243,12 @@ namespace processor
 				if (st) nae_wsola_destroy(st);
 			}
 			bool open() const { return pv != nullptr || st != nullptr; }
-			void create(Stretch_algorithm algo, bool phase_lock, int fft_size, bool formant, bool transients, float formant_shift, int sample_rate,
-						int channels, float velocity, float pitch)
+			void create(Stretch_algorithm algo, bool phase_lock, int fft_size, bool formant, bool transients, bool link_channels, float formant_shift,
+						int sample_rate, int channels, float velocity, float pitch)
 			{
-				const unsigned flags = (phase_lock ? NAE_STRETCH_PHASE_LOCK : 0u) | (transients ? NAE_STRETCH_TRANSIENTS : 0u);
-				// (phase_lock, fft_size, formant, formant_shift and transients are vocoder options: the WSOLA chain has none)
+				const unsigned flags = (phase_lock ? NAE_STRETCH_PHASE_LOCK : 0u) | (transients ? NAE_STRETCH_TRANSIENTS : 0u)
+									   | (link_channels ? NAE_STRETCH_LINK_CHANNELS : 0u);
+				// (phase_lock, fft_size, formant, formant_shift, transients and link_channels are vocoder options: the WSOLA chain has none)
 				if (algo == Stretch_algorithm::Soundtouch)
 					gpu::check(nae_wsola_create(gpu::context(), sample_rate, channels, velocity, pitch, &st), "nae_wsola_create");
 				else if (formant_shift != 0)   // the envelope stage with the default lifter, whether or not "formant" is set
@@ -268,7 +281,8 @@ namespace processor
 			const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
 			const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
 			const std::atomic<bool>& stop_token, float velocity, float pitch, const std::string& processor_name,
-			Stretch_algorithm algorithm, bool phase_lock, int fft_size, bool formant, bool transients, float formant_shift, Batch_stats& batch_stats
+			Stretch_algorithm algorithm, bool phase_lock, int fft_size, bool formant, bool transients, bool link_channels, float formant_shift,
+			Batch_stats& batch_stats
 		)
 		{
 			gpu::Node node;  // this node's context (own stream; device: gpu::pick_device): first local, destroyed last
@@ -367,7 +381,7 @@ namespace processor
 									infra::fmt("%d requires a sample rate between 8000 and 48000 Hz.", frame->sample_rate),
 									infra::fmt("Sample rate: %d", frame->sample_rate)
 								);
-							soundtouch.create(algorithm, phase_lock, fft_size, formant, transients, formant_shift, frame->sample_rate, frame->ch_layout.nb_channels, velocity, pitch);
+							soundtouch.create(algorithm, phase_lock, fft_size, formant, transients, link_channels, formant_shift, frame->sample_rate, frame->ch_layout.nb_channels, velocity, pitch);
 							channel_count = frame->ch_layout.nb_channels;
 							time_seconds = frame->pts * av_q2d(frame->time_base);
 							sample_rate = frame->sample_rate;
@@ -436,7 +450,7 @@ namespace processor
 	)
 	{
 		stretch_process_payload(input, output, stop_token, velocity, keep_pitch ? 1 / velocity : 1, get_processor_info().display_name,
-								algorithm, phase_lock, fft_size, false, transients, 0, batch_stats);  // :452-459
+								algorithm, phase_lock, fft_size, false, transients, link_channels, 0, batch_stats);  // :452-459
 	}
 
 	Json::Value Velocity_modifier::serialize() const
@@ -448,6 +462,7 @@ namespace processor
 		if (phase_lock) value["phase_lock"] = true;
 		if (fft_size != 1024) value["fft_size"] = fft_size;
 		if (transients) value["transients"] = true;
+		if (link_channels) value["link_channels"] = true;
 		return value;
 	}
 
@@ -459,6 +474,7 @@ namespace processor
 		phase_lock = phase_lock_from_json(value, "Velocity_modifier");
 		fft_size = fft_size_from_json(value, "Velocity_modifier", phase_lock);
 		transients = transients_from_json(value, "Velocity_modifier");
+		link_channels = link_channels_from_json(value, "Velocity_modifier");
 	}
 
 	// ------------------------------------------------------------------------------------------ Pitch_modifier
@@ -476,7 +492,7 @@ namespace processor
 	)
 	{
 		stretch_process_payload(input, output, stop_token, 1, std::pow(2.0f, pitch / 12.0f), get_processor_info().display_name,
-								algorithm, phase_lock, fft_size, formant, transients, formant_shift, batch_stats);  // :469-476
+								algorithm, phase_lock, fft_size, formant, transients, link_channels, formant_shift, batch_stats);  // :469-476
 	}
 
 	Json::Value Pitch_modifier::serialize() const
@@ -489,6 +505,7 @@ namespace processor
 		if (formant) value["formant"] = true;
 		if (formant_shift != 0) value["formant_shift"] = formant_shift;
 		if (transients) value["transients"] = true;
+		if (link_channels) value["link_channels"] = true;
 		return value;
 	}
 	void Pitch_modifier::deserialize(const Json::Value& value)
@@ -500,6 +517,7 @@ namespace processor
 		formant = formant_from_json(value, "Pitch_modifier");
 		formant_shift = formant_shift_from_json(value, "Pitch_modifier");
 		transients = transients_from_json(value, "Pitch_modifier");
+		link_channels = link_channels_from_json(value, "Pitch_modifier");
 	}
 
 	// ------------------------------------------------------------------------------------------ Audio_spectrum

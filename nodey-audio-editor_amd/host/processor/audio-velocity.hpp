@@ -38,6 +38,11 @@ namespace processor
 	// No key: false; a value that is not a bool: Runtime_error "Wrong field: transients"; written back only when true.  It combines with
 	// "phase_lock", "fft_size" and "formant"; with "algorithm": "soundtouch" it is kept and has no effect.
 	bool transients_from_json(const Json::Value& value, const char* node_name);
+	// "link_channels" (bool, optional): channel link of the vocoder (NAE_STRETCH_LINK_CHANNELS: on a stereo stream the onsets of "transients" and
+	// the regions of "phase_lock" are decided once per stream, on the two channels' mean power).  No key: false; a value that is not a bool:
+	// Runtime_error "Wrong field: link_channels"; written back only when true.  It combines with "phase_lock", "fft_size", "formant",
+	// "formant_shift" and "transients"; with "algorithm": "soundtouch" it is kept and has no effect.
+	bool link_channels_from_json(const Json::Value& value, const char* node_name);
 
 	class Velocity_modifier : public infra::Processor
 	{
@@ -47,6 +52,7 @@ namespace processor
 		bool phase_lock = false;
 		int fft_size = 1024;
 		bool transients = false;
+		bool link_channels = false;
 
 	  public:
 
@@ -63,7 +69,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override;            // velocity, keep_pitch (audio-velocity.cpp:479-485); algorithm, phase_lock, fft_size, transients when not the default
+		Json::Value serialize() const override;            // velocity, keep_pitch (audio-velocity.cpp:479-485); algorithm, phase_lock, fft_size, transients, link_channels when not the default
 		void deserialize(const Json::Value& value) override;  // :487-493
 	};
 
@@ -76,6 +82,7 @@ namespace processor
 		bool formant = false;
 		float formant_shift = 0;  // semitones
 		bool transients = false;
+		bool link_channels = false;
 
 	  public:
 
@@ -92,7 +99,7 @@ namespace processor
 			const std::atomic<bool>& stop_token,
 			std::any& user_data
 		) override;
-		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock, fft_size, formant, formant_shift, transients when not the default
+		Json::Value serialize() const override;            // pitch (:495-500); algorithm, phase_lock, fft_size, formant, formant_shift, transients, link_channels when not the default
 		void deserialize(const Json::Value& value) override;  // :502-505
 	};
 
