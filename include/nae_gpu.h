@@ -313,7 +313,7 @@ int nae_stretch_create_formant(nae_ctx* ctx, int sample_rate, int channels, floa
  * there they are a plain resampling (the formants move with the rate), while this entry with phi = 1 runs the envelope stage and keeps the
  * formants in place.  Flags, n_fft and lifter follow the _formant entries' rules.  phi not finite or <= 0: NAE_ERR_INVALID; outside
  * [NAE_FORMANT_SHIFT_MIN, NAE_FORMANT_SHIFT_MAX] = [0.25, 4] (+-24 semitones): NAE_ERR_UNSUPPORTED; phi is checked whatever the lifter.  The
- * cap NAE_FORMANT_MAX_GAIN stays.  Samples follow the tolerance path against tests/pv_fshift/ref_pv_fs.c; the result is independent of the
+ * cap NAE_FORMANT_MAX_GAIN stays.  Samples follow the tolerance path against tests/pv_ref/ref_pv.c; the result is independent of the
  * tiling, and a handle's output equals the block call's. */
 int nae_stretch_plan_make_shift(double rate, double pitch, double formant_ratio, int lifter, int n_fft, size_t in_len, nae_stretch_plan* plan);
 int nae_stretch_block_formant_shift_f32(nae_ctx* ctx, double rate, double pitch, unsigned flags, int n_fft, int lifter, double formant_ratio,
@@ -329,7 +329,7 @@ int nae_stretch_create_formant_shift(nae_ctx* ctx, int sample_rate, int channels
  * without onsets gives the unflagged call's bits.  It combines with NAE_STRETCH_PHASE_LOCK at 1024 (the locked maps reset too; the lock
  * at another size stays NAE_ERR_UNSUPPORTED); the _ex entries answer NAE_ERR_INVALID.  Without the vocoder stage (no tempo change) the flag
  * changes nothing.  Integer phases are bit-exact against the CPU
- * statement (tests/pv_transient/ref_pv_tr.c) and independent of the tiling; a handle's output equals the block call's. */
+ * statement (tests/pv_ref/ref_pv.c) and independent of the tiling; a handle's output equals the block call's. */
 #define NAE_STRETCH_TRANSIENTS 4u
 /* NAE_STRETCH_LINK_CHANNELS: channel link ("Channel link"), a flag of the _n, _formant and _formant_shift entries (block, create
  * and nae_debug_pv_tile_phase_n).  On a stereo stream the onset rule of NAE_STRETCH_TRANSIENTS and the peaks and regions of
@@ -338,7 +338,7 @@ int nae_stretch_create_formant_shift(nae_ctx* ctx, int sample_rate, int channels
  * synthesis phase.  The link is effective with ch == 2, the vocoder stage on and not forced, and the lock or transient preservation
  * effective; in every other case (mono, neither option, a forced stage, no vocoder stage) the call gives the bits of the call without
  * the flag.  With the lock at a size other than 1024 the call stays NAE_ERR_UNSUPPORTED; the _ex entries answer NAE_ERR_INVALID; bits 2
- * and 8 stay unknown flags.  Integer phases are bit-exact against the CPU statement (tests/pv_link/ref_pv_link.c) and independent of the
+ * and 8 stay unknown flags.  Integer phases are bit-exact against the CPU statement (tests/pv_ref/ref_pv.c) and independent of the
  * tiling; a handle's output equals the block call's. */
 #define NAE_STRETCH_LINK_CHANNELS 16u
 int nae_stretch_put(nae_stretch* h, const float* interleaved, size_t S);

@@ -1,4 +1,4 @@
-"""Formant shift independent of the pitch on the GPU ("Formant shift"), against the CPU statement tests/pv_fshift/ref_pv_fs.c.
+"""Formant shift independent of the pitch on the GPU ("Formant shift"), against the CPU statement tests/pv_ref/ref_pv.c.
 
 Cases: A a pitch change (both stage orders), B a tempo change only, C a rate change only (both orders; the forced stage with the transposer),
 D neither (the forced stage alone).  Bars: samples within 1e-4 relative RMS, the project's vocoder bar, at every frame size, mono and stereo,
@@ -14,7 +14,6 @@ import pytest
 
 import node_harness
 import orc
-import pv_fs_ref
 import pv_gpu
 import pv_ref
 from conftest import rel_rms
@@ -33,7 +32,7 @@ LOCK, TRANSIENTS = 1, 4
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_fs_ref.build(str(tmp_path_factory.mktemp("ref_pv_fs")))
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 def block(c, nae, x, ch, rate, pitch, phi, n_fft=1024, lifter=0, lock=False, transients=False, n_streams=1, planar=False):
@@ -72,7 +71,7 @@ def test_samples_vs_statement(nae, ref, n_fft, case, record_property):
                 assert "pv_env_kernel" in launched and not any(k.startswith("pv_any") or k.startswith("pv_phase") or "scan" in k for k in launched), launched
             else:
                 assert "pv_any_synth_formant_kernel" in launched and "pv_env_kernel" not in launched, launched
-            want = pv_fs_ref.stretch(ref, x, ch, rate, pitch, phi, n_fft, lifter=q)
+            want = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, lifter=q, formant_ratio=phi)
             assert got.size == want.size
             e = rel_rms(got, want)
             print(f"fshift {case} N={n_fft} ch={ch} planar={planar} phi={phi:.4f}: {e:.3e}")
@@ -86,7 +85,7 @@ def test_locked_pitch_change_vs_locked_statement(nae, ref):
         for name in ("A_first", "A_last"):
             rate, pitch = CASES[name]
             got = block(c, nae, x, 2, rate, pitch, DOWN, 1024, 68, lock=True)
-            want = pv_fs_ref.stretch(ref, x, 2, rate, pitch, DOWN, 1024, lock=True, lifter=68)
+            want = pv_ref.stretch(ref, x, 2, rate, pitch, 1024, lock=True, lifter=68, formant_ratio=DOWN)
             e = rel_rms(got, want)
             print(f"fshift locked {name}: {e:.3e}")
             assert got.size == want.size and e <= TOL, e
@@ -250,13 +249,13 @@ def test_error_codes(nae):
 def test_host_graph(ref, tmp_path, pitch_st, shift_st):
     """source -> Pitch_modifier {"pitch": p, "formant_shift": s} -> sink through the fiber runner: the block call's bits (checked by the
     harness), and the CPU statement within 1e-4"""
-    exe = node_harness.build("pv_fshift/host_pv_fshift.cpp", str(tmp_path))
+    exe = node_harness.build("pv_ref/host_pv_node.cpp", str(tmp_path))
     fin, fout = str(tmp_path / "in.f32"), str(tmp_path / "out.f32")
-    r = subprocess.run([exe, "gpu", str(pitch_st), str(shift_st), fin, fout], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "HOST PV FSHIFT OK gpu" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    r = subprocess.run([exe, "gpu", "formant_shift", str(pitch_st), str(shift_st), fin, fout], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "HOST PV NODE OK gpu formant_shift" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
     x, got = np.fromfile(fin, np.float32), np.fromfile(fout, np.float32)
     pitch = float(np.float32(2.0) ** np.float32(pitch_st / 12.0))
-    want = pv_fs_ref.stretch(ref, x, 2, 1.0, pitch, 2 ** (shift_st / 12), 1024, lifter=68)
+    want = pv_ref.stretch(ref, x, 2, 1.0, pitch, 1024, lifter=68, formant_ratio=2 ** (shift_st / 12))
     e = rel_rms(got, want)
     print(f"fshift host graph pitch {pitch_st:+d} shift {shift_st:+d}: {e:.3e}")
     assert got.size == want.size and e <= TOL, e

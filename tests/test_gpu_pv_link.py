@@ -1,5 +1,5 @@
 """Channel link (NAE_STRETCH_LINK_CHANNELS; DESIGN.md §3, "Channel link") on the GPU, against the CPU statement
-tests/pv_link/ref_pv_link.c.
+tests/pv_ref/ref_pv.c.
 
 Routes: every size with transient preservation, 1024 with the lock, 1024 with the lock and transient preservation.
 Bars: the integer synthesis phases are bit-exact at every route and tiling (the chunked scan from 256 tiles on included); the samples are
@@ -13,7 +13,6 @@ import numpy as np
 import pytest
 
 import node_harness
-import pv_link_ref
 import pv_ref
 from conftest import rel_rms
 from pv_gpu import profiled, same_bits, stream
@@ -32,7 +31,7 @@ ROUTES = [pytest.param(512, False, True, id="512-tr"), pytest.param(1024, False,
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_link_ref.build(str(tmp_path_factory.mktemp("ref_pv_link")))
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 def scene(L, seed=3, n_hits=None):
@@ -94,8 +93,8 @@ def test_integer_phases_bit_exact(nae, ref, n_fft, lock, tr, rate, pitch):
     frames; the linked phases are not the unlinked statement's"""
     L = 60000 * n_fft // 1024
     x = scene(L)
-    qs = pv_link_ref.synth_phase(ref, x, 2, rate, pitch, n_fft, lock, tr, link=True)
-    assert not np.array_equal(qs, pv_link_ref.synth_phase(ref, x, 2, rate, pitch, n_fft, lock, tr, link=False))
+    qs = pv_ref.synth_phase(ref, x, 2, rate, pitch, n_fft, lock, tr, link=True)
+    assert not np.array_equal(qs, pv_ref.synth_phase(ref, x, 2, rate, pitch, n_fft, lock, tr, link=False))
     for tile in (1, 3, 16, 64):
         with nae.Context(0) as c:
             c.debug_set("pv_tile", tile)
@@ -113,7 +112,7 @@ def test_long_stream_every_tiling_gives_the_same_bits(nae, ref, n_fft, lock, tr)
     x = scene(L, seed=11, n_hits=60)
     pl = nae.Context.stretch_plan(rate, pitch, L, n_fft)
     assert (pl.frames + 15) // 16 >= 256
-    qs = pv_link_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock, tr, link=True)
+    qs = pv_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock, tr, link=True)
     with nae.Context(0) as c:
         c.debug_set("pv_tile", 16)
         (got, t), launched = profiled(c, tile_phases, c, nae, x, ch, rate, pitch, n_fft, lock, tr)
@@ -136,7 +135,7 @@ def test_long_stream_every_tiling_gives_the_same_bits(nae, ref, n_fft, lock, tr)
 @pytest.mark.parametrize("stage", ["plain", "lifter", "shift-A", "shift-B"])
 @pytest.mark.parametrize("n_fft,lock,tr", ROUTES)
 def test_samples_vs_statement(ctx, nae, ref, n_fft, lock, tr, stage):
-    """within 1e-4 relative RMS of ref_pv_link_stretch: without a lifter, with the default lifter (_formant), and with _formant_shift in case
+    """within 1e-4 relative RMS of the linked CPU statement: without a lifter, with the default lifter (_formant), and with _formant_shift in case
     A (a pitch change) and case B (a tempo change only).  Measured values: DESIGN.md §3, "Channel link"."""
     x = scene(40000, seed=5)
     q = 0 if stage == "plain" else pv_ref.default_lifter(48000, n_fft)
@@ -144,8 +143,8 @@ def test_samples_vs_statement(ctx, nae, ref, n_fft, lock, tr, stage):
     pairs = [(1.5, 1 / 1.5)] if stage == "shift-B" else [(1.0, 2 ** (3 / 12)), (1.0, 2 ** (-7 / 12))] + ([(1.5, 1 / 1.5)] if stage == "plain" else [])
     for rate, pitch in pairs:
         got, launched = profiled(ctx, block, ctx, nae, x, 2, rate, pitch, n_fft, lock, tr, True, q, phi)
-        want = pv_link_ref.stretch(ref, x, 2, rate, pitch, n_fft, lock, q, tr, link=True, formant_ratio=phi)
-        unlinked = pv_link_ref.stretch(ref, x, 2, rate, pitch, n_fft, lock, q, tr, link=False, formant_ratio=phi)
+        want = pv_ref.stretch(ref, x, 2, rate, pitch, n_fft, lock, q, tr, link=True, formant_ratio=phi)
+        unlinked = pv_ref.stretch(ref, x, 2, rate, pitch, n_fft, lock, q, tr, link=False, formant_ratio=phi)
         assert got.size == want.size and np.isfinite(got).all()
         e = rel_rms(got, want)
         print(f"N={n_fft} lock={lock} tr={tr} {stage} rel RMS {rate:.4f}/{pitch:.4f}: {e:.3g} (to the unlinked statement {rel_rms(got, unlinked):.3g})")
@@ -268,7 +267,7 @@ def test_nan_in_one_channel(nae, ref, n_fft, lock, tr):
     L = 40000 * n_fft // 1024
     x = scene(L, seed=9).copy()
     x[2 * (L // 2) + 1] = np.nan
-    qs = pv_link_ref.synth_phase(ref, x, 2, 1.5, 1 / 1.5, n_fft, lock, tr, link=True)
+    qs = pv_ref.synth_phase(ref, x, 2, 1.5, 1 / 1.5, n_fft, lock, tr, link=True)
     for tile in (3, 16):
         with nae.Context(0) as c:
             c.debug_set("pv_tile", tile)
@@ -280,7 +279,7 @@ def test_host_graph_pitch_node_link_channels(tmp_path):
     """source -> Pitch_modifier {"pitch": 3, "fft_size": 2048, "transients": true, "link_channels": true} -> sink through the fiber runner
     equals the linked block call bit for bit and differs from the unlinked one; the same with {"pitch": 3, "phase_lock": true,
     "link_channels": true} at 1024"""
-    exe = node_harness.build("pv_link/host_pv_link.cpp", str(tmp_path))
-    for mode in ("gpu", "gpu_lock"):
-        r = subprocess.run([exe, mode], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and f"HOST PV LINK OK {mode}" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    exe = node_harness.build("pv_ref/host_pv_node.cpp", str(tmp_path))
+    for mode in (["gpu", "link_channels"], ["gpu", "link_channels", "lock"]):
+        r = subprocess.run([exe, *mode], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and "HOST PV NODE OK " + " ".join(mode) in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

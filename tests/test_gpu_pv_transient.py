@@ -1,5 +1,5 @@
 """Transient preservation (NAE_STRETCH_TRANSIENTS; DESIGN.md §3, "Transient preservation") on the GPU, against the CPU statement
-tests/pv_transient/ref_pv_tr.c.
+tests/pv_ref/ref_pv.c.
 
 Every test runs at every size unlocked and at 1024 locked (NAE_STRETCH_PHASE_LOCK | NAE_STRETCH_TRANSIENTS, the reset maps).
 Bars: the integer synthesis phases are bit-exact at every size and tiling (the segmented scan, the chunked scan from 256 tiles on, onsets on a
@@ -15,7 +15,6 @@ import pytest
 import node_harness
 import orc
 import pv_ref
-import pv_tr_ref
 from conftest import rel_rms
 from pv_gpu import profiled, same_bits, stream
 
@@ -31,7 +30,7 @@ ROUTES = [pytest.param(512, False, id="512"), pytest.param(1024, False, id="1024
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_tr_ref.build(str(tmp_path_factory.mktemp("ref_pv_tr")))
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 def attacks(L, ch, seed=3, n_hits=None):
@@ -111,7 +110,7 @@ def test_integer_phases_bit_exact(nae, ref, n_fft, lock, rate, pitch, ch):
     onsets fall on a 16-frame tile's first, second and last frame"""
     L = 60000 * n_fft // 1024
     for i, x in enumerate((attacks(L, ch), placed_clicks(nae, L, ch, rate, pitch, n_fft))):
-        qs = pv_tr_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock)
+        qs = pv_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock, transients=True)
         # the resets change the attacks' phases (a lone click in silence may already get its analysis phases without one: a flat spectrum
         # has no peak, so the locked frame runs unlocked)
         assert i == 1 or not np.array_equal(qs, pv_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock))
@@ -121,7 +120,7 @@ def test_integer_phases_bit_exact(nae, ref, n_fft, lock, rate, pitch, ch):
                 got, t = tile_phases(c, nae, x, ch, rate, pitch, n_fft, lock=lock)
             assert t == tile
             check_tiles(got, tile, qs, ch)
-    on = np.nonzero(pv_tr_ref.onsets(ref, x, ch, rate, pitch, n_fft).any(1))[0]
+    on = np.nonzero(pv_ref.onsets(ref, x, ch, rate, pitch, n_fft).any(1))[0]
     assert {0, 1, 15} <= set(on % 16), sorted(set(on % 16))
 
 
@@ -135,10 +134,10 @@ def test_chunked_scan_phases(nae, ref, n_fft, lock):
     pl = nae.Context.stretch_plan(rate, pitch, L, n_fft)
     n_tiles = (pl.frames + tile - 1) // tile
     assert n_tiles >= 256
-    on = np.nonzero(pv_tr_ref.onsets(ref, x, ch, rate, pitch, n_fft).any(1))[0]
+    on = np.nonzero(pv_ref.onsets(ref, x, ch, rate, pitch, n_fft).any(1))[0]
     per = (n_tiles + 15) // 16
     assert len(set(on // tile // per)) >= 8, on
-    qs = pv_tr_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock)
+    qs = pv_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock, transients=True)
     with nae.Context(0) as c:
         c.debug_set("pv_tile", tile)
         (got, t), launched = profiled(c, tile_phases, c, nae, x, ch, rate, pitch, n_fft, lock=lock)
@@ -153,12 +152,12 @@ def test_chunked_scan_phases(nae, ref, n_fft, lock):
 @pytest.mark.parametrize("rate,pitch", PAIRS)
 @pytest.mark.parametrize("n_fft,lock", ROUTES)
 def test_samples_vs_statement(ctx, nae, ref, n_fft, lock, rate, pitch, ch, lifter):
-    """within 1e-4 relative RMS of ref_pv_tr_stretch, with and without the formant lifter (it applies with the transposer on)"""
+    """within 1e-4 relative RMS of the flagged CPU statement, with and without the formant lifter (it applies with the transposer on)"""
     L = 40000
     x = attacks(L, ch, seed=5)
     q = pv_ref.default_lifter(48000, n_fft) if lifter == "default" else 0
     got, launched = profiled(ctx, block, ctx, nae, x, ch, rate, pitch, n_fft, True, q, lock)
-    want = pv_tr_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock, lifter=q)
+    want = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock, lifter=q, transients=True)
     assert got.size == want.size and np.isfinite(got).all()
     e = rel_rms(got, want)
     print(f"N={n_fft} lock={lock} rel RMS {rate:.4f}/{pitch:.4f} ch{ch} q{q}: {e:.3g}")
@@ -189,7 +188,7 @@ def onset_cuts(ref, nae, x, ch, rate, pitch, n_fft):
     """put sizes whose running totals make an onset frame available exactly, one sample early and one sample late"""
     L = x.size // ch
     pl = nae.Context.stretch_plan(rate, pitch, L, n_fft)
-    on = np.nonzero(pv_tr_ref.onsets(ref, x, ch, rate, pitch, n_fft).any(1))[0]
+    on = np.nonzero(pv_ref.onsets(ref, x, ch, rate, pitch, n_fft).any(1))[0]
     ends = []
     for i, f in enumerate(on[1:12]):
         end = (((int(f) - 1) * pl.ha_q24 + (1 << 23)) >> 24) - n_fft // 2 + n_fft
@@ -224,7 +223,7 @@ def test_without_onsets_the_flag_changes_nothing(nae, ref, n_fft, lock):
     unflagged call on the size-generic kernels, debug key pv_any = 1, which the flagged call runs; locked against the locked call)"""
     ch, rate, pitch = 2, 1.0, 2 ** (3 / 12)
     x = steady(60000, ch)
-    assert not pv_tr_ref.onsets(ref, x, ch, rate, pitch, n_fft).any()
+    assert not pv_ref.onsets(ref, x, ch, rate, pitch, n_fft).any()
     res = {}
     for tr in (False, True):
         with nae.Context(0) as c:
@@ -282,7 +281,7 @@ def test_flag_without_vocoder_is_a_no_op(ctx, nae):
 def test_host_graph_pitch_node_transients(tmp_path):
     """source -> Pitch_modifier {"pitch": 3, "fft_size": 2048, "transients": true} -> sink through the fiber runner equals the flagged block
     call bit for bit and differs from the unflagged one; the same with {"pitch": 3, "phase_lock": true, "transients": true} at 1024"""
-    exe = node_harness.build("pv_transient/host_pv_transient.cpp", str(tmp_path))
-    for mode in ("gpu", "gpu_lock"):
-        r = subprocess.run([exe, mode], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and f"HOST PV TRANSIENT OK {mode}" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    exe = node_harness.build("pv_ref/host_pv_node.cpp", str(tmp_path))
+    for mode in (["gpu", "transients"], ["gpu", "transients", "lock"]):
+        r = subprocess.run([exe, *mode], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and "HOST PV NODE OK " + " ".join(mode) in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

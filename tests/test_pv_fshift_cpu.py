@@ -1,8 +1,10 @@
 """Formant shift independent of the pitch ("Formant shift"), no GPU: the library's plan against the CPU statement
-tests/pv_fshift/ref_pv_fs.c in the four cases (A a pitch change, B a tempo change only, C a rate change only, D neither), limits and error
-codes; the statement against ref_pv_stretch at formant_ratio 1, its forced stage under the lock and transient preservation, and against the
-float64 numpy statement (tests/pv_fs_ref.py); what the shift does to a vowel; the host node's "formant_shift" key and the C ABI's
+tests/pv_ref/ref_pv.c in the four cases (A a pitch change, B a tempo change only, C a rate change only, D neither), limits and error
+codes; the shift rules against the plain rules at formant_ratio 1, its forced stage under the lock and transient preservation, and against the
+float64 numpy statement (tests/pv_fshift_numpy.py); what the shift does to a vowel; the host node's "formant_shift" key and the C ABI's
 declarations."""
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -12,7 +14,7 @@ import pytest
 
 import node_harness
 import orc
-import pv_fs_ref
+import pv_fshift_numpy
 import pv_ref
 from conftest import rel_rms
 from pv_gpu import tone
@@ -27,7 +29,7 @@ UP, DOWN = 2 ** (4 / 12), 2 ** (-5 / 12)
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_fs_ref.build(str(tmp_path_factory.mktemp("ref_pv_fs")))
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 @pytest.mark.parametrize("n_fft", pv_ref.SIZES)
@@ -41,8 +43,8 @@ def test_plan_is_the_statements(nae, ref, case, n_fft):
     for L in (0, 1, 777, 20000):
         for phi in (UP, DOWN, 1.0):
             got = nae.Context.stretch_plan(rate, pitch, L, n_fft, formant=q, formant_ratio=phi)
-            rc, want = pv_fs_ref.plan(ref, rate, pitch, phi, q, n_fft, L)
-            assert rc == 0 and pv_fs_ref.plan_fields(got) == pv_fs_ref.plan_fields(want), (L, phi)
+            rc, want = pv_ref.fs_plan(ref, rate, pitch, phi, q, n_fft, L)
+            assert rc == 0 and pv_ref.plan_fields(got) == pv_ref.plan_fields(want), (L, phi)
             plain = nae.Context.stretch_plan(rate, pitch, L, n_fft)
             forced = case[0] in "CD" and abs(plain.rate_eff / phi - 1.0) >= 1e-6
             assert (got.pv_on and got.tempo_eff == 1.0) == forced, (L, phi)
@@ -55,19 +57,19 @@ def test_plan_is_the_statements(nae, ref, case, n_fft):
                 # mid_len by the stage order's usual formula: the transposer's output when it runs first, else what it reads
                 assert got.mid_len == (int(np.floor(L / plain.rate_eff + 0.5)) if got.rs_first else plain.mid_len)
             else:
-                assert pv_fs_ref.plan_fields(got) == pv_fs_ref.plan_fields(plain), (L, phi)
+                assert pv_ref.plan_fields(got) == pv_ref.plan_fields(plain), (L, phi)
 
 
 def test_plan_without_the_envelope_stage_is_the_n_plan(nae):
     """lifter 0 with any ratio, and a ratio that cancels the transposer's (rho / phi = 1), give nae_stretch_plan_make_n's plan"""
     for n_fft in pv_ref.SIZES:
         for rate, pitch in CASES.values():
-            plain = pv_fs_ref.plan_fields(nae.Context.stretch_plan(rate, pitch, 5000, n_fft))
+            plain = pv_ref.plan_fields(nae.Context.stretch_plan(rate, pitch, 5000, n_fft))
             for phi in (0.25, DOWN, 1.0, UP, 4.0):
-                assert pv_fs_ref.plan_fields(nae.Context.stretch_plan(rate, pitch, 5000, n_fft, formant=0, formant_ratio=phi)) == plain
+                assert pv_ref.plan_fields(nae.Context.stretch_plan(rate, pitch, 5000, n_fft, formant=0, formant_ratio=phi)) == plain
             rho = nae.Context.stretch_plan(rate, pitch, 5000, n_fft).rate_eff
             for phi in (rho, rho * (1 + 5e-7)):
-                assert pv_fs_ref.plan_fields(nae.Context.stretch_plan(rate, pitch, 5000, n_fft, formant=17, formant_ratio=phi)) == plain
+                assert pv_ref.plan_fields(nae.Context.stretch_plan(rate, pitch, 5000, n_fft, formant=17, formant_ratio=phi)) == plain
 
 
 def test_plan_limits_and_error_codes(nae, ref):
@@ -82,10 +84,10 @@ def test_plan_limits_and_error_codes(nae, ref):
     for phi in (0.0, -1.0, float("nan"), float("inf"), -float("inf")):
         assert rc(1.0, 1.0, phi, 68, 1024) == INVALID, phi
         assert rc(1.0, 1.0, phi, 0, 1024) == INVALID, phi
-        assert pv_fs_ref.plan(ref, 1.0, 1.0, phi, 68, 1024, 1000)[0] == -1
+        assert pv_ref.fs_plan(ref, 1.0, 1.0, phi, 68, 1024, 1000)[0] == -1
     for phi in (0.2, 0.2499, 4.001, 5.0):
         assert rc(1.0, 1.0, phi, 68, 1024) == UNSUPPORTED, phi
-        assert pv_fs_ref.plan(ref, 1.0, 1.0, phi, 68, 1024, 1000)[0] == -2
+        assert pv_ref.fs_plan(ref, 1.0, 1.0, phi, 68, 1024, 1000)[0] == -2
     for phi in (0.25, 4.0):
         assert rc(1.0, 1.0, phi, 68, 1024) == 0, phi
     assert rc(1.0, 1.0, UP, -1, 1024) == INVALID and rc(1.0, 1.0, UP, 257, 1024) == INVALID and rc(1.0, 1.0, UP, 256, 1024) == 0
@@ -94,20 +96,27 @@ def test_plan_limits_and_error_codes(nae, ref):
     assert rc(1.0, 100.0, UP, 68, 1024) == UNSUPPORTED          # the tempo limit still holds
     spec = open(os.path.join(ROOT, "include", "nae_dsp_spec.h")).read()
     assert re.search(r"#define NAE_FORMANT_SHIFT_MIN 0\.25\b", spec) and re.search(r"#define NAE_FORMANT_SHIFT_MAX 4\.0\b", spec)
-    assert (nae.FORMANT_SHIFT_MIN, nae.FORMANT_SHIFT_MAX) == (0.25, 4.0) == (pv_fs_ref.SHIFT_MIN, pv_fs_ref.SHIFT_MAX)
+    assert (nae.FORMANT_SHIFT_MIN, nae.FORMANT_SHIFT_MAX) == (0.25, 4.0) == (pv_ref.SHIFT_MIN, pv_ref.SHIFT_MAX)
 
 
 @pytest.mark.parametrize("n_fft", pv_ref.SIZES)
 @pytest.mark.parametrize("case", ["A_up", "A_down", "B", "D"])
 def test_ratio_one_is_the_formant_statement(ref, case, n_fft):
-    """formant_ratio 1 in cases A, B, D: ref_pv_stretch with the same lifter bit for bit (and the lock at 1024)"""
+    """formant_ratio 1 in cases A, B, D (ref_pv_fs_plan, the envelope stage's own switch, g = rate_eff / phi): the plain rules (ref_pv_plan,
+    g = rate_eff) with the same lifter bit for bit (and the lock at 1024).  Where the vocoder runs, the plain rules' integer synthesis phases
+    are those recorded in tests/golden/pv_option_phase.json ("ratio one ...") from the statement this one replaced, at commit 602aacf"""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "pv_option_phase.json")))
     rate, pitch = CASES[case]
     q = pv_ref.default_lifter(48000, n_fft)
     for ch, x in ((1, orc.fill_uniform(9000, 5)), (2, np.stack([tone(9000), 0.5 * tone(9000)], 1).reshape(-1))):
         for lock in ((False, True) if n_fft == 1024 else (False,)):
-            got = pv_fs_ref.stretch(ref, x, ch, rate, pitch, 1.0, n_fft, lock=lock, lifter=q)
+            got = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock=lock, lifter=q, formant_ratio=1.0)
             want = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock=lock, lifter=q)
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (ch, lock)
+            if case != "D":
+                key = f"ratio one {case} ch{ch} {n_fft}" + (" locked" if lock else "")
+                digest = hashlib.sha256(np.ascontiguousarray(pv_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock), "<i4").tobytes()).hexdigest()
+                assert digest == golden[key], key
 
 
 @pytest.mark.parametrize("case", ["C_down", "C_up", "D"])
@@ -118,16 +127,16 @@ def test_forced_stage_ignores_lock_and_transients(ref, case):
     x = orc.fill_uniform(2 * 12000, 8) * np.repeat((np.arange(12000) % 4000 < 300).astype(np.float32) * 0.95 + 0.05, 2)   # bursts: onsets
     for n_fft in pv_ref.SIZES:
         q = pv_ref.default_lifter(48000, n_fft)
-        base = pv_fs_ref.stretch(ref, x, 2, rate, pitch, UP, n_fft, lifter=q)
+        base = pv_ref.stretch(ref, x, 2, rate, pitch, n_fft, lifter=q, formant_ratio=UP)
         for lock, tr in ((False, True), (True, False), (True, True)):
             if lock and n_fft != 1024:
                 continue
-            assert pv_fs_ref.forced_phase_diff(ref, x, 2, rate, pitch, UP, n_fft, lock, q, tr) == 0, (n_fft, lock, tr)
-            got = pv_fs_ref.stretch(ref, x, 2, rate, pitch, UP, n_fft, lock=lock, lifter=q, transients=tr)
+            assert pv_ref.forced_phase_diff(ref, x, 2, rate, pitch, UP, n_fft, lock, q, tr) == 0, (n_fft, lock, tr)
+            got = pv_ref.stretch(ref, x, 2, rate, pitch, n_fft, lock=lock, lifter=q, transients=tr, formant_ratio=UP)
             assert np.array_equal(got.view(np.uint32), base.view(np.uint32)), (n_fft, lock, tr)
-        assert pv_fs_ref.forced_phase_diff(ref, x, 2, rate, pitch, UP, n_fft, False, q, False) == 0
+        assert pv_ref.forced_phase_diff(ref, x, 2, rate, pitch, UP, n_fft, False, q, False) == 0
     # a stage that is not forced does move its phases (the counter counts)
-    assert pv_fs_ref.forced_phase_diff(ref, x, 2, 1.0, 2.0, UP, 1024, False, 68, False) > 0
+    assert pv_ref.forced_phase_diff(ref, x, 2, 1.0, 2.0, UP, 1024, False, 68, False) > 0
 
 
 NUMPY_CASES = [("A first", 1.0, 2.0), ("A last", 0.25, 2.0), ("B", 0.5, 2.0), ("C last", 0.8, 1.0), ("C first", 1.25, 1.0), ("D", 1.0, 1.0)]
@@ -142,8 +151,8 @@ def test_statement_matches_the_numpy_specification(ref, n_fft, name, rate, pitch
     x = orc.fill_uniform(24000, 3)
     q = pv_ref.default_lifter(48000, n_fft)
     for phi in (UP, DOWN):
-        got = pv_fs_ref.stretch(ref, x, 1, rate, pitch, phi, n_fft, lifter=q)
-        want = pv_fs_ref.numpy_stretch(x, 1, rate, pitch, n_fft, q, phi)
+        got = pv_ref.stretch(ref, x, 1, rate, pitch, n_fft, lifter=q, formant_ratio=phi)
+        want = pv_fshift_numpy.numpy_stretch(x, 1, rate, pitch, n_fft, q, phi)
         assert got.size == want.size
         e = rel_rms(got, want)
         print(f"{name} N={n_fft} phi={phi:.4f}: {e:.3e}")
@@ -211,7 +220,8 @@ def test_vowel_takes_the_shifted_envelope(ref, n_fft, pitch_st, shift_st):
     q = pv_ref.default_lifter(SR, n_fft)
     f1_in = harmonic_quality(x, F0, 1.0)[1]
     assert abs(f1_in - 717) < 5
-    y_on, y_one = pv_fs_ref.stretch(ref, x, 1, 1.0, p, phi, n_fft, lifter=q), pv_fs_ref.stretch(ref, x, 1, 1.0, p, 1.0, n_fft, lifter=q)
+    y_on = pv_ref.stretch(ref, x, 1, 1.0, p, n_fft, lifter=q, formant_ratio=phi)
+    y_one = pv_ref.stretch(ref, x, 1, 1.0, p, n_fft, lifter=q, formant_ratio=1.0)
     e_on, f1_on = harmonic_quality(y_on, F0 * p, phi)
     e_one, f1_one = harmonic_quality(y_one, F0 * p, phi)
     # what the envelopes themselves give on the output's harmonic grid in the same window
@@ -258,6 +268,6 @@ def test_host_node_formant_shift_key(tmp_path):
     """Pitch_modifier: "formant_shift" round-trips, is absent by default and at 0, a value that is not a number is "Wrong field:
     formant_shift", beyond +-24 it is a Runtime_error, it combines with phase_lock, fft_size, transients and formant, is kept with the
     soundtouch algorithm; Velocity_modifier has no such key"""
-    exe = node_harness.build("pv_fshift/host_pv_fshift.cpp", str(tmp_path))
-    r = subprocess.run([exe, "json"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "HOST PV FSHIFT OK json" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    exe = node_harness.build("pv_ref/host_pv_node.cpp", str(tmp_path))
+    r = subprocess.run([exe, "json", "formant_shift"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "HOST PV NODE OK json formant_shift" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

@@ -1,7 +1,9 @@
-"""Channel link of the K7 vocoder ("Channel link"), no GPU: the CPU statement (tests/pv_link/ref_pv_link.c) without the link
-is the transient statement bit for bit, duplicated mono is unchanged by the link, a one-sided hit resets both channels, the locked region
+"""Channel link of the K7 vocoder ("Channel link"), no GPU: the CPU statement (tests/pv_ref/ref_pv.c) without the link
+is each channel alone and the recorded phases, duplicated mono is unchanged by the link, a one-sided hit resets both channels, the locked region
 map is one per stream, the stereo coherence of a centred source does not get worse, and the C ABI, the binding and the host nodes carry
 the flag."""
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -10,7 +12,6 @@ import numpy as np
 import pytest
 
 import node_harness
-import pv_link_ref
 import pv_ref
 from pv_gpu import tone
 from test_pv_formant_cpu import vowel
@@ -23,7 +24,7 @@ INVALID, UNSUPPORTED = -1, -2
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_link_ref.build(str(tmp_path_factory.mktemp("ref_pv_link")))
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 def same_bits(a, b):
@@ -34,48 +35,42 @@ def stereo(left, right):
     return np.stack([left, right], 1).reshape(-1).astype(np.float32)
 
 
-def tr_stretch(ref, x, ch, rate, pitch, n_fft, lock, q, transients):
-    n = x.size // ch
-    _, pl = pv_ref.plan(ref, rate, pitch, n_fft, n)
-    out = np.empty(max(pl.out_len, 1) * ch, np.float32)
-    assert ref.ref_pv_tr_stretch(x.ctypes.data, n, ch, rate, pitch, n_fft, int(lock), q, int(transients), out.ctypes.data) == 0
-    return out[: pl.out_len * ch]
-
-
-def tr_phase(ref, x, ch, rate, pitch, n_fft, lock, transients):
-    n = x.size // ch
-    _, pl = pv_ref.plan(ref, rate, pitch, n_fft, n)
-    qs = np.empty((pl.frames, ch, n_fft // 2 + 1), np.int32)
-    assert ref.ref_pv_tr_synth_phase(x.ctypes.data, n, ch, rate, pitch, n_fft, int(lock), int(transients), qs.ctypes.data) == 0
-    return qs
+def phase_digest(qs):
+    return hashlib.sha256(np.ascontiguousarray(qs, "<i4").tobytes()).hexdigest()
 
 
 @pytest.mark.parametrize("n_fft", SIZES)
 @pytest.mark.parametrize("rate,pitch", [(1.0, 2 ** (3 / 12)), (1.0, 2 ** (-5 / 12)), (1.5, 1 / 1.5)])
 def test_unlinked_statement_is_the_transient_statement(ref, n_fft, rate, pitch):
-    """link = 0: samples and every frame's Qs equal ref_pv_tr_stretch / ref_pv_tr_synth_phase bit for bit — every size, the lock at 1024, with
-    and without transients, lifter 0 and the default lifter, mono and stereo, both stage orders; and with the _formant_shift rules
-    ref_pv_fs_stretch"""
+    """link = 0 — every size, the lock at 1024, with and without transients, both stage orders: a stereo stream is each of its channels run
+    alone as mono, bit for bit: the samples (lifter 0 and the default lifter), every frame's Qs and the onsets; and with the _formant_shift
+    rules the samples.  Mono and stereo, the integer synthesis phases of every frame are those recorded in
+    tests/golden/pv_option_phase.json ("unlinked ...": sha256 of the int32 [frames][ch][N/2 + 1] array) from the
+    transient statement this one replaced, at commit 602aacf, where the unlinked statement was tested equal to it"""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "pv_option_phase.json")))
     L = 12000
     m = tone(L)
     clicks = np.zeros(L, np.float32)
     clicks[3000::4000] = 0.8
-    for ch in (1, 2):
-        x = stereo(m + clicks, 0.5 * m) if ch == 2 else (m + clicks).astype(np.float32)
-        for lock in ((False, True) if n_fft == 1024 else (False,)):
-            for tr in (False, True):
-                for q in (0, pv_ref.default_lifter(SR, n_fft)):
-                    a = pv_link_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock, q, tr, link=False)
-                    assert same_bits(a, tr_stretch(ref, x, ch, rate, pitch, n_fft, lock, q, tr)), (ch, lock, tr, q)
-                assert np.array_equal(pv_link_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock, tr, link=False),
-                                      tr_phase(ref, x, ch, rate, pitch, n_fft, lock, tr)), (ch, lock, tr)
     x = stereo(m + clicks, 0.5 * m)
+    mono = [np.ascontiguousarray(x[c::2]) for c in (0, 1)]
+    for lock in ((False, True) if n_fft == 1024 else (False,)):
+        for tr in (False, True):
+            for q in (0, pv_ref.default_lifter(SR, n_fft)):
+                a = pv_ref.stretch(ref, x, 2, rate, pitch, n_fft, lock, q, tr, link=False)
+                for c in (0, 1):
+                    assert same_bits(np.ascontiguousarray(a[c::2]), pv_ref.stretch(ref, mono[c], 1, rate, pitch, n_fft, lock, q, tr)), (c, lock, tr, q)
+            qs, on, _ = pv_ref.taps(ref, x, 2, rate, pitch, n_fft, lock, tr, link=False)
+            key = f"{rate!r} {pitch!r} ch%d {n_fft}" + (" locked" if lock else "") + (" transients" if tr else "")
+            assert phase_digest(qs) == golden["unlinked " + key % 2], key % 2
+            for c in (0, 1):
+                qs_c, on_c, _ = pv_ref.taps(ref, mono[c], 1, rate, pitch, n_fft, lock, tr)
+                assert np.array_equal(qs[:, c], qs_c[:, 0]) and np.array_equal(on[:, c], on_c[:, 0]), (c, lock, tr)
+            assert phase_digest(pv_ref.synth_phase(ref, mono[0], 1, rate, pitch, n_fft, lock, tr)) == golden["unlinked " + key % 1], key % 1
     q = pv_ref.default_lifter(SR, n_fft)
-    a = pv_link_ref.stretch(ref, x, 2, rate, pitch, n_fft, False, q, True, link=False, formant_ratio=1.25)
-    n = x.size // 2
-    out = np.empty_like(a)
-    assert ref.ref_pv_fs_stretch(x.ctypes.data, n, 2, rate, pitch, n_fft, 0, q, 1, 1.25, out.ctypes.data) == 0
-    assert same_bits(a, out)
+    a = pv_ref.stretch(ref, x, 2, rate, pitch, n_fft, False, q, True, formant_ratio=1.25, link=False)
+    for c in (0, 1):
+        assert same_bits(np.ascontiguousarray(a[c::2]), pv_ref.stretch(ref, mono[c], 1, rate, pitch, n_fft, False, q, True, formant_ratio=1.25)), c
 
 
 @pytest.mark.parametrize("n_fft", SIZES)
@@ -90,11 +85,11 @@ def test_duplicated_mono_is_unchanged_by_the_link(ref, n_fft):
     cases = [(False, True)] + ([(True, False), (True, True)] if n_fft == 1024 else [])
     for lock, tr in cases:
         for rate, pitch in ((1.5, 1 / 1.5), (1.0, 2 ** (3 / 12))):
-            a = pv_link_ref.stretch(ref, x, 2, rate, pitch, n_fft, lock, 0, tr, link=True)
-            b = pv_link_ref.stretch(ref, x, 2, rate, pitch, n_fft, lock, 0, tr, link=False)
+            a = pv_ref.stretch(ref, x, 2, rate, pitch, n_fft, lock, 0, tr, link=True)
+            b = pv_ref.stretch(ref, x, 2, rate, pitch, n_fft, lock, 0, tr, link=False)
             assert same_bits(a, b), (lock, tr, rate)
-            ta = pv_link_ref.taps(ref, x, 2, rate, pitch, n_fft, lock, tr, link=True)
-            tb = pv_link_ref.taps(ref, x, 2, rate, pitch, n_fft, lock, tr, link=False)
+            ta = pv_ref.taps(ref, x, 2, rate, pitch, n_fft, lock, tr, link=True)
+            tb = pv_ref.taps(ref, x, 2, rate, pitch, n_fft, lock, tr, link=False)
             for u, v in zip(ta, tb):
                 assert np.array_equal(u, v), (lock, tr, rate)
             assert ta[1].any() or not tr, "the signal has onsets"
@@ -118,8 +113,8 @@ def test_one_sided_hit_resets_both_channels(ref, n_fft):
     its own Qa.  (The tone is at amplitude 0.05: the linked rule needs the click's power to rise over the tone's in 3/8 of the bins, which a
     single-sample click of amplitude 1 does in all bins but the tone's own few.)"""
     x, pos = one_sided_hit()
-    qs_u, on_u, _ = pv_link_ref.taps(ref, x, 2, 1.5, 1 / 1.5, n_fft, False, True, link=False)
-    qs, on_l, _ = pv_link_ref.taps(ref, x, 2, 1.5, 1 / 1.5, n_fft, False, True, link=True)
+    qs_u, on_u, _ = pv_ref.taps(ref, x, 2, 1.5, 1 / 1.5, n_fft, False, True, link=False)
+    qs, on_l, _ = pv_ref.taps(ref, x, 2, 1.5, 1 / 1.5, n_fft, False, True, link=True)
     assert not on_u[:, 1].any()
     assert on_u[:, 0].sum() == pos.size
     assert np.array_equal(on_l[:, 0], on_l[:, 1])
@@ -133,8 +128,8 @@ def test_one_sided_hit_resets_both_channels(ref, n_fft):
     f0 = int(f[0])
     assert np.array_equal(qs[:f0, 1], qs_u[:f0, 1]) and not np.array_equal(qs[f0, 1], qs_u[f0, 1])
     # and the linked output differs from the unlinked one in channel 1 only through those resets
-    y_l = pv_link_ref.stretch(ref, x, 2, 1.5, 1 / 1.5, n_fft, False, 0, True, link=True).reshape(-1, 2)
-    y_u = pv_link_ref.stretch(ref, x, 2, 1.5, 1 / 1.5, n_fft, False, 0, True, link=False).reshape(-1, 2)
+    y_l = pv_ref.stretch(ref, x, 2, 1.5, 1 / 1.5, n_fft, False, 0, True, link=True).reshape(-1, 2)
+    y_u = pv_ref.stretch(ref, x, 2, 1.5, 1 / 1.5, n_fft, False, 0, True, link=False).reshape(-1, 2)
     assert same_bits(np.ascontiguousarray(y_l[:, 0]), np.ascontiguousarray(y_u[:, 0]))        # channel 0 fired at the same frames already
     assert not same_bits(np.ascontiguousarray(y_l[:, 1]), np.ascontiguousarray(y_u[:, 1]))
 
@@ -156,8 +151,8 @@ def test_locked_regions_are_one_map_per_stream(ref, transients):
     peaks between the partials are each channel's own).  Rule 4 stays per channel: the linked Qs differ between the channels"""
     x = two_partials()
     for rate, pitch in ((0.6, 1 / 0.6), (1.5, 1 / 1.5)):
-        qs, _, sig_l = pv_link_ref.taps(ref, x, 2, rate, pitch, 1024, True, transients, link=True)
-        _, _, sig_u = pv_link_ref.taps(ref, x, 2, rate, pitch, 1024, True, transients, link=False)
+        qs, _, sig_l = pv_ref.taps(ref, x, 2, rate, pitch, 1024, True, transients, link=True)
+        _, _, sig_u = pv_ref.taps(ref, x, 2, rate, pitch, 1024, True, transients, link=False)
         assert np.array_equal(sig_l[:, 0], sig_l[:, 1])
         assert (sig_u[:, 0] != sig_u[:, 1]).any(axis=1).sum() >= 1
         assert (sig_l[1:, 0] != np.arange(513)).any(), "the frames are locked"
@@ -185,8 +180,8 @@ def test_stereo_coherence_does_not_get_worse(ref, velocity):
     velocity 0.6 and 1.5: 1 - rho_linked <= 1 - rho_unlinked.  The yardstick is the unlinked statement (the behaviour without the flag).
     Measured (1 - rho), unlinked / linked: see DESIGN.md §3, "Channel link"."""
     x = centred_vowel()
-    r_l = coherence(pv_link_ref.stretch(ref, x, 2, velocity, 1 / velocity, 1024, True, 0, False, link=True))
-    r_u = coherence(pv_link_ref.stretch(ref, x, 2, velocity, 1 / velocity, 1024, True, 0, False, link=False))
+    r_l = coherence(pv_ref.stretch(ref, x, 2, velocity, 1 / velocity, 1024, True, 0, False, link=True))
+    r_u = coherence(pv_ref.stretch(ref, x, 2, velocity, 1 / velocity, 1024, True, 0, False, link=False))
     print(f"velocity {velocity}: 1 - rho unlinked {1 - r_u:.6e} linked {1 - r_l:.6e}")
     assert 1 - r_l <= 1 - r_u, (velocity, 1 - r_u, 1 - r_l)
 
@@ -211,11 +206,11 @@ def test_link_is_effective_only_where_the_specification_says(ref):
     for kw in same:
         kw = dict(kw)
         sig = kw.pop("x")
-        assert same_bits(pv_link_ref.stretch(ref, sig, link=True, **kw), pv_link_ref.stretch(ref, sig, link=False, **kw)), kw
+        assert same_bits(pv_ref.stretch(ref, sig, link=True, **kw), pv_ref.stretch(ref, sig, link=False, **kw)), kw
     for kw in (dict(transients=True), dict(transients=True, lock=True), dict(transients=True, lifter=q, rate=1.0, pitch=2 ** (3 / 12)),
                dict(transients=True, lifter=q, formant_ratio=1.2, rate=1.0, pitch=2 ** (3 / 12))):
         kw = dict(dict(rate=1.5, pitch=1 / 1.5), **kw)
-        assert not same_bits(pv_link_ref.stretch(ref, x, 2, link=True, **kw), pv_link_ref.stretch(ref, x, 2, link=False, **kw)), kw
+        assert not same_bits(pv_ref.stretch(ref, x, 2, link=True, **kw), pv_ref.stretch(ref, x, 2, link=False, **kw)), kw
 
 
 def test_nan_in_one_channel(ref):
@@ -224,7 +219,7 @@ def test_nan_in_one_channel(ref):
     x, pos = one_sided_hit()
     x = x[: 2 * 30000].copy()
     x[2 * 4800 + 1] = np.nan                      # channel 1, under the first click
-    qs, on, _ = pv_link_ref.taps(ref, x, 2, 1.5, 1 / 1.5, 1024, False, True, link=True)
+    qs, on, _ = pv_ref.taps(ref, x, 2, 1.5, 1 / 1.5, 1024, False, True, link=True)
     assert np.array_equal(on[:, 0], on[:, 1])
     _, pl = pv_ref.plan(ref, 1.5, 1 / 1.5, 1024, 30000)
     f = np.arange(pl.frames)
@@ -241,10 +236,10 @@ def test_plan_and_flag_codes(ref, nae):
     for n_fft in SIZES:
         q = pv_ref.default_lifter(SR, n_fft)
         for kw in (dict(), dict(lifter=q), dict(lifter=q, formant_ratio=1.2)):
-            rc, y = pv_link_ref.stretch_rc(ref, x, 2, 1.0, 2 ** (3 / 12), n_fft, transients=True, link=True, **kw)
+            rc, y = pv_ref.stretch_rc(ref, x, 2, 1.0, 2 ** (3 / 12), n_fft, transients=True, link=True, **kw)
             assert rc == 0 and y is not None, (n_fft, kw)
             if n_fft != 1024:
-                rc, _ = pv_link_ref.stretch_rc(ref, x, 2, 1.0, 2 ** (3 / 12), n_fft, lock=True, link=True, **kw)
+                rc, _ = pv_ref.stretch_rc(ref, x, 2, 1.0, 2 ** (3 / 12), n_fft, lock=True, link=True, **kw)
                 assert rc == UNSUPPORTED, (n_fft, kw)
     h = open(os.path.join(ROOT, "include", "nae_gpu.h")).read()
     assert re.search(r"#define\s+NAE_STRETCH_LINK_CHANNELS\s+16u\b", h)
@@ -261,6 +256,6 @@ def test_plan_and_flag_codes(ref, nae):
 def test_host_node_link_channels_key(tmp_path):
     """Velocity_modifier / Pitch_modifier: "link_channels" is absent by default (the default serialisation is unchanged), written back only
     when true, a non-bool is "Wrong field: link_channels", it combines with the other vocoder keys and is kept with the soundtouch algorithm"""
-    exe = node_harness.build("pv_link/host_pv_link.cpp", str(tmp_path))
-    r = subprocess.run([exe, "json"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "HOST PV LINK OK json" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    exe = node_harness.build("pv_ref/host_pv_node.cpp", str(tmp_path))
+    r = subprocess.run([exe, "json", "link_channels"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "HOST PV NODE OK json link_channels" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

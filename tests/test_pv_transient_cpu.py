@@ -1,6 +1,8 @@
 """Transient preservation of the K7 vocoder ("Transient preservation"), no GPU: the CPU statement
-(tests/pv_transient/ref_pv_tr.c) without the flag is the vocoder's statement bit for bit, its onset rule is a numpy float32 restatement of
+(tests/pv_ref/ref_pv.c) without the flag is the oracle and the recorded phases, its onset rule is a numpy float32 restatement of
 the specification's, attacks stay sharp, steady signals give no onset, and the C ABI, the binding and the host nodes carry the flag."""
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -11,7 +13,6 @@ import pytest
 import node_harness
 import orc
 import pv_ref
-import pv_tr_ref
 from pv_gpu import tone
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,30 +25,53 @@ SETTINGS = [(0.6, 1 / 0.6), (1.5, 1 / 1.5), (1.0, 2 ** (3 / 12)), (1.0, 2 ** (-7
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return pv_tr_ref.build(str(tmp_path_factory.mktemp("ref_pv_tr")))
+    return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
 
 
 def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
+def phase_digest(qs):
+    return hashlib.sha256(np.ascontiguousarray(qs, "<i4").tobytes()).hexdigest()
+
+
+def faded(x, m=960):
+    """a 20 ms raised-cosine fade-out: an abrupt end is itself an attack (its splatter rises in every bin far from the signal's own).  The
+    start needs none: its first frames are high from frame 1 on, and frame 1 never fires."""
+    x = np.asarray(x, np.float64).copy()
+    x[-m:] *= 0.5 + 0.5 * np.cos(np.pi * np.arange(m) / m)
+    return x.astype(np.float32)
+
+
 @pytest.mark.parametrize("n_fft", SIZES)
 @pytest.mark.parametrize("ch", [1, 2])
 @pytest.mark.parametrize("rate,pitch", [(1.0, 2 ** (3 / 12)), (1.0, 2 ** (-5 / 12)), (1.5, 1 / 1.5)])
 def test_unflagged_statement_is_the_vocoder_statement(ref, n_fft, ch, rate, pitch):
-    """transients = 0: samples and every frame's Qs equal ref_pv_stretch / ref_pv_synth_phase bit for bit — every size, the lock at 1024,
-    lifter 0 and the default lifter, mono and stereo, both stage orders (pitch up: transposer first)"""
+    """transients = 0 — every size, the lock at 1024, mono and stereo, both stage orders (pitch up: transposer first): at 1024 unlocked with
+    lifter 0 the samples are the oracle's bit for bit; in every case the integer synthesis phases of every frame are those recorded in
+    tests/golden/pv_option_phase.json ("unflagged ...": sha256 of the int32 [frames][ch][N/2 + 1] array) from the
+    statement this one replaced, at commit 602aacf, where the unflagged transient statement was tested equal to it.  And the flag changes
+    nothing on a steady input: with the 20 ms fade-out of test_no_false_onsets, transients = 1 gives the bits of transients = 0, samples
+    (lifter 0 and the default lifter) and phases.  (Without the fade the two-tone's abrupt end fires one onset, in a frame whose window spans
+    the end, in every case here — at 602aacf too — so the fade is part of the claim.)"""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "pv_option_phase.json")))
     L = 12000
     m = tone(L)
     x = np.stack([m, 0.5 * m], 1).reshape(-1) if ch == 2 else m
+    xf = np.stack([faded(m), faded(0.5 * m)], 1).reshape(-1) if ch == 2 else faded(m)
     locks = (False, True) if n_fft == 1024 else (False,)
     for lock in locks:
+        if n_fft == 1024 and not lock:
+            assert same_bits(pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, transients=False), orc.stretch(x, ch, rate, pitch))
+        key = f"unflagged {rate!r} {pitch!r} ch{ch} {n_fft}" + (" locked" if lock else "")
+        assert phase_digest(pv_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock, transients=False)) == golden[key], key
         for q in (0, pv_ref.default_lifter(SR, n_fft)):
-            a = pv_tr_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock, q, transients=False)
-            b = pv_ref.stretch(ref, x, ch, rate, pitch, n_fft, lock, q)
+            a = pv_ref.stretch(ref, xf, ch, rate, pitch, n_fft, lock, q, transients=True)
+            b = pv_ref.stretch(ref, xf, ch, rate, pitch, n_fft, lock, q, transients=False)
             assert same_bits(a, b), (lock, q)
-        assert np.array_equal(pv_tr_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock, transients=False),
-                              pv_ref.synth_phase(ref, x, ch, rate, pitch, n_fft, lock)), lock
+        assert np.array_equal(pv_ref.synth_phase(ref, xf, ch, rate, pitch, n_fft, lock, transients=True),
+                              pv_ref.synth_phase(ref, xf, ch, rate, pitch, n_fft, lock, transients=False)), lock
 
 
 def numpy_onsets(P, n_fft):
@@ -98,14 +122,14 @@ def test_onset_rule_on_synthetic_spectra(ref, n_fft):
     }
     for name, (frames, want) in cases.items():
         P = np.stack(frames)
-        got = pv_tr_ref.onset_rule(ref, P, n_fft)
+        got = pv_ref.onset_rule(ref, P, n_fft)
         assert list(got) == want, name
         assert np.array_equal(got, numpy_onsets(P, n_fft)), name
     rng = np.random.default_rng(n_fft)
     for trial in range(20):
         P = (rng.exponential(1.0, (12, B)) * rng.choice([1e-9, 1.0, 8.0, 100.0], (12, 1))).astype(np.float32)
         P[rng.random(P.shape) < 0.01] = np.nan
-        assert np.array_equal(pv_tr_ref.onset_rule(ref, P, n_fft), numpy_onsets(P, n_fft)), trial
+        assert np.array_equal(pv_ref.onset_rule(ref, P, n_fft), numpy_onsets(P, n_fft)), trial
 
 
 def click_train():
@@ -119,7 +143,7 @@ def click_train():
 def click_width(ref, n_fft, transients):
     """the width of tests/test_pv_sizes_cpu.py's click_width on the flagged or unflagged statement"""
     x, pos = click_train()
-    y = pv_tr_ref.stretch(ref, x, 1, 1.5, 1 / 1.5, n_fft, transients=transients).astype(np.float64)
+    y = pv_ref.stretch(ref, x, 1, 1.5, 1 / 1.5, n_fft, transients=transients).astype(np.float64)
     widths = []
     for p in pos:
         c = int(round(p / 1.5))
@@ -136,7 +160,7 @@ def test_attacks_stay_sharp(ref):
     75 / 0.00001, 208 / 0.00002, 327 / 3.3, 709 / 0.0001 samples at 512 / 1024 / 2048 / 4096 (a single-sample click comes back a single sample)"""
     x, pos = click_train()
     for n_fft in SIZES:
-        on = pv_tr_ref.onsets(ref, x, 1, 1.5, 1 / 1.5, n_fft)[:, 0]
+        on = pv_ref.onsets(ref, x, 1, 1.5, 1 / 1.5, n_fft)[:, 0]
         f = np.nonzero(on)[0]
         assert f.size == pos.size, (n_fft, f)
         _, pl = pv_ref.plan(ref, 1.5, 1 / 1.5, n_fft, x.size)
@@ -147,14 +171,6 @@ def test_attacks_stay_sharp(ref):
     for n in (1024, 2048, 4096):
         assert w[n][1] <= 0.5 * w[n][0], w
     assert w[4096][1] <= w[1024][0], w
-
-
-def faded(x, m=960):
-    """a 20 ms raised-cosine fade-out: an abrupt end is itself an attack (its splatter rises in every bin far from the signal's own).  The
-    start needs none: its first frames are high from frame 1 on, and frame 1 never fires."""
-    x = np.asarray(x, np.float64).copy()
-    x[-m:] *= 0.5 + 0.5 * np.cos(np.pi * np.arange(m) / m)
-    return x.astype(np.float32)
 
 
 def steady_signals():
@@ -190,12 +206,12 @@ def test_no_false_onsets(ref, n_fft):
     for name, x in steady_signals().items():
         x = faded(x)
         for rate, pitch in SETTINGS:
-            assert not pv_tr_ref.onsets(ref, x, 1, rate, pitch, n_fft).any(), (name, rate, pitch)
-            assert same_bits(pv_tr_ref.stretch(ref, x, 1, rate, pitch, n_fft, transients=True),
-                             pv_tr_ref.stretch(ref, x, 1, rate, pitch, n_fft, transients=False)), (name, rate, pitch)
+            assert not pv_ref.onsets(ref, x, 1, rate, pitch, n_fft).any(), (name, rate, pitch)
+            assert same_bits(pv_ref.stretch(ref, x, 1, rate, pitch, n_fft, transients=True),
+                             pv_ref.stretch(ref, x, 1, rate, pitch, n_fft, transients=False)), (name, rate, pitch)
     x, pos = bursts()
     for rate, pitch in SETTINGS:
-        on = pv_tr_ref.onsets(ref, x, 1, rate, pitch, n_fft)[:, 0]
+        on = pv_ref.onsets(ref, x, 1, rate, pitch, n_fft)[:, 0]
         f = np.nonzero(on)[0]
         assert f.size == len(pos), (rate, pitch, f)
         _, pl = pv_ref.plan(ref, rate, pitch, n_fft, x.size)
@@ -220,6 +236,6 @@ def test_abi_declares_the_flag(nae):
 def test_host_node_transients_key(tmp_path):
     """Velocity_modifier / Pitch_modifier: "transients" is absent by default, written back only when true, a non-bool or true with
     "phase_lock" is "Wrong field: transients", it combines with "fft_size" and "formant" and is kept with the soundtouch algorithm"""
-    exe = node_harness.build("pv_transient/host_pv_transient.cpp", str(tmp_path))
-    r = subprocess.run([exe, "json"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "HOST PV TRANSIENT OK json" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    exe = node_harness.build("pv_ref/host_pv_node.cpp", str(tmp_path))
+    r = subprocess.run([exe, "json", "transients"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "HOST PV NODE OK json transients" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
