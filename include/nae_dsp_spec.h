@@ -22,6 +22,12 @@
 /* formant shift ("Formant shift"): the range of formant_ratio, +-24 semitones */
 #define NAE_FORMANT_SHIFT_MIN 0.25
 #define NAE_FORMANT_SHIFT_MAX 4.0
+/* K9 FIR filter ("K9 FIR filter"): overlap-save at frame size N = 512 ... 4096 with N / 2 new samples per block, so at most
+ * N / 2 + 1 taps — 2049 at 4096; the designs are Kaiser-windowed sincs with the transposer's beta; a tile the library chooses has at least
+ * NAE_FIR_MIN_TILE blocks (it re-reads half a block at its head) */
+#define NAE_FIR_MAX_TAPS 2049
+#define NAE_FIR_KAISER_BETA 8.0
+#define NAE_FIR_MIN_TILE 8
 /* transient preservation ("Transient preservation"): bin k of frame f rises iff P_f[k] > RISE * P_{f-1}[k] and
  * P_f[k] > FLOOR * N; frame f is "high" iff DEN * (rising bins) >= NUM * (N/2 + 1); an onset is an upward crossing of "high" at f >= 2.
  * RISE is +6 dB: at +3 dB steady white noise crosses 3/8 at N = 512 and 1024 (DESIGN.md gives the numbers). */

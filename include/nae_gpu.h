@@ -41,7 +41,8 @@ extern "C" {
  *   a library without it answers NAE_ERR_INVALID; nae_stretch_plan_make_shift, nae_stretch_block_formant_shift_f32 and
  *   nae_stretch_create_formant_shift (formant shift independent of the pitch); NAE_STRETCH_LINK_CHANNELS with the _n, _formant and
  *   _formant_shift entries (one onset decision and one phase-lock region map per stereo stream), probed by return code as
- *   NAE_STRETCH_TRANSIENTS is. */
+ *   NAE_STRETCH_TRANSIENTS is; nae_fir_pick_n_fft, nae_fir_block_f32, nae_fir_design and the nae_fir handle (nae_fir_create, _put, _put_host, _flush,
+ *   _available, _receive, _receive_host, _destroy): the FIR filter, K9. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -63,6 +64,7 @@ typedef struct nae_ctx nae_ctx;
 typedef struct nae_event nae_event;
 typedef struct nae_stretch nae_stretch;
 typedef struct nae_spectrum nae_spectrum;
+typedef struct nae_fir nae_fir;
 
 /* ------------------------------------------------------------------ context / plumbing */
 int nae_abi_version(void);
@@ -140,6 +142,7 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *   pv_any          1: unlocked 1024-point vocoder launches run the size-generic kernels of the other frame sizes (the same integer phases, bit
  *                   for bit; samples within the tolerance); the tile is pv_tile, else one of at least pv_min_ptile frames (default 64)
  *   td_nc           1 | 2 | 4: candidates per thread of the WSOLA search;  st_unfused  1: filter and cubic stage of the WSOLA chain as two launches
+ *   fir_tile        blocks (of n_fft / 2 samples) one wave of the FIR filter walks; every tiling gives the same bits
  * The same assignments, comma separated, in the environment variable NAE_DEBUG ("pv_flow=2,pv_fps=4") are applied when a context is created
  * (for measuring a program that creates its contexts itself, e.g. bench.py); an unknown key there fails nae_ctx_create with NAE_ERR_INVALID. */
 int nae_debug_set(nae_ctx* ctx, const char* key, long long value);
@@ -433,6 +436,45 @@ int nae_spectrum_put(nae_spectrum* h, const float* interleaved, size_t S);
 size_t nae_spectrum_available(nae_spectrum* h);                         /* whole frames ready */
 int nae_spectrum_receive(nae_spectrum* h, float* dst, size_t max_frames, size_t* got);
 int nae_spectrum_destroy(nae_spectrum* h);
+
+/* ------------------------------------------------------------------ K9 FIR filter
+ * no reference code (the reference has no filter node).  Spec ("K9 FIR filter"): taps h[0 ... L-1] in f32, one set for every stream
+ * and channel of a call; the result is the causal convolution y[n] = sum_{j < L} h[j] x[n - j], 0 <= n < in_len, x[n] = 0 for n < 0, computed by
+ * overlap-save at frame size N = n_fft = 512, 1024, 2048 or 4096 with M = B = N / 2 and 1 <= L <= B + 1, every step an IEEE operation in a fixed
+ * order:
+ *   1  H = r2c_N(h zero-padded to N), the canonical r2c without a window, bins 0 ... M — on the device, once per call or handle;
+ *   2  block b = 0 ... ceil(in_len / B) - 1 reads u[n] = x[b B - B + n], n < N (zero outside [0, in_len)); U = r2c_N(u), no window;
+ *   3  Y[k] = (U.x H.x - U.y H.y, U.x H.y + U.y H.x): four products, one subtract, one add, no FMA;
+ *   4  v = c2r_N(Y), the canonical c2r (split with T_N, conjugate, forward FFT_M, scale 1 / M; the imaginary parts of bins 0 and M dropped);
+ *   5  y[b B + n] = v[B + n], n < B, wherever b B + n < in_len.
+ * Bit-exact against the CPU statement (tests/fir_ref/ref_fir.c) and independent of the tiling.  A non-finite input sample changes only the
+ * blocks whose u contains it.  The bits depend on N, so N is part of the call: n_fft = 0 means nae_fir_pick_n_fft(n_taps), the smallest
+ * supported N with N / 2 + 1 >= n_taps (0 when there is none, or n_taps < 1).
+ * Errors: a null pointer, n_taps < 1 or ch not 1 or 2: NAE_ERR_INVALID; an unsupported n_fft, or n_taps > n_fft / 2 + 1: NAE_ERR_UNSUPPORTED;
+ * in_len = 0 or n_streams = 0: NAE_OK, nothing is launched.  src and dst are interleaved or planar views (src->stream_stride may be 0); dst
+ * receives in_len frames.  The context keeps the taps and H of its last block call: a call with the same taps and size computes neither again. */
+int nae_fir_pick_n_fft(int n_taps);
+int nae_fir_block_f32(nae_ctx* ctx, const float* taps_host, int n_taps, int n_fft, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                      const nae_sig* dst);
+/* SoundTouch-shaped streaming handle (interleaved f32, device pointers), parameters and errors as the block call's.  The first in_len frames it
+ * delivers equal the block call's bit for bit, however the input is cut into puts (whole blocks come out as they fill).  nae_fir_flush appends
+ * n_taps - 1 zero frames, so the tail of the convolution comes out too: in_len + n_taps - 1 frames in all, the block call on the input
+ * extended by those zeros.  A put after the flush: NAE_ERR_STATE. */
+int nae_fir_create(nae_ctx* ctx, const float* taps_host, int n_taps, int n_fft, int channels, nae_fir** h);
+int nae_fir_put(nae_fir* h, const float* interleaved, size_t S);
+int nae_fir_put_host(nae_fir* h, const float* interleaved_host, size_t S);
+int nae_fir_flush(nae_fir* h);
+size_t nae_fir_available(nae_fir* h);
+int nae_fir_receive(nae_fir* h, float* dst, size_t max_frames, size_t* got);
+int nae_fir_receive_host(nae_fir* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_fir_destroy(nae_fir* h);
+/* Linear-phase (type I) designs on the host, in double, rounded once to f32: n_taps = L odd, Kaiser window beta = 8 (the transposer's),
+ *   lp(fc)[n] = s[n] / sum s,  s[n] = c sinc(pi c t) w[n],  c = 2 fc / sample_rate,  t = n - (L - 1) / 2,  sinc(0) = 1,
+ *   w[n] = I0(beta sqrt(1 - a^2)) / I0(beta),  a = t / ((L - 1) / 2)  (L = 1: w = 1),
+ * kind 0 low-pass lp(f_hi); 1 high-pass delta[(L - 1) / 2] - lp(f_lo); 2 band-pass lp(f_hi) - lp(f_lo); 3 band-stop delta - (lp(f_hi) - lp(f_lo)).
+ * The frequencies a kind uses lie in (0, sample_rate / 2), f_lo < f_hi for kinds 2 and 3; the other one is ignored.  Anything else — another
+ * kind, an even or non-positive n_taps, sample_rate <= 0, a null pointer — is NAE_ERR_INVALID.  No context, no device work. */
+int nae_fir_design(int kind, int sample_rate, double f_lo, double f_hi, int n_taps, float* taps_host);
 
 /* ------------------------------------------------------------------ the 4-node graph of BASELINE.json
  * input -> mix(2) -> pitch -> FFT spectrum, one launch sequence over n_streams independent streams.

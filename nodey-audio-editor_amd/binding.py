@@ -34,6 +34,8 @@ EXPORTED_SYMBOLS = [
     "nae_spectrum_available", "nae_spectrum_receive", "nae_spectrum_destroy", "nae_graph4_run",
     "nae_wsola_plan_make", "nae_wsola_block_f32", "nae_wsola_create", "nae_wsola_put", "nae_wsola_put_host",
     "nae_wsola_flush", "nae_wsola_available", "nae_wsola_receive", "nae_wsola_receive_host", "nae_wsola_destroy",
+    "nae_fir_pick_n_fft", "nae_fir_block_f32", "nae_fir_design", "nae_fir_create", "nae_fir_put", "nae_fir_put_host", "nae_fir_flush",
+    "nae_fir_available", "nae_fir_receive", "nae_fir_receive_host", "nae_fir_destroy",
 ]
 
 
@@ -41,6 +43,8 @@ STRETCH_PHASE_LOCK = 1       # NAE_STRETCH_PHASE_LOCK (include/nae_gpu.h)
 STRETCH_TRANSIENTS = 4       # NAE_STRETCH_TRANSIENTS (include/nae_gpu.h): the _n and _formant entries only
 STRETCH_LINK_CHANNELS = 16   # NAE_STRETCH_LINK_CHANNELS: one onset decision and one lock map per stereo stream; the same entries
 FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX = 0.25, 4.0   # NAE_FORMANT_SHIFT_MIN / _MAX (include/nae_dsp_spec.h): the range of formant_ratio
+FIR_SIZES = (512, 1024, 2048, 4096)                 # frame sizes of the FIR filter: at most n_fft / 2 + 1 taps
+FIR_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}   # `kind` of nae_fir_design
 
 
 class NaeError(RuntimeError):
@@ -178,6 +182,11 @@ def load_library() -> C.CDLL:
         "nae_wsola_put_host": (i, [vp, vp, sz]), "nae_wsola_flush": (i, [vp]), "nae_wsola_available": (sz, [vp]),
         "nae_wsola_receive": (i, [vp, vp, sz, P(sz)]), "nae_wsola_receive_host": (i, [vp, vp, sz, P(sz)]),
         "nae_wsola_destroy": (i, [vp]),
+        "nae_fir_pick_n_fft": (i, [i]), "nae_fir_block_f32": (i, [vp, vp, i, i, P(Sig), sz, i, sz, P(Sig)]),
+        "nae_fir_design": (i, [i, i, d, d, i, vp]), "nae_fir_create": (i, [vp, vp, i, i, i, P(vp)]),
+        "nae_fir_put": (i, [vp, vp, sz]), "nae_fir_put_host": (i, [vp, vp, sz]), "nae_fir_flush": (i, [vp]),
+        "nae_fir_available": (sz, [vp]), "nae_fir_receive": (i, [vp, vp, sz, P(sz)]),
+        "nae_fir_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_fir_destroy": (i, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -517,6 +526,27 @@ class Context:
         """any size 256..4096 and hop 1..n_fft; records of n_fft/2 + 1 floats"""
         self._ck(self.lib.nae_spectrum_block_ex_f32(self.h, n_fft, hop, C.byref(src), T, ch, n_streams, dst, dst_stream_stride))
 
+    # -- K9
+    @staticmethod
+    def fir_pick_n_fft(n_taps: int) -> int:
+        """the smallest frame size with n_fft / 2 + 1 >= n_taps; 0 when there is none"""
+        return int(load_library().nae_fir_pick_n_fft(n_taps))
+
+    @staticmethod
+    def fir_design(kind, sample_rate: int, f_lo: float, f_hi: float, n_taps: int) -> np.ndarray:
+        """Kaiser-8 linear-phase taps (nae_fir_design); kind: "lowpass" (f_hi) | "highpass" (f_lo) | "bandpass" | "bandstop", or 0 ... 3"""
+        taps = np.empty(max(n_taps, 1), np.float32)
+        rc = load_library().nae_fir_design(FIR_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind), sample_rate, f_lo, f_hi, n_taps,
+                                           taps.ctypes.data)
+        if rc:
+            raise NaeError(f"nae_fir_design({kind}, {sample_rate}, {f_lo}, {f_hi}, {n_taps}) failed: {rc}")
+        return taps[:n_taps]
+
+    def fir_block(self, taps: np.ndarray, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig, n_fft: int = 0):
+        """y = h * x per stream and channel by overlap-save at frame size n_fft (0: fir_pick_n_fft(len(taps))); dst receives in_len frames"""
+        taps = np.ascontiguousarray(taps, np.float32)
+        self._ck(self.lib.nae_fir_block_f32(self.h, taps.ctypes.data, taps.size, n_fft, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     # -- graph
     def graph4(self, g: Graph4):
         self._ck(self.lib.nae_graph4_run(self.h, C.byref(g)))
@@ -574,4 +604,38 @@ class Stretcher:
     def close(self) -> None:
         if self.h:
             self.ctx.lib.nae_stretch_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class Fir:
+    """The FIR filter's streaming handle (nae_fir_create): put interleaved f32, flush (the tail: len(taps) - 1 more frames), receive."""
+
+    def __init__(self, ctx: Context, taps: np.ndarray, channels: int, n_fft: int = 0):
+        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+        taps = np.ascontiguousarray(taps, np.float32)
+        ctx._ck(ctx.lib.nae_fir_create(ctx.h, taps.ctypes.data, taps.size, n_fft, channels, C.byref(self.h)))
+
+    def put(self, dev_ptr: int, frames: int) -> None:
+        self.ctx._ck(self.ctx.lib.nae_fir_put(self.h, dev_ptr, frames))
+
+    def put_host(self, x: np.ndarray) -> None:
+        x = np.ascontiguousarray(x, np.float32)
+        self.ctx._ck(self.ctx.lib.nae_fir_put_host(self.h, x.ctypes.data, x.size // self.ch))
+
+    def flush(self) -> None:
+        self.ctx._ck(self.ctx.lib.nae_fir_flush(self.h))
+
+    def available(self) -> int:
+        return self.ctx.lib.nae_fir_available(self.h)
+
+    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
+        n = self.available() if max_frames is None else max_frames
+        out = np.empty(max(n, 1) * self.ch, np.float32)
+        got = C.c_size_t()
+        self.ctx._ck(self.ctx.lib.nae_fir_receive_host(self.h, out.ctypes.data, n, C.byref(got)))
+        return out[: got.value * self.ch]
+
+    def close(self) -> None:
+        if self.h:
+            self.ctx.lib.nae_fir_destroy(self.h)
             self.h = C.c_void_p()

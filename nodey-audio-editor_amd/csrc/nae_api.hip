@@ -267,6 +267,7 @@ int nae_debug_set(nae_ctx* ctx, const char* key, long long value)
     const bool count = value >= 0 && value <= 0x7fffffffll;
     auto one_of = [&](std::initializer_list<long long> ok) { for (long long v : ok) if (v == value) return true; return false; };
     if (k == "pv_tile" && count) ctx->pv_tile = (int)value;
+    else if (k == "fir_tile" && count) ctx->fir_tile = (int)value;
     else if (k == "pv_fps" && one_of({0, 1, 2, 4})) ctx->pv_fps = (int)value;
     else if (k == "pv_flow" && one_of({0, 1, 2})) ctx->pv_flow = (int)value;
     else if (k == "pv_lean" && flag) ctx->pv_lean = value != 0;
@@ -353,6 +354,7 @@ int nae_ctx_destroy(nae_ctx* ctx)
     if (ctx->ws_phase) (void)hipFree(ctx->ws_phase);
     if (ctx->ws_mid) (void)hipFree(ctx->ws_mid);
     nae_wsola_cache_free(ctx);
+    nae_fir_cache_free(ctx);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return NAE_OK;

@@ -32,6 +32,10 @@ struct nae_ctx {
     struct nae_wsola_cache* wsola_cache = nullptr;   // plan + workspaces of nae_wsola_block_f32 (nae_wsola.hip)
     int pv_tile = 0;             // frames per phase-vocoder tile; 0 = choose per call (nae_pick_pv_shape)
     int pv_fps = 0;              // pv_fps = 1|2|4: frames per step of the vocoder pipeline (0 = choose per call)
+    int fir_tile = 0;            // blocks per tile of the FIR filter; 0 = choose per launch (nae_pick_fir_tile)
+    // nae_fir_block_f32 keeps the last call's taps and their spectrum (kernels_fir.hip): [padded taps | H], sized for n_fft = 4096
+    float* d_fir_spec = nullptr; int fir_spec_n_fft = 0;
+    std::vector<float> h_fir_taps;
     // tuning / A-B switches: nae_debug_set(ctx, key, value) (include/nae_gpu.h lists the keys; NAE_DEBUG="key=value,..." applies them at context creation)
     bool dbg_st_unfused = false;     // st_unfused: WSOLA chain runs filter and cubic stage as separate launches
     int dbg_td_nc = 0;               // td_nc = 1|2|4: candidates per thread of the WSOLA search (0: by batch size)
@@ -206,6 +210,18 @@ constexpr int kPhasePad = 520; // int32 per (stream-channel, tile) record in the
 
 // nae_wsola.hip
 void nae_wsola_cache_free(nae_ctx* ctx);
+
+// kernels_fir.hip: the FIR filter ("K9 FIR filter").  nae_fir_check: the parameter rules of the block call and the handle (n_taps < 1
+// or ch not 1 / 2 NAE_ERR_INVALID; a size other than 512 ... 4096 or more than n_fft / 2 + 1 taps NAE_ERR_UNSUPPORTED; *n_fft 0 becomes the pick).
+// A spectrum buffer holds nae_fir_spec_floats(n_fft) floats: the taps zero-padded to n_fft, then H[0 ... n_fft / 2] (nae_fir_make_spec, which
+// waits for the upload of the host taps).  nae_launch_fir runs blocks [b_origin, b_stop) of signals of in_len samples, absolutely indexed.
+int nae_fir_check(nae_ctx* ctx, int n_taps, int ch, int* n_fft);
+size_t nae_fir_spec_floats(int n_fft);
+int nae_fir_make_spec(nae_ctx* ctx, const float* taps_host, int n_taps, int n_fft, float* d_spec);
+int nae_launch_fir(nae_ctx* ctx, int n_fft, const float* d_spec, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
+                   size_t b_origin, size_t b_stop);
+int nae_pick_fir_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc);
+void nae_fir_cache_free(nae_ctx* ctx);
 
 // kernels_nodes.hip
 int nae_launch_copy_sig(nae_ctx* ctx, const nae_sig* src, const nae_sig* dst, size_t S, int ch, size_t n_streams,

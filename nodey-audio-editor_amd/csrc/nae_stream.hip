@@ -38,7 +38,37 @@ struct nae_spectrum {
     size_t out_read = 0;           // frames handed out
 };
 
+// the FIR filter's handle ("K9 FIR filter"): whole blocks of n_fft / 2 samples are filtered as they become available
+struct nae_fir {
+    nae_ctx* ctx;
+    int ch, n_fft, n_taps;
+    float* d_spec = nullptr;       // the padded taps and their spectrum H (nae_fir_make_spec)
+    DevFifo in;                    // interleaved input, from the half block in front of the next block on
+    DevFifo out;                   // interleaved result
+    size_t blocks_done = 0, out_read = 0;
+    bool flushed = false;
+};
+
 namespace {
+
+// the blocks that became computable: every whole block, and after the flush the partial one at the end
+int fir_process(nae_fir* h)
+{
+    nae_ctx* ctx = h->ctx;
+    const size_t B = (size_t)h->n_fft / 2;
+    const size_t blocks = h->flushed ? (h->in.total + B - 1) / B : h->in.total / B;
+    if (blocks <= h->blocks_done) return NAE_OK;
+    const size_t produced = h->flushed ? h->in.total : blocks * B;
+    int rc = h->out.reserve(ctx, produced);
+    if (rc) return rc;
+    const nae_sig src = h->in.view(), dst = h->out.view();
+    rc = nae_launch_fir(ctx, h->n_fft, h->d_spec, &src, h->in.total, h->ch, 1, &dst, h->blocks_done, blocks);
+    if (rc) return rc;
+    h->out.total = produced;
+    h->blocks_done = blocks;
+    h->in.drop((long long)((blocks - 1) * B));       // the next block's first half
+    return NAE_OK;
+}
 
 inline long long frame_start_host(const nae_stretch_plan& pl, int n_fft, long long f)
 {
@@ -396,6 +426,97 @@ int nae_spectrum_destroy(nae_spectrum* h)
     (void)hipStreamSynchronize(h->ctx->stream);
     h->pending.free();
     h->out.free();
+    delete h;
+    return NAE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ FIR filter
+int nae_fir_create(nae_ctx* ctx, const float* taps_host, int n_taps, int n_fft, int channels, nae_fir** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    if (!taps_host) return nae_fail(ctx, NAE_ERR_INVALID, "fir: null pointer");
+    int rc = nae_fir_check(ctx, n_taps, channels, &n_fft);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_fir* s = new (std::nothrow) nae_fir();
+    if (!s) return NAE_ERR_NOMEM;
+    s->ctx = ctx;
+    s->ch = channels;
+    s->n_fft = n_fft;
+    s->n_taps = n_taps;
+    s->in.width = s->out.width = (size_t)channels;
+    if (hipMalloc((void**)&s->d_spec, nae_fir_spec_floats(n_fft) * sizeof(float)) != hipSuccess) {
+        delete s;
+        return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(fir spectrum)");
+    }
+    if ((rc = nae_fir_make_spec(ctx, taps_host, n_taps, n_fft, s->d_spec))) {
+        (void)hipFree(s->d_spec);
+        delete s;
+        return rc;
+    }
+    *h = s;
+    return NAE_OK;
+}
+
+static int fir_append(nae_fir* h, const float* p, size_t S, bool host)
+{
+    if (!h || (S && !p)) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (h->flushed) return nae_fail(h->ctx, NAE_ERR_STATE, "put after flush");
+    if (S == 0) return NAE_OK;
+    const int rc = h->in.push(h->ctx, p, S, host);
+    return rc ? rc : fir_process(h);
+}
+
+int nae_fir_put(nae_fir* h, const float* interleaved, size_t S) { return fir_append(h, interleaved, S, false); }
+int nae_fir_put_host(nae_fir* h, const float* interleaved_host, size_t S) { return fir_append(h, interleaved_host, S, true); }
+
+// n_taps - 1 zero frames behind the input: the tail of the convolution comes out, in_len + n_taps - 1 frames over the handle's life
+int nae_fir_flush(nae_fir* h)
+{
+    if (!h) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (h->flushed) return NAE_OK;
+    const size_t tail = (size_t)h->n_taps - 1;
+    if (tail) {
+        const int rc = h->in.reserve(h->ctx, h->in.total + tail);
+        if (rc) return rc;
+        const hipError_t e = hipMemsetAsync(h->in.at(h->in.total), 0, tail * h->in.width * sizeof(float), h->ctx->stream);
+        if (e != hipSuccess) return nae_check(h->ctx, e, "hipMemsetAsync(fir flush)");
+        h->in.total += tail;
+    }
+    h->flushed = true;
+    return fir_process(h);
+}
+
+size_t nae_fir_available(nae_fir* h) { return h ? h->out.total - h->out_read : 0; }
+
+static int fir_take(nae_fir* h, float* dst, size_t max_frames, size_t* got, bool host)
+{
+    if (!h || !got || (max_frames && !dst)) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    size_t n = h->out.total - h->out_read;
+    if (n > max_frames) n = max_frames;
+    *got = n;
+    if (n == 0) return NAE_OK;
+    const int rc = h->out.pop(h->ctx, h->out_read, dst, n, host);
+    if (rc) return rc;
+    h->out_read += n;
+    return NAE_OK;
+}
+
+int nae_fir_receive(nae_fir* h, float* dst, size_t max_frames, size_t* got) { return fir_take(h, dst, max_frames, got, false); }
+int nae_fir_receive_host(nae_fir* h, float* dst_host, size_t max_frames, size_t* got) { return fir_take(h, dst_host, max_frames, got, true); }
+
+int nae_fir_destroy(nae_fir* h)
+{
+    if (!h) return NAE_OK;
+    (void)nae_use_device(h->ctx);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    h->in.free();
+    h->out.free();
+    if (h->d_spec) (void)hipFree(h->d_spec);
     delete h;
     return NAE_OK;
 }

@@ -145,4 +145,6 @@ namespace infra
 {
 	// same, choosing what velocity_modifier / pitch_modifier nodes WITHOUT an "algorithm" key run (processor/audio-velocity.hpp)
 	void register_all_processors(processor::Stretch_algorithm default_algorithm);
+	// the nodes the reference has no class for (audio_filter): called after register_all_processors(), which stays the reference's list
+	void register_extension_processors();
 }

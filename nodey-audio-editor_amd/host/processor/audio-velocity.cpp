@@ -1,10 +1,12 @@
 #include "audio-velocity.hpp"
+#include "audio-filter.hpp"
 #include "gpu-context.hpp"
 #include "velocity-cadence.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <deque>
 
 namespace processor
 {
@@ -648,6 +650,206 @@ namespace processor
 				for (auto& stream : output_stream)
 					while (!stop_token && stream->try_push(out) != channel_op_status::success) nae_fiber::this_fiber::yield();
 			}
+		}
+		for (auto& stream : output_stream) stream->set_eof();
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_filter
+	namespace
+	{
+		const char* const kind_names[] = {"lowpass", "highpass", "bandpass", "bandstop"};
+	}
+
+	infra::Processor::Info Audio_filter::get_processor_info()
+	{
+		return {"audio_filter", "Audio Filter", false, [] { return std::unique_ptr<infra::Processor>(new Audio_filter); },
+				"Linear-phase FIR low-pass / high-pass / band-pass / band-stop by FFT fast convolution (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_filter::get_pin_attributes() const
+	{
+		return {
+			{"output", "Output", typeid(Audio_stream), false, [] { return std::make_shared<Audio_stream>(); }},
+			{"input", "Input", typeid(Audio_stream), true, [] { return std::make_shared<Audio_stream>(); }}
+		};
+	}
+
+	Json::Value Audio_filter::serialize() const
+	{
+		Json::Value value;
+		if (kind != Kind::Lowpass) value["kind"] = kind_names[(int)kind];
+		if (f_lo != default_f_lo) value["f_lo"] = f_lo;
+		if (f_hi != default_f_hi) value["f_hi"] = f_hi;
+		if (taps != default_taps) value["taps"] = taps;
+		if (fft_size != 0) value["fft_size"] = fft_size;
+		return value;
+	}
+
+	void Audio_filter::deserialize(const Json::Value& value)
+	{
+		const auto wrong = [](const char* field) {
+			return Runtime_error(
+				"Failed to deserialize JSON file",
+				"Audio_filter failed to serialize the JSON input because of missing or invalid fields.",
+				std::string("Wrong field: ") + field
+			);
+		};
+		// everything is read and checked first: a rejected value leaves the node as it was
+		Kind k = Kind::Lowpass;
+		if (value.isMember("kind"))
+		{
+			int found = -1;
+			if (value["kind"].isString())
+				for (int i = 0; i < 4; i++)
+					if (value["kind"].asString() == kind_names[i]) found = i;
+			if (found < 0) throw wrong("kind");
+			k = (Kind)found;
+		}
+		const auto hertz = [&](const char* key, float fallback) {
+			if (!value.isMember(key)) return fallback;
+			if (!value[key].isDouble() || !(value[key].asDouble() > 0.0 && value[key].asDouble() < 1e9)) throw wrong(key);
+			return value[key].asFloat();
+		};
+		const float lo = hertz("f_lo", default_f_lo), hi = hertz("f_hi", default_f_hi);
+		const auto integer = [&](const char* key, int fallback) {
+			if (!value.isMember(key)) return fallback;
+			const Json::Value& v = value[key];
+			// compared as a double with the range first: a number outside int's range is never converted
+			if (!v.isDouble() || !(v.asDouble() >= 1.0 && v.asDouble() <= 4096.0) || v.asDouble() != (double)v.asInt()) throw wrong(key);
+			return v.asInt();
+		};
+		const int n_taps = integer("taps", default_taps);
+		if (n_taps > max_taps || (n_taps & 1) == 0) throw wrong("taps");
+		const int n_fft = integer("fft_size", 0);
+		if (value.isMember("fft_size") && (nae_fir_pick_n_fft(n_fft / 2 + 1) != n_fft || n_taps > n_fft / 2 + 1)) throw wrong("fft_size");
+		kind = k;
+		f_lo = lo;
+		f_hi = hi;
+		taps = n_taps;
+		fft_size = n_fft;
+	}
+
+	void Audio_filter::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
+		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
+		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
+		if (!input_item.has_value())
+			throw Runtime_error("Audio Filter has no input", "Audio Filter requires an audio stream input to function properly.", "Input item 'input' not found");
+		Audio_stream& input_stream = input_item.value().get();
+		nae_ctx* ctx = gpu::context();
+		nae_fir* fir = nullptr;
+		struct Guard { nae_fir*& h; ~Guard() { if (h) nae_fir_destroy(h); } } guard{fir};
+		gpu::Device_buffer d_raw, d_f32, d_out;
+		gpu::Pinned_buffer h_raw, h_out;
+		int ch = 0;
+		size_t to_discard = (size_t)(taps - 1) / 2;  // the group delay
+		struct Shape { int nb_samples, sample_rate; int64_t pts; decltype(Frame_data::time_base) time_base; };
+		std::deque<Shape> shapes;     // the input frames whose output is still owed
+		std::vector<float> ready;     // filtered samples behind the group delay, interleaved, not yet cut into frames
+		size_t ready_pos = 0;         // frames of `ready` already delivered
+		std::shared_ptr<const Audio_frame> held;  // popped, but with another channel count than the batch in front of it
+
+		// everything the handle has ready comes down behind ONE wait and leaves as frames of the input's sizes
+		const auto deliver = [&]()
+		{
+			const size_t avail = nae_fir_available(fir);
+			if (avail == 0) { gpu::wait(stop_token); return; }
+			float* dev = static_cast<float*>(d_out.reserve(avail * ch * sizeof(float)));
+			float* host = static_cast<float*>(h_out.reserve(avail * ch * sizeof(float)));
+			size_t got = 0;
+			gpu::check(nae_fir_receive(fir, dev, avail, &got), "nae_fir_receive");
+			gpu::check(nae_memcpy_d2h(ctx, host, dev, got * ch * sizeof(float)), "d2h");
+			gpu::wait(stop_token);
+			const size_t skip = std::min(to_discard, got);
+			to_discard -= skip;
+			ready.erase(ready.begin(), ready.begin() + ready_pos * ch);
+			ready_pos = 0;
+			ready.insert(ready.end(), host + skip * ch, host + got * ch);
+			while (!shapes.empty() && !stop_token && ready.size() / ch - ready_pos >= (size_t)shapes.front().nb_samples)
+			{
+				const Shape s = shapes.front();
+				shapes.pop_front();
+				auto out = std::make_shared<Audio_frame>();
+				Frame_data* o = out->data();
+				o->format = AV_SAMPLE_FMT_FLT;
+				o->sample_rate = s.sample_rate;
+				o->nb_samples = s.nb_samples;
+				o->ch_layout.nb_channels = ch;
+				o->time_base = s.time_base;
+				o->pts = s.pts;
+				frame_get_buffer(o, 32);
+				std::memcpy(o->data[0], ready.data() + ready_pos * ch, (size_t)s.nb_samples * ch * sizeof(float));
+				ready_pos += s.nb_samples;
+				for (auto& stream : output_stream)
+					while (!stop_token && stream->try_push(out) != channel_op_status::success) nae_fiber::this_fiber::yield();
+			}
+		};
+
+		while (!stop_token)
+		{
+			// every frame that is already waiting (at most 16) is uploaded and put as one block (the handle's output does not depend on how
+			// its input is cut into puts)
+			constexpr size_t max_batch = 16;
+			std::vector<std::shared_ptr<const Audio_frame>> batch;
+			if (held) batch.push_back(std::move(held));
+			held.reset();
+			bool ended = false;
+			while (batch.size() < max_batch)
+			{
+				const auto pop_result = input_stream.try_pop();
+				if (!pop_result.has_value())
+				{
+					ended = input_stream.eof();
+					break;
+				}
+				if (!batch.empty() && pop_result.value()->data()->ch_layout.nb_channels != batch.front()->data()->ch_layout.nb_channels)
+				{
+					held = pop_result.value();
+					break;
+				}
+				batch.push_back(pop_result.value());
+			}
+			if (batch.empty())
+			{
+				if (!ended)
+				{
+					nae_fiber::this_fiber::yield();
+					continue;
+				}
+				if (fir != nullptr)
+				{
+					// the tail: (L - 1) / 2 of the L - 1 flushed frames complete the frames still owed
+					gpu::check(nae_fir_flush(fir), "nae_fir_flush");
+					deliver();
+				}
+				break;
+			}
+			const Frame_data* frame = batch.front()->data();
+			if (fir == nullptr)
+			{
+				ch = frame->ch_layout.nb_channels;
+				if (ch != 1 && ch != 2) throw Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
+				std::vector<float> h((size_t)taps);
+				if (nae_fir_design((int)kind, frame->sample_rate, f_lo, f_hi, taps, h.data()) != NAE_OK)
+					throw Runtime_error(
+						"Invalid filter frequencies", "The filter's corner frequencies must lie below half of the sample rate, the lower below the upper.",
+						infra::fmt("f_lo %g Hz, f_hi %g Hz at %d Hz", (double)f_lo, (double)f_hi, frame->sample_rate)
+					);
+				gpu::check(nae_fir_create(ctx, h.data(), taps, fft_size, ch, &fir), "nae_fir_create");
+			}
+			else if (frame->ch_layout.nb_channels != ch)
+				throw Runtime_error("Channel count changed", "The filter runs one stream of a fixed channel count.",
+									infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, ch));
+			for (const auto& f : batch) shapes.push_back({f->data()->nb_samples, f->data()->sample_rate, f->data()->pts, f->data()->time_base});
+			size_t total = 0;
+			float* samples = upload_as_f32(batch, h_raw, d_raw, d_f32, &total);
+			gpu::check(nae_fir_put(fir, samples, total), "nae_fir_put");
+			deliver();
 		}
 		for (auto& stream : output_stream) stream->set_eof();
 	}

@@ -13,6 +13,7 @@
 // would run with.  Every body returns what the reference returns when nothing changed: false (true = "pins changed", audio-amix.cpp:344-348).
 #include <algorithm>
 
+#include "audio-filter.hpp"
 #include "audio-mix.hpp"
 #include "audio-velocity.hpp"
 #include "audio-vol.hpp"
@@ -62,4 +63,16 @@ namespace processor
 
 	void Audio_spectrum::draw_title() {}
 	bool Audio_spectrum::draw_content(bool) { return false; }
+
+	void Audio_filter::draw_title() {}
+	bool Audio_filter::draw_content(bool)
+	{
+		// what the widgets would keep: an odd tap count in range, corners in order, and a frame size the taps fit (else the library's pick)
+		taps = std::clamp(taps, 1, max_taps) | 1;
+		f_lo = std::max(f_lo, 1.0f);
+		f_hi = std::max(f_hi, 1.0f);
+		if ((kind == Kind::Bandpass || kind == Kind::Bandstop) && f_lo > f_hi) std::swap(f_lo, f_hi);
+		if (fft_size != 0 && taps > fft_size / 2 + 1) fft_size = 0;
+		return false;
+	}
 }

@@ -1,7 +1,9 @@
 // register.cpp — fills Processor::processor_map with the GPU processors, under the identifiers of the CPU classes
 // they replace (reference list: src/register.cpp:16-23).  audio_input / audio_output are codec and device I/O and
-// stay the reference's own classes; audio_spectrum is new.
+// stay the reference's own classes; audio_spectrum is new.  Nodes the reference has no class for (audio_filter) are registered by a call of
+// their own, register_extension_processors(), so that register_all_processors() stays the mirror of the reference's list.
 #include "infra/processor.hpp"
+#include "processor/audio-filter.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -26,4 +28,7 @@ namespace infra
 
 	// the reference's signature (src/register.cpp:14, called from App::App): the vocoder is this library's default
 	void register_all_processors() { register_all_processors(processor::Stretch_algorithm::Vocoder); }
+
+	// the nodes beyond the reference's list; the editor calls it after register_all_processors()
+	void register_extension_processors() { register_each<processor::Audio_filter>(); }
 }
