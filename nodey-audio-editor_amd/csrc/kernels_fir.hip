@@ -195,7 +195,7 @@ size_t nae_fir_spec_floats(int n_fft) { return (size_t)n_fft + 2 * ((size_t)n_ff
 
 // Blocks per tile of a launch over `blocks` blocks of n_sc stream-channels, in the style of the vocoder's pick_wave_tile: the tiles are cut for one
 // round of the waves a CU holds (Fir<N>::kResident) where the stream-channels alone do not give them, and never shorter than NAE_FIR_MIN_TILE blocks
-// (a tile re-reads half a block at its head: at most 1 / 16 of its input).  fir_tile forces the tile.
+// (a tile re-reads half a block at its head: at most 1 / 16 of its input; a launch of fewer blocks is one tile).  fir_tile forces the tile.
 int nae_pick_fir_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc)
 {
     if (ctx->fir_tile > 0) return ctx->fir_tile;
@@ -204,7 +204,7 @@ int nae_pick_fir_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc)
     const size_t resident = n_fft == 512 ? Fir<512>::kResident : n_fft == 1024 ? Fir<1024>::kResident : n_fft == 2048 ? Fir<2048>::kResident
                                                                                                                        : Fir<4096>::kResident;
     size_t n_tiles = (resident * n_cu + n_sc - 1) / n_sc;
-    const size_t max_tiles = (blocks + NAE_FIR_MIN_TILE - 1) / NAE_FIR_MIN_TILE;
+    const size_t max_tiles = blocks / NAE_FIR_MIN_TILE;    // rounded down: 41 blocks are 5 tiles of 9, not 6 of 7
     if (n_tiles > max_tiles) n_tiles = max_tiles;
     if (n_tiles < 1) n_tiles = 1;
     const size_t tile = (blocks + n_tiles - 1) / n_tiles;

@@ -8,55 +8,13 @@ import pytest
 
 import fir_ref
 import node_harness
+from fir_gpu import CONFIGS, MIN_TILE, WAVES, _bits, _noise, fir_stream, gpu_fir, pick_tile, ref_fir, ref_fir_flushed, statement
 
 pytestmark = pytest.mark.gpu
 
-PAD = 8        # frames behind every destination signal that must stay untouched
-SENTINEL = np.float32(-12345.0)
-# (channels, streams, source layout, destination layout, shared source): interleaved and planar views on both sides, stream_stride = 0
-CONFIGS = ((1, 1, "i", "i", False), (2, 1, "i", "i", False), (1, 3, "p", "p", False), (2, 3, "p", "p", False),
-           (2, 3, "i", "p", False), (2, 1, "p", "i", False), (2, 3, "i", "i", True), (1, 3, "p", "p", True))
-
-
 @pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return fir_ref.build(str(tmp_path_factory.mktemp("ref_fir_gpu")))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def gpu_fir(nae, ctx, taps, n_fft, x, src_layout="i", dst_layout="i", shared=False):
-    """x[streams, n, ch] -> y[streams, n, ch] through nae_fir_block_f32; the frames behind each destination signal are checked untouched"""
-    n_streams, n, ch = x.shape
-    xs = x[:1] if shared else x
-    src_host = xs if src_layout == "i" else xs.transpose(0, 2, 1)
-    d_x = ctx.array(np.ascontiguousarray(src_host, np.float32).reshape(-1))
-    ss = 0 if shared else n * ch
-    src = nae.Sig(d_x.ptr, ss, 1, ch) if src_layout == "i" else nae.Sig(d_x.ptr, ss, n, 1)
-    m = n + PAD
-    d_y = ctx.array(np.full(n_streams * m * ch, SENTINEL, np.float32))
-    dst = nae.Sig(d_y.ptr, m * ch, 1, ch) if dst_layout == "i" else nae.Sig(d_y.ptr, m * ch, m, 1)
-    ctx.fir_block(taps, src, n, ch, n_streams, dst, n_fft)
-    out = d_y.download()
-    d_x.free()
-    d_y.free()
-    out = out.reshape(n_streams, m, ch) if dst_layout == "i" else out.reshape(n_streams, ch, m).transpose(0, 2, 1)
-    assert np.all(out[:, n:, :] == SENTINEL), "wrote behind in_len"
-    return np.ascontiguousarray(out[:, :n, :])
-
-
-def ref_fir(ref, taps, n_fft, x):
-    """the statement on x[streams, n, ch]"""
-    return np.stack([fir_ref.run(ref, taps, n_fft, s.reshape(-1), ch=x.shape[2]).reshape(s.shape) for s in x])
-
-
-def _noise(rng, n_streams, n, ch, shared=False):
-    x = rng.uniform(-1, 1, (n_streams, n, ch)).astype(np.float32)
-    if shared:
-        x[:] = x[0]
-    return x
+def ref():
+    return statement()
 
 
 @pytest.mark.parametrize("n_fft", fir_ref.SIZES)
@@ -112,6 +70,73 @@ def test_every_tiling_gives_the_same_bits(nae, ctx, ref, n_fft):
             assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x, "p", "p")), _bits(own)), tile
     finally:
         ctx.debug_set("fir_tile", 0)
+
+
+@pytest.mark.parametrize("n_fft", fir_ref.SIZES)
+def test_automatic_tiles(nae, ctx, ref, n_fft):
+    """fir_tile = 0 on signals long enough for nae_pick_fir_tile to cut them: block counts on both sides of one, two and several tiles, the last
+    tile ending in a partial block, 1 and 6 stream-channels.  At 256 CUs the rule's first term (a round of resident waves) is at least 128 tiles
+    here, so blocks / MIN_TILE alone decides, as it does for any CU count from 16 on."""
+    B = n_fft // 2
+    rng = np.random.default_rng(n_fft + 2)
+    taps = rng.uniform(-1, 1, B + 1).astype(np.float32)
+    ctx.debug_set("fir_tile", 0)
+    for blocks in (8, 9, 16, 17, 41, 67):
+        for ch, n_streams in ((1, 1), (2, 3)):
+            tile, n_tiles = pick_tile(n_fft, blocks, ch * n_streams)
+            assert tile >= MIN_TILE and (n_tiles > 1) == (blocks >= 16), (blocks, tile, n_tiles)
+            x = _noise(rng, n_streams, blocks * B - 5, ch)
+            got = gpu_fir(nae, ctx, taps, n_fft, x)
+            assert np.array_equal(_bits(got), _bits(ref_fir(ref, taps, n_fft, x))), (blocks, ch, n_streams, tile, n_tiles)
+    assert pick_tile(n_fft, 41, 1) == (9, 5) and pick_tile(n_fft, 67, 6) == (9, 8)
+
+
+@pytest.mark.parametrize("layout", ("i", "p"))
+@pytest.mark.parametrize("n_fft", fir_ref.SIZES)
+def test_a_full_and_a_partial_workgroup(nae, ctx, ref, n_fft, layout):
+    """5 stereo streams are 10 one-tile items against 8, 8, 7 and 3 waves per workgroup: a full workgroup and a partly filled last one at every
+    size; NaN between the source's streams"""
+    B = n_fft // 2
+    assert 10 > WAVES[n_fft] and 10 % WAVES[n_fft]
+    rng = np.random.default_rng(n_fft + 3)
+    taps = rng.uniform(-1, 1, B + 1).astype(np.float32)
+    x = _noise(rng, 5, 2 * B + 3, 2)
+    ctx.debug_set("fir_tile", 0)
+    got = gpu_fir(nae, ctx, taps, n_fft, x, layout, layout, gap=37)
+    assert np.array_equal(_bits(got), _bits(ref_fir(ref, taps, n_fft, x)))
+
+
+@pytest.mark.parametrize("n_fft", fir_ref.SIZES)
+def test_forced_tiles_over_several_workgroups(nae, ctx, ref, n_fft):
+    """7 blocks of 5 stereo streams in tiles of 1, 2, 3 and 100 blocks (more than there are): 70, 40, 30 and 10 items, so tiles of one
+    stream-channel lie in different workgroups and the last workgroup is partly filled"""
+    B = n_fft // 2
+    rng = np.random.default_rng(n_fft + 4)
+    taps = rng.uniform(-1, 1, B + 1).astype(np.float32)
+    x = _noise(rng, 5, 7 * B - 5, 2)
+    want = _bits(ref_fir(ref, taps, n_fft, x))
+    try:
+        for tile in (1, 2, 3, 100):
+            ctx.debug_set("fir_tile", tile)
+            assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x, gap=37)), want), tile
+            assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x, "p", "p", gap=37)), want), tile
+    finally:
+        ctx.debug_set("fir_tile", 0)
+
+
+@pytest.mark.parametrize("n_fft", fir_ref.SIZES)
+def test_unit_stride_at_odd_addresses(nae, ctx, ref, n_fft):
+    """the 8-byte accesses of the unit-stride kernel at 4-byte alignment, loads and stores: mono and planar stereo with both bases one float
+    past an allocation's start and an odd channel stride, so that channels 0 and 1 and streams 0 and 1 start at addresses of both parities"""
+    B = n_fft // 2
+    rng = np.random.default_rng(n_fft + 5)
+    taps = rng.uniform(-1, 1, B + 1).astype(np.float32)
+    n = 3 * B + 7
+    assert n % 2 == 1, "n and n + PAD are the planar channel strides"
+    for ch, layout in ((1, "i"), (1, "p"), (2, "p")):
+        x = _noise(rng, 2, n, ch)
+        got = gpu_fir(nae, ctx, taps, n_fft, x, layout, layout, gap=1, offset=1)
+        assert np.array_equal(_bits(got), _bits(ref_fir(ref, taps, n_fft, x))), (ch, layout)
 
 
 def test_nan_reaches_only_the_blocks_that_read_it(nae, ctx):
@@ -190,6 +215,102 @@ def test_handle_device_put_and_mono(nae, ctx, ref):
     finally:
         h.close()
         d_x.free()
+
+
+@pytest.mark.parametrize("ch", (1, 2))
+@pytest.mark.parametrize("n_fft", fir_ref.SIZES)
+def test_handle_launch_past_block_0_in_several_tiles(nae, ctx, ref, n_fft, ch):
+    """3 blocks and 11 frames, then 9 blocks in one put: the second launch computes blocks 3 ... 11 in tiles of 2, and every tile head reads
+    the half block in front of it through the FIFO's absolutely indexed view (mono: the unit-stride kernel); then the flushed tail"""
+    B = n_fft // 2
+    rng = np.random.default_rng(n_fft + 6 + ch)
+    taps = rng.uniform(-1, 1, B + 1).astype(np.float32)
+    x = _noise(rng, 1, 12 * B + 11, ch)[0]
+    try:
+        ctx.debug_set("fir_tile", 2)
+        got = fir_stream(nae, ctx, taps, n_fft, x, (3 * B + 11, 9 * B))
+    finally:
+        ctx.debug_set("fir_tile", 0)
+    assert np.array_equal(_bits(got), _bits(ref_fir_flushed(ref, taps, n_fft, x)))
+
+
+def test_the_context_keeps_the_right_taps(nae, ctx, ref):
+    """the block call's cache of the last taps and their spectrum: every call of each sequence equals the statement for ITS taps and size"""
+    rng = np.random.default_rng(41)
+    x = _noise(rng, 2, 3 * 256 + 7, 2)
+    a = rng.uniform(-1, 1, 200).astype(np.float32)
+    b = rng.uniform(-1, 1, 200).astype(np.float32)
+
+    def check(taps, n_fft, what):
+        want = ref_fir(ref, taps, n_fft, x)
+        assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x)), _bits(want)), what
+
+    # shorter taps after longer ones at the same size: padded taps left behind by A would show
+    check(a, 512, "A")
+    check(a[:3], 512, "A's first 3 taps after A")
+    # the same taps at another size and back
+    check(a, 512, "A at 512")
+    check(a, 1024, "A at 1024")
+    check(a, 512, "A at 512 again")
+    check(a, 512, "A at 512, a cache hit")
+    # same length, other taps
+    check(b, 512, "B after A")
+    # the caller rewrites its array in place: the library compares values, not the pointer
+    t = a.copy()
+    check(t, 512, "t = A")
+    t[:] = b[::-1]
+    check(t, 512, "t rewritten in place")
+    t[117] = np.float32(0.5)
+    check(t, 512, "one tap of t changed")
+    # a handle created between two block calls computes its own spectrum with the same routine and leaves the context's alone
+    check(a, 1024, "A at 1024 before the handle")
+    h = nae.Fir(ctx, b, 2, 1024)
+    check(a, 1024, "A at 1024 after the handle was created")
+    got = fir_stream(nae, ctx, b, 1024, x[0], (700, 75), handle=h)
+    assert np.array_equal(_bits(got), _bits(ref_fir_flushed(ref, b, 1024, x[0]))), "the handle's output, with B"
+    check(a, 1024, "A at 1024 after the handle ran")
+
+
+FLT_MIN = np.float32(1.17549435e-38)
+
+
+@pytest.mark.parametrize("n_fft", fir_ref.SIZES)
+def test_subnormal_input(nae, ctx, ref, n_fft):
+    """every step an IEEE operation: nothing on the way flushes a subnormal to zero.  The input is subnormal throughout, and so is part of the
+    statement's output (asserted: a condition on the input)"""
+    B = n_fft // 2
+    rng = np.random.default_rng(n_fft + 7)
+    taps = rng.uniform(-1, 1, 5).astype(np.float32)
+    x = rng.uniform(-1e-38, 1e-38, (2, 2 * B + 3, 2)).astype(np.float32)
+    want = ref_fir(ref, taps, n_fft, x)
+    sub = (np.abs(want) < FLT_MIN) & (want != 0)
+    assert sub.sum() > want.size // 4 and np.any(np.abs(want) >= FLT_MIN), "subnormal and normal output words"
+    assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x)), _bits(want))
+
+
+@pytest.mark.parametrize("n_fft", fir_ref.SIZES)
+def test_overflow(nae, ctx, ref, n_fft):
+    """samples near FLT_MAX in blocks 1 and 3 (sums of them overflow on the way) and one Inf in block 5: the non-finite output words are the
+    statement's, every other word is equal bit for bit.  NaN payload and sign are not compared."""
+    B = n_fft // 2
+    rng = np.random.default_rng(n_fft + 8)
+    taps = rng.uniform(-1, 1, 2).astype(np.float32)
+    x = _noise(rng, 1, 8 * B + 3, 2)
+    x[0, B + 5, 0] = 3e38
+    x[0, 3 * B + 9, 0] = 3e38
+    x[0, 3 * B + 10, 0] = -3e38
+    x[0, 3 * B + 40, 1] = 3e38
+    x[0, 3 * B + 41, 1] = 3e38
+    x[0, 5 * B + 1, 1] = np.inf
+    x[0, 7 * B + 2, 0] = 2.4e39 / B                      # the last FFT's sums pass FLT_MAX on the way to a few output words only
+    want = ref_fir(ref, taps, n_fft, x)
+    bad = ~np.isfinite(want)
+    assert np.all(bad[0, B:3 * B, 0]) and np.all(bad[0, 3 * B:5 * B]) and np.all(bad[0, 5 * B:7 * B, 1]), "the whole of these blocks"
+    assert 0 < bad[0, 7 * B:8 * B, 0].sum() < 8, "a few words of this one"
+    assert not bad[0, :B].any() and not bad[0, B:3 * B, 1].any() and not bad[0, 5 * B:7 * B, 0].any() and not bad[0, 7 * B:, 1].any()
+    got = gpu_fir(nae, ctx, taps, n_fft, x)
+    assert np.array_equal(~np.isfinite(got), bad), "the same words are non-finite"
+    assert np.array_equal(_bits(got)[~bad], _bits(want)[~bad])
 
 
 def test_error_codes(nae, ctx):

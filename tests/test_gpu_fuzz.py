@@ -1,5 +1,5 @@
 """GPU: a seeded, bounded subset of the randomised differential runs of tests/tools/fuzz_*.py (vocoder + spectrum, the
-SoundTouch-shaped chain, the N2 converter) against the CPU oracle.  The full runs (python tests/tools/fuzz_X.py CASES SEED)
+SoundTouch-shaped chain, the N2 converter, the FIR filter) against the CPU oracle and statements.  The full runs (python tests/tools/fuzz_X.py CASES SEED)
 draw more cases from the same generators; these fixed seeds keep the driver's `-m gpu` run to a few seconds per test."""
 import os
 import sys
@@ -40,3 +40,8 @@ def test_fuzz_wsola_seeded(nae, ctx):
 def test_fuzz_swr_seeded(nae, ctx):
     import fuzz_swr
     assert fuzz_swr.main(cases=10, seed=3, ctx=ctx, nae=nae) >= 6      # bit-exact for every cut into convert calls
+
+
+def test_fuzz_fir_seeded(nae, ctx):
+    import fuzz_fir
+    assert fuzz_fir.main(cases=36, seed=3, ctx=ctx, nae=nae) == 36     # block call and handle bit-exact in every case drawn

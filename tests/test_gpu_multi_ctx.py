@@ -13,6 +13,7 @@ import pytest
 
 import orc
 from conftest import rel_rms
+from fir_gpu import _noise, gpu_fir, ref_fir, ref_fir_flushed, statement
 
 pytestmark = pytest.mark.gpu
 
@@ -88,6 +89,43 @@ def test_two_contexts_interleaved_bit_exact(nae, ctx):
         b.close()
 
 
+def test_fir_on_two_contexts_interleaved(nae, ctx):
+    """two more contexts with taps and frame sizes of their own: block calls interleaved call by call (each context keeps the spectrum of ITS
+    last taps), then one nae_fir handle on each, fed alternately; every result is the statement's for that context's taps"""
+    ref = statement()
+    rng = np.random.default_rng(51)
+    cs = [nae.Context(0), nae.Context(0)]
+    taps = [rng.uniform(-1, 1, 200).astype(np.float32), rng.uniform(-1, 1, 600).astype(np.float32)]
+    sizes = [512, 2048]
+    hs = []
+    try:
+        for i in range(3):                                  # the second and third round are cache hits on both contexts
+            x = _noise(rng, 2, 9 * 256 + 7 + i, 2)
+            got = [gpu_fir(nae, c, t, n, x) for c, t, n in zip(cs, taps, sizes)]
+            for g, t, n in zip(got, taps, sizes):
+                assert np.array_equal(bits(g), bits(ref_fir(ref, t, n, x))), (i, n)
+        x = _noise(rng, 2, 30000, 2)
+        hs = [nae.Fir(c, t, 2, n) for c, t, n in zip(cs, taps, sizes)]
+        outs = [[], []]
+        for pos in range(0, 30000, 1700):
+            for k, h in enumerate(hs):
+                h.put_host(x[k, pos:pos + 1700].reshape(-1))
+                outs[k].append(h.receive_host())
+        for k, h in enumerate(hs):
+            h.flush()
+            outs[k].append(h.receive_host())
+            want = ref_fir_flushed(ref, taps[k], sizes[k], x[k])
+            assert np.array_equal(bits(np.concatenate(outs[k])), bits(want.reshape(-1))), k
+        # and the block call again behind the handles: still this context's taps
+        for c, t, n in zip(cs, taps, sizes):
+            assert np.array_equal(bits(gpu_fir(nae, c, t, n, x)), bits(ref_fir(ref, t, n, x))), n
+    finally:
+        for h in hs:
+            h.close()
+        for c in cs:
+            c.close()
+
+
 def test_event_query_and_cross_context_dependency(nae):
     a, b = nae.Context(0), nae.Context(0)
     try:
@@ -118,6 +156,11 @@ def test_contexts_driven_from_two_threads(nae):
     context by one thread).  Both threads make their FIRST vocoder call concurrently — the launch attribute that round 3 kept in a
     process-global flag is per context now."""
     results, errors = {}, []
+    ref = statement()
+    rng = np.random.default_rng(61)
+    fir_x = _noise(rng, 3, 5 * 256 + 3, 2)
+    fir_taps = [rng.uniform(-1, 1, 257).astype(np.float32) for _ in range(2)]      # each thread's context filters with its own taps
+    fir_out = {}
 
     def worker(k):
         try:
@@ -125,6 +168,7 @@ def test_contexts_driven_from_two_threads(nae):
             try:
                 for _ in range(3):
                     results[k] = node_results(nae, c, 7)
+                    fir_out[k] = gpu_fir(nae, c, fir_taps[k], 512, fir_x)
             finally:
                 c.close()
         except Exception as e:                                         # noqa: BLE001 — reported by the main thread
@@ -140,6 +184,8 @@ def test_contexts_driven_from_two_threads(nae):
     for u, v in zip(results[0][2], results[1][2]):
         assert np.array_equal(bits(u), bits(v))
     check_against_oracle(*results[0])
+    for k in range(2):
+        assert np.array_equal(bits(fir_out[k]), bits(ref_fir(ref, fir_taps[k], 512, fir_x))), k
 
 
 def test_two_devices_when_the_box_has_them(nae):

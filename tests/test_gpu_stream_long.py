@@ -1,14 +1,16 @@
-"""Long streams through every streaming handle (nae_stretch, nae_wsola, nae_swr, nae_spectrum): 300 000+ frames in an
+"""Long streams through every streaming handle (nae_stretch, nae_wsola, nae_swr, nae_spectrum, nae_fir): 300 000+ frames in an
 uneven cycle of put sizes, with receives that take everything, part of what is available or nothing.  Every device FIFO
-of the handles grows several times and is compacted many times; the output equals the block call or the oracle bit for
-bit."""
+of the handles grows several times and is compacted many times; the output equals the block call, the oracle or the CPU
+statement bit for bit."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import fir_ref
 import orc
 import pv_ref
+from fir_gpu import gpu_fir, statement
 from pv_gpu import block, same_bits
 from test_gpu_spectrum_sizes import bins, gpu_ex
 
@@ -37,7 +39,7 @@ def part(avail, share):
 
 
 def drive(lib, h, prefix, x, ch):
-    """put_host / available / receive_host / flush / receive everything of a nae_stretch or nae_wsola handle"""
+    """put_host / available / receive_host / flush / receive everything of a nae_stretch, nae_wsola or nae_fir handle"""
     put, available, receive = (getattr(lib, f"nae_{prefix}_{f}") for f in ("put_host", "available", "receive_host"))
     outs, got = [], C.c_size_t()
 
@@ -147,5 +149,54 @@ def test_spectrum_long_stream_equals_block(ctx, nae, n_fft, hop):
     assert lib.nae_spectrum_destroy(h) == 0
     assert frames == want.shape[0]
     out = d_o.download()[: want.size].reshape(want.shape)
+    d_x.free(); d_o.free()
+    assert same_bits(out, want)
+
+
+def fir_case(n_fft, n_taps, ch, seed):
+    """taps, 400 000 frames of noise, and the statement on the input extended by n_taps - 1 zero frames"""
+    rng = np.random.default_rng(seed)
+    taps = rng.uniform(-1, 1, n_taps).astype(np.float32)
+    x = orc.fill_uniform(L * ch, seed)
+    want = fir_ref.run(statement(), taps, n_fft, np.concatenate([x, np.zeros((n_taps - 1) * ch, np.float32)]), ch=ch)
+    return taps, x, want
+
+
+@pytest.mark.parametrize("n_fft,n_taps,ch", [(512, 257, 2), (4096, 2049, 1), (1024, 2, 2)])
+def test_fir_long_stream_equals_statement(ctx, nae, n_fft, n_taps, ch):
+    """in_len + n_taps - 1 frames come out: the statement on the zero-extended input, and in its first in_len frames the block call"""
+    taps, x, want = fir_case(n_fft, n_taps, ch, 43)
+    h = C.c_void_p()
+    assert ctx.lib.nae_fir_create(ctx.h, taps.ctypes.data, n_taps, n_fft, ch, C.byref(h)) == 0
+    y = drive(ctx.lib, h, "fir", x, ch)
+    assert y.size == (L + n_taps - 1) * ch
+    assert same_bits(y, want)
+    assert same_bits(y[: L * ch], gpu_fir(nae, ctx, taps, n_fft, x.reshape(1, L, ch)).reshape(-1))
+
+
+def test_fir_long_stream_device_puts_and_receives(ctx, nae):
+    """nae_fir_put / nae_fir_receive: the input FIFO is fed from device memory, and the output FIFO is popped device to device and then
+    compacted in place on the same stream"""
+    lib, n_fft, n_taps, ch = ctx.lib, 512, 257, 2
+    taps, x, want = fir_case(n_fft, n_taps, ch, 47)
+    h, got = C.c_void_p(), C.c_size_t()
+    assert lib.nae_fir_create(ctx.h, taps.ctypes.data, n_taps, n_fft, ch, C.byref(h)) == 0
+    d_x, d_o = ctx.array(x), ctx.empty(want.size + ch)
+    frames = 0
+    for pos, n, share in schedule(L):
+        assert lib.nae_fir_put(h, C.c_void_p(d_x.at(pos * ch)), n) == 0
+        take = part(lib.nae_fir_available(h), share)
+        assert lib.nae_fir_receive(h, C.c_void_p(d_o.at(frames * ch)), take, C.byref(got)) == 0
+        assert got.value == take
+        frames += take
+    assert lib.nae_fir_flush(h) == 0
+    assert lib.nae_fir_put(h, C.c_void_p(d_x.ptr), 1) == -5                # NAE_ERR_STATE: put after flush
+    rest = lib.nae_fir_available(h)
+    assert lib.nae_fir_receive(h, C.c_void_p(d_o.at(frames * ch)), rest, C.byref(got)) == 0
+    frames += got.value
+    assert lib.nae_fir_available(h) == 0
+    assert lib.nae_fir_destroy(h) == 0
+    assert frames == L + n_taps - 1
+    out = d_o.download()[: want.size]
     d_x.free(); d_o.free()
     assert same_bits(out, want)
