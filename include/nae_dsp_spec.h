@@ -28,6 +28,11 @@
 #define NAE_FIR_MAX_TAPS 2049
 #define NAE_FIR_KAISER_BETA 8.0
 #define NAE_FIR_MIN_TILE 8
+/* K10 long convolution ("K10 long convolution"): uniformly partitioned overlap-save, P = ceil(L / (N / 2)) partitions at frame size
+ * N = 512 ... 4096; nae_conv_pick_n_fft takes the smallest N with at most NAE_CONV_PICK_PARTS partitions (a rule, not a measurement), else 4096 */
+#define NAE_CONV_MAX_TAPS 262144
+#define NAE_CONV_MAX_PARTS 512
+#define NAE_CONV_PICK_PARTS 16
 /* transient preservation ("Transient preservation"): bin k of frame f rises iff P_f[k] > RISE * P_{f-1}[k] and
  * P_f[k] > FLOOR * N; frame f is "high" iff DEN * (rising bins) >= NUM * (N/2 + 1); an onset is an upward crossing of "high" at f >= 2.
  * RISE is +6 dB: at +3 dB steady white noise crosses 3/8 at N = 512 and 1024 (DESIGN.md gives the numbers). */

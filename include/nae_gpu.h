@@ -42,7 +42,8 @@ extern "C" {
  *   nae_stretch_create_formant_shift (formant shift independent of the pitch); NAE_STRETCH_LINK_CHANNELS with the _n, _formant and
  *   _formant_shift entries (one onset decision and one phase-lock region map per stereo stream), probed by return code as
  *   NAE_STRETCH_TRANSIENTS is; nae_fir_pick_n_fft, nae_fir_block_f32, nae_fir_design and the nae_fir handle (nae_fir_create, _put, _put_host, _flush,
- *   _available, _receive, _receive_host, _destroy): the FIR filter, K9. */
+ *   _available, _receive, _receive_host, _destroy): the FIR filter, K9; nae_conv_pick_n_fft, nae_conv_block_f32, nae_conv_reverb_taps,
+ *   nae_conv_design_reverb and the nae_conv handle (the same eight entries): the long convolution, K10. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -65,6 +66,7 @@ typedef struct nae_event nae_event;
 typedef struct nae_stretch nae_stretch;
 typedef struct nae_spectrum nae_spectrum;
 typedef struct nae_fir nae_fir;
+typedef struct nae_conv nae_conv;
 
 /* ------------------------------------------------------------------ context / plumbing */
 int nae_abi_version(void);
@@ -143,6 +145,9 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *                   for bit; samples within the tolerance); the tile is pv_tile, else one of at least pv_min_ptile frames (default 64)
  *   td_nc           1 | 2 | 4: candidates per thread of the WSOLA search;  st_unfused  1: filter and cubic stage of the WSOLA chain as two launches
  *   fir_tile        blocks (of n_fft / 2 samples) one wave of the FIR filter walks; every tiling gives the same bits
+ *   conv_tile       blocks one wave of the long convolution's accumulate kernel walks (0: the register tile, nae_pick_conv_tile)
+ *   conv_ring       spectrum slots per stream-channel of the long convolution's workspace ring (0: from the workspace cap; at least the
+ *                   partition count is used); a handle reads it when it is created.  Neither changes a result
  * The same assignments, comma separated, in the environment variable NAE_DEBUG ("pv_flow=2,pv_fps=4") are applied when a context is created
  * (for measuring a program that creates its contexts itself, e.g. bench.py); an unknown key there fails nae_ctx_create with NAE_ERR_INVALID. */
 int nae_debug_set(nae_ctx* ctx, const char* key, long long value);
@@ -475,6 +480,44 @@ int nae_fir_destroy(nae_fir* h);
  * The frequencies a kind uses lie in (0, sample_rate / 2), f_lo < f_hi for kinds 2 and 3; the other one is ignored.  Anything else — another
  * kind, an even or non-positive n_taps, sample_rate <= 0, a null pointer — is NAE_ERR_INVALID.  No context, no device work. */
 int nae_fir_design(int kind, int sample_rate, double f_lo, double f_hi, int n_taps, float* taps_host);
+
+/* ------------------------------------------------------------------ K10 long convolution
+ * no reference code.  Spec ("K10 long convolution"): taps h_c[0 ... L-1] in f32, 1 <= L <= NAE_CONV_MAX_TAPS, laid out
+ * [taps_ch][L] on the host: taps_ch = 1, one set for every channel, or taps_ch = ch, one per channel; one set (or pair) for every stream.  The
+ * result is the causal convolution y[n] = sum_{j < L} h_c[j] x[n - j], 0 <= n < in_len, x = 0 before the signal, by uniformly partitioned
+ * overlap-save at N = n_fft = 512 ... 4096, M = B = N / 2, P = ceil(L / B) <= NAE_CONV_MAX_PARTS partitions, every step an IEEE operation in a
+ * fixed order:
+ *   1  H_{c,p} = r2c_N(h_c[p B ... p B + B - 1] zero-padded to N), p < P (on the device, K9's routine);
+ *   2  U_b = r2c_N(u_b), u_b[n] = x[b B - B + n] (K9 step 2);
+ *   3  Y_b[k] = sum_{p = 0}^{min(b, P-1)} U_{b-p}[k] H_{c,p}[k], every product in K9's form, summed in increasing p from the p = 0 product by
+ *      one add per component and term;
+ *   4  v = c2r_N(Y_b);   5  y[b B + n] = v[B + n], n < B, wherever b B + n < in_len (K9 steps 4 and 5).
+ * Bit-exact against the CPU statement (tests/conv_ref/ref_conv.c), independent of every tiling, slab and ring size; with L <= B the bits of
+ * nae_fir_block_f32 at the same N.  A non-finite input sample i changes only blocks floor(i / B) ... floor(i / B) + P.  n_fft = 0 means
+ * nae_conv_pick_n_fft(n_taps): the smallest N with at most 16 partitions, else 4096; 0 when n_taps < 1, > NAE_CONV_MAX_TAPS or P > NAE_CONV_MAX_PARTS.
+ * Errors: a null pointer, n_taps < 1, ch not 1 or 2, taps_ch not 1 or ch: NAE_ERR_INVALID; more than NAE_CONV_MAX_TAPS taps, an unsupported
+ * n_fft or more than NAE_CONV_MAX_PARTS partitions: NAE_ERR_UNSUPPORTED; in_len = 0 or n_streams = 0: NAE_OK after the checks.  Views as K9's.
+ * The context keeps the taps and H of its last block call, apart from the FIR filter's. */
+int nae_conv_pick_n_fft(int n_taps);
+int nae_conv_block_f32(nae_ctx* ctx, const float* taps_host, int n_taps, int taps_ch, int n_fft, const nae_sig* src, size_t in_len, int ch,
+                       size_t n_streams, const nae_sig* dst);
+/* Streaming handle, nae_fir's in every respect (channels = ch): the first in_len frames equal the block call's however the input is cut;
+ * nae_conv_flush appends n_taps - 1 zero frames, so in_len + n_taps - 1 frames come out.  A put after the flush: NAE_ERR_STATE. */
+int nae_conv_create(nae_ctx* ctx, const float* taps_host, int n_taps, int taps_ch, int n_fft, int channels, nae_conv** h);
+int nae_conv_put(nae_conv* h, const float* interleaved, size_t S);
+int nae_conv_put_host(nae_conv* h, const float* interleaved_host, size_t S);
+int nae_conv_flush(nae_conv* h);
+size_t nae_conv_available(nae_conv* h);
+int nae_conv_receive(nae_conv* h, float* dst, size_t max_frames, size_t* got);
+int nae_conv_receive_host(nae_conv* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_conv_destroy(nae_conv* h);
+/* A synthetic room response on the host, in double, rounded once to f32: d = round(predelay_s sample_rate) silent taps, then noise
+ * g[n] = 2 u - 1, u = (z >> 11) 2^-53, z = splitmix64's output function of seed + (n + 1) 0x9E3779B97F4A7C15, under the envelope
+ * exp(-ln(1000) (n - d) / (rt60_s sample_rate)); r = e / sqrt(sum e^2) (summed in increasing n: unit energy), h[n] = wet r[n] + dry delta[n].
+ * nae_conv_reverb_taps gives the length to the -60 dB point, d + ceil(rt60_s sample_rate).  NAE_ERR_INVALID: sample_rate <= 0, rt60_s outside
+ * (0, 10], predelay_s outside [0, 1], dry or wet not finite, n_taps < d + 1, a null pointer.  No context, no device work. */
+int nae_conv_reverb_taps(int sample_rate, double rt60_s, double predelay_s);
+int nae_conv_design_reverb(int sample_rate, double rt60_s, double predelay_s, double dry, double wet, uint64_t seed, int n_taps, float* taps_host);
 
 /* ------------------------------------------------------------------ the 4-node graph of BASELINE.json
  * input -> mix(2) -> pitch -> FFT spectrum, one launch sequence over n_streams independent streams.

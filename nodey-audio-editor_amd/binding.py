@@ -36,6 +36,8 @@ EXPORTED_SYMBOLS = [
     "nae_wsola_flush", "nae_wsola_available", "nae_wsola_receive", "nae_wsola_receive_host", "nae_wsola_destroy",
     "nae_fir_pick_n_fft", "nae_fir_block_f32", "nae_fir_design", "nae_fir_create", "nae_fir_put", "nae_fir_put_host", "nae_fir_flush",
     "nae_fir_available", "nae_fir_receive", "nae_fir_receive_host", "nae_fir_destroy",
+    "nae_conv_pick_n_fft", "nae_conv_block_f32", "nae_conv_reverb_taps", "nae_conv_design_reverb", "nae_conv_create", "nae_conv_put",
+    "nae_conv_put_host", "nae_conv_flush", "nae_conv_available", "nae_conv_receive", "nae_conv_receive_host", "nae_conv_destroy",
 ]
 
 
@@ -187,6 +189,12 @@ def load_library() -> C.CDLL:
         "nae_fir_put": (i, [vp, vp, sz]), "nae_fir_put_host": (i, [vp, vp, sz]), "nae_fir_flush": (i, [vp]),
         "nae_fir_available": (sz, [vp]), "nae_fir_receive": (i, [vp, vp, sz, P(sz)]),
         "nae_fir_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_fir_destroy": (i, [vp]),
+        "nae_conv_pick_n_fft": (i, [i]), "nae_conv_block_f32": (i, [vp, vp, i, i, i, P(Sig), sz, i, sz, P(Sig)]),
+        "nae_conv_reverb_taps": (i, [i, d, d]), "nae_conv_design_reverb": (i, [i, d, d, d, d, C.c_uint64, i, vp]),
+        "nae_conv_create": (i, [vp, vp, i, i, i, i, P(vp)]),
+        "nae_conv_put": (i, [vp, vp, sz]), "nae_conv_put_host": (i, [vp, vp, sz]), "nae_conv_flush": (i, [vp]),
+        "nae_conv_available": (sz, [vp]), "nae_conv_receive": (i, [vp, vp, sz, P(sz)]),
+        "nae_conv_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_conv_destroy": (i, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -547,6 +555,39 @@ class Context:
         taps = np.ascontiguousarray(taps, np.float32)
         self._ck(self.lib.nae_fir_block_f32(self.h, taps.ctypes.data, taps.size, n_fft, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K10
+    @staticmethod
+    def conv_pick_n_fft(n_taps: int) -> int:
+        """the smallest frame size with at most 16 partitions of n_fft / 2 taps, else 4096; 0 when the response is not supported"""
+        return int(load_library().nae_conv_pick_n_fft(n_taps))
+
+    @staticmethod
+    def conv_reverb_taps(sample_rate: int, rt60_s: float, predelay_s: float) -> int:
+        """length of a designed response to its -60 dB point (nae_conv_reverb_taps)"""
+        n = int(load_library().nae_conv_reverb_taps(sample_rate, rt60_s, predelay_s))
+        if n < 0:
+            raise NaeError(f"nae_conv_reverb_taps({sample_rate}, {rt60_s}, {predelay_s}) failed: {n}")
+        return n
+
+    @staticmethod
+    def conv_design_reverb(sample_rate: int, rt60_s: float, predelay_s: float, dry: float, wet: float, seed: int,
+                           n_taps: Optional[int] = None) -> np.ndarray:
+        """exponentially decaying noise of unit energy behind the pre-delay, h = wet r + dry delta (nae_conv_design_reverb)"""
+        lib = load_library()
+        if n_taps is None:
+            n_taps = Context.conv_reverb_taps(sample_rate, rt60_s, predelay_s)
+        taps = np.empty(max(n_taps, 1), np.float32)
+        rc = lib.nae_conv_design_reverb(sample_rate, rt60_s, predelay_s, dry, wet, seed, n_taps, taps.ctypes.data)
+        if rc:
+            raise NaeError(f"nae_conv_design_reverb({sample_rate}, {rt60_s}, {predelay_s}, {dry}, {wet}, {seed}, {n_taps}) failed: {rc}")
+        return taps[:n_taps]
+
+    def conv_block(self, taps: np.ndarray, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig, n_fft: int = 0):
+        """y = h_c * x per stream and channel by partitioned overlap-save; taps [L] (one set) or [taps_ch][L]; dst receives in_len frames"""
+        taps = np.ascontiguousarray(taps, np.float32)
+        taps_ch, n_taps = (1, taps.size) if taps.ndim == 1 else taps.shape
+        self._ck(self.lib.nae_conv_block_f32(self.h, taps.ctypes.data, n_taps, taps_ch, n_fft, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     # -- graph
     def graph4(self, g: Graph4):
         self._ck(self.lib.nae_graph4_run(self.h, C.byref(g)))
@@ -639,3 +680,50 @@ class Fir:
         if self.h:
             self.ctx.lib.nae_fir_destroy(self.h)
             self.h = C.c_void_p()
+
+
+class Conv:
+    """The long convolution's streaming handle (nae_conv_create): put interleaved f32, flush (the tail: n_taps - 1 more frames), receive.
+    taps [L] (one set for every channel) or [channels][L]."""
+
+    def __init__(self, ctx: Context, taps: np.ndarray, channels: int, n_fft: int = 0):
+        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+        taps = np.ascontiguousarray(taps, np.float32)
+        taps_ch, n_taps = (1, taps.size) if taps.ndim == 1 else taps.shape
+        ctx._ck(ctx.lib.nae_conv_create(ctx.h, taps.ctypes.data, n_taps, taps_ch, n_fft, channels, C.byref(self.h)))
+
+    def put(self, dev_ptr: int, frames: int) -> None:
+        self.ctx._ck(self.ctx.lib.nae_conv_put(self.h, dev_ptr, frames))
+
+    def put_host(self, x: np.ndarray) -> None:
+        x = np.ascontiguousarray(x, np.float32)
+        self.ctx._ck(self.ctx.lib.nae_conv_put_host(self.h, x.ctypes.data, x.size // self.ch))
+
+    def flush(self) -> None:
+        self.ctx._ck(self.ctx.lib.nae_conv_flush(self.h))
+
+    def available(self) -> int:
+        return self.ctx.lib.nae_conv_available(self.h)
+
+    def receive(self, dev_ptr: int, max_frames: int) -> int:
+        got = C.c_size_t()
+        self.ctx._ck(self.ctx.lib.nae_conv_receive(self.h, dev_ptr, max_frames, C.byref(got)))
+        return got.value
+
+    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
+        n = self.available() if max_frames is None else max_frames
+        out = np.empty(max(n, 1) * self.ch, np.float32)
+        got = C.c_size_t()
+        self.ctx._ck(self.ctx.lib.nae_conv_receive_host(self.h, out.ctypes.data, n, C.byref(got)))
+        return out[: got.value * self.ch]
+
+    def close(self) -> None:
+        if self.h:
+            self.ctx.lib.nae_conv_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

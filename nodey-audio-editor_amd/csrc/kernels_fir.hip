@@ -7,30 +7,14 @@
 // carry[m - M/2] of its own lane — as the next block's first half, so every input sample is read once per tile plus one half block at the tile
 // head.  H = r2c_N(h zero-padded) comes from fir_taps_kernel, the same first pass, radix passes and split on one wave; the blocks read it from
 // global memory (16 KiB at 4096, shared by every wave of the launch: it stays in the vector L1 / L2).  Blocks do not depend on each other beyond
-// the samples they share, so every tiling and the streaming handle give the same bits.
-#include "pv_any.h"
+// the samples they share, so every tiling and the streaming handle give the same bits.  The geometry, the tile head and the r2c of a block live in
+// fir_block.h, which the long convolution (kernels_conv.hip) shares.
+#include "fir_block.h"
 #include <string.h>
 #include <math.h>
 #include <new>
 
 namespace nae {
-
-template <int N>
-struct Fir {
-    static constexpr int M = N / 2, B = N / 2, BINS = M + 1;
-    static constexpr int PAD = (BINS + 7) & ~7;           // complex per spectrum Y of a wave
-    static constexpr int NB = M / 64 + 1;                 // bins per lane: k = lane + 64 r; r = NB - 1 is bin M (lane 0)
-    static constexpr int KP = M / 128;                    // packed points per lane in a half block: m = lane + 64 j
-    using Gm = FftGeom<M, 1>;
-    static constexpr size_t kWave = (Gm::SCR + PAD + M / 2) * sizeof(cf);   // scratch, Y, the carried half block
-    static constexpr int kMaxWaves = (int)((160 * 1024 - 512 * sizeof(cf)) / kWave);
-    static constexpr int kWaves = kMaxWaves < 8 ? kMaxWaves : 8;           // 8, 8, 7, 3 waves per workgroup at N = 512 ... 4096 (PvEnv<N>'s)
-    // waves a CU holds: whole workgroups by LDS (24, 8, 7, 3), and no more than the registers hold — `make resources`: 79 / 84 VGPRs at 512 (unit /
-    // any stride: six / five waves per SIMD, so two workgroups always fit and a third only sometimes), 108 ... 251 above: 16, 8, 7, 3
-    static constexpr int kLdsResident = (int)((160 * 1024) / (512 * sizeof(cf) + kWaves * kWave)) * kWaves;
-    static constexpr int kResident = kLdsResident < 16 ? kLdsResident : 16;
-    static_assert(kWaves >= 1, "a wave's state fits a CU's LDS");
-};
 
 struct FirParams {
     long long in_len;      // samples of a stream-channel: reads outside [0, in_len) give zero, samples >= in_len are not stored
@@ -39,20 +23,6 @@ struct FirParams {
     long long n_items;     // (stream-channel, tile) pairs
     int tile, n_tiles, ch;
 };
-
-// packed point (x[i0], x[i0 + 1]) of one stream-channel; `inside`: both lie in [0, len) (wave-uniform)
-template <bool kUnit>
-__device__ __forceinline__ cf fir_load_pair(const float* p, long long fs, long long len, long long i0, bool inside)
-{
-    if (inside) {
-        if (kUnit) {
-            const f2u x = *reinterpret_cast<const f2u*>(p + i0);
-            return cf{x.x, x.y};
-        }
-        return cf{p[i0 * fs], p[(i0 + 1) * fs]};
-    }
-    return cf{(i0 >= 0 && i0 < len) ? p[i0 * fs] : 0.0f, (i0 + 1 >= 0 && i0 + 1 < len) ? p[(i0 + 1) * fs] : 0.0f};
-}
 
 template <int N, bool kUnit>
 __global__ __launch_bounds__(64 * (Fir<N>::kWaves)) void fir_block_kernel(SigViewD src, OutViewD out, FirParams p, const cf* __restrict__ hspec,
@@ -82,27 +52,12 @@ __global__ __launch_bounds__(64 * (Fir<N>::kWaves)) void fir_block_kernel(SigVie
     const long long b0 = p.b_origin + (long long)tile * p.tile;
     const long long b_end = b0 + p.tile < p.b_stop ? b0 + p.tile : p.b_stop;
 
-    // tile head: the half block in front of block b0 (zero in front of the signal; inside it otherwise: block b0 exists, so b0 B < in_len)
-#pragma unroll
-    for (int j = 0; j < F::KP; j++) {
-        const int m = lane + 64 * j;
-        lds_st(cw + m, b0 > 0 ? fir_load_pair<kUnit>(ip, src.fs, p.in_len, (b0 - 1) * B + 2 * m, true) : cf{0.0f, 0.0f});
-    }
+    fir_tile_head<N, kUnit>(cw, ip, src.fs, p.in_len, b0, lane);
 #pragma unroll 1
     for (long long b = b0; b < b_end; b++) {
         const long long n0 = b * B;
         const bool full = n0 + B <= p.in_len;              // wave-uniform
-        // U = r2c_N(u).  Point m of the first half comes from the carry; point m of the second half is read from memory and replaces carry[m - M/2].
-        // A butterfly row asks for m = l + S j in increasing j, so the lane that reads carry[m - M/2] (j < R1 / 2) is the one that overwrites it
-        // afterwards (j >= R1 / 2): the LDS accesses are volatile and stay in that order.
-        any_first_pass_from<Gm>(scr, w512l, tb.wm, lane, [&](int m) -> cf {
-            if (m < M / 2) return lds_ld(cw + m);
-            const cf x = fir_load_pair<kUnit>(ip, src.fs, p.in_len, n0 + 2 * (m - M / 2), full);
-            lds_st(cw + (m - M / 2), x);
-            return x;
-        });
-        any_passes8<Gm, (Gm::M / Gm::R1)>(scr, w512l, lane);
-        wave_lds_sync();
+        fir_block_r2c<N, kUnit>(scr, cw, w512l, tb, ip, src.fs, p.in_len, n0, full, lane);       // U = r2c_N(u), the carry moves on
         // Y = U H: four products, one subtract, one add (-ffp-contract=off: nothing fuses)
 #pragma unroll 2
         for (int r = 0; r < F::NB; r++) {
@@ -114,6 +69,9 @@ __global__ __launch_bounds__(64 * (Fir<N>::kWaves)) void fir_block_kernel(SigVie
             }
         }
         wave_lds_sync();
+        // (fir_block.h restates this second half as fir_block_c2r_store for the long convolution.  This kernel keeps its own text: built on that
+        // helper its unit-stride instantiation at 512 takes 82 VGPRs instead of 79 — five waves per SIMD instead of six — and the kernel is to
+        // keep its resource figures.)
         // v = c2r_N(Y): split with T_N, conjugate, forward FFT_M, scale by 1 / M and conjugate back (pva_synth_frame's)
         any_first_pass_from<Gm>(scr, w512l, tb.wm, lane, [&](int m) -> cf {
             cf xk = ys[m], xm = ys[M - m];
@@ -158,11 +116,7 @@ __global__ __launch_bounds__(64) void fir_taps_kernel(const float* __restrict__ 
     for (int i = threadIdx.x; i < 512; i += 64) w512l[i] = tb.w512[i];
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    any_first_pass_from<Gm>(scr, w512l, tb.wm, lane, [&](int m) -> cf { return cf{hpad[2 * m], hpad[2 * m + 1]}; });
-    any_passes8<Gm, (Gm::M / Gm::R1)>(scr, w512l, lane);
-    wave_lds_sync();
-#pragma unroll 1
-    for (int k = lane; k <= F::M; k += 64) hspec[k] = any_rfft_bin<Gm>(scr, tb.tn, k);
+    fir_taps_r2c<N>(scr, w512l, tb, hpad, N, hspec, lane);
 }
 
 template <int N>

@@ -268,6 +268,8 @@ int nae_debug_set(nae_ctx* ctx, const char* key, long long value)
     auto one_of = [&](std::initializer_list<long long> ok) { for (long long v : ok) if (v == value) return true; return false; };
     if (k == "pv_tile" && count) ctx->pv_tile = (int)value;
     else if (k == "fir_tile" && count) ctx->fir_tile = (int)value;
+    else if (k == "conv_tile" && count) ctx->conv_tile = (int)value;
+    else if (k == "conv_ring" && count) ctx->conv_ring = (int)value;
     else if (k == "pv_fps" && one_of({0, 1, 2, 4})) ctx->pv_fps = (int)value;
     else if (k == "pv_flow" && one_of({0, 1, 2})) ctx->pv_flow = (int)value;
     else if (k == "pv_lean" && flag) ctx->pv_lean = value != 0;
@@ -355,6 +357,7 @@ int nae_ctx_destroy(nae_ctx* ctx)
     if (ctx->ws_mid) (void)hipFree(ctx->ws_mid);
     nae_wsola_cache_free(ctx);
     nae_fir_cache_free(ctx);
+    nae_conv_cache_free(ctx);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return NAE_OK;

@@ -36,6 +36,12 @@ struct nae_ctx {
     // nae_fir_block_f32 keeps the last call's taps and their spectrum (kernels_fir.hip): [padded taps | H], sized for n_fft = 4096
     float* d_fir_spec = nullptr; int fir_spec_n_fft = 0;
     std::vector<float> h_fir_taps;
+    int conv_tile = 0;           // blocks per wave of the long convolution's accumulate kernel; 0 = nae_pick_conv_tile
+    int conv_ring = 0;           // spectrum slots per stream-channel of its workspace ring; 0 = from NAE_CONV_WS_BYTES (nae_pick_conv_ring)
+    // nae_conv_block_f32 keeps the last call's taps and their spectra (kernels_conv.hip), apart from the FIR filter's, and the ring of its launches
+    float* d_conv_spec = nullptr; size_t conv_spec_floats = 0; int conv_spec_n_fft = 0, conv_spec_taps_ch = 0;
+    std::vector<float> h_conv_taps;
+    void* ws_conv = nullptr; size_t ws_conv_bytes = 0;
     // tuning / A-B switches: nae_debug_set(ctx, key, value) (include/nae_gpu.h lists the keys; NAE_DEBUG="key=value,..." applies them at context creation)
     bool dbg_st_unfused = false;     // st_unfused: WSOLA chain runs filter and cubic stage as separate launches
     int dbg_td_nc = 0;               // td_nc = 1|2|4: candidates per thread of the WSOLA search (0: by batch size)
@@ -222,6 +228,28 @@ int nae_launch_fir(nae_ctx* ctx, int n_fft, const float* d_spec, const nae_sig* 
                    size_t b_origin, size_t b_stop);
 int nae_pick_fir_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc);
 void nae_fir_cache_free(nae_ctx* ctx);
+
+// kernels_conv.hip: the long convolution ("K10 long convolution").  nae_conv_check: the parameter rules of the block call and the handle
+// (n_taps < 1, ch not 1 / 2 or taps_ch not 1 / ch NAE_ERR_INVALID; more than NAE_CONV_MAX_TAPS taps, a size other than 512 ... 4096 or more than
+// NAE_CONV_MAX_PARTS partitions NAE_ERR_UNSUPPORTED; *n_fft 0 becomes the pick).  A spectrum buffer holds nae_conv_spec_floats floats: the
+// [taps_ch][parts n_fft / 2] padded taps, then H [taps_ch][parts][n_fft / 2 + 8] complex (nae_conv_make_spec, which waits for the upload).  A ring
+// holds nae_conv_ring_floats floats: [stream-channel][ring][n_fft / 2 + 8] complex, block j in slot j mod ring.  nae_launch_conv runs blocks
+// [b_origin, b_stop) of absolutely indexed signals in slabs of ring - (parts - 1) blocks and leaves the last spectra in the ring.
+// The workspace of a block call is capped at NAE_CONV_WS_BYTES: 256 MiB is the chip's Infinity Cache, so a slab's spectra written by one kernel
+// are still on the chip when the next reads them, and it holds slabs of NAE_CONV_MIN_SLAB blocks for 60 stereo streams at 4096 / 128 partitions;
+// larger batches run in groups of streams.  A handle's ring has room for slabs of NAE_CONV_HANDLE_SLAB blocks.
+constexpr size_t NAE_CONV_WS_BYTES = (size_t)256 << 20;
+constexpr int NAE_CONV_MIN_SLAB = 8, NAE_CONV_HANDLE_SLAB = 64;
+int nae_conv_check(nae_ctx* ctx, int n_taps, int taps_ch, int ch, int* n_fft);
+int nae_conv_parts(int n_taps, int n_fft);
+size_t nae_conv_spec_floats(int n_fft, int parts, int taps_ch);
+size_t nae_conv_ring_floats(int n_fft, size_t n_sc, size_t ring);
+int nae_conv_make_spec(nae_ctx* ctx, const float* taps_host, int n_taps, int taps_ch, int n_fft, float* d_spec);
+int nae_launch_conv(nae_ctx* ctx, int n_fft, int parts, int taps_ch, const float* d_spec, float* d_ring, size_t ring, const nae_sig* src,
+                    size_t in_len, int ch, size_t n_streams, const nae_sig* dst, size_t b_origin, size_t b_stop);
+int nae_pick_conv_tile(nae_ctx* ctx, int n_fft);
+size_t nae_pick_conv_ring(nae_ctx* ctx, int n_fft, int parts, size_t blocks, size_t n_sc);
+void nae_conv_cache_free(nae_ctx* ctx);
 
 // kernels_nodes.hip
 int nae_launch_copy_sig(nae_ctx* ctx, const nae_sig* src, const nae_sig* dst, size_t S, int ch, size_t n_streams,

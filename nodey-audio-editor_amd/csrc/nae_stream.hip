@@ -49,7 +49,38 @@ struct nae_fir {
     bool flushed = false;
 };
 
+// the long convolution's handle ("K10 long convolution"): nae_fir's, with the ring of spectra kept between puts
+struct nae_conv {
+    nae_ctx* ctx;
+    int ch, n_fft, n_taps, taps_ch, parts;
+    float* d_spec = nullptr;       // the padded taps and their spectra H (nae_conv_make_spec)
+    float* d_ring = nullptr;       // [ch][ring] spectra: the last parts - 1 blocks stay in it between puts
+    size_t ring = 0;
+    DevFifo in;                    // interleaved input, from the half block in front of the next block on
+    DevFifo out;                   // interleaved result
+    size_t blocks_done = 0, out_read = 0;
+    bool flushed = false;
+};
+
 namespace {
+
+int conv_process(nae_conv* h)
+{
+    nae_ctx* ctx = h->ctx;
+    const size_t B = (size_t)h->n_fft / 2;
+    const size_t blocks = h->flushed ? (h->in.total + B - 1) / B : h->in.total / B;
+    if (blocks <= h->blocks_done) return NAE_OK;
+    const size_t produced = h->flushed ? h->in.total : blocks * B;
+    int rc = h->out.reserve(ctx, produced);
+    if (rc) return rc;
+    const nae_sig src = h->in.view(), dst = h->out.view();
+    rc = nae_launch_conv(ctx, h->n_fft, h->parts, h->taps_ch, h->d_spec, h->d_ring, h->ring, &src, h->in.total, h->ch, 1, &dst, h->blocks_done, blocks);
+    if (rc) return rc;
+    h->out.total = produced;
+    h->blocks_done = blocks;
+    h->in.drop((long long)((blocks - 1) * B));       // the next block's first half
+    return NAE_OK;
+}
 
 // the blocks that became computable: every whole block, and after the flush the partial one at the end
 int fir_process(nae_fir* h)
@@ -517,6 +548,104 @@ int nae_fir_destroy(nae_fir* h)
     h->in.free();
     h->out.free();
     if (h->d_spec) (void)hipFree(h->d_spec);
+    delete h;
+    return NAE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ long convolution
+int nae_conv_create(nae_ctx* ctx, const float* taps_host, int n_taps, int taps_ch, int n_fft, int channels, nae_conv** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    if (!taps_host) return nae_fail(ctx, NAE_ERR_INVALID, "conv: null pointer");
+    int rc = nae_conv_check(ctx, n_taps, taps_ch, channels, &n_fft);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_conv* s = new (std::nothrow) nae_conv();
+    if (!s) return NAE_ERR_NOMEM;
+    s->ctx = ctx;
+    s->ch = channels;
+    s->n_fft = n_fft;
+    s->n_taps = n_taps;
+    s->taps_ch = taps_ch;
+    s->parts = nae_conv_parts(n_taps, n_fft);
+    s->ring = nae_pick_conv_ring(ctx, n_fft, s->parts, NAE_CONV_HANDLE_SLAB, (size_t)channels);
+    s->in.width = s->out.width = (size_t)channels;
+    if (hipMalloc((void**)&s->d_spec, nae_conv_spec_floats(n_fft, s->parts, taps_ch) * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&s->d_ring, nae_conv_ring_floats(n_fft, (size_t)channels, s->ring) * sizeof(float)) != hipSuccess) {
+        if (s->d_spec) (void)hipFree(s->d_spec);
+        delete s;
+        return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(conv spectra)");
+    }
+    if ((rc = nae_conv_make_spec(ctx, taps_host, n_taps, taps_ch, n_fft, s->d_spec))) {
+        (void)hipFree(s->d_spec);
+        (void)hipFree(s->d_ring);
+        delete s;
+        return rc;
+    }
+    *h = s;
+    return NAE_OK;
+}
+
+static int conv_append(nae_conv* h, const float* p, size_t S, bool host)
+{
+    if (!h || (S && !p)) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (h->flushed) return nae_fail(h->ctx, NAE_ERR_STATE, "put after flush");
+    if (S == 0) return NAE_OK;
+    const int rc = h->in.push(h->ctx, p, S, host);
+    return rc ? rc : conv_process(h);
+}
+
+int nae_conv_put(nae_conv* h, const float* interleaved, size_t S) { return conv_append(h, interleaved, S, false); }
+int nae_conv_put_host(nae_conv* h, const float* interleaved_host, size_t S) { return conv_append(h, interleaved_host, S, true); }
+
+// n_taps - 1 zero frames behind the input: the tail of the convolution comes out, in_len + n_taps - 1 frames over the handle's life
+int nae_conv_flush(nae_conv* h)
+{
+    if (!h) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (h->flushed) return NAE_OK;
+    const size_t tail = (size_t)h->n_taps - 1;
+    if (tail) {
+        const int rc = h->in.reserve(h->ctx, h->in.total + tail);
+        if (rc) return rc;
+        const hipError_t e = hipMemsetAsync(h->in.at(h->in.total), 0, tail * h->in.width * sizeof(float), h->ctx->stream);
+        if (e != hipSuccess) return nae_check(h->ctx, e, "hipMemsetAsync(conv flush)");
+        h->in.total += tail;
+    }
+    h->flushed = true;
+    return conv_process(h);
+}
+
+size_t nae_conv_available(nae_conv* h) { return h ? h->out.total - h->out_read : 0; }
+
+static int conv_take(nae_conv* h, float* dst, size_t max_frames, size_t* got, bool host)
+{
+    if (!h || !got || (max_frames && !dst)) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    size_t n = h->out.total - h->out_read;
+    if (n > max_frames) n = max_frames;
+    *got = n;
+    if (n == 0) return NAE_OK;
+    const int rc = h->out.pop(h->ctx, h->out_read, dst, n, host);
+    if (rc) return rc;
+    h->out_read += n;
+    return NAE_OK;
+}
+
+int nae_conv_receive(nae_conv* h, float* dst, size_t max_frames, size_t* got) { return conv_take(h, dst, max_frames, got, false); }
+int nae_conv_receive_host(nae_conv* h, float* dst_host, size_t max_frames, size_t* got) { return conv_take(h, dst_host, max_frames, got, true); }
+
+int nae_conv_destroy(nae_conv* h)
+{
+    if (!h) return NAE_OK;
+    (void)nae_use_device(h->ctx);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    h->in.free();
+    h->out.free();
+    if (h->d_spec) (void)hipFree(h->d_spec);
+    if (h->d_ring) (void)hipFree(h->d_ring);
     delete h;
     return NAE_OK;
 }

@@ -147,4 +147,6 @@ namespace infra
 	void register_all_processors(processor::Stretch_algorithm default_algorithm);
 	// the nodes the reference has no class for (audio_filter): called after register_all_processors(), which stays the reference's list
 	void register_extension_processors();
+	// the effect nodes (audio_reverb): called after the two above, each of which stays the list it was
+	void register_effect_processors();
 }

@@ -1,5 +1,6 @@
 #include "audio-velocity.hpp"
 #include "audio-filter.hpp"
+#include "audio-reverb.hpp"
 #include "gpu-context.hpp"
 #include "velocity-cadence.hpp"
 
@@ -849,6 +850,199 @@ namespace processor
 			size_t total = 0;
 			float* samples = upload_as_f32(batch, h_raw, d_raw, d_f32, &total);
 			gpu::check(nae_fir_put(fir, samples, total), "nae_fir_put");
+			deliver();
+		}
+		for (auto& stream : output_stream) stream->set_eof();
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_reverb
+	infra::Processor::Info Audio_reverb::get_processor_info()
+	{
+		return {"audio_reverb", "Audio Reverb", false, [] { return std::unique_ptr<infra::Processor>(new Audio_reverb); },
+				"Convolution reverb with a designed, per-channel decaying-noise response by partitioned FFT convolution (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_reverb::get_pin_attributes() const
+	{
+		return {
+			{"output", "Output", typeid(Audio_stream), false, [] { return std::make_shared<Audio_stream>(); }},
+			{"input", "Input", typeid(Audio_stream), true, [] { return std::make_shared<Audio_stream>(); }}
+		};
+	}
+
+	Json::Value Audio_reverb::serialize() const
+	{
+		Json::Value value;
+		if (rt60 != default_rt60) value["rt60"] = rt60;
+		if (predelay_ms != default_predelay_ms) value["predelay_ms"] = predelay_ms;
+		if (wet != default_wet) value["wet"] = wet;
+		if (dry != default_dry) value["dry"] = dry;
+		if (seed != 1) value["seed"] = (double)seed;   // below 2^53 (deserialize): exact
+		if (fft_size != 0) value["fft_size"] = fft_size;
+		return value;
+	}
+
+	void Audio_reverb::deserialize(const Json::Value& value)
+	{
+		const auto wrong = [](const char* field) {
+			return Runtime_error(
+				"Failed to deserialize JSON file",
+				"Audio_reverb failed to serialize the JSON input because of missing or invalid fields.",
+				std::string("Wrong field: ") + field
+			);
+		};
+		// everything is read and checked first: a rejected value leaves the node as it was
+		const auto real = [&](const char* key, double lo, double hi, double fallback) {
+			if (!value.isMember(key)) return fallback;
+			if (!value[key].isDouble() || !(value[key].asDouble() >= lo && value[key].asDouble() <= hi)) throw wrong(key);
+			return value[key].asDouble();
+		};
+		const double r = real("rt60", 0.1, 5.0, default_rt60), p = real("predelay_ms", 0.0, 200.0, default_predelay_ms);
+		const double w = real("wet", 0.0, 1.0, default_wet), d = real("dry", 0.0, 1.0, default_dry);
+		uint64_t sd = 1;
+		if (value.isMember("seed"))
+		{
+			// compared as a double with the range first: a number outside the integer range is never converted
+			const Json::Value& v = value["seed"];
+			if (!v.isDouble() || !(v.asDouble() >= 0.0 && v.asDouble() < 9007199254740992.0) || v.asDouble() != (double)(uint64_t)v.asDouble()) throw wrong("seed");
+			sd = (uint64_t)v.asDouble();
+		}
+		int n_fft = 0;
+		if (value.isMember("fft_size"))
+		{
+			const Json::Value& v = value["fft_size"];
+			if (!v.isDouble() || !(v.asDouble() >= 1.0 && v.asDouble() <= 4096.0) || v.asDouble() != (double)v.asInt()) throw wrong("fft_size");
+			n_fft = v.asInt();
+			if (nae_fir_pick_n_fft(n_fft / 2 + 1) != n_fft) throw wrong("fft_size");   // the filter's sizes: 512, 1024, 2048, 4096
+		}
+		rt60 = r;
+		predelay_ms = p;
+		wet = w;
+		dry = d;
+		seed = sd;
+		fft_size = n_fft;
+	}
+
+	void Audio_reverb::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
+		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
+		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
+		if (!input_item.has_value())
+			throw Runtime_error("Audio Reverb has no input", "Audio Reverb requires an audio stream input to function properly.", "Input item 'input' not found");
+		Audio_stream& input_stream = input_item.value().get();
+		nae_ctx* ctx = gpu::context();
+		nae_conv* conv = nullptr;
+		struct Guard { nae_conv*& h; ~Guard() { if (h) nae_conv_destroy(h); } } guard{conv};
+		gpu::Device_buffer d_raw, d_f32, d_out;
+		gpu::Pinned_buffer h_raw, h_out;
+		int ch = 0;
+		struct Shape { int nb_samples, sample_rate; int64_t pts; decltype(Frame_data::time_base) time_base; };
+		std::deque<Shape> shapes;     // the input frames whose output is still owed
+		std::vector<float> ready;     // convolved samples, interleaved, not yet cut into frames
+		size_t ready_pos = 0;         // frames of `ready` already delivered
+		std::shared_ptr<const Audio_frame> held;  // popped, but with another channel count than the batch in front of it
+
+		// everything the handle has ready comes down behind ONE wait and leaves as frames of the input's sizes
+		const auto deliver = [&]()
+		{
+			const size_t avail = nae_conv_available(conv);
+			if (avail == 0) { gpu::wait(stop_token); return; }
+			float* dev = static_cast<float*>(d_out.reserve(avail * ch * sizeof(float)));
+			float* host = static_cast<float*>(h_out.reserve(avail * ch * sizeof(float)));
+			size_t got = 0;
+			gpu::check(nae_conv_receive(conv, dev, avail, &got), "nae_conv_receive");
+			gpu::check(nae_memcpy_d2h(ctx, host, dev, got * ch * sizeof(float)), "d2h");
+			gpu::wait(stop_token);
+			ready.erase(ready.begin(), ready.begin() + ready_pos * ch);
+			ready_pos = 0;
+			ready.insert(ready.end(), host, host + got * ch);
+			while (!shapes.empty() && !stop_token && ready.size() / ch - ready_pos >= (size_t)shapes.front().nb_samples)
+			{
+				const Shape s = shapes.front();
+				shapes.pop_front();
+				auto out = std::make_shared<Audio_frame>();
+				Frame_data* o = out->data();
+				o->format = AV_SAMPLE_FMT_FLT;
+				o->sample_rate = s.sample_rate;
+				o->nb_samples = s.nb_samples;
+				o->ch_layout.nb_channels = ch;
+				o->time_base = s.time_base;
+				o->pts = s.pts;
+				frame_get_buffer(o, 32);
+				std::memcpy(o->data[0], ready.data() + ready_pos * ch, (size_t)s.nb_samples * ch * sizeof(float));
+				ready_pos += s.nb_samples;
+				for (auto& stream : output_stream)
+					while (!stop_token && stream->try_push(out) != channel_op_status::success) nae_fiber::this_fiber::yield();
+			}
+		};
+
+		while (!stop_token)
+		{
+			constexpr size_t max_batch = 16;   // as the filter node: every frame that is already waiting is put as one block
+			std::vector<std::shared_ptr<const Audio_frame>> batch;
+			if (held) batch.push_back(std::move(held));
+			held.reset();
+			bool ended = false;
+			while (batch.size() < max_batch)
+			{
+				const auto pop_result = input_stream.try_pop();
+				if (!pop_result.has_value())
+				{
+					ended = input_stream.eof();
+					break;
+				}
+				if (!batch.empty() && pop_result.value()->data()->ch_layout.nb_channels != batch.front()->data()->ch_layout.nb_channels)
+				{
+					held = pop_result.value();
+					break;
+				}
+				batch.push_back(pop_result.value());
+			}
+			if (batch.empty())
+			{
+				if (!ended)
+				{
+					nae_fiber::this_fiber::yield();
+					continue;
+				}
+				if (conv != nullptr)
+				{
+					// the last partial block comes out with the flush; the frames still owed are cut from it and the tail behind them is dropped
+					gpu::check(nae_conv_flush(conv), "nae_conv_flush");
+					deliver();
+				}
+				break;
+			}
+			const Frame_data* frame = batch.front()->data();
+			if (conv == nullptr)
+			{
+				ch = frame->ch_layout.nb_channels;
+				if (ch != 1 && ch != 2) throw Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
+				const int n_taps = nae_conv_reverb_taps(frame->sample_rate, rt60, predelay_ms / 1000.0);
+				if (n_taps < 1 || nae_conv_pick_n_fft(n_taps) == 0)   // the library's limits: 0 beyond them
+					throw Runtime_error(
+						"Reverb response too long", "The decay time and the pre-delay give a response longer than the convolution supports at this sample rate.",
+						infra::fmt("rt60 %g s, pre-delay %g ms at %d Hz: %d taps", rt60, predelay_ms, frame->sample_rate, n_taps)
+					);
+				std::vector<float> h((size_t)n_taps * ch);
+				for (int c = 0; c < ch; c++)
+					if (nae_conv_design_reverb(frame->sample_rate, rt60, predelay_ms / 1000.0, dry, wet, seed + (uint64_t)c, n_taps, h.data() + (size_t)c * n_taps) != NAE_OK)
+						throw Runtime_error("Invalid reverb parameters", "The reverb's response could not be designed.",
+											infra::fmt("rt60 %g s, pre-delay %g ms at %d Hz", rt60, predelay_ms, frame->sample_rate));
+				gpu::check(nae_conv_create(ctx, h.data(), n_taps, ch, fft_size, ch, &conv), "nae_conv_create");
+			}
+			else if (frame->ch_layout.nb_channels != ch)
+				throw Runtime_error("Channel count changed", "The reverb runs one stream of a fixed channel count.",
+									infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, ch));
+			for (const auto& f : batch) shapes.push_back({f->data()->nb_samples, f->data()->sample_rate, f->data()->pts, f->data()->time_base});
+			size_t total = 0;
+			float* samples = upload_as_f32(batch, h_raw, d_raw, d_f32, &total);
+			gpu::check(nae_conv_put(conv, samples, total), "nae_conv_put");
 			deliver();
 		}
 		for (auto& stream : output_stream) stream->set_eof();

@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "audio-filter.hpp"
+#include "audio-reverb.hpp"
 #include "audio-mix.hpp"
 #include "audio-velocity.hpp"
 #include "audio-vol.hpp"
@@ -73,6 +74,17 @@ namespace processor
 		f_hi = std::max(f_hi, 1.0f);
 		if ((kind == Kind::Bandpass || kind == Kind::Bandstop) && f_lo > f_hi) std::swap(f_lo, f_hi);
 		if (fft_size != 0 && taps > fft_size / 2 + 1) fft_size = 0;
+		return false;
+	}
+
+	void Audio_reverb::draw_title() {}
+	bool Audio_reverb::draw_content(bool)
+	{
+		// what the widgets would keep: every value inside its range
+		rt60 = std::clamp(rt60, 0.1, 5.0);
+		predelay_ms = std::clamp(predelay_ms, 0.0, 200.0);
+		wet = std::clamp(wet, 0.0, 1.0);
+		dry = std::clamp(dry, 0.0, 1.0);
 		return false;
 	}
 }

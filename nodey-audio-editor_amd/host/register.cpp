@@ -4,6 +4,7 @@
 // their own, register_extension_processors(), so that register_all_processors() stays the mirror of the reference's list.
 #include "infra/processor.hpp"
 #include "processor/audio-filter.hpp"
+#include "processor/audio-reverb.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -31,4 +32,7 @@ namespace infra
 
 	// the nodes beyond the reference's list; the editor calls it after register_all_processors()
 	void register_extension_processors() { register_each<processor::Audio_filter>(); }
+
+	// the effects built on the long convolution; a call of its own, so register_extension_processors() stays the list it was
+	void register_effect_processors() { register_each<processor::Audio_reverb>(); }
 }

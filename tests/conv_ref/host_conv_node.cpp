@@ -1,0 +1,207 @@
+// host_conv_node.cpp — the host mirror's reverb node (tests/test_conv_cpu.py and tests/test_gpu_conv.py build it through tests/node_harness.py).
+// `json`: no GPU — every key of audio_reverb round-trips, the defaults are not written back, wrong values are rejected.  `registry`: no GPU —
+// the processor map after register_all_processors(), register_extension_processors() and register_effect_processors().  `gpu`: a source ->
+// audio_reverb -> sink graph delivers the frames it received, with their sizes and pts, and the samples of nae_conv_block_f32 with the
+// designed per-channel taps, bit for bit.
+#include "../node_harness.hpp"
+#include "processor/audio-reverb.hpp"
+
+static bool at_defaults(const Audio_reverb& n)
+{
+	return n.rt60 == 1.5 && n.predelay_ms == 20 && n.wet == 0.3 && n.dry == 1 && n.seed == 1 && n.fft_size == 0;
+}
+
+// a rejected value leaves the node at its defaults
+static bool rejects(const Json::Value& v, const std::string& field)
+{
+	Audio_reverb node;
+	return rejects(node, v, field) && at_defaults(node);
+}
+
+static void test_json()
+{
+	Audio_reverb node;
+	CHECK(at_defaults(node), "defaults 1.5 s / 20 ms / 0.3 / 1 / seed 1 / pick");
+	CHECK(node.serialize().isNull(), "defaults are not written");
+	node.deserialize(Json::Value());
+	CHECK(at_defaults(node) && node.serialize().isNull(), "a project without the keys keeps the defaults");
+	for (double rt : {0.1, 1.5, 5.0})
+		for (double pre : {0.0, 20.0, 200.0})
+			for (int fft : {0, 512, 4096})
+			{
+				Json::Value v;
+				v["rt60"] = rt;
+				v["predelay_ms"] = pre;
+				v["wet"] = 0.75;
+				v["dry"] = 0.5;
+				v["seed"] = 77;
+				if (fft) v["fft_size"] = fft;
+				Audio_reverb a, b;
+				a.deserialize(v);
+				CHECK(a.rt60 == rt && a.predelay_ms == pre && a.wet == 0.75 && a.dry == 0.5 && a.seed == 77 && a.fft_size == fft, "read " << rt << " / " << pre << " / " << fft);
+				const Json::Value w = a.serialize();
+				CHECK(w.isMember("rt60") == (rt != 1.5) && w.isMember("predelay_ms") == (pre != 20.0) && w.isMember("wet") && w.isMember("dry") &&
+						  w.isMember("seed") && w.isMember("fft_size") == (fft != 0),
+					  "only non-defaults written: " << rt << " / " << pre << " / " << fft);
+				b.deserialize(w);
+				CHECK(b.rt60 == a.rt60 && b.predelay_ms == a.predelay_ms && b.wet == a.wet && b.dry == a.dry && b.seed == a.seed && b.fft_size == a.fft_size, "round trip");
+			}
+	{
+		Json::Value v;
+		v["wet"] = 0;
+		v["dry"] = 0;
+		v["seed"] = 0;
+		Audio_reverb a;
+		a.deserialize(v);
+		CHECK(a.wet == 0 && a.dry == 0 && a.seed == 0, "the lower ends are values");
+	}
+	struct Range { const char* key; double below, above; };
+	for (const Range& r : {Range{"rt60", 0.09, 5.01}, Range{"predelay_ms", -0.1, 200.5}, Range{"wet", -0.01, 1.01}, Range{"dry", -0.01, 1.01}})
+	{
+		Json::Value s, lo, hi;
+		s[r.key] = "much";
+		lo[r.key] = r.below;
+		hi[r.key] = r.above;
+		CHECK(rejects(s, r.key) && rejects(lo, r.key) && rejects(hi, r.key), r.key << ": a string and values outside the range rejected");
+	}
+	{
+		Json::Value s, n, f, big;
+		s["seed"] = "one";
+		n["seed"] = -1;
+		f["seed"] = 1.5;
+		big["seed"] = 1e30;
+		CHECK(rejects(s, "seed") && rejects(n, "seed") && rejects(f, "seed") && rejects(big, "seed"), "seed: a string, a negative, a fraction and 1e30 rejected");
+	}
+	for (double n : {0.0, 256.0, 1000.0, 8192.0, 1024.5, -1024.0})
+	{
+		Json::Value v;
+		v["fft_size"] = n;
+		CHECK(rejects(v, "fft_size"), "fft_size " << n << " rejected");
+	}
+	{
+		Json::Value s;
+		s["fft_size"] = "big";
+		CHECK(rejects(s, "fft_size"), "a string fft_size rejected");
+	}
+	{
+		Audio_reverb a;   // the headless draw_content keeps what the widgets would
+		a.rt60 = 9;
+		a.predelay_ms = -3;
+		a.wet = 2;
+		a.dry = -1;
+		CHECK(a.draw_content(false) == false && a.rt60 == 5 && a.predelay_ms == 0 && a.wet == 1 && a.dry == 0, "draw_content: values inside their ranges");
+	}
+}
+
+static void print_registry()
+{
+	std::cout << "REGISTRY";
+	for (const auto& [id, info] : infra::Processor::processor_map) std::cout << " " << id;
+	std::cout << "\n";
+}
+
+static void test_registry()
+{
+	infra::register_all_processors();
+	print_registry();
+	CHECK(infra::Processor::processor_map.size() == 7, "the reference's list: 7 entries");
+	infra::register_extension_processors();
+	print_registry();
+	CHECK(infra::Processor::processor_map.size() == 8 && infra::Processor::processor_map.count("audio_reverb") == 0, "with the extensions: 8 entries, no reverb");
+	infra::register_effect_processors();
+	print_registry();
+	CHECK(infra::Processor::processor_map.size() == 9 && infra::Processor::processor_map.count("audio_reverb") == 1, "with the effects: 9 entries");
+	if (infra::Processor::processor_map.count("audio_reverb"))
+	{
+		const auto node = infra::Processor::processor_map.at("audio_reverb").generate();
+		const auto pins = node->get_pin_attributes();
+		CHECK(node->get_processor_info_non_static().identifier == "audio_reverb" && pins.size() == 2, "generate() gives the node: two pins");
+		int inputs = 0;
+		for (const auto& p : pins) inputs += p.is_input && p.type.get() == typeid(Audio_stream);
+		CHECK(inputs == 1, "one audio input pin, one audio output pin");
+	}
+}
+
+static void test_gpu()
+{
+	// rt60 0.1 s and 5 ms at 48 kHz: 5040 taps, P = 5 at the picked 2048; frames of 1152 samples against blocks of 1024
+	const int S = 20000, frame_size = 1152;
+	const double rt60 = 0.1, pre_ms = 5, wet = 0.4, dry = 0.9;
+	const uint64_t seed = 9;
+	std::vector<float> x((size_t)S * 2);
+	uint64_t st = 4711;
+	for (auto& v : x)
+	{
+		st = st * 6364136223846793005ull + 1442695040888963407ull;
+		v = (float)((double)(st >> 40) / (double)(1ull << 24) * 2.0 - 1.0);
+	}
+	Runner r;
+	auto src = std::make_shared<Src>();
+	src->samples = x;
+	src->frame_size = frame_size;
+	auto reverb = std::make_shared<Audio_reverb>();
+	Json::Value v;
+	v["rt60"] = rt60;
+	v["predelay_ms"] = pre_ms;
+	v["wet"] = wet;
+	v["dry"] = dry;
+	v["seed"] = (int)seed;
+	reverb->deserialize(v);
+	auto sink = std::make_shared<Sink>();
+	r.add_node(1, src); r.add_node(2, reverb); r.add_node(3, sink);
+	r.add_link({1, "output", 2, "input"});
+	r.add_link({2, "output", 3, "input"});
+	const bool ok = r.run();
+	CHECK(ok, "source -> audio_reverb -> sink runs: " << r.get_processor_resources().at(2)->error_text);
+	if (!ok) return;
+	// the block call with the designed per-channel taps, through a context of its own
+	const int L = nae_conv_reverb_taps(48000, rt60, pre_ms / 1000.0);
+	CHECK(L == 240 + 4800, "response length: " << L);
+	std::vector<float> taps((size_t)L * 2);
+	for (int c = 0; c < 2; c++)
+		CHECK(nae_conv_design_reverb(48000, rt60, pre_ms / 1000.0, dry, wet, seed + c, L, taps.data() + (size_t)c * L) == 0, "design");
+	nae_ctx* ctx = nullptr;
+	CHECK(nae_ctx_create(0, &ctx) == 0, "context");
+	if (!ctx) return;
+	std::vector<float> y((size_t)S * 2);
+	void *d_x = nullptr, *d_y = nullptr;
+	CHECK(nae_malloc(ctx, x.size() * sizeof(float), &d_x) == 0 && nae_malloc(ctx, y.size() * sizeof(float), &d_y) == 0, "malloc");
+	CHECK(nae_memcpy_h2d(ctx, d_x, x.data(), x.size() * sizeof(float)) == 0, "h2d");
+	const nae_sig sx{d_x, 0, 1, 2}, sy{d_y, 0, 1, 2};
+	CHECK(nae_conv_block_f32(ctx, taps.data(), L, 2, 0, &sx, S, 2, 1, &sy) == 0, "block call");
+	CHECK(nae_memcpy_d2h(ctx, y.data(), d_y, y.size() * sizeof(float)) == 0 && nae_sync(ctx) == 0, "d2h");
+	nae_free(ctx, d_x);
+	nae_free(ctx, d_y);
+	nae_ctx_destroy(ctx);
+
+	const size_t n_frames = ((size_t)S + frame_size - 1) / frame_size;
+	CHECK(sink->frames.size() == n_frames, "as many frames as the source sent: " << sink->frames.size() << " vs " << n_frames);
+	size_t pos = 0, bad = 0;
+	bool shape_ok = true;
+	for (size_t f = 0; f < sink->frames.size(); f++)
+	{
+		const Frame_data* d = sink->frames[f]->data();
+		const int want_n = (int)std::min<size_t>(frame_size, (size_t)S - std::min<size_t>(S, f * frame_size));
+		const int64_t want_pts = (int64_t)((0.5 + double(f * frame_size) / 48000) * 1000000);   // the source's own formula
+		shape_ok = shape_ok && d->nb_samples == want_n && d->format == AV_SAMPLE_FMT_FLT && d->ch_layout.nb_channels == 2 && d->sample_rate == 48000 &&
+				   d->pts == want_pts && d->time_base.num == 1 && d->time_base.den == 1000000;
+		const float* got = reinterpret_cast<const float*>(d->data[0]);
+		for (int i = 0; i < d->nb_samples && pos < (size_t)S; i++, pos++)
+			for (int c = 0; c < 2; c++) bad += std::memcmp(&got[i * 2 + c], &y[pos * 2 + c], sizeof(float)) != 0;
+	}
+	CHECK(shape_ok, "frames of the input's sizes, format FLT, the source's pts and time base");
+	CHECK(pos == (size_t)S, "as many samples as the source sent: " << pos);
+	CHECK(bad == 0, "the samples of the block call with channel c's taps from seed + c: " << bad << " words differ");
+}
+
+int main(int argc, char** argv)
+{
+	const std::string mode = argc > 1 ? argv[1] : "json";
+	if (mode == "json") test_json();
+	else if (mode == "registry") test_registry();
+	else if (mode == "gpu") test_gpu();
+	else { std::cout << "usage: host_conv_node json|registry|gpu\n"; return 2; }
+	if (failures) { std::cout << failures << " failure(s)\n"; return 1; }
+	std::cout << "HOST CONV OK " << mode << "\n";
+	return 0;
+}
