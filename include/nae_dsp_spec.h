@@ -33,6 +33,22 @@
 #define NAE_CONV_MAX_TAPS 262144
 #define NAE_CONV_MAX_PARTS 512
 #define NAE_CONV_PICK_PARTS 16
+/* K11 biquad cascade ("K11 biquad cascade"): up to NAE_EQ_MAX_SECTIONS sections in double, tiled in time: a lane runs
+ * NAE_EQ_LANE samples, 64 lanes make a chunk of NAE_EQ_CHUNK samples on a grid that starts at the stream's sample 0.  The tiling is part of
+ * the specification: the bits depend on it. */
+#define NAE_EQ_MAX_SECTIONS 16
+#define NAE_EQ_LANE 16
+#define NAE_EQ_CHUNK (64 * NAE_EQ_LANE)
+/* nae_eq_design: the kinds, and the limits of q and gain_db */
+#define NAE_EQ_PEAK 0
+#define NAE_EQ_LOWSHELF 1
+#define NAE_EQ_HIGHSHELF 2
+#define NAE_EQ_LOWPASS 3
+#define NAE_EQ_HIGHPASS 4
+#define NAE_EQ_NOTCH 5
+#define NAE_EQ_MIN_Q 0.1
+#define NAE_EQ_MAX_Q 40.0
+#define NAE_EQ_MAX_GAIN_DB 24.0
 /* transient preservation ("Transient preservation"): bin k of frame f rises iff P_f[k] > RISE * P_{f-1}[k] and
  * P_f[k] > FLOOR * N; frame f is "high" iff DEN * (rising bins) >= NUM * (N/2 + 1); an onset is an upward crossing of "high" at f >= 2.
  * RISE is +6 dB: at +3 dB steady white noise crosses 3/8 at N = 512 and 1024 (DESIGN.md gives the numbers). */

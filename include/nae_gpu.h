@@ -43,7 +43,8 @@ extern "C" {
  *   _formant_shift entries (one onset decision and one phase-lock region map per stereo stream), probed by return code as
  *   NAE_STRETCH_TRANSIENTS is; nae_fir_pick_n_fft, nae_fir_block_f32, nae_fir_design and the nae_fir handle (nae_fir_create, _put, _put_host, _flush,
  *   _available, _receive, _receive_host, _destroy): the FIR filter, K9; nae_conv_pick_n_fft, nae_conv_block_f32, nae_conv_reverb_taps,
- *   nae_conv_design_reverb and the nae_conv handle (the same eight entries): the long convolution, K10. */
+ *   nae_conv_design_reverb and the nae_conv handle (the same eight entries): the long convolution, K10; nae_eq_design, nae_eq_block_f32 and
+ *   the nae_eq handle (the same eight entries): the biquad cascade, K11. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -67,6 +68,7 @@ typedef struct nae_stretch nae_stretch;
 typedef struct nae_spectrum nae_spectrum;
 typedef struct nae_fir nae_fir;
 typedef struct nae_conv nae_conv;
+typedef struct nae_eq nae_eq;
 
 /* ------------------------------------------------------------------ context / plumbing */
 int nae_abi_version(void);
@@ -518,6 +520,39 @@ int nae_conv_destroy(nae_conv* h);
  * (0, 10], predelay_s outside [0, 1], dry or wet not finite, n_taps < d + 1, a null pointer.  No context, no device work. */
 int nae_conv_reverb_taps(int sample_rate, double rt60_s, double predelay_s);
 int nae_conv_design_reverb(int sample_rate, double rt60_s, double predelay_s, double dry, double wet, uint64_t seed, int n_taps, float* taps_host);
+
+/* ------------------------------------------------------------------ K11 biquad cascade
+ * no reference code.  Spec ("K11 biquad cascade"): S sections, 1 <= S <= NAE_EQ_MAX_SECTIONS, each five doubles
+ * (b0, b1, b2, a1, a2) with a0 = 1, laid out [S][5] on the host; one set for every channel and stream.  f32 samples are widened to double,
+ * every section runs in double in transposed direct form II (y = b0 x + z1; z1 = (b1 x - a1 y) + z2; z2 = b2 x - a2 y), the signal stays in
+ * double between the sections and is rounded once to f32 behind the last.  The recurrence is computed parallel in time, and the tiling is
+ * part of the specification: chunks of NAE_EQ_CHUNK samples on a grid from sample 0, 64 lanes of NAE_EQ_LANE samples; per section a
+ * zero-state pass of every lane, a Kogge-Stone scan of the lanes' end states with the powers of the 16-step state map, and a correction of
+ * every sample with the zero-input responses p and q; every step one IEEE operation in a fixed order (DESIGN.md gives it).  Input past in_len
+ * is zero, output past in_len is not stored.  Bit-exact against the CPU statement (tests/eq_ref/ref_eq.c); any cut of the input into puts
+ * gives the same bits; a non-finite input sample i leaves every output sample before i as it was.
+ * Errors: a null pointer, n_sections < 1, ch not 1 or 2, a non-finite coefficient or a section that is not strictly stable (|a2| < 1 and
+ * |a1| < 1 + a2): NAE_ERR_INVALID; more than NAE_EQ_MAX_SECTIONS sections: NAE_ERR_UNSUPPORTED; in_len = 0 or n_streams = 0: NAE_OK after
+ * the checks, nothing is launched.  Views as K9's: interleaved or planar on either side, stream_stride 0 on the source.  The context keeps
+ * the tables of its last block call. */
+int nae_eq_block_f32(nae_ctx* ctx, const double* coef_host, int n_sections, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                     const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch): whole chunks come out as they fill; nae_eq_flush releases the partial last
+ * chunk, so in_len frames come out in all (an IIR has no tail to append), equal to the block call's however the input is cut.  A put after
+ * the flush: NAE_ERR_STATE. */
+int nae_eq_create(nae_ctx* ctx, const double* coef_host, int n_sections, int channels, nae_eq** h);
+int nae_eq_put(nae_eq* h, const float* interleaved, size_t S);
+int nae_eq_put_host(nae_eq* h, const float* interleaved_host, size_t S);
+int nae_eq_flush(nae_eq* h);
+size_t nae_eq_available(nae_eq* h);
+int nae_eq_receive(nae_eq* h, float* dst, size_t max_frames, size_t* got);
+int nae_eq_receive_host(nae_eq* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_eq_destroy(nae_eq* h);
+/* One section on the host, in double, by the Audio EQ Cookbook's forms: A = 10^(gain_db / 40), w0 = 2 pi freq / sample_rate,
+ * alpha = sin w0 / (2 q), every kind divided through by its a0.  kind: NAE_EQ_PEAK, NAE_EQ_LOWSHELF, NAE_EQ_HIGHSHELF (with 2 sqrt(A) alpha),
+ * NAE_EQ_LOWPASS, NAE_EQ_HIGHPASS, NAE_EQ_NOTCH (gain_db ignored) of nae_dsp_spec.h.  NAE_ERR_INVALID: an unknown kind, sample_rate <= 0,
+ * freq outside (0, sample_rate / 2), q outside [0.1, 40], |gain_db| > 24 or not finite, a null pointer.  No context, no device work. */
+int nae_eq_design(int kind, int sample_rate, double freq, double gain_db, double q, double coef_host[5]);
 
 /* ------------------------------------------------------------------ the 4-node graph of BASELINE.json
  * input -> mix(2) -> pitch -> FFT spectrum, one launch sequence over n_streams independent streams.

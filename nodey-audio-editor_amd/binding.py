@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = [
     "nae_fir_available", "nae_fir_receive", "nae_fir_receive_host", "nae_fir_destroy",
     "nae_conv_pick_n_fft", "nae_conv_block_f32", "nae_conv_reverb_taps", "nae_conv_design_reverb", "nae_conv_create", "nae_conv_put",
     "nae_conv_put_host", "nae_conv_flush", "nae_conv_available", "nae_conv_receive", "nae_conv_receive_host", "nae_conv_destroy",
+    "nae_eq_design", "nae_eq_block_f32", "nae_eq_create", "nae_eq_put", "nae_eq_put_host", "nae_eq_flush", "nae_eq_available", "nae_eq_receive",
+    "nae_eq_receive_host", "nae_eq_destroy",
 ]
 
 
@@ -47,6 +49,7 @@ STRETCH_LINK_CHANNELS = 16   # NAE_STRETCH_LINK_CHANNELS: one onset decision and
 FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX = 0.25, 4.0   # NAE_FORMANT_SHIFT_MIN / _MAX (include/nae_dsp_spec.h): the range of formant_ratio
 FIR_SIZES = (512, 1024, 2048, 4096)                 # frame sizes of the FIR filter: at most n_fft / 2 + 1 taps
 FIR_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}   # `kind` of nae_fir_design
+EQ_KINDS = ("peak", "lowshelf", "highshelf", "lowpass", "highpass", "notch")   # `kind` of nae_eq_design: NAE_EQ_PEAK ... NAE_EQ_NOTCH
 
 
 class NaeError(RuntimeError):
@@ -195,6 +198,11 @@ def load_library() -> C.CDLL:
         "nae_conv_put": (i, [vp, vp, sz]), "nae_conv_put_host": (i, [vp, vp, sz]), "nae_conv_flush": (i, [vp]),
         "nae_conv_available": (sz, [vp]), "nae_conv_receive": (i, [vp, vp, sz, P(sz)]),
         "nae_conv_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_conv_destroy": (i, [vp]),
+        "nae_eq_design": (i, [i, i, d, d, d, vp]), "nae_eq_block_f32": (i, [vp, vp, i, P(Sig), sz, i, sz, P(Sig)]),
+        "nae_eq_create": (i, [vp, vp, i, i, P(vp)]),
+        "nae_eq_put": (i, [vp, vp, sz]), "nae_eq_put_host": (i, [vp, vp, sz]), "nae_eq_flush": (i, [vp]),
+        "nae_eq_available": (sz, [vp]), "nae_eq_receive": (i, [vp, vp, sz, P(sz)]),
+        "nae_eq_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_eq_destroy": (i, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -588,6 +596,22 @@ class Context:
         taps_ch, n_taps = (1, taps.size) if taps.ndim == 1 else taps.shape
         self._ck(self.lib.nae_conv_block_f32(self.h, taps.ctypes.data, n_taps, taps_ch, n_fft, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K11
+    @staticmethod
+    def eq_design(kind, sample_rate: int, freq: float, gain_db: float = 0.0, q: float = 0.7071) -> np.ndarray:
+        """one section (b0, b1, b2, a1, a2) by the Audio EQ Cookbook's forms (nae_eq_design); kind: a name of EQ_KINDS or its number"""
+        k = EQ_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+        coef = np.empty(5, np.float64)
+        rc = load_library().nae_eq_design(k, sample_rate, freq, gain_db, q, coef.ctypes.data)
+        if rc:
+            raise NaeError(f"nae_eq_design({kind}, {sample_rate}, {freq}, {gain_db}, {q}) failed: {rc}")
+        return coef
+
+    def eq_block(self, coef: np.ndarray, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the biquad cascade coef[S][5] (doubles; a0 = 1) over every stream and channel; dst receives in_len frames"""
+        coef = np.ascontiguousarray(coef, np.float64).reshape(-1, 5)
+        self._ck(self.lib.nae_eq_block_f32(self.h, coef.ctypes.data, coef.shape[0], C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     # -- graph
     def graph4(self, g: Graph4):
         self._ck(self.lib.nae_graph4_run(self.h, C.byref(g)))
@@ -720,6 +744,51 @@ class Conv:
     def close(self) -> None:
         if self.h:
             self.ctx.lib.nae_conv_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Eq:
+    """The biquad cascade's streaming handle (nae_eq_create): put interleaved f32, flush (the partial last chunk), receive.  coef [S][5]."""
+
+    def __init__(self, ctx: Context, coef: np.ndarray, channels: int):
+        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+        coef = np.ascontiguousarray(coef, np.float64).reshape(-1, 5)
+        ctx._ck(ctx.lib.nae_eq_create(ctx.h, coef.ctypes.data, coef.shape[0], channels, C.byref(self.h)))
+
+    def put(self, dev_ptr: int, frames: int) -> None:
+        self.ctx._ck(self.ctx.lib.nae_eq_put(self.h, dev_ptr, frames))
+
+    def put_host(self, x: np.ndarray) -> None:
+        x = np.ascontiguousarray(x, np.float32)
+        self.ctx._ck(self.ctx.lib.nae_eq_put_host(self.h, x.ctypes.data, x.size // self.ch))
+
+    def flush(self) -> None:
+        self.ctx._ck(self.ctx.lib.nae_eq_flush(self.h))
+
+    def available(self) -> int:
+        return self.ctx.lib.nae_eq_available(self.h)
+
+    def receive(self, dev_ptr: int, max_frames: int) -> int:
+        got = C.c_size_t()
+        self.ctx._ck(self.ctx.lib.nae_eq_receive(self.h, dev_ptr, max_frames, C.byref(got)))
+        return got.value
+
+    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
+        n = self.available() if max_frames is None else max_frames
+        out = np.empty(max(n, 1) * self.ch, np.float32)
+        got = C.c_size_t()
+        self.ctx._ck(self.ctx.lib.nae_eq_receive_host(self.h, out.ctypes.data, n, C.byref(got)))
+        return out[: got.value * self.ch]
+
+    def close(self) -> None:
+        if self.h:
+            self.ctx.lib.nae_eq_destroy(self.h)
             self.h = C.c_void_p()
 
     def __enter__(self):

@@ -1,0 +1,301 @@
+// kernels_eq.hip — K11, the biquad cascade ("K11 biquad cascade") for gfx950: a recurrence computed parallel in time.
+//
+// One wave per stream-channel walks its chunks of C = 64 T samples (T = NAE_EQ_LANE = 16) in order.  A chunk is loaded coalesced (64
+// consecutive samples per load, 4 KiB of f32 per chunk) into LDS; lane l then reads its own T consecutive samples with a stride of T + 1
+// words between lanes, which is odd, so the 32 lanes of a ds_read_b32 group fall on 32 different banks.  Per section the lane runs the
+// recurrence from the zero state over its samples (y0 and the end state e_l), the wave scans the 64 end states in six Kogge-Stone steps with
+// the powers Phi^(2^j) of the T-step state map — the cross-lane moves are __shfl_up of a double, two 32-bit moves each —, and every sample gets
+// the zero-input response of the state its lane starts from: y = y0 + ((p[k] z1) + (q[k] z2)).  The samples stay in registers as doubles from
+// section to section and are rounded once behind the last.  The carry state of section s between chunks is kept by lane s: (z1, z2) in two
+// register pairs, read by a broadcast and replaced by the scan's last value; a handle keeps it in device memory between launches.  Everything
+// that depends on the coefficients — p, q and the six maps — is made on the host in double (eq_make_tables) into a constant block of
+// 16 x (5 + 56) doubles.  The coefficients and the maps are read from it at wave-uniform addresses; p and q of the call's sections are copied
+// into LDS once per launch and read there as broadcasts (read from the block they cost 28 SGPR spills).
+// The translation unit is built with -ffp-contract=off: every step is one IEEE operation, in the order of the CPU statement
+// (tests/eq_ref/ref_eq.c).  It shares no code with the other kernels.
+#include "nae_internal.h"
+#include <math.h>
+#include <string.h>
+
+namespace nae {
+
+constexpr int kEqT = NAE_EQ_LANE, kEqC = NAE_EQ_CHUNK, kEqStride = kEqT + 1;
+constexpr int kEqCoefs = 5, kEqTab = 2 * kEqT + 6 * 4;     // per section: b0 b1 b2 a1 a2 | p[T] q[T] Phi_0 ... Phi_5 (m00 m01 m10 m11 each)
+constexpr int kEqTabOfs = NAE_EQ_MAX_SECTIONS * kEqCoefs;  // the tables stand behind the coefficients of all sections
+constexpr size_t kEqBlockDoubles = (size_t)NAE_EQ_MAX_SECTIONS * (kEqCoefs + kEqTab);
+static_assert(kEqTab == 56 && kEqC == 1024, "DESIGN.md §3, K11: 56 doubles of tables per section, chunks of 1024 samples");
+
+struct EqView { float* base; long long ss, cs, fs; };
+struct EqParams {
+    long long in_len;      // samples of a stream-channel: reads at or past in_len give zero, samples there are not stored
+    long long c_origin;    // chunks [c_origin, c_stop) are computed (a handle continues where it stopped)
+    long long c_stop;
+    long long n_sc;        // stream-channels: one wave each
+    int ch, n_sections;
+};
+
+__device__ __forceinline__ void eq_lds_sync()
+{
+    // this wave's LDS writes before its following LDS reads of other lanes' words: DS operations of one wave execute in issue order
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// state: [n_sc][NAE_EQ_MAX_SECTIONS][2] doubles, the carry (z1, z2) of every section in front of chunk c_origin, replaced by the one behind chunk
+// c_stop - 1; null: zero in, nothing out (the block call)
+__global__ __launch_bounds__(64) void eq_cascade_kernel(EqView src, EqView out, EqParams p, const double* __restrict__ tab, double* state)
+{
+    __shared__ float stage[kEqC + 64];
+    __shared__ double pq[NAE_EQ_MAX_SECTIONS * 2 * kEqT];  // p and q of every section: read at wave-uniform addresses (a broadcast)
+    const int lane = threadIdx.x;
+    const long long sc = blockIdx.x;
+    if (sc >= p.n_sc) return;
+    for (int i = lane; i < p.n_sections * 2 * kEqT; i += 64) pq[i] = tab[kEqTabOfs + (i / (2 * kEqT)) * kEqTab + (i % (2 * kEqT))];
+    eq_lds_sync();
+    const long long s_idx = sc / p.ch;
+    const int c = (int)(sc % p.ch);
+    const float* ip = src.base + s_idx * src.ss + c * src.cs;
+    float* op = out.base + s_idx * out.ss + c * out.cs;
+    const int S = p.n_sections;
+
+    double st1 = 0.0, st2 = 0.0;                           // lane s: the carry of section s
+    if (state && lane < S) {
+        st1 = state[(sc * NAE_EQ_MAX_SECTIONS + lane) * 2];
+        st2 = state[(sc * NAE_EQ_MAX_SECTIONS + lane) * 2 + 1];
+    }
+#pragma unroll 1
+    for (long long ck = p.c_origin; ck < p.c_stop; ck++) {
+        const long long n0 = ck * kEqC;
+#pragma unroll
+        for (int j = 0; j < kEqT; j++) {
+            const int n = j * 64 + lane;
+            const long long g = n0 + n;
+            stage[n + (n >> 4)] = g < p.in_len ? ip[g * src.fs] : 0.0f;
+        }
+        eq_lds_sync();
+        double x[kEqT];
+#pragma unroll
+        for (int k = 0; k < kEqT; k++) x[k] = (double)stage[lane * kEqStride + k];
+#pragma unroll 1
+        for (int s = 0; s < S; s++) {
+            const double* cf = tab + s * kEqCoefs;
+            const double* t = pq + s * 2 * kEqT;
+            const double b0 = cf[0], b1 = cf[1], b2 = cf[2], a1 = cf[3], a2 = cf[4];
+            // 1: the zero-state pass
+            double z1 = 0.0, z2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < kEqT; k++) {
+                const double xv = x[k];
+                const double y = b0 * xv + z1;
+                z1 = (b1 * xv - a1 * y) + z2;
+                z2 = b2 * xv - a2 * y;
+                x[k] = y;
+            }
+            // 3: the carry.  E_0 takes the chunk's carry-in, then six steps, each reading the previous step's values
+            const double in1 = __shfl(st1, s), in2 = __shfl(st2, s);
+            const double* ph = tab + kEqTabOfs + s * kEqTab + 2 * kEqT;
+            if (lane == 0) {
+                const double e1 = z1 + ((ph[0] * in1) + (ph[1] * in2));
+                const double e2 = z2 + ((ph[2] * in1) + (ph[3] * in2));
+                z1 = e1;
+                z2 = e2;
+            }
+#pragma unroll
+            for (int j = 0; j < 6; j++) {
+                const double u1 = __shfl_up(z1, 1u << j), u2 = __shfl_up(z2, 1u << j);
+                const double e1 = z1 + ((ph[4 * j] * u1) + (ph[4 * j + 1] * u2));
+                const double e2 = z2 + ((ph[4 * j + 2] * u1) + (ph[4 * j + 3] * u2));
+                if (lane >= (1 << j)) {
+                    z1 = e1;
+                    z2 = e2;
+                }
+            }
+            double s1 = __shfl_up(z1, 1u), s2 = __shfl_up(z2, 1u);
+            if (lane == 0) {
+                s1 = in1;
+                s2 = in2;
+            }
+            const double o1 = __shfl(z1, 63), o2 = __shfl(z2, 63);
+            if (lane == s) {
+                st1 = o1;
+                st2 = o2;
+            }
+            // 4: the correction; y is the next section's input
+#pragma unroll
+            for (int k = 0; k < kEqT; k++) x[k] = x[k] + ((t[k] * s1) + (t[kEqT + k] * s2));
+        }
+        // the lanes read their own words above and write only them here; the coalesced read below needs the other lanes' words
+#pragma unroll
+        for (int k = 0; k < kEqT; k++) stage[lane * kEqStride + k] = (float)x[k];
+        eq_lds_sync();
+#pragma unroll
+        for (int j = 0; j < kEqT; j++) {
+            const int n = j * 64 + lane;
+            const long long g = n0 + n;
+            if (g < p.in_len) op[g * out.fs] = stage[n + (n >> 4)];
+        }
+        eq_lds_sync();                                     // the next chunk rewrites the stage
+    }
+    if (state && lane < S) {
+        state[(sc * NAE_EQ_MAX_SECTIONS + lane) * 2] = st1;
+        state[(sc * NAE_EQ_MAX_SECTIONS + lane) * 2 + 1] = st2;
+    }
+}
+
+} // namespace nae
+
+// ================================================================================================ host side
+using namespace nae;
+
+size_t nae_eq_block_doubles() { return kEqBlockDoubles; }
+
+// the one statement of the parameter rules of nae_eq_block_f32 and nae_eq_create (ctx may be null: no message then)
+int nae_eq_check(nae_ctx* ctx, const double* coef, int n_sections, int ch)
+{
+    const auto fail = [&](int code, const char* what) { return ctx ? nae_fail(ctx, code, what) : code; };
+    if (!coef) return fail(NAE_ERR_INVALID, "eq: null pointer");
+    if (n_sections < 1) return fail(NAE_ERR_INVALID, "eq: n_sections must be at least 1");
+    if (ch != 1 && ch != 2) return fail(NAE_ERR_INVALID, "channel count must be 1 or 2");
+    if (n_sections > NAE_EQ_MAX_SECTIONS) return fail(NAE_ERR_UNSUPPORTED, "eq: at most 16 sections");
+    for (int s = 0; s < n_sections; s++) {
+        const double* c = coef + 5 * s;
+        for (int i = 0; i < 5; i++)
+            if (!isfinite(c[i])) return fail(NAE_ERR_INVALID, "eq: non-finite coefficient");
+        if (!(fabs(c[4]) < 1.0 && fabs(c[3]) < 1.0 + c[4])) return fail(NAE_ERR_INVALID, "eq: section is not strictly stable");
+    }
+    return NAE_OK;
+}
+
+// DESIGN.md §3, "K11 biquad cascade", step 2: the constant block of a cascade, in double and in the literal order of the zero-input recurrence
+static void eq_make_tables(const double* coef, int n_sections, double* blk)
+{
+    memset(blk, 0, kEqBlockDoubles * sizeof(double));
+    for (int s = 0; s < n_sections; s++) {
+        const double a1 = coef[5 * s + 3], a2 = coef[5 * s + 4];
+        memcpy(blk + s * kEqCoefs, coef + 5 * s, 5 * sizeof(double));
+        double* t = blk + kEqTabOfs + s * kEqTab;
+        double* ph = t + 2 * kEqT;
+        for (int col = 0; col < 2; col++) {
+            double z1 = col == 0 ? 1.0 : 0.0, z2 = col == 0 ? 0.0 : 1.0;
+            for (int n = 0; n < kEqT; n++) {
+                const double y = z1;
+                z1 = -a1 * y + z2;
+                z2 = -a2 * y;
+                t[col * kEqT + n] = y;
+            }
+            ph[col] = z1;          // Phi: the two end states as columns, stored m00 m01 m10 m11
+            ph[2 + col] = z2;
+        }
+        for (int j = 1; j < 6; j++) {
+            const double* m = ph + 4 * (j - 1);
+            double* r = ph + 4 * j;
+            r[0] = (m[0] * m[0]) + (m[1] * m[2]);
+            r[1] = (m[0] * m[1]) + (m[1] * m[3]);
+            r[2] = (m[2] * m[0]) + (m[3] * m[2]);
+            r[3] = (m[2] * m[1]) + (m[3] * m[3]);
+        }
+    }
+}
+
+// the constant block of checked coefficients into d_block (nae_eq_block_doubles() doubles); waits for the upload
+int nae_eq_make_block(nae_ctx* ctx, const double* coef, int n_sections, double* d_block)
+{
+    std::vector<double> blk(kEqBlockDoubles);
+    eq_make_tables(coef, n_sections, blk.data());
+    (void)nae_use_device(ctx);
+    hipError_t e = hipMemcpyAsync(d_block, blk.data(), kEqBlockDoubles * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? NAE_OK : nae_check(ctx, e, "eq: table upload");
+}
+
+// chunks [c_origin, c_stop) of n_streams x ch signals of in_len samples (absolute indexing); d_state as the kernel's
+int nae_launch_eq(nae_ctx* ctx, const double* d_block, int n_sections, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                  const nae_sig* dst, size_t c_origin, size_t c_stop, double* d_state)
+{
+    if (c_stop <= c_origin || n_streams == 0) return NAE_OK;
+    const size_t n_sc = n_streams * (size_t)ch;
+    if (n_sc > 0x7fffffffull) return nae_fail(ctx, NAE_ERR_INVALID, "eq_cascade_kernel: grid too large");
+    EqParams p;
+    p.in_len = (long long)in_len;
+    p.c_origin = (long long)c_origin;
+    p.c_stop = (long long)c_stop;
+    p.n_sc = (long long)n_sc;
+    p.ch = ch;
+    p.n_sections = n_sections;
+    const EqView sv{static_cast<float*>(src->base), (long long)src->stream_stride, (long long)src->chan_stride, (long long)src->frame_stride};
+    const EqView ov{static_cast<float*>(dst->base), (long long)dst->stream_stride, (long long)dst->chan_stride, (long long)dst->frame_stride};
+    NAE_KLAUNCH(ctx, "eq_cascade_kernel", eq_cascade_kernel, dim3((unsigned)n_sc), dim3(64), 0, ctx->stream, sv, ov, p, d_block, d_state);
+    return nae_check(ctx, hipGetLastError(), "eq_cascade_kernel");
+}
+
+void nae_eq_cache_free(nae_ctx* ctx)
+{
+    if (ctx->d_eq_block) (void)hipFree(ctx->d_eq_block);
+    ctx->d_eq_block = nullptr;
+    ctx->h_eq_coef.clear();
+}
+
+extern "C" {
+
+int nae_eq_block_f32(nae_ctx* ctx, const double* coef_host, int n_sections, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                     const nae_sig* dst)
+{
+    if (!ctx) return NAE_ERR_INVALID;
+    if (!coef_host || !src || !dst) return nae_fail(ctx, NAE_ERR_INVALID, "eq: null pointer");
+    int rc = nae_eq_check(ctx, coef_host, n_sections, ch);
+    if (rc) return rc;
+    if (in_len == 0 || n_streams == 0) return NAE_OK;
+    if (!src->base || !dst->base) return nae_fail(ctx, NAE_ERR_INVALID, "eq: null pointer");
+    (void)nae_use_device(ctx);
+    // the tables are kept with the context: a call with the coefficients of the last one uploads nothing
+    const size_t n_coef = (size_t)n_sections * 5;
+    const bool same = ctx->d_eq_block && ctx->h_eq_coef.size() == n_coef && memcmp(ctx->h_eq_coef.data(), coef_host, n_coef * sizeof(double)) == 0;
+    if (!same) {
+        if (!ctx->d_eq_block && hipMalloc((void**)&ctx->d_eq_block, kEqBlockDoubles * sizeof(double)) != hipSuccess)
+            return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(eq tables)");
+        ctx->h_eq_coef.clear();                            // the upload is ordered on the stream behind a launch that still reads the last block
+        if ((rc = nae_eq_make_block(ctx, coef_host, n_sections, ctx->d_eq_block))) return rc;
+        ctx->h_eq_coef.assign(coef_host, coef_host + n_coef);
+    }
+    return nae_launch_eq(ctx, ctx->d_eq_block, n_sections, src, in_len, ch, n_streams, dst, 0, (in_len + kEqC - 1) / kEqC, nullptr);
+}
+
+// DESIGN.md §3, "K11 biquad cascade", "Design": the Audio EQ Cookbook's forms in double, divided through by a0
+int nae_eq_design(int kind, int sample_rate, double freq, double gain_db, double q, double coef_host[5])
+{
+    if (!coef_host || kind < NAE_EQ_PEAK || kind > NAE_EQ_NOTCH || sample_rate <= 0) return NAE_ERR_INVALID;
+    if (!(freq > 0.0 && freq < 0.5 * (double)sample_rate)) return NAE_ERR_INVALID;
+    if (!(q >= NAE_EQ_MIN_Q && q <= NAE_EQ_MAX_Q)) return NAE_ERR_INVALID;
+    if (!(fabs(gain_db) <= NAE_EQ_MAX_GAIN_DB)) return NAE_ERR_INVALID;
+    const double pi = 3.14159265358979323846;
+    const double A = pow(10.0, gain_db / 40.0);
+    const double w0 = 2.0 * pi * freq / (double)sample_rate;
+    const double cs = cos(w0), alpha = sin(w0) / (2.0 * q);
+    double b0, b1, b2, a0, a1, a2;
+    if (kind == NAE_EQ_PEAK) {
+        b0 = 1.0 + alpha * A; b1 = -2.0 * cs; b2 = 1.0 - alpha * A;
+        a0 = 1.0 + alpha / A; a1 = -2.0 * cs; a2 = 1.0 - alpha / A;
+    } else if (kind == NAE_EQ_LOWSHELF) {
+        const double r = 2.0 * sqrt(A) * alpha;
+        b0 = A * ((A + 1.0) - (A - 1.0) * cs + r); b1 = 2.0 * A * ((A - 1.0) - (A + 1.0) * cs); b2 = A * ((A + 1.0) - (A - 1.0) * cs - r);
+        a0 = (A + 1.0) + (A - 1.0) * cs + r; a1 = -2.0 * ((A - 1.0) + (A + 1.0) * cs); a2 = (A + 1.0) + (A - 1.0) * cs - r;
+    } else if (kind == NAE_EQ_HIGHSHELF) {
+        const double r = 2.0 * sqrt(A) * alpha;
+        b0 = A * ((A + 1.0) + (A - 1.0) * cs + r); b1 = -2.0 * A * ((A - 1.0) + (A + 1.0) * cs); b2 = A * ((A + 1.0) + (A - 1.0) * cs - r);
+        a0 = (A + 1.0) - (A - 1.0) * cs + r; a1 = 2.0 * ((A - 1.0) - (A + 1.0) * cs); a2 = (A + 1.0) - (A - 1.0) * cs - r;
+    } else {
+        a0 = 1.0 + alpha; a1 = -2.0 * cs; a2 = 1.0 - alpha;
+        if (kind == NAE_EQ_LOWPASS) { b0 = (1.0 - cs) / 2.0; b1 = 1.0 - cs; b2 = (1.0 - cs) / 2.0; }
+        else if (kind == NAE_EQ_HIGHPASS) { b0 = (1.0 + cs) / 2.0; b1 = -(1.0 + cs); b2 = (1.0 + cs) / 2.0; }
+        else { b0 = 1.0; b1 = -2.0 * cs; b2 = 1.0; }
+    }
+    coef_host[0] = b0 / a0;
+    coef_host[1] = b1 / a0;
+    coef_host[2] = b2 / a0;
+    coef_host[3] = a1 / a0;
+    coef_host[4] = a2 / a0;
+    return NAE_OK;
+}
+
+} // extern "C"

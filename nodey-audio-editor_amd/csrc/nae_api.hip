@@ -358,6 +358,7 @@ int nae_ctx_destroy(nae_ctx* ctx)
     nae_wsola_cache_free(ctx);
     nae_fir_cache_free(ctx);
     nae_conv_cache_free(ctx);
+    nae_eq_cache_free(ctx);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return NAE_OK;

@@ -42,6 +42,9 @@ struct nae_ctx {
     float* d_conv_spec = nullptr; size_t conv_spec_floats = 0; int conv_spec_n_fft = 0, conv_spec_taps_ch = 0;
     std::vector<float> h_conv_taps;
     void* ws_conv = nullptr; size_t ws_conv_bytes = 0;
+    // nae_eq_block_f32 keeps the last call's coefficients and their constant block (kernels_eq.hip)
+    double* d_eq_block = nullptr;
+    std::vector<double> h_eq_coef;
     // tuning / A-B switches: nae_debug_set(ctx, key, value) (include/nae_gpu.h lists the keys; NAE_DEBUG="key=value,..." applies them at context creation)
     bool dbg_st_unfused = false;     // st_unfused: WSOLA chain runs filter and cubic stage as separate launches
     int dbg_td_nc = 0;               // td_nc = 1|2|4: candidates per thread of the WSOLA search (0: by batch size)
@@ -250,6 +253,19 @@ int nae_launch_conv(nae_ctx* ctx, int n_fft, int parts, int taps_ch, const float
 int nae_pick_conv_tile(nae_ctx* ctx, int n_fft);
 size_t nae_pick_conv_ring(nae_ctx* ctx, int n_fft, int parts, size_t blocks, size_t n_sc);
 void nae_conv_cache_free(nae_ctx* ctx);
+
+// kernels_eq.hip: the biquad cascade ("K11 biquad cascade").  nae_eq_check: the parameter rules of the block call and the handle (a
+// null pointer, n_sections < 1, ch not 1 / 2, a non-finite coefficient or a section that is not strictly stable NAE_ERR_INVALID; more than
+// NAE_EQ_MAX_SECTIONS sections NAE_ERR_UNSUPPORTED).  A constant block holds nae_eq_block_doubles() doubles: the coefficients [16][5], then per
+// section p[16], q[16] and the six state maps (nae_eq_make_block, which waits for the upload).  nae_launch_eq runs chunks [c_origin, c_stop) of
+// absolutely indexed signals; d_state, [stream-channel][16][2] doubles, is the carry in front of c_origin and receives the one behind c_stop - 1
+// (null: zero, and nothing kept).
+size_t nae_eq_block_doubles();
+int nae_eq_check(nae_ctx* ctx, const double* coef, int n_sections, int ch);
+int nae_eq_make_block(nae_ctx* ctx, const double* coef, int n_sections, double* d_block);
+int nae_launch_eq(nae_ctx* ctx, const double* d_block, int n_sections, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                  const nae_sig* dst, size_t c_origin, size_t c_stop, double* d_state);
+void nae_eq_cache_free(nae_ctx* ctx);
 
 // kernels_nodes.hip
 int nae_launch_copy_sig(nae_ctx* ctx, const nae_sig* src, const nae_sig* dst, size_t S, int ch, size_t n_streams,

@@ -62,7 +62,39 @@ struct nae_conv {
     bool flushed = false;
 };
 
+// the biquad cascade's handle ("K11 biquad cascade"): whole chunks of NAE_EQ_CHUNK samples are filtered as they fill; the sections'
+// carry between two launches stays on the device
+struct nae_eq {
+    nae_ctx* ctx;
+    int ch, n_sections;
+    double* d_block = nullptr;     // coefficients and tables (nae_eq_make_block)
+    double* d_state = nullptr;     // [ch][NAE_EQ_MAX_SECTIONS][2]: every section's (z1, z2) behind the last chunk done
+    DevFifo in;                    // interleaved input, from the first sample of the next chunk on
+    DevFifo out;                   // interleaved result
+    size_t chunks_done = 0, out_read = 0;
+    bool flushed = false;
+};
+
 namespace {
+
+// the chunks that became computable: every whole chunk, and after the flush the partial one at the end
+int eq_process(nae_eq* h)
+{
+    nae_ctx* ctx = h->ctx;
+    const size_t C = NAE_EQ_CHUNK;
+    const size_t chunks = h->flushed ? (h->in.total + C - 1) / C : h->in.total / C;
+    if (chunks <= h->chunks_done) return NAE_OK;
+    const size_t produced = h->flushed ? h->in.total : chunks * C;
+    int rc = h->out.reserve(ctx, produced);
+    if (rc) return rc;
+    const nae_sig src = h->in.view(), dst = h->out.view();
+    rc = nae_launch_eq(ctx, h->d_block, h->n_sections, &src, h->in.total, h->ch, 1, &dst, h->chunks_done, chunks, h->d_state);
+    if (rc) return rc;
+    h->out.total = produced;
+    h->chunks_done = chunks;
+    h->in.drop((long long)(chunks * C));
+    return NAE_OK;
+}
 
 int conv_process(nae_conv* h)
 {
@@ -646,6 +678,94 @@ int nae_conv_destroy(nae_conv* h)
     h->out.free();
     if (h->d_spec) (void)hipFree(h->d_spec);
     if (h->d_ring) (void)hipFree(h->d_ring);
+    delete h;
+    return NAE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ biquad cascade
+int nae_eq_create(nae_ctx* ctx, const double* coef_host, int n_sections, int channels, nae_eq** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_eq_check(ctx, coef_host, n_sections, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_eq* s = new (std::nothrow) nae_eq();
+    if (!s) return NAE_ERR_NOMEM;
+    s->ctx = ctx;
+    s->ch = channels;
+    s->n_sections = n_sections;
+    s->in.width = s->out.width = (size_t)channels;
+    const size_t state_bytes = (size_t)channels * NAE_EQ_MAX_SECTIONS * 2 * sizeof(double);
+    if (hipMalloc((void**)&s->d_block, nae_eq_block_doubles() * sizeof(double)) != hipSuccess ||
+        hipMalloc((void**)&s->d_state, state_bytes) != hipSuccess) {
+        if (s->d_block) (void)hipFree(s->d_block);
+        delete s;
+        return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(eq tables)");
+    }
+    const hipError_t e = hipMemsetAsync(s->d_state, 0, state_bytes, ctx->stream);
+    rc = e != hipSuccess ? nae_check(ctx, e, "hipMemsetAsync(eq state)") : nae_eq_make_block(ctx, coef_host, n_sections, s->d_block);
+    if (rc) {
+        (void)hipFree(s->d_block);
+        (void)hipFree(s->d_state);
+        delete s;
+        return rc;
+    }
+    *h = s;
+    return NAE_OK;
+}
+
+static int eq_append(nae_eq* h, const float* p, size_t S, bool host)
+{
+    if (!h || (S && !p)) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (h->flushed) return nae_fail(h->ctx, NAE_ERR_STATE, "put after flush");
+    if (S == 0) return NAE_OK;
+    const int rc = h->in.push(h->ctx, p, S, host);
+    return rc ? rc : eq_process(h);
+}
+
+int nae_eq_put(nae_eq* h, const float* interleaved, size_t S) { return eq_append(h, interleaved, S, false); }
+int nae_eq_put_host(nae_eq* h, const float* interleaved_host, size_t S) { return eq_append(h, interleaved_host, S, true); }
+
+// the partial last chunk comes out: as many frames as were put over the handle's life (an IIR has no tail to append)
+int nae_eq_flush(nae_eq* h)
+{
+    if (!h) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (h->flushed) return NAE_OK;
+    h->flushed = true;
+    return eq_process(h);
+}
+
+size_t nae_eq_available(nae_eq* h) { return h ? h->out.total - h->out_read : 0; }
+
+static int eq_take(nae_eq* h, float* dst, size_t max_frames, size_t* got, bool host)
+{
+    if (!h || !got || (max_frames && !dst)) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    size_t n = h->out.total - h->out_read;
+    if (n > max_frames) n = max_frames;
+    *got = n;
+    if (n == 0) return NAE_OK;
+    const int rc = h->out.pop(h->ctx, h->out_read, dst, n, host);
+    if (rc) return rc;
+    h->out_read += n;
+    return NAE_OK;
+}
+
+int nae_eq_receive(nae_eq* h, float* dst, size_t max_frames, size_t* got) { return eq_take(h, dst, max_frames, got, false); }
+int nae_eq_receive_host(nae_eq* h, float* dst_host, size_t max_frames, size_t* got) { return eq_take(h, dst_host, max_frames, got, true); }
+
+int nae_eq_destroy(nae_eq* h)
+{
+    if (!h) return NAE_OK;
+    (void)nae_use_device(h->ctx);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    h->in.free();
+    h->out.free();
+    if (h->d_block) (void)hipFree(h->d_block);
+    if (h->d_state) (void)hipFree(h->d_state);
     delete h;
     return NAE_OK;
 }

@@ -149,4 +149,6 @@ namespace infra
 	void register_extension_processors();
 	// the effect nodes (audio_reverb): called after the two above, each of which stays the list it was
 	void register_effect_processors();
+	// the equalizer (audio_eq): called after the three above, each of which stays the list it was
+	void register_equalizer_processors();
 }

@@ -1,6 +1,7 @@
 #include "audio-velocity.hpp"
 #include "audio-filter.hpp"
 #include "audio-reverb.hpp"
+#include "audio-eq.hpp"
 #include "gpu-context.hpp"
 #include "velocity-cadence.hpp"
 
@@ -1043,6 +1044,221 @@ namespace processor
 			size_t total = 0;
 			float* samples = upload_as_f32(batch, h_raw, d_raw, d_f32, &total);
 			gpu::check(nae_conv_put(conv, samples, total), "nae_conv_put");
+			deliver();
+		}
+		for (auto& stream : output_stream) stream->set_eof();
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_eq
+	infra::Processor::Info Audio_eq::get_processor_info()
+	{
+		return {"audio_eq", "Audio Equalizer", false, [] { return std::unique_ptr<infra::Processor>(new Audio_eq); },
+				"Parametric equalizer: up to 16 peaking, shelving, low-pass, high-pass and notch bands as a biquad cascade in double (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_eq::get_pin_attributes() const
+	{
+		return {
+			{"output", "Output", typeid(Audio_stream), false, [] { return std::make_shared<Audio_stream>(); }},
+			{"input", "Input", typeid(Audio_stream), true, [] { return std::make_shared<Audio_stream>(); }}
+		};
+	}
+
+	static const char* const eq_kind_names[] = {"peak", "lowshelf", "highshelf", "lowpass", "highpass", "notch"};
+
+	Json::Value Audio_eq::serialize() const
+	{
+		Json::Value value;
+		if (bands.empty()) return value;
+		Json::Value list(Json::arrayValue);
+		for (const Band& b : bands)
+		{
+			Json::Value v;
+			if (b.kind != Kind::Peak) v["kind"] = eq_kind_names[(int)b.kind];
+			if (b.freq != Band::default_freq) v["freq"] = b.freq;
+			if (b.gain_db != Band::default_gain_db) v["gain_db"] = b.gain_db;
+			if (b.q != Band::default_q) v["q"] = b.q;
+			list.append(v);
+		}
+		value["bands"] = list;
+		return value;
+	}
+
+	void Audio_eq::deserialize(const Json::Value& value)
+	{
+		const auto wrong = [](const char* field) {
+			return Runtime_error(
+				"Failed to deserialize JSON file",
+				"Audio_eq failed to serialize the JSON input because of missing or invalid fields.",
+				std::string("Wrong field: ") + field
+			);
+		};
+		// everything is read and checked first: a rejected value leaves the node as it was
+		std::vector<Band> read;
+		if (value.isMember("bands"))
+		{
+			const Json::Value& list = value["bands"];
+			if (!list.isArray() || list.size() > max_bands) throw wrong("bands");
+			for (int i = 0; i < (int)list.size(); i++)
+			{
+				const Json::Value& v = list[i];
+				if (v.isArray() || v.isDouble() || v.isBool() || v.isString()) throw wrong("bands");   // an object, possibly without a key
+				Band b;
+				if (v.isMember("kind"))
+				{
+					if (!v["kind"].isString()) throw wrong("kind");
+					int k = 0;
+					while (k < 6 && v["kind"].asString() != eq_kind_names[k]) k++;
+					if (k == 6) throw wrong("kind");
+					b.kind = (Kind)k;
+				}
+				const auto real = [&](const char* key, double lo, double hi, double fallback) {
+					if (!v.isMember(key)) return fallback;
+					if (!v[key].isDouble() || !(v[key].asDouble() >= lo && v[key].asDouble() <= hi)) throw wrong(key);
+					return v[key].asDouble();
+				};
+				b.freq = real("freq", 0.0, 1e9, Band::default_freq);
+				if (!(b.freq > 0.0)) throw wrong("freq");
+				b.gain_db = real("gain_db", -24.0, 24.0, Band::default_gain_db);
+				b.q = real("q", 0.1, 40.0, Band::default_q);
+				read.push_back(b);
+			}
+		}
+		bands = std::move(read);
+	}
+
+	void Audio_eq::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
+		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
+		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
+		if (!input_item.has_value())
+			throw Runtime_error("Audio Equalizer has no input", "Audio Equalizer requires an audio stream input to function properly.", "Input item 'input' not found");
+		Audio_stream& input_stream = input_item.value().get();
+		if (bands.empty())
+		{
+			// a wire: the frames pass as they are
+			while (!stop_token)
+			{
+				const auto pop_result = input_stream.try_pop();
+				if (!pop_result.has_value())
+				{
+					if (input_stream.eof()) break;
+					nae_fiber::this_fiber::yield();
+					continue;
+				}
+				for (auto& stream : output_stream)
+					while (!stop_token && stream->try_push(pop_result.value()) != channel_op_status::success) nae_fiber::this_fiber::yield();
+			}
+			for (auto& stream : output_stream) stream->set_eof();
+			return;
+		}
+		nae_ctx* ctx = gpu::context();
+		nae_eq* eq = nullptr;
+		struct Guard { nae_eq*& h; ~Guard() { if (h) nae_eq_destroy(h); } } guard{eq};
+		gpu::Device_buffer d_raw, d_f32, d_out;
+		gpu::Pinned_buffer h_raw, h_out;
+		int ch = 0;
+		struct Shape { int nb_samples, sample_rate; int64_t pts; decltype(Frame_data::time_base) time_base; };
+		std::deque<Shape> shapes;     // the input frames whose output is still owed
+		std::vector<float> ready;     // filtered samples, interleaved, not yet cut into frames
+		size_t ready_pos = 0;         // frames of `ready` already delivered
+		std::shared_ptr<const Audio_frame> held;  // popped, but with another channel count than the batch in front of it
+
+		// everything the handle has ready comes down behind ONE wait and leaves as frames of the input's sizes
+		const auto deliver = [&]()
+		{
+			const size_t avail = nae_eq_available(eq);
+			if (avail == 0) { gpu::wait(stop_token); return; }
+			float* dev = static_cast<float*>(d_out.reserve(avail * ch * sizeof(float)));
+			float* host = static_cast<float*>(h_out.reserve(avail * ch * sizeof(float)));
+			size_t got = 0;
+			gpu::check(nae_eq_receive(eq, dev, avail, &got), "nae_eq_receive");
+			gpu::check(nae_memcpy_d2h(ctx, host, dev, got * ch * sizeof(float)), "d2h");
+			gpu::wait(stop_token);
+			ready.erase(ready.begin(), ready.begin() + ready_pos * ch);
+			ready_pos = 0;
+			ready.insert(ready.end(), host, host + got * ch);
+			while (!shapes.empty() && !stop_token && ready.size() / ch - ready_pos >= (size_t)shapes.front().nb_samples)
+			{
+				const Shape s = shapes.front();
+				shapes.pop_front();
+				auto out = std::make_shared<Audio_frame>();
+				Frame_data* o = out->data();
+				o->format = AV_SAMPLE_FMT_FLT;
+				o->sample_rate = s.sample_rate;
+				o->nb_samples = s.nb_samples;
+				o->ch_layout.nb_channels = ch;
+				o->time_base = s.time_base;
+				o->pts = s.pts;
+				frame_get_buffer(o, 32);
+				std::memcpy(o->data[0], ready.data() + ready_pos * ch, (size_t)s.nb_samples * ch * sizeof(float));
+				ready_pos += s.nb_samples;
+				for (auto& stream : output_stream)
+					while (!stop_token && stream->try_push(out) != channel_op_status::success) nae_fiber::this_fiber::yield();
+			}
+		};
+
+		while (!stop_token)
+		{
+			constexpr size_t max_batch = 16;   // as the filter node: every frame that is already waiting is put as one block
+			std::vector<std::shared_ptr<const Audio_frame>> batch;
+			if (held) batch.push_back(std::move(held));
+			held.reset();
+			bool ended = false;
+			while (batch.size() < max_batch)
+			{
+				const auto pop_result = input_stream.try_pop();
+				if (!pop_result.has_value())
+				{
+					ended = input_stream.eof();
+					break;
+				}
+				if (!batch.empty() && pop_result.value()->data()->ch_layout.nb_channels != batch.front()->data()->ch_layout.nb_channels)
+				{
+					held = pop_result.value();
+					break;
+				}
+				batch.push_back(pop_result.value());
+			}
+			if (batch.empty())
+			{
+				if (!ended)
+				{
+					nae_fiber::this_fiber::yield();
+					continue;
+				}
+				if (eq != nullptr)
+				{
+					// the partial last chunk comes out with the flush: an IIR has no tail, so every frame still owed is complete
+					gpu::check(nae_eq_flush(eq), "nae_eq_flush");
+					deliver();
+				}
+				break;
+			}
+			const Frame_data* frame = batch.front()->data();
+			if (eq == nullptr)
+			{
+				ch = frame->ch_layout.nb_channels;
+				if (ch != 1 && ch != 2) throw Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
+				std::vector<double> coef(bands.size() * 5);
+				for (size_t i = 0; i < bands.size(); i++)
+					if (nae_eq_design((int)bands[i].kind, frame->sample_rate, bands[i].freq, bands[i].gain_db, bands[i].q, coef.data() + 5 * i) != NAE_OK)
+						throw Runtime_error("Invalid equalizer band", "A band's frequency must lie below half the stream's sample rate.",
+											infra::fmt("band %d: %g Hz at %d Hz", (int)i, bands[i].freq, frame->sample_rate));
+				gpu::check(nae_eq_create(ctx, coef.data(), (int)bands.size(), ch, &eq), "nae_eq_create");
+			}
+			else if (frame->ch_layout.nb_channels != ch)
+				throw Runtime_error("Channel count changed", "The equalizer runs one stream of a fixed channel count.",
+									infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, ch));
+			for (const auto& f : batch) shapes.push_back({f->data()->nb_samples, f->data()->sample_rate, f->data()->pts, f->data()->time_base});
+			size_t total = 0;
+			float* samples = upload_as_f32(batch, h_raw, d_raw, d_f32, &total);
+			gpu::check(nae_eq_put(eq, samples, total), "nae_eq_put");
 			deliver();
 		}
 		for (auto& stream : output_stream) stream->set_eof();

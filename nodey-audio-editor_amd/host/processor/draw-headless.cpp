@@ -15,6 +15,7 @@
 
 #include "audio-filter.hpp"
 #include "audio-reverb.hpp"
+#include "audio-eq.hpp"
 #include "audio-mix.hpp"
 #include "audio-velocity.hpp"
 #include "audio-vol.hpp"
@@ -85,6 +86,20 @@ namespace processor
 		predelay_ms = std::clamp(predelay_ms, 0.0, 200.0);
 		wet = std::clamp(wet, 0.0, 1.0);
 		dry = std::clamp(dry, 0.0, 1.0);
+		return false;
+	}
+
+	void Audio_eq::draw_title() {}
+	bool Audio_eq::draw_content(bool)
+	{
+		// what the widgets would keep: at most 16 bands, every value inside its range
+		if (bands.size() > max_bands) bands.resize(max_bands);
+		for (auto& b : bands)
+		{
+			b.freq = std::max(b.freq, 1.0);
+			b.gain_db = std::clamp(b.gain_db, -24.0, 24.0);
+			b.q = std::clamp(b.q, 0.1, 40.0);
+		}
 		return false;
 	}
 }

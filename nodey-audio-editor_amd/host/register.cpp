@@ -5,6 +5,7 @@
 #include "infra/processor.hpp"
 #include "processor/audio-filter.hpp"
 #include "processor/audio-reverb.hpp"
+#include "processor/audio-eq.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -35,4 +36,7 @@ namespace infra
 
 	// the effects built on the long convolution; a call of its own, so register_extension_processors() stays the list it was
 	void register_effect_processors() { register_each<processor::Audio_reverb>(); }
+
+	// the equalizer on the biquad cascade; again a call of its own, so the three lists above stay what they were
+	void register_equalizer_processors() { register_each<processor::Audio_eq>(); }
 }

@@ -1,0 +1,179 @@
+"""K11 biquad cascade on the GPU, bit for bit against the CPU statement (tests/eq_ref/ref_eq.c): every length around the lane and the chunk,
+short and long cascades, every view, a launch of many workgroups, the streaming handle, non-finite and subnormal input, the error codes, and
+the host node (tests/eq_ref/host_eq_node.cpp)."""
+import ctypes as C
+import subprocess
+
+import numpy as np
+import pytest
+
+import eq_ref
+import node_harness
+from eq_gpu import CONFIGS, bits, eq_stream, gpu_eq, noise, statement
+
+pytestmark = pytest.mark.gpu
+
+T, CH = eq_ref.LANE, eq_ref.CHUNK
+LENGTHS = (1, T - 1, T, CH - 1, CH, CH + 1, 3 * CH + 7)
+INVALID, UNSUPPORTED, STATE = -1, -2, -5
+
+
+@pytest.fixture(scope="module")
+def ref():
+    return statement()
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return node_harness.build("eq_ref/host_eq_node.cpp", str(tmp_path_factory.mktemp("host_eq_gpu")))
+
+
+@pytest.mark.parametrize("n_sections", (1, 2, 16))
+@pytest.mark.parametrize("in_len", LENGTHS)
+def test_lengths_cascades_and_views(nae, ctx, ref, in_len, n_sections):
+    """mono and stereo, interleaved and planar on either side, stream_stride 0, 3 streams of distinct content"""
+    coef = eq_ref.cascade(n_sections)
+    rng = np.random.default_rng(1000 * n_sections + in_len)
+    for ch, n_streams, sl, dl, shared in CONFIGS:
+        x = noise(rng, n_streams, in_len, ch, shared)
+        want = eq_ref.run_streams(ref, coef, x)
+        got = gpu_eq(nae, ctx, coef, x, sl, dl, shared, gap=3 if sl == "p" else 0, chan_pad=5 if "p" in (sl, dl) else 0)
+        assert np.array_equal(bits(got), bits(want)), (ch, n_streams, sl, dl, shared, int(np.sum(bits(got) != bits(want))))
+
+
+@pytest.mark.parametrize("in_len", (T - 1, CH + 1, 3 * CH + 7))
+def test_odd_base_address(nae, ctx, ref, in_len):
+    """a base that is 4-byte aligned and no more, on both sides"""
+    coef = eq_ref.cascade(2)
+    rng = np.random.default_rng(in_len)
+    for ch, layout in ((1, "i"), (2, "i"), (2, "p")):
+        x = noise(rng, 3, in_len, ch)
+        for offset in (1, 3):
+            got = gpu_eq(nae, ctx, coef, x, layout, layout, offset=offset, chan_pad=2 if layout == "p" else 0)
+            assert np.array_equal(bits(got), bits(eq_ref.run_streams(ref, coef, x))), (ch, layout, offset)
+
+
+def test_hard_cascade(nae, ctx, ref):
+    """16 sections, four of them 20 Hz / Q 10 / +12 dB bells: the carry over three chunk borders in its worst conditioning"""
+    coef = eq_ref.hard_cascade()
+    x = noise(np.random.default_rng(5), 2, 3 * CH + 7, 2)
+    assert np.array_equal(bits(gpu_eq(nae, ctx, coef, x)), bits(eq_ref.run_streams(ref, coef, x)))
+
+
+def test_larger_launch(nae, ctx, ref):
+    """40 stereo streams x (2 C + 5): 80 waves, each a workgroup of its own"""
+    coef = eq_ref.cascade(4)
+    x = noise(np.random.default_rng(40), 40, 2 * CH + 5, 2)
+    want = eq_ref.run_streams(ref, coef, x)
+    assert np.array_equal(bits(gpu_eq(nae, ctx, coef, x)), bits(want))
+    assert np.array_equal(bits(gpu_eq(nae, ctx, coef, x, "p", "i", chan_pad=1)), bits(want))
+
+
+def test_the_context_keeps_its_tables_and_takes_new_ones(nae, ctx, ref):
+    x = noise(np.random.default_rng(6), 1, CH + 9, 2)
+    a, b = eq_ref.cascade(3), eq_ref.cascade(5)[2:]
+    for coef in (a, a, b, a):
+        assert np.array_equal(bits(gpu_eq(nae, ctx, coef, x)), bits(eq_ref.run_streams(ref, coef, x)))
+
+
+@pytest.mark.parametrize("ch", (1, 2))
+@pytest.mark.parametrize("put", (1, 7, 1023, 1025, 2500))
+def test_handle_equals_the_block_call(nae, ctx, ref, put, ch):
+    """any cut of the input into puts gives the same bits"""
+    in_len = 600 if put == 1 else 3 * CH + 7       # one-frame puts: a partial chunk, released by the flush alone
+    coef = eq_ref.cascade(16 if put == 1025 else 3)
+    x = noise(np.random.default_rng(put), 1, in_len, ch)
+    block = gpu_eq(nae, ctx, coef, x)[0]
+    assert np.array_equal(bits(block), bits(eq_ref.run_streams(ref, coef, x)[0]))
+    got = eq_stream(nae, ctx, coef, x[0], (put,), device=put == 1023)
+    assert got.shape == (in_len, ch) and np.array_equal(bits(got), bits(block))
+
+
+def test_handle_mixed_puts(nae, ctx, ref):
+    coef = eq_ref.cascade(2)
+    x = noise(np.random.default_rng(77), 1, 2 * CH + 300, 2)
+    want = eq_ref.run_streams(ref, coef, x)[0]
+    for puts, device in (((1, 7, 1023, 1025, 2500), False), ((1025, 1, 1022, 7), True), ((CH,), False), ((5 * CH,), True)):
+        assert np.array_equal(bits(eq_stream(nae, ctx, coef, x[0], puts, device)), bits(want)), puts
+
+
+@pytest.mark.parametrize("bad", (np.nan, np.inf, -np.inf))
+def test_non_finite_input_does_not_reach_back(nae, ctx, ref, bad):
+    """a non-finite sample at C + 5: every sample before it has the clean run's bits; from it on the statement's, a NaN for a NaN (its sign
+    and payload differ between the CPU and the GPU)"""
+    i = CH + 5
+    coef = eq_ref.cascade(16)
+    x = noise(np.random.default_rng(9), 2, 2 * CH + 40, 2)
+    clean = gpu_eq(nae, ctx, coef, x)
+    dirty_x = x.copy()
+    dirty_x[0, i, 1] = bad
+    got = gpu_eq(nae, ctx, coef, dirty_x)
+    assert np.array_equal(bits(got[:, :i]), bits(clean[:, :i])), "samples before the non-finite one changed"
+    assert np.array_equal(bits(got[1]), bits(clean[1])) and np.array_equal(bits(got[0, :, 0]), bits(clean[0, :, 0])), "another stream or channel changed"
+    want = eq_ref.run_streams(ref, coef, dirty_x)
+    nan_g, nan_w = np.isnan(got), np.isnan(want)
+    assert np.array_equal(nan_g, nan_w) and not np.isfinite(got[0, i, 1])
+    assert np.array_equal(bits(got)[~nan_g], bits(want)[~nan_w])
+
+
+def test_subnormal_input_is_not_flushed(nae, ctx, ref):
+    """f32 subnormals in, a gain near 1: subnormals out, as the statement's"""
+    coef = np.stack([eq_ref.design("peak", 48000, 1000.0, 0.5, 1.0), eq_ref.design("highshelf", 48000, 8000.0, -0.5, 0.7071)])
+    rng = np.random.default_rng(11)
+    x = (rng.integers(-(1 << 22), 1 << 22, (2, CH + 70, 2)).astype(np.int32) & np.int32(-0x7f800001)).view(np.float32)
+    x = np.ascontiguousarray(x)
+    assert np.all(np.abs(x) < np.finfo(np.float32).tiny) and np.count_nonzero(x) > x.size // 2
+    want = eq_ref.run_streams(ref, coef, x)
+    assert np.count_nonzero(want) > want.size // 2 and np.all(np.abs(want) < 4 * np.finfo(np.float32).tiny), "the statement keeps subnormals"
+    assert np.array_equal(bits(gpu_eq(nae, ctx, coef, x)), bits(want))
+
+
+def test_errors(nae, ctx):
+    lib = ctx.lib
+    d = ctx.array(np.zeros(64, np.float32))
+    sig = nae.Sig(d.ptr, 32, 1, 1)
+    good = eq_ref.cascade(2)
+    block = lambda coef, S, ch=1, src=C.byref(sig), dst=C.byref(sig), n=16, streams=1: lib.nae_eq_block_f32(ctx.h, coef, S, src, n, ch, streams, dst)
+    assert block(good.ctypes.data, 2) == 0
+    assert block(None, 2) == INVALID and block(good.ctypes.data, 2, src=None) == INVALID and block(good.ctypes.data, 2, dst=None) == INVALID
+    assert block(good.ctypes.data, 0) == INVALID and block(good.ctypes.data, -1) == INVALID
+    assert block(good.ctypes.data, 2, ch=0) == INVALID and block(good.ctypes.data, 2, ch=3) == INVALID
+    many = np.tile(good[0], (17, 1))
+    assert block(many.ctypes.data, 16) == 0 and block(many.ctypes.data, 17) == UNSUPPORTED
+    assert block(good.ctypes.data, 2, n=0) == 0 and block(good.ctypes.data, 2, streams=0) == 0, "nothing to do: NAE_OK"
+    h = C.c_void_p()
+    for sec in eq_ref.BAD_SECTIONS:
+        c = np.concatenate([good[0], np.array(sec, np.float64)])
+        assert block(c.ctypes.data, 2) == INVALID, sec
+        assert block(c.ctypes.data, 2, n=0) == INVALID, "checked before the empty call returns"
+        assert lib.nae_eq_create(ctx.h, c.ctypes.data, 2, 2, C.byref(h)) == INVALID and not h.value, sec
+    for sec in eq_ref.GOOD_SECTIONS:
+        c = np.array(sec, np.float64)
+        assert block(c.ctypes.data, 1) == 0, sec
+    assert lib.nae_eq_create(ctx.h, None, 1, 2, C.byref(h)) == INVALID
+    assert lib.nae_eq_create(ctx.h, good.ctypes.data, 0, 2, C.byref(h)) == INVALID
+    assert lib.nae_eq_create(ctx.h, good.ctypes.data, 2, 3, C.byref(h)) == INVALID
+    assert lib.nae_eq_create(ctx.h, many.ctypes.data, 17, 2, C.byref(h)) == UNSUPPORTED and not h.value
+    assert lib.nae_eq_create(ctx.h, good.ctypes.data, 2, 2, None) == INVALID
+    ctx.sync()
+    assert np.array_equal(d.download()[16:32], np.zeros(16, np.float32))
+    d.free()
+
+
+def test_host_node_graph(host):
+    """source -> audio_eq -> sink with 1152-sample frames: the source's frames, sizes and pts; the block call's samples with the designed
+    coefficients"""
+    r = subprocess.run([host, "gpu"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "HOST EQ OK gpu" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+def test_host_node_wire(host):
+    """an absent and an empty "bands" deliver the input's bits"""
+    r = subprocess.run([host, "wire"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "HOST EQ OK wire" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+def test_host_node_band_at_nyquist(host):
+    """a band at half the stream's sample rate is a Runtime_error on the first frame"""
+    r = subprocess.run([host, "nyquist"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "HOST EQ OK nyquist" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
