@@ -49,6 +49,21 @@
 #define NAE_EQ_MIN_Q 0.1
 #define NAE_EQ_MAX_Q 40.0
 #define NAE_EQ_MAX_GAIN_DB 24.0
+/* K12 dynamics ("K12 dynamics"): a compressor / look-ahead limiter in double, tiled in time as K11: a lane runs NAE_DYN_LANE
+ * samples, 64 lanes make a chunk of NAE_DYN_CHUNK samples on a grid that starts at the stream's sample 0; the look-ahead reaches at most
+ * NAE_DYN_MAX_LOOKAHEAD samples, one chunk; a zero sample stands at NAE_DYN_FLOOR_DB.  The tiling is part of the specification. */
+#define NAE_DYN_LANE 16
+#define NAE_DYN_CHUNK (64 * NAE_DYN_LANE)
+#define NAE_DYN_MAX_LOOKAHEAD 1024
+#define NAE_DYN_FLOOR_DB (-1000.0)
+/* nae_dyn_design: the ranges of its arguments (ratio: at least 1, INFINITY a limiter) */
+#define NAE_DYN_MIN_THRESHOLD_DB (-60.0)
+#define NAE_DYN_MAX_THRESHOLD_DB 0.0
+#define NAE_DYN_MAX_KNEE_DB 24.0
+#define NAE_DYN_MAX_ATTACK_S 0.5
+#define NAE_DYN_MIN_RELEASE_S 0.001
+#define NAE_DYN_MAX_RELEASE_S 5.0
+#define NAE_DYN_MAX_MAKEUP_DB 24.0
 /* transient preservation ("Transient preservation"): bin k of frame f rises iff P_f[k] > RISE * P_{f-1}[k] and
  * P_f[k] > FLOOR * N; frame f is "high" iff DEN * (rising bins) >= NUM * (N/2 + 1); an onset is an upward crossing of "high" at f >= 2.
  * RISE is +6 dB: at +3 dB steady white noise crosses 3/8 at N = 512 and 1024 (DESIGN.md gives the numbers). */

@@ -44,7 +44,8 @@ extern "C" {
  *   NAE_STRETCH_TRANSIENTS is; nae_fir_pick_n_fft, nae_fir_block_f32, nae_fir_design and the nae_fir handle (nae_fir_create, _put, _put_host, _flush,
  *   _available, _receive, _receive_host, _destroy): the FIR filter, K9; nae_conv_pick_n_fft, nae_conv_block_f32, nae_conv_reverb_taps,
  *   nae_conv_design_reverb and the nae_conv handle (the same eight entries): the long convolution, K10; nae_eq_design, nae_eq_block_f32 and
- *   the nae_eq handle (the same eight entries): the biquad cascade, K11. */
+ *   the nae_eq handle (the same eight entries): the biquad cascade, K11; nae_dyn_design, nae_dyn_block_f32 and the nae_dyn handle (the same
+ *   eight entries) with the record nae_dyn_params: the dynamics processor, K12. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -69,6 +70,7 @@ typedef struct nae_spectrum nae_spectrum;
 typedef struct nae_fir nae_fir;
 typedef struct nae_conv nae_conv;
 typedef struct nae_eq nae_eq;
+typedef struct nae_dyn nae_dyn;
 
 /* ------------------------------------------------------------------ context / plumbing */
 int nae_abi_version(void);
@@ -553,6 +555,54 @@ int nae_eq_destroy(nae_eq* h);
  * NAE_EQ_LOWPASS, NAE_EQ_HIGHPASS, NAE_EQ_NOTCH (gain_db ignored) of nae_dsp_spec.h.  NAE_ERR_INVALID: an unknown kind, sample_rate <= 0,
  * freq outside (0, sample_rate / 2), q outside [0.1, 40], |gain_db| > 24 or not finite, a null pointer.  No context, no device work. */
 int nae_eq_design(int kind, int sample_rate, double freq, double gain_db, double q, double coef_host[5]);
+
+/* ------------------------------------------------------------------ K12 dynamics
+ * no reference code.  Spec ("K12 dynamics"): a feed-forward compressor / look-ahead limiter in the dB domain with the smooth
+ * decoupled peak detector of Giannoulis, Massberg and Reiss, in double throughout, rounded once to f32.  One detector per stream-channel, or
+ * with link = 1 on a stereo stream one per stream on the larger of the two magnitudes.  Per sample: the level xg = K log2|x| (K = 20 log10 2;
+ * a zero sample stands at NAE_DYN_FLOOR_DB), the static curve's gain-reduction demand r >= 0 (threshold, slope = 1 - 1 / ratio, a quadratic
+ * knee of knee_db), the look-ahead d[n] = max(r[n] ... r[n + lookahead]), the release y1[n] = max(d[n], alpha_release y1[n-1] +
+ * (1 - alpha_release) d[n]), the attack yl[n] = alpha_attack yl[n-1] + (1 - alpha_attack) y1[n], and the gain 2^((makeup_db - yl[n]) / K).
+ * The log2 and the 2^x are fixed sequences of IEEE double operations that DESIGN.md states with their coefficients; the two recurrences are
+ * computed parallel in time on chunks of NAE_DYN_CHUNK samples on a grid from sample 0 (64 lanes of NAE_DYN_LANE samples, a Kogge-Stone scan
+ * of the lanes' step maps), and that tiling is part of the specification.  The call is compensated: output sample n is input sample n under
+ * a gain that has seen `lookahead` samples ahead; input past in_len is zero, in_len frames come out, output past in_len is not stored.
+ * Bit-exact against the CPU statement (tests/dyn_ref/ref_dyn.c); any cut of the input into puts gives the same bits; a non-finite input
+ * sample i leaves every output sample before i - lookahead as it was (from there on the output is unspecified; the call returns NAE_OK).
+ * With slope = 1, knee_db = 0 and alpha_attack = 0 no output exceeds 10^((threshold_db + makeup_db) / 20) but by the final rounding.
+ * Errors: a null pointer, ch not 1 or 2, a parameter that is not finite or outside its range (threshold_db -60 ... 0, slope 0 ... 1,
+ * knee_db 0 ... 24, both alphas in [0, 1), makeup_db -24 ... 24, lookahead >= 0, link 0 or 1): NAE_ERR_INVALID; lookahead above
+ * NAE_DYN_MAX_LOOKAHEAD: NAE_ERR_UNSUPPORTED; in_len = 0 or n_streams = 0: NAE_OK after the checks, nothing is launched.  Views as K11's. */
+typedef struct nae_dyn_params {
+    double threshold_db;    /* dB re full scale, -60 ... 0 */
+    double slope;           /* 1 - 1 / ratio, 0 ... 1; 1 is a limiter */
+    double knee_db;         /* width of the quadratic knee, 0 ... 24 */
+    double alpha_attack;    /* exp(-1 / (attack_s sample_rate)), 0 for no smoothing; [0, 1) */
+    double alpha_release;   /* exp(-1 / (release_s sample_rate)); [0, 1) */
+    double makeup_db;       /* -24 ... 24 */
+    int lookahead;          /* samples, 0 ... NAE_DYN_MAX_LOOKAHEAD */
+    int link;               /* 1: one detector per stereo stream */
+} nae_dyn_params;
+int nae_dyn_block_f32(nae_ctx* ctx, const nae_dyn_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                      const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch).  Before the flush the whole chunks whose look-ahead is complete are available:
+ * floor((put - lookahead) / NAE_DYN_CHUNK) chunks, never negative; nae_dyn_flush releases the rest, so in_len frames come out in all, equal
+ * to the block call's however the input is cut.  A put after the flush: NAE_ERR_STATE. */
+int nae_dyn_create(nae_ctx* ctx, const nae_dyn_params* params, int channels, nae_dyn** h);
+int nae_dyn_put(nae_dyn* h, const float* interleaved, size_t S);
+int nae_dyn_put_host(nae_dyn* h, const float* interleaved_host, size_t S);
+int nae_dyn_flush(nae_dyn* h);
+size_t nae_dyn_available(nae_dyn* h);
+int nae_dyn_receive(nae_dyn* h, float* dst, size_t max_frames, size_t* got);
+int nae_dyn_receive_host(nae_dyn* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_dyn_destroy(nae_dyn* h);
+/* The parameters on the host: slope = 1 - 1 / ratio (ratio = INFINITY: 1), alpha = exp(-1 / (t sample_rate)) (attack_s = 0: 0),
+ * lookahead = lround(lookahead_s sample_rate).  NAE_ERR_INVALID: sample_rate <= 0, link not 0 or 1, a null pointer, an argument that is
+ * not finite (but ratio = INFINITY) or outside threshold_db -60 ... 0, ratio >= 1, knee_db 0 ... 24, attack_s 0 ... 0.5, release_s
+ * 0.001 ... 5, makeup_db -24 ... 24, lookahead_s >= 0 (the constants of nae_dsp_spec.h); NAE_ERR_UNSUPPORTED: a look-ahead above
+ * NAE_DYN_MAX_LOOKAHEAD samples at this rate.  No context, no device work. */
+int nae_dyn_design(int sample_rate, double threshold_db, double ratio, double knee_db, double attack_s, double release_s, double lookahead_s,
+                   double makeup_db, int link, nae_dyn_params* out);
 
 /* ------------------------------------------------------------------ the 4-node graph of BASELINE.json
  * input -> mix(2) -> pitch -> FFT spectrum, one launch sequence over n_streams independent streams.

@@ -40,6 +40,8 @@ EXPORTED_SYMBOLS = [
     "nae_conv_put_host", "nae_conv_flush", "nae_conv_available", "nae_conv_receive", "nae_conv_receive_host", "nae_conv_destroy",
     "nae_eq_design", "nae_eq_block_f32", "nae_eq_create", "nae_eq_put", "nae_eq_put_host", "nae_eq_flush", "nae_eq_available", "nae_eq_receive",
     "nae_eq_receive_host", "nae_eq_destroy",
+    "nae_dyn_design", "nae_dyn_block_f32", "nae_dyn_create", "nae_dyn_put", "nae_dyn_put_host", "nae_dyn_flush", "nae_dyn_available",
+    "nae_dyn_receive", "nae_dyn_receive_host", "nae_dyn_destroy",
 ]
 
 
@@ -87,6 +89,12 @@ class Sig(C.Structure):
         ps = S if plane_stride is None else plane_stride
         ss = 0 if shared else (ps * ch if stream_stride is None else stream_stride)
         return Sig(ptr, ss, ps, 1)
+
+
+class DynParams(C.Structure):
+    """nae_dyn_params: the dynamics processor's parameters (include/nae_gpu.h); nae_dyn_design makes them from times and a ratio"""
+    _fields_ = [("threshold_db", C.c_double), ("slope", C.c_double), ("knee_db", C.c_double), ("alpha_attack", C.c_double),
+                ("alpha_release", C.c_double), ("makeup_db", C.c_double), ("lookahead", C.c_int), ("link", C.c_int)]
 
 
 class StretchPlan(C.Structure):
@@ -203,6 +211,11 @@ def load_library() -> C.CDLL:
         "nae_eq_put": (i, [vp, vp, sz]), "nae_eq_put_host": (i, [vp, vp, sz]), "nae_eq_flush": (i, [vp]),
         "nae_eq_available": (sz, [vp]), "nae_eq_receive": (i, [vp, vp, sz, P(sz)]),
         "nae_eq_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_eq_destroy": (i, [vp]),
+        "nae_dyn_design": (i, [i, d, d, d, d, d, d, d, i, P(DynParams)]), "nae_dyn_block_f32": (i, [vp, P(DynParams), P(Sig), sz, i, sz, P(Sig)]),
+        "nae_dyn_create": (i, [vp, P(DynParams), i, P(vp)]),
+        "nae_dyn_put": (i, [vp, vp, sz]), "nae_dyn_put_host": (i, [vp, vp, sz]), "nae_dyn_flush": (i, [vp]),
+        "nae_dyn_available": (sz, [vp]), "nae_dyn_receive": (i, [vp, vp, sz, P(sz)]),
+        "nae_dyn_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_dyn_destroy": (i, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -612,6 +625,23 @@ class Context:
         coef = np.ascontiguousarray(coef, np.float64).reshape(-1, 5)
         self._ck(self.lib.nae_eq_block_f32(self.h, coef.ctypes.data, coef.shape[0], C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K12
+    @staticmethod
+    def dyn_design(sample_rate: int, threshold_db: float = -18.0, ratio: float = 4.0, knee_db: float = 6.0, attack_s: float = 0.005,
+                   release_s: float = 0.1, lookahead_s: float = 0.0, makeup_db: float = 0.0, link: bool = True) -> "DynParams":
+        """the parameters of the dynamics processor from times and a ratio (nae_dyn_design); ratio = float("inf") is a limiter"""
+        out = DynParams()
+        rc = load_library().nae_dyn_design(sample_rate, threshold_db, ratio, knee_db, attack_s, release_s, lookahead_s, makeup_db, int(link),
+                                           C.byref(out))
+        if rc:
+            raise NaeError(f"nae_dyn_design({sample_rate}, {threshold_db}, {ratio}, {knee_db}, {attack_s}, {release_s}, {lookahead_s}, "
+                           f"{makeup_db}, {link}) failed: {rc}")
+        return out
+
+    def dyn_block(self, params: "DynParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the compressor / limiter `params` over every stream; dst receives in_len frames, compensated for the look-ahead"""
+        self._ck(self.lib.nae_dyn_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     # -- graph
     def graph4(self, g: Graph4):
         self._ck(self.lib.nae_graph4_run(self.h, C.byref(g)))
@@ -789,6 +819,51 @@ class Eq:
     def close(self) -> None:
         if self.h:
             self.ctx.lib.nae_eq_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Dyn:
+    """The dynamics processor's streaming handle (nae_dyn_create): put interleaved f32, flush, receive.  Before the flush the whole chunks
+    whose look-ahead is complete are available; the flush releases the rest."""
+
+    def __init__(self, ctx: Context, params: DynParams, channels: int):
+        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+        ctx._ck(ctx.lib.nae_dyn_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+    def put(self, dev_ptr: int, frames: int) -> None:
+        self.ctx._ck(self.ctx.lib.nae_dyn_put(self.h, dev_ptr, frames))
+
+    def put_host(self, x: np.ndarray) -> None:
+        x = np.ascontiguousarray(x, np.float32)
+        self.ctx._ck(self.ctx.lib.nae_dyn_put_host(self.h, x.ctypes.data, x.size // self.ch))
+
+    def flush(self) -> None:
+        self.ctx._ck(self.ctx.lib.nae_dyn_flush(self.h))
+
+    def available(self) -> int:
+        return self.ctx.lib.nae_dyn_available(self.h)
+
+    def receive(self, dev_ptr: int, max_frames: int) -> int:
+        got = C.c_size_t()
+        self.ctx._ck(self.ctx.lib.nae_dyn_receive(self.h, dev_ptr, max_frames, C.byref(got)))
+        return got.value
+
+    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
+        n = self.available() if max_frames is None else max_frames
+        out = np.empty(max(n, 1) * self.ch, np.float32)
+        got = C.c_size_t()
+        self.ctx._ck(self.ctx.lib.nae_dyn_receive_host(self.h, out.ctypes.data, n, C.byref(got)))
+        return out[: got.value * self.ch]
+
+    def close(self) -> None:
+        if self.h:
+            self.ctx.lib.nae_dyn_destroy(self.h)
             self.h = C.c_void_p()
 
     def __enter__(self):

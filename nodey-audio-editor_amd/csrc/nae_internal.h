@@ -267,6 +267,15 @@ int nae_launch_eq(nae_ctx* ctx, const double* d_block, int n_sections, const nae
                   const nae_sig* dst, size_t c_origin, size_t c_stop, double* d_state);
 void nae_eq_cache_free(nae_ctx* ctx);
 
+// kernels_dyn.hip: the dynamics processor ("K12 dynamics").  nae_dyn_check: the parameter rules of the block call and the handle.
+// nae_dyn_detectors: one per stream with `link` on stereo, else one per stream-channel.  nae_launch_dyn runs chunks [c_origin, c_stop) of
+// absolutely indexed signals and reads up to `lookahead` samples behind them (zero from in_len on); d_state, [detector][2] doubles, holds the
+// carries (y1, yl) in front of c_origin and receives the ones behind c_stop - 1 (null: zero, and nothing kept).
+int nae_dyn_check(nae_ctx* ctx, const nae_dyn_params* p, int ch);
+size_t nae_dyn_detectors(const nae_dyn_params* p, int ch, size_t n_streams);
+int nae_launch_dyn(nae_ctx* ctx, const nae_dyn_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
+                   size_t c_origin, size_t c_stop, double* d_state);
+
 // kernels_nodes.hip
 int nae_launch_copy_sig(nae_ctx* ctx, const nae_sig* src, const nae_sig* dst, size_t S, int ch, size_t n_streams,
                         bool scale, float volume);

@@ -75,7 +75,39 @@ struct nae_eq {
     bool flushed = false;
 };
 
+// the dynamics processor's handle ("K12 dynamics"): whole chunks of NAE_DYN_CHUNK samples are computed once the `lookahead` samples
+// behind them are there; the detectors' carries between two launches stay on the device
+struct nae_dyn {
+    nae_ctx* ctx;
+    int ch;
+    nae_dyn_params params;
+    double* d_state = nullptr;     // [detector][2]: (y1, yl) behind the last chunk done
+    DevFifo in;                    // interleaved input, from the first sample of the next chunk on
+    DevFifo out;                   // interleaved result
+    size_t chunks_done = 0, out_read = 0;
+    bool flushed = false;
+};
+
 namespace {
+
+// the chunks that became computable: every whole chunk whose look-ahead is complete, and after the flush all the rest
+int dyn_process(nae_dyn* h)
+{
+    nae_ctx* ctx = h->ctx;
+    const size_t C = NAE_DYN_CHUNK, la = (size_t)h->params.lookahead;
+    const size_t chunks = h->flushed ? (h->in.total + C - 1) / C : (h->in.total >= la ? (h->in.total - la) / C : 0);
+    if (chunks <= h->chunks_done) return NAE_OK;
+    const size_t produced = h->flushed ? h->in.total : chunks * C;
+    int rc = h->out.reserve(ctx, produced);
+    if (rc) return rc;
+    const nae_sig src = h->in.view(), dst = h->out.view();
+    rc = nae_launch_dyn(ctx, &h->params, &src, h->in.total, h->ch, 1, &dst, h->chunks_done, chunks, h->d_state);
+    if (rc) return rc;
+    h->out.total = produced;
+    h->chunks_done = chunks;
+    h->in.drop((long long)(chunks * C));
+    return NAE_OK;
+}
 
 // the chunks that became computable: every whole chunk, and after the flush the partial one at the end
 int eq_process(nae_eq* h)
@@ -765,6 +797,89 @@ int nae_eq_destroy(nae_eq* h)
     h->in.free();
     h->out.free();
     if (h->d_block) (void)hipFree(h->d_block);
+    if (h->d_state) (void)hipFree(h->d_state);
+    delete h;
+    return NAE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ dynamics
+int nae_dyn_create(nae_ctx* ctx, const nae_dyn_params* params, int channels, nae_dyn** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_dyn_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_dyn* s = new (std::nothrow) nae_dyn();
+    if (!s) return NAE_ERR_NOMEM;
+    s->ctx = ctx;
+    s->ch = channels;
+    s->params = *params;
+    s->in.width = s->out.width = (size_t)channels;
+    const size_t state_bytes = nae_dyn_detectors(params, channels, 1) * 2 * sizeof(double);
+    if (hipMalloc((void**)&s->d_state, state_bytes) != hipSuccess) {
+        delete s;
+        return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(dyn state)");
+    }
+    const hipError_t e = hipMemsetAsync(s->d_state, 0, state_bytes, ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(s->d_state);
+        delete s;
+        return nae_check(ctx, e, "hipMemsetAsync(dyn state)");
+    }
+    *h = s;
+    return NAE_OK;
+}
+
+static int dyn_append(nae_dyn* h, const float* p, size_t S, bool host)
+{
+    if (!h || (S && !p)) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (h->flushed) return nae_fail(h->ctx, NAE_ERR_STATE, "put after flush");
+    if (S == 0) return NAE_OK;
+    const int rc = h->in.push(h->ctx, p, S, host);
+    return rc ? rc : dyn_process(h);
+}
+
+int nae_dyn_put(nae_dyn* h, const float* interleaved, size_t S) { return dyn_append(h, interleaved, S, false); }
+int nae_dyn_put_host(nae_dyn* h, const float* interleaved_host, size_t S) { return dyn_append(h, interleaved_host, S, true); }
+
+// the chunks that waited for their look-ahead and the partial last one come out: as many frames as were put over the handle's life
+int nae_dyn_flush(nae_dyn* h)
+{
+    if (!h) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (h->flushed) return NAE_OK;
+    h->flushed = true;
+    return dyn_process(h);
+}
+
+size_t nae_dyn_available(nae_dyn* h) { return h ? h->out.total - h->out_read : 0; }
+
+static int dyn_take(nae_dyn* h, float* dst, size_t max_frames, size_t* got, bool host)
+{
+    if (!h || !got || (max_frames && !dst)) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    size_t n = h->out.total - h->out_read;
+    if (n > max_frames) n = max_frames;
+    *got = n;
+    if (n == 0) return NAE_OK;
+    const int rc = h->out.pop(h->ctx, h->out_read, dst, n, host);
+    if (rc) return rc;
+    h->out_read += n;
+    return NAE_OK;
+}
+
+int nae_dyn_receive(nae_dyn* h, float* dst, size_t max_frames, size_t* got) { return dyn_take(h, dst, max_frames, got, false); }
+int nae_dyn_receive_host(nae_dyn* h, float* dst_host, size_t max_frames, size_t* got) { return dyn_take(h, dst_host, max_frames, got, true); }
+
+int nae_dyn_destroy(nae_dyn* h)
+{
+    if (!h) return NAE_OK;
+    (void)nae_use_device(h->ctx);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    h->in.free();
+    h->out.free();
     if (h->d_state) (void)hipFree(h->d_state);
     delete h;
     return NAE_OK;

@@ -151,4 +151,6 @@ namespace infra
 	void register_effect_processors();
 	// the equalizer (audio_eq): called after the three above, each of which stays the list it was
 	void register_equalizer_processors();
+	// the dynamics node (audio_dynamics): called after the four above, each of which stays the list it was
+	void register_dynamics_processors();
 }

@@ -1,7 +1,9 @@
 #include "audio-velocity.hpp"
+#include <type_traits>
 #include "audio-filter.hpp"
 #include "audio-reverb.hpp"
 #include "audio-eq.hpp"
+#include "audio-dynamics.hpp"
 #include "gpu-context.hpp"
 #include "velocity-cadence.hpp"
 
@@ -1049,6 +1051,127 @@ namespace processor
 		for (auto& stream : output_stream) stream->set_eof();
 	}
 
+	// What the nodes on a compensated streaming handle share (the equalizer, the dynamics node): frames are put as they come, in batches;
+	// everything the handle has ready leaves as frames of the input's sizes, pts and time base; the flush at the end of the stream releases
+	// the rest.  `create` makes the handle from the first frame (its sample rate) and the channel count, or throws.
+	template <class Handle>
+	struct Handle_ops
+	{
+		int (*put)(Handle*, const float*, size_t);
+		int (*flush)(Handle*);
+		size_t (*available)(Handle*);
+		int (*receive)(Handle*, float*, size_t, size_t*);
+		int (*destroy)(Handle*);
+	};
+
+	template <class Handle, class Create>
+	static void run_on_handle(
+		Audio_stream& input_stream, const std::set<std::shared_ptr<Audio_stream>>& output_stream, const std::atomic<bool>& stop_token,
+		const std::type_identity_t<Handle_ops<Handle>>& ops, const Create& create
+	)
+	{
+		nae_ctx* ctx = gpu::context();
+		Handle* h = nullptr;
+		struct Guard { Handle*& h; int (*destroy)(Handle*); ~Guard() { if (h) destroy(h); } } guard{h, ops.destroy};
+		gpu::Device_buffer d_raw, d_f32, d_out;
+		gpu::Pinned_buffer h_raw, h_out;
+		int ch = 0;
+		struct Shape { int nb_samples, sample_rate; int64_t pts; decltype(Frame_data::time_base) time_base; };
+		std::deque<Shape> shapes;     // the input frames whose output is still owed
+		std::vector<float> ready;     // filtered samples, interleaved, not yet cut into frames
+		size_t ready_pos = 0;         // frames of `ready` already delivered
+		std::shared_ptr<const Audio_frame> held;  // popped, but with another channel count than the batch in front of it
+
+		// everything the handle has ready comes down behind ONE wait and leaves as frames of the input's sizes
+		const auto deliver = [&]()
+		{
+			const size_t avail = ops.available(h);
+			if (avail == 0) { gpu::wait(stop_token); return; }
+			float* dev = static_cast<float*>(d_out.reserve(avail * ch * sizeof(float)));
+			float* host = static_cast<float*>(h_out.reserve(avail * ch * sizeof(float)));
+			size_t got = 0;
+			gpu::check(ops.receive(h, dev, avail, &got), "receive");
+			gpu::check(nae_memcpy_d2h(ctx, host, dev, got * ch * sizeof(float)), "d2h");
+			gpu::wait(stop_token);
+			ready.erase(ready.begin(), ready.begin() + ready_pos * ch);
+			ready_pos = 0;
+			ready.insert(ready.end(), host, host + got * ch);
+			while (!shapes.empty() && !stop_token && ready.size() / ch - ready_pos >= (size_t)shapes.front().nb_samples)
+			{
+				const Shape s = shapes.front();
+				shapes.pop_front();
+				auto out = std::make_shared<Audio_frame>();
+				Frame_data* o = out->data();
+				o->format = AV_SAMPLE_FMT_FLT;
+				o->sample_rate = s.sample_rate;
+				o->nb_samples = s.nb_samples;
+				o->ch_layout.nb_channels = ch;
+				o->time_base = s.time_base;
+				o->pts = s.pts;
+				frame_get_buffer(o, 32);
+				std::memcpy(o->data[0], ready.data() + ready_pos * ch, (size_t)s.nb_samples * ch * sizeof(float));
+				ready_pos += s.nb_samples;
+				for (auto& stream : output_stream)
+					while (!stop_token && stream->try_push(out) != channel_op_status::success) nae_fiber::this_fiber::yield();
+			}
+		};
+
+		while (!stop_token)
+		{
+			constexpr size_t max_batch = 16;   // as the filter node: every frame that is already waiting is put as one block
+			std::vector<std::shared_ptr<const Audio_frame>> batch;
+			if (held) batch.push_back(std::move(held));
+			held.reset();
+			bool ended = false;
+			while (batch.size() < max_batch)
+			{
+				const auto pop_result = input_stream.try_pop();
+				if (!pop_result.has_value())
+				{
+					ended = input_stream.eof();
+					break;
+				}
+				if (!batch.empty() && pop_result.value()->data()->ch_layout.nb_channels != batch.front()->data()->ch_layout.nb_channels)
+				{
+					held = pop_result.value();
+					break;
+				}
+				batch.push_back(pop_result.value());
+			}
+			if (batch.empty())
+			{
+				if (!ended)
+				{
+					nae_fiber::this_fiber::yield();
+					continue;
+				}
+				if (h != nullptr)
+				{
+					// what the handle still holds comes out with the flush: every frame still owed is complete
+					gpu::check(ops.flush(h), "flush");
+					deliver();
+				}
+				break;
+			}
+			const Frame_data* frame = batch.front()->data();
+			if (h == nullptr)
+			{
+				ch = frame->ch_layout.nb_channels;
+				if (ch != 1 && ch != 2) throw infra::Processor::Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
+				h = create(ctx, frame, ch);
+			}
+			else if (frame->ch_layout.nb_channels != ch)
+				throw infra::Processor::Runtime_error("Channel count changed", "The node runs one stream of a fixed channel count.",
+									infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, ch));
+			for (const auto& f : batch) shapes.push_back({f->data()->nb_samples, f->data()->sample_rate, f->data()->pts, f->data()->time_base});
+			size_t total = 0;
+			float* samples = upload_as_f32(batch, h_raw, d_raw, d_f32, &total);
+			gpu::check(ops.put(h, samples, total), "put");
+			deliver();
+		}
+		for (auto& stream : output_stream) stream->set_eof();
+	}
+
 	// ------------------------------------------------------------------------------------------ Audio_eq
 	infra::Processor::Info Audio_eq::get_processor_info()
 	{
@@ -1157,110 +1280,122 @@ namespace processor
 			for (auto& stream : output_stream) stream->set_eof();
 			return;
 		}
-		nae_ctx* ctx = gpu::context();
-		nae_eq* eq = nullptr;
-		struct Guard { nae_eq*& h; ~Guard() { if (h) nae_eq_destroy(h); } } guard{eq};
-		gpu::Device_buffer d_raw, d_f32, d_out;
-		gpu::Pinned_buffer h_raw, h_out;
-		int ch = 0;
-		struct Shape { int nb_samples, sample_rate; int64_t pts; decltype(Frame_data::time_base) time_base; };
-		std::deque<Shape> shapes;     // the input frames whose output is still owed
-		std::vector<float> ready;     // filtered samples, interleaved, not yet cut into frames
-		size_t ready_pos = 0;         // frames of `ready` already delivered
-		std::shared_ptr<const Audio_frame> held;  // popped, but with another channel count than the batch in front of it
-
-		// everything the handle has ready comes down behind ONE wait and leaves as frames of the input's sizes
-		const auto deliver = [&]()
-		{
-			const size_t avail = nae_eq_available(eq);
-			if (avail == 0) { gpu::wait(stop_token); return; }
-			float* dev = static_cast<float*>(d_out.reserve(avail * ch * sizeof(float)));
-			float* host = static_cast<float*>(h_out.reserve(avail * ch * sizeof(float)));
-			size_t got = 0;
-			gpu::check(nae_eq_receive(eq, dev, avail, &got), "nae_eq_receive");
-			gpu::check(nae_memcpy_d2h(ctx, host, dev, got * ch * sizeof(float)), "d2h");
-			gpu::wait(stop_token);
-			ready.erase(ready.begin(), ready.begin() + ready_pos * ch);
-			ready_pos = 0;
-			ready.insert(ready.end(), host, host + got * ch);
-			while (!shapes.empty() && !stop_token && ready.size() / ch - ready_pos >= (size_t)shapes.front().nb_samples)
+		run_on_handle<nae_eq>(
+			input_stream, output_stream, stop_token, {nae_eq_put, nae_eq_flush, nae_eq_available, nae_eq_receive, nae_eq_destroy},
+			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
 			{
-				const Shape s = shapes.front();
-				shapes.pop_front();
-				auto out = std::make_shared<Audio_frame>();
-				Frame_data* o = out->data();
-				o->format = AV_SAMPLE_FMT_FLT;
-				o->sample_rate = s.sample_rate;
-				o->nb_samples = s.nb_samples;
-				o->ch_layout.nb_channels = ch;
-				o->time_base = s.time_base;
-				o->pts = s.pts;
-				frame_get_buffer(o, 32);
-				std::memcpy(o->data[0], ready.data() + ready_pos * ch, (size_t)s.nb_samples * ch * sizeof(float));
-				ready_pos += s.nb_samples;
-				for (auto& stream : output_stream)
-					while (!stop_token && stream->try_push(out) != channel_op_status::success) nae_fiber::this_fiber::yield();
-			}
-		};
-
-		while (!stop_token)
-		{
-			constexpr size_t max_batch = 16;   // as the filter node: every frame that is already waiting is put as one block
-			std::vector<std::shared_ptr<const Audio_frame>> batch;
-			if (held) batch.push_back(std::move(held));
-			held.reset();
-			bool ended = false;
-			while (batch.size() < max_batch)
-			{
-				const auto pop_result = input_stream.try_pop();
-				if (!pop_result.has_value())
-				{
-					ended = input_stream.eof();
-					break;
-				}
-				if (!batch.empty() && pop_result.value()->data()->ch_layout.nb_channels != batch.front()->data()->ch_layout.nb_channels)
-				{
-					held = pop_result.value();
-					break;
-				}
-				batch.push_back(pop_result.value());
-			}
-			if (batch.empty())
-			{
-				if (!ended)
-				{
-					nae_fiber::this_fiber::yield();
-					continue;
-				}
-				if (eq != nullptr)
-				{
-					// the partial last chunk comes out with the flush: an IIR has no tail, so every frame still owed is complete
-					gpu::check(nae_eq_flush(eq), "nae_eq_flush");
-					deliver();
-				}
-				break;
-			}
-			const Frame_data* frame = batch.front()->data();
-			if (eq == nullptr)
-			{
-				ch = frame->ch_layout.nb_channels;
-				if (ch != 1 && ch != 2) throw Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
 				std::vector<double> coef(bands.size() * 5);
 				for (size_t i = 0; i < bands.size(); i++)
 					if (nae_eq_design((int)bands[i].kind, frame->sample_rate, bands[i].freq, bands[i].gain_db, bands[i].q, coef.data() + 5 * i) != NAE_OK)
 						throw Runtime_error("Invalid equalizer band", "A band's frequency must lie below half the stream's sample rate.",
 											infra::fmt("band %d: %g Hz at %d Hz", (int)i, bands[i].freq, frame->sample_rate));
+				nae_eq* eq = nullptr;
 				gpu::check(nae_eq_create(ctx, coef.data(), (int)bands.size(), ch, &eq), "nae_eq_create");
+				return eq;
 			}
-			else if (frame->ch_layout.nb_channels != ch)
-				throw Runtime_error("Channel count changed", "The equalizer runs one stream of a fixed channel count.",
-									infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, ch));
-			for (const auto& f : batch) shapes.push_back({f->data()->nb_samples, f->data()->sample_rate, f->data()->pts, f->data()->time_base});
-			size_t total = 0;
-			float* samples = upload_as_f32(batch, h_raw, d_raw, d_f32, &total);
-			gpu::check(nae_eq_put(eq, samples, total), "nae_eq_put");
-			deliver();
+		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_dynamics
+	infra::Processor::Info Audio_dynamics::get_processor_info()
+	{
+		return {"audio_dynamics", "Audio Dynamics", false, [] { return std::unique_ptr<infra::Processor>(new Audio_dynamics); },
+				"Compressor / look-ahead limiter in the dB domain: threshold, ratio, soft knee, attack, release, make-up gain (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_dynamics::get_pin_attributes() const
+	{
+		return {
+			{"output", "Output", typeid(Audio_stream), false, [] { return std::make_shared<Audio_stream>(); }},
+			{"input", "Input", typeid(Audio_stream), true, [] { return std::make_shared<Audio_stream>(); }}
+		};
+	}
+
+	Json::Value Audio_dynamics::serialize() const
+	{
+		Json::Value value;
+		if (mode != Mode::Compressor) value["mode"] = "limiter";
+		if (threshold_db != default_threshold_db) value["threshold_db"] = threshold_db;
+		if (ratio != default_ratio) value["ratio"] = ratio;
+		if (knee_db != default_knee_db) value["knee_db"] = knee_db;
+		if (attack_ms != default_attack_ms) value["attack_ms"] = attack_ms;
+		if (release_ms != default_release_ms) value["release_ms"] = release_ms;
+		if (lookahead_ms != default_lookahead_ms) value["lookahead_ms"] = lookahead_ms;
+		if (makeup_db != default_makeup_db) value["makeup_db"] = makeup_db;
+		if (!link_channels) value["link_channels"] = false;
+		return value;
+	}
+
+	void Audio_dynamics::deserialize(const Json::Value& value)
+	{
+		const auto wrong = [](const char* field) {
+			return Runtime_error(
+				"Failed to deserialize JSON file",
+				"Audio_dynamics failed to serialize the JSON input because of missing or invalid fields.",
+				std::string("Wrong field: ") + field
+			);
+		};
+		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
+		Mode m = Mode::Compressor;
+		if (value.isMember("mode"))
+		{
+			if (!value["mode"].isString()) throw wrong("mode");
+			const std::string name = value["mode"].asString();
+			if (name == "limiter") m = Mode::Limiter;
+			else if (name != "compressor") throw wrong("mode");
 		}
-		for (auto& stream : output_stream) stream->set_eof();
+		const auto real = [&](const char* key, double lo, double hi, double fallback) {
+			if (!value.isMember(key)) return fallback;
+			if (!value[key].isDouble() || !(value[key].asDouble() >= lo && value[key].asDouble() <= hi)) throw wrong(key);
+			return value[key].asDouble();
+		};
+		const double t = real("threshold_db", -60.0, 0.0, default_threshold_db);
+		const double r = real("ratio", 1.0, 100.0, default_ratio);
+		const double k = real("knee_db", 0.0, 24.0, default_knee_db);
+		const double a = real("attack_ms", 0.0, 500.0, default_attack_ms);
+		const double rl = real("release_ms", 1.0, 5000.0, default_release_ms);
+		const double la = real("lookahead_ms", 0.0, 20.0, default_lookahead_ms);
+		const double mk = real("makeup_db", -24.0, 24.0, default_makeup_db);
+		bool link = true;
+		if (value.isMember("link_channels"))
+		{
+			if (!value["link_channels"].isBool()) throw wrong("link_channels");
+			link = value["link_channels"].asBool();
+		}
+		mode = m;
+		threshold_db = t; ratio = r; knee_db = k; attack_ms = a; release_ms = rl; lookahead_ms = la; makeup_db = mk;
+		link_channels = link;
+	}
+
+	void Audio_dynamics::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
+		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
+		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
+		if (!input_item.has_value())
+			throw Runtime_error("Audio Dynamics has no input", "Audio Dynamics requires an audio stream input to function properly.", "Input item 'input' not found");
+		Audio_stream& input_stream = input_item.value().get();
+		run_on_handle<nae_dyn>(
+			input_stream, output_stream, stop_token, {nae_dyn_put, nae_dyn_flush, nae_dyn_available, nae_dyn_receive, nae_dyn_destroy},
+			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
+			{
+				nae_dyn_params params;
+				const int rc = nae_dyn_design(frame->sample_rate, threshold_db, mode == Mode::Limiter ? INFINITY : ratio, knee_db, attack_ms / 1000.0,
+											  release_ms / 1000.0, lookahead_ms / 1000.0, makeup_db, link_channels ? 1 : 0, &params);
+				if (rc == NAE_ERR_UNSUPPORTED)
+					throw Runtime_error("Look-ahead too long", "The look-ahead must not exceed 1024 samples at the stream's sample rate.",
+										infra::fmt("lookahead %g ms at %d Hz", lookahead_ms, frame->sample_rate));
+				if (rc != NAE_OK)
+					throw Runtime_error("Invalid dynamics parameters", "A parameter of the dynamics node lies outside its range.",
+										infra::fmt("nae_dyn_design at %d Hz: code %d", frame->sample_rate, rc));
+				nae_dyn* dyn = nullptr;
+				gpu::check(nae_dyn_create(ctx, &params, ch, &dyn), "nae_dyn_create");
+				return dyn;
+			}
+		);
 	}
 }

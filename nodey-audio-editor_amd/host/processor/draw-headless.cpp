@@ -16,6 +16,7 @@
 #include "audio-filter.hpp"
 #include "audio-reverb.hpp"
 #include "audio-eq.hpp"
+#include "audio-dynamics.hpp"
 #include "audio-mix.hpp"
 #include "audio-velocity.hpp"
 #include "audio-vol.hpp"
@@ -100,6 +101,20 @@ namespace processor
 			b.gain_db = std::clamp(b.gain_db, -24.0, 24.0);
 			b.q = std::clamp(b.q, 0.1, 40.0);
 		}
+		return false;
+	}
+
+	void Audio_dynamics::draw_title() {}
+	bool Audio_dynamics::draw_content(bool)
+	{
+		// what the widgets would keep: every value inside its range
+		threshold_db = std::clamp(threshold_db, -60.0, 0.0);
+		ratio = std::clamp(ratio, 1.0, 100.0);
+		knee_db = std::clamp(knee_db, 0.0, 24.0);
+		attack_ms = std::clamp(attack_ms, 0.0, 500.0);
+		release_ms = std::clamp(release_ms, 1.0, 5000.0);
+		lookahead_ms = std::clamp(lookahead_ms, 0.0, 20.0);
+		makeup_db = std::clamp(makeup_db, -24.0, 24.0);
 		return false;
 	}
 }

@@ -6,6 +6,7 @@
 #include "processor/audio-filter.hpp"
 #include "processor/audio-reverb.hpp"
 #include "processor/audio-eq.hpp"
+#include "processor/audio-dynamics.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -39,4 +40,7 @@ namespace infra
 
 	// the equalizer on the biquad cascade; again a call of its own, so the three lists above stay what they were
 	void register_equalizer_processors() { register_each<processor::Audio_eq>(); }
+
+	// the compressor / limiter on the dynamics processor; a call of its own once more, so the four lists above stay what they were
+	void register_dynamics_processors() { register_each<processor::Audio_dynamics>(); }
 }
