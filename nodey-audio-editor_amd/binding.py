@@ -52,6 +52,7 @@ FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX = 0.25, 4.0   # NAE_FORMANT_SHIFT_MIN / _MA
 FIR_SIZES = (512, 1024, 2048, 4096)                 # frame sizes of the FIR filter: at most n_fft / 2 + 1 taps
 FIR_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}   # `kind` of nae_fir_design
 EQ_KINDS = ("peak", "lowshelf", "highshelf", "lowpass", "highpass", "notch")   # `kind` of nae_eq_design: NAE_EQ_PEAK ... NAE_EQ_NOTCH
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -176,10 +177,7 @@ def load_library() -> C.CDLL:
         "nae_stretch_plan_make_shift": (i, [d, d, d, i, i, sz, P(StretchPlan)]),
         "nae_stretch_block_formant_shift_f32": (i, [vp, d, d, u, i, i, d, P(Sig), sz, i, sz, P(Sig)]),
         "nae_stretch_create_formant_shift": (i, [vp, i, i, f, f, u, i, i, d, P(vp)]),
-        "nae_stretch_create": (i, [vp, i, i, f, f, P(vp)]), "nae_stretch_put": (i, [vp, vp, sz]),
-        "nae_stretch_put_host": (i, [vp, vp, sz]), "nae_stretch_flush": (i, [vp]),
-        "nae_stretch_available": (sz, [vp]), "nae_stretch_receive": (i, [vp, vp, sz, P(sz)]),
-        "nae_stretch_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_stretch_destroy": (i, [vp]),
+        "nae_stretch_create": (i, [vp, i, i, f, f, P(vp)]),
         "nae_swr_create": (i, [vp, i, i, i, i, P(vp)]),
         "nae_swr_convert_host": (i, [vp, P(vp), sz, vp, vp, sz, P(sz)]), "nae_swr_convert": (i, [vp, P(vp), sz, vp, vp, sz, P(sz)]),
         "nae_swr_buffered": (sz, [vp]),
@@ -191,32 +189,22 @@ def load_library() -> C.CDLL:
         "nae_spectrum_destroy": (i, [vp]), "nae_graph4_run": (i, [vp, P(Graph4)]),
         "nae_wsola_plan_make": (i, [i, i, d, d, sz, P(WsolaPlan)]),
         "nae_wsola_block_f32": (i, [vp, i, d, d, P(Sig), sz, i, sz, P(Sig), vp]),
-        "nae_wsola_create": (i, [vp, i, i, d, d, P(vp)]), "nae_wsola_put": (i, [vp, vp, sz]),
-        "nae_wsola_put_host": (i, [vp, vp, sz]), "nae_wsola_flush": (i, [vp]), "nae_wsola_available": (sz, [vp]),
-        "nae_wsola_receive": (i, [vp, vp, sz, P(sz)]), "nae_wsola_receive_host": (i, [vp, vp, sz, P(sz)]),
-        "nae_wsola_destroy": (i, [vp]),
+        "nae_wsola_create": (i, [vp, i, i, d, d, P(vp)]),
         "nae_fir_pick_n_fft": (i, [i]), "nae_fir_block_f32": (i, [vp, vp, i, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_fir_design": (i, [i, i, d, d, i, vp]), "nae_fir_create": (i, [vp, vp, i, i, i, P(vp)]),
-        "nae_fir_put": (i, [vp, vp, sz]), "nae_fir_put_host": (i, [vp, vp, sz]), "nae_fir_flush": (i, [vp]),
-        "nae_fir_available": (sz, [vp]), "nae_fir_receive": (i, [vp, vp, sz, P(sz)]),
-        "nae_fir_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_fir_destroy": (i, [vp]),
         "nae_conv_pick_n_fft": (i, [i]), "nae_conv_block_f32": (i, [vp, vp, i, i, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_conv_reverb_taps": (i, [i, d, d]), "nae_conv_design_reverb": (i, [i, d, d, d, d, C.c_uint64, i, vp]),
         "nae_conv_create": (i, [vp, vp, i, i, i, i, P(vp)]),
-        "nae_conv_put": (i, [vp, vp, sz]), "nae_conv_put_host": (i, [vp, vp, sz]), "nae_conv_flush": (i, [vp]),
-        "nae_conv_available": (sz, [vp]), "nae_conv_receive": (i, [vp, vp, sz, P(sz)]),
-        "nae_conv_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_conv_destroy": (i, [vp]),
         "nae_eq_design": (i, [i, i, d, d, d, vp]), "nae_eq_block_f32": (i, [vp, vp, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_eq_create": (i, [vp, vp, i, i, P(vp)]),
-        "nae_eq_put": (i, [vp, vp, sz]), "nae_eq_put_host": (i, [vp, vp, sz]), "nae_eq_flush": (i, [vp]),
-        "nae_eq_available": (sz, [vp]), "nae_eq_receive": (i, [vp, vp, sz, P(sz)]),
-        "nae_eq_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_eq_destroy": (i, [vp]),
         "nae_dyn_design": (i, [i, d, d, d, d, d, d, d, i, P(DynParams)]), "nae_dyn_block_f32": (i, [vp, P(DynParams), P(Sig), sz, i, sz, P(Sig)]),
         "nae_dyn_create": (i, [vp, P(DynParams), i, P(vp)]),
-        "nae_dyn_put": (i, [vp, vp, sz]), "nae_dyn_put_host": (i, [vp, vp, sz]), "nae_dyn_flush": (i, [vp]),
-        "nae_dyn_available": (sz, [vp]), "nae_dyn_receive": (i, [vp, vp, sz, P(sz)]),
-        "nae_dyn_receive_host": (i, [vp, vp, sz, P(sz)]), "nae_dyn_destroy": (i, [vp]),
     }
+    # the seven entries every put / receive handle has besides its create (the spectrum handle has four of them: spelled out above)
+    for prefix in HANDLE_PREFIXES:
+        sigs.update({prefix + "_put": (i, [vp, vp, sz]), prefix + "_put_host": (i, [vp, vp, sz]), prefix + "_flush": (i, [vp]),
+                     prefix + "_available": (sz, [vp]), prefix + "_receive": (i, [vp, vp, sz, P(sz)]),
+                     prefix + "_receive_host": (i, [vp, vp, sz, P(sz)]), prefix + "_destroy": (i, [vp])})
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -656,15 +644,65 @@ def formant_lifter(sample_rate: int, n_fft: int = 1024) -> int:
     return int(load_library().nae_stretch_formant_lifter(sample_rate, n_fft))
 
 
-class Stretcher:
+class _Handle:
+    """What the streaming handles share: put / put_host / flush / available / receive / receive_host / close on the entries `_prefix`_*.
+    A subclass's __init__ calls this one and then its create entry on self.h."""
+    _prefix = ""
+
+    def __init__(self, ctx: Context, channels: int):
+        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+
+    def _fn(self, name: str):
+        return getattr(self.ctx.lib, f"{self._prefix}_{name}")
+
+    def put(self, dev_ptr: int, frames: int) -> None:
+        self.ctx._ck(self._fn("put")(self.h, dev_ptr, frames))
+
+    def put_host(self, x: np.ndarray) -> None:
+        x = np.ascontiguousarray(x, np.float32)
+        self.ctx._ck(self._fn("put_host")(self.h, x.ctypes.data, x.size // self.ch))
+
+    def flush(self) -> None:
+        self.ctx._ck(self._fn("flush")(self.h))
+
+    def available(self) -> int:
+        return self._fn("available")(self.h)
+
+    def receive(self, dev_ptr: int, max_frames: int) -> int:
+        got = C.c_size_t()
+        self.ctx._ck(self._fn("receive")(self.h, dev_ptr, max_frames, C.byref(got)))
+        return got.value
+
+    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
+        n = self.available() if max_frames is None else max_frames
+        out = np.empty(max(n, 1) * self.ch, np.float32)
+        got = C.c_size_t()
+        self.ctx._ck(self._fn("receive_host")(self.h, out.ctypes.data, n, C.byref(got)))
+        return out[: got.value * self.ch]
+
+    def close(self) -> None:
+        if self.h:
+            self._fn("destroy")(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Stretcher(_Handle):
     """The SoundTouch-shaped streaming handle (nae_stretch_create_ex; nae_stretch_create_n for an n_fft other than 1024;
     nae_stretch_create_formant with a formant lifter; nae_stretch_create_formant_shift with a formant_ratio): put interleaved f32, flush,
     receive."""
 
+    _prefix = "nae_stretch"
+
     def __init__(self, ctx: Context, sample_rate: int, channels: int, rate: float, pitch: float, phase_lock: bool = False,
                  n_fft: int = 1024, formant: int = 0, transients: bool = False, formant_ratio: Optional[float] = None,
                  link_channels: bool = False):
-        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+        super().__init__(ctx, channels)
         flags = (STRETCH_PHASE_LOCK if phase_lock else 0) | (STRETCH_TRANSIENTS if transients else 0) | (STRETCH_LINK_CHANNELS if link_channels else 0)
         if formant_ratio is not None:
             ctx._ck(ctx.lib.nae_stretch_create_formant_shift(ctx.h, sample_rate, channels, rate, pitch, flags, n_fft, formant, formant_ratio,
@@ -676,198 +714,48 @@ class Stretcher:
         else:
             ctx._ck(ctx.lib.nae_stretch_create_ex(ctx.h, sample_rate, channels, rate, pitch, flags, C.byref(self.h)))
 
-    def put(self, dev_ptr: int, frames: int) -> None:
-        self.ctx._ck(self.ctx.lib.nae_stretch_put(self.h, dev_ptr, frames))
 
-    def put_host(self, x: np.ndarray) -> None:
-        x = np.ascontiguousarray(x, np.float32)
-        self.ctx._ck(self.ctx.lib.nae_stretch_put_host(self.h, x.ctypes.data, x.size // self.ch))
-
-    def flush(self) -> None:
-        self.ctx._ck(self.ctx.lib.nae_stretch_flush(self.h))
-
-    def available(self) -> int:
-        return self.ctx.lib.nae_stretch_available(self.h)
-
-    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
-        n = self.available() if max_frames is None else max_frames
-        out = np.empty(max(n, 1) * self.ch, np.float32)
-        got = C.c_size_t()
-        self.ctx._ck(self.ctx.lib.nae_stretch_receive_host(self.h, out.ctypes.data, n, C.byref(got)))
-        return out[: got.value * self.ch]
-
-    def close(self) -> None:
-        if self.h:
-            self.ctx.lib.nae_stretch_destroy(self.h)
-            self.h = C.c_void_p()
-
-
-class Fir:
+class Fir(_Handle):
     """The FIR filter's streaming handle (nae_fir_create): put interleaved f32, flush (the tail: len(taps) - 1 more frames), receive."""
 
+    _prefix = "nae_fir"
+
     def __init__(self, ctx: Context, taps: np.ndarray, channels: int, n_fft: int = 0):
-        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+        super().__init__(ctx, channels)
         taps = np.ascontiguousarray(taps, np.float32)
         ctx._ck(ctx.lib.nae_fir_create(ctx.h, taps.ctypes.data, taps.size, n_fft, channels, C.byref(self.h)))
 
-    def put(self, dev_ptr: int, frames: int) -> None:
-        self.ctx._ck(self.ctx.lib.nae_fir_put(self.h, dev_ptr, frames))
 
-    def put_host(self, x: np.ndarray) -> None:
-        x = np.ascontiguousarray(x, np.float32)
-        self.ctx._ck(self.ctx.lib.nae_fir_put_host(self.h, x.ctypes.data, x.size // self.ch))
-
-    def flush(self) -> None:
-        self.ctx._ck(self.ctx.lib.nae_fir_flush(self.h))
-
-    def available(self) -> int:
-        return self.ctx.lib.nae_fir_available(self.h)
-
-    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
-        n = self.available() if max_frames is None else max_frames
-        out = np.empty(max(n, 1) * self.ch, np.float32)
-        got = C.c_size_t()
-        self.ctx._ck(self.ctx.lib.nae_fir_receive_host(self.h, out.ctypes.data, n, C.byref(got)))
-        return out[: got.value * self.ch]
-
-    def close(self) -> None:
-        if self.h:
-            self.ctx.lib.nae_fir_destroy(self.h)
-            self.h = C.c_void_p()
-
-
-class Conv:
+class Conv(_Handle):
     """The long convolution's streaming handle (nae_conv_create): put interleaved f32, flush (the tail: n_taps - 1 more frames), receive.
     taps [L] (one set for every channel) or [channels][L]."""
 
+    _prefix = "nae_conv"
+
     def __init__(self, ctx: Context, taps: np.ndarray, channels: int, n_fft: int = 0):
-        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+        super().__init__(ctx, channels)
         taps = np.ascontiguousarray(taps, np.float32)
         taps_ch, n_taps = (1, taps.size) if taps.ndim == 1 else taps.shape
         ctx._ck(ctx.lib.nae_conv_create(ctx.h, taps.ctypes.data, n_taps, taps_ch, n_fft, channels, C.byref(self.h)))
 
-    def put(self, dev_ptr: int, frames: int) -> None:
-        self.ctx._ck(self.ctx.lib.nae_conv_put(self.h, dev_ptr, frames))
 
-    def put_host(self, x: np.ndarray) -> None:
-        x = np.ascontiguousarray(x, np.float32)
-        self.ctx._ck(self.ctx.lib.nae_conv_put_host(self.h, x.ctypes.data, x.size // self.ch))
-
-    def flush(self) -> None:
-        self.ctx._ck(self.ctx.lib.nae_conv_flush(self.h))
-
-    def available(self) -> int:
-        return self.ctx.lib.nae_conv_available(self.h)
-
-    def receive(self, dev_ptr: int, max_frames: int) -> int:
-        got = C.c_size_t()
-        self.ctx._ck(self.ctx.lib.nae_conv_receive(self.h, dev_ptr, max_frames, C.byref(got)))
-        return got.value
-
-    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
-        n = self.available() if max_frames is None else max_frames
-        out = np.empty(max(n, 1) * self.ch, np.float32)
-        got = C.c_size_t()
-        self.ctx._ck(self.ctx.lib.nae_conv_receive_host(self.h, out.ctypes.data, n, C.byref(got)))
-        return out[: got.value * self.ch]
-
-    def close(self) -> None:
-        if self.h:
-            self.ctx.lib.nae_conv_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-class Eq:
+class Eq(_Handle):
     """The biquad cascade's streaming handle (nae_eq_create): put interleaved f32, flush (the partial last chunk), receive.  coef [S][5]."""
 
+    _prefix = "nae_eq"
+
     def __init__(self, ctx: Context, coef: np.ndarray, channels: int):
-        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+        super().__init__(ctx, channels)
         coef = np.ascontiguousarray(coef, np.float64).reshape(-1, 5)
         ctx._ck(ctx.lib.nae_eq_create(ctx.h, coef.ctypes.data, coef.shape[0], channels, C.byref(self.h)))
 
-    def put(self, dev_ptr: int, frames: int) -> None:
-        self.ctx._ck(self.ctx.lib.nae_eq_put(self.h, dev_ptr, frames))
 
-    def put_host(self, x: np.ndarray) -> None:
-        x = np.ascontiguousarray(x, np.float32)
-        self.ctx._ck(self.ctx.lib.nae_eq_put_host(self.h, x.ctypes.data, x.size // self.ch))
-
-    def flush(self) -> None:
-        self.ctx._ck(self.ctx.lib.nae_eq_flush(self.h))
-
-    def available(self) -> int:
-        return self.ctx.lib.nae_eq_available(self.h)
-
-    def receive(self, dev_ptr: int, max_frames: int) -> int:
-        got = C.c_size_t()
-        self.ctx._ck(self.ctx.lib.nae_eq_receive(self.h, dev_ptr, max_frames, C.byref(got)))
-        return got.value
-
-    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
-        n = self.available() if max_frames is None else max_frames
-        out = np.empty(max(n, 1) * self.ch, np.float32)
-        got = C.c_size_t()
-        self.ctx._ck(self.ctx.lib.nae_eq_receive_host(self.h, out.ctypes.data, n, C.byref(got)))
-        return out[: got.value * self.ch]
-
-    def close(self) -> None:
-        if self.h:
-            self.ctx.lib.nae_eq_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-class Dyn:
+class Dyn(_Handle):
     """The dynamics processor's streaming handle (nae_dyn_create): put interleaved f32, flush, receive.  Before the flush the whole chunks
     whose look-ahead is complete are available; the flush releases the rest."""
 
+    _prefix = "nae_dyn"
+
     def __init__(self, ctx: Context, params: DynParams, channels: int):
-        self.ctx, self.ch, self.h = ctx, channels, C.c_void_p()
+        super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_dyn_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
-
-    def put(self, dev_ptr: int, frames: int) -> None:
-        self.ctx._ck(self.ctx.lib.nae_dyn_put(self.h, dev_ptr, frames))
-
-    def put_host(self, x: np.ndarray) -> None:
-        x = np.ascontiguousarray(x, np.float32)
-        self.ctx._ck(self.ctx.lib.nae_dyn_put_host(self.h, x.ctypes.data, x.size // self.ch))
-
-    def flush(self) -> None:
-        self.ctx._ck(self.ctx.lib.nae_dyn_flush(self.h))
-
-    def available(self) -> int:
-        return self.ctx.lib.nae_dyn_available(self.h)
-
-    def receive(self, dev_ptr: int, max_frames: int) -> int:
-        got = C.c_size_t()
-        self.ctx._ck(self.ctx.lib.nae_dyn_receive(self.h, dev_ptr, max_frames, C.byref(got)))
-        return got.value
-
-    def receive_host(self, max_frames: Optional[int] = None) -> np.ndarray:
-        n = self.available() if max_frames is None else max_frames
-        out = np.empty(max(n, 1) * self.ch, np.float32)
-        got = C.c_size_t()
-        self.ctx._ck(self.ctx.lib.nae_dyn_receive_host(self.h, out.ctypes.data, n, C.byref(got)))
-        return out[: got.value * self.ch]
-
-    def close(self) -> None:
-        if self.h:
-            self.ctx.lib.nae_dyn_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()

@@ -1,6 +1,8 @@
-// stream_util.h — grow-only device buffers and the absolutely indexed device FIFO of the streaming handles (not installed)
+// stream_util.h — grow-only device buffers, the absolutely indexed device FIFO of the streaming handles, and the handles' shared core: what
+// a handle is (StreamHandle, BlockHandle) and its put / flush / available / receive / destroy (not installed)
 #pragma once
 #include "nae_internal.h"
+#include <new>
 
 // grow-only device scratch; a grow does not keep the contents
 struct DevBuf {
@@ -131,3 +133,139 @@ struct DevFifo {
         *this = DevFifo{};
     }
 };
+
+// What every streaming handle is: a context, a channel count, an input and an output FIFO, the frames already handed out, and whether the
+// flush has been seen.  The device allocations a handle makes through dev_alloc() are its own: the destructor frees them with the FIFOs, so
+// a create that fails half way releases through the same routine as destroy.  process() computes what became computable after a put or
+// the flush and is the one thing a handle must supply.
+struct StreamHandle {
+    nae_ctx* ctx = nullptr;
+    int ch = 0;
+    DevFifo in;                  // interleaved input, from the first sample the next launch still needs on
+    DevFifo out;                 // result; elements [out_read, out.total) wait to be received
+    size_t out_read = 0;
+    size_t flush_tail = 0;       // zero frames the flush appends behind the input (the tail of an FIR)
+    bool flushed = false;
+    void* owned[4] = {};         // device allocations made by dev_alloc(): at most this many per handle (today's most is two)
+    int n_owned = 0;
+
+    virtual int process() = 0;
+    virtual ~StreamHandle()
+    {
+        in.free();
+        out.free();
+        for (int i = 0; i < n_owned; i++) (void)hipFree(owned[i]);
+    }
+
+    // `count` elements of device memory that live as long as the handle
+    template <class T>
+    int dev_alloc(T** p, size_t count, const char* what)
+    {
+        if (n_owned == (int)(sizeof(owned) / sizeof(owned[0]))) return nae_fail(ctx, NAE_ERR_NOMEM, "dev_alloc: the handle's table of device allocations is full");
+        if (hipMalloc((void**)p, count * sizeof(T)) != hipSuccess) return nae_fail(ctx, NAE_ERR_NOMEM, what);
+        owned[n_owned++] = *p;
+        return NAE_OK;
+    }
+};
+
+// A block handle computes its output in whole units of U frames (a half FFT frame, a chunk) as the input fills them.
+struct BlockHandle : StreamHandle {
+    size_t done = 0;             // units computed
+
+    // Runs the units that became computable, [done, ready): before the flush every whole unit with `wait` more frames behind it, after
+    // the flush all the rest with the partial one at the end.  launch(src, dst, from, to) computes them from the absolutely indexed views
+    // of the FIFOs; only when it succeeds do the output and `done` advance.  The last `keep` units of input stay in the FIFO (an
+    // overlap-save block reads the half frame in front of it).
+    template <class Launch>
+    int run_units(size_t U, size_t wait, size_t keep, const Launch& launch)
+    {
+        const size_t ready = flushed ? (in.total + U - 1) / U : (in.total >= wait ? (in.total - wait) / U : 0);
+        if (ready <= done) return NAE_OK;
+        const size_t produced = flushed ? in.total : ready * U;
+        int rc = out.reserve(ctx, produced);
+        if (rc) return rc;
+        const nae_sig src = in.view(), dst = out.view();
+        rc = launch(src, dst, done, ready);
+        if (rc) return rc;
+        out.total = produced;
+        done = ready;
+        in.drop((long long)((ready - keep) * U));
+        return NAE_OK;
+    }
+};
+
+// a new handle of type H on `ctx` with interleaved FIFOs of `channels` floats per frame; nullptr when out of memory
+template <class H>
+static inline H* handle_new(nae_ctx* ctx, int channels)
+{
+    H* h = new (std::nothrow) H();
+    if (!h) return nullptr;
+    h->ctx = ctx;
+    h->ch = channels;
+    h->in.width = h->out.width = (size_t)channels;
+    return h;
+}
+
+static inline int handle_destroy(StreamHandle* h)
+{
+    if (!h) return NAE_OK;
+    (void)nae_use_device(h->ctx);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    delete h;
+    return NAE_OK;
+}
+
+// the end of a create entry: hands the handle out, or releases it when a step after its construction failed
+template <class H>
+static inline int handle_created(H* h, int rc, H** out)
+{
+    if (rc) {
+        (void)handle_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return NAE_OK;
+}
+
+static inline int handle_append(StreamHandle* h, const float* p, size_t S, bool host)
+{
+    if (!h || (S && !p)) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (h->flushed) return nae_fail(h->ctx, NAE_ERR_STATE, "put after flush");
+    if (S == 0) return NAE_OK;
+    const int rc = h->in.push(h->ctx, p, S, host);
+    return rc ? rc : h->process();
+}
+
+// the input ends here: flush_tail zero frames go in behind it, and process() releases everything that is left
+static inline int handle_flush(StreamHandle* h)
+{
+    if (!h) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (h->flushed) return NAE_OK;
+    if (const size_t tail = h->flush_tail) {
+        const int rc = h->in.reserve(h->ctx, h->in.total + tail);
+        if (rc) return rc;
+        const hipError_t e = hipMemsetAsync(h->in.at(h->in.total), 0, tail * h->in.width * sizeof(float), h->ctx->stream);
+        if (e != hipSuccess) return nae_check(h->ctx, e, "hipMemsetAsync(flush)");
+        h->in.total += tail;
+    }
+    h->flushed = true;
+    return h->process();
+}
+
+static inline size_t handle_available(const StreamHandle* h) { return h ? h->out.total - h->out_read : 0; }
+
+static inline int handle_take(StreamHandle* h, float* dst, size_t max_frames, size_t* got, bool host)
+{
+    if (!h || !got || (max_frames && !dst)) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    size_t n = h->out.total - h->out_read;
+    if (n > max_frames) n = max_frames;
+    *got = n;
+    if (n == 0) return NAE_OK;
+    const int rc = h->out.pop(h->ctx, h->out_read, dst, n, host);
+    if (rc) return rc;
+    h->out_read += n;
+    return NAE_OK;
+}

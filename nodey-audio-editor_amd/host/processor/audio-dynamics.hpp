@@ -1,6 +1,6 @@
 // processor/audio-dynamics.hpp — a node the reference has no class for: a compressor / look-ahead limiter on the library's dynamics processor
 // (nae_dyn_*; DESIGN.md §3, "K12 dynamics").  Registered by infra::register_dynamics_processors().  Its process_payload stands in
-// audio-velocity.cpp, next to the equalizer node's: both run on the one loop that feeds a streaming handle and delivers its frames.
+// audio-effects.cpp, next to the equalizer node's: both run on the one loop that feeds a streaming handle and delivers its frames.
 #pragma once
 #include "audio-stream.hpp"
 

@@ -1,6 +1,6 @@
 // processor/audio-eq.hpp — a node the reference has no class for: a parametric equalizer on the library's biquad cascade (nae_eq_*;
 // DESIGN.md §3, "K11 biquad cascade").  Registered by infra::register_equalizer_processors().  Its process_payload stands in
-// audio-velocity.cpp, next to the filter node's, whose frame upload it shares.
+// audio-effects.cpp, on the loop the handle nodes share (run_on_handle).
 #pragma once
 #include "audio-stream.hpp"
 

@@ -1,6 +1,6 @@
 // processor/audio-filter.hpp — a node the reference has no class for: a linear-phase FIR filter (low-pass, high-pass, band-pass, band-stop)
 // on the library's FFT fast convolution (nae_fir_*; DESIGN.md §3, "K9 FIR filter").  Registered by infra::register_extension_processors().
-// Its process_payload stands in audio-velocity.cpp, next to the spectrum node's, whose frame upload it shares.
+// Its process_payload stands in audio-effects.cpp, on the loop the handle nodes share (run_on_handle).
 #pragma once
 #include "audio-stream.hpp"
 

@@ -1,6 +1,6 @@
 // processor/audio-reverb.hpp — a node the reference has no class for: a convolution reverb on the library's long convolution (nae_conv_*;
 // DESIGN.md §3, "K10 long convolution").  Registered by infra::register_effect_processors().  Its process_payload stands in
-// audio-velocity.cpp, next to the filter node's, whose frame upload it shares.
+// audio-effects.cpp, on the loop the handle nodes share (run_on_handle).
 #pragma once
 #include "audio-stream.hpp"
 
