@@ -1,10 +1,11 @@
-"""ctypes binding of the CPU statement of the long convolution (tests/conv_ref/ref_conv.c), built with gcc -ffp-contract=off as tests/fir_ref.py
-builds the FIR filter's; the library also holds the float64 restatement of the reverb design and, through its include, ref_fir_run."""
+"""ctypes binding of the CPU statement of the long convolution (tests/conv_ref/ref_conv.c), built by tests/cstatement.py; the
+library also holds the float64 restatement of the reverb design and, through its include, ref_fir_run."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import cstatement
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "conv_ref", "ref_conv.c")
@@ -13,11 +14,7 @@ MAX_TAPS, MAX_PARTS, PICK_PARTS = 262144, 512, 16      # NAE_CONV_MAX_TAPS, NAE_
 
 
 def build(out_dir):
-    so = os.path.join(out_dir, "libref_conv.so")
-    r = subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", SRC, "-o", so, "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    L = C.CDLL(so)
+    L = cstatement.build(SRC, out_dir)
     L.ref_conv_pick_n_fft.argtypes = [C.c_int]
     L.ref_conv_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     L.ref_fir_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]

@@ -1,11 +1,12 @@
-"""ctypes binding of the CPU statement of the dynamics processor (tests/dyn_ref/ref_dyn.c), built with gcc -ffp-contract=off as tests/eq_ref.py
-builds the equalizer's, the float64 restatements of the design and of the static curve, and the parameter sets the tests share."""
+"""ctypes binding of the CPU statement of the dynamics processor (tests/dyn_ref/ref_dyn.c), built by tests/cstatement.py, the float64
+restatements of the design and of the static curve, and the parameter sets the tests share."""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
+
+import cstatement
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "dyn_ref", "ref_dyn.c")
@@ -37,11 +38,7 @@ SLOW = dict(alpha_attack=alpha(0.5), alpha_release=alpha(5.0))
 
 
 def build(out_dir):
-    so = os.path.join(out_dir, "libref_dyn.so")
-    r = subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", SRC, "-o", so, "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    L = C.CDLL(so)
+    L = cstatement.build(SRC, out_dir)
     L.ref_dyn_check.argtypes = [C.POINTER(Params)]
     L.ref_dyn_run.argtypes = [C.POINTER(Params), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
     L.ref_dyn_run_f64.argtypes = [C.POINTER(Params), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]

@@ -100,13 +100,6 @@ static void test_json()
 	}
 }
 
-static void print_registry()
-{
-	std::cout << "REGISTRY";
-	for (const auto& [id, info] : infra::Processor::processor_map) std::cout << " " << id;
-	std::cout << "\n";
-}
-
 static void test_registry()
 {
 	infra::register_all_processors();
@@ -121,29 +114,15 @@ static void test_registry()
 	infra::register_dynamics_processors();
 	print_registry();
 	CHECK(infra::Processor::processor_map.size() == 11 && infra::Processor::processor_map.count("audio_dynamics") == 1, "with the dynamics node: 11 entries");
-	if (infra::Processor::processor_map.count("audio_dynamics"))
-	{
-		const auto node = infra::Processor::processor_map.at("audio_dynamics").generate();
-		const auto pins = node->get_pin_attributes();
-		CHECK(node->get_processor_info_non_static().identifier == "audio_dynamics" && pins.size() == 2, "generate() gives the node: two pins");
-		int inputs = 0;
-		for (const auto& p : pins) inputs += p.is_input && p.type.get() == typeid(Audio_stream);
-		CHECK(inputs == 1, "one audio input pin, one audio output pin");
-	}
+	check_generated("audio_dynamics");
 }
 
 // noise whose level swells from far under to over the threshold, the right channel quieter: the link matters
 static std::vector<float> noise(size_t frames)
 {
-	std::vector<float> x(frames * 2);
-	uint64_t st = 4711;
+	std::vector<float> x = uniform_noise(frames * 2);
 	for (size_t n = 0; n < frames; n++)
-		for (int c = 0; c < 2; c++)
-		{
-			st = st * 6364136223846793005ull + 1442695040888963407ull;
-			const double u = (double)(st >> 40) / (double)(1ull << 24) * 2.0 - 1.0;
-			x[n * 2 + c] = (float)(u * (0.02 + 0.9 * (double)((n / 500) % 7) / 6.0) * (c ? 0.4 : 1.0));
-		}
+		for (int c = 0; c < 2; c++) x[n * 2 + c] = (float)((double)x[n * 2 + c] * (0.02 + 0.9 * (double)((n / 500) % 7) / 6.0) * (c ? 0.4 : 1.0));
 	return x;
 }
 
@@ -160,46 +139,6 @@ static Json::Value graph_json(double lookahead_ms)
 	return v;
 }
 
-// source -> audio_dynamics -> sink; the frames' shapes are checked in check_frames, the samples by the caller
-static bool run_graph(const std::vector<float>& x, const Json::Value& json, int frame_size, std::shared_ptr<Sink>& sink, std::string* error = nullptr)
-{
-	Runner r;
-	auto src = std::make_shared<Src>();
-	src->samples = x;
-	src->frame_size = frame_size;
-	auto dyn = std::make_shared<Audio_dynamics>();
-	dyn->deserialize(json);
-	sink = std::make_shared<Sink>();
-	r.add_node(1, src); r.add_node(2, dyn); r.add_node(3, sink);
-	r.add_link({1, "output", 2, "input"});
-	r.add_link({2, "output", 3, "input"});
-	const bool ok = r.run();
-	if (error) *error = r.get_processor_resources().at(2)->error_text;
-	return ok;
-}
-
-static void check_frames(const Sink& sink, const std::vector<float>& want, size_t S, int frame_size, const char* what)
-{
-	const size_t n_frames = (S + frame_size - 1) / frame_size;
-	CHECK(sink.frames.size() == n_frames, "as many frames as the source sent: " << sink.frames.size() << " vs " << n_frames);
-	size_t pos = 0, bad = 0;
-	bool shape_ok = true;
-	for (size_t f = 0; f < sink.frames.size(); f++)
-	{
-		const Frame_data* d = sink.frames[f]->data();
-		const int want_n = (int)std::min<size_t>(frame_size, S - std::min<size_t>(S, f * frame_size));
-		const int64_t want_pts = (int64_t)((0.5 + double(f * frame_size) / 48000) * 1000000);   // the source's own formula
-		shape_ok = shape_ok && d->nb_samples == want_n && d->format == AV_SAMPLE_FMT_FLT && d->ch_layout.nb_channels == 2 && d->sample_rate == 48000 &&
-				   d->pts == want_pts && d->time_base.num == 1 && d->time_base.den == 1000000;
-		const float* got = reinterpret_cast<const float*>(d->data[0]);
-		for (int i = 0; i < d->nb_samples && pos < S; i++, pos++)
-			for (int c = 0; c < 2; c++) bad += std::memcmp(&got[i * 2 + c], &want[pos * 2 + c], sizeof(float)) != 0;
-	}
-	CHECK(shape_ok, "frames of the input's sizes, format FLT, the source's pts and time base");
-	CHECK(pos == S, "as many samples as the source sent: " << pos);
-	CHECK(bad == 0, what << ": " << bad << " words differ");
-}
-
 static void test_gpu()
 {
 	const int S = 20000, frame_size = 1152;
@@ -208,25 +147,14 @@ static void test_gpu()
 	{
 		std::shared_ptr<Sink> sink;
 		std::string error;
-		const bool ok = run_graph(x, graph_json(lookahead_ms), frame_size, sink, &error);
+		const bool ok = run_graph<Audio_dynamics>(x, graph_json(lookahead_ms), frame_size, sink, &error);
 		CHECK(ok, "source -> audio_dynamics -> sink runs: " << error);
 		if (!ok) return;
-		// the block call on the same samples with the designed parameters, through a context of its own
+		// the block call on the same samples with the designed parameters
 		nae_dyn_params params;
 		CHECK(nae_dyn_design(48000, -20, 6, 4, 0.0015, 0.06, lookahead_ms / 1000.0, 3, 1, &params) == 0 && params.lookahead == (lookahead_ms > 0 ? 120 : 0), "design");
-		nae_ctx* ctx = nullptr;
-		CHECK(nae_ctx_create(0, &ctx) == 0, "context");
-		if (!ctx) return;
-		std::vector<float> y((size_t)S * 2);
-		void *d_x = nullptr, *d_y = nullptr;
-		CHECK(nae_malloc(ctx, x.size() * sizeof(float), &d_x) == 0 && nae_malloc(ctx, y.size() * sizeof(float), &d_y) == 0, "malloc");
-		CHECK(nae_memcpy_h2d(ctx, d_x, x.data(), x.size() * sizeof(float)) == 0, "h2d");
-		const nae_sig sx{d_x, 0, 1, 2}, sy{d_y, 0, 1, 2};
-		CHECK(nae_dyn_block_f32(ctx, &params, &sx, S, 2, 1, &sy) == 0, "block call");
-		CHECK(nae_memcpy_d2h(ctx, y.data(), d_y, y.size() * sizeof(float)) == 0 && nae_sync(ctx) == 0, "d2h");
-		nae_free(ctx, d_x);
-		nae_free(ctx, d_y);
-		nae_ctx_destroy(ctx);
+		const std::vector<float> y = block_call(x, S, [&](nae_ctx* ctx, const nae_sig* sx, const nae_sig* sy) { return nae_dyn_block_f32(ctx, &params, sx, S, 2, 1, sy); });
+		if (y.empty()) return;
 		size_t changed = 0;
 		for (size_t i = 0; i < y.size(); i++) changed += std::fabs(y[i]) < 0.8f * std::fabs(x[i]);
 		CHECK(changed > y.size() / 10, "the graph's parameters compress: " << changed << " samples reduced");
@@ -239,30 +167,13 @@ static void test_lookahead()
 	const std::vector<float> x = noise(4000);
 	Json::Value v;
 	v["lookahead_ms"] = 20;   // 960 samples at the source's 48 kHz would do; the source below plays at 96 kHz: 1920
-	Runner r;
-	auto src = std::make_shared<Src>();
-	src->samples = x;
-	src->sample_rate = 96000;
-	auto dyn = std::make_shared<Audio_dynamics>();
-	dyn->deserialize(v);
-	auto sink = std::make_shared<Sink>();
-	r.add_node(1, src); r.add_node(2, dyn); r.add_node(3, sink);
-	r.add_link({1, "output", 2, "input"});
-	r.add_link({2, "output", 3, "input"});
-	const bool ok = r.run();
-	const std::string error = r.get_processor_resources().at(2)->error_text;
+	std::shared_ptr<Sink> sink;
+	std::string error;
+	const bool ok = run_graph<Audio_dynamics>(x, v, 1152, sink, &error, 96000);
 	CHECK(!ok && error.find("lookahead 20 ms at 96000 Hz") != std::string::npos, "a look-ahead of 1920 samples fails the run on the first frame: " << error);
 }
 
 int main(int argc, char** argv)
 {
-	const std::string mode = argc > 1 ? argv[1] : "json";
-	if (mode == "json") test_json();
-	else if (mode == "registry") test_registry();
-	else if (mode == "gpu") test_gpu();
-	else if (mode == "lookahead") test_lookahead();
-	else { std::cout << "usage: host_dyn_node json|registry|gpu|lookahead\n"; return 2; }
-	if (failures) { std::cout << failures << " failure(s)\n"; return 1; }
-	std::cout << "HOST DYN OK " << mode << "\n";
-	return 0;
+	return harness_main(argc, argv, "DYN", {{"json", test_json}, {"registry", test_registry}, {"gpu", test_gpu}, {"lookahead", test_lookahead}});
 }

@@ -1,11 +1,12 @@
-"""ctypes binding of the CPU statement of the biquad cascade (tests/eq_ref/ref_eq.c), built with gcc -ffp-contract=off as tests/fir_ref.py builds
-the FIR filter's, the float64 restatement of the design, the magnitude of a cascade from its coefficients, and the cascades the tests share."""
+"""ctypes binding of the CPU statement of the biquad cascade (tests/eq_ref/ref_eq.c), built by tests/cstatement.py, the float64
+restatement of the design, the magnitude of a cascade from its coefficients, and the cascades the tests share."""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
+
+import cstatement
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "eq_ref", "ref_eq.c")
@@ -20,11 +21,7 @@ GOOD_SECTIONS = ((1, 0, 0, 0, 0), (1, 0, 0, 1.499, 0.5), (1, 0, 0, 0, 0.999), (1
 
 
 def build(out_dir):
-    so = os.path.join(out_dir, "libref_eq.so")
-    r = subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", SRC, "-o", so, "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    L = C.CDLL(so)
+    L = cstatement.build(SRC, out_dir)
     L.ref_eq_check.argtypes = [C.c_void_p, C.c_int]
     for name in ("ref_eq_run", "ref_eq_run_f64", "ref_eq_sequential", "ref_eq_sequential_f32"):
         getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]

@@ -168,13 +168,6 @@ static void test_json()
 	}
 }
 
-static void print_registry()
-{
-	std::cout << "REGISTRY";
-	for (const auto& [id, info] : infra::Processor::processor_map) std::cout << " " << id;
-	std::cout << "\n";
-}
-
 static void test_registry()
 {
 	infra::register_all_processors();
@@ -185,27 +178,7 @@ static void test_registry()
 	infra::register_equalizer_processors();
 	print_registry();
 	CHECK(infra::Processor::processor_map.size() == 10 && infra::Processor::processor_map.count("audio_eq") == 1, "with the equalizer: 10 entries");
-	if (infra::Processor::processor_map.count("audio_eq"))
-	{
-		const auto node = infra::Processor::processor_map.at("audio_eq").generate();
-		const auto pins = node->get_pin_attributes();
-		CHECK(node->get_processor_info_non_static().identifier == "audio_eq" && pins.size() == 2, "generate() gives the node: two pins");
-		int inputs = 0;
-		for (const auto& p : pins) inputs += p.is_input && p.type.get() == typeid(Audio_stream);
-		CHECK(inputs == 1, "one audio input pin, one audio output pin");
-	}
-}
-
-static std::vector<float> noise(size_t n)
-{
-	std::vector<float> x(n);
-	uint64_t st = 4711;
-	for (auto& v : x)
-	{
-		st = st * 6364136223846793005ull + 1442695040888963407ull;
-		v = (float)((double)(st >> 40) / (double)(1ull << 24) * 2.0 - 1.0);
-	}
-	return x;
+	check_generated("audio_eq");
 }
 
 struct Band_spec { const char* kind; double freq, gain_db, q; };
@@ -227,56 +200,16 @@ static Json::Value graph_json()
 	return v;
 }
 
-// source -> audio_eq -> sink; the frames' shapes are checked here, the samples by the caller
-static bool run_graph(const std::vector<float>& x, const Json::Value& json, int frame_size, std::shared_ptr<Sink>& sink, std::string* error = nullptr)
-{
-	Runner r;
-	auto src = std::make_shared<Src>();
-	src->samples = x;
-	src->frame_size = frame_size;
-	auto eq = std::make_shared<Audio_eq>();
-	eq->deserialize(json);
-	sink = std::make_shared<Sink>();
-	r.add_node(1, src); r.add_node(2, eq); r.add_node(3, sink);
-	r.add_link({1, "output", 2, "input"});
-	r.add_link({2, "output", 3, "input"});
-	const bool ok = r.run();
-	if (error) *error = r.get_processor_resources().at(2)->error_text;
-	return ok;
-}
-
-static void check_frames(const Sink& sink, const std::vector<float>& want, size_t S, int frame_size, const char* what)
-{
-	const size_t n_frames = (S + frame_size - 1) / frame_size;
-	CHECK(sink.frames.size() == n_frames, "as many frames as the source sent: " << sink.frames.size() << " vs " << n_frames);
-	size_t pos = 0, bad = 0;
-	bool shape_ok = true;
-	for (size_t f = 0; f < sink.frames.size(); f++)
-	{
-		const Frame_data* d = sink.frames[f]->data();
-		const int want_n = (int)std::min<size_t>(frame_size, S - std::min<size_t>(S, f * frame_size));
-		const int64_t want_pts = (int64_t)((0.5 + double(f * frame_size) / 48000) * 1000000);   // the source's own formula
-		shape_ok = shape_ok && d->nb_samples == want_n && d->format == AV_SAMPLE_FMT_FLT && d->ch_layout.nb_channels == 2 && d->sample_rate == 48000 &&
-				   d->pts == want_pts && d->time_base.num == 1 && d->time_base.den == 1000000;
-		const float* got = reinterpret_cast<const float*>(d->data[0]);
-		for (int i = 0; i < d->nb_samples && pos < S; i++, pos++)
-			for (int c = 0; c < 2; c++) bad += std::memcmp(&got[i * 2 + c], &want[pos * 2 + c], sizeof(float)) != 0;
-	}
-	CHECK(shape_ok, "frames of the input's sizes, format FLT, the source's pts and time base");
-	CHECK(pos == S, "as many samples as the source sent: " << pos);
-	CHECK(bad == 0, what << ": " << bad << " words differ");
-}
-
 static void test_gpu()
 {
 	const int S = 20000, frame_size = 1152;
-	const std::vector<float> x = noise((size_t)S * 2);
+	const std::vector<float> x = uniform_noise((size_t)S * 2);
 	std::shared_ptr<Sink> sink;
 	std::string error;
-	const bool ok = run_graph(x, graph_json(), frame_size, sink, &error);
+	const bool ok = run_graph<Audio_eq>(x, graph_json(), frame_size, sink, &error);
 	CHECK(ok, "source -> audio_eq -> sink runs: " << error);
 	if (!ok) return;
-	// the block call on the same samples with the designed coefficients, through a context of its own
+	// the block call on the same samples with the designed coefficients
 	constexpr int n_bands = sizeof(graph_bands) / sizeof(graph_bands[0]);
 	double coef[n_bands * 5];
 	for (int i = 0; i < n_bands; i++)
@@ -285,33 +218,22 @@ static void test_gpu()
 		while (std::string(kinds[k]) != graph_bands[i].kind) k++;
 		CHECK(nae_eq_design(k, 48000, graph_bands[i].freq, graph_bands[i].gain_db, graph_bands[i].q, coef + 5 * i) == 0, "design");
 	}
-	nae_ctx* ctx = nullptr;
-	CHECK(nae_ctx_create(0, &ctx) == 0, "context");
-	if (!ctx) return;
-	std::vector<float> y((size_t)S * 2);
-	void *d_x = nullptr, *d_y = nullptr;
-	CHECK(nae_malloc(ctx, x.size() * sizeof(float), &d_x) == 0 && nae_malloc(ctx, y.size() * sizeof(float), &d_y) == 0, "malloc");
-	CHECK(nae_memcpy_h2d(ctx, d_x, x.data(), x.size() * sizeof(float)) == 0, "h2d");
-	const nae_sig sx{d_x, 0, 1, 2}, sy{d_y, 0, 1, 2};
-	CHECK(nae_eq_block_f32(ctx, coef, n_bands, &sx, S, 2, 1, &sy) == 0, "block call");
-	CHECK(nae_memcpy_d2h(ctx, y.data(), d_y, y.size() * sizeof(float)) == 0 && nae_sync(ctx) == 0, "d2h");
-	nae_free(ctx, d_x);
-	nae_free(ctx, d_y);
-	nae_ctx_destroy(ctx);
+	const std::vector<float> y = block_call(x, S, [&](nae_ctx* ctx, const nae_sig* sx, const nae_sig* sy) { return nae_eq_block_f32(ctx, coef, n_bands, sx, S, 2, 1, sy); });
+	if (y.empty()) return;
 	check_frames(*sink, y, S, frame_size, "the block call's samples with the designed coefficients");
 }
 
 static void test_wire()
 {
 	const int S = 5000, frame_size = 1152;
-	const std::vector<float> x = noise((size_t)S * 2);
+	const std::vector<float> x = uniform_noise((size_t)S * 2);
 	for (int empty = 0; empty < 2; empty++)
 	{
 		Json::Value v;
 		if (empty) v["bands"] = Json::Value(Json::arrayValue);
 		std::shared_ptr<Sink> sink;
 		std::string error;
-		const bool ok = run_graph(x, v, frame_size, sink, &error);
+		const bool ok = run_graph<Audio_eq>(x, v, frame_size, sink, &error);
 		CHECK(ok, "the wire runs: " << error);
 		if (ok) check_frames(*sink, x, S, frame_size, empty ? "empty bands: the input's bits" : "absent bands: the input's bits");
 	}
@@ -319,25 +241,16 @@ static void test_wire()
 
 static void test_nyquist()
 {
-	const std::vector<float> x = noise(4000);
+	const std::vector<float> x = uniform_noise(4000);
 	Json::Value b;
 	b["freq"] = 24000;    // Nyquist at the source's 48 kHz
 	std::shared_ptr<Sink> sink;
 	std::string error;
-	const bool ok = run_graph(x, one_band(b), 1152, sink, &error);
+	const bool ok = run_graph<Audio_eq>(x, one_band(b), 1152, sink, &error);
 	CHECK(!ok && error.find("band 0") != std::string::npos, "a band at Nyquist fails the run on the first frame: " << error);
 }
 
 int main(int argc, char** argv)
 {
-	const std::string mode = argc > 1 ? argv[1] : "json";
-	if (mode == "json") test_json();
-	else if (mode == "registry") test_registry();
-	else if (mode == "gpu") test_gpu();
-	else if (mode == "wire") test_wire();
-	else if (mode == "nyquist") test_nyquist();
-	else { std::cout << "usage: host_eq_node json|registry|gpu|wire|nyquist\n"; return 2; }
-	if (failures) { std::cout << failures << " failure(s)\n"; return 1; }
-	std::cout << "HOST EQ OK " << mode << "\n";
-	return 0;
+	return harness_main(argc, argv, "EQ", {{"json", test_json}, {"registry", test_registry}, {"gpu", test_gpu}, {"wire", test_wire}, {"nyquist", test_nyquist}});
 }

@@ -1,11 +1,12 @@
-"""ctypes binding of the CPU statement of the FIR filter (tests/fir_ref/ref_fir.c), built with gcc -ffp-contract=off as tests/pv_ref.py builds
-the vocoder's, and the float64 restatements the CPU tests compare against: the direct convolution and the Kaiser-8 designs."""
+"""ctypes binding of the CPU statement of the FIR filter (tests/fir_ref/ref_fir.c), built by tests/cstatement.py, and the float64 restatements
+the CPU tests compare against: the direct convolution and the Kaiser-8 designs."""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
+
+import cstatement
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "fir_ref", "ref_fir.c")
@@ -15,11 +16,7 @@ KAISER_BETA = 8.0
 
 
 def build(out_dir):
-    so = os.path.join(out_dir, "libref_fir.so")
-    r = subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", SRC, "-o", so, "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    L = C.CDLL(so)
+    L = cstatement.build(SRC, out_dir)
     L.ref_fir_pick_n_fft.argtypes = [C.c_int]
     L.ref_fir_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     return L

@@ -105,13 +105,6 @@ static void test_json()
 	}
 }
 
-static void print_registry()
-{
-	std::cout << "REGISTRY";
-	for (const auto& [id, info] : infra::Processor::processor_map) std::cout << " " << id;
-	std::cout << "\n";
-}
-
 static void test_registry()
 {
 	infra::register_all_processors();
@@ -120,98 +113,39 @@ static void test_registry()
 	infra::register_extension_processors();
 	print_registry();
 	CHECK(infra::Processor::processor_map.size() == 8 && infra::Processor::processor_map.count("audio_filter") == 1, "with the extensions: 8 entries");
-	if (infra::Processor::processor_map.count("audio_filter"))
-	{
-		const auto node = infra::Processor::processor_map.at("audio_filter").generate();
-		const auto pins = node->get_pin_attributes();
-		CHECK(node->get_processor_info_non_static().identifier == "audio_filter" && pins.size() == 2, "generate() gives the node: two pins");
-		int inputs = 0;
-		for (const auto& p : pins) inputs += p.is_input && p.type.get() == typeid(Audio_stream);
-		CHECK(inputs == 1, "one audio input pin, one audio output pin");
-	}
+	check_generated("audio_filter");
 }
 
 static void test_gpu()
 {
 	const int S = 20000, L = 513, D = (L - 1) / 2, frame_size = 1152;
-	std::vector<float> x((size_t)S * 2);
-	uint64_t st = 4711;
-	for (auto& v : x)
-	{
-		st = st * 6364136223846793005ull + 1442695040888963407ull;
-		v = (float)((double)(st >> 40) / (double)(1ull << 24) * 2.0 - 1.0);
-	}
-	Runner r;
-	auto src = std::make_shared<Src>();
-	src->samples = x;
-	src->frame_size = frame_size;
-	auto filter = std::make_shared<Audio_filter>();
+	const std::vector<float> x = uniform_noise((size_t)S * 2);
 	Json::Value v;
 	v["kind"] = "lowpass";
 	v["f_hi"] = 1000;
 	v["taps"] = L;
-	filter->deserialize(v);
-	auto sink = std::make_shared<Sink>();
-	r.add_node(1, src); r.add_node(2, filter); r.add_node(3, sink);
-	r.add_link({1, "output", 2, "input"});
-	r.add_link({2, "output", 3, "input"});
-	const bool ok = r.run();
-	CHECK(ok, "source -> audio_filter -> sink runs: " << r.get_processor_resources().at(2)->error_text);
+	std::shared_ptr<Sink> sink;
+	std::string error;
+	const bool ok = run_graph<Audio_filter>(x, v, frame_size, sink, &error);
+	CHECK(ok, "source -> audio_filter -> sink runs: " << error);
 	if (!ok) return;
-	// the block call on the same samples, and on the samples extended by L - 1 zeros (the flushed tail), through a context of its own
+	// the block call on the same samples, and on the samples extended by L - 1 zeros (the flushed tail)
 	std::vector<float> taps(L);
 	CHECK(nae_fir_design(0, 48000, 0, 1000, L, taps.data()) == 0, "design");
-	nae_ctx* ctx = nullptr;
-	CHECK(nae_ctx_create(0, &ctx) == 0, "context");
-	if (!ctx) return;
 	const size_t E = (size_t)S + L - 1;
-	std::vector<float> xe(E * 2, 0.0f), y((size_t)S * 2), ye(E * 2);
+	std::vector<float> xe(E * 2, 0.0f);
 	std::memcpy(xe.data(), x.data(), x.size() * sizeof(float));
-	void *d_x = nullptr, *d_y = nullptr;
-	CHECK(nae_malloc(ctx, xe.size() * sizeof(float), &d_x) == 0 && nae_malloc(ctx, ye.size() * sizeof(float), &d_y) == 0, "malloc");
-	CHECK(nae_memcpy_h2d(ctx, d_x, xe.data(), xe.size() * sizeof(float)) == 0, "h2d");
-	const nae_sig sx{d_x, 0, 1, 2}, sy{d_y, 0, 1, 2};
-	CHECK(nae_fir_block_f32(ctx, taps.data(), L, 0, &sx, S, 2, 1, &sy) == 0, "block call");
-	CHECK(nae_memcpy_d2h(ctx, y.data(), d_y, y.size() * sizeof(float)) == 0 && nae_sync(ctx) == 0, "d2h");
-	CHECK(nae_fir_block_f32(ctx, taps.data(), L, 0, &sx, E, 2, 1, &sy) == 0, "block call on the zero-extended input");
-	CHECK(nae_memcpy_d2h(ctx, ye.data(), d_y, ye.size() * sizeof(float)) == 0 && nae_sync(ctx) == 0, "d2h");
-	nae_free(ctx, d_x);
-	nae_free(ctx, d_y);
-	nae_ctx_destroy(ctx);
-
-	const size_t n_frames = ((size_t)S + frame_size - 1) / frame_size;
-	CHECK(sink->frames.size() == n_frames, "as many frames as the source sent: " << sink->frames.size() << " vs " << n_frames);
-	size_t pos = 0, bad = 0;
-	bool shape_ok = true;
-	for (size_t f = 0; f < sink->frames.size(); f++)
-	{
-		const Frame_data* d = sink->frames[f]->data();
-		const int want_n = (int)std::min<size_t>(frame_size, (size_t)S - std::min<size_t>(S, f * frame_size));
-		const int64_t want_pts = (int64_t)((0.5 + double(f * frame_size) / 48000) * 1000000);   // the source's own formula
-		shape_ok = shape_ok && d->nb_samples == want_n && d->format == AV_SAMPLE_FMT_FLT && d->ch_layout.nb_channels == 2 && d->sample_rate == 48000 &&
-				   d->pts == want_pts && d->time_base.num == 1 && d->time_base.den == 1000000;
-		const float* got = reinterpret_cast<const float*>(d->data[0]);
-		for (int i = 0; i < d->nb_samples && pos < (size_t)S; i++, pos++)
-			for (int c = 0; c < 2; c++)
-			{
-				const size_t n = pos + D;
-				const float want = n < (size_t)S ? y[n * 2 + c] : ye[n * 2 + c];
-				bad += std::memcmp(&got[i * 2 + c], &want, sizeof(float)) != 0;
-			}
-	}
-	CHECK(shape_ok, "frames of the input's sizes, format FLT, the source's pts and time base");
-	CHECK(pos == (size_t)S, "as many samples as the source sent: " << pos);
-	CHECK(bad == 0, "sample n = y[n + 256] of the block call, past the input's end the flushed tail: " << bad << " words differ");
+	const auto fir = [&](size_t n) { return [&taps, n](nae_ctx* ctx, const nae_sig* sx, const nae_sig* sy) { return nae_fir_block_f32(ctx, taps.data(), L, 0, sx, n, 2, 1, sy); }; };
+	const std::vector<float> y = block_call(x, S, fir(S)), ye = block_call(xe, E, fir(E));
+	if (y.empty() || ye.empty()) return;
+	// sample n = y[n + D] inside the input, past its end the zero-extended call's
+	std::vector<float> want((size_t)S * 2);
+	for (size_t n = 0; n < (size_t)S; n++)
+		for (int c = 0; c < 2; c++) want[n * 2 + c] = n + D < (size_t)S ? y[(n + D) * 2 + c] : ye[(n + D) * 2 + c];
+	check_frames(*sink, want, S, frame_size, "sample n = y[n + 256] of the block call, past the input's end the flushed tail");
 }
 
 int main(int argc, char** argv)
 {
-	const std::string mode = argc > 1 ? argv[1] : "json";
-	if (mode == "json") test_json();
-	else if (mode == "registry") test_registry();
-	else if (mode == "gpu") test_gpu();
-	else { std::cout << "usage: host_fir_node json|registry|gpu\n"; return 2; }
-	if (failures) { std::cout << failures << " failure(s)\n"; return 1; }
-	std::cout << "HOST FIR OK " << mode << "\n";
-	return 0;
+	return harness_main(argc, argv, "FIR", {{"json", test_json}, {"registry", test_registry}, {"gpu", test_gpu}});
 }

@@ -1,22 +1,29 @@
-// node_harness.hpp — what the host node harnesses (tests/pv_ref/host_pv_node.cpp, tests/spec_sizes/host_spectrum.cpp) share: a CHECK that
-// counts failures, a source node that plays interleaved stereo f32 in frames of frame_size, a sink node that keeps every frame, and
-// rejects<Node>(json, field), true when deserializing json throws "Wrong field: <field>".
+// node_harness.hpp — what the host node harnesses share.  All of them (tests/pv_ref/host_pv_node.cpp, tests/spec_sizes/host_spectrum.cpp and the
+// four effect nodes'): a CHECK that counts its evaluations and its failures, a source node that plays interleaved stereo f32 in frames of
+// frame_size, a sink node that keeps every frame, and rejects<Node>(json, field), true when deserializing json throws "Wrong field: <field>".
+// The effect nodes' (tests/fir_ref/host_fir_node.cpp, conv_ref/host_conv_node.cpp, eq_ref/host_eq_node.cpp, dyn_ref/host_dyn_node.cpp) besides:
+// uniform_noise, run_graph<Node> (source -> node -> sink), check_frames (the sink's frames against the source's shapes and the wanted words),
+// block_call (a block entry through a context of its own), print_registry / check_generated, and harness_main (the mode dispatch).
 #pragma once
 #include "infra/runner.hpp"
 #include "processor/audio-velocity.hpp"
 #include "nae_gpu.h"
 
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <iostream>
 
 using namespace processor;
 using infra::Runner;
 
-static int failures = 0;
+inline int failures = 0;
+inline long checks = 0;   // CHECKs evaluated: harness_main prints it, so that a harness that stops checking shows
 #define CHECK(cond, msg)                                                                       \
 	do {                                                                                       \
+		checks++;                                                                              \
 		if (!(cond)) { std::cout << "FAIL " << __LINE__ << ": " << msg << "\n"; failures++; } \
 	} while (0)
 
@@ -120,4 +127,123 @@ static bool rejects(const Json::Value& v, const std::string& field)
 {
 	Node node;
 	return rejects(node, v, field);
+}
+
+// n_floats draws from [-1, 1).  Every draw is k / 2^23 - 1 with k < 2^24: exact in float, so shaping it in double loses nothing.
+inline std::vector<float> uniform_noise(size_t n_floats, uint64_t seed = 4711)
+{
+	std::vector<float> x(n_floats);
+	for (auto& v : x)
+	{
+		seed = seed * 6364136223846793005ull + 1442695040888963407ull;
+		v = (float)((double)(seed >> 40) / (double)(1ull << 24) * 2.0 - 1.0);
+	}
+	return x;
+}
+
+// source -> Node (deserialized from json) -> sink; the frames' shapes are checked in check_frames, the samples by the caller
+template <class Node>
+bool run_graph(const std::vector<float>& x, const Json::Value& json, int frame_size, std::shared_ptr<Sink>& sink, std::string* error = nullptr,
+			   int sample_rate = 48000)
+{
+	Runner r;
+	auto src = std::make_shared<Src>();
+	src->samples = x;
+	src->frame_size = frame_size;
+	src->sample_rate = sample_rate;
+	auto node = std::make_shared<Node>();
+	node->deserialize(json);
+	sink = std::make_shared<Sink>();
+	r.add_node(1, src); r.add_node(2, node); r.add_node(3, sink);
+	r.add_link({1, "output", 2, "input"});
+	r.add_link({2, "output", 3, "input"});
+	const bool ok = r.run();
+	if (error) *error = r.get_processor_resources().at(2)->error_text;
+	return ok;
+}
+
+// the sink holds the frames a 48 kHz source of S stereo samples sent, and their words are want's
+inline void check_frames(const Sink& sink, const std::vector<float>& want, size_t S, int frame_size, const char* what)
+{
+	const size_t n_frames = (S + frame_size - 1) / frame_size;
+	CHECK(sink.frames.size() == n_frames, "as many frames as the source sent: " << sink.frames.size() << " vs " << n_frames);
+	size_t pos = 0, bad = 0;
+	bool shape_ok = true;
+	for (size_t f = 0; f < sink.frames.size(); f++)
+	{
+		const Frame_data* d = sink.frames[f]->data();
+		const int want_n = (int)std::min<size_t>(frame_size, S - std::min<size_t>(S, f * frame_size));
+		const int64_t want_pts = (int64_t)((0.5 + double(f * frame_size) / 48000) * 1000000);   // the source's own formula
+		shape_ok = shape_ok && d->nb_samples == want_n && d->format == AV_SAMPLE_FMT_FLT && d->ch_layout.nb_channels == 2 && d->sample_rate == 48000 &&
+				   d->pts == want_pts && d->time_base.num == 1 && d->time_base.den == 1000000;
+		const float* got = reinterpret_cast<const float*>(d->data[0]);
+		for (int i = 0; i < d->nb_samples && pos < S; i++, pos++)
+			for (int c = 0; c < 2; c++) bad += std::memcmp(&got[i * 2 + c], &want[pos * 2 + c], sizeof(float)) != 0;
+	}
+	CHECK(shape_ok, "frames of the input's sizes, format FLT, the source's pts and time base");
+	CHECK(pos == S, "as many samples as the source sent: " << pos);
+	CHECK(bad == 0, what << ": " << bad << " words differ");
+}
+
+// interleaved stereo x through a block entry, in a context of its own: call(ctx, &src, &dst) returns the entry's status -> the first out_frames
+// frames of the destination; empty when there is no context
+template <class Call>
+std::vector<float> block_call(const std::vector<float>& x, size_t out_frames, Call call)
+{
+	nae_ctx* ctx = nullptr;
+	CHECK(nae_ctx_create(0, &ctx) == 0, "context");
+	if (!ctx) return {};
+	std::vector<float> y(out_frames * 2);
+	void *d_x = nullptr, *d_y = nullptr;
+	CHECK(nae_malloc(ctx, x.size() * sizeof(float), &d_x) == 0 && nae_malloc(ctx, y.size() * sizeof(float), &d_y) == 0, "malloc");
+	CHECK(nae_memcpy_h2d(ctx, d_x, x.data(), x.size() * sizeof(float)) == 0, "h2d");
+	const nae_sig sx{d_x, 0, 1, 2}, sy{d_y, 0, 1, 2};
+	CHECK(call(ctx, &sx, &sy) == 0, "block call");
+	CHECK(nae_memcpy_d2h(ctx, y.data(), d_y, y.size() * sizeof(float)) == 0 && nae_sync(ctx) == 0, "d2h");
+	nae_free(ctx, d_x);
+	nae_free(ctx, d_y);
+	nae_ctx_destroy(ctx);
+	return y;
+}
+
+inline void print_registry()
+{
+	std::cout << "REGISTRY";
+	for (const auto& [id, info] : infra::Processor::processor_map) std::cout << " " << id;
+	std::cout << "\n";
+}
+
+// what the registry generates for id is that node: two pins, one of them an audio input
+inline void check_generated(const std::string& id)
+{
+	if (!infra::Processor::processor_map.count(id)) return;
+	const auto node = infra::Processor::processor_map.at(id).generate();
+	const auto pins = node->get_pin_attributes();
+	CHECK(node->get_processor_info_non_static().identifier == id && pins.size() == 2, "generate() gives the node: two pins");
+	int inputs = 0;
+	for (const auto& p : pins) inputs += p.is_input && p.type.get() == typeid(Audio_stream);
+	CHECK(inputs == 1, "one audio input pin, one audio output pin");
+}
+
+// main() of host_<name>_node: runs the mode argv[1] names ("json" without one) -> 0 and "HOST <NAME> OK <mode>", 1 after a failed CHECK, 2 and
+// the usage line for an unknown mode
+struct Mode_entry { const char* name; void (*run)(); };
+inline int harness_main(int argc, char** argv, const char* name, std::initializer_list<Mode_entry> modes)
+{
+	const std::string mode = argc > 1 ? argv[1] : "json";
+	for (const auto& m : modes)
+	{
+		if (mode != m.name) continue;
+		m.run();
+		std::cout << "CHECKS " << checks << "\n";
+		if (failures) { std::cout << failures << " failure(s)\n"; return 1; }
+		std::cout << "HOST " << name << " OK " << mode << "\n";
+		return 0;
+	}
+	std::cout << "usage: host_";
+	for (const char* c = name; *c; c++) std::cout << (char)std::tolower(*c);
+	std::cout << "_node";
+	for (const auto& m : modes) std::cout << (&m == modes.begin() ? " " : "|") << m.name;
+	std::cout << "\n";
+	return 2;
 }

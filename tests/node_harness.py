@@ -1,5 +1,6 @@
-"""Builds a host node harness (tests/pv_ref/host_pv_node.cpp, tests/spec_sizes/host_spectrum.cpp; both include tests/node_harness.hpp)
-against a current library and host archive, with the flags of tests/host/Makefile."""
+"""Builds a host node harness (tests/pv_ref/host_pv_node.cpp, tests/spec_sizes/host_spectrum.cpp and the four effect nodes'
+tests/*_ref/host_*_node.cpp; all include tests/node_harness.hpp) against a current library and host archive, with the flags of
+tests/host/Makefile."""
 import os
 import subprocess
 

@@ -1,11 +1,11 @@
 """ctypes binding of the CPU statement of the vocoder (tests/pv_ref/ref_pv.c): every frame size, the phase lock, the formant lifter,
-transient preservation, the formant shift and the channel link.  Built with gcc -ffp-contract=off against oracle/libnae_oracle.so."""
+transient preservation, the formant shift and the channel link.  Built by tests/cstatement.py against oracle/libnae_oracle.so."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import cstatement
 import orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,12 +17,7 @@ SHIFT_MIN, SHIFT_MAX = 0.25, 4.0
 
 def build(out_dir):
     orc.lib()                                           # builds oracle/libnae_oracle.so when it is missing
-    so = os.path.join(out_dir, "libref_pv.so")
-    r = subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", SRC, "-o", so,
-                        "-L" + orc.ORACLE_DIR, "-lnae_oracle", "-Wl,-rpath," + orc.ORACLE_DIR, "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    L = C.CDLL(so)
+    L = cstatement.build(SRC, out_dir, ("-L" + orc.ORACLE_DIR, "-lnae_oracle", "-Wl,-rpath," + orc.ORACLE_DIR))
     L.ref_pv_plan.argtypes = [C.c_double, C.c_double, C.c_int, C.c_size_t, C.POINTER(orc.Plan)]
     L.ref_pv_fs_plan.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_size_t, C.POINTER(orc.Plan)]
     # src, L, ch, rate, pitch, N, lock, q, transients, shift, phi, link, dst, qs, on, sig, qdiff

@@ -4,37 +4,26 @@ view, every accumulate tile, slabs of one and two blocks and a wrapped ring, the
 error codes, and the host node (tests/conv_ref/host_conv_node.cpp)."""
 import ctypes as C
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import conv_ref
 import node_harness
-from fir_gpu import CONFIGS, _bits, _noise, gpu_fir
+from block_gpu import CONFIGS, bits, flushed, noise, statement, stream, view_call
+from fir_gpu import gpu_fir
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def ref():
-    with tempfile.TemporaryDirectory(prefix="ref_conv_gpu") as tmp:
-        yield conv_ref.build(tmp)
+    return statement(conv_ref)
 
 
-class _AsFir:
-    """gpu_fir (tests/fir_gpu.py: every view, NaN-filled gaps, sentinels behind the destination) calls ctx.fir_block: here that is conv_block"""
-
-    def __init__(self, ctx):
-        self.array = ctx.array
-
-        def fir_block(taps, src, n, ch, n_streams, dst, n_fft):
-            ctx.conv_block(taps, src, n, ch, n_streams, dst, n_fft)
-        self.fir_block = fir_block
-
-
-def gpu_conv(nae, ctx, taps, n_fft, x, sl="i", dl="i", shared=False, **kw):
-    return gpu_fir(nae, _AsFir(ctx), taps, n_fft, x, sl, dl, shared, **kw)
+def gpu_conv(nae, ctx, taps, n_fft, x, *views, **kw):
+    """x[streams, n, ch] -> y[streams, n, ch] through nae_conv_block_f32 in a view of block_gpu.view_call's"""
+    return view_call(nae, ctx, lambda src, n, ch, n_streams, dst: ctx.conv_block(taps, src, n, ch, n_streams, dst, n_fft), x, *views, **kw)
 
 
 def _taps(rng, L, taps_ch=1):
@@ -44,7 +33,7 @@ def _taps(rng, L, taps_ch=1):
 def _check(nae, ctx, ref, taps, n_fft, x, *a, **kw):
     got = gpu_conv(nae, ctx, taps, n_fft, x, *a, **kw)
     want = conv_ref.run_streams(ref, taps, n_fft, x)
-    assert np.array_equal(_bits(got), _bits(want)), (n_fft, taps.shape, x.shape, a, kw)
+    assert np.array_equal(bits(got), bits(want)), (n_fft, taps.shape, x.shape, a, kw)
     return got
 
 
@@ -54,7 +43,7 @@ def test_block_bits_in_every_view(nae, ctx, ref, L):
     rng = np.random.default_rng(L)
     in_len = 7 * 256 + 3
     for ch, n_streams, sl, dl, shared in CONFIGS:
-        x = _noise(rng, n_streams, in_len, ch, shared)
+        x = noise(rng, n_streams, in_len, ch, shared)
         for taps_ch in sorted({1, ch}):
             _check(nae, ctx, ref, _taps(rng, L, taps_ch), 512, x, sl, dl, shared, gap=5, chan_pad=3 if "p" in (sl, dl) else 0)
 
@@ -63,17 +52,17 @@ def test_block_bits_in_every_view(nae, ctx, ref, L):
 def test_every_size_at_three_partitions(nae, ctx, ref, n_fft):
     B = n_fft // 2
     rng = np.random.default_rng(n_fft)
-    _check(nae, ctx, ref, _taps(rng, 2 * B + 5, 2), n_fft, _noise(rng, 2, 6 * B + 9, 2))
+    _check(nae, ctx, ref, _taps(rng, 2 * B + 5, 2), n_fft, noise(rng, 2, 6 * B + 9, 2))
 
 
 @pytest.mark.parametrize("n_fft", conv_ref.SIZES)
 def test_one_partition_equals_the_fir_filter(nae, ctx, n_fft):
     B = n_fft // 2
     rng = np.random.default_rng(n_fft + 1)
-    x = _noise(rng, 2, 3 * B + 7, 2)
+    x = noise(rng, 2, 3 * B + 7, 2)
     for L in (1, B):
         taps = _taps(rng, L)
-        assert np.array_equal(_bits(gpu_conv(nae, ctx, taps, n_fft, x)), _bits(gpu_fir(nae, ctx, taps, n_fft, x))), L
+        assert np.array_equal(bits(gpu_conv(nae, ctx, taps, n_fft, x)), bits(gpu_fir(nae, ctx, taps, n_fft, x))), L
 
 
 @pytest.mark.parametrize("n_fft,P", ((512, 6), (4096, 3)))
@@ -81,7 +70,7 @@ def test_every_tile_gives_the_same_bits(nae, ctx, ref, n_fft, P):
     """conv_tile 1, 2, 3 (shorter than the register tile at 512), 100 (one wave walks several register groups and a partial one) and automatic"""
     B = n_fft // 2
     rng = np.random.default_rng(5)
-    taps, x = _taps(rng, (P - 1) * B + 9, 2), _noise(rng, 1, 10 * B + 5, 2)
+    taps, x = _taps(rng, (P - 1) * B + 9, 2), noise(rng, 1, 10 * B + 5, 2)
     try:
         for tile in (1, 2, 3, 100, 0):
             ctx.debug_set("conv_tile", tile)
@@ -94,7 +83,7 @@ def test_every_ring_gives_the_same_bits(nae, ctx, ref):
     """P = 4: conv_ring P (slabs of 1 block), P + 1 (2 blocks) and 2 P + 3 (slabs of 8: the 13 blocks wrap the ring of 11 slots); a ring below P is
     raised to P"""
     rng = np.random.default_rng(6)
-    taps, x = _taps(rng, 773, 2), _noise(rng, 2, 12 * 256 + 50, 2)
+    taps, x = _taps(rng, 773, 2), noise(rng, 2, 12 * 256 + 50, 2)
     try:
         for ring in (4, 5, 11, 1):
             ctx.debug_set("conv_ring", ring)
@@ -106,7 +95,7 @@ def test_every_ring_gives_the_same_bits(nae, ctx, ref):
 def test_several_workgroups_and_a_partial_one(nae, ctx, ref):
     """N = 512: 9 stream-channels x 9 blocks are 27 accumulate waves (7 per workgroup: 3 whole, one of 6) and 9 spectrum waves (8 per workgroup)"""
     rng = np.random.default_rng(7)
-    _check(nae, ctx, ref, _taps(rng, 600), 512, _noise(rng, 9, 9 * 256 - 11, 1), "p", "p")
+    _check(nae, ctx, ref, _taps(rng, 600), 512, noise(rng, 9, 9 * 256 - 11, 1), "p", "p")
 
 
 @pytest.mark.parametrize("n_fft,L,blocks", ((512, 512 * 256, 520), (4096, 262144, 130)))
@@ -115,14 +104,14 @@ def test_the_limits(nae, ctx, ref, n_fft, L, blocks):
     B = n_fft // 2
     rng = np.random.default_rng(8)
     taps = (_taps(rng, L) * np.float32(0.05))
-    _check(nae, ctx, ref, taps, n_fft, _noise(rng, 1, blocks * B - 3, 1))
+    _check(nae, ctx, ref, taps, n_fft, noise(rng, 1, blocks * B - 3, 1))
 
 
 def test_a_nan_reaches_p_plus_one_blocks(nae, ctx, ref):
     """N = 512, P = 3, a NaN at sample i of block 4: blocks 4 ... 7 may change, the block holding it is non-finite, every other keeps its bits"""
     B, P = 256, 3
     rng = np.random.default_rng(9)
-    taps, x = _taps(rng, 2 * B + 40), _noise(rng, 1, 12 * B, 1)
+    taps, x = _taps(rng, 2 * B + 40), noise(rng, 1, 12 * B, 1)
     clean = gpu_conv(nae, ctx, taps, 512, x)
     i = 4 * B + 17
     x[0, i, 0] = np.nan
@@ -132,48 +121,23 @@ def test_a_nan_reaches_p_plus_one_blocks(nae, ctx, ref):
     want = conv_ref.run_streams(ref, taps, 512, x)
     bad = ~np.isfinite(want)
     assert np.array_equal(~np.isfinite(got), bad), "the same words are non-finite"
-    assert np.array_equal(_bits(got)[~bad], _bits(want)[~bad])
+    assert np.array_equal(bits(got)[~bad], bits(want)[~bad])
     b = i // B
-    assert np.array_equal(_bits(got[0, :b * B]), _bits(clean[0, :b * B]))
-    assert np.array_equal(_bits(got[0, (b + P + 1) * B:]), _bits(clean[0, (b + P + 1) * B:]))
+    assert np.array_equal(bits(got[0, :b * B]), bits(clean[0, :b * B]))
+    assert np.array_equal(bits(got[0, (b + P + 1) * B:]), bits(clean[0, (b + P + 1) * B:]))
     assert not np.isfinite(got[0, b * B:(b + 1) * B]).any()
 
 
 def conv_stream(nae, ctx, taps, n_fft, x, puts, device=False):
-    """x[n, ch] through a nae_conv handle: puts of the sizes in `puts` (the last one repeated), a receive after every put, flush, the rest"""
+    """x[n, ch] through a nae_conv handle by block_gpu.stream, received into device memory when the puts come from it"""
     n, ch = x.shape
     h = nae.Conv(ctx, taps, ch, n_fft)
-    d_x = ctx.array(x.reshape(-1)) if device else None
     d_y = ctx.empty((n + taps.shape[-1]) * ch) if device else None
     try:
-        parts, pos, i = [], 0, 0
-
-        def take():
-            if device:
-                k = h.receive(d_y.ptr, h.available())
-                parts.append(d_y.download()[:k * ch].copy())
-            else:
-                parts.append(h.receive_host())
-        while pos < n:
-            k = min(puts[min(i, len(puts) - 1)], n - pos)
-            i += 1
-            if device:
-                h.put(d_x.at(pos * ch), k)
-            else:
-                h.put_host(x[pos:pos + k].reshape(-1))
-            pos += k
-            if h.available():
-                take()
-        h.flush()
-        take()
-        assert h.available() == 0
-        assert ctx.lib.nae_conv_put_host(h.h, x.ctypes.data, 1) == -5, "put after flush: NAE_ERR_STATE"
+        return stream(h, ctx, x, puts, device, after_flush=flushed(h, n + taps.shape[-1] - 1), d_out=d_y)
     finally:
-        h.close()
-        for d in (d_x, d_y):
-            if d is not None:
-                d.free()
-    return np.concatenate(parts).reshape(-1, ch)
+        if d_y is not None:
+            d_y.free()
 
 
 @pytest.mark.parametrize("device", (False, True))
@@ -183,17 +147,17 @@ def test_handle_equals_the_block_call(nae, ctx, ref, device):
     are the block call's"""
     B, L = 256, 773
     rng = np.random.default_rng(10)
-    taps, x = _taps(rng, L, 2), _noise(rng, 1, 14 * B + 31, 2)[0]
+    taps, x = _taps(rng, L, 2), noise(rng, 1, 14 * B + 31, 2)[0]
     ext = np.concatenate([x, np.zeros((L - 1, 2), np.float32)])
     want = conv_ref.run_streams(ref, taps, 512, ext[None])[0]
     block = gpu_conv(nae, ctx, taps, 512, x[None])[0]
-    assert np.array_equal(_bits(block), _bits(want[:len(x)]))
+    assert np.array_equal(bits(block), bits(want[:len(x)]))
     try:
         for ring in (0, 6):
             ctx.debug_set("conv_ring", ring)
             got = conv_stream(nae, ctx, taps, 512, x, (1, B - 1, B, B + 1, 5 * B + 3), device)
             assert got.shape == (len(x) + L - 1, 2)
-            assert np.array_equal(_bits(got), _bits(want)), ring
+            assert np.array_equal(bits(got), bits(want)), ring
     finally:
         ctx.debug_set("conv_ring", 0)
 
@@ -202,20 +166,20 @@ def test_context_cache(nae, ctx, ref):
     """the context keeps H of the last call: the same taps twice, changed taps, changed taps_ch, changed N, and a FIR call in between (the two
     caches are separate)"""
     rng = np.random.default_rng(11)
-    x = _noise(rng, 1, 5 * 256 + 9, 2)
+    x = noise(rng, 1, 5 * 256 + 9, 2)
     a, b = _taps(rng, 600), _taps(rng, 600)
     fir_taps = _taps(rng, 100)
     fir_want = gpu_fir(nae, ctx, fir_taps, 512, x)
     _check(nae, ctx, ref, a, 512, x)
     _check(nae, ctx, ref, a, 512, x)
     _check(nae, ctx, ref, b, 512, x)
-    assert np.array_equal(_bits(gpu_fir(nae, ctx, fir_taps, 512, x)), _bits(fir_want))
+    assert np.array_equal(bits(gpu_fir(nae, ctx, fir_taps, 512, x)), bits(fir_want))
     _check(nae, ctx, ref, b, 512, x)
     _check(nae, ctx, ref, np.stack([b, b]), 512, x)
     _check(nae, ctx, ref, np.stack([b, a]), 512, x)
     _check(nae, ctx, ref, np.stack([b, a]), 1024, x)
     _check(nae, ctx, ref, b, 1024, x)
-    assert np.array_equal(_bits(gpu_fir(nae, ctx, fir_taps, 512, x)), _bits(fir_want))
+    assert np.array_equal(bits(gpu_fir(nae, ctx, fir_taps, 512, x)), bits(fir_want))
 
 
 def test_error_codes(nae, ctx):

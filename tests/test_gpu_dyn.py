@@ -10,7 +10,8 @@ import pytest
 
 import dyn_ref
 import node_harness
-from dyn_gpu import CONFIGS, bits, dyn_stream, gpu_dyn, lib_params, statement
+from block_gpu import CONFIGS, bits, statement
+from dyn_gpu import dyn_stream, gpu_dyn, lib_params
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +23,7 @@ MID = dict(alpha_attack=dyn_ref.alpha(0.002), alpha_release=dyn_ref.alpha(0.05))
 
 @pytest.fixture(scope="module")
 def ref():
-    return statement()
+    return statement(dyn_ref)
 
 
 @pytest.fixture(scope="module")

@@ -9,7 +9,8 @@ import pytest
 
 import eq_ref
 import node_harness
-from eq_gpu import CONFIGS, bits, eq_stream, gpu_eq, noise, statement
+from block_gpu import CONFIGS, bits, noise, statement
+from eq_gpu import eq_stream, gpu_eq
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +21,7 @@ INVALID, UNSUPPORTED, STATE = -1, -2, -5
 
 @pytest.fixture(scope="module")
 def ref():
-    return statement()
+    return statement(eq_ref)
 
 
 @pytest.fixture(scope="module")

@@ -8,13 +8,14 @@ import pytest
 
 import fir_ref
 import node_harness
-from fir_gpu import CONFIGS, MIN_TILE, WAVES, _bits, _noise, fir_stream, gpu_fir, pick_tile, ref_fir, ref_fir_flushed, statement
+from block_gpu import CONFIGS, bits, noise, statement
+from fir_gpu import MIN_TILE, WAVES, fir_stream, gpu_fir, pick_tile, ref_fir, ref_fir_flushed
 
 pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def ref():
-    return statement()
+    return statement(fir_ref)
 
 
 @pytest.mark.parametrize("n_fft", fir_ref.SIZES)
@@ -28,10 +29,10 @@ def test_block_bits_equal_the_statement(nae, ctx, ref, n_fft):
         for in_len in (1, B - 1, B, B + 1, 3 * B + 7):
             ch, n_streams, sl, dl, shared = CONFIGS[k % len(CONFIGS)]
             k += 1
-            x = _noise(rng, n_streams, in_len, ch, shared)
+            x = noise(rng, n_streams, in_len, ch, shared)
             got = gpu_fir(nae, ctx, taps, n_fft, x, sl, dl, shared)
             want = ref_fir(ref, taps, n_fft, x)
-            assert np.array_equal(_bits(got), _bits(want)), (n_fft, L, in_len, ch, n_streams, sl, dl, shared)
+            assert np.array_equal(bits(got), bits(want)), (n_fft, L, in_len, ch, n_streams, sl, dl, shared)
 
 
 @pytest.mark.parametrize("cfg", CONFIGS, ids=lambda c: f"ch{c[0]}-s{c[1]}-{c[2]}{c[3]}{'-shared' if c[4] else ''}")
@@ -41,18 +42,18 @@ def test_block_bits_in_every_view(nae, ctx, ref, cfg):
     n_fft, B = 512, 256
     rng = np.random.default_rng(77)
     taps = rng.uniform(-1, 1, B + 1).astype(np.float32)
-    x = _noise(rng, n_streams, 3 * B + 7, ch, shared)
+    x = noise(rng, n_streams, 3 * B + 7, ch, shared)
     got = gpu_fir(nae, ctx, taps, n_fft, x, sl, dl, shared)
-    assert np.array_equal(_bits(got), _bits(ref_fir(ref, taps, n_fft, x)))
+    assert np.array_equal(bits(got), bits(ref_fir(ref, taps, n_fft, x)))
 
 
 def test_pick_equals_explicit_size(nae, ctx):
     rng = np.random.default_rng(9)
-    x = _noise(rng, 2, 2500, 2)
+    x = noise(rng, 2, 2500, 2)
     for L, n_fft in ((1, 512), (257, 512), (258, 1024), (513, 1024), (514, 2048), (1026, 4096), (2049, 4096)):
         taps = rng.uniform(-1, 1, L).astype(np.float32)
         assert nae.Context.fir_pick_n_fft(L) == n_fft
-        assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, 0, x)), _bits(gpu_fir(nae, ctx, taps, n_fft, x))), L
+        assert np.array_equal(bits(gpu_fir(nae, ctx, taps, 0, x)), bits(gpu_fir(nae, ctx, taps, n_fft, x))), L
 
 
 @pytest.mark.parametrize("n_fft", (512, 4096))
@@ -60,14 +61,14 @@ def test_every_tiling_gives_the_same_bits(nae, ctx, ref, n_fft):
     B = n_fft // 2
     rng = np.random.default_rng(n_fft + 1)
     taps = rng.uniform(-1, 1, B + 1).astype(np.float32)
-    x = _noise(rng, 2, 7 * B + 5, 2)
+    x = noise(rng, 2, 7 * B + 5, 2)
     own = gpu_fir(nae, ctx, taps, n_fft, x)
-    assert np.array_equal(_bits(own), _bits(ref_fir(ref, taps, n_fft, x)))
+    assert np.array_equal(bits(own), bits(ref_fir(ref, taps, n_fft, x)))
     try:
         for tile in (1, 2, 3):
             ctx.debug_set("fir_tile", tile)
-            assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x)), _bits(own)), tile
-            assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x, "p", "p")), _bits(own)), tile
+            assert np.array_equal(bits(gpu_fir(nae, ctx, taps, n_fft, x)), bits(own)), tile
+            assert np.array_equal(bits(gpu_fir(nae, ctx, taps, n_fft, x, "p", "p")), bits(own)), tile
     finally:
         ctx.debug_set("fir_tile", 0)
 
@@ -85,9 +86,9 @@ def test_automatic_tiles(nae, ctx, ref, n_fft):
         for ch, n_streams in ((1, 1), (2, 3)):
             tile, n_tiles = pick_tile(n_fft, blocks, ch * n_streams)
             assert tile >= MIN_TILE and (n_tiles > 1) == (blocks >= 16), (blocks, tile, n_tiles)
-            x = _noise(rng, n_streams, blocks * B - 5, ch)
+            x = noise(rng, n_streams, blocks * B - 5, ch)
             got = gpu_fir(nae, ctx, taps, n_fft, x)
-            assert np.array_equal(_bits(got), _bits(ref_fir(ref, taps, n_fft, x))), (blocks, ch, n_streams, tile, n_tiles)
+            assert np.array_equal(bits(got), bits(ref_fir(ref, taps, n_fft, x))), (blocks, ch, n_streams, tile, n_tiles)
     assert pick_tile(n_fft, 41, 1) == (9, 5) and pick_tile(n_fft, 67, 6) == (9, 8)
 
 
@@ -100,10 +101,10 @@ def test_a_full_and_a_partial_workgroup(nae, ctx, ref, n_fft, layout):
     assert 10 > WAVES[n_fft] and 10 % WAVES[n_fft]
     rng = np.random.default_rng(n_fft + 3)
     taps = rng.uniform(-1, 1, B + 1).astype(np.float32)
-    x = _noise(rng, 5, 2 * B + 3, 2)
+    x = noise(rng, 5, 2 * B + 3, 2)
     ctx.debug_set("fir_tile", 0)
     got = gpu_fir(nae, ctx, taps, n_fft, x, layout, layout, gap=37)
-    assert np.array_equal(_bits(got), _bits(ref_fir(ref, taps, n_fft, x)))
+    assert np.array_equal(bits(got), bits(ref_fir(ref, taps, n_fft, x)))
 
 
 @pytest.mark.parametrize("n_fft", fir_ref.SIZES)
@@ -113,13 +114,13 @@ def test_forced_tiles_over_several_workgroups(nae, ctx, ref, n_fft):
     B = n_fft // 2
     rng = np.random.default_rng(n_fft + 4)
     taps = rng.uniform(-1, 1, B + 1).astype(np.float32)
-    x = _noise(rng, 5, 7 * B - 5, 2)
-    want = _bits(ref_fir(ref, taps, n_fft, x))
+    x = noise(rng, 5, 7 * B - 5, 2)
+    want = bits(ref_fir(ref, taps, n_fft, x))
     try:
         for tile in (1, 2, 3, 100):
             ctx.debug_set("fir_tile", tile)
-            assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x, gap=37)), want), tile
-            assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x, "p", "p", gap=37)), want), tile
+            assert np.array_equal(bits(gpu_fir(nae, ctx, taps, n_fft, x, gap=37)), want), tile
+            assert np.array_equal(bits(gpu_fir(nae, ctx, taps, n_fft, x, "p", "p", gap=37)), want), tile
     finally:
         ctx.debug_set("fir_tile", 0)
 
@@ -134,16 +135,16 @@ def test_unit_stride_at_odd_addresses(nae, ctx, ref, n_fft):
     n = 3 * B + 7
     assert n % 2 == 1, "n and n + PAD are the planar channel strides"
     for ch, layout in ((1, "i"), (1, "p"), (2, "p")):
-        x = _noise(rng, 2, n, ch)
+        x = noise(rng, 2, n, ch)
         got = gpu_fir(nae, ctx, taps, n_fft, x, layout, layout, gap=1, offset=1)
-        assert np.array_equal(_bits(got), _bits(ref_fir(ref, taps, n_fft, x))), (ch, layout)
+        assert np.array_equal(bits(got), bits(ref_fir(ref, taps, n_fft, x))), (ch, layout)
 
 
 def test_nan_reaches_only_the_blocks_that_read_it(nae, ctx):
     n_fft, B = 512, 256
     rng = np.random.default_rng(11)
     taps = rng.uniform(-1, 1, 65).astype(np.float32)
-    x = _noise(rng, 2, 5 * B + 3, 2)
+    x = noise(rng, 2, 5 * B + 3, 2)
     clean = gpu_fir(nae, ctx, taps, n_fft, x)
     p = 2 * B + 10                       # read by blocks 2 (its new half) and 3 (its carried half)
     x[1, p, 0] = np.nan
@@ -151,10 +152,10 @@ def test_nan_reaches_only_the_blocks_that_read_it(nae, ctx):
     hit = np.zeros(x.shape, bool)
     hit[1, 2 * B:4 * B, 0] = True
     assert np.all(np.isnan(got[hit])), "every sample of the two blocks is NaN"
-    assert np.array_equal(_bits(got)[~hit], _bits(clean)[~hit]), "no other output word changes"
+    assert np.array_equal(bits(got)[~hit], bits(clean)[~hit]), "no other output word changes"
     try:
         ctx.debug_set("fir_tile", 1)     # the block after the NaN starts a tile: it reads the sample through the tile head
-        assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x)), _bits(got))
+        assert np.array_equal(bits(gpu_fir(nae, ctx, taps, n_fft, x)), bits(got))
     finally:
         ctx.debug_set("fir_tile", 0)
 
@@ -165,7 +166,7 @@ def handle_case(nae, ctx, ref):
     rng = np.random.default_rng(21)
     L, in_len = 513, 5000
     taps = rng.uniform(-1, 1, L).astype(np.float32)
-    x = _noise(rng, 1, in_len, 2)
+    x = noise(rng, 1, in_len, 2)
     block = gpu_fir(nae, ctx, taps, 1024, x)[0]
     ext = np.concatenate([x, np.zeros((1, L - 1, 2), np.float32)], 1)
     tail = ref_fir(ref, taps, 1024, ext)[0]
@@ -192,8 +193,8 @@ def test_handle_equals_the_block_call_for_any_chunking(nae, ctx, handle_case, ch
         assert h.available() == 0
         got = np.concatenate(parts).reshape(-1, 2)
         assert got.shape[0] == in_len + L - 1
-        assert np.array_equal(_bits(got[:in_len]), _bits(block)), "the first in_len frames are the block call's"
-        assert np.array_equal(_bits(got), _bits(tail)), "and the tail is the statement on the zero-extended input"
+        assert np.array_equal(bits(got[:in_len]), bits(block)), "the first in_len frames are the block call's"
+        assert np.array_equal(bits(got), bits(tail)), "and the tail is the statement on the zero-extended input"
         assert ctx.lib.nae_fir_put_host(h.h, x.ctypes.data, 1) == -5, "put after flush: NAE_ERR_STATE, as the other handles"
     finally:
         h.close()
@@ -211,7 +212,7 @@ def test_handle_device_put_and_mono(nae, ctx, ref):
         h.flush()
         got = h.receive_host()
         want = fir_ref.run(ref, taps, 512, np.concatenate([x, np.zeros(1, np.float32)]))
-        assert np.array_equal(_bits(got), _bits(want))
+        assert np.array_equal(bits(got), bits(want))
     finally:
         h.close()
         d_x.free()
@@ -225,25 +226,25 @@ def test_handle_launch_past_block_0_in_several_tiles(nae, ctx, ref, n_fft, ch):
     B = n_fft // 2
     rng = np.random.default_rng(n_fft + 6 + ch)
     taps = rng.uniform(-1, 1, B + 1).astype(np.float32)
-    x = _noise(rng, 1, 12 * B + 11, ch)[0]
+    x = noise(rng, 1, 12 * B + 11, ch)[0]
     try:
         ctx.debug_set("fir_tile", 2)
         got = fir_stream(nae, ctx, taps, n_fft, x, (3 * B + 11, 9 * B))
     finally:
         ctx.debug_set("fir_tile", 0)
-    assert np.array_equal(_bits(got), _bits(ref_fir_flushed(ref, taps, n_fft, x)))
+    assert np.array_equal(bits(got), bits(ref_fir_flushed(ref, taps, n_fft, x)))
 
 
 def test_the_context_keeps_the_right_taps(nae, ctx, ref):
     """the block call's cache of the last taps and their spectrum: every call of each sequence equals the statement for ITS taps and size"""
     rng = np.random.default_rng(41)
-    x = _noise(rng, 2, 3 * 256 + 7, 2)
+    x = noise(rng, 2, 3 * 256 + 7, 2)
     a = rng.uniform(-1, 1, 200).astype(np.float32)
     b = rng.uniform(-1, 1, 200).astype(np.float32)
 
     def check(taps, n_fft, what):
         want = ref_fir(ref, taps, n_fft, x)
-        assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x)), _bits(want)), what
+        assert np.array_equal(bits(gpu_fir(nae, ctx, taps, n_fft, x)), bits(want)), what
 
     # shorter taps after longer ones at the same size: padded taps left behind by A would show
     check(a, 512, "A")
@@ -267,7 +268,7 @@ def test_the_context_keeps_the_right_taps(nae, ctx, ref):
     h = nae.Fir(ctx, b, 2, 1024)
     check(a, 1024, "A at 1024 after the handle was created")
     got = fir_stream(nae, ctx, b, 1024, x[0], (700, 75), handle=h)
-    assert np.array_equal(_bits(got), _bits(ref_fir_flushed(ref, b, 1024, x[0]))), "the handle's output, with B"
+    assert np.array_equal(bits(got), bits(ref_fir_flushed(ref, b, 1024, x[0]))), "the handle's output, with B"
     check(a, 1024, "A at 1024 after the handle ran")
 
 
@@ -285,7 +286,7 @@ def test_subnormal_input(nae, ctx, ref, n_fft):
     want = ref_fir(ref, taps, n_fft, x)
     sub = (np.abs(want) < FLT_MIN) & (want != 0)
     assert sub.sum() > want.size // 4 and np.any(np.abs(want) >= FLT_MIN), "subnormal and normal output words"
-    assert np.array_equal(_bits(gpu_fir(nae, ctx, taps, n_fft, x)), _bits(want))
+    assert np.array_equal(bits(gpu_fir(nae, ctx, taps, n_fft, x)), bits(want))
 
 
 @pytest.mark.parametrize("n_fft", fir_ref.SIZES)
@@ -295,7 +296,7 @@ def test_overflow(nae, ctx, ref, n_fft):
     B = n_fft // 2
     rng = np.random.default_rng(n_fft + 8)
     taps = rng.uniform(-1, 1, 2).astype(np.float32)
-    x = _noise(rng, 1, 8 * B + 3, 2)
+    x = noise(rng, 1, 8 * B + 3, 2)
     x[0, B + 5, 0] = 3e38
     x[0, 3 * B + 9, 0] = 3e38
     x[0, 3 * B + 10, 0] = -3e38
@@ -310,7 +311,7 @@ def test_overflow(nae, ctx, ref, n_fft):
     assert not bad[0, :B].any() and not bad[0, B:3 * B, 1].any() and not bad[0, 5 * B:7 * B, 0].any() and not bad[0, 7 * B:, 1].any()
     got = gpu_fir(nae, ctx, taps, n_fft, x)
     assert np.array_equal(~np.isfinite(got), bad), "the same words are non-finite"
-    assert np.array_equal(_bits(got)[~bad], _bits(want)[~bad])
+    assert np.array_equal(bits(got)[~bad], bits(want)[~bad])
 
 
 def test_error_codes(nae, ctx):

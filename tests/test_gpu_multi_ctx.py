@@ -11,9 +11,11 @@ import threading
 import numpy as np
 import pytest
 
+import fir_ref
 import orc
+from block_gpu import noise, statement
 from conftest import rel_rms
-from fir_gpu import _noise, gpu_fir, ref_fir, ref_fir_flushed, statement
+from fir_gpu import gpu_fir, ref_fir, ref_fir_flushed
 
 pytestmark = pytest.mark.gpu
 
@@ -92,7 +94,7 @@ def test_two_contexts_interleaved_bit_exact(nae, ctx):
 def test_fir_on_two_contexts_interleaved(nae, ctx):
     """two more contexts with taps and frame sizes of their own: block calls interleaved call by call (each context keeps the spectrum of ITS
     last taps), then one nae_fir handle on each, fed alternately; every result is the statement's for that context's taps"""
-    ref = statement()
+    ref = statement(fir_ref)
     rng = np.random.default_rng(51)
     cs = [nae.Context(0), nae.Context(0)]
     taps = [rng.uniform(-1, 1, 200).astype(np.float32), rng.uniform(-1, 1, 600).astype(np.float32)]
@@ -100,11 +102,11 @@ def test_fir_on_two_contexts_interleaved(nae, ctx):
     hs = []
     try:
         for i in range(3):                                  # the second and third round are cache hits on both contexts
-            x = _noise(rng, 2, 9 * 256 + 7 + i, 2)
+            x = noise(rng, 2, 9 * 256 + 7 + i, 2)
             got = [gpu_fir(nae, c, t, n, x) for c, t, n in zip(cs, taps, sizes)]
             for g, t, n in zip(got, taps, sizes):
                 assert np.array_equal(bits(g), bits(ref_fir(ref, t, n, x))), (i, n)
-        x = _noise(rng, 2, 30000, 2)
+        x = noise(rng, 2, 30000, 2)
         hs = [nae.Fir(c, t, 2, n) for c, t, n in zip(cs, taps, sizes)]
         outs = [[], []]
         for pos in range(0, 30000, 1700):
@@ -156,9 +158,9 @@ def test_contexts_driven_from_two_threads(nae):
     context by one thread).  Both threads make their FIRST vocoder call concurrently — the launch attribute that round 3 kept in a
     process-global flag is per context now."""
     results, errors = {}, []
-    ref = statement()
+    ref = statement(fir_ref)
     rng = np.random.default_rng(61)
-    fir_x = _noise(rng, 3, 5 * 256 + 3, 2)
+    fir_x = noise(rng, 3, 5 * 256 + 3, 2)
     fir_taps = [rng.uniform(-1, 1, 257).astype(np.float32) for _ in range(2)]      # each thread's context filters with its own taps
     fir_out = {}
 

@@ -10,7 +10,8 @@ import pytest
 import fir_ref
 import orc
 import pv_ref
-from fir_gpu import gpu_fir, statement
+from block_gpu import statement
+from fir_gpu import gpu_fir
 from pv_gpu import block, same_bits
 from test_gpu_spectrum_sizes import bins, gpu_ex
 
@@ -158,7 +159,7 @@ def fir_case(n_fft, n_taps, ch, seed):
     rng = np.random.default_rng(seed)
     taps = rng.uniform(-1, 1, n_taps).astype(np.float32)
     x = orc.fill_uniform(L * ch, seed)
-    want = fir_ref.run(statement(), taps, n_fft, np.concatenate([x, np.zeros((n_taps - 1) * ch, np.float32)]), ch=ch)
+    want = fir_ref.run(statement(fir_ref), taps, n_fft, np.concatenate([x, np.zeros((n_taps - 1) * ch, np.float32)]), ch=ch)
     return taps, x, want
 
 

@@ -13,7 +13,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import naeload
 import fir_ref
-from fir_gpu import _bits, _noise, fir_stream, gpu_fir, ref_fir, ref_fir_flushed, statement
+from block_gpu import bits, noise, statement
+from fir_gpu import fir_stream, gpu_fir, ref_fir, ref_fir_flushed
 
 
 def draw_taps(rng, nae, L):
@@ -32,7 +33,7 @@ def main(cases=60, seed=1, ctx=None, nae=None):
         nae = naeload.load()
     if ctx is None:
         ctx = nae.Context(0)
-    ref = statement()
+    ref = statement(fir_ref)
     done = 0
     try:
         for k in range(cases):
@@ -47,7 +48,7 @@ def main(cases=60, seed=1, ctx=None, nae=None):
             tile = int(rng.choice([0, 1, int(rng.integers(1, blocks + 3))]))
             ctx.debug_set("fir_tile", tile)
             if k % 3 == 2:
-                x = _noise(rng, 1, in_len, ch)[0]
+                x = noise(rng, 1, in_len, ch)[0]
                 puts = [int(p) for p in rng.integers(1, 6 * B, int(rng.integers(1, 6)))]
                 device = bool(rng.integers(2))
                 got = fir_stream(nae, ctx, taps, n_fft, x, puts, device=device)
@@ -60,12 +61,12 @@ def main(cases=60, seed=1, ctx=None, nae=None):
                 sl, dl = str(rng.choice(["i", "p"])), str(rng.choice(["i", "p"]))
                 shared = bool(rng.integers(4) == 0)
                 gap, chan_pad, offset = (int(rng.choice([0, 1, 37])) for _ in range(3))
-                x = _noise(rng, n_streams, in_len, ch, shared)
+                x = noise(rng, n_streams, in_len, ch, shared)
                 got = gpu_fir(nae, ctx, taps, n_fft, x, sl, dl, shared, gap=gap, offset=offset, chan_pad=chan_pad)
                 want = ref_fir(ref, taps, n_fft, x)
                 what = f"block {n_streams} streams {sl}{dl}{' shared' if shared else ''} gap {gap} pad {chan_pad} offset {offset}"
             assert got.shape == want.shape, (k, got.shape, want.shape)
-            assert np.array_equal(_bits(got), _bits(want)), f"case {k}: n_fft {n_fft} L {L} {kind} in_len {in_len} ch {ch} tile {tile} {what}: differs"
+            assert np.array_equal(bits(got), bits(want)), f"case {k}: n_fft {n_fft} L {L} {kind} in_len {in_len} ch {ch} tile {tile} {what}: differs"
             done += 1
             print(f"case {k:3d}: n_fft {n_fft:4d} L {L:4d} {kind:8s} in_len {in_len:6d} ch {ch} tile {tile:2d} {what}  bit-exact", flush=True)
     finally:
