@@ -79,13 +79,10 @@ __global__ __launch_bounds__(64 * (Conv<N>::kWavesS)) void conv_spectra_kernel(S
     if (item >= p.n_items) return;
     cf* scr = scratch + wave_id() * Gm::SCR;
     cf* cw = carry + wave_id() * (M / 2);
-    const long long sc = item / p.n_tiles;
-    const int tile = (int)(item % p.n_tiles);
-    const long long s_idx = sc / p.ch;
-    const int c = (int)(sc % p.ch);
-    const float* ip = src.base + s_idx * src.ss + c * src.cs;
-    cf* us = ws + sc * p.ring * F::PAD;
-    const long long b0 = p.b_origin + (long long)tile * p.tile;
+    const WaveTile w = wave_tile(item, p.n_tiles, p.ch);
+    const float* ip = src.base + w.s_idx * src.ss + w.c * src.cs;
+    cf* us = ws + w.sc * p.ring * F::PAD;
+    const long long b0 = p.b_origin + (long long)w.tile * p.tile;
     const long long b_end = b0 + p.tile < p.b_stop ? b0 + p.tile : p.b_stop;
     int slot = (int)(b0 % p.ring);
 
@@ -209,14 +206,11 @@ __global__ __launch_bounds__(64 * (Conv<N>::kWavesM)) void conv_mac_kernel(OutVi
     if (item >= p.n_items) return;
     cf* scr = scratch + wave_id() * Gm::SCR;
     cf* ys = yspec + wave_id() * (kT * F::PAD);
-    const long long sc = item / p.n_tiles;
-    const int tile = (int)(item % p.n_tiles);
-    const long long s_idx = sc / p.ch;
-    const int c = (int)(sc % p.ch);
-    float* op = out.base + s_idx * out.ss + c * out.cs;
-    const cf* us = ws + sc * p.ring * F::PAD;
-    const cf* hc = hspec + (long long)(p.taps_ch == 1 ? 0 : c) * p.parts * F::PAD;
-    const long long b0 = p.b_origin + (long long)tile * p.tile;
+    const WaveTile w = wave_tile(item, p.n_tiles, p.ch);
+    float* op = out.base + w.s_idx * out.ss + w.c * out.cs;
+    const cf* us = ws + w.sc * p.ring * F::PAD;
+    const cf* hc = hspec + (long long)(p.taps_ch == 1 ? 0 : w.c) * p.parts * F::PAD;
+    const long long b0 = p.b_origin + (long long)w.tile * p.tile;
     const long long b_end = b0 + p.tile < p.b_stop ? b0 + p.tile : p.b_stop;
 
 #pragma unroll 1
@@ -255,22 +249,24 @@ static int launch_conv_slab(nae_ctx* ctx, const SigViewD& src, const OutViewD& o
     size_t n_tiles = (blocks + (size_t)p.tile - 1) / (size_t)p.tile;
     p.n_tiles = (int)n_tiles;
     p.n_items = (long long)(n_sc * n_tiles);
-    long long grid = (p.n_items + V::kWavesS - 1) / V::kWavesS;
-    if (n_tiles > 0x7fffffffull || grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "conv_spectra_kernel: grid too large");
-    NAE_KLAUNCH(ctx, "conv_spectra_kernel", (unit_in ? conv_spectra_kernel<N, true> : conv_spectra_kernel<N, false>), dim3((unsigned)grid),
-                dim3(64 * V::kWavesS), 0, ctx->stream, src, p, ws, tb);
-    int rc = nae_check(ctx, hipGetLastError(), "conv_spectra_kernel");
+    // (a tile count past int32 cannot be a kernel argument: the launch's own refusal, in front of it)
+    static const char kSpectraGrid[] = "conv_spectra_kernel: grid too large", kMacGrid[] = "conv_mac_kernel: grid too large";
+    if (n_tiles > 0x7fffffffull) return nae_fail(ctx, NAE_ERR_INVALID, kSpectraGrid);
+    const int rc = with_flags(unit_in, [&](auto unit) {
+        return nae_launch_tiles(ctx, "conv_spectra_kernel", kSpectraGrid, conv_spectra_kernel<N, unit.value>, p.n_items, V::kWavesS, 64 * V::kWavesS, 0,
+                                src, p, ws, tb);
+    });
     if (rc) return rc;
     // sums
     p.tile = nae_pick_conv_tile(ctx, N);
     n_tiles = (blocks + (size_t)p.tile - 1) / (size_t)p.tile;
     p.n_tiles = (int)n_tiles;
     p.n_items = (long long)(n_sc * n_tiles);
-    grid = (p.n_items + V::kWavesM - 1) / V::kWavesM;
-    if (n_tiles > 0x7fffffffull || grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "conv_mac_kernel: grid too large");
-    NAE_KLAUNCH(ctx, "conv_mac_kernel", (unit_out ? conv_mac_kernel<N, true> : conv_mac_kernel<N, false>), dim3((unsigned)grid), dim3(64 * V::kWavesM),
-                0, ctx->stream, out, p, ws, hspec, tb);
-    return nae_check(ctx, hipGetLastError(), "conv_mac_kernel");
+    if (n_tiles > 0x7fffffffull) return nae_fail(ctx, NAE_ERR_INVALID, kMacGrid);
+    return with_flags(unit_out, [&](auto unit) {
+        return nae_launch_tiles(ctx, "conv_mac_kernel", kMacGrid, conv_mac_kernel<N, unit.value>, p.n_items, V::kWavesM, 64 * V::kWavesM, 0, out, p, ws,
+                                hspec, tb);
+    });
 }
 
 } // namespace nae
@@ -278,7 +274,6 @@ static int launch_conv_slab(nae_ctx* ctx, const SigViewD& src, const OutViewD& o
 // ================================================================================================ host side
 using namespace nae;
 
-static bool conv_size_ok(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096; }
 static size_t conv_pad(int n_fft) { return (size_t)n_fft / 2 + 8; }   // Fir<N>::PAD
 
 int nae_conv_parts(int n_taps, int n_fft) { return (int)(((long long)n_taps + n_fft / 2 - 1) / (n_fft / 2)); }
@@ -350,7 +345,7 @@ int nae_launch_conv(nae_ctx* ctx, int n_fft, int parts, int taps_ch, const float
     p.parts = parts;
     p.ring = (int)ring;
     const SigViewD sv = to_view(src);
-    const OutViewD ov{static_cast<float*>(dst->base), (long long)dst->stream_stride, (long long)dst->chan_stride, (long long)dst->frame_stride};
+    const OutViewD ov = to_out(dst);
     const cf* hspec = reinterpret_cast<const cf*>(d_spec + (size_t)taps_ch * (size_t)parts * ((size_t)n_fft / 2));
     const size_t slab = ring - ((size_t)parts - 1);
     for (size_t b = b_origin; b < b_stop; b += slab) {
@@ -384,7 +379,7 @@ int nae_conv_check(nae_ctx* ctx, int n_taps, int taps_ch, int ch, int* n_fft)
     if (taps_ch != 1 && taps_ch != ch) return nae_fail(ctx, NAE_ERR_INVALID, "conv: taps_ch must be 1 or the channel count");
     if (n_taps > NAE_CONV_MAX_TAPS) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "conv: at most NAE_CONV_MAX_TAPS taps");
     if (*n_fft == 0) *n_fft = nae_conv_pick_n_fft(n_taps);
-    if (!conv_size_ok(*n_fft)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "conv: n_fft must be 512, 1024, 2048 or 4096");
+    if (!nae_size_ok(*n_fft)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "conv: n_fft must be 512, 1024, 2048 or 4096");
     if (nae_conv_parts(n_taps, *n_fft) > NAE_CONV_MAX_PARTS) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "conv: at most NAE_CONV_MAX_PARTS partitions");
     return NAE_OK;
 }

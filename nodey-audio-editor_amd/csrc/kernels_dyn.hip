@@ -13,7 +13,7 @@
 // __shfl_up of doubles, every lane takes its start state from the scanned map of the lanes below it and the chunk's carry-in and runs its 16
 // samples as the plain recurrence.  The carries (y1, yl) stay in registers between chunks; a handle keeps them in device memory between
 // launches.  Built with -ffp-contract=off: every step is one IEEE operation in the order of the CPU statement (tests/dyn_ref/ref_dyn.c).
-#include "nae_internal.h"
+#include "launch.h"
 #include <math.h>
 #include <string.h>
 
@@ -25,7 +25,6 @@ static_assert(kDynT == 16 && kDynC == 1024 && NAE_DYN_MAX_LOOKAHEAD <= kDynC, "D
 constexpr double kDynK = 6.020599913279624;      // 20 log10(2)
 constexpr double kDynKInv = 0.1660964047443681;  // 1 / K
 
-struct DynView { float* base; long long ss, cs, fs; };
 struct DynParams {
     long long in_len;      // samples of a signal: reads at or past in_len give zero, samples there are not stored
     long long c_origin;    // chunks [c_origin, c_stop) are computed (a handle continues where it stopped)
@@ -108,7 +107,7 @@ __device__ __forceinline__ double dyn_demand(const DynCurve& p, float af, const 
 // state: [n_det][2] doubles, the carries (y1, yl) in front of chunk c_origin, replaced by the ones behind chunk c_stop - 1; null: zero in,
 // nothing out (the block call)
 template <int DC>
-__global__ __launch_bounds__(64) void dyn_kernel(DynView src, DynView out, DynParams p, double* state)
+__global__ __launch_bounds__(64) void dyn_kernel(SigViewD src, OutViewD out, DynParams p, double* state)
 {
     __shared__ float stage[kDynC + 64];
     __shared__ double ring[2 * kDynSlot];                  // r (la < 16) or P (la >= 16) of two chunks, chunk ck in slot ck & 1
@@ -358,7 +357,6 @@ int nae_launch_dyn(nae_ctx* ctx, const nae_dyn_params* dp, const nae_sig* src, s
 {
     if (c_stop <= c_origin || n_streams == 0) return NAE_OK;
     const size_t n_det = nae_dyn_detectors(dp, ch, n_streams);
-    if (n_det > 0x7fffffffull) return nae_fail(ctx, NAE_ERR_INVALID, "dyn_kernel: grid too large");
     DynParams p;
     p.in_len = (long long)in_len;
     p.c_origin = (long long)c_origin;
@@ -376,13 +374,11 @@ int nae_launch_dyn(nae_ctx* ctx, const nae_dyn_params* dp, const nae_sig* src, s
     p.v[kDynMakeup] = dp->makeup_db;
     p.ch = ch;
     p.la = dp->lookahead;
-    const DynView sv{static_cast<float*>(src->base), (long long)src->stream_stride, (long long)src->chan_stride, (long long)src->frame_stride};
-    const DynView ov{static_cast<float*>(dst->base), (long long)dst->stream_stride, (long long)dst->chan_stride, (long long)dst->frame_stride};
-    if (dp->link && ch == 2)
-        NAE_KLAUNCH(ctx, "dyn_kernel", dyn_kernel<2>, dim3((unsigned)n_det), dim3(64), 0, ctx->stream, sv, ov, p, d_state);
-    else
-        NAE_KLAUNCH(ctx, "dyn_kernel", dyn_kernel<1>, dim3((unsigned)n_det), dim3(64), 0, ctx->stream, sv, ov, p, d_state);
-    return nae_check(ctx, hipGetLastError(), "dyn_kernel");
+    // one wave per detector
+    return with_flags(dp->link && ch == 2, [&](auto linked) {
+        return nae_launch_tiles(ctx, "dyn_kernel", "dyn_kernel: grid too large", dyn_kernel<linked.value ? 2 : 1>, p.n_det, 1, 64, 0, to_view(src),
+                                to_out(dst), p, d_state);
+    });
 }
 
 extern "C" {

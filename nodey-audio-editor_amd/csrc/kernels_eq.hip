@@ -13,7 +13,7 @@
 // into LDS once per launch and read there as broadcasts (read from the block they cost 28 SGPR spills).
 // The translation unit is built with -ffp-contract=off: every step is one IEEE operation, in the order of the CPU statement
 // (tests/eq_ref/ref_eq.c).  It shares no code with the other kernels.
-#include "nae_internal.h"
+#include "launch.h"
 #include <math.h>
 #include <string.h>
 
@@ -25,7 +25,6 @@ constexpr int kEqTabOfs = NAE_EQ_MAX_SECTIONS * kEqCoefs;  // the tables stand b
 constexpr size_t kEqBlockDoubles = (size_t)NAE_EQ_MAX_SECTIONS * (kEqCoefs + kEqTab);
 static_assert(kEqTab == 56 && kEqC == 1024, "DESIGN.md §3, K11: 56 doubles of tables per section, chunks of 1024 samples");
 
-struct EqView { float* base; long long ss, cs, fs; };
 struct EqParams {
     long long in_len;      // samples of a stream-channel: reads at or past in_len give zero, samples there are not stored
     long long c_origin;    // chunks [c_origin, c_stop) are computed (a handle continues where it stopped)
@@ -44,7 +43,7 @@ __device__ __forceinline__ void eq_lds_sync()
 
 // state: [n_sc][NAE_EQ_MAX_SECTIONS][2] doubles, the carry (z1, z2) of every section in front of chunk c_origin, replaced by the one behind chunk
 // c_stop - 1; null: zero in, nothing out (the block call)
-__global__ __launch_bounds__(64) void eq_cascade_kernel(EqView src, EqView out, EqParams p, const double* __restrict__ tab, double* state)
+__global__ __launch_bounds__(64) void eq_cascade_kernel(SigViewD src, OutViewD out, EqParams p, const double* __restrict__ tab, double* state)
 {
     __shared__ float stage[kEqC + 64];
     __shared__ double pq[NAE_EQ_MAX_SECTIONS * 2 * kEqT];  // p and q of every section: read at wave-uniform addresses (a broadcast)
@@ -215,7 +214,6 @@ int nae_launch_eq(nae_ctx* ctx, const double* d_block, int n_sections, const nae
 {
     if (c_stop <= c_origin || n_streams == 0) return NAE_OK;
     const size_t n_sc = n_streams * (size_t)ch;
-    if (n_sc > 0x7fffffffull) return nae_fail(ctx, NAE_ERR_INVALID, "eq_cascade_kernel: grid too large");
     EqParams p;
     p.in_len = (long long)in_len;
     p.c_origin = (long long)c_origin;
@@ -223,10 +221,9 @@ int nae_launch_eq(nae_ctx* ctx, const double* d_block, int n_sections, const nae
     p.n_sc = (long long)n_sc;
     p.ch = ch;
     p.n_sections = n_sections;
-    const EqView sv{static_cast<float*>(src->base), (long long)src->stream_stride, (long long)src->chan_stride, (long long)src->frame_stride};
-    const EqView ov{static_cast<float*>(dst->base), (long long)dst->stream_stride, (long long)dst->chan_stride, (long long)dst->frame_stride};
-    NAE_KLAUNCH(ctx, "eq_cascade_kernel", eq_cascade_kernel, dim3((unsigned)n_sc), dim3(64), 0, ctx->stream, sv, ov, p, d_block, d_state);
-    return nae_check(ctx, hipGetLastError(), "eq_cascade_kernel");
+    // one wave per stream-channel
+    return nae_launch_tiles(ctx, "eq_cascade_kernel", "eq_cascade_kernel: grid too large", eq_cascade_kernel, p.n_sc, 1, 64, 0, to_view(src), to_out(dst),
+                            p, d_block, d_state);
 }
 
 void nae_eq_cache_free(nae_ctx* ctx)

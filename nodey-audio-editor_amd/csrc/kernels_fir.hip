@@ -43,13 +43,10 @@ __global__ __launch_bounds__(64 * (Fir<N>::kWaves)) void fir_block_kernel(SigVie
     cf* scr = scratch + wave_id() * Gm::SCR;
     cf* ys = yspec + wave_id() * F::PAD;
     cf* cw = carry + wave_id() * (M / 2);
-    const long long sc = item / p.n_tiles;
-    const int tile = (int)(item % p.n_tiles);
-    const long long s_idx = sc / p.ch;
-    const int c = (int)(sc % p.ch);
-    const float* ip = src.base + s_idx * src.ss + c * src.cs;
-    float* op = out.base + s_idx * out.ss + c * out.cs;
-    const long long b0 = p.b_origin + (long long)tile * p.tile;
+    const WaveTile w = wave_tile(item, p.n_tiles, p.ch);
+    const float* ip = src.base + w.s_idx * src.ss + w.c * src.cs;
+    float* op = out.base + w.s_idx * out.ss + w.c * out.cs;
+    const long long b0 = p.b_origin + (long long)w.tile * p.tile;
     const long long b_end = b0 + p.tile < p.b_stop ? b0 + p.tile : p.b_stop;
 
     fir_tile_head<N, kUnit>(cw, ip, src.fs, p.in_len, b0, lane);
@@ -123,12 +120,10 @@ template <int N>
 static int launch_fir(nae_ctx* ctx, const SigViewD& src, const OutViewD& out, const FirParams& p, const cf* hspec, const SpecAnyTables& tb)
 {
     using F = Fir<N>;
-    const long long grid = (p.n_items + F::kWaves - 1) / F::kWaves;
-    if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "fir_block_kernel: grid too large");
-    const bool unit = src.fs == 1 && out.fs == 1;
-    NAE_KLAUNCH(ctx, "fir_block_kernel", (unit ? fir_block_kernel<N, true> : fir_block_kernel<N, false>), dim3((unsigned)grid), dim3(64 * F::kWaves), 0,
-                ctx->stream, src, out, p, hspec, tb);
-    return nae_check(ctx, hipGetLastError(), "fir_block_kernel");
+    return with_flags(src.fs == 1 && out.fs == 1, [&](auto unit) {
+        return nae_launch_tiles(ctx, "fir_block_kernel", "fir_block_kernel: grid too large", fir_block_kernel<N, unit.value>, p.n_items, F::kWaves,
+                                64 * F::kWaves, 0, src, out, p, hspec, tb);
+    });
 }
 
 template <int N>
@@ -143,26 +138,15 @@ static int launch_fir_taps(nae_ctx* ctx, const float* hpad, cf* hspec, const Spe
 // ================================================================================================ host side
 using namespace nae;
 
-static bool fir_size_ok(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096; }
-
 size_t nae_fir_spec_floats(int n_fft) { return (size_t)n_fft + 2 * ((size_t)n_fft / 2 + 1); }
 
-// Blocks per tile of a launch over `blocks` blocks of n_sc stream-channels, in the style of the vocoder's pick_wave_tile: the tiles are cut for one
-// round of the waves a CU holds (Fir<N>::kResident) where the stream-channels alone do not give them, and never shorter than NAE_FIR_MIN_TILE blocks
-// (a tile re-reads half a block at its head: at most 1 / 16 of its input; a launch of fewer blocks is one tile).  fir_tile forces the tile.
+// Blocks per tile of a launch over `blocks` blocks of n_sc stream-channels: the one tile rule (nae_pick_tile) for the waves a CU holds
+// (Fir<N>::kResident), never shorter than NAE_FIR_MIN_TILE blocks, the number of tiles rounded down.  fir_tile forces the tile.
 int nae_pick_fir_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc)
 {
-    if (ctx->fir_tile > 0) return ctx->fir_tile;
-    const size_t n_cu = (size_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
-    if (blocks == 0 || n_sc == 0) return NAE_FIR_MIN_TILE;
     const size_t resident = n_fft == 512 ? Fir<512>::kResident : n_fft == 1024 ? Fir<1024>::kResident : n_fft == 2048 ? Fir<2048>::kResident
                                                                                                                        : Fir<4096>::kResident;
-    size_t n_tiles = (resident * n_cu + n_sc - 1) / n_sc;
-    const size_t max_tiles = blocks / NAE_FIR_MIN_TILE;    // rounded down: 41 blocks are 5 tiles of 9, not 6 of 7
-    if (n_tiles > max_tiles) n_tiles = max_tiles;
-    if (n_tiles < 1) n_tiles = 1;
-    const size_t tile = (blocks + n_tiles - 1) / n_tiles;
-    return (int)(tile < 0x40000000 ? tile : 0x40000000);
+    return nae_pick_tile(ctx, ctx->fir_tile, blocks, n_sc, resident, NAE_FIR_MIN_TILE, true);
 }
 
 // H of n_taps host taps into d_spec (nae_fir_spec_floats(n_fft) floats: the padded taps, then H[0 ... n_fft / 2]); waits for the upload
@@ -199,10 +183,8 @@ int nae_launch_fir(nae_ctx* ctx, int n_fft, const float* d_spec, const nae_sig* 
     p.n_tiles = (int)n_tiles;
     p.ch = ch;
     p.n_items = (long long)(n_sc * n_tiles);
-    const SigViewD sv = to_view(src);
-    const OutViewD ov{static_cast<float*>(dst->base), (long long)dst->stream_stride, (long long)dst->chan_stride, (long long)dst->frame_stride};
     const cf* hspec = reinterpret_cast<const cf*>(d_spec + n_fft);
-    return at_size(ctx, n_fft, [&](auto n) { return launch_fir<decltype(n)::value>(ctx, sv, ov, p, hspec, tb); });
+    return at_size(ctx, n_fft, [&](auto n) { return launch_fir<decltype(n)::value>(ctx, to_view(src), to_out(dst), p, hspec, tb); });
 }
 
 void nae_fir_cache_free(nae_ctx* ctx)
@@ -219,7 +201,7 @@ int nae_fir_check(nae_ctx* ctx, int n_taps, int ch, int* n_fft)
     if (n_taps < 1) return nae_fail(ctx, NAE_ERR_INVALID, "fir: n_taps must be at least 1");
     if (ch != 1 && ch != 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
     if (*n_fft == 0) *n_fft = nae_fir_pick_n_fft(n_taps);
-    if (!fir_size_ok(*n_fft)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "fir: n_fft must be 512, 1024, 2048 or 4096, and at most 2049 taps");
+    if (!nae_size_ok(*n_fft)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "fir: n_fft must be 512, 1024, 2048 or 4096, and at most 2049 taps");
     if (n_taps > *n_fft / 2 + 1) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "fir: at most n_fft / 2 + 1 taps");
     return NAE_OK;
 }
@@ -262,28 +244,16 @@ int nae_fir_block_f32(nae_ctx* ctx, const float* taps_host, int n_taps, int n_ff
 }
 
 // DESIGN.md §3, "K9 FIR filter", "Design": Kaiser-windowed sinc in double, rounded once
-static double fir_bessel_i0(double x)
-{
-    double sum = 1.0, term = 1.0;
-    const double q = x * x / 4.0;
-    for (int k = 1; k < 64; k++) {
-        term *= q / ((double)k * (double)k);
-        sum += term;
-        if (term < 1e-18 * sum) break;
-    }
-    return sum;
-}
-
 static void fir_lowpass(double fc, int sample_rate, int L, double* h)
 {
     const double pi = 3.14159265358979323846;
-    const double c = 2.0 * fc / (double)sample_rate, half = 0.5 * (double)(L - 1), i0b = fir_bessel_i0(NAE_FIR_KAISER_BETA);
+    const double c = 2.0 * fc / (double)sample_rate, half = 0.5 * (double)(L - 1), i0b = nae_bessel_i0(NAE_FIR_KAISER_BETA);
     double sum = 0.0;
     for (int n = 0; n < L; n++) {
         const double t = (double)n - half;
         const double a = L > 1 ? t / half : 0.0;
         const double r = 1.0 - a * a;
-        const double w = fir_bessel_i0(NAE_FIR_KAISER_BETA * sqrt(r > 0.0 ? r : 0.0)) / i0b;
+        const double w = nae_bessel_i0(NAE_FIR_KAISER_BETA * sqrt(r > 0.0 ? r : 0.0)) / i0b;
         const double arg = pi * c * t;
         const double sinc = arg == 0.0 ? 1.0 : sin(arg) / arg;
         h[n] = c * sinc * w;

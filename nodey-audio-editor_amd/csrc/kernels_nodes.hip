@@ -10,7 +10,7 @@
 //   K2 split/merge   audio-velocity.cpp:169-180,    K5 bimix v2   audio-bimix.cpp:624-627, 797-803, 833-850
 //                    audio-amix.cpp:263-269         K6 to-f32     audio-velocity.cpp:150-232
 //   K3 amix          audio-amix.cpp:293-307         clamp         audio-io.cpp:617-618
-#include "nae_internal.h"
+#include "launch.h"
 #include <algorithm>
 
 namespace nae {
@@ -109,12 +109,11 @@ static int launch_map_planes(nae_ctx* ctx, const void* const* src, void* const* 
 }
 
 // ------------------------------------------------------------------------------------------------ K2 / sig copy
-struct SigD { float* base; long long ss, cs, fs; };
 enum CopyMode { kGeneric = 0, kI2P = 1, kP2I = 2, kFlat = 3 };
 
 // stereo interleaved -> planar (optionally scaled): each thread moves 4 sample-frames (2 x float4 in)
 template <bool kScale>
-__global__ __launch_bounds__(kBlock) void copy_i2p_kernel(SigD src, SigD dst, long long S, float vol)
+__global__ __launch_bounds__(kBlock) void copy_i2p_kernel(SigViewD src, OutViewD dst, long long S, float vol)
 {
     const long long s = blockIdx.y;
     const float* __restrict__ in = src.base + s * src.ss;
@@ -139,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void copy_i2p_kernel(SigD src, SigD dst, lo
 }
 
 template <bool kScale>
-__global__ __launch_bounds__(kBlock) void copy_p2i_kernel(SigD src, SigD dst, long long S, float vol)
+__global__ __launch_bounds__(kBlock) void copy_p2i_kernel(SigViewD src, OutViewD dst, long long S, float vol)
 {
     const long long s = blockIdx.y;
     const float* __restrict__ iL = src.base + s * src.ss;
@@ -164,7 +163,7 @@ __global__ __launch_bounds__(kBlock) void copy_p2i_kernel(SigD src, SigD dst, lo
 
 // same element order on both sides and contiguous per stream: flat 16-byte copy of S*ch elements per stream
 template <bool kScale>
-__global__ __launch_bounds__(kBlock) void copy_flat_kernel(SigD src, SigD dst, long long n, float vol)
+__global__ __launch_bounds__(kBlock) void copy_flat_kernel(SigViewD src, OutViewD dst, long long n, float vol)
 {
     const long long s = blockIdx.y;
     const float* __restrict__ in = src.base + s * src.ss;
@@ -181,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void copy_flat_kernel(SigD src, SigD dst, l
 }
 
 template <bool kScale>
-__global__ __launch_bounds__(kBlock) void copy_generic_kernel(SigD src, SigD dst, long long S, int ch, float vol)
+__global__ __launch_bounds__(kBlock) void copy_generic_kernel(SigViewD src, OutViewD dst, long long S, int ch, float vol)
 {
     const long long s = blockIdx.y;
     const long long n = S * ch;
@@ -211,8 +210,8 @@ int nae_launch_copy_sig(nae_ctx* ctx, const nae_sig* src, const nae_sig* dst, si
     if (!ctx || !src || !dst || !src->base || !dst->base) return ctx ? nae_fail(ctx, NAE_ERR_INVALID, "null signal view") : NAE_ERR_INVALID;
     if (ch < 1) return nae_fail(ctx, NAE_ERR_INVALID, "channel count < 1");
     if (S == 0 || n_streams == 0) return NAE_OK;
-    SigD s{static_cast<float*>(src->base), (long long)src->stream_stride, (long long)src->chan_stride, (long long)src->frame_stride};
-    SigD d{static_cast<float*>(dst->base), (long long)dst->stream_stride, (long long)dst->chan_stride, (long long)dst->frame_stride};
+    const SigViewD s = to_view(src);
+    const OutViewD d = to_out(dst);
     int mode = kGeneric;
     if (ch == 2 && is_interleaved(src, 2) && is_planar(dst) && view_aligned(src, 0) && view_aligned(dst, dst->chan_stride)) mode = kI2P;
     else if (ch == 2 && is_planar(src) && is_interleaved(dst, 2) && view_aligned(src, src->chan_stride) && view_aligned(dst, 0)) mode = kP2I;
@@ -222,7 +221,8 @@ int nae_launch_copy_sig(nae_ctx* ctx, const nae_sig* src, const nae_sig* dst, si
         mode = kFlat;
     for (size_t s0 = 0; s0 < n_streams; s0 += 65535) {
         const unsigned ns = (unsigned)((n_streams - s0 < 65535) ? n_streams - s0 : 65535);
-        SigD ss = s, dd = d;
+        SigViewD ss = s;
+        OutViewD dd = d;
         ss.base += (long long)s0 * ss.ss;
         dd.base += (long long)s0 * dd.ss;
         const long long flat = (long long)S * ch;
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(kBlock) void amix_planes_kernel(MixPlanes a, float*
 struct MixSigs { const float* base[16]; long long ss[16], cs[16], fs[16]; float vol[16]; int n; };
 
 // fast path: every input interleaved stereo, output planar; 4 sample-frames per thread
-__global__ __launch_bounds__(kBlock) void amix_i2p_kernel(MixSigs a, SigD out, long long S)
+__global__ __launch_bounds__(kBlock) void amix_i2p_kernel(MixSigs a, OutViewD out, long long S)
 {
     const long long s = blockIdx.y;
     float* __restrict__ oL = out.base + s * out.ss;
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(kBlock) void amix_i2p_kernel(MixSigs a, SigD out, l
     }
 }
 
-__global__ __launch_bounds__(kBlock) void amix_generic_kernel(MixSigs a, SigD out, long long S)
+__global__ __launch_bounds__(kBlock) void amix_generic_kernel(MixSigs a, OutViewD out, long long S)
 {
     const long long s = blockIdx.y;
     const long long tid = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -656,12 +656,12 @@ int nae_amix_sig_f32(nae_ctx* ctx, const nae_sig* inputs, const float* vol, int 
         a.vol[i] = vol[i];
         fast = fast && is_interleaved(&inputs[i], 2) && view_aligned(&inputs[i], 0);
     }
-    SigD o{static_cast<float*>(out->base), (long long)out->stream_stride, (long long)out->chan_stride, (long long)out->frame_stride};
+    const OutViewD o = to_out(out);
     for (size_t s0 = 0; s0 < n_streams; s0 += 65535) {
         const unsigned ns = (unsigned)((n_streams - s0 < 65535) ? n_streams - s0 : 65535);
         MixSigs aa = a;
         for (int i = 0; i < n; i++) aa.base[i] += (long long)s0 * aa.ss[i];
-        SigD oo = o;
+        OutViewD oo = o;
         oo.base += (long long)s0 * oo.ss;
         unsigned gx = grid_for(fast ? S / 4 + 1 : 2 * S);
         if ((size_t)gx * ns > (size_t)kMaxGrid * 4) { gx = (unsigned)(((size_t)kMaxGrid * 4 + ns - 1) / ns); if (gx == 0) gx = 1; }

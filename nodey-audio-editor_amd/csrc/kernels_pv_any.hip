@@ -113,16 +113,15 @@ __global__ __launch_bounds__(64 * (PvAny<N, false, kTransient, kLink>::kWaves1))
     const int lane = threadIdx.x & 63;
     const long long item = (long long)blockIdx.x * P::kWaves1 + wave_id();
     if (item >= n_items) return;
-    const long long sc = item / p.n_tiles;
-    const int tile = (int)(item % p.n_tiles);
+    const WaveTile w = wave_tile(item, p.n_tiles, p.ch);
+    const long long s_idx = w.s_idx;
+    const int tile = w.tile, c = w.c;
     if (tile >= p.skip_from) return;                    // wave-uniform
     cf* scr = scratch + wave_id() * Gm::SCR;
     uint32_t* qp = state + wave_id() * 2 * P::ST + lane;  // [r * 64]: Qa_{f-1} of bin lane + 64 r
     uint32_t* acc = qp + P::ST;                          //           the tile's sum of increments
     float* pp = pprev + (kTransient ? wave_id() * P::ST + lane : 0);
     float* po = pother + (kLink ? wave_id() * P::ST + lane : 0);
-    const long long s_idx = sc / p.ch;
-    const int c = (int)(sc % p.ch);
     const ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
     const ChanView in2{src.base + s_idx * src.ss + (c ^ 1) * src.cs, src.fs, p.in_len};   // link (ch == 2): the stream's other channel
     const long long f0 = p.f_origin + (long long)tile * p.tile;
@@ -325,10 +324,9 @@ __global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient, kLink>::kWaves
     uint32_t* qs = qp + P::ST;                           //           Qs
     float* pp = pprev + (kTransient ? wave_id() * P::ST + lane : 0);
     float* po = pother + (kLink ? wave_id() * P::ST + lane : 0);
-    const long long sc = item / p.n_tiles;
-    const int tile = (int)(item % p.n_tiles);
-    const long long s_idx = sc / p.ch;
-    const int c = (int)(sc % p.ch);
+    const WaveTile w = wave_tile(item, p.n_tiles, p.ch);
+    const long long sc = w.sc, s_idx = w.s_idx;
+    const int tile = w.tile, c = w.c;
     const ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
     const ChanView in2{src.base + s_idx * src.ss + (c ^ 1) * src.cs, src.fs, p.in_len};   // link (ch == 2): the stream's other channel
     const long long b0 = p.f_origin + (long long)tile * p.tile;
@@ -457,53 +455,52 @@ __global__ __launch_bounds__(64 * (PvAny<N, kFormant, kTransient, kLink>::kWaves
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-template <int N, bool kTransient, bool kLink = false>
+// (unlocked, the link acts on the onset rule only: a linked kernel without transients does not exist, and nae_pv_resolve asks for none)
+template <int N, bool kUnit, bool kTransient, bool kLink>
 static int launch_phase(nae_ctx* ctx, const PvJob& j, const SpecAnyTables& tb)
 {
-    using P = PvAny<N, false, kTransient, kLink>;
-    const char* name = kLink ? "pv_any_phase_link_kernel" : kTransient ? "pv_any_phase_transient_kernel" : "pv_any_phase_kernel";
-    const long long items = j.n_sc * j.p.n_tiles;
-    const long long grid = (items + P::kWaves1 - 1) / P::kWaves1;
-    if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_phase_kernel: grid too large");
-    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pv_any_phase_kernel<N, true, kTransient, kLink> : pv_any_phase_kernel<N, false, kTransient, kLink>), dim3((unsigned)grid),
-                dim3(64 * P::kWaves1), 0, ctx->stream, j.src, j.p, items, j.phase_ws, tb);
-    return nae_check(ctx, hipGetLastError(), name);
+    if constexpr (kLink && !kTransient) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_phase_kernel: the link needs transients");
+    else {
+        using P = PvAny<N, false, kTransient, kLink>;
+        const char* name = kLink ? "pv_any_phase_link_kernel" : kTransient ? "pv_any_phase_transient_kernel" : "pv_any_phase_kernel";
+        const long long items = j.n_sc * j.p.n_tiles;
+        return nae_launch_tiles(ctx, name, "pv_any_phase_kernel: grid too large", pv_any_phase_kernel<N, kUnit, kTransient, kLink>, items, P::kWaves1,
+                                64 * P::kWaves1, 0, j.src, j.p, items, j.phase_ws, tb);
+    }
 }
 
-// from 256 tiles per stream-channel on, 16 threads per bin (pv_scan_chunked_kernel); else one (pv_scan_kernel)
+// from 256 tiles per stream-channel on, 16 threads per bin (pv_scan_chunked_kernel, one workgroup per (stream-channel, 64 bins)); else one
+// (pv_scan_kernel, 256 threads per workgroup)
 template <int N, bool kSeg>
 static int launch_scan(nae_ctx* ctx, const char* name, uint32_t* phase_ws, long long n_sc, int n_tiles, const uint32_t* carry_in,
                        uint32_t* carry_out, int n_read)
 {
     using P = PvAny<N>;
+    const char* grid_err = "pv_scan_kernel: grid too large";
     if (n_tiles >= 256 && n_sc * P::NB <= 0x7fffffffll) {
         if (kSeg) name = "pv_any_scan_chunked_transient_kernel";   // the segmented scans have profile names of their own
-        NAE_KLAUNCH(ctx, name, (pv_scan_chunked_kernel<N, kSeg>), dim3((unsigned)(n_sc * P::NB)), dim3(64 * kScanChunks), 0, ctx->stream,
-                    phase_ws, n_sc, n_tiles, carry_in, carry_out, n_read);
-        return nae_check(ctx, hipGetLastError(), name);
+        return nae_launch_tiles(ctx, name, grid_err, pv_scan_chunked_kernel<N, kSeg>, n_sc * P::NB, 1, 64 * kScanChunks, 0, phase_ws, n_sc, n_tiles,
+                                carry_in, carry_out, n_read);
     }
-    const long long grid = (n_sc * P::PAD + 255) / 256;
-    if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_scan_kernel: grid too large");
     if (kSeg) name = "pv_any_scan_transient_kernel";
-    NAE_KLAUNCH(ctx, name, (pv_scan_kernel<N, kSeg>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, phase_ws, n_sc, n_tiles, carry_in, carry_out,
-                n_read);
-    return nae_check(ctx, hipGetLastError(), name);
+    return nae_launch_tiles(ctx, name, grid_err, pv_scan_kernel<N, kSeg>, n_sc * P::PAD, 256, 256, 0, phase_ws, n_sc, n_tiles, carry_in, carry_out,
+                            n_read);
 }
 
-template <int N, bool kFormant, bool kTransient, bool kLink = false>
+template <int N, bool kUnit, bool kFormant, bool kTransient, bool kLink>
 static int launch_synth(nae_ctx* ctx, const PvJob& j, const SpecAnyTables& tb)
 {
-    using P = PvAny<N, kFormant, kTransient, kLink>;
-    const char* name = kLink      ? (kFormant ? "pv_any_synth_formant_link_kernel" : "pv_any_synth_link_kernel")
-                     : kTransient ? (kFormant ? "pv_any_synth_formant_transient_kernel" : "pv_any_synth_transient_kernel")
-                                  : (kFormant ? "pv_any_synth_formant_kernel" : "pv_any_synth_kernel");
-    const long long items = j.n_sc * j.p.n_tiles;
-    if (items == 0) return NAE_OK;
-    const long long grid = (items + P::kWaves3 - 1) / P::kWaves3;
-    if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_synth_kernel: grid too large");
-    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pv_any_synth_kernel<N, true, kFormant, kTransient, kLink> : pv_any_synth_kernel<N, false, kFormant, kTransient, kLink>),
-                dim3((unsigned)grid), dim3(64 * P::kWaves3), 0, ctx->stream, j.src, j.p, items, j.phase_ws, j.out, tb, j.lifter, j.g);
-    return nae_check(ctx, hipGetLastError(), name);
+    if constexpr (kLink && !kTransient) return nae_fail(ctx, NAE_ERR_INVALID, "pv_any_synth_kernel: the link needs transients");
+    else {
+        using P = PvAny<N, kFormant, kTransient, kLink>;
+        const char* name = kLink      ? (kFormant ? "pv_any_synth_formant_link_kernel" : "pv_any_synth_link_kernel")
+                         : kTransient ? (kFormant ? "pv_any_synth_formant_transient_kernel" : "pv_any_synth_transient_kernel")
+                                      : (kFormant ? "pv_any_synth_formant_kernel" : "pv_any_synth_kernel");
+        const long long items = j.n_sc * j.p.n_tiles;
+        if (items == 0) return NAE_OK;
+        return nae_launch_tiles(ctx, name, "pv_any_synth_kernel: grid too large", pv_any_synth_kernel<N, kUnit, kFormant, kTransient, kLink>, items,
+                                P::kWaves3, 64 * P::kWaves3, 0, j.src, j.p, items, j.phase_ws, j.out, tb, j.lifter, j.g);
+    }
 }
 
 } // namespace nae
@@ -513,17 +510,13 @@ using namespace nae;
 
 size_t nae_pv_record_pad(int n_fft) { return (size_t)((n_fft / 2 + 1 + 7) & ~7); }
 
-bool nae_pv_size_ok(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096; }
-
 int nae_pv_resident(nae_ctx* ctx, const nae_pv_run& r, PvKernels pass3)
 {
     if (pass3 == PvKernels::kLock) return 16;
     return at_size(ctx, r.n_fft, [&](auto n) {
         constexpr int N = decltype(n)::value;
         if (pass3 == PvKernels::kEnv) return PvEnv<N>::kResident;
-        if (r.link && r.transients) return r.lifter > 0 ? PvAny<N, true, true, true>::kResident3 : PvAny<N, false, true, true>::kResident3;
-        if (r.transients) return r.lifter > 0 ? PvAny<N, true, true>::kResident3 : PvAny<N, false, true>::kResident3;
-        return r.lifter > 0 ? PvAny<N, true>::kResident3 : PvAny<N>::kResident3;
+        return with_flags(r.lifter > 0, r.transients, r.link, [&](auto f, auto t, auto l) { return PvAny<N, f.value, t.value, t.value && l.value>::kResident3; });
     });
 }
 
@@ -533,9 +526,8 @@ int nae_launch_pvany_phase(nae_ctx* ctx, const PvJob& j)
     int rc = nae_spec_any_tables(ctx, j.n_fft, &tb);
     if (rc) return rc;
     return at_size(ctx, j.n_fft, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        if (j.link && j.transients) return launch_phase<N, true, true>(ctx, j, tb);
-        return j.transients ? launch_phase<N, true>(ctx, j, tb) : launch_phase<N, false>(ctx, j, tb);
+        return with_flags(j.unit_stride, j.transients, j.link,
+                          [&](auto u, auto t, auto l) { return launch_phase<decltype(n)::value, u.value, t.value, l.value>(ctx, j, tb); });
     });
 }
 
@@ -543,9 +535,9 @@ int nae_launch_pv_scan(nae_ctx* ctx, int n_fft, const char* name, uint32_t* phas
                        uint32_t* carry_out, int n_read, bool segmented)
 {
     return at_size(ctx, n_fft, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return segmented ? launch_scan<N, true>(ctx, name, phase_ws, n_sc, n_tiles, carry_in, carry_out, n_read)
-                         : launch_scan<N, false>(ctx, name, phase_ws, n_sc, n_tiles, carry_in, carry_out, n_read);
+        return with_flags(segmented, [&](auto seg) {
+            return launch_scan<decltype(n)::value, seg.value>(ctx, name, phase_ws, n_sc, n_tiles, carry_in, carry_out, n_read);
+        });
     });
 }
 
@@ -555,9 +547,8 @@ int nae_launch_pvany_synth(nae_ctx* ctx, const PvJob& j)
     int rc = nae_spec_any_tables(ctx, j.n_fft, &tb);
     if (rc) return rc;
     return at_size(ctx, j.n_fft, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        if (j.link && j.transients) return j.lifter > 0 ? launch_synth<N, true, true, true>(ctx, j, tb) : launch_synth<N, false, true, true>(ctx, j, tb);
-        if (j.transients) return j.lifter > 0 ? launch_synth<N, true, true>(ctx, j, tb) : launch_synth<N, false, true>(ctx, j, tb);
-        return j.lifter > 0 ? launch_synth<N, true, false>(ctx, j, tb) : launch_synth<N, false, false>(ctx, j, tb);
+        return with_flags(j.unit_stride, j.lifter > 0, j.transients, j.link, [&](auto u, auto f, auto t, auto l) {
+            return launch_synth<decltype(n)::value, u.value, f.value, t.value, l.value>(ctx, j, tb);
+        });
     });
 }

@@ -30,10 +30,9 @@ __global__ __launch_bounds__(64 * (PvEnv<N>::kWaves)) void pv_env_kernel(SigView
     cf* scr = scratch + wave_id() * Gm::SCR;
     cf* ys = yspec + wave_id() * P::PAD;
     float* lb = lbuf + wave_id() * P::PAD;
-    const long long sc = item / p.n_tiles;
-    const int tile = (int)(item % p.n_tiles);
-    const long long s_idx = sc / p.ch;
-    const int c = (int)(sc % p.ch);
+    const WaveTile w = wave_tile(item, p.n_tiles, p.ch);
+    const long long s_idx = w.s_idx;
+    const int tile = w.tile, c = w.c;
     const ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
     const long long b0 = p.f_origin + (long long)tile * p.tile;
     const long long b_end = b0 + p.tile < p.f_stop ? b0 + p.tile : p.f_stop;
@@ -71,11 +70,10 @@ static int launch_env(nae_ctx* ctx, const PvJob& j, const SpecAnyTables& tb)
     using E = PvEnv<N>;
     const long long items = j.n_sc * j.p.n_tiles;
     if (items == 0) return NAE_OK;
-    const long long grid = (items + E::kWaves - 1) / E::kWaves;
-    if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_env_kernel: grid too large");
-    NAE_KLAUNCH(ctx, "pv_env_kernel", (j.unit_stride ? pv_env_kernel<N, true> : pv_env_kernel<N, false>), dim3((unsigned)grid), dim3(64 * E::kWaves), 0,
-                ctx->stream, j.src, j.p, items, j.out, tb, j.lifter, j.g);
-    return nae_check(ctx, hipGetLastError(), "pv_env_kernel");
+    return with_flags(j.unit_stride, [&](auto unit) {
+        return nae_launch_tiles(ctx, "pv_env_kernel", "pv_env_kernel: grid too large", pv_env_kernel<N, unit.value>, items, E::kWaves, 64 * E::kWaves, 0,
+                                j.src, j.p, items, j.out, tb, j.lifter, j.g);
+    });
 }
 
 } // namespace nae

@@ -206,11 +206,10 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_map_kernel(SigViewD src, P
     uint16_t* ms = reinterpret_cast<uint16_t*>(mc + kT1024Pad);
     const long long item = (long long)blockIdx.x * kWaves + wave_id();
     if (item >= n_items) return;
-    const long long sc = item / p.n_tiles;
-    const int tile = (int)(item % p.n_tiles);
+    const WaveTile w = wave_tile(item, p.n_tiles, p.ch);
+    const long long s_idx = w.s_idx;
+    const int tile = w.tile, c = w.c;
     if (tile >= p.skip_from) return;                    // wave-uniform
-    const long long s_idx = sc / p.ch;
-    const int c = (int)(sc % p.ch);
     ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
     const ChanView in2{src.base + s_idx * src.ss + (c ^ 1) * src.cs, src.fs, p.in_len};   // link (ch == 2): the stream's other channel
 
@@ -488,10 +487,9 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
     uint32_t* qs = reinterpret_cast<uint32_t*>(mine + kPadScratchCf * sizeof(cf));
     const long long item = (long long)blockIdx.x * kWaves + wave_id();
     if (item >= n_items) return;
-    const long long sc = item / p.n_tiles;
-    const int tile = (int)(item % p.n_tiles);
-    const long long s_idx = sc / p.ch;
-    const int c = (int)(sc % p.ch);
+    const WaveTile w = wave_tile(item, p.n_tiles, p.ch);
+    const long long sc = w.sc, s_idx = w.s_idx;
+    const int tile = w.tile, c = w.c;
     ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
     const ChanView in2{src.base + s_idx * src.ss + (c ^ 1) * src.cs, src.fs, p.in_len};   // link (ch == 2): the stream's other channel
     PipeItem it;
@@ -632,78 +630,59 @@ __global__ __launch_bounds__(kThreads, 4) void pvlock_synth_kernel(SigViewD src,
 // ================================================================================================ host side
 using namespace nae;
 
-// the kernels here take more than 64 KiB of dynamic LDS: the attribute is set as for the vocoder pipeline (nae_pv_lds_attr), once per context
-// and kernel, the scan kernel at its largest size
-constexpr unsigned kAttrLockMap = 1u << 12, kAttrLockScan = 1u << 13, kAttrLockSynth = 1u << 14,   // nae_ctx::pv_attr_done (pipeline: bits 0-10)
-                   kAttrLockSynthF = 1u << 15, kAttrLockMapT = 1u << 16, kAttrLockScanT = 1u << 17, kAttrLockSynthT = 1u << 18,
-                   kAttrLockSynthFT = 1u << 19;   // a kLink instantiation: its unlinked kernel's bit << 8 (bits 20-27)
+// the kernels here take more than 64 KiB of dynamic LDS (the scan from 256 tiles on): the one launch path sets the attribute, as for the vocoder pipeline
 
 // transients: the kTransient instantiations (reset maps, the segmented scan; profile names pvlock_map_transient_kernel and
 // pvlock_scan_transient_kernel)
 // link: the kLink instantiations of the map kernel (pvlock_map_link_kernel, pvlock_map_transient_link_kernel); the scan does not change
+template <bool kUnit, bool kTransient, bool kLink>
+static int launch_lock_map(nae_ctx* ctx, const PvJob& j, uint32_t* maps, uint16_t* sig16)
+{
+    const char* name = kLink ? (kTransient ? "pvlock_map_transient_link_kernel" : "pvlock_map_link_kernel")
+                             : (kTransient ? "pvlock_map_transient_kernel" : "pvlock_map_kernel");
+    const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+    const long long items = j.n_sc * j.p.n_tiles;
+    return nae_launch_tiles(ctx, name, "pvlock_map_kernel: grid too large", pvlock_map_kernel<kUnit, kTransient, kLink>, items, kWaves, kThreads, kLdsLockMap,
+                            j.src, j.p, items, maps, sig16, tb);
+}
+
+// one workgroup per stream-channel, of one wave or (many tiles) of kLockChunks
+template <bool kTransient>
+static int launch_lock_scan(nae_ctx* ctx, const PvJob& j, int n_needed, const uint32_t* maps, const uint16_t* sig16, const uint32_t* carry_in,
+                            uint32_t* carry_out)
+{
+    const char* name = kTransient ? "pvlock_scan_transient_kernel" : "pvlock_scan_kernel";
+    const int nch = j.p.n_tiles >= 256 ? kLockChunks : 1;
+    return nae_launch_tiles(ctx, name, "pvlock_scan_kernel: grid too large", pvlock_scan_kernel<kTransient>, j.n_sc, 1, 64 * nch, nch * kLockScanWave,
+                            j.phase_ws, maps, sig16, j.p.n_tiles, carry_in, carry_out, n_needed);
+}
+
 int nae_launch_pvlock_phase(nae_ctx* ctx, const PvJob& j, int n_needed, uint32_t* maps, uint16_t* sig16, const uint32_t* carry_in, uint32_t* carry_out)
 {
-    const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
-    {
-        const long long items = j.n_sc * j.p.n_tiles;
-        const long long grid = (items + kWaves - 1) / kWaves;
-        if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_map_kernel: grid too large");
-        const char* name = j.link ? (j.transients ? "pvlock_map_transient_link_kernel" : "pvlock_map_link_kernel")
-                                  : (j.transients ? "pvlock_map_transient_kernel" : "pvlock_map_kernel");
-        auto k_unit = j.link ? (j.transients ? pvlock_map_kernel<true, true, true> : pvlock_map_kernel<true, false, true>)
-                             : (j.transients ? pvlock_map_kernel<true, true> : pvlock_map_kernel<true, false>);
-        auto k_strided = j.link ? (j.transients ? pvlock_map_kernel<false, true, true> : pvlock_map_kernel<false, false, true>)
-                                : (j.transients ? pvlock_map_kernel<false, true> : pvlock_map_kernel<false, false>);
-        int rc = nae_pv_lds_attr(ctx, (j.transients ? kAttrLockMapT : kAttrLockMap) << (j.link ? 8 : 0), kLdsLockMap, reinterpret_cast<const void*>(k_unit),
-                                 reinterpret_cast<const void*>(k_strided));
-        if (rc) return rc;
-        NAE_KLAUNCH(ctx, name, (j.unit_stride ? k_unit : k_strided), dim3((unsigned)grid), dim3(kThreads), kLdsLockMap, ctx->stream, j.src, j.p, items,
-                    maps, sig16, tb);
-        rc = nae_check(ctx, hipGetLastError(), name);
-        if (rc) return rc;
-    }
-    if (j.n_sc > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_scan_kernel: grid too large");
-    const char* name = j.transients ? "pvlock_scan_transient_kernel" : "pvlock_scan_kernel";
-    auto k_scan = j.transients ? pvlock_scan_kernel<true> : pvlock_scan_kernel<false>;
-    int rc = nae_pv_lds_attr(ctx, j.transients ? kAttrLockScanT : kAttrLockScan, kLockChunks * kLockScanWave, reinterpret_cast<const void*>(k_scan));
+    const int rc = with_flags(j.unit_stride, j.transients, j.link,
+                              [&](auto u, auto t, auto l) { return launch_lock_map<u.value, t.value, l.value>(ctx, j, maps, sig16); });
     if (rc) return rc;
-    const int nch = j.p.n_tiles >= 256 ? kLockChunks : 1;
-    NAE_KLAUNCH(ctx, name, k_scan, dim3((unsigned)j.n_sc), dim3(64 * nch), nch * kLockScanWave, ctx->stream, j.phase_ws, maps, sig16, j.p.n_tiles, carry_in,
-                carry_out, n_needed);
-    return nae_check(ctx, hipGetLastError(), name);
+    return with_flags(j.transients, [&](auto t) { return launch_lock_scan<t.value>(ctx, j, n_needed, maps, sig16, carry_in, carry_out); });
 }
 
-template <bool kFormant, bool kTransient, bool kLink = false>
-static int launch_lock_synth(nae_ctx* ctx, unsigned attr_bit, const char* name, const PvJob& j)
+// kFormant: formant preservation (pvlock_synth_formant_kernel); kTransient: onsets reset Qs (the *_transient_kernel instantiations); kLink: the
+// kLink instantiations (*_link_kernel)
+template <bool kUnit, bool kFormant, bool kTransient, bool kLink>
+static int launch_lock_synth(nae_ctx* ctx, const PvJob& j)
 {
-    const long long items = j.n_sc * j.p.n_tiles;
-    const long long grid = (items + kWaves - 1) / kWaves;
-    if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pvlock_synth_kernel: grid too large");
+    const char* name = kLink ? (kTransient ? (kFormant ? "pvlock_synth_formant_transient_link_kernel" : "pvlock_synth_transient_link_kernel")
+                                           : (kFormant ? "pvlock_synth_formant_link_kernel" : "pvlock_synth_link_kernel"))
+                             : (kTransient ? (kFormant ? "pvlock_synth_formant_transient_kernel" : "pvlock_synth_transient_kernel")
+                                           : (kFormant ? "pvlock_synth_formant_kernel" : "pvlock_synth_kernel"));
     const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
-    int rc = nae_pv_lds_attr(ctx, attr_bit, kLdsLockSynth, reinterpret_cast<const void*>(pvlock_synth_kernel<true, kFormant, kTransient, kLink>),
-                             reinterpret_cast<const void*>(pvlock_synth_kernel<false, kFormant, kTransient, kLink>));
-    if (rc) return rc;
-    NAE_KLAUNCH(ctx, name, (j.unit_stride ? pvlock_synth_kernel<true, kFormant, kTransient, kLink> : pvlock_synth_kernel<false, kFormant, kTransient, kLink>),
-                dim3((unsigned)grid), dim3(kThreads), kLdsLockSynth, ctx->stream, j.src, j.p, items, j.phase_ws, j.out, tb, j.lifter, j.g);
-    return nae_check(ctx, hipGetLastError(), name);
+    const long long items = j.n_sc * j.p.n_tiles;
+    return nae_launch_tiles(ctx, name, "pvlock_synth_kernel: grid too large", pvlock_synth_kernel<kUnit, kFormant, kTransient, kLink>, items, kWaves, kThreads,
+                            kLdsLockSynth, j.src, j.p, items, j.phase_ws, j.out, tb, j.lifter, j.g);
 }
 
-// lifter > 0: formant preservation (pvlock_synth_formant_kernel); transients: onsets reset Qs (the *_transient_kernel instantiations)
 int nae_launch_pvlock_synth(nae_ctx* ctx, const PvJob& j)
 {
     if (j.n_sc * j.p.n_tiles == 0) return NAE_OK;
-    if (j.link) {   // the kLink instantiations (*_link_kernel)
-        if (j.transients) {
-            if (j.lifter > 0) return launch_lock_synth<true, true, true>(ctx, kAttrLockSynthFT << 8, "pvlock_synth_formant_transient_link_kernel", j);
-            return launch_lock_synth<false, true, true>(ctx, kAttrLockSynthT << 8, "pvlock_synth_transient_link_kernel", j);
-        }
-        if (j.lifter > 0) return launch_lock_synth<true, false, true>(ctx, kAttrLockSynthF << 8, "pvlock_synth_formant_link_kernel", j);
-        return launch_lock_synth<false, false, true>(ctx, kAttrLockSynth << 8, "pvlock_synth_link_kernel", j);
-    }
-    if (j.transients) {
-        if (j.lifter > 0) return launch_lock_synth<true, true>(ctx, kAttrLockSynthFT, "pvlock_synth_formant_transient_kernel", j);
-        return launch_lock_synth<false, true>(ctx, kAttrLockSynthT, "pvlock_synth_transient_kernel", j);
-    }
-    if (j.lifter > 0) return launch_lock_synth<true, false>(ctx, kAttrLockSynthF, "pvlock_synth_formant_kernel", j);
-    return launch_lock_synth<false, false>(ctx, kAttrLockSynth, "pvlock_synth_kernel", j);
+    return with_flags(j.unit_stride, j.lifter > 0, j.transients, j.link,
+                      [&](auto u, auto f, auto t, auto l) { return launch_lock_synth<u.value, f.value, t.value, l.value>(ctx, j); });
 }

@@ -595,29 +595,24 @@ __global__ __launch_bounds__(kPipeThreads, 4) void pv_flow_kernel(SigViewD src, 
 
 using namespace nae;
 
-// one launch of one instantiation (attr_bit: its bit of nae_ctx::pv_attr_done, bits 0-10)
-template <typename K>
-static int pv_launch(nae_ctx* ctx, const char* name, K kernel_unit, K kernel_strided, unsigned attr_bit, size_t lds, unsigned groups, const PvJob& j)
+// one launch of one instantiation: kPipeSlots / kG items per workgroup
+template <int kG, typename K>
+static int pv_launch(nae_ctx* ctx, const char* name, K kernel, size_t lds, const PvJob& j)
 {
-    const int rc = nae_pv_lds_attr(ctx, attr_bit, lds, reinterpret_cast<const void*>(kernel_unit), reinterpret_cast<const void*>(kernel_strided));
-    if (rc) return rc;
     const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
-    NAE_KLAUNCH(ctx, name, j.unit_stride ? kernel_unit : kernel_strided, dim3(groups), dim3(kPipeThreads), lds, ctx->stream, j.src, j.p, j.n_sc, j.phase_ws,
-                j.out, tb);
-    return nae_check(ctx, hipGetLastError(), name);
+    return nae_launch_tiles(ctx, name, "pv_pipe_kernel: grid too large", kernel, j.n_sc * j.p.n_tiles, kPipeSlots / kG, kPipeThreads, lds, j.src, j.p,
+                            j.n_sc, j.phase_ws, j.out, tb);
 }
 
 template <int kG, bool kRich>
-static int pipe_launch(nae_ctx* ctx, unsigned groups, const PvJob& j)
+static int pipe_launch(nae_ctx* ctx, const PvJob& j)
 {
-    return pv_launch(ctx, "pv_pipe_kernel", &pv_pipe_kernel<true, kG, kRich>, &pv_pipe_kernel<false, kG, kRich>,
-                     1u << ((kG == 1 ? 0 : kG == 2 ? 1 : 2) * 2 + (kRich ? 1 : 0)), pipe_lds(kG), groups, j);
+    return with_flags(j.unit_stride, [&](auto u) { return pv_launch<kG>(ctx, "pv_pipe_kernel", &pv_pipe_kernel<u.value, kG, kRich>, pipe_lds(kG), j); });
 }
 template <int kG>
-static int flow_launch(nae_ctx* ctx, unsigned groups, const PvJob& j)
+static int flow_launch(nae_ctx* ctx, const PvJob& j)
 {
-    return pv_launch(ctx, "pv_flow_kernel", &pv_flow_kernel<true, kG>, &pv_flow_kernel<false, kG>, 1u << (8 + (kG == 1 ? 0 : kG == 2 ? 1 : 2)), flow_lds(kG),
-                     groups, j);
+    return with_flags(j.unit_stride, [&](auto u) { return pv_launch<kG>(ctx, "pv_flow_kernel", &pv_flow_kernel<u.value, kG>, flow_lds(kG), j); });
 }
 
 // frames_per_step: 1 = one stream-channel per slot; 2 / 4 = frame-interleaved (two / one stream-channel per four slots)
@@ -629,18 +624,16 @@ int nae_launch_pv_pipe(nae_ctx* ctx, const PvJob& j, int frames_per_step)
     const int units = kPipeSlots / frames_per_step;
     // stereo units come in channel pairs of one (stream, tile): n_sc is even, so items is
     const long long groups = (items + units - 1) / units;
-    if (groups > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_pipe_kernel: grid too large");
-    const unsigned g = (unsigned)groups;
     const bool one_per_cu = groups <= (long long)ctx->n_cu && !ctx->pv_lean;
     // at most one workgroup per CU, one frame per step (e.g. the 512 streams a rank of a 2-GPU job owns): the one-barrier schedule is 5 % faster; in the
     // frame-interleaved shapes it saves cycles and loses them to a lower clock (pv_flow = 2 forces it there)
     if (one_per_cu && (ctx->pv_flow >= 2 || (ctx->pv_flow == 1 && frames_per_step == 1))) {
-        if (frames_per_step == 1) return flow_launch<1>(ctx, g, j);
-        if (frames_per_step == 2) return flow_launch<2>(ctx, g, j);
-        return flow_launch<4>(ctx, g, j);
+        if (frames_per_step == 1) return flow_launch<1>(ctx, j);
+        if (frames_per_step == 2) return flow_launch<2>(ctx, j);
+        return flow_launch<4>(ctx, j);
     }
     // kRich: at most one workgroup per CU anyway (the frame-interleaved modes by their LDS; four slots per workgroup on a grid of at most n_cu workgroups)
-    if (frames_per_step == 1) return one_per_cu ? pipe_launch<1, true>(ctx, g, j) : pipe_launch<1, false>(ctx, g, j);
-    if (frames_per_step == 2) return pipe_launch<2, true>(ctx, g, j);
-    return pipe_launch<4, true>(ctx, g, j);
+    if (frames_per_step == 1) return with_flags(one_per_cu, [&](auto rich) { return pipe_launch<1, rich.value>(ctx, j); });
+    if (frames_per_step == 2) return pipe_launch<2, true>(ctx, j);
+    return pipe_launch<4, true>(ctx, j);
 }

@@ -34,11 +34,10 @@ __global__ __launch_bounds__(kThreads, 6) void pv_phase_kernel(SigViewD src, PvP
     cf* scratch = reinterpret_cast<cf*>(smem + kLdsTablesPad) + wave_id() * kPadScratchCf;
     const long long item = (long long)blockIdx.x * kWaves + wave_id();
     if (item >= n_items) return;
-    const long long sc = item / p.n_tiles;
-    const int tile = (int)(item % p.n_tiles);
+    const WaveTile w = wave_tile(item, p.n_tiles, p.ch);
+    const long long s_idx = w.s_idx;
+    const int tile = w.tile, c = w.c;
     if (tile >= p.skip_from) return;                    // wave-uniform
-    const long long s_idx = sc / p.ch;
-    const int c = (int)(sc % p.ch);
     ChanView in{src.base + s_idx * src.ss + c * src.cs, src.fs, p.in_len};
     const int kl = kl_of_lane(lane);
 
@@ -521,12 +520,6 @@ static int rs_pick_tile(double rho, long long* span_need)
     return tile;
 }
 
-static inline OutViewD to_out(const nae_sig* s)
-{
-    return OutViewD{static_cast<float*>(s->base), (long long)s->stream_stride, (long long)s->chan_stride,
-                    (long long)s->frame_stride};
-}
-
 // records [n_sc][n_tiles][nae_pv_record_pad(n_fft)] uint32 (the exclusive tile-prefix phases; 520 per record at 1024); locked (1024 only), then
 // the tile maps: c [n_sc][n_tiles][520] uint32, sigma [n_sc][n_tiles][520] uint16
 size_t nae_pv_workspace_bytes(bool lock, int n_fft, size_t n_frames, int ch, size_t n_streams, int tile)
@@ -600,12 +593,11 @@ int nae_launch_pv_phase(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_pla
     } else {
         // items are (stream-channel, tile) with tile fastest
         const long long items = n_sc * p.n_tiles;
-        const long long grid = (items + kWaves - 1) / kWaves;
-        if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, "pv_phase_kernel: grid too large");
         const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
-        NAE_KLAUNCH(ctx, "pv_phase_kernel", (j.unit_stride ? pv_phase_kernel<true> : pv_phase_kernel<false>), dim3((unsigned)grid), dim3(kThreads),
-                    kLdsPhase, ctx->stream, j.src, p, items, phase_ws, tb);
-        const int rc = nae_check(ctx, hipGetLastError(), "pv_phase_kernel");
+        const int rc = with_flags(j.unit_stride, [&](auto unit) {
+            return nae_launch_tiles(ctx, "pv_phase_kernel", "pv_phase_kernel: grid too large", pv_phase_kernel<unit.value>, items, kWaves, kThreads,
+                                    kLdsPhase, j.src, p, items, phase_ws, tb);
+        });
         if (rc) return rc;
     }
     return nae_launch_pv_scan(ctx, r.n_fft, pass1 == PvKernels::kAny ? "pv_any_scan_kernel" : "pv_scan_kernel", phase_ws, n_sc, p.n_tiles, carry_in,

@@ -93,7 +93,7 @@ static void build_tables(std::vector<nae::cf>& w512, std::vector<nae::cf>& t1024
     for (int n = 0; n < 1024; n++) hann[n] = (float)(0.5 - 0.5 * cos(two_pi * n / 1024.0));
 }
 
-static double bessel_i0(double x)
+double nae_bessel_i0(double x)
 {
     double sum = 1.0, term = 1.0;
     const double q = x * x / 4.0;
@@ -110,7 +110,7 @@ static void build_rs_table(double rate_eff, std::vector<float>& tab)
     const double pi = 3.14159265358979323846;
     const double c = NAE_RS_CUTOFF * (rate_eff > 1.0 ? 1.0 / rate_eff : 1.0);
     const double half = NAE_RS_TAPS / 2.0;
-    const double i0b = bessel_i0(NAE_RS_KAISER_BETA);
+    const double i0b = nae_bessel_i0(NAE_RS_KAISER_BETA);
     tab.resize((NAE_RS_PHASES + 1) * NAE_RS_TAPS);
     for (int p = 0; p <= NAE_RS_PHASES; p++) {
         double row[NAE_RS_TAPS], sum = 0.0;
@@ -118,7 +118,7 @@ static void build_rs_table(double rate_eff, std::vector<float>& tab)
             const double x = (double)(i - (NAE_RS_TAPS / 2 - 1)) - (double)p / NAE_RS_PHASES;
             const double a = x / half;
             double w = 0.0;
-            if (a > -1.0 && a < 1.0) w = bessel_i0(NAE_RS_KAISER_BETA * sqrt(1.0 - a * a)) / i0b;
+            if (a > -1.0 && a < 1.0) w = nae_bessel_i0(NAE_RS_KAISER_BETA * sqrt(1.0 - a * a)) / i0b;
             else if (a == 1.0 || a == -1.0) w = 1.0 / i0b;
             const double arg = pi * c * x;
             const double sinc = (fabs(arg) < 1e-12) ? 1.0 : sin(arg) / arg;
@@ -209,20 +209,19 @@ int nae_pick_pv_shape(nae_ctx* ctx, size_t frames, size_t n_sc, int* phase_tile,
     return (int)(pt * step);
 }
 
-// Tile of a block call whose pass 3 walks one tile per wave (the size-generic and the locked vocoder; synthesis tile = pass-1 tile): the tiles are
-// cut for one round of the `resident` pass-3 waves a CU holds where the stream-channels alone do not give them — more tiles would not add occupancy,
-// only re-analysis (a tile pays one priming and three tail frames) — and never shorter than `min_tile` frames.  A single tile per stream-channel
-// needs no pass 1.  pv_tile forces the tile.
-static int pick_wave_tile(nae_ctx* ctx, size_t frames, size_t n_sc, size_t resident, size_t min_tile)
+// The one tile rule (nae_internal.h).  For the vocoder: more tiles than one round of the resident pass-3 waves would not add occupancy, only
+// re-analysis (a tile pays one priming and three tail frames); a single tile per stream-channel needs no pass 1.  For the FIR filter: a tile
+// re-reads half a block at its head, at most 1 / 16 of its input, and a launch of fewer than min_tile blocks is one tile.
+int nae_pick_tile(nae_ctx* ctx, int forced, size_t units, size_t n_sc, size_t resident, size_t min_tile, bool max_tiles_down)
 {
-    if (ctx->pv_tile > 0) return ctx->pv_tile;
+    if (forced > 0) return forced;
     const size_t n_cu = (size_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
-    if (frames == 0 || n_sc == 0) return (int)min_tile;
+    if (units == 0 || n_sc == 0) return (int)min_tile;
     size_t n_tiles = (resident * n_cu + n_sc - 1) / n_sc;
-    const size_t max_tiles = (frames + min_tile - 1) / min_tile;
+    const size_t max_tiles = (units + (max_tiles_down ? 0 : min_tile - 1)) / min_tile;
     if (n_tiles > max_tiles) n_tiles = max_tiles;
     if (n_tiles < 1) n_tiles = 1;
-    const size_t tile = (frames + n_tiles - 1) / n_tiles;
+    const size_t tile = (units + n_tiles - 1) / n_tiles;
     return (int)(tile < 0x40000000 ? tile : 0x40000000);
 }
 
@@ -237,7 +236,7 @@ static int pv_block_shape(nae_ctx* ctx, const nae_pv_run& r, size_t frames, int 
     else {
         // the kernel's own residency (locked: four waves per SIMD), tiles of at least 64 frames (pv_min_ptile does not apply to the locked route)
         const size_t min_tile = pass3 != PvKernels::kLock && ctx->dbg_pv_min_ptile > 0 ? (size_t)ctx->dbg_pv_min_ptile : 64;
-        s->tile = s->phase_tile = pick_wave_tile(ctx, frames, n_sc, (size_t)nae_pv_resident(ctx, r, pass3), min_tile);
+        s->tile = s->phase_tile = nae_pick_tile(ctx, ctx->pv_tile, frames, n_sc, (size_t)nae_pv_resident(ctx, r, pass3), min_tile, false);
     }
     return nae_pv_reserve_ws(ctx, r, frames, ch, n_streams, s->phase_tile);
 }
@@ -543,7 +542,7 @@ int nae_stretch_plan_make_shift(double rate, double pitch, double formant_ratio,
 {
     if (!pl) return NAE_ERR_INVALID;
     memset(pl, 0, sizeof *pl);
-    if (!nae_pv_size_ok(n_fft)) return NAE_ERR_UNSUPPORTED;
+    if (!nae_size_ok(n_fft)) return NAE_ERR_UNSUPPORTED;
     const int hop = n_fft / 4;
     if (!(rate > 0.0) || !(pitch > 0.0)) return NAE_ERR_INVALID;
     if (!std::isfinite(formant_ratio) || !(formant_ratio > 0.0) || lifter < 0 || lifter > n_fft / 4) return NAE_ERR_INVALID;
@@ -607,7 +606,7 @@ int nae_pv_opts_check(nae_ctx* ctx, unsigned flags, unsigned allowed, int n_fft,
 {
     if (!ctx) return NAE_ERR_INVALID;
     if (flags & ~allowed) return nae_fail(ctx, NAE_ERR_INVALID, "unknown stretch flag");
-    if (!nae_pv_size_ok(n_fft)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
+    if (!nae_size_ok(n_fft)) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
     if ((flags & NAE_STRETCH_PHASE_LOCK) && n_fft != NAE_FFT_N) return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "phase locking runs at n_fft = 1024 only");
     if (lifter < 0 || lifter > n_fft / 4) return nae_fail(ctx, NAE_ERR_INVALID, "formant lifter must be in [0, n_fft / 4]");
     *o = nae_pv_opts{n_fft, lifter, (flags & NAE_STRETCH_PHASE_LOCK) != 0, (flags & NAE_STRETCH_TRANSIENTS) != 0, formant_ratio != nullptr,
@@ -733,7 +732,7 @@ int nae_stretch_block_n_f32(nae_ctx* ctx, double rate, double pitch, unsigned fl
 
 int nae_stretch_formant_lifter(int sample_rate, int n_fft)
 {
-    if (!nae_pv_size_ok(n_fft) || sample_rate <= 0) return 0;
+    if (!nae_size_ok(n_fft) || sample_rate <= 0) return 0;
     int q = sample_rate / 700;
     if (q < 1) q = 1;
     return q < n_fft / 4 ? q : n_fft / 4;

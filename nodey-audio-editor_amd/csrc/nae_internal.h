@@ -62,9 +62,9 @@ struct nae_ctx {
                                      // frame per step (default: where it is faster, profiles/r05_flow.md) / in every shape
     bool pv_lean = false;            // pv_lean: the vocoder pipeline keeps its 64-VGPR shape even when one workgroup per CU would allow
                                      // 128 (leaves half of the register file and 94 KB of LDS to a co-resident kernel: tools/coresidency.py)
-    // per-context, per-device launch state (a kernel attribute is set once per device: the flag lives with the context's device)
-    unsigned pv_attr_done = 0;       // bit per vocoder kernel (pv_pipe_kernel / pv_flow_kernel instantiation, pvlock_* kernel) whose dynamic-LDS
-                                     // attribute has been set through this context (nae_pv_lds_attr)
+    // per-context, per-device launch state (a kernel attribute is set once per device: the record lives with the context's device)
+    std::vector<const void*> lds_attr_done;   // the kernels (pv_pipe_kernel / pv_flow_kernel / pvlock_* instantiations, by address) whose
+                                              // dynamic-LDS attribute has been set through this context (nae_pv_lds_attr, launch.h)
     // optional per-kernel timing (hipEvent pairs on the ctx stream), used by bench.py for the roofline line
     bool prof_on = false;
     struct ProfSlot { const char* name; double total_ms; uint64_t launches; };
@@ -115,6 +115,15 @@ inline int nae_spectrum_check(int n_fft, int hop)
     if (hop < 1 || hop > n_fft) return NAE_ERR_INVALID;
     return NAE_OK;
 }
+// the frame sizes of the vocoder, the FIR filter and the long convolution (each caller has its own error text)
+inline bool nae_size_ok(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096; }
+// nae_api.hip: the modified Bessel function I0 of the Kaiser windows (the transposer's table, nae_fir_design), by its power series
+double nae_bessel_i0(double x);
+// nae_api.hip: the one tile rule of the launches that walk one tile per wave (the vocoder's pass 3 off the pipeline; the FIR filter and the long
+// convolution's spectra).  `forced` > 0 is the tile.  Else `units` frames or blocks of n_sc stream-channels are cut for one round of the
+// `resident` waves a CU holds where the stream-channels alone do not give them, into tiles of at least min_tile units: at most
+// ceil(units / min_tile) tiles, or with max_tiles_down floor(units / min_tile) — the FIR filter's, 41 blocks are 5 tiles of 9, not 6 of 7.
+int nae_pick_tile(nae_ctx* ctx, int forced, size_t units, size_t n_sc, size_t resident, size_t min_tile, bool max_tiles_down);
 // a continued stream processes frames / hop blocks [f_origin, f_origin + f_count) per call
 struct nae_pv_segment {
     long long f_origin, f_count;
@@ -204,9 +213,8 @@ int nae_launch_pv_phase(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_pla
                         int tile, int synth_tile, uint32_t* phase_ws, const nae_pv_segment* seg);
 int nae_launch_pv_synth(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_plan* pl, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
                         int tile, int phase_tile, uint32_t* phase_ws, const nae_sig* out, const nae_pv_segment* seg, int frames_per_step);
-// kernels_pv_any.hip: the vocoder sizes (512, 1024, 2048, 4096), the record length of a size (int32: N/2 + 1 padded to a multiple of 8), the
+// kernels_pv_any.hip: the record length of a size (int32: N/2 + 1 padded to a multiple of 8), the
 // pass-3 waves a CU holds on the kernels `pass3` (kAny: PvAny<N, formant, transients, link>::kResident3; kEnv: PvEnv<N>::kResident; kLock: 16)
-bool nae_pv_size_ok(int n_fft);
 size_t nae_pv_record_pad(int n_fft);
 int nae_pv_resident(nae_ctx* ctx, const nae_pv_run& r, PvKernels pass3);
 int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t src_len, int ch,

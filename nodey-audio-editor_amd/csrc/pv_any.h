@@ -3,7 +3,6 @@
 #pragma once
 #include "pv_roles.h"
 #include "fft_any.h"
-#include <type_traits>
 
 namespace nae {
 
@@ -230,18 +229,5 @@ struct PvEnv {
     static constexpr int kResident = kLdsResident < kVgprResident ? kLdsResident : kVgprResident;
     static_assert(kWaves >= 1, "a wave's state fits a CU's LDS");
 };
-
-// f(std::integral_constant<int, N>()) at the vocoder size N = n_fft
-template <typename F>
-static int at_size(nae_ctx* ctx, int n_fft, F&& f)
-{
-    switch (n_fft) {
-    case 512: return f(std::integral_constant<int, 512>());
-    case 1024: return f(std::integral_constant<int, 1024>());
-    case 2048: return f(std::integral_constant<int, 2048>());
-    case 4096: return f(std::integral_constant<int, 4096>());
-    default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
-    }
-}
 
 } // namespace nae

@@ -1,7 +1,7 @@
 // stft_common.h — kernel-side types and vocoder launch helpers shared by the STFT translation units (kernels_stft.hip, kernels_pvpipe.hip,
 // kernels_spectrum.hip, kernels_pvlock.hip).
 #pragma once
-#include "nae_internal.h"
+#include "launch.h"
 #include "stft_device.h"
 
 namespace nae {
@@ -9,15 +9,6 @@ namespace nae {
 constexpr int kT1024Pad = kPhasePad;             // 513 split twiddles / phases, padded to 520
 
 struct Tables { const cf* w512; const cf* t1024; const float* hann; };
-struct SigViewD { const float* base; long long ss, cs, fs; };
-struct OutViewD { float* base; long long ss, cs, fs; };
-
-inline SigViewD to_view(const nae_sig* s)
-{
-    return SigViewD{static_cast<const float*>(s->base), (long long)s->stream_stride, (long long)s->chan_stride,
-                    (long long)s->frame_stride};
-}
-
 // the 1024-point kernels on the padded FFT (spectrum, vocoder pass 1): 8-wave workgroups that stage Hann, the split twiddles,
 // W64 and the pass-A twiddles in LDS, followed by one padded FFT scratch per wave
 constexpr int kWaves = 8;                        // waves per workgroup
@@ -86,18 +77,12 @@ inline PvParams make_pv_params(const nae_stretch_plan& pl, size_t in_len, int ch
     return p;
 }
 
-// More than 64 KiB of dynamic LDS needs the attribute: once per kernel and DEVICE, so the flag (attr_bit of nae_ctx::pv_attr_done) lives in the
-// context (no process-global launch state: contexts of different devices, or driven by different threads, do not share it).  lds: the largest
-// launch of the kernel(s); k1 (optional): a second kernel under the same bit (the strided form of a unit-stride kernel).
-inline int nae_pv_lds_attr(nae_ctx* ctx, unsigned attr_bit, size_t lds, const void* k0, const void* k1 = nullptr)
+// The kernels that walk one wave per (stream-channel, tile) number their items with the tile fastest: stream-channel sc = (stream s_idx, channel c)
+struct WaveTile { long long sc, s_idx; int tile, c; };
+__device__ __forceinline__ WaveTile wave_tile(long long item, int n_tiles, int ch)
 {
-    if (ctx->pv_attr_done & attr_bit) return NAE_OK;
-    (void)nae_use_device(ctx);
-    hipError_t e = hipFuncSetAttribute(k0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && k1) e = hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return nae_check(ctx, e, "hipFuncSetAttribute(vocoder)");
-    ctx->pv_attr_done |= attr_bit;
-    return NAE_OK;
+    const long long sc = item / n_tiles;
+    return WaveTile{sc, sc / ch, (int)(item % n_tiles), (int)(sc % ch)};
 }
 
 __device__ __forceinline__ long long frame_start(const PvParams& p, long long f)

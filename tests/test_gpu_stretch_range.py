@@ -199,7 +199,7 @@ def cu_count():
 
 @pytest.mark.parametrize("n_fft", SIZES)
 def test_tile_policy_threshold(nae, ref, n_fft):
-    """pick_wave_tile at kResident3: below kResident3 * n_cu stream-channels a stream is cut into 2 tiles (pass 1 runs), from there on it is one tile
+    """nae_pick_tile at kResident3: below kResident3 * n_cu stream-channels a stream is cut into 2 tiles (pass 1 runs), from there on it is one tile
     (no pass 1).  Mono batches just below, at and above the switch, long enough for 65 frames (two 64-frame tiles): streams 0, middle and
     last equal their lone runs bit for bit, the first and last the restatement (at 1024 through the size-generic kernels, pv_any)"""
     n_cu = cu_count()
