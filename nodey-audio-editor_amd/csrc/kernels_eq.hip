@@ -8,7 +8,7 @@
 // the zero-input response of the state its lane starts from: y = y0 + ((p[k] z1) + (q[k] z2)).  The samples stay in registers as doubles from
 // section to section and are rounded once behind the last.  The carry state of section s between chunks is kept by lane s: (z1, z2) in two
 // register pairs, read by a broadcast and replaced by the scan's last value; a handle keeps it in device memory between launches.  Everything
-// that depends on the coefficients — p, q and the six maps — is made on the host in double (eq_make_tables) into a constant block of
+// that depends on the coefficients — p, q and the six maps — is made on the host in double-double (eq_make_tables) into a constant block of
 // 16 x (5 + 56) doubles.  The coefficients and the maps are read from it at wave-uniform addresses; p and q of the call's sections are copied
 // into LDS once per launch and read there as broadcasts (read from the block they cost 28 SGPR spills).
 // The translation unit is built with -ffp-contract=off: every step is one IEEE operation, in the order of the CPU statement
@@ -166,33 +166,72 @@ int nae_eq_check(nae_ctx* ctx, const double* coef, int n_sections, int ch)
     return NAE_OK;
 }
 
-// DESIGN.md §3, "K11 biquad cascade", step 2: the constant block of a cascade, in double and in the literal order of the zero-input recurrence
+// Double-double arithmetic for the tables: a value is hi + lo with |lo| <= ulp(hi) / 2, about 106 bits.  Every line is plain IEEE double
+// arithmetic (two-sum, and a two-product by fma()), written operation for operation as in tests/eq_ref/ref_eq.c: the two must give the same bits.
+struct EqDD { double hi, lo; };
+
+static EqDD dd_two_sum(double a, double b)
+{
+    const double s = a + b, bb = s - a;
+    return EqDD{s, (a - (s - bb)) + (b - bb)};
+}
+
+// |a| >= |b| or a == 0
+static EqDD dd_quick_sum(double a, double b)
+{
+    const double s = a + b;
+    return EqDD{s, b - (s - a)};
+}
+
+static EqDD dd_two_prod(double a, double b)
+{
+    const double p = a * b;
+    return EqDD{p, fma(a, b, -p)};
+}
+
+static EqDD dd_add(EqDD x, EqDD y)
+{
+    EqDD s = dd_two_sum(x.hi, y.hi);
+    const EqDD t = dd_two_sum(x.lo, y.lo);
+    s = dd_quick_sum(s.hi, s.lo + t.hi);
+    return dd_quick_sum(s.hi, s.lo + t.lo);
+}
+
+static EqDD dd_mul(EqDD x, EqDD y)
+{
+    const EqDD p = dd_two_prod(x.hi, y.hi);
+    return dd_quick_sum(p.hi, p.lo + ((x.hi * y.lo) + (x.lo * y.hi)));
+}
+
+// DESIGN.md §3, "K11 biquad cascade", step 2: the constant block of a cascade.  p, q and the six maps by the zero-input recurrence in its literal
+// order and five squarings, all in double-double; every entry is rounded to double once, at the end
 static void eq_make_tables(const double* coef, int n_sections, double* blk)
 {
     memset(blk, 0, kEqBlockDoubles * sizeof(double));
     for (int s = 0; s < n_sections; s++) {
-        const double a1 = coef[5 * s + 3], a2 = coef[5 * s + 4];
+        const EqDD na1 = {-coef[5 * s + 3], 0.0}, na2 = {-coef[5 * s + 4], 0.0};
         memcpy(blk + s * kEqCoefs, coef + 5 * s, 5 * sizeof(double));
         double* t = blk + kEqTabOfs + s * kEqTab;
         double* ph = t + 2 * kEqT;
+        EqDD m[4], r[4];
         for (int col = 0; col < 2; col++) {
-            double z1 = col == 0 ? 1.0 : 0.0, z2 = col == 0 ? 0.0 : 1.0;
+            EqDD z1 = {col == 0 ? 1.0 : 0.0, 0.0}, z2 = {col == 0 ? 0.0 : 1.0, 0.0};
             for (int n = 0; n < kEqT; n++) {
-                const double y = z1;
-                z1 = -a1 * y + z2;
-                z2 = -a2 * y;
-                t[col * kEqT + n] = y;
+                const EqDD y = z1;
+                z1 = dd_add(dd_mul(na1, y), z2);
+                z2 = dd_mul(na2, y);
+                t[col * kEqT + n] = y.hi + y.lo;
             }
-            ph[col] = z1;          // Phi: the two end states as columns, stored m00 m01 m10 m11
-            ph[2 + col] = z2;
+            m[col] = z1;           // Phi: the two end states as columns, stored m00 m01 m10 m11
+            m[2 + col] = z2;
         }
-        for (int j = 1; j < 6; j++) {
-            const double* m = ph + 4 * (j - 1);
-            double* r = ph + 4 * j;
-            r[0] = (m[0] * m[0]) + (m[1] * m[2]);
-            r[1] = (m[0] * m[1]) + (m[1] * m[3]);
-            r[2] = (m[2] * m[0]) + (m[3] * m[2]);
-            r[3] = (m[2] * m[1]) + (m[3] * m[3]);
+        for (int j = 0; j < 6; j++) {
+            for (int i = 0; i < 4; i++) ph[4 * j + i] = m[i].hi + m[i].lo;
+            r[0] = dd_add(dd_mul(m[0], m[0]), dd_mul(m[1], m[2]));
+            r[1] = dd_add(dd_mul(m[0], m[1]), dd_mul(m[1], m[3]));
+            r[2] = dd_add(dd_mul(m[2], m[0]), dd_mul(m[3], m[2]));
+            r[3] = dd_add(dd_mul(m[2], m[1]), dd_mul(m[3], m[3]));
+            for (int i = 0; i < 4; i++) m[i] = r[i];
         }
     }
 }

@@ -69,34 +69,45 @@ def view_call(nae, ctx, call, x, src_layout="i", dst_layout="i", shared=False, g
     return np.ascontiguousarray(out[:, :n, :])
 
 
-def stream(h, ctx, x, puts, device=False, on_put=None, after_flush=None, d_out=None):
+def stream(h, ctx, x, puts, device=False, on_put=None, after_flush=None, d_out=None, defer=False, piece=None):
     """x[n, ch] through the handle h, which is closed at the end: puts of the sizes in `puts` (the last one repeated) from the host or from
-    device memory, a receive of everything available after every put (into the device array d_out, if given, else into host memory), flush,
-    the rest -> [frames out, ch].  on_put(pos, taken, avail) after every put, with the frames put and received so far and those available;
+    device memory (device: one flag, or a sequence of flags taken in turn, put after put), a receive of everything available after every put
+    (into the device array d_out, if given, else into host memory), flush, the rest -> [frames out, ch].  defer: nothing is received before
+    the flush, so the handle's output grows while all of it is live.  piece: a receive takes at most that many frames, and is repeated
+    until nothing is left.  on_put(pos, taken, avail) after every put, with the frames put and received so far and those available;
     after_flush(taken) between the flush and the last receive."""
     n, ch = x.shape
-    d_x = ctx.array(x.reshape(-1)) if device else None
+    turn = tuple(device) if isinstance(device, (tuple, list)) else (device,)
+    d_x = ctx.array(x.reshape(-1)) if any(turn) else None
     try:
         parts, pos, i, taken = [], 0, 0, 0
 
         def take():
-            if d_out is None:
-                parts.append(h.receive_host())
-            else:
-                k = h.receive(d_out.ptr, h.available())
-                parts.append(d_out.download()[:k * ch].copy())
+            left = h.available()
+            while True:
+                k = left if piece is None else min(piece, left)
+                if d_out is None:
+                    part = h.receive_host() if piece is None else h.receive_host(k)
+                else:
+                    got = h.receive(d_out.ptr, k)
+                    part = d_out.download()[:got * ch].copy()
+                assert part.size == k * ch, "a receive delivers what was asked for and is available"
+                parts.append(part)
+                left -= k
+                if left == 0:
+                    break
         while pos < n:
             k = min(puts[min(i, len(puts) - 1)], n - pos)
-            i += 1
-            if device:
+            if turn[i % len(turn)]:
                 h.put(d_x.at(pos * ch), k)
             else:
                 h.put_host(x[pos:pos + k].reshape(-1))
+            i += 1
             pos += k
             avail = h.available()
             if on_put:
                 on_put(pos, taken, avail)
-            if avail:
+            if avail and not defer:
                 take()
                 taken += avail
         h.flush()

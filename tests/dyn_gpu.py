@@ -14,11 +14,11 @@ def gpu_dyn(nae, ctx, p, x, *views, **kw):
     return view_call(nae, ctx, lambda src, n, ch, n_streams, dst: ctx.dyn_block(lib_params(nae, p), src, n, ch, n_streams, dst), x, *views, **kw)
 
 
-def dyn_stream(nae, ctx, p, x, puts, device=False):
-    """x[n, ch] through a nae_dyn handle by block_gpu.stream -> [n, ch].  Before the flush what has become available is
-    floor((put - lookahead) / CHUNK) chunks, never negative."""
+def dyn_stream(nae, ctx, p, x, puts, device=False, **drive):
+    """x[n, ch] through a nae_dyn handle by block_gpu.stream (drive: its d_out, defer and piece) -> [n, ch].  Before the flush what has become
+    available is floor((put - lookahead) / CHUNK) chunks, never negative."""
     h = nae.Dyn(ctx, lib_params(nae, p), x.shape[1])
 
     def on_put(pos, taken, avail):
         assert taken + avail == max(pos - p.lookahead, 0) // dyn_ref.CHUNK * dyn_ref.CHUNK, "whole chunks whose look-ahead is complete"
-    return stream(h, ctx, x, puts, device, on_put, flushed(h, len(x)))
+    return stream(h, ctx, x, puts, device, on_put, flushed(h, len(x)), **drive)

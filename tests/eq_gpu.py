@@ -9,12 +9,12 @@ def gpu_eq(nae, ctx, coef, x, *views, **kw):
     return view_call(nae, ctx, lambda src, n, ch, n_streams, dst: ctx.eq_block(coef, src, n, ch, n_streams, dst), x, *views, **kw)
 
 
-def eq_stream(nae, ctx, coef, x, puts, device=False):
-    """x[n, ch] through a nae_eq handle by block_gpu.stream -> [n, ch].  What is available never exceeds what was put, and is whole chunks
-    until the flush."""
+def eq_stream(nae, ctx, coef, x, puts, device=False, **drive):
+    """x[n, ch] through a nae_eq handle by block_gpu.stream (drive: its d_out, defer and piece) -> [n, ch].  What is available never exceeds what
+    was put, and is whole chunks until the flush."""
     h = nae.Eq(ctx, coef, x.shape[1])
 
     def on_put(pos, taken, avail):
         assert taken + avail <= pos, "more available than was put"
         assert taken + avail == pos // eq_ref.CHUNK * eq_ref.CHUNK, "whole chunks come out as they fill"
-    return stream(h, ctx, x, puts, device, on_put, flushed(h, len(x)))
+    return stream(h, ctx, x, puts, device, on_put, flushed(h, len(x)), **drive)

@@ -23,9 +23,10 @@ GOOD_SECTIONS = ((1, 0, 0, 0, 0), (1, 0, 0, 1.499, 0.5), (1, 0, 0, 0, 0.999), (1
 def build(out_dir):
     L = cstatement.build(SRC, out_dir)
     L.ref_eq_check.argtypes = [C.c_void_p, C.c_int]
-    for name in ("ref_eq_run", "ref_eq_run_f64", "ref_eq_sequential", "ref_eq_sequential_f32"):
+    for name in ("ref_eq_run", "ref_eq_run_f64", "ref_eq_sequential", "ref_eq_sequential_f32", "ref_eq_sequential_ld"):
         getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     L.ref_eq_design.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    L.ref_eq_tables.argtypes, L.ref_eq_tables.restype = [C.c_double, C.c_double, C.c_void_p], None
     return L
 
 
@@ -75,6 +76,27 @@ def sequential_f32(L, coef, x):
     y = np.zeros(x.size, np.float32)
     assert L.ref_eq_sequential_f32(coef.ctypes.data, S, x.ctypes.data, x.size, 1, y.ctypes.data) == 0
     return y
+
+
+def sequential_ld(L, coef, x):
+    """the same recurrence with every value in long double, returned as double: the truth of the steady-state tests"""
+    coef, S = _coef(coef)
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.zeros(x.size, np.float64)
+    assert L.ref_eq_sequential_ld(coef.ctypes.data, S, x.ctypes.data, x.size, 1, y.ctypes.data) == 0
+    return y
+
+
+def ldbl_mant_dig(L):
+    """the significand bits of the statement's long double"""
+    return L.ref_eq_ldbl_mant_dig()
+
+
+def tables(L, a1, a2):
+    """the statement's tables of one section in the library's block order: p[16] q[16] Phi_0 ... Phi_5, each m00 m01 m10 m11"""
+    out = np.zeros(2 * LANE + 24, np.float64)
+    L.ref_eq_tables(float(a1), float(a2), out.ctypes.data)
+    return out
 
 
 def design(kind, sample_rate, freq, gain_db=0.0, q=0.7071):

@@ -1,6 +1,8 @@
 /* ref_eq.c — the CPU statement of K11, the biquad cascade ("K11 biquad cascade"): the tiled form the GPU computes, bit for bit
- * (ref_eq_run), the plain sequential double recurrence it is measured against (ref_eq_sequential), and the design (ref_eq_design).
+ * (ref_eq_run), the plain sequential double recurrence it is measured against (ref_eq_sequential), the same recurrence in long double that
+ * both are measured against at steady state (ref_eq_sequential_ld), the tables of one section (ref_eq_tables), and the design (ref_eq_design).
  * Built with -ffp-contract=off: every step is one IEEE double operation in the order written here. */
+#include <float.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -24,28 +26,81 @@ int ref_eq_check(const double* coef, int n_sections)
     return 0;
 }
 
-/* step 2: p, q and Phi_0 ... Phi_5 (m00 m01 m10 m11) of one section by the zero-input recurrence in its literal order */
+/* Double-double arithmetic for step 2: a value is hi + lo with |lo| <= ulp(hi) / 2, about 106 bits.  Every line is plain IEEE double
+ * arithmetic (two-sum, and a two-product by fma()), written operation for operation as in eq_make_tables (kernels_eq.hip): the two must
+ * give the same bits. */
+typedef struct { double hi, lo; } dd;
+
+static dd dd_two_sum(double a, double b)
+{
+    const double s = a + b, bb = s - a;
+    const dd r = { s, (a - (s - bb)) + (b - bb) };
+    return r;
+}
+
+/* |a| >= |b| or a == 0 */
+static dd dd_quick_sum(double a, double b)
+{
+    const double s = a + b;
+    const dd r = { s, b - (s - a) };
+    return r;
+}
+
+static dd dd_two_prod(double a, double b)
+{
+    const double p = a * b;
+    const dd r = { p, fma(a, b, -p) };
+    return r;
+}
+
+static dd dd_add(dd x, dd y)
+{
+    dd s = dd_two_sum(x.hi, y.hi);
+    const dd t = dd_two_sum(x.lo, y.lo);
+    s = dd_quick_sum(s.hi, s.lo + t.hi);
+    return dd_quick_sum(s.hi, s.lo + t.lo);
+}
+
+static dd dd_mul(dd x, dd y)
+{
+    const dd p = dd_two_prod(x.hi, y.hi);
+    return dd_quick_sum(p.hi, p.lo + ((x.hi * y.lo) + (x.lo * y.hi)));
+}
+
+/* step 2: p, q and Phi_0 ... Phi_5 (m00 m01 m10 m11) of one section by the zero-input recurrence in its literal order and five squarings, all in
+ * double-double; every entry is rounded to double once, at the end */
 static void tables(double a1, double a2, double* p, double* q, double phi[6][4])
 {
+    const dd na1 = { -a1, 0.0 }, na2 = { -a2, 0.0 };
+    dd m[4], r[4];
     for (int col = 0; col < 2; col++) {
-        double z1 = col == 0 ? 1.0 : 0.0, z2 = col == 0 ? 0.0 : 1.0;
+        dd z1 = { col == 0 ? 1.0 : 0.0, 0.0 }, z2 = { col == 0 ? 0.0 : 1.0, 0.0 };
         double* out = col == 0 ? p : q;
         for (int n = 0; n < T; n++) {
-            const double y = z1;
-            z1 = -a1 * y + z2;
-            z2 = -a2 * y;
-            out[n] = y;
+            const dd y = z1;
+            z1 = dd_add(dd_mul(na1, y), z2);
+            z2 = dd_mul(na2, y);
+            out[n] = y.hi + y.lo;
         }
-        phi[0][col] = z1;
-        phi[0][2 + col] = z2;
+        m[col] = z1;
+        m[2 + col] = z2;
     }
-    for (int j = 1; j < 6; j++) {
-        const double* m = phi[j - 1];
-        phi[j][0] = (m[0] * m[0]) + (m[1] * m[2]);
-        phi[j][1] = (m[0] * m[1]) + (m[1] * m[3]);
-        phi[j][2] = (m[2] * m[0]) + (m[3] * m[2]);
-        phi[j][3] = (m[2] * m[1]) + (m[3] * m[3]);
+    for (int j = 0; j < 6; j++) {
+        for (int i = 0; i < 4; i++) phi[j][i] = m[i].hi + m[i].lo;
+        r[0] = dd_add(dd_mul(m[0], m[0]), dd_mul(m[1], m[2]));
+        r[1] = dd_add(dd_mul(m[0], m[1]), dd_mul(m[1], m[3]));
+        r[2] = dd_add(dd_mul(m[2], m[0]), dd_mul(m[3], m[2]));
+        r[3] = dd_add(dd_mul(m[2], m[1]), dd_mul(m[3], m[3]));
+        for (int i = 0; i < 4; i++) m[i] = r[i];
     }
+}
+
+/* the statement's tables of one section in the library's block order: p[16] q[16] Phi_0 ... Phi_5, each m00 m01 m10 m11 */
+void ref_eq_tables(double a1, double a2, double* out)
+{
+    double phi[6][4];
+    tables(a1, a2, out, out + T, phi);
+    memcpy(out + 2 * T, phi, sizeof(phi));
 }
 
 /* one channel: x[n * stride], n < in_len, through the cascade: y[n * stride] rounded to f32 and / or yd[n] as it stands in double */
@@ -145,6 +200,32 @@ int ref_eq_sequential(const double* coef, int n_sections, const float* x, size_t
     }
     return 0;
 }
+
+/* the same recurrence with every value and operation in long double (64 bits of significand or more: ref_eq_ldbl_mant_dig), returned as
+ * double: what the two forms above are measured against at steady state */
+int ref_eq_sequential_ld(const double* coef, int n_sections, const float* x, size_t in_len, size_t stride, double* y)
+{
+    if (ref_eq_check(coef, n_sections) || !x || !y) return -1;
+    long double* v = malloc((in_len ? in_len : 1) * sizeof(long double));
+    if (!v) return -1;
+    for (size_t n = 0; n < in_len; n++) v[n] = (long double)x[n * stride];
+    for (int s = 0; s < n_sections; s++) {
+        const long double b0 = coef[5 * s], b1 = coef[5 * s + 1], b2 = coef[5 * s + 2], a1 = coef[5 * s + 3], a2 = coef[5 * s + 4];
+        long double z1 = 0.0L, z2 = 0.0L;
+        for (size_t n = 0; n < in_len; n++) {
+            const long double xv = v[n];
+            const long double yv = b0 * xv + z1;
+            z1 = (b1 * xv - a1 * yv) + z2;
+            z2 = b2 * xv - a2 * yv;
+            v[n] = yv;
+        }
+    }
+    for (size_t n = 0; n < in_len; n++) y[n] = (double)v[n];
+    free(v);
+    return 0;
+}
+
+int ref_eq_ldbl_mant_dig(void) { return LDBL_MANT_DIG; }
 
 /* the same recurrence with every value and operation in f32: what the choice of double is measured against */
 int ref_eq_sequential_f32(const double* coef, int n_sections, const float* x, size_t in_len, size_t stride, float* y)

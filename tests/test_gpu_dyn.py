@@ -1,6 +1,6 @@
 """K12 dynamics on the GPU, bit for bit against the CPU statement (tests/dyn_ref/ref_dyn.c): every length around the lane, the wave and the chunk
-at every look-ahead, every view, linked and unlinked detectors, hard and soft knee, limiter and compressor, the streaming handle, non-finite,
-subnormal and zero input, two contexts from two threads, the error codes, and the host node (tests/dyn_ref/host_dyn_node.cpp)."""
+at every look-ahead, every view, linked and unlinked detectors, hard and soft knee, limiter and compressor, a launch of 300 chunks, the
+streaming handle in short and in long streams, non-finite, subnormal and zero input, two contexts from two threads, the error codes, and the host node (tests/dyn_ref/host_dyn_node.cpp)."""
 import ctypes as C
 import subprocess
 import threading
@@ -84,6 +84,17 @@ def test_larger_launch(nae, ctx, ref):
         assert np.array_equal(bits(gpu_dyn(nae, ctx, p, x, "p", "i", chan_pad=1)), bits(dyn_ref.run_streams(ref, p, x)))
 
 
+@pytest.mark.parametrize("link", (1, 0))
+def test_long_launch(nae, ctx, ref, link):
+    """two stereo streams of 300 C + 7 samples, planar in and interleaved out, the slowest attack and release and the longest look-ahead: one
+    wave per detector walks 301 chunks, and the smoothed level it carries from chunk to chunk has a memory of hundreds of them"""
+    p = dyn_ref.params(lookahead=1024, link=link, **dyn_ref.SLOW)
+    x = loud(np.random.default_rng(300 + link), 2, 300 * CH + 7, 2)
+    got = gpu_dyn(nae, ctx, p, x, "p", "i", chan_pad=3)
+    want = dyn_ref.run_streams(ref, p, x)
+    assert np.array_equal(bits(got), bits(want)), int(np.sum(bits(got) != bits(want)))
+
+
 @pytest.mark.parametrize("la", (0, 17, 1024))
 @pytest.mark.parametrize("put", (1, 7, 1000, 1024, 1025, 5000))
 def test_handle_equals_the_block_call(nae, ctx, ref, put, la):
@@ -107,6 +118,35 @@ def test_handle_mixed_puts(nae, ctx, ref):
     want = dyn_ref.run_streams(ref, p, x)[0]
     for puts, device in (((1, 7, 1023, 1025, 2500), False), ((1025, 1, 1022, 7), True), ((CH,), False), ((5 * CH,), True), ((2 * CH + 40, 3, CH), True)):
         assert np.array_equal(bits(dyn_stream(nae, ctx, p, x[0], puts, device)), bits(want)), puts
+
+
+@pytest.fixture(scope="module")
+def long_stream(nae, ctx, ref):
+    """x[100 000, 2] (three times what a handle's FIFOs start with), the slowest attack and release, look-ahead 1024, linked: the block
+    call's result, the statement's bits"""
+    p = dyn_ref.params(lookahead=1024, link=1, **dyn_ref.SLOW)
+    x = loud(np.random.default_rng(100000), 1, 100000, 2)
+    block = gpu_dyn(nae, ctx, p, x)[0]
+    assert np.array_equal(bits(block), bits(dyn_ref.run_streams(ref, p, x)[0]))
+    puts = tuple(int(k) for k in np.random.default_rng(9000).integers(1, 9001, 64))
+    return p, x[0], block, puts
+
+
+@pytest.mark.parametrize("drive", ("received after every put", "received after the flush", "one put, received in pieces"))
+def test_handle_long_stream(nae, ctx, long_stream, drive):
+    """100 000 frames through a handle give the block call's bits, and `available` follows floor((put - 1024) / 1024) chunks after every
+    put (dyn_stream asserts it).  Seeded random puts of 1 ... 9000 frames, from the device and the host in turn: the input FIFO, which
+    keeps the look-ahead, runs out of room again and again and moves its live rest to the front in place, and the carries cross some twenty
+    launches; the same with nothing received before the flush: the output FIFO grows twice while all of it is live; one put of
+    everything, received device to device in pieces of 4096 frames"""
+    p, x, block, puts = long_stream
+    if drive == "one put, received in pieces":
+        d_out = ctx.array(np.zeros(4096 * 2, np.float32))
+        got = dyn_stream(nae, ctx, p, x, (len(x),), device=True, d_out=d_out, piece=4096)
+        d_out.free()
+    else:
+        got = dyn_stream(nae, ctx, p, x, puts, device=(True, False), defer=drive == "received after the flush")
+    assert got.shape == block.shape and np.array_equal(bits(got), bits(block)), int(np.sum(bits(got) != bits(block)))
 
 
 @pytest.mark.parametrize("la", (0, 17, 1024))

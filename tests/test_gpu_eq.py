@@ -1,6 +1,6 @@
 """K11 biquad cascade on the GPU, bit for bit against the CPU statement (tests/eq_ref/ref_eq.c): every length around the lane and the chunk,
-short and long cascades, every view, a launch of many workgroups, the streaming handle, non-finite and subnormal input, the error codes, and
-the host node (tests/eq_ref/host_eq_node.cpp)."""
+short and long cascades, every view, a launch of many workgroups, a launch of 300 chunks, the streaming handle in short and in long streams,
+non-finite and subnormal input, the error codes, and the host node (tests/eq_ref/host_eq_node.cpp)."""
 import ctypes as C
 import subprocess
 
@@ -70,6 +70,26 @@ def test_larger_launch(nae, ctx, ref):
     assert np.array_equal(bits(gpu_eq(nae, ctx, coef, x, "p", "i", chan_pad=1)), bits(want))
 
 
+def low_two_tone(n):
+    """20 Hz + 40 Hz at 48 kHz: what the hard cascade's bells, whose memory is tens of chunks long, respond to"""
+    t = np.arange(n)
+    return (0.5 * np.sin(2 * np.pi * 20 * t / 48000) + 0.3 * np.sin(2 * np.pi * 40 * t / 48000)).astype(np.float32)
+
+
+@pytest.mark.parametrize("name", ("hard", "S16"))
+def test_long_launch(nae, ctx, ref, name):
+    """two stereo streams of 300 C + 7 samples, planar in and interleaved out: one wave per stream-channel walks 301 chunks, far into the
+    steady state of the 20 - 60 Hz bells, where an error of the library's carry tables (made on the host, as the statement's, in
+    double-double) has added up over the filter's memory; channel 1 carries the low two-tone on top of the noise"""
+    coef = eq_ref.hard_cascade() if name == "hard" else eq_ref.cascade(16)
+    in_len = 300 * CH + 7
+    x = noise(np.random.default_rng(300), 2, in_len, 2)
+    x[:, :, 1] += low_two_tone(in_len)
+    got = gpu_eq(nae, ctx, coef, x, "p", "i", chan_pad=3)
+    want = eq_ref.run_streams(ref, coef, x)
+    assert np.array_equal(bits(got), bits(want)), int(np.sum(bits(got) != bits(want)))
+
+
 def test_the_context_keeps_its_tables_and_takes_new_ones(nae, ctx, ref):
     x = noise(np.random.default_rng(6), 1, CH + 9, 2)
     a, b = eq_ref.cascade(3), eq_ref.cascade(5)[2:]
@@ -96,6 +116,34 @@ def test_handle_mixed_puts(nae, ctx, ref):
     want = eq_ref.run_streams(ref, coef, x)[0]
     for puts, device in (((1, 7, 1023, 1025, 2500), False), ((1025, 1, 1022, 7), True), ((CH,), False), ((5 * CH,), True)):
         assert np.array_equal(bits(eq_stream(nae, ctx, coef, x[0], puts, device)), bits(want)), puts
+
+
+@pytest.fixture(scope="module")
+def long_stream(nae, ctx, ref):
+    """x[100 000, 2] (three times what a handle's FIFOs start with) through the hard cascade: the block call's result, the statement's bits"""
+    coef = eq_ref.hard_cascade()
+    x = noise(np.random.default_rng(100000), 1, 100000, 2)
+    x[0, :, 1] += low_two_tone(100000)
+    block = gpu_eq(nae, ctx, coef, x)[0]
+    assert np.array_equal(bits(block), bits(eq_ref.run_streams(ref, coef, x)[0]))
+    puts = tuple(int(k) for k in np.random.default_rng(9000).integers(1, 9001, 64))
+    return coef, x[0], block, puts
+
+
+@pytest.mark.parametrize("drive", ("received after every put", "received after the flush", "one put, received in pieces"))
+def test_handle_long_stream(nae, ctx, long_stream, drive):
+    """100 000 frames through a handle give the block call's bits.  Seeded random puts of 1 ... 9000 frames, from the device and the host in
+    turn: the input FIFO runs out of room again and again and moves its live rest to the front in place, and the carry of every section
+    crosses some twenty launches; the same with nothing received before the flush: the output FIFO grows twice while all of it is live; one
+    put of everything, received device to device in pieces of 4096 frames"""
+    coef, x, block, puts = long_stream
+    if drive == "one put, received in pieces":
+        d_out = ctx.array(np.zeros(4096 * 2, np.float32))
+        got = eq_stream(nae, ctx, coef, x, (len(x),), device=True, d_out=d_out, piece=4096)
+        d_out.free()
+    else:
+        got = eq_stream(nae, ctx, coef, x, puts, device=(True, False), defer=drive == "received after the flush")
+    assert got.shape == block.shape and np.array_equal(bits(got), bits(block)), int(np.sum(bits(got) != bits(block)))
 
 
 @pytest.mark.parametrize("bad", (np.nan, np.inf, -np.inf))
