@@ -64,6 +64,17 @@
 #define NAE_DYN_MIN_RELEASE_S 0.001
 #define NAE_DYN_MAX_RELEASE_S 5.0
 #define NAE_DYN_MAX_MAKEUP_DB 24.0
+/* K13 spectral gate ("K13 spectral gate"): noise reduction on the STFT at N = 512 ... 4096 and hop N / 4: a per-bin decision
+ * against a learned power profile, smoothed by an integer triangle over at most NAE_DENOISE_MAX_TIME frames and NAE_DENOISE_MAX_FREQ bins to
+ * either side (a wider frequency triangle pulls a pure tone down: DESIGN.md gives the figure); a tile the library chooses has at least
+ * NAE_DENOISE_MIN_TILE hop blocks (it pays 3 Tn + 3 analyses beyond its own frames) */
+#define NAE_DENOISE_MAX_TIME 8
+#define NAE_DENOISE_MAX_FREQ 4
+#define NAE_DENOISE_MIN_TILE 32
+/* nae_denoise_design: the ranges of its arguments */
+#define NAE_DENOISE_MAX_REDUCTION_DB 48.0
+#define NAE_DENOISE_MIN_SENSITIVITY_DB (-6.0)
+#define NAE_DENOISE_MAX_SENSITIVITY_DB 24.0
 /* transient preservation ("Transient preservation"): bin k of frame f rises iff P_f[k] > RISE * P_{f-1}[k] and
  * P_f[k] > FLOOR * N; frame f is "high" iff DEN * (rising bins) >= NUM * (N/2 + 1); an onset is an upward crossing of "high" at f >= 2.
  * RISE is +6 dB: at +3 dB steady white noise crosses 3/8 at N = 512 and 1024 (DESIGN.md gives the numbers). */

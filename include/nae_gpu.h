@@ -45,7 +45,8 @@ extern "C" {
  *   _available, _receive, _receive_host, _destroy): the FIR filter, K9; nae_conv_pick_n_fft, nae_conv_block_f32, nae_conv_reverb_taps,
  *   nae_conv_design_reverb and the nae_conv handle (the same eight entries): the long convolution, K10; nae_eq_design, nae_eq_block_f32 and
  *   the nae_eq handle (the same eight entries): the biquad cascade, K11; nae_dyn_design, nae_dyn_block_f32 and the nae_dyn handle (the same
- *   eight entries) with the record nae_dyn_params: the dynamics processor, K12. */
+ *   eight entries) with the record nae_dyn_params: the dynamics processor, K12; nae_denoise_design, nae_denoise_profile_f32,
+ *   nae_denoise_block_f32 and the nae_denoise handle (the same eight entries) with the record nae_denoise_params: the spectral gate, K13. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -71,6 +72,7 @@ typedef struct nae_fir nae_fir;
 typedef struct nae_conv nae_conv;
 typedef struct nae_eq nae_eq;
 typedef struct nae_dyn nae_dyn;
+typedef struct nae_denoise nae_denoise;
 
 /* ------------------------------------------------------------------ context / plumbing */
 int nae_abi_version(void);
@@ -152,6 +154,7 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *   conv_tile       blocks one wave of the long convolution's accumulate kernel walks (0: the register tile, nae_pick_conv_tile)
  *   conv_ring       spectrum slots per stream-channel of the long convolution's workspace ring (0: from the workspace cap; at least the
  *                   partition count is used); a handle reads it when it is created.  Neither changes a result
+ *   dn_tile         hop blocks (of n_fft / 4 samples) one wave of the spectral gate walks (0: nae_pick_denoise_tile); every tiling gives the same bits
  * The same assignments, comma separated, in the environment variable NAE_DEBUG ("pv_flow=2,pv_fps=4") are applied when a context is created
  * (for measuring a program that creates its contexts itself, e.g. bench.py); an unknown key there fails nae_ctx_create with NAE_ERR_INVALID. */
 int nae_debug_set(nae_ctx* ctx, const char* key, long long value);
@@ -603,6 +606,53 @@ int nae_dyn_destroy(nae_dyn* h);
  * NAE_DYN_MAX_LOOKAHEAD samples at this rate.  No context, no device work. */
 int nae_dyn_design(int sample_rate, double threshold_db, double ratio, double knee_db, double attack_s, double release_s, double lookahead_s,
                    double makeup_db, int link, nae_dyn_params* out);
+
+/* ------------------------------------------------------------------ K13 spectral gate
+ * no reference code.  Spec ("K13 spectral gate"): noise reduction on the STFT at n_fft = 512 ... 4096, hop H = n_fft / 4, in the
+ * vocoder's geometry at tempo 1 (frame f starts at sample (f - 3) H; the signal is zero outside [0, in_len)).  Per frame and bin the power
+ * p = X.x X.x + X.y X.y of the canonical r2c of the Hann-windowed frame is compared with the channel's learned noise power:
+ * d = p > profile[c][k] thr_scale (one f32 product; a NaN compares false; frames outside the signal are closed).  The decisions are smoothed
+ * in integers by a triangle over time_smooth frames and freq_smooth bins to either side (mirrored at bins 0 and n_fft / 2) to a count c of at
+ * most C = (time_smooth + 1)^2 (freq_smooth + 1)^2; the bin's gain is 1 where c = C and floor_gain + span ((float)c inv_c) elsewhere, with
+ * span = (float)(1 - floor_gain) and inv_c = (float)(1 / C) rounded once from double.  Synthesis is the vocoder's: c2r, window, overlap-add in
+ * increasing frame order, NAE_OLA_GAIN.  The output has the input's length and is aligned with it sample for sample; with floor_gain = 1 the
+ * call is the STFT identity.  Bit-exact against the CPU statement (tests/denoise_ref/ref_denoise.c) under every tiling (debug key dn_tile)
+ * and any cut of the input into puts.  A non-finite sample i changes only the samples from (floor(i / H) - time_smooth - 3) H up to, not
+ * including, (floor(i / H) + time_smooth + 4) H of its own stream-channel; the call returns NAE_OK.
+ * profile_dev: device memory, [profile_ch][n_fft / 2 + 1] noise powers; profile_ch = 1 is one profile for every channel.  It is read by the
+ * launch: keep it alive and unchanged until the stream has run it (a handle copies it at creation).
+ * Errors: a null pointer, ch not 1 or 2, profile_ch not 1 or ch, time_smooth outside 0 ... NAE_DENOISE_MAX_TIME, freq_smooth outside
+ * 0 ... NAE_DENOISE_MAX_FREQ, thr_scale negative or not finite, floor_gain outside [0, 1] or not finite: NAE_ERR_INVALID; n_fft other than 512,
+ * 1024, 2048, 4096: NAE_ERR_UNSUPPORTED; in_len = 0 or n_streams = 0: NAE_OK after the checks, nothing is launched.  Views as K9's. */
+typedef struct nae_denoise_params {
+    int n_fft;              /* 512, 1024, 2048 or 4096 */
+    int time_smooth;        /* Tn: frames to either side, 0 ... NAE_DENOISE_MAX_TIME */
+    int freq_smooth;        /* Fn: bins to either side, 0 ... NAE_DENOISE_MAX_FREQ */
+    float thr_scale;        /* a bin is open where its power exceeds profile * thr_scale; >= 0 */
+    float floor_gain;       /* gain of a fully closed bin, 0 ... 1 */
+} nae_denoise_params;
+/* The parameters on the host: thr_scale = (float)10^(sensitivity_db / 10), floor_gain = (float)10^(-reduction_db / 20).  NAE_ERR_INVALID: a null
+ * pointer, an argument that is not finite, reduction_db outside 0 ... 48, sensitivity_db outside -6 ... 24, a smoothing width outside its range;
+ * NAE_ERR_UNSUPPORTED: n_fft other than 512 ... 4096.  No context, no device work. */
+int nae_denoise_design(double reduction_db, double sensitivity_db, int n_fft, int time_smooth, int freq_smooth, nae_denoise_params* out);
+/* The noise profile of an excerpt: channel c of stream 0 of `src`, `len` samples.  The frames start at 0, H, 2 H, ... while start + n_fft <= len
+ * (n of them; n = 0: NAE_ERR_INVALID); profile_dev[c][k] = (float)(sum over the frames, in order, of (double)p[k] / (double)n).  Asynchronous on
+ * the context's stream, like the block entries; profile_dev receives [ch][n_fft / 2 + 1] floats. */
+int nae_denoise_profile_f32(nae_ctx* ctx, int n_fft, const nae_sig* src, size_t len, int ch, float* profile_dev);
+int nae_denoise_block_f32(nae_ctx* ctx, const nae_denoise_params* params, const float* profile_dev, int profile_ch, const nae_sig* src,
+                          size_t in_len, int ch, size_t n_streams, const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch); the profile is copied into memory the handle owns (on the context's stream: no
+ * wait).  With H = n_fft / 4, after every put floor((put total - (time_smooth + 3) H) / H) H frames have become available in all, never fewer
+ * than zero; nae_denoise_flush releases the rest, so in_len frames come out in all, equal to the block call's however the input is cut.  A put
+ * after the flush: NAE_ERR_STATE. */
+int nae_denoise_create(nae_ctx* ctx, const nae_denoise_params* params, const float* profile_dev, int profile_ch, int channels, nae_denoise** h);
+int nae_denoise_put(nae_denoise* h, const float* interleaved, size_t S);
+int nae_denoise_put_host(nae_denoise* h, const float* interleaved_host, size_t S);
+int nae_denoise_flush(nae_denoise* h);
+size_t nae_denoise_available(nae_denoise* h);
+int nae_denoise_receive(nae_denoise* h, float* dst, size_t max_frames, size_t* got);
+int nae_denoise_receive_host(nae_denoise* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_denoise_destroy(nae_denoise* h);
 
 /* ------------------------------------------------------------------ the 4-node graph of BASELINE.json
  * input -> mix(2) -> pitch -> FFT spectrum, one launch sequence over n_streams independent streams.

@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = [
     "nae_eq_receive_host", "nae_eq_destroy",
     "nae_dyn_design", "nae_dyn_block_f32", "nae_dyn_create", "nae_dyn_put", "nae_dyn_put_host", "nae_dyn_flush", "nae_dyn_available",
     "nae_dyn_receive", "nae_dyn_receive_host", "nae_dyn_destroy",
+    "nae_denoise_design", "nae_denoise_profile_f32", "nae_denoise_block_f32", "nae_denoise_create", "nae_denoise_put", "nae_denoise_put_host",
+    "nae_denoise_flush", "nae_denoise_available", "nae_denoise_receive", "nae_denoise_receive_host", "nae_denoise_destroy",
 ]
 
 
@@ -52,7 +54,7 @@ FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX = 0.25, 4.0   # NAE_FORMANT_SHIFT_MIN / _MA
 FIR_SIZES = (512, 1024, 2048, 4096)                 # frame sizes of the FIR filter: at most n_fft / 2 + 1 taps
 FIR_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}   # `kind` of nae_fir_design
 EQ_KINDS = ("peak", "lowshelf", "highshelf", "lowpass", "highpass", "notch")   # `kind` of nae_eq_design: NAE_EQ_PEAK ... NAE_EQ_NOTCH
-HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn")   # the handles with the full put / receive set of entries
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_denoise")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -96,6 +98,11 @@ class DynParams(C.Structure):
     """nae_dyn_params: the dynamics processor's parameters (include/nae_gpu.h); nae_dyn_design makes them from times and a ratio"""
     _fields_ = [("threshold_db", C.c_double), ("slope", C.c_double), ("knee_db", C.c_double), ("alpha_attack", C.c_double),
                 ("alpha_release", C.c_double), ("makeup_db", C.c_double), ("lookahead", C.c_int), ("link", C.c_int)]
+
+
+class DenoiseParams(C.Structure):
+    """nae_denoise_params: the spectral gate's parameters (include/nae_gpu.h); nae_denoise_design makes them from decibels"""
+    _fields_ = [("n_fft", C.c_int), ("time_smooth", C.c_int), ("freq_smooth", C.c_int), ("thr_scale", C.c_float), ("floor_gain", C.c_float)]
 
 
 class StretchPlan(C.Structure):
@@ -199,6 +206,9 @@ def load_library() -> C.CDLL:
         "nae_eq_create": (i, [vp, vp, i, i, P(vp)]),
         "nae_dyn_design": (i, [i, d, d, d, d, d, d, d, i, P(DynParams)]), "nae_dyn_block_f32": (i, [vp, P(DynParams), P(Sig), sz, i, sz, P(Sig)]),
         "nae_dyn_create": (i, [vp, P(DynParams), i, P(vp)]),
+        "nae_denoise_design": (i, [d, d, i, i, i, P(DenoiseParams)]), "nae_denoise_profile_f32": (i, [vp, i, P(Sig), sz, i, vp]),
+        "nae_denoise_block_f32": (i, [vp, P(DenoiseParams), vp, i, P(Sig), sz, i, sz, P(Sig)]),
+        "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
     }
     # the seven entries every put / receive handle has besides its create (the spectrum handle has four of them: spelled out above)
     for prefix in HANDLE_PREFIXES:
@@ -630,6 +640,25 @@ class Context:
         """the compressor / limiter `params` over every stream; dst receives in_len frames, compensated for the look-ahead"""
         self._ck(self.lib.nae_dyn_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K13
+    @staticmethod
+    def denoise_design(reduction_db: float = 12.0, sensitivity_db: float = 6.0, n_fft: int = 2048, time_smooth: int = 2,
+                       freq_smooth: int = 2) -> "DenoiseParams":
+        """the parameters of the spectral gate from decibels (nae_denoise_design)"""
+        out = DenoiseParams()
+        rc = load_library().nae_denoise_design(reduction_db, sensitivity_db, n_fft, time_smooth, freq_smooth, C.byref(out))
+        if rc:
+            raise NaeError(f"nae_denoise_design({reduction_db}, {sensitivity_db}, {n_fft}, {time_smooth}, {freq_smooth}) failed: {rc}")
+        return out
+
+    def denoise_profile(self, n_fft: int, src: Sig, length: int, ch: int, profile_ptr: int):
+        """the noise powers [ch][n_fft / 2 + 1] of the excerpt's whole frames into device memory at profile_ptr (asynchronous)"""
+        self._ck(self.lib.nae_denoise_profile_f32(self.h, n_fft, C.byref(src), length, ch, profile_ptr))
+
+    def denoise_block(self, params: "DenoiseParams", profile_ptr: int, profile_ch: int, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the spectral gate `params` against the device profile [profile_ch][n_fft / 2 + 1] over every stream; dst receives in_len frames"""
+        self._ck(self.lib.nae_denoise_block_f32(self.h, C.byref(params), profile_ptr, profile_ch, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     # -- graph
     def graph4(self, g: Graph4):
         self._ck(self.lib.nae_graph4_run(self.h, C.byref(g)))
@@ -759,3 +788,14 @@ class Dyn(_Handle):
     def __init__(self, ctx: Context, params: DynParams, channels: int):
         super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_dyn_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+
+class Denoise(_Handle):
+    """The spectral gate's streaming handle (nae_denoise_create): put interleaved f32, flush, receive.  The device profile
+    [profile_ch][n_fft / 2 + 1] is copied at creation.  Before the flush the hop blocks with time_smooth + 3 blocks behind them are available."""
+
+    _prefix = "nae_denoise"
+
+    def __init__(self, ctx: Context, params: DenoiseParams, profile_ptr: int, profile_ch: int, channels: int):
+        super().__init__(ctx, channels)
+        ctx._ck(ctx.lib.nae_denoise_create(ctx.h, C.byref(params), profile_ptr, profile_ch, channels, C.byref(self.h)))

@@ -267,6 +267,7 @@ int nae_debug_set(nae_ctx* ctx, const char* key, long long value)
     auto one_of = [&](std::initializer_list<long long> ok) { for (long long v : ok) if (v == value) return true; return false; };
     if (k == "pv_tile" && count) ctx->pv_tile = (int)value;
     else if (k == "fir_tile" && count) ctx->fir_tile = (int)value;
+    else if (k == "dn_tile" && count) ctx->dn_tile = (int)value;
     else if (k == "conv_tile" && count) ctx->conv_tile = (int)value;
     else if (k == "conv_ring" && count) ctx->conv_ring = (int)value;
     else if (k == "pv_fps" && one_of({0, 1, 2, 4})) ctx->pv_fps = (int)value;

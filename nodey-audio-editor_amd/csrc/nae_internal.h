@@ -42,6 +42,7 @@ struct nae_ctx {
     float* d_conv_spec = nullptr; size_t conv_spec_floats = 0; int conv_spec_n_fft = 0, conv_spec_taps_ch = 0;
     std::vector<float> h_conv_taps;
     void* ws_conv = nullptr; size_t ws_conv_bytes = 0;
+    int dn_tile = 0;             // hop blocks per tile of the spectral gate; 0 = choose per launch (nae_pick_denoise_tile)
     // nae_eq_block_f32 keeps the last call's coefficients and their constant block (kernels_eq.hip)
     double* d_eq_block = nullptr;
     std::vector<double> h_eq_coef;
@@ -283,6 +284,14 @@ int nae_dyn_check(nae_ctx* ctx, const nae_dyn_params* p, int ch);
 size_t nae_dyn_detectors(const nae_dyn_params* p, int ch, size_t n_streams);
 int nae_launch_dyn(nae_ctx* ctx, const nae_dyn_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
                    size_t c_origin, size_t c_stop, double* d_state);
+
+// kernels_denoise.hip: the spectral gate ("K13 spectral gate").  nae_denoise_check: the parameter rules of the block call and the
+// handle.  nae_launch_denoise runs hop blocks [b_origin, b_stop) of absolutely indexed signals of in_len samples: it reads from
+// (b_origin - time_smooth - 3) H on and, in front of a block, time_smooth + 3 blocks ahead (zero from in_len on), and keeps nothing between launches.
+int nae_denoise_check(nae_ctx* ctx, const nae_denoise_params* p, const float* profile_dev, int profile_ch, int ch);
+int nae_launch_denoise(nae_ctx* ctx, const nae_denoise_params* p, const float* d_profile, int profile_ch, const nae_sig* src, size_t in_len, int ch,
+                       size_t n_streams, const nae_sig* dst, size_t b_origin, size_t b_stop);
+int nae_pick_denoise_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc);
 
 // kernels_nodes.hip
 int nae_launch_copy_sig(nae_ctx* ctx, const nae_sig* src, const nae_sig* dst, size_t S, int ch, size_t n_streams,

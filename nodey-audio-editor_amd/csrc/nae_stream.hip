@@ -67,6 +67,15 @@ struct nae_dyn : BlockHandle {
     int process() override;
 };
 
+// the spectral gate's handle ("K13 spectral gate"): whole hop blocks of n_fft / 4 samples are computed once the time_smooth + 3
+// blocks behind them are there; the input stays from time_smooth + 3 blocks in front of the next block on, and nothing else is kept
+struct nae_denoise : BlockHandle {
+    nae_denoise_params params;
+    int profile_ch = 1;
+    float* d_profile = nullptr;    // [profile_ch][n_fft / 2 + 1], the handle's own copy
+    int process() override;
+};
+
 namespace {
 
 inline long long frame_start_host(const nae_stretch_plan& pl, int n_fft, long long f)
@@ -287,6 +296,14 @@ int nae_dyn::process()
     });
 }
 
+int nae_denoise::process()
+{
+    const size_t H = (size_t)params.n_fft / 4, reach = (size_t)params.time_smooth + 3;
+    return run_units(H, reach * H, reach, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
+        return nae_launch_denoise(ctx, &params, d_profile, profile_ch, &src, in.total, ch, 1, &dst, from, to);
+    });
+}
+
 extern "C" {
 
 static int stretch_create(nae_ctx* ctx, const nae_pv_opts& o, int sample_rate, int channels, float rate, float pitch, nae_stretch** h)
@@ -492,5 +509,32 @@ size_t nae_dyn_available(nae_dyn* h) { return handle_available(h); }
 int nae_dyn_receive(nae_dyn* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_dyn_receive_host(nae_dyn* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_dyn_destroy(nae_dyn* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ spectral gate
+int nae_denoise_create(nae_ctx* ctx, const nae_denoise_params* params, const float* profile_dev, int profile_ch, int channels, nae_denoise** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_denoise_check(ctx, params, profile_dev, profile_ch, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_denoise* s = handle_new<nae_denoise>(ctx, channels);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    s->profile_ch = profile_ch;
+    const size_t floats = (size_t)profile_ch * ((size_t)params->n_fft / 2 + 1);
+    rc = s->dev_alloc(&s->d_profile, floats, "hipMalloc(denoise profile)");
+    if (!rc) rc = nae_check(ctx, hipMemcpyAsync(s->d_profile, profile_dev, floats * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream),
+                            "hipMemcpyAsync(denoise profile)");
+    return handle_created(s, rc, h);
+}
+
+int nae_denoise_put(nae_denoise* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_denoise_put_host(nae_denoise* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+int nae_denoise_flush(nae_denoise* h) { return handle_flush(h); }
+size_t nae_denoise_available(nae_denoise* h) { return handle_available(h); }
+int nae_denoise_receive(nae_denoise* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_denoise_receive_host(nae_denoise* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_denoise_destroy(nae_denoise* h) { return handle_destroy(h); }
 
 } // extern "C"

@@ -153,4 +153,6 @@ namespace infra
 	void register_equalizer_processors();
 	// the dynamics node (audio_dynamics): called after the four above, each of which stays the list it was
 	void register_dynamics_processors();
+	// the restoration tools (audio_denoise): called after the five above, each of which stays the list it was
+	void register_restoration_processors();
 }

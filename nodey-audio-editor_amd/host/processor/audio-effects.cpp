@@ -1,10 +1,12 @@
-// processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq) and
-// Audio_dynamics (nae_dyn), and the one loop that feeds such a handle and delivers its frames (run_on_handle).
+// processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
+// Audio_dynamics (nae_dyn) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle).
 #include "audio-filter.hpp"
 #include "audio-reverb.hpp"
 #include "audio-eq.hpp"
 #include "audio-dynamics.hpp"
+#include "audio-denoise.hpp"
 #include "node-util.hpp"
+#include "nae_dsp_spec.h"
 
 #include <algorithm>
 #include <cmath>
@@ -20,6 +22,9 @@ namespace processor
 	// releases the rest, and what is left behind the last frame owed is dropped.  `create` makes the handle from the first frame (its sample
 	// rate) and the channel count, or throws.  The first `to_discard` frames of the handle's output are dropped (a linear-phase filter's group
 	// delay); `noun` is the node's word for itself in the "Channel count changed" error; ops.name is the prefix of the handle's entries.
+	// run_on_handle_held is the loop itself: hold(first frame) says how many samples must have arrived before the handle is made (the noise
+	// reduction learns from a stretch of its input).  Until then, or until the stream ends, the frames wait; create(ctx, first frame, ch,
+	// samples, total) then sees everything held, on the device as interleaved f32, and all of it is the handle's first put.
 	template <class Handle>
 	struct Handle_ops
 	{
@@ -31,10 +36,10 @@ namespace processor
 		int (*destroy)(Handle*);
 	};
 
-	template <class Handle, class Create>
-	static void run_on_handle(
+	template <class Handle, class Hold, class Create>
+	static void run_on_handle_held(
 		Audio_stream& input_stream, const std::set<std::shared_ptr<Audio_stream>>& output_stream, const std::atomic<bool>& stop_token,
-		const std::type_identity_t<Handle_ops<Handle>>& ops, const char* noun, size_t to_discard, const Create& create
+		const std::type_identity_t<Handle_ops<Handle>>& ops, const char* noun, size_t to_discard, const Hold& hold, const Create& create
 	)
 	{
 		nae_ctx* ctx = gpu::context();
@@ -48,6 +53,8 @@ namespace processor
 		std::vector<float> ready;     // processed samples behind the discarded ones, interleaved, not yet cut into frames
 		size_t ready_pos = 0;         // frames of `ready` already delivered
 		std::shared_ptr<const Audio_frame> held;  // popped, but with another channel count than the batch in front of it
+		std::vector<std::shared_ptr<const Audio_frame>> pending;   // frames not yet put: they wait while the handle waits for `need` samples
+		size_t pending_samples = 0, need = 0;
 
 		// a failed GPU call is reported by its entry's name (ops.name + suffix), put together only when it failed
 		const auto check = [&](int rc, const char* suffix) { if (rc != NAE_OK) gpu::check(rc, (std::string(ops.name) + suffix).c_str()); };
@@ -92,13 +99,43 @@ namespace processor
 		{
 			bool ended = false;
 			const std::vector<std::shared_ptr<const Audio_frame>> batch = collect_batch(input_stream, held, &ended);
-			if (batch.empty())
+			if (batch.empty() && !ended)
 			{
-				if (!ended)
+				nae_fiber::this_fiber::yield();
+				continue;
+			}
+			if (!batch.empty())
+			{
+				const Frame_data* frame = batch.front()->data();
+				if (ch == 0)
 				{
-					nae_fiber::this_fiber::yield();
-					continue;
+					ch = frame->ch_layout.nb_channels;
+					if (ch != 1 && ch != 2) throw infra::Processor::Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
+					need = hold(frame);
 				}
+				else if (frame->ch_layout.nb_channels != ch)
+					throw infra::Processor::Runtime_error("Channel count changed", infra::fmt("The %s runs one stream of a fixed channel count.", noun),
+										infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, ch));
+				for (const auto& f : batch)
+				{
+					shapes.push_back({f->data()->nb_samples, f->data()->sample_rate, f->data()->pts, f->data()->time_base});
+					pending.push_back(f);
+					pending_samples += (size_t)f->data()->nb_samples;
+				}
+			}
+			const bool at_end = batch.empty() && ended;
+			if (!pending.empty() && (h != nullptr || pending_samples >= need || at_end))
+			{
+				size_t total = 0;
+				float* samples = upload_as_f32(pending, h_raw, d_raw, d_f32, &total);
+				if (h == nullptr) h = create(ctx, pending.front()->data(), ch, samples, total);
+				check(ops.put(h, samples, total), "_put");
+				pending.clear();
+				pending_samples = 0;
+				deliver();
+			}
+			if (at_end)
+			{
 				if (h != nullptr)
 				{
 					// what the handle still holds comes out with the flush: every frame still owed is complete
@@ -107,23 +144,21 @@ namespace processor
 				}
 				break;
 			}
-			const Frame_data* frame = batch.front()->data();
-			if (h == nullptr)
-			{
-				ch = frame->ch_layout.nb_channels;
-				if (ch != 1 && ch != 2) throw infra::Processor::Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
-				h = create(ctx, frame, ch);
-			}
-			else if (frame->ch_layout.nb_channels != ch)
-				throw infra::Processor::Runtime_error("Channel count changed", infra::fmt("The %s runs one stream of a fixed channel count.", noun),
-									infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, ch));
-			for (const auto& f : batch) shapes.push_back({f->data()->nb_samples, f->data()->sample_rate, f->data()->pts, f->data()->time_base});
-			size_t total = 0;
-			float* samples = upload_as_f32(batch, h_raw, d_raw, d_f32, &total);
-			check(ops.put(h, samples, total), "_put");
-			deliver();
 		}
 		for (auto& stream : output_stream) stream->set_eof();
+	}
+
+	// a handle made from the first frame alone: nothing is held
+	template <class Handle, class Create>
+	static void run_on_handle(
+		Audio_stream& input_stream, const std::set<std::shared_ptr<Audio_stream>>& output_stream, const std::atomic<bool>& stop_token,
+		const std::type_identity_t<Handle_ops<Handle>>& ops, const char* noun, size_t to_discard, const Create& create
+	)
+	{
+		run_on_handle_held<Handle>(
+			input_stream, output_stream, stop_token, ops, noun, to_discard, [](const Frame_data*) { return (size_t)0; },
+			[&](nae_ctx* ctx, const Frame_data* frame, int ch, const float*, size_t) { return create(ctx, frame, ch); }
+		);
 	}
 
 	// ------------------------------------------------------------------------------------------ Audio_filter
@@ -497,6 +532,100 @@ namespace processor
 				nae_dyn* dyn = nullptr;
 				gpu::check(nae_dyn_create(ctx, &params, ch, &dyn), "nae_dyn_create");
 				return dyn;
+			}
+		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_denoise
+	infra::Processor::Info Audio_denoise::get_processor_info()
+	{
+		return {"audio_denoise", "Audio Noise Reduction", false, [] { return std::unique_ptr<infra::Processor>(new Audio_denoise); },
+				"Noise reduction: a spectral gate against a noise profile learned from a stretch of the input, smoothed over time and frequency (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_denoise::get_pin_attributes() const { return io_pins(); }
+
+	Json::Value Audio_denoise::serialize() const
+	{
+		Json::Value value;
+		if (reduction_db != default_reduction_db) value["reduction_db"] = reduction_db;
+		if (sensitivity_db != default_sensitivity_db) value["sensitivity_db"] = sensitivity_db;
+		if (fft_size != default_fft_size) value["fft_size"] = fft_size;
+		if (time_smooth != default_time_smooth) value["time_smooth"] = time_smooth;
+		if (freq_smooth != default_freq_smooth) value["freq_smooth"] = freq_smooth;
+		if (profile_start_ms != default_profile_start_ms) value["profile_start_ms"] = profile_start_ms;
+		if (profile_ms != default_profile_ms) value["profile_ms"] = profile_ms;
+		return value;
+	}
+
+	void Audio_denoise::deserialize(const Json::Value& value)
+	{
+		const auto wrong = [](const char* field) { return wrong_field("Audio_denoise", field); };
+		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
+		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_denoise", key, lo, hi, fallback); };
+		const auto integer = [&](const char* key, int lo, int hi, int fallback) {
+			if (!value.isMember(key)) return fallback;
+			const Json::Value& v = value[key];
+			// compared as a double with the range first: a number outside int's range is never converted
+			if (!v.isDouble() || !(v.asDouble() >= (double)lo && v.asDouble() <= (double)hi) || v.asDouble() != (double)v.asInt()) throw wrong(key);
+			return v.asInt();
+		};
+		const double r = real("reduction_db", 0.0, NAE_DENOISE_MAX_REDUCTION_DB, default_reduction_db);
+		const double s = real("sensitivity_db", NAE_DENOISE_MIN_SENSITIVITY_DB, NAE_DENOISE_MAX_SENSITIVITY_DB, default_sensitivity_db);
+		const int n = integer("fft_size", 512, 4096, default_fft_size);
+		if (n != 512 && n != 1024 && n != 2048 && n != 4096) throw wrong("fft_size");
+		const int tn = integer("time_smooth", 0, NAE_DENOISE_MAX_TIME, default_time_smooth);
+		const int fn = integer("freq_smooth", 0, NAE_DENOISE_MAX_FREQ, default_freq_smooth);
+		const double ps = real("profile_start_ms", 0.0, 60000.0, default_profile_start_ms);
+		const double pm = real("profile_ms", 20.0, 10000.0, default_profile_ms);
+		reduction_db = r; sensitivity_db = s; fft_size = n; time_smooth = tn; freq_smooth = fn; profile_start_ms = ps; profile_ms = pm;
+	}
+
+	void Audio_denoise::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
+		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
+		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
+		if (!input_item.has_value())
+			throw Runtime_error("Audio Noise Reduction has no input", "Audio Noise Reduction requires an audio stream input to function properly.", "Input item 'input' not found");
+		Audio_stream& input_stream = input_item.value().get();
+		gpu::Device_buffer d_profile;   // the learned profile: the handle copies it on the stream, so it stays until the node ends
+		// the stretch the node learns from, in samples at the stream's rate
+		const auto stretch = [&](const Frame_data* frame, size_t* start) {
+			*start = (size_t)std::llround(profile_start_ms / 1000.0 * frame->sample_rate);
+			return (size_t)std::llround(profile_ms / 1000.0 * frame->sample_rate);
+		};
+		run_on_handle_held<nae_denoise>(
+			input_stream, output_stream, stop_token,
+			{"nae_denoise", nae_denoise_put, nae_denoise_flush, nae_denoise_available, nae_denoise_receive, nae_denoise_destroy}, "node", 0,
+			[&](const Frame_data* frame)
+			{
+				size_t start = 0;
+				const size_t len = stretch(frame, &start);
+				return start + len;
+			},
+			[&](nae_ctx* ctx, const Frame_data* frame, int ch, const float* samples, size_t total)
+			{
+				size_t start = 0;
+				const size_t len = stretch(frame, &start);
+				const size_t have = total > start ? std::min(len, total - start) : 0;
+				if (have < (size_t)fft_size)
+					throw Runtime_error("Noise profile too short", "The stream ended before the stretch the noise is learned from held one analysis frame.",
+										infra::fmt("%d samples of the stretch at %g ms, fft_size %d", (int)have, profile_start_ms, fft_size));
+				nae_denoise_params params;
+				if (nae_denoise_design(reduction_db, sensitivity_db, fft_size, time_smooth, freq_smooth, &params) != NAE_OK)
+					throw Runtime_error("Invalid noise reduction parameters", "A parameter of the noise reduction node lies outside its range.",
+										infra::fmt("reduction %g dB, sensitivity %g dB, fft_size %d", reduction_db, sensitivity_db, fft_size));
+				float* profile = static_cast<float*>(d_profile.reserve((size_t)ch * (fft_size / 2 + 1) * sizeof(float)));
+				const nae_sig excerpt{const_cast<float*>(samples) + start * ch, 0, 1, (size_t)ch};
+				gpu::check(nae_denoise_profile_f32(ctx, fft_size, &excerpt, have, ch, profile), "nae_denoise_profile_f32");
+				nae_denoise* dn = nullptr;
+				gpu::check(nae_denoise_create(ctx, &params, profile, ch, ch, &dn), "nae_denoise_create");
+				return dn;
 			}
 		);
 	}

@@ -17,6 +17,7 @@
 #include "audio-reverb.hpp"
 #include "audio-eq.hpp"
 #include "audio-dynamics.hpp"
+#include "audio-denoise.hpp"
 #include "audio-mix.hpp"
 #include "audio-velocity.hpp"
 #include "audio-vol.hpp"
@@ -115,6 +116,20 @@ namespace processor
 		release_ms = std::clamp(release_ms, 1.0, 5000.0);
 		lookahead_ms = std::clamp(lookahead_ms, 0.0, 20.0);
 		makeup_db = std::clamp(makeup_db, -24.0, 24.0);
+		return false;
+	}
+
+	void Audio_denoise::draw_title() {}
+	bool Audio_denoise::draw_content(bool)
+	{
+		// what the widgets would keep: every value inside its range, a frame size the library has (else the default)
+		reduction_db = std::clamp(reduction_db, 0.0, 48.0);
+		sensitivity_db = std::clamp(sensitivity_db, -6.0, 24.0);
+		if (fft_size != 512 && fft_size != 1024 && fft_size != 2048 && fft_size != 4096) fft_size = default_fft_size;
+		time_smooth = std::clamp(time_smooth, 0, 8);
+		freq_smooth = std::clamp(freq_smooth, 0, 4);
+		profile_start_ms = std::clamp(profile_start_ms, 0.0, 60000.0);
+		profile_ms = std::clamp(profile_ms, 20.0, 10000.0);
 		return false;
 	}
 }

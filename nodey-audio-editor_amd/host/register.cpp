@@ -7,6 +7,7 @@
 #include "processor/audio-reverb.hpp"
 #include "processor/audio-eq.hpp"
 #include "processor/audio-dynamics.hpp"
+#include "processor/audio-denoise.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -43,4 +44,7 @@ namespace infra
 
 	// the compressor / limiter on the dynamics processor; a call of its own once more, so the four lists above stay what they were
 	void register_dynamics_processors() { register_each<processor::Audio_dynamics>(); }
+
+	// the restoration tools: noise reduction on the spectral gate; a call of its own, so the five lists above stay what they were
+	void register_restoration_processors() { register_each<processor::Audio_denoise>(); }
 }
