@@ -158,13 +158,79 @@ __global__ __launch_bounds__(kPipeThreads, kRich ? 4 : 8) void pv_pipe_kernel(Si
         /*pipe:r1-end*/
     } else if (role <= 2) {
         // ------------------------------------------------------------------------------------------ R2a / R2b: phases
+        // (the role's two barriers of step t, written once for both of its loops)
+        auto barrier_a = [&](int t) { (void)t; pipe_barrier();   /*A*/ };   // Z of the frame analysed in step t is complete
+        auto barrier_b = [&](int t) { (void)t; pipe_barrier();   /*B*/ };   // R1 may overwrite its scratch
+        if (kG == 1) {
+            // One frame per step (the headline shape).  The tile's frames f_first + ia, ia = 0 .. n - 1, pass in steps t = ia + 1; step 0 and the steps from
+            // n + 1 on only keep the barriers.  Frame ia = 0 is the one special frame — frame 0 of the stream, whose increment is its analysis phase, or
+            // (f_first = b0 - 1) the frame that only primes the next one's deviation — so it is peeled off, and the loop over ia = 1 .. n - 1 has no test on
+            // a frame number left but the carry frame's: qs, qp and the rotated bins are produced in the registers they live in.
+            // qp is not the previous frame's analysis phase but that phase moved on by the hop's expected advance (pv_advance.h, PhaseLane::advance_base).
+            // The role's code exists once per half, the half a constant in each: half 1 carries nothing for bins 256 and 512, half 0 no tests for them.
+            auto phase_role = [&](auto half) {
+                PhaseLane P;
+                P.init(tb, half.value, lane);
+                P.init_advance(p);
+                uint32_t qs[5], qp[5];                        // [4]: bin 512 (h = 0)
+                P.load_base(qs, base_phase, p, it);
+#pragma unroll
+                for (int q = 0; q < 5; q++) qp[q] = 0;
+                const bool first_live = __builtin_amdgcn_readfirstlane((int)(b0 - f_first)) == 0;     // then f_first = b0 = 0: frame 0 of the stream
+                const int n_s = __builtin_amdgcn_readfirstlane(n);
+                auto idle = [&](int t) {
+                    barrier_a(t);
+                    pipe_prio(prio_slot, role, now);
+                    barrier_b(t);
+                    now = __builtin_amdgcn_s_memtime();
+                };
+                auto step = [&](int ia, auto first) {
+                    barrier_a(ia + 1);
+                    pipe_prio(prio_slot, role, now);
+                    cf va[5], A[2], B[2], z256{0.0f, 0.0f};
+                    P.read_z(S1, A, B, z256);
+                    P.split(A, B, z256, va);
+                    barrier_b(ia + 1);
+                    now = __builtin_amdgcn_s_memtime();
+                    uint32_t qa[5] = {0, 0, 0, 0, 0};
+                    P.phases(va, qa);
+                    const long long fa = f_first + ia;
+                    if (first.value) {
+                        if (first_live) {
+#pragma unroll
+                            for (int q = 0; q < 5; q++) qs[q] += qa[q];
+                        }
+                    } else {
+                        const unsigned d = (unsigned)(frame_start(p, fa) - frame_start(p, fa - 1));
+                        const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
+                        uint32_t inc[5];
+                        P.inc_from_base(qa, qp, R, inc);
+#pragma unroll
+                        for (int q = 0; q < 5; q++) qs[q] += inc[q];
+                    }
+                    // what the next frame measures its deviation against: this frame's phases moved on by the hop to it
+                    P.advance_base(p, qa, (unsigned)(frame_start(p, fa + 1) - frame_start(p, fa)), qp);
+                    if (fa == p.carry_frame) P.carry_store_here(p, sc, qs);     // (64-bit equality is a scalar compare)
+                    if (!first.value || first_live) P.synth_items(Y, va, qs, qa);
+                };
+                idle(0);
+                step(0, std::true_type{});                        // (n >= 1: pipe_item)
+#pragma unroll 1
+                for (int ia = 1; ia < n_s; ia++) step(ia, std::false_type{});
+#pragma unroll 1
+                for (int t = n_s + 1; t < T; t++) idle(t);
+            };
+            if (role == 1) phase_role(std::integral_constant<int, 0>{});
+            else phase_role(std::integral_constant<int, 1>{});
+            return;
+        }
         PhaseLane P;
         P.init(tb, role - 1, lane);
         uint32_t qs[5], qp[5];                                // [4]: bin 512 (h = 0)
         P.load_base(qs, base_phase, p, it);
 #pragma unroll
         for (int q = 0; q < 5; q++) qp[q] = 0;
-        cf hx[5];                                             // kG > 1: the frame analysed in the previous step ([4]: bin 512)
+        cf hx[5];                                             // the frame analysed in the previous step ([4]: bin 512)
         uint32_t hqa[5] = {0, 0, 0, 0, 0};
 #pragma unroll
         for (int q = 0; q < 5; q++) hx[q] = cf{0.0f, 0.0f};
@@ -172,19 +238,17 @@ __global__ __launch_bounds__(kPipeThreads, kRich ? 4 : 8) void pv_pipe_kernel(Si
         for (int t = 0; t < T; t++) {
             const int ia = kG * (t - 1) + j;                  // index (from f_first) of the frame analysed in this step
             const bool act_a = t >= 1 && ia < n;
-            const long long fa = f_first + ia;
-            const int ib = ia - kG;                           // kG > 1: the frame whose phase is advanced in this step
-            const bool act_b = kG > 1 && t >= 2 && ib < n;
+            const int ib = ia - kG;                           // the frame whose phase is advanced in this step
+            const bool act_b = t >= 2 && ib < n;
             const long long fb = f_first + ib;
-            pipe_barrier();                                   /*A*/  // Z of frame fa is complete
-            if (kG == 1) pipe_prio(prio_slot, role, now);
+            barrier_a(t);
             cf va[5];
             if (act_a) {
                 cf A[2], B[2], z256{0.0f, 0.0f};
                 P.read_z(S1, A, B, z256);
                 P.split(A, B, z256, va);
             }
-            if (kG > 1) {
+            {
                 // increment of the held frame fb: its predecessor's analysis phases were left in LDS one step ago (slot j-1), or
                 // two steps ago by the last slot (j = 0)
                 uint32_t inc[5] = {0, 0, 0, 0, 0};
@@ -195,46 +259,22 @@ __global__ __launch_bounds__(kPipeThreads, kRich ? 4 : 8) void pv_pipe_kernel(Si
                 }
                 P.write5(x_inc(slot), inc);
             }
-            pipe_barrier();                                   /*B*/  // R1 may overwrite its scratch
-            if (kG == 1) now = __builtin_amdgcn_s_memtime();
+            barrier_b(t);
             uint32_t qa[5] = {0, 0, 0, 0, 0};
             if (act_a) P.phases(va, qa);
-            if (kG == 1) {
-                if (act_a) {
-                    // (written out rather than through PhaseLane::inc_of_frame: the same instructions, but this form keeps the headline kernel's schedule — 0.5 % of it)
-                    if (fa >= b0) {
-                        if (fa == 0) {
+            if (act_a) P.write5(x_qa(slot, t & 1), qa);
+            if (act_b) {
+                // running phase: the increments of the unit's slots up to this one; all of them move the base on
+                uint32_t iv[kG][5], mine[5];
 #pragma unroll
-                            for (int q = 0; q < 5; q++) qs[q] += qa[q];
-                        } else {
-                            const unsigned d = (unsigned)(frame_start(p, fa) - frame_start(p, fa - 1));
-                            const unsigned R = (d == (unsigned)p.d0) ? p.r_q24_0 : p.r_q24_1;
-                            uint32_t inc[5];
-                            P.inc_items(qa, qp, d, R, inc);
+                for (int i2 = 0; i2 < kG; i2++) P.read5(x_inc(slot - j + i2), iv[i2]);
+                r2_running_phase<kG>(qs, mine, iv, j);
+                if (fb == p.carry_frame) P.carry_store(p, sc, mine);
+                if (fb >= b0) P.synth_items(Y, hx, mine, hqa);
+            }
+            if (act_a) {
 #pragma unroll
-                            for (int q = 0; q < 5; q++) qs[q] += inc[q];
-                        }
-                    }
-#pragma unroll
-                    for (int q = 0; q < 5; q++) qp[q] = qa[q];
-                    if (fa == p.carry_frame) P.carry_store(p, sc, qs);
-                    if (fa >= b0) P.synth_items(Y, va, qs, qa);
-                }
-            } else {
-                if (act_a) P.write5(x_qa(slot, t & 1), qa);
-                if (act_b) {
-                    // running phase: the increments of the unit's slots up to this one; all of them move the base on
-                    uint32_t iv[kG][5], mine[5];
-#pragma unroll
-                    for (int i2 = 0; i2 < kG; i2++) P.read5(x_inc(slot - j + i2), iv[i2]);
-                    r2_running_phase<kG>(qs, mine, iv, j);
-                    if (fb == p.carry_frame) P.carry_store(p, sc, mine);
-                    if (fb >= b0) P.synth_items(Y, hx, mine, hqa);
-                }
-                if (act_a) {
-#pragma unroll
-                    for (int q = 0; q < 5; q++) { hx[q] = va[q]; hqa[q] = qa[q]; }
-                }
+                for (int q = 0; q < 5; q++) { hx[q] = va[q]; hqa[q] = qa[q]; }
             }
         }
     } else {
@@ -250,11 +290,13 @@ __global__ __launch_bounds__(kPipeThreads, kRich ? 4 : 8) void pv_pipe_kernel(Si
         const bool dense = dense_shape && ((reinterpret_cast<uintptr_t>(optr - c) & 15) == 0);   // (optr - c: channel 0 of the stream)
         int pend_be = -1;                                     // block waiting in the exchange area (wave-uniform; the same in both channel waves)
         auto xchg = [&]() { return reinterpret_cast<cf*>(xbase + (size_t)(slot & ~1) * kPipeXchgPerSlot); };
+        const TileRel rel = pipe_tile_rel(p, it);             // kG = 1: the loop's tests on frame and block numbers, as indices from f_first
+        const int n_s = __builtin_amdgcn_readfirstlane(n);
 #pragma unroll 1
         for (int t = 0; t < T; t++) {
             const int iz = kG * (t - (kDepth - (kG == 1 ? 0 : 1))) + j;      // kG = 1: t - 2;  kG > 1: t - 3
             const long long fz = f_first + iz;
-            const bool active = iz >= 0 && iz < n && fz >= b0;
+            const bool active = kG == 1 ? (iz >= rel.b0 && iz < n_s) : (iz >= 0 && iz < n && fz >= b0);     // (rel.b0 >= 0)
             pipe_barrier();                                   /*A*/  // the FFT input of frame fz is complete
             if (kG == 1) pipe_prio(prio_slot, role, now);
             if (kG == 1 && pend_be >= 0) {
@@ -317,15 +359,18 @@ __global__ __launch_bounds__(kPipeThreads, kRich ? 4 : 8) void pv_pipe_kernel(Si
                 if (kG == 1) {
                     float o[4];
                     r3_ola_shift(r0, r1, r2, y, o);
-                    const long long be = fz - 3;
-                    if (dense && be >= b0 && be < b_end && (be + 1) * NAE_HOP <= p.mid_len) {
-                        const int lx = pipe_lane<!kRich>(lane);
-                        cf* XB = xchg();
-                        lds_st(XB + (2 * c + 0) * 64 + lx, cf{o[0], o[1]});
-                        lds_st(XB + (2 * c + 1) * 64 + lx, cf{o[2], o[3]});
-                        pend_be = (int)be;
-                    } else {
-                        r3_store_block(p, it, bo, be, o, pipe_lane<!kRich>(lane));   // wave-uniform: the block's base pointer stays scalar
+                    const int ie = iz - 3;                     // the block this frame completes, from f_first
+                    if (ie >= rel.b0 && ie < rel.b_end && ie < rel.part) {
+                        if (dense && ie < rel.full) {
+                            const int lx = pipe_lane<!kRich>(lane);
+                            cf* XB = xchg();
+                            lds_st(XB + (2 * c + 0) * 64 + lx, cf{o[0], o[1]});
+                            lds_st(XB + (2 * c + 1) * 64 + lx, cf{o[2], o[3]});
+                            pend_be = (int)(fz - 3);
+                        } else {
+                            // wave-uniform: the block's base pointer stays scalar
+                            r3_store_block_at(p, bo, fz - 3, ie < rel.full, o, pipe_lane<!kRich>(lane));
+                        }
                     }
                 } else {
                     float* po = x_ola(slot, t % kGens) + 4 * lb;

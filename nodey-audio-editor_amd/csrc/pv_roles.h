@@ -5,6 +5,7 @@
 // test_k7_pipeline_modes_agree_bit_for_bit).
 #pragma once
 #include "stft_common.h"
+#include "pv_advance.h"
 
 namespace nae {
 
@@ -26,14 +27,19 @@ __device__ __forceinline__ int pipe_lane(int lane)
     return lane;
 }
 
-// exact phase increment of one hop for bin k: adv + round(dw * R / 2^24)
+// the lane index formed where it is asked for, from nothing that waits in a register: for paths a launch takes once or never (the phase roles' carry store,
+// their general advance formula), whose bin numbers would otherwise pin a VGPR of the 64 through the whole frame loop
+__device__ __forceinline__ int pipe_lane_here()
+{
+    unsigned all = ~0u;
+    asm volatile("" : "+s"(all));
+    return (int)__builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
+}
+
+// exact phase increment of one hop for bin k: adv + round(dw * R / 2^24), by the general formula (pv_advance.h)
 __device__ __forceinline__ uint32_t pipe_inc(uint32_t qa, uint32_t qp, unsigned k, unsigned d, unsigned R)
 {
-    const uint32_t e = ((k * d) & (NAE_FFT_N - 1)) << 22;
-    const int32_t dw = (int32_t)(qa - qp - e);
-    const uint32_t adv = ((k * NAE_HOP) & (NAE_FFT_N - 1)) << 22;
-    const long long scaled = ((long long)dw * (long long)(int32_t)R + (1ll << (NAE_R_FRAC_BITS - 1))) >> NAE_R_FRAC_BITS;
-    return adv + (uint32_t)scaled;
+    return pv_inc(qa, qp, pv_expected_advance(k, d), k, R);
 }
 
 // synthesis bin X e^{i (qs - qa)} (tolerance path: v_sin / v_cos take turns)
@@ -163,6 +169,7 @@ struct PhaseLane {
     int h, k0, km0;            // half; items 0 / 2: k0, k0 + 64; items 1 / 3: km0 = 512 - k0 (256 in lane 0 of h = 0), 448 - k0
     bool dc;                   // the lane of bins 0, 256 and 512
     cf tk[2], tm[2], tms;      // split twiddles of the items' bins; tms: of the pair's mirror (differs from tm[0] in lane 0 of h = 0: bin 512)
+    uint32_t ea[2][2];         // one frame per step: expected advance of items 0 and 1 over the plan's hops d0 ([0]) and d0 + 1 ([1]); init_advance
 
     __device__ __forceinline__ void init(const Tables& tb, int half, int lane)
     {
@@ -244,6 +251,51 @@ struct PhaseLane {
         inc[3] = pipe_inc(qa[3], qv[3], (unsigned)(448 - k0), d, R);
         inc[4] = (h == 0) ? pipe_inc(qa[4], qv[4], 512u, d, R) : 0u;
     }
+    // One frame per step, the form without a multiply per bin and frame (pv_advance.h).  The plan's hops are d0 and d0 + 1 and a lane's bins never change,
+    // so the expected advances of items 0 and 1 over either hop are four constants; item 2 (bin k0 + 64) is item 0's plus d << 28, item 3 (bin 448 - k0)
+    // is (448 d) << 22 minus item 0's, bin 512's is d << 31: scalars.
+    __device__ __forceinline__ unsigned item_bin(int q, int k) const { return (unsigned)(q == 0 ? k : q == 1 ? (dc ? 256 : 512 - k) : q == 2 ? k + 64 : 448 - k); }
+    __device__ __forceinline__ void init_advance(const PvParams& p)
+    {
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            ea[i][0] = pv_advance_const(item_bin(0, k0), (unsigned)p.d0 + i);
+            ea[i][1] = pv_advance_const(item_bin(1, k0), (unsigned)p.d0 + i);
+        }
+    }
+    // what a frame with analysis phases qa leaves for its successor, d samples on (wave-uniform): base = qa + e(d); the successor's deviation is qa' - base
+    __device__ __forceinline__ void advance_base(const PvParams& p, const uint32_t (&qa)[5], unsigned d, uint32_t (&base)[5]) const
+    {
+        // (the hop goes through a scalar register the optimiser cannot see through: what it could form of a known hop and a lane's constants — e0 + (d0 << 28), ... —
+        // it would keep in a VGPR per hop through the whole frame loop, and the phase roles have none to spare)
+        auto put = [&](uint32_t e0, uint32_t e1) {
+            unsigned ds = d;
+            asm volatile("" : "+s"(ds));
+            base[0] = qa[0] + e0;
+            base[1] = qa[1] + e1;
+            base[2] = qa[2] + pv_advance_plus64(e0, ds);
+            base[3] = qa[3] + pv_advance_mirror448(e0, ds);
+        };
+        if (d == (unsigned)p.d0) {
+            put(ea[0][0], ea[0][1]);
+        } else if (d == (unsigned)p.d0 + 1u) {
+            put(ea[1][0], ea[1][1]);
+        } else {
+            // a third hop, which no plan holds: the general formula, its bin numbers formed here rather than kept in registers
+            const int k = pipe_lane_here() + 128 * h;
+            put(pv_expected_advance(item_bin(0, k), d), pv_expected_advance(item_bin(1, k), d));
+        }
+        base[4] = (h == 0) ? qa[4] + pv_advance_nyquist(d) : 0u;
+    }
+    __device__ __forceinline__ void inc_from_base(const uint32_t (&qa)[5], const uint32_t (&base)[5], unsigned R, uint32_t (&inc)[5]) const
+    {
+        // (the ratio in a VGPR: the five multiply-adds then take their 64-bit rounding constant from a scalar pair instead of a VGPR pair kept all loop long)
+        unsigned Rv = R;
+        asm volatile("" : "+v"(Rv));
+#pragma unroll
+        for (int q = 0; q < 4; q++) inc[q] = pv_inc_from_base(qa[q], base[q], item_bin(q, k0), Rv);
+        inc[4] = (h == 0) ? pv_inc_from_base(qa[4], base[4], 512u, Rv) : 0u;
+    }
     // increment of frame f against its predecessor's analysis phases (frame 0: its analysis phase itself)
     __device__ __forceinline__ void inc_of_frame(const PvParams& p, long long f, const uint32_t (&qa)[5], const uint32_t (&qprev)[5], uint32_t (&inc)[5]) const
     {
@@ -258,6 +310,14 @@ struct PhaseLane {
     }
     // a continued stream carries the synthesis phase behind its segment's last frame on (nae_stream.hip)
     __device__ __forceinline__ void carry_store(const PvParams& p, long long sc, const uint32_t (&q)[5]) const { write5(p.carry_out + sc * kT1024Pad, q); }
+    // the same for the 64-VGPR build (once per launch: bin index and 64-bit addresses are formed here instead of waiting in registers all loop long)
+    __device__ __forceinline__ void carry_store_here(const PvParams& p, long long sc, const uint32_t (&q)[5]) const
+    {
+        uint32_t* dst = p.carry_out + sc * kT1024Pad;
+        const int k = pipe_lane_here() + 128 * h;
+        dst[k] = q[0]; dst[dc ? 256 : 512 - k] = q[1]; dst[k + 64] = q[2]; dst[448 - k] = q[3];
+        if (dc) dst[512] = q[4];
+    }
     // rotation by the phase difference and the in-lane c2r pre-twiddle: R3's FFT input Zin[k], Zin[512 - k]
     // (conjugated, inverse = conj(FFT(conj Z)) / 512; 2E, 2D: see kSynthGain)
     __device__ __forceinline__ void synth_items(cf* Y, const cf (&x)[5], const uint32_t (&qsv)[5], const uint32_t (&qav)[5]) const
@@ -358,15 +418,16 @@ __device__ __forceinline__ void r3_quarter_source(int slot, int j, int i, int t,
 // a finished hop block to the destination: buffer stores off a scalar descriptor of the block + one 32-bit lane offset (plain pointer stores made
 // hipcc hoist four 64-bit per-lane addresses out of the frame loop); the last block of a stream may be partial
 struct BlockOut { float* optr; long long out_fs; bool out_vec; };
-__device__ __forceinline__ void r3_store_block(const PvParams& p, const PipeItem& it, const BlockOut& bo, long long be, const float (&o)[4], int ls)
+// block be, known to lie in the tile and to start inside the stream; full: it ends inside the stream too
+__device__ __forceinline__ void r3_store_block_at(const PvParams& p, const BlockOut& bo, long long be, bool full, const float (&o)[4], int ls)
 {
-    if (be >= it.b0 && be < it.b_end && be * NAE_HOP < p.mid_len) {
+    {
         float* pb = bo.optr + be * NAE_HOP * bo.out_fs;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(pb, 0, -1, 0x00020000);
         auto st = [&](unsigned byte_off, float v) { __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, (int)byte_off, 0, 0); };
         const unsigned fs4 = 4u * (unsigned)bo.out_fs;              // bytes between consecutive samples
         const unsigned oa = 2u * (unsigned)ls * fs4;                // sample 2 lane of the block
-        if ((be + 1) * NAE_HOP <= p.mid_len) {
+        if (full) {
             if (bo.out_vec) {
                 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                 __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(o[0]), __float_as_uint(o[1])}, rs, (int)(8u * ls), 0, 0);
@@ -382,6 +443,24 @@ __device__ __forceinline__ void r3_store_block(const PvParams& p, const PipeItem
             if (129 + 2 * ls < rem) st(oa + 129u * fs4, o[3]);
         }
     }
+}
+__device__ __forceinline__ void r3_store_block(const PvParams& p, const PipeItem& it, const BlockOut& bo, long long be, const float (&o)[4], int ls)
+{
+    if (be >= it.b0 && be < it.b_end && be * NAE_HOP < p.mid_len) r3_store_block_at(p, bo, be, (be + 1) * NAE_HOP <= p.mid_len, o, ls);
+}
+// One frame per step: the loop's tests on block numbers as 32-bit indices from the tile's first frame f_first, so that each is one scalar compare (a
+// 64-bit order compare of two scalars runs on the vector ALU).  A tile's frame count fits an int; limits beyond it are clamped.
+struct TileRel {
+    int b0, b_end;             // the tile's blocks
+    int full, part;            // blocks below `full` end inside the stream, blocks below `part` start inside it
+};
+__device__ __forceinline__ TileRel pipe_tile_rel(const PvParams& p, const PipeItem& it)
+{
+    auto rel = [&](long long v) {
+        v -= it.f_first;
+        return __builtin_amdgcn_readfirstlane((int)(v < -8 ? -8 : v > 0x7fffffffll ? 0x7fffffffll : v));     // (indices from -3 on are asked)
+    };
+    return TileRel{rel(it.b0), rel(it.b_end), rel(p.mid_len / NAE_HOP), rel((p.mid_len + NAE_HOP - 1) / NAE_HOP)};
 }
 // interleaved stereo, one frame per step: the wave of channel c writes HALF c of the interleaved block — samples 128 c + 2 lane, + 1 of both channels = 16
 // contiguous bytes per lane, 1 KiB per wave — from its own two values (ch_c) and its partner's (ch_o), instead of four dwords that fill a quarter of every 16 bytes
