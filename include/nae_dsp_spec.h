@@ -75,6 +75,31 @@
 #define NAE_DENOISE_MAX_REDUCTION_DB 48.0
 #define NAE_DENOISE_MIN_SENSITIVITY_DB (-6.0)
 #define NAE_DENOISE_MAX_SENSITIVITY_DB 24.0
+/* K14 loudness ("K14 loudness"): the BS.1770-4 meter.  The K-weighting's analog prototypes (nae_loud_design maps them to a
+ * sample rate by the bilinear form); sample rates NAE_LOUD_MIN_RATE ... NAE_LOUD_MAX_RATE that are multiples of NAE_LOUD_SUBS_PER_S, so the
+ * 100 ms sub-block is a whole number of samples; the cascade is K11's tiling with NAE_LOUD_SECTIONS sections.  The true-peak oversampler:
+ * NAE_LOUD_TP_PHASES phases of NAE_LOUD_TP_TAPS taps from one Kaiser-windowed sinc (beta NAE_FIR_KAISER_BETA) of their product taps. */
+#define NAE_LOUD_SHELF_F0 1681.974450955533
+#define NAE_LOUD_SHELF_GAIN_DB 3.999843853973347
+#define NAE_LOUD_SHELF_Q 0.7071752369554196
+#define NAE_LOUD_SHELF_VB_EXP 0.4996667741545416
+#define NAE_LOUD_HP_F0 38.13547087602444
+#define NAE_LOUD_HP_Q 0.5003270373238773
+#define NAE_LOUD_SECTIONS 2
+#define NAE_LOUD_MIN_RATE 8000
+#define NAE_LOUD_MAX_RATE 192000
+#define NAE_LOUD_SUBS_PER_S 10
+#define NAE_LOUD_BLOCK_SUBS 4
+#define NAE_LOUD_ABS_GATE_LUFS (-70.0)
+#define NAE_LOUD_OFFSET 0.691
+#define NAE_LOUD_REL_GATE 0.1
+#define NAE_LOUD_TP_PHASES 4
+#define NAE_LOUD_TP_TAPS 12
+/* nae_loud_design: the ranges of its arguments */
+#define NAE_LOUD_MIN_TARGET_LUFS (-70.0)
+#define NAE_LOUD_MAX_TARGET_LUFS (-5.0)
+#define NAE_LOUD_MIN_CEILING_DBTP (-20.0)
+#define NAE_LOUD_MAX_GAIN_DB 40.0
 /* transient preservation ("Transient preservation"): bin k of frame f rises iff P_f[k] > RISE * P_{f-1}[k] and
  * P_f[k] > FLOOR * N; frame f is "high" iff DEN * (rising bins) >= NUM * (N/2 + 1); an onset is an upward crossing of "high" at f >= 2.
  * RISE is +6 dB: at +3 dB steady white noise crosses 3/8 at N = 512 and 1024 (DESIGN.md gives the numbers). */

@@ -46,7 +46,10 @@ extern "C" {
  *   nae_conv_design_reverb and the nae_conv handle (the same eight entries): the long convolution, K10; nae_eq_design, nae_eq_block_f32 and
  *   the nae_eq handle (the same eight entries): the biquad cascade, K11; nae_dyn_design, nae_dyn_block_f32 and the nae_dyn handle (the same
  *   eight entries) with the record nae_dyn_params: the dynamics processor, K12; nae_denoise_design, nae_denoise_profile_f32,
- *   nae_denoise_block_f32 and the nae_denoise handle (the same eight entries) with the record nae_denoise_params: the spectral gate, K13. */
+ *   nae_denoise_block_f32 and the nae_denoise handle (the same eight entries) with the record nae_denoise_params: the spectral gate, K13;
+ *   nae_loud_design, nae_loud_lufs, nae_loud_measure_f32, nae_loud_apply_f32, nae_loud_normalize_f32 and the measuring handle nae_loud
+ *   (nae_loud_create, _put, _put_host, _flush, _get_result, _destroy) with the records nae_loud_params and nae_loud_result: the BS.1770
+ *   loudness meter and normalizer, K14. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -73,6 +76,7 @@ typedef struct nae_conv nae_conv;
 typedef struct nae_eq nae_eq;
 typedef struct nae_dyn nae_dyn;
 typedef struct nae_denoise nae_denoise;
+typedef struct nae_loud nae_loud;
 
 /* ------------------------------------------------------------------ context / plumbing */
 int nae_abi_version(void);
@@ -653,6 +657,73 @@ size_t nae_denoise_available(nae_denoise* h);
 int nae_denoise_receive(nae_denoise* h, float* dst, size_t max_frames, size_t* got);
 int nae_denoise_receive_host(nae_denoise* h, float* dst_host, size_t max_frames, size_t* got);
 int nae_denoise_destroy(nae_denoise* h);
+
+/* ------------------------------------------------------------------ K14 loudness
+ * no reference code.  Spec ("K14 loudness"): the programme loudness of ITU-R BS.1770-4 / EBU R 128 with the true peak, and the one
+ * gain that brings a stream to a target loudness under a true-peak ceiling.  ch is 1 or 2, every channel weight is 1.  Per channel the f32
+ * samples run through the K-weighting, two biquads in double in K11's tiled form (chunks of NAE_EQ_CHUNK samples from sample 0, 64 lanes of
+ * NAE_EQ_LANE samples, K11's tables; the signal w stays a double).  With B = sample_rate / 10 (100 ms) the energy E_c[u] of sub-block u is the
+ * sum of w w over [u B, (u + 1) B), for the U = floor(in_len / B) complete sub-blocks, in a fixed order: per chunk every lane adds its own
+ * samples of the sub-block in index order from 0.0, the 64 lane sums are added by a butterfly over the distances 32, 16, 8, 4, 2, 1, and the
+ * chunk's sum is added to E_c[u] in chunk order.  Gating block j = 0 ... U - 4 (400 ms, 75 % overlap) has
+ * z_c[j] = ((E[j] + E[j + 1]) + (E[j + 2] + E[j + 3])) / (4 B) and p[j] = z_0[j] (+ z_1[j]).  mean1 is the mean of the p[j] > gate_abs, summed
+ * in block order; mean2 the mean of the p[j] with p > gate_abs and p > 0.1 mean1.  No block past the gates: mean2 = 0, the stream "has no
+ * loudness" and its gain is 1.  The true peak of a channel, in f32: max |v_p[n]| over the four phases p and n = 0 ... in_len + 10 of
+ * v_p[n] = sum over k = 0 ... 11, in this order, of t_p[k] x[n - k] (x zero outside the signal; the taps: nae_dsp_spec.h, NAE_LOUD_TP_*).
+ * gain = sqrt(target / mean2); with P the largest of the channels' true and sample peaks and gain P > ceiling_lin it is ceiling_lin / P; it is
+ * at most max_gain_lin; gain_f32 = (float)gain, and normalizing is y = x gain_f32, one f32 product.  Bit-exact against the CPU statement
+ * (tests/loud_ref/ref_loud.c): every field of the record and every output sample.  A non-finite input sample does not fault; the record of
+ * its stream is then unspecified.
+ * Errors: a null pointer, ch not 1 or 2, a record nae_loud_design did not make (coefficients not finite or not strictly stable, sub_block not
+ * sample_rate / 10, a level that is not positive and finite): NAE_ERR_INVALID; a sample rate outside the rate rule: NAE_ERR_UNSUPPORTED;
+ * in_len = 0 or n_streams = 0: NAE_OK after the checks, nothing is launched.  Views as K11's.  All three entries are asynchronous on the
+ * context's stream; the sub-block energies live in a workspace of the context (8 bytes per stream-channel and 100 ms). */
+typedef struct nae_loud_params {
+    int sample_rate;        /* 8000 ... 192000, a multiple of 10 */
+    int sub_block;          /* B = sample_rate / 10 */
+    double coef[10];        /* the K-weighting: shelf, high-pass, each (b0, b1, b2, a1, a2) */
+    double gate_abs;        /* 10^((-70 + 0.691) / 10): the absolute gate as an energy */
+    double target;          /* 10^((target_lufs + 0.691) / 10) */
+    double ceiling_lin;     /* 10^(ceiling_dbtp / 20) */
+    double max_gain_lin;    /* 10^(max_gain_db / 20) */
+} nae_loud_params;
+typedef struct nae_loud_result {
+    double mean2;           /* gated mean energy; 0: the stream has no loudness.  LUFS = nae_loud_lufs(mean2) */
+    double momentary_max;   /* the largest p[j]; 0 without a block */
+    double gain;
+    float gain_f32;
+    float true_peak[2];     /* per channel, linear; [1] is 0 with one channel */
+    float sample_peak[2];
+    unsigned blocks_total, blocks_abs, blocks_rel;   /* gating blocks, those past the absolute gate, those past both gates */
+} nae_loud_result;
+/* The parameters on the host.  The K-weighting from its analog prototypes by the bilinear form, K = tan(pi f0 / sample_rate): the shelf
+ * f0 = NAE_LOUD_SHELF_F0, Vh = 10^(NAE_LOUD_SHELF_GAIN_DB / 20), Vb = Vh^NAE_LOUD_SHELF_VB_EXP, Q = NAE_LOUD_SHELF_Q:
+ * a0 = 1 + K / Q + K K, b = (Vh + Vb K / Q + K K, 2 (K K - Vh), Vh - Vb K / Q + K K) / a0, a = (2 (K K - 1), 1 - K / Q + K K) / a0; the high-pass
+ * f0 = NAE_LOUD_HP_F0, Q = NAE_LOUD_HP_Q: b = (1, -2, 1), a as the shelf's.  At 48 kHz this is BS.1770's table to better than 1e-13.
+ * NAE_ERR_INVALID: a null pointer, an argument that is not finite, target_lufs outside -70 ... -5, ceiling_dbtp outside -20 ... 0, max_gain_db
+ * outside 0 ... 40; NAE_ERR_UNSUPPORTED: sample_rate outside 8000 ... 192000 or not a multiple of 10.  No context, no device work. */
+int nae_loud_design(int sample_rate, double target_lufs, double ceiling_dbtp, double max_gain_db, nae_loud_params* out);
+/* -0.691 + 10 log10(energy): the loudness of a mean energy (mean2, momentary_max) in LUFS; -infinity for 0.  Host only. */
+double nae_loud_lufs(double energy);
+/* results_dev: device memory, one nae_loud_result per stream */
+int nae_loud_measure_f32(nae_ctx* ctx, const nae_loud_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                         nae_loud_result* results_dev);
+/* y = x results_dev[stream].gain_f32 */
+int nae_loud_apply_f32(nae_ctx* ctx, const nae_loud_result* results_dev, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                       const nae_sig* dst);
+/* measure, then apply; results_dev may be null (the records then stay in the context's workspace); dst may be src */
+int nae_loud_normalize_f32(nae_ctx* ctx, const nae_loud_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                           const nae_sig* dst, nae_loud_result* results_dev);
+/* Measuring handle on the shared device FIFO (channels = ch): whole chunks are measured as they fill and leave the FIFO, the sub-block
+ * energies grow on the device; nae_loud_flush measures the rest and runs the gates; nae_loud_get_result then copies the record to the host
+ * (it waits for the stream).  The record equals the block call's however the input is cut.  nae_loud_get_result before the flush, or a put
+ * after it: NAE_ERR_STATE. */
+int nae_loud_create(nae_ctx* ctx, const nae_loud_params* params, int channels, nae_loud** h);
+int nae_loud_put(nae_loud* h, const float* interleaved, size_t S);
+int nae_loud_put_host(nae_loud* h, const float* interleaved_host, size_t S);
+int nae_loud_flush(nae_loud* h);
+int nae_loud_get_result(nae_loud* h, nae_loud_result* out_host);
+int nae_loud_destroy(nae_loud* h);
 
 /* ------------------------------------------------------------------ the 4-node graph of BASELINE.json
  * input -> mix(2) -> pitch -> FFT spectrum, one launch sequence over n_streams independent streams.

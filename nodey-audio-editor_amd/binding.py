@@ -44,6 +44,8 @@ EXPORTED_SYMBOLS = [
     "nae_dyn_receive", "nae_dyn_receive_host", "nae_dyn_destroy",
     "nae_denoise_design", "nae_denoise_profile_f32", "nae_denoise_block_f32", "nae_denoise_create", "nae_denoise_put", "nae_denoise_put_host",
     "nae_denoise_flush", "nae_denoise_available", "nae_denoise_receive", "nae_denoise_receive_host", "nae_denoise_destroy",
+    "nae_loud_design", "nae_loud_lufs", "nae_loud_measure_f32", "nae_loud_apply_f32", "nae_loud_normalize_f32", "nae_loud_create", "nae_loud_put",
+    "nae_loud_put_host", "nae_loud_flush", "nae_loud_get_result", "nae_loud_destroy",
 ]
 
 
@@ -103,6 +105,23 @@ class DynParams(C.Structure):
 class DenoiseParams(C.Structure):
     """nae_denoise_params: the spectral gate's parameters (include/nae_gpu.h); nae_denoise_design makes them from decibels"""
     _fields_ = [("n_fft", C.c_int), ("time_smooth", C.c_int), ("freq_smooth", C.c_int), ("thr_scale", C.c_float), ("floor_gain", C.c_float)]
+
+
+class LoudParams(C.Structure):
+    """nae_loud_params: the loudness meter's parameters (include/nae_gpu.h); nae_loud_design makes them from a sample rate and decibels"""
+    _fields_ = [("sample_rate", C.c_int), ("sub_block", C.c_int), ("coef", C.c_double * 10), ("gate_abs", C.c_double), ("target", C.c_double),
+                ("ceiling_lin", C.c_double), ("max_gain_lin", C.c_double)]
+
+
+class LoudResult(C.Structure):
+    """nae_loud_result: one stream's measurement and gain (include/nae_gpu.h)"""
+    _fields_ = [("mean2", C.c_double), ("momentary_max", C.c_double), ("gain", C.c_double), ("gain_f32", C.c_float), ("true_peak", C.c_float * 2),
+                ("sample_peak", C.c_float * 2), ("blocks_total", C.c_uint), ("blocks_abs", C.c_uint), ("blocks_rel", C.c_uint)]
+
+    @property
+    def lufs(self) -> float:
+        """the integrated loudness; -inf for a stream without loudness"""
+        return float("-inf") if self.mean2 == 0.0 else load_library().nae_loud_lufs(self.mean2)
 
 
 class StretchPlan(C.Structure):
@@ -209,6 +228,11 @@ def load_library() -> C.CDLL:
         "nae_denoise_design": (i, [d, d, i, i, i, P(DenoiseParams)]), "nae_denoise_profile_f32": (i, [vp, i, P(Sig), sz, i, vp]),
         "nae_denoise_block_f32": (i, [vp, P(DenoiseParams), vp, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
+        "nae_loud_design": (i, [i, d, d, d, P(LoudParams)]), "nae_loud_lufs": (d, [d]),
+        "nae_loud_measure_f32": (i, [vp, P(LoudParams), P(Sig), sz, i, sz, vp]), "nae_loud_apply_f32": (i, [vp, vp, P(Sig), sz, i, sz, P(Sig)]),
+        "nae_loud_normalize_f32": (i, [vp, P(LoudParams), P(Sig), sz, i, sz, P(Sig), vp]),
+        "nae_loud_create": (i, [vp, P(LoudParams), i, P(vp)]), "nae_loud_put": (i, [vp, vp, sz]), "nae_loud_put_host": (i, [vp, vp, sz]),
+        "nae_loud_flush": (i, [vp]), "nae_loud_get_result": (i, [vp, P(LoudResult)]), "nae_loud_destroy": (i, [vp]),
     }
     # the seven entries every put / receive handle has besides its create (the spectrum handle has four of them: spelled out above)
     for prefix in HANDLE_PREFIXES:
@@ -659,6 +683,35 @@ class Context:
         """the spectral gate `params` against the device profile [profile_ch][n_fft / 2 + 1] over every stream; dst receives in_len frames"""
         self._ck(self.lib.nae_denoise_block_f32(self.h, C.byref(params), profile_ptr, profile_ch, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K14
+    @staticmethod
+    def loud_design(sample_rate: int, target_lufs: float = -14.0, ceiling_dbtp: float = -1.0, max_gain_db: float = 20.0) -> "LoudParams":
+        """the K-weighting at sample_rate and the levels of the normalizer as energies and linear gains (nae_loud_design)"""
+        out = LoudParams()
+        rc = load_library().nae_loud_design(sample_rate, target_lufs, ceiling_dbtp, max_gain_db, C.byref(out))
+        if rc:
+            raise NaeError(f"nae_loud_design({sample_rate}, {target_lufs}, {ceiling_dbtp}, {max_gain_db}) failed: {rc}")
+        return out
+
+    def loud_measure(self, params: "LoudParams", src: Sig, in_len: int, ch: int, n_streams: int, results_ptr: int):
+        """BS.1770 loudness, peaks and normalizing gain of every stream into n_streams nae_loud_result records at results_ptr (asynchronous)"""
+        self._ck(self.lib.nae_loud_measure_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, results_ptr))
+
+    def loud_apply(self, results_ptr: int, src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """every stream times the gain_f32 of its record at results_ptr"""
+        self._ck(self.lib.nae_loud_apply_f32(self.h, results_ptr, C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
+    def loud_normalize(self, params: "LoudParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig, results_ptr: int = 0):
+        """loud_measure, then loud_apply; results_ptr 0: the records stay in the library's workspace"""
+        self._ck(self.lib.nae_loud_normalize_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst), results_ptr or None))
+
+    def loud_results(self, results_ptr: int, n_streams: int):
+        """the n_streams records at results_ptr, on the host (waits for the stream)"""
+        out = (LoudResult * n_streams)()
+        self._ck(self.lib.nae_memcpy_d2h(self.h, C.addressof(out), results_ptr, C.sizeof(out)))
+        self.sync()
+        return list(out)
+
     # -- graph
     def graph4(self, g: Graph4):
         self._ck(self.lib.nae_graph4_run(self.h, C.byref(g)))
@@ -799,3 +852,23 @@ class Denoise(_Handle):
     def __init__(self, ctx: Context, params: DenoiseParams, profile_ptr: int, profile_ch: int, channels: int):
         super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_denoise_create(ctx.h, C.byref(params), profile_ptr, profile_ch, channels, C.byref(self.h)))
+
+
+class Loud(_Handle):
+    """The loudness meter's handle (nae_loud_create): put interleaved f32, flush, result().  It hands out no samples: available() is 0 and there
+    is nothing to receive."""
+
+    _prefix = "nae_loud"
+
+    def __init__(self, ctx: Context, params: LoudParams, channels: int):
+        super().__init__(ctx, channels)
+        ctx._ck(ctx.lib.nae_loud_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+    def available(self) -> int:
+        return 0
+
+    def result(self) -> LoudResult:
+        """the record behind the flush (NAE_ERR_STATE in front of it)"""
+        out = LoudResult()
+        self.ctx._ck(self.ctx.lib.nae_loud_get_result(self.h, C.byref(out)))
+        return out

@@ -12,18 +12,12 @@
 // 16 x (5 + 56) doubles.  The coefficients and the maps are read from it at wave-uniform addresses; p and q of the call's sections are copied
 // into LDS once per launch and read there as broadcasts (read from the block they cost 28 SGPR spills).
 // The translation unit is built with -ffp-contract=off: every step is one IEEE operation, in the order of the CPU statement
-// (tests/eq_ref/ref_eq.c).  It shares no code with the other kernels.
-#include "launch.h"
+// (tests/eq_ref/ref_eq.c).  The section's steps stand in eq_cascade.h, which the loudness meter (kernels_loud.hip) runs too.
+#include "eq_cascade.h"
 #include <math.h>
 #include <string.h>
 
 namespace nae {
-
-constexpr int kEqT = NAE_EQ_LANE, kEqC = NAE_EQ_CHUNK, kEqStride = kEqT + 1;
-constexpr int kEqCoefs = 5, kEqTab = 2 * kEqT + 6 * 4;     // per section: b0 b1 b2 a1 a2 | p[T] q[T] Phi_0 ... Phi_5 (m00 m01 m10 m11 each)
-constexpr int kEqTabOfs = NAE_EQ_MAX_SECTIONS * kEqCoefs;  // the tables stand behind the coefficients of all sections
-constexpr size_t kEqBlockDoubles = (size_t)NAE_EQ_MAX_SECTIONS * (kEqCoefs + kEqTab);
-static_assert(kEqTab == 56 && kEqC == 1024, "DESIGN.md §3, K11: 56 doubles of tables per section, chunks of 1024 samples");
 
 struct EqParams {
     long long in_len;      // samples of a stream-channel: reads at or past in_len give zero, samples there are not stored
@@ -32,14 +26,6 @@ struct EqParams {
     long long n_sc;        // stream-channels: one wave each
     int ch, n_sections;
 };
-
-__device__ __forceinline__ void eq_lds_sync()
-{
-    // this wave's LDS writes before its following LDS reads of other lanes' words: DS operations of one wave execute in issue order
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // state: [n_sc][NAE_EQ_MAX_SECTIONS][2] doubles, the carry (z1, z2) of every section in front of chunk c_origin, replaced by the one behind chunk
 // c_stop - 1; null: zero in, nothing out (the block call)
@@ -78,51 +64,7 @@ __global__ __launch_bounds__(64) void eq_cascade_kernel(SigViewD src, OutViewD o
         for (int k = 0; k < kEqT; k++) x[k] = (double)stage[lane * kEqStride + k];
 #pragma unroll 1
         for (int s = 0; s < S; s++) {
-            const double* cf = tab + s * kEqCoefs;
-            const double* t = pq + s * 2 * kEqT;
-            const double b0 = cf[0], b1 = cf[1], b2 = cf[2], a1 = cf[3], a2 = cf[4];
-            // 1: the zero-state pass
-            double z1 = 0.0, z2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < kEqT; k++) {
-                const double xv = x[k];
-                const double y = b0 * xv + z1;
-                z1 = (b1 * xv - a1 * y) + z2;
-                z2 = b2 * xv - a2 * y;
-                x[k] = y;
-            }
-            // 3: the carry.  E_0 takes the chunk's carry-in, then six steps, each reading the previous step's values
-            const double in1 = __shfl(st1, s), in2 = __shfl(st2, s);
-            const double* ph = tab + kEqTabOfs + s * kEqTab + 2 * kEqT;
-            if (lane == 0) {
-                const double e1 = z1 + ((ph[0] * in1) + (ph[1] * in2));
-                const double e2 = z2 + ((ph[2] * in1) + (ph[3] * in2));
-                z1 = e1;
-                z2 = e2;
-            }
-#pragma unroll
-            for (int j = 0; j < 6; j++) {
-                const double u1 = __shfl_up(z1, 1u << j), u2 = __shfl_up(z2, 1u << j);
-                const double e1 = z1 + ((ph[4 * j] * u1) + (ph[4 * j + 1] * u2));
-                const double e2 = z2 + ((ph[4 * j + 2] * u1) + (ph[4 * j + 3] * u2));
-                if (lane >= (1 << j)) {
-                    z1 = e1;
-                    z2 = e2;
-                }
-            }
-            double s1 = __shfl_up(z1, 1u), s2 = __shfl_up(z2, 1u);
-            if (lane == 0) {
-                s1 = in1;
-                s2 = in2;
-            }
-            const double o1 = __shfl(z1, 63), o2 = __shfl(z2, 63);
-            if (lane == s) {
-                st1 = o1;
-                st2 = o2;
-            }
-            // 4: the correction; y is the next section's input
-#pragma unroll
-            for (int k = 0; k < kEqT; k++) x[k] = x[k] + ((t[k] * s1) + (t[kEqT + k] * s2));
+            eq_section(x, s, lane, tab, pq, st1, st2);
         }
         // the lanes read their own words above and write only them here; the coalesced read below needs the other lanes' words
 #pragma unroll
@@ -205,7 +147,7 @@ static EqDD dd_mul(EqDD x, EqDD y)
 
 // DESIGN.md §3, "K11 biquad cascade", step 2: the constant block of a cascade.  p, q and the six maps by the zero-input recurrence in its literal
 // order and five squarings, all in double-double; every entry is rounded to double once, at the end
-static void eq_make_tables(const double* coef, int n_sections, double* blk)
+void eq_make_tables(const double* coef, int n_sections, double* blk)
 {
     memset(blk, 0, kEqBlockDoubles * sizeof(double));
     for (int s = 0; s < n_sections; s++) {

@@ -359,6 +359,7 @@ int nae_ctx_destroy(nae_ctx* ctx)
     nae_fir_cache_free(ctx);
     nae_conv_cache_free(ctx);
     nae_eq_cache_free(ctx);
+    nae_loud_cache_free(ctx);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return NAE_OK;

@@ -46,6 +46,10 @@ struct nae_ctx {
     // nae_eq_block_f32 keeps the last call's coefficients and their constant block (kernels_eq.hip)
     double* d_eq_block = nullptr;
     std::vector<double> h_eq_coef;
+    // the loudness entries keep the last call's K-weighting and its constant block, and their workspace: states, sub-block energies, records (kernels_loud.hip)
+    void* d_loud_block = nullptr;
+    std::vector<double> h_loud_coef;
+    void* ws_loud = nullptr; size_t ws_loud_bytes = 0;
     // tuning / A-B switches: nae_debug_set(ctx, key, value) (include/nae_gpu.h lists the keys; NAE_DEBUG="key=value,..." applies them at context creation)
     bool dbg_st_unfused = false;     // st_unfused: WSOLA chain runs filter and cubic stage as separate launches
     int dbg_td_nc = 0;               // td_nc = 1|2|4: candidates per thread of the WSOLA search (0: by batch size)
@@ -292,6 +296,24 @@ int nae_denoise_check(nae_ctx* ctx, const nae_denoise_params* p, const float* pr
 int nae_launch_denoise(nae_ctx* ctx, const nae_denoise_params* p, const float* d_profile, int profile_ch, const nae_sig* src, size_t in_len, int ch,
                        size_t n_streams, const nae_sig* dst, size_t b_origin, size_t b_stop);
 int nae_pick_denoise_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc);
+
+// kernels_loud.hip: the loudness meter ("K14 loudness").  nae_loud_check: the parameter rules of the block entries and the handle.  A
+// constant block holds nae_loud_block_bytes() bytes: K11's block of the two K-weighting sections, then the true-peak taps (nae_loud_make_block,
+// which waits for the upload).  nae_launch_loud_measure runs chunks [c_origin, c_stop) of absolutely indexed signals: d_state, n_streams x ch
+// records of nae_loud_state_bytes() bytes, is what a stream-channel carries (zero in front of sample 0) and holds the peaks behind c_stop - 1;
+// d_E holds the sub-block energies, sub-block u of channel c of stream s at [s * e_ss + u * ch + c], zero before the first launch; sums of
+// sub-blocks from n_sub on are dropped.  nae_loud_chunks: the chunks of in_len samples a handle has measured before its flush (the whole ones)
+// and behind it (the true peak reaches 11 samples past the end).  nae_launch_loud_gate: the gates and the gain of signals of in_len samples.
+size_t nae_loud_block_bytes();
+size_t nae_loud_state_bytes();
+int nae_loud_check(nae_ctx* ctx, const nae_loud_params* p, int ch);
+int nae_loud_make_block(nae_ctx* ctx, const nae_loud_params* p, void* d_block);
+size_t nae_loud_chunks(size_t in_len, bool flushed);
+int nae_launch_loud_measure(nae_ctx* ctx, const nae_loud_params* p, const void* d_block, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                            size_t c_origin, size_t c_stop, void* d_state, double* d_E, size_t e_ss, size_t n_sub);
+int nae_launch_loud_gate(nae_ctx* ctx, const nae_loud_params* p, size_t in_len, int ch, size_t n_streams, const void* d_state, const double* d_E,
+                         size_t e_ss, nae_loud_result* d_results);
+void nae_loud_cache_free(nae_ctx* ctx);
 
 // kernels_nodes.hip
 int nae_launch_copy_sig(nae_ctx* ctx, const nae_sig* src, const nae_sig* dst, size_t S, int ch, size_t n_streams,

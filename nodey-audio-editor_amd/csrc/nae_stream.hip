@@ -76,6 +76,21 @@ struct nae_denoise : BlockHandle {
     int process() override;
 };
 
+// the loudness meter's handle ("K14 loudness"): whole chunks of NAE_EQ_CHUNK samples are measured as they fill and leave the FIFO
+// (the state carries the 11 samples the true peak reads in front of a chunk); the sub-block energies grow on the device; the flush measures the
+// rest and runs the gates.  Nothing comes out of it but the record.
+struct nae_loud : StreamHandle {
+    nae_loud_params params;
+    void* d_block = nullptr;       // the K-weighting's tables and the true-peak taps (nae_loud_make_block)
+    void* d_state = nullptr;       // [ch] records of nae_loud_state_bytes() bytes
+    nae_loud_result* d_result = nullptr;
+    double* d_E = nullptr;         // [e_cap][ch] sub-block energies; grown by doubling, the new part zero
+    size_t e_cap = 0, done = 0;    // sub-blocks d_E holds; chunks measured
+    int reserve_E(size_t want);
+    int process() override;
+    ~nae_loud() override { if (d_E) (void)hipFree(d_E); }
+};
+
 namespace {
 
 inline long long frame_start_host(const nae_stretch_plan& pl, int n_fft, long long f)
@@ -302,6 +317,46 @@ int nae_denoise::process()
     return run_units(H, reach * H, reach, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
         return nae_launch_denoise(ctx, &params, d_profile, profile_ch, &src, in.total, ch, 1, &dst, from, to);
     });
+}
+
+int nae_loud::reserve_E(size_t want)
+{
+    if (want <= e_cap) return NAE_OK;
+    size_t cap = e_cap ? e_cap : 1024;
+    while (cap < want) cap *= 2;
+    double* np = nullptr;
+    if (hipMalloc((void**)&np, cap * ch * sizeof(double)) != hipSuccess) return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(loud sub-blocks)");
+    hipError_t e = hipMemsetAsync(np, 0, cap * ch * sizeof(double), ctx->stream);
+    if (e == hipSuccess && d_E) e = hipMemcpyAsync(np, d_E, e_cap * ch * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(np);
+        return nae_check(ctx, e, "loud: sub-block array");
+    }
+    if (d_E) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(d_E);
+    }
+    d_E = np;
+    e_cap = cap;
+    return NAE_OK;
+}
+
+int nae_loud::process()
+{
+    const size_t ready = nae_loud_chunks(in.total, flushed);
+    if (ready > done) {
+        // every sub-block the chunks up to `ready` meet has its entry
+        int rc = reserve_E(ready * NAE_EQ_CHUNK / (size_t)params.sub_block + 1);
+        if (rc) return rc;
+        const nae_sig src = in.view();
+        rc = nae_launch_loud_measure(ctx, &params, d_block, &src, in.total, ch, 1, done, ready, d_state, d_E, e_cap * ch, e_cap);
+        if (rc) return rc;
+        done = ready;
+        in.drop((long long)(ready * NAE_EQ_CHUNK));
+    }
+    if (!flushed) return NAE_OK;
+    const int rc = reserve_E(1);
+    return rc ? rc : nae_launch_loud_gate(ctx, &params, in.total, ch, 1, d_state, d_E, e_cap * ch, d_result);
 }
 
 extern "C" {
@@ -536,5 +591,41 @@ size_t nae_denoise_available(nae_denoise* h) { return handle_available(h); }
 int nae_denoise_receive(nae_denoise* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_denoise_receive_host(nae_denoise* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_denoise_destroy(nae_denoise* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ loudness
+int nae_loud_create(nae_ctx* ctx, const nae_loud_params* params, int channels, nae_loud** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_loud_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_loud* s = handle_new<nae_loud>(ctx, channels);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    const size_t state_bytes = (size_t)channels * nae_loud_state_bytes();
+    rc = s->dev_alloc((char**)&s->d_block, nae_loud_block_bytes(), "hipMalloc(loud tables)");
+    if (!rc) rc = s->dev_alloc((char**)&s->d_state, state_bytes, "hipMalloc(loud state)");
+    if (!rc) rc = s->dev_alloc(&s->d_result, 1, "hipMalloc(loud record)");
+    if (!rc) rc = nae_check(ctx, hipMemsetAsync(s->d_state, 0, state_bytes, ctx->stream), "hipMemsetAsync(loud state)");
+    if (!rc) rc = nae_loud_make_block(ctx, params, s->d_block);
+    return handle_created(s, rc, h);
+}
+
+int nae_loud_put(nae_loud* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_loud_put_host(nae_loud* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+// flush: the partial last chunk, and one more where the true peak's tail reaches past it, are measured; the gates run
+int nae_loud_flush(nae_loud* h) { return handle_flush(h); }
+int nae_loud_destroy(nae_loud* h) { return handle_destroy(h); }
+
+int nae_loud_get_result(nae_loud* h, nae_loud_result* out_host)
+{
+    if (!h || !out_host) return NAE_ERR_INVALID;
+    (void)nae_use_device(h->ctx);
+    if (!h->flushed) return nae_fail(h->ctx, NAE_ERR_STATE, "result before flush");
+    hipError_t e = hipMemcpyAsync(out_host, h->d_result, sizeof(nae_loud_result), hipMemcpyDeviceToHost, h->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->ctx->stream);
+    return e == hipSuccess ? NAE_OK : nae_check(h->ctx, e, "loud: result download");
+}
 
 } // extern "C"

@@ -155,4 +155,6 @@ namespace infra
 	void register_dynamics_processors();
 	// the restoration tools (audio_denoise): called after the five above, each of which stays the list it was
 	void register_restoration_processors();
+	// the mastering tools (audio_loudness): called after the six above, each of which stays the list it was
+	void register_mastering_processors();
 }

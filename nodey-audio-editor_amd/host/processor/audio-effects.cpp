@@ -1,16 +1,19 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
-// Audio_dynamics (nae_dyn) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle).
+// Audio_dynamics (nae_dyn) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
+// and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 #include "audio-filter.hpp"
 #include "audio-reverb.hpp"
 #include "audio-eq.hpp"
 #include "audio-dynamics.hpp"
 #include "audio-denoise.hpp"
+#include "audio-loudness.hpp"
 #include "node-util.hpp"
 #include "nae_dsp_spec.h"
 
 #include <algorithm>
 #include <cmath>
 #include <deque>
+#include <optional>
 #include <type_traits>
 
 namespace processor
@@ -628,5 +631,176 @@ namespace processor
 				return dn;
 			}
 		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_loudness
+	infra::Processor::Info Audio_loudness::get_processor_info()
+	{
+		return {"audio_loudness", "Audio Loudness", false, [] { return std::unique_ptr<infra::Processor>(new Audio_loudness); },
+				"Loudness normalization: ITU-R BS.1770 integrated loudness and true peak, one gain to a target level under a true-peak ceiling (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_loudness::get_pin_attributes() const { return io_pins(); }
+
+	Json::Value Audio_loudness::serialize() const
+	{
+		Json::Value value;
+		if (target_lufs != default_target_lufs) value["target_lufs"] = target_lufs;
+		if (true_peak_db != default_true_peak_db) value["true_peak_db"] = true_peak_db;
+		if (max_gain_db != default_max_gain_db) value["max_gain_db"] = max_gain_db;
+		return value;
+	}
+
+	void Audio_loudness::deserialize(const Json::Value& value)
+	{
+		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
+		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_loudness", key, lo, hi, fallback); };
+		const double t = real("target_lufs", NAE_LOUD_MIN_TARGET_LUFS, NAE_LOUD_MAX_TARGET_LUFS, default_target_lufs);
+		const double p = real("true_peak_db", NAE_LOUD_MIN_CEILING_DBTP, 0.0, default_true_peak_db);
+		const double m = real("max_gain_db", 0.0, NAE_LOUD_MAX_GAIN_DB, default_max_gain_db);
+		target_lufs = t; true_peak_db = p; max_gain_db = m;
+	}
+
+	void Audio_loudness::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		// this node's context (own stream) is made when the first gating block has arrived: a shorter stream never touches the GPU.  First
+		// local, destroyed last — after the handle guard and the buffers
+		std::optional<gpu::Node> node;
+		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
+		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
+		if (!input_item.has_value())
+			throw Runtime_error("Audio Loudness has no input", "Audio Loudness requires an audio stream input to function properly.", "Input item 'input' not found");
+		Audio_stream& input_stream = input_item.value().get();
+		nae_loud* h = nullptr;
+		struct Guard { nae_loud*& h; ~Guard() { if (h) nae_loud_destroy(h); } } guard{h};
+		struct Buffers { gpu::Device_buffer d_raw, d_f32; gpu::Pinned_buffer h_raw, h_f32; };
+		std::optional<Buffers> buf;
+		int ch = 0;
+		struct Shape { int nb_samples, sample_rate; int64_t pts; decltype(Frame_data::time_base) time_base; };
+		std::vector<Shape> shapes;                                  // every frame received
+		std::vector<float> kept;                                    // their samples as interleaved f32, from the first put on
+		std::vector<std::shared_ptr<const Audio_frame>> pending;    // frames not yet put: they wait for the first 400 ms
+		size_t pending_samples = 0;
+		std::shared_ptr<const Audio_frame> held;
+		const auto push = [&](const std::shared_ptr<const Audio_frame>& frame) {
+			for (auto& stream : output_stream)
+				while (!stop_token && stream->try_push(frame) != channel_op_status::success) nae_fiber::this_fiber::yield();
+		};
+
+		while (!stop_token)
+		{
+			bool ended = false;
+			const std::vector<std::shared_ptr<const Audio_frame>> batch = collect_batch(input_stream, held, &ended);
+			if (batch.empty() && !ended)
+			{
+				nae_fiber::this_fiber::yield();
+				continue;
+			}
+			for (const auto& f : batch)
+			{
+				const Frame_data* frame = f->data();
+				if (ch == 0)
+				{
+					ch = frame->ch_layout.nb_channels;
+					if (ch != 1 && ch != 2) throw Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
+				}
+				else if (frame->ch_layout.nb_channels != ch)
+					throw Runtime_error("Channel count changed", "The node runs one stream of a fixed channel count.",
+										infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, ch));
+				// one gain from one meter: the K-weighting and the sub-block are the first frame's rate's
+				if (!shapes.empty() && frame->sample_rate != shapes.front().sample_rate)
+					throw Runtime_error("Sample rate changed", "The node runs one stream of a fixed sample rate.",
+										infra::fmt("Got %d Hz after %d Hz", frame->sample_rate, shapes.front().sample_rate));
+				shapes.push_back({frame->nb_samples, frame->sample_rate, frame->pts, frame->time_base});
+				pending.push_back(f);
+				pending_samples += (size_t)frame->nb_samples;
+			}
+			// one gating block: NAE_LOUD_BLOCK_SUBS sub-blocks of 1 / NAE_LOUD_SUBS_PER_S seconds
+			const bool block_there = !pending.empty() && pending_samples * NAE_LOUD_SUBS_PER_S >= (size_t)NAE_LOUD_BLOCK_SUBS * pending.front()->data()->sample_rate;
+			if (!pending.empty() && (h != nullptr || block_there))
+			{
+				if (h == nullptr)
+				{
+					const int sample_rate = pending.front()->data()->sample_rate;
+					nae_loud_params params;
+					const int rc = nae_loud_design(sample_rate, target_lufs, true_peak_db, max_gain_db, &params);
+					if (rc == NAE_ERR_UNSUPPORTED)
+						throw Runtime_error("Unsupported sample rate", "The loudness meter runs at 8000 ... 192000 Hz, in multiples of 10 Hz.",
+											infra::fmt("%d Hz", sample_rate));
+					if (rc != NAE_OK)
+						throw Runtime_error("Invalid loudness parameters", "A parameter of the loudness node lies outside its range.",
+											infra::fmt("nae_loud_design at %d Hz: code %d", sample_rate, rc));
+					node.emplace();
+					buf.emplace();
+					gpu::check(nae_loud_create(node->ctx(), &params, ch, &h), "nae_loud_create");
+				}
+				size_t total = 0;
+				float* samples = upload_as_f32(pending, buf->h_raw, buf->d_raw, buf->d_f32, &total);
+				gpu::check(nae_loud_put(h, samples, total), "nae_loud_put");
+				// the node keeps the f32 samples the meter saw.  Packed float frames (and mono planar ones) already are those samples; integer
+				// and planar stereo frames were converted on the device and come back from there.  Either way the batch is waited for: the
+				// staging buffers are reused by the next one
+				bool wire = true;
+				for (const auto& f : pending)
+					wire = wire && (f->data()->format == AV_SAMPLE_FMT_FLT || (f->data()->format == AV_SAMPLE_FMT_FLTP && ch == 1));
+				if (wire)
+				{
+					gpu::wait(stop_token);
+					for (const auto& f : pending)
+					{
+						const float* data = reinterpret_cast<const float*>(f->data()->data[0]);
+						kept.insert(kept.end(), data, data + (size_t)f->data()->nb_samples * ch);
+					}
+				}
+				else
+				{
+					float* host = static_cast<float*>(buf->h_f32.reserve(total * ch * sizeof(float)));
+					gpu::check(nae_memcpy_d2h(node->ctx(), host, samples, total * ch * sizeof(float)), "d2h");
+					gpu::wait(stop_token);
+					kept.insert(kept.end(), host, host + total * ch);
+				}
+				pending.clear();
+				pending_samples = 0;
+			}
+			if (batch.empty() && ended)
+			{
+				if (h == nullptr)
+				{
+					// under 400 ms: no gating block, no loudness — the frames pass as they are
+					for (const auto& f : pending) push(f);
+					break;
+				}
+				gpu::check(nae_loud_flush(h), "nae_loud_flush");
+				gpu::wait(stop_token);
+				nae_loud_result result;
+				gpu::check(nae_loud_get_result(h, &result), "nae_loud_get_result");
+				const float gain = result.gain_f32;
+				size_t pos = 0;
+				for (const Shape& s : shapes)
+				{
+					if (stop_token) break;
+					auto out = std::make_shared<Audio_frame>();
+					Frame_data* o = out->data();
+					o->format = AV_SAMPLE_FMT_FLT;
+					o->sample_rate = s.sample_rate;
+					o->nb_samples = s.nb_samples;
+					o->ch_layout.nb_channels = ch;
+					o->time_base = s.time_base;
+					o->pts = s.pts;
+					frame_get_buffer(o, 32);
+					float* dst = reinterpret_cast<float*>(o->data[0]);
+					const size_t n = (size_t)s.nb_samples * ch;
+					for (size_t i = 0; i < n; i++) dst[i] = kept[pos + i] * gain;   // one f32 product, as loud_apply_kernel's
+					pos += n;
+					push(out);
+				}
+				break;
+			}
+		}
+		for (auto& stream : output_stream) stream->set_eof();
 	}
 }

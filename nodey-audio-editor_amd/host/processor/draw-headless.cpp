@@ -18,9 +18,11 @@
 #include "audio-eq.hpp"
 #include "audio-dynamics.hpp"
 #include "audio-denoise.hpp"
+#include "audio-loudness.hpp"
 #include "audio-mix.hpp"
 #include "audio-velocity.hpp"
 #include "audio-vol.hpp"
+#include "nae_dsp_spec.h"
 
 namespace processor
 {
@@ -130,6 +132,16 @@ namespace processor
 		freq_smooth = std::clamp(freq_smooth, 0, 4);
 		profile_start_ms = std::clamp(profile_start_ms, 0.0, 60000.0);
 		profile_ms = std::clamp(profile_ms, 20.0, 10000.0);
+		return false;
+	}
+
+	void Audio_loudness::draw_title() {}
+	bool Audio_loudness::draw_content(bool)
+	{
+		// what the widgets would keep: every value inside its range
+		target_lufs = std::clamp(target_lufs, NAE_LOUD_MIN_TARGET_LUFS, NAE_LOUD_MAX_TARGET_LUFS);
+		true_peak_db = std::clamp(true_peak_db, NAE_LOUD_MIN_CEILING_DBTP, 0.0);
+		max_gain_db = std::clamp(max_gain_db, 0.0, NAE_LOUD_MAX_GAIN_DB);
 		return false;
 	}
 }

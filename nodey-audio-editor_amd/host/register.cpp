@@ -8,6 +8,7 @@
 #include "processor/audio-eq.hpp"
 #include "processor/audio-dynamics.hpp"
 #include "processor/audio-denoise.hpp"
+#include "processor/audio-loudness.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -47,4 +48,7 @@ namespace infra
 
 	// the restoration tools: noise reduction on the spectral gate; a call of its own, so the five lists above stay what they were
 	void register_restoration_processors() { register_each<processor::Audio_denoise>(); }
+
+	// the mastering tools: loudness normalization on the BS.1770 meter; a call of its own, so the six lists above stay what they were
+	void register_mastering_processors() { register_each<processor::Audio_loudness>(); }
 }
