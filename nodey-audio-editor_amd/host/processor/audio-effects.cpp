@@ -1,6 +1,7 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
 // Audio_dynamics (nae_dyn) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
+// Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
 #include "audio-filter.hpp"
 #include "audio-reverb.hpp"
 #include "audio-eq.hpp"
@@ -12,7 +13,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <deque>
 #include <optional>
 #include <type_traits>
 
@@ -25,9 +25,10 @@ namespace processor
 	// releases the rest, and what is left behind the last frame owed is dropped.  `create` makes the handle from the first frame (its sample
 	// rate) and the channel count, or throws.  The first `to_discard` frames of the handle's output are dropped (a linear-phase filter's group
 	// delay); `noun` is the node's word for itself in the "Channel count changed" error; ops.name is the prefix of the handle's entries.
-	// run_on_handle_held is the loop itself: hold(first frame) says how many samples must have arrived before the handle is made (the noise
-	// reduction learns from a stretch of its input).  Until then, or until the stream ends, the frames wait; create(ctx, first frame, ch,
-	// samples, total) then sees everything held, on the device as interleaved f32, and all of it is the handle's first put.
+	// run_on_handle_held is the loop itself, between the intake (take_in) and the cutting of the output (cut_and_push): hold(first frame) says
+	// how many samples must have arrived before the handle is made (the noise reduction learns from a stretch of its input).  Until then, or
+	// until the stream ends, the frames wait; create(ctx, first frame, ch, samples, total) then sees everything held, on the device as
+	// interleaved f32, and all of it is the handle's first put.
 	template <class Handle>
 	struct Handle_ops
 	{
@@ -41,7 +42,7 @@ namespace processor
 
 	template <class Handle, class Hold, class Create>
 	static void run_on_handle_held(
-		Audio_stream& input_stream, const std::set<std::shared_ptr<Audio_stream>>& output_stream, const std::atomic<bool>& stop_token,
+		Audio_stream& input_stream, const Output_streams& output_stream, const std::atomic<bool>& stop_token,
 		const std::type_identity_t<Handle_ops<Handle>>& ops, const char* noun, size_t to_discard, const Hold& hold, const Create& create
 	)
 	{
@@ -50,14 +51,9 @@ namespace processor
 		struct Guard { Handle*& h; int (*destroy)(Handle*); ~Guard() { if (h) destroy(h); } } guard{h, ops.destroy};
 		gpu::Device_buffer d_raw, d_f32, d_out;
 		gpu::Pinned_buffer h_raw, h_out;
-		int ch = 0;
-		struct Shape { int nb_samples, sample_rate; int64_t pts; decltype(Frame_data::time_base) time_base; };
-		std::deque<Shape> shapes;     // the input frames whose output is still owed
+		Intake in;
 		std::vector<float> ready;     // processed samples behind the discarded ones, interleaved, not yet cut into frames
 		size_t ready_pos = 0;         // frames of `ready` already delivered
-		std::shared_ptr<const Audio_frame> held;  // popped, but with another channel count than the batch in front of it
-		std::vector<std::shared_ptr<const Audio_frame>> pending;   // frames not yet put: they wait while the handle waits for `need` samples
-		size_t pending_samples = 0, need = 0;
 
 		// a failed GPU call is reported by its entry's name (ops.name + suffix), put together only when it failed
 		const auto check = [&](int rc, const char* suffix) { if (rc != NAE_OK) gpu::check(rc, (std::string(ops.name) + suffix).c_str()); };
@@ -67,77 +63,33 @@ namespace processor
 		{
 			const size_t avail = ops.available(h);
 			if (avail == 0) { gpu::wait(stop_token); return; }
-			float* dev = static_cast<float*>(d_out.reserve(avail * ch * sizeof(float)));
-			float* host = static_cast<float*>(h_out.reserve(avail * ch * sizeof(float)));
+			float* dev = static_cast<float*>(d_out.reserve(avail * in.ch * sizeof(float)));
+			float* host = static_cast<float*>(h_out.reserve(avail * in.ch * sizeof(float)));
 			size_t got = 0;
 			check(ops.receive(h, dev, avail, &got), "_receive");
-			gpu::check(nae_memcpy_d2h(ctx, host, dev, got * ch * sizeof(float)), "d2h");
+			gpu::check(nae_memcpy_d2h(ctx, host, dev, got * in.ch * sizeof(float)), "d2h");
 			gpu::wait(stop_token);
-			ready.erase(ready.begin(), ready.begin() + ready_pos * ch);
-			ready_pos = 0;
+			ready.erase(ready.begin(), ready.begin() + ready_pos * in.ch);
 			const size_t skip = std::min(to_discard, got);
 			to_discard -= skip;
-			ready.insert(ready.end(), host + skip * ch, host + got * ch);
-			while (!shapes.empty() && !stop_token && ready.size() / ch - ready_pos >= (size_t)shapes.front().nb_samples)
-			{
-				const Shape s = shapes.front();
-				shapes.pop_front();
-				auto out = std::make_shared<Audio_frame>();
-				Frame_data* o = out->data();
-				o->format = AV_SAMPLE_FMT_FLT;
-				o->sample_rate = s.sample_rate;
-				o->nb_samples = s.nb_samples;
-				o->ch_layout.nb_channels = ch;
-				o->time_base = s.time_base;
-				o->pts = s.pts;
-				frame_get_buffer(o, 32);
-				std::memcpy(o->data[0], ready.data() + ready_pos * ch, (size_t)s.nb_samples * ch * sizeof(float));
-				ready_pos += s.nb_samples;
-				for (auto& stream : output_stream)
-					while (!stop_token && stream->try_push(out) != channel_op_status::success) nae_fiber::this_fiber::yield();
-			}
+			ready.insert(ready.end(), host + skip * in.ch, host + got * in.ch);
+			ready_pos = cut_and_push(in.shapes, ready.data(), ready.size() / in.ch, in.ch, output_stream, stop_token);
 		};
 
 		while (!stop_token)
 		{
-			bool ended = false;
-			const std::vector<std::shared_ptr<const Audio_frame>> batch = collect_batch(input_stream, held, &ended);
-			if (batch.empty() && !ended)
-			{
-				nae_fiber::this_fiber::yield();
-				continue;
-			}
-			if (!batch.empty())
-			{
-				const Frame_data* frame = batch.front()->data();
-				if (ch == 0)
-				{
-					ch = frame->ch_layout.nb_channels;
-					if (ch != 1 && ch != 2) throw infra::Processor::Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
-					need = hold(frame);
-				}
-				else if (frame->ch_layout.nb_channels != ch)
-					throw infra::Processor::Runtime_error("Channel count changed", infra::fmt("The %s runs one stream of a fixed channel count.", noun),
-										infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, ch));
-				for (const auto& f : batch)
-				{
-					shapes.push_back({f->data()->nb_samples, f->data()->sample_rate, f->data()->pts, f->data()->time_base});
-					pending.push_back(f);
-					pending_samples += (size_t)f->data()->nb_samples;
-				}
-			}
-			const bool at_end = batch.empty() && ended;
-			if (!pending.empty() && (h != nullptr || pending_samples >= need || at_end))
+			if (!take_in(in, input_stream, noun, hold)) continue;
+			if (!in.pending.empty() && (h != nullptr || in.pending_samples >= in.need || in.at_end))
 			{
 				size_t total = 0;
-				float* samples = upload_as_f32(pending, h_raw, d_raw, d_f32, &total);
-				if (h == nullptr) h = create(ctx, pending.front()->data(), ch, samples, total);
+				float* samples = upload_as_f32(in.pending, h_raw, d_raw, d_f32, &total);
+				if (h == nullptr) h = create(ctx, in.pending.front()->data(), in.ch, samples, total);
 				check(ops.put(h, samples, total), "_put");
-				pending.clear();
-				pending_samples = 0;
+				in.pending.clear();
+				in.pending_samples = 0;
 				deliver();
 			}
-			if (at_end)
+			if (in.at_end)
 			{
 				if (h != nullptr)
 				{
@@ -154,7 +106,7 @@ namespace processor
 	// a handle made from the first frame alone: nothing is held
 	template <class Handle, class Create>
 	static void run_on_handle(
-		Audio_stream& input_stream, const std::set<std::shared_ptr<Audio_stream>>& output_stream, const std::atomic<bool>& stop_token,
+		Audio_stream& input_stream, const Output_streams& output_stream, const std::atomic<bool>& stop_token,
 		const std::type_identity_t<Handle_ops<Handle>>& ops, const char* noun, size_t to_discard, const Create& create
 	)
 	{
@@ -209,16 +161,9 @@ namespace processor
 			return value[key].asFloat();
 		};
 		const float lo = hertz("f_lo", default_f_lo), hi = hertz("f_hi", default_f_hi);
-		const auto integer = [&](const char* key, int fallback) {
-			if (!value.isMember(key)) return fallback;
-			const Json::Value& v = value[key];
-			// compared as a double with the range first: a number outside int's range is never converted
-			if (!v.isDouble() || !(v.asDouble() >= 1.0 && v.asDouble() <= 4096.0) || v.asDouble() != (double)v.asInt()) throw wrong(key);
-			return v.asInt();
-		};
-		const int n_taps = integer("taps", default_taps);
+		const int n_taps = int_from_json(value, "Audio_filter", "taps", 1, 4096, default_taps);
 		if (n_taps > max_taps || (n_taps & 1) == 0) throw wrong("taps");
-		const int n_fft = integer("fft_size", 0);
+		const int n_fft = int_from_json(value, "Audio_filter", "fft_size", 1, 4096, 0);
 		if (value.isMember("fft_size") && (nae_fir_pick_n_fft(n_fft / 2 + 1) != n_fft || n_taps > n_fft / 2 + 1)) throw wrong("fft_size");
 		kind = k;
 		f_lo = lo;
@@ -233,14 +178,11 @@ namespace processor
 		const std::atomic<bool>& stop_token, std::any&
 	)
 	{
-		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
-		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
-		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
-		if (!input_item.has_value())
-			throw Runtime_error("Audio Filter has no input", "Audio Filter requires an audio stream input to function properly.", "Input item 'input' not found");
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Filter");
 		// the group delay is dropped in front; the tail makes up for it: (L - 1) / 2 of the L - 1 flushed frames complete the frames still owed
 		run_on_handle<nae_fir>(
-			input_item.value().get(), output_stream, stop_token,
+			io.input, io.output, stop_token,
 			{"nae_fir", nae_fir_put, nae_fir_flush, nae_fir_available, nae_fir_receive, nae_fir_destroy}, "filter", (size_t)(taps - 1) / 2,
 			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
 			{
@@ -293,14 +235,8 @@ namespace processor
 			if (!v.isDouble() || !(v.asDouble() >= 0.0 && v.asDouble() < 9007199254740992.0) || v.asDouble() != (double)(uint64_t)v.asDouble()) throw wrong("seed");
 			sd = (uint64_t)v.asDouble();
 		}
-		int n_fft = 0;
-		if (value.isMember("fft_size"))
-		{
-			const Json::Value& v = value["fft_size"];
-			if (!v.isDouble() || !(v.asDouble() >= 1.0 && v.asDouble() <= 4096.0) || v.asDouble() != (double)v.asInt()) throw wrong("fft_size");
-			n_fft = v.asInt();
-			if (nae_fir_pick_n_fft(n_fft / 2 + 1) != n_fft) throw wrong("fft_size");   // the filter's sizes: 512, 1024, 2048, 4096
-		}
+		const int n_fft = int_from_json(value, "Audio_reverb", "fft_size", 1, 4096, 0);
+		if (value.isMember("fft_size") && nae_fir_pick_n_fft(n_fft / 2 + 1) != n_fft) throw wrong("fft_size");   // the filter's sizes: 512, 1024, 2048, 4096
 		rt60 = r;
 		predelay_ms = p;
 		wet = w;
@@ -315,14 +251,11 @@ namespace processor
 		const std::atomic<bool>& stop_token, std::any&
 	)
 	{
-		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
-		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
-		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
-		if (!input_item.has_value())
-			throw Runtime_error("Audio Reverb has no input", "Audio Reverb requires an audio stream input to function properly.", "Input item 'input' not found");
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Reverb");
 		// the last partial block comes out with the flush; the frames still owed are cut from it and the tail behind them is dropped
 		run_on_handle<nae_conv>(
-			input_item.value().get(), output_stream, stop_token,
+			io.input, io.output, stop_token,
 			{"nae_conv", nae_conv_put, nae_conv_flush, nae_conv_available, nae_conv_receive, nae_conv_destroy}, "reverb", 0,
 			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
 			{
@@ -412,32 +345,15 @@ namespace processor
 		const std::atomic<bool>& stop_token, std::any&
 	)
 	{
-		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
-		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
-		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
-		if (!input_item.has_value())
-			throw Runtime_error("Audio Equalizer has no input", "Audio Equalizer requires an audio stream input to function properly.", "Input item 'input' not found");
-		Audio_stream& input_stream = input_item.value().get();
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Equalizer");
 		if (bands.empty())
 		{
-			// a wire: the frames pass as they are
-			while (!stop_token)
-			{
-				const auto pop_result = input_stream.try_pop();
-				if (!pop_result.has_value())
-				{
-					if (input_stream.eof()) break;
-					nae_fiber::this_fiber::yield();
-					continue;
-				}
-				for (auto& stream : output_stream)
-					while (!stop_token && stream->try_push(pop_result.value()) != channel_op_status::success) nae_fiber::this_fiber::yield();
-			}
-			for (auto& stream : output_stream) stream->set_eof();
+			pass_through(io.input, io.output, stop_token);
 			return;
 		}
 		run_on_handle<nae_eq>(
-			input_stream, output_stream, stop_token, {"nae_eq", nae_eq_put, nae_eq_flush, nae_eq_available, nae_eq_receive, nae_eq_destroy}, "node", 0,
+			io.input, io.output, stop_token, {"nae_eq", nae_eq_put, nae_eq_flush, nae_eq_available, nae_eq_receive, nae_eq_destroy}, "node", 0,
 			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
 			{
 				std::vector<double> coef(bands.size() * 5);
@@ -513,14 +429,10 @@ namespace processor
 		const std::atomic<bool>& stop_token, std::any&
 	)
 	{
-		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
-		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
-		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
-		if (!input_item.has_value())
-			throw Runtime_error("Audio Dynamics has no input", "Audio Dynamics requires an audio stream input to function properly.", "Input item 'input' not found");
-		Audio_stream& input_stream = input_item.value().get();
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Dynamics");
 		run_on_handle<nae_dyn>(
-			input_stream, output_stream, stop_token, {"nae_dyn", nae_dyn_put, nae_dyn_flush, nae_dyn_available, nae_dyn_receive, nae_dyn_destroy}, "node", 0,
+			io.input, io.output, stop_token, {"nae_dyn", nae_dyn_put, nae_dyn_flush, nae_dyn_available, nae_dyn_receive, nae_dyn_destroy}, "node", 0,
 			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
 			{
 				nae_dyn_params params;
@@ -566,19 +478,12 @@ namespace processor
 		const auto wrong = [](const char* field) { return wrong_field("Audio_denoise", field); };
 		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
 		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_denoise", key, lo, hi, fallback); };
-		const auto integer = [&](const char* key, int lo, int hi, int fallback) {
-			if (!value.isMember(key)) return fallback;
-			const Json::Value& v = value[key];
-			// compared as a double with the range first: a number outside int's range is never converted
-			if (!v.isDouble() || !(v.asDouble() >= (double)lo && v.asDouble() <= (double)hi) || v.asDouble() != (double)v.asInt()) throw wrong(key);
-			return v.asInt();
-		};
 		const double r = real("reduction_db", 0.0, NAE_DENOISE_MAX_REDUCTION_DB, default_reduction_db);
 		const double s = real("sensitivity_db", NAE_DENOISE_MIN_SENSITIVITY_DB, NAE_DENOISE_MAX_SENSITIVITY_DB, default_sensitivity_db);
-		const int n = integer("fft_size", 512, 4096, default_fft_size);
+		const int n = int_from_json(value, "Audio_denoise", "fft_size", 512, 4096, default_fft_size);
 		if (n != 512 && n != 1024 && n != 2048 && n != 4096) throw wrong("fft_size");
-		const int tn = integer("time_smooth", 0, NAE_DENOISE_MAX_TIME, default_time_smooth);
-		const int fn = integer("freq_smooth", 0, NAE_DENOISE_MAX_FREQ, default_freq_smooth);
+		const int tn = int_from_json(value, "Audio_denoise", "time_smooth", 0, NAE_DENOISE_MAX_TIME, default_time_smooth);
+		const int fn = int_from_json(value, "Audio_denoise", "freq_smooth", 0, NAE_DENOISE_MAX_FREQ, default_freq_smooth);
 		const double ps = real("profile_start_ms", 0.0, 60000.0, default_profile_start_ms);
 		const double pm = real("profile_ms", 20.0, 10000.0, default_profile_ms);
 		reduction_db = r; sensitivity_db = s; fft_size = n; time_smooth = tn; freq_smooth = fn; profile_start_ms = ps; profile_ms = pm;
@@ -590,12 +495,8 @@ namespace processor
 		const std::atomic<bool>& stop_token, std::any&
 	)
 	{
-		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
-		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
-		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
-		if (!input_item.has_value())
-			throw Runtime_error("Audio Noise Reduction has no input", "Audio Noise Reduction requires an audio stream input to function properly.", "Input item 'input' not found");
-		Audio_stream& input_stream = input_item.value().get();
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Noise Reduction");
 		gpu::Device_buffer d_profile;   // the learned profile: the handle copies it on the stream, so it stays until the node ends
 		// the stretch the node learns from, in samples at the stream's rate
 		const auto stretch = [&](const Frame_data* frame, size_t* start) {
@@ -603,7 +504,7 @@ namespace processor
 			return (size_t)std::llround(profile_ms / 1000.0 * frame->sample_rate);
 		};
 		run_on_handle_held<nae_denoise>(
-			input_stream, output_stream, stop_token,
+			io.input, io.output, stop_token,
 			{"nae_denoise", nae_denoise_put, nae_denoise_flush, nae_denoise_available, nae_denoise_receive, nae_denoise_destroy}, "node", 0,
 			[&](const Frame_data* frame)
 			{
@@ -670,62 +571,32 @@ namespace processor
 		// this node's context (own stream) is made when the first gating block has arrived: a shorter stream never touches the GPU.  First
 		// local, destroyed last — after the handle guard and the buffers
 		std::optional<gpu::Node> node;
-		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
-		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
-		if (!input_item.has_value())
-			throw Runtime_error("Audio Loudness has no input", "Audio Loudness requires an audio stream input to function properly.", "Input item 'input' not found");
-		Audio_stream& input_stream = input_item.value().get();
+		const Node_streams io = node_streams(input, output, "Audio Loudness");
 		nae_loud* h = nullptr;
 		struct Guard { nae_loud*& h; ~Guard() { if (h) nae_loud_destroy(h); } } guard{h};
 		struct Buffers { gpu::Device_buffer d_raw, d_f32; gpu::Pinned_buffer h_raw, h_f32; };
 		std::optional<Buffers> buf;
-		int ch = 0;
-		struct Shape { int nb_samples, sample_rate; int64_t pts; decltype(Frame_data::time_base) time_base; };
-		std::vector<Shape> shapes;                                  // every frame received
-		std::vector<float> kept;                                    // their samples as interleaved f32, from the first put on
-		std::vector<std::shared_ptr<const Audio_frame>> pending;    // frames not yet put: they wait for the first 400 ms
-		size_t pending_samples = 0;
-		std::shared_ptr<const Audio_frame> held;
-		const auto push = [&](const std::shared_ptr<const Audio_frame>& frame) {
-			for (auto& stream : output_stream)
-				while (!stop_token && stream->try_push(frame) != channel_op_status::success) nae_fiber::this_fiber::yield();
+		Intake in;                  // its shapes are every frame received: nothing leaves before the end
+		std::vector<float> kept;    // their samples as interleaved f32, from the first put on
+		// the frames wait for one gating block: NAE_LOUD_BLOCK_SUBS sub-blocks of 1 / NAE_LOUD_SUBS_PER_S seconds, rounded up to whole samples
+		const auto gating_block = [](const Frame_data* frame) {
+			const size_t per_s = (size_t)NAE_LOUD_BLOCK_SUBS * frame->sample_rate;
+			return per_s / NAE_LOUD_SUBS_PER_S + (per_s % NAE_LOUD_SUBS_PER_S != 0);
 		};
 
 		while (!stop_token)
 		{
-			bool ended = false;
-			const std::vector<std::shared_ptr<const Audio_frame>> batch = collect_batch(input_stream, held, &ended);
-			if (batch.empty() && !ended)
-			{
-				nae_fiber::this_fiber::yield();
-				continue;
-			}
-			for (const auto& f : batch)
-			{
-				const Frame_data* frame = f->data();
-				if (ch == 0)
-				{
-					ch = frame->ch_layout.nb_channels;
-					if (ch != 1 && ch != 2) throw Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", ch));
-				}
-				else if (frame->ch_layout.nb_channels != ch)
-					throw Runtime_error("Channel count changed", "The node runs one stream of a fixed channel count.",
-										infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, ch));
-				// one gain from one meter: the K-weighting and the sub-block are the first frame's rate's
-				if (!shapes.empty() && frame->sample_rate != shapes.front().sample_rate)
+			if (!take_in(in, io.input, "node", gating_block)) continue;
+			// one gain from one meter: the K-weighting and the sub-block are the first frame's rate's
+			for (const auto& f : in.pending)
+				if (f->data()->sample_rate != in.shapes.front().sample_rate)
 					throw Runtime_error("Sample rate changed", "The node runs one stream of a fixed sample rate.",
-										infra::fmt("Got %d Hz after %d Hz", frame->sample_rate, shapes.front().sample_rate));
-				shapes.push_back({frame->nb_samples, frame->sample_rate, frame->pts, frame->time_base});
-				pending.push_back(f);
-				pending_samples += (size_t)frame->nb_samples;
-			}
-			// one gating block: NAE_LOUD_BLOCK_SUBS sub-blocks of 1 / NAE_LOUD_SUBS_PER_S seconds
-			const bool block_there = !pending.empty() && pending_samples * NAE_LOUD_SUBS_PER_S >= (size_t)NAE_LOUD_BLOCK_SUBS * pending.front()->data()->sample_rate;
-			if (!pending.empty() && (h != nullptr || block_there))
+										infra::fmt("Got %d Hz after %d Hz", f->data()->sample_rate, in.shapes.front().sample_rate));
+			if (!in.pending.empty() && (h != nullptr || in.pending_samples >= in.need))
 			{
 				if (h == nullptr)
 				{
-					const int sample_rate = pending.front()->data()->sample_rate;
+					const int sample_rate = in.shapes.front().sample_rate;
 					nae_loud_params params;
 					const int rc = nae_loud_design(sample_rate, target_lufs, true_peak_db, max_gain_db, &params);
 					if (rc == NAE_ERR_UNSUPPORTED)
@@ -736,71 +607,53 @@ namespace processor
 											infra::fmt("nae_loud_design at %d Hz: code %d", sample_rate, rc));
 					node.emplace();
 					buf.emplace();
-					gpu::check(nae_loud_create(node->ctx(), &params, ch, &h), "nae_loud_create");
+					gpu::check(nae_loud_create(node->ctx(), &params, in.ch, &h), "nae_loud_create");
 				}
 				size_t total = 0;
-				float* samples = upload_as_f32(pending, buf->h_raw, buf->d_raw, buf->d_f32, &total);
+				float* samples = upload_as_f32(in.pending, buf->h_raw, buf->d_raw, buf->d_f32, &total);
 				gpu::check(nae_loud_put(h, samples, total), "nae_loud_put");
 				// the node keeps the f32 samples the meter saw.  Packed float frames (and mono planar ones) already are those samples; integer
 				// and planar stereo frames were converted on the device and come back from there.  Either way the batch is waited for: the
 				// staging buffers are reused by the next one
 				bool wire = true;
-				for (const auto& f : pending)
-					wire = wire && (f->data()->format == AV_SAMPLE_FMT_FLT || (f->data()->format == AV_SAMPLE_FMT_FLTP && ch == 1));
+				for (const auto& f : in.pending)
+					wire = wire && (f->data()->format == AV_SAMPLE_FMT_FLT || (f->data()->format == AV_SAMPLE_FMT_FLTP && in.ch == 1));
 				if (wire)
 				{
 					gpu::wait(stop_token);
-					for (const auto& f : pending)
+					for (const auto& f : in.pending)
 					{
 						const float* data = reinterpret_cast<const float*>(f->data()->data[0]);
-						kept.insert(kept.end(), data, data + (size_t)f->data()->nb_samples * ch);
+						kept.insert(kept.end(), data, data + (size_t)f->data()->nb_samples * in.ch);
 					}
 				}
 				else
 				{
-					float* host = static_cast<float*>(buf->h_f32.reserve(total * ch * sizeof(float)));
-					gpu::check(nae_memcpy_d2h(node->ctx(), host, samples, total * ch * sizeof(float)), "d2h");
+					float* host = static_cast<float*>(buf->h_f32.reserve(total * in.ch * sizeof(float)));
+					gpu::check(nae_memcpy_d2h(node->ctx(), host, samples, total * in.ch * sizeof(float)), "d2h");
 					gpu::wait(stop_token);
-					kept.insert(kept.end(), host, host + total * ch);
+					kept.insert(kept.end(), host, host + total * in.ch);
 				}
-				pending.clear();
-				pending_samples = 0;
+				in.pending.clear();
+				in.pending_samples = 0;
 			}
-			if (batch.empty() && ended)
+			if (in.at_end)
 			{
 				if (h == nullptr)
 				{
 					// under 400 ms: no gating block, no loudness — the frames pass as they are
-					for (const auto& f : pending) push(f);
+					for (const auto& f : in.pending) push_to_all(io.output, f, stop_token);
 					break;
 				}
 				gpu::check(nae_loud_flush(h), "nae_loud_flush");
 				gpu::wait(stop_token);
 				nae_loud_result result;
 				gpu::check(nae_loud_get_result(h, &result), "nae_loud_get_result");
-				const float gain = result.gain_f32;
-				size_t pos = 0;
-				for (const Shape& s : shapes)
-				{
-					if (stop_token) break;
-					auto out = std::make_shared<Audio_frame>();
-					Frame_data* o = out->data();
-					o->format = AV_SAMPLE_FMT_FLT;
-					o->sample_rate = s.sample_rate;
-					o->nb_samples = s.nb_samples;
-					o->ch_layout.nb_channels = ch;
-					o->time_base = s.time_base;
-					o->pts = s.pts;
-					frame_get_buffer(o, 32);
-					float* dst = reinterpret_cast<float*>(o->data[0]);
-					const size_t n = (size_t)s.nb_samples * ch;
-					for (size_t i = 0; i < n; i++) dst[i] = kept[pos + i] * gain;   // one f32 product, as loud_apply_kernel's
-					pos += n;
-					push(out);
-				}
+				for (float& v : kept) v *= result.gain_f32;   // one f32 product, as loud_apply_kernel's
+				cut_and_push(in.shapes, kept.data(), kept.size() / in.ch, in.ch, io.output, stop_token);
 				break;
 			}
 		}
-		for (auto& stream : output_stream) stream->set_eof();
+		for (auto& stream : io.output) stream->set_eof();
 	}
 }

@@ -4,7 +4,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 namespace processor
 {
@@ -67,17 +66,7 @@ namespace processor
 		std::shared_ptr<Audio_frame> construct_audio_frame_float(const float* samples, size_t n_frames, int sample_rate,
 																 int channel_count, float time_us)
 		{
-			auto new_frame = std::make_shared<Audio_frame>();
-			Frame_data* frame = new_frame->data();
-			frame->sample_rate = sample_rate;
-			frame->ch_layout.nb_channels = channel_count;
-			frame->nb_samples = static_cast<int>(n_frames);
-			frame->format = AV_SAMPLE_FMT_FLT;
-			frame->time_base = {1, 1000000};
-			frame->pts = static_cast<int64_t>(time_us);
-			frame_get_buffer(frame, 32);
-			std::memcpy(frame->data[0], samples, n_frames * channel_count * sizeof(float));
-			return new_frame;
+			return make_f32_frame(samples, static_cast<int>(n_frames), channel_count, sample_rate, static_cast<int64_t>(time_us), {1, 1000000});
 		}
 
 		// the object soundtouch_process_payload talks to: the phase-vocoder handle (default) or the
@@ -134,22 +123,14 @@ namespace processor
 			Batch_stats& batch_stats
 		)
 		{
-			gpu::Node node;  // this node's context (own stream; device: gpu::pick_device): first local, destroyed last
+			gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
 			batch_stats = {};
-			const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
-			const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
-			if (!input_item.has_value())
-				throw infra::Processor::Runtime_error(
-					processor_name + " has no input",
-					processor_name + " requires an audio stream input to function properly.",
-					"Input item 'input' not found"
-				);
-			Audio_stream& input_stream = input_item.value().get();
+			const Node_streams io = node_streams(input, output, processor_name);
 			Stretcher soundtouch;
 			gpu::Device_buffer d_raw, d_f32, d_out;
 			gpu::Pinned_buffer h_raw, h_out;
 			bool input_stream_eof = false, pending_put = false;
-			std::shared_ptr<const Audio_frame> held;  // popped, but with another channel count than the batch in front of it
+			Frame_ptr held;  // popped, but with another channel count than the batch in front of it
 			int channel_count = 0, sample_rate = 0;
 			double time_seconds = 0.0;
 
@@ -178,12 +159,7 @@ namespace processor
 					auto new_frame = construct_audio_frame_float(host + pos * channel_count, n, sample_rate, channel_count, (float)(time_seconds * 1000000));
 					time_seconds += double(n) / sample_rate;
 					pos += n;
-					for (auto& stream : output_stream)
-						while (!stop_token)
-						{
-							if (stream->try_push(new_frame) == channel_op_status::success) break;
-							nae_fiber::this_fiber::yield();
-						}
+					push_to_all(io.output, new_frame, stop_token);
 				}
 			};
 
@@ -194,30 +170,7 @@ namespace processor
 					// Batching: the reference puts one frame per round; here every frame that is already waiting
 					// (at most 16) is uploaded, converted and put as ONE block behind one wait.  The handle's output does not
 					// depend on how its input is cut into puts (tests/test_gpu_stft.py, test_gpu_wsola.py: chunking invariance).
-					constexpr size_t max_batch = 16;
-					std::vector<std::shared_ptr<const Audio_frame>> batch;
-					if (held) batch.push_back(std::move(held));
-					held.reset();
-					while (batch.size() < max_batch && !input_stream_eof)
-					{
-						const auto pop_result = input_stream.try_pop();
-						if (!pop_result.has_value())
-						{
-							if (pop_result.error() != channel_op_status::empty)
-								throw infra::Processor::Runtime_error(
-									"Unexpected error when fetching audio frame", processor_name + " encountered an unexpected error.",
-									infra::fmt("Channel fetch error: %d", (int)pop_result.error())
-								);
-							if (input_stream.eof()) input_stream_eof = true;
-							break;
-						}
-						if (!batch.empty() && pop_result.value()->data()->ch_layout.nb_channels != batch.front()->data()->ch_layout.nb_channels)
-						{
-							held = pop_result.value();
-							break;
-						}
-						batch.push_back(pop_result.value());
-					}
+					const std::vector<Frame_ptr> batch = collect_batch(io.input, held, &input_stream_eof);
 					if (!batch.empty())
 					{
 						constexpr size_t max_queued_samples = 65536;
@@ -280,7 +233,7 @@ namespace processor
 					break;
 				nae_fiber::this_fiber::yield();
 			}
-			for (auto& stream : output_stream) stream->set_eof();
+			for (auto& stream : io.output) stream->set_eof();
 		}
 	}
 
@@ -388,13 +341,9 @@ namespace processor
 	void Audio_spectrum::deserialize(const Json::Value& value)
 	{
 		const auto wrong = [](const char* field) { return wrong_field("Audio_spectrum", field); };
-		const auto integer = [&](const char* key, int fallback) {
-			if (!value.isMember(key)) return fallback;  // no key: the default (a project saved before the key existed)
-			const Json::Value& v = value[key];
-			if (!v.isDouble() || v.asDouble() != (double)v.asInt()) throw wrong(key);
-			return v.asInt();
-		};
-		const int n = integer("fft_size", default_fft_size), h = integer("hop", default_hop);
+		// no key: the default (a project saved before the key existed).  The ranges are the widest nae_spectrum_frames_ex accepts anything in
+		const int n = int_from_json(value, "Audio_spectrum", "fft_size", 256, 4096, default_fft_size);
+		const int h = int_from_json(value, "Audio_spectrum", "hop", 1, 4096, default_hop);
 		if (nae_spectrum_frames_ex((size_t)n, n, 1) == 0) throw wrong("fft_size");
 		if (nae_spectrum_frames_ex((size_t)n, n, h) == 0) throw wrong("hop");
 		fft_size = n;
@@ -407,12 +356,8 @@ namespace processor
 		const std::atomic<bool>& stop_token, std::any&
 	)
 	{
-		gpu::Node node;  // this node's context (own stream): first local, destroyed last — before the handle guard and the buffers
-		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
-		const auto output_stream = infra::get_output_item<Audio_stream>(output, "output");
-		if (!input_item.has_value())
-			throw Runtime_error("FFT Spectrum has no input", "FFT Spectrum requires an audio stream input to function properly.", "Input item 'input' not found");
-		Audio_stream& input_stream = input_item.value().get();
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "FFT Spectrum");
 		nae_ctx* ctx = gpu::context();
 		last_context = ctx;
 		nae_spectrum* spectrum = nullptr;
@@ -421,12 +366,12 @@ namespace processor
 		gpu::Pinned_buffer h_raw, h_out;
 		int ch = 0, sample_rate = 0;
 		double time_seconds = 0.0;
-		std::shared_ptr<const Audio_frame> held;  // popped, but with another channel count than the batch in front of it
+		Frame_ptr held;  // popped, but with another channel count than the batch in front of it
 
 		while (!stop_token)
 		{
 			bool ended = false;
-			const std::vector<std::shared_ptr<const Audio_frame>> batch = collect_batch(input_stream, held, &ended);
+			const std::vector<Frame_ptr> batch = collect_batch(io.input, held, &ended);
 			if (batch.empty())
 			{
 				if (ended) break;  // a trailing partial window produces no frame
@@ -457,21 +402,10 @@ namespace processor
 			gpu::wait(stop_token);
 			for (size_t f = 0; f < got && !stop_token; f++)
 			{
-				auto out = std::make_shared<Audio_frame>();
-				Frame_data* o = out->data();
-				o->format = AV_SAMPLE_FMT_FLTP;
-				o->sample_rate = sample_rate;
-				o->nb_samples = bins;
-				o->ch_layout.nb_channels = ch;
-				o->time_base = {1, 1000000};
-				o->pts = (int64_t)(time_seconds * 1000000);
-				frame_get_buffer(o, 32);
-				for (int c = 0; c < ch; c++) std::memcpy(o->data[c], host + (f * ch + c) * bins, bins * sizeof(float));
+				push_to_all(io.output, make_f32_frame(host + f * rec, bins, ch, sample_rate, (int64_t)(time_seconds * 1000000), {1, 1000000}, true), stop_token);
 				time_seconds += (double)hop / sample_rate;
-				for (auto& stream : output_stream)
-					while (!stop_token && stream->try_push(out) != channel_op_status::success) nae_fiber::this_fiber::yield();
 			}
 		}
-		for (auto& stream : output_stream) stream->set_eof();
+		for (auto& stream : io.output) stream->set_eof();
 	}
 }

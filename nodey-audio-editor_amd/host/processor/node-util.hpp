@@ -1,21 +1,41 @@
-// processor/node-util.hpp — what the nodes of audio-velocity.cpp and audio-effects.cpp share (not part of the plugin interface): the pins, the
-// JSON field readers and their error, the collection of a batch of waiting frames and its upload as interleaved f32.
+// processor/node-util.hpp — what the nodes of audio-velocity.cpp and audio-effects.cpp share (not part of the plugin interface), each piece
+// written once: the pins and the node's streams (node_streams, with the "has no input" error), the JSON field readers and their error, the way
+// out (push_to_all, make_f32_frame, pass_through), the collection of a batch of waiting frames and its upload as interleaved f32, and the two
+// ends of a node that sits on a handle: take_in (frames in, held until enough have come) and cut_and_push (f32 out, as frames of the input's shapes).
 #pragma once
 #include "audio-stream.hpp"
 #include "gpu-context.hpp"
 
 #include <cstring>
+#include <deque>
 #include <string>
 #include <vector>
 
 namespace processor::detail
 {
+	using Frame_ptr = std::shared_ptr<const Audio_frame>;
+	using Output_streams = std::set<std::shared_ptr<Audio_stream>>;
+	using Time_base = decltype(Frame_data::time_base);
+
 	inline std::vector<infra::Processor::Pin_attribute> io_pins()
 	{
 		return {
 			{"output", "Output", typeid(Audio_stream), false, [] { return std::make_shared<Audio_stream>(); }},
 			{"input", "Input", typeid(Audio_stream), true, [] { return std::make_shared<Audio_stream>(); }}
 		};
+	}
+
+	// the stream on the node's "input" pin and every stream on its "output" pin; a node without an input is the user's error, under its display name
+	struct Node_streams { Audio_stream& input; Output_streams output; };
+	inline Node_streams node_streams(const infra::Processor::Input_map& input, const infra::Processor::Output_map& output, const std::string& display_name)
+	{
+		const auto input_item = infra::get_input_item<Audio_stream>(input, "input");
+		Output_streams output_stream = infra::get_output_item<Audio_stream>(output, "output");
+		if (!input_item.has_value())
+			throw infra::Processor::Runtime_error(
+				display_name + " has no input", display_name + " requires an audio stream input to function properly.", "Input item 'input' not found"
+			);
+		return {input_item.value().get(), std::move(output_stream)};
 	}
 
 	// the error of a JSON field of the wrong type or outside its range
@@ -44,13 +64,61 @@ namespace processor::detail
 		return value[key].asDouble();
 	}
 
+	// an optional integer in [lo, hi]: no key is the fallback.  Compared as a double with the range first: a number outside int's range is never
+	// converted
+	inline int int_from_json(const Json::Value& value, const char* node_name, const char* key, int lo, int hi, int fallback)
+	{
+		if (!value.isMember(key)) return fallback;
+		const Json::Value& v = value[key];
+		if (!v.isDouble() || !(v.asDouble() >= (double)lo && v.asDouble() <= (double)hi) || v.asDouble() != (double)v.asInt()) throw wrong_field(node_name, key);
+		return v.asInt();
+	}
+
+	// the frame goes to every output stream; a full stream is waited for, yielding, unless the run is stopped
+	inline void push_to_all(const Output_streams& output_stream, const Frame_ptr& frame, const std::atomic<bool>& stop_token)
+	{
+		for (auto& stream : output_stream)
+			while (!stop_token && stream->try_push(frame) != channel_op_status::success) nae_fiber::this_fiber::yield();
+	}
+
+	// a float frame of n samples of ch channels: packed (AV_SAMPLE_FMT_FLT) from interleaved samples, or planar (AV_SAMPLE_FMT_FLTP) from ch planes
+	// of n floats back to back
+	inline std::shared_ptr<Audio_frame> make_f32_frame(const float* samples, int n, int ch, int sample_rate, int64_t pts, Time_base time_base, bool planar = false)
+	{
+		auto out = std::make_shared<Audio_frame>();
+		Frame_data* o = out->data();
+		o->format = planar ? AV_SAMPLE_FMT_FLTP : AV_SAMPLE_FMT_FLT;
+		o->sample_rate = sample_rate;
+		o->nb_samples = n;
+		o->ch_layout.nb_channels = ch;
+		o->time_base = time_base;
+		o->pts = pts;
+		frame_get_buffer(o, 32);
+		const int planes = planar ? ch : 1;
+		for (int p = 0; p < planes; p++) std::memcpy(o->data[p], samples + (size_t)p * n, (size_t)n * (ch / planes) * sizeof(float));
+		return out;
+	}
+
+	// a wire: the frames pass as they are, then the end of the stream
+	inline void pass_through(Audio_stream& input_stream, const Output_streams& output_stream, const std::atomic<bool>& stop_token)
+	{
+		while (!stop_token)
+		{
+			const auto pop_result = input_stream.try_pop();
+			if (pop_result.has_value()) push_to_all(output_stream, pop_result.value(), stop_token);
+			else if (input_stream.eof()) break;
+			else nae_fiber::this_fiber::yield();
+		}
+		for (auto& stream : output_stream) stream->set_eof();
+	}
+
 	// Every frame that is already waiting, at most 16: a node uploads and puts them as ONE block behind one wait (a handle's output does not
 	// depend on how its input is cut into puts).  A frame of another channel count than the batch in front of it is held back for the next
 	// call.  *ended: the stream had nothing more and is at its end.
-	inline std::vector<std::shared_ptr<const Audio_frame>> collect_batch(Audio_stream& input_stream, std::shared_ptr<const Audio_frame>& held, bool* ended)
+	inline std::vector<Frame_ptr> collect_batch(Audio_stream& input_stream, Frame_ptr& held, bool* ended)
 	{
 		constexpr size_t max_batch = 16;
-		std::vector<std::shared_ptr<const Audio_frame>> batch;
+		std::vector<Frame_ptr> batch;
 		if (held) batch.push_back(std::move(held));
 		held.reset();
 		*ended = false;
@@ -78,7 +146,7 @@ namespace processor::detail
 	//   * a run of planar stereo float frames of equal length is interleaved by ONE strided launch (frames as "streams");
 	//   * integer formats: nae_to_f32_interleaved per frame (the reference's literal divisors).
 	// Everything is queued on the stream.  All frames have the channel count of the first.
-	inline float* upload_as_f32(const std::vector<std::shared_ptr<const Audio_frame>>& frames, gpu::Pinned_buffer& h_raw, gpu::Device_buffer& d_raw,
+	inline float* upload_as_f32(const std::vector<Frame_ptr>& frames, gpu::Pinned_buffer& h_raw, gpu::Device_buffer& d_raw,
 						 gpu::Device_buffer& d_f32, size_t* total_samples)
 	{
 		nae_ctx* ctx = gpu::context();
@@ -163,5 +231,68 @@ namespace processor::detail
 			}
 		}
 		return out;
+	}
+
+	// The intake of a node that sits on a handle.  The frames of one stream of a fixed channel count come in by batches and wait in `pending`
+	// until the node puts them: at once when its handle exists, else when `need` samples have arrived (hold(first frame) says how many the
+	// handle is made from) or the stream has ended.  Every frame taken in leaves its shape behind: the output is cut into frames of these.
+	struct Shape { int nb_samples, sample_rate; int64_t pts; Time_base time_base; };
+	struct Intake
+	{
+		int ch = 0;                       // the stream's channel count: the first frame's
+		std::deque<Shape> shapes;         // the frames taken in whose output is still owed
+		std::vector<Frame_ptr> pending;   // frames not yet put
+		size_t pending_samples = 0, need = 0;
+		bool at_end = false;              // nothing waited and the stream is at its end
+		Frame_ptr held;                   // popped, but with another channel count than the batch in front of it
+	};
+
+	// One turn of the intake.  false: nothing waited and the stream goes on — the fiber has yielded, the caller comes again.  `noun` is the
+	// node's word for itself in the "Channel count changed" error.
+	template <class Hold>
+	bool take_in(Intake& in, Audio_stream& input_stream, const char* noun, const Hold& hold)
+	{
+		bool ended = false;
+		const std::vector<Frame_ptr> batch = collect_batch(input_stream, in.held, &ended);
+		in.at_end = batch.empty() && ended;
+		if (batch.empty() && !ended)
+		{
+			nae_fiber::this_fiber::yield();
+			return false;
+		}
+		if (batch.empty()) return true;
+		const Frame_data* frame = batch.front()->data();
+		if (in.ch == 0)
+		{
+			in.ch = frame->ch_layout.nb_channels;
+			if (in.ch != 1 && in.ch != 2)
+				throw infra::Processor::Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels", in.ch));
+			in.need = hold(frame);
+		}
+		else if (frame->ch_layout.nb_channels != in.ch)
+			throw infra::Processor::Runtime_error("Channel count changed", infra::fmt("The %s runs one stream of a fixed channel count.", noun),
+												  infra::fmt("Got %d channels after %d", frame->ch_layout.nb_channels, in.ch));
+		for (const auto& f : batch)
+		{
+			in.shapes.push_back({f->data()->nb_samples, f->data()->sample_rate, f->data()->pts, f->data()->time_base});
+			in.pending.push_back(f);
+			in.pending_samples += (size_t)f->data()->nb_samples;
+		}
+		return true;
+	}
+
+	// The counterpart: n samples of interleaved f32 leave as packed float frames of the shapes at the front of the queue, as long as a whole
+	// frame is there -> the samples that left
+	inline size_t cut_and_push(std::deque<Shape>& shapes, const float* samples, size_t n, int ch, const Output_streams& output_stream, const std::atomic<bool>& stop_token)
+	{
+		size_t pos = 0;
+		while (!shapes.empty() && !stop_token && n - pos >= (size_t)shapes.front().nb_samples)
+		{
+			const Shape s = shapes.front();
+			shapes.pop_front();
+			push_to_all(output_stream, make_f32_frame(samples + pos * ch, s.nb_samples, ch, s.sample_rate, s.pts, s.time_base), stop_token);
+			pos += s.nb_samples;
+		}
+		return pos;
 	}
 }

@@ -3,6 +3,7 @@
 // JSON arrays of json_mini.hpp behave as JsonCpp's.  `registry`: no GPU — the processor map after the three existing registration calls and
 // after register_equalizer_processors().  `gpu`: a source -> audio_eq -> sink graph delivers the frames it received, with their sizes and pts,
 // and the samples of nae_eq_block_f32 with the designed coefficients, bit for bit.  `wire`: an empty "bands" delivers the input's bits.
+// `wire_s16`: no kernel runs — without bands a packed S16 stream arrives as it was sent, format, sizes, pts and words.
 // `nyquist`: a band at or above half the sample rate fails the run on the first frame.
 #include "../node_harness.hpp"
 #include "processor/audio-eq.hpp"
@@ -239,6 +240,33 @@ static void test_wire()
 	}
 }
 
+// the wire converts nothing: 2500 samples of packed S16 in frames of 1000 arrive as 1000 / 1000 / 500 of S16, pts and words unchanged
+static void test_wire_s16()
+{
+	const int S = 2500, frame_size = 1000;
+	const std::vector<float> x = uniform_noise((size_t)S * 2);
+	const std::vector<int16_t> sent = quantise_s16(x.data(), x.size());
+	std::shared_ptr<Sink> sink;
+	std::string error;
+	const bool ok = run_graph<Audio_eq>(x, Json::Value(), frame_size, sink, &error, 48000, AV_SAMPLE_FMT_S16);
+	CHECK(ok, "the wire runs: " << error);
+	if (!ok) return;
+	CHECK(sink->frames.size() == 3, "as many frames as the source sent: " << sink->frames.size());
+	const int sizes[] = {1000, 1000, 500};
+	size_t pos = 0;
+	for (size_t f = 0; f < sink->frames.size() && f < 3; f++)
+	{
+		const Frame_data* d = sink->frames[f]->data();
+		const int64_t want_pts = (int64_t)((0.5 + double(f * frame_size) / 48000) * 1000000);   // the source's own formula
+		const bool shape_ok = d->format == AV_SAMPLE_FMT_S16 && d->nb_samples == sizes[f] && d->ch_layout.nb_channels == 2 && d->sample_rate == 48000 &&
+							  d->pts == want_pts && d->time_base.num == 1 && d->time_base.den == 1000000;
+		CHECK(shape_ok, "frame " << f << ": S16, " << sizes[f] << " samples, the source's pts and time base");
+		if (!shape_ok) return;
+		CHECK(std::memcmp(d->data[0], sent.data() + pos * 2, (size_t)sizes[f] * 2 * sizeof(int16_t)) == 0, "frame " << f << ": the words the source sent");
+		pos += sizes[f];
+	}
+}
+
 static void test_nyquist()
 {
 	const std::vector<float> x = uniform_noise(4000);
@@ -252,5 +280,5 @@ static void test_nyquist()
 
 int main(int argc, char** argv)
 {
-	return harness_main(argc, argv, "EQ", {{"json", test_json}, {"registry", test_registry}, {"gpu", test_gpu}, {"wire", test_wire}, {"nyquist", test_nyquist}});
+	return harness_main(argc, argv, "EQ", {{"json", test_json}, {"registry", test_registry}, {"gpu", test_gpu}, {"wire", test_wire}, {"wire_s16", test_wire_s16}, {"nyquist", test_nyquist}});
 }

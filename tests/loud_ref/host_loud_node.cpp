@@ -3,7 +3,8 @@
 // `registry`: no GPU — the processor map after the six existing registration calls and after register_mastering_processors().
 // `short`: no GPU — a stream under 400 ms passes as it is, frame for frame.  `gpu`: a source -> audio_loudness -> sink graph with frames that
 // do not divide the stream delivers the frames it received, with their sizes and pts, and the samples of nae_loud_normalize_f32 on the whole
-// stream, bit for bit.
+// stream, bit for bit: from packed float, planar float and packed S16 stereo (the f32 signal the device makes of them), and from a mono
+// stream of exactly one gating block.
 #include "../node_harness.hpp"
 #include "processor/audio-loudness.hpp"
 #include "nae_dsp_spec.h"
@@ -106,31 +107,68 @@ static void test_short()
 	}
 }
 
-static void test_gpu()
+// the f32 signal the node sees of a packed S16 source: nae_to_f32_interleaved on the source's words, in a context of the harness's own
+static std::vector<float> s16_seen_as_f32(const std::vector<float>& x, int ch)
 {
-	// 30037 samples in frames of 1000: 30 whole frames and one of 37, none of them a multiple of a chunk or a sub-block; noise at -30 dB, so
-	// the default target asks for gain and the ceiling does not bind
-	const int S = 30037, frame_size = 1000;
-	std::vector<float> x = uniform_noise((size_t)S * 2);
-	for (size_t i = 0; i < x.size(); i++) x[i] *= (i & 1) ? 0.015625f : 0.03125f;
+	const std::vector<int16_t> q = quantise_s16(x.data(), x.size());
+	std::vector<float> seen(x.size());
+	nae_ctx* ctx = nullptr;
+	CHECK(nae_ctx_create(0, &ctx) == 0, "context");
+	if (!ctx) return {};
+	void *d_q = nullptr, *d_f = nullptr;
+	CHECK(nae_malloc(ctx, q.size() * sizeof(int16_t), &d_q) == 0 && nae_malloc(ctx, seen.size() * sizeof(float), &d_f) == 0, "malloc");
+	CHECK(nae_memcpy_h2d(ctx, d_q, q.data(), q.size() * sizeof(int16_t)) == 0, "h2d");
+	const void* planes[1] = {d_q};
+	CHECK(nae_to_f32_interleaved(ctx, AV_SAMPLE_FMT_S16, planes, x.size() / ch, ch, static_cast<float*>(d_f)) == 0, "nae_to_f32_interleaved");
+	CHECK(nae_memcpy_d2h(ctx, seen.data(), d_f, seen.size() * sizeof(float)) == 0 && nae_sync(ctx) == 0, "d2h");
+	nae_free(ctx, d_q);
+	nae_free(ctx, d_f);
+	nae_ctx_destroy(ctx);
+	return seen;
+}
+
+// x, S samples of ch channels, leaves a source of `format` in frames of 1000; `seen` is the f32 signal the node has of it.  The sink holds the
+// source's frames, sizes and pts, and the samples of nae_loud_normalize_f32 on the whole of `seen`, bit for bit
+static void graph_against_the_block_entry(const std::vector<float>& x, const std::vector<float>& seen, int S, int format, int ch, const char* what)
+{
+	const int frame_size = 1000;
 	Json::Value v;
 	v["target_lufs"] = -16;
 	v["true_peak_db"] = -1.5;
 	std::shared_ptr<Sink> sink;
 	std::string error;
-	const bool ok = run_graph<Audio_loudness>(x, v, frame_size, sink, &error);
-	CHECK(ok, "source -> audio_loudness -> sink runs: " << error);
-	if (!ok) return;
+	const bool ok = run_graph<Audio_loudness>(x, v, frame_size, sink, &error, 48000, format, ch);
+	CHECK(ok, what << ": source -> audio_loudness -> sink runs: " << error);
+	if (!ok || seen.empty()) return;
 	nae_loud_params params;
 	CHECK(nae_loud_design(48000, -16, -1.5, 20, &params) == 0, "design");
-	const std::vector<float> y = block_call(x, S, [&](nae_ctx* ctx, const nae_sig* sx, const nae_sig* sy) {
-		return nae_loud_normalize_f32(ctx, &params, sx, S, 2, 1, sy, nullptr);
-	});
+	const std::vector<float> y = block_call(seen, S, [&](nae_ctx* ctx, const nae_sig* sx, const nae_sig* sy) {
+		return nae_loud_normalize_f32(ctx, &params, sx, S, ch, 1, sy, nullptr);
+	}, ch);
 	if (y.empty()) return;
 	size_t changed = 0;
-	for (size_t i = 0; i < y.size(); i++) changed += y[i] != x[i];
-	CHECK(changed > y.size() / 2, "the gain is not 1: " << changed << " words changed");
-	check_frames(*sink, y, S, frame_size, "the samples of nae_loud_normalize_f32 on the whole stream");
+	for (size_t i = 0; i < y.size(); i++) changed += y[i] != seen[i];
+	CHECK(changed > y.size() / 2, what << ": the gain is not 1: " << changed << " words changed");
+	check_frames(*sink, y, S, frame_size, what, ch);
+}
+
+static void test_gpu()
+{
+	// 30037 samples in frames of 1000: 30 whole frames and one of 37, none of them a multiple of a chunk or a sub-block; noise at -30 dB, so
+	// the default target asks for gain and the ceiling does not bind
+	const int S = 30037;
+	std::vector<float> x = uniform_noise((size_t)S * 2);
+	for (size_t i = 0; i < x.size(); i++) x[i] *= (i & 1) ? 0.015625f : 0.03125f;
+	graph_against_the_block_entry(x, x, S, AV_SAMPLE_FMT_FLT, 2, "the samples of nae_loud_normalize_f32 on the whole stream");
+	// converted input: the node keeps what the device made of the frames.  Planar float is the same floats; of packed S16 it is
+	// nae_to_f32_interleaved's signal
+	graph_against_the_block_entry(x, x, S, AV_SAMPLE_FMT_FLTP, 2, "planar float: nae_loud_normalize_f32 on the same floats");
+	graph_against_the_block_entry(x, s16_seen_as_f32(x, 2), S, AV_SAMPLE_FMT_S16, 2, "packed S16: nae_loud_normalize_f32 on the converted words");
+	// mono, and exactly one gating block at 48 kHz (one sample more than `short`'s 19199): the handle is made, the gain applied
+	const int M = 19200;
+	std::vector<float> m = uniform_noise((size_t)M, 77);
+	for (float& s : m) s *= 0.03125f;
+	graph_against_the_block_entry(m, m, M, AV_SAMPLE_FMT_FLT, 1, "mono, one gating block: nae_loud_normalize_f32 with ch = 1");
 }
 
 int main(int argc, char** argv)

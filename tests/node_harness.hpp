@@ -1,6 +1,7 @@
 // node_harness.hpp — what the host node harnesses share.  All of them (tests/pv_ref/host_pv_node.cpp, tests/spec_sizes/host_spectrum.cpp and the
-// four effect nodes'): a CHECK that counts its evaluations and its failures, a source node that plays interleaved stereo f32 in frames of
-// frame_size, a sink node that keeps every frame, and rejects<Node>(json, field), true when deserializing json throws "Wrong field: <field>".
+// four effect nodes'): a CHECK that counts its evaluations and its failures, a source node that plays interleaved f32 (stereo, packed float
+// unless told otherwise) in frames of frame_size, a sink node that keeps every frame, and rejects<Node>(json, field), true when deserializing
+// json throws "Wrong field: <field>".
 // The effect nodes' (tests/fir_ref/host_fir_node.cpp, conv_ref/host_conv_node.cpp, eq_ref/host_eq_node.cpp, dyn_ref/host_dyn_node.cpp) besides:
 // uniform_noise, run_graph<Node> (source -> node -> sink), check_frames (the sink's frames against the source's shapes and the wanted words),
 // block_call (a block entry through a context of its own), print_registry / check_generated, and harness_main (the mode dispatch).
@@ -27,12 +28,21 @@ inline long checks = 0;   // CHECKs evaluated: harness_main prints it, so that a
 		if (!(cond)) { std::cout << "FAIL " << __LINE__ << ": " << msg << "\n"; failures++; } \
 	} while (0)
 
+// what a source of format AV_SAMPLE_FMT_S16 sends for x: the nearest of 32767 steps
+inline std::vector<int16_t> quantise_s16(const float* x, size_t n)
+{
+	std::vector<int16_t> q(n);
+	for (size_t i = 0; i < n; i++) q[i] = (int16_t)std::lrint(x[i] * 32767.0f);
+	return q;
+}
+
 class Src : public infra::Processor
 {
   public:
 
-	std::vector<float> samples;  // interleaved stereo
+	std::vector<float> samples;  // interleaved, `channels` of them
 	int frame_size = 1152, sample_rate = 48000;
+	int format = AV_SAMPLE_FMT_FLT, channels = 2;  // the frames' format: AV_SAMPLE_FMT_FLT, _FLTP (the planes of samples) or _S16 (quantise_s16 of samples)
 	double start_seconds = 0.5;
 
 	static Info get_processor_info() { return {"test_source", "Source", false, [] { return std::unique_ptr<Processor>(new Src); }, ""}; }
@@ -50,20 +60,27 @@ class Src : public infra::Processor
 						 std::any&) override
 	{
 		const auto outs = infra::get_output_item<Audio_stream>(output, "output");
-		const size_t total = samples.size() / 2;
+		const size_t total = samples.size() / channels;
 		for (size_t pos = 0; pos < total && !stop_token; pos += frame_size)
 		{
 			const int n = (int)std::min<size_t>(frame_size, total - pos);
 			auto frame = std::make_shared<Audio_frame>();
 			Frame_data* f = frame->data();
-			f->format = AV_SAMPLE_FMT_FLT;
+			f->format = format;
 			f->sample_rate = sample_rate;
 			f->nb_samples = n;
-			f->ch_layout.nb_channels = 2;
+			f->ch_layout.nb_channels = channels;
 			f->time_base = {1, 1000000};
 			f->pts = (int64_t)((start_seconds + double(pos) / sample_rate) * 1000000);
 			frame_get_buffer(f, 32);
-			std::memcpy(f->data[0], samples.data() + pos * 2, (size_t)n * 2 * sizeof(float));
+			const float* x = samples.data() + pos * channels;
+			if (format == AV_SAMPLE_FMT_FLTP)
+				for (int c = 0; c < channels; c++)
+					for (int i = 0; i < n; i++) reinterpret_cast<float*>(f->data[c])[i] = x[(size_t)i * channels + c];
+			else if (format == AV_SAMPLE_FMT_S16)
+				std::memcpy(f->data[0], quantise_s16(x, (size_t)n * channels).data(), (size_t)n * channels * sizeof(int16_t));
+			else
+				std::memcpy(f->data[0], x, (size_t)n * channels * sizeof(float));
 			for (auto& o : outs)
 				while (!stop_token && o->try_push(frame) != channel_op_status::success) nae_fiber::this_fiber::yield();
 		}
@@ -144,13 +161,15 @@ inline std::vector<float> uniform_noise(size_t n_floats, uint64_t seed = 4711)
 // source -> Node (deserialized from json) -> sink; the frames' shapes are checked in check_frames, the samples by the caller
 template <class Node>
 bool run_graph(const std::vector<float>& x, const Json::Value& json, int frame_size, std::shared_ptr<Sink>& sink, std::string* error = nullptr,
-			   int sample_rate = 48000)
+			   int sample_rate = 48000, int format = AV_SAMPLE_FMT_FLT, int channels = 2)
 {
 	Runner r;
 	auto src = std::make_shared<Src>();
 	src->samples = x;
 	src->frame_size = frame_size;
 	src->sample_rate = sample_rate;
+	src->format = format;
+	src->channels = channels;
 	auto node = std::make_shared<Node>();
 	node->deserialize(json);
 	sink = std::make_shared<Sink>();
@@ -162,8 +181,8 @@ bool run_graph(const std::vector<float>& x, const Json::Value& json, int frame_s
 	return ok;
 }
 
-// the sink holds the frames a 48 kHz source of S stereo samples sent, and their words are want's
-inline void check_frames(const Sink& sink, const std::vector<float>& want, size_t S, int frame_size, const char* what)
+// the sink holds the frames a 48 kHz source of S samples of ch channels sent, as packed float, and their words are want's
+inline void check_frames(const Sink& sink, const std::vector<float>& want, size_t S, int frame_size, const char* what, int ch = 2)
 {
 	const size_t n_frames = (S + frame_size - 1) / frame_size;
 	CHECK(sink.frames.size() == n_frames, "as many frames as the source sent: " << sink.frames.size() << " vs " << n_frames);
@@ -174,30 +193,30 @@ inline void check_frames(const Sink& sink, const std::vector<float>& want, size_
 		const Frame_data* d = sink.frames[f]->data();
 		const int want_n = (int)std::min<size_t>(frame_size, S - std::min<size_t>(S, f * frame_size));
 		const int64_t want_pts = (int64_t)((0.5 + double(f * frame_size) / 48000) * 1000000);   // the source's own formula
-		shape_ok = shape_ok && d->nb_samples == want_n && d->format == AV_SAMPLE_FMT_FLT && d->ch_layout.nb_channels == 2 && d->sample_rate == 48000 &&
+		shape_ok = shape_ok && d->nb_samples == want_n && d->format == AV_SAMPLE_FMT_FLT && d->ch_layout.nb_channels == ch && d->sample_rate == 48000 &&
 				   d->pts == want_pts && d->time_base.num == 1 && d->time_base.den == 1000000;
 		const float* got = reinterpret_cast<const float*>(d->data[0]);
 		for (int i = 0; i < d->nb_samples && pos < S; i++, pos++)
-			for (int c = 0; c < 2; c++) bad += std::memcmp(&got[i * 2 + c], &want[pos * 2 + c], sizeof(float)) != 0;
+			for (int c = 0; c < ch; c++) bad += std::memcmp(&got[i * ch + c], &want[pos * ch + c], sizeof(float)) != 0;
 	}
 	CHECK(shape_ok, "frames of the input's sizes, format FLT, the source's pts and time base");
 	CHECK(pos == S, "as many samples as the source sent: " << pos);
 	CHECK(bad == 0, what << ": " << bad << " words differ");
 }
 
-// interleaved stereo x through a block entry, in a context of its own: call(ctx, &src, &dst) returns the entry's status -> the first out_frames
-// frames of the destination; empty when there is no context
+// interleaved x of ch channels through a block entry, in a context of its own: call(ctx, &src, &dst) returns the entry's status -> the first
+// out_frames frames of the destination; empty when there is no context
 template <class Call>
-std::vector<float> block_call(const std::vector<float>& x, size_t out_frames, Call call)
+std::vector<float> block_call(const std::vector<float>& x, size_t out_frames, Call call, int ch = 2)
 {
 	nae_ctx* ctx = nullptr;
 	CHECK(nae_ctx_create(0, &ctx) == 0, "context");
 	if (!ctx) return {};
-	std::vector<float> y(out_frames * 2);
+	std::vector<float> y(out_frames * ch);
 	void *d_x = nullptr, *d_y = nullptr;
 	CHECK(nae_malloc(ctx, x.size() * sizeof(float), &d_x) == 0 && nae_malloc(ctx, y.size() * sizeof(float), &d_y) == 0, "malloc");
 	CHECK(nae_memcpy_h2d(ctx, d_x, x.data(), x.size() * sizeof(float)) == 0, "h2d");
-	const nae_sig sx{d_x, 0, 1, 2}, sy{d_y, 0, 1, 2};
+	const nae_sig sx{d_x, 0, 1, (size_t)ch}, sy{d_y, 0, 1, (size_t)ch};
 	CHECK(call(ctx, &sx, &sy) == 0, "block call");
 	CHECK(nae_memcpy_d2h(ctx, y.data(), d_y, y.size() * sizeof(float)) == 0 && nae_sync(ctx) == 0, "d2h");
 	nae_free(ctx, d_x);

@@ -222,6 +222,13 @@ def test_host_node_wire(host):
     assert r.returncode == 0 and "HOST EQ OK wire" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
+def test_host_node_wire_passes_s16_as_it_came(host):
+    """without bands a packed S16 stream of 2500 samples in frames of 1000 arrives as S16 frames of 1000 / 1000 / 500 with the source's pts and
+    words (no kernel runs; the node still opens its context first, so the mode needs a device)"""
+    r = subprocess.run([host, "wire_s16"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "HOST EQ OK wire_s16" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
 def test_host_node_band_at_nyquist(host):
     """a band at half the stream's sample rate is a Runtime_error on the first frame"""
     r = subprocess.run([host, "nyquist"], capture_output=True, text=True, timeout=120)
