@@ -64,6 +64,8 @@
 #define NAE_DYN_MIN_RELEASE_S 0.001
 #define NAE_DYN_MAX_RELEASE_S 5.0
 #define NAE_DYN_MAX_MAKEUP_DB 24.0
+/* K15 keyed dynamics ("K15 keyed dynamics"): K12 whose detector reads a key through at most this many K11 sections */
+#define NAE_DYNKEY_MAX_SECTIONS 4
 /* K13 spectral gate ("K13 spectral gate"): noise reduction on the STFT at N = 512 ... 4096 and hop N / 4: a per-bin decision
  * against a learned power profile, smoothed by an integer triangle over at most NAE_DENOISE_MAX_TIME frames and NAE_DENOISE_MAX_FREQ bins to
  * either side (a wider frequency triangle pulls a pure tone down: DESIGN.md gives the figure); a tile the library chooses has at least

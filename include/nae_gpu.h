@@ -21,6 +21,7 @@
 #define NAE_GPU_H
 #include <stddef.h>
 #include <stdint.h>
+#include "nae_dsp_spec.h" /* NAE_DYNKEY_MAX_SECTIONS, the extent of nae_dynkey_params::coef */
 
 #ifdef __cplusplus
 extern "C" {
@@ -49,7 +50,8 @@ extern "C" {
  *   nae_denoise_block_f32 and the nae_denoise handle (the same eight entries) with the record nae_denoise_params: the spectral gate, K13;
  *   nae_loud_design, nae_loud_lufs, nae_loud_measure_f32, nae_loud_apply_f32, nae_loud_normalize_f32 and the measuring handle nae_loud
  *   (nae_loud_create, _put, _put_host, _flush, _get_result, _destroy) with the records nae_loud_params and nae_loud_result: the BS.1770
- *   loudness meter and normalizer, K14. */
+ *   loudness meter and normalizer, K14; nae_dynkey_block_f32 and the nae_dynkey handle (the same eight entries) with the record
+ *   nae_dynkey_params: the keyed (side-chain) dynamics, K15. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -75,6 +77,7 @@ typedef struct nae_fir nae_fir;
 typedef struct nae_conv nae_conv;
 typedef struct nae_eq nae_eq;
 typedef struct nae_dyn nae_dyn;
+typedef struct nae_dynkey nae_dynkey;
 typedef struct nae_denoise nae_denoise;
 typedef struct nae_loud nae_loud;
 
@@ -610,6 +613,41 @@ int nae_dyn_destroy(nae_dyn* h);
  * NAE_DYN_MAX_LOOKAHEAD samples at this rate.  No context, no device work. */
 int nae_dyn_design(int sample_rate, double threshold_db, double ratio, double knee_db, double attack_s, double release_s, double lookahead_s,
                    double makeup_db, int link, nae_dyn_params* out);
+
+/* ------------------------------------------------------------------ K15 keyed dynamics
+ * no reference code.  Spec ("K15 keyed dynamics"): K12 with a side-chain.  The detector's level comes from a key magnitude m[n]
+ * instead of |x[n]|: the key is the signal itself (key_ch = 0, `key` null) or an external view of in_len samples with 1 or ch channels
+ * (every view K11 takes, stream_stride = 0 included: one key for many streams), run per key channel through n_sections biquads in K11's tiled
+ * form exactly (coefficients b0 b1 b2 a1 a2 in double under K11's stability rule, the same tables, order of operations and carry), and
+ * m = (float)|w|, rounded once; with n_sections = 0 m = |key|.  A linked stereo detector reads the larger m of the key's channels; unlinked,
+ * detector c reads key channel c, or channel 0 of a mono key.  The demand is zero from in_len on: the key is zero there, and the filter's
+ * ringing past the end is no demand.  Everything else is K12's, applied to the signal: y = (float)((double)x gain), compensated, in_len
+ * frames out.  So an internal key, or a key equal to the signal, with no section gives nae_dyn_block_f32's bits, and a key filtered by n
+ * sections the bits of the call with no section keyed by nae_eq_block_f32's output of that key.  Bit-exact against the CPU statement
+ * (tests/dynkey_ref/ref_dynkey.c).  A non-finite key sample i leaves every output sample before i - lookahead as it was (nothing is specified
+ * from there on: an IIR carries it); with an external key a non-finite signal sample changes its own output sample only.
+ * Errors: K12's, then NAE_ERR_INVALID for key_ch not 0, 1 or ch, a key view with key_ch = 0 or none with key_ch > 0, negative n_sections,
+ * a non-finite or not strictly stable section; NAE_ERR_UNSUPPORTED for more than NAE_DYNKEY_MAX_SECTIONS sections; in_len = 0 or
+ * n_streams = 0: NAE_OK after the checks.  nae_dyn_design and nae_eq_design fill the record. */
+typedef struct nae_dynkey_params {
+    nae_dyn_params dyn;
+    int key_ch;                                   /* 0: the signal is its own key; else 1 or ch */
+    int n_sections;                               /* 0 ... NAE_DYNKEY_MAX_SECTIONS */
+    double coef[NAE_DYNKEY_MAX_SECTIONS][5];
+} nae_dynkey_params;
+int nae_dynkey_block_f32(nae_ctx* ctx, const nae_dynkey_params* params, const nae_sig* src, const nae_sig* key /* null iff key_ch = 0 */,
+                         size_t in_len, int ch, size_t n_streams, const nae_sig* dst);
+/* Streaming handle.  A put carries frames of channels + key_ch floats, the signal's channels and then the key's, so the two cannot fall out
+ * of step; a receive delivers frames of `channels` floats.  Availability, flush and errors as nae_dyn's; any cut of the input into puts gives
+ * the block call's bits. */
+int nae_dynkey_create(nae_ctx* ctx, const nae_dynkey_params* params, int channels, nae_dynkey** h);
+int nae_dynkey_put(nae_dynkey* h, const float* interleaved, size_t S);
+int nae_dynkey_put_host(nae_dynkey* h, const float* interleaved_host, size_t S);
+int nae_dynkey_flush(nae_dynkey* h);
+size_t nae_dynkey_available(nae_dynkey* h);
+int nae_dynkey_receive(nae_dynkey* h, float* dst, size_t max_frames, size_t* got);
+int nae_dynkey_receive_host(nae_dynkey* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_dynkey_destroy(nae_dynkey* h);
 
 /* ------------------------------------------------------------------ K13 spectral gate
  * no reference code.  Spec ("K13 spectral gate"): noise reduction on the STFT at n_fft = 512 ... 4096, hop H = n_fft / 4, in the

@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = [
     "nae_eq_receive_host", "nae_eq_destroy",
     "nae_dyn_design", "nae_dyn_block_f32", "nae_dyn_create", "nae_dyn_put", "nae_dyn_put_host", "nae_dyn_flush", "nae_dyn_available",
     "nae_dyn_receive", "nae_dyn_receive_host", "nae_dyn_destroy",
+    "nae_dynkey_block_f32", "nae_dynkey_create", "nae_dynkey_put", "nae_dynkey_put_host", "nae_dynkey_flush", "nae_dynkey_available",
+    "nae_dynkey_receive", "nae_dynkey_receive_host", "nae_dynkey_destroy",
     "nae_denoise_design", "nae_denoise_profile_f32", "nae_denoise_block_f32", "nae_denoise_create", "nae_denoise_put", "nae_denoise_put_host",
     "nae_denoise_flush", "nae_denoise_available", "nae_denoise_receive", "nae_denoise_receive_host", "nae_denoise_destroy",
     "nae_loud_design", "nae_loud_lufs", "nae_loud_measure_f32", "nae_loud_apply_f32", "nae_loud_normalize_f32", "nae_loud_create", "nae_loud_put",
@@ -56,7 +58,8 @@ FORMANT_SHIFT_MIN, FORMANT_SHIFT_MAX = 0.25, 4.0   # NAE_FORMANT_SHIFT_MIN / _MA
 FIR_SIZES = (512, 1024, 2048, 4096)                 # frame sizes of the FIR filter: at most n_fft / 2 + 1 taps
 FIR_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}   # `kind` of nae_fir_design
 EQ_KINDS = ("peak", "lowshelf", "highshelf", "lowpass", "highpass", "notch")   # `kind` of nae_eq_design: NAE_EQ_PEAK ... NAE_EQ_NOTCH
-HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_denoise")   # the handles with the full put / receive set of entries
+DYNKEY_MAX_SECTIONS = 4                             # NAE_DYNKEY_MAX_SECTIONS (include/nae_dsp_spec.h): the key filter's sections
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -100,6 +103,26 @@ class DynParams(C.Structure):
     """nae_dyn_params: the dynamics processor's parameters (include/nae_gpu.h); nae_dyn_design makes them from times and a ratio"""
     _fields_ = [("threshold_db", C.c_double), ("slope", C.c_double), ("knee_db", C.c_double), ("alpha_attack", C.c_double),
                 ("alpha_release", C.c_double), ("makeup_db", C.c_double), ("lookahead", C.c_int), ("link", C.c_int)]
+
+
+class DynKeyParams(C.Structure):
+    """nae_dynkey_params: the keyed dynamics' parameters (include/nae_gpu.h): nae_dyn_params, the key's channels (0: the signal is its own
+    key) and the key filter's sections (b0, b1, b2, a1, a2), which nae_eq_design makes"""
+    _fields_ = [("dyn", DynParams), ("key_ch", C.c_int), ("n_sections", C.c_int), ("coef", (C.c_double * 5) * DYNKEY_MAX_SECTIONS)]
+
+    @staticmethod
+    def make(dyn: DynParams, key_ch: int = 0, coef=()) -> "DynKeyParams":
+        """coef: [n][5], at most DYNKEY_MAX_SECTIONS sections (more raise: the record has no room for them)"""
+        coef = np.asarray(coef, np.float64).reshape(-1, 5)
+        if coef.shape[0] > DYNKEY_MAX_SECTIONS:
+            raise NaeError(f"nae_dynkey_params holds at most {DYNKEY_MAX_SECTIONS} sections")
+        p = DynKeyParams()
+        p.dyn = dyn
+        p.key_ch, p.n_sections = key_ch, coef.shape[0]
+        for s_, row in enumerate(coef):
+            for i_, v in enumerate(row):
+                p.coef[s_][i_] = v
+        return p
 
 
 class DenoiseParams(C.Structure):
@@ -225,6 +248,7 @@ def load_library() -> C.CDLL:
         "nae_eq_create": (i, [vp, vp, i, i, P(vp)]),
         "nae_dyn_design": (i, [i, d, d, d, d, d, d, d, i, P(DynParams)]), "nae_dyn_block_f32": (i, [vp, P(DynParams), P(Sig), sz, i, sz, P(Sig)]),
         "nae_dyn_create": (i, [vp, P(DynParams), i, P(vp)]),
+        "nae_dynkey_block_f32": (i, [vp, P(DynKeyParams), P(Sig), P(Sig), sz, i, sz, P(Sig)]), "nae_dynkey_create": (i, [vp, P(DynKeyParams), i, P(vp)]),
         "nae_denoise_design": (i, [d, d, i, i, i, P(DenoiseParams)]), "nae_denoise_profile_f32": (i, [vp, i, P(Sig), sz, i, vp]),
         "nae_denoise_block_f32": (i, [vp, P(DenoiseParams), vp, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
@@ -660,6 +684,11 @@ class Context:
                            f"{makeup_db}, {link}) failed: {rc}")
         return out
 
+    def dynkey_block(self, params: "DynKeyParams", src: Sig, key: Optional[Sig], in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the keyed dynamics (nae_dynkey_block_f32): key is None exactly when params.key_ch is 0"""
+        self._ck(self.lib.nae_dynkey_block_f32(self.h, C.byref(params), C.byref(src), C.byref(key) if key is not None else None, in_len, ch,
+                                               n_streams, C.byref(dst)))
+
     def dyn_block(self, params: "DynParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
         """the compressor / limiter `params` over every stream; dst receives in_len frames, compensated for the look-ahead"""
         self._ck(self.lib.nae_dyn_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
@@ -841,6 +870,22 @@ class Dyn(_Handle):
     def __init__(self, ctx: Context, params: DynParams, channels: int):
         super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_dyn_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+
+class DynKey(_Handle):
+    """The keyed dynamics' streaming handle (nae_dynkey_create): a put carries frames of channels + key_ch floats, the signal's channels and
+    then the key's; a receive delivers frames of `channels` floats.  Availability and flush as Dyn's."""
+
+    _prefix = "nae_dynkey"
+
+    def __init__(self, ctx: Context, params: DynKeyParams, channels: int):
+        super().__init__(ctx, channels)
+        self.in_width = channels + params.key_ch
+        ctx._ck(ctx.lib.nae_dynkey_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+    def put_host(self, x: np.ndarray) -> None:
+        x = np.ascontiguousarray(x, np.float32)
+        self.ctx._ck(self._fn("put_host")(self.h, x.ctypes.data, x.size // self.in_width))
 
 
 class Denoise(_Handle):

@@ -207,6 +207,24 @@ int nae_launch_eq(nae_ctx* ctx, const double* d_block, int n_sections, const nae
                             p, d_block, d_state);
 }
 
+// the context's constant block of checked coefficients: the tables are kept with the context, so a call with the coefficients of the last one
+// uploads nothing (nae_eq_block_f32, and the key filter of nae_dynkey_block_f32)
+int nae_eq_cached_block(nae_ctx* ctx, const double* coef_host, int n_sections, double** d_block)
+{
+    (void)nae_use_device(ctx);
+    const size_t n_coef = (size_t)n_sections * 5;
+    const bool same = ctx->d_eq_block && ctx->h_eq_coef.size() == n_coef && memcmp(ctx->h_eq_coef.data(), coef_host, n_coef * sizeof(double)) == 0;
+    if (!same) {
+        if (!ctx->d_eq_block && hipMalloc((void**)&ctx->d_eq_block, kEqBlockDoubles * sizeof(double)) != hipSuccess)
+            return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(eq tables)");
+        ctx->h_eq_coef.clear();                            // the upload is ordered on the stream behind a launch that still reads the last block
+        if (const int rc = nae_eq_make_block(ctx, coef_host, n_sections, ctx->d_eq_block)) return rc;
+        ctx->h_eq_coef.assign(coef_host, coef_host + n_coef);
+    }
+    *d_block = ctx->d_eq_block;
+    return NAE_OK;
+}
+
 void nae_eq_cache_free(nae_ctx* ctx)
 {
     if (ctx->d_eq_block) (void)hipFree(ctx->d_eq_block);
@@ -225,18 +243,9 @@ int nae_eq_block_f32(nae_ctx* ctx, const double* coef_host, int n_sections, cons
     if (rc) return rc;
     if (in_len == 0 || n_streams == 0) return NAE_OK;
     if (!src->base || !dst->base) return nae_fail(ctx, NAE_ERR_INVALID, "eq: null pointer");
-    (void)nae_use_device(ctx);
-    // the tables are kept with the context: a call with the coefficients of the last one uploads nothing
-    const size_t n_coef = (size_t)n_sections * 5;
-    const bool same = ctx->d_eq_block && ctx->h_eq_coef.size() == n_coef && memcmp(ctx->h_eq_coef.data(), coef_host, n_coef * sizeof(double)) == 0;
-    if (!same) {
-        if (!ctx->d_eq_block && hipMalloc((void**)&ctx->d_eq_block, kEqBlockDoubles * sizeof(double)) != hipSuccess)
-            return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(eq tables)");
-        ctx->h_eq_coef.clear();                            // the upload is ordered on the stream behind a launch that still reads the last block
-        if ((rc = nae_eq_make_block(ctx, coef_host, n_sections, ctx->d_eq_block))) return rc;
-        ctx->h_eq_coef.assign(coef_host, coef_host + n_coef);
-    }
-    return nae_launch_eq(ctx, ctx->d_eq_block, n_sections, src, in_len, ch, n_streams, dst, 0, (in_len + kEqC - 1) / kEqC, nullptr);
+    double* d_block = nullptr;
+    if ((rc = nae_eq_cached_block(ctx, coef_host, n_sections, &d_block))) return rc;
+    return nae_launch_eq(ctx, d_block, n_sections, src, in_len, ch, n_streams, dst, 0, (in_len + kEqC - 1) / kEqC, nullptr);
 }
 
 // DESIGN.md §3, "K11 biquad cascade", "Design": the Audio EQ Cookbook's forms in double, divided through by a0

@@ -279,6 +279,8 @@ int nae_eq_make_block(nae_ctx* ctx, const double* coef, int n_sections, double* 
 int nae_launch_eq(nae_ctx* ctx, const double* d_block, int n_sections, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
                   const nae_sig* dst, size_t c_origin, size_t c_stop, double* d_state);
 void nae_eq_cache_free(nae_ctx* ctx);
+// the context's own constant block, made of checked coefficients unless they are the last call's (nae_eq_block_f32 and nae_dynkey_block_f32)
+int nae_eq_cached_block(nae_ctx* ctx, const double* coef_host, int n_sections, double** d_block);
 
 // kernels_dyn.hip: the dynamics processor ("K12 dynamics").  nae_dyn_check: the parameter rules of the block call and the handle.
 // nae_dyn_detectors: one per stream with `link` on stereo, else one per stream-channel.  nae_launch_dyn runs chunks [c_origin, c_stop) of
@@ -288,6 +290,16 @@ int nae_dyn_check(nae_ctx* ctx, const nae_dyn_params* p, int ch);
 size_t nae_dyn_detectors(const nae_dyn_params* p, int ch, size_t n_streams);
 int nae_launch_dyn(nae_ctx* ctx, const nae_dyn_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
                    size_t c_origin, size_t c_stop, double* d_state);
+
+// kernels_dynkey.hip: the keyed dynamics ("K15 keyed dynamics").  nae_dynkey_check: K12's rules, then the key's (key_ch not 0, 1
+// or ch, negative n_sections, a non-finite or not strictly stable section NAE_ERR_INVALID; more than NAE_DYNKEY_MAX_SECTIONS
+// NAE_ERR_UNSUPPORTED).  nae_launch_dynkey is nae_launch_dyn under a key (`key` is not read with key_ch = 0: the signal is its own key);
+// d_block: the key filter's K11 constant block (unused with no section); d_fstate, nae_dynkey_filter_doubles() doubles, holds the filter's
+// carries in front of c_origin and receives the ones in front of c_stop, the chunk the next launch levels first (null: zero, nothing kept).
+int nae_dynkey_check(nae_ctx* ctx, const nae_dynkey_params* p, int ch);
+size_t nae_dynkey_filter_doubles(const nae_dynkey_params* p, int ch, size_t n_streams);
+int nae_launch_dynkey(nae_ctx* ctx, const nae_dynkey_params* p, const double* d_block, const nae_sig* src, const nae_sig* key, size_t in_len, int ch,
+                      size_t n_streams, const nae_sig* dst, size_t c_origin, size_t c_stop, double* d_state, double* d_fstate);
 
 // kernels_denoise.hip: the spectral gate ("K13 spectral gate").  nae_denoise_check: the parameter rules of the block call and the
 // handle.  nae_launch_denoise runs hop blocks [b_origin, b_stop) of absolutely indexed signals of in_len samples: it reads from

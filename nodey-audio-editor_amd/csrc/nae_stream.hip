@@ -67,6 +67,16 @@ struct nae_dyn : BlockHandle {
     int process() override;
 };
 
+// the keyed dynamics' handle ("K15 keyed dynamics"): nae_dyn's, with an input FIFO of ch + key_ch floats per frame — the signal's
+// channels, then the key's — and the key filter's carries in front of the next chunk beside the detectors'
+struct nae_dynkey : BlockHandle {
+    nae_dynkey_params params;
+    double* d_block = nullptr;     // the key filter's coefficients and tables (nae_eq_make_block); null with no section
+    double* d_state = nullptr;     // [detector][2]: (y1, yl) behind the last chunk done
+    double* d_fstate = nullptr;    // nae_dynkey_filter_doubles(): the filter's (z1, z2) behind the last chunk done
+    int process() override;
+};
+
 // the spectral gate's handle ("K13 spectral gate"): whole hop blocks of n_fft / 4 samples are computed once the time_smooth + 3
 // blocks behind them are there; the input stays from time_smooth + 3 blocks in front of the next block on, and nothing else is kept
 struct nae_denoise : BlockHandle {
@@ -308,6 +318,15 @@ int nae_dyn::process()
 {
     return run_units(NAE_DYN_CHUNK, (size_t)params.lookahead, 0, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
         return nae_launch_dyn(ctx, &params, &src, in.total, ch, 1, &dst, from, to, d_state);
+    });
+}
+
+int nae_dynkey::process()
+{
+    return run_units(NAE_DYN_CHUNK, (size_t)params.dyn.lookahead, 0, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
+        // the key's channels stand behind the signal's in every frame
+        const nae_sig key{static_cast<float*>(src.base) + ch, src.stream_stride, src.chan_stride, src.frame_stride};
+        return nae_launch_dynkey(ctx, &params, d_block, &src, &key, in.total, ch, 1, &dst, from, to, d_state, d_fstate);
     });
 }
 
@@ -564,6 +583,38 @@ size_t nae_dyn_available(nae_dyn* h) { return handle_available(h); }
 int nae_dyn_receive(nae_dyn* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_dyn_receive_host(nae_dyn* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_dyn_destroy(nae_dyn* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ keyed dynamics
+int nae_dynkey_create(nae_ctx* ctx, const nae_dynkey_params* params, int channels, nae_dynkey** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_dynkey_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_dynkey* s = handle_new<nae_dynkey>(ctx, channels, params->key_ch);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    const size_t state_doubles = nae_dyn_detectors(&params->dyn, channels, 1) * 2, filter_doubles = nae_dynkey_filter_doubles(params, channels, 1);
+    rc = s->dev_alloc(&s->d_state, state_doubles, "hipMalloc(dynkey state)");
+    if (!rc) rc = nae_check(ctx, hipMemsetAsync(s->d_state, 0, state_doubles * sizeof(double), ctx->stream), "hipMemsetAsync(dynkey state)");
+    if (!rc && params->n_sections) {
+        rc = s->dev_alloc(&s->d_fstate, filter_doubles, "hipMalloc(dynkey state)");
+        if (!rc) rc = nae_check(ctx, hipMemsetAsync(s->d_fstate, 0, filter_doubles * sizeof(double), ctx->stream), "hipMemsetAsync(dynkey state)");
+        if (!rc) rc = s->dev_alloc(&s->d_block, nae_eq_block_doubles(), "hipMalloc(dynkey tables)");
+        if (!rc) rc = nae_eq_make_block(ctx, &params->coef[0][0], params->n_sections, s->d_block);
+    }
+    return handle_created(s, rc, h);
+}
+
+int nae_dynkey_put(nae_dynkey* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_dynkey_put_host(nae_dynkey* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+// flush: as nae_dyn's
+int nae_dynkey_flush(nae_dynkey* h) { return handle_flush(h); }
+size_t nae_dynkey_available(nae_dynkey* h) { return handle_available(h); }
+int nae_dynkey_receive(nae_dynkey* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_dynkey_receive_host(nae_dynkey* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_dynkey_destroy(nae_dynkey* h) { return handle_destroy(h); }
 
 // ------------------------------------------------------------------------------------------------ spectral gate
 int nae_denoise_create(nae_ctx* ctx, const nae_denoise_params* params, const float* profile_dev, int profile_ch, int channels, nae_denoise** h)

@@ -194,15 +194,17 @@ struct BlockHandle : StreamHandle {
     }
 };
 
-// a new handle of type H on `ctx` with interleaved FIFOs of `channels` floats per frame; nullptr when out of memory
+// a new handle of type H on `ctx` with interleaved FIFOs of `channels` floats per frame, `in_extra` more on the input side (channels that
+// ride with the signal and do not come out: a key); nullptr when out of memory
 template <class H>
-static inline H* handle_new(nae_ctx* ctx, int channels)
+static inline H* handle_new(nae_ctx* ctx, int channels, int in_extra = 0)
 {
     H* h = new (std::nothrow) H();
     if (!h) return nullptr;
     h->ctx = ctx;
     h->ch = channels;
-    h->in.width = h->out.width = (size_t)channels;
+    h->out.width = (size_t)channels;
+    h->in.width = (size_t)(channels + in_extra);
     return h;
 }
 

@@ -157,4 +157,6 @@ namespace infra
 	void register_restoration_processors();
 	// the mastering tools (audio_loudness): called after the six above, each of which stays the list it was
 	void register_mastering_processors();
+	// the side-chain compressor (audio_sidechain): called after the seven above, each of which stays the list it was
+	void register_sidechain_processors();
 }

@@ -20,10 +20,11 @@ namespace processor
 	// are designed from the stream's sample rate when the first frame arrives (nae_dyn_design); a look-ahead of more than 1024 samples at
 	// that rate is a Runtime_error then.  The node delivers exactly the frames it received, as packed float frames of their sizes, pts and
 	// time base — the look-ahead is compensated — and flushes at the end of the stream.
-	class Audio_dynamics : public infra::Processor
+	// the nine keys as a record of its own: the dynamics node is one, and the side-chain node (audio-sidechain.hpp) holds one.  from_json reads
+	// and checks every key before it changes anything (node_name: the reader's name in the error); to_json leaves the defaults out; clamp is
+	// what the widgets would keep.  Bodies: audio-effects.cpp.
+	struct Dynamics_settings
 	{
-	  public:
-
 		enum class Mode { Compressor = 0, Limiter };
 		static constexpr double default_threshold_db = -18, default_ratio = 4, default_knee_db = 6, default_attack_ms = 5, default_release_ms = 100,
 								default_lookahead_ms = 0, default_makeup_db = 0;
@@ -31,6 +32,15 @@ namespace processor
 		double threshold_db = default_threshold_db, ratio = default_ratio, knee_db = default_knee_db, attack_ms = default_attack_ms,
 			   release_ms = default_release_ms, lookahead_ms = default_lookahead_ms, makeup_db = default_makeup_db;
 		bool link_channels = true;
+
+		Json::Value to_json() const;
+		void from_json(const Json::Value& value, const char* node_name);
+		void clamp();
+	};
+
+	class Audio_dynamics : public infra::Processor, public Dynamics_settings
+	{
+	  public:
 
 		static infra::Processor::Info get_processor_info();
 		Processor::Info get_processor_info_non_static() const override { return get_processor_info(); }

@@ -1,11 +1,12 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
-// Audio_dynamics (nae_dyn) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
+// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 // Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
 #include "audio-filter.hpp"
 #include "audio-reverb.hpp"
 #include "audio-eq.hpp"
 #include "audio-dynamics.hpp"
+#include "audio-sidechain.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "node-util.hpp"
@@ -40,6 +41,38 @@ namespace processor
 		int (*destroy)(Handle*);
 	};
 
+	// The way out of a node on a handle: everything the handle has ready comes down behind ONE wait and leaves as frames of the shapes owed
+	// (cut_and_push).  The first to_discard frames of the handle's output are dropped.
+	struct Handle_output
+	{
+		gpu::Device_buffer d_out;
+		gpu::Pinned_buffer h_out;
+		std::vector<float> ready;     // processed samples behind the discarded ones, interleaved, not yet cut into frames
+		size_t ready_pos = 0;         // frames of `ready` already delivered
+		size_t to_discard = 0;
+
+		template <class Handle>
+		void deliver(Handle* h, const Handle_ops<Handle>& ops, int ch, std::deque<Shape>& shapes, const Output_streams& output_stream,
+					 const std::atomic<bool>& stop_token)
+		{
+			nae_ctx* ctx = gpu::context();
+			const size_t avail = ops.available(h);
+			if (avail == 0) { gpu::wait(stop_token); return; }
+			float* dev = static_cast<float*>(d_out.reserve(avail * ch * sizeof(float)));
+			float* host = static_cast<float*>(h_out.reserve(avail * ch * sizeof(float)));
+			size_t got = 0;
+			const int rc = ops.receive(h, dev, avail, &got);
+			if (rc != NAE_OK) gpu::check(rc, (std::string(ops.name) + "_receive").c_str());
+			gpu::check(nae_memcpy_d2h(ctx, host, dev, got * ch * sizeof(float)), "d2h");
+			gpu::wait(stop_token);
+			ready.erase(ready.begin(), ready.begin() + ready_pos * ch);
+			const size_t skip = std::min(to_discard, got);
+			to_discard -= skip;
+			ready.insert(ready.end(), host + skip * ch, host + got * ch);
+			ready_pos = cut_and_push(shapes, ready.data(), ready.size() / ch, ch, output_stream, stop_token);
+		}
+	};
+
 	template <class Handle, class Hold, class Create>
 	static void run_on_handle_held(
 		Audio_stream& input_stream, const Output_streams& output_stream, const std::atomic<bool>& stop_token,
@@ -49,32 +82,16 @@ namespace processor
 		nae_ctx* ctx = gpu::context();
 		Handle* h = nullptr;
 		struct Guard { Handle*& h; int (*destroy)(Handle*); ~Guard() { if (h) destroy(h); } } guard{h, ops.destroy};
-		gpu::Device_buffer d_raw, d_f32, d_out;
-		gpu::Pinned_buffer h_raw, h_out;
+		gpu::Device_buffer d_raw, d_f32;
+		gpu::Pinned_buffer h_raw;
 		Intake in;
-		std::vector<float> ready;     // processed samples behind the discarded ones, interleaved, not yet cut into frames
-		size_t ready_pos = 0;         // frames of `ready` already delivered
+		Handle_output out;
+		out.to_discard = to_discard;
 
 		// a failed GPU call is reported by its entry's name (ops.name + suffix), put together only when it failed
 		const auto check = [&](int rc, const char* suffix) { if (rc != NAE_OK) gpu::check(rc, (std::string(ops.name) + suffix).c_str()); };
 
-		// everything the handle has ready comes down behind ONE wait and leaves as frames of the input's sizes
-		const auto deliver = [&]()
-		{
-			const size_t avail = ops.available(h);
-			if (avail == 0) { gpu::wait(stop_token); return; }
-			float* dev = static_cast<float*>(d_out.reserve(avail * in.ch * sizeof(float)));
-			float* host = static_cast<float*>(h_out.reserve(avail * in.ch * sizeof(float)));
-			size_t got = 0;
-			check(ops.receive(h, dev, avail, &got), "_receive");
-			gpu::check(nae_memcpy_d2h(ctx, host, dev, got * in.ch * sizeof(float)), "d2h");
-			gpu::wait(stop_token);
-			ready.erase(ready.begin(), ready.begin() + ready_pos * in.ch);
-			const size_t skip = std::min(to_discard, got);
-			to_discard -= skip;
-			ready.insert(ready.end(), host + skip * in.ch, host + got * in.ch);
-			ready_pos = cut_and_push(in.shapes, ready.data(), ready.size() / in.ch, in.ch, output_stream, stop_token);
-		};
+		const auto deliver = [&]() { out.deliver(h, ops, in.ch, in.shapes, output_stream, stop_token); };
 
 		while (!stop_token)
 		{
@@ -288,56 +305,73 @@ namespace processor
 
 	static const char* const eq_kind_names[] = {"peak", "lowshelf", "highshelf", "lowpass", "highpass", "notch"};
 
+	// a list of bands in audio_eq's format, which audio_sidechain's "key_filter" has too: the defaults are not written
+	static Json::Value bands_to_json(const std::vector<Audio_eq::Band>& bands)
+	{
+		Json::Value list(Json::arrayValue);
+		for (const Audio_eq::Band& b : bands)
+		{
+			Json::Value v;
+			if (b.kind != Audio_eq::Kind::Peak) v["kind"] = eq_kind_names[(int)b.kind];
+			if (b.freq != Audio_eq::Band::default_freq) v["freq"] = b.freq;
+			if (b.gain_db != Audio_eq::Band::default_gain_db) v["gain_db"] = b.gain_db;
+			if (b.q != Audio_eq::Band::default_q) v["q"] = b.q;
+			list.append(v);
+		}
+		return list;
+	}
+
+	// value[key], if there, as at most max_bands bands; the list's own faults are "Wrong field: <key>", a band's "Wrong field: <its key>"
+	static std::vector<Audio_eq::Band> bands_from_json(const Json::Value& value, const char* node_name, const char* key, size_t max_bands)
+	{
+		const auto wrong = [&](const char* field) { return wrong_field(node_name, field); };
+		std::vector<Audio_eq::Band> read;
+		if (!value.isMember(key)) return read;
+		const Json::Value& list = value[key];
+		if (!list.isArray() || list.size() > max_bands) throw wrong(key);
+		for (int i = 0; i < (int)list.size(); i++)
+		{
+			const Json::Value& v = list[i];
+			if (v.isArray() || v.isDouble() || v.isBool() || v.isString()) throw wrong(key);   // an object, possibly without a key
+			Audio_eq::Band b;
+			if (v.isMember("kind"))
+			{
+				if (!v["kind"].isString()) throw wrong("kind");
+				int k = 0;
+				while (k < 6 && v["kind"].asString() != eq_kind_names[k]) k++;
+				if (k == 6) throw wrong("kind");
+				b.kind = (Audio_eq::Kind)k;
+			}
+			const auto real = [&](const char* name, double lo, double hi, double fallback) { return real_from_json(v, node_name, name, lo, hi, fallback); };
+			b.freq = real("freq", 0.0, 1e9, Audio_eq::Band::default_freq);
+			if (!(b.freq > 0.0)) throw wrong("freq");
+			b.gain_db = real("gain_db", -24.0, 24.0, Audio_eq::Band::default_gain_db);
+			b.q = real("q", 0.1, 40.0, Audio_eq::Band::default_q);
+			read.push_back(b);
+		}
+		return read;
+	}
+
+	// the bands' sections at the stream's sample rate (nae_eq_design); a band at or above Nyquist is the user's error
+	static std::vector<double> design_bands(const std::vector<Audio_eq::Band>& bands, int sample_rate)
+	{
+		std::vector<double> coef(bands.size() * 5);
+		for (size_t i = 0; i < bands.size(); i++)
+			if (nae_eq_design((int)bands[i].kind, sample_rate, bands[i].freq, bands[i].gain_db, bands[i].q, coef.data() + 5 * i) != NAE_OK)
+				throw infra::Processor::Runtime_error("Invalid equalizer band", "A band's frequency must lie below half the stream's sample rate.",
+									infra::fmt("band %d: %g Hz at %d Hz", (int)i, bands[i].freq, sample_rate));
+		return coef;
+	}
+
 	Json::Value Audio_eq::serialize() const
 	{
 		Json::Value value;
-		if (bands.empty()) return value;
-		Json::Value list(Json::arrayValue);
-		for (const Band& b : bands)
-		{
-			Json::Value v;
-			if (b.kind != Kind::Peak) v["kind"] = eq_kind_names[(int)b.kind];
-			if (b.freq != Band::default_freq) v["freq"] = b.freq;
-			if (b.gain_db != Band::default_gain_db) v["gain_db"] = b.gain_db;
-			if (b.q != Band::default_q) v["q"] = b.q;
-			list.append(v);
-		}
-		value["bands"] = list;
+		if (!bands.empty()) value["bands"] = bands_to_json(bands);
 		return value;
 	}
 
-	void Audio_eq::deserialize(const Json::Value& value)
-	{
-		const auto wrong = [](const char* field) { return wrong_field("Audio_eq", field); };
-		// everything is read and checked first: a rejected value leaves the node as it was
-		std::vector<Band> read;
-		if (value.isMember("bands"))
-		{
-			const Json::Value& list = value["bands"];
-			if (!list.isArray() || list.size() > max_bands) throw wrong("bands");
-			for (int i = 0; i < (int)list.size(); i++)
-			{
-				const Json::Value& v = list[i];
-				if (v.isArray() || v.isDouble() || v.isBool() || v.isString()) throw wrong("bands");   // an object, possibly without a key
-				Band b;
-				if (v.isMember("kind"))
-				{
-					if (!v["kind"].isString()) throw wrong("kind");
-					int k = 0;
-					while (k < 6 && v["kind"].asString() != eq_kind_names[k]) k++;
-					if (k == 6) throw wrong("kind");
-					b.kind = (Kind)k;
-				}
-				const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(v, "Audio_eq", key, lo, hi, fallback); };
-				b.freq = real("freq", 0.0, 1e9, Band::default_freq);
-				if (!(b.freq > 0.0)) throw wrong("freq");
-				b.gain_db = real("gain_db", -24.0, 24.0, Band::default_gain_db);
-				b.q = real("q", 0.1, 40.0, Band::default_q);
-				read.push_back(b);
-			}
-		}
-		bands = std::move(read);
-	}
+	// everything is read and checked first: a rejected value leaves the node as it was
+	void Audio_eq::deserialize(const Json::Value& value) { bands = bands_from_json(value, "Audio_eq", "bands", max_bands); }
 
 	void Audio_eq::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
@@ -356,11 +390,7 @@ namespace processor
 			io.input, io.output, stop_token, {"nae_eq", nae_eq_put, nae_eq_flush, nae_eq_available, nae_eq_receive, nae_eq_destroy}, "node", 0,
 			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
 			{
-				std::vector<double> coef(bands.size() * 5);
-				for (size_t i = 0; i < bands.size(); i++)
-					if (nae_eq_design((int)bands[i].kind, frame->sample_rate, bands[i].freq, bands[i].gain_db, bands[i].q, coef.data() + 5 * i) != NAE_OK)
-						throw Runtime_error("Invalid equalizer band", "A band's frequency must lie below half the stream's sample rate.",
-											infra::fmt("band %d: %g Hz at %d Hz", (int)i, bands[i].freq, frame->sample_rate));
+				const std::vector<double> coef = design_bands(bands, frame->sample_rate);
 				nae_eq* eq = nullptr;
 				gpu::check(nae_eq_create(ctx, coef.data(), (int)bands.size(), ch, &eq), "nae_eq_create");
 				return eq;
@@ -377,7 +407,7 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_dynamics::get_pin_attributes() const { return io_pins(); }
 
-	Json::Value Audio_dynamics::serialize() const
+	Json::Value Dynamics_settings::to_json() const
 	{
 		Json::Value value;
 		if (mode != Mode::Compressor) value["mode"] = "limiter";
@@ -392,10 +422,10 @@ namespace processor
 		return value;
 	}
 
-	void Audio_dynamics::deserialize(const Json::Value& value)
+	void Dynamics_settings::from_json(const Json::Value& value, const char* node_name)
 	{
-		const auto wrong = [](const char* field) { return wrong_field("Audio_dynamics", field); };
-		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
+		const auto wrong = [&](const char* field) { return wrong_field(node_name, field); };
+		// everything is read and checked first: a rejected value leaves the record as it was; an absent key is its default
 		Mode m = Mode::Compressor;
 		if (value.isMember("mode"))
 		{
@@ -404,7 +434,7 @@ namespace processor
 			if (name == "limiter") m = Mode::Limiter;
 			else if (name != "compressor") throw wrong("mode");
 		}
-		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_dynamics", key, lo, hi, fallback); };
+		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, node_name, key, lo, hi, fallback); };
 		const double t = real("threshold_db", -60.0, 0.0, default_threshold_db);
 		const double r = real("ratio", 1.0, 100.0, default_ratio);
 		const double k = real("knee_db", 0.0, 24.0, default_knee_db);
@@ -423,6 +453,35 @@ namespace processor
 		link_channels = link;
 	}
 
+	void Dynamics_settings::clamp()
+	{
+		threshold_db = std::clamp(threshold_db, -60.0, 0.0);
+		ratio = std::clamp(ratio, 1.0, 100.0);
+		knee_db = std::clamp(knee_db, 0.0, 24.0);
+		attack_ms = std::clamp(attack_ms, 0.0, 500.0);
+		release_ms = std::clamp(release_ms, 1.0, 5000.0);
+		lookahead_ms = std::clamp(lookahead_ms, 0.0, 20.0);
+		makeup_db = std::clamp(makeup_db, -24.0, 24.0);
+	}
+
+	// the settings as the library's parameters at the stream's sample rate (nae_dyn_design); a look-ahead too long for that rate is the user's error
+	static nae_dyn_params design_dynamics(const Dynamics_settings& s, int sample_rate)
+	{
+		nae_dyn_params params;
+		const int rc = nae_dyn_design(sample_rate, s.threshold_db, s.mode == Dynamics_settings::Mode::Limiter ? INFINITY : s.ratio, s.knee_db,
+									  s.attack_ms / 1000.0, s.release_ms / 1000.0, s.lookahead_ms / 1000.0, s.makeup_db, s.link_channels ? 1 : 0, &params);
+		if (rc == NAE_ERR_UNSUPPORTED)
+			throw infra::Processor::Runtime_error("Look-ahead too long", "The look-ahead must not exceed 1024 samples at the stream's sample rate.",
+								infra::fmt("lookahead %g ms at %d Hz", s.lookahead_ms, sample_rate));
+		if (rc != NAE_OK)
+			throw infra::Processor::Runtime_error("Invalid dynamics parameters", "A parameter of the dynamics node lies outside its range.",
+								infra::fmt("nae_dyn_design at %d Hz: code %d", sample_rate, rc));
+		return params;
+	}
+
+	Json::Value Audio_dynamics::serialize() const { return to_json(); }
+	void Audio_dynamics::deserialize(const Json::Value& value) { from_json(value, "Audio_dynamics"); }
+
 	void Audio_dynamics::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
 		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
@@ -435,20 +494,208 @@ namespace processor
 			io.input, io.output, stop_token, {"nae_dyn", nae_dyn_put, nae_dyn_flush, nae_dyn_available, nae_dyn_receive, nae_dyn_destroy}, "node", 0,
 			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
 			{
-				nae_dyn_params params;
-				const int rc = nae_dyn_design(frame->sample_rate, threshold_db, mode == Mode::Limiter ? INFINITY : ratio, knee_db, attack_ms / 1000.0,
-											  release_ms / 1000.0, lookahead_ms / 1000.0, makeup_db, link_channels ? 1 : 0, &params);
-				if (rc == NAE_ERR_UNSUPPORTED)
-					throw Runtime_error("Look-ahead too long", "The look-ahead must not exceed 1024 samples at the stream's sample rate.",
-										infra::fmt("lookahead %g ms at %d Hz", lookahead_ms, frame->sample_rate));
-				if (rc != NAE_OK)
-					throw Runtime_error("Invalid dynamics parameters", "A parameter of the dynamics node lies outside its range.",
-										infra::fmt("nae_dyn_design at %d Hz: code %d", frame->sample_rate, rc));
+				const nae_dyn_params params = design_dynamics(*this, frame->sample_rate);
 				nae_dyn* dyn = nullptr;
 				gpu::check(nae_dyn_create(ctx, &params, ch, &dyn), "nae_dyn_create");
 				return dyn;
 			}
 		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_sidechain
+	infra::Processor::Info Audio_sidechain::get_processor_info()
+	{
+		return {"audio_sidechain", "Audio Side-chain Dynamics", false, [] { return std::unique_ptr<infra::Processor>(new Audio_sidechain); },
+				"Compressor / limiter whose detector listens to a key input, or to the signal through a filter: ducking, de-essing (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_sidechain::get_pin_attributes() const
+	{
+		std::vector<infra::Processor::Pin_attribute> pins = io_pins();
+		pins.push_back({"key", "Key", typeid(Audio_stream), true, [] { return std::make_shared<Audio_stream>(); }});
+		return pins;
+	}
+
+	Json::Value Audio_sidechain::serialize() const
+	{
+		Json::Value value = dynamics.to_json();
+		if (!key_filter.empty()) value["key_filter"] = bands_to_json(key_filter);
+		return value;
+	}
+
+	void Audio_sidechain::deserialize(const Json::Value& value)
+	{
+		// everything is read and checked first: a rejected value leaves the node as it was
+		Dynamics_settings d;
+		d.from_json(value, "Audio_sidechain");
+		std::vector<Audio_eq::Band> bands = bands_from_json(value, "Audio_sidechain", "key_filter", max_bands);
+		dynamics = d;
+		key_filter = std::move(bands);
+	}
+
+	namespace
+	{
+		// One pin of the side-chain node: every frame that waits is taken at once and its samples are kept as interleaved f32 on the host, from
+		// `base` (the stream's sample index of samples[0]) on; `total` samples have arrived.  Packed float frames (and mono planar ones) already
+		// are those samples; the others are converted on the device (upload_as_f32) and come back from there, waited for.
+		struct Pin_intake
+		{
+			int ch = 0, sample_rate = 0;
+			double t0 = 0.0;               // the first frame's pts in seconds
+			bool started = false, ended = false;
+			std::vector<float> samples;
+			size_t base = 0, total = 0;
+			std::deque<Shape> shapes;      // of every frame taken (the input pin's are the output's)
+			gpu::Device_buffer d_raw, d_f32;
+			gpu::Pinned_buffer h_raw, h_f32;
+
+			// -> whether anything came
+			bool take(Audio_stream& stream, const char* what, const std::atomic<bool>& stop_token)
+			{
+				std::vector<Frame_ptr> batch;
+				while (true)
+				{
+					const auto pop_result = stream.try_pop();
+					if (!pop_result.has_value())
+					{
+						ended = stream.eof();
+						break;
+					}
+					batch.push_back(pop_result.value());
+				}
+				if (batch.empty()) return false;
+				const Frame_data* first = batch.front()->data();
+				if (!started)
+				{
+					started = true;
+					ch = first->ch_layout.nb_channels;
+					sample_rate = first->sample_rate;
+					t0 = (double)first->pts * (double)first->time_base.num / (double)first->time_base.den;
+					if (ch != 1 && ch != 2)
+						throw infra::Processor::Runtime_error("Invalid channel count", "Only mono and stereo audio are supported.", infra::fmt("Got %d channels on %s", ch, what));
+				}
+				bool wire = true;
+				for (const auto& f : batch)
+				{
+					const Frame_data* d = f->data();
+					if (d->ch_layout.nb_channels != ch || d->sample_rate != sample_rate)
+						throw infra::Processor::Runtime_error("Stream format changed", "The node runs streams of a fixed channel count and sample rate.",
+															  infra::fmt("Got %d channels at %d Hz after %d at %d Hz on %s", d->ch_layout.nb_channels, d->sample_rate, ch, sample_rate, what));
+					shapes.push_back({d->nb_samples, d->sample_rate, d->pts, d->time_base});
+					wire = wire && (d->format == AV_SAMPLE_FMT_FLT || (d->format == AV_SAMPLE_FMT_FLTP && ch == 1));
+				}
+				if (wire)
+					for (const auto& f : batch)
+					{
+						const float* data = reinterpret_cast<const float*>(f->data()->data[0]);
+						samples.insert(samples.end(), data, data + (size_t)f->data()->nb_samples * ch);
+						total += (size_t)f->data()->nb_samples;
+					}
+				else
+				{
+					size_t n = 0;
+					float* dev = upload_as_f32(batch, h_raw, d_raw, d_f32, &n);
+					float* host = static_cast<float*>(h_f32.reserve(n * ch * sizeof(float)));
+					gpu::check(nae_memcpy_d2h(gpu::context(), host, dev, n * ch * sizeof(float)), "d2h");
+					gpu::wait(stop_token);
+					samples.insert(samples.end(), host, host + n * ch);
+					total += n;
+				}
+				return true;
+			}
+
+			// forget the samples below stream index `upto`
+			void drop(size_t upto)
+			{
+				if (upto <= base) return;
+				samples.erase(samples.begin(), samples.begin() + std::min(samples.size(), (upto - base) * (size_t)ch));
+				base = upto;
+			}
+		};
+	}
+
+	void Audio_sidechain::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Side-chain Dynamics");
+		const auto key_item = infra::get_input_item<Audio_stream>(input, "key");   // not connected: the signal is its own key
+		nae_ctx* ctx = gpu::context();
+		const Handle_ops<nae_dynkey> ops{"nae_dynkey", nae_dynkey_put, nae_dynkey_flush, nae_dynkey_available, nae_dynkey_receive, nae_dynkey_destroy};
+		nae_dynkey* h = nullptr;
+		struct Guard { nae_dynkey*& h; ~Guard() { if (h) nae_dynkey_destroy(h); } } guard{h};
+		Pin_intake in, key;
+		Handle_output out;
+		std::vector<float> frames;   // a put: the signal's channels, then the key's, frame by frame
+		long long o = 0;             // the key sample for input sample n is key[n - o]
+		int key_ch = 0;
+		size_t put = 0;              // input samples put
+		if (!key_item.has_value()) key.ended = true;
+
+		while (!stop_token)
+		{
+			bool moved = in.take(io.input, "the input", stop_token);
+			if (key_item.has_value() && key.take(key_item.value().get(), "the key", stop_token)) moved = true;
+			if (h == nullptr && in.started && (key.started || key.ended))
+			{
+				// the first frames: the key is lined up once, and the handle is made for the input's channels and the key's
+				if (key.started)
+				{
+					if (key.sample_rate != in.sample_rate)
+						throw Runtime_error("Key sample rate differs", "The key must have the input's sample rate.",
+											infra::fmt("key %d Hz, input %d Hz", key.sample_rate, in.sample_rate));
+					if (key.ch != 1 && key.ch != in.ch)
+						throw Runtime_error("Key channel count", "The key must be mono or have the input's channel count.",
+											infra::fmt("key %d channels, input %d", key.ch, in.ch));
+					o = std::llround((key.t0 - in.t0) * (double)in.sample_rate);
+				}
+				// a key pin that ended without a frame keys with silence
+				key_ch = key_item.has_value() ? (key.started ? key.ch : 1) : 0;
+				nae_dynkey_params params{};
+				params.dyn = design_dynamics(dynamics, in.sample_rate);
+				params.key_ch = key_ch;
+				params.n_sections = (int)key_filter.size();
+				const std::vector<double> coef = design_bands(key_filter, in.sample_rate);
+				std::copy(coef.begin(), coef.end(), &params.coef[0][0]);
+				gpu::check(nae_dynkey_create(ctx, &params, in.ch, &h), "nae_dynkey_create");
+			}
+			if (h != nullptr)
+			{
+				// an input sample is put when its key sample has arrived or the key stream has ended
+				size_t upto = in.total;
+				if (key_ch && !key.ended) upto = (size_t)std::clamp<long long>((long long)key.total + o, 0, (long long)in.total);
+				if (upto > put)
+				{
+					const size_t n = upto - put, w = (size_t)(in.ch + key_ch);
+					frames.assign(n * w, 0.0f);   // zero outside what the key stream delivered
+					for (size_t i = 0; i < n; i++)
+					{
+						for (int c = 0; c < in.ch; c++) frames[i * w + c] = in.samples[(put + i - in.base) * in.ch + c];
+						const long long j = (long long)(put + i) - o;
+						if (key_ch && j >= 0 && (size_t)j < key.total)
+							for (int c = 0; c < key_ch; c++) frames[i * w + in.ch + c] = key.samples[((size_t)j - key.base) * key_ch + c];
+					}
+					gpu::check(nae_dynkey_put_host(h, frames.data(), n), "nae_dynkey_put_host");
+					put = upto;
+					in.drop(put);
+					if (key_ch) key.drop((size_t)std::max<long long>((long long)put - o, 0));
+					out.deliver(h, ops, in.ch, in.shapes, io.output, stop_token);
+					moved = true;
+				}
+				if (in.ended && put == in.total)
+				{
+					gpu::check(nae_dynkey_flush(h), "nae_dynkey_flush");
+					out.deliver(h, ops, in.ch, in.shapes, io.output, stop_token);
+					break;
+				}
+			}
+			else if (in.ended && !in.started) break;   // an input without a frame
+			if (!moved) nae_fiber::this_fiber::yield();
+		}
+		for (auto& stream : io.output) stream->set_eof();
 	}
 
 	// ------------------------------------------------------------------------------------------ Audio_denoise

@@ -17,6 +17,7 @@
 #include "audio-reverb.hpp"
 #include "audio-eq.hpp"
 #include "audio-dynamics.hpp"
+#include "audio-sidechain.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "audio-mix.hpp"
@@ -110,14 +111,22 @@ namespace processor
 	void Audio_dynamics::draw_title() {}
 	bool Audio_dynamics::draw_content(bool)
 	{
-		// what the widgets would keep: every value inside its range
-		threshold_db = std::clamp(threshold_db, -60.0, 0.0);
-		ratio = std::clamp(ratio, 1.0, 100.0);
-		knee_db = std::clamp(knee_db, 0.0, 24.0);
-		attack_ms = std::clamp(attack_ms, 0.0, 500.0);
-		release_ms = std::clamp(release_ms, 1.0, 5000.0);
-		lookahead_ms = std::clamp(lookahead_ms, 0.0, 20.0);
-		makeup_db = std::clamp(makeup_db, -24.0, 24.0);
+		clamp();   // what the widgets would keep: every value inside its range
+		return false;
+	}
+
+	void Audio_sidechain::draw_title() {}
+	bool Audio_sidechain::draw_content(bool)
+	{
+		// what the widgets would keep: the dynamics' values inside their ranges, at most 4 bands, every band's value inside its range
+		dynamics.clamp();
+		if (key_filter.size() > max_bands) key_filter.resize(max_bands);
+		for (auto& b : key_filter)
+		{
+			b.freq = std::max(b.freq, 1.0);
+			b.gain_db = std::clamp(b.gain_db, -24.0, 24.0);
+			b.q = std::clamp(b.q, 0.1, 40.0);
+		}
 		return false;
 	}
 

@@ -9,6 +9,7 @@
 #include "processor/audio-dynamics.hpp"
 #include "processor/audio-denoise.hpp"
 #include "processor/audio-loudness.hpp"
+#include "processor/audio-sidechain.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -51,4 +52,7 @@ namespace infra
 
 	// the mastering tools: loudness normalization on the BS.1770 meter; a call of its own, so the six lists above stay what they were
 	void register_mastering_processors() { register_each<processor::Audio_loudness>(); }
+
+	// the side-chain compressor on the keyed dynamics; a call of its own, so the seven lists above stay what they were
+	void register_sidechain_processors() { register_each<processor::Audio_sidechain>(); }
 }
