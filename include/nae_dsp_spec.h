@@ -66,6 +66,13 @@
 #define NAE_DYN_MAX_MAKEUP_DB 24.0
 /* K15 keyed dynamics ("K15 keyed dynamics"): K12 whose detector reads a key through at most this many K11 sections */
 #define NAE_DYNKEY_MAX_SECTIONS 4
+/* K16 echo ("K16 echo"): a feedback delay whose loop is one K11 cascade per chunk.  The delay is at least one K11 chunk, so the
+ * delayed input of a chunk lies wholly in the past; the loop's damping filter has at most NAE_ECHO_MAX_SECTIONS K11 sections; |feedback| is at
+ * most NAE_ECHO_MAX_FEEDBACK */
+#define NAE_ECHO_MIN_DELAY NAE_EQ_CHUNK
+#define NAE_ECHO_MAX_DELAY (1 << 20)
+#define NAE_ECHO_MAX_SECTIONS 4
+#define NAE_ECHO_MAX_FEEDBACK 0.99
 /* K13 spectral gate ("K13 spectral gate"): noise reduction on the STFT at N = 512 ... 4096 and hop N / 4: a per-bin decision
  * against a learned power profile, smoothed by an integer triangle over at most NAE_DENOISE_MAX_TIME frames and NAE_DENOISE_MAX_FREQ bins to
  * either side (a wider frequency triangle pulls a pure tone down: DESIGN.md gives the figure); a tile the library chooses has at least

@@ -21,7 +21,7 @@
 #define NAE_GPU_H
 #include <stddef.h>
 #include <stdint.h>
-#include "nae_dsp_spec.h" /* NAE_DYNKEY_MAX_SECTIONS, the extent of nae_dynkey_params::coef */
+#include "nae_dsp_spec.h" /* NAE_DYNKEY_MAX_SECTIONS and NAE_ECHO_MAX_SECTIONS, the extents of nae_dynkey_params::coef and nae_echo_params::coef */
 
 #ifdef __cplusplus
 extern "C" {
@@ -51,7 +51,8 @@ extern "C" {
  *   nae_loud_design, nae_loud_lufs, nae_loud_measure_f32, nae_loud_apply_f32, nae_loud_normalize_f32 and the measuring handle nae_loud
  *   (nae_loud_create, _put, _put_host, _flush, _get_result, _destroy) with the records nae_loud_params and nae_loud_result: the BS.1770
  *   loudness meter and normalizer, K14; nae_dynkey_block_f32 and the nae_dynkey handle (the same eight entries) with the record
- *   nae_dynkey_params: the keyed (side-chain) dynamics, K15. */
+ *   nae_dynkey_params: the keyed (side-chain) dynamics, K15; nae_echo_design, nae_echo_block_f32 and the nae_echo handle (the same eight
+ *   entries) with the record nae_echo_params: the echo, K16. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -78,6 +79,7 @@ typedef struct nae_conv nae_conv;
 typedef struct nae_eq nae_eq;
 typedef struct nae_dyn nae_dyn;
 typedef struct nae_dynkey nae_dynkey;
+typedef struct nae_echo nae_echo;
 typedef struct nae_denoise nae_denoise;
 typedef struct nae_loud nae_loud;
 
@@ -162,6 +164,8 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *   conv_ring       spectrum slots per stream-channel of the long convolution's workspace ring (0: from the workspace cap; at least the
  *                   partition count is used); a handle reads it when it is created.  Neither changes a result
  *   dn_tile         hop blocks (of n_fft / 4 samples) one wave of the spectral gate walks (0: nae_pick_denoise_tile); every tiling gives the same bits
+ *   echo_group      streams per launch of nae_echo_block_f32 (0: as many as keep the delay lines inside the 256 MiB workspace cap); every grouping
+ *                   gives the same bits
  * The same assignments, comma separated, in the environment variable NAE_DEBUG ("pv_flow=2,pv_fps=4") are applied when a context is created
  * (for measuring a program that creates its contexts itself, e.g. bench.py); an unknown key there fails nae_ctx_create with NAE_ERR_INVALID. */
 int nae_debug_set(nae_ctx* ctx, const char* key, long long value);
@@ -648,6 +652,55 @@ size_t nae_dynkey_available(nae_dynkey* h);
 int nae_dynkey_receive(nae_dynkey* h, float* dst, size_t max_frames, size_t* got);
 int nae_dynkey_receive_host(nae_dynkey* h, float* dst_host, size_t max_frames, size_t* got);
 int nae_dynkey_destroy(nae_dynkey* h);
+
+/* ------------------------------------------------------------------ K16 echo
+ * no reference code.  Spec ("K16 echo"): a feedback delay with a damping filter in the loop and optional ping-pong.  Per
+ * stream-channel c a delay line w_c of f32 samples; s(c) = 1 - c with cross = 1 on a stereo stream, else c; D_c = delay[c] (mono: delay[0]).
+ * For n = 0 ... in_len - 1, every step one IEEE double operation in the order written:
+ *   v_c[n] = n >= D_c ? (double)w_s(c)[n - D_c] : 0
+ *   f_c    = the n_sections biquads of K11 over v_c in K11's tiled form exactly (chunks of NAE_EQ_CHUNK samples from n = 0, zero state in front
+ *            of n = 0, the same tables, order of operations and carry), kept in double; n_sections = 0: f_c = v_c
+ *   w_c[n] = (float)((double)x_c[n] + (feedback f_c[n]))            the line: rounded once per trip
+ *   y_c[n] = (float)((dry (double)x_c[n]) + (wet f_c[n]))
+ * A delay of at least one chunk puts the whole delayed input of a chunk in the past, so the loop needs no scan over the delay: a chunk is one
+ * K11 cascade over known samples.  Input past in_len is zero, output past in_len is not stored; the echoes' tail past in_len is dropped (a
+ * caller who wants it puts zeros).  Bit-exact against the CPU statement (tests/echo_ref/ref_echo.c); any cut of the input into puts gives the
+ * same bits.  A non-finite sample stays in its own stream (and, without cross, in its own channel) and reaches no sample before it.
+ * Stability: with |feedback| < 1 the loop is stable when no section's gain exceeds 1 at any frequency, which holds for what nae_echo_design
+ * makes; with the caller's own coefficients the loop gain is the caller's responsibility: nothing here checks it.
+ * Errors: a null pointer, ch not 1 or 2, feedback, wet or dry not finite, |feedback| > NAE_ECHO_MAX_FEEDBACK, cross not 0 or 1, negative
+ * n_sections, a non-finite or not strictly stable section: NAE_ERR_INVALID; a delay (of a channel the call has) outside
+ * [NAE_ECHO_MIN_DELAY, NAE_ECHO_MAX_DELAY] or more than NAE_ECHO_MAX_SECTIONS sections: NAE_ERR_UNSUPPORTED; in_len = 0 or n_streams = 0:
+ * NAE_OK after the checks, nothing is launched.  Views and aliasing as nae_eq_block_f32's.  The lines of a block call live in a grow-only
+ * workspace of the context; a batch whose lines exceed 256 MiB runs in groups of streams (debug key echo_group). */
+typedef struct nae_echo_params {
+    int delay[2];                                 /* samples per channel, NAE_ECHO_MIN_DELAY ... NAE_ECHO_MAX_DELAY; mono reads delay[0] */
+    double feedback;                              /* g, |g| <= NAE_ECHO_MAX_FEEDBACK */
+    int cross;                                    /* 1: ping-pong, each channel's loop reads the other channel's line (stereo only) */
+    double wet, dry;
+    int n_sections;                               /* 0 ... NAE_ECHO_MAX_SECTIONS */
+    double coef[NAE_ECHO_MAX_SECTIONS][5];        /* the loop's damping filter: K11 sections b0 b1 b2 a1 a2 */
+} nae_echo_params;
+int nae_echo_block_f32(nae_ctx* ctx, const nae_echo_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                       const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch): whole chunks of NAE_EQ_CHUNK frames come out as they fill; nae_echo_flush
+ * releases the partial last chunk, so in_len frames come out in all, equal to the block call's however the input is cut (the chunks are
+ * counted from the stream's first sample).  The handle owns its delay lines and the sections' carries.  A put after the flush: NAE_ERR_STATE. */
+int nae_echo_create(nae_ctx* ctx, const nae_echo_params* params, int channels, nae_echo** h);
+int nae_echo_put(nae_echo* h, const float* interleaved, size_t S);
+int nae_echo_put_host(nae_echo* h, const float* interleaved_host, size_t S);
+int nae_echo_flush(nae_echo* h);
+size_t nae_echo_available(nae_echo* h);
+int nae_echo_receive(nae_echo* h, float* dst, size_t max_frames, size_t* got);
+int nae_echo_receive_host(nae_echo* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_echo_destroy(nae_echo* h);
+/* The record on the host: delay[c] = lround(delay_s sample_rate) for the left and the right channel; damp_hz > 0 adds a NAE_EQ_LOWPASS section,
+ * then lowcut_hz > 0 a NAE_EQ_HIGHPASS section, both by nae_eq_design with q = 1 / sqrt 2 (Butterworth sections: their gain never exceeds 1,
+ * so the designed loop with |feedback| < 1 is stable).  NAE_ERR_INVALID: sample_rate <= 0, a null pointer, an argument that is not finite,
+ * a delay outside [NAE_ECHO_MIN_DELAY, NAE_ECHO_MAX_DELAY] samples at this rate, |feedback| > NAE_ECHO_MAX_FEEDBACK, a negative corner or one
+ * at or above sample_rate / 2, cross not 0 or 1.  No context, no device work. */
+int nae_echo_design(int sample_rate, double delay_s_left, double delay_s_right, double feedback, double damp_hz, double lowcut_hz, double wet,
+                    double dry, int cross, nae_echo_params* out);
 
 /* ------------------------------------------------------------------ K13 spectral gate
  * no reference code.  Spec ("K13 spectral gate"): noise reduction on the STFT at n_fft = 512 ... 4096, hop H = n_fft / 4, in the

@@ -44,6 +44,8 @@ EXPORTED_SYMBOLS = [
     "nae_dyn_receive", "nae_dyn_receive_host", "nae_dyn_destroy",
     "nae_dynkey_block_f32", "nae_dynkey_create", "nae_dynkey_put", "nae_dynkey_put_host", "nae_dynkey_flush", "nae_dynkey_available",
     "nae_dynkey_receive", "nae_dynkey_receive_host", "nae_dynkey_destroy",
+    "nae_echo_design", "nae_echo_block_f32", "nae_echo_create", "nae_echo_put", "nae_echo_put_host", "nae_echo_flush", "nae_echo_available",
+    "nae_echo_receive", "nae_echo_receive_host", "nae_echo_destroy",
     "nae_denoise_design", "nae_denoise_profile_f32", "nae_denoise_block_f32", "nae_denoise_create", "nae_denoise_put", "nae_denoise_put_host",
     "nae_denoise_flush", "nae_denoise_available", "nae_denoise_receive", "nae_denoise_receive_host", "nae_denoise_destroy",
     "nae_loud_design", "nae_loud_lufs", "nae_loud_measure_f32", "nae_loud_apply_f32", "nae_loud_normalize_f32", "nae_loud_create", "nae_loud_put",
@@ -59,7 +61,8 @@ FIR_SIZES = (512, 1024, 2048, 4096)                 # frame sizes of the FIR fil
 FIR_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}   # `kind` of nae_fir_design
 EQ_KINDS = ("peak", "lowshelf", "highshelf", "lowpass", "highpass", "notch")   # `kind` of nae_eq_design: NAE_EQ_PEAK ... NAE_EQ_NOTCH
 DYNKEY_MAX_SECTIONS = 4                             # NAE_DYNKEY_MAX_SECTIONS (include/nae_dsp_spec.h): the key filter's sections
-HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise")   # the handles with the full put / receive set of entries
+ECHO_MIN_DELAY, ECHO_MAX_DELAY, ECHO_MAX_SECTIONS, ECHO_MAX_FEEDBACK = 1024, 1 << 20, 4, 0.99   # NAE_ECHO_* (include/nae_dsp_spec.h)
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -119,6 +122,28 @@ class DynKeyParams(C.Structure):
         p = DynKeyParams()
         p.dyn = dyn
         p.key_ch, p.n_sections = key_ch, coef.shape[0]
+        for s_, row in enumerate(coef):
+            for i_, v in enumerate(row):
+                p.coef[s_][i_] = v
+        return p
+
+
+class EchoParams(C.Structure):
+    """nae_echo_params: the echo's parameters (include/nae_gpu.h): the channels' delays in samples, the feedback, ping-pong, wet and dry, and the
+    loop's damping sections (b0, b1, b2, a1, a2); nae_echo_design makes them from seconds and corner frequencies"""
+    _fields_ = [("delay", C.c_int * 2), ("feedback", C.c_double), ("cross", C.c_int), ("wet", C.c_double), ("dry", C.c_double),
+                ("n_sections", C.c_int), ("coef", (C.c_double * 5) * ECHO_MAX_SECTIONS)]
+
+    @staticmethod
+    def make(delay, feedback: float, cross: bool = False, wet: float = 1.0, dry: float = 1.0, coef=()) -> "EchoParams":
+        """delay: samples, one number or (left, right); coef: [n][5], at most ECHO_MAX_SECTIONS sections (more raise)"""
+        coef = np.asarray(coef, np.float64).reshape(-1, 5)
+        if coef.shape[0] > ECHO_MAX_SECTIONS:
+            raise NaeError(f"nae_echo_params holds at most {ECHO_MAX_SECTIONS} sections")
+        left, right = (delay, delay) if np.isscalar(delay) else delay
+        p = EchoParams()
+        p.delay[0], p.delay[1] = int(left), int(right)
+        p.feedback, p.cross, p.wet, p.dry, p.n_sections = feedback, int(cross), wet, dry, coef.shape[0]
         for s_, row in enumerate(coef):
             for i_, v in enumerate(row):
                 p.coef[s_][i_] = v
@@ -249,6 +274,8 @@ def load_library() -> C.CDLL:
         "nae_dyn_design": (i, [i, d, d, d, d, d, d, d, i, P(DynParams)]), "nae_dyn_block_f32": (i, [vp, P(DynParams), P(Sig), sz, i, sz, P(Sig)]),
         "nae_dyn_create": (i, [vp, P(DynParams), i, P(vp)]),
         "nae_dynkey_block_f32": (i, [vp, P(DynKeyParams), P(Sig), P(Sig), sz, i, sz, P(Sig)]), "nae_dynkey_create": (i, [vp, P(DynKeyParams), i, P(vp)]),
+        "nae_echo_design": (i, [i, d, d, d, d, d, d, d, i, P(EchoParams)]),
+        "nae_echo_block_f32": (i, [vp, P(EchoParams), P(Sig), sz, i, sz, P(Sig)]), "nae_echo_create": (i, [vp, P(EchoParams), i, P(vp)]),
         "nae_denoise_design": (i, [d, d, i, i, i, P(DenoiseParams)]), "nae_denoise_profile_f32": (i, [vp, i, P(Sig), sz, i, vp]),
         "nae_denoise_block_f32": (i, [vp, P(DenoiseParams), vp, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
@@ -671,6 +698,22 @@ class Context:
         coef = np.ascontiguousarray(coef, np.float64).reshape(-1, 5)
         self._ck(self.lib.nae_eq_block_f32(self.h, coef.ctypes.data, coef.shape[0], C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K16
+    @staticmethod
+    def echo_design(sample_rate: int, delay_s: float = 0.35, delay_s_right: Optional[float] = None, feedback: float = 0.4, damp_hz: float = 0.0,
+                    lowcut_hz: float = 0.0, wet: float = 0.35, dry: float = 1.0, cross: bool = False) -> "EchoParams":
+        """the echo's parameters from seconds and corner frequencies (nae_echo_design); delay_s_right None: the left delay"""
+        out = EchoParams()
+        right = delay_s if delay_s_right is None else delay_s_right
+        rc = load_library().nae_echo_design(sample_rate, delay_s, right, feedback, damp_hz, lowcut_hz, wet, dry, int(cross), C.byref(out))
+        if rc:
+            raise NaeError(f"nae_echo_design({sample_rate}, {delay_s}, {right}, {feedback}, {damp_hz}, {lowcut_hz}, {wet}, {dry}, {cross}) failed: {rc}")
+        return out
+
+    def echo_block(self, params: "EchoParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the echo `params` over every stream (nae_echo_block_f32); dst receives in_len frames"""
+        self._ck(self.lib.nae_echo_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     # -- K12
     @staticmethod
     def dyn_design(sample_rate: int, threshold_db: float = -18.0, ratio: float = 4.0, knee_db: float = 6.0, attack_s: float = 0.005,
@@ -886,6 +929,16 @@ class DynKey(_Handle):
     def put_host(self, x: np.ndarray) -> None:
         x = np.ascontiguousarray(x, np.float32)
         self.ctx._ck(self._fn("put_host")(self.h, x.ctypes.data, x.size // self.in_width))
+
+
+class Echo(_Handle):
+    """The echo's streaming handle (nae_echo_create): put interleaved f32, flush (the partial last chunk; the echoes' tail is dropped), receive."""
+
+    _prefix = "nae_echo"
+
+    def __init__(self, ctx: Context, params: EchoParams, channels: int):
+        super().__init__(ctx, channels)
+        ctx._ck(ctx.lib.nae_echo_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
 
 
 class Denoise(_Handle):

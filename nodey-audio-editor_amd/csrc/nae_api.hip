@@ -270,6 +270,7 @@ int nae_debug_set(nae_ctx* ctx, const char* key, long long value)
     else if (k == "dn_tile" && count) ctx->dn_tile = (int)value;
     else if (k == "conv_tile" && count) ctx->conv_tile = (int)value;
     else if (k == "conv_ring" && count) ctx->conv_ring = (int)value;
+    else if (k == "echo_group" && count) ctx->echo_group = (int)value;
     else if (k == "pv_fps" && one_of({0, 1, 2, 4})) ctx->pv_fps = (int)value;
     else if (k == "pv_flow" && one_of({0, 1, 2})) ctx->pv_flow = (int)value;
     else if (k == "pv_lean" && flag) ctx->pv_lean = value != 0;
@@ -360,6 +361,7 @@ int nae_ctx_destroy(nae_ctx* ctx)
     nae_conv_cache_free(ctx);
     nae_eq_cache_free(ctx);
     nae_loud_cache_free(ctx);
+    nae_echo_cache_free(ctx);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return NAE_OK;

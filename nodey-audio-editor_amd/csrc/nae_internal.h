@@ -50,6 +50,9 @@ struct nae_ctx {
     void* d_loud_block = nullptr;
     std::vector<double> h_loud_coef;
     void* ws_loud = nullptr; size_t ws_loud_bytes = 0;
+    // nae_echo_block_f32's delay lines, one ring per stream-channel of a launch group (kernels_echo.hip)
+    void* ws_echo = nullptr; size_t ws_echo_bytes = 0;
+    int echo_group = 0;          // streams per launch of the echo's block call; 0 = from NAE_CONV_WS_BYTES
     // tuning / A-B switches: nae_debug_set(ctx, key, value) (include/nae_gpu.h lists the keys; NAE_DEBUG="key=value,..." applies them at context creation)
     bool dbg_st_unfused = false;     // st_unfused: WSOLA chain runs filter and cubic stage as separate launches
     int dbg_td_nc = 0;               // td_nc = 1|2|4: candidates per thread of the WSOLA search (0: by batch size)
@@ -300,6 +303,17 @@ int nae_dynkey_check(nae_ctx* ctx, const nae_dynkey_params* p, int ch);
 size_t nae_dynkey_filter_doubles(const nae_dynkey_params* p, int ch, size_t n_streams);
 int nae_launch_dynkey(nae_ctx* ctx, const nae_dynkey_params* p, const double* d_block, const nae_sig* src, const nae_sig* key, size_t in_len, int ch,
                       size_t n_streams, const nae_sig* dst, size_t c_origin, size_t c_stop, double* d_state, double* d_fstate);
+
+// kernels_echo.hip: the echo ("K16 echo").  nae_echo_check: the parameter rules of the block call and the handle.  nae_echo_ring: R, the
+// samples of a stream-channel's delay line.  nae_launch_echo runs chunks [c_origin, c_stop) of absolutely indexed signals, one workgroup per
+// stream: d_block is the sections' K11 constant block (unused with no section); d_line, n_streams x ch rings of R floats, holds every line's
+// last R samples by absolute index mod R (never read in front of sample 0: nothing to clear); d_state, [stream-channel][NAE_ECHO_MAX_SECTIONS][2]
+// doubles, is the sections' carry in front of c_origin and receives the one behind c_stop - 1 (null: zero, and nothing kept).
+int nae_echo_check(nae_ctx* ctx, const nae_echo_params* p, int ch);
+size_t nae_echo_ring(const nae_echo_params* p, int ch);
+int nae_launch_echo(nae_ctx* ctx, const nae_echo_params* p, const double* d_block, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                    const nae_sig* dst, size_t c_origin, size_t c_stop, float* d_line, double* d_state);
+void nae_echo_cache_free(nae_ctx* ctx);
 
 // kernels_denoise.hip: the spectral gate ("K13 spectral gate").  nae_denoise_check: the parameter rules of the block call and the
 // handle.  nae_launch_denoise runs hop blocks [b_origin, b_stop) of absolutely indexed signals of in_len samples: it reads from

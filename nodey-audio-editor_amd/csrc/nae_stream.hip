@@ -77,6 +77,16 @@ struct nae_dynkey : BlockHandle {
     int process() override;
 };
 
+// the echo's handle ("K16 echo"): whole chunks of NAE_EQ_CHUNK samples are computed as they fill; the delay lines and the sections' carry
+// between two launches stay on the device.  Chunks are counted from the stream's first sample, so any cut into puts gives the block call's bits
+struct nae_echo : BlockHandle {
+    nae_echo_params params;
+    double* d_block = nullptr;     // the sections' coefficients and tables (nae_eq_make_block); null with no section
+    float* d_line = nullptr;       // [ch][nae_echo_ring()]: the lines' last samples, by absolute index mod the ring
+    double* d_state = nullptr;     // [ch][NAE_ECHO_MAX_SECTIONS][2]: every section's (z1, z2) behind the last chunk done
+    int process() override;
+};
+
 // the spectral gate's handle ("K13 spectral gate"): whole hop blocks of n_fft / 4 samples are computed once the time_smooth + 3
 // blocks behind them are there; the input stays from time_smooth + 3 blocks in front of the next block on, and nothing else is kept
 struct nae_denoise : BlockHandle {
@@ -327,6 +337,13 @@ int nae_dynkey::process()
         // the key's channels stand behind the signal's in every frame
         const nae_sig key{static_cast<float*>(src.base) + ch, src.stream_stride, src.chan_stride, src.frame_stride};
         return nae_launch_dynkey(ctx, &params, d_block, &src, &key, in.total, ch, 1, &dst, from, to, d_state, d_fstate);
+    });
+}
+
+int nae_echo::process()
+{
+    return run_units(NAE_EQ_CHUNK, 0, 0, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
+        return nae_launch_echo(ctx, &params, d_block, &src, in.total, ch, 1, &dst, from, to, d_line, d_state);
     });
 }
 
@@ -615,6 +632,38 @@ size_t nae_dynkey_available(nae_dynkey* h) { return handle_available(h); }
 int nae_dynkey_receive(nae_dynkey* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_dynkey_receive_host(nae_dynkey* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_dynkey_destroy(nae_dynkey* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ echo
+int nae_echo_create(nae_ctx* ctx, const nae_echo_params* params, int channels, nae_echo** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_echo_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_echo* s = handle_new<nae_echo>(ctx, channels);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    const size_t state_doubles = (size_t)channels * NAE_ECHO_MAX_SECTIONS * 2;
+    // the lines are not cleared: sample n - D of a line is read only once it has been written
+    rc = s->dev_alloc(&s->d_line, (size_t)channels * nae_echo_ring(params, channels), "hipMalloc(echo lines)");
+    if (!rc) rc = s->dev_alloc(&s->d_state, state_doubles, "hipMalloc(echo state)");
+    if (!rc) rc = nae_check(ctx, hipMemsetAsync(s->d_state, 0, state_doubles * sizeof(double), ctx->stream), "hipMemsetAsync(echo state)");
+    if (!rc && params->n_sections) {
+        rc = s->dev_alloc(&s->d_block, nae_eq_block_doubles(), "hipMalloc(echo tables)");
+        if (!rc) rc = nae_eq_make_block(ctx, &params->coef[0][0], params->n_sections, s->d_block);
+    }
+    return handle_created(s, rc, h);
+}
+
+int nae_echo_put(nae_echo* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_echo_put_host(nae_echo* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+// flush: the partial last chunk comes out: as many frames as were put over the handle's life (the echoes' tail is dropped: flush_tail = 0)
+int nae_echo_flush(nae_echo* h) { return handle_flush(h); }
+size_t nae_echo_available(nae_echo* h) { return handle_available(h); }
+int nae_echo_receive(nae_echo* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_echo_receive_host(nae_echo* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_echo_destroy(nae_echo* h) { return handle_destroy(h); }
 
 // ------------------------------------------------------------------------------------------------ spectral gate
 int nae_denoise_create(nae_ctx* ctx, const nae_denoise_params* params, const float* profile_dev, int profile_ch, int channels, nae_denoise** h)

@@ -159,4 +159,6 @@ namespace infra
 	void register_mastering_processors();
 	// the side-chain compressor (audio_sidechain): called after the seven above, each of which stays the list it was
 	void register_sidechain_processors();
+	// the echo (audio_echo): called after the eight above, each of which stays the list it was
+	void register_echo_processors();
 }

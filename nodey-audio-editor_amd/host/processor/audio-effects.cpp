@@ -1,5 +1,5 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
-// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
+// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 // Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
 #include "audio-filter.hpp"
@@ -7,6 +7,7 @@
 #include "audio-eq.hpp"
 #include "audio-dynamics.hpp"
 #include "audio-sidechain.hpp"
+#include "audio-echo.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "node-util.hpp"
@@ -696,6 +697,89 @@ namespace processor
 			if (!moved) nae_fiber::this_fiber::yield();
 		}
 		for (auto& stream : io.output) stream->set_eof();
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_echo
+	infra::Processor::Info Audio_echo::get_processor_info()
+	{
+		return {"audio_echo", "Audio Echo", false, [] { return std::unique_ptr<infra::Processor>(new Audio_echo); },
+				"Echo: a feedback delay with damped repeats, per-channel delay times and ping-pong between the channels (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_echo::get_pin_attributes() const { return io_pins(); }
+
+	Json::Value Audio_echo::serialize() const
+	{
+		Json::Value value;
+		if (delay_ms != default_delay_ms) value["delay_ms"] = delay_ms;
+		if (delay_ms_right.has_value()) value["delay_ms_right"] = *delay_ms_right;
+		if (feedback != default_feedback) value["feedback"] = feedback;
+		if (ping_pong) value["ping_pong"] = true;
+		if (damp_hz != default_damp_hz) value["damp_hz"] = damp_hz;
+		if (lowcut_hz != default_lowcut_hz) value["lowcut_hz"] = lowcut_hz;
+		if (wet != default_wet) value["wet"] = wet;
+		if (dry != default_dry) value["dry"] = dry;
+		return value;
+	}
+
+	void Audio_echo::deserialize(const Json::Value& value)
+	{
+		const auto wrong = [](const char* field) { return wrong_field("Audio_echo", field); };
+		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
+		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_echo", key, lo, hi, fallback); };
+		// a delay has no range of its own but its sign: what it may be depends on the stream's sample rate (process_payload)
+		const auto delay = [&](const char* key, double fallback) {
+			const double d = real(key, 0.0, 1e9, fallback);
+			if (!(d > 0.0)) throw wrong(key);
+			return d;
+		};
+		// a corner: 0 for none, else inside [lo, hi]
+		const auto corner = [&](const char* key, double lo, double hi) {
+			const double hz = real(key, 0.0, hi, 0.0);
+			if (hz != 0.0 && hz < lo) throw wrong(key);
+			return hz;
+		};
+		const double d = delay("delay_ms", default_delay_ms);
+		std::optional<double> dr;
+		if (value.isMember("delay_ms_right")) dr = delay("delay_ms_right", default_delay_ms);
+		const double g = real("feedback", 0.0, 0.95, default_feedback);
+		const bool pp = bool_from_json(value, "Audio_echo", "ping_pong");
+		const double dh = corner("damp_hz", 200.0, 20000.0), lh = corner("lowcut_hz", 20.0, 2000.0);
+		const double w = real("wet", 0.0, 1.0, default_wet), dy = real("dry", 0.0, 1.0, default_dry);
+		delay_ms = d; delay_ms_right = dr; feedback = g; ping_pong = pp; damp_hz = dh; lowcut_hz = lh; wet = w; dry = dy;
+	}
+
+	void Audio_echo::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Echo");
+		run_on_handle<nae_echo>(
+			io.input, io.output, stop_token, {"nae_echo", nae_echo_put, nae_echo_flush, nae_echo_available, nae_echo_receive, nae_echo_destroy}, "node", 0,
+			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
+			{
+				// the delays at the stream's sample rate: the library runs 1024 ... 1048576 samples
+				const double right_ms = delay_ms_right.value_or(delay_ms);
+				for (const double ms : {delay_ms, right_ms})
+				{
+					const double samples = ms / 1000.0 * frame->sample_rate;
+					const long long n = std::llround(std::min(samples, 1e12));
+					if (n < NAE_ECHO_MIN_DELAY || n > NAE_ECHO_MAX_DELAY)
+						throw Runtime_error("Echo delay out of range", "The delay must be 1024 to 1048576 samples at the stream's sample rate.",
+											infra::fmt("delay %g ms at %d Hz: %g samples", ms, frame->sample_rate, samples));
+				}
+				nae_echo_params params;
+				if (nae_echo_design(frame->sample_rate, delay_ms / 1000.0, right_ms / 1000.0, feedback, damp_hz, lowcut_hz, wet, dry, ping_pong ? 1 : 0, &params) != NAE_OK)
+					throw Runtime_error("Invalid echo parameters", "The loop filter's corner frequencies must lie below half the stream's sample rate.",
+										infra::fmt("damp %g Hz, low cut %g Hz at %d Hz", damp_hz, lowcut_hz, frame->sample_rate));
+				nae_echo* echo = nullptr;
+				gpu::check(nae_echo_create(ctx, &params, ch, &echo), "nae_echo_create");
+				return echo;
+			}
+		);
 	}
 
 	// ------------------------------------------------------------------------------------------ Audio_denoise

@@ -18,6 +18,7 @@
 #include "audio-eq.hpp"
 #include "audio-dynamics.hpp"
 #include "audio-sidechain.hpp"
+#include "audio-echo.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "audio-mix.hpp"
@@ -127,6 +128,20 @@ namespace processor
 			b.gain_db = std::clamp(b.gain_db, -24.0, 24.0);
 			b.q = std::clamp(b.q, 0.1, 40.0);
 		}
+		return false;
+	}
+
+	void Audio_echo::draw_title() {}
+	bool Audio_echo::draw_content(bool)
+	{
+		// what the widgets would keep: every value inside its range; a corner between 0 and its lowest value is that value
+		delay_ms = std::clamp(delay_ms, 1.0, 1e9);
+		if (delay_ms_right.has_value()) delay_ms_right = std::clamp(*delay_ms_right, 1.0, 1e9);
+		feedback = std::clamp(feedback, 0.0, 0.95);
+		if (damp_hz != 0.0) damp_hz = std::clamp(damp_hz, 200.0, 20000.0);
+		if (lowcut_hz != 0.0) lowcut_hz = std::clamp(lowcut_hz, 20.0, 2000.0);
+		wet = std::clamp(wet, 0.0, 1.0);
+		dry = std::clamp(dry, 0.0, 1.0);
 		return false;
 	}
 

@@ -10,6 +10,7 @@
 #include "processor/audio-denoise.hpp"
 #include "processor/audio-loudness.hpp"
 #include "processor/audio-sidechain.hpp"
+#include "processor/audio-echo.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -55,4 +56,7 @@ namespace infra
 
 	// the side-chain compressor on the keyed dynamics; a call of its own, so the seven lists above stay what they were
 	void register_sidechain_processors() { register_each<processor::Audio_sidechain>(); }
+
+	// the delay effects: the echo; a call of its own, so the eight lists above stay what they were
+	void register_echo_processors() { register_each<processor::Audio_echo>(); }
 }
