@@ -1,8 +1,10 @@
 """What the GPU tests of the block entries and their streaming handles share (FIR filter, long convolution, equalizer, dynamics: tests/fir_gpu.py,
 eq_gpu.py, dyn_gpu.py and tests/test_gpu_conv.py bind their entries to it): the views every block entry is called in, a bit view, the noise,
 the CPU statements built once per process, `view_call` (a block call with guard words around the signals) and `stream` (the put loop of a
-handle).  tests/test_block_harness_cpu.py pins, without a GPU, that the guards catch what they are there to catch."""
+handle); for the large batches of tests/test_gpu_batch.py, `each_stream` (a statement on every stream) and `mismatch` (which streams differ).
+tests/test_block_harness_cpu.py pins, without a GPU, that the guards catch what they are there to catch."""
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -26,6 +28,30 @@ def statement(ref_module):
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def each_stream(fn, n_streams):
+    """np.stack of fn(0) ... fn(n_streams - 1): a statement on every stream of a large batch, on a few threads.  The statements are C calls
+    through ctypes, which releases the interpreter's lock around them, and they keep no state between calls, so the result does not depend
+    on the threads; fn(0) runs first and alone."""
+    if n_streams < 16:
+        return np.stack([fn(i) for i in range(n_streams)])
+    first = fn(0)
+    with ThreadPoolExecutor(max_workers=8) as pool:
+        return np.stack([first] + list(pool.map(fn, range(1, n_streams))))
+
+
+def mismatch(got, want, first=8):
+    """"" where got[streams, n, ch] has want's bits; else a message for an assertion on a large batch: how many streams differ, and the first
+    few (stream, channel, first differing sample, differing samples) of them: a pattern in the indices is the diagnosis"""
+    assert got.shape == want.shape, (got.shape, want.shape)
+    diff = bits(got) != bits(want)
+    pairs = np.argwhere(diff.any(axis=1))
+    if len(pairs) == 0:
+        return ""
+    where = [(int(s), int(c), int(np.argmax(diff[s, :, c])), int(diff[s, :, c].sum())) for s, c in pairs[:first]]
+    return (f"{len(np.unique(pairs[:, 0]))} of {got.shape[0]} streams differ ({len(pairs)} stream-channels); "
+            f"first (stream, channel, first sample, samples): {where}")
 
 
 def noise(rng, n_streams, n, ch, shared=False):

@@ -1,15 +1,21 @@
 """K11 biquad cascade on the GPU, bit for bit against the CPU statement (tests/eq_ref/ref_eq.c): every length around the lane and the chunk,
-short and long cascades, every view, a launch of many workgroups, a launch of 300 chunks, the streaming handle in short and in long streams,
-non-finite and subnormal input, the error codes, and the host node (tests/eq_ref/host_eq_node.cpp)."""
+short and long cascades, every view, a launch of many workgroups, a launch of 300 chunks, the context's table cache under its three users
+(nae_eq_block_f32, nae_echo_block_f32, nae_dynkey_block_f32), the streaming handle in short and in long streams, non-finite and subnormal
+input, the error codes, and the host node (tests/eq_ref/host_eq_node.cpp)."""
 import ctypes as C
 import subprocess
 
 import numpy as np
 import pytest
 
+import dyn_ref
+import dynkey_ref
+import echo_ref
 import eq_ref
 import node_harness
 from block_gpu import CONFIGS, bits, noise, statement
+from dynkey_gpu import lib_params as dynkey_params
+from echo_gpu import lib_params as echo_params
 from eq_gpu import eq_stream, gpu_eq
 
 pytestmark = pytest.mark.gpu
@@ -95,6 +101,93 @@ def test_the_context_keeps_its_tables_and_takes_new_ones(nae, ctx, ref):
     a, b = eq_ref.cascade(3), eq_ref.cascade(5)[2:]
     for coef in (a, a, b, a):
         assert np.array_equal(bits(gpu_eq(nae, ctx, coef, x)), bits(eq_ref.run_streams(ref, coef, x)))
+
+
+def cache_steps():
+    """(entry, coefficients, what the step is there for): nae_eq_cached_block keeps one constant block per context, keyed by the last
+    coefficients, and the equalizer, the echo (its loop filter) and the keyed dynamics (its key filter) all go through it"""
+    a, b, other = eq_ref.cascade(4), eq_ref.cascade(6)[4:], eq_ref.cascade(9)[6:]
+    return (("eq", a, "A"), ("echo", a, "A from another entry: a hit"), ("eq", a[:2], "A's first two: the bytes are a prefix, only the count differs"),
+            ("dynkey", b, "B after A[:2]: a miss on the same count"), ("echo", None, "an echo without sections: it does not ask the cache"),
+            ("dynkey", b, "B behind the echo without sections: a hit"), ("handle", other, "a handle with other coefficients: its upload waits for the stream"),
+            ("echo", b, "B behind the handle: the handle's tables are its own"), ("eq", a, "A after B: a miss on another count"),
+            ("dynkey", a[:2], "A then A[:2] from another entry"), ("echo", a[:2], "a hit"), ("eq", a, "the first set again"))
+
+
+def cache_walk(nae, contexts, orders, x, key):
+    """orders[k][i] is issued on contexts[k], step by step across the contexts, with no sync between the calls (the outputs are downloaded
+    behind the last one) -> [k][i] the outputs of the block calls, None for a handle's step"""
+    n_streams, n, ch = x.shape
+    dev = []
+    for c, order in zip(contexts, orders):
+        dev.append((c.array(x.reshape(-1)), c.array(key.reshape(-1)), [None if entry == "handle" else c.empty(x.size) for entry, _, _ in order]))
+    handles = []
+    try:
+        for i in range(len(orders[0])):
+            for c, order, (d_x, d_key, d_ys) in zip(contexts, orders, dev):
+                entry, coef, _ = order[i]
+                if entry == "handle":
+                    handles.append(nae.Eq(c, coef, ch))
+                    continue
+                src, ksig, dst = (nae.Sig.interleaved(d.ptr, n, ch) for d in (d_x, d_key, d_ys[i]))
+                if entry == "eq":
+                    c.eq_block(coef, src, n, ch, n_streams, dst)
+                elif entry == "echo":
+                    c.echo_block(echo_params(nae, cache_echo(coef)), src, n, ch, n_streams, dst)
+                else:
+                    c.dynkey_block(dynkey_params(nae, cache_dynkey(coef)), src, ksig, n, ch, n_streams, dst)
+        return [[None if d is None else d.download().reshape(x.shape) for d in d_ys] for _, _, d_ys in dev]
+    finally:
+        for h in handles:
+            h.close()
+        for d_x, d_key, d_ys in dev:
+            for d in [d_x, d_key] + [d for d in d_ys if d is not None]:
+                d.free()
+
+
+def cache_echo(coef):
+    return echo_ref.params((1024, 1500), 0.5, 1, 0.6, 0.8, () if coef is None else coef)
+
+
+def cache_dynkey(coef):
+    return dynkey_ref.params(dyn_ref.params(lookahead=17, link=1, alpha_attack=dyn_ref.alpha(0.002), alpha_release=dyn_ref.alpha(0.05)), 2, coef)
+
+
+def test_the_table_cache_under_its_three_users(nae, ctx):
+    """every call of the walk equals the statement for ITS coefficients: on one context, then on that context and a second one whose walk is
+    three steps ahead, call by call, so that each context must keep its own tables (tests/test_gpu_multi_ctx.py does this for the FIR filter)"""
+    rng = np.random.default_rng(61)
+    x = noise(rng, 2, 2 * 3072 + 7, 2)
+    key = noise(rng, 2, 2 * 3072 + 7, 2)
+    steps = cache_steps()
+    refs = {"eq": statement(eq_ref), "echo": statement(echo_ref), "dynkey": statement(dynkey_ref)}
+
+    def want(entry, coef):
+        if entry == "eq":
+            return eq_ref.run_streams(refs["eq"], coef, x)
+        if entry == "echo":
+            return echo_ref.run_streams(refs["echo"], cache_echo(coef), x)
+        return dynkey_ref.run_streams(refs["dynkey"], cache_dynkey(coef), x, key)
+
+    wants = {what: want(entry, coef) for entry, coef, what in steps if entry != "handle"}
+    distinct = {bits(w).tobytes() for w in wants.values()}
+    assert len(distinct) == len({(e, None if c is None else c.tobytes()) for e, c, _ in steps if e != "handle"}), "other coefficients, other bits"
+
+    def check(got, order, label):
+        for i, (entry, coef, what) in enumerate(order):
+            if entry != "handle":
+                w = wants[what]
+                assert np.array_equal(bits(got[i]), bits(w)), (label, i, entry, what, int(np.sum(bits(got[i]) != bits(w))))
+
+    check(cache_walk(nae, [ctx], [steps], x, key)[0], steps, "one context")
+    second = nae.Context(0)
+    try:
+        ahead = steps[3:] + steps[:3]
+        got = cache_walk(nae, [ctx, second], [steps, ahead], x, key)
+        check(got[0], steps, "first of two contexts")
+        check(got[1], ahead, "second of two contexts")
+    finally:
+        second.close()
 
 
 @pytest.mark.parametrize("ch", (1, 2))

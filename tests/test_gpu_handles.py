@@ -1,7 +1,7 @@
-"""One contract for the put / receive handles (nae_fir, nae_conv, nae_eq, nae_dyn, nae_stretch), through the C entries: puts that cross a
-unit boundary and leave a partial last unit, receives in pieces into device and host memory, the state after the flush, and the output,
-bit for bit the block entry's on the whole input, in the length include/nae_gpu.h states.  For the FIR filter and the convolution the block
-entry runs on the input extended by n_taps - 1 zero frames: that is what the header says a flushed handle delivers."""
+"""One contract for the put / receive handles (nae_fir, nae_conv, nae_eq, nae_dyn, nae_denoise, nae_dynkey, nae_echo, nae_stretch), through the C
+entries: puts that cross a unit boundary and leave a partial last unit, receives in pieces into device and host memory, the state after the
+flush, and the output, bit for bit the block entry's on the whole input, in the length include/nae_gpu.h states.  For the FIR filter and the
+convolution the block entry runs on the input extended by n_taps - 1 zero frames: that is what the header says a flushed handle delivers."""
 import ctypes as C
 import os
 import re
@@ -78,6 +78,41 @@ def dyn_case(nae, ctx):
     return x, lambda h: lib.nae_dyn_create(ctx.h, C.byref(params), 2, h), want, 48
 
 
+def denoise_case(nae, ctx):
+    """n_fft 512 against the profile nae_denoise_profile_f32 measures on device from an excerpt of steady noise; the input's level wanders
+    around the excerpt's, so the gate opens and closes.  The handle copies the profile at creation"""
+    lib = ctx.lib
+    t = np.arange(3000)[:, None]
+    x = (noise(7, 3000, 2) * 10.0 ** (14.0 * np.sin(2 * np.pi * t / 1500.0 + np.array([0.0, 2.0])) / 20.0)).astype(np.float32)
+    params = nae.DenoiseParams(512, 2, 2, 1.0, 0.25)
+    d_n, d_p = ctx.array(noise(8, 4096, 2).reshape(-1)), ctx.empty(2 * 257)
+    assert lib.nae_denoise_profile_f32(ctx.h, 512, C.byref(nae.Sig(d_n.ptr, 0, 1, 2)), 4096, 2, d_p.ptr) == OK
+    want = block(nae, ctx, x, len(x), lambda s, n, ch, d: lib.nae_denoise_block_f32(ctx.h, C.byref(params), d_p.ptr, 2, s, n, ch, 1, d))
+    assert 1e-3 < np.abs(want - x).max() and 1e-3 < np.abs(want - np.float32(0.25) * x).max(), "neither the input nor all at the floor gain"
+    d_n.free()
+    return x, lambda h: lib.nae_denoise_create(ctx.h, C.byref(params), d_p.ptr, 2, 2, h), want, None
+
+
+def dynkey_case(nae, ctx):
+    """self-keyed through two sections (key_ch = 0), so a put frame is `ch` floats; look-ahead 48"""
+    lib, x = ctx.lib, noise(9, 2500, 2)
+    coef = [nae.Context.eq_design("highpass", 48000, 150.0), nae.Context.eq_design("peak", 48000, 3000.0, 6.0, 1.0)]
+    params = nae.DynKeyParams.make(nae.Context.dyn_design(48000, lookahead_s=0.001, link=True), 0, coef)
+    assert params.dyn.lookahead == 48 and params.n_sections == 2
+    want = block(nae, ctx, x, len(x), lambda s, n, ch, d: lib.nae_dynkey_block_f32(ctx.h, C.byref(params), s, None, n, ch, 1, d))
+    return x, lambda h: lib.nae_dynkey_create(ctx.h, C.byref(params), 2, h), want, 48
+
+
+def echo_case(nae, ctx):
+    """ping-pong at delays 1024 and 1500 through two sections; 3 R + 7 frames wrap the handle's ring three times"""
+    lib = ctx.lib
+    coef = [nae.Context.eq_design("lowpass", 48000, 4000.0), nae.Context.eq_design("highpass", 48000, 150.0)]
+    params = nae.EchoParams.make((1024, 1500), -0.9, True, 0.6, 0.8, coef)
+    x = noise(10, 3 * 3072 + 7, 2)
+    want = block(nae, ctx, x, len(x), lambda s, n, ch, d: lib.nae_echo_block_f32(ctx.h, C.byref(params), s, n, ch, 1, d))
+    return x, lambda h: lib.nae_echo_create(ctx.h, C.byref(params), 2, h), want, None
+
+
 def stretch_case(nae, ctx):
     lib, x = ctx.lib, noise(6, 8192, 1)
     pitch = float(np.float32(2 ** (3 / 12)))   # the handle takes floats
@@ -86,9 +121,10 @@ def stretch_case(nae, ctx):
     return x, lambda h: lib.nae_stretch_create(ctx.h, 48000, 1, 1.0, pitch, h), want, None
 
 
-CASES = {"fir": fir_case, "conv": conv_case, "eq": eq_case, "dyn": dyn_case, "stretch": stretch_case}
+CASES = {"fir": fir_case, "conv": conv_case, "eq": eq_case, "dyn": dyn_case, "denoise": denoise_case, "dynkey": dynkey_case, "echo": echo_case,
+         "stretch": stretch_case}
 # the lengths the header states: in_len + n_taps - 1, in_len, the plan's out_len (stretch_case: `want` has it)
-OUT_LEN = {"fir": 3000 + 31 - 1, "conv": 3000 + 700 - 1, "eq": 2500, "dyn": 2500}
+OUT_LEN = {"fir": 3000 + 31 - 1, "conv": 3000 + 700 - 1, "eq": 2500, "dyn": 2500, "denoise": 3000, "dynkey": 2500, "echo": 3 * 3072 + 7}
 
 
 @pytest.mark.parametrize("prefix", CASES)

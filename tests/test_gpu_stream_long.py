@@ -1,16 +1,27 @@
-"""Long streams through every streaming handle (nae_stretch, nae_wsola, nae_swr, nae_spectrum, nae_fir): 300 000+ frames in an
-uneven cycle of put sizes, with receives that take everything, part of what is available or nothing.  Every device FIFO
-of the handles grows several times and is compacted many times; the output equals the block call, the oracle or the CPU
-statement bit for bit."""
+"""Long streams through every streaming handle (nae_stretch, nae_wsola, nae_swr, nae_spectrum, nae_fir and the block-handle family nae_eq,
+nae_dyn, nae_dynkey, nae_echo, nae_conv, nae_denoise): 300 000+ frames in an uneven cycle of put sizes, with receives that take
+everything, part of what is available or nothing.  Every device FIFO of the handles grows several times and is compacted many times; the
+output equals the block call, the oracle or the CPU statement bit for bit."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import conv_ref
+import denoise_ref
+import dyn_ref
+import dynkey_ref
+import echo_ref
+import eq_ref
 import fir_ref
 import orc
 import pv_ref
 from block_gpu import statement
+from denoise_gpu import lib_params as denoise_params
+from dyn_gpu import lib_params as dyn_params
+from dynkey_gpu import lib_params as dynkey_params
+from echo_gpu import lib_params as echo_params
+from eq_gpu import gpu_eq
 from fir_gpu import gpu_fir
 from pv_gpu import block, same_bits
 from test_gpu_spectrum_sizes import bins, gpu_ex
@@ -39,8 +50,10 @@ def part(avail, share):
     return 0 if share is None else (avail if share == 1.0 else avail // 2 + 1 if avail else 0)
 
 
-def drive(lib, h, prefix, x, ch):
-    """put_host / available / receive_host / flush / receive everything of a nae_stretch, nae_wsola or nae_fir handle"""
+def drive(lib, h, prefix, x, ch, in_ch=None):
+    """put_host / available / receive_host / flush / receive everything of a handle with these entries (nae_stretch, nae_wsola, nae_fir, the
+    block handles); in_ch: the floats of a put frame where they are not the ch of a received one (nae_dynkey's carry the key)"""
+    in_ch = ch if in_ch is None else in_ch
     put, available, receive = (getattr(lib, f"nae_{prefix}_{f}") for f in ("put_host", "available", "receive_host"))
     outs, got = [], C.c_size_t()
 
@@ -51,8 +64,8 @@ def drive(lib, h, prefix, x, ch):
             assert got.value == n
             outs.append(buf)
 
-    for pos, n, share in schedule(x.size // ch):
-        chunk = np.ascontiguousarray(x[pos * ch:(pos + n) * ch])
+    for pos, n, share in schedule(x.size // in_ch):
+        chunk = np.ascontiguousarray(x[pos * in_ch:(pos + n) * in_ch])
         assert put(h, chunk.ctypes.data, n) == 0
         take(part(available(h), share))
     assert getattr(lib, f"nae_{prefix}_flush")(h) == 0
@@ -201,3 +214,110 @@ def test_fir_long_stream_device_puts_and_receives(ctx, nae):
     out = d_o.download()[: want.size]
     d_x.free(); d_o.free()
     assert same_bits(out, want)
+
+
+# ---------------------------------------------------------------------------------------------------- the block-handle family
+def loud_frames(seed, ch):
+    """L frames of noise whose level wanders 14 dB under and over the -18 dB threshold: a signal the dynamics move, a key"""
+    rng = np.random.default_rng(seed)
+    t = np.arange(L)[:, None]
+    return (rng.uniform(-1, 1, (L, ch)) * 10.0 ** ((-18.0 + 14.0 * np.sin(2 * np.pi * t / 411.0 + np.arange(ch))) / 20.0)).astype(np.float32)
+
+
+def test_eq_long_stream_equals_statement(ctx, nae):
+    """four sections; the statement's bits, which are the block call's"""
+    coef, ch = eq_ref.cascade(4), 2
+    x = orc.fill_uniform(L * ch, 53)
+    y = drive(ctx.lib, nae.Eq(ctx, coef, ch).h, "eq", x, ch)
+    want = eq_ref.run(statement(eq_ref), coef, x, ch=ch)
+    assert y.size == L * ch and same_bits(y, want)
+    assert same_bits(y, gpu_eq(nae, ctx, coef, x.reshape(1, L, ch)).reshape(-1))
+
+
+def test_dyn_long_stream_equals_statement(ctx, nae):
+    p, x = dyn_ref.params(lookahead=48, link=1, alpha_attack=dyn_ref.alpha(0.002), alpha_release=dyn_ref.alpha(0.05)), loud_frames(59, 2)
+    y = drive(ctx.lib, nae.Dyn(ctx, dyn_params(nae, p), 2).h, "dyn", x.reshape(-1), 2)
+    want = dyn_ref.run(statement(dyn_ref), p, x)
+    assert np.mean(want != x) > 0.5, "the statement's gain moves"
+    assert y.size == want.size and same_bits(y, want.reshape(-1))
+
+
+def test_dynkey_long_stream_equals_statement(ctx, nae):
+    """a stereo key through four slow sections, interleaved into the puts: frames of 4 floats go in, frames of 2 come out"""
+    dp = dyn_ref.params(lookahead=48, link=1, alpha_attack=dyn_ref.alpha(0.002), alpha_release=dyn_ref.alpha(0.05))
+    p = dynkey_ref.params(dp, 2, dynkey_ref.key_filters()[4])
+    x, key = orc.fill_uniform(L * 2, 61).reshape(L, 2), loud_frames(67, 2)
+    frames = np.ascontiguousarray(np.concatenate([x, key], 1)).reshape(-1)
+    y = drive(ctx.lib, nae.DynKey(ctx, dynkey_params(nae, p), 2).h, "dynkey", frames, 2, in_ch=4)
+    want = dynkey_ref.run(statement(dynkey_ref), p, x, key)
+    assert np.mean(want != x) > 0.5, "the statement's gain moves"
+    assert y.size == want.size and same_bits(y, want.reshape(-1))
+
+
+def echo_case(seed):
+    """delays 1500 and 1024 with cross and the designed pair of loop filters: the ring of 3072 samples wraps 130 times, and every put boundary
+    falls somewhere else in it"""
+    p = echo_ref.params((1500, 1024), -0.9, 1, 0.6, 0.8, echo_ref.loop_filters()[2])
+    x = orc.fill_uniform(L * 2, seed).reshape(L, 2)
+    want = echo_ref.run(statement(echo_ref), p, x)
+    assert not np.array_equal(want[1500:], (0.8 * x[1500:].astype(np.float64)).astype(np.float32)), "the statement's repeats are there"
+    return p, x, want
+
+
+def test_echo_long_stream_equals_statement(ctx, nae):
+    p, x, want = echo_case(71)
+    y = drive(ctx.lib, nae.Echo(ctx, echo_params(nae, p), 2).h, "echo", x.reshape(-1), 2)
+    assert y.size == want.size and same_bits(y, want.reshape(-1))
+
+
+def test_echo_long_stream_device_puts_and_receives(ctx, nae):
+    """nae_echo_put / nae_echo_receive: fed from device memory and popped device to device, as the FIR filter's handle above"""
+    lib, ch = ctx.lib, 2
+    p, x, want = echo_case(73)
+    h, got = nae.Echo(ctx, echo_params(nae, p), ch).h, C.c_size_t()
+    d_x, d_o = ctx.array(x.reshape(-1)), ctx.empty(want.size + ch)
+    frames = 0
+    for pos, n, share in schedule(L):
+        assert lib.nae_echo_put(h, C.c_void_p(d_x.at(pos * ch)), n) == 0
+        take = part(lib.nae_echo_available(h), share)
+        assert lib.nae_echo_receive(h, C.c_void_p(d_o.at(frames * ch)), take, C.byref(got)) == 0
+        assert got.value == take
+        frames += take
+    assert lib.nae_echo_flush(h) == 0
+    assert lib.nae_echo_put(h, C.c_void_p(d_x.ptr), 1) == -5               # NAE_ERR_STATE: put after flush
+    rest = lib.nae_echo_available(h)
+    assert lib.nae_echo_receive(h, C.c_void_p(d_o.at(frames * ch)), rest, C.byref(got)) == 0
+    frames += got.value
+    assert lib.nae_echo_available(h) == 0
+    assert lib.nae_echo_destroy(h) == 0
+    assert frames == L
+    out = d_o.download()[: want.size]
+    d_x.free(); d_o.free()
+    assert same_bits(out, want.reshape(-1))
+
+
+def test_conv_long_stream_equals_statement(ctx, nae):
+    """n_fft 512 with 2000 taps per channel (8 partitions): in_len + n_taps - 1 frames come out, the statement on the zero-extended input"""
+    n_taps, ch = 2000, 2
+    rng = np.random.default_rng(79)
+    taps = (rng.uniform(-1, 1, (ch, n_taps)) * np.exp(-np.arange(n_taps) / 400.0)).astype(np.float32)
+    x = orc.fill_uniform(L * ch, 79)
+    y = drive(ctx.lib, nae.Conv(ctx, taps, ch, 512).h, "conv", x, ch)
+    want = conv_ref.run(statement(conv_ref), taps, 512, np.concatenate([x, np.zeros((n_taps - 1) * ch, np.float32)]), ch=ch)
+    assert y.size == (L + n_taps - 1) * ch and same_bits(y, want)
+
+
+def test_denoise_long_stream_equals_statement(ctx, nae):
+    """n_fft 1024 against a profile per channel; the level wanders around the profile's, so the gate opens and closes all along"""
+    n_fft, ch = 1024, 2
+    p = denoise_ref.params(n_fft, 2, 2, 1.0, 0.1)
+    profile = denoise_ref.flat_profile(n_fft, ch, tilt_db=-3.0)
+    x = denoise_ref.wander(np.random.default_rng(83), 1, L, ch, period=3.0 * n_fft)[0]
+    d_p = ctx.array(profile.reshape(-1))
+    h = nae.Denoise(ctx, denoise_params(nae, p), d_p.ptr, ch, ch).h
+    ctx.sync()
+    d_p.free()                                             # the handle has its own copy
+    y = drive(ctx.lib, h, "denoise", x.reshape(-1), ch)
+    want = denoise_ref.run(statement(denoise_ref), p, profile, x)
+    assert 1e-3 < np.abs(want - x).max() and 1e-3 < np.abs(want - np.float32(0.1) * x).max(), "neither the input nor all at the floor gain"
+    assert y.size == want.size and same_bits(y, want.reshape(-1))
