@@ -73,6 +73,17 @@
 #define NAE_ECHO_MAX_DELAY (1 << 20)
 #define NAE_ECHO_MAX_SECTIONS 4
 #define NAE_ECHO_MAX_FEEDBACK 0.99
+/* K17 modulated delay ("K17 modulated delay"): chorus, flanger and vibrato: one short delay d = delay + depth l(n) swept by an
+ * LFO l, read between samples by 4-point Lagrange interpolation, with feedback.  delay - depth >= NAE_MOD_MIN_DELAY keeps the newest sample a
+ * tap reads behind the one it computes; delay + depth <= NAE_MOD_MAX_DELAY (64 ms at 48 kHz) lets a ring of 4096 floats hold one chunk of
+ * NAE_EQ_CHUNK samples and the deepest reach, floor(d) + 2; at most NAE_MOD_MAX_VOICES taps of one LFO at different phases; |feedback| is at
+ * most NAE_MOD_MAX_FEEDBACK */
+#define NAE_MOD_MIN_DELAY 2.0
+#define NAE_MOD_MAX_DELAY 3070.0
+#define NAE_MOD_MAX_VOICES 4
+#define NAE_MOD_MAX_FEEDBACK 0.95
+#define NAE_MOD_SINE 0
+#define NAE_MOD_TRIANGLE 1
 /* K13 spectral gate ("K13 spectral gate"): noise reduction on the STFT at N = 512 ... 4096 and hop N / 4: a per-bin decision
  * against a learned power profile, smoothed by an integer triangle over at most NAE_DENOISE_MAX_TIME frames and NAE_DENOISE_MAX_FREQ bins to
  * either side (a wider frequency triangle pulls a pure tone down: DESIGN.md gives the figure); a tile the library chooses has at least

@@ -21,7 +21,7 @@
 #define NAE_GPU_H
 #include <stddef.h>
 #include <stdint.h>
-#include "nae_dsp_spec.h" /* NAE_DYNKEY_MAX_SECTIONS and NAE_ECHO_MAX_SECTIONS, the extents of nae_dynkey_params::coef and nae_echo_params::coef */
+#include "nae_dsp_spec.h" /* NAE_DYNKEY_MAX_SECTIONS, NAE_ECHO_MAX_SECTIONS and NAE_MOD_MAX_VOICES, the extents of nae_dynkey_params::coef, nae_echo_params::coef and nae_mod_params::voice_phase */
 
 #ifdef __cplusplus
 extern "C" {
@@ -52,7 +52,8 @@ extern "C" {
  *   (nae_loud_create, _put, _put_host, _flush, _get_result, _destroy) with the records nae_loud_params and nae_loud_result: the BS.1770
  *   loudness meter and normalizer, K14; nae_dynkey_block_f32 and the nae_dynkey handle (the same eight entries) with the record
  *   nae_dynkey_params: the keyed (side-chain) dynamics, K15; nae_echo_design, nae_echo_block_f32 and the nae_echo handle (the same eight
- *   entries) with the record nae_echo_params: the echo, K16. */
+ *   entries) with the record nae_echo_params: the echo, K16; nae_mod_design, nae_mod_block_f32 and the nae_mod handle (the same eight
+ *   entries) with the record nae_mod_params: the modulated delay (chorus, flanger, vibrato), K17. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -80,6 +81,7 @@ typedef struct nae_eq nae_eq;
 typedef struct nae_dyn nae_dyn;
 typedef struct nae_dynkey nae_dynkey;
 typedef struct nae_echo nae_echo;
+typedef struct nae_mod nae_mod;
 typedef struct nae_denoise nae_denoise;
 typedef struct nae_loud nae_loud;
 
@@ -166,6 +168,8 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *   dn_tile         hop blocks (of n_fft / 4 samples) one wave of the spectral gate walks (0: nae_pick_denoise_tile); every tiling gives the same bits
  *   echo_group      streams per launch of nae_echo_block_f32 (0: as many as keep the delay lines inside the 256 MiB workspace cap); every grouping
  *                   gives the same bits
+ *   mod_sub         samples one wave of the modulated delay computes in parallel, 1 ... 64 (0: 64 without feedback, else min(64, floor(delay -
+ *                   depth) - 1)); a value above that rule's is cut down to it; every value gives the same bits
  * The same assignments, comma separated, in the environment variable NAE_DEBUG ("pv_flow=2,pv_fps=4") are applied when a context is created
  * (for measuring a program that creates its contexts itself, e.g. bench.py); an unknown key there fails nae_ctx_create with NAE_ERR_INVALID. */
 int nae_debug_set(nae_ctx* ctx, const char* key, long long value);
@@ -701,6 +705,64 @@ int nae_echo_destroy(nae_echo* h);
  * at or above sample_rate / 2, cross not 0 or 1.  No context, no device work. */
 int nae_echo_design(int sample_rate, double delay_s_left, double delay_s_right, double feedback, double damp_hz, double lowcut_hz, double wet,
                     double dry, int cross, nae_echo_params* out);
+
+/* ------------------------------------------------------------------ K17 modulated delay (chorus, flanger, vibrato)
+ * no reference code.  Spec ("K17 modulated delay"): one short delay whose length an LFO sweeps, read between samples, with
+ * feedback.  Per stream-channel c a line w of f32 samples.  For n = 0 ... in_len - 1 (n counts from the stream's first sample, 64-bit) and
+ * voice v = 0 ... n_voices - 1, every step one IEEE double operation in the order written:
+ *   phi = (uint32)(phase0 + voice_phase[v] + (c == 1 ? phase_ch : 0) + (uint32)((uint64)n rate_inc))          all mod 2^32
+ *   t   = (double)(int32)phi 2^-31                                                                            in [-1, 1)
+ *   l   = NAE_MOD_SINE:     y = (4 t) (1 - |t|);  l = (0.225 ((y |y|) - y)) + y          within 1.1e-3 of sin(pi t), |l| <= 1
+ *         NAE_MOD_TRIANGLE: l = (2 |t|) - 1
+ *   d = delay + (depth l);  k = floor(d);  f = d - k
+ *   a = w[n - k + 1], b = w[n - k], c2 = w[n - k - 1], e = w[n - k - 2]                  as double; an index below 0 reads 0
+ *   ca = ((-(f (f - 1))) (f - 2)) (1 / 6);  cb = (((f + 1) (f - 1)) (f - 2)) 0.5;  cc = ((-((f + 1) f)) (f - 2)) 0.5;  ce = (((f + 1) f) (f - 1)) (1 / 6)
+ *   tap_v = (((ca a) + (cb b)) + (cc c2)) + (ce e)                                       4-point Lagrange interpolation
+ * then v = tap_0 (+ tap_1 ... in voice order), u = v (1 / n_voices) and
+ *   w[n] = feedback == 0 ? x[n] : (float)((double)x[n] + (feedback u))                   the line: rounded once per trip
+ *   y[n] = (float)((dry (double)x[n]) + (wet u))
+ * delay - depth >= NAE_MOD_MIN_DELAY puts the newest sample a tap reads, n - k + 1, behind n: floor(delay - depth) - 1 consecutive samples read
+ * only line samples in front of them and are computed in parallel; no sample's arithmetic depends on how many are.  Output past in_len is
+ * not stored and the tail past in_len is dropped (a caller who wants it puts zeros).  Bit-exact against the CPU statement
+ * (tests/mod_ref/ref_mod.c); any cut of the input into puts gives the same bits.  A non-finite sample stays in its stream-channel and reaches
+ * no sample before it.
+ * Errors: a null pointer, ch not 1 or 2, a non-finite delay, depth, feedback, wet or dry, |feedback| > NAE_MOD_MAX_FEEDBACK, depth < 0,
+ * n_voices < 1, an unknown shape: NAE_ERR_INVALID; delay - depth < NAE_MOD_MIN_DELAY, delay + depth > NAE_MOD_MAX_DELAY (both in double as
+ * written) or more than NAE_MOD_MAX_VOICES voices: NAE_ERR_UNSUPPORTED; in_len = 0 or n_streams = 0: NAE_OK after the checks, nothing is
+ * launched.  Views as nae_eq_block_f32's, stream_stride 0 on the source included; dst may be src in the same view.  No workspace. */
+typedef struct nae_mod_params {
+    double delay;                                 /* the centre delay in samples */
+    double depth;                                 /* the sweep's amplitude in samples, >= 0 */
+    double feedback;                              /* g, |g| <= NAE_MOD_MAX_FEEDBACK */
+    double wet, dry;
+    uint32_t rate_inc;                            /* the LFO's phase step per sample, in turns 2^32 */
+    uint32_t phase0;                              /* the LFO's phase at n = 0 */
+    uint32_t phase_ch;                            /* added on channel 1 only: the stereo spread (mono does not read it) */
+    int n_voices;                                 /* 1 ... NAE_MOD_MAX_VOICES */
+    uint32_t voice_phase[NAE_MOD_MAX_VOICES];     /* every voice's phase offset */
+    int shape;                                    /* NAE_MOD_SINE or NAE_MOD_TRIANGLE */
+} nae_mod_params;
+int nae_mod_block_f32(nae_ctx* ctx, const nae_mod_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch): whole chunks of NAE_EQ_CHUNK frames come out as they fill; nae_mod_flush
+ * releases the partial last chunk, so in_len frames come out in all, equal to the block call's however the input is cut (phases and samples
+ * are counted from the stream's first sample).  The handle keeps the last 3072 line samples of every channel and the sample count.  A put
+ * after the flush: NAE_ERR_STATE. */
+int nae_mod_create(nae_ctx* ctx, const nae_mod_params* params, int channels, nae_mod** h);
+int nae_mod_put(nae_mod* h, const float* interleaved, size_t S);
+int nae_mod_put_host(nae_mod* h, const float* interleaved_host, size_t S);
+int nae_mod_flush(nae_mod* h);
+size_t nae_mod_available(nae_mod* h);
+int nae_mod_receive(nae_mod* h, float* dst, size_t max_frames, size_t* got);
+int nae_mod_receive_host(nae_mod* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_mod_destroy(nae_mod* h);
+/* The record on the host: delay = (delay_ms 1e-3) sample_rate and depth = (depth_ms 1e-3) sample_rate in double, not rounded;
+ * rate_inc = (uint32)llround((rate_hz / sample_rate) 2^32); voice_phase[v] = (uint32)(((uint64)v << 32) / voices): the voices spread evenly over
+ * a turn; phase_ch = (uint32)llround(spread 2^31): a spread of 1 puts the right channel half a turn behind; phase0 = 0.  rate_hz = 0 is a
+ * fixed comb.  NAE_ERR_INVALID: sample_rate <= 0, a null pointer, an argument that is not finite, rate_hz outside [0, 20], depth_ms < 0,
+ * a delay range outside [NAE_MOD_MIN_DELAY, NAE_MOD_MAX_DELAY] samples at this rate, |feedback| > NAE_MOD_MAX_FEEDBACK, voices outside
+ * 1 ... NAE_MOD_MAX_VOICES, spread outside [0, 1], an unknown shape.  No context, no device work. */
+int nae_mod_design(int sample_rate, double rate_hz, double delay_ms, double depth_ms, double feedback, int voices, double spread, int shape,
+                   double wet, double dry, nae_mod_params* out);
 
 /* ------------------------------------------------------------------ K13 spectral gate
  * no reference code.  Spec ("K13 spectral gate"): noise reduction on the STFT at n_fft = 512 ... 4096, hop H = n_fft / 4, in the

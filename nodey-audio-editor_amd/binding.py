@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = [
     "nae_dynkey_receive", "nae_dynkey_receive_host", "nae_dynkey_destroy",
     "nae_echo_design", "nae_echo_block_f32", "nae_echo_create", "nae_echo_put", "nae_echo_put_host", "nae_echo_flush", "nae_echo_available",
     "nae_echo_receive", "nae_echo_receive_host", "nae_echo_destroy",
+    "nae_mod_design", "nae_mod_block_f32", "nae_mod_create", "nae_mod_put", "nae_mod_put_host", "nae_mod_flush", "nae_mod_available",
+    "nae_mod_receive", "nae_mod_receive_host", "nae_mod_destroy",
     "nae_denoise_design", "nae_denoise_profile_f32", "nae_denoise_block_f32", "nae_denoise_create", "nae_denoise_put", "nae_denoise_put_host",
     "nae_denoise_flush", "nae_denoise_available", "nae_denoise_receive", "nae_denoise_receive_host", "nae_denoise_destroy",
     "nae_loud_design", "nae_loud_lufs", "nae_loud_measure_f32", "nae_loud_apply_f32", "nae_loud_normalize_f32", "nae_loud_create", "nae_loud_put",
@@ -62,7 +64,9 @@ FIR_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}   # `kin
 EQ_KINDS = ("peak", "lowshelf", "highshelf", "lowpass", "highpass", "notch")   # `kind` of nae_eq_design: NAE_EQ_PEAK ... NAE_EQ_NOTCH
 DYNKEY_MAX_SECTIONS = 4                             # NAE_DYNKEY_MAX_SECTIONS (include/nae_dsp_spec.h): the key filter's sections
 ECHO_MIN_DELAY, ECHO_MAX_DELAY, ECHO_MAX_SECTIONS, ECHO_MAX_FEEDBACK = 1024, 1 << 20, 4, 0.99   # NAE_ECHO_* (include/nae_dsp_spec.h)
-HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo")   # the handles with the full put / receive set of entries
+MOD_MIN_DELAY, MOD_MAX_DELAY, MOD_MAX_VOICES, MOD_MAX_FEEDBACK = 2.0, 3070.0, 4, 0.95   # NAE_MOD_* (include/nae_dsp_spec.h)
+MOD_SHAPES = ("sine", "triangle")                   # `shape` of nae_mod_params: NAE_MOD_SINE, NAE_MOD_TRIANGLE
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -147,6 +151,28 @@ class EchoParams(C.Structure):
         for s_, row in enumerate(coef):
             for i_, v in enumerate(row):
                 p.coef[s_][i_] = v
+        return p
+
+
+class ModParams(C.Structure):
+    """nae_mod_params: the modulated delay's parameters (include/nae_gpu.h): the centre delay and the sweep's depth in samples, the feedback, wet
+    and dry, the LFO's phase step, start phase and stereo spread in turns 2^32, the voices' phase offsets and the shape; nae_mod_design makes
+    them from milliseconds and hertz"""
+    _fields_ = [("delay", C.c_double), ("depth", C.c_double), ("feedback", C.c_double), ("wet", C.c_double), ("dry", C.c_double),
+                ("rate_inc", C.c_uint32), ("phase0", C.c_uint32), ("phase_ch", C.c_uint32), ("n_voices", C.c_int),
+                ("voice_phase", C.c_uint32 * MOD_MAX_VOICES), ("shape", C.c_int)]
+
+    @staticmethod
+    def make(delay: float, depth: float, feedback: float = 0.0, wet: float = 1.0, dry: float = 1.0, rate_inc: int = 0, phase0: int = 0,
+             phase_ch: int = 0, voice_phase=(0,), shape: int = 0) -> "ModParams":
+        """voice_phase: one offset per voice, at most MOD_MAX_VOICES (more raise)"""
+        if len(voice_phase) > MOD_MAX_VOICES:
+            raise NaeError(f"nae_mod_params holds at most {MOD_MAX_VOICES} voices")
+        p = ModParams()
+        p.delay, p.depth, p.feedback, p.wet, p.dry = delay, depth, feedback, wet, dry
+        p.rate_inc, p.phase0, p.phase_ch, p.n_voices, p.shape = rate_inc & 0xffffffff, phase0 & 0xffffffff, phase_ch & 0xffffffff, len(voice_phase), shape
+        for v, ph in enumerate(voice_phase):
+            p.voice_phase[v] = ph & 0xffffffff
         return p
 
 
@@ -276,6 +302,8 @@ def load_library() -> C.CDLL:
         "nae_dynkey_block_f32": (i, [vp, P(DynKeyParams), P(Sig), P(Sig), sz, i, sz, P(Sig)]), "nae_dynkey_create": (i, [vp, P(DynKeyParams), i, P(vp)]),
         "nae_echo_design": (i, [i, d, d, d, d, d, d, d, i, P(EchoParams)]),
         "nae_echo_block_f32": (i, [vp, P(EchoParams), P(Sig), sz, i, sz, P(Sig)]), "nae_echo_create": (i, [vp, P(EchoParams), i, P(vp)]),
+        "nae_mod_design": (i, [i, d, d, d, d, i, d, i, d, d, P(ModParams)]),
+        "nae_mod_block_f32": (i, [vp, P(ModParams), P(Sig), sz, i, sz, P(Sig)]), "nae_mod_create": (i, [vp, P(ModParams), i, P(vp)]),
         "nae_denoise_design": (i, [d, d, i, i, i, P(DenoiseParams)]), "nae_denoise_profile_f32": (i, [vp, i, P(Sig), sz, i, vp]),
         "nae_denoise_block_f32": (i, [vp, P(DenoiseParams), vp, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
@@ -714,6 +742,21 @@ class Context:
         """the echo `params` over every stream (nae_echo_block_f32); dst receives in_len frames"""
         self._ck(self.lib.nae_echo_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K17
+    @staticmethod
+    def mod_design(sample_rate: int, rate_hz: float = 0.8, delay_ms: float = 12.0, depth_ms: float = 3.0, feedback: float = 0.0, voices: int = 3,
+                   spread: float = 0.5, shape: str = "sine", wet: float = 0.5, dry: float = 1.0) -> "ModParams":
+        """the modulated delay's parameters from milliseconds and hertz (nae_mod_design); the defaults are a chorus"""
+        out = ModParams()
+        rc = load_library().nae_mod_design(sample_rate, rate_hz, delay_ms, depth_ms, feedback, voices, spread, MOD_SHAPES.index(shape), wet, dry, C.byref(out))
+        if rc:
+            raise NaeError(f"nae_mod_design({sample_rate}, {rate_hz}, {delay_ms}, {depth_ms}, {feedback}, {voices}, {spread}, {shape}, {wet}, {dry}) failed: {rc}")
+        return out
+
+    def mod_block(self, params: "ModParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the modulated delay `params` over every stream (nae_mod_block_f32); dst receives in_len frames"""
+        self._ck(self.lib.nae_mod_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     # -- K12
     @staticmethod
     def dyn_design(sample_rate: int, threshold_db: float = -18.0, ratio: float = 4.0, knee_db: float = 6.0, attack_s: float = 0.005,
@@ -939,6 +982,16 @@ class Echo(_Handle):
     def __init__(self, ctx: Context, params: EchoParams, channels: int):
         super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_echo_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+
+class Mod(_Handle):
+    """The modulated delay's streaming handle (nae_mod_create): put interleaved f32, flush (the partial last chunk; the tail is dropped), receive."""
+
+    _prefix = "nae_mod"
+
+    def __init__(self, ctx: Context, params: ModParams, channels: int):
+        super().__init__(ctx, channels)
+        ctx._ck(ctx.lib.nae_mod_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
 
 
 class Denoise(_Handle):

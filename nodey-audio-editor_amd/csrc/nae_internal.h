@@ -53,6 +53,7 @@ struct nae_ctx {
     // nae_echo_block_f32's delay lines, one ring per stream-channel of a launch group (kernels_echo.hip)
     void* ws_echo = nullptr; size_t ws_echo_bytes = 0;
     int echo_group = 0;          // streams per launch of the echo's block call; 0 = from NAE_CONV_WS_BYTES
+    int mod_sub = 0;             // samples a wave of the modulated delay computes in parallel, 1 ... 64; 0 = the rule of kernels_mod.hip
     // tuning / A-B switches: nae_debug_set(ctx, key, value) (include/nae_gpu.h lists the keys; NAE_DEBUG="key=value,..." applies them at context creation)
     bool dbg_st_unfused = false;     // st_unfused: WSOLA chain runs filter and cubic stage as separate launches
     int dbg_td_nc = 0;               // td_nc = 1|2|4: candidates per thread of the WSOLA search (0: by batch size)
@@ -314,6 +315,15 @@ size_t nae_echo_ring(const nae_echo_params* p, int ch);
 int nae_launch_echo(nae_ctx* ctx, const nae_echo_params* p, const double* d_block, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
                     const nae_sig* dst, size_t c_origin, size_t c_stop, float* d_line, double* d_state);
 void nae_echo_cache_free(nae_ctx* ctx);
+
+// kernels_mod.hip: the modulated delay ("K17 modulated delay").  nae_mod_check: the parameter rules of the block call and the handle.
+// nae_launch_mod runs chunks [c_origin, c_stop) of absolutely indexed signals, one wave per stream-channel: d_state, [stream-channel]
+// [NAE_MOD_KEEP] floats, is every line's last NAE_MOD_KEEP samples in front of chunk c_origin and receives those in front of chunk c_stop
+// (null: zero, and nothing kept: the block call, which starts at chunk 0).
+constexpr size_t NAE_MOD_KEEP = 3072;
+int nae_mod_check(nae_ctx* ctx, const nae_mod_params* p, int ch);
+int nae_launch_mod(nae_ctx* ctx, const nae_mod_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
+                   size_t c_origin, size_t c_stop, float* d_state);
 
 // kernels_denoise.hip: the spectral gate ("K13 spectral gate").  nae_denoise_check: the parameter rules of the block call and the
 // handle.  nae_launch_denoise runs hop blocks [b_origin, b_stop) of absolutely indexed signals of in_len samples: it reads from

@@ -87,6 +87,15 @@ struct nae_echo : BlockHandle {
     int process() override;
 };
 
+// the modulated delay's handle ("K17 modulated delay"): whole chunks of NAE_EQ_CHUNK samples are computed as they fill; every channel's
+// last NAE_MOD_KEEP line samples between two launches stay on the device, and `done` is the sample count.  Phases and runs are counted from the
+// stream's first sample, so any cut into puts gives the block call's bits
+struct nae_mod : BlockHandle {
+    nae_mod_params params;
+    float* d_state = nullptr;      // [ch][NAE_MOD_KEEP]: the lines' samples in front of the next chunk (zero in front of the first)
+    int process() override;
+};
+
 // the spectral gate's handle ("K13 spectral gate"): whole hop blocks of n_fft / 4 samples are computed once the time_smooth + 3
 // blocks behind them are there; the input stays from time_smooth + 3 blocks in front of the next block on, and nothing else is kept
 struct nae_denoise : BlockHandle {
@@ -344,6 +353,13 @@ int nae_echo::process()
 {
     return run_units(NAE_EQ_CHUNK, 0, 0, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
         return nae_launch_echo(ctx, &params, d_block, &src, in.total, ch, 1, &dst, from, to, d_line, d_state);
+    });
+}
+
+int nae_mod::process()
+{
+    return run_units(NAE_EQ_CHUNK, 0, 0, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
+        return nae_launch_mod(ctx, &params, &src, in.total, ch, 1, &dst, from, to, d_state);
     });
 }
 
@@ -664,6 +680,33 @@ size_t nae_echo_available(nae_echo* h) { return handle_available(h); }
 int nae_echo_receive(nae_echo* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_echo_receive_host(nae_echo* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_echo_destroy(nae_echo* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ modulated delay
+int nae_mod_create(nae_ctx* ctx, const nae_mod_params* params, int channels, nae_mod** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_mod_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_mod* s = handle_new<nae_mod>(ctx, channels);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    // the line in front of the stream's first sample is zero
+    const size_t state_floats = (size_t)channels * NAE_MOD_KEEP;
+    rc = s->dev_alloc(&s->d_state, state_floats, "hipMalloc(mod lines)");
+    if (!rc) rc = nae_check(ctx, hipMemsetAsync(s->d_state, 0, state_floats * sizeof(float), ctx->stream), "hipMemsetAsync(mod lines)");
+    return handle_created(s, rc, h);
+}
+
+int nae_mod_put(nae_mod* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_mod_put_host(nae_mod* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+// flush: the partial last chunk comes out: as many frames as were put over the handle's life (the tail is dropped: flush_tail = 0)
+int nae_mod_flush(nae_mod* h) { return handle_flush(h); }
+size_t nae_mod_available(nae_mod* h) { return handle_available(h); }
+int nae_mod_receive(nae_mod* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_mod_receive_host(nae_mod* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_mod_destroy(nae_mod* h) { return handle_destroy(h); }
 
 // ------------------------------------------------------------------------------------------------ spectral gate
 int nae_denoise_create(nae_ctx* ctx, const nae_denoise_params* params, const float* profile_dev, int profile_ch, int channels, nae_denoise** h)

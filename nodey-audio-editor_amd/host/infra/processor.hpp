@@ -161,4 +161,6 @@ namespace infra
 	void register_sidechain_processors();
 	// the echo (audio_echo): called after the eight above, each of which stays the list it was
 	void register_echo_processors();
+	// the modulation effects (audio_modulation): called after the nine above, each of which stays the list it was
+	void register_modulation_processors();
 }

@@ -1,5 +1,5 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
-// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
+// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 // Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
 #include "audio-filter.hpp"
@@ -8,6 +8,7 @@
 #include "audio-dynamics.hpp"
 #include "audio-sidechain.hpp"
 #include "audio-echo.hpp"
+#include "audio-modulation.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "node-util.hpp"
@@ -778,6 +779,81 @@ namespace processor
 				nae_echo* echo = nullptr;
 				gpu::check(nae_echo_create(ctx, &params, ch, &echo), "nae_echo_create");
 				return echo;
+			}
+		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_modulation
+	infra::Processor::Info Audio_modulation::get_processor_info()
+	{
+		return {"audio_modulation", "Audio Modulation", false, [] { return std::unique_ptr<infra::Processor>(new Audio_modulation); },
+				"Chorus, flanger and vibrato: a short delay swept by an LFO, up to four voices, feedback and stereo spread (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_modulation::get_pin_attributes() const { return io_pins(); }
+
+	Json::Value Audio_modulation::serialize() const
+	{
+		Json::Value value;
+		if (rate_hz != default_rate_hz) value["rate_hz"] = rate_hz;
+		if (delay_ms != default_delay_ms) value["delay_ms"] = delay_ms;
+		if (depth_ms != default_depth_ms) value["depth_ms"] = depth_ms;
+		if (feedback != default_feedback) value["feedback"] = feedback;
+		if (voices != default_voices) value["voices"] = voices;
+		if (spread != default_spread) value["spread"] = spread;
+		if (shape != Shape::Sine) value["shape"] = "triangle";
+		if (wet != default_wet) value["wet"] = wet;
+		if (dry != default_dry) value["dry"] = dry;
+		return value;
+	}
+
+	void Audio_modulation::deserialize(const Json::Value& value)
+	{
+		const auto wrong = [](const char* field) { return wrong_field("Audio_modulation", field); };
+		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
+		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_modulation", key, lo, hi, fallback); };
+		const double r = real("rate_hz", 0.0, 20.0, default_rate_hz);
+		// a delay has no range of its own but its sign: what it may be depends on the stream's sample rate (process_payload)
+		const double d = real("delay_ms", 0.0, 1e9, default_delay_ms);
+		if (!(d > 0.0)) throw wrong("delay_ms");
+		const double dp = real("depth_ms", 0.0, 1e9, default_depth_ms);
+		const double g = real("feedback", -0.95, 0.95, default_feedback);
+		const int v = int_from_json(value, "Audio_modulation", "voices", 1, NAE_MOD_MAX_VOICES, default_voices);
+		const double sp = real("spread", 0.0, 1.0, default_spread);
+		Shape sh = Shape::Sine;
+		if (value.isMember("shape"))
+		{
+			if (!value["shape"].isString()) throw wrong("shape");
+			const std::string name = value["shape"].asString();
+			if (name == "triangle") sh = Shape::Triangle;
+			else if (name != "sine") throw wrong("shape");
+		}
+		const double w = real("wet", 0.0, 1.0, default_wet), dy = real("dry", 0.0, 1.0, default_dry);
+		rate_hz = r; delay_ms = d; depth_ms = dp; feedback = g; voices = v; spread = sp; shape = sh; wet = w; dry = dy;
+	}
+
+	void Audio_modulation::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Modulation");
+		run_on_handle<nae_mod>(
+			io.input, io.output, stop_token, {"nae_mod", nae_mod_put, nae_mod_flush, nae_mod_available, nae_mod_receive, nae_mod_destroy}, "node", 0,
+			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
+			{
+				// the sweep at the stream's sample rate: the library runs 2 ... 3070 samples, and the design is the one statement of that
+				nae_mod_params params;
+				if (nae_mod_design(frame->sample_rate, rate_hz, delay_ms, depth_ms, feedback, voices, spread, shape == Shape::Triangle ? NAE_MOD_TRIANGLE : NAE_MOD_SINE,
+								   wet, dry, &params) != NAE_OK)
+					throw Runtime_error("Modulation delay out of range", "The delay less the depth must be at least 2 samples, and the delay plus the depth at most 3070 samples, at the stream's sample rate.",
+										infra::fmt("delay %g ms, depth %g ms at %d Hz: %g to %g samples", delay_ms, depth_ms, frame->sample_rate,
+												   (delay_ms - depth_ms) * 1e-3 * frame->sample_rate, (delay_ms + depth_ms) * 1e-3 * frame->sample_rate));
+				nae_mod* mod = nullptr;
+				gpu::check(nae_mod_create(ctx, &params, ch, &mod), "nae_mod_create");
+				return mod;
 			}
 		);
 	}

@@ -19,6 +19,7 @@
 #include "audio-dynamics.hpp"
 #include "audio-sidechain.hpp"
 #include "audio-echo.hpp"
+#include "audio-modulation.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "audio-mix.hpp"
@@ -140,6 +141,21 @@ namespace processor
 		feedback = std::clamp(feedback, 0.0, 0.95);
 		if (damp_hz != 0.0) damp_hz = std::clamp(damp_hz, 200.0, 20000.0);
 		if (lowcut_hz != 0.0) lowcut_hz = std::clamp(lowcut_hz, 20.0, 2000.0);
+		wet = std::clamp(wet, 0.0, 1.0);
+		dry = std::clamp(dry, 0.0, 1.0);
+		return false;
+	}
+
+	void Audio_modulation::draw_title() {}
+	bool Audio_modulation::draw_content(bool)
+	{
+		// what the widgets would keep: every value inside its range
+		rate_hz = std::clamp(rate_hz, 0.0, 20.0);
+		delay_ms = std::clamp(delay_ms, 0.05, 1e9);
+		depth_ms = std::clamp(depth_ms, 0.0, 1e9);
+		feedback = std::clamp(feedback, -0.95, 0.95);
+		voices = std::clamp(voices, 1, 4);
+		spread = std::clamp(spread, 0.0, 1.0);
 		wet = std::clamp(wet, 0.0, 1.0);
 		dry = std::clamp(dry, 0.0, 1.0);
 		return false;

@@ -11,6 +11,7 @@
 #include "processor/audio-loudness.hpp"
 #include "processor/audio-sidechain.hpp"
 #include "processor/audio-echo.hpp"
+#include "processor/audio-modulation.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -59,4 +60,7 @@ namespace infra
 
 	// the delay effects: the echo; a call of its own, so the eight lists above stay what they were
 	void register_echo_processors() { register_each<processor::Audio_echo>(); }
+
+	// the modulation effects: chorus, flanger and vibrato on the modulated delay; a call of its own, so the nine lists above stay what they were
+	void register_modulation_processors() { register_each<processor::Audio_modulation>(); }
 }
