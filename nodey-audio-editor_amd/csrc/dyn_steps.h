@@ -6,8 +6,9 @@
 //
 // One wave per detector walks its chunks of C = 64 T samples (T = NAE_DYN_LANE = 16) in order, as eq_cascade_kernel walks its stream-channel.
 // A chunk is loaded coalesced (64 consecutive samples per load) into an LDS stage, where lane l reads its own T consecutive samples at a stride
-// of T + 1 words, odd, so the 32 lanes of a ds_read_b32 group fall on 32 banks.  The look-ahead needs the demand r of `la` samples past the
-// chunk: the loop is one chunk ahead with steps 1 and 2 and keeps what the sliding maximum needs of two chunks in an LDS ring — r itself for
+// of T + 1 words, odd, so the 32 lanes of a ds_read_b32 group fall on 32 banks: the tiling, the stage and the wave's LDS ordering stand in
+// chunk_stage.h.  The look-ahead needs the demand r of `la` samples past the chunk:
+// the loop is one chunk ahead with steps 1 and 2 and keeps what the sliding maximum needs of two chunks in an LDS ring — r itself for
 // la < 16, where a lane reads the la words behind each of its samples, and for la >= 16 the running maximum P of every lane's 16 samples from
 // its first on, with the 128 lane maxima M: a window that leaves its lane is the rest of that lane (a suffix maximum, in registers), the whole
 // lanes between (M) and P at its last sample.  The ring's doubles stand 17 to a lane, 34 words, so the 32 lanes of a ds_read_b64 group fall on
@@ -16,12 +17,12 @@
 // carry-in and runs its 16 samples as the plain recurrence.  The carries (y1, yl) stay in registers between chunks; a handle keeps them in
 // device memory between launches.
 #pragma once
-#include "launch.h"
+#include "chunk_stage.h"
 
 namespace nae {
 
-constexpr int kDynT = NAE_DYN_LANE, kDynC = NAE_DYN_CHUNK, kDynStride = kDynT + 1, kDynSlot = 64 * kDynStride;
-static_assert(kDynT == 16 && kDynC == 1024 && NAE_DYN_MAX_LOOKAHEAD <= kDynC, "DESIGN.md §3, K12: chunks of 1024 samples, a look-ahead of at most one chunk");
+constexpr int kDynSlot = 64 * kChunkStride;          // a chunk of the ring: chunk_word's layout, in doubles
+static_assert(NAE_DYN_MAX_LOOKAHEAD <= kChunkC, "DESIGN.md §3, K12: a look-ahead of at most one chunk");
 
 constexpr double kDynK = 6.020599913279624;      // 20 log10(2)
 constexpr double kDynKInv = 0.1660964047443681;  // 1 / K
@@ -38,14 +39,6 @@ struct DynParams {
 // VGPRs: as kernel arguments they are 20 SGPRs through the whole chunk loop, which with the views and the loop's own then spill.
 enum { kDynThr, kDynSlope, kDynKnee, kDynHalfKnee, kDynInv2Knee, kDynAa, kDynOma, kDynAr, kDynOmr, kDynMakeup, kDynParams };
 struct DynCurve { double thr, slope, knee, half_knee, inv_2knee; };
-
-__device__ __forceinline__ void dyn_lds_sync()
-{
-    // this wave's LDS writes before its following LDS reads of other lanes' words: DS operations of one wave execute in issue order
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ double dyn_max(double a, double b) { return __builtin_fmax(a, b); }
 
@@ -108,34 +101,27 @@ __device__ __forceinline__ double dyn_demand(const DynCurve& p, float af, const 
 // the staged load: chunk ck of the channel at cp + ofs (frames fs apart, in_len of them, zero behind) through the stage; lane l gets its
 // samples [l T, l T + T)
 __device__ inline void dyn_load(float* stage, const float* cp, long long ofs, long long fs, long long in_len, long long ck, int lane,
-                                         float (&x)[kDynT])
+                                         float (&x)[kChunkT])
 {
-#pragma unroll 4                                           // not 16: sixteen bounds masks are 32 SGPRs
-    for (int j = 0; j < kDynT; j++) {
-        const int n = j * 64 + lane;
-        const long long g = ck * kDynC + n;
-        const float v = cp[ofs + (g < in_len ? g : in_len - 1) * fs];   // always a sample of the signal: no branch
-        stage[n + (n >> 4)] = g < in_len ? v : 0.0f;
-    }
-    dyn_lds_sync();
-#pragma unroll
-    for (int k = 0; k < kDynT; k++) x[k] = stage[lane * kDynStride + k];
-    dyn_lds_sync();                                        // the next use rewrites the stage
+    chunk_load<true, 4>(stage, cp + ofs, fs, ck * kChunkC, in_len, lane);   // four loads together, not 16: sixteen bounds masks are 32 SGPRs
+    chunk_lds_sync();
+    chunk_lane_read(stage, lane, x);
+    chunk_lds_sync();                                      // the next use rewrites the stage
 }
 
 // the magnitude of steps 1 and 2 where nothing is filtered: |.| of KC channels at kp (cs apart), the larger of two
 template <int KC>
 __device__ inline void dyn_plain_level(float* stage, const float* kp, long long cs, long long fs, long long in_len, long long ck, int lane,
-                                       float (&x)[kDynT])
+                                       float (&x)[kChunkT])
 {
     dyn_load(stage, kp, 0, fs, in_len, ck, lane, x);
 #pragma unroll
-    for (int k = 0; k < kDynT; k++) x[k] = fabsf(x[k]);
+    for (int k = 0; k < kChunkT; k++) x[k] = fabsf(x[k]);
     if constexpr (KC == 2) {
-        float x1[kDynT];
+        float x1[kChunkT];
         dyn_load(stage, kp, cs, fs, in_len, ck, lane, x1);
 #pragma unroll
-        for (int k = 0; k < kDynT; k++) {
+        for (int k = 0; k < kChunkT; k++) {
             const float b = fabsf(x1[k]);
             x[k] = b > x[k] ? b : x[k];
         }
@@ -151,7 +137,7 @@ struct DynPlainKey {
     const SigViewD& v;
     const DynParams& p;
     int lane;
-    __device__ void level(float* stage, long long ck, float (&x)[kDynT]) { dyn_plain_level<KC>(stage, kp, v.cs, v.fs, p.in_len, ck, lane, x); }
+    __device__ void level(float* stage, long long ck, float (&x)[kChunkT]) { dyn_plain_level<KC>(stage, kp, v.cs, v.fs, p.in_len, ck, lane, x); }
     __device__ void skip() {}
     static constexpr bool kSpareSgprs = false;
 };
@@ -164,7 +150,7 @@ template <int DC, class Mag>
 __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src, const OutViewD& out, const DynParams& p, double* state,
                                          long long det, int lane, Mag& mag)
 {
-    __shared__ float stage[kDynC + 64];
+    __shared__ float stage[kChunkStage];
     __shared__ double ring[2 * kDynSlot];                  // r (la < 16) or P (la >= 16) of two chunks, chunk ck in slot ck & 1
     __shared__ double lane_max[128];                       // M of the same two chunks
     __shared__ double coef[kDynCoefs];
@@ -173,8 +159,8 @@ __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src,
     if (lane < kDynCoefs) coef[lane] = kDynCoef[lane];
     if (lane < kDynParams) prm[lane] = p.v[lane];
     if (lane == 0) la_lds = p.la;
-    dyn_lds_sync();
-    const bool wide = p.la >= kDynT;
+    chunk_lds_sync();
+    const bool wide = p.la >= kChunkT;
 
     // where the detector's carries stand, or null; with kSpareSgprs as the compiler cannot follow it, so in a VGPR pair, not in two SGPRs
     // through the chunk loop
@@ -185,17 +171,17 @@ __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src,
         y1c = carry[0];
         ylc = carry[1];
     }
-    double dc[kDynT];       // what its look-ahead maximum starts from: r (la < 16) or the suffix maximum of the lane (la >= 16)
+    double dc[kChunkT];     // what its look-ahead maximum starts from: r (la < 16) or the suffix maximum of the lane (la >= 16)
 
     // steps 1 and 2 of chunk ck: what its maximum starts from, and its part of the ring
-    const auto level = [&](long long ck, double (&d0)[kDynT]) {
-        float x[kDynT];
+    const auto level = [&](long long ck, double (&d0)[kChunkT]) {
+        float x[kChunkT];
         mag.level(stage, ck, x);
         const DynCurve cv{prm[kDynThr], prm[kDynSlope], prm[kDynKnee], prm[kDynHalfKnee], prm[kDynInv2Knee]};
-        double* slot = ring + (int)(ck & 1) * kDynSlot + lane * kDynStride;   // sample m of an even chunk and its successor at m + (m >> 4)
+        double* slot = ring + (int)(ck & 1) * kDynSlot + lane * kChunkStride;   // sample m of an even chunk and its successor at chunk_word(m)
         double run = 0.0;
 #pragma unroll
-        for (int k = 0; k < kDynT; k++) {
+        for (int k = 0; k < kChunkT; k++) {
             const double r = dyn_demand(cv, x[k], coef);
             d0[k] = r;
             run = k == 0 ? r : dyn_max(run, r);
@@ -205,16 +191,16 @@ __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src,
         lane_max[(int)(ck & 1) * 64 + lane] = run;
         if (wide) {
 #pragma unroll
-            for (int k = kDynT - 2; k >= 0; k--) d0[k] = dyn_max(d0[k], d0[k + 1]);
+            for (int k = kChunkT - 2; k >= 0; k--) d0[k] = dyn_max(d0[k], d0[k + 1]);
         }
     };
 
     // the same of a chunk whose demand is not needed or is known: wholly past in_len its input is zero, and the demand of zero is 0
-    const auto quiet = [&](long long ck, double (&d0)[kDynT]) {
+    const auto quiet = [&](long long ck, double (&d0)[kChunkT]) {
         mag.skip();
-        double* slot = ring + (int)(ck & 1) * kDynSlot + lane * kDynStride;
+        double* slot = ring + (int)(ck & 1) * kDynSlot + lane * kChunkStride;
 #pragma unroll
-        for (int k = 0; k < kDynT; k++) {
+        for (int k = 0; k < kChunkT; k++) {
             d0[k] = 0.0;
             slot[k] = 0.0;
         }
@@ -224,30 +210,30 @@ __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src,
     level(p.c_origin, dc);
 #pragma unroll 1
     for (long long ck = p.c_origin; ck < p.c_stop; ck++) {
-        const long long n0 = ck * kDynC;
-        double dn[kDynT];
+        const long long n0 = ck * kChunkC;
+        double dn[kChunkT];
         // the lane number the scans' masks are made of: where a Mag asks for it, one the compiler cannot follow, so the seven masks are made
         // chunk by chunk and do not hold fourteen SGPRs through the Mag's level
         int sl = lane;
         if constexpr (Mag::kSpareSgprs) asm volatile("" : "+v"(sl));
         // one chunk ahead — but not past the signal's end, and not behind the launch's last chunk when nothing looks ahead: steps 1 and 2 are
         // the costliest stage
-        if ((ck + 1) * kDynC >= p.in_len || (ck + 1 == p.c_stop && !p.la)) quiet(ck + 1, dn);
+        if ((ck + 1) * kChunkC >= p.in_len || (ck + 1 == p.c_stop && !p.la)) quiet(ck + 1, dn);
         else level(ck + 1, dn);
-        dyn_lds_sync();
-        // step 3: d[n] = max(r[n] ... r[n + la]); sample m of the two chunks, m < 2048 counted from an even chunk's first, stands at m + (m >> 4).
+        chunk_lds_sync();
+        // step 3: d[n] = max(r[n] ... r[n + la]); sample m of the two chunks, m < 2048 counted from an even chunk's first, stands at chunk_word(m).
         // The look-ahead is read from LDS here, behind the fence: what depends on it and on k is then made where it is used, sixteen compares,
         // not carried through the whole chunk loop as sixteen masks and sixteen addresses.
         const int la = la_lds, q = la >> 4, rem = la & 15;
         const double ar = prm[kDynAr], omr = prm[kDynOmr], aa = prm[kDynAa], oma = prm[kDynOma], makeup = prm[kDynMakeup];
-        const int m0 = (int)(ck & 1) * kDynC + lane * kDynT;
+        const int m0 = (int)(ck & 1) * kChunkC + lane * kChunkT;
         if (!wide) {
 #pragma unroll 1
             for (int t = 1; t <= la; t++) {
 #pragma unroll
-                for (int k = 0; k < kDynT; k++) {
-                    const int m = (m0 + k + t) & (2 * kDynC - 1);
-                    dc[k] = dyn_max(dc[k], ring[m + (m >> 4)]);
+                for (int k = 0; k < kChunkT; k++) {
+                    const int m = (m0 + k + t) & (2 * kChunkC - 1);
+                    dc[k] = dyn_max(dc[k], ring[chunk_word(m)]);
                 }
             }
         } else {
@@ -258,16 +244,16 @@ __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src,
             for (int t = 1; t < q; t++) r1 = dyn_max(r1, lane_max[(l0 + t) & 127]);
             const double r2 = dyn_max(r1, lane_max[(l0 + q) & 127]);
 #pragma unroll
-            for (int k = 0; k < kDynT; k++) {
-                const int m = (m0 + k + la) & (2 * kDynC - 1);
-                dc[k] = dyn_max(dc[k], dyn_max(k + rem >= kDynT ? r2 : r1, ring[m + (m >> 4)]));
+            for (int k = 0; k < kChunkT; k++) {
+                const int m = (m0 + k + la) & (2 * kChunkC - 1);
+                dc[k] = dyn_max(dc[k], dyn_max(k + rem >= kChunkT ? r2 : r1, ring[chunk_word(m)]));
             }
         }
         // step 4: y1 = max(d, ar y1 + omr d), the step as the map y -> max(c, a y + b)
         {
             double A = ar, B = omr * dc[0], M = dc[0];
 #pragma unroll
-            for (int k = 1; k < kDynT; k++) {
+            for (int k = 1; k < kChunkT; k++) {
                 const double bk = omr * dc[k];
                 A = ar * A;
                 B = (ar * B) + bk;
@@ -289,7 +275,7 @@ __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src,
             double s = dyn_max(pM, (pA * y1c) + pB);
             if (sl == 0) s = y1c;
 #pragma unroll
-            for (int k = 0; k < kDynT; k++) {
+            for (int k = 0; k < kChunkT; k++) {
                 s = dyn_max(dc[k], (ar * s) + (omr * dc[k]));
                 dc[k] = s;
             }
@@ -299,7 +285,7 @@ __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src,
         {
             double A = aa, B = oma * dc[0];
 #pragma unroll
-            for (int k = 1; k < kDynT; k++) {
+            for (int k = 1; k < kChunkT; k++) {
                 const double bk = oma * dc[k];
                 A = aa * A;
                 B = (aa * B) + bk;
@@ -318,7 +304,7 @@ __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src,
             double s = (pA * ylc) + pB;
             if (sl == 0) s = ylc;
 #pragma unroll
-            for (int k = 0; k < kDynT; k++) {
+            for (int k = 0; k < kChunkT; k++) {
                 s = (aa * s) + (oma * dc[k]);
                 dc[k] = s;
             }
@@ -326,27 +312,23 @@ __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src,
         }
         // step 6: the gain, once per detector and sample; the chunk's samples are read again (they came through the caches a chunk ago)
 #pragma unroll
-        for (int k = 0; k < kDynT; k++) {
+        for (int k = 0; k < kChunkT; k++) {
             dc[k] = dyn_exp2((makeup - dc[k]) * kDynKInv, coef);
             if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int c = 0; c < DC; c++) {
-            float x[kDynT];
+            float x[kChunkT];
             dyn_load(stage, ip, c * src.cs, src.fs, p.in_len, ck, lane, x);
 #pragma unroll
-            for (int k = 0; k < kDynT; k++) stage[lane * kDynStride + k] = (float)((double)x[k] * dc[k]);
-            dyn_lds_sync();
-#pragma unroll 4
-            for (int j = 0; j < kDynT; j++) {
-                const int n = j * 64 + lane;
-                const long long g = n0 + n;
-                if (g < p.in_len) op[c * out.cs + g * out.fs] = stage[n + (n >> 4)];
-            }
-            dyn_lds_sync();                                // the next channel, or the next chunk, rewrites the stage
+            for (int k = 0; k < kChunkT; k++) x[k] = (float)((double)x[k] * dc[k]);
+            chunk_lane_write(stage, lane, x);
+            chunk_lds_sync();
+            chunk_store<4>(stage, op + c * out.cs, out.fs, n0, p.in_len, lane);
+            chunk_lds_sync();                              // the next channel, or the next chunk, rewrites the stage
         }
 #pragma unroll
-        for (int k = 0; k < kDynT; k++) dc[k] = dn[k];
+        for (int k = 0; k < kChunkT; k++) dc[k] = dn[k];
     }
     if (carry && lane == 0) {
         carry[0] = y1c;

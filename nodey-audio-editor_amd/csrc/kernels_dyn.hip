@@ -36,21 +36,21 @@ using namespace nae;
 // the one statement of the parameter rules of nae_dyn_block_f32 and nae_dyn_create (ctx may be null: no message then)
 int nae_dyn_check(nae_ctx* ctx, const nae_dyn_params* p, int ch)
 {
-    const auto fail = [&](int code, const char* what) { return ctx ? nae_fail(ctx, code, what) : code; };
-    if (!p) return fail(NAE_ERR_INVALID, "dyn: null pointer");
-    if (ch != 1 && ch != 2) return fail(NAE_ERR_INVALID, "channel count must be 1 or 2");
+    if (!p) return nae_fail_opt(ctx, NAE_ERR_INVALID, "dyn: null pointer");
+    if (ch != 1 && ch != 2) return nae_fail_opt(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
     if (!isfinite(p->threshold_db) || !isfinite(p->slope) || !isfinite(p->knee_db) || !isfinite(p->alpha_attack) || !isfinite(p->alpha_release) ||
         !isfinite(p->makeup_db))
-        return fail(NAE_ERR_INVALID, "dyn: non-finite parameter");
-    if (p->threshold_db < NAE_DYN_MIN_THRESHOLD_DB || p->threshold_db > NAE_DYN_MAX_THRESHOLD_DB) return fail(NAE_ERR_INVALID, "dyn: threshold_db outside -60 ... 0");
-    if (p->slope < 0.0 || p->slope > 1.0) return fail(NAE_ERR_INVALID, "dyn: slope outside 0 ... 1");
-    if (p->knee_db < 0.0 || p->knee_db > NAE_DYN_MAX_KNEE_DB) return fail(NAE_ERR_INVALID, "dyn: knee_db outside 0 ... 24");
+        return nae_fail_opt(ctx, NAE_ERR_INVALID, "dyn: non-finite parameter");
+    if (p->threshold_db < NAE_DYN_MIN_THRESHOLD_DB || p->threshold_db > NAE_DYN_MAX_THRESHOLD_DB)
+        return nae_fail_opt(ctx, NAE_ERR_INVALID, "dyn: threshold_db outside -60 ... 0");
+    if (p->slope < 0.0 || p->slope > 1.0) return nae_fail_opt(ctx, NAE_ERR_INVALID, "dyn: slope outside 0 ... 1");
+    if (p->knee_db < 0.0 || p->knee_db > NAE_DYN_MAX_KNEE_DB) return nae_fail_opt(ctx, NAE_ERR_INVALID, "dyn: knee_db outside 0 ... 24");
     if (p->alpha_attack < 0.0 || p->alpha_attack >= 1.0 || p->alpha_release < 0.0 || p->alpha_release >= 1.0)
-        return fail(NAE_ERR_INVALID, "dyn: alpha outside [0, 1)");
-    if (p->makeup_db < -NAE_DYN_MAX_MAKEUP_DB || p->makeup_db > NAE_DYN_MAX_MAKEUP_DB) return fail(NAE_ERR_INVALID, "dyn: makeup_db outside -24 ... 24");
-    if (p->lookahead < 0) return fail(NAE_ERR_INVALID, "dyn: negative lookahead");
-    if (p->link != 0 && p->link != 1) return fail(NAE_ERR_INVALID, "dyn: link must be 0 or 1");
-    if (p->lookahead > NAE_DYN_MAX_LOOKAHEAD) return fail(NAE_ERR_UNSUPPORTED, "dyn: lookahead above 1024 samples");
+        return nae_fail_opt(ctx, NAE_ERR_INVALID, "dyn: alpha outside [0, 1)");
+    if (p->makeup_db < -NAE_DYN_MAX_MAKEUP_DB || p->makeup_db > NAE_DYN_MAX_MAKEUP_DB) return nae_fail_opt(ctx, NAE_ERR_INVALID, "dyn: makeup_db outside -24 ... 24");
+    if (p->lookahead < 0) return nae_fail_opt(ctx, NAE_ERR_INVALID, "dyn: negative lookahead");
+    if (p->link != 0 && p->link != 1) return nae_fail_opt(ctx, NAE_ERR_INVALID, "dyn: link must be 0 or 1");
+    if (p->lookahead > NAE_DYN_MAX_LOOKAHEAD) return nae_fail_opt(ctx, NAE_ERR_UNSUPPORTED, "dyn: lookahead above 1024 samples");
     return NAE_OK;
 }
 
@@ -102,7 +102,7 @@ int nae_dyn_block_f32(nae_ctx* ctx, const nae_dyn_params* params, const nae_sig*
     if (rc) return rc;
     if (in_len == 0 || n_streams == 0) return NAE_OK;
     if (!src->base || !dst->base) return nae_fail(ctx, NAE_ERR_INVALID, "dyn: null pointer");
-    return nae_launch_dyn(ctx, params, src, in_len, ch, n_streams, dst, 0, (in_len + kDynC - 1) / kDynC, nullptr);
+    return nae_launch_dyn(ctx, params, src, in_len, ch, n_streams, dst, 0, nae_chunks(in_len), nullptr);
 }
 
 // DESIGN.md §3, "K12 dynamics", "Design"

@@ -17,7 +17,6 @@
 
 namespace nae {
 
-static_assert(kEqT == kDynT && kEqC == kDynC, "DESIGN.md §3, K15: the key filter runs in the dynamics' tiling");
 static_assert(NAE_DYNKEY_MAX_SECTIONS <= NAE_EQ_MAX_SECTIONS && NAE_DYNKEY_MAX_SECTIONS <= 64, "a lane per section, in K11's constant block");
 
 // What the key source needs per level, kept in LDS and read where a level starts, as wave-uniform values: as kernel arguments the key's
@@ -44,7 +43,7 @@ struct DynKeySource {
     double st1[KC], st2[KC], sv1[KC], sv2[KC];
     static constexpr bool kSpareSgprs = FILT;          // the sections need the SGPRs the walk's lane masks and addresses would hold through their level
 
-    __device__ void level(float* stage, long long ck, float (&x)[kDynT])
+    __device__ void level(float* stage, long long ck, float (&x)[kChunkT])
     {
         const float* kp = reinterpret_cast<const float*>(dynkey_uniform(kw[kKeyBase]));
         const long long cs = dynkey_uniform(kw[kKeyCs]), fs = dynkey_uniform(kw[kKeyFs]);
@@ -59,18 +58,18 @@ struct DynKeySource {
                 asm volatile("" : "+v"(ln));
                 sv1[c] = st1[c];
                 sv2[c] = st2[c];
-                float xf[kDynT];
+                float xf[kChunkT];
                 dyn_load(stage, kp, c * cs, fs, p.in_len, ck, lane, xf);
-                double w[kDynT];
+                double w[kChunkT];
 #pragma unroll
-                for (int k = 0; k < kDynT; k++) w[k] = (double)xf[k];
+                for (int k = 0; k < kChunkT; k++) w[k] = (double)xf[k];
 #pragma unroll 1
                 for (int s = 0; s < n_sections; s++) eq_section(w, s, ln, tab, pq, st1[c], st2[c]);
                 // the lane's samples inside the signal: one number, compared where it is used (sixteen bounds masks are 32 SGPRs)
-                const long long left = p.in_len - (ck * kDynC + ln * kDynT);
-                const int inside = left < 0 ? 0 : (left > kDynT ? kDynT : (int)left);
+                const long long left = p.in_len - (ck * kChunkC + ln * kChunkT);
+                const int inside = left < 0 ? 0 : (left > kChunkT ? kChunkT : (int)left);
 #pragma unroll
-                for (int k = 0; k < kDynT; k++) {
+                for (int k = 0; k < kChunkT; k++) {
                     const float m = k < inside ? (float)fabs(w[k]) : 0.0f;         // the ringing behind the signal's end is no demand
                     x[k] = c == 0 ? m : (m > x[k] ? m : x[k]);
                     if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);          // four samples' masks in flight, not sixteen
@@ -94,7 +93,7 @@ template <int DC, int KC, bool FILT>
 __global__ __launch_bounds__(64) void dynkey_kernel(SigViewD src, SigViewD key, OutViewD out, DynParams p, int key_ch, int n_sections,
                                                     const double* __restrict__ tab, double* state, double* fstate)
 {
-    constexpr int kTab = FILT ? kEqTabOfs + NAE_DYNKEY_MAX_SECTIONS * kEqTab : 1, kPq = FILT ? NAE_DYNKEY_MAX_SECTIONS * 2 * kEqT : 1;
+    constexpr int kTab = FILT ? kEqTabOfs + NAE_DYNKEY_MAX_SECTIONS * kEqTab : 1, kPq = FILT ? NAE_DYNKEY_MAX_SECTIONS * 2 * kChunkT : 1;
     __shared__ long long kw[kKeyWords];
     __shared__ double ltab[kTab];      // the constant block as far as the sections reach: read at wave-uniform addresses (a broadcast)
     __shared__ double pq[kPq];         // p and q of every section, as eq_cascade_kernel keeps them
@@ -117,7 +116,7 @@ __global__ __launch_bounds__(64) void dynkey_kernel(SigViewD src, SigViewD key, 
     double* carry = FILT && fstate && lane < n_sections ? fstate + (det * KC * NAE_DYNKEY_MAX_SECTIONS + lane) * 2 : nullptr;
     if constexpr (FILT) {
         for (int i = lane; i < kEqTabOfs + n_sections * kEqTab; i += 64) ltab[i] = tab[i];
-        for (int i = lane; i < n_sections * 2 * kEqT; i += 64) pq[i] = tab[kEqTabOfs + (i / (2 * kEqT)) * kEqTab + (i % (2 * kEqT))];
+        eq_stage_pq(pq, tab, n_sections, lane, 64);
 #pragma unroll
         for (int c = 0; c < KC; c++) {
             mag.st1[c] = mag.st2[c] = 0.0;
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(64) void dynkey_kernel(SigViewD src, SigViewD key, 
             }
         }
     }
-    eq_lds_sync();
+    chunk_lds_sync();
     dyn_walk<DC>(ip, op, src, out, p, state, det, lane, mag);
     if constexpr (FILT) {
 #pragma unroll
@@ -149,13 +148,12 @@ using namespace nae;
 // nae_dyn_check, then the key's
 int nae_dynkey_check(nae_ctx* ctx, const nae_dynkey_params* p, int ch)
 {
-    const auto fail = [&](int code, const char* what) { return ctx ? nae_fail(ctx, code, what) : code; };
-    if (!p) return fail(NAE_ERR_INVALID, "dynkey: null pointer");
+    if (!p) return nae_fail_opt(ctx, NAE_ERR_INVALID, "dynkey: null pointer");
     const int rc = nae_dyn_check(ctx, &p->dyn, ch);
     if (rc) return rc;
-    if (p->key_ch != 0 && p->key_ch != 1 && p->key_ch != ch) return fail(NAE_ERR_INVALID, "dynkey: key_ch must be 0, 1 or the channel count");
-    if (p->n_sections < 0) return fail(NAE_ERR_INVALID, "dynkey: negative n_sections");
-    if (p->n_sections > NAE_DYNKEY_MAX_SECTIONS) return fail(NAE_ERR_UNSUPPORTED, "dynkey: at most 4 sections");
+    if (p->key_ch != 0 && p->key_ch != 1 && p->key_ch != ch) return nae_fail_opt(ctx, NAE_ERR_INVALID, "dynkey: key_ch must be 0, 1 or the channel count");
+    if (p->n_sections < 0) return nae_fail_opt(ctx, NAE_ERR_INVALID, "dynkey: negative n_sections");
+    if (p->n_sections > NAE_DYNKEY_MAX_SECTIONS) return nae_fail_opt(ctx, NAE_ERR_UNSUPPORTED, "dynkey: at most 4 sections");
     return p->n_sections ? nae_eq_check(ctx, &p->coef[0][0], p->n_sections, p->key_ch ? p->key_ch : ch) : NAE_OK;   // the sections run on the key's channels
 }
 
@@ -199,7 +197,7 @@ int nae_dynkey_block_f32(nae_ctx* ctx, const nae_dynkey_params* params, const na
     // the key filter's tables are the context's, with nae_eq_block_f32's: a call with the coefficients of the last one uploads nothing
     double* d_block = nullptr;
     if (params->n_sections && (rc = nae_eq_cached_block(ctx, &params->coef[0][0], params->n_sections, &d_block))) return rc;
-    return nae_launch_dynkey(ctx, params, d_block, src, key, in_len, ch, n_streams, dst, 0, (in_len + kDynC - 1) / kDynC, nullptr, nullptr);
+    return nae_launch_dynkey(ctx, params, d_block, src, key, in_len, ch, n_streams, dst, 0, nae_chunks(in_len), nullptr, nullptr);
 }
 
 } // extern "C"

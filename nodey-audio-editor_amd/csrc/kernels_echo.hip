@@ -3,7 +3,7 @@
 // The delay is at least one K11 chunk (NAE_ECHO_MIN_DELAY = NAE_EQ_CHUNK), so when a chunk starts, all of its delayed input has been written:
 // a chunk of the loop is one K11 cascade over known samples, and the recurrence over the delay needs no scan.  One workgroup per stream, one
 // wave per channel; every wave walks the chunks in order.  Per chunk a wave loads its 1024 input samples and the 1024 delayed samples of the
-// line it listens to (its own, or with `cross` the other channel's) coalesced into two LDS stages in K11's lane order (eq_cascade.h), runs
+// line it listens to (its own, or with `cross` the other channel's) coalesced into two LDS stages in K11's lane order (chunk_stage.h), runs
 // eq_section per section on the delayed samples, forms the line's new samples w and the output y in registers, and stores both coalesced
 // through the same stages.  The line is a ring of R samples per stream-channel in device memory, R the smallest multiple of the chunk with
 // R >= max(D_0, D_1) + 1024, addressed by the absolute sample index mod R: a chunk's store never wraps (its load may, at any sample), and the
@@ -32,18 +32,16 @@ struct EchoParams {
     int delay[2];
 };
 
-constexpr int kEchoStage = kEqC + 64;   // K11's padded chunk: sample n at n + (n >> 4)
-
 // line: [n_streams][ch][R] floats; state: [n_streams][ch][NAE_ECHO_MAX_SECTIONS][2] doubles, the carry (z1, z2) of every section in front of
 // chunk c_origin, replaced by the one behind chunk c_stop - 1; null: zero in, nothing out (the block call)
 __global__ __launch_bounds__(128) void echo_kernel(SigViewD src, OutViewD out, EchoParams p, const double* __restrict__ tab, float* line, double* state)
 {
-    __shared__ float stage[2][2][kEchoStage];                    // [wave][x / y | v / w]
-    __shared__ double pq[NAE_ECHO_MAX_SECTIONS * 2 * kEqT];      // p and q of every section: read at wave-uniform addresses (a broadcast)
+    __shared__ float stage[2][2][kChunkStage];                   // [wave][x / y | v / w]
+    __shared__ double pq[NAE_ECHO_MAX_SECTIONS * 2 * kChunkT];   // p and q of every section: read at wave-uniform addresses (a broadcast)
     const int lane = threadIdx.x & 63, c = threadIdx.x >> 6;
     const long long s_idx = blockIdx.x;
     if (s_idx >= p.n_streams) return;                            // the whole workgroup: no wave is left alone at a barrier
-    for (int i = threadIdx.x; i < p.n_sections * 2 * kEqT; i += blockDim.x) pq[i] = tab[kEqTabOfs + (i / (2 * kEqT)) * kEqTab + (i % (2 * kEqT))];
+    eq_stage_pq(pq, tab, p.n_sections, threadIdx.x, blockDim.x);
     __syncthreads();
     float* sx = stage[c][0];
     float* sv = stage[c][1];
@@ -56,20 +54,17 @@ __global__ __launch_bounds__(128) void echo_kernel(SigViewD src, OutViewD out, E
     float* wline = line + sc * R;
     const double g = p.g, wet = p.wet, dry = p.dry;
 
-    double st1 = 0.0, st2 = 0.0;                                 // lane s: the carry of section s
-    if (state && lane < S) {
-        st1 = state[(sc * NAE_ECHO_MAX_SECTIONS + lane) * 2];
-        st2 = state[(sc * NAE_ECHO_MAX_SECTIONS + lane) * 2 + 1];
-    }
+    double st1, st2;                                             // lane s: the carry of section s
+    eq_carry_load(state, sc, NAE_ECHO_MAX_SECTIONS, lane, S, st1, st2);
 #pragma unroll 1
     for (long long ck = p.c_origin; ck < p.c_stop; ck++) {
-        const long long n0 = ck * kEqC;
+        const long long n0 = ck * kChunkC;
         // sample n0 - D of the listened line stands at rpos (n0 - D may be negative: such samples are not read)
         long long rpos = (n0 - D) % R;
         if (rpos < 0) rpos += R;
         const long long wpos = n0 % R;                           // R is a multiple of the chunk: [wpos, wpos + 1024) does not wrap
 #pragma unroll
-        for (int j = 0; j < kEqT; j++) {
+        for (int j = 0; j < kChunkT; j++) {
             const int n = j * 64 + lane;
             const long long gi = n0 + n;
             long long r = rpos + n;
@@ -78,36 +73,41 @@ __global__ __launch_bounds__(128) void echo_kernel(SigViewD src, OutViewD out, E
             // is dropped behind them: 32 loads in flight, not 32 branches that each wait for their own
             const bool in = gi < p.in_len;
             const float xv = ip[(in ? gi : p.in_len - 1) * src.fs], lv = rline[r];
-            sx[n + (n >> 4)] = in ? xv : 0.0f;
-            sv[n + (n >> 4)] = in && gi >= D ? lv : 0.0f;
+            sx[chunk_word(n)] = in ? xv : 0.0f;
+            sv[chunk_word(n)] = in && gi >= D ? lv : 0.0f;
         }
-        eq_lds_sync();
-        float xs[kEqT];
-        double f[kEqT];
+        chunk_lds_sync();
+        float xs[kChunkT];
+        double f[kChunkT];
+        // the two stages word by word, not one chunk_lane_read after the other: that order measured 5 ... 10 % slower at 8 streams
+        // (profiles/r24_chunk_stage.md)
 #pragma unroll
-        for (int k = 0; k < kEqT; k++) {
-            xs[k] = sx[lane * kEqStride + k];
-            f[k] = (double)sv[lane * kEqStride + k];
+        for (int k = 0; k < kChunkT; k++) {
+            xs[k] = sx[lane * kChunkStride + k];
+            f[k] = (double)sv[lane * kChunkStride + k];
         }
 #pragma unroll 1
         for (int s = 0; s < S; s++) {
             eq_section(f, s, lane, tab, pq, st1, st2);
         }
         // the lanes read their own words above and write only them here; the coalesced reads below need the other lanes' words
+        double y[kChunkT];
 #pragma unroll
-        for (int k = 0; k < kEqT; k++) {
+        for (int k = 0; k < kChunkT; k++) {
             const double xd = (double)xs[k];
-            sv[lane * kEqStride + k] = (float)(xd + (g * f[k]));
-            sx[lane * kEqStride + k] = (float)((dry * xd) + (wet * f[k]));
+            y[k] = (dry * xd) + (wet * f[k]);
+            f[k] = xd + (g * f[k]);                              // w, the line's new sample
         }
-        eq_lds_sync();
+        chunk_lane_write(sv, lane, f);
+        chunk_lane_write(sx, lane, y);
+        chunk_lds_sync();
 #pragma unroll
-        for (int j = 0; j < kEqT; j++) {
+        for (int j = 0; j < kChunkT; j++) {
             const int n = j * 64 + lane;
             const long long gi = n0 + n;
             if (gi < p.in_len) {
-                op[gi * out.fs] = sx[n + (n >> 4)];
-                wline[wpos + n] = sv[n + (n >> 4)];
+                op[gi * out.fs] = sx[chunk_word(n)];
+                wline[wpos + n] = sv[chunk_word(n)];
             }
         }
         // this chunk's line stores, of both waves, before the next chunk's line loads (and the stages' reads before they are rewritten).
@@ -117,10 +117,7 @@ __global__ __launch_bounds__(128) void echo_kernel(SigViewD src, OutViewD out, E
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    if (state && lane < S) {
-        state[(sc * NAE_ECHO_MAX_SECTIONS + lane) * 2] = st1;
-        state[(sc * NAE_ECHO_MAX_SECTIONS + lane) * 2 + 1] = st2;
-    }
+    eq_carry_store(state, sc, NAE_ECHO_MAX_SECTIONS, lane, S, st1, st2);
 }
 
 } // namespace nae
@@ -131,17 +128,16 @@ using namespace nae;
 // the one statement of the parameter rules of nae_echo_block_f32 and nae_echo_create (ctx may be null: no message then)
 int nae_echo_check(nae_ctx* ctx, const nae_echo_params* p, int ch)
 {
-    const auto fail = [&](int code, const char* what) { return ctx ? nae_fail(ctx, code, what) : code; };
-    if (!p) return fail(NAE_ERR_INVALID, "echo: null pointer");
-    if (ch != 1 && ch != 2) return fail(NAE_ERR_INVALID, "channel count must be 1 or 2");
-    if (!isfinite(p->feedback) || !isfinite(p->wet) || !isfinite(p->dry)) return fail(NAE_ERR_INVALID, "echo: non-finite parameter");
-    if (!(fabs(p->feedback) <= NAE_ECHO_MAX_FEEDBACK)) return fail(NAE_ERR_INVALID, "echo: |feedback| above 0.99");
-    if (p->cross != 0 && p->cross != 1) return fail(NAE_ERR_INVALID, "echo: cross must be 0 or 1");
-    if (p->n_sections < 0) return fail(NAE_ERR_INVALID, "echo: negative n_sections");
-    if (p->n_sections > NAE_ECHO_MAX_SECTIONS) return fail(NAE_ERR_UNSUPPORTED, "echo: at most 4 sections");
+    if (!p) return nae_fail_opt(ctx, NAE_ERR_INVALID, "echo: null pointer");
+    if (ch != 1 && ch != 2) return nae_fail_opt(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
+    if (!isfinite(p->feedback) || !isfinite(p->wet) || !isfinite(p->dry)) return nae_fail_opt(ctx, NAE_ERR_INVALID, "echo: non-finite parameter");
+    if (!(fabs(p->feedback) <= NAE_ECHO_MAX_FEEDBACK)) return nae_fail_opt(ctx, NAE_ERR_INVALID, "echo: |feedback| above 0.99");
+    if (p->cross != 0 && p->cross != 1) return nae_fail_opt(ctx, NAE_ERR_INVALID, "echo: cross must be 0 or 1");
+    if (p->n_sections < 0) return nae_fail_opt(ctx, NAE_ERR_INVALID, "echo: negative n_sections");
+    if (p->n_sections > NAE_ECHO_MAX_SECTIONS) return nae_fail_opt(ctx, NAE_ERR_UNSUPPORTED, "echo: at most 4 sections");
     for (int c = 0; c < ch; c++)
         if (p->delay[c] < NAE_ECHO_MIN_DELAY || p->delay[c] > NAE_ECHO_MAX_DELAY)
-            return fail(NAE_ERR_UNSUPPORTED, "echo: the delay must be 1024 ... 1048576 samples");
+            return nae_fail_opt(ctx, NAE_ERR_UNSUPPORTED, "echo: the delay must be 1024 ... 1048576 samples");
     return p->n_sections ? nae_eq_check(ctx, &p->coef[0][0], p->n_sections, ch) : NAE_OK;
 }
 
@@ -149,7 +145,7 @@ int nae_echo_check(nae_ctx* ctx, const nae_echo_params* p, int ch)
 size_t nae_echo_ring(const nae_echo_params* p, int ch)
 {
     const size_t d = (size_t)(ch == 2 && p->delay[1] > p->delay[0] ? p->delay[1] : p->delay[0]);
-    return (d + 2 * (size_t)kEqC - 1) / kEqC * kEqC;
+    return nae_chunks(d + kChunkC) * kChunkC;
 }
 
 // chunks [c_origin, c_stop) of n_streams x ch signals of in_len samples (absolute indexing); d_block: the sections' K11 constant block, unused
@@ -203,7 +199,7 @@ int nae_echo_block_f32(nae_ctx* ctx, const nae_echo_params* params, const nae_si
     group = group < 1 ? 1 : group < n_streams ? group : n_streams;
     rc = nae_ws_reserve(ctx, &ctx->ws_echo, &ctx->ws_echo_bytes, group * line_bytes);
     if (rc) return rc;
-    const size_t chunks = (in_len + kEqC - 1) / kEqC;
+    const size_t chunks = nae_chunks(in_len);
     for (size_t s0 = 0; s0 < n_streams; s0 += group) {
         const size_t n = s0 + group < n_streams ? group : n_streams - s0;
         nae_sig gs = *src, gd = *dst;

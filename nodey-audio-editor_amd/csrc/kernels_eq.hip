@@ -12,7 +12,8 @@
 // 16 x (5 + 56) doubles.  The coefficients and the maps are read from it at wave-uniform addresses; p and q of the call's sections are copied
 // into LDS once per launch and read there as broadcasts (read from the block they cost 28 SGPR spills).
 // The translation unit is built with -ffp-contract=off: every step is one IEEE operation, in the order of the CPU statement
-// (tests/eq_ref/ref_eq.c).  The section's steps stand in eq_cascade.h, which the loudness meter (kernels_loud.hip) runs too.
+// (tests/eq_ref/ref_eq.c).  The tiling and the LDS stage stand in chunk_stage.h, which every chunked kernel shares; the section's steps, the copy
+// of p and q and the carries' way in and out in eq_cascade.h, which the loudness meter, the keyed dynamics and the echo run too.
 #include "eq_cascade.h"
 #include <math.h>
 #include <string.h>
@@ -31,57 +32,39 @@ struct EqParams {
 // c_stop - 1; null: zero in, nothing out (the block call)
 __global__ __launch_bounds__(64) void eq_cascade_kernel(SigViewD src, OutViewD out, EqParams p, const double* __restrict__ tab, double* state)
 {
-    __shared__ float stage[kEqC + 64];
-    __shared__ double pq[NAE_EQ_MAX_SECTIONS * 2 * kEqT];  // p and q of every section: read at wave-uniform addresses (a broadcast)
+    __shared__ float stage[kChunkStage];
+    __shared__ double pq[NAE_EQ_MAX_SECTIONS * 2 * kChunkT];   // p and q of every section: read at wave-uniform addresses (a broadcast)
     const int lane = threadIdx.x;
     const long long sc = blockIdx.x;
     if (sc >= p.n_sc) return;
-    for (int i = lane; i < p.n_sections * 2 * kEqT; i += 64) pq[i] = tab[kEqTabOfs + (i / (2 * kEqT)) * kEqTab + (i % (2 * kEqT))];
-    eq_lds_sync();
+    eq_stage_pq(pq, tab, p.n_sections, lane, 64);
+    chunk_lds_sync();
     const long long s_idx = sc / p.ch;
     const int c = (int)(sc % p.ch);
     const float* ip = src.base + s_idx * src.ss + c * src.cs;
     float* op = out.base + s_idx * out.ss + c * out.cs;
     const int S = p.n_sections;
 
-    double st1 = 0.0, st2 = 0.0;                           // lane s: the carry of section s
-    if (state && lane < S) {
-        st1 = state[(sc * NAE_EQ_MAX_SECTIONS + lane) * 2];
-        st2 = state[(sc * NAE_EQ_MAX_SECTIONS + lane) * 2 + 1];
-    }
+    double st1, st2;                                       // lane s: the carry of section s
+    eq_carry_load(state, sc, NAE_EQ_MAX_SECTIONS, lane, S, st1, st2);
 #pragma unroll 1
     for (long long ck = p.c_origin; ck < p.c_stop; ck++) {
-        const long long n0 = ck * kEqC;
-#pragma unroll
-        for (int j = 0; j < kEqT; j++) {
-            const int n = j * 64 + lane;
-            const long long g = n0 + n;
-            stage[n + (n >> 4)] = g < p.in_len ? ip[g * src.fs] : 0.0f;
-        }
-        eq_lds_sync();
-        double x[kEqT];
-#pragma unroll
-        for (int k = 0; k < kEqT; k++) x[k] = (double)stage[lane * kEqStride + k];
+        const long long n0 = ck * kChunkC;
+        chunk_load<false, kChunkT>(stage, ip, src.fs, n0, p.in_len, lane);
+        chunk_lds_sync();
+        double x[kChunkT];
+        chunk_lane_read(stage, lane, x);
 #pragma unroll 1
         for (int s = 0; s < S; s++) {
             eq_section(x, s, lane, tab, pq, st1, st2);
         }
         // the lanes read their own words above and write only them here; the coalesced read below needs the other lanes' words
-#pragma unroll
-        for (int k = 0; k < kEqT; k++) stage[lane * kEqStride + k] = (float)x[k];
-        eq_lds_sync();
-#pragma unroll
-        for (int j = 0; j < kEqT; j++) {
-            const int n = j * 64 + lane;
-            const long long g = n0 + n;
-            if (g < p.in_len) op[g * out.fs] = stage[n + (n >> 4)];
-        }
-        eq_lds_sync();                                     // the next chunk rewrites the stage
+        chunk_lane_write(stage, lane, x);
+        chunk_lds_sync();
+        chunk_store<kChunkT>(stage, op, out.fs, n0, p.in_len, lane);
+        chunk_lds_sync();                                  // the next chunk rewrites the stage
     }
-    if (state && lane < S) {
-        state[(sc * NAE_EQ_MAX_SECTIONS + lane) * 2] = st1;
-        state[(sc * NAE_EQ_MAX_SECTIONS + lane) * 2 + 1] = st2;
-    }
+    eq_carry_store(state, sc, NAE_EQ_MAX_SECTIONS, lane, S, st1, st2);
 }
 
 } // namespace nae
@@ -94,16 +77,15 @@ size_t nae_eq_block_doubles() { return kEqBlockDoubles; }
 // the one statement of the parameter rules of nae_eq_block_f32 and nae_eq_create (ctx may be null: no message then)
 int nae_eq_check(nae_ctx* ctx, const double* coef, int n_sections, int ch)
 {
-    const auto fail = [&](int code, const char* what) { return ctx ? nae_fail(ctx, code, what) : code; };
-    if (!coef) return fail(NAE_ERR_INVALID, "eq: null pointer");
-    if (n_sections < 1) return fail(NAE_ERR_INVALID, "eq: n_sections must be at least 1");
-    if (ch != 1 && ch != 2) return fail(NAE_ERR_INVALID, "channel count must be 1 or 2");
-    if (n_sections > NAE_EQ_MAX_SECTIONS) return fail(NAE_ERR_UNSUPPORTED, "eq: at most 16 sections");
+    if (!coef) return nae_fail_opt(ctx, NAE_ERR_INVALID, "eq: null pointer");
+    if (n_sections < 1) return nae_fail_opt(ctx, NAE_ERR_INVALID, "eq: n_sections must be at least 1");
+    if (ch != 1 && ch != 2) return nae_fail_opt(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
+    if (n_sections > NAE_EQ_MAX_SECTIONS) return nae_fail_opt(ctx, NAE_ERR_UNSUPPORTED, "eq: at most 16 sections");
     for (int s = 0; s < n_sections; s++) {
         const double* c = coef + 5 * s;
         for (int i = 0; i < 5; i++)
-            if (!isfinite(c[i])) return fail(NAE_ERR_INVALID, "eq: non-finite coefficient");
-        if (!(fabs(c[4]) < 1.0 && fabs(c[3]) < 1.0 + c[4])) return fail(NAE_ERR_INVALID, "eq: section is not strictly stable");
+            if (!isfinite(c[i])) return nae_fail_opt(ctx, NAE_ERR_INVALID, "eq: non-finite coefficient");
+        if (!(fabs(c[4]) < 1.0 && fabs(c[3]) < 1.0 + c[4])) return nae_fail_opt(ctx, NAE_ERR_INVALID, "eq: section is not strictly stable");
     }
     return NAE_OK;
 }
@@ -154,15 +136,15 @@ void eq_make_tables(const double* coef, int n_sections, double* blk)
         const EqDD na1 = {-coef[5 * s + 3], 0.0}, na2 = {-coef[5 * s + 4], 0.0};
         memcpy(blk + s * kEqCoefs, coef + 5 * s, 5 * sizeof(double));
         double* t = blk + kEqTabOfs + s * kEqTab;
-        double* ph = t + 2 * kEqT;
+        double* ph = t + 2 * kChunkT;
         EqDD m[4], r[4];
         for (int col = 0; col < 2; col++) {
             EqDD z1 = {col == 0 ? 1.0 : 0.0, 0.0}, z2 = {col == 0 ? 0.0 : 1.0, 0.0};
-            for (int n = 0; n < kEqT; n++) {
+            for (int n = 0; n < kChunkT; n++) {
                 const EqDD y = z1;
                 z1 = dd_add(dd_mul(na1, y), z2);
                 z2 = dd_mul(na2, y);
-                t[col * kEqT + n] = y.hi + y.lo;
+                t[col * kChunkT + n] = y.hi + y.lo;
             }
             m[col] = z1;           // Phi: the two end states as columns, stored m00 m01 m10 m11
             m[2 + col] = z2;
@@ -245,7 +227,7 @@ int nae_eq_block_f32(nae_ctx* ctx, const double* coef_host, int n_sections, cons
     if (!src->base || !dst->base) return nae_fail(ctx, NAE_ERR_INVALID, "eq: null pointer");
     double* d_block = nullptr;
     if ((rc = nae_eq_cached_block(ctx, coef_host, n_sections, &d_block))) return rc;
-    return nae_launch_eq(ctx, d_block, n_sections, src, in_len, ch, n_streams, dst, 0, (in_len + kEqC - 1) / kEqC, nullptr);
+    return nae_launch_eq(ctx, d_block, n_sections, src, in_len, ch, n_streams, dst, 0, nae_chunks(in_len), nullptr);
 }
 
 // DESIGN.md §3, "K11 biquad cascade", "Design": the Audio EQ Cookbook's forms in double, divided through by a0

@@ -1,6 +1,6 @@
 // kernels_loud.hip — K14, the loudness meter and normalizer ("K14 loudness") for gfx950: ITU-R BS.1770-4 / EBU R 128.
 //
-// loud_measure_kernel: one wave per stream-channel walks its chunks of 1024 samples in order, as K11 does (eq_cascade.h): a chunk is loaded
+// loud_measure_kernel: one wave per stream-channel walks its chunks of 1024 samples in order, as K11 does (chunk_stage.h): a chunk is loaded
 // coalesced into LDS and lane l reads its own 16 samples at a stride of 17 words.  In one pass over the chunk the lane runs the four phases of
 // the true-peak oversampler on the staged f32 samples (its own 16 and the 11 in front of them, which are the lane before's; the 11 in front of
 // the chunk stand in the stage's first row, where lane 63 leaves its samples for the next chunk), the K-weighting — K11's cascade with two
@@ -22,16 +22,16 @@ namespace nae {
 constexpr int kLdS = NAE_LOUD_SECTIONS, kLdPhases = NAE_LOUD_TP_PHASES, kLdTaps = NAE_LOUD_TP_TAPS, kLdHist = kLdTaps - 1;
 constexpr int kLdTapCount = kLdPhases * kLdTaps;
 // the stage: row r = 0 ... 64 of 16 samples at 17 r; row 0 is the 16 samples in front of the chunk, row l + 1 lane l's
-constexpr int kLdStage = (kEqC + kEqT) + (kEqC + kEqT) / kEqT;
+constexpr int kLdStage = (kChunkC + kChunkT) + (kChunkC + kChunkT) / kChunkT;
 // the constant block: K11's block of the two sections, then the 48 taps [phase][k] as f32
 constexpr size_t kLdBlockBytes = kEqBlockDoubles * sizeof(double) + kLdTapCount * sizeof(float);
-static_assert(kLdHist <= kEqT && kLdS <= NAE_EQ_MAX_SECTIONS, "the history is part of one lane's samples");
+static_assert(kLdHist <= kChunkT && kLdS <= NAE_EQ_MAX_SECTIONS, "the history is part of one lane's samples");
 
 // what a stream-channel carries between two launches; all zero in front of sample 0
 struct LoudState {
     double z[kLdS][2];     // the sections' carries (z1, z2)
     float true_peak, sample_peak;
-    float hist[kEqT];      // the 16 samples in front of the next chunk (the last 11 are read)
+    float hist[kChunkT];   // the 16 samples in front of the next chunk (the last 11 are read)
 };
 
 struct LoudParams {
@@ -47,14 +47,14 @@ struct LoudParams {
 __global__ __launch_bounds__(64) void loud_measure_kernel(SigViewD src, LoudParams p, const double* __restrict__ tab, LoudState* state, double* E)
 {
     __shared__ float stage[kLdStage];
-    __shared__ double pq[kLdS * 2 * kEqT];
+    __shared__ double pq[kLdS * 2 * kChunkT];
     const int lane = threadIdx.x;
     const long long sc = blockIdx.x;
     if (sc >= p.n_sc) return;
     const float* __restrict__ taps = reinterpret_cast<const float*>(tab + kEqBlockDoubles);
     LoudState* st = state + sc;
-    for (int i = lane; i < kLdS * 2 * kEqT; i += 64) pq[i] = tab[kEqTabOfs + (i / (2 * kEqT)) * kEqTab + (i % (2 * kEqT))];
-    if (lane < kEqT) stage[lane] = st->hist[lane];
+    eq_stage_pq(pq, tab, kLdS, lane, 64);
+    if (lane < kChunkT) stage[lane] = st->hist[lane];
     const long long s_idx = sc / p.ch;
     const int c = (int)(sc % p.ch);
     const float* ip = src.base + s_idx * src.ss + c * src.cs;
@@ -66,34 +66,28 @@ __global__ __launch_bounds__(64) void loud_measure_kernel(SigViewD src, LoudPara
         st2 = st->z[lane][1];
     }
     float tp = 0.0f, sp = 0.0f;                            // this lane's peaks over the launch
-    long long u_open = p.c_origin * kEqC / p.B;            // the open sub-block and its sum so far (wave-uniform)
+    long long u_open = p.c_origin * kChunkC / p.B;         // the open sub-block and its sum so far (wave-uniform)
     double e_open = u_open < p.n_sub ? Esc[u_open * p.ch] : 0.0;
     const long long tp_stop = p.in_len + kLdHist;          // v_p[n] counts for n < tp_stop
 #pragma unroll 1
     for (long long ck = p.c_origin; ck < p.c_stop; ck++) {
-        const long long n0 = ck * kEqC;
-#pragma unroll
-        for (int j = 0; j < kEqT; j++) {
-            const int n = j * 64 + lane;
-            const long long g = n0 + n;
-            stage[kEqStride + n + (n >> 4)] = g < p.in_len ? ip[g * src.fs] : 0.0f;
-        }
-        eq_lds_sync();
+        const long long n0 = ck * kChunkC;
+        chunk_load<false, kChunkT>(stage + kChunkStride, ip, src.fs, n0, p.in_len, lane);   // behind row 0
+        chunk_lds_sync();
         // xs[i]: sample 16 lane - 11 + i of the chunk: the last 11 of the row above, then the lane's own
-        float xs[kLdHist + kEqT];
+        float xs[kLdHist + kChunkT];
 #pragma unroll
-        for (int i = 0; i < kLdHist; i++) xs[i] = stage[lane * kEqStride + (kEqT - kLdHist) + i];
-#pragma unroll
-        for (int k = 0; k < kEqT; k++) xs[kLdHist + k] = stage[(lane + 1) * kEqStride + k];
+        for (int i = 0; i < kLdHist; i++) xs[i] = stage[lane * kChunkStride + (kChunkT - kLdHist) + i];
+        chunk_lane_read(stage + kChunkStride, lane, xs + kLdHist);
         // every lane has read the row above it; lane 63's samples are the next chunk's row 0
         if (lane == 63) {
 #pragma unroll
-            for (int k = 0; k < kEqT; k++) stage[k] = xs[kLdHist + k];
+            for (int k = 0; k < kChunkT; k++) stage[k] = xs[kLdHist + k];
         }
         // the peaks
-        const long long n_lane = n0 + lane * kEqT;
+        const long long n_lane = n0 + lane * kChunkT;
 #pragma unroll
-        for (int k = 0; k < kEqT; k++) {
+        for (int k = 0; k < kChunkT; k++) {
             const float ax = fabsf(xs[kLdHist + k]);
             sp = ax > sp ? ax : sp;
             const bool counts = n_lane + k < tp_stop;
@@ -107,21 +101,21 @@ __global__ __launch_bounds__(64) void loud_measure_kernel(SigViewD src, LoudPara
             }
         }
         // the K-weighting
-        double x[kEqT];
+        double x[kChunkT];
 #pragma unroll
-        for (int k = 0; k < kEqT; k++) x[k] = (double)xs[kLdHist + k];
+        for (int k = 0; k < kChunkT; k++) x[k] = (double)xs[kLdHist + k];
 #pragma unroll 1
         for (int s = 0; s < kLdS; s++) eq_section(x, s, lane, tab, pq, st1, st2);
         // the sub-blocks the chunk meets
-        const long long u_last = (n0 + kEqC - 1) / p.B;
+        const long long u_last = (n0 + kChunkC - 1) / p.B;
 #pragma unroll 1
         for (long long u = n0 / p.B; u <= u_last; u++) {
             // the lane's samples k of [lo, hi) lie in sub-block u
             const long long first = u * p.B - n_lane;
-            const int lo = (int)(first < 0 ? 0 : first > kEqT ? kEqT : first), hi = (int)(first + p.B < 0 ? 0 : first + p.B > kEqT ? kEqT : first + p.B);
+            const int lo = (int)(first < 0 ? 0 : first > kChunkT ? kChunkT : first), hi = (int)(first + p.B < 0 ? 0 : first + p.B > kChunkT ? kChunkT : first + p.B);
             double sum = 0.0;
 #pragma unroll
-            for (int k = 0; k < kEqT; k++) {
+            for (int k = 0; k < kChunkT; k++) {
                 const double sq = x[k] * x[k];
                 sum = (k >= lo && k < hi) ? sum + sq : sum;
             }
@@ -134,7 +128,7 @@ __global__ __launch_bounds__(64) void loud_measure_kernel(SigViewD src, LoudPara
             }
             e_open = e_open + sum;
         }
-        eq_lds_sync();                                     // the next chunk rewrites the stage
+        chunk_lds_sync();                                  // the next chunk rewrites the stage
     }
     if (lane == 0 && u_open < p.n_sub) Esc[u_open * p.ch] = e_open;
 #pragma unroll
@@ -152,7 +146,7 @@ __global__ __launch_bounds__(64) void loud_measure_kernel(SigViewD src, LoudPara
         st->z[lane][0] = st1;
         st->z[lane][1] = st2;
     }
-    if (lane < kEqT) st->hist[lane] = stage[lane];
+    if (lane < kChunkT) st->hist[lane] = stage[lane];
 }
 
 struct LoudGateParams {
@@ -286,15 +280,14 @@ static bool loud_rate_ok(int sample_rate)
 // the one statement of the parameter rules of the block entries and nae_loud_create (ctx may be null: no message then)
 int nae_loud_check(nae_ctx* ctx, const nae_loud_params* p, int ch)
 {
-    const auto fail = [&](int code, const char* what) { return ctx ? nae_fail(ctx, code, what) : code; };
-    if (!p) return fail(NAE_ERR_INVALID, "loud: null pointer");
-    if (ch != 1 && ch != 2) return fail(NAE_ERR_INVALID, "channel count must be 1 or 2");
-    if (!loud_rate_ok(p->sample_rate)) return fail(NAE_ERR_UNSUPPORTED, "loud: the sample rate must be 8000 ... 192000 and a multiple of 10");
-    if (p->sub_block != p->sample_rate / NAE_LOUD_SUBS_PER_S) return fail(NAE_ERR_INVALID, "loud: sub_block is not sample_rate / 10");
+    if (!p) return nae_fail_opt(ctx, NAE_ERR_INVALID, "loud: null pointer");
+    if (ch != 1 && ch != 2) return nae_fail_opt(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
+    if (!loud_rate_ok(p->sample_rate)) return nae_fail_opt(ctx, NAE_ERR_UNSUPPORTED, "loud: the sample rate must be 8000 ... 192000 and a multiple of 10");
+    if (p->sub_block != p->sample_rate / NAE_LOUD_SUBS_PER_S) return nae_fail_opt(ctx, NAE_ERR_INVALID, "loud: sub_block is not sample_rate / 10");
     const int rc = nae_eq_check(ctx, p->coef, kLdS, ch);
     if (rc) return rc;
     for (const double v : {p->gate_abs, p->target, p->ceiling_lin, p->max_gain_lin})
-        if (!(isfinite(v) && v > 0.0)) return fail(NAE_ERR_INVALID, "loud: a level is not positive and finite");
+        if (!(isfinite(v) && v > 0.0)) return nae_fail_opt(ctx, NAE_ERR_INVALID, "loud: a level is not positive and finite");
     return NAE_OK;
 }
 
@@ -312,7 +305,7 @@ int nae_loud_make_block(nae_ctx* ctx, const nae_loud_params* p, void* d_block)
 
 size_t nae_loud_chunks(size_t in_len, bool flushed)
 {
-    return flushed ? (in_len ? (in_len + kLdHist + kEqC - 1) / kEqC : 0) : in_len / kEqC;
+    return flushed ? (in_len ? nae_chunks(in_len + kLdHist) : 0) : in_len / kChunkC;
 }
 
 int nae_launch_loud_measure(nae_ctx* ctx, const nae_loud_params* p, const void* d_block, const nae_sig* src, size_t in_len, int ch, size_t n_streams,

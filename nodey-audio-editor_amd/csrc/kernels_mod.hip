@@ -11,11 +11,11 @@
 // the line's samples [n0 - 4096, n0 - 3072) stood, which no tap reads any more — and walks the chunk in runs of L: lane j < L computes the
 // voices' phases and delays, reads four ring words per voice, forms the tap, writes w over its own x in the ring (with feedback only: without,
 // w is x) and stores y, the run's lanes together (an LDS stage of one chunk in front of 16 coalesced stores was measured too:
-// profiles/r23_mod.md).  Between two runs the wave's LDS writes are ordered in front of its next reads (eq_lds_sync).
+// profiles/r23_mod.md).  Between two runs the wave's LDS writes are ordered in front of its next reads (chunk_lds_sync).
 // Samples in front of the stream's first read as zero: the 3072 ring words in front of the first chunk are filled from the handle's state, or
 // with zeros, before the first load.
 // The translation unit is built with -ffp-contract=off: every step is one IEEE operation, in the order of tests/mod_ref/ref_mod.c.
-#include "eq_cascade.h"
+#include "chunk_stage.h"
 #include <math.h>
 #include <string.h>
 
@@ -26,7 +26,7 @@ constexpr int kModRing = 4096, kModKeep = (int)NAE_MOD_KEEP;
 // 2048 waves (1024 stereo streams) then land ten on some CUs and fewer on others, and the launch ends with the fullest: the default chorus
 // measured 9.3 ms in most rounds and 7.4 in some, against 7.2 ... 7.3 in all with eight (profiles/r23_mod.md)
 constexpr int kModHold = 1024;
-static_assert(kModKeep + kEqC == kModRing && (double)kModKeep == NAE_MOD_MAX_DELAY + 2.0, "the ring holds one chunk and the deepest reach, floor(d) + 2");
+static_assert(kModKeep + kChunkC == kModRing && (double)kModKeep == NAE_MOD_MAX_DELAY + 2.0, "the ring holds one chunk and the deepest reach, floor(d) + 2");
 
 struct ModParams {
     long long in_len;      // samples of a stream-channel: samples at or past in_len are not stored
@@ -73,28 +73,28 @@ __global__ __launch_bounds__(64) void mod_kernel(SigViewD src, OutViewD out, Mod
 
     // the line in front of the first chunk (its indices may be negative: the mask is the index mod 4096 all the same)
     {
-        const long long first = p.c_origin * kEqC - kModKeep;
+        const long long first = p.c_origin * kChunkC - kModKeep;
         for (int j = lane; j < kModKeep; j += 64) ring[(int)((first + j) & (kModRing - 1))] = state ? state[sc * kModKeep + j] : 0.0f;
     }
 #pragma unroll 1
     for (long long ck = p.c_origin; ck < p.c_stop; ck++) {
-        const long long n0 = ck * kEqC;
+        const long long n0 = ck * kChunkC;
         const int slot0 = (int)(n0 & (kModRing - 1));              // a multiple of the chunk: [slot0, slot0 + 1024) does not wrap
         // every load is issued whatever the sample's place, from an address inside the signal, and what lies past in_len is dropped behind it:
         // 16 loads in flight, not 16 branches that each wait for their own
 #pragma unroll
-        for (int j = 0; j < kEqT; j++) {
+        for (int j = 0; j < kChunkT; j++) {
             const int i = j * 64 + lane;
             const long long gi = n0 + i;
             const bool in = gi < p.in_len;
             const float xv = ip[(in ? gi : p.in_len - 1) * src.fs];
             ring[slot0 + i] = in ? xv : 0.0f;
         }
-        eq_lds_sync();
+        chunk_lds_sync();
 #pragma unroll 1
-        for (int r = 0; r < kEqC; r += L) {
+        for (int r = 0; r < kChunkC; r += L) {
             const int i = r + lane;
-            if (lane < L && i < kEqC) {
+            if (lane < L && i < kChunkC) {
                 const long long gi = n0 + i;
                 const double xd = (double)ring[slot0 + i];
                 const unsigned turn = (unsigned)gi * rate_inc;     // the low 32 bits of n rate_inc
@@ -124,12 +124,12 @@ __global__ __launch_bounds__(64) void mod_kernel(SigViewD src, OutViewD out, Mod
                 if (gi < p.in_len) op[gi * out.fs] = y;
             }
             // this run's line samples before the next run's taps; without feedback the ring holds the input and no run writes it
-            if (loop) eq_lds_sync();
+            if (loop) chunk_lds_sync();
         }
     }
     if (state) {
-        eq_lds_sync();
-        const long long first = p.c_stop * kEqC - kModKeep;
+        chunk_lds_sync();
+        const long long first = p.c_stop * kChunkC - kModKeep;
         for (int j = lane; j < kModKeep; j += 64) state[sc * kModKeep + j] = ring[(int)((first + j) & (kModRing - 1))];
     }
 }
@@ -142,18 +142,17 @@ using namespace nae;
 // the one statement of the parameter rules of nae_mod_block_f32 and nae_mod_create (ctx may be null: no message then)
 int nae_mod_check(nae_ctx* ctx, const nae_mod_params* p, int ch)
 {
-    const auto fail = [&](int code, const char* what) { return ctx ? nae_fail(ctx, code, what) : code; };
-    if (!p) return fail(NAE_ERR_INVALID, "mod: null pointer");
-    if (ch != 1 && ch != 2) return fail(NAE_ERR_INVALID, "channel count must be 1 or 2");
+    if (!p) return nae_fail_opt(ctx, NAE_ERR_INVALID, "mod: null pointer");
+    if (ch != 1 && ch != 2) return nae_fail_opt(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
     if (!isfinite(p->delay) || !isfinite(p->depth) || !isfinite(p->feedback) || !isfinite(p->wet) || !isfinite(p->dry))
-        return fail(NAE_ERR_INVALID, "mod: non-finite parameter");
-    if (!(fabs(p->feedback) <= NAE_MOD_MAX_FEEDBACK)) return fail(NAE_ERR_INVALID, "mod: |feedback| above 0.95");
-    if (p->depth < 0.0) return fail(NAE_ERR_INVALID, "mod: negative depth");
-    if (p->n_voices < 1) return fail(NAE_ERR_INVALID, "mod: n_voices below 1");
-    if (p->shape != NAE_MOD_SINE && p->shape != NAE_MOD_TRIANGLE) return fail(NAE_ERR_INVALID, "mod: unknown shape");
-    if (p->n_voices > NAE_MOD_MAX_VOICES) return fail(NAE_ERR_UNSUPPORTED, "mod: at most 4 voices");
+        return nae_fail_opt(ctx, NAE_ERR_INVALID, "mod: non-finite parameter");
+    if (!(fabs(p->feedback) <= NAE_MOD_MAX_FEEDBACK)) return nae_fail_opt(ctx, NAE_ERR_INVALID, "mod: |feedback| above 0.95");
+    if (p->depth < 0.0) return nae_fail_opt(ctx, NAE_ERR_INVALID, "mod: negative depth");
+    if (p->n_voices < 1) return nae_fail_opt(ctx, NAE_ERR_INVALID, "mod: n_voices below 1");
+    if (p->shape != NAE_MOD_SINE && p->shape != NAE_MOD_TRIANGLE) return nae_fail_opt(ctx, NAE_ERR_INVALID, "mod: unknown shape");
+    if (p->n_voices > NAE_MOD_MAX_VOICES) return nae_fail_opt(ctx, NAE_ERR_UNSUPPORTED, "mod: at most 4 voices");
     if (!(p->delay - p->depth >= NAE_MOD_MIN_DELAY) || !(p->delay + p->depth <= NAE_MOD_MAX_DELAY))
-        return fail(NAE_ERR_UNSUPPORTED, "mod: delay - depth must be at least 2 and delay + depth at most 3070 samples");
+        return nae_fail_opt(ctx, NAE_ERR_UNSUPPORTED, "mod: delay - depth must be at least 2 and delay + depth at most 3070 samples");
     return NAE_OK;
 }
 
@@ -200,7 +199,7 @@ int nae_mod_block_f32(nae_ctx* ctx, const nae_mod_params* params, const nae_sig*
     if (rc) return rc;
     if (in_len == 0 || n_streams == 0) return NAE_OK;
     if (!src->base || !dst->base) return nae_fail(ctx, NAE_ERR_INVALID, "mod: null pointer");
-    return nae_launch_mod(ctx, params, src, in_len, ch, n_streams, dst, 0, (in_len + kEqC - 1) / kEqC, nullptr);
+    return nae_launch_mod(ctx, params, src, in_len, ch, n_streams, dst, 0, nae_chunks(in_len), nullptr);
 }
 
 // DESIGN.md §3, "K17 modulated delay", "Design"

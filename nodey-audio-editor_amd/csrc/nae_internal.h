@@ -110,6 +110,8 @@ struct nae_event { hipEvent_t ev; };
 
 int nae_check(nae_ctx* ctx, hipError_t e, const char* what);
 int nae_fail(nae_ctx* ctx, int code, const char* what);
+// the nae_*_check functions' failure: ctx may be null (a caller that wants the code alone), no message then
+inline int nae_fail_opt(nae_ctx* ctx, int code, const char* what) { return ctx ? nae_fail(ctx, code, what) : code; }
 int nae_ws_reserve(nae_ctx* ctx, void** p, size_t* have, size_t want);
 
 // kernels_spectrum.hip: every supported size and hop (arguments checked by the caller); picks the kernel
