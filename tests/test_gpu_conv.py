@@ -10,7 +10,8 @@ import pytest
 
 import conv_ref
 import node_harness
-from block_gpu import CONFIGS, bits, flushed, noise, statement, stream, view_call
+from block_gpu import CONFIGS, bits, noise, statement
+from conv_gpu import conv_stream, gpu_conv
 from fir_gpu import gpu_fir
 
 pytestmark = pytest.mark.gpu
@@ -19,11 +20,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def ref():
     return statement(conv_ref)
-
-
-def gpu_conv(nae, ctx, taps, n_fft, x, *views, **kw):
-    """x[streams, n, ch] -> y[streams, n, ch] through nae_conv_block_f32 in a view of block_gpu.view_call's"""
-    return view_call(nae, ctx, lambda src, n, ch, n_streams, dst: ctx.conv_block(taps, src, n, ch, n_streams, dst, n_fft), x, *views, **kw)
 
 
 def _taps(rng, L, taps_ch=1):
@@ -126,18 +122,6 @@ def test_a_nan_reaches_p_plus_one_blocks(nae, ctx, ref):
     assert np.array_equal(bits(got[0, :b * B]), bits(clean[0, :b * B]))
     assert np.array_equal(bits(got[0, (b + P + 1) * B:]), bits(clean[0, (b + P + 1) * B:]))
     assert not np.isfinite(got[0, b * B:(b + 1) * B]).any()
-
-
-def conv_stream(nae, ctx, taps, n_fft, x, puts, device=False):
-    """x[n, ch] through a nae_conv handle by block_gpu.stream, received into device memory when the puts come from it"""
-    n, ch = x.shape
-    h = nae.Conv(ctx, taps, ch, n_fft)
-    d_y = ctx.empty((n + taps.shape[-1]) * ch) if device else None
-    try:
-        return stream(h, ctx, x, puts, device, after_flush=flushed(h, n + taps.shape[-1] - 1), d_out=d_y)
-    finally:
-        if d_y is not None:
-            d_y.free()
 
 
 @pytest.mark.parametrize("device", (False, True))

@@ -1,5 +1,5 @@
 """GPU: a seeded, bounded subset of the randomised differential runs of tests/tools/fuzz_*.py (vocoder + spectrum, the
-SoundTouch-shaped chain, the N2 converter, the FIR filter) against the CPU oracle and statements.  The full runs (python tests/tools/fuzz_X.py CASES SEED)
+SoundTouch-shaped chain, the N2 converter, the FIR filter, the effect nodes K10 ... K17) against the CPU oracle and statements.  The full runs (python tests/tools/fuzz_X.py CASES SEED)
 draw more cases from the same generators; these fixed seeds keep the driver's `-m gpu` run to a few seconds per test."""
 import os
 import sys
@@ -45,3 +45,12 @@ def test_fuzz_swr_seeded(nae, ctx):
 def test_fuzz_fir_seeded(nae, ctx):
     import fuzz_fir
     assert fuzz_fir.main(cases=36, seed=3, ctx=ctx, nae=nae) == 36     # block call and handle bit-exact in every case drawn
+
+
+@pytest.mark.parametrize("node", ("conv", "eq", "dyn", "dynkey", "denoise", "loud", "echo", "mod"))
+def test_fuzz_effects_seeded(nae, ctx, node):
+    """block entry and handle of every effect node bit-exact in every case drawn: parameters over the header's whole ranges, edge lengths, views,
+    debug keys and put patterns (tests/test_fuzz_effects_cpu.py pins which edges these seeds reach)"""
+    import fuzz_effects
+    cases, seed = fuzz_effects.SEEDED[node]
+    assert fuzz_effects.main(node, cases=cases, seed=seed, ctx=ctx, nae=nae) == cases

@@ -1,4 +1,4 @@
-"""One contract for the put / receive handles (nae_fir, nae_conv, nae_eq, nae_dyn, nae_denoise, nae_dynkey, nae_echo, nae_stretch), through the C
+"""One contract for the put / receive handles (nae_fir, nae_conv, nae_eq, nae_dyn, nae_denoise, nae_dynkey, nae_echo, nae_mod, nae_stretch), through the C
 entries: puts that cross a unit boundary and leave a partial last unit, receives in pieces into device and host memory, the state after the
 flush, and the output, bit for bit the block entry's on the whole input, in the length include/nae_gpu.h states.  For the FIR filter and the
 convolution the block entry runs on the input extended by n_taps - 1 zero frames: that is what the header says a flushed handle delivers."""
@@ -113,6 +113,15 @@ def echo_case(nae, ctx):
     return x, lambda h: lib.nae_echo_create(ctx.h, C.byref(params), 2, h), want, None
 
 
+def mod_case(nae, ctx):
+    """a flanger with feedback and two voices (runs of 16 samples); 3 * 4096 + 7 frames wrap the handle's ring three times"""
+    lib = ctx.lib
+    params = nae.ModParams.make(24.0, 7.0, 0.9, 0.6, 0.8, (1 << 32) // 997, 3, 1 << 30, (0, 1 << 31))
+    x = noise(11, 3 * 4096 + 7, 2)
+    want = block(nae, ctx, x, len(x), lambda s, n, ch, d: lib.nae_mod_block_f32(ctx.h, C.byref(params), s, n, ch, 1, d))
+    return x, lambda h: lib.nae_mod_create(ctx.h, C.byref(params), 2, h), want, None
+
+
 def stretch_case(nae, ctx):
     lib, x = ctx.lib, noise(6, 8192, 1)
     pitch = float(np.float32(2 ** (3 / 12)))   # the handle takes floats
@@ -122,9 +131,10 @@ def stretch_case(nae, ctx):
 
 
 CASES = {"fir": fir_case, "conv": conv_case, "eq": eq_case, "dyn": dyn_case, "denoise": denoise_case, "dynkey": dynkey_case, "echo": echo_case,
-         "stretch": stretch_case}
+         "mod": mod_case, "stretch": stretch_case}
 # the lengths the header states: in_len + n_taps - 1, in_len, the plan's out_len (stretch_case: `want` has it)
-OUT_LEN = {"fir": 3000 + 31 - 1, "conv": 3000 + 700 - 1, "eq": 2500, "dyn": 2500, "denoise": 3000, "dynkey": 2500, "echo": 3 * 3072 + 7}
+OUT_LEN = {"fir": 3000 + 31 - 1, "conv": 3000 + 700 - 1, "eq": 2500, "dyn": 2500, "denoise": 3000, "dynkey": 2500, "echo": 3 * 3072 + 7,
+           "mod": 3 * 4096 + 7}
 
 
 @pytest.mark.parametrize("prefix", CASES)
