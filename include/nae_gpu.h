@@ -406,6 +406,9 @@ int nae_wsola_plan_make(int sample_rate, int channels, double rate, double pitch
  * flush, receive-all).  offsets_dbg (device, optional): [n_streams][n_seq - 1] chosen overlap offsets. */
 int nae_wsola_block_f32(nae_ctx* ctx, int sample_rate, double rate, double pitch, const nae_sig* src, size_t in_len, int ch,
                         size_t n_streams, const nae_sig* dst, int32_t* offsets_dbg);
+/* streaming form: the calls and the argument rule of the other handles.  A null handle, a null `got`, or a null pointer with a non-zero
+ * count: NAE_ERR_INVALID whatever the handle's state; a put after the flush: NAE_ERR_STATE.  What comes out follows the put sequence (every
+ * put runs the chain on what has arrived, and the flush counts from the frames received so far), as SoundTouch's does. */
 int nae_wsola_create(nae_ctx* ctx, int sample_rate, int channels, double rate, double pitch, nae_wsola** h);
 int nae_wsola_put(nae_wsola* h, const float* interleaved, size_t S);
 int nae_wsola_put_host(nae_wsola* h, const float* interleaved_host, size_t S);

@@ -4,7 +4,8 @@
 // audio-velocity.cpp:369-428): putSamples / numSamples / receiveSamples / flush.
 //
 // Every handle stands on stream_util.h's core (StreamHandle / BlockHandle): put, flush, available, receive and destroy are written there
-// once.  A handle adds its own fields, its create entry and process(), the step that computes what became computable.
+// once.  A handle adds its own fields, its create entry and process(), the step that computes what became computable.  nae_wsola
+// (nae_wsola.hip) and nae_swr (nae_swr.hip) stand on the same core beside their own host code.
 #include "nae_internal.h"
 #include <stdio.h>
 #include <stdlib.h>

@@ -15,7 +15,6 @@
 // template does: even and odd taps in two float accumulators, in increasing order, no fused multiply-add.
 #include "stream_util.h"
 #include <math.h>
-#include <new>
 #include <string.h>
 
 namespace {
@@ -187,16 +186,21 @@ __global__ __launch_bounds__(kSwrTile) void swr_resample_kernel(SwrKernelArgs a)
 
 } // namespace
 
-struct nae_swr {
-    nae_ctx* ctx;
+// On stream_util.h's handle core for what a handle is and how it is made and released; `in` and `out` hold interleaved stereo f32 frames
+// whatever the input's channel count, and `flushed` is the drain.  The convert entries feed and empty the FIFOs themselves.
+struct nae_swr : StreamHandle {
     int in_fmt, in_rate, in_ch, out_rate;
     bool identity;
     SwrPlan pl{};
     float* d_bank = nullptr;
-    DevFifo in, out;           // interleaved stereo f32 frames
-    size_t n_read = 0;
     DevBuf raw, f32, planes;   // staging of one convert call
-    bool flushed = false;
+    int process() override;      // the outputs that became computable; equal rates: a wire, nothing to compute
+    ~nae_swr() override
+    {
+        devbuf_free(raw);
+        devbuf_free(f32);
+        devbuf_free(planes);
+    }
 };
 
 static int swr_run(nae_swr* h)
@@ -233,6 +237,8 @@ static int swr_run(nae_swr* h)
     return NAE_OK;
 }
 
+int nae_swr::process() { return identity ? NAE_OK : swr_run(this); }
+
 extern "C" {
 
 int nae_swr_create(nae_ctx* ctx, int in_fmt, int in_rate, int in_channels, int out_rate, nae_swr** h)
@@ -246,25 +252,25 @@ int nae_swr_create(nae_ctx* ctx, int in_fmt, int in_rate, int in_channels, int o
     }
     if (in_channels != 1 && in_channels != 2) return nae_fail(ctx, NAE_ERR_INVALID, "channel count must be 1 or 2");
     if (in_rate <= 0 || out_rate <= 0) return nae_fail(ctx, NAE_ERR_INVALID, "sample rates must be positive");
-    nae_swr* s = new (std::nothrow) nae_swr();
+    const bool identity = in_rate == out_rate;
+    SwrPlan pl{};
+    int rc = identity ? NAE_OK : swr_plan_make(in_rate, out_rate, &pl);
+    if (rc) return nae_fail(ctx, rc, "sample-rate ratio outside the supported range (at most ~15x down, reducible to 30-bit increments)");
+    nae_swr* s = handle_new<nae_swr>(ctx, 2);        // the FIFOs' frames are stereo whatever in_channels is
     if (!s) return NAE_ERR_NOMEM;
-    s->ctx = ctx; s->in_fmt = in_fmt; s->in_rate = in_rate; s->in_ch = in_channels; s->out_rate = out_rate;
-    s->identity = in_rate == out_rate;
-    s->in.width = s->out.width = 2;
-    if (!s->identity) {
-        int rc = swr_plan_make(in_rate, out_rate, &s->pl);
-        if (rc) { delete s; return nae_fail(ctx, rc, "sample-rate ratio outside the supported range (at most ~15x down, reducible to 30-bit increments)"); }
+    s->in_fmt = in_fmt; s->in_rate = in_rate; s->in_ch = in_channels; s->out_rate = out_rate;
+    s->identity = identity;
+    s->pl = pl;
+    if (!identity) {
         std::vector<float> bank;
-        swr_build_filter(s->pl, bank);
-        hipError_t e = hipMalloc((void**)&s->d_bank, bank.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(s->d_bank, bank.data(), bank.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { if (s->d_bank) (void)hipFree(s->d_bank); delete s; return nae_check(ctx, e, "filter bank upload"); }
+        swr_build_filter(pl, bank);
+        rc = s->dev_alloc(&s->d_bank, bank.size(), "hipMalloc(filter bank)");
+        if (!rc) rc = nae_check(ctx, hipMemcpy(s->d_bank, bank.data(), bank.size() * sizeof(float), hipMemcpyHostToDevice), "filter bank upload");
     }
-    *h = s;
-    return NAE_OK;
+    return handle_created(s, rc, h);
 }
 
-size_t nae_swr_buffered(nae_swr* h) { return h ? h->out.total - h->n_read : 0; }
+size_t nae_swr_buffered(nae_swr* h) { return handle_available(h); }
 
 /* upload + format conversion of one call's input, appended to the input FIFO (or, equal rates, straight to the output
  * FIFO: a wire); queued on the stream, nothing waited for */
@@ -305,15 +311,15 @@ static int swr_feed(nae_swr* h, const void* const* planes, size_t n_in)
 static int swr_emit(nae_swr* h, float* dL, float* dR, size_t max_out, size_t* n_out)
 {
     nae_ctx* ctx = h->ctx;
-    size_t n = h->out.total - h->n_read;
+    size_t n = h->out.total - h->out_read;
     if (n > max_out) n = max_out;
     *n_out = n;
     if (n == 0) return NAE_OK;
     float* planes_out[2] = {dL, dR};
-    int rc = nae_deinterleave_f32(ctx, h->out.at(h->n_read), planes_out, n, 2);
+    int rc = nae_deinterleave_f32(ctx, h->out.at(h->out_read), planes_out, n, 2);
     if (rc) return rc;
-    h->n_read += n;
-    h->out.drop((long long)h->n_read);
+    h->out_read += n;
+    h->out.drop((long long)h->out_read);
     return NAE_OK;
 }
 
@@ -325,7 +331,7 @@ static int swr_convert_common(nae_swr* h, const void* const* planes, size_t n_in
     } else if (!planes) {
         h->flushed = true;
     }
-    return h->identity ? NAE_OK : swr_run(h);
+    return h->process();
 }
 
 /* swr_convert(ctx, out, max_out, in, n_in): consumes all n_in frames, delivers at most max_out, keeps the rest; planes == NULL
@@ -338,7 +344,7 @@ int nae_swr_convert_host(nae_swr* h, const void* const* planes, size_t n_in, flo
     *n_out = 0;
     int rc;
     if ((rc = swr_convert_common(h, planes, n_in))) return rc;
-    size_t n = h->out.total - h->n_read;
+    size_t n = h->out.total - h->out_read;
     if (n > max_out) n = max_out;
     if (n == 0) {
         // the caller may reuse its planes
@@ -366,17 +372,6 @@ int nae_swr_convert(nae_swr* h, const void* const* planes, size_t n_in, float* o
     return swr_emit(h, outL, outR, max_out, n_out);
 }
 
-int nae_swr_destroy(nae_swr* h)
-{
-    if (!h) return NAE_OK;
-    (void)nae_use_device(h->ctx);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    h->in.free();
-    h->out.free();
-    devbuf_free(h->raw); devbuf_free(h->f32); devbuf_free(h->planes);
-    if (h->d_bank) (void)hipFree(h->d_bank);
-    delete h;
-    return NAE_OK;
-}
+int nae_swr_destroy(nae_swr* h) { return handle_destroy(h); }
 
 } // extern "C"

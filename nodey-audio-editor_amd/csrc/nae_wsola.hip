@@ -1,5 +1,6 @@
 // nae_wsola.hip — host side of K7 option A (SoundTouch-shaped WSOLA chain): parameters, the scalar bookkeeping of
-// st_chain.h, the block entry point and the streaming handle.  Device work is in kernels_wsola.hip.
+// st_chain.h, the block entry point and the streaming handle (nae_wsola, on stream_util.h's handle core).  Device work is in
+// kernels_wsola.hip.
 //
 // Replaces soundtouch::SoundTouch as used by /root/reference/src/processor/audio-velocity.cpp:369-428.
 #include "st_chain.h"
@@ -180,6 +181,52 @@ static int upload_cu(nae_ctx* ctx, const CuTable& tab, size_t first, size_t coun
 
 using namespace nae;
 
+// A grow-only device table; a grow does not keep the contents.  It waits for the stream (the old table may still be in use), frees, then
+// allocates, so a failed grow leaves an empty table behind and never a stale pointer.  One growth rule for every user: half as much again.
+template <class T>
+struct DevTab {
+    T* p = nullptr;
+    size_t cap = 0;                 // elements
+
+    int reserve(nae_ctx* ctx, size_t want, const char* what)
+    {
+        if (want <= cap) return NAE_OK;
+        (void)hipStreamSynchronize(ctx->stream);
+        free();
+        const size_t ncap = want + want / 2 + 1024;
+        T* np = nullptr;
+        if (hipMalloc((void**)&np, ncap * sizeof(T)) != hipSuccess) return nae_fail(ctx, NAE_ERR_NOMEM, what);
+        p = np;
+        cap = ncap;
+        return NAE_OK;
+    }
+
+    void free()
+    {
+        if (p) (void)hipFree(p);
+        *this = DevTab{};
+    }
+};
+
+// the cubic stage's table on the device: the source position and the fraction of every output (CuTable's two columns).  Each column knows its
+// own capacity, so a grow that fails at the second one leaves nothing to put right
+struct CuDevTable {
+    DevTab<long long> pos;
+    DevTab<float> fract;
+
+    int reserve(nae_ctx* ctx, size_t want)
+    {
+        const int rc = pos.reserve(ctx, want, "hipMalloc(cubic table)");
+        return rc ? rc : fract.reserve(ctx, want, "hipMalloc(cubic table)");
+    }
+
+    void free()
+    {
+        pos.free();
+        fract.free();
+    }
+};
+
 // plan cache of the block entry point (one entry: the bench and batch jobs repeat one parameter set)
 struct nae_wsola_cache {
     bool valid = false;
@@ -189,11 +236,9 @@ struct nae_wsola_cache {
     StCfg cfg;
     StState fin;
     long long out_len = 0;
-    long long* d_pos = nullptr;
-    float* d_fract = nullptr;
-    size_t tab_cap = 0;
-    int* d_tile_n = nullptr;        // first cubic output of every fused filter+cubic tile (orders 0 and 1)
-    size_t tile_cap = 0, n_tiles = 0;
+    CuDevTable tab;
+    DevTab<int> tile_n;             // first cubic output of every fused filter+cubic tile (orders 0 and 1)
+    size_t n_tiles = 0;
     void* ws_a = nullptr; size_t ws_a_bytes = 0;
     void* ws_b = nullptr; size_t ws_b_bytes = 0;
 };
@@ -208,9 +253,8 @@ void nae_wsola_cache_free(nae_ctx* ctx)
 {
     nae_wsola_cache* c = ctx->wsola_cache;
     if (!c) return;
-    if (c->d_pos) (void)hipFree(c->d_pos);
-    if (c->d_fract) (void)hipFree(c->d_fract);
-    if (c->d_tile_n) (void)hipFree(c->d_tile_n);
+    c->tab.free();
+    c->tile_n.free();
     if (c->ws_a) (void)hipFree(c->ws_a);
     if (c->ws_b) (void)hipFree(c->ws_b);
     delete c;
@@ -273,34 +317,18 @@ int nae_wsola_block_f32(nae_ctx* ctx, int sample_rate, double rate, double pitch
         st_sim_put(wc->cfg, s, (long long)in_len, &tab);
         wc->out_len = sim_flush(wc->cfg, s, 0, &tab, nullptr);
         wc->fin = s;
-        if (tab.pos.size() > wc->tab_cap) {
-            (void)hipStreamSynchronize(ctx->stream);
-            if (wc->d_pos) (void)hipFree(wc->d_pos);
-            if (wc->d_fract) (void)hipFree(wc->d_fract);
-            wc->d_pos = nullptr; wc->d_fract = nullptr; wc->tab_cap = 0;
-            const size_t cap = tab.pos.size() + tab.pos.size() / 8 + 1024;
-            if (hipMalloc((void**)&wc->d_pos, cap * sizeof(long long)) != hipSuccess ||
-                hipMalloc((void**)&wc->d_fract, cap * sizeof(float)) != hipSuccess)
-                return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(cubic table)");
-            wc->tab_cap = cap;
-        }
-        rc = upload_cu(ctx, tab, 0, tab.pos.size(), wc->d_pos, wc->d_fract);
+        rc = wc->tab.reserve(ctx, tab.pos.size());
+        if (!rc) rc = upload_cu(ctx, tab, 0, tab.pos.size(), wc->tab.pos.p, wc->tab.fract.p);
         if (rc) return rc;
         wc->n_tiles = 0;
         if (wc->cfg.order != 2) {
             // filter and cubic stage are adjacent: they run as one launch, tile by tile
             std::vector<int> tile_n;
             st_tile_starts(tab, wc->cfg.order == 0 ? wc->out_len : s.cu_out, tile_n);
-            if (tile_n.size() > wc->tile_cap) {
-                (void)hipStreamSynchronize(ctx->stream);
-                if (wc->d_tile_n) (void)hipFree(wc->d_tile_n);
-                wc->d_tile_n = nullptr; wc->tile_cap = 0;
-                const size_t cap = tile_n.size() + tile_n.size() / 8 + 64;
-                if (hipMalloc((void**)&wc->d_tile_n, cap * sizeof(int)) != hipSuccess) return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(tile table)");
-                wc->tile_cap = cap;
-            }
+            rc = wc->tile_n.reserve(ctx, tile_n.size(), "hipMalloc(tile table)");
+            if (rc) return rc;
             if (!tile_n.empty()) {
-                hipError_t e = hipMemcpyAsync(wc->d_tile_n, tile_n.data(), tile_n.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+                hipError_t e = hipMemcpyAsync(wc->tile_n.p, tile_n.data(), tile_n.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
                 if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(tile table)");
                 wc->n_tiles = tile_n.size() - 1;
@@ -334,30 +362,32 @@ int nae_wsola_block_f32(nae_ctx* ctx, int sample_rate, double rate, double pitch
     const StOut o_dst{(float*)dst->base, (long long)dst->stream_stride, (long long)dst->chan_stride, (long long)dst->frame_stride, 0};
     const TdRange all{0, 0, fin.td_nseq, 0.0, 1, cfg.order == 0 ? (long long)len1 : wc->out_len};
     const long long n_offs = fin.td_nseq > 0 ? fin.td_nseq - 1 : 0;
+    const long long* d_pos = wc->tab.pos.p;
+    const float* d_fract = wc->tab.fract.p;
     switch (cfg.order) {
     case 0:
         rc = st_launch_td(ctx, cfg, v_src, all, o_a, n_streams, nullptr, offsets_dbg, n_offs);
         if (!rc && !ctx->dbg_st_unfused)
-            rc = st_launch_aa_cu(ctx, cfg, v_a, wc->d_pos, wc->d_fract, wc->d_tile_n, wc->n_tiles, wc->out_len, o_dst, n_streams);
+            rc = st_launch_aa_cu(ctx, cfg, v_a, d_pos, d_fract, wc->tile_n.p, wc->n_tiles, wc->out_len, o_dst, n_streams);
         else {
             if (!rc) rc = st_launch_aa(ctx, cfg, v_a, 0, fin.aa_out, o_b, n_streams);
-            if (!rc) rc = st_launch_cu(ctx, cfg, v_b, wc->d_pos, wc->d_fract, 0, 0, wc->out_len, o_dst, n_streams);
+            if (!rc) rc = st_launch_cu(ctx, cfg, v_b, d_pos, d_fract, 0, 0, wc->out_len, o_dst, n_streams);
         }
         break;
     case 1:
         if (!ctx->dbg_st_unfused)
-            rc = st_launch_aa_cu(ctx, cfg, v_src, wc->d_pos, wc->d_fract, wc->d_tile_n, wc->n_tiles, fin.cu_out, o_b, n_streams);
+            rc = st_launch_aa_cu(ctx, cfg, v_src, d_pos, d_fract, wc->tile_n.p, wc->n_tiles, fin.cu_out, o_b, n_streams);
         else {
             rc = st_launch_aa(ctx, cfg, v_src, 0, fin.aa_out, o_a, n_streams);
-            if (!rc) rc = st_launch_cu(ctx, cfg, v_a, wc->d_pos, wc->d_fract, 0, 0, fin.cu_out, o_b, n_streams);
+            if (!rc) rc = st_launch_cu(ctx, cfg, v_a, d_pos, d_fract, 0, 0, fin.cu_out, o_b, n_streams);
         }
         if (!rc) rc = st_launch_td(ctx, cfg, v_b, all, o_dst, n_streams, nullptr, offsets_dbg, n_offs);
         break;
     default:
         if (!ctx->dbg_st_unfused)
-            rc = st_launch_cu_aa(ctx, cfg, v_src, wc->d_pos, wc->d_fract, fin.cu_out, fin.aa_out, o_b, n_streams);
+            rc = st_launch_cu_aa(ctx, cfg, v_src, d_pos, d_fract, fin.cu_out, fin.aa_out, o_b, n_streams);
         else {
-            rc = st_launch_cu(ctx, cfg, v_src, wc->d_pos, wc->d_fract, 0, 0, fin.cu_out, o_a, n_streams);
+            rc = st_launch_cu(ctx, cfg, v_src, d_pos, d_fract, 0, 0, fin.cu_out, o_a, n_streams);
             if (!rc) rc = st_launch_aa(ctx, cfg, v_a, 0, fin.aa_out, o_b, n_streams);
         }
         if (!rc) rc = st_launch_td(ctx, cfg, v_b, all, o_dst, n_streams, nullptr, offsets_dbg, n_offs);
@@ -371,19 +401,22 @@ int nae_wsola_block_f32(nae_ctx* ctx, int sample_rate, double rate, double pitch
 // ------------------------------------------------------------------ streaming handle
 // SoundTouch-shaped calls (audio-velocity.cpp:403 putSamples, :399 numSamples, :298 receiveSamples, :427 flush) on
 // one stream.  Every put advances the scalar bookkeeping, then each stage is launched once for the index range
-// that became computable; the FIFOs between the stages are addressed by absolute frame index.
-struct nae_wsola {
-    nae_ctx* ctx = nullptr;
+// that became computable; the FIFOs between the stages are addressed by absolute frame index.  The handle stands on stream_util.h's core:
+// `in` holds the frames really put (the flush's zeros are virtual), and put, flush, available, receive and destroy are the core's.
+struct nae_wsola : StreamHandle {
     StCfg cfg;
     StState st;                  // everything up to this state has been computed on the device
-    long long* d_pos = nullptr;
-    float* d_fract = nullptr;
-    size_t tab_cap = 0;
-    DevFifo in, a, b, out;       // input (frames really put: flush zeros are virtual), stage 1 -> 2, stage 2 -> 3, result
+    size_t fed = 0;              // frames of `in` that `st` has seen
+    CuDevTable tab;              // the cubic outputs of one step
+    DevFifo a, b;                // stage 1 -> 2, stage 2 -> 3
     float* d_mid = nullptr;      // stretcher tail carried between calls
-    long long received = 0;
-    long long out_limit = -1;    // total frames that may ever be handed out once flushed
-    bool flushed = false;
+    int process() override;
+    ~nae_wsola() override
+    {
+        a.free();
+        b.free();
+        tab.free();
+    }
 };
 
 namespace {
@@ -398,18 +431,8 @@ int wsola_run(nae_wsola* h, const StState& before)
     // so a put never blocks)
     const long long cu_new = now.cu_out - before.cu_out;
     if (cu_new > 0) {
-        if ((size_t)cu_new > h->tab_cap) {
-            (void)hipStreamSynchronize(ctx->stream);     // growth only: the old table may still be in use
-            if (h->d_pos) (void)hipFree(h->d_pos);
-            if (h->d_fract) (void)hipFree(h->d_fract);
-            h->d_pos = nullptr; h->d_fract = nullptr; h->tab_cap = 0;
-            const size_t cap = (size_t)cu_new * 2 + 4096;
-            if (hipMalloc((void**)&h->d_pos, cap * sizeof(long long)) != hipSuccess ||
-                hipMalloc((void**)&h->d_fract, cap * sizeof(float)) != hipSuccess)
-                return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(cubic table)");
-            h->tab_cap = cap;
-        }
-        rc = st_launch_cu_table(ctx, before.cu_pos, before.cu_fract, c.rate, cu_new, h->d_pos, h->d_fract);
+        rc = h->tab.reserve(ctx, (size_t)cu_new);
+        if (!rc) rc = st_launch_cu_table(ctx, before.cu_pos, before.cu_fract, c.rate, cu_new, h->tab.pos.p, h->tab.fract.p);
         if (rc) return rc;
     }
     DevFifo* chain[4] = {&h->in, &h->a, &h->b, &h->out};
@@ -433,7 +456,7 @@ int wsola_run(nae_wsola* h, const StState& before)
             } else if (kind == 1) {
                 rc = st_launch_aa(ctx, c, vin, out_before, out_now, vout, 1);
             } else {
-                rc = st_launch_cu(ctx, c, vin, h->d_pos, h->d_fract, before.cu_out, out_before, out_now, vout, 1);
+                rc = st_launch_cu(ctx, c, vin, h->tab.pos.p, h->tab.fract.p, before.cu_out, out_before, out_now, vout, 1);
             }
             if (rc) return rc;
             dst.total = (size_t)out_now;
@@ -447,104 +470,51 @@ int wsola_run(nae_wsola* h, const StState& before)
 
 } // namespace
 
+// the one step behind a put and the flush: the bookkeeping takes the frames that arrived, or the flush's zero puts, and the stages run
+int nae_wsola::process()
+{
+    const StState before = st;
+    long long release = 0;
+    if (flushed) {
+        release = sim_flush(cfg, st, (long long)out_read, nullptr, nullptr);
+    } else {
+        st_sim_put(cfg, st, (long long)(in.total - fed), nullptr);
+        fed = in.total;
+    }
+    const int rc = wsola_run(this, before);
+    if (rc) return rc;
+    // the flush releases `release` frames and no more; nothing runs after it, so cutting the FIFO's end short says so once and for all
+    if (flushed && out_read + (size_t)release < out.total) out.total = out_read + (size_t)release;
+    return NAE_OK;
+}
+
 extern "C" {
 
 int nae_wsola_create(nae_ctx* ctx, int sample_rate, int channels, double rate, double pitch, nae_wsola** out)
 {
-    if (!ctx) return NAE_ERR_INVALID;
+    if (!ctx || !out) return NAE_ERR_INVALID;
+    *out = nullptr;
     (void)nae_use_device(ctx);
-    if (!out) return nae_fail(ctx, NAE_ERR_INVALID, "nae_wsola_create: null handle pointer");
-    nae_wsola* h = new (std::nothrow) nae_wsola();
-    if (!h) return nae_fail(ctx, NAE_ERR_NOMEM, "nae_wsola_create");
-    h->ctx = ctx;
-    const int rc = st_cfg_make(h->cfg, sample_rate, channels, rate, pitch);
-    if (rc) {
-        delete h;
+    StCfg cfg;
+    int rc = st_cfg_make(cfg, sample_rate, channels, rate, pitch);
+    if (rc)
         return nae_fail(ctx, rc, rc == NAE_ERR_UNSUPPORTED ? "nae_wsola_create: sample rate outside 8000..48000 Hz or ratio out of range"
                                                            : "nae_wsola_create: bad parameters");
-    }
-    h->in.width = h->a.width = h->b.width = h->out.width = (size_t)channels;
-    if (hipMalloc((void**)&h->d_mid, (size_t)h->cfg.ovl * (size_t)channels * sizeof(float)) != hipSuccess) {
-        delete h;
-        return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(stretcher tail)");
-    }
-    *out = h;
-    return NAE_OK;
+    nae_wsola* h = handle_new<nae_wsola>(ctx, channels);
+    if (!h) return NAE_ERR_NOMEM;
+    h->cfg = cfg;
+    h->a.width = h->b.width = (size_t)channels;
+    rc = h->dev_alloc(&h->d_mid, (size_t)cfg.ovl * (size_t)channels, "hipMalloc(stretcher tail)");
+    return handle_created(h, rc, out);
 }
 
-static int wsola_append(nae_wsola* h, const float* p, size_t S, bool host)
-{
-    if (!h) return NAE_ERR_INVALID;
-    (void)nae_use_device(h->ctx);
-    nae_ctx* ctx = h->ctx;
-    if (h->flushed) return nae_fail(ctx, NAE_ERR_STATE, "nae_wsola_put after flush");
-    if (S == 0) return NAE_OK;
-    if (!p) return nae_fail(ctx, NAE_ERR_INVALID, "nae_wsola_put: null samples");
-    const int rc = h->in.push(ctx, p, S, host);
-    if (rc) return rc;
-    const StState before = h->st;
-    st_sim_put(h->cfg, h->st, (long long)S, nullptr);
-    return wsola_run(h, before);
-}
-
-int nae_wsola_put(nae_wsola* h, const float* interleaved, size_t S) { return wsola_append(h, interleaved, S, false); }
-int nae_wsola_put_host(nae_wsola* h, const float* interleaved, size_t S) { return wsola_append(h, interleaved, S, true); }
-
-int nae_wsola_flush(nae_wsola* h)
-{
-    if (!h) return NAE_ERR_INVALID;
-    (void)nae_use_device(h->ctx);
-    if (h->flushed) return NAE_OK;
-    const StState before = h->st;
-    const long long avail = sim_flush(h->cfg, h->st, h->received, nullptr, nullptr);
-    const int rc = wsola_run(h, before);
-    if (rc) return rc;
-    h->out_limit = h->received + avail;
-    h->flushed = true;
-    return NAE_OK;
-}
-
-size_t nae_wsola_available(const nae_wsola* h)
-{
-    if (!h) return 0;
-    long long total = (long long)h->out.total;
-    if (h->out_limit >= 0 && total > h->out_limit) total = h->out_limit;
-    return total > h->received ? (size_t)(total - h->received) : 0;
-}
-
-static int wsola_take(nae_wsola* h, float* dst, size_t max_frames, size_t* got, bool host)
-{
-    if (!h) return NAE_ERR_INVALID;
-    (void)nae_use_device(h->ctx);
-    nae_ctx* ctx = h->ctx;
-    size_t n = nae_wsola_available(h);
-    if (n > max_frames) n = max_frames;
-    if (got) *got = n;
-    if (n == 0) return NAE_OK;
-    if (!dst) return nae_fail(ctx, NAE_ERR_INVALID, "nae_wsola_receive: null destination");
-    const int rc = h->out.pop(ctx, (size_t)h->received, dst, n, host);
-    if (rc) return rc;
-    h->received += (long long)n;
-    return NAE_OK;
-}
-
-int nae_wsola_receive(nae_wsola* h, float* dst, size_t max_frames, size_t* got) { return wsola_take(h, dst, max_frames, got, false); }
-int nae_wsola_receive_host(nae_wsola* h, float* dst, size_t max_frames, size_t* got) { return wsola_take(h, dst, max_frames, got, true); }
-
-int nae_wsola_destroy(nae_wsola* h)
-{
-    if (!h) return NAE_OK;
-    if (h->ctx) (void)nae_use_device(h->ctx);
-    if (h->ctx && h->ctx->stream) (void)hipStreamSynchronize(h->ctx->stream);
-    h->in.free();
-    h->a.free();
-    h->b.free();
-    h->out.free();
-    if (h->d_mid) (void)hipFree(h->d_mid);
-    if (h->d_pos) (void)hipFree(h->d_pos);
-    if (h->d_fract) (void)hipFree(h->d_fract);
-    delete h;
-    return NAE_OK;
-}
+int nae_wsola_put(nae_wsola* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_wsola_put_host(nae_wsola* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+// flush: the zero puts of SoundTouch::flush (sim_flush); what it releases is counted from the frames received so far
+int nae_wsola_flush(nae_wsola* h) { return handle_flush(h); }
+size_t nae_wsola_available(const nae_wsola* h) { return handle_available(h); }
+int nae_wsola_receive(nae_wsola* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_wsola_receive_host(nae_wsola* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_wsola_destroy(nae_wsola* h) { return handle_destroy(h); }
 
 } // extern "C"

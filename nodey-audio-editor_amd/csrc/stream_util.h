@@ -1,5 +1,7 @@
 // stream_util.h — grow-only device buffers, the absolutely indexed device FIFO of the streaming handles, and the handles' shared core: what
-// a handle is (StreamHandle, BlockHandle) and its put / flush / available / receive / destroy (not installed)
+// a handle is (StreamHandle, BlockHandle) and its put / flush / available / receive / destroy (not installed).  Every handle of the library
+// stands on it: the eleven of nae_stream.hip, nae_wsola (nae_wsola.hip) and nae_swr (nae_swr.hip, whose convert entries feed and empty the
+// FIFOs themselves)
 #pragma once
 #include "nae_internal.h"
 #include <new>
@@ -146,7 +148,7 @@ struct StreamHandle {
     size_t out_read = 0;
     size_t flush_tail = 0;       // zero frames the flush appends behind the input (the tail of an FIR)
     bool flushed = false;
-    void* owned[4] = {};         // device allocations made by dev_alloc(): at most this many per handle (today's most is two)
+    void* owned[3] = {};         // device allocations made by dev_alloc(): at most this many per handle (nae_dynkey, nae_echo and nae_loud make three)
     int n_owned = 0;
 
     virtual int process() = 0;

@@ -1,7 +1,10 @@
-"""One contract for the put / receive handles (nae_fir, nae_conv, nae_eq, nae_dyn, nae_denoise, nae_dynkey, nae_echo, nae_mod, nae_stretch), through the C
-entries: puts that cross a unit boundary and leave a partial last unit, receives in pieces into device and host memory, the state after the
-flush, and the output, bit for bit the block entry's on the whole input, in the length include/nae_gpu.h states.  For the FIR filter and the
-convolution the block entry runs on the input extended by n_taps - 1 zero frames: that is what the header says a flushed handle delivers."""
+"""One contract for the put / receive handles (nae_fir, nae_conv, nae_eq, nae_dyn, nae_denoise, nae_dynkey, nae_echo, nae_mod, nae_stretch, nae_wsola),
+through the C entries: puts that cross a unit boundary and leave a partial last unit, receives in pieces into device and host memory, the state
+after the flush, and the output, bit for bit the block entry's on the whole input, in the length include/nae_gpu.h states.  For the FIR filter and
+the convolution the block entry runs on the input extended by n_taps - 1 zero frames: that is what the header says a flushed handle delivers.
+The WSOLA chain is the exception in what it is compared with: its output follows the put sequence (every put runs the stretcher on what has
+arrived, and the flush counts from what was received), so `want` is not the block entry's output but the CPU oracle's for the same puts,
+orc.st_process(..., chunk=the cuts), bit for bit and in length; there is no length the header could state and no look-ahead rule."""
 import ctypes as C
 import os
 import re
@@ -9,11 +12,14 @@ import re
 import numpy as np
 import pytest
 
+import orc
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, INVALID, STATE = 0, -1, -5                 # enum nae_status (include/nae_gpu.h)
 CUTS = (1, 1023, 1025, 7)                      # then the rest: a unit boundary inside a put, single frames, a partial last unit
+WSOLA_CUTS = (1, 1023, 5000, 7)                # the 5000-frame put crosses the stretcher's first sample_req
 PIECE = 100                                    # max_frames of every receive
 
 
@@ -130,8 +136,21 @@ def stretch_case(nae, ctx):
     return x, lambda h: lib.nae_stretch_create(ctx.h, 48000, 1, 1.0, pitch, h), want, None
 
 
+def wsola_case(order, rate, pitch):
+    """48 kHz stereo, one case per stage order (0: stretcher, filter, transposer; 1: filter, transposer, stretcher; 2: transposer, filter,
+    stretcher)"""
+    def case(nae, ctx):
+        n = 20000
+        assert ctx.wsola_plan(48000, 2, rate, pitch, n).order == order
+        x = orc.fill_uniform(n * 2, 40 + order)
+        want = orc.st_process(x, 2, 48000, rate, pitch, chunk=list(WSOLA_CUTS) + [n - sum(WSOLA_CUTS)]).reshape(-1, 2)
+        return x.reshape(n, 2), lambda h: ctx.lib.nae_wsola_create(ctx.h, 48000, 2, rate, pitch, h), want, None
+    return case
+
+
 CASES = {"fir": fir_case, "conv": conv_case, "eq": eq_case, "dyn": dyn_case, "denoise": denoise_case, "dynkey": dynkey_case, "echo": echo_case,
-         "mod": mod_case, "stretch": stretch_case}
+         "mod": mod_case, "stretch": stretch_case,
+         "wsola0": wsola_case(0, 1.0, 2 ** (3 / 12)), "wsola1": wsola_case(1, 1.5, 1 / 1.5), "wsola2": wsola_case(2, 0.8, 1.0)}
 # the lengths the header states: in_len + n_taps - 1, in_len, the plan's out_len (stretch_case: `want` has it)
 OUT_LEN = {"fir": 3000 + 31 - 1, "conv": 3000 + 700 - 1, "eq": 2500, "dyn": 2500, "denoise": 3000, "dynkey": 2500, "echo": 3 * 3072 + 7,
            "mod": 3 * 4096 + 7}
@@ -144,7 +163,8 @@ def test_handle_contract(nae, ctx, prefix):
     n, ch = x.shape
     if prefix in OUT_LEN:
         assert len(want) == OUT_LEN[prefix]
-    entry = {name: getattr(lib, f"nae_{prefix}_{name}") for name in ("put", "put_host", "flush", "available", "receive", "receive_host", "destroy")}
+    family, cuts = (prefix[:-1], WSOLA_CUTS) if prefix.startswith("wsola") else (prefix, CUTS)
+    entry = {name: getattr(lib, f"nae_{family}_{name}") for name in ("put", "put_host", "flush", "available", "receive", "receive_host", "destroy")}
     h = C.c_void_p()
     assert create(C.byref(h)) == OK
     d_x, d_piece = ctx.array(x.reshape(-1)), ctx.empty(PIECE * ch)
@@ -182,7 +202,7 @@ def test_handle_contract(nae, ctx, prefix):
 
     try:
         pos, received = 0, 0
-        for k in CUTS + (n - sum(CUTS),):
+        for k in cuts + (n - sum(cuts),):
             assert put(pos, k) == OK
             pos += k
             if lookahead is not None:

@@ -330,6 +330,38 @@ def test_n2_input_conversion(ctx, nae):
     assert lib.nae_swr_create(ctx.h, nae.FMT_FLT, 48000, 6, 48000, C.byref(h)) == -1
 
 
+def test_n2_input_after_the_drain_is_refused(ctx, nae):
+    """after the drain call (planes = NULL) a convert with input answers NAE_ERR_STATE, through either entry, and what waits in the handle
+    stays as it is"""
+    import ctypes as C
+    lib = ctx.lib
+    n = 3000
+    x = orc.fill_uniform(2 * n, 73)
+    planes = (C.c_void_p * 1)(x.ctypes.data)
+    h, got = C.c_void_p(), C.c_size_t()
+    assert lib.nae_swr_create(ctx.h, nae.FMT_FLT, 44100, 2, 48000, C.byref(h)) == 0
+    L, R = np.zeros(4096, np.float32), np.zeros(4096, np.float32)
+    d = ctx.empty(2 * 4096)
+    try:
+        assert lib.nae_swr_convert_host(h, planes, n, L.ctypes.data, R.ctypes.data, 1000, C.byref(got)) == 0
+        assert got.value == 1000
+        assert lib.nae_swr_convert_host(h, None, 0, L.ctypes.data, R.ctypes.data, 1000, C.byref(got)) == 0       # the drain
+        assert got.value == 1000
+        waiting = lib.nae_swr_buffered(h)
+        assert waiting == orc.swr_resample(x[0::2].copy(), 44100, 48000).size - 2000, "the oracle's length for the whole input, less the two receives"
+        got.value = 77
+        assert lib.nae_swr_convert_host(h, planes, n, L.ctypes.data, R.ctypes.data, 1000, C.byref(got)) == -5    # NAE_ERR_STATE
+        assert got.value == 0 and lib.nae_swr_buffered(h) == waiting
+        got.value = 77
+        assert lib.nae_swr_convert(h, planes, n, d.ptr, d.ptr + 4 * 4096, 1000, C.byref(got)) == -5
+        assert got.value == 0 and lib.nae_swr_buffered(h) == waiting
+        assert lib.nae_swr_convert_host(h, None, 0, L.ctypes.data, R.ctypes.data, 4096, C.byref(got)) == 0
+        assert got.value == waiting and lib.nae_swr_buffered(h) == 0
+    finally:
+        assert lib.nae_swr_destroy(h) == 0
+        d.free()
+
+
 def swr_drive(ctx, nae, fmt, in_rate, ch, planes_of, n_total, chunks, max_out=4096, queued=False):
     """swr_convert-style driving of nae_swr: put the chunks (receiving at most max_out frames per call), then drain.
     queued: through nae_swr_convert — device planes, nothing waited for until every call has been queued"""

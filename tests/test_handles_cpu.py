@@ -47,8 +47,7 @@ def test_null_handle(nae, prefix):
 
 
 def test_create_with_a_null_handle_pointer(nae):
-    """The entries that look at the out-pointer before they touch the context or the device.  nae_wsola_create is left out: it selects the
-    context's device before it looks at the pointer, so a null pointer there needs a live context."""
+    """The entries that look at the out-pointer before they touch the context or the device."""
     lib = nae.load_library()
     taps, coef, params = (C.c_float * 3)(0, 1, 0), (C.c_double * 5)(1, 0, 0, 0, 0), nae.DynParams()
     assert lib.nae_stretch_create(None, 48000, 2, 1.0, 1.0, None) == INVALID
@@ -61,3 +60,5 @@ def test_create_with_a_null_handle_pointer(nae):
     assert lib.nae_conv_create(None, taps, 3, 1, 0, 2, None) == INVALID
     assert lib.nae_eq_create(None, coef, 1, 2, None) == INVALID
     assert lib.nae_dyn_create(None, C.byref(params), 2, None) == INVALID
+    assert lib.nae_wsola_create(None, 48000, 2, 1.0, 1.0, None) == INVALID
+    assert lib.nae_swr_create(None, nae.FMT_FLT, 44100, 2, 48000, None) == INVALID
