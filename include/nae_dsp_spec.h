@@ -84,6 +84,13 @@
 #define NAE_MOD_MAX_FEEDBACK 0.95
 #define NAE_MOD_SINE 0
 #define NAE_MOD_TRIANGLE 1
+/* K18 saturation ("K18 saturation"): a static curve run oversampled by M = 1, 2, 4 or NAE_SAT_MAX_OS.  The anti-alias prototype is
+ * nae_fir_design's Kaiser low-pass with 2 NAE_SAT_HALF M + 1 taps at cutoff 1 / M: NAE_SAT_HALF taps of the base rate to either side, once up
+ * and once down, so the latency is 2 NAE_SAT_HALF samples for every M > 1 */
+#define NAE_SAT_HALF 16
+#define NAE_SAT_MAX_OS 8
+#define NAE_SAT_SOFT 0
+#define NAE_SAT_HARD 1
 /* K13 spectral gate ("K13 spectral gate"): noise reduction on the STFT at N = 512 ... 4096 and hop N / 4: a per-bin decision
  * against a learned power profile, smoothed by an integer triangle over at most NAE_DENOISE_MAX_TIME frames and NAE_DENOISE_MAX_FREQ bins to
  * either side (a wider frequency triangle pulls a pure tone down: DESIGN.md gives the figure); a tile the library chooses has at least

@@ -53,7 +53,8 @@ extern "C" {
  *   loudness meter and normalizer, K14; nae_dynkey_block_f32 and the nae_dynkey handle (the same eight entries) with the record
  *   nae_dynkey_params: the keyed (side-chain) dynamics, K15; nae_echo_design, nae_echo_block_f32 and the nae_echo handle (the same eight
  *   entries) with the record nae_echo_params: the echo, K16; nae_mod_design, nae_mod_block_f32 and the nae_mod handle (the same eight
- *   entries) with the record nae_mod_params: the modulated delay (chorus, flanger, vibrato), K17. */
+ *   entries) with the record nae_mod_params: the modulated delay (chorus, flanger, vibrato), K17; nae_sat_latency, nae_sat_taps,
+ *   nae_sat_design, nae_sat_block_f32 and the nae_sat handle (the same eight entries) with the record nae_sat_params: the saturation, K18. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -82,6 +83,7 @@ typedef struct nae_dyn nae_dyn;
 typedef struct nae_dynkey nae_dynkey;
 typedef struct nae_echo nae_echo;
 typedef struct nae_mod nae_mod;
+typedef struct nae_sat nae_sat;
 typedef struct nae_denoise nae_denoise;
 typedef struct nae_loud nae_loud;
 
@@ -170,6 +172,8 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *                   gives the same bits
  *   mod_sub         samples one wave of the modulated delay computes in parallel, 1 ... 64 (0: 64 without feedback, else min(64, floor(delay -
  *                   depth) - 1)); a value above that rule's is cut down to it; every value gives the same bits
+ *   sat_tile        chunks (of NAE_EQ_CHUNK samples) one wave of the saturation walks (0: nae_pick_sat_tile, which cuts a small batch until the CUs
+ *                   are full); every tiling gives the same bits
  * The same assignments, comma separated, in the environment variable NAE_DEBUG ("pv_flow=2,pv_fps=4") are applied when a context is created
  * (for measuring a program that creates its contexts itself, e.g. bench.py); an unknown key there fails nae_ctx_create with NAE_ERR_INVALID. */
 int nae_debug_set(nae_ctx* ctx, const char* key, long long value);
@@ -766,6 +770,56 @@ int nae_mod_destroy(nae_mod* h);
  * 1 ... NAE_MOD_MAX_VOICES, spread outside [0, 1], an unknown shape.  No context, no device work. */
 int nae_mod_design(int sample_rate, double rate_hz, double delay_ms, double depth_ms, double feedback, int voices, double spread, int shape,
                    double wet, double dry, nae_mod_params* out);
+
+/* ------------------------------------------------------------------ K18 saturation (drive, soft and hard clipping)
+ * no reference code.  Spec ("K18 saturation"): a static curve run at M = oversample times the sample rate, M in {1, 2, 4, 8}, so that
+ * the harmonics it makes do not fold back into the audible band.  K = NAE_SAT_HALF = 16.
+ * Taps, M > 1: N = 2 K M + 1; hd[j] = nae_fir_design(kind 0, sample_rate 2 M, f_hi 1.0, n_taps N)[j] (Kaiser beta 8, cutoff 1 / M, unit sum, rounded
+ * once to f32); hu[j] = M hd[j] (exact).  No tap is skipped, whatever its value.
+ * Per stream-channel, n = 0 ... in_len - 1, x[i] = 0 for i < 0, every step one IEEE f32 operation in the order written, fma the fused one:
+ *   up     for p = 0 ... M - 1, m = M n + p:  a = hu[p] x[n];  for i = 1, 2, ... while p + i M <= 2 K M:  a = fma(hu[p + i M], x[n - i], a);  u[m] = a
+ *   shape  t = fma(g, u[m], b);  v[m] = f(t) - f(b);  v[m] = 0 for m < 0
+ *            NAE_SAT_SOFT: c = t > 3 ? 3 : (t < -3 ? -3 : t);  q = c c;  f = (c (27 + q)) / (27 + (9 q))          the Pade form of tanh
+ *            NAE_SAT_HARD: f = t > 1 ? 1 : (t < -1 ? -1 : t)
+ *   down   s = hd[0] v[M n];  for j = 1 ... 2 K M:  s = fma(hd[j], v[M n - j], s)
+ *   mix    y[n] = (dry x[n - D]) + (wet s),  D = 2 K = 32 the latency
+ * M = 1: no filter, D = 0: y[n] = (dry x[n]) + (wet (f(fma(g, x[n], b)) - f(b))).
+ * y[n] depends on x[n - 64 ... n] alone: any cut into chunks, tiles, launches or puts gives the same bits; with b = 0 negating x negates y; a
+ * non-finite x[n] reaches y[n ... n + 64] of its own stream-channel and nothing else; output past in_len is not stored.  Bit-exact against the
+ * CPU statement (tests/sat_ref/ref_sat.c).
+ * Errors: a null pointer, ch not 1 or 2, a non-finite field, an unknown curve: NAE_ERR_INVALID; oversample not 1, 2, 4 or 8: NAE_ERR_UNSUPPORTED;
+ * dst->base equal to src->base: NAE_ERR_INVALID (a tile reads the 64 samples in front of it after a neighbouring wave may have written them: the
+ * call does not work in place; views that overlap otherwise are not detected and give undefined samples); in_len = 0 or n_streams = 0: NAE_OK
+ * after the checks, nothing is launched.  The block call is causal and writes in_len frames (a caller who wants the last D puts D zeros).  Views
+ * as nae_eq_block_f32's, stream_stride 0 on the source included.  The context keeps the device taps of every M it has run: a warm call allocates
+ * and waits for nothing.  No workspace. */
+typedef struct nae_sat_params {
+    int oversample;     /* M: 1, 2, 4 or 8 */
+    int curve;          /* NAE_SAT_SOFT or NAE_SAT_HARD */
+    float drive;        /* g */
+    float bias;         /* b */
+    float wet, dry;
+} nae_sat_params;
+int nae_sat_latency(int oversample);                       /* D: 0 for 1, 32 for 2, 4 and 8, -1 otherwise */
+int nae_sat_taps(int oversample, float* hd_host);          /* writes the 2 K M + 1 taps hd and returns their count; 0 for M = 1 (and for an M that is not supported, or null) */
+int nae_sat_block_f32(nae_ctx* ctx, const nae_sat_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch): whole chunks of NAE_EQ_CHUNK frames come out as they fill (the last chunk of input
+ * stays for the 64 samples the next one reads in front of it); nae_sat_flush puts D zero frames behind the input and releases the rest, so
+ * in_len + D frames come out in all, equal to the block call's on the input extended by D zeros however the input is cut.  A put after the
+ * flush: NAE_ERR_STATE. */
+int nae_sat_create(nae_ctx* ctx, const nae_sat_params* params, int channels, nae_sat** h);
+int nae_sat_put(nae_sat* h, const float* interleaved, size_t S);
+int nae_sat_put_host(nae_sat* h, const float* interleaved_host, size_t S);
+int nae_sat_flush(nae_sat* h);
+size_t nae_sat_available(nae_sat* h);
+int nae_sat_receive(nae_sat* h, float* dst, size_t max_frames, size_t* got);
+int nae_sat_receive_host(nae_sat* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_sat_destroy(nae_sat* h);
+/* The record on the host, in double, each field rounded once to f32: drive = 10^(drive_db / 20), drive_db in [0, 48]; bias in [0, 1] (an
+ * asymmetric curve: even harmonics); wet = mix 10^(output_db / 20), output_db in [-24, 24], mix in [0, 1]; dry = 1 - mix.  NAE_ERR_INVALID: a
+ * null pointer, an argument that is not finite or outside its range, an unknown curve; NAE_ERR_UNSUPPORTED: oversample not 1, 2, 4 or 8.  No
+ * context, no device work. */
+int nae_sat_design(double drive_db, double bias, int curve, int oversample, double output_db, double mix, nae_sat_params* out);
 
 /* ------------------------------------------------------------------ K13 spectral gate
  * no reference code.  Spec ("K13 spectral gate"): noise reduction on the STFT at n_fft = 512 ... 4096, hop H = n_fft / 4, in the

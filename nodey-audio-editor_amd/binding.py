@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = [
     "nae_echo_receive", "nae_echo_receive_host", "nae_echo_destroy",
     "nae_mod_design", "nae_mod_block_f32", "nae_mod_create", "nae_mod_put", "nae_mod_put_host", "nae_mod_flush", "nae_mod_available",
     "nae_mod_receive", "nae_mod_receive_host", "nae_mod_destroy",
+    "nae_sat_latency", "nae_sat_taps", "nae_sat_design", "nae_sat_block_f32", "nae_sat_create", "nae_sat_put", "nae_sat_put_host", "nae_sat_flush",
+    "nae_sat_available", "nae_sat_receive", "nae_sat_receive_host", "nae_sat_destroy",
     "nae_denoise_design", "nae_denoise_profile_f32", "nae_denoise_block_f32", "nae_denoise_create", "nae_denoise_put", "nae_denoise_put_host",
     "nae_denoise_flush", "nae_denoise_available", "nae_denoise_receive", "nae_denoise_receive_host", "nae_denoise_destroy",
     "nae_loud_design", "nae_loud_lufs", "nae_loud_measure_f32", "nae_loud_apply_f32", "nae_loud_normalize_f32", "nae_loud_create", "nae_loud_put",
@@ -66,7 +68,9 @@ DYNKEY_MAX_SECTIONS = 4                             # NAE_DYNKEY_MAX_SECTIONS (i
 ECHO_MIN_DELAY, ECHO_MAX_DELAY, ECHO_MAX_SECTIONS, ECHO_MAX_FEEDBACK = 1024, 1 << 20, 4, 0.99   # NAE_ECHO_* (include/nae_dsp_spec.h)
 MOD_MIN_DELAY, MOD_MAX_DELAY, MOD_MAX_VOICES, MOD_MAX_FEEDBACK = 2.0, 3070.0, 4, 0.95   # NAE_MOD_* (include/nae_dsp_spec.h)
 MOD_SHAPES = ("sine", "triangle")                   # `shape` of nae_mod_params: NAE_MOD_SINE, NAE_MOD_TRIANGLE
-HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod")   # the handles with the full put / receive set of entries
+SAT_HALF, SAT_MAX_OS = 16, 8                        # NAE_SAT_HALF, NAE_SAT_MAX_OS (include/nae_dsp_spec.h)
+SAT_CURVES = ("soft", "hard")                       # `curve` of nae_sat_params: NAE_SAT_SOFT, NAE_SAT_HARD
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -173,6 +177,18 @@ class ModParams(C.Structure):
         p.rate_inc, p.phase0, p.phase_ch, p.n_voices, p.shape = rate_inc & 0xffffffff, phase0 & 0xffffffff, phase_ch & 0xffffffff, len(voice_phase), shape
         for v, ph in enumerate(voice_phase):
             p.voice_phase[v] = ph & 0xffffffff
+        return p
+
+
+class SatParams(C.Structure):
+    """nae_sat_params: the saturation's parameters (include/nae_gpu.h): the oversampling factor, the curve, the drive g, the bias b, wet and dry;
+    nae_sat_design makes them from decibels and a mix"""
+    _fields_ = [("oversample", C.c_int), ("curve", C.c_int), ("drive", C.c_float), ("bias", C.c_float), ("wet", C.c_float), ("dry", C.c_float)]
+
+    @staticmethod
+    def make(oversample: int = 4, curve: int = 0, drive: float = 1.0, bias: float = 0.0, wet: float = 1.0, dry: float = 0.0) -> "SatParams":
+        p = SatParams()
+        p.oversample, p.curve, p.drive, p.bias, p.wet, p.dry = oversample, curve, drive, bias, wet, dry
         return p
 
 
@@ -304,6 +320,8 @@ def load_library() -> C.CDLL:
         "nae_echo_block_f32": (i, [vp, P(EchoParams), P(Sig), sz, i, sz, P(Sig)]), "nae_echo_create": (i, [vp, P(EchoParams), i, P(vp)]),
         "nae_mod_design": (i, [i, d, d, d, d, i, d, i, d, d, P(ModParams)]),
         "nae_mod_block_f32": (i, [vp, P(ModParams), P(Sig), sz, i, sz, P(Sig)]), "nae_mod_create": (i, [vp, P(ModParams), i, P(vp)]),
+        "nae_sat_latency": (i, [i]), "nae_sat_taps": (i, [i, vp]), "nae_sat_design": (i, [d, d, i, i, d, d, P(SatParams)]),
+        "nae_sat_block_f32": (i, [vp, P(SatParams), P(Sig), sz, i, sz, P(Sig)]), "nae_sat_create": (i, [vp, P(SatParams), i, P(vp)]),
         "nae_denoise_design": (i, [d, d, i, i, i, P(DenoiseParams)]), "nae_denoise_profile_f32": (i, [vp, i, P(Sig), sz, i, vp]),
         "nae_denoise_block_f32": (i, [vp, P(DenoiseParams), vp, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
@@ -757,6 +775,33 @@ class Context:
         """the modulated delay `params` over every stream (nae_mod_block_f32); dst receives in_len frames"""
         self._ck(self.lib.nae_mod_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K18
+    @staticmethod
+    def sat_latency(oversample: int) -> int:
+        """the saturation's latency in samples (nae_sat_latency): 0 at 1, 32 at 2, 4 and 8, -1 otherwise"""
+        return load_library().nae_sat_latency(oversample)
+
+    @staticmethod
+    def sat_taps(oversample: int) -> np.ndarray:
+        """the anti-alias prototype hd of an oversampling factor (nae_sat_taps): 32 M + 1 taps, none at 1"""
+        taps = np.empty(2 * SAT_HALF * SAT_MAX_OS + 1, np.float32)
+        n = load_library().nae_sat_taps(oversample, taps.ctypes.data)
+        return taps[:n].copy()
+
+    @staticmethod
+    def sat_design(drive_db: float = 12.0, bias: float = 0.0, curve: str = "soft", oversample: int = 4, output_db: float = 0.0,
+                   mix: float = 1.0) -> "SatParams":
+        """the saturation's parameters from decibels and a mix (nae_sat_design)"""
+        out = SatParams()
+        rc = load_library().nae_sat_design(drive_db, bias, SAT_CURVES.index(curve), oversample, output_db, mix, C.byref(out))
+        if rc:
+            raise NaeError(f"nae_sat_design({drive_db}, {bias}, {curve}, {oversample}, {output_db}, {mix}) failed: {rc}")
+        return out
+
+    def sat_block(self, params: "SatParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the saturation `params` over every stream (nae_sat_block_f32); dst receives in_len frames and must not be src"""
+        self._ck(self.lib.nae_sat_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     # -- K12
     @staticmethod
     def dyn_design(sample_rate: int, threshold_db: float = -18.0, ratio: float = 4.0, knee_db: float = 6.0, attack_s: float = 0.005,
@@ -992,6 +1037,16 @@ class Mod(_Handle):
     def __init__(self, ctx: Context, params: ModParams, channels: int):
         super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_mod_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+
+class Sat(_Handle):
+    """The saturation's streaming handle (nae_sat_create): put interleaved f32, flush (the latency's tail: in_len + D frames come out in all), receive."""
+
+    _prefix = "nae_sat"
+
+    def __init__(self, ctx: Context, params: SatParams, channels: int):
+        super().__init__(ctx, channels)
+        ctx._ck(ctx.lib.nae_sat_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
 
 
 class Denoise(_Handle):

@@ -272,6 +272,7 @@ int nae_debug_set(nae_ctx* ctx, const char* key, long long value)
     else if (k == "conv_ring" && count) ctx->conv_ring = (int)value;
     else if (k == "echo_group" && count) ctx->echo_group = (int)value;
     else if (k == "mod_sub" && value >= 0 && value <= 64) ctx->mod_sub = (int)value;
+    else if (k == "sat_tile" && count) ctx->sat_tile = (int)value;
     else if (k == "pv_fps" && one_of({0, 1, 2, 4})) ctx->pv_fps = (int)value;
     else if (k == "pv_flow" && one_of({0, 1, 2})) ctx->pv_flow = (int)value;
     else if (k == "pv_lean" && flag) ctx->pv_lean = value != 0;
@@ -363,6 +364,7 @@ int nae_ctx_destroy(nae_ctx* ctx)
     nae_eq_cache_free(ctx);
     nae_loud_cache_free(ctx);
     nae_echo_cache_free(ctx);
+    nae_sat_cache_free(ctx);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return NAE_OK;

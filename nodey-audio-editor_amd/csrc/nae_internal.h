@@ -54,6 +54,10 @@ struct nae_ctx {
     void* ws_echo = nullptr; size_t ws_echo_bytes = 0;
     int echo_group = 0;          // streams per launch of the echo's block call; 0 = from NAE_CONV_WS_BYTES
     int mod_sub = 0;             // samples a wave of the modulated delay computes in parallel, 1 ... 64; 0 = the rule of kernels_mod.hip
+    int sat_tile = 0;            // chunks per wave of the saturation; 0 = choose per launch (nae_pick_sat_tile)
+    // the saturation keeps the device taps of every oversampling factor it has run (kernels_sat.hip): three slots [hd | hu], bit i of sat_taps_have: slot i is there
+    float* d_sat_taps = nullptr; unsigned sat_taps_have = 0;
+    std::vector<float> h_sat_taps;
     // tuning / A-B switches: nae_debug_set(ctx, key, value) (include/nae_gpu.h lists the keys; NAE_DEBUG="key=value,..." applies them at context creation)
     bool dbg_st_unfused = false;     // st_unfused: WSOLA chain runs filter and cubic stage as separate launches
     int dbg_td_nc = 0;               // td_nc = 1|2|4: candidates per thread of the WSOLA search (0: by batch size)
@@ -326,6 +330,16 @@ constexpr size_t NAE_MOD_KEEP = 3072;
 int nae_mod_check(nae_ctx* ctx, const nae_mod_params* p, int ch);
 int nae_launch_mod(nae_ctx* ctx, const nae_mod_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
                    size_t c_origin, size_t c_stop, float* d_state);
+
+// kernels_sat.hip: the saturation ("K18 saturation").  nae_sat_check: the parameter rules of the block call and the handle.
+// nae_launch_sat runs chunks [c_origin, c_stop) of absolutely indexed signals of in_len samples, one wave per stream-channel and tile of
+// nae_pick_sat_tile chunks: it reads from 64 samples in front of chunk c_origin on (zero below sample 0 and from in_len on) and keeps nothing
+// between launches.
+int nae_sat_check(nae_ctx* ctx, const nae_sat_params* p, int ch);
+int nae_launch_sat(nae_ctx* ctx, const nae_sat_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
+                   size_t c_origin, size_t c_stop);
+int nae_pick_sat_tile(nae_ctx* ctx, size_t chunks, size_t n_sc);
+void nae_sat_cache_free(nae_ctx* ctx);
 
 // kernels_denoise.hip: the spectral gate ("K13 spectral gate").  nae_denoise_check: the parameter rules of the block call and the
 // handle.  nae_launch_denoise runs hop blocks [b_origin, b_stop) of absolutely indexed signals of in_len samples: it reads from

@@ -97,6 +97,14 @@ struct nae_mod : BlockHandle {
     int process() override;
 };
 
+// the saturation's handle ("K18 saturation"): whole chunks of NAE_EQ_CHUNK samples are computed as they fill; the kernel keeps nothing
+// between launches and reads the 64 samples in front of a chunk from the input itself, so the last chunk of input stays in the FIFO; the flush puts
+// the latency's zero frames behind the input (flush_tail)
+struct nae_sat : BlockHandle {
+    nae_sat_params params;
+    int process() override;
+};
+
 // the spectral gate's handle ("K13 spectral gate"): whole hop blocks of n_fft / 4 samples are computed once the time_smooth + 3
 // blocks behind them are there; the input stays from time_smooth + 3 blocks in front of the next block on, and nothing else is kept
 struct nae_denoise : BlockHandle {
@@ -361,6 +369,13 @@ int nae_mod::process()
 {
     return run_units(NAE_EQ_CHUNK, 0, 0, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
         return nae_launch_mod(ctx, &params, &src, in.total, ch, 1, &dst, from, to, d_state);
+    });
+}
+
+int nae_sat::process()
+{
+    return run_units(NAE_EQ_CHUNK, 0, 1, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
+        return nae_launch_sat(ctx, &params, &src, in.total, ch, 1, &dst, from, to);
     });
 }
 
@@ -708,6 +723,30 @@ size_t nae_mod_available(nae_mod* h) { return handle_available(h); }
 int nae_mod_receive(nae_mod* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_mod_receive_host(nae_mod* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_mod_destroy(nae_mod* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ saturation
+int nae_sat_create(nae_ctx* ctx, const nae_sat_params* params, int channels, nae_sat** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    const int rc = nae_sat_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_sat* s = handle_new<nae_sat>(ctx, channels);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    s->flush_tail = (size_t)nae_sat_latency(params->oversample);
+    return handle_created(s, NAE_OK, h);
+}
+
+int nae_sat_put(nae_sat* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_sat_put_host(nae_sat* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+// flush: the latency's zero frames go in behind the input and the partial last chunk comes out: in_len + D frames over the handle's life
+int nae_sat_flush(nae_sat* h) { return handle_flush(h); }
+size_t nae_sat_available(nae_sat* h) { return handle_available(h); }
+int nae_sat_receive(nae_sat* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_sat_receive_host(nae_sat* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_sat_destroy(nae_sat* h) { return handle_destroy(h); }
 
 // ------------------------------------------------------------------------------------------------ spectral gate
 int nae_denoise_create(nae_ctx* ctx, const nae_denoise_params* params, const float* profile_dev, int profile_ch, int channels, nae_denoise** h)

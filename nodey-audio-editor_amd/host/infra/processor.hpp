@@ -163,4 +163,6 @@ namespace infra
 	void register_echo_processors();
 	// the modulation effects (audio_modulation): called after the nine above, each of which stays the list it was
 	void register_modulation_processors();
+	// the saturation (audio_saturation): called after the ten above, each of which stays the list it was
+	void register_saturation_processors();
 }

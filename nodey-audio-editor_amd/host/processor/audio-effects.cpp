@@ -1,5 +1,5 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
-// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
+// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 // Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
 #include "audio-filter.hpp"
@@ -9,6 +9,7 @@
 #include "audio-sidechain.hpp"
 #include "audio-echo.hpp"
 #include "audio-modulation.hpp"
+#include "audio-saturation.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "node-util.hpp"
@@ -854,6 +855,72 @@ namespace processor
 				nae_mod* mod = nullptr;
 				gpu::check(nae_mod_create(ctx, &params, ch, &mod), "nae_mod_create");
 				return mod;
+			}
+		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_saturation
+	infra::Processor::Info Audio_saturation::get_processor_info()
+	{
+		return {"audio_saturation", "Audio Saturation", false, [] { return std::unique_ptr<infra::Processor>(new Audio_saturation); },
+				"Drive, saturation and clipping: a soft or hard curve run oversampled so its harmonics do not alias (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_saturation::get_pin_attributes() const { return io_pins(); }
+
+	Json::Value Audio_saturation::serialize() const
+	{
+		Json::Value value;
+		if (drive_db != default_drive_db) value["drive_db"] = drive_db;
+		if (curve != Curve::Soft) value["curve"] = "hard";
+		if (bias != default_bias) value["bias"] = bias;
+		if (oversample != default_oversample) value["oversample"] = oversample;
+		if (output_db != default_output_db) value["output_db"] = output_db;
+		if (mix != default_mix) value["mix"] = mix;
+		return value;
+	}
+
+	void Audio_saturation::deserialize(const Json::Value& value)
+	{
+		const auto wrong = [](const char* field) { return wrong_field("Audio_saturation", field); };
+		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
+		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_saturation", key, lo, hi, fallback); };
+		const double dr = real("drive_db", 0.0, 48.0, default_drive_db);
+		Curve cv = Curve::Soft;
+		if (value.isMember("curve"))
+		{
+			if (!value["curve"].isString()) throw wrong("curve");
+			const std::string name = value["curve"].asString();
+			if (name == "hard") cv = Curve::Hard;
+			else if (name != "soft") throw wrong("curve");
+		}
+		const double bs = real("bias", 0.0, 1.0, default_bias);
+		const int os = int_from_json(value, "Audio_saturation", "oversample", 1, NAE_SAT_MAX_OS, default_oversample);
+		if (nae_sat_latency(os) < 0) throw wrong("oversample");
+		const double od = real("output_db", -24.0, 24.0, default_output_db);
+		const double mx = real("mix", 0.0, 1.0, default_mix);
+		drive_db = dr; curve = cv; bias = bs; oversample = os; output_db = od; mix = mx;
+	}
+
+	void Audio_saturation::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Saturation");
+		// the latency is dropped in front; the flush's tail of as many frames completes the frames still owed
+		run_on_handle<nae_sat>(
+			io.input, io.output, stop_token, {"nae_sat", nae_sat_put, nae_sat_flush, nae_sat_available, nae_sat_receive, nae_sat_destroy}, "node",
+			(size_t)nae_sat_latency(oversample),
+			[&](nae_ctx* ctx, const Frame_data*, int ch)
+			{
+				nae_sat_params params;
+				gpu::check(nae_sat_design(drive_db, bias, curve == Curve::Hard ? NAE_SAT_HARD : NAE_SAT_SOFT, oversample, output_db, mix, &params), "nae_sat_design");
+				nae_sat* sat = nullptr;
+				gpu::check(nae_sat_create(ctx, &params, ch, &sat), "nae_sat_create");
+				return sat;
 			}
 		);
 	}

@@ -20,6 +20,7 @@
 #include "audio-sidechain.hpp"
 #include "audio-echo.hpp"
 #include "audio-modulation.hpp"
+#include "audio-saturation.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "audio-mix.hpp"
@@ -158,6 +159,18 @@ namespace processor
 		spread = std::clamp(spread, 0.0, 1.0);
 		wet = std::clamp(wet, 0.0, 1.0);
 		dry = std::clamp(dry, 0.0, 1.0);
+		return false;
+	}
+
+	void Audio_saturation::draw_title() {}
+	bool Audio_saturation::draw_content(bool)
+	{
+		// what the widgets would keep: every value inside its range, the oversampling factor a power of two
+		drive_db = std::clamp(drive_db, 0.0, 48.0);
+		bias = std::clamp(bias, 0.0, 1.0);
+		oversample = oversample >= 8 ? 8 : oversample >= 4 ? 4 : oversample >= 2 ? 2 : 1;
+		output_db = std::clamp(output_db, -24.0, 24.0);
+		mix = std::clamp(mix, 0.0, 1.0);
 		return false;
 	}
 

@@ -12,6 +12,7 @@
 #include "processor/audio-sidechain.hpp"
 #include "processor/audio-echo.hpp"
 #include "processor/audio-modulation.hpp"
+#include "processor/audio-saturation.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -63,4 +64,7 @@ namespace infra
 
 	// the modulation effects: chorus, flanger and vibrato on the modulated delay; a call of its own, so the nine lists above stay what they were
 	void register_modulation_processors() { register_each<processor::Audio_modulation>(); }
+
+	// the nonlinear effects: drive, saturation and clipping; a call of its own, so the ten lists above stay what they were
+	void register_saturation_processors() { register_each<processor::Audio_saturation>(); }
 }
