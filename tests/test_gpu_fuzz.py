@@ -1,5 +1,6 @@
 """GPU: a seeded, bounded subset of the randomised differential runs of tests/tools/fuzz_*.py (vocoder + spectrum, the
-SoundTouch-shaped chain, the N2 converter, the FIR filter, the effect nodes K10 ... K17) against the CPU oracle and statements.  The full runs (python tests/tools/fuzz_X.py CASES SEED)
+SoundTouch-shaped chain, the N2 converter, the FIR filter, the effect nodes K10 ... K17, the graph step mix -> pitch -> spectrum in every split
+and layout) against the CPU oracle and statements.  The full runs (python tests/tools/fuzz_X.py CASES SEED)
 draw more cases from the same generators; these fixed seeds keep the driver's `-m gpu` run to a few seconds per test."""
 import os
 import sys
@@ -54,3 +55,12 @@ def test_fuzz_effects_seeded(nae, ctx, node):
     import fuzz_effects
     cases, seed = fuzz_effects.SEEDED[node]
     assert fuzz_effects.main(node, cases=cases, seed=seed, ctx=ctx, nae=nae) == cases
+
+
+def test_fuzz_graph_seeded(nae, ctx):
+    """the graph step input -> mix(2) -> pitch -> spectrum at drawn ragged lengths, base offsets and strides: nae_graph4_run, the same with the mix
+    fuse off, the three nodes one by one and nae_debug_graph4_stages give the same bits, the expected kernels, the oracle's mix and spectrum and
+    touch nothing outside their views (tests/test_fuzz_graph_cpu.py pins which edges this seed reaches)"""
+    import fuzz_graph
+    cases, seed = fuzz_graph.SEEDED
+    assert fuzz_graph.main(cases=cases, seed=seed, ctx=ctx, nae=nae) == cases

@@ -560,3 +560,69 @@ def test_random_signal_layouts(ctx, nae):
             assert np.array_equal(d_dst.download(), want), ("amix", case, lay_src, lay_dst, n_streams, S)
             d_src2.free()
         d_src.free(); d_dst.free()
+
+
+def _view(n_streams, S, ch, planar, stream_pad=0, plane_pad=0, shared=False):
+    """an aligned view with strides padded up to a multiple of 4 -> (floats, (stream, channel, frame strides), index array [s][c][i])"""
+    cs = ((S + 3) & ~3) + plane_pad if planar else 1
+    fs = 1 if planar else ch
+    ss = 0 if shared else ((ch * (cs if planar else S) + 3) & ~3) + stream_pad
+    idx = np.arange(n_streams)[:, None, None] * ss + np.arange(ch)[None, :, None] * cs + np.arange(S)[None, None, :] * fs
+    return int(idx.max()) + 5, (ss, cs, fs), idx
+
+
+def _only_kernel(ctx, call):
+    ctx.prof_reset(); ctx.prof_enable(True)
+    try:
+        call()
+        ctx.sync()
+    finally:
+        ctx.prof_enable(False)
+    return sorted(ctx.prof_report())
+
+
+@pytest.mark.parametrize("S", [1, 2, 3, 5, 258, 1001, 4099])
+def test_aligned_but_ragged_layouts(ctx, nae, S):
+    """the scalar tails of the 16-byte kernels: S = 1, 2, 3 (mod 4) with aligned bases and stream and plane strides padded to multiples of 4, so
+    that copy_i2p_kernel, copy_p2i_kernel, copy_flat_kernel and amix_i2p_kernel (1, 2 and 16 inputs, one of them shared by the streams) really
+    run; expected values by plain numpy indexing, the sentinel everywhere outside the view"""
+    assert S % 4
+    rng = np.random.default_rng(20260200 + S)
+    for n_streams in (1, 3):
+        for kernel, ch, src_planar, dst_planar in (("copy_i2p_kernel", 2, False, True), ("copy_p2i_kernel", 2, True, False),
+                                                   ("copy_flat_kernel", 2, False, False), ("copy_flat_kernel", 1, True, True)):
+            for scale in (False, True):
+                n_src, st_s, idx_s = _view(n_streams, S, ch, src_planar, stream_pad=4 * int(rng.integers(0, 3)), plane_pad=4 * int(rng.integers(0, 2)))
+                n_dst, st_d, idx_d = _view(n_streams, S, ch, dst_planar, stream_pad=4 * int(rng.integers(0, 3)), plane_pad=4 * int(rng.integers(0, 2)))
+                src = rng.uniform(-1, 1, n_src).astype(np.float32)
+                d_src, d_dst = ctx.array(src), ctx.array(np.full(n_dst, 7.0, np.float32))
+                s_sig, d_sig = nae.Sig(d_src.ptr, *st_s), nae.Sig(d_dst.ptr, *st_d)
+                vol = float(np.float32(rng.uniform(0, 2)))
+                if scale:
+                    ran = _only_kernel(ctx, lambda: ctx.gain_sig(s_sig, d_sig, S, ch, n_streams, vol))
+                else:
+                    ran = _only_kernel(ctx, lambda: ctx.copy_sig(s_sig, d_sig, S, ch, n_streams))
+                assert ran == [kernel], (ran, kernel, n_streams, ch, st_s, st_d)
+                want = np.full(n_dst, 7.0, np.float32)
+                want[idx_d] = (src[idx_s] * np.float32(vol)).astype(np.float32) if scale else src[idx_s]
+                assert np.array_equal(d_dst.download().view(np.uint32), want.view(np.uint32)), (kernel, scale, n_streams, ch, st_s, st_d)
+                d_src.free(); d_dst.free()
+        for n_in in (1, 2, 16):
+            shared_at = n_in - 1 if n_in > 1 else -1                     # the last input of several: one buffer for every stream
+            n_dst, st_d, idx_d = _view(n_streams, S, 2, True, stream_pad=4 * int(rng.integers(0, 3)), plane_pad=4 * int(rng.integers(0, 2)))
+            ins, sigs, acc = [], [], np.zeros(idx_d.shape, np.float32)
+            vols = [float(np.float32(v)) for v in rng.uniform(-1, 1, n_in)]
+            for k in range(n_in):
+                n_src, st_s, idx_s = _view(n_streams, S, 2, False, stream_pad=4 * int(rng.integers(0, 3)), shared=k == shared_at)
+                x = rng.uniform(-1, 1, n_src).astype(np.float32)
+                ins.append(ctx.array(x))
+                sigs.append(nae.Sig(ins[-1].ptr, *st_s))
+                acc = (acc + (x[idx_s] * np.float32(vols[k])).astype(np.float32)).astype(np.float32)
+            d_dst = ctx.array(np.full(n_dst, 7.0, np.float32))
+            ran = _only_kernel(ctx, lambda: ctx.amix_sig(sigs, vols, nae.Sig(d_dst.ptr, *st_d), S, n_streams))
+            assert ran == ["amix_i2p_kernel"], (ran, n_in, n_streams, st_d)
+            want = np.full(n_dst, 7.0, np.float32)
+            want[idx_d] = acc
+            assert np.array_equal(d_dst.download().view(np.uint32), want.view(np.uint32)), ("amix", n_in, n_streams, st_d)
+            for d in ins + [d_dst]:
+                d.free()

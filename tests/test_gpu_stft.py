@@ -316,39 +316,59 @@ def test_k7_full_size_properties(ctx, nae):
 
 @pytest.mark.parametrize("n_streams,S,semis,rate,shared_b,planar_mix,vols", [
     (3, 20000, 3, 1.0, True, True, (0.5, 0.5)),        # transposer first: the mix is fused into its staging
-    (6, 8193, 5, 1.0, False, True, (0.3, 0.9)),        # one full group of 4 streams + a partial one, odd length
+    (6, 8193, 5, 1.0, False, True, (0.3, 0.9)),        # odd length in unpadded views (stream strides 16386, planes 8193): NOT fused, the mix and
+                                                       # the transposer run as amix_generic_kernel + resample_tile_kernel (4 streams + a partial group)
     (5, 3000, 3, 1.0, True, False, (1.0, 0.25)),       # interleaved mix output; shorter than 3 transposer tiles
     (2, 20000, -4, 1.0, True, True, (0.5, 0.5)),       # vocoder first: the mix stays a launch of its own
     (2, 12000, 0, 1.5, True, True, (0.5, 0.5)),        # plain rate change (transposer only)
     (1, 6000, 0, 1.0, True, True, (0.5, 0.5)),         # identity pitch node
+    (6, 8193, 5, 1.0, False, "padded", (0.3, 0.9)),    # the odd length with stream and plane strides padded to multiples of 4: fused, one full
+                                                       # group of 4 streams + a partial one, a ragged last group of 4 frames
 ])
 def test_graph4_matches_node_by_node_oracle(ctx, nae, n_streams, S, semis, rate, shared_b, planar_mix, vols):
-    """input -> mix(2) -> pitch -> spectrum: every node's output against the oracle run node by node"""
-    a = orc.fill_uniform(n_streams * S * 2, 51)
-    b = orc.fill_uniform((1 if shared_b else n_streams) * S * 2, 52)
+    """input -> mix(2) -> pitch -> spectrum: every node's output against the oracle run node by node.  planar_mix "padded": a planar mix, and
+    every view's rows padded up to a multiple of 4 frames (the row length R below), which keeps an odd length on the 16-byte routes; at a length
+    that is no multiple of 4 the route the front stage took is asserted as well"""
+    padded = planar_mix == "padded"
+    planar_mix = bool(planar_mix)
+    R = (S + 3) & ~3 if padded else S
+    a, b = np.zeros(n_streams * R * 2, np.float32), np.zeros((1 if shared_b else n_streams) * R * 2, np.float32)
+    a.reshape(n_streams, R, 2)[:, :S] = orc.fill_uniform(n_streams * S * 2, 51).reshape(n_streams, S, 2)
+    b.reshape(-1, R, 2)[:, :S] = orc.fill_uniform((1 if shared_b else n_streams) * S * 2, 52).reshape(-1, S, 2)
     p = 2 ** (semis / 12)
     pl = ctx.stretch_plan(rate, p, S)
     F = ctx.spectrum_frames(pl.out_len)
     d_a, d_b = ctx.array(a), ctx.array(b)
-    d_mix, d_pitch, d_spec = ctx.empty(n_streams * S * 2), ctx.empty(max(1, n_streams * pl.out_len * 2)), ctx.empty(max(1, n_streams * F * 2 * 513))
+    d_mix, d_pitch, d_spec = ctx.empty(n_streams * R * 2), ctx.empty(max(1, n_streams * pl.out_len * 2)), ctx.empty(max(1, n_streams * F * 2 * 513))
     g = nae.Graph4()
-    g.in_a = nae.Sig.interleaved(d_a.ptr, S, 2)
-    g.in_b = nae.Sig.interleaved(d_b.ptr, S, 2, shared=shared_b)
+    g.in_a = nae.Sig.interleaved(d_a.ptr, R, 2)
+    g.in_b = nae.Sig.interleaved(d_b.ptr, R, 2, shared=shared_b)
     g.vol_a, g.vol_b = vols
-    g.mix_out = nae.Sig.planar(d_mix.ptr, S, 2) if planar_mix else nae.Sig.interleaved(d_mix.ptr, S, 2)
+    g.mix_out = nae.Sig.planar(d_mix.ptr, R, 2) if planar_mix else nae.Sig.interleaved(d_mix.ptr, R, 2)
     g.rate, g.pitch = rate, p
     g.pitch_out = nae.Sig.interleaved(d_pitch.ptr, pl.out_len, 2)
     g.spec_out, g.spec_stream_stride = d_spec.ptr, F * 2 * 513
     g.S, g.n_streams = S, n_streams
-    ctx.graph4(g)
+    if S % 4:
+        ctx.prof_reset(); ctx.prof_enable(True)
+    try:
+        ctx.graph4(g)
+        ctx.sync()
+    finally:
+        if S % 4:
+            ctx.prof_enable(False)
+    if S % 4:
+        front = {"mix_resample_tile_kernel"} if padded else {"amix_generic_kernel", "resample_tile_kernel"}
+        every = {"mix_resample_tile_kernel", "amix_i2p_kernel", "amix_generic_kernel", "resample_tile_kernel", "resample_kernel"}
+        assert set(ctx.prof_report()) & every == front, sorted(ctx.prof_report())
     mix, pitch, spec = d_mix.download(), d_pitch.download(), d_spec.download()
     for s in range(n_streams):
-        xs = a.reshape(n_streams, S, 2)[s]
-        bs = b.reshape(-1, S, 2)[0 if shared_b else s]
-        L, R = orc.amix([xs[:, 0], bs[:, 0]], [xs[:, 1], bs[:, 1]], list(vols))
-        m = mix.reshape(n_streams, 2, S)[s] if planar_mix else mix.reshape(n_streams, S, 2)[s].T
-        assert np.array_equal(m[0], L) and np.array_equal(m[1], R), s                      # mix: bit-exact
-        ref_p = orc.stretch(np.stack([L, R], 1).reshape(-1), 2, rate, p)
+        xs = a.reshape(n_streams, R, 2)[s, :S]
+        bs = b.reshape(-1, R, 2)[0 if shared_b else s, :S]
+        L, Rt = orc.amix([xs[:, 0], bs[:, 0]], [xs[:, 1], bs[:, 1]], list(vols))
+        m = mix.reshape(n_streams, 2, R)[s, :, :S] if planar_mix else mix.reshape(n_streams, R, 2)[s, :S].T
+        assert np.array_equal(m[0], L) and np.array_equal(m[1], Rt), s                     # mix: bit-exact
+        ref_p = orc.stretch(np.stack([L, Rt], 1).reshape(-1), 2, rate, p)
         got_p = pitch[: n_streams * pl.out_len * 2].reshape(n_streams, -1)[s]
         assert rel_rms(got_p, ref_p) <= TOL                                                # pitch: tolerance
         if F:
