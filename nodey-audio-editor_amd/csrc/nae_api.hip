@@ -779,6 +779,12 @@ static int pv_tile_phase_impl(nae_ctx* ctx, const nae_pv_opts& o, double rate, d
     const size_t bins = (size_t)o.n_fft / 2 + 1, pad = nae_pv_record_pad(o.n_fft);
     const size_t need = n_streams * ch * n_tiles * bins;
     if (dst_capacity < need) return nae_fail(ctx, NAE_ERR_INVALID, "destination too small");
+    if (n_tiles == 1) {
+        // a single tile: nae_launch_pv_phase writes no record (pass 3 starts from zero by itself, PvParams::base_zero), so the workspace holds
+        // whatever an earlier call left; the phase in front of tile 0 is zero
+        memset(dst_host, 0, need * sizeof(int32_t));
+        return NAE_OK;
+    }
     const size_t ws_bytes = nae_pv_workspace_bytes(false, o.n_fft, pl.frames, ch, n_streams, tile);   // the records (the locked workspace begins with them)
     if ((rc = nae_pv_reserve_ws(ctx, run, pl.frames, ch, n_streams, tile))) return rc;
     const nae_sig* pv_src = src;

@@ -1,6 +1,7 @@
 """GPU: a seeded, bounded subset of the randomised differential runs of tests/tools/fuzz_*.py (vocoder + spectrum, the
 SoundTouch-shaped chain, the N2 converter, the FIR filter, the effect nodes K10 ... K17, the graph step mix -> pitch -> spectrum in every split
-and layout) against the CPU oracle and statements.  The full runs (python tests/tools/fuzz_X.py CASES SEED)
+and layout, the vocoder's options — lock, transients, channel link, lifter, formant shift, batches, tilings, layouts, handle — on inputs with
+onsets) against the CPU oracle and statements.  The full runs (python tests/tools/fuzz_X.py CASES SEED)
 draw more cases from the same generators; these fixed seeds keep the driver's `-m gpu` run to a few seconds per test."""
 import os
 import sys
@@ -64,3 +65,13 @@ def test_fuzz_graph_seeded(nae, ctx):
     import fuzz_graph
     cases, seed = fuzz_graph.SEEDED
     assert fuzz_graph.main(cases=cases, seed=seed, ctx=ctx, nae=nae) == cases
+
+
+def test_fuzz_pv_options_seeded(nae, ctx):
+    """the vocoder's option space on the scene whose channels and streams have onsets of their own: integer phases bit-exact and samples
+    within 1e-4 of the statement in every stream, every stream of a batch equal to its lone run, the handle equal to the block call, nothing
+    written outside the destination view, and the kernels of the effective options (tests/test_fuzz_pv_cpu.py pins which edges this seed
+    reaches)"""
+    import fuzz_pv_options
+    cases, seed = fuzz_pv_options.SEEDED
+    assert fuzz_pv_options.main(cases=cases, seed=seed, ctx=ctx, nae=nae) == cases

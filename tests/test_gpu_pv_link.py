@@ -15,7 +15,7 @@ import pytest
 import node_harness
 import pv_ref
 from conftest import rel_rms
-from pv_gpu import profiled, same_bits, stream
+from pv_gpu import profiled, same_bits, scene, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -32,29 +32,6 @@ ROUTES = [pytest.param(512, False, True, id="512-tr"), pytest.param(1024, False,
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
     return pv_ref.build(str(tmp_path_factory.mktemp("ref_pv")))
-
-
-def scene(L, seed=3, n_hits=None):
-    """a stereo stream whose channels decide differently on their own: two partials at different levels per channel over independent quiet
-    noise, with clicks and decaying noise bursts at seeded places — a third in the left channel only, a third in the right only, a third in
-    both at different levels"""
-    rng = np.random.default_rng(seed)
-    n = np.arange(L)
-    a, b = np.sin(2 * np.pi * 1000.0 * n / 48000), np.sin(2 * np.pi * 3300.0 * n / 48000)
-    x = 0.01 * rng.standard_normal((L, 2))
-    x[:, 0] += 0.05 * a + 0.01 * b
-    x[:, 1] += 0.01 * a + 0.04 * b
-    n_hits = n_hits or max(6, L // 6000)
-    for i, p in enumerate(np.sort(rng.choice(np.arange(2000, L - 3000), n_hits, replace=False))):
-        gains = ((1.0, 0.0), (0.0, 1.0), (1.0, 0.3))[i % 3]
-        if rng.random() < 0.5:
-            hit = np.zeros(2400)
-            hit[0] = 0.9
-        else:
-            hit = 0.6 * np.exp(-np.arange(2400) / 300.0) * rng.standard_normal(2400)
-        x[p:p + 2400, 0] += gains[0] * hit
-        x[p:p + 2400, 1] += gains[1] * hit
-    return np.ascontiguousarray(x, np.float32).reshape(-1)
 
 
 def block(c, nae, x, ch, rate, pitch, n_fft, lock=False, transients=False, link=True, lifter=0, formant_ratio=None, n_streams=1):

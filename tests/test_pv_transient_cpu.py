@@ -13,7 +13,7 @@ import pytest
 import node_harness
 import orc
 import pv_ref
-from pv_gpu import tone
+from pv_gpu import RANGE_RHOS, RANGE_TEMPOS, hard_bursts, placed_clicks, range_case, tone
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = (512, 1024, 2048, 4096)
@@ -219,6 +219,29 @@ def test_no_false_onsets(ref, n_fft):
         scale = pl.rate_eff if pl.rs_first else 1.0          # transposer first: the vocoder reads the transposed signal
         for p, s in zip(pos, starts):
             assert s <= p / scale < s + n_fft, (rate, pitch, p, s)
+
+
+@pytest.mark.parametrize("n_fft", SIZES)
+def test_range_rows_fire_in_one_channel_only(nae, ref, n_fft):
+    """the premise of tests/test_gpu_pv_transient.py::test_transients_over_the_tempo_range, where it can be checked: in every row (tempo
+    0.26, 3.9, 8, 16 and 1/64, the transposer off, behind and in front) the statement has an onset in the left channel only and one in the
+    right only; above tempo 1/2 the placed clicks' onsets fall on a 16-frame tile's first, second and last frame.  At 1/64 the analysis hop
+    is N/256 samples and nothing within full scale fires — the same clicks at height 0.9, and the hard bursts that fire at 0.26, give no
+    onset — while the clicks of height 4096 in digital silence that the rows use do."""
+    for tempo in RANGE_TEMPOS:
+        for rho in RANGE_RHOS:
+            x, L, rate, pitch = range_case(nae, n_fft, tempo, rho)
+            on = pv_ref.onsets(ref, x, 2, rate, pitch, n_fft)
+            assert 48 <= on.shape[0] <= 1200, (tempo, rho, on.shape)
+            left, right = np.nonzero(on[:, 0] & ~on[:, 1])[0], np.nonzero(on[:, 1] & ~on[:, 0])[0]
+            assert left.size and right.size, (tempo, rho, left, right)
+            if tempo > 0.5:
+                assert {0, 1, 15} <= set(np.nonzero(on.any(1))[0] % 16), (tempo, rho)
+            if tempo < 1 / 32:
+                H, Lb = n_fft // 4, int(14 * n_fft * max(rho, 1.0))              # two bursts
+                for quiet in (placed_clicks(nae, L, 2, rate, pitch, n_fft, first=1, every=1, depth=int(H * tempo), sides=True),
+                              hard_bursts(nae, Lb, rate, pitch, n_fft)):
+                    assert np.abs(quiet).max() > 0.5 and not pv_ref.onsets(ref, quiet, 2, rate, pitch, n_fft).any(), (tempo, rho)
 
 
 def test_abi_declares_the_flag(nae):
