@@ -125,15 +125,18 @@ def profiled(c, fn, *args, **kw):
     return out, set(c.prof_report())
 
 
-def block(c, nae, x, ch, rate, pitch, n_fft=1024, lock=False, lifter=0, n_streams=1, planar_in=False, planar_out=False):
-    """the block call on x, [n_streams][L][ch] flattened -> interleaved [n_streams * out_len * ch], whatever the layouts on the device"""
+def block(c, nae, x, ch, rate, pitch, n_fft=1024, lock=False, lifter=0, n_streams=1, planar_in=False, planar_out=False, transients=False,
+          link=False, formant_ratio=None):
+    """the block call on x, [n_streams][L][ch] flattened -> interleaved [n_streams * out_len * ch], whatever the layouts on the device;
+    formant_ratio given: the _formant_shift entry and its plan"""
     L = x.size // (ch * n_streams)
-    pl = c.stretch_plan(rate, pitch, L, n_fft)
+    pl = c.stretch_plan(rate, pitch, L, n_fft, lifter, formant_ratio) if formant_ratio is not None else c.stretch_plan(rate, pitch, L, n_fft)
     flat = np.ascontiguousarray(x.reshape(n_streams, L, ch).transpose(0, 2, 1)).reshape(-1) if planar_in else x
     d_x, d_o = c.array(np.ascontiguousarray(flat, np.float32)), c.empty(max(1, n_streams * pl.out_len * ch))
     src = nae.Sig.planar(d_x.ptr, L, ch) if planar_in else nae.Sig.interleaved(d_x.ptr, L, ch)
     dst = nae.Sig.planar(d_o.ptr, pl.out_len, ch) if planar_out else nae.Sig.interleaved(d_o.ptr, pl.out_len, ch)
-    c.stretch_block(rate, pitch, src, L, ch, n_streams, dst, phase_lock=lock, n_fft=n_fft, formant=lifter)
+    c.stretch_block(rate, pitch, src, L, ch, n_streams, dst, phase_lock=lock, n_fft=n_fft, formant=lifter, transients=transients,
+                    formant_ratio=formant_ratio, link_channels=link)
     out = d_o.download()[: n_streams * pl.out_len * ch]
     d_x.free(); d_o.free()
     if planar_out:
