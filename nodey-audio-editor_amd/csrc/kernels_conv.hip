@@ -233,8 +233,7 @@ __global__ __launch_bounds__(64 * (Conv<N>::kWavesM)) void conv_mac_kernel(OutVi
 template <int N>
 static int launch_conv_taps(nae_ctx* ctx, const float* hpad, cf* hspec, int n, const SpecAnyTables& tb)
 {
-    NAE_KLAUNCH(ctx, "conv_taps_kernel", conv_taps_kernel<N>, dim3((unsigned)n), dim3(64), 0, ctx->stream, hpad, hspec, tb);
-    return nae_check(ctx, hipGetLastError(), "conv_taps_kernel");
+    return nae_launch_grid(ctx, "conv_taps_kernel", conv_taps_kernel<N>, dim3((unsigned)n), dim3(64), 0, hpad, hspec, tb);
 }
 
 template <int N>

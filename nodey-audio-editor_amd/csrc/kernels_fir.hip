@@ -129,8 +129,7 @@ static int launch_fir(nae_ctx* ctx, const SigViewD& src, const OutViewD& out, co
 template <int N>
 static int launch_fir_taps(nae_ctx* ctx, const float* hpad, cf* hspec, const SpecAnyTables& tb)
 {
-    NAE_KLAUNCH(ctx, "fir_taps_kernel", fir_taps_kernel<N>, dim3(1), dim3(64), 0, ctx->stream, hpad, hspec, tb);
-    return nae_check(ctx, hipGetLastError(), "fir_taps_kernel");
+    return nae_launch_grid(ctx, "fir_taps_kernel", fir_taps_kernel<N>, dim3(1), dim3(64), 0, hpad, hspec, tb);
 }
 
 } // namespace nae

@@ -28,6 +28,13 @@ static inline unsigned grid_for(size_t work_items)
     if (g == 0) g = 1;
     return (unsigned)g;
 }
+// x extent of a (work, ns streams) grid: grid_for, cut so that the whole launch holds about 4 kMaxGrid workgroups
+static inline unsigned grid_for(size_t work_items, size_t ns)
+{
+    unsigned gx = grid_for(work_items);
+    if ((size_t)gx * ns > (size_t)kMaxGrid * 4) { gx = (unsigned)(((size_t)kMaxGrid * 4 + ns - 1) / ns); if (gx == 0) gx = 1; }
+    return gx;
+}
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -103,9 +110,7 @@ static int launch_map_planes(nae_ctx* ctx, const void* const* src, void* const* 
         vec = vec && aligned16(src[p]) && aligned16(dst[p]);
     }
     const size_t items = vec ? (n / Vec16<T>::n + Vec16<T>::n) : n;
-    NAE_KLAUNCH(ctx, what, (map_planes_kernel<T, Op>), dim3(grid_for(items), planes), dim3(kBlock), 0, ctx->stream, pp, n,
-                       op, vec);
-    return nae_check(ctx, hipGetLastError(), what);
+    return nae_launch_grid(ctx, what, map_planes_kernel<T, Op>, dim3(grid_for(items), planes), dim3(kBlock), 0, pp, n, op, vec);
 }
 
 // ------------------------------------------------------------------------------------------------ K2 / sig copy
@@ -219,32 +224,20 @@ int nae_launch_copy_sig(nae_ctx* ctx, const nae_sig* src, const nae_sig* dst, si
               (is_planar(src) && is_planar(dst) && src->chan_stride == S && dst->chan_stride == S) || ch == 1) &&
              (ch > 1 || (src->frame_stride == 1 && dst->frame_stride == 1)) && view_aligned(src, 0) && view_aligned(dst, 0))
         mode = kFlat;
-    for (size_t s0 = 0; s0 < n_streams; s0 += 65535) {
-        const unsigned ns = (unsigned)((n_streams - s0 < 65535) ? n_streams - s0 : 65535);
-        SigViewD ss = s;
-        OutViewD dd = d;
-        ss.base += (long long)s0 * ss.ss;
-        dd.base += (long long)s0 * dd.ss;
-        const long long flat = (long long)S * ch;
-        unsigned gx = grid_for(mode == kGeneric ? (size_t)flat : (size_t)flat / 4 + 1);
-        if ((size_t)gx * ns > (size_t)kMaxGrid * 4) { gx = (unsigned)(((size_t)kMaxGrid * 4 + ns - 1) / ns); if (gx == 0) gx = 1; }
-        dim3 grid(gx, ns), block(kBlock);
-#define NAE_LAUNCH(K, ...)                                                                        \
-        do {                                                                                      \
-            if (scale) NAE_KLAUNCH(ctx, #K, (K<true>), grid, block, 0, ctx->stream, __VA_ARGS__);   \
-            else NAE_KLAUNCH(ctx, #K, (K<false>), grid, block, 0, ctx->stream, __VA_ARGS__);        \
-        } while (0)
-        switch (mode) {
-        case kI2P: NAE_LAUNCH(copy_i2p_kernel, ss, dd, (long long)S, volume); break;
-        case kP2I: NAE_LAUNCH(copy_p2i_kernel, ss, dd, (long long)S, volume); break;
-        case kFlat: NAE_LAUNCH(copy_flat_kernel, ss, dd, flat, volume); break;
-        default: NAE_LAUNCH(copy_generic_kernel, ss, dd, (long long)S, ch, volume); break;
-        }
-#undef NAE_LAUNCH
-        int rc = nae_check(ctx, hipGetLastError(), "copy_sig kernel");
-        if (rc) return rc;
-    }
-    return NAE_OK;
+    const long long flat = (long long)S * ch;
+    return for_stream_slices(n_streams, 1, [&](size_t s0, size_t ns) {
+        const SigViewD ss = at_stream(s, s0);
+        const OutViewD dd = at_stream(d, s0);
+        const dim3 grid(grid_for(mode == kGeneric ? (size_t)flat : (size_t)flat / 4 + 1, ns), (unsigned)ns), block(kBlock);
+        return with_flags(scale, [&](auto sc) {
+            switch (mode) {
+            case kI2P: return nae_launch_grid(ctx, "copy_i2p_kernel", copy_i2p_kernel<sc.value>, grid, block, 0, ss, dd, (long long)S, volume);
+            case kP2I: return nae_launch_grid(ctx, "copy_p2i_kernel", copy_p2i_kernel<sc.value>, grid, block, 0, ss, dd, (long long)S, volume);
+            case kFlat: return nae_launch_grid(ctx, "copy_flat_kernel", copy_flat_kernel<sc.value>, grid, block, 0, ss, dd, flat, volume);
+            default: return nae_launch_grid(ctx, "copy_generic_kernel", copy_generic_kernel<sc.value>, grid, block, 0, ss, dd, (long long)S, ch, volume);
+            }
+        });
+    });
 }
 
 namespace nae {
@@ -285,6 +278,11 @@ __global__ __launch_bounds__(kBlock) void amix_planes_kernel(MixPlanes a, float*
 }
 
 struct MixSigs { const float* base[16]; long long ss[16], cs[16], fs[16]; float vol[16]; int n; };
+inline MixSigs at_stream(MixSigs a, size_t s0)
+{
+    for (int i = 0; i < a.n; i++) a.base[i] += (long long)s0 * a.ss[i];
+    return a;
+}
 
 // fast path: every input interleaved stereo, output planar; 4 sample-frames per thread
 __global__ __launch_bounds__(kBlock) void amix_i2p_kernel(MixSigs a, OutViewD out, long long S)
@@ -491,17 +489,11 @@ int nae_fill_uniform_f32(nae_ctx* ctx, float* dst, size_t n_per_stream, size_t s
 {
     if (!ctx || !dst) return NAE_ERR_INVALID;
     if (n_per_stream == 0 || n_streams == 0) return NAE_OK;
-    for (size_t s0 = 0; s0 < n_streams; s0 += 65535) {
-        const unsigned ns = (unsigned)((n_streams - s0 < 65535) ? n_streams - s0 : 65535);
-        unsigned gx = grid_for(n_per_stream);
-        if ((size_t)gx * ns > (size_t)kMaxGrid * 4) { gx = (unsigned)(((size_t)kMaxGrid * 4 + ns - 1) / ns); if (gx == 0) gx = 1; }
-        NAE_KLAUNCH(ctx, "fill_uniform_kernel", fill_uniform_kernel, dim3(gx, ns), dim3(kBlock), 0, ctx->stream,
-                    dst + s0 * stream_stride, n_per_stream, stream_stride, (unsigned long long)(first_stream + s0),
-                    (unsigned long long)input_index);
-        int rc = nae_check(ctx, hipGetLastError(), "fill_uniform_kernel");
-        if (rc) return rc;
-    }
-    return NAE_OK;
+    return for_stream_slices(n_streams, 1, [&](size_t s0, size_t ns) {
+        return nae_launch_grid(ctx, "fill_uniform_kernel", fill_uniform_kernel, dim3(grid_for(n_per_stream, ns), (unsigned)ns), dim3(kBlock), 0,
+                               dst + s0 * stream_stride, n_per_stream, stream_stride, (unsigned long long)(first_stream + s0),
+                               (unsigned long long)input_index);
+    });
 }
 
 // test utility: number of 32-bit words that differ between two device buffers, added to *d_count (full-size parity tests
@@ -570,8 +562,7 @@ int nae_mono_to_stereo_f32(nae_ctx* ctx, const float* mono, float* dst, size_t S
     if (!ctx || !mono || !dst) return NAE_ERR_INVALID;
     if (S == 0) return NAE_OK;
     if (reinterpret_cast<uintptr_t>(dst) & 7) return nae_fail(ctx, NAE_ERR_INVALID, "dst must be 8-byte aligned");
-    NAE_KLAUNCH(ctx, "mono_to_stereo_kernel", mono_to_stereo_kernel, dim3(grid_for(S)), dim3(kBlock), 0, ctx->stream, mono, dst, S, gain);
-    return nae_check(ctx, hipGetLastError(), "mono_to_stereo_kernel");
+    return nae_launch_grid(ctx, "mono_to_stereo_kernel", mono_to_stereo_kernel, dim3(grid_for(S)), dim3(kBlock), 0, mono, dst, S, gain);
 }
 
 int nae_clamp_f32(nae_ctx* ctx, float* data, size_t n)
@@ -636,8 +627,7 @@ int nae_amix_f32(nae_ctx* ctx, const float* const* inL, const float* const* inR,
         a.inL[i] = inL[i]; a.inR[i] = inR[i]; a.vol[i] = vol[i];
         vec = vec && aligned16(inL[i]) && aligned16(inR[i]);
     }
-    NAE_KLAUNCH(ctx, "amix_planes_kernel", amix_planes_kernel, dim3(grid_for(vec ? S / 4 + 4 : S)), dim3(kBlock), 0, ctx->stream, a, outL, outR, S, vec);
-    return nae_check(ctx, hipGetLastError(), "amix_planes_kernel");
+    return nae_launch_grid(ctx, "amix_planes_kernel", amix_planes_kernel, dim3(grid_for(vec ? S / 4 + 4 : S)), dim3(kBlock), 0, a, outL, outR, S, vec);
 }
 
 int nae_amix_sig_f32(nae_ctx* ctx, const nae_sig* inputs, const float* vol, int n, const nae_sig* out, size_t S,
@@ -657,20 +647,12 @@ int nae_amix_sig_f32(nae_ctx* ctx, const nae_sig* inputs, const float* vol, int 
         fast = fast && is_interleaved(&inputs[i], 2) && view_aligned(&inputs[i], 0);
     }
     const OutViewD o = to_out(out);
-    for (size_t s0 = 0; s0 < n_streams; s0 += 65535) {
-        const unsigned ns = (unsigned)((n_streams - s0 < 65535) ? n_streams - s0 : 65535);
-        MixSigs aa = a;
-        for (int i = 0; i < n; i++) aa.base[i] += (long long)s0 * aa.ss[i];
-        OutViewD oo = o;
-        oo.base += (long long)s0 * oo.ss;
-        unsigned gx = grid_for(fast ? S / 4 + 1 : 2 * S);
-        if ((size_t)gx * ns > (size_t)kMaxGrid * 4) { gx = (unsigned)(((size_t)kMaxGrid * 4 + ns - 1) / ns); if (gx == 0) gx = 1; }
-        if (fast) NAE_KLAUNCH(ctx, "amix_i2p_kernel", amix_i2p_kernel, dim3(gx, ns), dim3(kBlock), 0, ctx->stream, aa, oo, (long long)S);
-        else NAE_KLAUNCH(ctx, "amix_generic_kernel", amix_generic_kernel, dim3(gx, ns), dim3(kBlock), 0, ctx->stream, aa, oo, (long long)S);
-        int rc = nae_check(ctx, hipGetLastError(), "amix_sig kernel");
-        if (rc) return rc;
-    }
-    return NAE_OK;
+    return for_stream_slices(n_streams, 1, [&](size_t s0, size_t ns) {
+        const dim3 grid(grid_for(fast ? S / 4 + 1 : 2 * S, ns), (unsigned)ns);
+        return fast ? nae_launch_grid(ctx, "amix_i2p_kernel", amix_i2p_kernel, grid, dim3(kBlock), 0, at_stream(a, s0), at_stream(o, s0), (long long)S)
+                    : nae_launch_grid(ctx, "amix_generic_kernel", amix_generic_kernel, grid, dim3(kBlock), 0, at_stream(a, s0), at_stream(o, s0),
+                                      (long long)S);
+    });
 }
 
 int nae_bimix_f32(nae_ctx* ctx, const float* ll, const float* lr, const float* rl, const float* rr, float bias,
@@ -680,9 +662,8 @@ int nae_bimix_f32(nae_ctx* ctx, const float* ll, const float* lr, const float* r
     if (S == 0) return NAE_OK;
     const float bias_minus = (1 - bias), bias_plus = (1 + bias); // audio-bimix.cpp:310-311
     const bool vec = aligned16(ll) && aligned16(lr) && aligned16(rl) && aligned16(rr) && aligned16(outL) && aligned16(outR);
-    NAE_KLAUNCH(ctx, "bimix_kernel", bimix_kernel, dim3(grid_for(vec ? S / 4 + 4 : S)), dim3(kBlock), 0, ctx->stream, ll, lr, rl, rr,
-                       bias_minus, bias_plus, outL, outR, S, vec);
-    return nae_check(ctx, hipGetLastError(), "bimix_kernel");
+    return nae_launch_grid(ctx, "bimix_kernel", bimix_kernel, dim3(grid_for(vec ? S / 4 + 4 : S)), dim3(kBlock), 0, ll, lr, rl, rr, bias_minus,
+                           bias_plus, outL, outR, S, vec);
 }
 
 int nae_bimix2_downmix_f32(nae_ctx* ctx, const float* l, const float* r, float* mono, size_t S)
@@ -690,8 +671,7 @@ int nae_bimix2_downmix_f32(nae_ctx* ctx, const float* l, const float* r, float* 
     if (!ctx || !l || !r || !mono) return NAE_ERR_INVALID;
     if (S == 0) return NAE_OK;
     const bool vec = aligned16(l) && aligned16(r) && aligned16(mono);
-    NAE_KLAUNCH(ctx, "downmix_kernel", downmix_kernel, dim3(grid_for(vec ? S / 4 + 4 : S)), dim3(kBlock), 0, ctx->stream, l, r, mono, S, vec);
-    return nae_check(ctx, hipGetLastError(), "downmix_kernel");
+    return nae_launch_grid(ctx, "downmix_kernel", downmix_kernel, dim3(grid_for(vec ? S / 4 + 4 : S)), dim3(kBlock), 0, l, r, mono, S, vec);
 }
 
 int nae_bimix2_interleave_f32(nae_ctx* ctx, float* dst, const float* earlier, const float* later, size_t unaligned,
@@ -702,9 +682,8 @@ int nae_bimix2_interleave_f32(nae_ctx* ctx, float* dst, const float* earlier, co
     if (earlier_offset != 0 && earlier_offset != 1) return nae_fail(ctx, NAE_ERR_INVALID, "earlier_offset must be 0 or 1");
     if (unaligned + aligned == 0) return NAE_OK;
     if (reinterpret_cast<uintptr_t>(dst) & 7) return nae_fail(ctx, NAE_ERR_INVALID, "dst must be 8-byte aligned");
-    NAE_KLAUNCH(ctx, "bimix2_interleave_kernel", bimix2_interleave_kernel, dim3(grid_for(unaligned + aligned)), dim3(kBlock), 0, ctx->stream, dst,
-                       earlier, later ? later : earlier, unaligned, aligned, earlier_offset);
-    return nae_check(ctx, hipGetLastError(), "bimix2_interleave_kernel");
+    return nae_launch_grid(ctx, "bimix2_interleave_kernel", bimix2_interleave_kernel, dim3(grid_for(unaligned + aligned)), dim3(kBlock), 0, dst,
+                           earlier, later ? later : earlier, unaligned, aligned, earlier_offset);
 }
 
 int nae_to_f32_interleaved(nae_ctx* ctx, int fmt, const void* const* planes, size_t S, int ch, float* dst)
@@ -718,17 +697,9 @@ int nae_to_f32_interleaved(nae_ctx* ctx, int fmt, const void* const* planes, siz
         pl.p[c] = planes[c];
     }
     if (S == 0) return NAE_OK;
-    const dim3 grid(grid_for(S * ch)), block(kBlock);
-    switch (fmt) {
-    case NAE_FMT_FLT: NAE_KLAUNCH(ctx, "to_f32_kernel", (to_f32_kernel<NAE_FMT_FLT>), grid, block, 0, ctx->stream, pl, S, ch, dst); break;
-    case NAE_FMT_FLTP: NAE_KLAUNCH(ctx, "to_f32_kernel", (to_f32_kernel<NAE_FMT_FLTP>), grid, block, 0, ctx->stream, pl, S, ch, dst); break;
-    case NAE_FMT_S16: NAE_KLAUNCH(ctx, "to_f32_kernel", (to_f32_kernel<NAE_FMT_S16>), grid, block, 0, ctx->stream, pl, S, ch, dst); break;
-    case NAE_FMT_S16P: NAE_KLAUNCH(ctx, "to_f32_kernel", (to_f32_kernel<NAE_FMT_S16P>), grid, block, 0, ctx->stream, pl, S, ch, dst); break;
-    case NAE_FMT_S32: NAE_KLAUNCH(ctx, "to_f32_kernel", (to_f32_kernel<NAE_FMT_S32>), grid, block, 0, ctx->stream, pl, S, ch, dst); break;
-    case NAE_FMT_S32P: NAE_KLAUNCH(ctx, "to_f32_kernel", (to_f32_kernel<NAE_FMT_S32P>), grid, block, 0, ctx->stream, pl, S, ch, dst); break;
-    default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "Unsupported sample format"); // audio-velocity.cpp:223-228
-    }
-    return nae_check(ctx, hipGetLastError(), "to_f32_kernel");
+    return at_format(ctx, fmt, [&](auto f) {
+        return nae_launch_grid(ctx, "to_f32_kernel", to_f32_kernel<f.value>, dim3(grid_for(S * ch)), dim3(kBlock), 0, pl, S, ch, dst);
+    });
 }
 
 } // extern "C"

@@ -414,34 +414,33 @@ int nae_spec_any_tables(nae_ctx* ctx, int n_fft, SpecAnyTables* tb)
 }
 
 template <int N, int kLoad>
-static void launch_any_as(nae_ctx* ctx, const SigViewD& v, int ch, long long hop, long long F, long long n_groups, long long items,
-                          float* dst, size_t dst_stream_stride, const SpecAnyTables& tb)
+static int launch_any_as(nae_ctx* ctx, const SigViewD& v, int ch, long long hop, long long F, long long n_groups, long long items,
+                         float* dst, size_t dst_stream_stride, const SpecAnyTables& tb)
 {
     // one item per wave (measured faster than waves walking items from a grid of 8 workgroups per CU: profiles/r07_spec_sizes.md);
     // a launch holds at most 2^22 workgroups (grid x block < 2^32 work-items), longer jobs take several
     constexpr long long kMaxItems = (1ll << 22) * kAnyWaves;
     for (long long item0 = 0; item0 < items; item0 += kMaxItems) {
         const long long n = items - item0 < kMaxItems ? items - item0 : kMaxItems;
-        const unsigned grid = (unsigned)((n + kAnyWaves - 1) / kAnyWaves);
-        NAE_KLAUNCH(ctx, "spectrum_any_kernel", (spectrum_any_kernel<N, kLoad>), dim3(grid), dim3(kAnyThreads), 0, ctx->stream, v, ch,
-                    hop, F, n_groups, item0, items, dst, (long long)dst_stream_stride, tb);
+        const int rc = nae_launch_tiles(ctx, "spectrum_any_kernel", "spectrum_any_kernel: grid too large", spectrum_any_kernel<N, kLoad>, n, kAnyWaves,
+                                        kAnyThreads, 0, v, ch, hop, F, n_groups, item0, items, dst, (long long)dst_stream_stride, tb);
+        if (rc) return rc;
     }
+    return NAE_OK;
 }
 
 template <int N>
-static void launch_any(nae_ctx* ctx, const nae_sig* src, int ch, long long hop, long long F, size_t n_streams, float* dst,
-                       size_t dst_stream_stride, const SpecAnyTables& tb)
+static int launch_any(nae_ctx* ctx, const nae_sig* src, int ch, long long hop, long long F, size_t n_streams, float* dst,
+                      size_t dst_stream_stride, const SpecAnyTables& tb)
 {
     constexpr int G = SpecGeom<N>::G;
     const long long n_groups = (F + G - 1) / G;
     const long long items = n_groups * (long long)n_streams * ch;
     const SigViewD v = to_view(src);
-    if (src->frame_stride == 1)
-        launch_any_as<N, kLoadUnit>(ctx, v, ch, hop, F, n_groups, items, dst, dst_stream_stride, tb);
-    else if ((unsigned long long)src->frame_stride * N < (1ull << 31))
-        launch_any_as<N, kLoadStride32>(ctx, v, ch, hop, F, n_groups, items, dst, dst_stream_stride, tb);
-    else
-        launch_any_as<N, kLoadStride64>(ctx, v, ch, hop, F, n_groups, items, dst, dst_stream_stride, tb);
+    if (src->frame_stride == 1) return launch_any_as<N, kLoadUnit>(ctx, v, ch, hop, F, n_groups, items, dst, dst_stream_stride, tb);
+    if ((unsigned long long)src->frame_stride * N < (1ull << 31))
+        return launch_any_as<N, kLoadStride32>(ctx, v, ch, hop, F, n_groups, items, dst, dst_stream_stride, tb);
+    return launch_any_as<N, kLoadStride64>(ctx, v, ch, hop, F, n_groups, items, dst, dst_stream_stride, tb);
 }
 
 } // namespace nae
@@ -470,18 +469,11 @@ int nae_launch_spectrum(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, si
         SpecAnyTables tb;
         const int rc = nae_spec_any_tables(ctx, n_fft, &tb);
         if (rc) return rc;
-        switch (n_fft) {
-        case 256: launch_any<256>(ctx, src, ch, hop, (long long)F, n_streams, dst, dst_stream_stride, tb); break;
-        case 512: launch_any<512>(ctx, src, ch, hop, (long long)F, n_streams, dst, dst_stream_stride, tb); break;
-        case 1024: launch_any<1024>(ctx, src, ch, hop, (long long)F, n_streams, dst, dst_stream_stride, tb); break;
-        case 2048: launch_any<2048>(ctx, src, ch, hop, (long long)F, n_streams, dst, dst_stream_stride, tb); break;
-        case 4096: launch_any<4096>(ctx, src, ch, hop, (long long)F, n_streams, dst, dst_stream_stride, tb); break;
-        default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "spectrum: n_fft must be a power of two in [256, 4096]");   // (callers check first)
-        }
-        return nae_check(ctx, hipGetLastError(), "spectrum_any_kernel");
+        return pick_value<256, 512, 1024, 2048, 4096>(ctx, n_fft, "spectrum: n_fft must be a power of two in [256, 4096]", [&](auto n) {   // (callers check first)
+            return launch_any<decltype(n)::value>(ctx, src, ch, hop, (long long)F, n_streams, dst, dst_stream_stride, tb);
+        });
     }
     const long long items = (long long)(F * n_streams);
-    const unsigned grid = (unsigned)((items + kWaves - 1) / kWaves);
     Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
     const bool stereo_fast = ch == 2 && src->chan_stride == 1 && src->frame_stride == 2 && src->stream_stride % 4 == 0 &&
                              (reinterpret_cast<uintptr_t>(src->base) & 15) == 0 && !ctx->dbg_spec_generic;
@@ -523,20 +515,14 @@ int nae_launch_spectrum(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, si
             if (e != hipSuccess) return nae_check(ctx, e, "hipMemsetAsync(spectrum work counter)");
         }
         const bool wide = (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && dst_stream_stride % 2 == 0 && !ctx->dbg_spec_narrow;
-        if (wide)
-            NAE_KLAUNCH(ctx, "spectrum_stereo_kernel", spectrum_stereo_kernel<true>, dim3((unsigned)groups), dim3(kThreads),
-                        kLdsSpec, ctx->stream, static_cast<const float*>(src->base), (long long)src->stream_stride,
-                        (long long)F, w, dst, (long long)dst_stream_stride, tb);
-        else
-            NAE_KLAUNCH(ctx, "spectrum_stereo_kernel", spectrum_stereo_kernel<false>, dim3((unsigned)groups), dim3(kThreads),
-                        kLdsSpec, ctx->stream, static_cast<const float*>(src->base), (long long)src->stream_stride,
-                        (long long)F, w, dst, (long long)dst_stream_stride, tb);
+        return with_flags(wide, [&](auto wd) {
+            return nae_launch_grid(ctx, "spectrum_stereo_kernel", spectrum_stereo_kernel<wd.value>, dim3((unsigned)groups), dim3(kThreads), kLdsSpec,
+                                   static_cast<const float*>(src->base), (long long)src->stream_stride, (long long)F, w, dst,
+                                   (long long)dst_stream_stride, tb);
+        });
     }
-    else if (src->frame_stride == 1)
-        NAE_KLAUNCH(ctx, "spectrum_kernel", (spectrum_kernel<true>), dim3(grid), dim3(kThreads), kLdsSpec, ctx->stream, to_view(src),
-                    (long long)T, ch, (long long)F, items, dst, (long long)dst_stream_stride, tb);
-    else
-        NAE_KLAUNCH(ctx, "spectrum_kernel", (spectrum_kernel<false>), dim3(grid), dim3(kThreads), kLdsSpec, ctx->stream, to_view(src),
-                    (long long)T, ch, (long long)F, items, dst, (long long)dst_stream_stride, tb);
-    return nae_check(ctx, hipGetLastError(), "spectrum_kernel");
+    return with_flags(src->frame_stride == 1, [&](auto unit) {
+        return nae_launch_tiles(ctx, "spectrum_kernel", "spectrum_kernel: grid too large", spectrum_kernel<unit.value>, items, kWaves, kThreads,
+                                kLdsSpec, to_view(src), (long long)T, ch, (long long)F, items, dst, (long long)dst_stream_stride, tb);
+    });
 }

@@ -17,7 +17,7 @@
 //   st_cu_kernel   4-point cubic read at host-tabulated positions (the position accumulator is a sequential
 //                  double recurrence that does not depend on the audio: st_chain.h).
 #include "st_chain.h"
-#include <type_traits>
+#include "launch.h"
 
 namespace nae {
 
@@ -55,6 +55,18 @@ __device__ __forceinline__ void st_frame(const DOut& d, float* obase, long long 
     }
 }
 
+// the four Catmull-Rom weights at fraction fr, in the library's expression order (the order is observable: results are compared bit for bit)
+__device__ __forceinline__ void cubic_weights(float fr, float& y0, float& y1, float& y2, float& y3)
+{
+    const float x2 = fr, x1 = x2 * x2, x0 = x1 * x2, x3 = 1.0f;
+    y0 = ((-0.5f * x0 + 1.0f * x1) + -0.5f * x2) + 0.0f * x3;
+    y1 = ((1.5f * x0 + -2.5f * x1) + 0.0f * x2) + 1.0f * x3;
+    y2 = ((-1.5f * x0 + 2.0f * x1) + 0.5f * x2) + 0.0f * x3;
+    y3 = ((0.5f * x0 + -0.5f * x1) + 0.0f * x2) + 0.0f * x3;
+}
+
+inline StView at_stream(StView v, size_t s0) { v.base += (long long)s0 * v.ss; return v; }
+inline StOut at_stream(StOut o, size_t s0) { o.base += (long long)s0 * o.ss; return o; }
 static DView dview(const StView& v, int ch)
 {
     const bool vec = ch == 2 && v.cs == 1 && v.fs == 2 && (reinterpret_cast<uintptr_t>(v.base) & 7) == 0 && (v.ss & 1) == 0;
@@ -459,13 +471,17 @@ int st_launch_td(nae_ctx* ctx, const StCfg& c, const StView& in, const TdRange& 
     const size_t lds = ((size_t)(nc >= 4 ? 2 : 1) * rows * p.S * c.ch + (size_t)c.ovl * c.ch + 16 + 2 * (size_t)c.ovl) * sizeof(float);
     if (lds > 60 * 1024) return nae_fail(ctx, NAE_ERR_INVALID, "WSOLA window does not fit LDS");
     const dim3 grid((unsigned)n_streams);
-#define NAE_TD(CHN, NCN) NAE_KLAUNCH(ctx, "st_td_kernel", (st_td_kernel<CHN, NCN>), grid, dim3(td_threads(NCN)), lds, ctx->stream, \
-                                     dview(in, CHN), p, dout(out, CHN), mid_state, offs_dbg, offs_stride)
-    if (c.ch == 2 && nc == 4 && p.S == 180) NAE_KLAUNCH(ctx, "st_td_kernel", (st_td_kernel<2, 4, 180>), grid, dim3(256), lds, ctx->stream, dview(in, 2), p, dout(out, 2), mid_state, offs_dbg, offs_stride);
-    else if (c.ch == 2) { if (nc == 4) NAE_TD(2, 4); else if (nc == 2) NAE_TD(2, 2); else NAE_TD(2, 1); }
-    else { if (nc == 4) NAE_TD(1, 4); else if (nc == 2) NAE_TD(1, 2); else NAE_TD(1, 1); }
-#undef NAE_TD
-    return nae_check(ctx, hipGetLastError(), "st_td_kernel");
+    auto launch = [&](auto kernel, auto chn, int threads) {
+        return nae_launch_grid(ctx, "st_td_kernel", kernel, grid, dim3(threads), lds, dview(in, chn.value), p, dout(out, chn.value), mid_state,
+                               offs_dbg, offs_stride);
+    };
+    // the row stride as a compile-time value (KS) for the stereo 48-kHz geometry
+    if (c.ch == 2 && nc == 4 && p.S == 180) return launch(st_td_kernel<2, 4, 180>, std::integral_constant<int, 2>(), 256);
+    return with_channels(c.ch, [&](auto chn) {
+        return pick_value<1, 2, 4>(ctx, nc, "WSOLA: 1, 2 or 4 candidates per thread", [&](auto ncn) {
+            return launch(st_td_kernel<decltype(chn)::value, decltype(ncn)::value>, chn, td_threads(decltype(ncn)::value));
+        });
+    });
 }
 
 // ------------------------------------------------------------------ AA: 64-tap FIR
@@ -510,11 +526,8 @@ __global__ __launch_bounds__(256, 8) void st_aa_kernel(DView in, AaParams p, DOu
             for (int c = 0; c < CH; c++) x.x[c] = 0.0f;
             if (n < cu.n_limit) {
                 const long long a = cu.pos[n];
-                const float x2 = cu.fr[n], x1 = x2 * x2, x0 = x1 * x2, x3 = 1.0f;
-                const float y0 = ((-0.5f * x0 + 1.0f * x1) + -0.5f * x2) + 0.0f * x3;
-                const float y1 = ((1.5f * x0 + -2.5f * x1) + 0.0f * x2) + 1.0f * x3;
-                const float y2 = ((-1.5f * x0 + 2.0f * x1) + 0.5f * x2) + 0.0f * x3;
-                const float y3 = ((0.5f * x0 + -0.5f * x1) + 0.0f * x2) + 0.0f * x3;
+                float y0, y1, y2, y3;
+                cubic_weights(cu.fr[n], y0, y1, y2, y3);
                 const Frame<CH> p0 = ld_frame<CH>(in, sbase, a), p1 = ld_frame<CH>(in, sbase, a + 1);
                 const Frame<CH> p2 = ld_frame<CH>(in, sbase, a + 2), p3 = ld_frame<CH>(in, sbase, a + 3);
 #pragma unroll
@@ -608,11 +621,8 @@ __global__ __launch_bounds__(256, 8) void st_aa_kernel(DView in, AaParams p, DOu
     if (n_hi > cu.n_limit) n_hi = cu.n_limit;
     for (long long n = n_lo + tid; n < n_hi; n += 256) {
         const int a = (int)(cu.pos[n] - jt);              // 0 <= a and a + 3 < 1024 by construction of tile_n
-        const float x2 = cu.fr[n], x1 = x2 * x2, x0 = x1 * x2, x3 = 1.0f;
-        const float y0 = ((-0.5f * x0 + 1.0f * x1) + -0.5f * x2) + 0.0f * x3;
-        const float y1 = ((1.5f * x0 + -2.5f * x1) + 0.0f * x2) + 1.0f * x3;
-        const float y2 = ((-1.5f * x0 + 2.0f * x1) + 0.5f * x2) + 0.0f * x3;
-        const float y3 = ((0.5f * x0 + -0.5f * x1) + 0.0f * x2) + 0.0f * x3;
+        float y0, y1, y2, y3;
+        cubic_weights(cu.fr[n], y0, y1, y2, y3);
         Frame<CH> o;
 #pragma unroll
         for (int c = 0; c < CH; c++)
@@ -621,28 +631,29 @@ __global__ __launch_bounds__(256, 8) void st_aa_kernel(DView in, AaParams p, DOu
     }
 }
 
+// the one body of the three filter launchers: `tiles` workgroups per stream filter outputs [j0, j1) with the cubic stage `cu` behind the filter
+// (kCubic), in front of it (kCubicIn) or absent
+template <bool kCubic, bool kCubicIn>
+static int launch_aa(nae_ctx* ctx, const StCfg& c, const StView& in, long long j0, long long j1, const CuFuse& cu, unsigned tiles, const StOut& out,
+                     size_t n_streams)
+{
+    AaParams p;
+    for (int k = 0; k < kAaLen; k++) p.h[k] = c.aa[k];
+    p.j0 = j0; p.j1 = j1;
+    return for_stream_slices(n_streams, 1, [&](size_t s0, size_t ns) {
+        return with_channels(c.ch, [&](auto chn) {
+            constexpr int CH = decltype(chn)::value;
+            return nae_launch_grid(ctx, "st_aa_kernel", st_aa_kernel<CH, kCubic, kCubicIn>, dim3(tiles, (unsigned)ns), dim3(256), 0,
+                                   dview(at_stream(in, s0), CH), p, dout(at_stream(out, s0), CH), cu);
+        });
+    });
+}
+
 int st_launch_aa(nae_ctx* ctx, const StCfg& c, const StView& in, long long j0, long long j1, const StOut& out,
                  size_t n_streams)
 {
     if (j1 <= j0 || n_streams == 0) return NAE_OK;
-    AaParams p;
-    for (int k = 0; k < kAaLen; k++) p.h[k] = c.aa[k];
-    p.j0 = j0; p.j1 = j1;
-    const unsigned tiles = (unsigned)((j1 - j0 + kAaTile - 1) / kAaTile);
-    for (size_t s0 = 0; s0 < n_streams; s0 += 65535) {
-        const unsigned ns = (unsigned)((n_streams - s0 < 65535) ? n_streams - s0 : 65535);
-        StView vin = in;
-        vin.base += (long long)s0 * in.ss;
-        StOut vout = out;
-        vout.base += (long long)s0 * out.ss;
-        if (c.ch == 2)
-            NAE_KLAUNCH(ctx, "st_aa_kernel", (st_aa_kernel<2, false>), dim3(tiles, ns), dim3(256), 0, ctx->stream, dview(vin, 2), p,
-                        dout(vout, 2), CuFuse{});
-        else
-            NAE_KLAUNCH(ctx, "st_aa_kernel", (st_aa_kernel<1, false>), dim3(tiles, ns), dim3(256), 0, ctx->stream, dview(vin, 1), p,
-                        dout(vout, 1), CuFuse{});
-    }
-    return nae_check(ctx, hipGetLastError(), "st_aa_kernel");
+    return launch_aa<false, false>(ctx, c, in, j0, j1, CuFuse{}, (unsigned)((j1 - j0 + kAaTile - 1) / kAaTile), out, n_streams);
 }
 
 // filter + cubic in one launch: cubic outputs [0, n_limit) of every stream from filter input `in`; d_tile_n has tiles + 1
@@ -651,24 +662,7 @@ int st_launch_aa_cu(nae_ctx* ctx, const StCfg& c, const StView& in, const long l
                     size_t tiles, long long n_limit, const StOut& out, size_t n_streams)
 {
     if (tiles == 0 || n_limit <= 0 || n_streams == 0) return NAE_OK;
-    AaParams p;
-    for (int k = 0; k < kAaLen; k++) p.h[k] = c.aa[k];
-    p.j0 = 0; p.j1 = 0;
-    const CuFuse cu{d_pos, d_fract, d_tile_n, n_limit};
-    for (size_t s0 = 0; s0 < n_streams; s0 += 65535) {
-        const unsigned ns = (unsigned)((n_streams - s0 < 65535) ? n_streams - s0 : 65535);
-        StView vin = in;
-        vin.base += (long long)s0 * in.ss;
-        StOut vout = out;
-        vout.base += (long long)s0 * out.ss;
-        if (c.ch == 2)
-            NAE_KLAUNCH(ctx, "st_aa_kernel", (st_aa_kernel<2, true>), dim3((unsigned)tiles, ns), dim3(256), 0, ctx->stream,
-                        dview(vin, 2), p, dout(vout, 2), cu);
-        else
-            NAE_KLAUNCH(ctx, "st_aa_kernel", (st_aa_kernel<1, true>), dim3((unsigned)tiles, ns), dim3(256), 0, ctx->stream,
-                        dview(vin, 1), p, dout(vout, 1), cu);
-    }
-    return nae_check(ctx, hipGetLastError(), "st_aa_cu_kernel");
+    return launch_aa<true, false>(ctx, c, in, 0, 0, CuFuse{d_pos, d_fract, d_tile_n, n_limit}, (unsigned)tiles, out, n_streams);
 }
 
 // cubic + filter in one launch (rate < 1): filter outputs [0, j1) of every stream; the filter's input frame n is the
@@ -677,25 +671,7 @@ int st_launch_cu_aa(nae_ctx* ctx, const StCfg& c, const StView& in, const long l
                     long long j1, const StOut& out, size_t n_streams)
 {
     if (j1 <= 0 || n_streams == 0) return NAE_OK;
-    AaParams p;
-    for (int k = 0; k < kAaLen; k++) p.h[k] = c.aa[k];
-    p.j0 = 0; p.j1 = j1;
-    const CuFuse cu{d_pos, d_fract, nullptr, n_cu};
-    const unsigned tiles = (unsigned)((j1 + kAaTile - 1) / kAaTile);
-    for (size_t s0 = 0; s0 < n_streams; s0 += 65535) {
-        const unsigned ns = (unsigned)((n_streams - s0 < 65535) ? n_streams - s0 : 65535);
-        StView vin = in;
-        vin.base += (long long)s0 * in.ss;
-        StOut vout = out;
-        vout.base += (long long)s0 * out.ss;
-        if (c.ch == 2)
-            NAE_KLAUNCH(ctx, "st_aa_kernel", (st_aa_kernel<2, false, true>), dim3(tiles, ns), dim3(256), 0, ctx->stream, dview(vin, 2),
-                        p, dout(vout, 2), cu);
-        else
-            NAE_KLAUNCH(ctx, "st_aa_kernel", (st_aa_kernel<1, false, true>), dim3(tiles, ns), dim3(256), 0, ctx->stream, dview(vin, 1),
-                        p, dout(vout, 1), cu);
-    }
-    return nae_check(ctx, hipGetLastError(), "st_cu_aa_kernel");
+    return launch_aa<false, true>(ctx, c, in, 0, j1, CuFuse{d_pos, d_fract, nullptr, n_cu}, (unsigned)((j1 + kAaTile - 1) / kAaTile), out, n_streams);
 }
 
 // (position, fraction) of `count` consecutive cubic outputs, continued on the device from the state (pos0, fract0):
@@ -721,8 +697,7 @@ __global__ void st_cu_table_kernel(long long pos0, double fract0, double rate, l
 int st_launch_cu_table(nae_ctx* ctx, long long pos0, double fract0, double rate, long long count, long long* d_pos, float* d_fract)
 {
     if (count <= 0) return NAE_OK;
-    NAE_KLAUNCH(ctx, "st_cu_table_kernel", st_cu_table_kernel, dim3(1), dim3(64), 0, ctx->stream, pos0, fract0, rate, count, d_pos, d_fract);
-    return nae_check(ctx, hipGetLastError(), "st_cu_table_kernel");
+    return nae_launch_grid(ctx, "st_cu_table_kernel", st_cu_table_kernel, dim3(1), dim3(64), 0, pos0, fract0, rate, count, d_pos, d_fract);
 }
 
 // first cubic output of every fused tile: tile t covers filter outputs [1021 t, 1021 t + 1024)
@@ -756,11 +731,8 @@ __global__ __launch_bounds__(256) void st_cu_kernel(DView in, const long long* _
     const long long n = n0 + (long long)(blockIdx.x % blocks) * 256 + threadIdx.x;
     if (n >= n1) return;
     const long long a = pos[n - tab_origin];
-    const float x2 = fr[n - tab_origin], x1 = x2 * x2, x0 = x1 * x2, x3 = 1.0f;
-    const float y0 = ((-0.5f * x0 + 1.0f * x1) + -0.5f * x2) + 0.0f * x3;
-    const float y1 = ((1.5f * x0 + -2.5f * x1) + 0.0f * x2) + 1.0f * x3;
-    const float y2 = ((-1.5f * x0 + 2.0f * x1) + 0.5f * x2) + 0.0f * x3;
-    const float y3 = ((0.5f * x0 + -0.5f * x1) + 0.0f * x2) + 0.0f * x3;
+    float y0, y1, y2, y3;
+    cubic_weights(fr[n - tab_origin], y0, y1, y2, y3);
     Frame<CH> p0[kCuGroup], p1[kCuGroup], p2[kCuGroup], p3[kCuGroup];
 #pragma unroll
     for (int k = 0; k < kCuGroup; k++) {
@@ -794,19 +766,15 @@ int st_launch_cu(nae_ctx* ctx, const StCfg& c, const StView& in, const long long
     const size_t max_ns = max_groups * kCuGroup;
     for (size_t s0 = 0; s0 < n_streams; s0 += max_ns) {
         const size_t ns = (n_streams - s0 < max_ns) ? n_streams - s0 : max_ns;
-        StView vin = in;
-        vin.base += (long long)s0 * in.ss;
-        StOut vout = out;
-        vout.base += (long long)s0 * out.ss;
         const unsigned grid = (unsigned)(blocks * ((ns + kCuGroup - 1) / kCuGroup));
-        if (c.ch == 2)
-            NAE_KLAUNCH(ctx, "st_cu_kernel", (st_cu_kernel<2>), dim3(grid), dim3(256), 0, ctx->stream, dview(vin, 2), d_pos, d_fract,
-                        tab_origin, n0, n1, dout(vout, 2), (long long)ns, (unsigned)blocks);
-        else
-            NAE_KLAUNCH(ctx, "st_cu_kernel", (st_cu_kernel<1>), dim3(grid), dim3(256), 0, ctx->stream, dview(vin, 1), d_pos, d_fract,
-                        tab_origin, n0, n1, dout(vout, 1), (long long)ns, (unsigned)blocks);
+        const int rc = with_channels(c.ch, [&](auto chn) {
+            constexpr int CH = decltype(chn)::value;
+            return nae_launch_grid(ctx, "st_cu_kernel", st_cu_kernel<CH>, dim3(grid), dim3(256), 0, dview(at_stream(in, s0), CH), d_pos, d_fract,
+                                   tab_origin, n0, n1, dout(at_stream(out, s0), CH), (long long)ns, (unsigned)blocks);
+        });
+        if (rc) return rc;
     }
-    return nae_check(ctx, hipGetLastError(), "st_cu_kernel");
+    return NAE_OK;
 }
 
 } // namespace nae

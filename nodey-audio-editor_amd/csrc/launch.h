@@ -1,5 +1,6 @@
-// launch.h — the launch layer of the tiled kernels, once: the device views of a nae_sig, the dynamic-LDS attribute, the one launch path, and
-// the picks that turn a run-time frame size or flag into a compile-time one.  Every kernel file includes it (the STFT ones through stft_common.h).
+// launch.h — the launch layer of every kernel, once: the device views of a nae_sig, the dynamic-LDS attribute, the one launch (NAE_KLAUNCH and
+// the launch's error stand here and nowhere else), the grid of the tiled kernels, the slices of a batch of streams, and the picks that turn a
+// run-time frame size, format, channel count or flag into a compile-time one.  Every kernel file includes it (the STFT ones through stft_common.h).
 #pragma once
 #include "nae_internal.h"
 #include <type_traits>
@@ -34,34 +35,71 @@ inline int nae_pv_lds_attr(nae_ctx* ctx, size_t lds, const void* kernel)
     return NAE_OK;
 }
 
-// The one launch path of a kernel that works on `items` pieces, `per_wg` of them per workgroup of `threads` threads with `lds` bytes of dynamic
-// LDS: the grid, its bound (grid_err: the text of NAE_ERR_INVALID), the LDS attribute, the launch under the profile name, the launch's error.
-// A site that launches nothing for zero items returns before it calls.
+// The one launch: the LDS attribute above 64 KiB, the launch under the profile name, and the launch's error, whose text is the profile name.
+template <class K, class... A>
+int nae_launch_grid(nae_ctx* ctx, const char* name, K kernel, dim3 grid, dim3 block, size_t lds, const A&... args)
+{
+    if (lds > 64 * 1024) {
+        const int rc = nae_pv_lds_attr(ctx, lds, reinterpret_cast<const void*>(kernel));
+        if (rc) return rc;
+    }
+    NAE_KLAUNCH(ctx, name, kernel, grid, block, lds, ctx->stream, args...);
+    return nae_check(ctx, hipGetLastError(), name);
+}
+
+// A kernel that works on `items` pieces, `per_wg` of them per workgroup of `threads` threads with `lds` bytes of dynamic LDS: the grid and its
+// bound (grid_err: the text of NAE_ERR_INVALID), then the one launch.  A site that launches nothing for zero items returns before it calls.
 template <class K, class... A>
 int nae_launch_tiles(nae_ctx* ctx, const char* name, const char* grid_err, K kernel, long long items, int per_wg, int threads, size_t lds,
                      const A&... args)
 {
     const long long grid = (items + per_wg - 1) / per_wg;
     if (grid > 0x7fffffffll) return nae_fail(ctx, NAE_ERR_INVALID, grid_err);
-    if (lds > 64 * 1024) {
-        const int rc = nae_pv_lds_attr(ctx, lds, reinterpret_cast<const void*>(kernel));
-        if (rc) return rc;
-    }
-    NAE_KLAUNCH(ctx, name, kernel, dim3((unsigned)grid), dim3(threads), lds, ctx->stream, args...);
-    return nae_check(ctx, hipGetLastError(), name);
+    return nae_launch_grid(ctx, name, kernel, dim3((unsigned)grid), dim3(threads), lds, args...);
 }
 
-// f(std::integral_constant<int, N>()) at the frame size N = n_fft of the vocoder, the FIR filter and the long convolution
+// Kernels whose grid is (tiles, streams): blockIdx.y holds at most 65535 entries, `group` streams each (1, or the 4 that share a workgroup), so
+// a batch goes out in slices.  f(s0, ns) launches streams [s0, s0 + ns) on views moved there with at_stream; the first non-zero return ends
+// the call, so no slice is launched behind a failed one.
+template <typename F>
+static int for_stream_slices(size_t n_streams, int group, F&& f)
+{
+    const size_t per_launch = (size_t)65535 * group;
+    for (size_t s0 = 0; s0 < n_streams; s0 += per_launch) {
+        const int rc = f(s0, n_streams - s0 < per_launch ? n_streams - s0 : per_launch);
+        if (rc) return rc;
+    }
+    return NAE_OK;
+}
+inline SigViewD at_stream(SigViewD v, size_t s0) { v.base += (long long)s0 * v.ss; return v; }
+inline OutViewD at_stream(OutViewD v, size_t s0) { v.base += (long long)s0 * v.ss; return v; }
+
+// f(std::integral_constant<int, V>()) for the V of the list that equals v, else NAE_ERR_UNSUPPORTED with the text `none`: turns a run-time
+// frame size or sample format into a compile-time one
+template <int... Vs, typename F>
+static int pick_value(nae_ctx* ctx, int v, const char* none, F&& f)
+{
+    int rc = NAE_OK;
+    const bool hit = ((v == Vs ? (rc = f(std::integral_constant<int, Vs>()), true) : false) || ...);
+    return hit ? rc : nae_fail(ctx, NAE_ERR_UNSUPPORTED, none);
+}
+// at the frame size N = n_fft of the vocoder, the FIR filter and the long convolution
 template <typename F>
 static int at_size(nae_ctx* ctx, int n_fft, F&& f)
 {
-    switch (n_fft) {
-    case 512: return f(std::integral_constant<int, 512>());
-    case 1024: return f(std::integral_constant<int, 1024>());
-    case 2048: return f(std::integral_constant<int, 2048>());
-    case 4096: return f(std::integral_constant<int, 4096>());
-    default: return nae_fail(ctx, NAE_ERR_UNSUPPORTED, "vocoder: n_fft must be 512, 1024, 2048 or 4096");
-    }
+    return pick_value<512, 1024, 2048, 4096>(ctx, n_fft, "vocoder: n_fft must be 512, 1024, 2048 or 4096", f);
+}
+// at the sample format of a frame that K6 converts (audio-velocity.cpp:223-228 refuses every other)
+template <typename F>
+static int at_format(nae_ctx* ctx, int fmt, F&& f)
+{
+    return pick_value<NAE_FMT_FLT, NAE_FMT_FLTP, NAE_FMT_S16, NAE_FMT_S16P, NAE_FMT_S32, NAE_FMT_S32P>(ctx, fmt, "Unsupported sample format", f);
+}
+// f(std::integral_constant<int, CH>()) for mono and stereo kernels: 2 is stereo, anything else the caller let through is mono
+template <typename F>
+static int with_channels(int ch, F&& f)
+{
+    return ch == 2 ? f(std::integral_constant<int, 2>()) : f(std::integral_constant<int, 1>());
 }
 
 // f(std::bool_constant<a>(), ...) for run-time flags a, ...: the variant pick of every launcher.  f is a generic lambda; a combination that has

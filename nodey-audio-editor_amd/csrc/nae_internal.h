@@ -232,6 +232,7 @@ int nae_launch_pv_synth(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_pla
 // pass-3 waves a CU holds on the kernels `pass3` (kAny: PvAny<N, formant, transients, link>::kResident3; kEnv: PvEnv<N>::kResident; kLock: 16)
 size_t nae_pv_record_pad(int n_fft);
 int nae_pv_resident(nae_ctx* ctx, const nae_pv_run& r, PvKernels pass3);
+// kernels_resample.hip: the rate transposer alone (outputs [j_begin, j_end)), and with the two-input mix fused into its staging
 int nae_launch_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* src, size_t src_len, int ch,
                         size_t n_streams, const float* d_tab, const nae_sig* out, size_t j_begin, size_t j_end);
 int nae_launch_mix_resample(nae_ctx* ctx, const nae_stretch_plan* pl, const nae_sig* a, const nae_sig* b, float va, float vb,

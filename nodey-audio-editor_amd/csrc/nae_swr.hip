@@ -14,6 +14,7 @@
 // (a tile touches few of the 1024 phases: 44.1 -> 48 kHz cycles through 160).  Taps are summed as the library's C
 // template does: even and odd taps in two float accumulators, in increasing order, no fused multiply-add.
 #include "stream_util.h"
+#include "launch.h"
 #include <math.h>
 #include <string.h>
 
@@ -225,8 +226,7 @@ static int swr_run(nae_swr* h)
     a.out = out.at(out.total);
     a.span_cap = (int)((double)kSwrTile * p.in_rate / p.out_rate) + p.L + 4;
     const unsigned grid = (unsigned)((count + kSwrTile - 1) / kSwrTile);
-    NAE_KLAUNCH(ctx, "swr_resample_kernel", swr_resample_kernel, dim3(grid), dim3(kSwrTile), (size_t)a.span_cap * sizeof(float2), ctx->stream, a);
-    rc = nae_check(ctx, hipGetLastError(), "swr_resample_kernel");
+    rc = nae::nae_launch_grid(ctx, "swr_resample_kernel", swr_resample_kernel, dim3(grid), dim3(kSwrTile), (size_t)a.span_cap * sizeof(float2), a);
     if (rc) return rc;
     out.total = n_avail;
     // input in front of the next window is no longer needed (a window that starts in front of sample 0 reflects about

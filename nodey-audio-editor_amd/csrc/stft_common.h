@@ -1,5 +1,5 @@
 // stft_common.h — kernel-side types and vocoder launch helpers shared by the STFT translation units (kernels_stft.hip, kernels_pvpipe.hip,
-// kernels_spectrum.hip, kernels_pvlock.hip).
+// kernels_spectrum.hip, kernels_pvlock.hip) and the rate transposer (kernels_resample.hip).
 #pragma once
 #include "launch.h"
 #include "stft_device.h"

@@ -4,6 +4,8 @@ Every row is one block call with profiling on in a fresh context; the complete {
 tests/golden/launch_names.json.  The rows are the smallest shapes that still take every launcher of the tiled kernels — the vocoder at
 every size, flag combination and layout (pass 1, scan and pass 3 all launch), the 1024-point pipeline in its six shapes, and the four
 effect nodes — so a launcher that picks another instantiation's name, launches once more or once less, or drops a launch shows here.
+The "node" rows do the same for K1 - K8, the WSOLA chain and the input conversion, one row per branch of each launcher's variant pick
+(nae_debug_diff_u32 launches outside the profile: its row pins that it stays there).
 
 The golden file is not written by the library under test: it was recorded by running this file as a script
 (python tests/test_gpu_launch_names.py --record tests/golden/launch_names.json) on the commit in front of the one that wrote the launch
@@ -42,6 +44,33 @@ def rows():
                                  debug={"pv_tile": 16, "pv_fps": fps, "pv_flow": flow})))
         for fx in ("fir", "conv", "eq", "dyn link=0", "dyn link=1"):
             out.append((f"{fx} {layout}", "fx", dict(fx=fx, layout=layout)))
+    # K1 - K8, the WSOLA chain and the input conversion: one row per branch of each launcher's variant pick
+    for mode in ("i2p", "p2i", "flat", "generic"):
+        for scale in (False, True):
+            out.append((f"copy_sig {mode}{' scaled' if scale else ''}", "node", dict(op="copy_sig", mode=mode, scale=scale)))
+    for op in ("gain f32", "gain s16", "gain s32", "amix planes", "amix_sig fast", "amix_sig generic", "bimix", "downmix", "bimix2_interleave",
+               "mono_to_stereo", "fill_uniform", "diff_u32", "swr"):
+        out.append((op, "node", dict(op=op)))
+    for fmt in ("FLT", "FLTP", "S16", "S16P", "S32", "S32P"):
+        out.append((f"to_f32 {fmt}", "node", dict(op="to_f32", fmt=fmt)))
+    out.append(("spectrum stereo", "node", dict(op="spectrum", layout="interleaved")))
+    out.append(("spectrum generic unit stride", "node", dict(op="spectrum", layout="planar")))
+    out.append(("spectrum generic frame stride 2", "node", dict(op="spectrum", layout="interleaved", debug={"spec_generic": 1})))
+    for n in (256, 512, 1024, 2048, 4096):
+        out.append((f"spectrum_any {n} hop {n // 2}", "node", dict(op="spectrum", layout="planar", n_fft=n, hop=n // 2)))
+    out.append(("spectrum_any 512 hop 100 frame stride 2", "node", dict(op="spectrum", layout="interleaved", n_fft=512, hop=100)))
+    out.append(("transposer stereo group of 4", "node", dict(op="transposer", ch=2, n_streams=4, rate=1.25)))
+    out.append(("transposer stereo alone", "node", dict(op="transposer", ch=2, n_streams=2, rate=1.25)))
+    out.append(("transposer mono", "node", dict(op="transposer", ch=1, n_streams=2, rate=1.25)))
+    out.append(("transposer direct", "node", dict(op="transposer", ch=2, n_streams=2, rate=4101 / 512)))
+    out.append(("graph4 front stage: fused mix", "node", dict(op="graph4 front")))
+    for ch in (1, 2):
+        for name, rate, pitch in (("below 1", 0.8, 1.0), ("at 1", 0.5, 2.0), ("above 1", 1.25, 1.0)):    # effective rate = rate * pitch
+            out.append((f"wsola ch={ch} rate {name} nc=2", "node", dict(op="wsola", ch=ch, rate=rate, pitch=pitch, sr=48000, debug={"td_nc": 2})))
+        out.append((f"wsola ch={ch} rate above 1 nc=4", "node", dict(op="wsola", ch=ch, rate=1.25, pitch=1.0, sr=48000, debug={"td_nc": 4})))
+        # the block call fuses the cubic stage into the filter's launch; st_unfused gives it a launch of its own
+        out.append((f"wsola ch={ch} rate above 1 unfused", "node", dict(op="wsola", ch=ch, rate=1.25, pitch=1.0, sr=48000, debug={"st_unfused": 1})))
+    out.append(("wsola ch=2 44.1 kHz nc=4", "node", dict(op="wsola", ch=2, rate=1.25, pitch=1.0, sr=44100, debug={"td_nc": 4})))
     return out
 
 
@@ -54,8 +83,122 @@ def _sig(nae, ptr, L, layout):
     return nae.Sig.planar(ptr, L, CH) if layout == "planar" else nae.Sig.interleaved(ptr, L, CH)
 
 
+def _node(nae, c, a):
+    """one call of a K1 - K8, WSOLA or conversion row on context c: the buffers are made first, the call alone is profiled"""
+    import ctypes as C
+    op, L, N = a["op"], L_FX, N_STREAMS
+    bufs = []
+
+    def dev(n, dtype=np.float32):
+        d = c.empty(n, dtype)
+        if dtype == np.float32:
+            c.fill_uniform(d.ptr, n, n, 1, 0, len(bufs))
+        else:
+            d.zero()
+        bufs.append(d)
+        return d
+
+    def inter(d, length, ch=CH):
+        return nae.Sig.interleaved(d.ptr, length, ch)
+
+    if op == "copy_sig":
+        x, o = dev(N * L * CH), dev(N * (L + 1) * CH)
+        src = nae.Sig.planar(x.ptr, L, CH) if a["mode"] == "p2i" else inter(x, L)
+        dst = {"i2p": nae.Sig.planar(o.ptr, L, CH), "p2i": inter(o, L), "flat": inter(o, L),
+               "generic": nae.Sig.planar(o.ptr, L, CH, plane_stride=L + 1)}[a["mode"]]      # planes that are not 16-byte aligned
+        run = (lambda: c.gain_sig(src, dst, L, CH, N, 0.5)) if a["scale"] else (lambda: c.copy_sig(src, dst, L, CH, N))
+    elif op.startswith("gain "):
+        dt = {"f32": np.float32, "s16": np.int16, "s32": np.int32}[op[5:]]
+        x, o = dev(L, dt), dev(L, dt)
+        run = lambda: c.gain(dt, [x.ptr], [o.ptr], L, 0.5)
+    elif op == "amix planes":
+        p = [dev(L) for _ in range(6)]
+        run = lambda: c.amix([p[0].ptr, p[1].ptr], [p[2].ptr, p[3].ptr], [0.5, 0.25], p[4].ptr, p[5].ptr, L)
+    elif op.startswith("amix_sig"):
+        x, y, o = dev(N * L * CH), dev(N * L * CH), dev(N * L * CH)
+        dst = nae.Sig.planar(o.ptr, L, CH) if op.endswith("fast") else inter(o, L)
+        run = lambda: c.amix_sig([inter(x, L), inter(y, L)], [0.5, 0.25], dst, L, N)
+    elif op == "bimix":
+        p = [dev(L) for _ in range(6)]
+        run = lambda: c.bimix(p[0].ptr, p[1].ptr, p[2].ptr, p[3].ptr, 0.25, p[4].ptr, p[5].ptr, L)
+    elif op == "downmix":
+        p = [dev(L) for _ in range(3)]
+        run = lambda: c.bimix2_downmix(p[0].ptr, p[1].ptr, p[2].ptr, L)
+    elif op == "bimix2_interleave":
+        e, l, o = dev(L), dev(L), dev(2 * L)
+        run = lambda: c.bimix2_interleave(o.ptr, e.ptr, l.ptr, 100, L - 100, 0)
+    elif op == "mono_to_stereo":
+        m, o = dev(L), dev(2 * L)
+        run = lambda: c._ck(c.lib.nae_mono_to_stereo_f32(c.h, m.ptr, o.ptr, L, 0.5))
+    elif op == "fill_uniform":
+        x = dev(N * L)
+        run = lambda: c.fill_uniform(x.ptr, L, L, N, 0, 0)
+    elif op == "diff_u32":
+        x, y, cnt = dev(L), dev(L), dev(1, np.uint64)
+        run = lambda: c.diff_words(x.ptr, y.ptr, L, cnt.ptr)
+    elif op == "to_f32":
+        fmt = a["fmt"]
+        x = dev(L * CH, {"FLT": np.float32, "S16": np.int16, "S32": np.int32}[fmt.rstrip("P")])
+        planes = [x.at(0), x.at(L)] if fmt.endswith("P") else [x.ptr]
+        o = dev(L * CH)
+
+        def run():
+            assert c.to_f32_interleaved(getattr(nae, "FMT_" + fmt), planes, L, CH, o.ptr) == 0
+    elif op == "swr":
+        host = np.zeros(2 * 4410, np.float32)
+
+        def run():
+            h, got = C.c_void_p(), C.c_size_t()
+            outL, outR = np.zeros(6000, np.float32), np.zeros(6000, np.float32)
+            assert c.lib.nae_swr_create(c.h, nae.FMT_FLT, 44100, 2, 48000, C.byref(h)) == 0
+            assert c.lib.nae_swr_convert_host(h, (C.c_void_p * 1)(host.ctypes.data), 4410, outL.ctypes.data, outR.ctypes.data, 6000, C.byref(got)) == 0
+            assert got.value > 0 and c.lib.nae_swr_destroy(h) == 0
+    elif op == "spectrum":
+        x = dev(N * L * CH)
+        src = _sig(nae, x.ptr, L, a["layout"])
+        n, hop = a.get("n_fft", 1024), a.get("hop", 256)
+        F = c.spectrum_frames_ex(L, n, hop)
+        assert F > 0
+        o = dev(N * F * CH * (n // 2 + 1))
+        if "n_fft" in a:
+            run = lambda: c.spectrum_block_ex(n, hop, src, L, CH, N, o.ptr, F * CH * (n // 2 + 1))
+        else:
+            run = lambda: c.spectrum_block(src, L, CH, N, o.ptr, F * CH * 513)
+    elif op == "transposer":
+        ch, n, rate = a["ch"], a["n_streams"], a["rate"]
+        pl = c.stretch_plan(rate, 1.0, L)
+        assert pl.rs_on and not pl.pv_on
+        x, o = dev(n * L * ch), dev(n * pl.out_len * ch)
+        run = lambda: c.stretch_block(rate, 1.0, inter(x, L, ch), L, ch, n, inter(o, pl.out_len, ch))
+    elif op == "graph4 front":
+        pl = c.stretch_plan(1.0, PITCH, L)
+        F = c.spectrum_frames(pl.out_len)
+        x, y, mix, pitch, spec = dev(N * L * 2), dev(N * L * 2), dev(N * L * 2), dev(N * pl.out_len * 2), dev(N * F * 2 * 513)
+        g = nae.Graph4()
+        g.in_a, g.in_b, g.vol_a, g.vol_b = inter(x, L), inter(y, L), 0.5, 0.5
+        g.mix_out, g.rate, g.pitch, g.pitch_out = nae.Sig.planar(mix.ptr, L, 2), 1.0, PITCH, inter(pitch, pl.out_len)
+        g.spec_out, g.spec_stream_stride, g.S, g.n_streams = spec.ptr, F * 2 * 513, L, N
+        run = lambda: c.graph4_stages(g, 1)
+    else:
+        assert op == "wsola", op
+        ch, Lw = a["ch"], L_PV
+        pl = c.wsola_plan(a["sr"], ch, a["rate"], a["pitch"], Lw)
+        x, o = dev(N * Lw * ch), dev(max(1, N * pl.out_len * ch))
+        run = lambda: c.wsola_block(a["sr"], a["rate"], a["pitch"], inter(x, Lw, ch), Lw, ch, N, inter(o, pl.out_len, ch))
+    c.sync()
+    c.prof_reset()
+    c.prof_enable(True)
+    run()
+    c.sync()
+    c.prof_enable(False)
+    for d in bufs:
+        d.free()
+
+
 def _call(nae, c, kind, a):
     """one block call of the row on context c (the signal is uniform noise: the launches do not depend on it)"""
+    if kind == "node":
+        return _node(nae, c, a)
     L = L_PV if kind == "pv" else L_FX
     d_x = c.empty(N_STREAMS * L * CH)
     c.fill_uniform(d_x.ptr, L * CH, L * CH, N_STREAMS, 0, 0)

@@ -281,6 +281,28 @@ def test_k7_batched_streams_are_independent(ctx, nae):
             assert rel_rms(got[s], orc.stretch(x.reshape(n_streams, -1)[s], ch, 1.0, p)) <= TOL
 
 
+@pytest.mark.parametrize("ch,n_streams,edge", [(2, 65535 * 4 + 3, 65535 * 4), (1, 65535 + 3, 65535)])
+def test_k7_transposer_alone_across_a_stream_slice(ctx, nae, ch, n_streams, edge):
+    """blockIdx.y holds 65535 entries (stereo: groups of 4 streams), so a larger batch of the transposer alone (rate 1.25, pitch 1) goes out
+    in two launches with the views moved to the second slice's first stream.  8 frames per stream, every stream its own noise: the streams on
+    both sides of the slice edge, the first and the last equal the oracle bit for bit, and every stream equals the same stream run through
+    calls of 60000 streams, which fit one slice"""
+    L, rate = 8, 1.25
+    x = np.random.default_rng(65535 + ch).uniform(-1.0, 1.0, n_streams * L * ch).astype(np.float32)
+    ctx.prof_reset(); ctx.prof_enable(True)
+    got, pl = gpu_stretch(ctx, nae, x, ch, rate, 1.0, n_streams)
+    ctx.prof_enable(False)
+    assert pl.rs_on and not pl.pv_on and pl.out_len > 0
+    assert {k: int(v[1]) for k, v in ctx.prof_report().items()} == {"resample_tile_kernel": 2}, ctx.prof_report()
+    got = got.reshape(n_streams, -1)
+    for s in (0, edge - 1, edge, n_streams - 1):
+        want = orc.stretch(x.reshape(n_streams, -1)[s], ch, rate, 1.0)
+        assert np.array_equal(got[s].view(np.uint32), want.view(np.uint32)), s
+    for s0 in range(0, n_streams, 60000):
+        part, _ = gpu_stretch(ctx, nae, x.reshape(n_streams, -1)[s0: s0 + 60000].reshape(-1), ch, rate, 1.0, min(60000, n_streams - s0))
+        assert np.array_equal(part.view(np.uint32), got[s0: s0 + 60000].reshape(-1).view(np.uint32)), s0
+
+
 def test_k7_edge_lengths(ctx, nae):
     p = 2 ** (3 / 12)
     for L in (0, 1, 255, 256, 1023, 1025):

@@ -176,7 +176,7 @@ def test_formant_stage_needs_broadband_content(ref):
 
 def launch_names():
     names = set()
-    for f in ("kernels_pvpipe.hip", "kernels_pv_any.hip", "kernels_pvlock.hip", "kernels_pvenv.hip", "kernels_stft.hip"):
+    for f in ("kernels_pvpipe.hip", "kernels_pv_any.hip", "kernels_pvlock.hip", "kernels_pvenv.hip", "kernels_stft.hip", "kernels_resample.hip"):
         with open(os.path.join(CSRC, f)) as fh:
             names |= set(re.findall(r'"([a-z0-9_]+_kernel)"', fh.read()))
     return names

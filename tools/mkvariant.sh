@@ -2,7 +2,7 @@
 # build a variant of libnae_gpu.so for A/B timing:  tools/mkvariant.sh TAG [extra stft flags...]
 # e.g. tools/mkvariant.sh slp  (re-enables SLP)   tools/mkvariant.sh x -DNAE_FOO=1
 # The translation units and their flags are the Makefile's (SRC, HIPFLAGS, NOSLP).  The extra flags (+slp: drop -fno-slp-vectorize) apply to
-# the STFT, pipeline and spectrum TUs; SRC_STFT / SRC_PVPIPE: a patched copy in place of kernels_stft.hip / kernels_pvpipe.hip (tools/experiments).
+# the STFT, transposer, pipeline and spectrum TUs; SRC_STFT / SRC_PVPIPE: a patched copy in place of kernels_stft.hip / kernels_pvpipe.hip (tools/experiments).
 set -e
 TAG=$1; shift
 D=$(cd "$(dirname "$0")/../nodey-audio-editor_amd" && pwd)
@@ -19,7 +19,7 @@ for f in $(mk SRC); do
   case $n in
     kernels_stft)   src=${SRC_STFT:-$src};   fl="$STFT -I$D/csrc" ;;
     kernels_pvpipe) src=${SRC_PVPIPE:-$src}; fl="$STFT -I$D/csrc" ;;
-    kernels_spectrum) fl="$STFT" ;;
+    kernels_spectrum|kernels_resample) fl="$STFT" ;;
     *) if [[ "$NOSLP" == *" $f "* ]]; then fl="-fno-slp-vectorize"; else fl="$NODEFLAGS"; fi ;;
   esac
   $HIPCC $HIPFLAGS $fl -c "$src" -o "$O/$n.o" &

@@ -33,7 +33,7 @@ def compiler_resources():
     import subprocess
     res = {}
     src_dir = os.path.join(ROOT, "nodey-audio-editor_amd", "csrc")
-    for tu in ("kernels_stft.hip", "kernels_pvpipe.hip", "kernels_wsola.hip"):
+    for tu in ("kernels_stft.hip", "kernels_resample.hip", "kernels_pvpipe.hip", "kernels_wsola.hip"):
         r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
                             "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(src_dir, tu), "-o", "/dev/null"], capture_output=True, text=True)
         cur = None
