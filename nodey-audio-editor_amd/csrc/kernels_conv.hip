@@ -358,18 +358,6 @@ int nae_launch_conv(nae_ctx* ctx, int n_fft, int parts, int taps_ch, const float
     return NAE_OK;
 }
 
-void nae_conv_cache_free(nae_ctx* ctx)
-{
-    if (ctx->d_conv_spec) (void)hipFree(ctx->d_conv_spec);
-    if (ctx->ws_conv) (void)hipFree(ctx->ws_conv);
-    ctx->d_conv_spec = nullptr;
-    ctx->conv_spec_floats = 0;
-    ctx->ws_conv = nullptr;
-    ctx->ws_conv_bytes = 0;
-    ctx->conv_spec_n_fft = ctx->conv_spec_taps_ch = 0;
-    ctx->h_conv_taps.clear();
-}
-
 // the one statement of the parameter rules of nae_conv_block_f32 and nae_conv_create; *n_fft 0 becomes the library's pick
 int nae_conv_check(nae_ctx* ctx, int n_taps, int taps_ch, int ch, int* n_fft)
 {
@@ -406,25 +394,9 @@ int nae_conv_block_f32(nae_ctx* ctx, const float* taps_host, int n_taps, int tap
     const int parts = nae_conv_parts(n_taps, n_fft);
     const size_t all = (size_t)taps_ch * (size_t)n_taps;
     // H is kept with the context: a call with the taps, the channel layout and the size of the last one computes nothing again
-    const bool same = ctx->d_conv_spec && ctx->conv_spec_n_fft == n_fft && ctx->conv_spec_taps_ch == taps_ch && ctx->h_conv_taps.size() == all &&
-                      memcmp(ctx->h_conv_taps.data(), taps_host, all * sizeof(float)) == 0;
-    if (!same) {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);            // a launch in flight may still read the last H
-        if (e != hipSuccess) return nae_check(ctx, e, "hipStreamSynchronize");
-        ctx->conv_spec_n_fft = 0;
-        const size_t want = nae_conv_spec_floats(n_fft, parts, taps_ch);
-        if (want > ctx->conv_spec_floats) {
-            if (ctx->d_conv_spec) (void)hipFree(ctx->d_conv_spec);
-            ctx->d_conv_spec = nullptr;
-            ctx->conv_spec_floats = 0;
-            if (hipMalloc((void**)&ctx->d_conv_spec, want * sizeof(float)) != hipSuccess) return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(conv spectra)");
-            ctx->conv_spec_floats = want;
-        }
-        if ((rc = nae_conv_make_spec(ctx, taps_host, n_taps, taps_ch, n_fft, ctx->d_conv_spec))) return rc;
-        ctx->h_conv_taps.assign(taps_host, taps_host + all);
-        ctx->conv_spec_n_fft = n_fft;
-        ctx->conv_spec_taps_ch = taps_ch;
-    }
+    rc = ctx->conv_spec.get(ctx, {n_fft, taps_ch}, taps_host, all * sizeof(float), nae_conv_spec_floats(n_fft, parts, taps_ch) * sizeof(float),
+                            "conv spectra", [&] { return nae_conv_make_spec(ctx, taps_host, n_taps, taps_ch, n_fft, ctx->conv_spec.as<float>()); });
+    if (rc) return rc;
     const size_t B = (size_t)n_fft / 2, blocks = (in_len + B - 1) / B;
     // streams per launch group: as many as leave the ring room for slabs of NAE_CONV_MIN_SLAB blocks inside the workspace cap (every stream with
     // conv_ring set)
@@ -435,17 +407,11 @@ int nae_conv_block_f32(nae_ctx* ctx, const float* taps_host, int n_taps, int tap
         group = fit < 1 ? 1 : fit < n_streams ? fit : n_streams;
     }
     const size_t ring = nae_pick_conv_ring(ctx, n_fft, parts, blocks, group * (size_t)ch);
-    rc = nae_ws_reserve(ctx, &ctx->ws_conv, &ctx->ws_conv_bytes, nae_conv_ring_floats(n_fft, group * (size_t)ch, ring) * sizeof(float));
+    rc = ctx->ws_conv.reserve(ctx, nae_conv_ring_floats(n_fft, group * (size_t)ch, ring) * sizeof(float), "workspace");
     if (rc) return rc;
-    for (size_t s0 = 0; s0 < n_streams; s0 += group) {
-        const size_t n = s0 + group < n_streams ? group : n_streams - s0;
-        nae_sig gs = *src, gd = *dst;
-        gs.base = static_cast<float*>(src->base) + s0 * src->stream_stride;
-        gd.base = static_cast<float*>(dst->base) + s0 * dst->stream_stride;
-        rc = nae_launch_conv(ctx, n_fft, parts, taps_ch, ctx->d_conv_spec, static_cast<float*>(ctx->ws_conv), ring, &gs, in_len, ch, n, &gd, 0, blocks);
-        if (rc) return rc;
-    }
-    return NAE_OK;
+    return nae_for_stream_groups(src, dst, n_streams, group, [&](const nae_sig& gs, const nae_sig& gd, size_t n) {
+        return nae_launch_conv(ctx, n_fft, parts, taps_ch, ctx->conv_spec.as<float>(), ctx->ws_conv.as<float>(), ring, &gs, in_len, ch, n, &gd, 0, blocks);
+    });
 }
 
 // DESIGN.md §3, "K10 long convolution", "Reverb design": exponentially decaying noise in double, rounded once

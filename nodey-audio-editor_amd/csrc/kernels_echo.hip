@@ -173,13 +173,6 @@ int nae_launch_echo(nae_ctx* ctx, const nae_echo_params* ep, const double* d_blo
                             d_block, d_line, d_state);
 }
 
-void nae_echo_cache_free(nae_ctx* ctx)
-{
-    if (ctx->ws_echo) (void)hipFree(ctx->ws_echo);
-    ctx->ws_echo = nullptr;
-    ctx->ws_echo_bytes = 0;
-}
-
 extern "C" {
 
 int nae_echo_block_f32(nae_ctx* ctx, const nae_echo_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst)
@@ -197,18 +190,12 @@ int nae_echo_block_f32(nae_ctx* ctx, const nae_echo_params* params, const nae_si
     const size_t line_bytes = nae_echo_ring(params, ch) * (size_t)ch * sizeof(float);
     size_t group = ctx->echo_group > 0 ? (size_t)ctx->echo_group : NAE_CONV_WS_BYTES / line_bytes;
     group = group < 1 ? 1 : group < n_streams ? group : n_streams;
-    rc = nae_ws_reserve(ctx, &ctx->ws_echo, &ctx->ws_echo_bytes, group * line_bytes);
+    rc = ctx->ws_echo.reserve(ctx, group * line_bytes, "workspace");
     if (rc) return rc;
     const size_t chunks = nae_chunks(in_len);
-    for (size_t s0 = 0; s0 < n_streams; s0 += group) {
-        const size_t n = s0 + group < n_streams ? group : n_streams - s0;
-        nae_sig gs = *src, gd = *dst;
-        gs.base = static_cast<float*>(src->base) + s0 * src->stream_stride;
-        gd.base = static_cast<float*>(dst->base) + s0 * dst->stream_stride;
-        rc = nae_launch_echo(ctx, params, d_block, &gs, in_len, ch, n, &gd, 0, chunks, static_cast<float*>(ctx->ws_echo), nullptr);
-        if (rc) return rc;
-    }
-    return NAE_OK;
+    return nae_for_stream_groups(src, dst, n_streams, group, [&](const nae_sig& gs, const nae_sig& gd, size_t n) {
+        return nae_launch_echo(ctx, params, d_block, &gs, in_len, ch, n, &gd, 0, chunks, ctx->ws_echo.as<float>(), nullptr);
+    });
 }
 
 // DESIGN.md §3, "K16 echo", "Design": the delays to the nearest sample, the loop's low-pass and high-pass by nae_eq_design at q = 1 / sqrt 2

@@ -195,23 +195,10 @@ int nae_eq_cached_block(nae_ctx* ctx, const double* coef_host, int n_sections, d
 {
     (void)nae_use_device(ctx);
     const size_t n_coef = (size_t)n_sections * 5;
-    const bool same = ctx->d_eq_block && ctx->h_eq_coef.size() == n_coef && memcmp(ctx->h_eq_coef.data(), coef_host, n_coef * sizeof(double)) == 0;
-    if (!same) {
-        if (!ctx->d_eq_block && hipMalloc((void**)&ctx->d_eq_block, kEqBlockDoubles * sizeof(double)) != hipSuccess)
-            return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(eq tables)");
-        ctx->h_eq_coef.clear();                            // the upload is ordered on the stream behind a launch that still reads the last block
-        if (const int rc = nae_eq_make_block(ctx, coef_host, n_sections, ctx->d_eq_block)) return rc;
-        ctx->h_eq_coef.assign(coef_host, coef_host + n_coef);
-    }
-    *d_block = ctx->d_eq_block;
-    return NAE_OK;
-}
-
-void nae_eq_cache_free(nae_ctx* ctx)
-{
-    if (ctx->d_eq_block) (void)hipFree(ctx->d_eq_block);
-    ctx->d_eq_block = nullptr;
-    ctx->h_eq_coef.clear();
+    const int rc = ctx->eq_block.get(ctx, {}, coef_host, n_coef * sizeof(double), kEqBlockDoubles * sizeof(double), "eq tables",
+                                     [&] { return nae_eq_make_block(ctx, coef_host, n_sections, ctx->eq_block.as<double>()); });
+    *d_block = ctx->eq_block.as<double>();
+    return rc;
 }
 
 extern "C" {

@@ -186,14 +186,6 @@ int nae_launch_fir(nae_ctx* ctx, int n_fft, const float* d_spec, const nae_sig* 
     return at_size(ctx, n_fft, [&](auto n) { return launch_fir<decltype(n)::value>(ctx, to_view(src), to_out(dst), p, hspec, tb); });
 }
 
-void nae_fir_cache_free(nae_ctx* ctx)
-{
-    if (ctx->d_fir_spec) (void)hipFree(ctx->d_fir_spec);
-    ctx->d_fir_spec = nullptr;
-    ctx->fir_spec_n_fft = 0;
-    ctx->h_fir_taps.clear();
-}
-
 // the one statement of the parameter rules of nae_fir_block_f32 and nae_fir_create; *n_fft 0 becomes the library's pick
 int nae_fir_check(nae_ctx* ctx, int n_taps, int ch, int* n_fft)
 {
@@ -226,20 +218,11 @@ int nae_fir_block_f32(nae_ctx* ctx, const float* taps_host, int n_taps, int n_ff
     if (!src->base || !dst->base) return nae_fail(ctx, NAE_ERR_INVALID, "fir: null pointer");
     (void)nae_use_device(ctx);
     // H is kept with the context: a call with the taps and the size of the last one computes nothing again
-    const bool same = ctx->d_fir_spec && ctx->fir_spec_n_fft == n_fft && ctx->h_fir_taps.size() == (size_t)n_taps &&
-                      memcmp(ctx->h_fir_taps.data(), taps_host, (size_t)n_taps * sizeof(float)) == 0;
-    if (!same) {
-        if (!ctx->d_fir_spec && hipMalloc((void**)&ctx->d_fir_spec, nae_fir_spec_floats(4096) * sizeof(float)) != hipSuccess)
-            return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(fir spectrum)");
-        const hipError_t e = hipStreamSynchronize(ctx->stream);            // a launch in flight may still read the last H
-        if (e != hipSuccess) return nae_check(ctx, e, "hipStreamSynchronize");
-        ctx->fir_spec_n_fft = 0;
-        if ((rc = nae_fir_make_spec(ctx, taps_host, n_taps, n_fft, ctx->d_fir_spec))) return rc;
-        ctx->h_fir_taps.assign(taps_host, taps_host + n_taps);
-        ctx->fir_spec_n_fft = n_fft;
-    }
+    rc = ctx->fir_spec.get(ctx, {n_fft}, taps_host, (size_t)n_taps * sizeof(float), nae_fir_spec_floats(n_fft) * sizeof(float), "fir spectrum",
+                           [&] { return nae_fir_make_spec(ctx, taps_host, n_taps, n_fft, ctx->fir_spec.as<float>()); });
+    if (rc) return rc;
     const size_t B = (size_t)n_fft / 2;
-    return nae_launch_fir(ctx, n_fft, ctx->d_fir_spec, src, in_len, ch, n_streams, dst, 0, (in_len + B - 1) / B);
+    return nae_launch_fir(ctx, n_fft, ctx->fir_spec.as<float>(), src, in_len, ch, n_streams, dst, 0, (in_len + B - 1) / B);
 }
 
 // DESIGN.md §3, "K9 FIR filter", "Design": Kaiser-windowed sinc in double, rounded once

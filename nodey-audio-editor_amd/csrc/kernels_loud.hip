@@ -345,41 +345,26 @@ int nae_launch_loud_gate(nae_ctx* ctx, const nae_loud_params* p, size_t in_len, 
                             static_cast<const LoudState*>(d_state), d_results);
 }
 
-void nae_loud_cache_free(nae_ctx* ctx)
-{
-    if (ctx->d_loud_block) (void)hipFree(ctx->d_loud_block);
-    if (ctx->ws_loud) (void)hipFree(ctx->ws_loud);
-    ctx->d_loud_block = nullptr;
-    ctx->ws_loud = nullptr;
-    ctx->ws_loud_bytes = 0;
-    ctx->h_loud_coef.clear();
-}
-
 // measure into `results` (device; null: the records in the context's workspace), which *used receives
 static int loud_measure(nae_ctx* ctx, const nae_loud_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, nae_loud_result* results,
                         nae_loud_result** used)
 {
     (void)nae_use_device(ctx);
     // the tables are kept with the context: a call with the coefficients of the last one uploads nothing
-    const bool same = ctx->d_loud_block && ctx->h_loud_coef.size() == 5 * kLdS && memcmp(ctx->h_loud_coef.data(), p->coef, sizeof(p->coef)) == 0;
-    if (!same) {
-        if (!ctx->d_loud_block && hipMalloc(&ctx->d_loud_block, kLdBlockBytes) != hipSuccess) return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(loud tables)");
-        ctx->h_loud_coef.clear();                          // the upload is ordered on the stream behind a launch that still reads the last block
-        const int rc = nae_loud_make_block(ctx, p, ctx->d_loud_block);
-        if (rc) return rc;
-        ctx->h_loud_coef.assign(p->coef, p->coef + 5 * kLdS);
-    }
+    int rc = ctx->loud_block.get(ctx, {}, p->coef, sizeof(p->coef), kLdBlockBytes, "loud tables",
+                                 [&] { return nae_loud_make_block(ctx, p, ctx->loud_block.dev.p); });
+    if (rc) return rc;
     // the workspace: [stream-channel] LoudState | [stream][sub-block][channel] doubles | [stream] records
     const size_t n_sc = n_streams * (size_t)ch;
     const size_t U = in_len / (size_t)p->sub_block, n_sub = U ? U : 1, e_ss = n_sub * (size_t)ch;
     const size_t state_bytes = n_sc * sizeof(LoudState), e_bytes = n_streams * e_ss * sizeof(double);
-    int rc = nae_ws_reserve(ctx, &ctx->ws_loud, &ctx->ws_loud_bytes, state_bytes + e_bytes + n_streams * sizeof(nae_loud_result));
+    rc = ctx->ws_loud.reserve(ctx, state_bytes + e_bytes + n_streams * sizeof(nae_loud_result), "workspace");
     if (rc) return rc;
-    char* ws = static_cast<char*>(ctx->ws_loud);
+    char* ws = ctx->ws_loud.as<char>();
     double* d_E = reinterpret_cast<double*>(ws + state_bytes);
     *used = results ? results : reinterpret_cast<nae_loud_result*>(ws + state_bytes + e_bytes);
     rc = nae_check(ctx, hipMemsetAsync(ws, 0, state_bytes + e_bytes, ctx->stream), "hipMemsetAsync(loud workspace)");
-    if (!rc) rc = nae_launch_loud_measure(ctx, p, ctx->d_loud_block, src, in_len, ch, n_streams, 0, nae_loud_chunks(in_len, true), ws, d_E, e_ss, U);
+    if (!rc) rc = nae_launch_loud_measure(ctx, p, ctx->loud_block.dev.p, src, in_len, ch, n_streams, 0, nae_loud_chunks(in_len, true), ws, d_E, e_ss, U);
     if (!rc) rc = nae_launch_loud_gate(ctx, p, in_len, ch, n_streams, ws, d_E, e_ss, *used);
     return rc;
 }

@@ -640,7 +640,7 @@ static int launch_lock_map(nae_ctx* ctx, const PvJob& j, uint32_t* maps, uint16_
 {
     const char* name = kLink ? (kTransient ? "pvlock_map_transient_link_kernel" : "pvlock_map_link_kernel")
                              : (kTransient ? "pvlock_map_transient_kernel" : "pvlock_map_kernel");
-    const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+    const Tables tb = tables_1024(ctx);
     const long long items = j.n_sc * j.p.n_tiles;
     return nae_launch_tiles(ctx, name, "pvlock_map_kernel: grid too large", pvlock_map_kernel<kUnit, kTransient, kLink>, items, kWaves, kThreads, kLdsLockMap,
                             j.src, j.p, items, maps, sig16, tb);
@@ -674,7 +674,7 @@ static int launch_lock_synth(nae_ctx* ctx, const PvJob& j)
                                            : (kFormant ? "pvlock_synth_formant_link_kernel" : "pvlock_synth_link_kernel"))
                              : (kTransient ? (kFormant ? "pvlock_synth_formant_transient_kernel" : "pvlock_synth_transient_kernel")
                                            : (kFormant ? "pvlock_synth_formant_kernel" : "pvlock_synth_kernel"));
-    const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+    const Tables tb = tables_1024(ctx);
     const long long items = j.n_sc * j.p.n_tiles;
     return nae_launch_tiles(ctx, name, "pvlock_synth_kernel: grid too large", pvlock_synth_kernel<kUnit, kFormant, kTransient, kLink>, items, kWaves, kThreads,
                             kLdsLockSynth, j.src, j.p, items, j.phase_ws, j.out, tb, j.lifter, j.g);

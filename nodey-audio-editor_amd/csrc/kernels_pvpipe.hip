@@ -644,7 +644,7 @@ using namespace nae;
 template <int kG, typename K>
 static int pv_launch(nae_ctx* ctx, const char* name, K kernel, size_t lds, const PvJob& j)
 {
-    const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+    const Tables tb = tables_1024(ctx);
     return nae_launch_tiles(ctx, name, "pv_pipe_kernel: grid too large", kernel, j.n_sc * j.p.n_tiles, kPipeSlots / kG, kPipeThreads, lds, j.src, j.p,
                             j.n_sc, j.phase_ws, j.out, tb);
 }

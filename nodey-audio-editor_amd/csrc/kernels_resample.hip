@@ -77,7 +77,7 @@ constexpr int kRsMaxSpan = 4096 + 32;            // staged source samples per ch
 // (The table is 8 KB per workgroup out of L2; one dword per thread and trip with a wait in every trip — what the first version
 // did — put eight serial L2 round trips in front of every workgroup's staging loads.)
 // Assumes (checked where it can be): workgroups of kRsThreads threads (every caller's __launch_bounds__), a 16-byte aligned
-// table (hipMalloc), rows of a whole number of float4.
+// table (nae_ctx::rs_tab, an allocation of its own), rows of a whole number of float4.
 constexpr int kRsThreads = 256;
 constexpr int kRsRowQuads = NAE_RS_TAPS / 4;                                 // float4 per coefficient row
 static_assert(NAE_RS_TAPS % 4 == 0 && (kRsRowQuads & (kRsRowQuads - 1)) == 0, "a coefficient row is a power-of-two number of float4");

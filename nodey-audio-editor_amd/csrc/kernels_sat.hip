@@ -313,31 +313,24 @@ static int sat_taps_dev(nae_ctx* ctx, int M, const float** d_taps)
 {
     const int slot = M == 2 ? 0 : M == 4 ? 1 : 2;
     (void)nae_use_device(ctx);
-    if (!ctx->d_sat_taps) {
-        if (hipMalloc((void**)&ctx->d_sat_taps, 3 * kSatSlot * sizeof(float)) != hipSuccess) return nae_fail(ctx, NAE_ERR_NOMEM, "hipMalloc(sat taps)");
-        ctx->h_sat_taps.assign(3 * kSatSlot, 0.0f);
+    if (!ctx->sat_taps.p) {
         ctx->sat_taps_have = 0;
+        const int rc = ctx->sat_taps.reserve(ctx, 3 * kSatSlot * sizeof(float), "sat taps");
+        if (rc) return rc;
     }
+    float* d_slot = ctx->sat_taps.as<float>() + slot * kSatSlot;
     if (!(ctx->sat_taps_have & (1 << slot))) {
-        float* h = ctx->h_sat_taps.data() + slot * kSatSlot;
+        float h[kSatSlot] = {};
         const int n = nae_sat_taps(M, h);
         if (n != 2 * kSatK * M + 1) return nae_fail(ctx, NAE_ERR_INVALID, "sat: tap design failed");
         for (int j = 0; j < n; j++) h[kSatTapRow + j] = (float)M * h[j];          // exact: M is a power of two
-        hipError_t e = hipMemcpyAsync(ctx->d_sat_taps + slot * kSatSlot, h, kSatSlot * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+        hipError_t e = hipMemcpyAsync(d_slot, h, kSatSlot * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) return nae_check(ctx, e, "sat: taps upload");
         ctx->sat_taps_have |= 1 << slot;
     }
-    *d_taps = ctx->d_sat_taps + slot * kSatSlot;
+    *d_taps = d_slot;
     return NAE_OK;
-}
-
-void nae_sat_cache_free(nae_ctx* ctx)
-{
-    if (ctx->d_sat_taps) (void)hipFree(ctx->d_sat_taps);
-    ctx->d_sat_taps = nullptr;
-    ctx->sat_taps_have = 0;
-    ctx->h_sat_taps.clear();
 }
 
 static inline bool sat_flat_view(const void* base, long long ss, long long cs, long long fs, int ch)

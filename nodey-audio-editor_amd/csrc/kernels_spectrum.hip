@@ -365,51 +365,13 @@ static int spec_pick_chunk(long long frames, long long n_streams, int n_cu)
     return (int)best_chunk;
 }
 
-// table slot of a size that passed nae_spectrum_check: 256 -> 0 ... 4096 -> 4
-static int spec_any_slot(int n_fft) { return ilog2c(n_fft) - 8; }
-
-// Hann_N, T_N and W_M of one size: double, one rounding to f32; built on first use, freed with the context.
-// n_fft = 1024 uses the context's own tables (the same formulas, built at creation).  The size-generic vocoder (kernels_pv_any.hip) reads them too.
+// the tables of a size for the size-generic kernels (the spectrum's, the vocoder's, the filters'): built at the size's first call
 int nae_spec_any_tables(nae_ctx* ctx, int n_fft, SpecAnyTables* tb)
 {
-    tb->w512 = ctx->d_w512;
-    if (n_fft == NAE_FFT_N) {
-        tb->hann = ctx->d_hann;
-        tb->tn = ctx->d_t1024;
-        tb->wm = ctx->d_w512;
-        return NAE_OK;
-    }
-    const int slot = spec_any_slot(n_fft);
-    nae_ctx::SpecAnyTab& t = ctx->spec_any_tab[slot];
-    if (!t.hann) {
-        const int M = n_fft / 2;
-        const double two_pi = 6.283185307179586476925286766559;
-        std::vector<float> hann(n_fft);
-        std::vector<cf> tn(M + 1), wm(M);
-        for (int n = 0; n < n_fft; n++) hann[n] = (float)(0.5 - 0.5 * cos(two_pi * n / (double)n_fft));
-        for (int k = 0; k <= M; k++) tn[k] = cf{(float)cos(two_pi * k / (double)n_fft), (float)(-sin(two_pi * k / (double)n_fft))};
-        for (int k = 0; k < M; k++) wm[k] = cf{(float)cos(two_pi * k / (double)M), (float)(-sin(two_pi * k / (double)M))};
-        (void)nae_use_device(ctx);
-        float* d_hann = nullptr;
-        cf *d_tn = nullptr, *d_wm = nullptr;
-        bool ok = hipMalloc((void**)&d_hann, n_fft * sizeof(float)) == hipSuccess &&
-                  hipMalloc((void**)&d_tn, (M + 1) * sizeof(cf)) == hipSuccess && hipMalloc((void**)&d_wm, M * sizeof(cf)) == hipSuccess;
-        ok = ok && hipMemcpy(d_hann, hann.data(), n_fft * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(d_tn, tn.data(), (M + 1) * sizeof(cf), hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(d_wm, wm.data(), M * sizeof(cf), hipMemcpyHostToDevice) == hipSuccess;
-        if (!ok) {
-            if (d_hann) (void)hipFree(d_hann);
-            if (d_tn) (void)hipFree(d_tn);
-            if (d_wm) (void)hipFree(d_wm);
-            return nae_fail(ctx, NAE_ERR_HIP, "spectrum tables: hipMalloc / hipMemcpy failed");
-        }
-        t.hann = d_hann;
-        t.tn = d_tn;
-        t.wm = d_wm;
-    }
-    tb->hann = t.hann;
-    tb->tn = t.tn;
-    tb->wm = t.wm;
+    const int rc = nae_fft_tab_ensure(ctx, n_fft);
+    if (rc) return rc;
+    const nae_fft_tab t = nae_fft_tab_of(ctx, n_fft);
+    *tb = SpecAnyTables{t.hann, t.tn, t.wm, nae_fft_tab_of(ctx, NAE_FFT_N).wm};
     return NAE_OK;
 }
 
@@ -447,14 +409,24 @@ static int launch_any(nae_ctx* ctx, const nae_sig* src, int ch, long long hop, l
 
 using namespace nae;
 
-void nae_spec_any_free(nae_ctx* ctx)
+// Hann_N, T_N and W_M of one size (the layout: nae_internal.h): double, one rounding to f32, one upload
+int nae_fft_tab_ensure(nae_ctx* ctx, int n_fft)
 {
-    for (auto& t : ctx->spec_any_tab) {
-        if (t.hann) (void)hipFree(t.hann);
-        if (t.tn) (void)hipFree(t.tn);
-        if (t.wm) (void)hipFree(t.wm);
-        t = nae_ctx::SpecAnyTab{};
-    }
+    CtxBuf& t = ctx->fft_tab[ilog2c(n_fft) - 8];
+    if (t.p) return NAE_OK;
+    const int M = n_fft / 2;
+    const double two_pi = 6.283185307179586476925286766559;
+    std::vector<char> img(nae_fft_tab_bytes(n_fft), 0);
+    float* hann = reinterpret_cast<float*>(img.data());
+    cf* tn = reinterpret_cast<cf*>(img.data() + nae_fft_tab_tn(n_fft));
+    cf* wm = reinterpret_cast<cf*>(img.data() + nae_fft_tab_wm(n_fft));
+    for (int n = 0; n < n_fft; n++) hann[n] = (float)(0.5 - 0.5 * cos(two_pi * n / (double)n_fft));
+    for (int k = 0; k <= M; k++) tn[k] = cf{(float)cos(two_pi * k / (double)n_fft), (float)(-sin(two_pi * k / (double)n_fft))};
+    for (int k = 0; k < M; k++) wm[k] = cf{(float)cos(two_pi * k / (double)M), (float)(-sin(two_pi * k / (double)M))};
+    int rc = t.reserve(ctx, img.size(), "spectrum tables");
+    if (!rc) rc = nae_check(ctx, hipMemcpy(t.p, img.data(), img.size(), hipMemcpyHostToDevice), "hipMemcpy(spectrum tables)");
+    if (rc) t.release();
+    return rc;
 }
 
 // the one spectrum launcher (arguments checked by nae_spectrum_block_ex_f32): the size-generic kernel for every size and hop
@@ -474,13 +446,13 @@ int nae_launch_spectrum(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, si
         });
     }
     const long long items = (long long)(F * n_streams);
-    Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+    const Tables tb = tables_1024(ctx);
     const bool stereo_fast = ch == 2 && src->chan_stride == 1 && src->frame_stride == 2 && src->stream_stride % 4 == 0 &&
                              (reinterpret_cast<uintptr_t>(src->base) & 15) == 0 && !ctx->dbg_spec_generic;
     if (stereo_fast) {
         const long long slots = (long long)ctx->n_cu * 16;                   // waves a launch keeps resident (two workgroups per CU)
         SpecWork w{};
-        w.counters = ctx->d_spec_ctr;
+        w.counters = ctx->spec_ctr.as<unsigned>();
         const long long coarse_all = (((long long)F + kSpecChunk - 1) / kSpecChunk) * (long long)n_streams;
         if (coarse_all < 6 * slots) {
             // small batch: one list of equal chunks, sized so that the waves fill a whole number of rounds
@@ -511,7 +483,7 @@ int nae_launch_spectrum(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, si
         w.dynamic = items > groups * kWaves ? 1u : 0u;
         if (w.dynamic) {
             (void)nae_use_device(ctx);
-            const hipError_t e = hipMemsetAsync(ctx->d_spec_ctr, 0, sizeof(unsigned), ctx->stream);
+            const hipError_t e = hipMemsetAsync(ctx->spec_ctr.p, 0, sizeof(unsigned), ctx->stream);
             if (e != hipSuccess) return nae_check(ctx, e, "hipMemsetAsync(spectrum work counter)");
         }
         const bool wide = (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && dst_stream_stride % 2 == 0 && !ctx->dbg_spec_narrow;

@@ -96,7 +96,7 @@ size_t nae_pv_workspace_bytes(bool lock, int n_fft, size_t n_frames, int ch, siz
 int nae_pv_reserve_ws(nae_ctx* ctx, const nae_pv_run& r, size_t n_frames, int ch, size_t n_streams, int tile)
 {
     if (r.forced) return NAE_OK;
-    return nae_ws_reserve(ctx, &ctx->ws_phase, &ctx->ws_phase_bytes, nae_pv_workspace_bytes(r.lock, r.n_fft, n_frames, ch, n_streams, tile));
+    return ctx->ws_phase.reserve(ctx, nae_pv_workspace_bytes(r.lock, r.n_fft, n_frames, ch, n_streams, tile), "workspace");
 }
 
 // what both passes hand their leaf launchers (pass 1: no output)
@@ -157,7 +157,7 @@ int nae_launch_pv_phase(nae_ctx* ctx, const nae_pv_run& r, const nae_stretch_pla
     } else {
         // items are (stream-channel, tile) with tile fastest
         const long long items = n_sc * p.n_tiles;
-        const Tables tb{ctx->d_w512, ctx->d_t1024, ctx->d_hann};
+        const Tables tb = tables_1024(ctx);
         const int rc = with_flags(j.unit_stride, [&](auto unit) {
             return nae_launch_tiles(ctx, "pv_phase_kernel", "pv_phase_kernel: grid too large", pv_phase_kernel<unit.value>, items, kWaves, kThreads,
                                     kLdsPhase, j.src, p, items, phase_ws, tb);

@@ -11,8 +11,6 @@
 #include <string.h>
 #include <new>
 
-namespace nae { struct cf { float x, y; }; }
-
 int nae_fail(nae_ctx* ctx, int code, const char* what)
 {
     if (ctx) snprintf(ctx->err, sizeof ctx->err, "%s", what);
@@ -60,37 +58,10 @@ static void prof_collect(nae_ctx* ctx)
     ctx->prof_pairs.clear();
 }
 
-int nae_ws_reserve(nae_ctx* ctx, void** p, size_t* have, size_t want)
+int nae_ctx_drain(nae_ctx* ctx)
 {
-    if (*have >= want && *p) return NAE_OK;
     (void)nae_use_device(ctx);
-    if (*p) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return nae_check(ctx, e, "hipStreamSynchronize");
-        (void)hipFree(*p);
-        *p = nullptr;
-        *have = 0;
-    }
-    size_t bytes = want + want / 8 + 4096;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        (void)nae_check(ctx, e, "hipMalloc(workspace)");
-        return NAE_ERR_NOMEM;
-    }
-    *have = bytes;
-    return NAE_OK;
-}
-
-static void build_tables(std::vector<nae::cf>& w512, std::vector<nae::cf>& t1024, std::vector<float>& hann)
-{
-    const double two_pi = 6.283185307179586476925286766559;
-    w512.resize(512);
-    t1024.resize(513);
-    hann.resize(1024);
-    for (int k = 0; k < 512; k++) w512[k] = nae::cf{(float)cos(two_pi * k / 512.0), (float)(-sin(two_pi * k / 512.0))};
-    for (int k = 0; k <= 512; k++) t1024[k] = nae::cf{(float)cos(two_pi * k / 1024.0), (float)(-sin(two_pi * k / 1024.0))};
-    for (int n = 0; n < 1024; n++) hann[n] = (float)(0.5 - 0.5 * cos(two_pi * n / 1024.0));
+    return nae_check(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
 }
 
 double nae_bessel_i0(double x)
@@ -131,20 +102,11 @@ static void build_rs_table(double rate_eff, std::vector<float>& tab)
 
 int nae_ensure_rs_table(nae_ctx* ctx, double rate_eff)
 {
-    if (ctx->d_rs_tab && ctx->rs_tab_rate == rate_eff) return NAE_OK;
-    (void)nae_use_device(ctx);
-    if (!ctx->d_rs_tab) {
-        hipError_t e = hipMalloc((void**)&ctx->d_rs_tab, (NAE_RS_PHASES + 1) * NAE_RS_TAPS * sizeof(float));
-        if (e != hipSuccess) return nae_check(ctx, e, "hipMalloc(rs table)");
-    } else {
-        hipError_t e = hipStreamSynchronize(ctx->stream); // the previous table may still be in use
-        if (e != hipSuccess) return nae_check(ctx, e, "hipStreamSynchronize");
-    }
-    build_rs_table(rate_eff, ctx->h_rs_tab);
-    hipError_t e = hipMemcpy(ctx->d_rs_tab, ctx->h_rs_tab.data(), ctx->h_rs_tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpy(rs table)");
-    ctx->rs_tab_rate = rate_eff;
-    return NAE_OK;
+    return ctx->rs_tab.get(ctx, {}, &rate_eff, sizeof rate_eff, (NAE_RS_PHASES + 1) * NAE_RS_TAPS * sizeof(float), "rs table", [&] {
+        std::vector<float> tab;
+        build_rs_table(rate_eff, tab);
+        return nae_check(ctx, hipMemcpy(ctx->rs_tab.as<float>(), tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(rs table)");
+    });
 }
 
 // Shape of the phase vocoder for a block call: frames per step of the pipeline (kernels_pvpipe.hip), synthesis tile, pass-1 tile.
@@ -329,16 +291,9 @@ int nae_ctx_create(int device, nae_ctx** out)
             pos = end + 1;
         }
     }
-    std::vector<nae::cf> w512, t1024;
-    std::vector<float> hann;
-    build_tables(w512, t1024, hann);
-    bool ok = hipMalloc((void**)&ctx->d_w512, 512 * sizeof(nae::cf)) == hipSuccess &&
-              hipMalloc((void**)&ctx->d_t1024, 520 * sizeof(nae::cf)) == hipSuccess &&
-              hipMalloc((void**)&ctx->d_hann, 1024 * sizeof(float)) == hipSuccess &&
-              hipMalloc((void**)&ctx->d_spec_ctr, 64) == hipSuccess && hipMemset(ctx->d_spec_ctr, 0, 64) == hipSuccess;
-    ok = ok && hipMemcpy(ctx->d_w512, w512.data(), 512 * sizeof(nae::cf), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(ctx->d_t1024, t1024.data(), 513 * sizeof(nae::cf), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(ctx->d_hann, hann.data(), 1024 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    // the 1024-point tables up front (the first call of that size pays nothing; every size reads its W512), and the spectrum's work counter
+    const bool ok = nae_fft_tab_ensure(ctx, NAE_FFT_N) == NAE_OK && ctx->spec_ctr.reserve(ctx, 64, "spectrum work counter") == NAE_OK &&
+                    hipMemset(ctx->spec_ctr.p, 0, 64) == hipSuccess;
     if (!ok) { nae_ctx_destroy(ctx); return NAE_ERR_HIP; }
     *out = ctx;
     return NAE_OK;
@@ -350,23 +305,8 @@ int nae_ctx_destroy(nae_ctx* ctx)
     (void)nae_use_device(ctx);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     prof_collect(ctx);
-    if (ctx->d_w512) (void)hipFree(ctx->d_w512);
-    if (ctx->d_t1024) (void)hipFree(ctx->d_t1024);
-    if (ctx->d_hann) (void)hipFree(ctx->d_hann);
-    if (ctx->d_spec_ctr) (void)hipFree(ctx->d_spec_ctr);
-    nae_spec_any_free(ctx);
-    if (ctx->d_rs_tab) (void)hipFree(ctx->d_rs_tab);
-    if (ctx->ws_phase) (void)hipFree(ctx->ws_phase);
-    if (ctx->ws_mid) (void)hipFree(ctx->ws_mid);
-    nae_wsola_cache_free(ctx);
-    nae_fir_cache_free(ctx);
-    nae_conv_cache_free(ctx);
-    nae_eq_cache_free(ctx);
-    nae_loud_cache_free(ctx);
-    nae_echo_cache_free(ctx);
-    nae_sat_cache_free(ctx);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;                  // the device is selected and the stream drained: every CtxBuf of the context frees itself
     return NAE_OK;
 }
 
@@ -384,9 +324,7 @@ void* nae_ctx_stream(nae_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; 
 
 int nae_sync(nae_ctx* ctx)
 {
-    if (!ctx) return NAE_ERR_INVALID;
-    (void)nae_use_device(ctx);
-    return nae_check(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return ctx ? nae_ctx_drain(ctx) : NAE_ERR_INVALID;
 }
 
 int nae_poll(nae_ctx* ctx)
@@ -603,9 +541,9 @@ static int check_sig(nae_ctx* ctx, const nae_sig* s, const char* what)
 static int reserve_mid(nae_ctx* ctx, const nae_stretch_plan& pl, int ch, size_t n_streams, nae_sig* mid)
 {
     const size_t mid_stride = (pl.mid_len + 3) & ~(size_t)3;
-    const int rc = nae_ws_reserve(ctx, &ctx->ws_mid, &ctx->ws_mid_bytes, n_streams * ch * mid_stride * sizeof(float));
+    const int rc = ctx->ws_mid.reserve(ctx, n_streams * ch * mid_stride * sizeof(float), "workspace");
     if (rc) return rc;
-    *mid = nae_sig{ctx->ws_mid, (size_t)ch * mid_stride, mid_stride, 1};
+    *mid = nae_sig{ctx->ws_mid.p, (size_t)ch * mid_stride, mid_stride, 1};
     return NAE_OK;
 }
 
@@ -678,13 +616,13 @@ static int stretch_block_impl(nae_ctx* ctx, const nae_pv_opts& o, double rate, d
     } else if (pl.rs_first) {
         rc = 1;
         if (mix_pending && ch == 2) {
-            rc = nae_launch_mix_resample(ctx, &pl, front->a, front->b, front->va, front->vb, src, in_len, n_streams, ctx->d_rs_tab, &mid);
+            rc = nae_launch_mix_resample(ctx, &pl, front->a, front->b, front->va, front->vb, src, in_len, n_streams, ctx->rs_tab.as<float>(), &mid);
             if (rc < 0) return rc;
             if (rc == 0) mix_pending = false;
         }
         if (rc == 1) {
             if ((rc = run_mix())) return rc;
-            rc = nae_launch_resample(ctx, &pl, src, in_len, ch, n_streams, ctx->d_rs_tab, &mid, 0, pl.mid_len);
+            rc = nae_launch_resample(ctx, &pl, src, in_len, ch, n_streams, ctx->rs_tab.as<float>(), &mid, 0, pl.mid_len);
             if (rc) return rc;
         }
         pv_src = &mid;
@@ -700,16 +638,16 @@ static int stretch_block_impl(nae_ctx* ctx, const nae_pv_opts& o, double rate, d
         PvBlockShape sh;
         if ((rc = pv_block_shape(ctx, run, pl.frames, ch, n_streams, &sh))) return rc;
         const nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, pv_out_len, nullptr, nullptr};
-        rc = nae_launch_pv_phase(ctx, run, &pl, pv_src, pv_in_len, ch, n_streams, sh.phase_tile, sh.tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+        rc = nae_launch_pv_phase(ctx, run, &pl, pv_src, pv_in_len, ch, n_streams, sh.phase_tile, sh.tile, ctx->ws_phase.as<uint32_t>(), &seg);
         if (rc) return rc;
-        rc = nae_launch_pv_synth(ctx, run, &pl, pv_src, pv_in_len, ch, n_streams, sh.tile, sh.phase_tile, static_cast<uint32_t*>(ctx->ws_phase),
+        rc = nae_launch_pv_synth(ctx, run, &pl, pv_src, pv_in_len, ch, n_streams, sh.tile, sh.phase_tile, ctx->ws_phase.as<uint32_t>(),
                                  pv_dst, &seg, sh.frames_per_step);
         if (rc) return rc;
     }
     if (pl.rs_on && !pl.rs_first) {
         const nae_sig* rs_src = pl.pv_on ? &mid : src;
         const size_t rs_src_len = pl.pv_on ? pl.mid_len : in_len;
-        rc = nae_launch_resample(ctx, &pl, rs_src, rs_src_len, ch, n_streams, ctx->d_rs_tab, dst, 0, pl.out_len);
+        rc = nae_launch_resample(ctx, &pl, rs_src, rs_src_len, ch, n_streams, ctx->rs_tab.as<float>(), dst, 0, pl.out_len);
         if (rc) return rc;
     }
     return NAE_OK;
@@ -795,16 +733,16 @@ static int pv_tile_phase_impl(nae_ctx* ctx, const nae_pv_opts& o, double rate, d
         if (rc) return rc;
         rc = nae_ensure_rs_table(ctx, pl.rate_eff);
         if (rc) return rc;
-        rc = nae_launch_resample(ctx, &pl, src, in_len, ch, n_streams, ctx->d_rs_tab, &mid, 0, pl.mid_len);
+        rc = nae_launch_resample(ctx, &pl, src, in_len, ch, n_streams, ctx->rs_tab.as<float>(), &mid, 0, pl.mid_len);
         if (rc) return rc;
         pv_src = &mid;
         pv_in_len = pl.mid_len;
     }
     const nae_pv_segment seg{0, (long long)pl.frames, (long long)pl.frames, 0, nullptr, nullptr};
-    rc = nae_launch_pv_phase(ctx, run, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+    rc = nae_launch_pv_phase(ctx, run, &pl, pv_src, pv_in_len, ch, n_streams, tile, tile, ctx->ws_phase.as<uint32_t>(), &seg);
     if (rc) return rc;
     std::vector<int32_t> tmp(ws_bytes / sizeof(int32_t));
-    hipError_t e = hipMemcpyAsync(tmp.data(), ctx->ws_phase, ws_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t e = hipMemcpyAsync(tmp.data(), ctx->ws_phase.p, ws_bytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return nae_check(ctx, e, "copy phase workspace");
     for (size_t rec = 0; rec < n_streams * ch * n_tiles; rec++)

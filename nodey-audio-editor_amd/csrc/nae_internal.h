@@ -3,11 +3,17 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <memory>
 #include <vector>
 #include "../../include/nae_gpu.h"
 #include "../../include/nae_dsp_spec.h"
 
+#include "ctx_mem.h"
+
 namespace nae { struct cf; }
+struct nae_wsola_cache;
+void nae_wsola_cache_free(nae_wsola_cache* c);   // nae_wsola.hip: the one release hook of the incomplete type (its members free themselves)
+struct nae_wsola_cache_deleter { void operator()(nae_wsola_cache* c) const { nae_wsola_cache_free(c); } };
 
 struct nae_ctx {
     int device = 0;
@@ -16,48 +22,35 @@ struct nae_ctx {
     char err[512] = {0};
     char name[256] = {0};
     int n_cu = 256;              // compute units of the device (launch-shape decisions)
-    // read-only tables (built on the host in double, rounded once to f32)
-    nae::cf* d_w512 = nullptr;   // exp(-2 pi i k/512),  k = 0..511
-    nae::cf* d_t1024 = nullptr;  // exp(-2 pi i k/1024), k = 0..512
-    float* d_hann = nullptr;     // periodic Hann, 1024
-    unsigned* d_spec_ctr = nullptr;  // work counter of the persistent stereo spectrum kernel (zeroed on the stream in front of every drawing launch; kernels_spectrum.hip)
-    // tables of the spectrum sizes other than 1024 (n_fft = 256, 512, -, 2048, 4096), built on first use (kernels_spectrum.hip)
-    struct SpecAnyTab { float* hann = nullptr; nae::cf* tn = nullptr; nae::cf* wm = nullptr; };
-    SpecAnyTab spec_any_tab[5];
-    // grow-only workspaces
-    void* ws_phase = nullptr; size_t ws_phase_bytes = 0;
-    void* ws_mid = nullptr;   size_t ws_mid_bytes = 0;
-    float* d_rs_tab = nullptr; double rs_tab_rate = 0.0;
-    std::vector<float> h_rs_tab;
-    struct nae_wsola_cache* wsola_cache = nullptr;   // plan + workspaces of nae_wsola_block_f32 (nae_wsola.hip)
+    // The context's device memory is CtxBuf and CtxConst members (ctx_mem.h) and nothing else: each frees itself when the context goes, so
+    // nae_ctx_destroy lists no node, and a node that adds memory adds a member.
+    // read-only FFT tables of n_fft = 256 ... 4096, slot log2 n_fft - 8 (built on the host in double, rounded once to f32): 1024's
+    // with the context, the others on first use (nae_fft_tab_ensure; the layout of a slot: nae_fft_tab_of below)
+    CtxBuf fft_tab[5];
+    CtxBuf spec_ctr;             // work counter of the persistent stereo spectrum kernel (zeroed on the stream in front of every drawing launch; kernels_spectrum.hip)
+    CtxBuf ws_phase;             // the vocoder's phase records (nae_pv_reserve_ws; the stretch handle's segments run on it too)
+    CtxBuf ws_mid;               // the signal between the transposer and the vocoder
+    CtxConst rs_tab;             // the transposer's coefficient table, keyed by rate_eff (nae_ensure_rs_table)
+    std::unique_ptr<nae_wsola_cache, nae_wsola_cache_deleter> wsola_cache;   // plan + workspaces of nae_wsola_block_f32 (nae_wsola.hip)
     int pv_tile = 0;             // frames per phase-vocoder tile; 0 = choose per call (nae_pick_pv_shape)
     int pv_fps = 0;              // pv_fps = 1|2|4: frames per step of the vocoder pipeline (0 = choose per call)
     int fir_tile = 0;            // blocks per tile of the FIR filter; 0 = choose per launch (nae_pick_fir_tile)
-    // nae_fir_block_f32 keeps the last call's taps and their spectrum (kernels_fir.hip): [padded taps | H], sized for n_fft = 4096
-    float* d_fir_spec = nullptr; int fir_spec_n_fft = 0;
-    std::vector<float> h_fir_taps;
+    CtxConst fir_spec;           // nae_fir_block_f32's [padded taps | H] of the last call's n_fft and taps (kernels_fir.hip)
     int conv_tile = 0;           // blocks per wave of the long convolution's accumulate kernel; 0 = nae_pick_conv_tile
     int conv_ring = 0;           // spectrum slots per stream-channel of its workspace ring; 0 = from NAE_CONV_WS_BYTES (nae_pick_conv_ring)
-    // nae_conv_block_f32 keeps the last call's taps and their spectra (kernels_conv.hip), apart from the FIR filter's, and the ring of its launches
-    float* d_conv_spec = nullptr; size_t conv_spec_floats = 0; int conv_spec_n_fft = 0, conv_spec_taps_ch = 0;
-    std::vector<float> h_conv_taps;
-    void* ws_conv = nullptr; size_t ws_conv_bytes = 0;
+    CtxConst conv_spec;          // nae_conv_block_f32's spectra of the last call's n_fft, taps_ch and taps, apart from the FIR filter's (kernels_conv.hip)
+    CtxBuf ws_conv;              // the ring of its launches
     int dn_tile = 0;             // hop blocks per tile of the spectral gate; 0 = choose per launch (nae_pick_denoise_tile)
-    // nae_eq_block_f32 keeps the last call's coefficients and their constant block (kernels_eq.hip)
-    double* d_eq_block = nullptr;
-    std::vector<double> h_eq_coef;
-    // the loudness entries keep the last call's K-weighting and its constant block, and their workspace: states, sub-block energies, records (kernels_loud.hip)
-    void* d_loud_block = nullptr;
-    std::vector<double> h_loud_coef;
-    void* ws_loud = nullptr; size_t ws_loud_bytes = 0;
-    // nae_echo_block_f32's delay lines, one ring per stream-channel of a launch group (kernels_echo.hip)
-    void* ws_echo = nullptr; size_t ws_echo_bytes = 0;
+    CtxConst eq_block;           // the constant block of the last call's sections: the EQ, echo and keyed-dynamics block calls (nae_eq_cached_block)
+    CtxConst loud_block;         // the loudness entries' constant block of the last call's K-weighting (kernels_loud.hip)
+    CtxBuf ws_loud;              // their workspace: states, sub-block energies, records
+    CtxBuf ws_echo;              // nae_echo_block_f32's delay lines, one ring per stream-channel of a launch group (kernels_echo.hip)
     int echo_group = 0;          // streams per launch of the echo's block call; 0 = from NAE_CONV_WS_BYTES
     int mod_sub = 0;             // samples a wave of the modulated delay computes in parallel, 1 ... 64; 0 = the rule of kernels_mod.hip
     int sat_tile = 0;            // chunks per wave of the saturation; 0 = choose per launch (nae_pick_sat_tile)
-    // the saturation keeps the device taps of every oversampling factor it has run (kernels_sat.hip): three slots [hd | hu], bit i of sat_taps_have: slot i is there
-    float* d_sat_taps = nullptr; unsigned sat_taps_have = 0;
-    std::vector<float> h_sat_taps;
+    // the saturation keeps the device taps of every oversampling factor it has run (kernels_sat.hip): three slots [hd | hu], bit i of sat_taps_have:
+    // slot i is there.  No last-call constant: a slot never changes once uploaded
+    CtxBuf sat_taps; unsigned sat_taps_have = 0;
     // tuning / A-B switches: nae_debug_set(ctx, key, value) (include/nae_gpu.h lists the keys; NAE_DEBUG="key=value,..." applies them at context creation)
     bool dbg_st_unfused = false;     // st_unfused: WSOLA chain runs filter and cubic stage as separate launches
     int dbg_td_nc = 0;               // td_nc = 1|2|4: candidates per thread of the WSOLA search (0: by batch size)
@@ -116,12 +109,26 @@ int nae_check(nae_ctx* ctx, hipError_t e, const char* what);
 int nae_fail(nae_ctx* ctx, int code, const char* what);
 // the nae_*_check functions' failure: ctx may be null (a caller that wants the code alone), no message then
 inline int nae_fail_opt(nae_ctx* ctx, int code, const char* what) { return ctx ? nae_fail(ctx, code, what) : code; }
-int nae_ws_reserve(nae_ctx* ctx, void** p, size_t* have, size_t want);
+
+// kernels_spectrum.hip: the tables of size n_fft in ctx->fft_tab, built at the size's first call.  A slot is one buffer, every table on a
+// 256-byte boundary as an allocation of its own would be: Hann_N [N] floats | T_N[k] = exp(-2 pi i k / N), k = 0 ... M = N / 2 | W_M[k], k < M.
+// Kernels may read T_N in 16-byte pieces: at every size its M + 1 entries are followed by 31 zero ones (1024 had 520 entries for its 513).
+// W512, which every size reads, is the W_M of 1024.
+int nae_fft_tab_ensure(nae_ctx* ctx, int n_fft);
+struct nae_fft_tab { const float* hann; const nae::cf* tn; const nae::cf* wm; };
+constexpr size_t nae_fft_tab_tn(int n_fft) { return (size_t)n_fft * sizeof(float); }                               // byte offsets
+constexpr size_t nae_fft_tab_wm(int n_fft) { return nae_fft_tab_tn(n_fft) + (size_t)n_fft / 2 * 8 + 256; }
+constexpr size_t nae_fft_tab_bytes(int n_fft) { return nae_fft_tab_wm(n_fft) + (size_t)n_fft / 2 * 8; }
+inline nae_fft_tab nae_fft_tab_of(const nae_ctx* ctx, int n_fft)
+{
+    const char* p = ctx->fft_tab[__builtin_ctz((unsigned)n_fft) - 8].as<char>();
+    return nae_fft_tab{reinterpret_cast<const float*>(p), reinterpret_cast<const nae::cf*>(p + nae_fft_tab_tn(n_fft)),
+                       reinterpret_cast<const nae::cf*>(p + nae_fft_tab_wm(n_fft))};
+}
 
 // kernels_spectrum.hip: every supported size and hop (arguments checked by the caller); picks the kernel
 int nae_launch_spectrum(nae_ctx* ctx, int n_fft, int hop, const nae_sig* src, size_t T, int ch, size_t n_streams, float* dst,
                         size_t dst_stream_stride);
-void nae_spec_any_free(nae_ctx* ctx);
 // the one statement of the spectrum's parameter rules (nae_spectrum_frames_ex, nae_spectrum_block_ex_f32, nae_spectrum_create):
 // n_fft a power of two in [256, 4096], else NAE_ERR_UNSUPPORTED; 1 <= hop <= n_fft, else NAE_ERR_INVALID
 inline int nae_spectrum_check(int n_fft, int hop)
@@ -139,6 +146,20 @@ double nae_bessel_i0(double x);
 // `resident` waves a CU holds where the stream-channels alone do not give them, into tiles of at least min_tile units: at most
 // ceil(units / min_tile) tiles, or with max_tiles_down floor(units / min_tile) — the FIR filter's, 41 blocks are 5 tiles of 9, not 6 of 7.
 int nae_pick_tile(nae_ctx* ctx, int forced, size_t units, size_t n_sc, size_t resident, size_t min_tile, bool max_tiles_down);
+// The block calls whose workspace holds `group` streams at a time (the long convolution's ring, the echo's lines): f(src, dst, n) on the views
+// of streams [s0, s0 + n), group after group; the first non-zero return ends the call.
+template <class F>
+int nae_for_stream_groups(const nae_sig* src, const nae_sig* dst, size_t n_streams, size_t group, const F& f)
+{
+    for (size_t s0 = 0; s0 < n_streams; s0 += group) {
+        nae_sig gs = *src, gd = *dst;
+        gs.base = static_cast<float*>(src->base) + s0 * src->stream_stride;
+        gd.base = static_cast<float*>(dst->base) + s0 * dst->stream_stride;
+        const int rc = f(gs, gd, s0 + group < n_streams ? group : n_streams - s0);
+        if (rc) return rc;
+    }
+    return NAE_OK;
+}
 // a continued stream processes frames / hop blocks [f_origin, f_origin + f_count) per call
 struct nae_pv_segment {
     long long f_origin, f_count;
@@ -241,9 +262,6 @@ int nae_ensure_rs_table(nae_ctx* ctx, double rate_eff);
 int nae_pick_pv_shape(nae_ctx* ctx, size_t frames, size_t n_sc, int* phase_tile, int* frames_per_step);
 constexpr int kPhasePad = 520; // int32 per (stream-channel, tile) record in the phase workspace
 
-// nae_wsola.hip
-void nae_wsola_cache_free(nae_ctx* ctx);
-
 // kernels_fir.hip: the FIR filter ("K9 FIR filter").  nae_fir_check: the parameter rules of the block call and the handle (n_taps < 1
 // or ch not 1 / 2 NAE_ERR_INVALID; a size other than 512 ... 4096 or more than n_fft / 2 + 1 taps NAE_ERR_UNSUPPORTED; *n_fft 0 becomes the pick).
 // A spectrum buffer holds nae_fir_spec_floats(n_fft) floats: the taps zero-padded to n_fft, then H[0 ... n_fft / 2] (nae_fir_make_spec, which
@@ -254,7 +272,6 @@ int nae_fir_make_spec(nae_ctx* ctx, const float* taps_host, int n_taps, int n_ff
 int nae_launch_fir(nae_ctx* ctx, int n_fft, const float* d_spec, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
                    size_t b_origin, size_t b_stop);
 int nae_pick_fir_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc);
-void nae_fir_cache_free(nae_ctx* ctx);
 
 // kernels_conv.hip: the long convolution ("K10 long convolution").  nae_conv_check: the parameter rules of the block call and the handle
 // (n_taps < 1, ch not 1 / 2 or taps_ch not 1 / ch NAE_ERR_INVALID; more than NAE_CONV_MAX_TAPS taps, a size other than 512 ... 4096 or more than
@@ -276,7 +293,6 @@ int nae_launch_conv(nae_ctx* ctx, int n_fft, int parts, int taps_ch, const float
                     size_t in_len, int ch, size_t n_streams, const nae_sig* dst, size_t b_origin, size_t b_stop);
 int nae_pick_conv_tile(nae_ctx* ctx, int n_fft);
 size_t nae_pick_conv_ring(nae_ctx* ctx, int n_fft, int parts, size_t blocks, size_t n_sc);
-void nae_conv_cache_free(nae_ctx* ctx);
 
 // kernels_eq.hip: the biquad cascade ("K11 biquad cascade").  nae_eq_check: the parameter rules of the block call and the handle (a
 // null pointer, n_sections < 1, ch not 1 / 2, a non-finite coefficient or a section that is not strictly stable NAE_ERR_INVALID; more than
@@ -289,7 +305,6 @@ int nae_eq_check(nae_ctx* ctx, const double* coef, int n_sections, int ch);
 int nae_eq_make_block(nae_ctx* ctx, const double* coef, int n_sections, double* d_block);
 int nae_launch_eq(nae_ctx* ctx, const double* d_block, int n_sections, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
                   const nae_sig* dst, size_t c_origin, size_t c_stop, double* d_state);
-void nae_eq_cache_free(nae_ctx* ctx);
 // the context's own constant block, made of checked coefficients unless they are the last call's (nae_eq_block_f32 and nae_dynkey_block_f32)
 int nae_eq_cached_block(nae_ctx* ctx, const double* coef_host, int n_sections, double** d_block);
 
@@ -321,7 +336,6 @@ int nae_echo_check(nae_ctx* ctx, const nae_echo_params* p, int ch);
 size_t nae_echo_ring(const nae_echo_params* p, int ch);
 int nae_launch_echo(nae_ctx* ctx, const nae_echo_params* p, const double* d_block, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
                     const nae_sig* dst, size_t c_origin, size_t c_stop, float* d_line, double* d_state);
-void nae_echo_cache_free(nae_ctx* ctx);
 
 // kernels_mod.hip: the modulated delay ("K17 modulated delay").  nae_mod_check: the parameter rules of the block call and the handle.
 // nae_launch_mod runs chunks [c_origin, c_stop) of absolutely indexed signals, one wave per stream-channel: d_state, [stream-channel]
@@ -340,7 +354,6 @@ int nae_sat_check(nae_ctx* ctx, const nae_sat_params* p, int ch);
 int nae_launch_sat(nae_ctx* ctx, const nae_sat_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
                    size_t c_origin, size_t c_stop);
 int nae_pick_sat_tile(nae_ctx* ctx, size_t chunks, size_t n_sc);
-void nae_sat_cache_free(nae_ctx* ctx);
 
 // kernels_denoise.hip: the spectral gate ("K13 spectral gate").  nae_denoise_check: the parameter rules of the block call and the
 // handle.  nae_launch_denoise runs hop blocks [b_origin, b_stop) of absolutely indexed signals of in_len samples: it reads from
@@ -366,7 +379,6 @@ int nae_launch_loud_measure(nae_ctx* ctx, const nae_loud_params* p, const void* 
                             size_t c_origin, size_t c_stop, void* d_state, double* d_E, size_t e_ss, size_t n_sub);
 int nae_launch_loud_gate(nae_ctx* ctx, const nae_loud_params* p, size_t in_len, int ch, size_t n_streams, const void* d_state, const double* d_E,
                          size_t e_ss, nae_loud_result* d_results);
-void nae_loud_cache_free(nae_ctx* ctx);
 
 // kernels_nodes.hip
 int nae_launch_copy_sig(nae_ctx* ctx, const nae_sig* src, const nae_sig* dst, size_t S, int ch, size_t n_streams,

@@ -169,9 +169,9 @@ int stretch_pv_stage(nae_stretch* h, const nae_stretch_plan& pl, const nae_sig& 
         if (!h->carry[i] && (rc = h->dev_alloc(&h->carry[i], (size_t)ch * nae_pv_record_pad(h->opts.n_fft), "hipMalloc(carry)"))) return rc;
     const nae_pv_segment seg{(long long)h->blocks_done, (long long)count, (long long)F_r, limit,
                              h->blocks_done && !forced ? h->carry[h->carry_cur] : nullptr, h->carry[h->carry_cur ^ 1], one_tile};
-    rc = nae_launch_pv_phase(ctx, h->run, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &seg);
+    rc = nae_launch_pv_phase(ctx, h->run, &pl, &src, src_len, ch, 1, tile, tile, ctx->ws_phase.as<uint32_t>(), &seg);
     if (rc) return rc;
-    rc = nae_launch_pv_synth(ctx, h->run, &pl, &src, src_len, ch, 1, tile, tile, static_cast<uint32_t*>(ctx->ws_phase), &dst, &seg, fps);
+    rc = nae_launch_pv_synth(ctx, h->run, &pl, &src, src_len, ch, 1, tile, tile, ctx->ws_phase.as<uint32_t>(), &dst, &seg, fps);
     if (rc) return rc;
     h->carry_cur ^= 1;
     h->blocks_done = B_r;
@@ -212,7 +212,7 @@ int stretch_process(nae_stretch* h)
             if (!rc) rc = mid.reserve(ctx, J_r);
             if (rc) return rc;
             const nae_sig src = in.view(), dst = mid.view();
-            rc = nae_launch_resample(ctx, &pl, &src, in.total, ch, 1, ctx->d_rs_tab, &dst, mid.total, J_r);
+            rc = nae_launch_resample(ctx, &pl, &src, in.total, ch, 1, ctx->rs_tab.as<float>(), &dst, mid.total, J_r);
             if (rc) return rc;
             mid.total = J_r;
             const unsigned __int128 pos = (unsigned __int128)J_r * pl.step_q32;
@@ -287,7 +287,7 @@ int stretch_process(nae_stretch* h)
             if (rc) return rc;
             const nae_sig sv = src.view(), dv = out.view();
             const size_t src_len = h->flushed && pl.pv_on ? fin.mid_len : src.total;
-            rc = nae_launch_resample(ctx, &pl, &sv, src_len, ch, 1, ctx->d_rs_tab, &dv, out.total, J_r);
+            rc = nae_launch_resample(ctx, &pl, &sv, src_len, ch, 1, ctx->rs_tab.as<float>(), &dv, out.total, J_r);
             if (rc) return rc;
             out.total = J_r;
             // source still needed: from idx(J_r) - 7, rounded DOWN to a multiple of 4 samples as the tiled kernel stages it

@@ -181,50 +181,18 @@ static int upload_cu(nae_ctx* ctx, const CuTable& tab, size_t first, size_t coun
 
 using namespace nae;
 
-// A grow-only device table; a grow does not keep the contents.  It waits for the stream (the old table may still be in use), frees, then
-// allocates, so a failed grow leaves an empty table behind and never a stale pointer.  One growth rule for every user: half as much again.
-template <class T>
-struct DevTab {
-    T* p = nullptr;
-    size_t cap = 0;                 // elements
-
-    int reserve(nae_ctx* ctx, size_t want, const char* what)
-    {
-        if (want <= cap) return NAE_OK;
-        (void)hipStreamSynchronize(ctx->stream);
-        free();
-        const size_t ncap = want + want / 2 + 1024;
-        T* np = nullptr;
-        if (hipMalloc((void**)&np, ncap * sizeof(T)) != hipSuccess) return nae_fail(ctx, NAE_ERR_NOMEM, what);
-        p = np;
-        cap = ncap;
-        return NAE_OK;
-    }
-
-    void free()
-    {
-        if (p) (void)hipFree(p);
-        *this = DevTab{};
-    }
-};
-
 // the cubic stage's table on the device: the source position and the fraction of every output (CuTable's two columns).  Each column knows its
 // own capacity, so a grow that fails at the second one leaves nothing to put right
 struct CuDevTable {
-    DevTab<long long> pos;
-    DevTab<float> fract;
+    CtxBuf pos, fract;
 
     int reserve(nae_ctx* ctx, size_t want)
     {
-        const int rc = pos.reserve(ctx, want, "hipMalloc(cubic table)");
-        return rc ? rc : fract.reserve(ctx, want, "hipMalloc(cubic table)");
+        const int rc = pos.reserve(ctx, want * sizeof(long long), "cubic table");
+        return rc ? rc : fract.reserve(ctx, want * sizeof(float), "cubic table");
     }
-
-    void free()
-    {
-        pos.free();
-        fract.free();
-    }
+    long long* d_pos() const { return pos.as<long long>(); }
+    float* d_fract() const { return fract.as<float>(); }
 };
 
 // plan cache of the block entry point (one entry: the bench and batch jobs repeat one parameter set)
@@ -237,29 +205,12 @@ struct nae_wsola_cache {
     StState fin;
     long long out_len = 0;
     CuDevTable tab;
-    DevTab<int> tile_n;             // first cubic output of every fused filter+cubic tile (orders 0 and 1)
+    CtxBuf tile_n;                  // first cubic output of every fused filter+cubic tile (orders 0 and 1), ints
     size_t n_tiles = 0;
-    void* ws_a = nullptr; size_t ws_a_bytes = 0;
-    void* ws_b = nullptr; size_t ws_b_bytes = 0;
+    CtxBuf ws_a, ws_b;              // the signals between the stages
 };
 
-static nae_wsola_cache* cache_of(nae_ctx* ctx)
-{
-    if (!ctx->wsola_cache) ctx->wsola_cache = new (std::nothrow) nae_wsola_cache();
-    return ctx->wsola_cache;
-}
-
-void nae_wsola_cache_free(nae_ctx* ctx)
-{
-    nae_wsola_cache* c = ctx->wsola_cache;
-    if (!c) return;
-    c->tab.free();
-    c->tile_n.free();
-    if (c->ws_a) (void)hipFree(c->ws_a);
-    if (c->ws_b) (void)hipFree(c->ws_b);
-    delete c;
-    ctx->wsola_cache = nullptr;
-}
+void nae_wsola_cache_free(nae_wsola_cache* c) { delete c; }
 
 static int plan_fill(const StCfg& cfg, const StState& fin, long long out_len, size_t in_len, long long zeros, nae_wsola_plan* pl)
 {
@@ -305,7 +256,8 @@ int nae_wsola_block_f32(nae_ctx* ctx, int sample_rate, double rate, double pitch
     if (!ctx) return NAE_ERR_INVALID;
     (void)nae_use_device(ctx);
     if (!src || !dst || !src->base || !dst->base) return nae_fail(ctx, NAE_ERR_INVALID, "nae_wsola_block_f32: null signal");
-    nae_wsola_cache* wc = cache_of(ctx);
+    if (!ctx->wsola_cache) ctx->wsola_cache.reset(new (std::nothrow) nae_wsola_cache());
+    nae_wsola_cache* wc = ctx->wsola_cache.get();
     if (!wc) return nae_fail(ctx, NAE_ERR_NOMEM, "plan cache");
     int rc;
     if (!(wc->valid && wc->sr == sample_rate && wc->ch == ch && wc->rate == rate && wc->pitch == pitch && wc->in_len == in_len)) {
@@ -318,17 +270,17 @@ int nae_wsola_block_f32(nae_ctx* ctx, int sample_rate, double rate, double pitch
         wc->out_len = sim_flush(wc->cfg, s, 0, &tab, nullptr);
         wc->fin = s;
         rc = wc->tab.reserve(ctx, tab.pos.size());
-        if (!rc) rc = upload_cu(ctx, tab, 0, tab.pos.size(), wc->tab.pos.p, wc->tab.fract.p);
+        if (!rc) rc = upload_cu(ctx, tab, 0, tab.pos.size(), wc->tab.d_pos(), wc->tab.d_fract());
         if (rc) return rc;
         wc->n_tiles = 0;
         if (wc->cfg.order != 2) {
             // filter and cubic stage are adjacent: they run as one launch, tile by tile
             std::vector<int> tile_n;
             st_tile_starts(tab, wc->cfg.order == 0 ? wc->out_len : s.cu_out, tile_n);
-            rc = wc->tile_n.reserve(ctx, tile_n.size(), "hipMalloc(tile table)");
+            rc = wc->tile_n.reserve(ctx, tile_n.size() * sizeof(int), "tile table");
             if (rc) return rc;
             if (!tile_n.empty()) {
-                hipError_t e = hipMemcpyAsync(wc->tile_n.p, tile_n.data(), tile_n.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+                hipError_t e = hipMemcpyAsync(wc->tile_n.as<int>(), tile_n.data(), tile_n.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
                 if (e != hipSuccess) return nae_check(ctx, e, "hipMemcpyAsync(tile table)");
                 wc->n_tiles = tile_n.size() - 1;
@@ -349,26 +301,25 @@ int nae_wsola_block_f32(nae_ctx* ctx, int sample_rate, double rate, double pitch
     default: len1 = (size_t)fin.cu_out; len2 = (size_t)fin.aa_out; break;
     }
     const size_t stride1 = (len1 + 8) * w, stride2 = (len2 + 8) * w;
-    rc = nae_ws_reserve(ctx, &wc->ws_a, &wc->ws_a_bytes, n_streams * stride1 * sizeof(float));
-    if (rc) return rc;
-    rc = nae_ws_reserve(ctx, &wc->ws_b, &wc->ws_b_bytes, n_streams * stride2 * sizeof(float));
+    rc = wc->ws_a.reserve(ctx, n_streams * stride1 * sizeof(float), "workspace");
+    if (!rc) rc = wc->ws_b.reserve(ctx, n_streams * stride2 * sizeof(float), "workspace");
     if (rc) return rc;
     const StView v_src{(const float*)src->base, (long long)src->stream_stride, (long long)src->chan_stride,
                        (long long)src->frame_stride, 0, (long long)in_len};
-    const StOut o_a{(float*)wc->ws_a, (long long)stride1, 1, (long long)w, 0};
-    const StOut o_b{(float*)wc->ws_b, (long long)stride2, 1, (long long)w, 0};
-    const StView v_a{(const float*)wc->ws_a, (long long)stride1, 1, (long long)w, 0, (long long)len1};
-    const StView v_b{(const float*)wc->ws_b, (long long)stride2, 1, (long long)w, 0, (long long)len2};
+    const StOut o_a{wc->ws_a.as<float>(), (long long)stride1, 1, (long long)w, 0};
+    const StOut o_b{wc->ws_b.as<float>(), (long long)stride2, 1, (long long)w, 0};
+    const StView v_a{wc->ws_a.as<float>(), (long long)stride1, 1, (long long)w, 0, (long long)len1};
+    const StView v_b{wc->ws_b.as<float>(), (long long)stride2, 1, (long long)w, 0, (long long)len2};
     const StOut o_dst{(float*)dst->base, (long long)dst->stream_stride, (long long)dst->chan_stride, (long long)dst->frame_stride, 0};
     const TdRange all{0, 0, fin.td_nseq, 0.0, 1, cfg.order == 0 ? (long long)len1 : wc->out_len};
     const long long n_offs = fin.td_nseq > 0 ? fin.td_nseq - 1 : 0;
-    const long long* d_pos = wc->tab.pos.p;
-    const float* d_fract = wc->tab.fract.p;
+    const long long* d_pos = wc->tab.d_pos();
+    const float* d_fract = wc->tab.d_fract();
     switch (cfg.order) {
     case 0:
         rc = st_launch_td(ctx, cfg, v_src, all, o_a, n_streams, nullptr, offsets_dbg, n_offs);
         if (!rc && !ctx->dbg_st_unfused)
-            rc = st_launch_aa_cu(ctx, cfg, v_a, d_pos, d_fract, wc->tile_n.p, wc->n_tiles, wc->out_len, o_dst, n_streams);
+            rc = st_launch_aa_cu(ctx, cfg, v_a, d_pos, d_fract, wc->tile_n.as<int>(), wc->n_tiles, wc->out_len, o_dst, n_streams);
         else {
             if (!rc) rc = st_launch_aa(ctx, cfg, v_a, 0, fin.aa_out, o_b, n_streams);
             if (!rc) rc = st_launch_cu(ctx, cfg, v_b, d_pos, d_fract, 0, 0, wc->out_len, o_dst, n_streams);
@@ -376,7 +327,7 @@ int nae_wsola_block_f32(nae_ctx* ctx, int sample_rate, double rate, double pitch
         break;
     case 1:
         if (!ctx->dbg_st_unfused)
-            rc = st_launch_aa_cu(ctx, cfg, v_src, d_pos, d_fract, wc->tile_n.p, wc->n_tiles, fin.cu_out, o_b, n_streams);
+            rc = st_launch_aa_cu(ctx, cfg, v_src, d_pos, d_fract, wc->tile_n.as<int>(), wc->n_tiles, fin.cu_out, o_b, n_streams);
         else {
             rc = st_launch_aa(ctx, cfg, v_src, 0, fin.aa_out, o_a, n_streams);
             if (!rc) rc = st_launch_cu(ctx, cfg, v_a, d_pos, d_fract, 0, 0, fin.cu_out, o_b, n_streams);
@@ -415,7 +366,6 @@ struct nae_wsola : StreamHandle {
     {
         a.free();
         b.free();
-        tab.free();
     }
 };
 
@@ -432,7 +382,7 @@ int wsola_run(nae_wsola* h, const StState& before)
     const long long cu_new = now.cu_out - before.cu_out;
     if (cu_new > 0) {
         rc = h->tab.reserve(ctx, (size_t)cu_new);
-        if (!rc) rc = st_launch_cu_table(ctx, before.cu_pos, before.cu_fract, c.rate, cu_new, h->tab.pos.p, h->tab.fract.p);
+        if (!rc) rc = st_launch_cu_table(ctx, before.cu_pos, before.cu_fract, c.rate, cu_new, h->tab.d_pos(), h->tab.d_fract());
         if (rc) return rc;
     }
     DevFifo* chain[4] = {&h->in, &h->a, &h->b, &h->out};
@@ -456,7 +406,7 @@ int wsola_run(nae_wsola* h, const StState& before)
             } else if (kind == 1) {
                 rc = st_launch_aa(ctx, c, vin, out_before, out_now, vout, 1);
             } else {
-                rc = st_launch_cu(ctx, c, vin, h->tab.pos.p, h->tab.fract.p, before.cu_out, out_before, out_now, vout, 1);
+                rc = st_launch_cu(ctx, c, vin, h->tab.d_pos(), h->tab.d_fract(), before.cu_out, out_before, out_now, vout, 1);
             }
             if (rc) return rc;
             dst.total = (size_t)out_now;

@@ -9,6 +9,12 @@ namespace nae {
 constexpr int kT1024Pad = kPhasePad;             // 513 split twiddles / phases, padded to 520
 
 struct Tables { const cf* w512; const cf* t1024; const float* hann; };
+// the context's own, built at its creation (nae_fft_tab_ensure): W512 is the W_M of the size
+inline Tables tables_1024(const nae_ctx* ctx)
+{
+    const nae_fft_tab t = nae_fft_tab_of(ctx, NAE_FFT_N);
+    return Tables{t.wm, t.tn, t.hann};
+}
 // the 1024-point kernels on the padded FFT (spectrum, vocoder pass 1): 8-wave workgroups that stage Hann, the split twiddles,
 // W64 and the pass-A twiddles in LDS, followed by one padded FFT scratch per wave
 constexpr int kWaves = 8;                        // waves per workgroup
