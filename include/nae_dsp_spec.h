@@ -91,6 +91,19 @@
 #define NAE_SAT_MAX_OS 8
 #define NAE_SAT_SOFT 0
 #define NAE_SAT_HARD 1
+/* K19 gate ("K19 gate"): a noise gate / downward expander on K12's tiling (NAE_DYN_LANE, NAE_DYN_CHUNK), look-ahead limit
+ * (NAE_DYN_MAX_LOOKAHEAD) and floor (NAE_DYN_FLOOR_DB); the hold reaches at most NAE_GATE_MAX_HOLD samples */
+#define NAE_GATE_MAX_HOLD (1 << 21)
+#define NAE_GATE_MIN_THRESHOLD_DB (-90.0)
+#define NAE_GATE_MAX_THRESHOLD_DB 0.0
+#define NAE_GATE_MAX_SLOPE 99.0
+#define NAE_GATE_MAX_RANGE_DB 120.0
+/* nae_gate_design: the ranges of its arguments (attack and release are K12's: NAE_DYN_MAX_ATTACK_S, NAE_DYN_MIN_RELEASE_S, NAE_DYN_MAX_RELEASE_S) */
+#define NAE_GATE_MAX_HYSTERESIS_DB 24.0
+#define NAE_GATE_MAX_RATIO 100.0
+#define NAE_GATE_MAX_HOLD_S 10.0
+#define NAE_GATE_MODE_GATE 0
+#define NAE_GATE_MODE_EXPANDER 1
 /* K13 spectral gate ("K13 spectral gate"): noise reduction on the STFT at N = 512 ... 4096 and hop N / 4: a per-bin decision
  * against a learned power profile, smoothed by an integer triangle over at most NAE_DENOISE_MAX_TIME frames and NAE_DENOISE_MAX_FREQ bins to
  * either side (a wider frequency triangle pulls a pure tone down: DESIGN.md gives the figure); a tile the library chooses has at least

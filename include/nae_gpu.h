@@ -54,7 +54,9 @@ extern "C" {
  *   nae_dynkey_params: the keyed (side-chain) dynamics, K15; nae_echo_design, nae_echo_block_f32 and the nae_echo handle (the same eight
  *   entries) with the record nae_echo_params: the echo, K16; nae_mod_design, nae_mod_block_f32 and the nae_mod handle (the same eight
  *   entries) with the record nae_mod_params: the modulated delay (chorus, flanger, vibrato), K17; nae_sat_latency, nae_sat_taps,
- *   nae_sat_design, nae_sat_block_f32 and the nae_sat handle (the same eight entries) with the record nae_sat_params: the saturation, K18. */
+ *   nae_sat_design, nae_sat_block_f32 and the nae_sat handle (the same eight entries) with the record nae_sat_params: the saturation, K18;
+ *   nae_gate_design, nae_gate_block_f32 and the nae_gate handle (the same eight entries) with the record nae_gate_params: the noise gate and
+ *   downward expander, K19. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -84,6 +86,7 @@ typedef struct nae_dynkey nae_dynkey;
 typedef struct nae_echo nae_echo;
 typedef struct nae_mod nae_mod;
 typedef struct nae_sat nae_sat;
+typedef struct nae_gate nae_gate;
 typedef struct nae_denoise nae_denoise;
 typedef struct nae_loud nae_loud;
 
@@ -820,6 +823,63 @@ int nae_sat_destroy(nae_sat* h);
  * null pointer, an argument that is not finite or outside its range, an unknown curve; NAE_ERR_UNSUPPORTED: oversample not 1, 2, 4 or 8.  No
  * context, no device work. */
 int nae_sat_design(double drive_db, double bias, int curve, int oversample, double output_db, double mix, nae_sat_params* out);
+
+/* ------------------------------------------------------------------ K19 gate (noise gate and downward expander)
+ * no reference code.  Spec ("K19 gate"): one detector per stream-channel, or with link = 1 on a stereo stream one per stream.
+ * Arithmetic is double, every step one IEEE operation in the order written, rounded once to f32.  K = 20 log10(2), KINV = 1 / K, dyn_log2 and
+ * dyn_exp2 are K12's.  Per detector, n = 0 ... in_len - 1, input at or past in_len zero:
+ *   level       a[n] = |x[n]| in f32, with link the larger of the two channels' (b > a ? b : a, a the first channel's)
+ *   hysteresis  s[n] = 1 where a[n] >= open_lin, 0 where a[n] < close_lin, else s[n - 1]; s[-1] = 0; a NaN keeps the state
+ *   hold        the gate is open at n iff some m in [n - hold, n + lookahead] has s[m] = 1 (integers, exact)
+ *   depth       expand = 0: range_db.  expand = 1: xg = K dyn_log2((double)a[n]), a zero sample at NAE_DYN_FLOOR_DB; u = threshold_db - xg;
+ *               v = slope u; depth = u <= 0 ? 0 : (v < range_db ? v : range_db)
+ *   smoother    y[n] = (alpha y[n - 1]) + b; open: alpha = alpha_attack, b = 0.0; closed: alpha = alpha_release,
+ *               b = (1 - alpha_release) depth[n], the factor made once; y[-1] = range_db
+ *   gain        g[n] = dyn_exp2((0.0 - y[n]) KINV); out_c[n] = (float)((double)x_c[n] g[n]) for each channel of the detector
+ * The smoother is tiled on K12's grid (NAE_DYN_LANE samples per lane, chunks of NAE_DYN_CHUNK counted from the stream's sample 0): a lane
+ * composes its 16 maps, the 64 maps are scanned in six Kogge-Stone steps, a lane starts from the scanned map of the lane below it applied to
+ * the chunk's carry and runs the plain recurrence; the tiling is part of the specification.  The call is compensated as K12 is: output
+ * sample n is input sample n under a decision that has seen lookahead samples ahead; in_len frames come out and nothing past in_len is
+ * stored.  So any cut into puts gives the block call's bits; with alpha_attack = 0 a signal that never falls below open_lin comes out bit
+ * for bit; a non-finite sample i leaves every output sample before i - lookahead as it was, and the call returns NAE_OK.  Bit-exact against
+ * the CPU statement (tests/gate_ref/ref_gate.c).
+ * Errors: a null pointer, ch not 1 or 2, a field that is not finite or outside its range (0 < close_lin <= open_lin; threshold_db -90 ... 0;
+ * slope 0 ... 99; range_db 0 ... 120; the alphas in [0, 1); hold and lookahead not negative; expand and link 0 or 1): NAE_ERR_INVALID; a
+ * lookahead above NAE_DYN_MAX_LOOKAHEAD or a hold above NAE_GATE_MAX_HOLD: NAE_ERR_UNSUPPORTED; in_len = 0 or n_streams = 0: NAE_OK after
+ * the checks, nothing is launched.  Views as nae_dyn_block_f32's: stream_stride 0 on the source and dst->base == src->base are allowed. */
+typedef struct nae_gate_params {
+    float open_lin, close_lin;   /* the two thresholds as magnitudes */
+    double threshold_db;         /* the expander's depth starts here */
+    double slope;                /* ratio - 1; not read with expand = 0 */
+    double range_db;             /* the deepest attenuation */
+    double alpha_attack, alpha_release;
+    int hold;                    /* samples */
+    int lookahead;               /* samples */
+    int expand;                  /* 0: gate, 1: downward expander */
+    int link;                    /* 1: one detector per stereo stream */
+} nae_gate_params;
+int nae_gate_block_f32(nae_ctx* ctx, const nae_gate_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                       const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch): before the flush floor((put - lookahead) / NAE_DYN_CHUNK) whole chunks are
+ * available, never negative; nae_gate_flush releases the rest, so in_len frames come out in all, equal to the block call's however the input
+ * is cut.  A put after the flush: NAE_ERR_STATE. */
+int nae_gate_create(nae_ctx* ctx, const nae_gate_params* params, int channels, nae_gate** h);
+int nae_gate_put(nae_gate* h, const float* interleaved, size_t S);
+int nae_gate_put_host(nae_gate* h, const float* interleaved_host, size_t S);
+int nae_gate_flush(nae_gate* h);
+size_t nae_gate_available(nae_gate* h);
+int nae_gate_receive(nae_gate* h, float* dst, size_t max_frames, size_t* got);
+int nae_gate_receive_host(nae_gate* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_gate_destroy(nae_gate* h);
+/* The record on the host, in double: open_lin = (float)10^(threshold_db / 20); close_lin = (float)10^((threshold_db - hysteresis_db) / 20);
+ * slope = ratio - 1; alpha = exp(-1 / (t sample_rate)), attack_s = 0 gives 0; hold = lround(hold_s sample_rate); lookahead as nae_dyn_design
+ * makes it; expand = mode.  mode: NAE_GATE_MODE_GATE or NAE_GATE_MODE_EXPANDER.  Ranges: threshold_db -90 ... 0, hysteresis_db 0 ... 24,
+ * range_db 0 ... 120, ratio 1 ... 100, attack_s 0 ... 0.5, hold_s 0 ... 10, release_s 0.001 ... 5, lookahead_s not negative.
+ * NAE_ERR_INVALID: a null pointer, sample_rate <= 0, an unknown mode, link not 0 or 1, an argument that is not finite or outside its range;
+ * NAE_ERR_UNSUPPORTED: a look-ahead above NAE_DYN_MAX_LOOKAHEAD samples or a hold above NAE_GATE_MAX_HOLD samples at that rate.  No
+ * context, no device work. */
+int nae_gate_design(int sample_rate, int mode, double threshold_db, double hysteresis_db, double range_db, double ratio, double attack_s,
+                    double hold_s, double release_s, double lookahead_s, int link, nae_gate_params* out);
 
 /* ------------------------------------------------------------------ K13 spectral gate
  * no reference code.  Spec ("K13 spectral gate"): noise reduction on the STFT at n_fft = 512 ... 4096, hop H = n_fft / 4, in the

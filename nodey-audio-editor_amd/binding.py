@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = [
     "nae_mod_receive", "nae_mod_receive_host", "nae_mod_destroy",
     "nae_sat_latency", "nae_sat_taps", "nae_sat_design", "nae_sat_block_f32", "nae_sat_create", "nae_sat_put", "nae_sat_put_host", "nae_sat_flush",
     "nae_sat_available", "nae_sat_receive", "nae_sat_receive_host", "nae_sat_destroy",
+    "nae_gate_design", "nae_gate_block_f32", "nae_gate_create", "nae_gate_put", "nae_gate_put_host", "nae_gate_flush", "nae_gate_available",
+    "nae_gate_receive", "nae_gate_receive_host", "nae_gate_destroy",
     "nae_denoise_design", "nae_denoise_profile_f32", "nae_denoise_block_f32", "nae_denoise_create", "nae_denoise_put", "nae_denoise_put_host",
     "nae_denoise_flush", "nae_denoise_available", "nae_denoise_receive", "nae_denoise_receive_host", "nae_denoise_destroy",
     "nae_loud_design", "nae_loud_lufs", "nae_loud_measure_f32", "nae_loud_apply_f32", "nae_loud_normalize_f32", "nae_loud_create", "nae_loud_put",
@@ -70,7 +72,9 @@ MOD_MIN_DELAY, MOD_MAX_DELAY, MOD_MAX_VOICES, MOD_MAX_FEEDBACK = 2.0, 3070.0, 4,
 MOD_SHAPES = ("sine", "triangle")                   # `shape` of nae_mod_params: NAE_MOD_SINE, NAE_MOD_TRIANGLE
 SAT_HALF, SAT_MAX_OS = 16, 8                        # NAE_SAT_HALF, NAE_SAT_MAX_OS (include/nae_dsp_spec.h)
 SAT_CURVES = ("soft", "hard")                       # `curve` of nae_sat_params: NAE_SAT_SOFT, NAE_SAT_HARD
-HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat")   # the handles with the full put / receive set of entries
+GATE_MAX_HOLD = 1 << 21                             # NAE_GATE_MAX_HOLD (include/nae_dsp_spec.h)
+GATE_MODES = ("gate", "expander")                   # `mode` of nae_gate_design: NAE_GATE_MODE_GATE, NAE_GATE_MODE_EXPANDER
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat", "nae_gate")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -190,6 +194,15 @@ class SatParams(C.Structure):
         p = SatParams()
         p.oversample, p.curve, p.drive, p.bias, p.wet, p.dry = oversample, curve, drive, bias, wet, dry
         return p
+
+
+class GateParams(C.Structure):
+    """nae_gate_params: the gate's parameters (include/nae_gpu.h): the two thresholds as magnitudes, the expander's threshold and slope, the
+    range, the two smoothing coefficients, hold and look-ahead in samples, the mode and the channel link; nae_gate_design makes them from
+    decibels and times"""
+    _fields_ = [("open_lin", C.c_float), ("close_lin", C.c_float), ("threshold_db", C.c_double), ("slope", C.c_double), ("range_db", C.c_double),
+                ("alpha_attack", C.c_double), ("alpha_release", C.c_double), ("hold", C.c_int), ("lookahead", C.c_int), ("expand", C.c_int),
+                ("link", C.c_int)]
 
 
 class DenoiseParams(C.Structure):
@@ -322,6 +335,8 @@ def load_library() -> C.CDLL:
         "nae_mod_block_f32": (i, [vp, P(ModParams), P(Sig), sz, i, sz, P(Sig)]), "nae_mod_create": (i, [vp, P(ModParams), i, P(vp)]),
         "nae_sat_latency": (i, [i]), "nae_sat_taps": (i, [i, vp]), "nae_sat_design": (i, [d, d, i, i, d, d, P(SatParams)]),
         "nae_sat_block_f32": (i, [vp, P(SatParams), P(Sig), sz, i, sz, P(Sig)]), "nae_sat_create": (i, [vp, P(SatParams), i, P(vp)]),
+        "nae_gate_design": (i, [i, i, d, d, d, d, d, d, d, d, i, P(GateParams)]),
+        "nae_gate_block_f32": (i, [vp, P(GateParams), P(Sig), sz, i, sz, P(Sig)]), "nae_gate_create": (i, [vp, P(GateParams), i, P(vp)]),
         "nae_denoise_design": (i, [d, d, i, i, i, P(DenoiseParams)]), "nae_denoise_profile_f32": (i, [vp, i, P(Sig), sz, i, vp]),
         "nae_denoise_block_f32": (i, [vp, P(DenoiseParams), vp, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
@@ -802,6 +817,24 @@ class Context:
         """the saturation `params` over every stream (nae_sat_block_f32); dst receives in_len frames and must not be src"""
         self._ck(self.lib.nae_sat_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K19
+    @staticmethod
+    def gate_design(sample_rate: int, mode: str = "gate", threshold_db: float = -40.0, hysteresis_db: float = 3.0, range_db: float = 60.0,
+                    ratio: float = 2.0, attack_s: float = 0.001, hold_s: float = 0.05, release_s: float = 0.1, lookahead_s: float = 0.0,
+                    link: bool = True) -> "GateParams":
+        """the gate's parameters from decibels and times (nae_gate_design); mode "expander" reads `ratio`"""
+        out = GateParams()
+        rc = load_library().nae_gate_design(sample_rate, GATE_MODES.index(mode), threshold_db, hysteresis_db, range_db, ratio, attack_s, hold_s,
+                                            release_s, lookahead_s, int(link), C.byref(out))
+        if rc:
+            raise NaeError(f"nae_gate_design({sample_rate}, {mode}, {threshold_db}, {hysteresis_db}, {range_db}, {ratio}, {attack_s}, {hold_s}, "
+                           f"{release_s}, {lookahead_s}, {link}) failed: {rc}")
+        return out
+
+    def gate_block(self, params: "GateParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the gate / expander `params` over every stream (nae_gate_block_f32); dst receives in_len frames, compensated for the look-ahead"""
+        self._ck(self.lib.nae_gate_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     # -- K12
     @staticmethod
     def dyn_design(sample_rate: int, threshold_db: float = -18.0, ratio: float = 4.0, knee_db: float = 6.0, attack_s: float = 0.005,
@@ -1047,6 +1080,17 @@ class Sat(_Handle):
     def __init__(self, ctx: Context, params: SatParams, channels: int):
         super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_sat_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+
+class Gate(_Handle):
+    """The gate's streaming handle (nae_gate_create): put interleaved f32, flush, receive.  Before the flush the whole chunks of 1024 frames
+    with `lookahead` frames behind them are available."""
+
+    _prefix = "nae_gate"
+
+    def __init__(self, ctx: Context, params: GateParams, channels: int):
+        super().__init__(ctx, channels)
+        ctx._ck(ctx.lib.nae_gate_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
 
 
 class Denoise(_Handle):

@@ -355,6 +355,15 @@ int nae_launch_sat(nae_ctx* ctx, const nae_sat_params* p, const nae_sig* src, si
                    size_t c_origin, size_t c_stop);
 int nae_pick_sat_tile(nae_ctx* ctx, size_t chunks, size_t n_sc);
 
+// kernels_gate.hip: the gate ("K19 gate").  nae_gate_check: the parameter rules of the block call and the handle.
+// nae_gate_detectors: one per stream with `link` on stereo, else one per stream-channel.  nae_launch_gate runs chunks [c_origin, c_stop) of
+// absolutely indexed signals of in_len samples; d_state, three 64-bit words per detector, holds the carries in front of chunk c_origin (the
+// hysteresis state, the last set sample or -1, y's bits) and then the ones in front of chunk c_stop; null: the start of a stream, nothing kept.
+int nae_gate_check(nae_ctx* ctx, const nae_gate_params* p, int ch);
+size_t nae_gate_detectors(const nae_gate_params* p, int ch, size_t n_streams);
+int nae_launch_gate(nae_ctx* ctx, const nae_gate_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
+                    size_t c_origin, size_t c_stop, long long* d_state);
+
 // kernels_denoise.hip: the spectral gate ("K13 spectral gate").  nae_denoise_check: the parameter rules of the block call and the
 // handle.  nae_launch_denoise runs hop blocks [b_origin, b_stop) of absolutely indexed signals of in_len samples: it reads from
 // (b_origin - time_smooth - 3) H on and, in front of a block, time_smooth + 3 blocks ahead (zero from in_len on), and keeps nothing between launches.

@@ -105,6 +105,14 @@ struct nae_sat : BlockHandle {
     int process() override;
 };
 
+// the gate's handle ("K19 gate"): whole chunks of NAE_DYN_CHUNK samples are computed once the `lookahead` samples behind them are
+// there; the detectors' carries in front of the next chunk stay on the device between two launches
+struct nae_gate : BlockHandle {
+    nae_gate_params params;
+    long long* d_state = nullptr;  // [detector][3]: the hysteresis state, the last set sample or -1, and y's bits in front of the next chunk
+    int process() override;
+};
+
 // the spectral gate's handle ("K13 spectral gate"): whole hop blocks of n_fft / 4 samples are computed once the time_smooth + 3
 // blocks behind them are there; the input stays from time_smooth + 3 blocks in front of the next block on, and nothing else is kept
 struct nae_denoise : BlockHandle {
@@ -376,6 +384,13 @@ int nae_sat::process()
 {
     return run_units(NAE_EQ_CHUNK, 0, 1, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
         return nae_launch_sat(ctx, &params, &src, in.total, ch, 1, &dst, from, to);
+    });
+}
+
+int nae_gate::process()
+{
+    return run_units(NAE_DYN_CHUNK, (size_t)params.lookahead, 0, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
+        return nae_launch_gate(ctx, &params, &src, in.total, ch, 1, &dst, from, to, d_state);
     });
 }
 
@@ -747,6 +762,40 @@ size_t nae_sat_available(nae_sat* h) { return handle_available(h); }
 int nae_sat_receive(nae_sat* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_sat_receive_host(nae_sat* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_sat_destroy(nae_sat* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ gate
+int nae_gate_create(nae_ctx* ctx, const nae_gate_params* params, int channels, nae_gate** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_gate_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_gate* s = handle_new<nae_gate>(ctx, channels);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    // in front of sample 0: closed, no set sample, and the y an endless silence leaves
+    long long first[2][3];
+    const size_t n_det = nae_gate_detectors(params, channels, 1);
+    for (size_t d = 0; d < n_det; d++) {
+        first[d][0] = 0;
+        first[d][1] = -1;
+        memcpy(&first[d][2], &params->range_db, sizeof(double));
+    }
+    rc = s->dev_alloc(&s->d_state, n_det * 3, "hipMalloc(gate state)");
+    if (!rc) rc = nae_check(ctx, hipMemcpyAsync(s->d_state, first, n_det * 3 * sizeof(long long), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(gate state)");
+    if (!rc) rc = nae_check(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(gate state)");   // `first` is this call's
+    return handle_created(s, rc, h);
+}
+
+int nae_gate_put(nae_gate* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_gate_put_host(nae_gate* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+// flush: the chunks that waited for their look-ahead and the partial last one come out: as many frames as were put over the handle's life
+int nae_gate_flush(nae_gate* h) { return handle_flush(h); }
+size_t nae_gate_available(nae_gate* h) { return handle_available(h); }
+int nae_gate_receive(nae_gate* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_gate_receive_host(nae_gate* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_gate_destroy(nae_gate* h) { return handle_destroy(h); }
 
 // ------------------------------------------------------------------------------------------------ spectral gate
 int nae_denoise_create(nae_ctx* ctx, const nae_denoise_params* params, const float* profile_dev, int profile_ch, int channels, nae_denoise** h)

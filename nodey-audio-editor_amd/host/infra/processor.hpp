@@ -165,4 +165,6 @@ namespace infra
 	void register_modulation_processors();
 	// the saturation (audio_saturation): called after the ten above, each of which stays the list it was
 	void register_saturation_processors();
+	// the gate (audio_gate): called after the eleven above, each of which stays the list it was
+	void register_gate_processors();
 }

@@ -1,5 +1,5 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
-// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
+// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat), Audio_gate (nae_gate) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 // Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
 #include "audio-filter.hpp"
@@ -10,6 +10,7 @@
 #include "audio-echo.hpp"
 #include "audio-modulation.hpp"
 #include "audio-saturation.hpp"
+#include "audio-gate.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "node-util.hpp"
@@ -921,6 +922,93 @@ namespace processor
 				nae_sat* sat = nullptr;
 				gpu::check(nae_sat_create(ctx, &params, ch, &sat), "nae_sat_create");
 				return sat;
+			}
+		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_gate
+	infra::Processor::Info Audio_gate::get_processor_info()
+	{
+		return {"audio_gate", "Audio Gate", false, [] { return std::unique_ptr<infra::Processor>(new Audio_gate); },
+				"Noise gate / downward expander: threshold, hysteresis, range, attack, hold, release, look-ahead (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_gate::get_pin_attributes() const { return io_pins(); }
+
+	Json::Value Audio_gate::serialize() const
+	{
+		Json::Value value;
+		if (mode != Mode::Gate) value["mode"] = "expander";
+		if (threshold_db != default_threshold_db) value["threshold_db"] = threshold_db;
+		if (hysteresis_db != default_hysteresis_db) value["hysteresis_db"] = hysteresis_db;
+		if (range_db != default_range_db) value["range_db"] = range_db;
+		if (ratio != default_ratio) value["ratio"] = ratio;
+		if (attack_ms != default_attack_ms) value["attack_ms"] = attack_ms;
+		if (hold_ms != default_hold_ms) value["hold_ms"] = hold_ms;
+		if (release_ms != default_release_ms) value["release_ms"] = release_ms;
+		if (lookahead_ms != default_lookahead_ms) value["lookahead_ms"] = lookahead_ms;
+		if (!link_channels) value["link_channels"] = false;
+		return value;
+	}
+
+	void Audio_gate::deserialize(const Json::Value& value)
+	{
+		const auto wrong = [](const char* field) { return wrong_field("Audio_gate", field); };
+		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
+		Mode m = Mode::Gate;
+		if (value.isMember("mode"))
+		{
+			if (!value["mode"].isString()) throw wrong("mode");
+			const std::string name = value["mode"].asString();
+			if (name == "expander") m = Mode::Expander;
+			else if (name != "gate") throw wrong("mode");
+		}
+		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_gate", key, lo, hi, fallback); };
+		const double t = real("threshold_db", -90.0, 0.0, default_threshold_db);
+		const double hy = real("hysteresis_db", 0.0, 24.0, default_hysteresis_db);
+		const double rg = real("range_db", 0.0, 120.0, default_range_db);
+		const double r = real("ratio", 1.0, 100.0, default_ratio);
+		const double a = real("attack_ms", 0.0, 500.0, default_attack_ms);
+		const double h = real("hold_ms", 0.0, 10000.0, default_hold_ms);
+		const double rl = real("release_ms", 1.0, 5000.0, default_release_ms);
+		const double la = real("lookahead_ms", 0.0, 20.0, default_lookahead_ms);
+		bool link = true;
+		if (value.isMember("link_channels"))
+		{
+			if (!value["link_channels"].isBool()) throw wrong("link_channels");
+			link = value["link_channels"].asBool();
+		}
+		mode = m;
+		threshold_db = t; hysteresis_db = hy; range_db = rg; ratio = r; attack_ms = a; hold_ms = h; release_ms = rl; lookahead_ms = la;
+		link_channels = link;
+	}
+
+	void Audio_gate::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Gate");
+		run_on_handle<nae_gate>(
+			io.input, io.output, stop_token, {"nae_gate", nae_gate_put, nae_gate_flush, nae_gate_available, nae_gate_receive, nae_gate_destroy}, "node", 0,
+			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
+			{
+				// the settings as the library's parameters at the stream's sample rate; a look-ahead too long for that rate is the user's error
+				nae_gate_params params;
+				const int rc = nae_gate_design(frame->sample_rate, mode == Mode::Expander ? NAE_GATE_MODE_EXPANDER : NAE_GATE_MODE_GATE, threshold_db,
+											   hysteresis_db, range_db, ratio, attack_ms / 1000.0, hold_ms / 1000.0, release_ms / 1000.0, lookahead_ms / 1000.0,
+											   link_channels ? 1 : 0, &params);
+				if (rc == NAE_ERR_UNSUPPORTED)
+					throw infra::Processor::Runtime_error("Look-ahead too long", "The look-ahead must not exceed 1024 samples at the stream's sample rate.",
+										infra::fmt("lookahead %g ms, hold %g ms at %d Hz", lookahead_ms, hold_ms, frame->sample_rate));
+				if (rc != NAE_OK)
+					throw infra::Processor::Runtime_error("Invalid gate parameters", "A parameter of the gate node lies outside its range.",
+										infra::fmt("nae_gate_design at %d Hz: code %d", frame->sample_rate, rc));
+				nae_gate* gate = nullptr;
+				gpu::check(nae_gate_create(ctx, &params, ch, &gate), "nae_gate_create");
+				return gate;
 			}
 		);
 	}

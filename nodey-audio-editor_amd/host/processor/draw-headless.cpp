@@ -21,6 +21,7 @@
 #include "audio-echo.hpp"
 #include "audio-modulation.hpp"
 #include "audio-saturation.hpp"
+#include "audio-gate.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "audio-mix.hpp"
@@ -171,6 +172,21 @@ namespace processor
 		oversample = oversample >= 8 ? 8 : oversample >= 4 ? 4 : oversample >= 2 ? 2 : 1;
 		output_db = std::clamp(output_db, -24.0, 24.0);
 		mix = std::clamp(mix, 0.0, 1.0);
+		return false;
+	}
+
+	void Audio_gate::draw_title() {}
+	bool Audio_gate::draw_content(bool)
+	{
+		// what the widgets would keep: every value inside its range
+		threshold_db = std::clamp(threshold_db, -90.0, 0.0);
+		hysteresis_db = std::clamp(hysteresis_db, 0.0, 24.0);
+		range_db = std::clamp(range_db, 0.0, 120.0);
+		ratio = std::clamp(ratio, 1.0, 100.0);
+		attack_ms = std::clamp(attack_ms, 0.0, 500.0);
+		hold_ms = std::clamp(hold_ms, 0.0, 10000.0);
+		release_ms = std::clamp(release_ms, 1.0, 5000.0);
+		lookahead_ms = std::clamp(lookahead_ms, 0.0, 20.0);
 		return false;
 	}
 

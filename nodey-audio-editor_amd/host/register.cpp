@@ -13,6 +13,7 @@
 #include "processor/audio-echo.hpp"
 #include "processor/audio-modulation.hpp"
 #include "processor/audio-saturation.hpp"
+#include "processor/audio-gate.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -67,4 +68,7 @@ namespace infra
 
 	// the nonlinear effects: drive, saturation and clipping; a call of its own, so the ten lists above stay what they were
 	void register_saturation_processors() { register_each<processor::Audio_saturation>(); }
+
+	// the gate and downward expander; a call of its own, so the eleven lists above stay what they were
+	void register_gate_processors() { register_each<processor::Audio_gate>(); }
 }
