@@ -19,15 +19,21 @@ namespace processor
 	// has arrived or the stream ends, computes one profile per channel on the device (nae_denoise_profile_f32) and then runs everything it held
 	// and the rest through the gate.  A stream that ends with fewer than fft_size samples in the stretch is a Runtime_error.  The node delivers
 	// exactly the frames it received, as packed float frames of their sizes, pts and time base, and flushes at the end of the stream.
-	class Audio_denoise : public infra::Processor
+	// the keys above as a plain copyable record: the node is one
+	struct Denoise_settings
 	{
-	  public:
-
 		static constexpr double default_reduction_db = 12, default_sensitivity_db = 6, default_profile_start_ms = 0, default_profile_ms = 500;
 		static constexpr int default_fft_size = 2048, default_time_smooth = 2, default_freq_smooth = 2;
 		double reduction_db = default_reduction_db, sensitivity_db = default_sensitivity_db, profile_start_ms = default_profile_start_ms,
 			   profile_ms = default_profile_ms;
 		int fft_size = default_fft_size, time_smooth = default_time_smooth, freq_smooth = default_freq_smooth;
+
+		void clamp();   // what the widgets would keep; the fields are stated once, in audio-effects.cpp (node-fields.hpp)
+	};
+
+	class Audio_denoise : public infra::Processor, public Denoise_settings
+	{
+	  public:
 
 		static infra::Processor::Info get_processor_info();
 		Processor::Info get_processor_info_non_static() const override { return get_processor_info(); }

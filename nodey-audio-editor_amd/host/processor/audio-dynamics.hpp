@@ -20,9 +20,7 @@ namespace processor
 	// are designed from the stream's sample rate when the first frame arrives (nae_dyn_design); a look-ahead of more than 1024 samples at
 	// that rate is a Runtime_error then.  The node delivers exactly the frames it received, as packed float frames of their sizes, pts and
 	// time base — the look-ahead is compensated — and flushes at the end of the stream.
-	// the nine keys as a record of its own: the dynamics node is one, and the side-chain node (audio-sidechain.hpp) holds one.  from_json reads
-	// and checks every key before it changes anything (node_name: the reader's name in the error); to_json leaves the defaults out; clamp is
-	// what the widgets would keep.  Bodies: audio-effects.cpp.
+	// the nine keys as a plain copyable record: the dynamics node is one, and the side-chain node (audio-sidechain.hpp) holds one
 	struct Dynamics_settings
 	{
 		enum class Mode { Compressor = 0, Limiter };
@@ -33,9 +31,7 @@ namespace processor
 			   release_ms = default_release_ms, lookahead_ms = default_lookahead_ms, makeup_db = default_makeup_db;
 		bool link_channels = true;
 
-		Json::Value to_json() const;
-		void from_json(const Json::Value& value, const char* node_name);
-		void clamp();
+		void clamp();   // what the widgets would keep; the fields are stated once, in audio-effects.cpp (node-fields.hpp)
 	};
 
 	class Audio_dynamics : public infra::Processor, public Dynamics_settings

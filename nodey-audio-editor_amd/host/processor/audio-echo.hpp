@@ -21,16 +21,22 @@ namespace processor
 	// are designed from the stream's sample rate when the first frame arrives (nae_echo_design); a delay under 1024 or above 1048576 samples
 	// at that rate, or a corner at or above Nyquist, is a Runtime_error then.  The node delivers exactly the frames it received, as packed
 	// float frames of their sizes, pts and time base, and flushes at the end of the stream: the repeats that would sound after it are dropped.
-	class Audio_echo : public infra::Processor
+	// the keys above as a plain copyable record: the node is one
+	struct Echo_settings
 	{
-	  public:
-
 		static constexpr double default_delay_ms = 350, default_feedback = 0.4, default_damp_hz = 0, default_lowcut_hz = 0, default_wet = 0.35,
 								default_dry = 1;
 		double delay_ms = default_delay_ms;
 		std::optional<double> delay_ms_right;   // none: the left delay
 		double feedback = default_feedback, damp_hz = default_damp_hz, lowcut_hz = default_lowcut_hz, wet = default_wet, dry = default_dry;
 		bool ping_pong = false;
+
+		void clamp();   // what the widgets would keep; the fields are stated once, in audio-effects.cpp (node-fields.hpp)
+	};
+
+	class Audio_echo : public infra::Processor, public Echo_settings
+	{
+	  public:
 
 		static infra::Processor::Info get_processor_info();
 		Processor::Info get_processor_info_non_static() const override { return get_processor_info(); }

@@ -2,6 +2,10 @@
 // Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat), Audio_gate (nae_gate) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 // Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
+// A node's parameters are stated once: the members and their defaults in the settings record of audio-<node>.hpp, and here, in front of the
+// node, ONE list of fields (node-fields.hpp) with each key, its bounds and whatever rule the plain range does not say.  serialize, deserialize
+// and the record's clamp (draw-headless.cpp's draw_content) are one call on that list each.  A new node adds its record, its list, those
+// three calls and its process_payload; a rule between two fields (the filter's taps against its frame size) is written by hand next to the calls.
 #include "audio-filter.hpp"
 #include "audio-reverb.hpp"
 #include "audio-eq.hpp"
@@ -13,7 +17,7 @@
 #include "audio-gate.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
-#include "node-util.hpp"
+#include "node-fields.hpp"
 #include "nae_dsp_spec.h"
 
 #include <algorithm>
@@ -141,6 +145,20 @@ namespace processor
 	namespace
 	{
 		const char* const kind_names[] = {"lowpass", "highpass", "bandpass", "bandstop"};
+		// a corner lies inside (0, 1e9), both ends open; the widgets keep it from 1 Hz up
+		constexpr Rule<float> corner{[](double hz, double lo, double hi) { return hz > lo && hz < hi; }, above_lo_unbounded<1.0f>.keep};
+		// an odd tap count; clamp makes an even one the next odd one
+		constexpr Rule<int> odd{[](int n, int, int) { return (n & 1) == 1; }, [](int n, int lo, int hi) { return std::clamp(n, lo, hi) | 1; }};
+		// one of the library's frame sizes (512, 1024, 2048, 4096), 0 when absent: the library's pick
+		constexpr Rule<int> frame_size{[](int n, int, int) { return nae_fir_pick_n_fft(n / 2 + 1) == n; }, as_it_is<int>};
+		constexpr Number filter_fft_size{"fft_size", &Filter_settings::fft_size, 0, 1, 4096, frame_size};
+		constexpr std::tuple filter_fields{
+			Choice{"kind", &Filter_settings::kind, kind_names},
+			Number{"f_lo", &Filter_settings::f_lo, Filter_settings::default_f_lo, 0.0, 1e9, corner},
+			Number{"f_hi", &Filter_settings::f_hi, Filter_settings::default_f_hi, 0.0, 1e9, corner},
+			Number{"taps", &Filter_settings::taps, Filter_settings::default_taps, 1, Filter_settings::max_taps, odd},
+			filter_fft_size,
+		};
 	}
 
 	infra::Processor::Info Audio_filter::get_processor_info()
@@ -151,47 +169,17 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_filter::get_pin_attributes() const { return io_pins(); }
 
-	Json::Value Audio_filter::serialize() const
-	{
-		Json::Value value;
-		if (kind != Kind::Lowpass) value["kind"] = kind_names[(int)kind];
-		if (f_lo != default_f_lo) value["f_lo"] = f_lo;
-		if (f_hi != default_f_hi) value["f_hi"] = f_hi;
-		if (taps != default_taps) value["taps"] = taps;
-		if (fft_size != 0) value["fft_size"] = fft_size;
-		return value;
-	}
+	Json::Value Audio_filter::serialize() const { return to_json(*this, filter_fields); }
 
 	void Audio_filter::deserialize(const Json::Value& value)
 	{
-		const auto wrong = [](const char* field) { return wrong_field("Audio_filter", field); };
-		// everything is read and checked first: a rejected value leaves the node as it was
-		Kind k = Kind::Lowpass;
-		if (value.isMember("kind"))
-		{
-			int found = -1;
-			if (value["kind"].isString())
-				for (int i = 0; i < 4; i++)
-					if (value["kind"].asString() == kind_names[i]) found = i;
-			if (found < 0) throw wrong("kind");
-			k = (Kind)found;
-		}
-		const auto hertz = [&](const char* key, float fallback) {
-			if (!value.isMember(key)) return fallback;
-			if (!value[key].isDouble() || !(value[key].asDouble() > 0.0 && value[key].asDouble() < 1e9)) throw wrong(key);
-			return value[key].asFloat();
-		};
-		const float lo = hertz("f_lo", default_f_lo), hi = hertz("f_hi", default_f_hi);
-		const int n_taps = int_from_json(value, "Audio_filter", "taps", 1, 4096, default_taps);
-		if (n_taps > max_taps || (n_taps & 1) == 0) throw wrong("taps");
-		const int n_fft = int_from_json(value, "Audio_filter", "fft_size", 1, 4096, 0);
-		if (value.isMember("fft_size") && (nae_fir_pick_n_fft(n_fft / 2 + 1) != n_fft || n_taps > n_fft / 2 + 1)) throw wrong("fft_size");
-		kind = k;
-		f_lo = lo;
-		f_hi = hi;
-		taps = n_taps;
-		fft_size = n_fft;
+		const Filter_settings read = from_json<Filter_settings>(value, "Audio_filter", filter_fields);
+		// a frame size that was given must hold the taps
+		if (read.fft_size != 0 && read.taps > read.fft_size / 2 + 1) throw wrong_field("Audio_filter", filter_fft_size.key);
+		Filter_settings::operator=(read);
 	}
+
+	void Filter_settings::clamp() { detail::clamp(*this, filter_fields); }
 
 	void Audio_filter::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
@@ -229,42 +217,38 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_reverb::get_pin_attributes() const { return io_pins(); }
 
-	Json::Value Audio_reverb::serialize() const
+	namespace
 	{
-		Json::Value value;
-		if (rt60 != default_rt60) value["rt60"] = rt60;
-		if (predelay_ms != default_predelay_ms) value["predelay_ms"] = predelay_ms;
-		if (wet != default_wet) value["wet"] = wet;
-		if (dry != default_dry) value["dry"] = dry;
-		if (seed != 1) value["seed"] = (double)seed;   // below 2^53 (deserialize): exact
-		if (fft_size != 0) value["fft_size"] = fft_size;
-		return value;
+		// an exact integer below 2^53, written as a double; not clamped
+		struct Seed
+		{
+			const char* key;
+
+			void write(const Reverb_settings& r, Json::Value& value) const { if (r.seed != Reverb_settings::default_seed) value[key] = (double)r.seed; }
+			void read(Reverb_settings& r, const Json::Value& value, const char* node_name) const
+			{
+				r.seed = Reverb_settings::default_seed;
+				if (!value.isMember(key)) return;
+				// compared as a double with the range first: a number outside the integer range is never converted
+				const Json::Value& v = value[key];
+				if (!v.isDouble() || !(v.asDouble() >= 0.0 && v.asDouble() < 9007199254740992.0) || v.asDouble() != (double)(uint64_t)v.asDouble()) throw wrong_field(node_name, key);
+				r.seed = (uint64_t)v.asDouble();
+			}
+			void keep(Reverb_settings&) const {}
+		};
+		constexpr std::tuple reverb_fields{
+			Number{"rt60", &Reverb_settings::rt60, Reverb_settings::default_rt60, 0.1, 5.0},
+			Number{"predelay_ms", &Reverb_settings::predelay_ms, Reverb_settings::default_predelay_ms, 0.0, 200.0},
+			Number{"wet", &Reverb_settings::wet, Reverb_settings::default_wet, 0.0, 1.0},
+			Number{"dry", &Reverb_settings::dry, Reverb_settings::default_dry, 0.0, 1.0},
+			Seed{"seed"},
+			Number{"fft_size", &Reverb_settings::fft_size, 0, 1, 4096, frame_size},   // the filter's sizes
+		};
 	}
 
-	void Audio_reverb::deserialize(const Json::Value& value)
-	{
-		const auto wrong = [](const char* field) { return wrong_field("Audio_reverb", field); };
-		// everything is read and checked first: a rejected value leaves the node as it was
-		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_reverb", key, lo, hi, fallback); };
-		const double r = real("rt60", 0.1, 5.0, default_rt60), p = real("predelay_ms", 0.0, 200.0, default_predelay_ms);
-		const double w = real("wet", 0.0, 1.0, default_wet), d = real("dry", 0.0, 1.0, default_dry);
-		uint64_t sd = 1;
-		if (value.isMember("seed"))
-		{
-			// compared as a double with the range first: a number outside the integer range is never converted
-			const Json::Value& v = value["seed"];
-			if (!v.isDouble() || !(v.asDouble() >= 0.0 && v.asDouble() < 9007199254740992.0) || v.asDouble() != (double)(uint64_t)v.asDouble()) throw wrong("seed");
-			sd = (uint64_t)v.asDouble();
-		}
-		const int n_fft = int_from_json(value, "Audio_reverb", "fft_size", 1, 4096, 0);
-		if (value.isMember("fft_size") && nae_fir_pick_n_fft(n_fft / 2 + 1) != n_fft) throw wrong("fft_size");   // the filter's sizes: 512, 1024, 2048, 4096
-		rt60 = r;
-		predelay_ms = p;
-		wet = w;
-		dry = d;
-		seed = sd;
-		fft_size = n_fft;
-	}
+	Json::Value Audio_reverb::serialize() const { return to_json(*this, reverb_fields); }
+	void Audio_reverb::deserialize(const Json::Value& value) { Reverb_settings::operator=(from_json<Reverb_settings>(value, "Audio_reverb", reverb_fields)); }
+	void Reverb_settings::clamp() { detail::clamp(*this, reverb_fields); }
 
 	void Audio_reverb::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
@@ -307,51 +291,39 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_eq::get_pin_attributes() const { return io_pins(); }
 
-	static const char* const eq_kind_names[] = {"peak", "lowshelf", "highshelf", "lowpass", "highpass", "notch"};
+	namespace
+	{
+		const char* const eq_kind_names[] = {"peak", "lowshelf", "highshelf", "lowpass", "highpass", "notch"};
+		constexpr std::tuple band_fields{
+			Choice{"kind", &Audio_eq::Band::kind, eq_kind_names},
+			Number{"freq", &Audio_eq::Band::freq, Audio_eq::Band::default_freq, 0.0, 1e9, above_lo_unbounded<1.0>},
+			Number{"gain_db", &Audio_eq::Band::gain_db, Audio_eq::Band::default_gain_db, -24.0, 24.0},
+			Number{"q", &Audio_eq::Band::q, Audio_eq::Band::default_q, 0.1, 40.0},
+		};
+	}
+
+	void Audio_eq::Band::clamp() { detail::clamp(*this, band_fields); }
 
 	// a list of bands in audio_eq's format, which audio_sidechain's "key_filter" has too: the defaults are not written
 	static Json::Value bands_to_json(const std::vector<Audio_eq::Band>& bands)
 	{
 		Json::Value list(Json::arrayValue);
-		for (const Audio_eq::Band& b : bands)
-		{
-			Json::Value v;
-			if (b.kind != Audio_eq::Kind::Peak) v["kind"] = eq_kind_names[(int)b.kind];
-			if (b.freq != Audio_eq::Band::default_freq) v["freq"] = b.freq;
-			if (b.gain_db != Audio_eq::Band::default_gain_db) v["gain_db"] = b.gain_db;
-			if (b.q != Audio_eq::Band::default_q) v["q"] = b.q;
-			list.append(v);
-		}
+		for (const Audio_eq::Band& b : bands) list.append(to_json(b, band_fields));
 		return list;
 	}
 
 	// value[key], if there, as at most max_bands bands; the list's own faults are "Wrong field: <key>", a band's "Wrong field: <its key>"
 	static std::vector<Audio_eq::Band> bands_from_json(const Json::Value& value, const char* node_name, const char* key, size_t max_bands)
 	{
-		const auto wrong = [&](const char* field) { return wrong_field(node_name, field); };
 		std::vector<Audio_eq::Band> read;
 		if (!value.isMember(key)) return read;
 		const Json::Value& list = value[key];
-		if (!list.isArray() || list.size() > max_bands) throw wrong(key);
+		if (!list.isArray() || list.size() > max_bands) throw wrong_field(node_name, key);
 		for (int i = 0; i < (int)list.size(); i++)
 		{
 			const Json::Value& v = list[i];
-			if (v.isArray() || v.isDouble() || v.isBool() || v.isString()) throw wrong(key);   // an object, possibly without a key
-			Audio_eq::Band b;
-			if (v.isMember("kind"))
-			{
-				if (!v["kind"].isString()) throw wrong("kind");
-				int k = 0;
-				while (k < 6 && v["kind"].asString() != eq_kind_names[k]) k++;
-				if (k == 6) throw wrong("kind");
-				b.kind = (Audio_eq::Kind)k;
-			}
-			const auto real = [&](const char* name, double lo, double hi, double fallback) { return real_from_json(v, node_name, name, lo, hi, fallback); };
-			b.freq = real("freq", 0.0, 1e9, Audio_eq::Band::default_freq);
-			if (!(b.freq > 0.0)) throw wrong("freq");
-			b.gain_db = real("gain_db", -24.0, 24.0, Audio_eq::Band::default_gain_db);
-			b.q = real("q", 0.1, 40.0, Audio_eq::Band::default_q);
-			read.push_back(b);
+			if (v.isArray() || v.isDouble() || v.isBool() || v.isString()) throw wrong_field(node_name, key);   // an object, possibly without a key
+			read.push_back(from_json<Audio_eq::Band>(v, node_name, band_fields));
 		}
 		return read;
 	}
@@ -411,62 +383,23 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_dynamics::get_pin_attributes() const { return io_pins(); }
 
-	Json::Value Dynamics_settings::to_json() const
+	namespace
 	{
-		Json::Value value;
-		if (mode != Mode::Compressor) value["mode"] = "limiter";
-		if (threshold_db != default_threshold_db) value["threshold_db"] = threshold_db;
-		if (ratio != default_ratio) value["ratio"] = ratio;
-		if (knee_db != default_knee_db) value["knee_db"] = knee_db;
-		if (attack_ms != default_attack_ms) value["attack_ms"] = attack_ms;
-		if (release_ms != default_release_ms) value["release_ms"] = release_ms;
-		if (lookahead_ms != default_lookahead_ms) value["lookahead_ms"] = lookahead_ms;
-		if (makeup_db != default_makeup_db) value["makeup_db"] = makeup_db;
-		if (!link_channels) value["link_channels"] = false;
-		return value;
+		const char* const dynamics_mode_names[] = {"compressor", "limiter"};
+		constexpr std::tuple dynamics_fields{
+			Choice{"mode", &Dynamics_settings::mode, dynamics_mode_names},
+			Number{"threshold_db", &Dynamics_settings::threshold_db, Dynamics_settings::default_threshold_db, NAE_DYN_MIN_THRESHOLD_DB, NAE_DYN_MAX_THRESHOLD_DB},
+			Number{"ratio", &Dynamics_settings::ratio, Dynamics_settings::default_ratio, 1.0, 100.0},
+			Number{"knee_db", &Dynamics_settings::knee_db, Dynamics_settings::default_knee_db, 0.0, NAE_DYN_MAX_KNEE_DB},
+			Number{"attack_ms", &Dynamics_settings::attack_ms, Dynamics_settings::default_attack_ms, 0.0, 500.0},
+			Number{"release_ms", &Dynamics_settings::release_ms, Dynamics_settings::default_release_ms, 1.0, 5000.0},
+			Number{"lookahead_ms", &Dynamics_settings::lookahead_ms, Dynamics_settings::default_lookahead_ms, 0.0, 20.0},
+			Number{"makeup_db", &Dynamics_settings::makeup_db, Dynamics_settings::default_makeup_db, -NAE_DYN_MAX_MAKEUP_DB, NAE_DYN_MAX_MAKEUP_DB},
+			Flag{"link_channels", &Dynamics_settings::link_channels, true},
+		};
 	}
 
-	void Dynamics_settings::from_json(const Json::Value& value, const char* node_name)
-	{
-		const auto wrong = [&](const char* field) { return wrong_field(node_name, field); };
-		// everything is read and checked first: a rejected value leaves the record as it was; an absent key is its default
-		Mode m = Mode::Compressor;
-		if (value.isMember("mode"))
-		{
-			if (!value["mode"].isString()) throw wrong("mode");
-			const std::string name = value["mode"].asString();
-			if (name == "limiter") m = Mode::Limiter;
-			else if (name != "compressor") throw wrong("mode");
-		}
-		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, node_name, key, lo, hi, fallback); };
-		const double t = real("threshold_db", -60.0, 0.0, default_threshold_db);
-		const double r = real("ratio", 1.0, 100.0, default_ratio);
-		const double k = real("knee_db", 0.0, 24.0, default_knee_db);
-		const double a = real("attack_ms", 0.0, 500.0, default_attack_ms);
-		const double rl = real("release_ms", 1.0, 5000.0, default_release_ms);
-		const double la = real("lookahead_ms", 0.0, 20.0, default_lookahead_ms);
-		const double mk = real("makeup_db", -24.0, 24.0, default_makeup_db);
-		bool link = true;
-		if (value.isMember("link_channels"))
-		{
-			if (!value["link_channels"].isBool()) throw wrong("link_channels");
-			link = value["link_channels"].asBool();
-		}
-		mode = m;
-		threshold_db = t; ratio = r; knee_db = k; attack_ms = a; release_ms = rl; lookahead_ms = la; makeup_db = mk;
-		link_channels = link;
-	}
-
-	void Dynamics_settings::clamp()
-	{
-		threshold_db = std::clamp(threshold_db, -60.0, 0.0);
-		ratio = std::clamp(ratio, 1.0, 100.0);
-		knee_db = std::clamp(knee_db, 0.0, 24.0);
-		attack_ms = std::clamp(attack_ms, 0.0, 500.0);
-		release_ms = std::clamp(release_ms, 1.0, 5000.0);
-		lookahead_ms = std::clamp(lookahead_ms, 0.0, 20.0);
-		makeup_db = std::clamp(makeup_db, -24.0, 24.0);
-	}
+	void Dynamics_settings::clamp() { detail::clamp(*this, dynamics_fields); }
 
 	// the settings as the library's parameters at the stream's sample rate (nae_dyn_design); a look-ahead too long for that rate is the user's error
 	static nae_dyn_params design_dynamics(const Dynamics_settings& s, int sample_rate)
@@ -483,8 +416,8 @@ namespace processor
 		return params;
 	}
 
-	Json::Value Audio_dynamics::serialize() const { return to_json(); }
-	void Audio_dynamics::deserialize(const Json::Value& value) { from_json(value, "Audio_dynamics"); }
+	Json::Value Audio_dynamics::serialize() const { return to_json(*this, dynamics_fields); }
+	void Audio_dynamics::deserialize(const Json::Value& value) { Dynamics_settings::operator=(from_json<Dynamics_settings>(value, "Audio_dynamics", dynamics_fields)); }
 
 	void Audio_dynamics::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
@@ -522,7 +455,7 @@ namespace processor
 
 	Json::Value Audio_sidechain::serialize() const
 	{
-		Json::Value value = dynamics.to_json();
+		Json::Value value = to_json(dynamics, dynamics_fields);
 		if (!key_filter.empty()) value["key_filter"] = bands_to_json(key_filter);
 		return value;
 	}
@@ -530,8 +463,7 @@ namespace processor
 	void Audio_sidechain::deserialize(const Json::Value& value)
 	{
 		// everything is read and checked first: a rejected value leaves the node as it was
-		Dynamics_settings d;
-		d.from_json(value, "Audio_sidechain");
+		const Dynamics_settings d = from_json<Dynamics_settings>(value, "Audio_sidechain", dynamics_fields);
 		std::vector<Audio_eq::Band> bands = bands_from_json(value, "Audio_sidechain", "key_filter", max_bands);
 		dynamics = d;
 		key_filter = std::move(bands);
@@ -711,46 +643,24 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_echo::get_pin_attributes() const { return io_pins(); }
 
-	Json::Value Audio_echo::serialize() const
+	namespace
 	{
-		Json::Value value;
-		if (delay_ms != default_delay_ms) value["delay_ms"] = delay_ms;
-		if (delay_ms_right.has_value()) value["delay_ms_right"] = *delay_ms_right;
-		if (feedback != default_feedback) value["feedback"] = feedback;
-		if (ping_pong) value["ping_pong"] = true;
-		if (damp_hz != default_damp_hz) value["damp_hz"] = damp_hz;
-		if (lowcut_hz != default_lowcut_hz) value["lowcut_hz"] = lowcut_hz;
-		if (wet != default_wet) value["wet"] = wet;
-		if (dry != default_dry) value["dry"] = dry;
-		return value;
+		// a delay has no range of its own but its sign: what it may be depends on the stream's sample rate (process_payload)
+		constexpr std::tuple echo_fields{
+			Number{"delay_ms", &Echo_settings::delay_ms, Echo_settings::default_delay_ms, 0.0, 1e9, above_lo<1.0>},
+			Optional_real{"delay_ms_right", &Echo_settings::delay_ms_right, 0.0, 1e9, above_lo<1.0>},
+			Number{"feedback", &Echo_settings::feedback, Echo_settings::default_feedback, 0.0, 0.95},
+			Flag{"ping_pong", &Echo_settings::ping_pong, false},
+			Number{"damp_hz", &Echo_settings::damp_hz, Echo_settings::default_damp_hz, 0.0, 20000.0, none_or_from<200.0>},
+			Number{"lowcut_hz", &Echo_settings::lowcut_hz, Echo_settings::default_lowcut_hz, 0.0, 2000.0, none_or_from<20.0>},
+			Number{"wet", &Echo_settings::wet, Echo_settings::default_wet, 0.0, 1.0},
+			Number{"dry", &Echo_settings::dry, Echo_settings::default_dry, 0.0, 1.0},
+		};
 	}
 
-	void Audio_echo::deserialize(const Json::Value& value)
-	{
-		const auto wrong = [](const char* field) { return wrong_field("Audio_echo", field); };
-		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
-		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_echo", key, lo, hi, fallback); };
-		// a delay has no range of its own but its sign: what it may be depends on the stream's sample rate (process_payload)
-		const auto delay = [&](const char* key, double fallback) {
-			const double d = real(key, 0.0, 1e9, fallback);
-			if (!(d > 0.0)) throw wrong(key);
-			return d;
-		};
-		// a corner: 0 for none, else inside [lo, hi]
-		const auto corner = [&](const char* key, double lo, double hi) {
-			const double hz = real(key, 0.0, hi, 0.0);
-			if (hz != 0.0 && hz < lo) throw wrong(key);
-			return hz;
-		};
-		const double d = delay("delay_ms", default_delay_ms);
-		std::optional<double> dr;
-		if (value.isMember("delay_ms_right")) dr = delay("delay_ms_right", default_delay_ms);
-		const double g = real("feedback", 0.0, 0.95, default_feedback);
-		const bool pp = bool_from_json(value, "Audio_echo", "ping_pong");
-		const double dh = corner("damp_hz", 200.0, 20000.0), lh = corner("lowcut_hz", 20.0, 2000.0);
-		const double w = real("wet", 0.0, 1.0, default_wet), dy = real("dry", 0.0, 1.0, default_dry);
-		delay_ms = d; delay_ms_right = dr; feedback = g; ping_pong = pp; damp_hz = dh; lowcut_hz = lh; wet = w; dry = dy;
-	}
+	Json::Value Audio_echo::serialize() const { return to_json(*this, echo_fields); }
+	void Audio_echo::deserialize(const Json::Value& value) { Echo_settings::operator=(from_json<Echo_settings>(value, "Audio_echo", echo_fields)); }
+	void Echo_settings::clamp() { detail::clamp(*this, echo_fields); }
 
 	void Audio_echo::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
@@ -794,45 +704,26 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_modulation::get_pin_attributes() const { return io_pins(); }
 
-	Json::Value Audio_modulation::serialize() const
+	namespace
 	{
-		Json::Value value;
-		if (rate_hz != default_rate_hz) value["rate_hz"] = rate_hz;
-		if (delay_ms != default_delay_ms) value["delay_ms"] = delay_ms;
-		if (depth_ms != default_depth_ms) value["depth_ms"] = depth_ms;
-		if (feedback != default_feedback) value["feedback"] = feedback;
-		if (voices != default_voices) value["voices"] = voices;
-		if (spread != default_spread) value["spread"] = spread;
-		if (shape != Shape::Sine) value["shape"] = "triangle";
-		if (wet != default_wet) value["wet"] = wet;
-		if (dry != default_dry) value["dry"] = dry;
-		return value;
+		const char* const shape_names[] = {"sine", "triangle"};
+		// a delay has no range of its own but its sign: what it may be depends on the stream's sample rate (process_payload)
+		constexpr std::tuple modulation_fields{
+			Number{"rate_hz", &Modulation_settings::rate_hz, Modulation_settings::default_rate_hz, 0.0, 20.0},
+			Number{"delay_ms", &Modulation_settings::delay_ms, Modulation_settings::default_delay_ms, 0.0, 1e9, above_lo<0.05>},
+			Number{"depth_ms", &Modulation_settings::depth_ms, Modulation_settings::default_depth_ms, 0.0, 1e9},
+			Number{"feedback", &Modulation_settings::feedback, Modulation_settings::default_feedback, -0.95, 0.95},
+			Number{"voices", &Modulation_settings::voices, Modulation_settings::default_voices, 1, NAE_MOD_MAX_VOICES},
+			Number{"spread", &Modulation_settings::spread, Modulation_settings::default_spread, 0.0, 1.0},
+			Choice{"shape", &Modulation_settings::shape, shape_names},
+			Number{"wet", &Modulation_settings::wet, Modulation_settings::default_wet, 0.0, 1.0},
+			Number{"dry", &Modulation_settings::dry, Modulation_settings::default_dry, 0.0, 1.0},
+		};
 	}
 
-	void Audio_modulation::deserialize(const Json::Value& value)
-	{
-		const auto wrong = [](const char* field) { return wrong_field("Audio_modulation", field); };
-		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
-		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_modulation", key, lo, hi, fallback); };
-		const double r = real("rate_hz", 0.0, 20.0, default_rate_hz);
-		// a delay has no range of its own but its sign: what it may be depends on the stream's sample rate (process_payload)
-		const double d = real("delay_ms", 0.0, 1e9, default_delay_ms);
-		if (!(d > 0.0)) throw wrong("delay_ms");
-		const double dp = real("depth_ms", 0.0, 1e9, default_depth_ms);
-		const double g = real("feedback", -0.95, 0.95, default_feedback);
-		const int v = int_from_json(value, "Audio_modulation", "voices", 1, NAE_MOD_MAX_VOICES, default_voices);
-		const double sp = real("spread", 0.0, 1.0, default_spread);
-		Shape sh = Shape::Sine;
-		if (value.isMember("shape"))
-		{
-			if (!value["shape"].isString()) throw wrong("shape");
-			const std::string name = value["shape"].asString();
-			if (name == "triangle") sh = Shape::Triangle;
-			else if (name != "sine") throw wrong("shape");
-		}
-		const double w = real("wet", 0.0, 1.0, default_wet), dy = real("dry", 0.0, 1.0, default_dry);
-		rate_hz = r; delay_ms = d; depth_ms = dp; feedback = g; voices = v; spread = sp; shape = sh; wet = w; dry = dy;
-	}
+	Json::Value Audio_modulation::serialize() const { return to_json(*this, modulation_fields); }
+	void Audio_modulation::deserialize(const Json::Value& value) { Modulation_settings::operator=(from_json<Modulation_settings>(value, "Audio_modulation", modulation_fields)); }
+	void Modulation_settings::clamp() { detail::clamp(*this, modulation_fields); }
 
 	void Audio_modulation::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
@@ -869,39 +760,26 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_saturation::get_pin_attributes() const { return io_pins(); }
 
-	Json::Value Audio_saturation::serialize() const
+	namespace
 	{
-		Json::Value value;
-		if (drive_db != default_drive_db) value["drive_db"] = drive_db;
-		if (curve != Curve::Soft) value["curve"] = "hard";
-		if (bias != default_bias) value["bias"] = bias;
-		if (oversample != default_oversample) value["oversample"] = oversample;
-		if (output_db != default_output_db) value["output_db"] = output_db;
-		if (mix != default_mix) value["mix"] = mix;
-		return value;
+		const char* const curve_names[] = {"soft", "hard"};
+		// a factor the library has: 1, 2, 4 ... NAE_SAT_MAX_OS; clamp rounds down to one of them
+		constexpr Rule<int> power_of_two{
+			[](int os, int, int) { return nae_sat_latency(os) >= 0; },
+			[](int os, int lo, int hi) { while (hi > lo && hi > os) hi /= 2; return hi; }};
+		constexpr std::tuple saturation_fields{
+			Number{"drive_db", &Saturation_settings::drive_db, Saturation_settings::default_drive_db, 0.0, 48.0},
+			Choice{"curve", &Saturation_settings::curve, curve_names},
+			Number{"bias", &Saturation_settings::bias, Saturation_settings::default_bias, 0.0, 1.0},
+			Number{"oversample", &Saturation_settings::oversample, Saturation_settings::default_oversample, 1, NAE_SAT_MAX_OS, power_of_two},
+			Number{"output_db", &Saturation_settings::output_db, Saturation_settings::default_output_db, -24.0, 24.0},
+			Number{"mix", &Saturation_settings::mix, Saturation_settings::default_mix, 0.0, 1.0},
+		};
 	}
 
-	void Audio_saturation::deserialize(const Json::Value& value)
-	{
-		const auto wrong = [](const char* field) { return wrong_field("Audio_saturation", field); };
-		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
-		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_saturation", key, lo, hi, fallback); };
-		const double dr = real("drive_db", 0.0, 48.0, default_drive_db);
-		Curve cv = Curve::Soft;
-		if (value.isMember("curve"))
-		{
-			if (!value["curve"].isString()) throw wrong("curve");
-			const std::string name = value["curve"].asString();
-			if (name == "hard") cv = Curve::Hard;
-			else if (name != "soft") throw wrong("curve");
-		}
-		const double bs = real("bias", 0.0, 1.0, default_bias);
-		const int os = int_from_json(value, "Audio_saturation", "oversample", 1, NAE_SAT_MAX_OS, default_oversample);
-		if (nae_sat_latency(os) < 0) throw wrong("oversample");
-		const double od = real("output_db", -24.0, 24.0, default_output_db);
-		const double mx = real("mix", 0.0, 1.0, default_mix);
-		drive_db = dr; curve = cv; bias = bs; oversample = os; output_db = od; mix = mx;
-	}
+	Json::Value Audio_saturation::serialize() const { return to_json(*this, saturation_fields); }
+	void Audio_saturation::deserialize(const Json::Value& value) { Saturation_settings::operator=(from_json<Saturation_settings>(value, "Audio_saturation", saturation_fields)); }
+	void Saturation_settings::clamp() { detail::clamp(*this, saturation_fields); }
 
 	void Audio_saturation::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
@@ -935,53 +813,26 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_gate::get_pin_attributes() const { return io_pins(); }
 
-	Json::Value Audio_gate::serialize() const
+	namespace
 	{
-		Json::Value value;
-		if (mode != Mode::Gate) value["mode"] = "expander";
-		if (threshold_db != default_threshold_db) value["threshold_db"] = threshold_db;
-		if (hysteresis_db != default_hysteresis_db) value["hysteresis_db"] = hysteresis_db;
-		if (range_db != default_range_db) value["range_db"] = range_db;
-		if (ratio != default_ratio) value["ratio"] = ratio;
-		if (attack_ms != default_attack_ms) value["attack_ms"] = attack_ms;
-		if (hold_ms != default_hold_ms) value["hold_ms"] = hold_ms;
-		if (release_ms != default_release_ms) value["release_ms"] = release_ms;
-		if (lookahead_ms != default_lookahead_ms) value["lookahead_ms"] = lookahead_ms;
-		if (!link_channels) value["link_channels"] = false;
-		return value;
+		const char* const gate_mode_names[] = {"gate", "expander"};
+		constexpr std::tuple gate_fields{
+			Choice{"mode", &Gate_settings::mode, gate_mode_names},
+			Number{"threshold_db", &Gate_settings::threshold_db, Gate_settings::default_threshold_db, NAE_GATE_MIN_THRESHOLD_DB, NAE_GATE_MAX_THRESHOLD_DB},
+			Number{"hysteresis_db", &Gate_settings::hysteresis_db, Gate_settings::default_hysteresis_db, 0.0, NAE_GATE_MAX_HYSTERESIS_DB},
+			Number{"range_db", &Gate_settings::range_db, Gate_settings::default_range_db, 0.0, NAE_GATE_MAX_RANGE_DB},
+			Number{"ratio", &Gate_settings::ratio, Gate_settings::default_ratio, 1.0, NAE_GATE_MAX_RATIO},
+			Number{"attack_ms", &Gate_settings::attack_ms, Gate_settings::default_attack_ms, 0.0, 500.0},
+			Number{"hold_ms", &Gate_settings::hold_ms, Gate_settings::default_hold_ms, 0.0, 10000.0},
+			Number{"release_ms", &Gate_settings::release_ms, Gate_settings::default_release_ms, 1.0, 5000.0},
+			Number{"lookahead_ms", &Gate_settings::lookahead_ms, Gate_settings::default_lookahead_ms, 0.0, 20.0},
+			Flag{"link_channels", &Gate_settings::link_channels, true},
+		};
 	}
 
-	void Audio_gate::deserialize(const Json::Value& value)
-	{
-		const auto wrong = [](const char* field) { return wrong_field("Audio_gate", field); };
-		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
-		Mode m = Mode::Gate;
-		if (value.isMember("mode"))
-		{
-			if (!value["mode"].isString()) throw wrong("mode");
-			const std::string name = value["mode"].asString();
-			if (name == "expander") m = Mode::Expander;
-			else if (name != "gate") throw wrong("mode");
-		}
-		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_gate", key, lo, hi, fallback); };
-		const double t = real("threshold_db", -90.0, 0.0, default_threshold_db);
-		const double hy = real("hysteresis_db", 0.0, 24.0, default_hysteresis_db);
-		const double rg = real("range_db", 0.0, 120.0, default_range_db);
-		const double r = real("ratio", 1.0, 100.0, default_ratio);
-		const double a = real("attack_ms", 0.0, 500.0, default_attack_ms);
-		const double h = real("hold_ms", 0.0, 10000.0, default_hold_ms);
-		const double rl = real("release_ms", 1.0, 5000.0, default_release_ms);
-		const double la = real("lookahead_ms", 0.0, 20.0, default_lookahead_ms);
-		bool link = true;
-		if (value.isMember("link_channels"))
-		{
-			if (!value["link_channels"].isBool()) throw wrong("link_channels");
-			link = value["link_channels"].asBool();
-		}
-		mode = m;
-		threshold_db = t; hysteresis_db = hy; range_db = rg; ratio = r; attack_ms = a; hold_ms = h; release_ms = rl; lookahead_ms = la;
-		link_channels = link;
-	}
+	Json::Value Audio_gate::serialize() const { return to_json(*this, gate_fields); }
+	void Audio_gate::deserialize(const Json::Value& value) { Gate_settings::operator=(from_json<Gate_settings>(value, "Audio_gate", gate_fields)); }
+	void Gate_settings::clamp() { detail::clamp(*this, gate_fields); }
 
 	void Audio_gate::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
@@ -1022,34 +873,25 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_denoise::get_pin_attributes() const { return io_pins(); }
 
-	Json::Value Audio_denoise::serialize() const
+	namespace
 	{
-		Json::Value value;
-		if (reduction_db != default_reduction_db) value["reduction_db"] = reduction_db;
-		if (sensitivity_db != default_sensitivity_db) value["sensitivity_db"] = sensitivity_db;
-		if (fft_size != default_fft_size) value["fft_size"] = fft_size;
-		if (time_smooth != default_time_smooth) value["time_smooth"] = time_smooth;
-		if (freq_smooth != default_freq_smooth) value["freq_smooth"] = freq_smooth;
-		if (profile_start_ms != default_profile_start_ms) value["profile_start_ms"] = profile_start_ms;
-		if (profile_ms != default_profile_ms) value["profile_ms"] = profile_ms;
-		return value;
+		// a frame size the library has; clamp falls back to the default
+		constexpr bool is_stft_size(int n, int, int) { return n == 512 || n == 1024 || n == 2048 || n == 4096; }
+		constexpr Rule<int> stft_size{is_stft_size, [](int n, int lo, int hi) { return is_stft_size(n, lo, hi) ? n : Denoise_settings::default_fft_size; }};
+		constexpr std::tuple denoise_fields{
+			Number{"reduction_db", &Denoise_settings::reduction_db, Denoise_settings::default_reduction_db, 0.0, NAE_DENOISE_MAX_REDUCTION_DB},
+			Number{"sensitivity_db", &Denoise_settings::sensitivity_db, Denoise_settings::default_sensitivity_db, NAE_DENOISE_MIN_SENSITIVITY_DB, NAE_DENOISE_MAX_SENSITIVITY_DB},
+			Number{"fft_size", &Denoise_settings::fft_size, Denoise_settings::default_fft_size, 512, 4096, stft_size},
+			Number{"time_smooth", &Denoise_settings::time_smooth, Denoise_settings::default_time_smooth, 0, NAE_DENOISE_MAX_TIME},
+			Number{"freq_smooth", &Denoise_settings::freq_smooth, Denoise_settings::default_freq_smooth, 0, NAE_DENOISE_MAX_FREQ},
+			Number{"profile_start_ms", &Denoise_settings::profile_start_ms, Denoise_settings::default_profile_start_ms, 0.0, 60000.0},
+			Number{"profile_ms", &Denoise_settings::profile_ms, Denoise_settings::default_profile_ms, 20.0, 10000.0},
+		};
 	}
 
-	void Audio_denoise::deserialize(const Json::Value& value)
-	{
-		const auto wrong = [](const char* field) { return wrong_field("Audio_denoise", field); };
-		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
-		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_denoise", key, lo, hi, fallback); };
-		const double r = real("reduction_db", 0.0, NAE_DENOISE_MAX_REDUCTION_DB, default_reduction_db);
-		const double s = real("sensitivity_db", NAE_DENOISE_MIN_SENSITIVITY_DB, NAE_DENOISE_MAX_SENSITIVITY_DB, default_sensitivity_db);
-		const int n = int_from_json(value, "Audio_denoise", "fft_size", 512, 4096, default_fft_size);
-		if (n != 512 && n != 1024 && n != 2048 && n != 4096) throw wrong("fft_size");
-		const int tn = int_from_json(value, "Audio_denoise", "time_smooth", 0, NAE_DENOISE_MAX_TIME, default_time_smooth);
-		const int fn = int_from_json(value, "Audio_denoise", "freq_smooth", 0, NAE_DENOISE_MAX_FREQ, default_freq_smooth);
-		const double ps = real("profile_start_ms", 0.0, 60000.0, default_profile_start_ms);
-		const double pm = real("profile_ms", 20.0, 10000.0, default_profile_ms);
-		reduction_db = r; sensitivity_db = s; fft_size = n; time_smooth = tn; freq_smooth = fn; profile_start_ms = ps; profile_ms = pm;
-	}
+	Json::Value Audio_denoise::serialize() const { return to_json(*this, denoise_fields); }
+	void Audio_denoise::deserialize(const Json::Value& value) { Denoise_settings::operator=(from_json<Denoise_settings>(value, "Audio_denoise", denoise_fields)); }
+	void Denoise_settings::clamp() { detail::clamp(*this, denoise_fields); }
 
 	void Audio_denoise::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
@@ -1105,24 +947,18 @@ namespace processor
 
 	std::vector<infra::Processor::Pin_attribute> Audio_loudness::get_pin_attributes() const { return io_pins(); }
 
-	Json::Value Audio_loudness::serialize() const
+	namespace
 	{
-		Json::Value value;
-		if (target_lufs != default_target_lufs) value["target_lufs"] = target_lufs;
-		if (true_peak_db != default_true_peak_db) value["true_peak_db"] = true_peak_db;
-		if (max_gain_db != default_max_gain_db) value["max_gain_db"] = max_gain_db;
-		return value;
+		constexpr std::tuple loudness_fields{
+			Number{"target_lufs", &Loudness_settings::target_lufs, Loudness_settings::default_target_lufs, NAE_LOUD_MIN_TARGET_LUFS, NAE_LOUD_MAX_TARGET_LUFS},
+			Number{"true_peak_db", &Loudness_settings::true_peak_db, Loudness_settings::default_true_peak_db, NAE_LOUD_MIN_CEILING_DBTP, 0.0},
+			Number{"max_gain_db", &Loudness_settings::max_gain_db, Loudness_settings::default_max_gain_db, 0.0, NAE_LOUD_MAX_GAIN_DB},
+		};
 	}
 
-	void Audio_loudness::deserialize(const Json::Value& value)
-	{
-		// everything is read and checked first: a rejected value leaves the node as it was; an absent key is its default
-		const auto real = [&](const char* key, double lo, double hi, double fallback) { return real_from_json(value, "Audio_loudness", key, lo, hi, fallback); };
-		const double t = real("target_lufs", NAE_LOUD_MIN_TARGET_LUFS, NAE_LOUD_MAX_TARGET_LUFS, default_target_lufs);
-		const double p = real("true_peak_db", NAE_LOUD_MIN_CEILING_DBTP, 0.0, default_true_peak_db);
-		const double m = real("max_gain_db", 0.0, NAE_LOUD_MAX_GAIN_DB, default_max_gain_db);
-		target_lufs = t; true_peak_db = p; max_gain_db = m;
-	}
+	Json::Value Audio_loudness::serialize() const { return to_json(*this, loudness_fields); }
+	void Audio_loudness::deserialize(const Json::Value& value) { Loudness_settings::operator=(from_json<Loudness_settings>(value, "Audio_loudness", loudness_fields)); }
+	void Loudness_settings::clamp() { detail::clamp(*this, loudness_fields); }
 
 	void Audio_loudness::process_payload(
 		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,

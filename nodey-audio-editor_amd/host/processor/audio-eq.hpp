@@ -27,6 +27,8 @@ namespace processor
 			static constexpr double default_freq = 1000, default_gain_db = 0, default_q = 0.707;
 			Kind kind = Kind::Peak;
 			double freq = default_freq, gain_db = default_gain_db, q = default_q;
+
+			void clamp();   // what the widgets would keep; the fields are stated once, in audio-effects.cpp (node-fields.hpp)
 		};
 		static constexpr size_t max_bands = 16;
 		std::vector<Band> bands;

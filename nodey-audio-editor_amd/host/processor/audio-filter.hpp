@@ -17,10 +17,9 @@ namespace processor
 	// Runtime_error then).  The node compensates the filter's group delay: it drops the first (L - 1) / 2 filtered frames and flushes at the
 	// end of the stream, so it delivers exactly the frames it received — output sample n is y[n + (L - 1) / 2] — as packed float frames of
 	// the input frames' sizes, pts and time base.
-	class Audio_filter : public infra::Processor
+	// the keys above as a plain copyable record: the node is one
+	struct Filter_settings
 	{
-	  public:
-
 		enum class Kind { Lowpass, Highpass, Bandpass, Bandstop };
 		static constexpr int default_taps = 513, max_taps = 2049;
 		static constexpr float default_f_lo = 100, default_f_hi = 1000;
@@ -28,6 +27,13 @@ namespace processor
 		float f_lo = default_f_lo, f_hi = default_f_hi;
 		int taps = default_taps;
 		int fft_size = 0;  // 0: the library's pick
+
+		void clamp();   // what the widgets would keep; the fields are stated once, in audio-effects.cpp (node-fields.hpp)
+	};
+
+	class Audio_filter : public infra::Processor, public Filter_settings
+	{
+	  public:
 
 		static infra::Processor::Info get_processor_info();
 		Processor::Info get_processor_info_non_static() const override { return get_processor_info(); }

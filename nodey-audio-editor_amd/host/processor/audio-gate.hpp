@@ -24,10 +24,9 @@ namespace processor
 	// A value of the wrong type or outside these ranges: Runtime_error "Wrong field: <key>".  Defaults are not written back.  The
 	// parameters are designed from the stream's sample rate on the first frame; a look-ahead above 1024 samples at that rate is a
 	// Runtime_error then.  The node delivers exactly the frames it received, as packed float frames of their sizes, pts and time base.
-	class Audio_gate : public infra::Processor
+	// the keys above as a plain copyable record: the node is one
+	struct Gate_settings
 	{
-	  public:
-
 		enum class Mode { Gate, Expander };
 		static constexpr double default_threshold_db = -40, default_hysteresis_db = 3, default_range_db = 60, default_ratio = 2, default_attack_ms = 1,
 								default_hold_ms = 50, default_release_ms = 100, default_lookahead_ms = 0;
@@ -35,6 +34,13 @@ namespace processor
 		double threshold_db = default_threshold_db, hysteresis_db = default_hysteresis_db, range_db = default_range_db, ratio = default_ratio,
 			   attack_ms = default_attack_ms, hold_ms = default_hold_ms, release_ms = default_release_ms, lookahead_ms = default_lookahead_ms;
 		bool link_channels = true;
+
+		void clamp();   // what the widgets would keep; the fields are stated once, in audio-effects.cpp (node-fields.hpp)
+	};
+
+	class Audio_gate : public infra::Processor, public Gate_settings
+	{
+	  public:
 
 		static infra::Processor::Info get_processor_info();
 		Processor::Info get_processor_info_non_static() const override { return get_processor_info(); }

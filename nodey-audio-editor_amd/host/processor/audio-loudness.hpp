@@ -17,12 +17,18 @@ namespace processor
 	// the bits of nae_loud_normalize_f32 on the whole stream.  A stream shorter than 400 ms has no gating block and no loudness: its frames pass
 	// as they are, and no GPU is touched.  A sample rate outside 8000 ... 192000 or not a multiple of 10 is a Runtime_error once 400 ms arrived; a frame of another rate than the first's
 	// is one at once.
-	class Audio_loudness : public infra::Processor
+	// the keys above as a plain copyable record: the node is one
+	struct Loudness_settings
 	{
-	  public:
-
 		static constexpr double default_target_lufs = -14, default_true_peak_db = -1, default_max_gain_db = 20;
 		double target_lufs = default_target_lufs, true_peak_db = default_true_peak_db, max_gain_db = default_max_gain_db;
+
+		void clamp();   // what the widgets would keep; the fields are stated once, in audio-effects.cpp (node-fields.hpp)
+	};
+
+	class Audio_loudness : public infra::Processor, public Loudness_settings
+	{
+	  public:
 
 		static infra::Processor::Info get_processor_info();
 		Processor::Info get_processor_info_non_static() const override { return get_processor_info(); }

@@ -22,10 +22,9 @@ namespace processor
 	// are designed from the stream's sample rate when the first frame arrives (nae_mod_design); a delay range [delay - depth, delay + depth]
 	// outside 2 ... 3070 samples at that rate is a Runtime_error then.  The node delivers exactly the frames it received, as packed float
 	// frames of their sizes, pts and time base, and flushes at the end of the stream: what would sound after it is dropped.
-	class Audio_modulation : public infra::Processor
+	// the keys above as a plain copyable record: the node is one
+	struct Modulation_settings
 	{
-	  public:
-
 		enum class Shape { Sine, Triangle };
 		static constexpr double default_rate_hz = 0.8, default_delay_ms = 12, default_depth_ms = 3, default_feedback = 0, default_spread = 0.5,
 								default_wet = 0.5, default_dry = 1;
@@ -34,6 +33,13 @@ namespace processor
 			   spread = default_spread, wet = default_wet, dry = default_dry;
 		int voices = default_voices;
 		Shape shape = Shape::Sine;
+
+		void clamp();   // what the widgets would keep; the fields are stated once, in audio-effects.cpp (node-fields.hpp)
+	};
+
+	class Audio_modulation : public infra::Processor, public Modulation_settings
+	{
+	  public:
 
 		static infra::Processor::Info get_processor_info();
 		Processor::Info get_processor_info_non_static() const override { return get_processor_info(); }

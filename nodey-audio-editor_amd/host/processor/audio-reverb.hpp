@@ -18,14 +18,21 @@ namespace processor
 	// the first frame arrives (nae_conv_design_reverb); one longer than the library's limits is a Runtime_error then.  The node is causal and
 	// uncompensated: it delivers exactly the frames it received, as packed float frames of their sizes, pts and time base, and drops the tail
 	// past the end of the stream.
-	class Audio_reverb : public infra::Processor
+	// the keys above as a plain copyable record: the node is one
+	struct Reverb_settings
 	{
-	  public:
-
 		static constexpr double default_rt60 = 1.5, default_predelay_ms = 20, default_wet = 0.3, default_dry = 1;
 		double rt60 = default_rt60, predelay_ms = default_predelay_ms, wet = default_wet, dry = default_dry;
-		uint64_t seed = 1;
+		static constexpr uint64_t default_seed = 1;
+		uint64_t seed = default_seed;
 		int fft_size = 0;  // 0: the library's pick
+
+		void clamp();   // what the widgets would keep; the fields are stated once, in audio-effects.cpp (node-fields.hpp)
+	};
+
+	class Audio_reverb : public infra::Processor, public Reverb_settings
+	{
+	  public:
 
 		static infra::Processor::Info get_processor_info();
 		Processor::Info get_processor_info_non_static() const override { return get_processor_info(); }

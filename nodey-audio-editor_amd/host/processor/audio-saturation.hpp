@@ -18,16 +18,22 @@ namespace processor
 	// the output carries no offset while the input is silent, but a driven signal gains one: an audio_eq high-pass behind the node removes it.
 	// The node drops the library's latency (32 samples at oversample 2, 4 and 8, none at 1) in front, as audio_filter drops its group
 	// delay, and delivers exactly the frames it received, as packed float frames of their sizes, pts and time base.
-	class Audio_saturation : public infra::Processor
+	// the keys above as a plain copyable record: the node is one
+	struct Saturation_settings
 	{
-	  public:
-
 		enum class Curve { Soft, Hard };
 		static constexpr double default_drive_db = 12, default_bias = 0, default_output_db = 0, default_mix = 1;
 		static constexpr int default_oversample = 4;
 		double drive_db = default_drive_db, bias = default_bias, output_db = default_output_db, mix = default_mix;
 		int oversample = default_oversample;
 		Curve curve = Curve::Soft;
+
+		void clamp();   // what the widgets would keep; the fields are stated once, in audio-effects.cpp (node-fields.hpp)
+	};
+
+	class Audio_saturation : public infra::Processor, public Saturation_settings
+	{
+	  public:
 
 		static infra::Processor::Info get_processor_info();
 		Processor::Info get_processor_info_non_static() const override { return get_processor_info(); }

@@ -1,5 +1,6 @@
 // processor/node-util.hpp — what the nodes of audio-velocity.cpp and audio-effects.cpp share (not part of the plugin interface), each piece
-// written once: the pins and the node's streams (node_streams, with the "has no input" error), the JSON field readers and their error, the way
+// written once: the pins and the node's streams (node_streams, with the "has no input" error), the JSON field readers and their error (a node
+// does not call them key by key: it states its parameters as one list of fields, node-fields.hpp, which stands on these readers), the way
 // out (push_to_all, make_f32_frame, pass_through), the collection of a batch of waiting frames and its upload as interleaved f32, and the two
 // ends of a node that sits on a handle: take_in (frames in, held until enough have come) and cut_and_push (f32 out, as frames of the input's shapes).
 #pragma once
@@ -48,10 +49,10 @@ namespace processor::detail
 		);
 	}
 
-	// an optional bool: no key is false, a value that is not a bool is the wrong field
-	inline bool bool_from_json(const Json::Value& value, const char* node_name, const char* key)
+	// an optional bool: no key is the fallback, a value that is not a bool is the wrong field
+	inline bool bool_from_json(const Json::Value& value, const char* node_name, const char* key, bool fallback = false)
 	{
-		if (!value.isMember(key)) return false;
+		if (!value.isMember(key)) return fallback;
 		if (!value[key].isBool()) throw wrong_field(node_name, key);
 		return value[key].asBool();
 	}

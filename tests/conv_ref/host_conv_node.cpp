@@ -93,19 +93,7 @@ static void test_json()
 	}
 }
 
-static void test_registry()
-{
-	infra::register_all_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 7, "the reference's list: 7 entries");
-	infra::register_extension_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 8 && infra::Processor::processor_map.count("audio_reverb") == 0, "with the extensions: 8 entries, no reverb");
-	infra::register_effect_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 9 && infra::Processor::processor_map.count("audio_reverb") == 1, "with the effects: 9 entries");
-	check_generated("audio_reverb");
-}
+static void test_registry() { check_registry("audio_reverb"); }
 
 static void test_gpu()
 {

@@ -100,22 +100,7 @@ static void test_json()
 	}
 }
 
-static void test_registry()
-{
-	infra::register_all_processors();
-	CHECK(infra::Processor::processor_map.size() == 7, "the reference's list: 7 entries");
-	infra::register_extension_processors();
-	CHECK(infra::Processor::processor_map.size() == 8, "with the filter: 8");
-	infra::register_effect_processors();
-	CHECK(infra::Processor::processor_map.size() == 9, "with the reverb: 9");
-	infra::register_equalizer_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 10 && infra::Processor::processor_map.count("audio_dynamics") == 0, "the four existing calls: 10 entries, no audio_dynamics");
-	infra::register_dynamics_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 11 && infra::Processor::processor_map.count("audio_dynamics") == 1, "with the dynamics node: 11 entries");
-	check_generated("audio_dynamics");
-}
+static void test_registry() { check_registry("audio_dynamics"); }
 
 // noise whose level swells from far under to over the threshold, the right channel quieter: the link matters
 static std::vector<float> noise(size_t frames)

@@ -110,23 +110,7 @@ static void test_json()
 	}
 }
 
-static void test_registry()
-{
-	infra::register_all_processors();
-	infra::register_extension_processors();
-	infra::register_effect_processors();
-	infra::register_equalizer_processors();
-	infra::register_dynamics_processors();
-	infra::register_restoration_processors();
-	infra::register_mastering_processors();
-	infra::register_sidechain_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 14 && infra::Processor::processor_map.count("audio_echo") == 0, "the eight existing calls: 14 entries, no audio_echo");
-	infra::register_echo_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 15 && infra::Processor::processor_map.count("audio_echo") == 1, "with the echo: 15 entries");
-	check_generated("audio_echo");
-}
+static void test_registry() { check_registry("audio_echo"); }
 
 static void graph_case(int channels, const Json::Value& json, double delay_s_left, double delay_s_right, double feedback, double damp_hz, double lowcut_hz,
 					   double wet, double dry, int cross, const char* what)

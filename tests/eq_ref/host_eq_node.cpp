@@ -169,18 +169,7 @@ static void test_json()
 	}
 }
 
-static void test_registry()
-{
-	infra::register_all_processors();
-	infra::register_extension_processors();
-	infra::register_effect_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 9 && infra::Processor::processor_map.count("audio_eq") == 0, "the three existing calls: 9 entries, no audio_eq");
-	infra::register_equalizer_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 10 && infra::Processor::processor_map.count("audio_eq") == 1, "with the equalizer: 10 entries");
-	check_generated("audio_eq");
-}
+static void test_registry() { check_registry("audio_eq"); }
 
 struct Band_spec { const char* kind; double freq, gain_db, q; };
 static const Band_spec graph_bands[] = {{"highpass", 40, 0, 0.7071}, {"peak", 1000, 6, 1}, {"lowshelf", 150, -4, 0.707}, {"notch", 50, 0, 30}, {"highshelf", 9000, 3, 0.9}};

@@ -128,36 +128,7 @@ static void test_json()
 	}
 }
 
-static void test_registry()
-{
-	infra::register_all_processors();
-	CHECK(infra::Processor::processor_map.size() == 7, "the reference's list: 7 entries");
-	infra::register_extension_processors();
-	CHECK(infra::Processor::processor_map.size() == 8, "with the filter: 8");
-	infra::register_effect_processors();
-	CHECK(infra::Processor::processor_map.size() == 9, "with the reverb: 9");
-	infra::register_equalizer_processors();
-	CHECK(infra::Processor::processor_map.size() == 10, "with the equalizer: 10");
-	infra::register_dynamics_processors();
-	CHECK(infra::Processor::processor_map.size() == 11, "with the dynamics: 11");
-	infra::register_restoration_processors();
-	CHECK(infra::Processor::processor_map.size() == 12, "with the noise reduction: 12");
-	infra::register_mastering_processors();
-	CHECK(infra::Processor::processor_map.size() == 13, "with the loudness: 13");
-	infra::register_sidechain_processors();
-	CHECK(infra::Processor::processor_map.size() == 14, "with the side-chain: 14");
-	infra::register_echo_processors();
-	CHECK(infra::Processor::processor_map.size() == 15, "with the echo: 15");
-	infra::register_modulation_processors();
-	CHECK(infra::Processor::processor_map.size() == 16, "with the modulation: 16");
-	infra::register_saturation_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 17 && infra::Processor::processor_map.count("audio_gate") == 0, "the eleven existing calls: 17 entries, no audio_gate");
-	infra::register_gate_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 18 && infra::Processor::processor_map.count("audio_gate") == 1, "with the gate node: 18 entries");
-	check_generated("audio_gate");
-}
+static void test_registry() { check_registry("audio_gate"); }
 
 // noise in stretches of 5000 samples at -6 dB and at -66 dB, the right channel quieter: the gate opens, holds and closes, and the link matters
 static std::vector<float> noise(size_t frames, int channels)

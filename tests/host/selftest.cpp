@@ -7,6 +7,17 @@
 #include "processor/audio-velocity.hpp"
 #include "processor/gpu-context.hpp"
 #include "processor/audio-vol.hpp"
+#include "processor/audio-filter.hpp"
+#include "processor/audio-reverb.hpp"
+#include "processor/audio-eq.hpp"
+#include "processor/audio-dynamics.hpp"
+#include "processor/audio-sidechain.hpp"
+#include "processor/audio-echo.hpp"
+#include "processor/audio-modulation.hpp"
+#include "processor/audio-saturation.hpp"
+#include "processor/audio-gate.hpp"
+#include "processor/audio-denoise.hpp"
+#include "processor/audio-loudness.hpp"
 #include "../../oracle/nae_oracle.h"
 
 #include "processor/bimix-align.hpp"
@@ -341,6 +352,187 @@ static void test_headless_draw_hooks()
 	// audio-amix.cpp:379-387: the unlocked weights are divided by their sum (1.25), a locked one stays
 	CHECK(back["volumes0"].asFloat() == 0.5f / 1.25f && back["volumes1"].asFloat() == 0.25f && back["volumes2"].asFloat() == 0.75f / 1.25f,
 		  "mixer weights renormalised as the GUI does: " << back["volumes0"].asFloat() << " " << back["volumes1"].asFloat() << " " << back["volumes2"].asFloat());
+}
+
+// Two things about the effect nodes' parameters that their own harnesses (tests/*_ref/host_*_node.cpp, one wrong key at a time) do not pin.
+// The reading order: of two wrong keys the earlier one in the node's order is named, an extra rule (odd taps) at its field's place and not
+// behind all fields, and the node keeps what it had.  And what draw_content() keeps where that is not "the JSON range": an open lower bound
+// has a floor of its own, a corner may stay 0, and the integer rules round.  Enums, bools, the reverb's seed and the frame sizes are not touched.
+template <class Node>
+static bool names_first(Node& node, std::initializer_list<std::pair<const char*, Json::Value>> wrong, const std::string& field)
+{
+	Json::Value v;
+	for (const auto& [key, bad] : wrong) v[key] = bad;
+	try { node.deserialize(v); } catch (const infra::Processor::Runtime_error& e) { return e.detail == "Wrong field: " + field; }
+	return false;
+}
+
+static void test_effect_field_order_and_clamps()
+{
+	const auto drawn = [](infra::Processor& node) { return node.draw_content(false) == false; };
+	const auto band_list = [](std::initializer_list<std::pair<const char*, Json::Value>> keys) {
+		Json::Value band, list(Json::arrayValue);
+		for (const auto& [key, v] : keys) band[key] = v;
+		list.append(band);
+		return list;
+	};
+	{
+		Audio_filter f;
+		f.taps = 101;
+		CHECK(names_first(f, {{"f_lo", -1.0}, {"fft_size", 1000}}, "f_lo") && f.taps == 101, "filter: f_lo before fft_size");
+		CHECK(names_first(f, {{"taps", 100}, {"fft_size", 1000}}, "taps") && f.taps == 101, "filter: an even taps before a wrong fft_size");
+		CHECK(names_first(f, {{"taps", 513}, {"fft_size", 512}}, "fft_size") && f.taps == 101, "filter: taps that do not fit the frame size");
+		f.kind = Audio_filter::Kind::Highpass; f.taps = 0; f.f_lo = -5.0f; f.f_hi = 0.5f; f.fft_size = 7;
+		CHECK(drawn(f) && f.taps == 1 && f.f_lo == 1.0f && f.f_hi == 1.0f && f.fft_size == 7 && f.kind == Audio_filter::Kind::Highpass, "filter: floors 1 tap, 1 Hz");
+		f.taps = 5000; f.f_lo = 2e9f; f.f_hi = 3e9f;
+		CHECK(drawn(f) && f.taps == 2049 && f.f_lo == 2e9f && f.f_hi == 3e9f, "filter: at most 2049 taps; the corners have no ceiling");
+		f.taps = 100;
+		CHECK(drawn(f) && f.taps == 101, "filter: an even tap count becomes the next odd one");
+		f.kind = Audio_filter::Kind::Bandpass; f.f_lo = 500.0f; f.f_hi = 100.0f; f.taps = 513; f.fft_size = 512;
+		CHECK(drawn(f) && f.f_lo == 100.0f && f.f_hi == 500.0f && f.fft_size == 0, "filter: a band's corners in order; a frame size the taps do not fit is dropped");
+		f.fft_size = 1024;
+		CHECK(drawn(f) && f.fft_size == 1024, "filter: a frame size the taps fit stays");
+	}
+	{
+		Audio_reverb r;
+		r.wet = 0.7;
+		CHECK(names_first(r, {{"predelay_ms", 300.0}, {"fft_size", 1000}}, "predelay_ms") && r.wet == 0.7, "reverb: predelay_ms before fft_size");
+		CHECK(names_first(r, {{"seed", 0.5}, {"fft_size", 1000}}, "seed") && r.wet == 0.7, "reverb: seed before fft_size");
+		r.rt60 = 0.0; r.predelay_ms = -1.0; r.wet = -1.0; r.dry = -1.0; r.seed = 77; r.fft_size = 123;
+		CHECK(drawn(r) && r.rt60 == 0.1 && r.predelay_ms == 0.0 && r.wet == 0.0 && r.dry == 0.0 && r.seed == 77 && r.fft_size == 123, "reverb: floors; seed and frame size untouched");
+		r.rt60 = 9.0; r.predelay_ms = 500.0; r.wet = 2.0; r.dry = 2.0;
+		CHECK(drawn(r) && r.rt60 == 5.0 && r.predelay_ms == 200.0 && r.wet == 1.0 && r.dry == 1.0 && r.seed == 77 && r.fft_size == 123, "reverb: ceilings");
+	}
+	const auto band_clamps = [&](infra::Processor& node, std::vector<Audio_eq::Band>& bands, size_t max_bands, const char* what) {
+		bands.assign(max_bands + 1, Audio_eq::Band{Audio_eq::Kind::Notch, 0.5, -30.0, 0.01});
+		CHECK(drawn(node) && bands.size() == max_bands, what << ": at most " << max_bands << " bands");
+		bool floors = true, ceilings = true;
+		for (const auto& b : bands) floors = floors && b.kind == Audio_eq::Kind::Notch && b.freq == 1.0 && b.gain_db == -24.0 && b.q == 0.1;
+		CHECK(floors, what << ": band floors 1 Hz, -24 dB, q 0.1");
+		for (auto& b : bands) { b.freq = 5e9; b.gain_db = 30.0; b.q = 100.0; }
+		drawn(node);
+		for (const auto& b : bands) ceilings = ceilings && b.kind == Audio_eq::Kind::Notch && b.freq == 5e9 && b.gain_db == 24.0 && b.q == 40.0;
+		CHECK(ceilings, what << ": band ceilings 24 dB, q 40; the frequency has none");
+	};
+	{
+		Audio_eq e;
+		e.bands.resize(2);
+		Json::Value v;
+		v["bands"] = band_list({{"freq", -1.0}, {"q", 100.0}});
+		bool named = false;
+		try { e.deserialize(v); } catch (const infra::Processor::Runtime_error& x) { named = x.detail == "Wrong field: freq"; }
+		CHECK(named && e.bands.size() == 2, "eq band: freq before q");
+		band_clamps(e, e.bands, Audio_eq::max_bands, "eq");
+	}
+	const auto dynamics_clamps = [&](infra::Processor& node, Dynamics_settings& d, const char* what) {
+		d.mode = Dynamics_settings::Mode::Limiter; d.link_channels = false;
+		d.threshold_db = -100; d.ratio = 0; d.knee_db = -1; d.attack_ms = -1; d.release_ms = 0; d.lookahead_ms = -1; d.makeup_db = -30;
+		CHECK(drawn(node) && d.threshold_db == -60 && d.ratio == 1 && d.knee_db == 0 && d.attack_ms == 0 && d.release_ms == 1 && d.lookahead_ms == 0 && d.makeup_db == -24,
+			  what << ": floors");
+		d.threshold_db = 5; d.ratio = 500; d.knee_db = 30; d.attack_ms = 600; d.release_ms = 9000; d.lookahead_ms = 50; d.makeup_db = 30;
+		CHECK(drawn(node) && d.threshold_db == 0 && d.ratio == 100 && d.knee_db == 24 && d.attack_ms == 500 && d.release_ms == 5000 && d.lookahead_ms == 20 && d.makeup_db == 24,
+			  what << ": ceilings");
+		CHECK(d.mode == Dynamics_settings::Mode::Limiter && !d.link_channels, what << ": mode and link untouched");
+	};
+	{
+		Audio_dynamics d;
+		d.ratio = 8;
+		CHECK(names_first(d, {{"threshold_db", 5.0}, {"link_channels", 1}}, "threshold_db") && d.ratio == 8, "dynamics: threshold_db before link_channels");
+		dynamics_clamps(d, d, "dynamics");
+	}
+	{
+		Audio_sidechain s;
+		s.dynamics.ratio = 8;
+		s.key_filter.resize(1);
+		CHECK(names_first(s, {{"threshold_db", 5.0}, {"key_filter", 3}}, "threshold_db") && s.dynamics.ratio == 8 && s.key_filter.size() == 1, "side-chain: threshold_db before key_filter");
+		CHECK(names_first(s, {{"link_channels", 1}, {"key_filter", 3}}, "link_channels") && s.dynamics.ratio == 8 && s.key_filter.size() == 1, "side-chain: the dynamics' keys before key_filter");
+		CHECK(names_first(s, {{"ratio", 2.0}, {"key_filter", band_list({{"freq", -1.0}, {"q", 100.0}})}}, "freq") && s.dynamics.ratio == 8, "side-chain: a wrong band leaves the dynamics as they were");
+		dynamics_clamps(s, s.dynamics, "side-chain");
+		band_clamps(s, s.key_filter, Audio_sidechain::max_bands, "side-chain");
+	}
+	{
+		Audio_echo e;
+		e.feedback = 0.7;
+		CHECK(names_first(e, {{"delay_ms_right", -1.0}, {"dry", 2.0}}, "delay_ms_right") && e.feedback == 0.7 && !e.delay_ms_right.has_value(), "echo: delay_ms_right before dry");
+		e.ping_pong = true; e.delay_ms = 0.5; e.feedback = -1; e.damp_hz = 0; e.lowcut_hz = 0; e.wet = -1; e.dry = -1;
+		CHECK(drawn(e) && e.delay_ms == 1.0 && !e.delay_ms_right.has_value() && e.feedback == 0 && e.damp_hz == 0 && e.lowcut_hz == 0 && e.wet == 0 && e.dry == 0,
+			  "echo: a delay's floor is 1 ms, no right delay stays none, a corner of 0 stays 0");
+		e.delay_ms_right = 0.5; e.damp_hz = 100; e.lowcut_hz = 5;
+		CHECK(drawn(e) && e.delay_ms_right == 1.0 && e.damp_hz == 200 && e.lowcut_hz == 20, "echo: the right delay's floor; a corner between 0 and its lowest value is that value");
+		e.delay_ms = 2e9; e.delay_ms_right = 2e9; e.feedback = 1; e.damp_hz = 30000; e.lowcut_hz = 3000; e.wet = 2; e.dry = 2;
+		CHECK(drawn(e) && e.delay_ms == 1e9 && e.delay_ms_right == 1e9 && e.feedback == 0.95 && e.damp_hz == 20000 && e.lowcut_hz == 2000 && e.wet == 1 && e.dry == 1 && e.ping_pong,
+			  "echo: ceilings; ping_pong untouched");
+	}
+	{
+		Audio_modulation m;
+		m.spread = 0.25;
+		CHECK(names_first(m, {{"delay_ms", 0.0}, {"dry", 2.0}}, "delay_ms") && m.spread == 0.25, "modulation: delay_ms before dry");
+		m.shape = Audio_modulation::Shape::Triangle;
+		m.rate_hz = -1; m.delay_ms = 0.01; m.depth_ms = -1; m.feedback = -1; m.voices = 0; m.spread = -1; m.wet = -1; m.dry = -1;
+		CHECK(drawn(m) && m.rate_hz == 0 && m.delay_ms == 0.05 && m.depth_ms == 0 && m.feedback == -0.95 && m.voices == 1 && m.spread == 0 && m.wet == 0 && m.dry == 0,
+			  "modulation: floors; the delay's is 0.05 ms");
+		m.rate_hz = 30; m.delay_ms = 2e9; m.depth_ms = 2e9; m.feedback = 1; m.voices = 9; m.spread = 2; m.wet = 2; m.dry = 2;
+		CHECK(drawn(m) && m.rate_hz == 20 && m.delay_ms == 1e9 && m.depth_ms == 1e9 && m.feedback == 0.95 && m.voices == 4 && m.spread == 1 && m.wet == 1 && m.dry == 1 &&
+				  m.shape == Audio_modulation::Shape::Triangle,
+			  "modulation: ceilings; shape untouched");
+	}
+	{
+		Audio_saturation s;
+		s.bias = 0.5;
+		CHECK(names_first(s, {{"curve", "fuzz"}, {"mix", 2.0}}, "curve") && s.bias == 0.5, "saturation: curve before mix");
+		CHECK(names_first(s, {{"oversample", 3}, {"mix", 2.0}}, "oversample") && s.bias == 0.5, "saturation: an oversample the library has not, before mix");
+		s.curve = Audio_saturation::Curve::Hard;
+		s.drive_db = -1; s.bias = -1; s.oversample = 0; s.output_db = -30; s.mix = -1;
+		CHECK(drawn(s) && s.drive_db == 0 && s.bias == 0 && s.oversample == 1 && s.output_db == -24 && s.mix == 0, "saturation: floors; oversample 0 becomes 1");
+		s.drive_db = 60; s.bias = 2; s.oversample = 100; s.output_db = 30; s.mix = 2;
+		CHECK(drawn(s) && s.drive_db == 48 && s.bias == 1 && s.oversample == 8 && s.output_db == 24 && s.mix == 1 && s.curve == Audio_saturation::Curve::Hard,
+			  "saturation: ceilings; oversample 100 becomes 8; curve untouched");
+		for (const auto& [os, want] : {std::pair{3, 2}, {5, 4}, {7, 4}, {9, 8}, {-3, 1}, {2, 2}})
+		{
+			s.oversample = os;
+			CHECK(drawn(s) && s.oversample == want, "saturation: oversample " << os << " rounds down to " << want);
+		}
+	}
+	{
+		Audio_gate g;
+		g.range_db = 35;
+		CHECK(names_first(g, {{"threshold_db", 5.0}, {"link_channels", 1}}, "threshold_db") && g.range_db == 35, "gate: threshold_db before link_channels");
+		g.mode = Audio_gate::Mode::Expander; g.link_channels = false;
+		g.threshold_db = -100; g.hysteresis_db = -1; g.range_db = -1; g.ratio = 0; g.attack_ms = -1; g.hold_ms = -1; g.release_ms = 0; g.lookahead_ms = -1;
+		CHECK(drawn(g) && g.threshold_db == -90 && g.hysteresis_db == 0 && g.range_db == 0 && g.ratio == 1 && g.attack_ms == 0 && g.hold_ms == 0 && g.release_ms == 1 &&
+				  g.lookahead_ms == 0,
+			  "gate: floors");
+		g.threshold_db = 3; g.hysteresis_db = 30; g.range_db = 200; g.ratio = 500; g.attack_ms = 600; g.hold_ms = 1e6; g.release_ms = 9000; g.lookahead_ms = 50;
+		CHECK(drawn(g) && g.threshold_db == 0 && g.hysteresis_db == 24 && g.range_db == 120 && g.ratio == 100 && g.attack_ms == 500 && g.hold_ms == 10000 && g.release_ms == 5000 &&
+				  g.lookahead_ms == 20 && g.mode == Audio_gate::Mode::Expander && !g.link_channels,
+			  "gate: ceilings; mode and link untouched");
+	}
+	{
+		Audio_denoise d;
+		d.time_smooth = 5;
+		CHECK(names_first(d, {{"sensitivity_db", 100.0}, {"profile_ms", 1.0}}, "sensitivity_db") && d.time_smooth == 5, "denoise: sensitivity_db before profile_ms");
+		CHECK(names_first(d, {{"fft_size", 1000}, {"time_smooth", 9}}, "fft_size") && d.time_smooth == 5, "denoise: a frame size the library has not, before time_smooth");
+		d.reduction_db = -1; d.sensitivity_db = -10; d.fft_size = 100; d.time_smooth = -1; d.freq_smooth = -1; d.profile_start_ms = -1; d.profile_ms = 1;
+		CHECK(drawn(d) && d.reduction_db == 0 && d.sensitivity_db == -6 && d.fft_size == 2048 && d.time_smooth == 0 && d.freq_smooth == 0 && d.profile_start_ms == 0 && d.profile_ms == 20,
+			  "denoise: floors; a frame size below the library's is the default");
+		d.reduction_db = 60; d.sensitivity_db = 30; d.fft_size = 8192; d.time_smooth = 9; d.freq_smooth = 9; d.profile_start_ms = 1e6; d.profile_ms = 1e6;
+		CHECK(drawn(d) && d.reduction_db == 48 && d.sensitivity_db == 24 && d.fft_size == 2048 && d.time_smooth == 8 && d.freq_smooth == 4 && d.profile_start_ms == 60000 &&
+				  d.profile_ms == 10000,
+			  "denoise: ceilings; a frame size above the library's is the default");
+		d.fft_size = 1000;
+		CHECK(drawn(d) && d.fft_size == 2048, "denoise: a frame size between the library's is the default");
+		d.fft_size = 1024;
+		CHECK(drawn(d) && d.fft_size == 1024, "denoise: a frame size the library has stays");
+	}
+	{
+		Audio_loudness l;
+		l.target_lufs = -23;
+		CHECK(names_first(l, {{"true_peak_db", 1.0}, {"max_gain_db", 100.0}}, "true_peak_db") && l.target_lufs == -23, "loudness: true_peak_db before max_gain_db");
+		l.target_lufs = -80; l.true_peak_db = -30; l.max_gain_db = -1;
+		CHECK(drawn(l) && l.target_lufs == -70 && l.true_peak_db == -20 && l.max_gain_db == 0, "loudness: floors");
+		l.target_lufs = 0; l.true_peak_db = 3; l.max_gain_db = 50;
+		CHECK(drawn(l) && l.target_lufs == -5 && l.true_peak_db == 0 && l.max_gain_db == 40, "loudness: ceilings");
+	}
 }
 
 static void test_error_capture()
@@ -1173,6 +1365,7 @@ int main(int argc, char** argv)
 	test_streams_and_scheduler();
 	test_registry_and_json();
 	test_headless_draw_hooks();
+	test_effect_field_order_and_clamps();
 	test_bimix_align_step();
 	test_default_stretch_algorithm();
 	test_velocity_cadence_rules();

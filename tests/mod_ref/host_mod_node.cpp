@@ -101,25 +101,7 @@ static void test_json()
 	}
 }
 
-static void test_registry()
-{
-	infra::register_all_processors();
-	infra::register_extension_processors();
-	infra::register_effect_processors();
-	infra::register_equalizer_processors();
-	infra::register_dynamics_processors();
-	infra::register_restoration_processors();
-	infra::register_mastering_processors();
-	infra::register_sidechain_processors();
-	infra::register_echo_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 15 && infra::Processor::processor_map.count("audio_modulation") == 0,
-		  "the nine existing calls: 15 entries, no audio_modulation");
-	infra::register_modulation_processors();
-	print_registry();
-	CHECK(infra::Processor::processor_map.size() == 16 && infra::Processor::processor_map.count("audio_modulation") == 1, "with the modulation node: 16 entries");
-	check_generated("audio_modulation");
-}
+static void test_registry() { check_registry("audio_modulation"); }
 
 static void graph_case(int channels, const Json::Value& json, double rate_hz, double delay_ms, double depth_ms, double feedback, int voices, double spread,
 					   int shape, double wet, double dry, const char* what)

@@ -4,7 +4,8 @@
 // json throws "Wrong field: <field>".
 // The effect nodes' (tests/fir_ref/host_fir_node.cpp, conv_ref/host_conv_node.cpp, eq_ref/host_eq_node.cpp, dyn_ref/host_dyn_node.cpp) besides:
 // uniform_noise, run_graph<Node> (source -> node -> sink), check_frames (the sink's frames against the source's shapes and the wanted words),
-// block_call (a block entry through a context of its own), print_registry / check_generated, and harness_main (the mode dispatch).
+// block_call (a block entry through a context of its own), check_registry (the one walk through the registration calls, with print_registry and
+// check_generated), and harness_main (the mode dispatch).
 #pragma once
 #include "infra/runner.hpp"
 #include "processor/audio-velocity.hpp"
@@ -242,6 +243,48 @@ inline void check_generated(const std::string& id)
 	int inputs = 0;
 	for (const auto& p : pins) inputs += p.is_input && p.type.get() == typeid(Audio_stream);
 	CHECK(inputs == 1, "one audio input pin, one audio output pin");
+}
+
+// The registration calls in the order an editor makes them, the node each one adds beyond the reference's seven, and the registry's size behind it.
+struct Registration { void (*call)(); const char* adds; size_t count; };
+inline const Registration registrations[] = {
+	{[] { infra::register_all_processors(); }, "", 7},
+	{infra::register_extension_processors, "audio_filter", 8},
+	{infra::register_effect_processors, "audio_reverb", 9},
+	{infra::register_equalizer_processors, "audio_eq", 10},
+	{infra::register_dynamics_processors, "audio_dynamics", 11},
+	{infra::register_restoration_processors, "audio_denoise", 12},
+	{infra::register_mastering_processors, "audio_loudness", 13},
+	{infra::register_sidechain_processors, "audio_sidechain", 14},
+	{infra::register_echo_processors, "audio_echo", 15},
+	{infra::register_modulation_processors, "audio_modulation", 16},
+	{infra::register_saturation_processors, "audio_saturation", 17},
+	{infra::register_gate_processors, "audio_gate", 18},
+};
+
+// the `registry` mode of a node's harness: the calls up to the one that adds id, the size behind every one of them; id is not there before its
+// call and is there behind it, and the registry is printed on both sides of that call (the Python tests read the two lines).  What the
+// registry then generates for id is checked by check_generated, or by the harness's own check for a node with other pins.
+inline void check_registry(const std::string& id, void (*generated)(const std::string&) = check_generated)
+{
+	const auto& map = infra::Processor::processor_map;
+	for (const Registration& r : registrations)
+	{
+		const bool adds = id == r.adds;
+		if (adds)
+		{
+			print_registry();
+			CHECK(map.count(id) == 0, "no " << id << " before its call");
+		}
+		r.call();
+		CHECK(map.size() == r.count, "behind the call that adds " << (*r.adds ? r.adds : "the reference's list") << ": " << map.size() << " entries, not " << r.count);
+		if (!adds) continue;
+		print_registry();
+		CHECK(map.count(id) == 1, id << " behind its call");
+		generated(id);
+		return;
+	}
+	CHECK(false, "no registration call adds " << id);
 }
 
 // main() of host_<name>_node: runs the mode argv[1] names ("json" without one) -> 0 and "HOST <NAME> OK <mode>", 1 after a failed CHECK, 2 and
