@@ -104,6 +104,11 @@
 #define NAE_GATE_MAX_HOLD_S 10.0
 #define NAE_GATE_MODE_GATE 0
 #define NAE_GATE_MODE_EXPANDER 1
+/* K20 multiband ("K20 multiband"): a Linkwitz-Riley crossover tree of K11 sections into 2 ... NAE_MB_MAX_BANDS bands, K12 on every
+ * band, and the bands' sum.  The tree of B bands has 4, 9 or 14 sections in fixed slots: at most NAE_MB_MAX_SECTIONS, inside K11's constant
+ * block of NAE_EQ_MAX_SECTIONS */
+#define NAE_MB_MAX_BANDS 4
+#define NAE_MB_MAX_SECTIONS 14
 /* K13 spectral gate ("K13 spectral gate"): noise reduction on the STFT at N = 512 ... 4096 and hop N / 4: a per-bin decision
  * against a learned power profile, smoothed by an integer triangle over at most NAE_DENOISE_MAX_TIME frames and NAE_DENOISE_MAX_FREQ bins to
  * either side (a wider frequency triangle pulls a pure tone down: DESIGN.md gives the figure); a tile the library chooses has at least

@@ -56,7 +56,8 @@ extern "C" {
  *   entries) with the record nae_mod_params: the modulated delay (chorus, flanger, vibrato), K17; nae_sat_latency, nae_sat_taps,
  *   nae_sat_design, nae_sat_block_f32 and the nae_sat handle (the same eight entries) with the record nae_sat_params: the saturation, K18;
  *   nae_gate_design, nae_gate_block_f32 and the nae_gate handle (the same eight entries) with the record nae_gate_params: the noise gate and
- *   downward expander, K19. */
+ *   downward expander, K19; nae_mb_design, nae_mb_block_f32 and the nae_mb handle (the same eight entries) with the record nae_mb_params:
+ *   the multiband compressor, K20. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -87,6 +88,7 @@ typedef struct nae_echo nae_echo;
 typedef struct nae_mod nae_mod;
 typedef struct nae_sat nae_sat;
 typedef struct nae_gate nae_gate;
+typedef struct nae_mb nae_mb;
 typedef struct nae_denoise nae_denoise;
 typedef struct nae_loud nae_loud;
 
@@ -177,6 +179,9 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *                   depth) - 1)); a value above that rule's is cut down to it; every value gives the same bits
  *   sat_tile        chunks (of NAE_EQ_CHUNK samples) one wave of the saturation walks (0: nae_pick_sat_tile, which cuts a small batch until the CUs
  *                   are full); every tiling gives the same bits
+ *   mb_group        streams per launch group of nae_mb_block_f32 (0: as many as keep the band planes inside the 256 MiB workspace cap)
+ *   mb_slab         chunks (of NAE_EQ_CHUNK samples) per slab of the multiband compressor's three kernels (0: as many as the cap then holds; a
+ *                   handle reads it when it is created, 0: 64).  Every grouping and every slab gives the same bits
  * The same assignments, comma separated, in the environment variable NAE_DEBUG ("pv_flow=2,pv_fps=4") are applied when a context is created
  * (for measuring a program that creates its contexts itself, e.g. bench.py); an unknown key there fails nae_ctx_create with NAE_ERR_INVALID. */
 int nae_debug_set(nae_ctx* ctx, const char* key, long long value);
@@ -880,6 +885,60 @@ int nae_gate_destroy(nae_gate* h);
  * context, no device work. */
 int nae_gate_design(int sample_rate, int mode, double threshold_db, double hysteresis_db, double range_db, double ratio, double attack_s,
                     double hold_s, double release_s, double lookahead_s, int link, nae_gate_params* out);
+
+/* ------------------------------------------------------------------ K20 multiband (crossover and per-band compressor)
+ * no reference code.  Spec ("K20 multiband"): a crossover tree of K11 sections splits every channel into B = n_bands bands,
+ * 2 ... NAE_MB_MAX_BANDS; K12 runs on every band under the band's own record; the bands are added.  The sections coef[s] = (b0, b1, b2, a1, a2)
+ * stand in fixed slots, n_sections = 4, 9 or 14 of them, each under K11's stability rule, each run in K11's tiled form exactly (the tables
+ * of nae_eq_block_f32, the same order of operations, the same carry), the signal double between the sections of a path:
+ *   B = 2   s0 s1 = LP(f1); s2 s3 = HP(f1).                                   band0 = x s0 s1; band1 = x s2 s3
+ *   B = 3   s0 s1 = LP(f1); s2 = AP(f2); s3 s4 = HP(f1); s5 s6 = LP(f2); s7 s8 = HP(f2).
+ *           band0 = x s0 s1 s2; h = x s3 s4; band1 = h s5 s6; band2 = h s7 s8
+ *   B = 4   s0 s1 = LP(f2); s2 = AP(f3); s3 s4 = LP(f1); s5 s6 = HP(f1); s7 s8 = HP(f2); s9 = AP(f1); s10 s11 = LP(f3); s12 s13 = HP(f3).
+ *           l = x s0 s1 s2; band0 = l s3 s4; band1 = l s5 s6; h = x s7 s8 s9; band2 = h s10 s11; band3 = h s12 s13
+ * The block call takes any checked sections in these slots; nae_mb_design fills them with the halves of fourth-order Linkwitz-Riley
+ * crossovers and the all-passes that make the bands add to AP(f1) ... AP(f_(B-1)), a flat magnitude.
+ *   band signal  xb_b[n] = (float)w_b[n], the path's double output rounded once: nae_eq_block_f32's output for the path's sections, bit for bit
+ *   per band     yb_b = K12 on xb_b with band[b]: steps 1 - 6 and the tiling of nae_dyn_block_f32, zero demand from in_len on; lookahead and
+ *                link are equal in all bands.  A band in bypass_mask has yb_b = xb_b (a band with slope 0 and makeup_db 0 gives the same bits:
+ *                dyn_exp2(0) is exactly 1)
+ *   sum          y[n] = (float)((((double)yb_0 + (double)yb_1) + (double)yb_2) + (double)yb_3) over the bands not in mute_mask, in band order,
+ *                starting from the first of them; 0.0f where every band is muted.  Muting all bands but one is a solo
+ * So the call equals the composition of the existing entries per band, eq then dyn then the sum; every tiling, slab, group of streams and cut
+ * into puts gives the same bits; in_len frames come out, compensated for the look-ahead as K12 is; a non-finite sample i leaves every output
+ * sample before i - lookahead as it was, and the call returns NAE_OK.  Bit-exact against the CPU statement (tests/mb_ref/ref_mb.c).
+ * Errors: a null pointer, ch not 1 or 2, n_bands < 2, n_sections not the tree's count for n_bands, a section that is not finite or not
+ * strictly stable, a band record nae_dyn_block_f32 would refuse as invalid, lookahead or link unequal between the bands, a mask bit at or
+ * above n_bands: NAE_ERR_INVALID; n_bands above NAE_MB_MAX_BANDS or a lookahead above NAE_DYN_MAX_LOOKAHEAD: NAE_ERR_UNSUPPORTED; in_len = 0
+ * or n_streams = 0: NAE_OK after the checks, nothing is launched.  Views as nae_eq_block_f32's: stream_stride 0 on the source and
+ * dst->base == src->base in the same view are allowed.  The band signals stand in a workspace of the context of at most 256 MiB: a larger
+ * batch runs in groups of streams and slabs of chunks (debug keys mb_group, mb_slab). */
+typedef struct nae_mb_params {
+    int n_bands;                          /* B: 2 ... NAE_MB_MAX_BANDS */
+    int n_sections;                       /* 4, 9 or 14: the tree of B bands */
+    double coef[NAE_MB_MAX_SECTIONS][5];  /* the slots' sections */
+    nae_dyn_params band[NAE_MB_MAX_BANDS];
+    unsigned mute_mask, bypass_mask;      /* bit b: band b is left out of the sum / passes its compressor by */
+} nae_mb_params;
+int nae_mb_block_f32(nae_ctx* ctx, const nae_mb_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch): before the flush floor((put - lookahead) / NAE_DYN_CHUNK) whole chunks are
+ * available, never negative; nae_mb_flush releases the rest, so in_len frames come out in all, equal to the block call's however the input
+ * is cut.  A put after the flush: NAE_ERR_STATE. */
+int nae_mb_create(nae_ctx* ctx, const nae_mb_params* params, int channels, nae_mb** h);
+int nae_mb_put(nae_mb* h, const float* interleaved, size_t S);
+int nae_mb_put_host(nae_mb* h, const float* interleaved_host, size_t S);
+int nae_mb_flush(nae_mb* h);
+size_t nae_mb_available(nae_mb* h);
+int nae_mb_receive(nae_mb* h, float* dst, size_t max_frames, size_t* got);
+int nae_mb_receive_host(nae_mb* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_mb_destroy(nae_mb* h);
+/* The record on the host, in double: crossover_hz[0 ... n_bands - 2] strictly ascending, each valid for nae_eq_design at sample_rate; LP(f) and
+ * HP(f) are nae_eq_design(NAE_EQ_LOWPASS | NAE_EQ_HIGHPASS, sample_rate, f, 0, 0.7071067811865476), two of each in a row a fourth-order
+ * Linkwitz-Riley half; AP(f) is the cookbook's all-pass of the same w0, alpha and q: b = (1 - alpha, -2 cos w0, 1 + alpha) / a0,
+ * a = (-2 cos w0, 1 - alpha) / a0, a0 = 1 + alpha.  bands[0 ... n_bands - 1] come from nae_dyn_design.  Anything the block call would refuse, a
+ * null pointer, sample_rate <= 0 or n_bands outside 2 ... NAE_MB_MAX_BANDS: NAE_ERR_INVALID.  No context, no device work. */
+int nae_mb_design(int sample_rate, int n_bands, const double* crossover_hz, const nae_dyn_params* bands, unsigned mute_mask, unsigned bypass_mask,
+                  nae_mb_params* out);
 
 /* ------------------------------------------------------------------ K13 spectral gate
  * no reference code.  Spec ("K13 spectral gate"): noise reduction on the STFT at n_fft = 512 ... 4096, hop H = n_fft / 4, in the

@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = [
     "nae_sat_available", "nae_sat_receive", "nae_sat_receive_host", "nae_sat_destroy",
     "nae_gate_design", "nae_gate_block_f32", "nae_gate_create", "nae_gate_put", "nae_gate_put_host", "nae_gate_flush", "nae_gate_available",
     "nae_gate_receive", "nae_gate_receive_host", "nae_gate_destroy",
+    "nae_mb_design", "nae_mb_block_f32", "nae_mb_create", "nae_mb_put", "nae_mb_put_host", "nae_mb_flush", "nae_mb_available",
+    "nae_mb_receive", "nae_mb_receive_host", "nae_mb_destroy",
     "nae_denoise_design", "nae_denoise_profile_f32", "nae_denoise_block_f32", "nae_denoise_create", "nae_denoise_put", "nae_denoise_put_host",
     "nae_denoise_flush", "nae_denoise_available", "nae_denoise_receive", "nae_denoise_receive_host", "nae_denoise_destroy",
     "nae_loud_design", "nae_loud_lufs", "nae_loud_measure_f32", "nae_loud_apply_f32", "nae_loud_normalize_f32", "nae_loud_create", "nae_loud_put",
@@ -74,7 +76,8 @@ SAT_HALF, SAT_MAX_OS = 16, 8                        # NAE_SAT_HALF, NAE_SAT_MAX_
 SAT_CURVES = ("soft", "hard")                       # `curve` of nae_sat_params: NAE_SAT_SOFT, NAE_SAT_HARD
 GATE_MAX_HOLD = 1 << 21                             # NAE_GATE_MAX_HOLD (include/nae_dsp_spec.h)
 GATE_MODES = ("gate", "expander")                   # `mode` of nae_gate_design: NAE_GATE_MODE_GATE, NAE_GATE_MODE_EXPANDER
-HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat", "nae_gate")   # the handles with the full put / receive set of entries
+MB_MAX_BANDS, MB_MAX_SECTIONS = 4, 14               # NAE_MB_MAX_BANDS, NAE_MB_MAX_SECTIONS (include/nae_dsp_spec.h)
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat", "nae_gate", "nae_mb")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -203,6 +206,30 @@ class GateParams(C.Structure):
     _fields_ = [("open_lin", C.c_float), ("close_lin", C.c_float), ("threshold_db", C.c_double), ("slope", C.c_double), ("range_db", C.c_double),
                 ("alpha_attack", C.c_double), ("alpha_release", C.c_double), ("hold", C.c_int), ("lookahead", C.c_int), ("expand", C.c_int),
                 ("link", C.c_int)]
+
+
+class MbParams(C.Structure):
+    """nae_mb_params: the multiband compressor's parameters (include/nae_gpu.h): the band count, the crossover tree's sections (b0, b1, b2, a1,
+    a2) in their fixed slots, one nae_dyn_params per band, and the mute and bypass masks; nae_mb_design makes them from crossover frequencies"""
+    _fields_ = [("n_bands", C.c_int), ("n_sections", C.c_int), ("coef", (C.c_double * 5) * MB_MAX_SECTIONS), ("band", DynParams * MB_MAX_BANDS),
+                ("mute_mask", C.c_uint), ("bypass_mask", C.c_uint)]
+
+    @staticmethod
+    def make(coef, bands, mute_mask: int = 0, bypass_mask: int = 0, n_bands: Optional[int] = None, n_sections: Optional[int] = None) -> "MbParams":
+        """coef: [n][5], at most MB_MAX_SECTIONS sections; bands: at most MB_MAX_BANDS DynParams (more of either raise: the record has no room
+        for them); n_bands, n_sections: counts that differ from the lengths, for the rejections"""
+        coef = np.asarray(coef, np.float64).reshape(-1, 5)
+        if coef.shape[0] > MB_MAX_SECTIONS or len(bands) > MB_MAX_BANDS:
+            raise NaeError(f"nae_mb_params holds at most {MB_MAX_SECTIONS} sections and {MB_MAX_BANDS} bands")
+        p = MbParams()
+        p.n_bands, p.n_sections = len(bands) if n_bands is None else n_bands, coef.shape[0] if n_sections is None else n_sections
+        for s_, row in enumerate(coef):
+            for i_, v in enumerate(row):
+                p.coef[s_][i_] = v
+        for b_, band in enumerate(bands):
+            p.band[b_] = band
+        p.mute_mask, p.bypass_mask = mute_mask, bypass_mask
+        return p
 
 
 class DenoiseParams(C.Structure):
@@ -337,6 +364,8 @@ def load_library() -> C.CDLL:
         "nae_sat_block_f32": (i, [vp, P(SatParams), P(Sig), sz, i, sz, P(Sig)]), "nae_sat_create": (i, [vp, P(SatParams), i, P(vp)]),
         "nae_gate_design": (i, [i, i, d, d, d, d, d, d, d, d, i, P(GateParams)]),
         "nae_gate_block_f32": (i, [vp, P(GateParams), P(Sig), sz, i, sz, P(Sig)]), "nae_gate_create": (i, [vp, P(GateParams), i, P(vp)]),
+        "nae_mb_design": (i, [i, i, vp, vp, C.c_uint, C.c_uint, P(MbParams)]),
+        "nae_mb_block_f32": (i, [vp, P(MbParams), P(Sig), sz, i, sz, P(Sig)]), "nae_mb_create": (i, [vp, P(MbParams), i, P(vp)]),
         "nae_denoise_design": (i, [d, d, i, i, i, P(DenoiseParams)]), "nae_denoise_profile_f32": (i, [vp, i, P(Sig), sz, i, vp]),
         "nae_denoise_block_f32": (i, [vp, P(DenoiseParams), vp, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
@@ -835,6 +864,24 @@ class Context:
         """the gate / expander `params` over every stream (nae_gate_block_f32); dst receives in_len frames, compensated for the look-ahead"""
         self._ck(self.lib.nae_gate_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K20
+    @staticmethod
+    def mb_design(sample_rate: int, crossover_hz, bands, mute_mask: int = 0, bypass_mask: int = 0) -> "MbParams":
+        """the multiband compressor's parameters from len(bands) - 1 ascending crossover frequencies and the bands' DynParams (nae_mb_design)"""
+        xs = np.ascontiguousarray(crossover_hz, np.float64).reshape(-1)
+        if len(bands) != xs.size + 1:
+            raise NaeError(f"nae_mb_design: {xs.size} crossovers need {xs.size + 1} bands, not {len(bands)}")
+        recs = (DynParams * max(len(bands), 1))(*bands)
+        out = MbParams()
+        rc = load_library().nae_mb_design(sample_rate, len(bands), xs.ctypes.data, C.addressof(recs), mute_mask, bypass_mask, C.byref(out))
+        if rc:
+            raise NaeError(f"nae_mb_design({sample_rate}, {xs.tolist()}, {len(bands)} bands, {mute_mask}, {bypass_mask}) failed: {rc}")
+        return out
+
+    def mb_block(self, params: "MbParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the multiband compressor `params` over every stream (nae_mb_block_f32); dst receives in_len frames, compensated for the look-ahead"""
+        self._ck(self.lib.nae_mb_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     # -- K12
     @staticmethod
     def dyn_design(sample_rate: int, threshold_db: float = -18.0, ratio: float = 4.0, knee_db: float = 6.0, attack_s: float = 0.005,
@@ -1091,6 +1138,17 @@ class Gate(_Handle):
     def __init__(self, ctx: Context, params: GateParams, channels: int):
         super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_gate_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+
+class Multiband(_Handle):
+    """The multiband compressor's streaming handle (nae_mb_create): put interleaved f32, flush, receive.  Before the flush the whole chunks of
+    1024 frames with `lookahead` frames behind them are available."""
+
+    _prefix = "nae_mb"
+
+    def __init__(self, ctx: Context, params: MbParams, channels: int):
+        super().__init__(ctx, channels)
+        ctx._ck(ctx.lib.nae_mb_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
 
 
 class Denoise(_Handle):

@@ -235,6 +235,8 @@ int nae_debug_set(nae_ctx* ctx, const char* key, long long value)
     else if (k == "echo_group" && count) ctx->echo_group = (int)value;
     else if (k == "mod_sub" && value >= 0 && value <= 64) ctx->mod_sub = (int)value;
     else if (k == "sat_tile" && count) ctx->sat_tile = (int)value;
+    else if (k == "mb_group" && count) ctx->mb_group = (int)value;
+    else if (k == "mb_slab" && count) ctx->mb_slab = (int)value;
     else if (k == "pv_fps" && one_of({0, 1, 2, 4})) ctx->pv_fps = (int)value;
     else if (k == "pv_flow" && one_of({0, 1, 2})) ctx->pv_flow = (int)value;
     else if (k == "pv_lean" && flag) ctx->pv_lean = value != 0;

@@ -48,6 +48,9 @@ struct nae_ctx {
     int echo_group = 0;          // streams per launch of the echo's block call; 0 = from NAE_CONV_WS_BYTES
     int mod_sub = 0;             // samples a wave of the modulated delay computes in parallel, 1 ... 64; 0 = the rule of kernels_mod.hip
     int sat_tile = 0;            // chunks per wave of the saturation; 0 = choose per launch (nae_pick_sat_tile)
+    CtxBuf ws_mb;                // nae_mb_block_f32's carries and band planes of a launch group and slab (kernels_mb.hip)
+    int mb_group = 0;            // streams per launch group of the multiband compressor's block call; 0 = from NAE_CONV_WS_BYTES
+    int mb_slab = 0;             // chunks per slab of its three kernels; 0 = from NAE_CONV_WS_BYTES (a handle: 64)
     // the saturation keeps the device taps of every oversampling factor it has run (kernels_sat.hip): three slots [hd | hu], bit i of sat_taps_have:
     // slot i is there.  No last-call constant: a slot never changes once uploaded
     CtxBuf sat_taps; unsigned sat_taps_have = 0;
@@ -363,6 +366,18 @@ int nae_gate_check(nae_ctx* ctx, const nae_gate_params* p, int ch);
 size_t nae_gate_detectors(const nae_gate_params* p, int ch, size_t n_streams);
 int nae_launch_gate(nae_ctx* ctx, const nae_gate_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
                     size_t c_origin, size_t c_stop, long long* d_state);
+
+// kernels_mb.hip: the multiband compressor ("K20 multiband").  nae_mb_check: the parameter rules of the block call and the handle.
+// nae_mb_run runs chunks [c_origin, c_stop) of absolutely indexed signals of in_len samples in slabs of at most `slab` chunks: d_block is the
+// tree's K11 constant block; d_planes, nae_mb_plane_floats() floats, holds a slab's band signals and the chunk behind it; d_state,
+// nae_mb_state_doubles() doubles, holds the sections' carries [stream-channel][16][2] and then the detectors' [band][detector][2] in front of
+// chunk c_origin (zero at the start of a stream) and receives the ones in front of chunk c_stop.  nae_mb_handle_slab: the slab of a handle.
+int nae_mb_check(nae_ctx* ctx, const nae_mb_params* p, int ch);
+size_t nae_mb_plane_floats(const nae_mb_params* p, int ch, size_t n_streams, size_t slab);
+size_t nae_mb_state_doubles(const nae_mb_params* p, int ch, size_t n_streams);
+size_t nae_mb_handle_slab(const nae_ctx* ctx);
+int nae_mb_run(nae_ctx* ctx, const nae_mb_params* p, const double* d_block, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+               const nae_sig* dst, size_t c_origin, size_t c_stop, float* d_planes, size_t slab, double* d_state);
 
 // kernels_denoise.hip: the spectral gate ("K13 spectral gate").  nae_denoise_check: the parameter rules of the block call and the
 // handle.  nae_launch_denoise runs hop blocks [b_origin, b_stop) of absolutely indexed signals of in_len samples: it reads from

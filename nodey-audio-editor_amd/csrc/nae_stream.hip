@@ -113,6 +113,18 @@ struct nae_gate : BlockHandle {
     int process() override;
 };
 
+// the multiband compressor's handle ("K20 multiband"): whole chunks of NAE_DYN_CHUNK samples are computed once the `lookahead`
+// samples behind them are there, in slabs through the handle's own band planes; the sections' and the detectors' carries in front of the next
+// chunk stay on the device between two launches
+struct nae_mb : BlockHandle {
+    nae_mb_params params;
+    double* d_block = nullptr;     // the tree's coefficients and tables (nae_eq_make_block)
+    float* d_planes = nullptr;     // nae_mb_plane_floats(): the band signals of a slab and the chunk behind it
+    double* d_state = nullptr;     // nae_mb_state_doubles(): the carries in front of the next chunk
+    size_t slab = 0;               // chunks per slab (nae_mb_handle_slab at the create)
+    int process() override;
+};
+
 // the spectral gate's handle ("K13 spectral gate"): whole hop blocks of n_fft / 4 samples are computed once the time_smooth + 3
 // blocks behind them are there; the input stays from time_smooth + 3 blocks in front of the next block on, and nothing else is kept
 struct nae_denoise : BlockHandle {
@@ -391,6 +403,13 @@ int nae_gate::process()
 {
     return run_units(NAE_DYN_CHUNK, (size_t)params.lookahead, 0, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
         return nae_launch_gate(ctx, &params, &src, in.total, ch, 1, &dst, from, to, d_state);
+    });
+}
+
+int nae_mb::process()
+{
+    return run_units(NAE_DYN_CHUNK, (size_t)params.band[0].lookahead, 0, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
+        return nae_mb_run(ctx, &params, d_block, &src, in.total, ch, 1, &dst, from, to, d_planes, slab, d_state);
     });
 }
 
@@ -796,6 +815,37 @@ size_t nae_gate_available(nae_gate* h) { return handle_available(h); }
 int nae_gate_receive(nae_gate* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_gate_receive_host(nae_gate* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_gate_destroy(nae_gate* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ multiband
+int nae_mb_create(nae_ctx* ctx, const nae_mb_params* params, int channels, nae_mb** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_mb_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_mb* s = handle_new<nae_mb>(ctx, channels);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    s->slab = nae_mb_handle_slab(ctx);
+    // in front of sample 0 every carry is zero; the planes are written before they are read
+    const size_t state_doubles = nae_mb_state_doubles(params, channels, 1);
+    rc = s->dev_alloc(&s->d_state, state_doubles, "hipMalloc(mb state)");
+    if (!rc) rc = nae_check(ctx, hipMemsetAsync(s->d_state, 0, state_doubles * sizeof(double), ctx->stream), "hipMemsetAsync(mb state)");
+    if (!rc) rc = s->dev_alloc(&s->d_planes, nae_mb_plane_floats(params, channels, 1, s->slab), "hipMalloc(mb planes)");
+    if (!rc) rc = s->dev_alloc(&s->d_block, nae_eq_block_doubles(), "hipMalloc(mb tables)");
+    if (!rc) rc = nae_eq_make_block(ctx, &params->coef[0][0], params->n_sections, s->d_block);
+    return handle_created(s, rc, h);
+}
+
+int nae_mb_put(nae_mb* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_mb_put_host(nae_mb* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+// flush: the chunks that waited for their look-ahead and the partial last one come out: as many frames as were put over the handle's life
+int nae_mb_flush(nae_mb* h) { return handle_flush(h); }
+size_t nae_mb_available(nae_mb* h) { return handle_available(h); }
+int nae_mb_receive(nae_mb* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_mb_receive_host(nae_mb* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_mb_destroy(nae_mb* h) { return handle_destroy(h); }
 
 // ------------------------------------------------------------------------------------------------ spectral gate
 int nae_denoise_create(nae_ctx* ctx, const nae_denoise_params* params, const float* profile_dev, int profile_ch, int channels, nae_denoise** h)

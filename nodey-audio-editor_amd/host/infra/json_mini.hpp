@@ -1,6 +1,6 @@
 // json_mini.hpp — the handful of Json::Value operations the processors' serialize()/deserialize() use
 // (reference: JsonCpp, include/infra/processor.hpp:6,93-96).  Only what the hot-path nodes touch: objects of
-// bool / int / double / string members, and arrays of values (the equalizer's bands).  Not a JSON parser: project files are the editor's
+// bool / int / double / string members, and arrays of values or of objects (the equalizer's bands, the multiband compressor's).  Not a JSON parser: project files are the editor's
 // business (out of scope).
 #pragma once
 #include <map>
@@ -10,7 +10,7 @@
 
 namespace Json
 {
-	enum ValueType { nullValue = 0, arrayValue = 6 };  // JsonCpp's numbering; only what Value(ValueType) is called with
+	enum ValueType { nullValue = 0, arrayValue = 6, objectValue = 7 };  // JsonCpp's numbering; only what Value(ValueType) is called with
 
 	class Value
 	{
@@ -32,6 +32,8 @@ namespace Json
 
 		// JsonCpp's array operations: append to an array (a null value becomes one), element by index, size() of an array
 		bool isArray() const { return array; }
+		// an object: what is neither an array nor a scalar.  An object without members and a null value are one here (JsonCpp tells them apart)
+		bool isObject() const { return !array && std::holds_alternative<std::monostate>(scalar); }
 		Value& append(const Value& v)
 		{
 			array = true;

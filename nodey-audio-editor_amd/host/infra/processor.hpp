@@ -167,4 +167,6 @@ namespace infra
 	void register_saturation_processors();
 	// the gate (audio_gate): called after the eleven above, each of which stays the list it was
 	void register_gate_processors();
+	// the multiband compressor (audio_multiband): called after the twelve above, each of which stays the list it was
+	void register_multiband_processors();
 }

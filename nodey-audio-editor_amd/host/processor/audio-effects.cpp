@@ -1,5 +1,5 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
-// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat), Audio_gate (nae_gate) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
+// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat), Audio_gate (nae_gate), Audio_multiband (nae_mb) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 // Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
 // A node's parameters are stated once: the members and their defaults in the settings record of audio-<node>.hpp, and here, in front of the
@@ -15,6 +15,7 @@
 #include "audio-modulation.hpp"
 #include "audio-saturation.hpp"
 #include "audio-gate.hpp"
+#include "audio-multiband.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "node-fields.hpp"
@@ -860,6 +861,152 @@ namespace processor
 				nae_gate* gate = nullptr;
 				gpu::check(nae_gate_create(ctx, &params, ch, &gate), "nae_gate_create");
 				return gate;
+			}
+		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_multiband
+	infra::Processor::Info Audio_multiband::get_processor_info()
+	{
+		return {"audio_multiband", "Audio Multiband Compressor", false, [] { return std::unique_ptr<infra::Processor>(new Audio_multiband); },
+				"Multiband compressor: two to four bands on Linkwitz-Riley crossovers, a compressor, a mute and a bypass per band (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_multiband::get_pin_attributes() const { return io_pins(); }
+
+	namespace
+	{
+		// A band's compressor keys are audio_dynamics' own fields, taken out of its one list: threshold_db, ratio, knee_db, attack_ms, release_ms
+		// and makeup_db.  The mode, the look-ahead and the link are not a band's: the last two are the node's, for all bands.
+		constexpr std::tuple multiband_band_dynamics_fields{std::get<1>(dynamics_fields), std::get<2>(dynamics_fields), std::get<3>(dynamics_fields),
+															std::get<4>(dynamics_fields), std::get<5>(dynamics_fields), std::get<7>(dynamics_fields)};
+		constexpr std::tuple multiband_band_flags{
+			Flag{"mute", &Multiband_settings::Band::mute, false},
+			Flag{"bypass", &Multiband_settings::Band::bypass, false},
+		};
+		constexpr std::tuple multiband_fields{
+			Number{"lookahead_ms", &Multiband_settings::lookahead_ms, Multiband_settings::default_lookahead_ms, 0.0, 20.0},
+			Flag{"link_channels", &Multiband_settings::link_channels, true},
+		};
+
+		Json::Value multiband_band_to_json(const Multiband_settings::Band& band)
+		{
+			Json::Value value = to_json(band.dynamics, multiband_band_dynamics_fields);
+			std::apply([&](const auto&... f) { (f.write(band, value), ...); }, multiband_band_flags);
+			return value;
+		}
+
+		// 1 ... 3 strictly ascending frequencies; absent: the default pair
+		std::vector<double> multiband_crossovers_from_json(const Json::Value& value, const char* node_name)
+		{
+			if (!value.isMember("crossovers")) return Multiband_settings{}.crossovers;
+			const Json::Value& list = value["crossovers"];
+			if (!list.isArray() || list.size() < 1 || list.size() > Multiband_settings::max_crossovers) throw wrong_field(node_name, "crossovers");
+			std::vector<double> crossovers;
+			for (int i = 0; i < (int)list.size(); i++)
+			{
+				const Json::Value& f = list[i];
+				if (!f.isDouble() || !(f.asDouble() >= Multiband_settings::min_crossover_hz && f.asDouble() <= Multiband_settings::max_crossover_hz) ||
+					(!crossovers.empty() && !(f.asDouble() > crossovers.back())))
+					throw wrong_field(node_name, "crossovers");
+				crossovers.push_back(f.asDouble());
+			}
+			return crossovers;
+		}
+
+		// exactly n_bands objects; absent: every band at the defaults
+		std::vector<Multiband_settings::Band> multiband_bands_from_json(const Json::Value& value, const char* node_name, size_t n_bands)
+		{
+			std::vector<Multiband_settings::Band> bands(n_bands);
+			if (!value.isMember("bands")) return bands;
+			const Json::Value& list = value["bands"];
+			if (!list.isArray() || list.size() != n_bands) throw wrong_field(node_name, "bands");
+			for (int b = 0; b < (int)list.size(); b++)
+			{
+				if (!list[b].isObject()) throw wrong_field(node_name, "bands");
+				bands[b].dynamics = from_json<Dynamics_settings>(list[b], node_name, multiband_band_dynamics_fields);
+				std::apply([&](const auto&... f) { (f.read(bands[b], list[b], node_name), ...); }, multiband_band_flags);
+			}
+			return bands;
+		}
+	}
+
+	Json::Value Audio_multiband::serialize() const
+	{
+		Json::Value value = to_json<Multiband_settings>(*this, multiband_fields);
+		if (crossovers != Multiband_settings{}.crossovers)
+		{
+			Json::Value list(Json::arrayValue);
+			for (double f : crossovers) list.append(f);
+			value["crossovers"] = list;
+		}
+		Json::Value list(Json::arrayValue);
+		bool any = false;
+		for (const Band& band : bands)
+		{
+			const Json::Value b = multiband_band_to_json(band);
+			any = any || !b.isNull();
+			list.append(b.isNull() ? Json::Value(Json::objectValue) : b);
+		}
+		if (any) value["bands"] = list;
+		return value;
+	}
+
+	void Audio_multiband::deserialize(const Json::Value& value)
+	{
+		// everything is read and checked first: a rejected value leaves the node as it was
+		Multiband_settings s = from_json<Multiband_settings>(value, "Audio_multiband", multiband_fields);
+		s.crossovers = multiband_crossovers_from_json(value, "Audio_multiband");
+		s.bands = multiband_bands_from_json(value, "Audio_multiband", s.crossovers.size() + 1);
+		Multiband_settings::operator=(std::move(s));
+	}
+
+	void Multiband_settings::clamp()
+	{
+		detail::clamp(*this, multiband_fields);
+		if (crossovers.empty()) crossovers = Multiband_settings{}.crossovers;
+		if (crossovers.size() > max_crossovers) crossovers.resize(max_crossovers);
+		for (double& f : crossovers) f = std::clamp(f, min_crossover_hz, max_crossover_hz);
+		std::sort(crossovers.begin(), crossovers.end());
+		bands.resize(crossovers.size() + 1);
+		for (Band& band : bands) detail::clamp(band.dynamics, multiband_band_dynamics_fields);
+	}
+
+	void Audio_multiband::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Multiband Compressor");
+		run_on_handle<nae_mb>(
+			io.input, io.output, stop_token, {"nae_mb", nae_mb_put, nae_mb_flush, nae_mb_available, nae_mb_receive, nae_mb_destroy}, "node", 0,
+			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
+			{
+				// the settings as the library's parameters at the stream's sample rate: every band's compressor under the node's look-ahead and link
+				// (design_dynamics: a look-ahead too long for that rate is the user's error), then the crossover tree
+				nae_dyn_params band_params[NAE_MB_MAX_BANDS];
+				unsigned mute_mask = 0, bypass_mask = 0;
+				for (size_t b = 0; b < bands.size(); b++)
+				{
+					Dynamics_settings d = bands[b].dynamics;
+					d.mode = Dynamics_settings::Mode::Compressor;
+					d.lookahead_ms = lookahead_ms;
+					d.link_channels = link_channels;
+					band_params[b] = design_dynamics(d, frame->sample_rate);
+					mute_mask |= (bands[b].mute ? 1u : 0u) << b;
+					bypass_mask |= (bands[b].bypass ? 1u : 0u) << b;
+				}
+				nae_mb_params params;
+				const int rc = nae_mb_design(frame->sample_rate, (int)bands.size(), crossovers.data(), band_params, mute_mask, bypass_mask, &params);
+				if (rc != NAE_OK)
+					throw infra::Processor::Runtime_error("Invalid crossover", "Every crossover must lie below half the stream's sample rate.",
+										infra::fmt("nae_mb_design with %d bands, highest crossover %g Hz at %d Hz: code %d", (int)bands.size(), crossovers.back(),
+												   frame->sample_rate, rc));
+				nae_mb* mb = nullptr;
+				gpu::check(nae_mb_create(ctx, &params, ch, &mb), "nae_mb_create");
+				return mb;
 			}
 		);
 	}

@@ -22,6 +22,7 @@
 #include "audio-modulation.hpp"
 #include "audio-saturation.hpp"
 #include "audio-gate.hpp"
+#include "audio-multiband.hpp"
 #include "audio-denoise.hpp"
 #include "audio-loudness.hpp"
 #include "audio-mix.hpp"
@@ -126,6 +127,9 @@ namespace processor
 
 	void Audio_gate::draw_title() {}
 	bool Audio_gate::draw_content(bool) { clamp(); return false; }
+
+	void Audio_multiband::draw_title() {}
+	bool Audio_multiband::draw_content(bool) { clamp(); return false; }   // ascending crossovers, one band more than crossovers
 
 	void Audio_denoise::draw_title() {}
 	bool Audio_denoise::draw_content(bool) { clamp(); return false; }   // a frame size the library has, else the default

@@ -14,6 +14,7 @@
 #include "processor/audio-modulation.hpp"
 #include "processor/audio-saturation.hpp"
 #include "processor/audio-gate.hpp"
+#include "processor/audio-multiband.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -71,4 +72,7 @@ namespace infra
 
 	// the gate and downward expander; a call of its own, so the eleven lists above stay what they were
 	void register_gate_processors() { register_each<processor::Audio_gate>(); }
+
+	// the multiband compressor; a call of its own, so the twelve lists above stay what they were
+	void register_multiband_processors() { register_each<processor::Audio_multiband>(); }
 }
