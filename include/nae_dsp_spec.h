@@ -120,6 +120,14 @@
 #define NAE_DENOISE_MAX_REDUCTION_DB 48.0
 #define NAE_DENOISE_MIN_SENSITIVITY_DB (-6.0)
 #define NAE_DENOISE_MAX_SENSITIVITY_DB 24.0
+/* K21 separation ("K21 separation"): harmonic/percussive separation on K13's STFT: the median of the 16-bit keys of the power
+ * over at most NAE_HPSS_MAX_SPAN frames to either side against the median over at most NAE_HPSS_MAX_SPAN bins to either side; a tile the
+ * library chooses has at least NAE_HPSS_MIN_TILE hop blocks (it pays 2 Tn key analyses and three whole frames beyond its own) */
+#define NAE_HPSS_MAX_SPAN 8
+#define NAE_HPSS_MIN_TILE 64
+/* nae_hpss_design: the range of its two levels; NAE_HPSS_MIN_DB itself is gain 0 */
+#define NAE_HPSS_MIN_DB (-120.0)
+#define NAE_HPSS_MAX_DB 12.0
 /* K14 loudness ("K14 loudness"): the BS.1770-4 meter.  The K-weighting's analog prototypes (nae_loud_design maps them to a
  * sample rate by the bilinear form); sample rates NAE_LOUD_MIN_RATE ... NAE_LOUD_MAX_RATE that are multiples of NAE_LOUD_SUBS_PER_S, so the
  * 100 ms sub-block is a whole number of samples; the cascade is K11's tiling with NAE_LOUD_SECTIONS sections.  The true-peak oversampler:

@@ -57,7 +57,8 @@ extern "C" {
  *   nae_sat_design, nae_sat_block_f32 and the nae_sat handle (the same eight entries) with the record nae_sat_params: the saturation, K18;
  *   nae_gate_design, nae_gate_block_f32 and the nae_gate handle (the same eight entries) with the record nae_gate_params: the noise gate and
  *   downward expander, K19; nae_mb_design, nae_mb_block_f32 and the nae_mb handle (the same eight entries) with the record nae_mb_params:
- *   the multiband compressor, K20. */
+ *   the multiband compressor, K20; nae_hpss_design, nae_hpss_block_f32 and the nae_hpss handle (the same eight entries) with the record
+ *   nae_hpss_params: the harmonic/percussive separation, K21. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -90,6 +91,7 @@ typedef struct nae_sat nae_sat;
 typedef struct nae_gate nae_gate;
 typedef struct nae_mb nae_mb;
 typedef struct nae_denoise nae_denoise;
+typedef struct nae_hpss nae_hpss;
 typedef struct nae_loud nae_loud;
 
 /* ------------------------------------------------------------------ context / plumbing */
@@ -173,6 +175,7 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *   conv_ring       spectrum slots per stream-channel of the long convolution's workspace ring (0: from the workspace cap; at least the
  *                   partition count is used); a handle reads it when it is created.  Neither changes a result
  *   dn_tile         hop blocks (of n_fft / 4 samples) one wave of the spectral gate walks (0: nae_pick_denoise_tile); every tiling gives the same bits
+ *   hpss_tile       hop blocks (of n_fft / 4 samples) one wave of the separation walks (0: nae_pick_hpss_tile); every tiling gives the same bits
  *   echo_group      streams per launch of nae_echo_block_f32 (0: as many as keep the delay lines inside the 256 MiB workspace cap); every grouping
  *                   gives the same bits
  *   mod_sub         samples one wave of the modulated delay computes in parallel, 1 ... 64 (0: 64 without feedback, else min(64, floor(delay -
@@ -986,6 +989,47 @@ size_t nae_denoise_available(nae_denoise* h);
 int nae_denoise_receive(nae_denoise* h, float* dst, size_t max_frames, size_t* got);
 int nae_denoise_receive_host(nae_denoise* h, float* dst_host, size_t max_frames, size_t* got);
 int nae_denoise_destroy(nae_denoise* h);
+
+/* ------------------------------------------------------------------ K21 separation
+ * no reference code.  Spec ("K21 separation"): harmonic/percussive separation by medians over the STFT (Fitzgerald), in K13's
+ * geometry: n_fft = 512 ... 4096, hop H = n_fft / 4, frame f starts at sample (f - 3) H, the signal is zero outside [0, in_len).  Per frame
+ * and bin the key q = (uint16)(bits(p) >> 16) is the upper half of the f32 power p = X.x X.x + X.y X.y (0 for a frame outside the signal);
+ * value(q) is the float whose bits are q << 16.  Hq is the median of the keys of time_span frames to either side at that bin, Pq the median
+ * of the keys of freq_span bins to either side in that frame (mirrored at bins 0 and n_fft / 2), both in integers.  The mask m is, hard:
+ * 1 where Hq >= Pq, else 0; soft: with h = value(Hq), p = value(Pq) and s = (double)h + (double)p, 0.5 where s = 0, else (float)((double)h / s).
+ * The bin's gain is G = gain_p + d m (one product, one add) with d = (float)((double)gain_h - (double)gain_p).  Synthesis is the vocoder's:
+ * c2r, window, overlap-add in increasing frame order, NAE_OLA_GAIN.  The output has the input's length and is aligned with it sample for
+ * sample; with gain_h = gain_p the call is the STFT identity times that gain.  Bit-exact against the CPU statement
+ * (tests/hpss_ref/ref_hpss.c) under every tiling (debug key hpss_tile) and any cut of the input into puts.  Inputs whose power overflows f32
+ * are unspecified.
+ * Errors: a null pointer, ch not 1 or 2, a span outside 0 ... NAE_HPSS_MAX_SPAN, hard not 0 or 1, a gain that is negative, above
+ * (float)10^(NAE_HPSS_MAX_DB / 20) or not finite: NAE_ERR_INVALID; n_fft other than 512, 1024, 2048, 4096: NAE_ERR_UNSUPPORTED; in_len = 0 or
+ * n_streams = 0: NAE_OK after the checks, nothing is launched.  Views as K9's. */
+typedef struct nae_hpss_params {
+    int n_fft;              /* 512, 1024, 2048 or 4096 */
+    int time_span;          /* Tn: frames to either side of the harmonic median, 0 ... NAE_HPSS_MAX_SPAN */
+    int freq_span;          /* Fn: bins to either side of the percussive median, 0 ... NAE_HPSS_MAX_SPAN */
+    int hard;               /* 1: the binary mask; 0: the soft one */
+    float gain_h;           /* gain of a bin that is all harmonic (m = 1) */
+    float gain_p;           /* gain of a bin that is all percussive (m = 0) */
+} nae_hpss_params;
+/* The parameters on the host, in double: a level at or below NAE_HPSS_MIN_DB is gain 0, else gain = (float)10^(dB / 20).  NAE_ERR_INVALID: a
+ * null pointer, a level that is not finite or outside NAE_HPSS_MIN_DB ... NAE_HPSS_MAX_DB, a span outside 0 ... NAE_HPSS_MAX_SPAN, hard not
+ * 0 or 1; NAE_ERR_UNSUPPORTED: n_fft other than 512 ... 4096.  No context, no device work. */
+int nae_hpss_design(double harmonic_db, double percussive_db, int n_fft, int time_span, int freq_span, int hard, nae_hpss_params* out);
+int nae_hpss_block_f32(nae_ctx* ctx, const nae_hpss_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                       const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch).  With H = n_fft / 4, after every put floor((put total - (time_span + 3) H) / H) H
+ * frames have become available in all, never fewer than zero; nae_hpss_flush releases the rest, so in_len frames come out in all, equal to
+ * the block call's however the input is cut.  A put after the flush: NAE_ERR_STATE. */
+int nae_hpss_create(nae_ctx* ctx, const nae_hpss_params* params, int channels, nae_hpss** h);
+int nae_hpss_put(nae_hpss* h, const float* interleaved, size_t S);
+int nae_hpss_put_host(nae_hpss* h, const float* interleaved_host, size_t S);
+int nae_hpss_flush(nae_hpss* h);
+size_t nae_hpss_available(nae_hpss* h);
+int nae_hpss_receive(nae_hpss* h, float* dst, size_t max_frames, size_t* got);
+int nae_hpss_receive_host(nae_hpss* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_hpss_destroy(nae_hpss* h);
 
 /* ------------------------------------------------------------------ K14 loudness
  * no reference code.  Spec ("K14 loudness"): the programme loudness of ITU-R BS.1770-4 / EBU R 128 with the true peak, and the one

@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = [
     "nae_mb_receive", "nae_mb_receive_host", "nae_mb_destroy",
     "nae_denoise_design", "nae_denoise_profile_f32", "nae_denoise_block_f32", "nae_denoise_create", "nae_denoise_put", "nae_denoise_put_host",
     "nae_denoise_flush", "nae_denoise_available", "nae_denoise_receive", "nae_denoise_receive_host", "nae_denoise_destroy",
+    "nae_hpss_design", "nae_hpss_block_f32", "nae_hpss_create", "nae_hpss_put", "nae_hpss_put_host", "nae_hpss_flush", "nae_hpss_available",
+    "nae_hpss_receive", "nae_hpss_receive_host", "nae_hpss_destroy",
     "nae_loud_design", "nae_loud_lufs", "nae_loud_measure_f32", "nae_loud_apply_f32", "nae_loud_normalize_f32", "nae_loud_create", "nae_loud_put",
     "nae_loud_put_host", "nae_loud_flush", "nae_loud_get_result", "nae_loud_destroy",
 ]
@@ -77,7 +79,9 @@ SAT_CURVES = ("soft", "hard")                       # `curve` of nae_sat_params:
 GATE_MAX_HOLD = 1 << 21                             # NAE_GATE_MAX_HOLD (include/nae_dsp_spec.h)
 GATE_MODES = ("gate", "expander")                   # `mode` of nae_gate_design: NAE_GATE_MODE_GATE, NAE_GATE_MODE_EXPANDER
 MB_MAX_BANDS, MB_MAX_SECTIONS = 4, 14               # NAE_MB_MAX_BANDS, NAE_MB_MAX_SECTIONS (include/nae_dsp_spec.h)
-HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat", "nae_gate", "nae_mb")   # the handles with the full put / receive set of entries
+HPSS_MAX_SPAN = 8                                   # NAE_HPSS_MAX_SPAN (include/nae_dsp_spec.h)
+HPSS_MASKS = ("soft", "hard")                       # `hard` of nae_hpss_design: 0, 1
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat", "nae_gate", "nae_mb", "nae_hpss")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -237,6 +241,11 @@ class DenoiseParams(C.Structure):
     _fields_ = [("n_fft", C.c_int), ("time_smooth", C.c_int), ("freq_smooth", C.c_int), ("thr_scale", C.c_float), ("floor_gain", C.c_float)]
 
 
+class HpssParams(C.Structure):
+    """nae_hpss_params: the separation's parameters (include/nae_gpu.h); nae_hpss_design makes them from decibels"""
+    _fields_ = [("n_fft", C.c_int), ("time_span", C.c_int), ("freq_span", C.c_int), ("hard", C.c_int), ("gain_h", C.c_float), ("gain_p", C.c_float)]
+
+
 class LoudParams(C.Structure):
     """nae_loud_params: the loudness meter's parameters (include/nae_gpu.h); nae_loud_design makes them from a sample rate and decibels"""
     _fields_ = [("sample_rate", C.c_int), ("sub_block", C.c_int), ("coef", C.c_double * 10), ("gate_abs", C.c_double), ("target", C.c_double),
@@ -369,6 +378,8 @@ def load_library() -> C.CDLL:
         "nae_denoise_design": (i, [d, d, i, i, i, P(DenoiseParams)]), "nae_denoise_profile_f32": (i, [vp, i, P(Sig), sz, i, vp]),
         "nae_denoise_block_f32": (i, [vp, P(DenoiseParams), vp, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
+        "nae_hpss_design": (i, [d, d, i, i, i, i, P(HpssParams)]),
+        "nae_hpss_block_f32": (i, [vp, P(HpssParams), P(Sig), sz, i, sz, P(Sig)]), "nae_hpss_create": (i, [vp, P(HpssParams), i, P(vp)]),
         "nae_loud_design": (i, [i, d, d, d, P(LoudParams)]), "nae_loud_lufs": (d, [d]),
         "nae_loud_measure_f32": (i, [vp, P(LoudParams), P(Sig), sz, i, sz, vp]), "nae_loud_apply_f32": (i, [vp, vp, P(Sig), sz, i, sz, P(Sig)]),
         "nae_loud_normalize_f32": (i, [vp, P(LoudParams), P(Sig), sz, i, sz, P(Sig), vp]),
@@ -915,6 +926,20 @@ class Context:
             raise NaeError(f"nae_denoise_design({reduction_db}, {sensitivity_db}, {n_fft}, {time_smooth}, {freq_smooth}) failed: {rc}")
         return out
 
+    @staticmethod
+    def hpss_design(harmonic_db: float = 0.0, percussive_db: float = -120.0, n_fft: int = 2048, time_span: int = 8, freq_span: int = 8,
+                    mask: str = "soft") -> "HpssParams":
+        """the parameters of the harmonic/percussive separation from decibels (nae_hpss_design); a level of -120 dB is gain 0"""
+        out = HpssParams()
+        rc = load_library().nae_hpss_design(harmonic_db, percussive_db, n_fft, time_span, freq_span, HPSS_MASKS.index(mask), C.byref(out))
+        if rc:
+            raise NaeError(f"nae_hpss_design({harmonic_db}, {percussive_db}, {n_fft}, {time_span}, {freq_span}, {mask}) failed: {rc}")
+        return out
+
+    def hpss_block(self, params: "HpssParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the separation `params` over every stream (nae_hpss_block_f32); dst receives in_len frames"""
+        self._ck(self.lib.nae_hpss_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     def denoise_profile(self, n_fft: int, src: Sig, length: int, ch: int, profile_ptr: int):
         """the noise powers [ch][n_fft / 2 + 1] of the excerpt's whole frames into device memory at profile_ptr (asynchronous)"""
         self._ck(self.lib.nae_denoise_profile_f32(self.h, n_fft, C.byref(src), length, ch, profile_ptr))
@@ -1160,6 +1185,17 @@ class Denoise(_Handle):
     def __init__(self, ctx: Context, params: DenoiseParams, profile_ptr: int, profile_ch: int, channels: int):
         super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_denoise_create(ctx.h, C.byref(params), profile_ptr, profile_ch, channels, C.byref(self.h)))
+
+
+class Hpss(_Handle):
+    """The separation's streaming handle (nae_hpss_create): put interleaved f32, flush, receive.  Before the flush the hop blocks with
+    time_span + 3 blocks behind them are available."""
+
+    _prefix = "nae_hpss"
+
+    def __init__(self, ctx: Context, params: HpssParams, channels: int):
+        super().__init__(ctx, channels)
+        ctx._ck(ctx.lib.nae_hpss_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
 
 
 class Loud(_Handle):

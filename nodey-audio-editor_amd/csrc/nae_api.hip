@@ -230,6 +230,7 @@ int nae_debug_set(nae_ctx* ctx, const char* key, long long value)
     if (k == "pv_tile" && count) ctx->pv_tile = (int)value;
     else if (k == "fir_tile" && count) ctx->fir_tile = (int)value;
     else if (k == "dn_tile" && count) ctx->dn_tile = (int)value;
+    else if (k == "hpss_tile" && count) ctx->hpss_tile = (int)value;
     else if (k == "conv_tile" && count) ctx->conv_tile = (int)value;
     else if (k == "conv_ring" && count) ctx->conv_ring = (int)value;
     else if (k == "echo_group" && count) ctx->echo_group = (int)value;

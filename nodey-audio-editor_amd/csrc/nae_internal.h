@@ -41,6 +41,7 @@ struct nae_ctx {
     CtxConst conv_spec;          // nae_conv_block_f32's spectra of the last call's n_fft, taps_ch and taps, apart from the FIR filter's (kernels_conv.hip)
     CtxBuf ws_conv;              // the ring of its launches
     int dn_tile = 0;             // hop blocks per tile of the spectral gate; 0 = choose per launch (nae_pick_denoise_tile)
+    int hpss_tile = 0;           // hop blocks per tile of the separation; 0 = choose per launch (nae_pick_hpss_tile)
     CtxConst eq_block;           // the constant block of the last call's sections: the EQ, echo and keyed-dynamics block calls (nae_eq_cached_block)
     CtxConst loud_block;         // the loudness entries' constant block of the last call's K-weighting (kernels_loud.hip)
     CtxBuf ws_loud;              // their workspace: states, sub-block energies, records
@@ -386,6 +387,14 @@ int nae_denoise_check(nae_ctx* ctx, const nae_denoise_params* p, const float* pr
 int nae_launch_denoise(nae_ctx* ctx, const nae_denoise_params* p, const float* d_profile, int profile_ch, const nae_sig* src, size_t in_len, int ch,
                        size_t n_streams, const nae_sig* dst, size_t b_origin, size_t b_stop);
 int nae_pick_denoise_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc);
+
+// kernels_hpss.hip: the harmonic/percussive separation ("K21 separation").  nae_hpss_check: the parameter rules of the block call
+// and the handle.  nae_launch_hpss runs hop blocks [b_origin, b_stop) of absolutely indexed signals of in_len samples: it reads from
+// (b_origin - time_span - 3) H on and, in front of a block, time_span + 3 blocks ahead (zero from in_len on), and keeps nothing between launches.
+int nae_hpss_check(nae_ctx* ctx, const nae_hpss_params* p, int ch);
+int nae_launch_hpss(nae_ctx* ctx, const nae_hpss_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
+                    size_t b_origin, size_t b_stop);
+int nae_pick_hpss_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc);
 
 // kernels_loud.hip: the loudness meter ("K14 loudness").  nae_loud_check: the parameter rules of the block entries and the handle.  A
 // constant block holds nae_loud_block_bytes() bytes: K11's block of the two K-weighting sections, then the true-peak taps (nae_loud_make_block,

@@ -134,6 +134,13 @@ struct nae_denoise : BlockHandle {
     int process() override;
 };
 
+// the separation's handle ("K21 separation"): whole hop blocks of n_fft / 4 samples are computed once the time_span + 3 blocks behind
+// them are there; the input stays from time_span + 3 blocks in front of the next block on, and nothing else is kept
+struct nae_hpss : BlockHandle {
+    nae_hpss_params params;
+    int process() override;
+};
+
 // the loudness meter's handle ("K14 loudness"): whole chunks of NAE_EQ_CHUNK samples are measured as they fill and leave the FIFO
 // (the state carries the 11 samples the true peak reads in front of a chunk); the sub-block energies grow on the device; the flush measures the
 // rest and runs the gates.  Nothing comes out of it but the record.
@@ -418,6 +425,14 @@ int nae_denoise::process()
     const size_t H = (size_t)params.n_fft / 4, reach = (size_t)params.time_smooth + 3;
     return run_units(H, reach * H, reach, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
         return nae_launch_denoise(ctx, &params, d_profile, profile_ch, &src, in.total, ch, 1, &dst, from, to);
+    });
+}
+
+int nae_hpss::process()
+{
+    const size_t H = (size_t)params.n_fft / 4, reach = (size_t)params.time_span + 3;
+    return run_units(H, reach * H, reach, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
+        return nae_launch_hpss(ctx, &params, &src, in.total, ch, 1, &dst, from, to);
     });
 }
 
@@ -873,6 +888,28 @@ size_t nae_denoise_available(nae_denoise* h) { return handle_available(h); }
 int nae_denoise_receive(nae_denoise* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_denoise_receive_host(nae_denoise* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_denoise_destroy(nae_denoise* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ separation
+int nae_hpss_create(nae_ctx* ctx, const nae_hpss_params* params, int channels, nae_hpss** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    const int rc = nae_hpss_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_hpss* s = handle_new<nae_hpss>(ctx, channels);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    return handle_created(s, NAE_OK, h);
+}
+
+int nae_hpss_put(nae_hpss* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_hpss_put_host(nae_hpss* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+int nae_hpss_flush(nae_hpss* h) { return handle_flush(h); }
+size_t nae_hpss_available(nae_hpss* h) { return handle_available(h); }
+int nae_hpss_receive(nae_hpss* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_hpss_receive_host(nae_hpss* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_hpss_destroy(nae_hpss* h) { return handle_destroy(h); }
 
 // ------------------------------------------------------------------------------------------------ loudness
 int nae_loud_create(nae_ctx* ctx, const nae_loud_params* params, int channels, nae_loud** h)

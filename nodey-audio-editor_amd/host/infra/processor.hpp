@@ -169,4 +169,6 @@ namespace infra
 	void register_gate_processors();
 	// the multiband compressor (audio_multiband): called after the twelve above, each of which stays the list it was
 	void register_multiband_processors();
+	// the harmonic/percussive separation (audio_separation): called after the thirteen above, each of which stays the list it was
+	void register_separation_processors();
 }

@@ -1,5 +1,5 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
-// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat), Audio_gate (nae_gate), Audio_multiband (nae_mb) and Audio_denoise (nae_denoise), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
+// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat), Audio_gate (nae_gate), Audio_multiband (nae_mb), Audio_denoise (nae_denoise) and Audio_separation (nae_hpss), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 // Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
 // A node's parameters are stated once: the members and their defaults in the settings record of audio-<node>.hpp, and here, in front of the
@@ -17,6 +17,7 @@
 #include "audio-gate.hpp"
 #include "audio-multiband.hpp"
 #include "audio-denoise.hpp"
+#include "audio-separation.hpp"
 #include "audio-loudness.hpp"
 #include "node-fields.hpp"
 #include "nae_dsp_spec.h"
@@ -1081,6 +1082,56 @@ namespace processor
 				nae_denoise* dn = nullptr;
 				gpu::check(nae_denoise_create(ctx, &params, profile, ch, ch, &dn), "nae_denoise_create");
 				return dn;
+			}
+		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_separation
+	infra::Processor::Info Audio_separation::get_processor_info()
+	{
+		return {"audio_separation", "Audio Separation", false, [] { return std::unique_ptr<infra::Processor>(new Audio_separation); },
+				"Harmonic/percussive separation: a level for the tonal and one for the transient part, split by medians over time and frequency (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_separation::get_pin_attributes() const { return io_pins(); }
+
+	namespace
+	{
+		const char* const separation_mask_names[] = {"soft", "hard"};
+		constexpr std::tuple separation_fields{
+			Number{"harmonic_db", &Separation_settings::harmonic_db, Separation_settings::default_harmonic_db, NAE_HPSS_MIN_DB, NAE_HPSS_MAX_DB},
+			Number{"percussive_db", &Separation_settings::percussive_db, Separation_settings::default_percussive_db, NAE_HPSS_MIN_DB, NAE_HPSS_MAX_DB},
+			Choice{"mask", &Separation_settings::mask, separation_mask_names},
+			Number{"fft_size", &Separation_settings::fft_size, Separation_settings::default_fft_size, 512, 4096, stft_size},   // the noise reduction's rule and default
+			Number{"time_span", &Separation_settings::time_span, Separation_settings::default_time_span, 0, NAE_HPSS_MAX_SPAN},
+			Number{"freq_span", &Separation_settings::freq_span, Separation_settings::default_freq_span, 0, NAE_HPSS_MAX_SPAN},
+		};
+		static_assert(Separation_settings::default_fft_size == Denoise_settings::default_fft_size, "stft_size clamps to the one default");
+	}
+
+	Json::Value Audio_separation::serialize() const { return to_json(*this, separation_fields); }
+	void Audio_separation::deserialize(const Json::Value& value) { Separation_settings::operator=(from_json<Separation_settings>(value, "Audio_separation", separation_fields)); }
+	void Separation_settings::clamp() { detail::clamp(*this, separation_fields); }
+
+	void Audio_separation::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Separation");
+		run_on_handle<nae_hpss>(
+			io.input, io.output, stop_token, {"nae_hpss", nae_hpss_put, nae_hpss_flush, nae_hpss_available, nae_hpss_receive, nae_hpss_destroy}, "node", 0,
+			[&](nae_ctx* ctx, const Frame_data*, int ch)
+			{
+				nae_hpss_params params;
+				if (nae_hpss_design(harmonic_db, percussive_db, fft_size, time_span, freq_span, mask == Mask::Hard ? 1 : 0, &params) != NAE_OK)
+					throw infra::Processor::Runtime_error("Invalid separation parameters", "A parameter of the separation node lies outside its range.",
+										infra::fmt("harmonic %g dB, percussive %g dB, fft_size %d", harmonic_db, percussive_db, fft_size));
+				nae_hpss* hp = nullptr;
+				gpu::check(nae_hpss_create(ctx, &params, ch, &hp), "nae_hpss_create");
+				return hp;
 			}
 		);
 	}

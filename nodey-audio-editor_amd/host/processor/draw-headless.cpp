@@ -24,6 +24,7 @@
 #include "audio-gate.hpp"
 #include "audio-multiband.hpp"
 #include "audio-denoise.hpp"
+#include "audio-separation.hpp"
 #include "audio-loudness.hpp"
 #include "audio-mix.hpp"
 #include "audio-velocity.hpp"
@@ -133,6 +134,9 @@ namespace processor
 
 	void Audio_denoise::draw_title() {}
 	bool Audio_denoise::draw_content(bool) { clamp(); return false; }   // a frame size the library has, else the default
+
+	void Audio_separation::draw_title() {}
+	bool Audio_separation::draw_content(bool) { clamp(); return false; }   // a frame size the library has, else the default
 
 	void Audio_loudness::draw_title() {}
 	bool Audio_loudness::draw_content(bool) { clamp(); return false; }

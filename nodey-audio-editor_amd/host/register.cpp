@@ -15,6 +15,7 @@
 #include "processor/audio-saturation.hpp"
 #include "processor/audio-gate.hpp"
 #include "processor/audio-multiband.hpp"
+#include "processor/audio-separation.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -75,4 +76,7 @@ namespace infra
 
 	// the multiband compressor; a call of its own, so the twelve lists above stay what they were
 	void register_multiband_processors() { register_each<processor::Audio_multiband>(); }
+
+	// the harmonic/percussive separation; a call of its own, so the thirteen lists above stay what they were
+	void register_separation_processors() { register_each<processor::Audio_separation>(); }
 }
