@@ -104,6 +104,16 @@
 #define NAE_GATE_MAX_HOLD_S 10.0
 #define NAE_GATE_MODE_GATE 0
 #define NAE_GATE_MODE_EXPANDER 1
+/* K22 limiter ("K22 limiter"): a true-peak look-ahead brickwall on K12's tiling (NAE_DYN_LANE, NAE_DYN_CHUNK), floor
+ * (NAE_DYN_FLOOR_DB) and release range (NAE_DYN_MIN_RELEASE_S, NAE_DYN_MAX_RELEASE_S), with K14's oversampler (NAE_LOUD_TP_PHASES,
+ * NAE_LOUD_TP_TAPS) as the detector: its level reaches NAE_LIM_TP_REACH samples to either side of a sample, and the look-ahead with that
+ * reach stays within one chunk.  The attack is a moving sum of ceil(y1 NAE_LIM_Q_SCALE) as integers. */
+#define NAE_LIM_TP_REACH 6
+#define NAE_LIM_MAX_LOOKAHEAD (NAE_DYN_CHUNK - NAE_LIM_TP_REACH)
+#define NAE_LIM_Q_SCALE 16777216.0
+#define NAE_LIM_MIN_CEILING_DB (-20.0)
+#define NAE_LIM_MAX_CEILING_DB 0.0
+#define NAE_LIM_MAX_GAIN_DB 24.0
 /* K20 multiband ("K20 multiband"): a Linkwitz-Riley crossover tree of K11 sections into 2 ... NAE_MB_MAX_BANDS bands, K12 on every
  * band, and the bands' sum.  The tree of B bands has 4, 9 or 14 sections in fixed slots: at most NAE_MB_MAX_SECTIONS, inside K11's constant
  * block of NAE_EQ_MAX_SECTIONS */

@@ -58,7 +58,8 @@ extern "C" {
  *   nae_gate_design, nae_gate_block_f32 and the nae_gate handle (the same eight entries) with the record nae_gate_params: the noise gate and
  *   downward expander, K19; nae_mb_design, nae_mb_block_f32 and the nae_mb handle (the same eight entries) with the record nae_mb_params:
  *   the multiband compressor, K20; nae_hpss_design, nae_hpss_block_f32 and the nae_hpss handle (the same eight entries) with the record
- *   nae_hpss_params: the harmonic/percussive separation, K21. */
+ *   nae_hpss_params: the harmonic/percussive separation, K21; nae_lim_design, nae_lim_block_f32 and the nae_lim handle (the same eight
+ *   entries) with the record nae_lim_params: the true-peak look-ahead limiter, K22. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -92,6 +93,7 @@ typedef struct nae_gate nae_gate;
 typedef struct nae_mb nae_mb;
 typedef struct nae_denoise nae_denoise;
 typedef struct nae_hpss nae_hpss;
+typedef struct nae_lim nae_lim;
 typedef struct nae_loud nae_loud;
 
 /* ------------------------------------------------------------------ context / plumbing */
@@ -1030,6 +1032,56 @@ size_t nae_hpss_available(nae_hpss* h);
 int nae_hpss_receive(nae_hpss* h, float* dst, size_t max_frames, size_t* got);
 int nae_hpss_receive_host(nae_hpss* h, float* dst_host, size_t max_frames, size_t* got);
 int nae_hpss_destroy(nae_hpss* h);
+
+/* ------------------------------------------------------------------ K22 limiter (true-peak look-ahead brickwall)
+ * no reference code.  Spec ("K22 limiter"): one detector per stream-channel, or with link = 1 on a stereo stream one per stream.
+ * Every step is one IEEE operation in the order written, the output rounded once to f32.  K = 20 log10(2), KINV = 1 / K, dyn_log2 and
+ * dyn_exp2 are K12's; every maximum of f32 is a > m ? a : m.  Per detector, x zero outside [0, in_len), la = lookahead:
+ *   level       a_c[n] = |x_c[n]|.  true_peak = 1: v_p[m] = K14's phase p at m (the same taps, tap 0 times x[m] first), e_c[m] the largest
+ *               |v_p[m]| over p = 0 ... 3 from 0.0f on, L_c[n] = max(a_c[n], e_c[n + 5], e_c[n + 6]) in that order, D = 6; true_peak = 0:
+ *               L_c = a_c, D = 0.  Linked: L = L_1 > L_0 ? L_1 : L_0
+ *   demand      xg = K dyn_log2((double)L), a zero L at NAE_DYN_FLOOR_DB; u = (xg + gain_db) - ceiling_db; r[n] = u > 0 ? u : 0
+ *   look-ahead  d[n] = max(r[n] ... r[n + la])
+ *   release     y1[n] = max(d[n], (alpha_release y1[n - 1]) + (omr d[n])), omr = 1 - alpha_release made once, y1[-1] = 0, in K12's tiled
+ *               form (NAE_DYN_LANE samples per lane, chunks of NAE_DYN_CHUNK from the stream's sample 0, six Kogge-Stone steps)
+ *   attack      q[n] = (int64) ceil(y1[n] 2^24), 0 where that is not finite; q[n] = q[0] for n < 0; W[n] = q[n - la] + ... + q[n] in
+ *               integers; s[n] = (double)W[n] / (double)((la + 1) 2^24)
+ *   gain        g[n] = dyn_exp2((gain_db - s[n]) KINV); out_c[n] = (float)((double)x_c[n] g[n]) for each channel of the detector
+ * The call is compensated as K12 is: output n is input n under a gain that has seen la + D samples ahead; in_len frames come out and
+ * nothing past in_len is stored.  s[n] >= r[n], so |out[n]| <= 10^(ceiling_db / 20) (1 + 2^-22) for any input, release and look-ahead; the
+ * gain starts at its reduced value (no ramp at sample 0); any cut into puts gives the block call's bits; a non-finite sample i leaves every
+ * output before i - la - D as it was, and the call returns NAE_OK.  Bit-exact against the CPU statement (tests/lim_ref/ref_lim.c).
+ * Errors: a null pointer, ch not 1 or 2, a field that is not finite or outside its range (ceiling_db -20 ... 0; gain_db -24 ... 24;
+ * alpha_release in [0, 1); lookahead not negative; true_peak and link 0 or 1): NAE_ERR_INVALID; a lookahead above NAE_LIM_MAX_LOOKAHEAD:
+ * NAE_ERR_UNSUPPORTED; in_len = 0 or n_streams = 0: NAE_OK after the checks, nothing is launched.  Views as nae_dyn_block_f32's:
+ * stream_stride 0 on the source and dst->base == src->base are allowed. */
+typedef struct nae_lim_params {
+    double ceiling_db;           /* no output sample lies above it */
+    double gain_db;              /* the drive in front of the limiter */
+    double alpha_release;
+    int lookahead;               /* samples: the length of the attack's box less one */
+    int true_peak;               /* 1: the detector hears K14's 4x oversampled signal */
+    int link;                    /* 1: one detector per stereo stream */
+} nae_lim_params;
+int nae_lim_block_f32(nae_ctx* ctx, const nae_lim_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                      const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch): before the flush floor((put - lookahead - D) / NAE_DYN_CHUNK) whole chunks are
+ * available, never negative; nae_lim_flush releases the rest, so in_len frames come out in all, equal to the block call's however the input
+ * is cut.  A put after the flush: NAE_ERR_STATE. */
+int nae_lim_create(nae_ctx* ctx, const nae_lim_params* params, int channels, nae_lim** h);
+int nae_lim_put(nae_lim* h, const float* interleaved, size_t S);
+int nae_lim_put_host(nae_lim* h, const float* interleaved_host, size_t S);
+int nae_lim_flush(nae_lim* h);
+size_t nae_lim_available(nae_lim* h);
+int nae_lim_receive(nae_lim* h, float* dst, size_t max_frames, size_t* got);
+int nae_lim_receive_host(nae_lim* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_lim_destroy(nae_lim* h);
+/* The record on the host, in double: alpha_release = exp(-1 / (release_s sample_rate)); lookahead = lround(lookahead_s sample_rate).
+ * Ranges: ceiling_db -20 ... 0, gain_db -24 ... 24, release_s 0.001 ... 5, lookahead_s not negative, true_peak and link 0 or 1.
+ * NAE_ERR_INVALID: a null pointer, sample_rate <= 0, an argument that is not finite or outside its range; NAE_ERR_UNSUPPORTED: a look-ahead
+ * above NAE_LIM_MAX_LOOKAHEAD samples at that rate.  No context, no device work. */
+int nae_lim_design(int sample_rate, double ceiling_db, double gain_db, double release_s, double lookahead_s, int true_peak, int link,
+                   nae_lim_params* out);
 
 /* ------------------------------------------------------------------ K14 loudness
  * no reference code.  Spec ("K14 loudness"): the programme loudness of ITU-R BS.1770-4 / EBU R 128 with the true peak, and the one

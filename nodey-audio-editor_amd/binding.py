@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = [
     "nae_denoise_flush", "nae_denoise_available", "nae_denoise_receive", "nae_denoise_receive_host", "nae_denoise_destroy",
     "nae_hpss_design", "nae_hpss_block_f32", "nae_hpss_create", "nae_hpss_put", "nae_hpss_put_host", "nae_hpss_flush", "nae_hpss_available",
     "nae_hpss_receive", "nae_hpss_receive_host", "nae_hpss_destroy",
+    "nae_lim_design", "nae_lim_block_f32", "nae_lim_create", "nae_lim_put", "nae_lim_put_host", "nae_lim_flush", "nae_lim_available",
+    "nae_lim_receive", "nae_lim_receive_host", "nae_lim_destroy",
     "nae_loud_design", "nae_loud_lufs", "nae_loud_measure_f32", "nae_loud_apply_f32", "nae_loud_normalize_f32", "nae_loud_create", "nae_loud_put",
     "nae_loud_put_host", "nae_loud_flush", "nae_loud_get_result", "nae_loud_destroy",
 ]
@@ -81,7 +83,8 @@ GATE_MODES = ("gate", "expander")                   # `mode` of nae_gate_design:
 MB_MAX_BANDS, MB_MAX_SECTIONS = 4, 14               # NAE_MB_MAX_BANDS, NAE_MB_MAX_SECTIONS (include/nae_dsp_spec.h)
 HPSS_MAX_SPAN = 8                                   # NAE_HPSS_MAX_SPAN (include/nae_dsp_spec.h)
 HPSS_MASKS = ("soft", "hard")                       # `hard` of nae_hpss_design: 0, 1
-HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat", "nae_gate", "nae_mb", "nae_hpss")   # the handles with the full put / receive set of entries
+LIM_MAX_LOOKAHEAD, LIM_TP_REACH = 1018, 6           # NAE_LIM_MAX_LOOKAHEAD, NAE_LIM_TP_REACH (include/nae_dsp_spec.h)
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat", "nae_gate", "nae_mb", "nae_hpss", "nae_lim")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -241,6 +244,13 @@ class DenoiseParams(C.Structure):
     _fields_ = [("n_fft", C.c_int), ("time_smooth", C.c_int), ("freq_smooth", C.c_int), ("thr_scale", C.c_float), ("floor_gain", C.c_float)]
 
 
+class LimParams(C.Structure):
+    """nae_lim_params: the limiter's parameters (include/nae_gpu.h): the ceiling and the drive in decibels, the release coefficient, the
+    look-ahead in samples, the true-peak detector and the channel link; nae_lim_design makes them from decibels and times"""
+    _fields_ = [("ceiling_db", C.c_double), ("gain_db", C.c_double), ("alpha_release", C.c_double), ("lookahead", C.c_int),
+                ("true_peak", C.c_int), ("link", C.c_int)]
+
+
 class HpssParams(C.Structure):
     """nae_hpss_params: the separation's parameters (include/nae_gpu.h); nae_hpss_design makes them from decibels"""
     _fields_ = [("n_fft", C.c_int), ("time_span", C.c_int), ("freq_span", C.c_int), ("hard", C.c_int), ("gain_h", C.c_float), ("gain_p", C.c_float)]
@@ -378,6 +388,8 @@ def load_library() -> C.CDLL:
         "nae_denoise_design": (i, [d, d, i, i, i, P(DenoiseParams)]), "nae_denoise_profile_f32": (i, [vp, i, P(Sig), sz, i, vp]),
         "nae_denoise_block_f32": (i, [vp, P(DenoiseParams), vp, i, P(Sig), sz, i, sz, P(Sig)]),
         "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
+        "nae_lim_design": (i, [i, d, d, d, d, i, i, P(LimParams)]),
+        "nae_lim_block_f32": (i, [vp, P(LimParams), P(Sig), sz, i, sz, P(Sig)]), "nae_lim_create": (i, [vp, P(LimParams), i, P(vp)]),
         "nae_hpss_design": (i, [d, d, i, i, i, i, P(HpssParams)]),
         "nae_hpss_block_f32": (i, [vp, P(HpssParams), P(Sig), sz, i, sz, P(Sig)]), "nae_hpss_create": (i, [vp, P(HpssParams), i, P(vp)]),
         "nae_loud_design": (i, [i, d, d, d, P(LoudParams)]), "nae_loud_lufs": (d, [d]),
@@ -940,6 +952,21 @@ class Context:
         """the separation `params` over every stream (nae_hpss_block_f32); dst receives in_len frames"""
         self._ck(self.lib.nae_hpss_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K22
+    @staticmethod
+    def lim_design(sample_rate: int, ceiling_db: float = -1.0, gain_db: float = 0.0, release_s: float = 0.1, lookahead_s: float = 0.0015,
+                   true_peak: bool = True, link: bool = True) -> "LimParams":
+        """the limiter's parameters from decibels and times (nae_lim_design)"""
+        out = LimParams()
+        rc = load_library().nae_lim_design(sample_rate, ceiling_db, gain_db, release_s, lookahead_s, int(true_peak), int(link), C.byref(out))
+        if rc:
+            raise NaeError(f"nae_lim_design({sample_rate}, {ceiling_db}, {gain_db}, {release_s}, {lookahead_s}, {true_peak}, {link}) failed: {rc}")
+        return out
+
+    def lim_block(self, params: "LimParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the limiter `params` over every stream (nae_lim_block_f32); dst receives in_len frames, compensated for the look-ahead"""
+        self._ck(self.lib.nae_lim_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     def denoise_profile(self, n_fft: int, src: Sig, length: int, ch: int, profile_ptr: int):
         """the noise powers [ch][n_fft / 2 + 1] of the excerpt's whole frames into device memory at profile_ptr (asynchronous)"""
         self._ck(self.lib.nae_denoise_profile_f32(self.h, n_fft, C.byref(src), length, ch, profile_ptr))
@@ -1185,6 +1212,17 @@ class Denoise(_Handle):
     def __init__(self, ctx: Context, params: DenoiseParams, profile_ptr: int, profile_ch: int, channels: int):
         super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_denoise_create(ctx.h, C.byref(params), profile_ptr, profile_ch, channels, C.byref(self.h)))
+
+
+class Limiter(_Handle):
+    """The limiter's streaming handle (nae_lim_create): put interleaved f32, flush, receive.  Before the flush the whole chunks of 1024 frames
+    with `lookahead` frames, and 6 more with `true_peak`, behind them are available."""
+
+    _prefix = "nae_lim"
+
+    def __init__(self, ctx: Context, params: LimParams, channels: int):
+        super().__init__(ctx, channels)
+        ctx._ck(ctx.lib.nae_lim_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
 
 
 class Hpss(_Handle):

@@ -1,6 +1,7 @@
 // dyn_steps.h — what the dynamics processor (kernels_dyn.hip, K12) and the keyed dynamics (kernels_dynkey.hip, K15) share: the launch record,
 // the two functions of the specification, the static curve, the staged load, and the walk of one wave over its detector's chunks (DESIGN.md
-// §3, "K12 dynamics", steps 1 to 6).  The two kernels differ in where the magnitude of steps 1 and 2 comes from; the walk takes that as a
+// §3, "K12 dynamics", steps 1 to 6).  Steps 3 and 4 stand as functions of their own (dyn_lookahead_max, dyn_release_scan): the limiter
+// (kernels_lim.hip, K22) runs them too.  The two kernels differ in where the magnitude of steps 1 and 2 comes from; the walk takes that as a
 // `Mag`, and states every other step once.  Both translation units are built with -ffp-contract=off: every step is one IEEE operation in
 // the order of the CPU statement (tests/dyn_ref/ref_dyn.c).
 //
@@ -142,6 +143,73 @@ struct DynPlainKey {
     static constexpr bool kSpareSgprs = false;
 };
 
+// step 3 of chunk ck: d[n] = max(r[n] ... r[n + la]) on dc, which holds what the maximum starts from: r (la < 16) or the lane's suffix maximum
+// (la >= 16).  ring: r or P of two chunks, sample m of the two, m < 2048 counted from an even chunk's first, at chunk_word(m); lane_max: M of
+// the same two chunks.  K12's, K15's and K22's.
+__device__ __forceinline__ void dyn_lookahead_max(const double* ring, const double* lane_max, long long ck, int lane, int la, bool wide,
+                                                  double (&dc)[kChunkT])
+{
+    const int q = la >> 4, rem = la & 15;
+    const int m0 = (int)(ck & 1) * kChunkC + lane * kChunkT;
+    if (!wide) {
+#pragma unroll 1
+        for (int t = 1; t <= la; t++) {
+#pragma unroll
+            for (int k = 0; k < kChunkT; k++) {
+                const int m = (m0 + k + t) & (2 * kChunkC - 1);
+                dc[k] = dyn_max(dc[k], ring[chunk_word(m)]);
+            }
+        }
+    } else {
+        // the whole lanes between: l + 1 ... l + q - 1, and l + q too where the window ends in lane l + q + 1
+        const int l0 = (int)(ck & 1) * 64 + lane;
+        double r1 = 0.0;
+#pragma unroll 1
+        for (int t = 1; t < q; t++) r1 = dyn_max(r1, lane_max[(l0 + t) & 127]);
+        const double r2 = dyn_max(r1, lane_max[(l0 + q) & 127]);
+#pragma unroll
+        for (int k = 0; k < kChunkT; k++) {
+            const int m = (m0 + k + la) & (2 * kChunkC - 1);
+            dc[k] = dyn_max(dc[k], dyn_max(k + rem >= kChunkT ? r2 : r1, ring[chunk_word(m)]));
+        }
+    }
+}
+
+// step 4 of a chunk: y1 = max(d, ar y1 + omr d) on dc, the step as the map y -> max(c, a y + b); sl: the lane number the scan's masks are made
+// of; y1c: the carry in front of the chunk, replaced by the one behind it
+__device__ __forceinline__ void dyn_release_scan(double ar, double omr, int sl, double& y1c, double (&dc)[kChunkT])
+{
+    double A = ar, B = omr * dc[0], M = dc[0];
+#pragma unroll
+    for (int k = 1; k < kChunkT; k++) {
+        const double bk = omr * dc[k];
+        A = ar * A;
+        B = (ar * B) + bk;
+        M = dyn_max(dc[k], (ar * M) + bk);
+    }
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        const double uA = __shfl_up(A, 1u << j), uB = __shfl_up(B, 1u << j), uM = __shfl_up(M, 1u << j);
+        const double nA = A * uA;
+        const double nB = (A * uB) + B;
+        const double nM = dyn_max(M, (A * uM) + B);
+        if (sl >= (1 << j)) {
+            A = nA;
+            B = nB;
+            M = nM;
+        }
+    }
+    const double pA = __shfl_up(A, 1u), pB = __shfl_up(B, 1u), pM = __shfl_up(M, 1u);
+    double s = dyn_max(pM, (pA * y1c) + pB);
+    if (sl == 0) s = y1c;
+#pragma unroll
+    for (int k = 0; k < kChunkT; k++) {
+        s = dyn_max(dc[k], (ar * s) + (omr * dc[k]));
+        dc[k] = s;
+    }
+    y1c = __shfl(s, 63);
+}
+
 // The walk of detector `det`'s wave over chunks [c_origin, c_stop): ip, op: the detector's first signal channel in and out (DC of them, src.cs
 // and out.cs apart).  state: [n_det][2] doubles, the carries (y1, yl) in front of chunk c_origin, replaced by the ones behind chunk
 // c_stop - 1; null: zero in, nothing out (the block call).  mag.level runs one chunk ahead of the rest: chunk c_origin first, and chunk c_stop
@@ -224,63 +292,10 @@ __device__ inline void dyn_walk(const float* ip, float* op, const SigViewD& src,
         // step 3: d[n] = max(r[n] ... r[n + la]); sample m of the two chunks, m < 2048 counted from an even chunk's first, stands at chunk_word(m).
         // The look-ahead is read from LDS here, behind the fence: what depends on it and on k is then made where it is used, sixteen compares,
         // not carried through the whole chunk loop as sixteen masks and sixteen addresses.
-        const int la = la_lds, q = la >> 4, rem = la & 15;
+        const int la = la_lds;
         const double ar = prm[kDynAr], omr = prm[kDynOmr], aa = prm[kDynAa], oma = prm[kDynOma], makeup = prm[kDynMakeup];
-        const int m0 = (int)(ck & 1) * kChunkC + lane * kChunkT;
-        if (!wide) {
-#pragma unroll 1
-            for (int t = 1; t <= la; t++) {
-#pragma unroll
-                for (int k = 0; k < kChunkT; k++) {
-                    const int m = (m0 + k + t) & (2 * kChunkC - 1);
-                    dc[k] = dyn_max(dc[k], ring[chunk_word(m)]);
-                }
-            }
-        } else {
-            // the whole lanes between: l + 1 ... l + q - 1, and l + q too where the window ends in lane l + q + 1
-            const int l0 = (int)(ck & 1) * 64 + lane;
-            double r1 = 0.0;
-#pragma unroll 1
-            for (int t = 1; t < q; t++) r1 = dyn_max(r1, lane_max[(l0 + t) & 127]);
-            const double r2 = dyn_max(r1, lane_max[(l0 + q) & 127]);
-#pragma unroll
-            for (int k = 0; k < kChunkT; k++) {
-                const int m = (m0 + k + la) & (2 * kChunkC - 1);
-                dc[k] = dyn_max(dc[k], dyn_max(k + rem >= kChunkT ? r2 : r1, ring[chunk_word(m)]));
-            }
-        }
-        // step 4: y1 = max(d, ar y1 + omr d), the step as the map y -> max(c, a y + b)
-        {
-            double A = ar, B = omr * dc[0], M = dc[0];
-#pragma unroll
-            for (int k = 1; k < kChunkT; k++) {
-                const double bk = omr * dc[k];
-                A = ar * A;
-                B = (ar * B) + bk;
-                M = dyn_max(dc[k], (ar * M) + bk);
-            }
-#pragma unroll
-            for (int j = 0; j < 6; j++) {
-                const double uA = __shfl_up(A, 1u << j), uB = __shfl_up(B, 1u << j), uM = __shfl_up(M, 1u << j);
-                const double nA = A * uA;
-                const double nB = (A * uB) + B;
-                const double nM = dyn_max(M, (A * uM) + B);
-                if (sl >= (1 << j)) {
-                    A = nA;
-                    B = nB;
-                    M = nM;
-                }
-            }
-            const double pA = __shfl_up(A, 1u), pB = __shfl_up(B, 1u), pM = __shfl_up(M, 1u);
-            double s = dyn_max(pM, (pA * y1c) + pB);
-            if (sl == 0) s = y1c;
-#pragma unroll
-            for (int k = 0; k < kChunkT; k++) {
-                s = dyn_max(dc[k], (ar * s) + (omr * dc[k]));
-                dc[k] = s;
-            }
-            y1c = __shfl(s, 63);
-        }
+        dyn_lookahead_max(ring, lane_max, ck, lane, la, wide, dc);
+        dyn_release_scan(ar, omr, sl, y1c, dc);
         // step 5: yl = aa yl + oma y1, the step as the map y -> a y + b
         {
             double A = aa, B = oma * dc[0];

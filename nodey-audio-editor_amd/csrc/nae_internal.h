@@ -396,6 +396,19 @@ int nae_launch_hpss(nae_ctx* ctx, const nae_hpss_params* p, const nae_sig* src, 
                     size_t b_origin, size_t b_stop);
 int nae_pick_hpss_tile(nae_ctx* ctx, int n_fft, size_t blocks, size_t n_sc);
 
+// kernels_lim.hip: the limiter ("K22 limiter").  nae_lim_check: the parameter rules of the block call and the handle.
+// nae_lim_detectors: one per stream with `link` on stereo, else one per stream-channel.  nae_lim_wait: lookahead + D, the samples behind a chunk
+// its gain reads.  nae_launch_lim runs chunks [c_origin, c_stop) of absolutely indexed signals of in_len samples and reads from 16 samples in
+// front of chunk c_origin on (zero below sample 0 and from in_len on); d_state, nae_lim_state_words() 64-bit words per detector, holds the
+// carries in front of chunk c_origin (y1's bits, the running total of q, the prefix sums of chunk c_origin - 1) and then the ones in front of
+// chunk c_stop; all zero or null: the start of a stream (null: nothing kept).
+int nae_lim_check(nae_ctx* ctx, const nae_lim_params* p, int ch);
+size_t nae_lim_detectors(const nae_lim_params* p, int ch, size_t n_streams);
+size_t nae_lim_state_words();
+size_t nae_lim_wait(const nae_lim_params* p);
+int nae_launch_lim(nae_ctx* ctx, const nae_lim_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
+                   size_t c_origin, size_t c_stop, unsigned long long* d_state);
+
 // kernels_loud.hip: the loudness meter ("K14 loudness").  nae_loud_check: the parameter rules of the block entries and the handle.  A
 // constant block holds nae_loud_block_bytes() bytes: K11's block of the two K-weighting sections, then the true-peak taps (nae_loud_make_block,
 // which waits for the upload).  nae_launch_loud_measure runs chunks [c_origin, c_stop) of absolutely indexed signals: d_state, n_streams x ch
@@ -408,6 +421,7 @@ size_t nae_loud_state_bytes();
 int nae_loud_check(nae_ctx* ctx, const nae_loud_params* p, int ch);
 int nae_loud_make_block(nae_ctx* ctx, const nae_loud_params* p, void* d_block);
 size_t nae_loud_chunks(size_t in_len, bool flushed);
+void nae_loud_taps(float* out);   // the 48 true-peak taps [phase][k] as f32: K14's, and K22's detector
 int nae_launch_loud_measure(nae_ctx* ctx, const nae_loud_params* p, const void* d_block, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
                             size_t c_origin, size_t c_stop, void* d_state, double* d_E, size_t e_ss, size_t n_sub);
 int nae_launch_loud_gate(nae_ctx* ctx, const nae_loud_params* p, size_t in_len, int ch, size_t n_streams, const void* d_state, const double* d_E,

@@ -141,6 +141,15 @@ struct nae_hpss : BlockHandle {
     int process() override;
 };
 
+// the limiter's handle ("K22 limiter"): whole chunks of NAE_DYN_CHUNK samples are computed once the `lookahead` samples behind them
+// and the detector's reach are there; the chunk in front of the next one stays in the FIFO (the true-peak FIR reads its last samples), and the
+// detectors' carries stay on the device between two launches
+struct nae_lim : BlockHandle {
+    nae_lim_params params;
+    unsigned long long* d_state = nullptr;  // [detector][nae_lim_state_words()]: y1's bits, the running total of q, the last chunk's prefix sums
+    int process() override;
+};
+
 // the loudness meter's handle ("K14 loudness"): whole chunks of NAE_EQ_CHUNK samples are measured as they fill and leave the FIFO
 // (the state carries the 11 samples the true peak reads in front of a chunk); the sub-block energies grow on the device; the flush measures the
 // rest and runs the gates.  Nothing comes out of it but the record.
@@ -425,6 +434,13 @@ int nae_denoise::process()
     const size_t H = (size_t)params.n_fft / 4, reach = (size_t)params.time_smooth + 3;
     return run_units(H, reach * H, reach, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
         return nae_launch_denoise(ctx, &params, d_profile, profile_ch, &src, in.total, ch, 1, &dst, from, to);
+    });
+}
+
+int nae_lim::process()
+{
+    return run_units(NAE_DYN_CHUNK, nae_lim_wait(&params), 1, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
+        return nae_launch_lim(ctx, &params, &src, in.total, ch, 1, &dst, from, to, d_state);
     });
 }
 
@@ -910,6 +926,33 @@ size_t nae_hpss_available(nae_hpss* h) { return handle_available(h); }
 int nae_hpss_receive(nae_hpss* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_hpss_receive_host(nae_hpss* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_hpss_destroy(nae_hpss* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ limiter
+int nae_lim_create(nae_ctx* ctx, const nae_lim_params* params, int channels, nae_lim** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_lim_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_lim* s = handle_new<nae_lim>(ctx, channels);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    // in front of sample 0: y1 = 0 and nothing summed; the prefix sums are made at chunk 0
+    const size_t words = nae_lim_detectors(params, channels, 1) * nae_lim_state_words();
+    rc = s->dev_alloc(&s->d_state, words, "hipMalloc(lim state)");
+    if (!rc) rc = nae_check(ctx, hipMemsetAsync(s->d_state, 0, words * sizeof(unsigned long long), ctx->stream), "hipMemsetAsync(lim state)");
+    return handle_created(s, rc, h);
+}
+
+int nae_lim_put(nae_lim* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_lim_put_host(nae_lim* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+// flush: the chunks that waited for their look-ahead and the partial last one come out: as many frames as were put over the handle's life
+int nae_lim_flush(nae_lim* h) { return handle_flush(h); }
+size_t nae_lim_available(nae_lim* h) { return handle_available(h); }
+int nae_lim_receive(nae_lim* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_lim_receive_host(nae_lim* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_lim_destroy(nae_lim* h) { return handle_destroy(h); }
 
 // ------------------------------------------------------------------------------------------------ loudness
 int nae_loud_create(nae_ctx* ctx, const nae_loud_params* params, int channels, nae_loud** h)

@@ -171,4 +171,6 @@ namespace infra
 	void register_multiband_processors();
 	// the harmonic/percussive separation (audio_separation): called after the thirteen above, each of which stays the list it was
 	void register_separation_processors();
+	// the true-peak limiter (audio_limiter): called after the fourteen above, each of which stays the list it was
+	void register_limiter_processors();
 }

@@ -1,5 +1,5 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
-// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat), Audio_gate (nae_gate), Audio_multiband (nae_mb), Audio_denoise (nae_denoise) and Audio_separation (nae_hpss), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
+// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat), Audio_gate (nae_gate), Audio_multiband (nae_mb), Audio_denoise (nae_denoise), Audio_separation (nae_hpss) and Audio_limiter (nae_lim), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 // Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
 // A node's parameters are stated once: the members and their defaults in the settings record of audio-<node>.hpp, and here, in front of the
@@ -15,6 +15,7 @@
 #include "audio-modulation.hpp"
 #include "audio-saturation.hpp"
 #include "audio-gate.hpp"
+#include "audio-limiter.hpp"
 #include "audio-multiband.hpp"
 #include "audio-denoise.hpp"
 #include "audio-separation.hpp"
@@ -1132,6 +1133,60 @@ namespace processor
 				nae_hpss* hp = nullptr;
 				gpu::check(nae_hpss_create(ctx, &params, ch, &hp), "nae_hpss_create");
 				return hp;
+			}
+		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_limiter
+	infra::Processor::Info Audio_limiter::get_processor_info()
+	{
+		return {"audio_limiter", "Audio Limiter", false, [] { return std::unique_ptr<infra::Processor>(new Audio_limiter); },
+				"True-peak look-ahead brickwall limiter: ceiling, drive, release, look-ahead, oversampled detector (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_limiter::get_pin_attributes() const { return io_pins(); }
+
+	namespace
+	{
+		constexpr std::tuple limiter_fields{
+			Number{"ceiling_db", &Limiter_settings::ceiling_db, Limiter_settings::default_ceiling_db, NAE_LIM_MIN_CEILING_DB, NAE_LIM_MAX_CEILING_DB},
+			Number{"gain_db", &Limiter_settings::gain_db, Limiter_settings::default_gain_db, -NAE_LIM_MAX_GAIN_DB, NAE_LIM_MAX_GAIN_DB},
+			Number{"release_ms", &Limiter_settings::release_ms, Limiter_settings::default_release_ms, 1.0, 5000.0},
+			Number{"lookahead_ms", &Limiter_settings::lookahead_ms, Limiter_settings::default_lookahead_ms, 0.0, 20.0},
+			Flag{"true_peak", &Limiter_settings::true_peak, true},
+			Flag{"link_channels", &Limiter_settings::link_channels, true},
+		};
+	}
+
+	Json::Value Audio_limiter::serialize() const { return to_json(*this, limiter_fields); }
+	void Audio_limiter::deserialize(const Json::Value& value) { Limiter_settings::operator=(from_json<Limiter_settings>(value, "Audio_limiter", limiter_fields)); }
+	void Limiter_settings::clamp() { detail::clamp(*this, limiter_fields); }
+
+	void Audio_limiter::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Limiter");
+		run_on_handle<nae_lim>(
+			io.input, io.output, stop_token, {"nae_lim", nae_lim_put, nae_lim_flush, nae_lim_available, nae_lim_receive, nae_lim_destroy}, "node", 0,
+			[&](nae_ctx* ctx, const Frame_data* frame, int ch)
+			{
+				// the settings as the library's parameters at the stream's sample rate; a look-ahead too long for that rate is the user's error
+				nae_lim_params params;
+				const int rc = nae_lim_design(frame->sample_rate, ceiling_db, gain_db, release_ms / 1000.0, lookahead_ms / 1000.0, true_peak ? 1 : 0,
+											  link_channels ? 1 : 0, &params);
+				if (rc == NAE_ERR_UNSUPPORTED)
+					throw infra::Processor::Runtime_error("Look-ahead too long", "The look-ahead must not exceed 1018 samples at the stream's sample rate.",
+										infra::fmt("lookahead %g ms at %d Hz", lookahead_ms, frame->sample_rate));
+				if (rc != NAE_OK)
+					throw infra::Processor::Runtime_error("Invalid limiter parameters", "A parameter of the limiter node lies outside its range.",
+										infra::fmt("nae_lim_design at %d Hz: code %d", frame->sample_rate, rc));
+				nae_lim* lim = nullptr;
+				gpu::check(nae_lim_create(ctx, &params, ch, &lim), "nae_lim_create");
+				return lim;
 			}
 		);
 	}

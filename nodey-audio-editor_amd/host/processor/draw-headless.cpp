@@ -22,6 +22,7 @@
 #include "audio-modulation.hpp"
 #include "audio-saturation.hpp"
 #include "audio-gate.hpp"
+#include "audio-limiter.hpp"
 #include "audio-multiband.hpp"
 #include "audio-denoise.hpp"
 #include "audio-separation.hpp"
@@ -137,6 +138,8 @@ namespace processor
 
 	void Audio_separation::draw_title() {}
 	bool Audio_separation::draw_content(bool) { clamp(); return false; }   // a frame size the library has, else the default
+	void Audio_limiter::draw_title() {}
+	bool Audio_limiter::draw_content(bool) { clamp(); return false; }
 
 	void Audio_loudness::draw_title() {}
 	bool Audio_loudness::draw_content(bool) { clamp(); return false; }

@@ -16,6 +16,7 @@
 #include "processor/audio-gate.hpp"
 #include "processor/audio-multiband.hpp"
 #include "processor/audio-separation.hpp"
+#include "processor/audio-limiter.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -79,4 +80,7 @@ namespace infra
 
 	// the harmonic/percussive separation; a call of its own, so the thirteen lists above stay what they were
 	void register_separation_processors() { register_each<processor::Audio_separation>(); }
+
+	// the true-peak limiter; a call of its own, so the fourteen lists above stay what they were
+	void register_limiter_processors() { register_each<processor::Audio_limiter>(); }
 }

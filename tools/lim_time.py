@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Times nae_lim_block_f32 (K22, the limiter) with the true-peak detector and with the sample-peak detector next to nae_dyn_block_f32 (K12) in
+limiter mode at the same look-ahead and nae_gain_sig_f32, between two nae_event_records: warm, interleaved (every round times every case
+once, in turn), the median over the rounds, with the shader clock read before and after.
+
+    python tools/lim_time.py [--runs 7] [--warmup 2] [--quick] [--limit SECONDS]
+
+Cases, stereo at 48 kHz, linked, on uniform noise of +-1 whose level swells every 0.25 s between -30 and +18 dB around -6 dB, so a limiter
+at -1 dB works and rests (look-ahead 72 samples, release 100 ms):
+  g    nae_gain_sig_f32: 16 bytes per stereo frame
+  d72  nae_dyn_block_f32 in limiter mode (threshold -1 dB, ratio inf, no knee, attack 0, release 100 ms) at look-ahead 72
+  T72  the limiter with true_peak = 1 at look-ahead 72 (ceiling -1 dB, gain 0 dB)
+  S72  the limiter with true_peak = 0 at look-ahead 72
+Beside each case the HBM floor (16 bytes per frame over 6.29 TB/s) is printed; the ratios T72/d72 and S72/d72 are reported, nothing is
+asserted about them.
+Shapes: 1024 stereo streams x 10 s and 8 stereo streams x 10 s (--quick: 64 streams x 2 s and 8 streams x 2 s).  Every shape is a step of its
+own: a fresh child process (this file with --shape) under a time limit of --limit seconds (default 240), and the first step that fails or
+runs out of time ends the run with its exit status; nothing more is started on the device after it.  One JSON line per shape."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPES = {"large": ("1024 streams x 10 s", 1024, 480000), "small": ("8 streams x 10 s", 8, 480000),
+          "quick-large": ("64 streams x 2 s", 64, 96000), "quick-small": ("8 streams x 2 s", 8, 96000)}
+HBM_BYTES_PER_S = 6.29e12
+RATE = 48000
+
+
+def run_shape(shape, runs, warmup):
+    import numpy as np
+    import naeload
+    nae = naeload.load()
+    name, n_streams, T = SHAPES[shape]
+    ch = 2
+    with nae.Context(0) as ctx:
+        d_in, d_out = ctx.empty(n_streams * T * ch), ctx.empty(n_streams * T * ch)
+        ctx.fill_uniform(d_in.ptr, T * ch, T * ch, n_streams, 0, 0)
+        src, dst = nae.Sig.interleaved(d_in.ptr, T, ch), nae.Sig.interleaved(d_out.ptr, T, ch)
+        # the swell: one stream's envelope, applied in place to every stream by the library's own gain, 0.25 s at a time
+        steps = T // (RATE // 4)
+        for k in range(steps):
+            level = 10.0 ** ((-6.0 + 24.0 * np.sin(2 * np.pi * k / 7.0)) / 20.0)
+            part = nae.Sig(d_in.at(k * (RATE // 4) * ch), T * ch, 1, ch)
+            ctx.gain_sig(part, part, RATE // 4, ch, n_streams, float(level))
+        traffic = 2 * n_streams * ch * T * 4
+        cases = [("g", "nae_gain_sig_f32", lambda: ctx.gain_sig(src, dst, T, ch, n_streams, 0.5))]
+        LA = 72
+        p = nae.Context.dyn_design(RATE, threshold_db=-1.0, ratio=float("inf"), knee_db=0.0, attack_s=0.0, release_s=0.1, lookahead_s=LA / RATE)
+        cases.append((f"d{LA}", f"nae_dyn_block_f32 in limiter mode, look-ahead {LA}", lambda p=p: ctx.dyn_block(p, src, T, ch, n_streams, dst)))
+        for tag, tp in (("T", True), ("S", False)):
+            p = nae.Context.lim_design(RATE, ceiling_db=-1.0, gain_db=0.0, release_s=0.1, lookahead_s=LA / RATE, true_peak=tp)
+            cases.append((f"{tag}{LA}", f"limiter, true_peak {int(tp)}, look-ahead {LA}", lambda p=p: ctx.lim_block(p, src, T, ch, n_streams, dst)))
+        a, b = ctx.event(), ctx.event()
+        for _ in range(warmup):
+            for _, _, fn in cases:
+                fn()
+        ctx.sync()
+        clock_before = ctx.clock_ghz()
+        ms = {c[0]: [] for c in cases}
+        for _ in range(runs):
+            for tag, _, fn in cases:
+                ctx.record(a)
+                fn()
+                ctx.record(b)
+                ms[tag].append(ctx.elapsed_ms(a, b))
+        clock_after = ctx.clock_ghz()
+        ctx.destroy_event(a)
+        ctx.destroy_event(b)
+        floor_ms = traffic / HBM_BYTES_PER_S * 1e3
+        rows = []
+        for tag, what, _ in cases:
+            med = statistics.median(ms[tag])
+            rows.append({"shape": name, "case": tag, "what": what, "ms": med, "min_ms": min(ms[tag]), "max_ms": max(ms[tag]), "bytes": traffic,
+                         "gbytes_per_s": traffic / med / 1e6, "hbm_floor_ms": floor_ms})
+            print(f"{name}: ({tag}) {what}: {med:.3f} ms (min {min(ms[tag]):.3f}, max {max(ms[tag]):.3f}); {traffic / med / 1e6:.1f} GB/s; "
+                  f"{med / floor_ms:.2f} x the HBM floor of {floor_ms:.3f} ms", flush=True)
+        t = {r["case"]: r["ms"] for r in rows}
+        print(f"{name}: T72/d72 {t['T72'] / t['d72']:.3f}, S72/d72 {t['S72'] / t['d72']:.3f}; clock {clock_before:.3f} GHz before, {clock_after:.3f} GHz after",
+              flush=True)
+        d_in.free()
+        d_out.free()
+        print(json.dumps({"device": ctx.name(), "runs": runs, "clock_ghz": [clock_before, clock_after], "rows": rows}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--quick", action="store_true", help="a sixteenth of the large shape's streams, and a fifth of the length")
+    ap.add_argument("--limit", type=float, default=240.0, help="seconds each shape's process may take")
+    ap.add_argument("--shape", choices=sorted(SHAPES), help="run this one shape in this process (what the driver starts)")
+    args = ap.parse_args()
+    if args.shape:
+        run_shape(args.shape, args.runs, args.warmup)
+        return 0
+    for key in (("quick-large", "quick-small") if args.quick else ("large", "small")):
+        cmd = [sys.executable, os.path.abspath(__file__), "--shape", key, "--runs", str(args.runs), "--warmup", str(args.warmup)]
+        try:
+            rc = subprocess.run(cmd, timeout=args.limit).returncode
+        except subprocess.TimeoutExpired:
+            print(f"{key}: no result within {args.limit:g} s; stopping", flush=True)
+            return 124
+        if rc:
+            print(f"{key}: exit status {rc}; stopping", flush=True)
+            return rc
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
