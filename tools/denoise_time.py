@@ -7,19 +7,19 @@ process: warm, the median of several runs.
 
 Shapes: 1024 stereo streams x 10 s at 48 kHz with the library's tile, and 8 stereo streams x 60 s with the library's tile and with forced ones
 (debug key dn_tile) (--quick: 64 streams x 2 s and 8 streams x 6 s).  The node's defaults: 12 dB reduction, 6 dB sensitivity, Tn = Fn = 2;
-the profile is learned from the first half second of stream 0.  Every shape is a step of its own: a fresh child process (this file with
---shape) under a time limit of --limit seconds (default 180), and the first step that fails or runs out of time ends the run with its exit
-status; nothing more is started on the device after it.  Per case: the time and the traffic rate at the 8 bytes per sample and channel the
-call must move.  One JSON line per shape (profiles/r19_denoise.md is written from them)."""
-import argparse
+the profile is learned from the first half second of stream 0.  Every shape is a step of nodetime.drive under --limit (default 180 s).  Per
+case: the time and the traffic rate at the 8 bytes per sample and channel the call must move.  One JSON line per shape
+(profiles/r19_denoise.md is written from them).
+Steps: large, small (--quick: quick-large, quick-small)."""
 import json
 import os
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import nodetime  # noqa: E402
 
+steps = nodetime.shape_steps
 SHAPES = {"large": ("1024 streams x 10 s", 1024, 480000, (0,)), "small": ("8 streams x 60 s", 8, 2880000, (0, 8, 16, 32, 128, 512)),
           "quick-large": ("64 streams x 2 s", 64, 96000, (0,)), "quick-small": ("8 streams x 6 s", 8, 288000, (0, 8, 16, 32, 128, 512))}
 
@@ -31,35 +31,19 @@ def run_shape(key, runs, warmup, n_fft):
     name, n_streams, T, tiles = SHAPES[key]
     rows, ch = [], 2
     with nae.Context(0) as ctx:
-        d_in = ctx.empty(n_streams * T * ch)
-        ctx.fill_uniform(d_in.ptr, T * ch, T * ch, n_streams, 0, 0)
-        d_out = ctx.empty(n_streams * T * ch)
+        d_in, d_out, src, dst = nodetime.setup(nae, ctx, n_streams, T)
         d_prof = ctx.empty(ch * (n_fft // 2 + 1))
-        src, dst = nae.Sig.interleaved(d_in.ptr, T, ch), nae.Sig.interleaved(d_out.ptr, T, ch)
         ctx.denoise_profile(n_fft, src, 24000, ch, d_prof.ptr)
         p = nae.Context.denoise_design(12.0, 6.0, n_fft, 2, 2)
         q, phi = nae.formant_lifter(48000, n_fft), 2 ** (4 / 12)
         assert ctx.stretch_plan(1.0, 1.0, T, n_fft, formant=q, formant_ratio=phi).out_len == T
-        calls = {"env": lambda: ctx.stretch_block(1.0, 1.0, src, T, ch, n_streams, dst, n_fft=n_fft, formant=q, formant_ratio=phi)}
+        cases = [("env", "env", lambda: ctx.stretch_block(1.0, 1.0, src, T, ch, n_streams, dst, n_fft=n_fft, formant=q, formant_ratio=phi))]
         for tile in tiles:
             def gate(tile=tile):
                 ctx.debug_set("dn_tile", tile)
                 ctx.denoise_block(p, d_prof.ptr, ch, src, T, ch, n_streams, dst)
-            calls[f"gate, dn_tile {tile}"] = gate
-        a, b = ctx.event(), ctx.event()
-        for _ in range(warmup):
-            for fn in calls.values():
-                fn()
-        ctx.sync()
-        ms = {k: [] for k in calls}
-        for _ in range(runs):
-            for k, fn in calls.items():           # alternating: every round times every call once
-                ctx.record(a)
-                fn()
-                ctx.record(b)
-                ms[k].append(ctx.elapsed_ms(a, b))
-        ctx.destroy_event(a)
-        ctx.destroy_event(b)
+            cases.append((f"gate, dn_tile {tile}", "gate", gate))
+        ms, _, _ = nodetime.rounds(ctx, cases, runs, warmup, clock=False)    # alternating: every round times every call once
         samples = n_streams * ch * T
         for k, v in ms.items():
             med = statistics.median(v)
@@ -68,35 +52,18 @@ def run_shape(key, runs, warmup, n_fft):
             print(f"{name}, n_fft {n_fft}: {k}: {med:.3f} ms (min {min(v):.3f}, max {max(v):.3f}); {samples * 8 / med / 1e6:.1f} GB/s; "
                   f"{med / statistics.median(ms['env']):.2f}x the envelope pass", flush=True)
         ghz = ctx.clock_ghz()
-        d_in.free()
-        d_out.free()
-        d_prof.free()
+        nodetime.release(d_in, d_out, d_prof)
         print(json.dumps({"device": ctx.name(), "runs": runs, "clock_ghz": ghz, "rows": rows}), flush=True)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap = nodetime.parser(180.0, "a sixteenth of the large shape's streams, and a fifth or a tenth of the lengths", choices=sorted(SHAPES))
     ap.add_argument("--n-fft", type=int, default=2048)
-    ap.add_argument("--quick", action="store_true", help="a sixteenth of the large shape's streams, and a fifth or a tenth of the lengths")
-    ap.add_argument("--limit", type=float, default=180.0, help="seconds each shape's process may take")
-    ap.add_argument("--shape", choices=sorted(SHAPES), help="run this one shape in this process (what the driver starts)")
     args = ap.parse_args()
     if args.shape:
         run_shape(args.shape, args.runs, args.warmup, args.n_fft)
         return 0
-    for key in (("quick-large", "quick-small") if args.quick else ("large", "small")):
-        cmd = [sys.executable, os.path.abspath(__file__), "--shape", key, "--runs", str(args.runs), "--warmup", str(args.warmup), "--n-fft", str(args.n_fft)]
-        try:
-            rc = subprocess.run(cmd, timeout=args.limit).returncode
-        except subprocess.TimeoutExpired:
-            print(f"{key}: no result within {args.limit:g} s; stopping", flush=True)
-            return 124
-        if rc:
-            print(f"{key}: exit status {rc}; stopping", flush=True)
-            return rc
-    return 0
+    return nodetime.drive(__file__, steps(args.quick), args.limit, nodetime.counts(args) + ["--n-fft", str(args.n_fft)])
 
 
 if __name__ == "__main__":

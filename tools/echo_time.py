@@ -9,34 +9,30 @@ Cases, stereo at 48 kHz:
   b  the echo at D = 350 ms, the same two sections in the loop: 16 bytes per sample (the signal in and out, the line out and in)
   c  b with ping-pong and delays of 350 and 250 ms
   d  the echo with no section
-Shapes: 1024 stereo streams x 10 s and 8 stereo streams x 10 s (--quick: 64 streams x 2 s and 8 streams x 2 s).  Every shape is a step of its
-own: a fresh child process (this file with --shape) under a time limit of --limit seconds (default 180), and the first step that fails or
-runs out of time ends the run with its exit status; nothing more is started on the device after it.  One JSON line per shape
-(profiles/r22_echo.md is written from them)."""
-import argparse
+Shapes: 1024 stereo streams x 10 s and 8 stereo streams x 10 s (--quick: 64 streams x 2 s and 8 streams x 2 s).  Every shape is a step of
+nodetime.drive under --limit (default 180 s).  One JSON line per shape
+(profiles/r22_echo.md is written from them).
+Steps: large, small (--quick: quick-large, quick-small)."""
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import nodetime  # noqa: E402
 
-SHAPES = {"large": ("1024 streams x 10 s", 1024, 480000), "small": ("8 streams x 10 s", 8, 480000),
-          "quick-large": ("64 streams x 2 s", 64, 96000), "quick-small": ("8 streams x 2 s", 8, 96000)}
+steps = nodetime.shape_steps
 
 
 def run_shape(shape, runs, warmup):
     import numpy as np
     import naeload
     nae = naeload.load()
-    name, n_streams, T = SHAPES[shape]
+    name, n_streams, T = nodetime.SHAPES[shape]
     ch = 2
     with nae.Context(0) as ctx:
-        d_in, d_out = ctx.empty(n_streams * T * ch), ctx.empty(n_streams * T * ch)
-        ctx.fill_uniform(d_in.ptr, T * ch, T * ch, n_streams, 0, 0)
-        src, dst = nae.Sig.interleaved(d_in.ptr, T, ch), nae.Sig.interleaved(d_out.ptr, T, ch)
+        d_in, d_out, src, dst = nodetime.setup(nae, ctx, n_streams, T)
         plain = nae.Context.echo_design(48000, 0.35, None, 0.4, 4000.0, 100.0, 0.35, 1.0, False)
         pong = nae.Context.echo_design(48000, 0.35, 0.25, 0.4, 4000.0, 100.0, 0.35, 1.0, True)
         bare = nae.Context.echo_design(48000, 0.35, None, 0.4, 0.0, 0.0, 0.35, 1.0, False)
@@ -46,22 +42,7 @@ def run_shape(shape, runs, warmup):
                  ("b", "echo, 350 ms, 2 sections", lambda: ctx.echo_block(plain, src, T, ch, n_streams, dst), 4 * signal),
                  ("c", "echo, ping-pong 350 / 250 ms, 2 sections", lambda: ctx.echo_block(pong, src, T, ch, n_streams, dst), 4 * signal),
                  ("d", "echo, 350 ms, no section", lambda: ctx.echo_block(bare, src, T, ch, n_streams, dst), 4 * signal))
-        a, b = ctx.event(), ctx.event()
-        for _ in range(warmup):
-            for _, _, fn, _ in cases:
-                fn()
-        ctx.sync()
-        clock_before = ctx.clock_ghz()
-        ms = {c[0]: [] for c in cases}
-        for _ in range(runs):
-            for tag, _, fn, _ in cases:
-                ctx.record(a)
-                fn()
-                ctx.record(b)
-                ms[tag].append(ctx.elapsed_ms(a, b))
-        clock_after = ctx.clock_ghz()
-        ctx.destroy_event(a)
-        ctx.destroy_event(b)
+        ms, clock_before, clock_after = nodetime.rounds(ctx, cases, runs, warmup)
         rows = []
         for tag, what, _, traffic in cases:
             med = statistics.median(ms[tag])
@@ -71,33 +52,16 @@ def run_shape(shape, runs, warmup):
         t = {r["case"]: r["ms"] for r in rows}
         print(f"{name}: b/a {t['b'] / t['a']:.3f} (traffic 2), c/a {t['c'] / t['a']:.3f}, d/a {t['d'] / t['a']:.3f}; "
               f"clock {clock_before:.3f} GHz before, {clock_after:.3f} GHz after", flush=True)
-        d_in.free()
-        d_out.free()
+        nodetime.release(d_in, d_out)
         print(json.dumps({"device": ctx.name(), "runs": runs, "clock_ghz": [clock_before, clock_after], "rows": rows}), flush=True)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--quick", action="store_true", help="a sixteenth of the large shape's streams, and a fifth of the length")
-    ap.add_argument("--limit", type=float, default=180.0, help="seconds each shape's process may take")
-    ap.add_argument("--shape", choices=sorted(SHAPES), help="run this one shape in this process (what the driver starts)")
-    args = ap.parse_args()
+    args = nodetime.parser(180.0, choices=sorted(nodetime.SHAPES)).parse_args()
     if args.shape:
         run_shape(args.shape, args.runs, args.warmup)
         return 0
-    for key in (("quick-large", "quick-small") if args.quick else ("large", "small")):
-        cmd = [sys.executable, os.path.abspath(__file__), "--shape", key, "--runs", str(args.runs), "--warmup", str(args.warmup)]
-        try:
-            rc = subprocess.run(cmd, timeout=args.limit).returncode
-        except subprocess.TimeoutExpired:
-            print(f"{key}: no result within {args.limit:g} s; stopping", flush=True)
-            return 124
-        if rc:
-            print(f"{key}: exit status {rc}; stopping", flush=True)
-            return rc
-    return 0
+    return nodetime.drive(__file__, steps(args.quick), args.limit, nodetime.counts(args))
 
 
 if __name__ == "__main__":

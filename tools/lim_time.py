@@ -13,21 +13,19 @@ at -1 dB works and rests (look-ahead 72 samples, release 100 ms):
   S72  the limiter with true_peak = 0 at look-ahead 72
 Beside each case the HBM floor (16 bytes per frame over 6.29 TB/s) is printed; the ratios T72/d72 and S72/d72 are reported, nothing is
 asserted about them.
-Shapes: 1024 stereo streams x 10 s and 8 stereo streams x 10 s (--quick: 64 streams x 2 s and 8 streams x 2 s).  Every shape is a step of its
-own: a fresh child process (this file with --shape) under a time limit of --limit seconds (default 240), and the first step that fails or
-runs out of time ends the run with its exit status; nothing more is started on the device after it.  One JSON line per shape."""
-import argparse
+Shapes: 1024 stereo streams x 10 s and 8 stereo streams x 10 s (--quick: 64 streams x 2 s and 8 streams x 2 s), each a step of
+nodetime.drive under --limit (default 240 s).  One JSON line per shape.
+Steps: large, small (--quick: quick-large, quick-small)."""
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import nodetime  # noqa: E402
 
-SHAPES = {"large": ("1024 streams x 10 s", 1024, 480000), "small": ("8 streams x 10 s", 8, 480000),
-          "quick-large": ("64 streams x 2 s", 64, 96000), "quick-small": ("8 streams x 2 s", 8, 96000)}
+steps = nodetime.shape_steps
 HBM_BYTES_PER_S = 6.29e12
 RATE = 48000
 
@@ -36,15 +34,12 @@ def run_shape(shape, runs, warmup):
     import numpy as np
     import naeload
     nae = naeload.load()
-    name, n_streams, T = SHAPES[shape]
+    name, n_streams, T = nodetime.SHAPES[shape]
     ch = 2
     with nae.Context(0) as ctx:
-        d_in, d_out = ctx.empty(n_streams * T * ch), ctx.empty(n_streams * T * ch)
-        ctx.fill_uniform(d_in.ptr, T * ch, T * ch, n_streams, 0, 0)
-        src, dst = nae.Sig.interleaved(d_in.ptr, T, ch), nae.Sig.interleaved(d_out.ptr, T, ch)
+        d_in, d_out, src, dst = nodetime.setup(nae, ctx, n_streams, T)
         # the swell: one stream's envelope, applied in place to every stream by the library's own gain, 0.25 s at a time
-        steps = T // (RATE // 4)
-        for k in range(steps):
+        for k in range(T // (RATE // 4)):
             level = 10.0 ** ((-6.0 + 24.0 * np.sin(2 * np.pi * k / 7.0)) / 20.0)
             part = nae.Sig(d_in.at(k * (RATE // 4) * ch), T * ch, 1, ch)
             ctx.gain_sig(part, part, RATE // 4, ch, n_streams, float(level))
@@ -56,22 +51,7 @@ def run_shape(shape, runs, warmup):
         for tag, tp in (("T", True), ("S", False)):
             p = nae.Context.lim_design(RATE, ceiling_db=-1.0, gain_db=0.0, release_s=0.1, lookahead_s=LA / RATE, true_peak=tp)
             cases.append((f"{tag}{LA}", f"limiter, true_peak {int(tp)}, look-ahead {LA}", lambda p=p: ctx.lim_block(p, src, T, ch, n_streams, dst)))
-        a, b = ctx.event(), ctx.event()
-        for _ in range(warmup):
-            for _, _, fn in cases:
-                fn()
-        ctx.sync()
-        clock_before = ctx.clock_ghz()
-        ms = {c[0]: [] for c in cases}
-        for _ in range(runs):
-            for tag, _, fn in cases:
-                ctx.record(a)
-                fn()
-                ctx.record(b)
-                ms[tag].append(ctx.elapsed_ms(a, b))
-        clock_after = ctx.clock_ghz()
-        ctx.destroy_event(a)
-        ctx.destroy_event(b)
+        ms, clock_before, clock_after = nodetime.rounds(ctx, cases, runs, warmup)
         floor_ms = traffic / HBM_BYTES_PER_S * 1e3
         rows = []
         for tag, what, _ in cases:
@@ -83,33 +63,16 @@ def run_shape(shape, runs, warmup):
         t = {r["case"]: r["ms"] for r in rows}
         print(f"{name}: T72/d72 {t['T72'] / t['d72']:.3f}, S72/d72 {t['S72'] / t['d72']:.3f}; clock {clock_before:.3f} GHz before, {clock_after:.3f} GHz after",
               flush=True)
-        d_in.free()
-        d_out.free()
+        nodetime.release(d_in, d_out)
         print(json.dumps({"device": ctx.name(), "runs": runs, "clock_ghz": [clock_before, clock_after], "rows": rows}), flush=True)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--quick", action="store_true", help="a sixteenth of the large shape's streams, and a fifth of the length")
-    ap.add_argument("--limit", type=float, default=240.0, help="seconds each shape's process may take")
-    ap.add_argument("--shape", choices=sorted(SHAPES), help="run this one shape in this process (what the driver starts)")
-    args = ap.parse_args()
+    args = nodetime.parser(240.0, choices=sorted(nodetime.SHAPES)).parse_args()
     if args.shape:
         run_shape(args.shape, args.runs, args.warmup)
         return 0
-    for key in (("quick-large", "quick-small") if args.quick else ("large", "small")):
-        cmd = [sys.executable, os.path.abspath(__file__), "--shape", key, "--runs", str(args.runs), "--warmup", str(args.warmup)]
-        try:
-            rc = subprocess.run(cmd, timeout=args.limit).returncode
-        except subprocess.TimeoutExpired:
-            print(f"{key}: no result within {args.limit:g} s; stopping", flush=True)
-            return 124
-        if rc:
-            print(f"{key}: exit status {rc}; stopping", flush=True)
-            return rc
-    return 0
+    return nodetime.drive(__file__, steps(args.quick), args.limit, nodetime.counts(args))
 
 
 if __name__ == "__main__":

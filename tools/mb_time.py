@@ -13,24 +13,27 @@ Cases, stereo at 48 kHz, linked, on uniform noise of +-1 whose level swells ever
   M2 M3 M4     nae_mb_block_f32 at look-ahead 0;  M2L M3L M4L at look-ahead 1024
   C2 C3 C4     the composition at look-ahead 0;   C2L C3L C4L at look-ahead 1024 (its sum is not computed: it is charged nothing for it)
 Beside each case the HBM floor (16 bytes per frame over 6.29 TB/s) is printed.
-Shapes: 1024 stereo streams x 10 s (--quick: 64 streams x 2 s).  Every shape is a step of its own: a fresh child process (this file with
---shape) under a time limit of --limit seconds (default 400), and the first step that fails or runs out of time ends the run with its exit
-status; nothing more is started on the device after it.  One JSON line per shape."""
-import argparse
+Shapes: 1024 stereo streams x 10 s (--quick: 64 streams x 2 s).  Every shape is a step of nodetime.drive under --limit (default 400 s).  One
+JSON line per shape.
+Steps: large (--quick: quick-large)."""
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import nodetime  # noqa: E402
 
 SHAPES = {"large": ("1024 streams x 10 s", 1024, 480000), "quick-large": ("64 streams x 2 s", 64, 96000)}
 HBM_BYTES_PER_S = 6.29e12
 RATE = 48000
 CROSSOVERS = {2: (200.0,), 3: (120.0, 2500.0), 4: (120.0, 1000.0, 6000.0)}
 PATHS = {2: ((0, 1), (2, 3)), 3: ((0, 1, 2), (3, 4, 5, 6), (3, 4, 7, 8)), 4: ((0, 1, 2, 3, 4), (0, 1, 2, 5, 6), (7, 8, 9, 10, 11), (7, 8, 9, 12, 13))}
+
+
+def steps(quick):
+    return nodetime.shape_steps(quick, ("large",))
 
 
 def run_shape(shape, runs, warmup):
@@ -40,9 +43,7 @@ def run_shape(shape, runs, warmup):
     name, n_streams, T = SHAPES[shape]
     ch = 2
     with nae.Context(0) as ctx:
-        d_in, d_out = ctx.empty(n_streams * T * ch), ctx.empty(n_streams * T * ch)
-        ctx.fill_uniform(d_in.ptr, T * ch, T * ch, n_streams, 0, 0)
-        src, dst = nae.Sig.interleaved(d_in.ptr, T, ch), nae.Sig.interleaved(d_out.ptr, T, ch)
+        d_in, d_out, src, dst = nodetime.setup(nae, ctx, n_streams, T)
         # the swell: one stream's envelope, applied in place to every stream by the library's own gain, 0.25 s at a time
         for k in range(T // (RATE // 4)):
             level = 10.0 ** ((-30.0 + 24.0 * np.sin(2 * np.pi * k / 7.0)) / 20.0)
@@ -65,22 +66,7 @@ def run_shape(shape, runs, warmup):
                 cases.append((f"M{n_bands}{tail}", f"nae_mb_block_f32, {n_bands} bands, look-ahead {la}", lambda p=p: ctx.mb_block(p, src, T, ch, n_streams, dst)))
                 cases.append((f"C{n_bands}{tail}", f"{n_bands} x eq + {n_bands} x dyn, look-ahead {la}",
                               lambda p=p, n_bands=n_bands, band=band: composition(p, n_bands, band)))
-        a, b = ctx.event(), ctx.event()
-        for _ in range(warmup):
-            for _, _, fn in cases:
-                fn()
-        ctx.sync()
-        clock_before = ctx.clock_ghz()
-        ms = {c[0]: [] for c in cases}
-        for _ in range(runs):
-            for tag, _, fn in cases:
-                ctx.record(a)
-                fn()
-                ctx.record(b)
-                ms[tag].append(ctx.elapsed_ms(a, b))
-        clock_after = ctx.clock_ghz()
-        ctx.destroy_event(a)
-        ctx.destroy_event(b)
+        ms, clock_before, clock_after = nodetime.rounds(ctx, cases, runs, warmup)
         # every kernel's total per call, under the profile (an event pair around every launch)
         kernels = {c[0]: {} for c in cases}
         ctx.prof_enable(True)
@@ -106,33 +92,16 @@ def run_shape(shape, runs, warmup):
         t = {r["case"]: r["ms"] for r in rows}
         print(f"{name}: " + ", ".join(f"M{k}/C{k} {t[f'M{k}'] / t[f'C{k}']:.3f}" for k in ("2", "3", "4", "2L", "3L", "4L")) +
               f"; clock {clock_before:.3f} GHz before, {clock_after:.3f} GHz after the timed rounds, {clock_last:.3f} GHz after the profiled ones", flush=True)
-        d_in.free()
-        d_out.free()
+        nodetime.release(d_in, d_out)
         print(json.dumps({"device": ctx.name(), "runs": runs, "clock_ghz": [clock_before, clock_after, clock_last], "rows": rows}), flush=True)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--quick", action="store_true", help="a sixteenth of the large shape's streams, and a fifth of the length")
-    ap.add_argument("--limit", type=float, default=400.0, help="seconds each shape's process may take")
-    ap.add_argument("--shape", choices=sorted(SHAPES), help="run this one shape in this process (what the driver starts)")
-    args = ap.parse_args()
+    args = nodetime.parser(400.0, runs=5, choices=sorted(SHAPES)).parse_args()
     if args.shape:
         run_shape(args.shape, args.runs, args.warmup)
         return 0
-    for key in (("quick-large",) if args.quick else ("large",)):
-        cmd = [sys.executable, os.path.abspath(__file__), "--shape", key, "--runs", str(args.runs), "--warmup", str(args.warmup)]
-        try:
-            rc = subprocess.run(cmd, timeout=args.limit).returncode
-        except subprocess.TimeoutExpired:
-            print(f"{key}: no result within {args.limit:g} s; stopping", flush=True)
-            return 124
-        if rc:
-            print(f"{key}: exit status {rc}; stopping", flush=True)
-            return rc
-    return 0
+    return nodetime.drive(__file__, steps(args.quick), args.limit, nodetime.counts(args))
 
 
 if __name__ == "__main__":

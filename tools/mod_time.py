@@ -10,34 +10,30 @@ Cases, stereo at 48 kHz:
   c  the default chorus: 12 ms +- 3 ms at 0.8 Hz, three voices, no feedback (runs of 64 samples): 8 bytes per sample, 16 per stereo frame
   d  a flanger at runs of 64: delay 144, depth 48 samples, 0.25 Hz, feedback 0.7, one voice
   e  the same flanger at runs of 16: delay 24, depth 7 samples
-Shapes: 1024 stereo streams x 10 s and 8 stereo streams x 10 s (--quick: 64 streams x 2 s and 8 streams x 2 s).  Every shape is a step of its
-own: a fresh child process (this file with --shape) under a time limit of --limit seconds (default 180), and the first step that fails or
-runs out of time ends the run with its exit status; nothing more is started on the device after it.  One JSON line per shape
-(profiles/r23_mod.md is written from them)."""
-import argparse
+Shapes: 1024 stereo streams x 10 s and 8 stereo streams x 10 s (--quick: 64 streams x 2 s and 8 streams x 2 s).  Every shape is a step of
+nodetime.drive under --limit (default 180 s).  One JSON line per shape
+(profiles/r23_mod.md is written from them).
+Steps: large, small (--quick: quick-large, quick-small)."""
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import nodetime  # noqa: E402
 
-SHAPES = {"large": ("1024 streams x 10 s", 1024, 480000), "small": ("8 streams x 10 s", 8, 480000),
-          "quick-large": ("64 streams x 2 s", 64, 96000), "quick-small": ("8 streams x 2 s", 8, 96000)}
+steps = nodetime.shape_steps
 
 
 def run_shape(shape, runs, warmup):
     import numpy as np
     import naeload
     nae = naeload.load()
-    name, n_streams, T = SHAPES[shape]
+    name, n_streams, T = nodetime.SHAPES[shape]
     ch = 2
     with nae.Context(0) as ctx:
-        d_in, d_out = ctx.empty(n_streams * T * ch), ctx.empty(n_streams * T * ch)
-        ctx.fill_uniform(d_in.ptr, T * ch, T * ch, n_streams, 0, 0)
-        src, dst = nae.Sig.interleaved(d_in.ptr, T, ch), nae.Sig.interleaved(d_out.ptr, T, ch)
+        d_in, d_out, src, dst = nodetime.setup(nae, ctx, n_streams, T)
         echo = nae.Context.echo_design(48000, 0.35, None, 0.4, 4000.0, 100.0, 0.35, 1.0, False)
         coef = np.array([[echo.coef[s][i] for i in range(5)] for s in range(2)])
         chorus = nae.Context.mod_design(48000)
@@ -50,22 +46,7 @@ def run_shape(shape, runs, warmup):
                  ("c", "chorus, 3 voices, no feedback, runs of 64", lambda: ctx.mod_block(chorus, src, T, ch, n_streams, dst), 2 * signal),
                  ("d", "flanger (144, 48), feedback 0.7, runs of 64", lambda: ctx.mod_block(wide, src, T, ch, n_streams, dst), 2 * signal),
                  ("e", "flanger (24, 7), feedback 0.7, runs of 16", lambda: ctx.mod_block(narrow, src, T, ch, n_streams, dst), 2 * signal))
-        a, b = ctx.event(), ctx.event()
-        for _ in range(warmup):
-            for _, _, fn, _ in cases:
-                fn()
-        ctx.sync()
-        clock_before = ctx.clock_ghz()
-        ms = {c[0]: [] for c in cases}
-        for _ in range(runs):
-            for tag, _, fn, _ in cases:
-                ctx.record(a)
-                fn()
-                ctx.record(b)
-                ms[tag].append(ctx.elapsed_ms(a, b))
-        clock_after = ctx.clock_ghz()
-        ctx.destroy_event(a)
-        ctx.destroy_event(b)
+        ms, clock_before, clock_after = nodetime.rounds(ctx, cases, runs, warmup)
         rows = []
         for tag, what, _, traffic in cases:
             med = statistics.median(ms[tag])
@@ -75,33 +56,16 @@ def run_shape(shape, runs, warmup):
         t = {r["case"]: r["ms"] for r in rows}
         print(f"{name}: c/a {t['c'] / t['a']:.3f}, d/a {t['d'] / t['a']:.3f}, e/a {t['e'] / t['a']:.3f}, e/d {t['e'] / t['d']:.3f}, c/b {t['c'] / t['b']:.3f}; "
               f"clock {clock_before:.3f} GHz before, {clock_after:.3f} GHz after", flush=True)
-        d_in.free()
-        d_out.free()
+        nodetime.release(d_in, d_out)
         print(json.dumps({"device": ctx.name(), "runs": runs, "clock_ghz": [clock_before, clock_after], "rows": rows}), flush=True)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--quick", action="store_true", help="a sixteenth of the large shape's streams, and a fifth of the length")
-    ap.add_argument("--limit", type=float, default=180.0, help="seconds each shape's process may take")
-    ap.add_argument("--shape", choices=sorted(SHAPES), help="run this one shape in this process (what the driver starts)")
-    args = ap.parse_args()
+    args = nodetime.parser(180.0, choices=sorted(nodetime.SHAPES)).parse_args()
     if args.shape:
         run_shape(args.shape, args.runs, args.warmup)
         return 0
-    for key in (("quick-large", "quick-small") if args.quick else ("large", "small")):
-        cmd = [sys.executable, os.path.abspath(__file__), "--shape", key, "--runs", str(args.runs), "--warmup", str(args.warmup)]
-        try:
-            rc = subprocess.run(cmd, timeout=args.limit).returncode
-        except subprocess.TimeoutExpired:
-            print(f"{key}: no result within {args.limit:g} s; stopping", flush=True)
-            return 124
-        if rc:
-            print(f"{key}: exit status {rc}; stopping", flush=True)
-            return rc
-    return 0
+    return nodetime.drive(__file__, steps(args.quick), args.limit, nodetime.counts(args))
 
 
 if __name__ == "__main__":

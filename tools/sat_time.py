@@ -11,21 +11,19 @@ Cases, stereo at 48 kHz, drive 12 dB on uniform noise of +-1, bias 0, wet 1, dry
   s1 ... s8 / h1 ... h8   the soft and the hard curve at oversample 1, 2, 4 and 8
 Beside each case the HBM floor (16 bytes per frame over 6.29 TB/s) is printed; the VALU floor is worked out in profiles/r26_sat.md from the
 v_* instructions of the two loop bodies in the gfx950 ISA (hipcc -S), at 2.15 cycles per wave-instruction and the clock printed here.  --tile forces sat_tile (chunks per wave).
-Shapes: 1024 stereo streams x 10 s and 8 stereo streams x 10 s (--quick: 64 streams x 2 s and 8 streams x 2 s).  Every shape is a step of its
-own: a fresh child process (this file with --shape) under a time limit of --limit seconds (default 240), and the first step that fails or
-runs out of time ends the run with its exit status; nothing more is started on the device after it.  One JSON line per shape."""
-import argparse
+Shapes: 1024 stereo streams x 10 s and 8 stereo streams x 10 s (--quick: 64 streams x 2 s and 8 streams x 2 s).  Every shape is a step of
+nodetime.drive under --limit (default 240 s).  One JSON line per shape.
+Steps: large, small (--quick: quick-large, quick-small)."""
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import nodetime  # noqa: E402
 
-SHAPES = {"large": ("1024 streams x 10 s", 1024, 480000), "small": ("8 streams x 10 s", 8, 480000),
-          "quick-large": ("64 streams x 2 s", 64, 96000), "quick-small": ("8 streams x 2 s", 8, 96000)}
+steps = nodetime.shape_steps
 HBM_BYTES_PER_S = 6.29e12
 
 
@@ -33,14 +31,12 @@ def run_shape(shape, runs, warmup, tile):
     import numpy as np
     import naeload
     nae = naeload.load()
-    name, n_streams, T = SHAPES[shape]
+    name, n_streams, T = nodetime.SHAPES[shape]
     ch = 2
     with nae.Context(0) as ctx:
         if tile:
             ctx.debug_set("sat_tile", tile)
-        d_in, d_out = ctx.empty(n_streams * T * ch), ctx.empty(n_streams * T * ch)
-        ctx.fill_uniform(d_in.ptr, T * ch, T * ch, n_streams, 0, 0)
-        src, dst = nae.Sig.interleaved(d_in.ptr, T, ch), nae.Sig.interleaved(d_out.ptr, T, ch)
+        d_in, d_out, src, dst = nodetime.setup(nae, ctx, n_streams, T)
         coef = np.stack([nae.Context.eq_design("lowpass", 48000, 4000.0), nae.Context.eq_design("highpass", 48000, 100.0)])
         traffic = 2 * n_streams * ch * T * 4
         cases = [("g", "nae_gain_sig_f32", lambda: ctx.gain_sig(src, dst, T, ch, n_streams, 0.5)),
@@ -49,22 +45,7 @@ def run_shape(shape, runs, warmup, tile):
             for m in (1, 2, 4, 8):
                 p = nae.Context.sat_design(12.0, 0.0, curve, m)
                 cases.append((f"{curve[0]}{m}", f"saturation, {curve}, oversample {m}", lambda p=p: ctx.sat_block(p, src, T, ch, n_streams, dst)))
-        a, b = ctx.event(), ctx.event()
-        for _ in range(warmup):
-            for _, _, fn in cases:
-                fn()
-        ctx.sync()
-        clock_before = ctx.clock_ghz()
-        ms = {c[0]: [] for c in cases}
-        for _ in range(runs):
-            for tag, _, fn in cases:
-                ctx.record(a)
-                fn()
-                ctx.record(b)
-                ms[tag].append(ctx.elapsed_ms(a, b))
-        clock_after = ctx.clock_ghz()
-        ctx.destroy_event(a)
-        ctx.destroy_event(b)
+        ms, clock_before, clock_after = nodetime.rounds(ctx, cases, runs, warmup)
         floor_ms = traffic / HBM_BYTES_PER_S * 1e3
         rows = []
         for tag, what, _ in cases:
@@ -76,34 +57,18 @@ def run_shape(shape, runs, warmup, tile):
         t = {r["case"]: r["ms"] for r in rows}
         print(f"{name}: s1/g {t['s1'] / t['g']:.3f}, h1/g {t['h1'] / t['g']:.3f}, s4/q {t['s4'] / t['q']:.3f}; sat_tile {tile}; "
               f"clock {clock_before:.3f} GHz before, {clock_after:.3f} GHz after", flush=True)
-        d_in.free()
-        d_out.free()
+        nodetime.release(d_in, d_out)
         print(json.dumps({"device": ctx.name(), "runs": runs, "sat_tile": tile, "clock_ghz": [clock_before, clock_after], "rows": rows}), flush=True)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--quick", action="store_true", help="a sixteenth of the large shape's streams, and a fifth of the length")
-    ap.add_argument("--limit", type=float, default=240.0, help="seconds each shape's process may take")
+    ap = nodetime.parser(240.0, choices=sorted(nodetime.SHAPES))
     ap.add_argument("--tile", type=int, default=0, help="sat_tile: chunks per wave (0: the library's pick)")
-    ap.add_argument("--shape", choices=sorted(SHAPES), help="run this one shape in this process (what the driver starts)")
     args = ap.parse_args()
     if args.shape:
         run_shape(args.shape, args.runs, args.warmup, args.tile)
         return 0
-    for key in (("quick-large", "quick-small") if args.quick else ("large", "small")):
-        cmd = [sys.executable, os.path.abspath(__file__), "--shape", key, "--runs", str(args.runs), "--warmup", str(args.warmup), "--tile", str(args.tile)]
-        try:
-            rc = subprocess.run(cmd, timeout=args.limit).returncode
-        except subprocess.TimeoutExpired:
-            print(f"{key}: no result within {args.limit:g} s; stopping", flush=True)
-            return 124
-        if rc:
-            print(f"{key}: exit status {rc}; stopping", flush=True)
-            return rc
-    return 0
+    return nodetime.drive(__file__, steps(args.quick), args.limit, nodetime.counts(args) + ["--tile", str(args.tile)])
 
 
 if __name__ == "__main__":
