@@ -1002,8 +1002,14 @@ int nae_denoise_destroy(nae_denoise* h);
  * The bin's gain is G = gain_p + d m (one product, one add) with d = (float)((double)gain_h - (double)gain_p).  Synthesis is the vocoder's:
  * c2r, window, overlap-add in increasing frame order, NAE_OLA_GAIN.  The output has the input's length and is aligned with it sample for
  * sample; with gain_h = gain_p the call is the STFT identity times that gain.  Bit-exact against the CPU statement
- * (tests/hpss_ref/ref_hpss.c) under every tiling (debug key hpss_tile) and any cut of the input into puts.  Inputs whose power overflows f32
- * are unspecified.
+ * (tests/hpss_ref/ref_hpss.c) under every tiling (debug key hpss_tile) and any cut of the input into puts.  Finite inputs whose power
+ * overflows f32 are unspecified.  A non-finite sample i changes only the samples from (floor(i / H) - time_span - 3) H up to, not
+ * including, (floor(i / H) + time_span + 4) H of its own stream-channel, and the output is non-finite only from (floor(i / H) - 3) H up
+ * to, not including, (floor(i / H) + 4) H: the blocks fed by the four frames that hold the sample.  Outside those blocks the output is
+ * finite and has the statement's bits; the call returns NAE_OK.  (The sample makes every key of its four frames non-finite; such a key
+ * ranks above every finite one whatever its sign and payload, and a frame without the sample sees at most min(4, time_span) of them among
+ * its 2 time_span + 1, never a majority: its medians stay finite.  The overflow sentence is about finite samples alone: their spectrum stays
+ * finite while a power is +Inf, and the mask there is not specified; a non-finite sample's frames are non-finite under any mask.)
  * Errors: a null pointer, ch not 1 or 2, a span outside 0 ... NAE_HPSS_MAX_SPAN, hard not 0 or 1, a gain that is negative, above
  * (float)10^(NAE_HPSS_MAX_DB / 20) or not finite: NAE_ERR_INVALID; n_fft other than 512, 1024, 2048, 4096: NAE_ERR_UNSUPPORTED; in_len = 0 or
  * n_streams = 0: NAE_OK after the checks, nothing is launched.  Views as K9's. */

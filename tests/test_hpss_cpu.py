@@ -1,12 +1,14 @@
 """K21 separation, no GPU: the CPU statement (tests/hpss_ref/ref_hpss.c) — what the GPU computes bit for bit — as the STFT identity, its medians
 against a brute-force sort, its keys and its output against the float64 numpy restatement (tests/hpss_ref.py), on a chord under a click train,
 as a sum of its two parts and in its degenerate cases; the design's formulas, ranges and error codes; the header's entries; the separation
-node's JSON and the fourteen registration calls (tests/hpss_ref/host_hpss_node.cpp).  The measured figures stand with their tests and in
-DESIGN.md §3, "K21 separation"."""
+node's JSON and the fourteen registration calls (tests/hpss_ref/host_hpss_node.cpp); which edges the seeded run of tests/tools/fuzz_hpss.py
+reaches; the header's contract for a non-finite sample, on the statement; and that the quiet signal of the GPU's subnormal test puts the keys
+on the subnormal grid.  The measured figures stand with their tests and in DESIGN.md §3, "K21 separation"."""
 import ctypes as C
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -263,3 +265,140 @@ def test_registration(host):
     lines = [l.split()[1:] for l in r.stdout.splitlines() if l.startswith("REGISTRY ")]
     assert [len(l) for l in lines] == [19, 20]
     assert "audio_separation" not in lines[0] and sorted(lines[1]) == sorted(lines[0] + ["audio_separation"])
+
+
+# ---------------------------------------------------------------------------------------------------- the seeded fuzz run, pinned
+@pytest.fixture(scope="module")
+def fuzz():
+    """tests/tools/fuzz_hpss.py and the case records tests/test_gpu_hpss.py::test_fuzz_hpss_seeded runs"""
+    sys.path.insert(0, os.path.join(hpss_ref.ROOT, "tests", "tools"))
+    import fuzz_hpss
+    cases, seed = fuzz_hpss.SEEDED
+    assert 20 <= cases <= 32
+    return fuzz_hpss, list(fuzz_hpss.draw(cases, seed))
+
+
+def test_the_fuzz_draw_is_the_seeds_alone(fuzz):
+    fuzz_hpss, run = fuzz
+    again = list(fuzz_hpss.draw(len(run), fuzz_hpss.SEEDED[1]))
+    assert again == run
+    assert all(np.array_equal(bits(fuzz_hpss.signal(a)), bits(fuzz_hpss.signal(b))) for a, b in zip(run[:3], again[:3]))
+    assert list(fuzz_hpss.draw(len(run), fuzz_hpss.SEEDED[1] + 1)) != run
+
+
+def test_the_seeded_fuzz_run_reaches_every_edge(fuzz):
+    """what the GPU test's cases contain; a seed that loses one of these is changed, not the assertion"""
+    _, run = fuzz
+    blocks = lambda c: -(-c["n"] // (c["n_fft"] // 4))
+    assert {c["n_fft"] for c in run} == set(hpss_ref.SIZES), "all four sizes"
+    assert {c["time_span"] for c in run} >= {0, 1, 8} and {c["freq_span"] for c in run} >= {0, 1, 8}, "the spans at their edges"
+    assert {c["mask"] for c in run} == set(hpss_ref.MASKS), "both masks"
+    assert any(-120.0 in (c["harmonic_db"], c["percussive_db"]) for c in run), "a gain of 0"
+    assert {c["tile"] for c in run} >= {0, 1, 2, 3, 7}, "the library's tile and every forced one"
+    assert any(c["shared"] for c in run), "a shared source"
+    assert any(c["handle"] for c in run) and any(not c["handle"] for c in run), "the handle and the block entry"
+    assert any(c["n"] == 1 for c in run) and any(c["n"] > 1 and c["n"] % (c["n_fft"] // 4) == 0 for c in run), "one sample, and whole hop blocks"
+    assert any(c["time_span"] == 8 and blocks(c) >= 17 for c in run), "Tn = 8 over at least 17 blocks"
+    assert any(c["time_span"] == 8 and blocks(c) >= 17 and c["tile"] == 0 and not c["handle"] for c in run), \
+        "... in one launch of one tile: the ring's head comes back to slot 0"
+
+
+def test_the_seeded_fuzz_run_is_finite_and_both_medians_win(nae, ref, fuzz):
+    """the statement on every case's own parameters and signal: finite output, and over the run Hq >= Pq at some bins and not at others"""
+    fuzz_hpss, run = fuzz
+    harmonic = total = 0
+    for c in run:
+        p, x = fuzz_hpss.params(nae, c), fuzz_hpss.signal(c)
+        for s in x[:1] if c["shared"] else x:
+            y, _, hq, pq, _ = hpss_ref.run(ref, p, s, detail=True)
+            assert np.all(np.isfinite(y)), c
+            harmonic += int((hq >= pq).sum())
+            total += hq.size
+    print(f"seeded fuzz run: Hq >= Pq at {harmonic} of {total} bins")
+    assert 0 < harmonic < total
+
+
+# ---------------------------------------------------------------------------------------------------- a non-finite sample
+BAD = (np.nan, np.inf, -np.inf)
+
+
+def reach(n_fft, tn, i):
+    """a non-finite sample i -> ((lo, hi) of the samples it may change, (lo, hi) of those that may be non-finite): b = floor(i / H), the sample
+    lies in frames b ... b + 3, their keys enter the time medians of frames b - Tn ... b + 3 + Tn, and frame f feeds blocks f - 3 ... f"""
+    H = n_fft // 4
+    b = i // H
+    return ((b - tn - 3) * H, (b + tn + 4) * H), ((b - 3) * H, (b + 4) * H)
+
+
+@pytest.mark.parametrize("mask", ("soft", "hard"))
+@pytest.mark.parametrize("tn", (0, 1, 8))
+@pytest.mark.parametrize("n_fft", (512, 4096))
+def test_non_finite_sample_stays_local(ref, n_fft, tn, mask):
+    """the statement obeys the contract of include/nae_gpu.h: a NaN, +Inf or -Inf at sample i of one channel changes only the samples of that
+    channel inside [(b - Tn - 3) H, (b + Tn + 4) H), and the output is non-finite exactly inside [(b - 3) H, (b + 4) H): a clean frame sees at
+    most four non-finite keys in its window of 2 Tn + 1, never a majority, and such a key ranks above every finite one whatever its sign and
+    payload (the statement's are 0x7FC0 and 0xFFC0 both).  For Tn > 0 the change does reach past the non-finite blocks."""
+    H = n_fft // 4
+    i = 14 * H + 5
+    x = hpss_ref.wander(np.random.default_rng(n_fft + tn), 1, 30 * H + 40, 2, period=3.0 * n_fft)[0]
+    p = hpss_ref.params(n_fft, tn, 8, int(mask == "hard"), 1.0, 0.0)
+    clean = hpss_ref.run(ref, p, x)
+    (lo, hi), (nlo, nhi) = reach(n_fft, tn, i)
+    assert 0 < lo and hi < len(x)
+    signs = set()
+    for bad in BAD:
+        dirty = x.copy()
+        dirty[i, 1] = bad
+        y, q, _, _, _ = hpss_ref.run(ref, p, dirty, detail=True)
+        changed = np.flatnonzero(bits(y[:, 1]) != bits(clean[:, 1]))
+        wild = np.flatnonzero(~np.isfinite(y[:, 1]))
+        print(f"n_fft {n_fft}, Tn {tn}, {mask}, {bad}: changed {changed.min()} ... {changed.max()} inside {lo} ... {hi - 1}; non-finite {wild.min()} ... {wild.max()}")
+        assert lo <= changed.min() and changed.max() < hi, "only the reach changes"
+        assert np.array_equal(wild, np.arange(nlo, nhi)), "non-finite exactly in the blocks the four frames feed"
+        assert np.array_equal(bits(y[:, 0]), bits(clean[:, 0])), "the other channel"
+        assert (changed.min() < nlo and changed.max() >= nhi) == (tn > 0), "with Tn > 0 the medians of clean frames change too"
+        keys = q[1, i // H:i // H + 4]
+        assert np.all((keys & 0x7FFF) >= 0x7F80), "every key of the four frames is non-finite"
+        signs |= {int(k) >> 15 for k in np.unique(keys)}
+    assert signs == {0, 1}, "the statement's NaN keys carry both signs: 0x7FC0 and 0xFFC0"
+
+
+# ---------------------------------------------------------------------------------------------------- subnormal powers
+QUIET = 2.0 ** -66
+
+
+def quiet(n_fft, ch, scale=QUIET):
+    """wandering noise of 20 blocks and a rest around 1e-20: every sample a normal f32, the powers of its bins around 1e-39, where a key is
+    the upper half of a subnormal -> x[1, n, ch]"""
+    H = n_fft // 4
+    x = hpss_ref.wander(np.random.default_rng(66 + n_fft + ch), 1, 20 * H + 7, ch, period=3.0 * n_fft)
+    return (x * np.float32(scale)).astype(np.float32)
+
+
+def quiet_shares(ref, n_fft, scale=QUIET):
+    """over the mono and the stereo signal of quiet(): (share of subnormal keys, share of zero keys, share of bins with Hq >= Pq) among the
+    frames that lie wholly inside the signal (3 ... 19), and whether any output sample is not zero"""
+    sub = zero = harm = total = 0
+    some = False
+    for ch in (1, 2):
+        y, q, hq, pq, _ = hpss_ref.run(ref, hpss_ref.params(n_fft, 8, 8, 0, 1.0, 0.0), quiet(n_fft, ch, scale)[0], detail=True)
+        q, hq, pq = q[:, 3:20], hq[:, 3:20], pq[:, 3:20]
+        sub += int(((q >= 0x0001) & (q <= 0x007F)).sum())
+        zero += int((q == 0).sum())
+        harm += int((hq >= pq).sum())
+        total += q.size
+        some = some or bool(np.any(y))
+    return sub / total, zero / total, harm / total, some
+
+
+@pytest.mark.parametrize("n_fft", hpss_ref.SIZES)
+def test_subnormal_powers(ref, n_fft):
+    """the signal of tests/test_gpu_hpss.py::test_subnormal_powers puts the keys on the subnormal grid: between 20 % and 80 % of the keys of
+    the frames inside the signal are subnormal (0x0001 ... 0x007F), at most 10 % are zero, each median wins at between 20 % and 80 % of the
+    bins and the output is not zero.  Measured (subnormal / zero / Hq >= Pq): 47.6 / 3.2 / 36.6 % at 512, 42.4 / 1.6 / 38.6 % at 1024,
+    35.3 / 0.9 / 38.4 % at 2048, 37.2 / 0.6 / 46.3 % at 4096.  Four times louder (2^-64) too few keys are subnormal at every size
+    (17.2 / 10.9 / 6.3 / 4.5 %), four times quieter (2^-68) too many are zero up to 2048 (25.7 / 18.3 / 11.2 %; 8.6 % at 4096)."""
+    sub, zero, harm, some = quiet_shares(ref, n_fft)
+    print(f"subnormal powers, n_fft {n_fft}: {100 * sub:.1f} % of the keys subnormal, {100 * zero:.1f} % zero, Hq >= Pq at {100 * harm:.1f} % of the bins")
+    assert 0.2 <= sub <= 0.8 and zero <= 0.1 and 0.2 <= harm <= 0.8 and some
+    assert np.all(np.abs(quiet(n_fft, 2)[quiet(n_fft, 2) != 0]) >= np.finfo(np.float32).tiny), "the samples themselves are normal"

@@ -3,7 +3,8 @@
 (tests/hpss_ref/ref_hpss.c), bit for bit.  A case draws the frame size, the two spans over 0 ... 8 (their edges more often), the mask, two
 levels over the whole range the header states (-120 dB, gain 0, more often), a length from the hop's edges or a uniform one, a forced tile or
 the library's, a signal of wandering noise with clicks and a tone in it, the channel and stream counts, a view with gaps or a shared source
-and, for one case in three, the handle with random put sizes from the host and the device in turn.  draw() needs no device.
+and, for one case in three, the handle with random put sizes from the host and the device in turn.  draw() needs no device;
+tests/test_hpss_cpu.py pins, without a GPU, which edges SEEDED reaches.
     python tests/tools/fuzz_hpss.py [cases=60] [seed=1]"""
 import os
 import sys
@@ -17,6 +18,8 @@ import hpss_ref
 from block_gpu import CONFIGS, mismatch, statement
 from fuzz_effects import pick
 from hpss_gpu import gpu_hpss, hpss_stream
+
+SEEDED = (24, 7)                                                 # what tests/test_gpu_hpss.py runs: cases, seed
 
 
 def draw(cases, seed):
