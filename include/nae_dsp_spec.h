@@ -114,6 +114,20 @@
 #define NAE_LIM_MIN_CEILING_DB (-20.0)
 #define NAE_LIM_MAX_CEILING_DB 0.0
 #define NAE_LIM_MAX_GAIN_DB 24.0
+/* K23 dither ("K23 dither"): requantisation to NAE_DITHER_MIN_BITS ... NAE_DITHER_MAX_BITS bits with dither of one of four kinds
+ * and an error feedback of at most NAE_DITHER_MAX_TAPS taps whose absolute sum is at most NAE_DITHER_MAX_TAP_SUM. */
+#define NAE_DITHER_MIN_BITS 8
+#define NAE_DITHER_MAX_BITS 24
+#define NAE_DITHER_MAX_TAPS 12
+#define NAE_DITHER_MAX_TAP_SUM 64.0
+#define NAE_DITHER_NONE 0
+#define NAE_DITHER_RECTANGULAR 1
+#define NAE_DITHER_TRIANGULAR 2
+#define NAE_DITHER_HIGHPASS 3
+#define NAE_DITHER_SHAPE_NONE 0
+#define NAE_DITHER_SHAPE_FIRST 1
+#define NAE_DITHER_SHAPE_SECOND 2
+#define NAE_DITHER_SHAPE_LIPSHITZ 3
 /* K20 multiband ("K20 multiband"): a Linkwitz-Riley crossover tree of K11 sections into 2 ... NAE_MB_MAX_BANDS bands, K12 on every
  * band, and the bands' sum.  The tree of B bands has 4, 9 or 14 sections in fixed slots: at most NAE_MB_MAX_SECTIONS, inside K11's constant
  * block of NAE_EQ_MAX_SECTIONS */

@@ -59,7 +59,9 @@ extern "C" {
  *   downward expander, K19; nae_mb_design, nae_mb_block_f32 and the nae_mb handle (the same eight entries) with the record nae_mb_params:
  *   the multiband compressor, K20; nae_hpss_design, nae_hpss_block_f32 and the nae_hpss handle (the same eight entries) with the record
  *   nae_hpss_params: the harmonic/percussive separation, K21; nae_lim_design, nae_lim_block_f32 and the nae_lim handle (the same eight
- *   entries) with the record nae_lim_params: the true-peak look-ahead limiter, K22. */
+ *   entries) with the record nae_lim_params: the true-peak look-ahead limiter, K22; nae_dither_design, nae_dither_block_f32 and the
+ *   nae_dither handle (the same eight entries) with the record nae_dither_params: word-length reduction with dither and noise shaping,
+ *   K23. */
 #define NAE_ABI_VERSION 3
 
 typedef enum nae_status {
@@ -94,6 +96,7 @@ typedef struct nae_mb nae_mb;
 typedef struct nae_denoise nae_denoise;
 typedef struct nae_hpss nae_hpss;
 typedef struct nae_lim nae_lim;
+typedef struct nae_dither nae_dither;
 typedef struct nae_loud nae_loud;
 
 /* ------------------------------------------------------------------ context / plumbing */
@@ -178,6 +181,8 @@ int nae_debug_clock_ghz(nae_ctx* ctx, double* ghz);
  *                   partition count is used); a handle reads it when it is created.  Neither changes a result
  *   dn_tile         hop blocks (of n_fft / 4 samples) one wave of the spectral gate walks (0: nae_pick_denoise_tile); every tiling gives the same bits
  *   hpss_tile       hop blocks (of n_fft / 4 samples) one wave of the separation walks (0: nae_pick_hpss_tile); every tiling gives the same bits
+ *   dither_roles    who does the feed-forward work of the dither's error-feedback kernel: 1 the four producer waves of the workgroup, 2 the walking
+ *                   wave itself (0: the library's choice, 1); every value gives the same bits
  *   echo_group      streams per launch of nae_echo_block_f32 (0: as many as keep the delay lines inside the 256 MiB workspace cap); every grouping
  *                   gives the same bits
  *   mod_sub         samples one wave of the modulated delay computes in parallel, 1 ... 64 (0: 64 without feedback, else min(64, floor(delay -
@@ -1088,6 +1093,49 @@ int nae_lim_destroy(nae_lim* h);
  * above NAE_LIM_MAX_LOOKAHEAD samples at that rate.  No context, no device work. */
 int nae_lim_design(int sample_rate, double ceiling_db, double gain_db, double release_s, double lookahead_s, int true_peak, int link,
                    nae_lim_params* out);
+
+/* ------------------------------------------------------------------ K23 dither (word-length reduction: TPDF dither, noise-shaped requantisation)
+ * no reference code.  Spec ("K23 dither"): the f32 output lies on the grid of a `bits`-bit word, b = bits, S = 2^(b - 1).  Per
+ * stream-channel, sample index n >= 0, all in double; "fused" is one fma with one rounding, every other step one IEEE operation:
+ *   t[n] = (double)x[n] S                          one multiply, exact; a sample that is not finite counts as x[n] = 0
+ *   u[n] = t[n] - sum c_k e[n - k]                  K fused steps u = fma(-c_k, e[n - k], u) from k = K down to k = 1; e[m] = 0 for m < 0
+ *   q[n] = rint(u[n] + d[n])                        one add, one round to nearest, ties to even
+ *   e[n] = q[n] - u[n]                              one subtract: the dithered quantiser's whole error, taken before the clamp
+ *   y[n] = (float)(clamp(q[n], -S, S - 1) / S)      exact
+ * so y - x = (e * ntf) / S with NTF(z) = 1 - sum c_k z^-k.  Dither d[n] in LSB, a function of (seed, stream index in the call, channel, n):
+ * fin(z) is the splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31), G =
+ * 0x9E3779B97F4A7C15, all modulo 2^64; key = fin(fin(fin(seed + G) + stream) + channel); h[n] = fin(key + G n); r1[n] = (int32)(h >> 32) 2^-32,
+ * r2[n] = (int32)(h & 0xffffffff) 2^-32.  kind NAE_DITHER_NONE: d = 0; _RECTANGULAR: d = r1; _TRIANGULAR: d = r1 + r2; _HIGHPASS: d[n] = r1[n] -
+ * r1[n - 1], r1[-1] = 0.  A source with stream_stride 0 still gives every stream its own dither.  y S is an integer in [-S, S - 1]: any later
+ * conversion to an integer format of at least `bits` bits reproduces it exactly; integer output planes are not part of this entry.  The
+ * presets' curves are fixed in z: the `lipshitz` taps were designed for 44.1 kHz, and their curve moves with the sample rate.
+ * Bit-exact against the CPU statement (tests/dither_ref/ref_dither.c) under either value of the debug key dither_roles and any cut of the
+ * input into puts.  Errors: a null pointer, ch not 1 or 2, bits outside 8 ... 24, an unknown kind, n_taps outside 0 ... 12, a tap that is
+ * not finite, sum |c_k| above 64: NAE_ERR_INVALID; in_len = 0 or n_streams = 0: NAE_OK after the checks, nothing is launched.  Views as
+ * nae_dyn_block_f32's: stream_stride 0 on the source and dst->base == src->base are allowed. */
+typedef struct nae_dither_params {
+    int bits;                    /* word length, 8 ... 24 */
+    int kind;                    /* NAE_DITHER_NONE, _RECTANGULAR, _TRIANGULAR, _HIGHPASS (include/nae_dsp_spec.h) */
+    int n_taps;                  /* K, 0 ... 12 */
+    double taps[12];             /* c_1 ... c_K of NTF(z) = 1 - sum c_k z^-k */
+    unsigned long long seed;
+} nae_dither_params;
+int nae_dither_block_f32(nae_ctx* ctx, const nae_dither_params* params, const nae_sig* src, size_t in_len, int ch, size_t n_streams,
+                         const nae_sig* dst);
+/* Streaming handle on the shared device FIFO (channels = ch): no latency, every frame put is available after that put.  The handle is stream
+ * 0 of its call; the K errors per channel and the position n stay on the device and in the handle between launches, so any cut of the
+ * input gives the block call's bits for one stream.  A put after the flush: NAE_ERR_STATE. */
+int nae_dither_create(nae_ctx* ctx, const nae_dither_params* params, int channels, nae_dither** h);
+int nae_dither_put(nae_dither* h, const float* interleaved, size_t S);
+int nae_dither_put_host(nae_dither* h, const float* interleaved_host, size_t S);
+int nae_dither_flush(nae_dither* h);
+size_t nae_dither_available(nae_dither* h);
+int nae_dither_receive(nae_dither* h, float* dst, size_t max_frames, size_t* got);
+int nae_dither_receive_host(nae_dither* h, float* dst_host, size_t max_frames, size_t* got);
+int nae_dither_destroy(nae_dither* h);
+/* The record on the host: shaping NAE_DITHER_SHAPE_NONE (no taps), _FIRST {1}, _SECOND {2, -1}, _LIPSHITZ {2.033, -2.165, 1.959, -1.590,
+ * 0.6149}.  NAE_ERR_INVALID: a null pointer, bits outside 8 ... 24, an unknown kind or preset.  No context, no device work. */
+int nae_dither_design(int bits, int kind, int shaping, unsigned long long seed, nae_dither_params* out);
 
 /* ------------------------------------------------------------------ K14 loudness
  * no reference code.  Spec ("K14 loudness"): the programme loudness of ITU-R BS.1770-4 / EBU R 128 with the true peak, and the one

@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = [
     "nae_hpss_receive", "nae_hpss_receive_host", "nae_hpss_destroy",
     "nae_lim_design", "nae_lim_block_f32", "nae_lim_create", "nae_lim_put", "nae_lim_put_host", "nae_lim_flush", "nae_lim_available",
     "nae_lim_receive", "nae_lim_receive_host", "nae_lim_destroy",
+    "nae_dither_design", "nae_dither_block_f32", "nae_dither_create", "nae_dither_put", "nae_dither_put_host", "nae_dither_flush",
+    "nae_dither_available", "nae_dither_receive", "nae_dither_receive_host", "nae_dither_destroy",
     "nae_loud_design", "nae_loud_lufs", "nae_loud_measure_f32", "nae_loud_apply_f32", "nae_loud_normalize_f32", "nae_loud_create", "nae_loud_put",
     "nae_loud_put_host", "nae_loud_flush", "nae_loud_get_result", "nae_loud_destroy",
 ]
@@ -84,7 +86,10 @@ MB_MAX_BANDS, MB_MAX_SECTIONS = 4, 14               # NAE_MB_MAX_BANDS, NAE_MB_M
 HPSS_MAX_SPAN = 8                                   # NAE_HPSS_MAX_SPAN (include/nae_dsp_spec.h)
 HPSS_MASKS = ("soft", "hard")                       # `hard` of nae_hpss_design: 0, 1
 LIM_MAX_LOOKAHEAD, LIM_TP_REACH = 1018, 6           # NAE_LIM_MAX_LOOKAHEAD, NAE_LIM_TP_REACH (include/nae_dsp_spec.h)
-HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat", "nae_gate", "nae_mb", "nae_hpss", "nae_lim")   # the handles with the full put / receive set of entries
+DITHER_MIN_BITS, DITHER_MAX_BITS, DITHER_MAX_TAPS = 8, 24, 12   # NAE_DITHER_MIN_BITS, NAE_DITHER_MAX_BITS, NAE_DITHER_MAX_TAPS (include/nae_dsp_spec.h)
+DITHER_KINDS = ("none", "rectangular", "triangular", "highpass")   # `kind` of nae_dither_params: NAE_DITHER_NONE ... NAE_DITHER_HIGHPASS
+DITHER_SHAPINGS = ("none", "first", "second", "lipshitz")          # `shaping` of nae_dither_design: NAE_DITHER_SHAPE_NONE ... _LIPSHITZ
+HANDLE_PREFIXES = ("nae_stretch", "nae_wsola", "nae_fir", "nae_conv", "nae_eq", "nae_dyn", "nae_dynkey", "nae_denoise", "nae_echo", "nae_mod", "nae_sat", "nae_gate", "nae_mb", "nae_hpss", "nae_lim", "nae_dither")   # the handles with the full put / receive set of entries
 
 
 class NaeError(RuntimeError):
@@ -251,6 +256,12 @@ class LimParams(C.Structure):
                 ("true_peak", C.c_int), ("link", C.c_int)]
 
 
+class DitherParams(C.Structure):
+    """nae_dither_params: the dither's parameters (include/nae_gpu.h): the word length, the dither's kind, the error feedback's taps c_1 ... c_K
+    and the seed; nae_dither_design makes them from a preset's name"""
+    _fields_ = [("bits", C.c_int), ("kind", C.c_int), ("n_taps", C.c_int), ("taps", C.c_double * 12), ("seed", C.c_uint64)]
+
+
 class HpssParams(C.Structure):
     """nae_hpss_params: the separation's parameters (include/nae_gpu.h); nae_hpss_design makes them from decibels"""
     _fields_ = [("n_fft", C.c_int), ("time_span", C.c_int), ("freq_span", C.c_int), ("hard", C.c_int), ("gain_h", C.c_float), ("gain_p", C.c_float)]
@@ -390,6 +401,8 @@ def load_library() -> C.CDLL:
         "nae_denoise_create": (i, [vp, P(DenoiseParams), vp, i, i, P(vp)]),
         "nae_lim_design": (i, [i, d, d, d, d, i, i, P(LimParams)]),
         "nae_lim_block_f32": (i, [vp, P(LimParams), P(Sig), sz, i, sz, P(Sig)]), "nae_lim_create": (i, [vp, P(LimParams), i, P(vp)]),
+        "nae_dither_design": (i, [i, i, i, C.c_uint64, P(DitherParams)]),
+        "nae_dither_block_f32": (i, [vp, P(DitherParams), P(Sig), sz, i, sz, P(Sig)]), "nae_dither_create": (i, [vp, P(DitherParams), i, P(vp)]),
         "nae_hpss_design": (i, [d, d, i, i, i, i, P(HpssParams)]),
         "nae_hpss_block_f32": (i, [vp, P(HpssParams), P(Sig), sz, i, sz, P(Sig)]), "nae_hpss_create": (i, [vp, P(HpssParams), i, P(vp)]),
         "nae_loud_design": (i, [i, d, d, d, P(LoudParams)]), "nae_loud_lufs": (d, [d]),
@@ -967,6 +980,22 @@ class Context:
         """the limiter `params` over every stream (nae_lim_block_f32); dst receives in_len frames, compensated for the look-ahead"""
         self._ck(self.lib.nae_lim_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
 
+    # -- K23
+    @staticmethod
+    def dither_design(bits: int = 16, kind: str = "triangular", shaping: str = "none", seed: int = 1) -> "DitherParams":
+        """the dither's parameters from the names of the kind and of the shaping preset (nae_dither_design)"""
+        if kind not in DITHER_KINDS or shaping not in DITHER_SHAPINGS:
+            raise NaeError(f"dither_design: kind {kind!r} or shaping {shaping!r} is not a name of DITHER_KINDS / DITHER_SHAPINGS")
+        out = DitherParams()
+        rc = load_library().nae_dither_design(bits, DITHER_KINDS.index(kind), DITHER_SHAPINGS.index(shaping), seed, C.byref(out))
+        if rc:
+            raise NaeError(f"nae_dither_design({bits}, {kind}, {shaping}, {seed}) failed: {rc}")
+        return out
+
+    def dither_block(self, params: "DitherParams", src: Sig, in_len: int, ch: int, n_streams: int, dst: Sig):
+        """the dither `params` over every stream (nae_dither_block_f32); dst receives in_len frames on the grid of params.bits bits"""
+        self._ck(self.lib.nae_dither_block_f32(self.h, C.byref(params), C.byref(src), in_len, ch, n_streams, C.byref(dst)))
+
     def denoise_profile(self, n_fft: int, src: Sig, length: int, ch: int, profile_ptr: int):
         """the noise powers [ch][n_fft / 2 + 1] of the excerpt's whole frames into device memory at profile_ptr (asynchronous)"""
         self._ck(self.lib.nae_denoise_profile_f32(self.h, n_fft, C.byref(src), length, ch, profile_ptr))
@@ -1223,6 +1252,20 @@ class Limiter(_Handle):
     def __init__(self, ctx: Context, params: LimParams, channels: int):
         super().__init__(ctx, channels)
         ctx._ck(ctx.lib.nae_lim_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+
+class Dither(_Handle):
+    """The dither's streaming handle (nae_dither_create): put interleaved f32, flush, receive.  No latency: every frame put is available
+    after that put."""
+
+    _prefix = "nae_dither"
+
+    def __init__(self, ctx: Context, params: DitherParams, channels: int):
+        super().__init__(ctx, channels)
+        ctx._ck(ctx.lib.nae_dither_create(ctx.h, C.byref(params), channels, C.byref(self.h)))
+
+
+dither_design = Context.dither_design
 
 
 class Hpss(_Handle):

@@ -233,6 +233,7 @@ int nae_debug_set(nae_ctx* ctx, const char* key, long long value)
     else if (k == "hpss_tile" && count) ctx->hpss_tile = (int)value;
     else if (k == "conv_tile" && count) ctx->conv_tile = (int)value;
     else if (k == "conv_ring" && count) ctx->conv_ring = (int)value;
+    else if (k == "dither_roles" && one_of({0, 1, 2})) ctx->dither_roles = (int)value;
     else if (k == "echo_group" && count) ctx->echo_group = (int)value;
     else if (k == "mod_sub" && value >= 0 && value <= 64) ctx->mod_sub = (int)value;
     else if (k == "sat_tile" && count) ctx->sat_tile = (int)value;

@@ -46,6 +46,7 @@ struct nae_ctx {
     CtxConst loud_block;         // the loudness entries' constant block of the last call's K-weighting (kernels_loud.hip)
     CtxBuf ws_loud;              // their workspace: states, sub-block energies, records
     CtxBuf ws_echo;              // nae_echo_block_f32's delay lines, one ring per stream-channel of a launch group (kernels_echo.hip)
+    int dither_roles = 0;        // who does the dither's feed-forward work: 0 / 1 the producer waves, 2 the walking wave (kernels_dither.hip)
     int echo_group = 0;          // streams per launch of the echo's block call; 0 = from NAE_CONV_WS_BYTES
     int mod_sub = 0;             // samples a wave of the modulated delay computes in parallel, 1 ... 64; 0 = the rule of kernels_mod.hip
     int sat_tile = 0;            // chunks per wave of the saturation; 0 = choose per launch (nae_pick_sat_tile)
@@ -408,6 +409,14 @@ size_t nae_lim_state_words();
 size_t nae_lim_wait(const nae_lim_params* p);
 int nae_launch_lim(nae_ctx* ctx, const nae_lim_params* p, const nae_sig* src, size_t in_len, int ch, size_t n_streams, const nae_sig* dst,
                    size_t c_origin, size_t c_stop, unsigned long long* d_state);
+
+// kernels_dither.hip: the dither ("K23 dither").  nae_dither_check: the parameter rules of the block call and the handle.
+// nae_launch_dither computes frames [first, stop) of absolutely indexed signals, frame i being sample n = i of its stream; d_state,
+// NAE_DITHER_MAX_TAPS doubles per stream-channel, holds the errors e[first - 1], e[first - 2], ... on entry and those in front of `stop` on
+// return; null: the start of a stream (nothing kept).  Without taps it is not read.
+int nae_dither_check(nae_ctx* ctx, const nae_dither_params* p, int ch);
+int nae_launch_dither(nae_ctx* ctx, const nae_dither_params* p, const nae_sig* src, int ch, size_t n_streams, const nae_sig* dst, size_t first,
+                      size_t stop, double* d_state);
 
 // kernels_loud.hip: the loudness meter ("K14 loudness").  nae_loud_check: the parameter rules of the block entries and the handle.  A
 // constant block holds nae_loud_block_bytes() bytes: K11's block of the two K-weighting sections, then the true-peak taps (nae_loud_make_block,

@@ -150,6 +150,14 @@ struct nae_lim : BlockHandle {
     int process() override;
 };
 
+// the dither's handle ("K23 dither"): a unit is one frame and nothing is waited for or kept, so every put is computed at once
+// from the position it reached; the K errors per channel stay on the device between two launches
+struct nae_dither : BlockHandle {
+    nae_dither_params params;
+    double* d_state = nullptr;  // [channel][NAE_DITHER_MAX_TAPS]: e[n - 1], e[n - 2], ... in front of the next frame
+    int process() override;
+};
+
 // the loudness meter's handle ("K14 loudness"): whole chunks of NAE_EQ_CHUNK samples are measured as they fill and leave the FIFO
 // (the state carries the 11 samples the true peak reads in front of a chunk); the sub-block energies grow on the device; the flush measures the
 // rest and runs the gates.  Nothing comes out of it but the record.
@@ -441,6 +449,13 @@ int nae_lim::process()
 {
     return run_units(NAE_DYN_CHUNK, nae_lim_wait(&params), 1, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
         return nae_launch_lim(ctx, &params, &src, in.total, ch, 1, &dst, from, to, d_state);
+    });
+}
+
+int nae_dither::process()
+{
+    return run_units(1, 0, 0, [&](const nae_sig& src, const nae_sig& dst, size_t from, size_t to) {
+        return nae_launch_dither(ctx, &params, &src, ch, 1, &dst, from, to, d_state);
     });
 }
 
@@ -953,6 +968,33 @@ size_t nae_lim_available(nae_lim* h) { return handle_available(h); }
 int nae_lim_receive(nae_lim* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
 int nae_lim_receive_host(nae_lim* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
 int nae_lim_destroy(nae_lim* h) { return handle_destroy(h); }
+
+// ------------------------------------------------------------------------------------------------ dither
+int nae_dither_create(nae_ctx* ctx, const nae_dither_params* params, int channels, nae_dither** h)
+{
+    if (!ctx || !h) return NAE_ERR_INVALID;
+    *h = nullptr;
+    int rc = nae_dither_check(ctx, params, channels);
+    if (rc) return rc;
+    (void)nae_use_device(ctx);
+    nae_dither* s = handle_new<nae_dither>(ctx, channels);
+    if (!s) return NAE_ERR_NOMEM;
+    s->params = *params;
+    // in front of sample 0 every error is zero
+    const size_t words = (size_t)channels * NAE_DITHER_MAX_TAPS;
+    rc = s->dev_alloc(&s->d_state, words, "hipMalloc(dither state)");
+    if (!rc) rc = nae_check(ctx, hipMemsetAsync(s->d_state, 0, words * sizeof(double), ctx->stream), "hipMemsetAsync(dither state)");
+    return handle_created(s, rc, h);
+}
+
+int nae_dither_put(nae_dither* h, const float* interleaved, size_t S) { return handle_append(h, interleaved, S, false); }
+int nae_dither_put_host(nae_dither* h, const float* interleaved_host, size_t S) { return handle_append(h, interleaved_host, S, true); }
+// flush: nothing was held back; from here on a put is refused
+int nae_dither_flush(nae_dither* h) { return handle_flush(h); }
+size_t nae_dither_available(nae_dither* h) { return handle_available(h); }
+int nae_dither_receive(nae_dither* h, float* dst, size_t max_frames, size_t* got) { return handle_take(h, dst, max_frames, got, false); }
+int nae_dither_receive_host(nae_dither* h, float* dst_host, size_t max_frames, size_t* got) { return handle_take(h, dst_host, max_frames, got, true); }
+int nae_dither_destroy(nae_dither* h) { return handle_destroy(h); }
 
 // ------------------------------------------------------------------------------------------------ loudness
 int nae_loud_create(nae_ctx* ctx, const nae_loud_params* params, int channels, nae_loud** h)

@@ -1,6 +1,6 @@
 // stream_util.h — grow-only device buffers, the absolutely indexed device FIFO of the streaming handles, and the handles' shared core: what
 // a handle is (StreamHandle, BlockHandle) and its put / flush / available / receive / destroy (not installed).  Every handle of the library
-// stands on it: the fifteen of nae_stream.hip, nae_wsola (nae_wsola.hip) and nae_swr (nae_swr.hip, whose convert entries feed and empty the
+// stands on it: the sixteen of nae_stream.hip, nae_wsola (nae_wsola.hip) and nae_swr (nae_swr.hip, whose convert entries feed and empty the
 // FIFOs themselves)
 #pragma once
 #include "nae_internal.h"

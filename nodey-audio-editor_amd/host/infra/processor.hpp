@@ -173,4 +173,6 @@ namespace infra
 	void register_separation_processors();
 	// the true-peak limiter (audio_limiter): called after the fourteen above, each of which stays the list it was
 	void register_limiter_processors();
+	// the dither (audio_dither): called after the fifteen above, each of which stays the list it was
+	void register_dither_processors();
 }

@@ -1,5 +1,5 @@
 // processor/audio-effects.cpp — the nodes on a block streaming handle: Audio_filter (nae_fir), Audio_reverb (nae_conv), Audio_eq (nae_eq),
-// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat), Audio_gate (nae_gate), Audio_multiband (nae_mb), Audio_denoise (nae_denoise), Audio_separation (nae_hpss) and Audio_limiter (nae_lim), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
+// Audio_dynamics (nae_dyn), Audio_sidechain (nae_dynkey, two input pins and a loop of its own), Audio_echo (nae_echo), Audio_modulation (nae_mod), Audio_saturation (nae_sat), Audio_gate (nae_gate), Audio_multiband (nae_mb), Audio_denoise (nae_denoise), Audio_separation (nae_hpss), Audio_limiter (nae_lim) and Audio_dither (nae_dither), and the one loop that feeds such a handle and delivers its frames (run_on_handle);
 // and Audio_loudness (nae_loud), whose handle measures and hands out no samples: the node holds them and applies the one gain at the end.
 // Both loops stand on node-util.hpp's two ends, take_in and cut_and_push; what is written here is what lies between them.
 // A node's parameters are stated once: the members and their defaults in the settings record of audio-<node>.hpp, and here, in front of the
@@ -16,6 +16,7 @@
 #include "audio-saturation.hpp"
 #include "audio-gate.hpp"
 #include "audio-limiter.hpp"
+#include "audio-dither.hpp"
 #include "audio-multiband.hpp"
 #include "audio-denoise.hpp"
 #include "audio-separation.hpp"
@@ -1187,6 +1188,114 @@ namespace processor
 				nae_lim* lim = nullptr;
 				gpu::check(nae_lim_create(ctx, &params, ch, &lim), "nae_lim_create");
 				return lim;
+			}
+		);
+	}
+
+	// ------------------------------------------------------------------------------------------ Audio_dither
+	infra::Processor::Info Audio_dither::get_processor_info()
+	{
+		return {"audio_dither", "Audio Dither", false, [] { return std::unique_ptr<infra::Processor>(new Audio_dither); },
+				"Word-length reduction: TPDF dither and noise-shaped requantisation to 8 ... 24 bits (MI355X)"};
+	}
+
+	std::vector<infra::Processor::Pin_attribute> Audio_dither::get_pin_attributes() const { return io_pins(); }
+
+	namespace
+	{
+		// the library's kind of each name, in the enumerators' order (the default first)
+		const char* const dither_kind_names[] = {"triangular", "none", "rectangular", "highpass"};
+		constexpr int dither_kinds[] = {NAE_DITHER_TRIANGULAR, NAE_DITHER_NONE, NAE_DITHER_RECTANGULAR, NAE_DITHER_HIGHPASS};
+		const char* const dither_shaping_names[] = {"none", "first", "second", "lipshitz"};
+
+		// 1 ... NAE_DITHER_MAX_TAPS finite numbers whose absolute sum is at most NAE_DITHER_MAX_TAP_SUM; no key is no taps, and no taps are not written;
+		// not clamped
+		struct Dither_taps
+		{
+			const char* key;
+
+			void write(const Dither_settings& r, Json::Value& value) const
+			{
+				if (r.taps.empty()) return;
+				Json::Value a(Json::arrayValue);
+				for (double c : r.taps) a.append(c);
+				value[key] = a;
+			}
+			void read(Dither_settings& r, const Json::Value& value, const char* node_name) const
+			{
+				r.taps.clear();
+				if (!value.isMember(key)) return;
+				const Json::Value& a = value[key];
+				if (!a.isArray() || a.size() < 1 || a.size() > NAE_DITHER_MAX_TAPS) throw wrong_field(node_name, key);
+				double sum = 0;
+				const int n = (int)a.size();
+				for (int k = 0; k < n; k++)
+				{
+					if (!a[k].isDouble() || !std::isfinite(a[k].asDouble())) throw wrong_field(node_name, key);
+					sum += std::fabs(a[k].asDouble());
+				}
+				if (!(sum <= NAE_DITHER_MAX_TAP_SUM)) throw wrong_field(node_name, key);
+				for (int k = 0; k < n; k++) r.taps.push_back(a[k].asDouble());
+			}
+			void keep(Dither_settings&) const {}
+		};
+		// an exact integer below 2^53, written as a double; not clamped
+		struct Dither_seed
+		{
+			const char* key;
+
+			void write(const Dither_settings& r, Json::Value& value) const { if (r.seed != Dither_settings::default_seed) value[key] = (double)r.seed; }
+			void read(Dither_settings& r, const Json::Value& value, const char* node_name) const
+			{
+				r.seed = Dither_settings::default_seed;
+				if (!value.isMember(key)) return;
+				// compared as a double with the range first: a number outside the integer range is never converted
+				const Json::Value& v = value[key];
+				if (!v.isDouble() || !(v.asDouble() >= 0.0 && v.asDouble() < 9007199254740992.0) || v.asDouble() != (double)(uint64_t)v.asDouble()) throw wrong_field(node_name, key);
+				r.seed = (uint64_t)v.asDouble();
+			}
+			void keep(Dither_settings&) const {}
+		};
+		constexpr std::tuple dither_fields{
+			Number{"bits", &Dither_settings::bits, Dither_settings::default_bits, NAE_DITHER_MIN_BITS, NAE_DITHER_MAX_BITS},
+			Choice{"dither", &Dither_settings::dither, dither_kind_names},
+			Choice{"shaping", &Dither_settings::shaping, dither_shaping_names},
+			Dither_taps{"taps"},
+			Dither_seed{"seed"},
+		};
+	}
+
+	Json::Value Audio_dither::serialize() const { return to_json(*this, dither_fields); }
+	void Audio_dither::deserialize(const Json::Value& value) { Dither_settings::operator=(from_json<Dither_settings>(value, "Audio_dither", dither_fields)); }
+	void Dither_settings::clamp() { detail::clamp(*this, dither_fields); }
+
+	void Audio_dither::process_payload(
+		const std::map<std::string, std::shared_ptr<infra::Processor::Product>>& input,
+		const std::map<std::string, std::set<std::shared_ptr<infra::Processor::Product>>>& output,
+		const std::atomic<bool>& stop_token, std::any&
+	)
+	{
+		gpu::Node node;  // first local, destroyed last (gpu-context.hpp)
+		const Node_streams io = node_streams(input, output, "Audio Dither");
+		run_on_handle<nae_dither>(
+			io.input, io.output, stop_token, {"nae_dither", nae_dither_put, nae_dither_flush, nae_dither_available, nae_dither_receive, nae_dither_destroy},
+			"node", 0,
+			[&](nae_ctx* ctx, const Frame_data*, int ch)
+			{
+				// the preset's record, then the taps of the node's own where it has them: no sample rate enters
+				nae_dither_params params;
+				const int rc = nae_dither_design(bits, dither_kinds[(size_t)dither], (int)shaping, seed, &params);
+				if (rc != NAE_OK)
+					throw infra::Processor::Runtime_error("Invalid dither parameters", "A parameter of the dither node lies outside its range.",
+										infra::fmt("nae_dither_design: code %d", rc));
+				if (!taps.empty())
+				{
+					params.n_taps = (int)taps.size();
+					for (size_t k = 0; k < taps.size(); k++) params.taps[k] = taps[k];
+				}
+				nae_dither* d = nullptr;
+				gpu::check(nae_dither_create(ctx, &params, ch, &d), "nae_dither_create");
+				return d;
 			}
 		);
 	}

@@ -23,6 +23,7 @@
 #include "audio-saturation.hpp"
 #include "audio-gate.hpp"
 #include "audio-limiter.hpp"
+#include "audio-dither.hpp"
 #include "audio-multiband.hpp"
 #include "audio-denoise.hpp"
 #include "audio-separation.hpp"
@@ -140,6 +141,8 @@ namespace processor
 	bool Audio_separation::draw_content(bool) { clamp(); return false; }   // a frame size the library has, else the default
 	void Audio_limiter::draw_title() {}
 	bool Audio_limiter::draw_content(bool) { clamp(); return false; }
+	void Audio_dither::draw_title() {}
+	bool Audio_dither::draw_content(bool) { clamp(); return false; }   // the word length in range; names, taps and seed are not clamped
 
 	void Audio_loudness::draw_title() {}
 	bool Audio_loudness::draw_content(bool) { clamp(); return false; }

@@ -17,6 +17,7 @@
 #include "processor/audio-multiband.hpp"
 #include "processor/audio-separation.hpp"
 #include "processor/audio-limiter.hpp"
+#include "processor/audio-dither.hpp"
 #include "processor/audio-mix.hpp"
 #include "processor/audio-velocity.hpp"
 #include "processor/audio-vol.hpp"
@@ -83,4 +84,7 @@ namespace infra
 
 	// the true-peak limiter; a call of its own, so the fourteen lists above stay what they were
 	void register_limiter_processors() { register_each<processor::Audio_limiter>(); }
+
+	// the dither; a call of its own, so the fifteen lists above stay what they were
+	void register_dither_processors() { register_each<processor::Audio_dither>(); }
 }
